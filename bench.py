@@ -17,6 +17,12 @@ non-headline line): CoOp 16-shot prompts (n_ctx 16, 500 classes), DAC per-class 
 features, TempScaling scalar; reported with the text features cached and with the text tower re-run every batch (the
 reference's behaviour, trainers/classification/coop.py:208-210).
 Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line (`value`, `ms_per_step`, ECE / accuracy of those steps).  Everything
+else it can measure or check -- the sustained loop and power, the class-rows-only step (`value_cls_only`), the per-kernel roofline and
+ceilings, the other BASELINE configs, the tail timing, the CPU oracle baseline and its parity, the text tower re-timed, the CoOp per-batch
+schedule -- runs only with `--full`.  `--dump-outputs DIR` writes what the last timed step returned (logits, normalised image features,
+conf, pred) and the ECE bins / ECE / accuracy of the timed steps as DIR/<name>.npy (float32 / float64), so that two builds can be compared.
 """
 from __future__ import annotations
 
@@ -49,7 +55,7 @@ def parse():
     ap.add_argument("--workload", choices=("zeroshot", "coop_dac", "level1", "stream"), default="zeroshot",
                     help="zeroshot = the headline (BASELINE configs[1]); coop_dac = configs[2]; level1 = the reference caller's own statements "
                          "with only build_model swapped (INTEGRATION level 1); stream = host fp32 batches through runner.device_batches")
-    ap.add_argument("--sustained-seconds", type=float, default=3.2, help="length of the second, sustained timed loop (0 = skip)")
+    ap.add_argument("--sustained-seconds", type=float, default=3.2, help="--full: length of the second, sustained timed loop (0 = skip)")
     ap.add_argument("--batch", type=int, default=256, help="images per GPU per step")
     ap.add_argument("--classes", type=int, default=None, help="default: 1000 (zeroshot) / 500 (coop_dac)")
     ap.add_argument("--model", default="ViT-B/16")
@@ -61,9 +67,14 @@ def parse():
                     help="N = 1 only: process the image shards of this many ranks in ONE process (batch = ranks x --batch); with "
                          "--exchange-f16 the outputs equal rank 0's of the real N-process run bit for bit (self-test aid)")
     ap.add_argument("--dump", default=None, help="rank 0: save logits / conf / pred / ECE bins of the last step to this .npz")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true", help="skip the per-kernel profile (functional multi-rank self-tests)")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the per-GPU shapes of BASELINE configs[2] / [3] / [4] (other_configs)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0: write the outputs of the last timed step (and the ECE bins of the timed steps) to DIR/<name>.npy, float32 / float64")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement and check beyond the headline: sustained loop + power, value_cls_only, roofline / ceiling / "
+                         "other_configs / tail, CPU baseline + parity, text tower re-timed, CoOp per-batch schedule (off: setup, warm-up, timed steps only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU oracle baseline and its parity")
+    ap.add_argument("--no-roofline", action="store_true", help="--full: skip the per-kernel profile (functional multi-rank self-tests)")
+    ap.add_argument("--no-other-configs", action="store_true", help="--full: skip the per-GPU shapes of BASELINE configs[2] / [3] / [4] (other_configs)")
     ap.add_argument("--cpu-batch", type=int, default=32)
     ap.add_argument("--cpu-classes", type=int, default=100, help="BASELINE configs[0]: Caltech101-sized prompt set")
     ap.add_argument("--cpu-seconds", type=float, default=20.0)
@@ -122,6 +133,32 @@ def timed_ms(fn, iters):
     e1.record()
     torch.cuda.synchronize()
     return e0.elapsed_time(e1) / iters
+
+
+DUMP_OUTPUTS_MAX_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(out_dir, last, bins, res):
+    """--dump-outputs: what the timed path handed its caller in the LAST timed step -- fused_tail's (logits, normalised image features,
+    conf, pred) -- and what the evaluator holds after the timed steps (ECE bins, ECE and accuracy in percent), one DIR/<name>.npy each,
+    float32 as computed or float64 (pred, the bins and the metrics; exact).  Over 64 MB in all, the per-row arrays keep a fixed seeded
+    sample of rows, the same rows in each, and `rows` names them."""
+    logits, feats, conf, pred = last
+    arrays = {"logits": logits.float().cpu().numpy(), "image_features": feats.float().cpu().numpy(),
+              "conf": conf.float().cpu().numpy(), "pred": pred.cpu().numpy().astype(np.float64)}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_OUTPUTS_MAX_BYTES:
+        n = logits.shape[0]
+        k = max(1, int(n * (DUMP_OUTPUTS_MAX_BYTES - 2 ** 20) / total))
+        rows = np.sort(np.random.default_rng(0).choice(n, size=k, replace=False))
+        arrays = {name: a[rows] for name, a in arrays.items()}
+        arrays["rows"] = rows.astype(np.float64)
+    arrays["ece_bins"] = np.asarray(bins, dtype=np.float64)
+    arrays["ece_percent"] = np.asarray(res["ece"], dtype=np.float64)
+    arrays["accuracy_percent"] = np.asarray(res["accuracy"], dtype=np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def kernel_roofline(model, syn, geom, model_name, B, images):
@@ -611,6 +648,8 @@ def main():
     if args.workload in ("level1", "stream"):
         if world != 1:
             raise SystemExit(f"--workload {args.workload} is a single-GPU line")
+        if args.dump_outputs:
+            raise SystemExit(f"--dump-outputs: the zeroshot / coop_dac step only, not --workload {args.workload}")
         sd_ = syn.synthetic_state_dict(args.model, seed=0)
         model_ = build_model(dict(sd_), {"trainer": "ZeroshotCLIP"}).to(dev)
         print(json.dumps(level1_workload(args, dev, syn, model_, sd_) if args.workload == "level1" else stream_workload(args, dev, syn, model_)))
@@ -662,14 +701,15 @@ def main():
             tuned_new._cache = None
             tuned_new._cache_key = None
             return tuned_new.text_features()
-        # the reference's schedule: prompt learner + text tower on every batch (coop.py:208-210).  The mirror's cache_text_features=False
-        # runs that per-batch tower call on the fp16 residual stream (per-call flag; the cached features above keep the fp32 stream)
-        per_batch = CoOpCLIP(model, ids_new, n_ctx=n_ctx, logit_scale=1.0, seed=3, cache_text_features=False)
-        per_batch.overlap_towers = os.environ.get("BENCH_OVERLAP_TOWERS", "1") == "1"   # text tower on a side stream beside the image tower
-        text_again = per_batch.text_features
-        with torch.no_grad():
-            text_s = timed_ms(text_fp32_stream, 5) * 1e-3
-            text_s_per_batch = timed_ms(text_again, 5) * 1e-3
+        if args.full:
+            # the reference's schedule: prompt learner + text tower on every batch (coop.py:208-210).  The mirror's cache_text_features=False
+            # runs that per-batch tower call on the fp16 residual stream (per-call flag; the cached features above keep the fp32 stream)
+            per_batch = CoOpCLIP(model, ids_new, n_ctx=n_ctx, logit_scale=1.0, seed=3, cache_text_features=False)
+            per_batch.overlap_towers = os.environ.get("BENCH_OVERLAP_TOWERS", "1") == "1"   # text tower on a side stream beside the image tower
+            text_again = per_batch.text_features
+            with torch.no_grad():
+                text_s = timed_ms(text_fp32_stream, 5) * 1e-3
+                text_s_per_batch = timed_ms(text_again, 5) * 1e-3
         text_features = tuned_new.text_features()
     else:
         ids = syn.synthetic_token_ids(Cn, args.model, seed=0)
@@ -678,10 +718,11 @@ def main():
         zs = in_turn(lambda: ZeroshotCLIP(model, ids))
         torch.cuda.synchronize()
         text_s_cold = time.perf_counter() - t0
-        t0 = time.perf_counter()
-        in_turn(lambda: zs.build_model(ids))
-        torch.cuda.synchronize()
-        text_s = time.perf_counter() - t0
+        if args.full:
+            t0 = time.perf_counter()
+            in_turn(lambda: zs.build_model(ids))
+            torch.cuda.synchronize()
+            text_s = time.perf_counter() - t0
         text_features, scale = zs.text_features, zs.scale
 
     img_seed = rank if args.images_seed is None else args.images_seed + rank
@@ -746,7 +787,9 @@ def main():
         elapsed, last = run(labels, args.steps)
         res = evaluator.evaluate()
         bins_np = evaluator.bins.cpu().numpy().copy()
-        if args.sustained_seconds > 0:
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, last, bins_np, res)
+        if args.full and args.sustained_seconds > 0:
             # a second timed loop of the SAME step, long enough for the chip to reach its power / clock steady state (the K-step headline
             # region is ~0.2 s); `value` stays the K-step number
             n_s = max(args.steps, int(np.ceil(args.sustained_seconds / (elapsed / args.steps))))
@@ -758,21 +801,22 @@ def main():
                                   "ratio_to_value": (world * B * n_s / el_s) / (world * B * args.steps / elapsed)}
             if sampler:
                 extra["power"] = sampler.stop()
-        with _lib.option("cls_only_last_block", 1):   # the product default, same step, same K steps
-            for _ in range(max(1, args.warmup // 2)):
-                step(labels)
-            elapsed_cls, _ = run(labels, args.steps)
-        Lv, Dv = geom.vision_tokens, geom.vision_width
-        flops_cls = syn.flops_per_image(args.model) - (Lv * (24 * Dv * Dv + 4 * Lv * Dv) - (4 * Lv * Dv * Dv + 20 * Dv * Dv + 4 * Lv * Dv))
-        extra["value_cls_only"] = world * B * args.steps / elapsed_cls
-        extra["cls_only"] = {
-            "what": "the same step with cls_only_last_block = 1 (product default): the last image block computes K | V for every token, Q / attention / "
-                    "out-proj / MLP for the class rows only (clip/model.py:419: ln_post reads x[:, 0, :])",
-            "images_per_s": world * B * args.steps / elapsed_cls, "ms_per_step": 1e3 * elapsed_cls / args.steps,
-            "gflop_per_image_issued": flops_cls / 1e9, "gflop_per_image_every_row": syn.flops_per_image(args.model) / 1e9,
-            "tower_tflops_issued": flops_cls * world * B * args.steps / elapsed_cls / 1e12,
-            "speedup_vs_value": elapsed / elapsed_cls}
-        if coop:
+        if args.full:
+            with _lib.option("cls_only_last_block", 1):   # the product default, same step, same K steps
+                for _ in range(max(1, args.warmup // 2)):
+                    step(labels)
+                elapsed_cls, _ = run(labels, args.steps)
+            Lv, Dv = geom.vision_tokens, geom.vision_width
+            flops_cls = syn.flops_per_image(args.model) - (Lv * (24 * Dv * Dv + 4 * Lv * Dv) - (4 * Lv * Dv * Dv + 20 * Dv * Dv + 4 * Lv * Dv))
+            extra["value_cls_only"] = world * B * args.steps / elapsed_cls
+            extra["cls_only"] = {
+                "what": "the same step with cls_only_last_block = 1 (product default): the last image block computes K | V for every token, Q / attention / "
+                        "out-proj / MLP for the class rows only (clip/model.py:419: ln_post reads x[:, 0, :])",
+                "images_per_s": world * B * args.steps / elapsed_cls, "ms_per_step": 1e3 * elapsed_cls / args.steps,
+                "gflop_per_image_issued": flops_cls / 1e9, "gflop_per_image_every_row": syn.flops_per_image(args.model) / 1e9,
+                "tower_tflops_issued": flops_cls * world * B * args.steps / elapsed_cls / 1e12,
+                "speedup_vs_value": elapsed / elapsed_cls}
+        if coop and args.full:
             n_rt = max(2, args.steps // 2)
             for _ in range(2):
                 step(labels, True)
@@ -839,7 +883,7 @@ def main():
                    if world > 1 else "single GPU"},
         "images_per_sec_per_gpu": B * args.steps / elapsed,
         "tower_tflops": syn.flops_per_image(args.model) * world * B * args.steps / elapsed / 1e12,
-        "text_tower_once_s": text_s, "text_tower_first_call_s": text_s_cold,
+        **({"text_tower_once_s": text_s} if args.full else {}), "text_tower_first_call_s": text_s_cold,
         "ece_percent": res["ece"], "accuracy_percent": res["accuracy"],
     }
     out.update(extra)
@@ -847,7 +891,7 @@ def main():
         out["exchange"] = {"backend": exchange.backend, "rccl_ranks": exchange.rccl_ranks, "bytes_per_rank_per_step": 2 * B * E,
                            "world_size": world}
 
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         with torch.no_grad():
             out["roofline"] = kernel_roofline(model, syn, geom, args.model, B, images)
             if rank == 0 and world == 1:
@@ -891,7 +935,7 @@ def main():
                        "peak": HBM_PEAK_BYTES_PER_S / 1e9, "frac": tail_bytes / (tail_ms * 1e-3) / HBM_PEAK_BYTES_PER_S,
                        "bytes_note": "algorithmic: image features in + text features in + fp32 logits out + (conf, pred, label) per row"}
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not coop:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not coop:
         v, cores, avail, sample, lg_ref, cpu_images, cpu_labels = cpu_baseline(sd, args.model, args.cpu_classes, args.cpu_batch,
                                                                                 args.cpu_seconds)
         out["cpu_baseline"] = {"value": v, "unit": "images/s", "cores": cores, "cores_available": avail, "kind": "port", "sample": sample}

@@ -14,7 +14,7 @@ rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/text" -- python3 "
 find "$OUT/text" -name "*kernel_stats.csv" -exec cp {} "$OUT/text_tower_kernel_stats.csv" \;
 rm -rf "$OUT/vitl" "$OUT/text"
 cd "$ROOT"
-python3 bench.py --workload coop_dac > "$OUT/bench_coop_dac.json" 2> "$OUT/bench_coop_dac.err"
+python3 bench.py --full --workload coop_dac > "$OUT/bench_coop_dac.json" 2> "$OUT/bench_coop_dac.err"
 python3 bench.py --workload level1 > "$OUT/bench_level1.json" 2> "$OUT/bench_level1.err"
 python3 bench.py --workload stream > "$OUT/bench_stream.json" 2> "$OUT/bench_stream.err"
 python3 tools/text_bench.py > "$OUT/text_bench.txt" 2>&1
