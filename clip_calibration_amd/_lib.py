@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CLIPMI_LIBRARY") or os.path.join(_HERE, "csrc", "libclipmi.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "clipmi.h")
 
-ABI_VERSION = 13
+ABI_VERSION = 14
 
 OK, ERR_ARG, ERR_SHAPE, ERR_HIP, ERR_WORKSPACE, ERR_STATE = 0, -1, -2, -3, -4, -5
 F16, F32 = 0, 1
@@ -74,6 +74,8 @@ _SIGNATURES = {
     "clipmi_get_option": (_i, [C.c_char_p, C.POINTER(_i)]),
     "clipmi_gemm_f16": (_i, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _vp]),
     "clipmi_gemm_residual_f16": (_i, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, C.POINTER(_i), _i, _i, _i, _vp]),
+    "clipmi_gemm_residual_fold": (_i, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, C.POINTER(_i), _i, _i, _i, _vp]),
+    "clipmi_gemm_ln_fold": (_i, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i, _i64, _i, _i, _f, _vp, _vp, _i64, _i, _i, _i, _i, _i, _vp]),
     "clipmi_layernorm": (_i, [_vp, _i, _i64, _vp, _vp, _vp, _vp, _i, _i64, _i, _i, _f, _vp]),
     "clipmi_attention": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "clipmi_patchify": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp]),

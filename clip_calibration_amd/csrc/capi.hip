@@ -580,6 +580,44 @@ int clipmi_gemm_residual_f16(const void* A, int64_t lda, const void* W, int64_t 
   return launch_gemm(a, (hipStream_t)stream);
 }
 
+// The fp32-stream residual GEMM with the LayerNorm-fold outputs (the text tower's out-proj / c_proj): x[m,n] += A[m,:] . W[n,:] + bias[n] in place,
+// x16 = fp16(x) (ld = ldx) and the partials of the fp32 row, stats[(t * M + m) * 2 ..].  *parts (host) receives the number of column tiles.
+int clipmi_gemm_residual_fold(const void* A, int64_t lda, const void* W, int64_t ldw, const float* bias, float* x, int64_t ldx, void* x16,
+                              float* stats, int* parts, int M, int N, int K, clipmi_stream_t stream) {
+  CLIPMI_REQUIRE(parts, CLIPMI_ERR_ARG, "gemm_residual_fold: null parts pointer");
+  *parts = 0;
+  CLIPMI_REQUIRE(x && x16 && stats, CLIPMI_ERR_ARG, "gemm_residual_fold: null x / x16 / stats");
+  CLIPMI_REQUIRE((uintptr_t)stats % 16 == 0, CLIPMI_ERR_ARG, "gemm_residual_fold: stats must be 16-byte aligned");
+  if (M == 0) return CLIPMI_OK;
+  GemmArgs a{};
+  a.A = (const half_t*)A; a.lda = lda; a.W = (const half_t*)W; a.ldw = ldw; a.bias = bias; a.residual = x; a.out = x; a.ldo = ldx;
+  a.out_dtype = CLIPMI_F32; a.M = M; a.N = N; a.K = K; a.epilogue = CLIPMI_EPI_BIAS_RESIDUAL;
+  a.x16 = (half_t*)x16; a.stats_out = stats; a.parts_out = parts;
+  return launch_gemm(a, (hipStream_t)stream);
+}
+
+// A LayerNorm-folded consumer GEMM (in-proj / c_fc behind a fold producer) as an operator: launch_gemm with the fold arguments as the tower
+// drivers fill them (capi.hip run_block_step), ln_plane / ln_row_stride / ln_rows included.
+int clipmi_gemm_ln_fold(const void* A, int64_t lda, const void* W_f, int64_t ldw, const float* c, const float* g, const float* stats, int parts,
+                        int64_t ln_plane, int ln_row_stride, int ln_dim, float eps, float* ln_rows, void* out, int64_t ldo, int out_dtype, int M,
+                        int N, int K, int epilogue, clipmi_stream_t stream) {
+  CLIPMI_REQUIRE(epilogue == CLIPMI_EPI_BIAS || epilogue == CLIPMI_EPI_BIAS_QUICKGELU, CLIPMI_ERR_ARG,
+                 "gemm_ln_fold: epilogue %d (BIAS or BIAS_QUICKGELU only)", epilogue);
+  CLIPMI_REQUIRE(stats && g && c, CLIPMI_ERR_ARG, "gemm_ln_fold: null stats / g / c");
+  CLIPMI_REQUIRE(parts >= 1 && parts <= LN_MAX_PARTS, CLIPMI_ERR_ARG, "gemm_ln_fold: %d partials (1..%d)", parts, LN_MAX_PARTS);
+  CLIPMI_REQUIRE(ln_dim > 0 && ln_row_stride >= 1 && ln_plane >= 0, CLIPMI_ERR_ARG, "gemm_ln_fold: ln_dim %d, ln_row_stride %d, ln_plane %lld",
+                 ln_dim, ln_row_stride, (long long)ln_plane);
+  CLIPMI_REQUIRE((uintptr_t)stats % 8 == 0 && (uintptr_t)ln_rows % 8 == 0 && (uintptr_t)g % 16 == 0, CLIPMI_ERR_ARG,
+                 "gemm_ln_fold: stats / ln_rows must be 8-byte aligned, g 16-byte aligned");
+  if (M == 0) return CLIPMI_OK;
+  GemmArgs a{};
+  a.A = (const half_t*)A; a.lda = lda; a.W = (const half_t*)W_f; a.ldw = ldw; a.bias = c; a.out = out; a.ldo = ldo; a.out_dtype = out_dtype;
+  a.M = M; a.N = N; a.K = K; a.epilogue = epilogue;
+  a.ln_stats = stats; a.ln_parts = parts; a.ln_g = g; a.ln_dim = ln_dim; a.ln_eps = eps; a.ln_rows = ln_rows;
+  a.ln_plane = ln_plane; a.ln_row_stride = ln_row_stride;
+  return launch_gemm(a, (hipStream_t)stream);
+}
+
 // ---------------------------------------------------------------- model level
 int clipmi_create(const clipmi_geometry* geom, clipmi_model** out) {
   CLIPMI_REQUIRE(geom && out, CLIPMI_ERR_ARG, "create: null pointer");

@@ -77,8 +77,12 @@ struct Tile {
 // rounding point (clip/model.py:174-177: c_fc's output is an fp16 tensor before QuickGELU reads it) -- which lets gemm_stream_kernel keep a tile's
 // pre-activations as 64 fp16 registers and apply the activation inside the NEXT tile's K loop, two registers per 16-MFMA compute part, where the vector
 // pipe has nothing else to do (profiles/r06_gelu_in_compute_part.txt).  Every kernel goes through gelu_preact / quick_gelu_h (or, in that K loop, the
-// same five operations as single instructions: gelu_uop): the same bits wherever the activation is applied.
+// same five operations as single instructions: gelu_uop; the tile kernels: quick_gelu_h_tile).  The streamed kernel's two forms give the same bits;
+// the tile kernels round the product once instead of twice and agree with them to one ulp; every form is within one fp16 ulp of the correctly
+// rounded activation on every finite fp16 input, the sign of a zero included (tests/test_gpu_ln_fold.py).
 //   t = -k h (one rounding); e = 2^t; d = 1 + e; r = 1 / d; out = fp16(h r)      h -> +big: e = 0, out = h; h -> -big: e = inf, r = 0, out = -0
+// (-0 is also the correctly rounded result there: h sigmoid(1.702 h) is a tiny negative number.)  gelu_uop forms h r with v_fma_mix_f32, whose
+// addend is therefore -0, not +0: h r + (-0) is h r for every product, while h r + 0 would turn the -0 of h < -52.13 (and of h = -0) into +0.
 constexpr float GELU_K = 2.4554669595930157f;
 // v = acc * rstd + (bias - mean rstd g), explicit fused multiply-adds
 __device__ __forceinline__ f16x4 gelu_preact(const f32x4& acc, float rs, float mrs, const f32x4& bias, const f32x4& g) {
@@ -93,8 +97,28 @@ __device__ __forceinline__ float quick_gelu_h1(half_t h) {
   const float d = 1.0f + __builtin_amdgcn_exp2f(t);
   return z * __builtin_amdgcn_rcpf(d);
 }
+// the streamed kernel's last-tile tail: fp32 product, then fp16 (as gelu_uop)
 __device__ __forceinline__ f16x4 quick_gelu_h(const f16x4& h) {
   return f16x4{(half_t)quick_gelu_h1(h[0]), (half_t)quick_gelu_h1(h[1]), (half_t)quick_gelu_h1(h[2]), (half_t)quick_gelu_h1(h[3])};
+}
+// The tile kernels: the product h r rounded ONCE, straight to fp16 (v_fma_mixlo_f16 / v_fma_mixhi_f16) with a -0 addend.  In C (as quick_gelu_h
+// above) hipcc folds the product and the conversion of these kernels into the same instruction but with a +0 addend, which turns the -0 of every
+// underflowing negative activation into +0; the streamed kernel keeps the fp32 product (two roundings), so the two agree to one ulp, not bit for bit.
+__device__ __forceinline__ f16x4 quick_gelu_h_tile(const f16x4& h) {
+  typedef unsigned int u32x2_ __attribute__((ext_vector_type(2)));
+  float z[4], r[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    z[q] = (float)h[q];
+    r[q] = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(z[q] * -GELU_K));
+    asm("" : "+v"(r[q]));   // the reciprocal as an ordinary VGPR value (its trans-unit latency is the compiler's to cover before the reads below)
+  }
+  unsigned int lo = 0u, hi = 0u;
+  asm("s_nop 1\n\tv_fma_mixlo_f16 %0, %1, %2, neg(0)" : "+v"(lo) : "v"(z[0]), "v"(r[0]));
+  asm("v_fma_mixhi_f16 %0, %1, %2, neg(0)" : "+v"(lo) : "v"(z[1]), "v"(r[1]));
+  asm("v_fma_mixlo_f16 %0, %1, %2, neg(0)" : "+v"(hi) : "v"(z[2]), "v"(r[2]));
+  asm("v_fma_mixhi_f16 %0, %1, %2, neg(0)" : "+v"(hi) : "v"(z[3]), "v"(r[3]));
+  return __builtin_bit_cast(f16x4, u32x2_{lo, hi});
 }
 // fp32 outputs (OUT_F32 callers: tests, fp32 hidden activations): nothing is rounded on the way
 __device__ __forceinline__ float quick_gelu(float z) {
@@ -121,8 +145,9 @@ __device__ __forceinline__ void gelu_uop(u32x4_t& w4, float& tl, float& th, floa
   if constexpr (Q == 5) asm volatile("v_add_f32 %0, 1.0, %0" : "+v"(th));
   if constexpr (Q == 6) asm volatile("v_rcp_f32 %0, %0" : "+v"(tl));
   if constexpr (Q == 7) asm volatile("v_rcp_f32 %0, %0" : "+v"(th));
-  if constexpr (Q == 8) asm volatile("v_fma_mix_f32 %0, %1, %0, 0 op_sel_hi:[1,0,0]" : "+v"(tl) : "v"(w4[E]));
-  if constexpr (Q == 9) asm volatile("v_fma_mix_f32 %0, %1, %0, 0 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(th) : "v"(w4[E]));
+  // Q 8 / 9: addend neg(0) = -0 (a source modifier on the inline constant: same encoding length, same issue)
+  if constexpr (Q == 8) asm volatile("v_fma_mix_f32 %0, %1, %0, neg(0) op_sel_hi:[1,0,0]" : "+v"(tl) : "v"(w4[E]));
+  if constexpr (Q == 9) asm volatile("v_fma_mix_f32 %0, %1, %0, neg(0) op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(th) : "v"(w4[E]));
   if constexpr (Q == 10) asm volatile("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(w4[E]) : "v"(tl), "v"(th));
 }
 
@@ -199,7 +224,7 @@ __device__ __forceinline__ void epilogue_f16_staged(f32x4 (&acc)[T::TN][T::TM], 
           const int i = h * 4 + ii;
           f32x4 v;
           if constexpr (EPI == CLIPMI_EPI_BIAS_QUICKGELU) {
-            const f16x4 o = quick_gelu_h(gelu_preact(acc[i][jc * CH + jj], rs, mrs, bias[i], lng[i]));
+            const f16x4 o = quick_gelu_h_tile(gelu_preact(acc[i][jc * CH + jj], rs, mrs, bias[i], lng[i]));
             v = f32x4{(float)o[0], (float)o[1], (float)o[2], (float)o[3]};   // (exact: rounded again below without change)
           } else {
             v = acc[i][jc * CH + jj] * rs + (bias[i] - mrs * lng[i]);
@@ -559,7 +584,7 @@ __device__ __forceinline__ void epilogue_direct(f32x4 (&acc)[T::TN][T::TM], cons
 #pragma unroll
           for (int e = 0; e < 4; ++e) v[e] = quick_gelu(__builtin_fmaf(v[e], rs, __builtin_fmaf(-mrs, g[e], b[e])));
         } else {
-          const f16x4 o = quick_gelu_h(gelu_preact(v, rs, mrs, b, g));
+          const f16x4 o = quick_gelu_h_tile(gelu_preact(v, rs, mrs, b, g));
           v = f32x4{(float)o[0], (float)o[1], (float)o[2], (float)o[3]};
         }
       }
@@ -1954,7 +1979,7 @@ int launch_gemm(const GemmArgs& a, hipStream_t s) {
   const bool f32 = a.out_dtype == CLIPMI_F32;
   CLIPMI_REQUIRE(f32 || a.out_dtype == CLIPMI_F16, CLIPMI_ERR_ARG, "gemm: bad out_dtype %d", a.out_dtype);
 
-  KArgs k;
+  KArgs k{};
   k.A = a.A; k.lda = a.lda; k.W = a.W; k.ldw = a.ldw; k.bias = a.bias; k.residual = static_cast<const float*>(a.residual);
   k.residual16 = static_cast<const half_t*>(a.residual);
   k.out = a.out; k.ldo = a.ldo; k.M = a.M; k.N = a.N; k.K = a.K;

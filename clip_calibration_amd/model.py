@@ -384,12 +384,8 @@ class CLIP(nn.Module):
             return t.data_ptr()
 
         def fold(lin_w, lin_b, ln):
-            """LayerNorm folded into the following Linear (csrc/gemm.hip "LayerNorm folded into the GEMMs"):
-            w_f = fp16(gamma * W), g = row sums of that fp16 w_f (what the MFMA multiplies), c = W beta + b."""
-            w32 = lin_w.detach().float()
-            wf = (w32 * ln.weight.detach().float()[None, :]).to(torch.float16).contiguous()
-            gsum = wf.float().sum(dim=1).contiguous()
-            c = (w32 @ ln.bias.detach().float() + lin_b.detach().float()).contiguous()
+            """LayerNorm folded into the following Linear (ops.fold_layernorm_linear)."""
+            wf, gsum, c = ops.fold_layernorm_linear(lin_w, lin_b, ln.weight, ln.bias)
             keep.extend([wf, gsum, c])
             return wf.data_ptr(), gsum.data_ptr(), c.data_ptr()
 

@@ -1,7 +1,8 @@
 """Operator-level Python entry points: torch tensors in, HIP kernels through the C ABI, torch tensors out.
 
 torch is used for device memory and streams only; every wrapper checks device / dtype / contiguity and raises if the
-input is not a ROCm tensor -- nothing here computes on the CPU or with torch ops.
+input is not a ROCm tensor -- nothing here computes on the CPU or with torch ops (the one exception is weight
+preparation: fold_layernorm_linear).
 """
 from __future__ import annotations
 
@@ -81,6 +82,78 @@ def gemm_residual_f16(a: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, x16:
     check(lib.clipmi_gemm_residual_f16(a.data_ptr(), K, w.data_ptr(), K, bias.data_ptr(), x16.data_ptr(), N, stats.data_ptr(),
                                        C.byref(parts), M, N, K, _stream()), "clipmi_gemm_residual_f16")
     return stats, parts.value
+
+
+def fold_layernorm_linear(w: torch.Tensor, b: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor):
+    """Weight preparation of the LayerNorm fold (csrc/gemm.hip "LayerNorm folded into the GEMMs"), on the device the weights are on:
+    ``Linear(LayerNorm(x)) = rstd * (x @ w_f^T) - rstd * mean * g + c`` with w_f = fp16(gamma * W), g = row sums of that fp16 w_f (what
+    the MFMA multiplies, so the mean term cancels as inside a LayerNorm) and c = W beta + b, all in fp32.  Returns (w_f, g, c), contiguous."""
+    w32 = w.detach().float()
+    wf = (w32 * gamma.detach().float()[None, :]).to(torch.float16).contiguous()
+    g = wf.float().sum(dim=1).contiguous()
+    c = (w32 @ beta.detach().float() + b.detach().float()).contiguous()
+    return wf, g, c
+
+
+def gemm_residual_fold(a: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, x: torch.Tensor, x16: Optional[torch.Tensor] = None):
+    """``x <- x + a @ w^T + bias`` in place on the fp32 stream (reference clip/model.py:186-187), plus the LayerNorm-fold outputs:
+    x16 = fp16(x) and the row partials ``stats[t, m] = (sum, sum of squares)`` of the fp32 row m over column tile t.
+    Returns (x16, stats fp32 [8, M, 2], parts)."""
+    import ctypes as C
+    a = _dev(a, "a", (torch.float16,))
+    w = _dev(w, "w", (torch.float16,))
+    bias = _dev(bias, "bias", (torch.float32,))
+    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()):
+        raise TypeError("gemm_residual_fold: x must be a contiguous fp32 GPU tensor (it is updated in place)")
+    M, K = a.shape
+    N = w.shape[0]
+    if w.shape[1] != K or tuple(x.shape) != (M, N) or bias.numel() != N:
+        raise ValueError(f"gemm_residual_fold: a {tuple(a.shape)}, w {tuple(w.shape)}, bias {tuple(bias.shape)}, x {tuple(x.shape)}")
+    if x16 is None:
+        x16 = torch.empty(M, N, dtype=torch.float16, device=a.device)
+    x16 = _dev(x16, "x16", (torch.float16,))
+    if tuple(x16.shape) != (M, N):
+        raise ValueError(f"gemm_residual_fold: x16 {tuple(x16.shape)}, expected [{M},{N}]")
+    stats = torch.empty(8, M, 2, dtype=torch.float32, device=a.device)
+    parts = C.c_int(0)
+    check(lib.clipmi_gemm_residual_fold(a.data_ptr(), K, w.data_ptr(), K, bias.data_ptr(), x.data_ptr(), N, x16.data_ptr(),
+                                        stats.data_ptr(), C.byref(parts), M, N, K, _stream()), "clipmi_gemm_residual_fold")
+    return x16, stats, parts.value
+
+
+def gemm_ln_fold(a: torch.Tensor, w_f: torch.Tensor, c: torch.Tensor, g: torch.Tensor, stats: torch.Tensor, parts: int,
+                 ln_dim: int, eps: float = 1e-5, ln_plane: int = 0, ln_row_stride: int = 1, ln_rows: Optional[torch.Tensor] = None,
+                 epilogue: int = _lib.EPI_BIAS, out_dtype: torch.dtype = torch.float16) -> torch.Tensor:
+    """``epi(LayerNorm(x) @ W^T + b)`` as the LayerNorm-folded consumer GEMM (in-proj / c_fc): a = fp16(x) [M, K],
+    (w_f, g, c) from fold_layernorm_linear, row statistics from ``parts`` producer partials: row m's partial p is the float pair at
+    ``stats.view(-1)[2 * (p * ln_plane + m * ln_row_stride)]`` (ln_plane 0 = M; pass a 1-d view that starts at a later row to offset them).
+    ln_rows: optional fp32 [M, 2] scratch (lets the streamed kernel take more than 4 partials).  epilogue EPI_BIAS or EPI_BIAS_QUICKGELU."""
+    a = _dev(a, "a", (torch.float16,))
+    w_f = _dev(w_f, "w_f", (torch.float16,))
+    c = _dev(c, "c", (torch.float32,))
+    g = _dev(g, "g", (torch.float32,))
+    if not (isinstance(stats, torch.Tensor) and stats.is_cuda and stats.dtype == torch.float32 and stats.is_contiguous()):
+        raise TypeError("gemm_ln_fold: stats must be a contiguous fp32 GPU tensor")
+    N, K = w_f.shape
+    M = a.shape[0]
+    if a.shape[1] != K:
+        raise ValueError(f"gemm_ln_fold: a is {tuple(a.shape)} but w_f is {tuple(w_f.shape)}")
+    plane = ln_plane if ln_plane > 0 else M
+    if M > 0 and stats.numel() < 2 * ((parts - 1) * plane + (M - 1) * ln_row_stride + 1):
+        raise ValueError(f"gemm_ln_fold: stats has {stats.numel()} floats, {parts} partials of plane {plane} need more")
+    if c.numel() != N or g.numel() != N:
+        raise ValueError("gemm_ln_fold: c and g must have N elements")
+    pr = None
+    if ln_rows is not None:
+        ln_rows = _dev(ln_rows, "ln_rows", (torch.float32,))
+        if ln_rows.numel() < 2 * M:
+            raise ValueError("gemm_ln_fold: ln_rows needs [M, 2]")
+        pr = ln_rows.data_ptr()
+    out = torch.empty(M, N, dtype=out_dtype, device=w_f.device)
+    check(lib.clipmi_gemm_ln_fold(a.data_ptr(), K, w_f.data_ptr(), K, c.data_ptr(), g.data_ptr(), stats.data_ptr(), int(parts),
+                                  int(ln_plane), int(ln_row_stride), int(ln_dim), float(eps), pr, out.data_ptr(), N, _DT[out_dtype],
+                                  M, N, K, int(epilogue), _stream()), "clipmi_gemm_ln_fold")
+    return out
 
 
 def layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float = 1e-5,

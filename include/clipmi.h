@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define CLIPMI_ABI_VERSION 13
+#define CLIPMI_ABI_VERSION 14
 
 typedef void* clipmi_stream_t; /* hipStream_t */
 
@@ -122,6 +122,24 @@ int clipmi_gemm_f16(const void* A, int64_t lda, const void* W, int64_t ldw, cons
  * (lda), W fp16 [N,K] (ldw), bias fp32 [N], x16 fp16 [M,N] (ldx), stats fp32 [8 * M * 2] (room for the largest count).  K % 64 == 0, N % 8 == 0, ldx % 8 == 0, 16-byte aligned. */
 int clipmi_gemm_residual_f16(const void* A, int64_t lda, const void* W, int64_t ldw, const float* bias, void* x16, int64_t ldx,
                              float* stats, int* parts, int M, int N, int K, clipmi_stream_t stream);
+
+/* The residual GEMM of a block on the fp32 residual stream with the LayerNorm-fold outputs (the text tower's out-proj / c_proj):
+ * x[m,n] += A[m,:] . W[n,:] + bias[n] IN PLACE (fp32), x16[m,n] = fp16(x[m,n]) and the row partials of the fp32 row:
+ * stats[(t * M + m) * 2 + {0,1}] = (sum, sum of squares) over column tile t; *parts as for clipmi_gemm_residual_f16.  x fp32 and x16 fp16
+ * [M,N], both with leading dimension ldx; stats fp32 [8 * M * 2].  K % 64 == 0, N % 8 == 0, ldx % 8 == 0, 16-byte aligned. */
+int clipmi_gemm_residual_fold(const void* A, int64_t lda, const void* W, int64_t ldw, const float* bias, float* x, int64_t ldx, void* x16,
+                              float* stats, int* parts, int M, int N, int K, clipmi_stream_t stream);
+
+/* A LayerNorm-folded consumer GEMM (in-proj / c_fc with ln_1 / ln_2 folded in, csrc/gemm.hip "LayerNorm folded into the GEMMs"):
+ * out[m,n] = epi(rstd[m] * (A[m,:] . W_f[n,:]) - rstd[m] mean[m] g[n] + c[n]), epilogue CLIPMI_EPI_BIAS or CLIPMI_EPI_BIAS_QUICKGELU,
+ * mean / rstd (eps inside the square root) from the `parts` producer partials of row m over ln_dim columns:
+ * stats[(p * ln_plane + m * ln_row_stride) * 2 + {0,1}], p < parts (ln_plane 0 = M).  W_f = fp16(gamma W), g = row sums of W_f,
+ * c = W beta + b (clip_calibration_amd.ops.fold_layernorm_linear).  ln_rows: optional fp32 [M][2] scratch that lets the streamed kernel
+ * take more than 4 partials (else NULL).  A fp16 (lda), W_f fp16 (ldw), out fp16 / fp32 (out_dtype, ldo); g, c fp32 [N]; 1 <= parts <= 8,
+ * ln_row_stride >= 1; K % 64 == 0, N % 4 == 0, 16-byte aligned operands, 8-byte aligned stats / ln_rows. */
+int clipmi_gemm_ln_fold(const void* A, int64_t lda, const void* W_f, int64_t ldw, const float* c, const float* g, const float* stats, int parts,
+                        int64_t ln_plane, int ln_row_stride, int ln_dim, float eps, float* ln_rows, void* out, int64_t ldo, int out_dtype,
+                        int M, int N, int K, int epilogue, clipmi_stream_t stream);
 
 /* LayerNorm subclass with fp32 statistics (clip/model.py:153-159): y[r,:] = (x[row(r),:] - mean) * rsqrt(var+eps)
  * * gamma + beta.  row(r) = gather_idx ? gather_idx[r] : r, addressed with in_stride (elements).  D % 4 == 0,

@@ -439,3 +439,70 @@ def test_live_rows_is_host_logic():
     assert wr() is None
     model.text_dead_row_elimination = False
     assert model.live_rows(ids) == model.context_length
+
+
+def test_fold_entries_validate_arguments_without_a_gpu():
+    """clipmi_gemm_ln_fold / clipmi_gemm_residual_fold refuse bad fold arguments before anything reaches a device."""
+    L = _lib.lib
+    p = ctypes.c_void_p(4096)
+    ok = dict(parts=3, plane=0, stride=1, g=p, epi=_lib.EPI_BIAS, stats=p, A=p)
+
+    def fold(**kw):
+        a = dict(ok, **kw)
+        return L.clipmi_gemm_ln_fold(a["A"], 768, p, 768, p, a["g"], a["stats"], a["parts"], a["plane"], a["stride"], 768, 1e-5, None,
+                                     p, 3072, _lib.F16, 256, 3072, 768, a["epi"], None)
+    assert fold(parts=0) == _lib.ERR_ARG and "partials" in _lib.last_error()
+    assert fold(parts=9) == _lib.ERR_ARG
+    assert fold(g=None) == _lib.ERR_ARG and "g" in _lib.last_error()
+    assert fold(stats=None) == _lib.ERR_ARG
+    assert fold(stride=0) == _lib.ERR_ARG and "ln_row_stride" in _lib.last_error()
+    assert fold(epi=_lib.EPI_BIAS_RESIDUAL) == _lib.ERR_ARG and "epilogue" in _lib.last_error()
+    assert fold(epi=_lib.EPI_NONE) == _lib.ERR_ARG
+    assert fold(stats=ctypes.c_void_p(4100)) == _lib.ERR_ARG and "aligned" in _lib.last_error()    # 4-byte aligned statistics
+    assert fold(A=ctypes.c_void_p(4104)) == _lib.ERR_ARG and "aligned" in _lib.last_error()        # 8-byte aligned operand
+    parts = ctypes.c_int(-1)
+    assert L.clipmi_gemm_residual_fold(p, 768, p, 768, p, p, 768, p, p, None, 256, 768, 768, None) == _lib.ERR_ARG   # no parts pointer
+    assert L.clipmi_gemm_residual_fold(p, 768, p, 768, p, None, 768, p, p, ctypes.byref(parts), 256, 768, 768, None) == _lib.ERR_ARG
+    assert parts.value == 0
+    assert L.clipmi_gemm_residual_fold(p, 768, p, 768, p, p, 768, p, ctypes.c_void_p(4104), ctypes.byref(parts), 256, 768, 768,
+                                       None) == _lib.ERR_ARG                                         # misaligned statistics
+    assert L.clipmi_gemm_residual_fold(p, 768, p, 768, p, p, 768, p, p, ctypes.byref(parts), 256, 764, 768, None) == _lib.ERR_ARG   # N % 8
+
+
+def _fold_before_the_move(lin_w, lin_b, gamma, beta):
+    """The weight preparation as model.py wrote it inline before it became ops.fold_layernorm_linear."""
+    w32 = lin_w.detach().float()
+    wf = (w32 * gamma.detach().float()[None, :]).to(torch.float16).contiguous()
+    gsum = wf.float().sum(dim=1).contiguous()
+    c = (w32 @ beta.detach().float() + lin_b.detach().float()).contiguous()
+    return wf, gsum, c
+
+
+def test_fold_layernorm_linear_is_layernorm_then_linear():
+    """ops.fold_layernorm_linear: rstd (x @ w_f^T) - rstd mean g + c is LayerNorm(x; gamma, beta) @ W^T + b exactly up to the fp16 rounding of
+    gamma W -- in fp64 with W' = w_f / gamma (the weights the fold actually applies) to ~1e-12; g is the row sums of the fp16 w_f; the tensors
+    are bit for bit those model.py built before the helper existed."""
+    from clip_calibration_amd import ops
+    g = torch.Generator().manual_seed(0)
+    N, D = 96, 128
+    W = (torch.randn(N, D, generator=g) * 0.05).half()
+    b = torch.randn(N, generator=g) * 0.1
+    gamma = 1.0 + 0.3 * torch.randn(D, generator=g)
+    beta = 0.2 * torch.randn(D, generator=g)
+    wf, gs, c = ops.fold_layernorm_linear(W, b, gamma, beta)
+    for t, t0 in zip((wf, gs, c), _fold_before_the_move(W, b, gamma, beta)):
+        assert t.dtype == t0.dtype and torch.equal(t, t0) and t.is_contiguous()
+    assert wf.dtype == torch.float16 and torch.equal(wf, (W.float() * gamma[None, :]).half())
+    assert torch.equal(gs, wf.float().sum(1))
+    x = torch.randn(64, D, generator=g, dtype=torch.float64) * 3 + 5
+    mu = x.mean(1, keepdim=True)
+    rstd = 1.0 / torch.sqrt(((x - mu) ** 2).mean(1, keepdim=True) + 1e-5)
+    folded = rstd * (x @ wf.double().t()) - rstd * mu * gs.double()[None, :] + c.double()[None, :]
+    W_eff = wf.double() / gamma.double()[None, :]
+    c64 = W.double() @ beta.double() + b.double()
+    ref = ((x - mu) * rstd * gamma.double()) @ W_eff.t() + c64
+    assert float((folded - ref).abs().max()) <= 1e-12 * float(ref.abs().max()) + float((c.double() - c64).abs().max())
+    assert float((c.double() - c64).abs().max()) <= 1e-6 * float(c64.abs().max())
+    # and against the unfolded LayerNorm -> Linear, where only the fp16 rounding of gamma W separates them
+    ln_lin = torch.nn.functional.layer_norm(x, (D,), gamma.double(), beta.double(), 1e-5) @ W.double().t() + b.double()
+    assert float((folded - ln_lin).abs().max()) <= 2e-3 * float(ln_lin.abs().max())
