@@ -14,13 +14,14 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CLIPMI_LIBRARY") or os.path.join(_HERE, "csrc", "libclipmi.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "clipmi.h")
 
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 OK, ERR_ARG, ERR_SHAPE, ERR_HIP, ERR_WORKSPACE, ERR_STATE = 0, -1, -2, -3, -4, -5
 F16, F32 = 0, 1
 COMM_ID_BYTES = 128
 EPI_NONE, EPI_BIAS, EPI_BIAS_QUICKGELU, EPI_BIAS_RESIDUAL, EPI_BIAS_RELU, EPI_BIAS_RESIDUAL16_RELU = 0, 1, 2, 3, 4, 5
 CALL_DEFAULT, CALL_STREAM_F32, CALL_STREAM_F16 = 0, 1, 2   # per-call flags of the tower calls (include/clipmi.h)
+FILTER_BILINEAR, FILTER_BICUBIC = 2, 3                      # clipmi_preprocess filters (Pillow's numbers)
 
 
 class ClipmiError(RuntimeError):
@@ -51,6 +52,12 @@ class TextWeights(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in (
         "token_embedding", "positional_embedding", "ln_final_g", "ln_final_b", "proj_t")] + [
         ("blocks", C.POINTER(BlockWeights))]
+
+
+class ImageDesc(C.Structure):
+    """clipmi_image_desc: byte (y, x, c) of image b is pixels[offset + y*stride_y + x*stride_x + c*stride_c]."""
+    _fields_ = [("offset", C.c_int64), ("height", C.c_int32), ("width", C.c_int32),
+                ("stride_y", C.c_int64), ("stride_x", C.c_int64), ("stride_c", C.c_int64)]
 
 
 class PromptHook(C.Structure):
@@ -122,6 +129,8 @@ _SIGNATURES = {
     "clipmi_encode_text": (_i, [_vp, _vp, _i, _i, _vp, _vp, _sz, _u, _vp]),
     "clipmi_profile_block": (_i, [_vp, _i, _i, _i, _vp, _sz, C.POINTER(_f), _vp]),
     "clipmi_encode_image_timed": (_i, [_vp, _vp, _i, _i, _vp, _vp, _sz, _u, C.POINTER(_f), _i, C.POINTER(_i), _vp]),
+    "clipmi_preprocess_workspace_bytes": (_sz, [_vp, _i, _i, _i]),
+    "clipmi_preprocess": (_i, [_vp, _i64, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _sz, _vp]),
     "clipmi_probe_mfma_f16": (_i, [_vp, _vp, _vp, _i, _i, C.POINTER(_i), _vp]),
 }
 

@@ -497,6 +497,16 @@ int clipmi_logits(const float* img_n, const float* txt_n, float scale, const flo
   return launch_logits(img_n, txt_n, scale, dac_conf, logits, conf, pred, B, C, E, (hipStream_t)stream);
 }
 
+size_t clipmi_preprocess_workspace_bytes(const clipmi_image_desc* images, int B, int n_px, int filter) {
+  return preprocess_workspace_bytes(images, B, n_px, filter);
+}
+
+int clipmi_preprocess(const void* pixels, int64_t pixels_bytes, const clipmi_image_desc* images, int B, int n_px, int filter,
+                      const float* table, void* out, int out_dtype, void* workspace, size_t workspace_bytes, clipmi_stream_t stream) {
+  return launch_preprocess(pixels, pixels_bytes, images, B, n_px, filter, table, out, out_dtype, workspace, workspace_bytes,
+                           (hipStream_t)stream);
+}
+
 size_t clipmi_fused_tail_workspace_bytes(int B, int C) { return (B < 0 || C < 0) ? 0 : fused_tail_workspace_bytes(B, C); }
 
 int clipmi_fused_tail(const void* img, int img_dtype, int normalize, const float* txt_n, float scale, const float* dac_conf, float* logits,

@@ -295,6 +295,9 @@ int launch_logits_per_image(const float* img_n, const float* txt, float scale, c
 int launch_ece_accumulate(const float* conf, const int32_t* pred, const int64_t* labels, int n, double* bins,
                           int n_bins, hipStream_t s);
 
+size_t preprocess_workspace_bytes(const clipmi_image_desc* images, int B, int n_px, int filter);   // 0 on bad arguments
+int launch_preprocess(const void* pixels, int64_t pixels_bytes, const clipmi_image_desc* images, int B, int n_px, int filter,
+                      const float* table, void* out, int out_dtype, void* workspace, size_t workspace_bytes, hipStream_t s);
 int launch_knn(const float* q, const float* refs, float* out, int Nq, int Nr, int E, int K, hipStream_t s);
 
 static inline int round_up(int x, int m) { return (x + m - 1) / m * m; }

@@ -26,7 +26,7 @@ from .evaluator import DeviceCalibrationEvaluator
 from .proximity import knn_dists_device
 
 
-def device_batches(loader: Iterable[Tuple[torch.Tensor, torch.Tensor]], device="cuda", depth: int = 2):
+def device_batches(loader: Iterable[Tuple[torch.Tensor, torch.Tensor]], device="cuda", depth: int = 2, preprocess=None):
     """``parse_batch_test`` for a host loader (Dassl: ``batch["img"].to(device), batch["label"].to(device)``, reference
     trainers/classification/base_learner.py:84-88,175-182) without its per-batch stall: the copy of batch i + 1 is issued on a SIDE
     stream while batch i computes, and the consumer's stream waits on the copy's event, never the host.
@@ -35,6 +35,9 @@ def device_batches(loader: Iterable[Tuple[torch.Tensor, torch.Tensor]], device="
       queued the previous batch's launches, so the GPU computes meanwhile (an extra host-side copy into a pinned ring was measured
       3x SLOWER than that: 154 MB of memcpy per batch of 256 on one host thread, profiles/r03_stream_input.txt);
     * tensors that already live on the device pass through.
+    With ``preprocess`` (a ``clip_calibration_amd.preprocess.Preprocess``) the batches are decoded uint8 images -- a tensor or a
+    ``PackedImages`` (DataLoader ``collate_fn=pack_images``) -- and each is copied AND preprocessed on the side stream: the consumer
+    receives the [B, 3, n_px, n_px] batch behind the same event wait.
     Yields (image_on_device, label_on_device), ``depth - 1`` batches ahead."""
     dev = torch.device(device)
     if dev.type != "cuda":
@@ -43,6 +46,8 @@ def device_batches(loader: Iterable[Tuple[torch.Tensor, torch.Tensor]], device="
     pending = []                    # (device image, device label, copy-done event), oldest first
 
     def stage(image, label):
+        if preprocess is not None:
+            return stage_preprocessed(image, torch.as_tensor(label))
         image, label = torch.as_tensor(image), torch.as_tensor(label)
         if image.is_cuda:
             ev = torch.cuda.Event()
@@ -50,6 +55,21 @@ def device_batches(loader: Iterable[Tuple[torch.Tensor, torch.Tensor]], device="
             return image, label.to(dev, non_blocking=True), ev
         with torch.cuda.stream(copy_stream):
             d_img = image.to(dev, non_blocking=image.is_pinned())
+            d_lab = label.to(dev, non_blocking=label.is_pinned())
+            ev = torch.cuda.Event()
+            ev.record(copy_stream)
+        return d_img, d_lab, ev
+
+    def stage_preprocessed(image, label):
+        if not hasattr(image, "is_cuda"):
+            image = torch.as_tensor(image)
+        if image.is_cuda:                                   # produced on the consumer's stream: the side stream waits for it
+            copy_stream.wait_stream(torch.cuda.current_stream(dev))
+            (image.data if hasattr(image, "shapes") else image).record_stream(copy_stream)
+        with torch.cuda.stream(copy_stream):
+            if not image.is_cuda:
+                image = image.to(dev, non_blocking=image.is_pinned())
+            d_img = preprocess(image)
             d_lab = label.to(dev, non_blocking=label.is_pinned())
             ev = torch.cuda.Event()
             ev.record(copy_stream)

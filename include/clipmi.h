@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define CLIPMI_ABI_VERSION 14
+#define CLIPMI_ABI_VERSION 15
 
 typedef void* clipmi_stream_t; /* hipStream_t */
 
@@ -468,6 +468,42 @@ int clipmi_profile_block(clipmi_model* m, int batch, int iters, int only, void* 
  * entries written (> 0) or a negative error code; synchronises the stream; `out` receives the features as usual. */
 int clipmi_encode_image_timed(clipmi_model* m, const void* image, int image_dtype, int batch, float* out, void* workspace,
                               size_t workspace_bytes, unsigned flags, float* us_out, int n_us, int* n_pre_out, clipmi_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------
+ * Image preprocessing: the reference's test transform (clip/clip.py:74-81 `_transform`, Dassl's test transform with
+ * INPUT.INTERPOLATION "bicubic" / "bilinear") for a ragged batch of decoded uint8 RGB images, on the device.
+ * ---------------------------------------------------------------------------------------------------- */
+
+/* One input image inside the caller's uint8 pixel buffer: byte (y, x, c) is pixels[offset + y*stride_y + x*stride_x + c*stride_c],
+ * c = 0, 1, 2 = R, G, B (HWC: stride_x = 3, stride_c = 1; CHW: stride_x = 1, stride_c = height * width; strided views likewise). */
+typedef struct {
+  int64_t offset;
+  int32_t height, width;
+  int64_t stride_y, stride_x, stride_c;
+} clipmi_image_desc;
+
+enum { CLIPMI_FILTER_BILINEAR = 2, CLIPMI_FILTER_BICUBIC = 3 };   /* Pillow's Image.BILINEAR / Image.BICUBIC */
+
+/* Device workspace clipmi_preprocess needs for these images (host descriptors): the descriptor copy plus the tap tables of the
+ * cropped outputs (2 * B * n_px * kmax int32, kmax = Pillow's largest kernel size over the batch).  0 when an argument is bad. */
+size_t clipmi_preprocess_workspace_bytes(const clipmi_image_desc* images, int B, int n_px, int filter);
+
+/* Resize(n_px, filter) on the shorter side + CenterCrop(n_px) + ToTensor + Normalize of B uint8 RGB images of any sizes:
+ *   1. torchvision's resize size: the shorter side becomes n_px, the longer int(n_px * long / short) (identity if it already is n_px);
+ *   2. Pillow's Image.resize for 8-bit images (libImaging/Resample.c), bit-exact: horizontal pass then vertical, uint8 intermediate,
+ *      taps in double normalised by their sum, PRECISION_BITS = 22 fixed point, int32 accumulation from 1 << 21, >> 22, clamp to 0..255;
+ *      only the n_px x n_px outputs CenterCrop keeps are computed (top = round((new_h - n_px) / 2), half to even; left likewise);
+ *   3. out[b, c, y, x] = table[c * 256 + u] for the resized byte u: `table` (device, fp32 [3][256]) is ToTensor + Normalize evaluated on
+ *      the host, ((float)u / 255 - mean[c]) / std[c] in fp32 (an identity table u -> (float)u returns the resized bytes); fp16 output
+ *      rounds the table's value to nearest even (what `image.type(self.dtype)` does in encode_image).
+ * pixels: device uint8 buffer of pixels_bytes bytes; images: HOST descriptors, every field checked against pixels_bytes before anything
+ * is launched (1 <= B <= 65535, 1 <= height, width <= 32768, 1 <= n_px <= 4096: CLIPMI_ERR_SHAPE; bad filter or dtype, null pointers,
+ * a byte outside the buffer: CLIPMI_ERR_ARG).  The descriptors are copied into the workspace on `stream` (hipMemcpyAsync: page-locked
+ * descriptors must stay unchanged until the stream has passed the call; pageable ones are staged by the runtime); no synchronisation.
+ * out: [B, 3, n_px, n_px] contiguous, out_dtype CLIPMI_F16 or CLIPMI_F32.  workspace: 256-byte aligned, at least
+ * clipmi_preprocess_workspace_bytes(images, B, n_px, filter) bytes; one workspace serves one call in flight.  Two launches. */
+int clipmi_preprocess(const void* pixels, int64_t pixels_bytes, const clipmi_image_desc* images, int B, int n_px, int filter,
+                      const float* table, void* out, int out_dtype, void* workspace, size_t workspace_bytes, clipmi_stream_t stream);
 
 /* Ceiling probe for bench.py (`ceiling.mfma_only`; not on any product path): a register-only loop of v_mfma_f32_16x16x32_f16 -- no LDS, no
  * memory inside the loop -- on one workgroup of `waves` waves (1..8: two per SIMD, 256 registers each) per CU, every wave holding two register-resident sets of 4 + 4
