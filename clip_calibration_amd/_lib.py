@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CLIPMI_LIBRARY") or os.path.join(_HERE, "csrc", "libclipmi.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "clipmi.h")
 
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 OK, ERR_ARG, ERR_SHAPE, ERR_HIP, ERR_WORKSPACE, ERR_STATE = 0, -1, -2, -3, -4, -5
 F16, F32 = 0, 1
@@ -58,6 +58,12 @@ class ImageDesc(C.Structure):
     """clipmi_image_desc: byte (y, x, c) of image b is pixels[offset + y*stride_y + x*stride_x + c*stride_c]."""
     _fields_ = [("offset", C.c_int64), ("height", C.c_int32), ("width", C.c_int32),
                 ("stride_y", C.c_int64), ("stride_x", C.c_int64), ("stride_c", C.c_int64)]
+
+
+class ProcalModel(C.Structure):
+    """clipmi_procal_model: the fitted ProCal point sets as the kernels take them (include/clipmi.h)."""
+    _fields_ = [("points_true", C.c_void_p), ("points_false", C.c_void_p), ("n_true", C.c_int32), ("n_false", C.c_int32),
+                ("scale", (C.c_double * 2) * 2), ("norm", C.c_double * 2), ("ratio", C.c_double)]
 
 
 class PromptHook(C.Structure):
@@ -115,6 +121,8 @@ _SIGNATURES = {
     "clipmi_softmax_rows": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     "clipmi_knn_dists": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "clipmi_ece_accumulate": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp]),
+    "clipmi_procal_kde": (_i, [C.POINTER(ProcalModel), _vp, _vp, _vp, _i, _vp]),
+    "clipmi_procal_rows": (_i, [C.POINTER(ProcalModel), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     "clipmi_create": (_i, [C.POINTER(Geometry), C.POINTER(_vp)]),
     "clipmi_destroy": (_i, [_vp]),
     "clipmi_set_vision_weights": (_i, [_vp, C.POINTER(VisionWeights)]),

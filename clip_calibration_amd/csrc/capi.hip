@@ -570,6 +570,16 @@ int clipmi_knn_dists(const float* queries, const float* refs, float* out, int Nq
   return launch_knn(queries, refs, out, Nq, Nr, E, K, (hipStream_t)stream);
 }
 
+int clipmi_procal_kde(const clipmi_procal_model* model, const float* conf, const float* proximity, float* cstar, int n,
+                      clipmi_stream_t stream) {
+  return launch_procal_kde(model, conf, proximity, cstar, n, (hipStream_t)stream);
+}
+
+int clipmi_procal_rows(const clipmi_procal_model* model, const float* logits, const float* dac_conf, const float* proximity,
+                       float* probs, float* conf, int32_t* pred, float* cstar, int n, int C, clipmi_stream_t stream) {
+  return launch_procal_rows(model, logits, dac_conf, proximity, probs, conf, pred, cstar, n, C, (hipStream_t)stream);
+}
+
 int clipmi_ece_accumulate(const float* conf, const int32_t* pred, const int64_t* labels, int n, double* bins, int n_bins,
                           clipmi_stream_t stream) {
   return launch_ece_accumulate(conf, pred, labels, n, bins, n_bins, (hipStream_t)stream);

@@ -299,6 +299,9 @@ size_t preprocess_workspace_bytes(const clipmi_image_desc* images, int B, int n_
 int launch_preprocess(const void* pixels, int64_t pixels_bytes, const clipmi_image_desc* images, int B, int n_px, int filter,
                       const float* table, void* out, int out_dtype, void* workspace, size_t workspace_bytes, hipStream_t s);
 int launch_knn(const float* q, const float* refs, float* out, int Nq, int Nr, int E, int K, hipStream_t s);
+int launch_procal_kde(const clipmi_procal_model* model, const float* conf, const float* proximity, float* cstar, int n, hipStream_t s);
+int launch_procal_rows(const clipmi_procal_model* model, const float* logits, const float* dac_conf, const float* proximity, float* probs,
+                       float* conf, int32_t* pred, float* cstar, int n, int C, hipStream_t s);
 
 static inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 static inline size_t align256(size_t x) { return (x + 255) & ~size_t(255); }

@@ -322,6 +322,41 @@ def ece_accumulate(conf: torch.Tensor, pred: torch.Tensor, labels: torch.Tensor,
                                     n_bins, _stream()), "clipmi_ece_accumulate")
 
 
+def procal_kde(model: "_lib.ProcalModel", conf: torch.Tensor, proximity: torch.Tensor) -> torch.Tensor:
+    """ProCal's c* = T / max(T + ratio F, 1e-10) per (conf, proximity) pair (density_ratio_calibration.py:100-105) for a fitted
+    ``model`` whose point sets live on this device (procal.DensityRatioCalibration.device_model)."""
+    conf = _dev(conf, "conf", (torch.float32,))
+    proximity = _dev(proximity, "proximity", (torch.float32,))
+    if conf.dim() != 1 or proximity.shape != conf.shape:
+        raise ValueError(f"procal_kde: conf {tuple(conf.shape)} and proximity {tuple(proximity.shape)} must be equal 1-d shapes")
+    cstar = torch.empty_like(conf)
+    check(lib.clipmi_procal_kde(model, conf.data_ptr(), proximity.data_ptr(), cstar.data_ptr(), conf.numel(), _stream()),
+          "clipmi_procal_kde")
+    return cstar
+
+
+def procal_rows(model: "_lib.ProcalModel", logits: torch.Tensor, proximity: torch.Tensor, dac_conf: Optional[torch.Tensor] = None,
+                want_probs: bool = False, want_cstar: bool = False):
+    """softmax(DAC(logits)) -> ProCal -> the evaluator's top-1 (vl_calibrator.py:83-109, vl_evaluator.py:68,83), one launch:
+    returns (probs fp32 [N,C] or None, conf' fp32 [N], pred' int32 [N], c* fp32 [N] or None); logits untouched."""
+    logits = _dev(logits, "logits", (torch.float32,))
+    proximity = _dev(proximity, "proximity", (torch.float32,))
+    if logits.dim() != 2 or proximity.dim() != 1 or proximity.shape[0] != logits.shape[0]:
+        raise ValueError(f"procal_rows: logits {tuple(logits.shape)} need a proximity of one entry per row, got {tuple(proximity.shape)}")
+    N, Cn = logits.shape
+    dac_conf, pd = _opt(dac_conf, "dac_conf", (torch.float32,))
+    if dac_conf is not None and dac_conf.numel() != Cn:
+        raise ValueError("procal_rows: dac_conf must have one entry per class")
+    probs = torch.empty_like(logits) if want_probs else None
+    cstar = torch.empty(N, dtype=torch.float32, device=logits.device) if want_cstar else None
+    conf = torch.empty(N, dtype=torch.float32, device=logits.device)
+    pred = torch.empty(N, dtype=torch.int32, device=logits.device)
+    check(lib.clipmi_procal_rows(model, logits.data_ptr(), pd, proximity.data_ptr(), None if probs is None else probs.data_ptr(),
+                                 conf.data_ptr(), pred.data_ptr(), None if cstar is None else cstar.data_ptr(), N, Cn, _stream()),
+          "clipmi_procal_rows")
+    return probs, conf, pred, cstar
+
+
 # ---- CoCoOp glue (cocoop.py:154-199) -------------------------------------------------------------------------------
 def cocoop_ctx(img_n: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor,
                ctx: torch.Tensor) -> torch.Tensor:

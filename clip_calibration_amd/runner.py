@@ -140,19 +140,32 @@ def test(infer: Callable, loader: Iterable[Tuple[torch.Tensor, torch.Tensor]], v
          device="cuda", group=None) -> "OrderedDict[str, float]":
     """VLBaseLearner.test (base_learner.py:59-152): inference over the split, DAC, softmax top-1, proximity of every test
     image to the base-class val images (exp(-mean K-NN distance), :121-137), then the evaluator's metrics.  Under
-    torch.distributed each rank passes its own shard of the loader; samples are gathered before the sample-level metrics."""
+    torch.distributed each rank passes its own shard of the loader; samples are gathered before the sample-level metrics.
+    With ProCal on (``calibrator.procal_active``) the evaluator sees the top-1 of the ProCal-calibrated rows instead: the
+    (DAC-scaled) logits of the split are kept on the device until the proximity is known, then one ``clipmi_procal_rows`` launch
+    per rank -- before the gather, as proximity is per sample -- yields (conf', pred')."""
     ev = DeviceCalibrationEvaluator(ece_bins, device=device, keep_samples=True, piece_bins=piece_bins)
     dac = calibrator.class_confidence_device(device) if calibrator is not None else None
-    feats = []
+    procal = calibrator.procal_device() if calibrator is not None else None
+    if procal is not None and val_dict is None:
+        raise ValueError("test: ProCal needs val_dict for the test-image proximity")
+    feats, kept_logits, kept_labels = [], [], []
     for image, label in device_batches(loader, device):
         out = _call(infer, image, dac_conf=dac, want_conf_pred=True)
-        ev.process(out[3], out[4], label)
+        if procal is None:
+            ev.process(out[3], out[4], label)
+        else:   # out[0] already holds the DAC-scaled logits (the fused logits kernels scale in place): no DAC again below
+            kept_logits.append(out[0])
+            kept_labels.append(label)
         feats.append(out[1])
     proximity = None
     if val_dict is not None and feats:
         refs = torch.as_tensor(np.asarray(val_dict["val_image_features"]), dtype=torch.float32, device=device)
         k = min(image_k, refs.shape[0])
         proximity = torch.exp(-knn_dists_device(torch.cat(feats).float(), refs, k).mean(dim=1))
+    if procal is not None and kept_logits:
+        _, conf, pred = procal.predict_device(torch.cat(kept_logits).float(), proximity)
+        ev.process(conf, pred, torch.cat(kept_labels))
     if group is not None or (torch.distributed.is_available() and torch.distributed.is_initialized()
                              and torch.distributed.get_world_size() > 1):
         from .parallel import gather_samples

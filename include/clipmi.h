@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define CLIPMI_ABI_VERSION 15
+#define CLIPMI_ABI_VERSION 16
 
 typedef void* clipmi_stream_t; /* hipStream_t */
 
@@ -299,6 +299,39 @@ int clipmi_ece_accumulate(const float* conf, const int32_t* pred, const int64_t*
  * fp32; E % 64 == 0; 1 <= K <= min(16, Nr).  (The "val image" variant asks for K+1 against itself and drops column 0.) */
 int clipmi_knn_dists(const float* queries, const float* refs, float* out, int Nq, int Nr, int E, int K,
                      clipmi_stream_t stream);
+
+/* ProCal, the proximity-informed density-ratio calibrator (trainers/calibration/density_ratio_calibration.py:28-117, used by
+ * vl_calibrator.py:112-121 on base_calibration_mode "scaling_based" with procal_flag).  The fit stays on the host (float64); the
+ * device evaluates, per test row with confidence c and proximity p,
+ *   c* = T / max(T + ratio * F, 1e-10),  S(c, p) = norm_S * sum_{s in S} exp(-((c - s_c) / h_c)^2 / 2 - ((p - s_p) / h_p)^2 / 2)
+ * for the sets T (correct val samples) and F (incorrect), norm_S = 1 / (|S| h_c h_p 2 pi): statsmodels' KDEMultivariate.pdf with a
+ * Gaussian product kernel.  The model describes the fitted sets as the kernels take them: point i of set k (k = 0: T, 1: F) is
+ * (points_k[2 i], points_k[2 i + 1]) = (s_c * scale[k][0], s_p * scale[k][1]) with scale = sqrt(log2(e) / 2) / h, so that a pair term
+ * is exp2(-(du^2 + dv^2)) of the equally scaled query.  Host struct; the point arrays are device fp64, 16-byte aligned, n_true and
+ * n_false >= 2, every scale and norm finite and > 0, ratio finite and >= 0. */
+typedef struct clipmi_procal_model {
+  const double* points_true;
+  const double* points_false;
+  int32_t n_true, n_false;
+  double scale[2][2];
+  double norm[2];
+  double ratio;
+} clipmi_procal_model;
+
+/* c*[i] for given confidences and proximities (fp32 [n] each; cstar fp32 [n]).  n == 0: CLIPMI_OK.  One launch. */
+int clipmi_procal_kde(const clipmi_procal_model* model, const float* conf, const float* proximity, float* cstar, int n,
+                      clipmi_stream_t stream);
+
+/* VLCalibration.predict with ProCal (vl_calibrator.py:83-109) plus the evaluator's top-1 of the result (vl_evaluator.py:68, 83), in
+ * one launch and without host synchronisation.  Per row of logits fp32 [n, C] (not modified):
+ *   y = logits * (dac_conf ? dac_conf[argmax logits] : 1), probs = softmax(y), i1 = argmax (lowest index on ties), c* from
+ *   (probs[i1], proximity[i]); out[i1] = c*, out[j] = probs[j] * (1 - c*) / S for j != i1, S = sum_{j != i1} probs[j], evaluated as
+ *   exp(y_j - y_i2) / sum_{j != i1} exp(y_j - y_i2) so that it never underflows; a row whose other probabilities are all exactly zero
+ *   (C == 1, or every other y is -inf) keeps them at 0 (the reference divides 0 by 0 there).
+ * Outputs: pred[i] = argmax out (int32, lowest index on ties) and conf[i] = out[pred[i]] (fp32, required); probs fp32 [n, C] the whole
+ * calibrated matrix and cstar fp32 [n], both optional (NULL).  proximity fp32 [n].  n == 0: CLIPMI_OK. */
+int clipmi_procal_rows(const clipmi_procal_model* model, const float* logits, const float* dac_conf, const float* proximity,
+                       float* probs, float* conf, int32_t* pred, float* cstar, int n, int C, clipmi_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------
  * Multi-GPU exchange: one process per GPU, the image batch sharded over the ranks, weights and text
