@@ -150,26 +150,13 @@ __device__ __forceinline__ void attend_block(const char* const (&kread)[4], cons
 // stricter, never weaker.  Dense single-block form only (vision towers: no causal mask), with (NKT-1)*32 < L <= (NKT-1)*32 + 8:
 // the last key tile holds at most 8 live keys (193..200 tokens at NKT = 7).
 // ---------------------------------------------------------------------------------------------------------------
-// CLIPMI_ATTN_ABLATE (build-time, diagnostic builds only: results are wrong with any bit set; tools/attn_ablate.sh): 1 no v_exp, 2 no P.V /
-// row-sum MFMAs, 4 no S MFMAs, 8 query waves 4-6 idle (one query wave per SIMD), 16 no row-sum MFMA,
-// 32 no max phase, 64 no LDS fragment reads, 128 operands read as if every (sequence, head) held K | V | Q contiguously (what a head-major
-// in-projection output would give the loader), 256 no output stores,
-// 512 operand DMA marked non-temporal, 1024 output stores non-temporal, 2048 output stores write-through (sc0 sc1)
-#ifndef CLIPMI_ATTN_ABLATE
-#define CLIPMI_ATTN_ABLATE 0
-#endif
 #ifdef CLIPMI_TUNING
 #define CLIPMI_ATTN_STAMP(slot, dep) do { asm volatile("" :: "v"(dep)); if (sp) sp[slot] = (long long)__builtin_amdgcn_s_memrealtime(); } while (0)
 #else
 #define CLIPMI_ATTN_STAMP(slot, dep) do { } while (0)
 #endif
-#if CLIPMI_ATTN_ABLATE & 64
-#define CLIPMI_DS_READ_B128(dst, addr, off) asm volatile("" : "=v"(dst) : "v"(addr), "n"(off))
-#define CLIPMI_DS_READ_TR16_B64(dst, addr, off) asm volatile("" : "=v"(dst) : "v"(addr), "n"(off))
-#else
 #define CLIPMI_DS_READ_B128(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off))
 #define CLIPMI_DS_READ_TR16_B64(dst, addr, off) asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off))
-#endif
 
 template <int N>
 __device__ __forceinline__ void lds_wait4(f16x8& a, f16x8& b, f16x8& c, f16x8& d) {
@@ -228,15 +215,9 @@ __device__ __forceinline__ void attend_dense_pf(const uint32_t (&ka)[4], const u
       } else {
         lds_wait4<0>(kf[CUR][0], kf[CUR][1], kf[CUR][2], kf[CUR][3]);
       }
-      if constexpr (CLIPMI_ATTN_ABLATE & 4) {
-        asm volatile("" :: "v"(kf[CUR][0]), "v"(kf[CUR][1]), "v"(kf[CUR][2]), "v"(kf[CUR][3]));
-        s[T] = zero16;
-        asm volatile("" : "+v"(s[T]));
-      } else {
-        s[T] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[CUR][0], qf[0], zero16, 0, 0, 0);
+      s[T] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[CUR][0], qf[0], zero16, 0, 0, 0);
 #pragma unroll
-        for (int ks = 1; ks < 4; ++ks) s[T] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[CUR][ks], qf[ks], s[T], 0, 0, 0);
-      }
+      for (int ks = 1; ks < 4; ++ks) s[T] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[CUR][ks], qf[ks], s[T], 0, 0, 0);
       if constexpr (KT == NKT - 1) {   // the only tile that can hold keys at or beyond L
         // L <= (NKT - 1) * 32 + 8 (the caller's contract: 193..200 tokens): registers e >= 4 of this tile are keys >= L in EVERY
         // lane (key = 32 KT + (e & 3) + 8 (e >> 2) + 4 hh) -- P = 0 exactly, so they get no mask, no max, no exponent, and the
@@ -259,15 +240,11 @@ __device__ __forceinline__ void attend_dense_pf(const uint32_t (&ka)[4], const u
     read_v<G0 * 4096>(vf[0], va);
     // ---- group max of the raw scores, online rescale (nothing to rescale in the first group)
     float mloc = NEG_BIG;
-    if constexpr (CLIPMI_ATTN_ABLATE & 32) {
-      mloc = 40.f;
-    } else {
 #pragma unroll
-      for (int t = 0; t < G; ++t)
+    for (int t = 0; t < G; ++t)
 #pragma unroll
-        for (int e = 0; e < ((G0 + t == NKT - 1) ? 4 : 16); e += 2) mloc = fmaxf(fmaxf(s[t][e], s[t][e + 1]), mloc);
-      mloc = fmaxf(mloc, __shfl_xor(mloc, 32, 64));
-    }
+      for (int e = 0; e < ((G0 + t == NKT - 1) ? 4 : 16); e += 2) mloc = fmaxf(fmaxf(s[t][e], s[t][e + 1]), mloc);
+    mloc = fmaxf(mloc, __shfl_xor(mloc, 32, 64));
     const float m_new = G0 == 0 ? mloc : fmaxf(m_run, mloc);
     if constexpr (G0 > 0) {
       const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * C);
@@ -292,9 +269,7 @@ __device__ __forceinline__ void attend_dense_pf(const uint32_t (&ka)[4], const u
       f16x8 pf;
 #pragma unroll
       for (int j = 0; j < 8; ++j)
-        pf[j] = (TAILT && 8 * SS + j >= 4) ? (half_t)0.f
-                : (CLIPMI_ATTN_ABLATE & 1) ? (half_t)__builtin_fmaf(s[T][8 * SS + j], C, -mc)
-                                           : (half_t)__builtin_amdgcn_exp2f(__builtin_fmaf(s[T][8 * SS + j], C, -mc));
+        pf[j] = (TAILT && 8 * SS + j >= 4) ? (half_t)0.f : (half_t)__builtin_amdgcn_exp2f(__builtin_fmaf(s[T][8 * SS + j], C, -mc));
       if constexpr (!LAST) lds_wait4h<4>(vf[CUR][0], vf[CUR][1], vf[CUR][2], vf[CUR][3]);
       else lds_wait4h<0>(vf[CUR][0], vf[CUR][1], vf[CUR][2], vf[CUR][3]);
       CLIPMI_VALU_TO_MFMA_FENCE(pf);
@@ -303,21 +278,13 @@ __device__ __forceinline__ void attend_dense_pf(const uint32_t (&ka)[4], const u
         const f16x4 lo = vf[CUR][dt * 2], hi = vf[CUR][dt * 2 + 1];
         f16x8 v8 = f16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
         CLIPMI_VALU_TO_MFMA_FENCE(v8);   // the two halves may have been moved together by VALU copies
-        if constexpr (CLIPMI_ATTN_ABLATE & 2) {
-          asm volatile("" :: "v"(v8), "v"(pf));
-          if (G0 == 0 && STEP == 0) { oacc[dt] = zero16; asm volatile("" : "+v"(oacc[dt])); }
-        } else if (G0 == 0 && STEP == 0) oacc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(v8, pf, zero16, 0, 0, 0);
+        if (G0 == 0 && STEP == 0) oacc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(v8, pf, zero16, 0, 0, 0);
         else oacc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(v8, pf, oacc[dt], 0, 0, 0);
       }
-      if constexpr (CLIPMI_ATTN_ABLATE & (2 | 16)) {
-        asm volatile("" :: "v"(pf));
-        if (G0 == 0 && STEP == 0) { lacc = zero16; lacc[0] = 1.f; asm volatile("" : "+v"(lacc)); }
-      } else {
-        f16x8 one_rows = ones;
-        CLIPMI_VALU_TO_MFMA_FENCE(one_rows);   // the constant may be re-materialised by a v_mov right in front of its use
-        if (G0 == 0 && STEP == 0) lacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(one_rows, pf, zero16, 0, 0, 0);
-        else lacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(one_rows, pf, lacc, 0, 0, 0);
-      }
+      f16x8 one_rows = ones;
+      CLIPMI_VALU_TO_MFMA_FENCE(one_rows);   // the constant may be re-materialised by a v_mov right in front of its use
+      if (G0 == 0 && STEP == 0) lacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(one_rows, pf, zero16, 0, 0, 0);
+      else lacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(one_rows, pf, lacc, 0, 0, 0);
     };
     auto pv_tile = [&](auto t_tag) {
       pv_step(t_tag, std::integral_constant<int, 0>{});
@@ -409,8 +376,7 @@ __device__ __forceinline__ void store_out_lines(half_t* tile_row0, int64_t row_s
     const int r = rl + 8 * j;
     u32x4* dst = reinterpret_cast<u32x4*>(reinterpret_cast<char*>(tile_row0 + r * row_stride_halves) + 16 * p);
     if (r < nrows) {
-      if constexpr (NT || (CLIPMI_ATTN_ABLATE & 1024)) asm volatile("global_store_dwordx4 %0, %1, off nt" :: "v"(dst), "v"(line[j]) : "memory");
-      else if constexpr (CLIPMI_ATTN_ABLATE & 2048) asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" :: "v"(dst), "v"(line[j]) : "memory");
+      if constexpr (NT) asm volatile("global_store_dwordx4 %0, %1, off nt" :: "v"(dst), "v"(line[j]) : "memory");
       else *dst = line[j];
     }
   }
@@ -579,9 +545,8 @@ __device__ __forceinline__ void attention_vision_body(const half_t* __restrict__
     const int lr = lane >> 3, cs = lane & 7;
     const int swv = (cs ^ (((lr >> 1) & 1) << 2)) << 4;                                        // V: chunk ^ (((row >> 1) & 1) << 2)
     const int swk[2] = {(cs ^ (lr >> 1)) << 4, (cs ^ (4 + (lr >> 1))) << 4};                    // K, Q: chunk ^ ((row >> 1) & 7), by group parity
-    constexpr bool FAKE = (CLIPMI_ATTN_ABLATE & 128) != 0;
-    const int lane_row = lr * (FAKE ? 64 : (int)ld) * 2;
-    const int gstep = 8 * (FAKE ? 64 : (int)ld) * 2;                                            // one group further
+    const int lane_row = lr * (int)ld * 2;
+    const int gstep = 8 * (int)ld * 2;                                                          // one group further
     auto radd = [](int base, int add) {
       int r;
       asm volatile("v_add_u32 %0, %1, %2" : "=v"(r) : "v"(base), "s"(add));
@@ -589,17 +554,16 @@ __device__ __forceinline__ void attention_vision_body(const half_t* __restrict__
     };
     auto stage = [&](int it_, int buf) {
       const int n = it_ / H, h = it_ - n * H;
-      const half_t* base = FAKE ? qkv + (int64_t)it_ * 3 * L * 64 : qkv + (int64_t)n * L * ld + h * 64;
-      const __amdgpu_buffer_rsrc_t rs = make_rsrc(base, FAKE ? (int64_t)3 * L * 64 * 2 : ((int64_t)L * ld - h * 64) * 2);   // rows >= L: outside, read as zero
-      const int koff = FAKE ? L * 64 * 2 : D * 2;
+      const half_t* base = qkv + (int64_t)n * L * ld + h * 64;
+      const __amdgpu_buffer_rsrc_t rs = make_rsrc(base, ((int64_t)L * ld - h * 64) * 2);   // rows >= L: outside, read as zero
+      const int koff = D * 2;
       char* B = smem + buf * VBUF;
 #pragma unroll
       for (int g = 0; g < VROWS / 8; ++g) {
         const int kq = lane_row + swk[g & 1];
-        constexpr int AUX = (CLIPMI_ATTN_ABLATE & 512) ? 2 : 0;   // nt
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, CLIPMI_LDS_PTR(B + g * 1024), 16, radd(kq + koff, g * gstep), 0, 0, AUX);                        // K
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, CLIPMI_LDS_PTR(B + VARR + g * 1024), 16, radd(lane_row + swv + 2 * koff, g * gstep), 0, 0, AUX);  // V
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, CLIPMI_LDS_PTR(B + 2 * VARR + g * 1024), 16, radd(kq, g * gstep), 0, 0, AUX);                      // Q
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, CLIPMI_LDS_PTR(B + g * 1024), 16, radd(kq + koff, g * gstep), 0, 0, 0);                        // K
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, CLIPMI_LDS_PTR(B + VARR + g * 1024), 16, radd(lane_row + swv + 2 * koff, g * gstep), 0, 0, 0);  // V
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, CLIPMI_LDS_PTR(B + 2 * VARR + g * 1024), 16, radd(kq, g * gstep), 0, 0, 0);                      // Q
       }
     };
     stage(item, 0);
@@ -663,7 +627,6 @@ __device__ __forceinline__ void attention_vision_body(const half_t* __restrict__
       const uint32_t va[2] = {lb + (uint32_t)vro[0], lb + (uint32_t)vro[1]};
       const uint32_t qa[4] = {lb + (uint32_t)qro[0], lb + (uint32_t)qro[1], lb + (uint32_t)qro[2], lb + (uint32_t)qro[3]};
 #ifdef CLIPMI_TUNING
-      if ((CLIPMI_ATTN_ABLATE & 8) && wave >= 4) continue;
       attend_dense_pf<NKT, GROUP>(ka, va, qa, L, hh, oacc, lacc, stamp ? sp : nullptr);
 #else
       attend_dense_pf<NKT, GROUP>(ka, va, qa, L, hh, oacc, lacc);
@@ -673,15 +636,11 @@ __device__ __forceinline__ void attention_vision_body(const half_t* __restrict__
     asm volatile("" :: "v"(oacc[0][0]), "v"(oacc[1][15]), "v"(lacc[0]));
     if (stamp) sp[2] = (long long)__builtin_amdgcn_s_memrealtime();
 #endif
-    if constexpr (CLIPMI_ATTN_ABLATE & 256) {
-      asm volatile("" :: "v"(oacc[0]), "v"(oacc[1]), "v"(lacc[0]));
-    } else {
-      // the wave's own Q rows of this item are dead (qf was read before the first MFMA): its output tile goes through them as full lines.
-      // Rows >= VROWS of the last tile would lie in the other buffer's K rows (being written by the loader): never parked (nrows <= 5 there).
-      const int n = item / H, h = item - n * H;
-      const int nrows = L - q0 < 32 ? L - q0 : 32;
-      store_out_lines<NT>(out + ((int64_t)n * L + q0) * D + h * 64, D, lds_base + (uint32_t)(buf * VBUF + 2 * VARR + q0 * 128), oacc, lacc[0], lane, nrows);
-    }
+    // the wave's own Q rows of this item are dead (qf was read before the first MFMA): its output tile goes through them as full lines.
+    // Rows >= VROWS of the last tile would lie in the other buffer's K rows (being written by the loader): never parked (nrows <= 5 there).
+    const int n = item / H, h = item - n * H;
+    const int nrows = L - q0 < 32 ? L - q0 : 32;
+    store_out_lines<NT>(out + ((int64_t)n * L + q0) * D + h * 64, D, lds_base + (uint32_t)(buf * VBUF + 2 * VARR + q0 * 128), oacc, lacc[0], lane, nrows);
 #ifdef CLIPMI_TUNING
     if (stamp) sp[3] = (long long)__builtin_amdgcn_s_memrealtime();
 #endif
@@ -848,10 +807,7 @@ constexpr int RKEYS = RTPB * 32;            // keys per block
 constexpr int RIMG = RKEYS * 128;           // one operand image of a block
 constexpr int RSLOT = 2 * RIMG;             // K | V
 constexpr int RNSLOT = 3;
-#ifndef CLIPMI_RING_WAVES
-#define CLIPMI_RING_WAVES 11
-#endif
-constexpr int RNW = CLIPMI_RING_WAVES;      // compute waves = query tiles per pass; the loader is wave RNW.  11 + 1 = 12 waves: three on every SIMD, 168 VGPRs
+constexpr int RNW = 11;                     // compute waves = query tiles per pass; the loader is wave RNW.  11 + 1 = 12 waves: three on every SIMD, 168 VGPRs
 constexpr int RTHREADS = (RNW + 1) * 64;
 constexpr int RQ = RNW * 32 * 128;          // the Q tiles of a pass
 constexpr int RSMEM = RNSLOT * RSLOT + RQ;  // 96 KiB + 44 KiB
@@ -889,12 +845,6 @@ __host__ __device__ inline int ring_spot(unsigned i) { return (int)((i >> 19) & 
 // The row sums stay in `lacc` (ones-tile MFMA accumulator) for the WHOLE pass and are read by the vector pipe once, at the pass end, behind
 // CLIPMI_MFMA_TO_VALU_FENCE3 (common.h): a per-group `l += lacc[0]` right behind the group's last MFMAs -- hipcc put `s_nop 10` between them -- is
 // the second co-residency hazard of this code base (52-160 of 200 LayerNorm launches wrong beside the kernel, 0 with more wait states).
-// CLIPMI_RING_ABLATE (build-time, diagnostic builds only: results are wrong with any bit set; make ring_ablate, tools/lib_ab.py):
-// 1 no exponent work (P = the raw score bits) | 2 no MFMAs (S and P.V) | 4 no LDS fragment reads | 8 no maximum | 16 no fma in front of v_exp |
-// 32 no per-block barrier (loader and compute waves run free: races, timing only) | 64 no LDS-DMA at all (compute on whatever the LDS holds)
-#ifndef CLIPMI_RING_ABLATE
-#define CLIPMI_RING_ABLATE 0
-#endif
 template <int CNT>
 __device__ __forceinline__ void ring_attend(const uint32_t (&ka)[4], const uint32_t (&va)[2], const f16x8 (&qf)[4], const f16x8& ones, int k_lo, int L,
                                             int hh, float& m_run, f32x16 (&oacc)[2], f32x16& lacc, long long* sp = nullptr) {
@@ -904,37 +854,19 @@ __device__ __forceinline__ void ring_attend(const uint32_t (&ka)[4], const uint3
   f16x4 vf[2][4];
   f32x16 s[CNT];
   static_assert(CNT == 1 || CNT == 2, "one or two key tiles per softmax group");
-  constexpr bool NO_LDS = (CLIPMI_RING_ABLATE & 4) != 0, NO_MFMA = (CLIPMI_RING_ABLATE & 2) != 0;
-  if constexpr (NO_LDS) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        kf[i][j] = qf[j];
-        vf[i][j] = f16x4{qf[j][0], qf[j][1], qf[j][2], qf[j][3]};
-        asm volatile("" : "+v"(kf[i][j]), "+v"(vf[i][j]));
-      }
-  } else {
-    read_k<0>(kf[0], ka);
-  }
+  read_k<0>(kf[0], ka);
   auto s_tile = [&](auto t_tag) {
     constexpr int T = decltype(t_tag)::value;
     constexpr int CUR = T & 1;
-    if constexpr (NO_LDS) {
-    } else if constexpr (T + 1 < CNT) {
+    if constexpr (T + 1 < CNT) {
       read_k<T + 1>(kf[CUR ^ 1], ka);
       lds_wait4<4>(kf[CUR][0], kf[CUR][1], kf[CUR][2], kf[CUR][3]);
     } else {
       lds_wait4<0>(kf[CUR][0], kf[CUR][1], kf[CUR][2], kf[CUR][3]);
     }
-    if constexpr (NO_MFMA) {
+    s[T] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[CUR][0], qf[0], zero16, 0, 0, 0);
 #pragma unroll
-      for (int e = 0; e < 16; ++e) s[T][e] = (float)kf[CUR][e & 3][e >> 2] + (float)qf[e & 3][e >> 2];
-    } else {
-      s[T] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[CUR][0], qf[0], zero16, 0, 0, 0);
-#pragma unroll
-      for (int ks = 1; ks < 4; ++ks) s[T] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[CUR][ks], qf[ks], s[T], 0, 0, 0);
-    }
+    for (int ks = 1; ks < 4; ++ks) s[T] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[CUR][ks], qf[ks], s[T], 0, 0, 0);
     if (k_lo + T * 32 + 32 > L) {   // wave-uniform: the item's last key tile
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
@@ -946,17 +878,13 @@ __device__ __forceinline__ void ring_attend(const uint32_t (&ka)[4], const uint3
   s_tile(std::integral_constant<int, 0>{});
   if constexpr (CNT > 1) s_tile(std::integral_constant<int, 1>{});
   CLIPMI_RING_STAMP(3, s[CNT - 1][0]);
-  if constexpr (!NO_LDS) read_v<0>(vf[0], va);   // the P.V phase opens with these: behind the maximum and the rescale by the time they are needed
+  read_v<0>(vf[0], va);   // the P.V phase opens with these: behind the maximum and the rescale by the time they are needed
   float mloc = NEG_BIG;
-  if constexpr (CLIPMI_RING_ABLATE & 8) {
-    mloc = s[0][0];
-  } else {
 #pragma unroll
-    for (int t = 0; t < CNT; ++t)
+  for (int t = 0; t < CNT; ++t)
 #pragma unroll
-      for (int e = 0; e < 16; e += 2) mloc = fmaxf(fmaxf(s[t][e], s[t][e + 1]), mloc);
-    mloc = fmaxf(mloc, swap32_f(mloc));
-  }
+    for (int e = 0; e < 16; e += 2) mloc = fmaxf(fmaxf(s[t][e], s[t][e + 1]), mloc);
+  mloc = fmaxf(mloc, swap32_f(mloc));
   // The reference point of the exponentials moves only when some query's maximum has grown by more than RING_SLACK (2^8 in P): with 32 queries per wave
   // "some lane saw a new maximum" holds in nearly every group (SQ_INSTS_VALU: 96 vector instructions per tile where the straight path has 56 -- the 48
   // accumulator multiplies of this branch), while a maximum that jumps by e^5.5 after the first group is rare.  In between P = 2^((s - m_run) C) <= 256:
@@ -980,20 +908,11 @@ __device__ __forceinline__ void ring_attend(const uint32_t (&ka)[4], const uint3
     constexpr int T = decltype(t_tag)::value, SS = decltype(ss_tag)::value;
     constexpr int STEP = T * 2 + SS, CUR = STEP & 1;
     constexpr bool LAST = STEP == 2 * CNT - 1;
-    if constexpr (!LAST && !NO_LDS) read_v<((STEP + 1) / 2) * 4096 + ((STEP + 1) & 1) * 2048>(vf[CUR ^ 1], va);
+    if constexpr (!LAST) read_v<((STEP + 1) / 2) * 4096 + ((STEP + 1) & 1) * 2048>(vf[CUR ^ 1], va);
     f16x8 pf;
-    if constexpr (CLIPMI_RING_ABLATE & 1) {
-      const f32x4 raw = f32x4{s[T][8 * SS], s[T][8 * SS + 1] + mc, s[T][8 * SS + 2], s[T][8 * SS + 3]};
-      pf = __builtin_bit_cast(f16x8, raw);
-    } else if constexpr (CLIPMI_RING_ABLATE & 16) {
 #pragma unroll
-      for (int j = 0; j < 8; ++j) pf[j] = (half_t)__builtin_amdgcn_exp2f(s[T][8 * SS + j]);
-    } else {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) pf[j] = (half_t)__builtin_amdgcn_exp2f(__builtin_fmaf(s[T][8 * SS + j], C, -mc));
-    }
-    if constexpr (NO_LDS) {
-    } else if constexpr (!LAST) lds_wait4h<4>(vf[CUR][0], vf[CUR][1], vf[CUR][2], vf[CUR][3]);
+    for (int j = 0; j < 8; ++j) pf[j] = (half_t)__builtin_amdgcn_exp2f(__builtin_fmaf(s[T][8 * SS + j], C, -mc));
+    if constexpr (!LAST) lds_wait4h<4>(vf[CUR][0], vf[CUR][1], vf[CUR][2], vf[CUR][3]);
     else lds_wait4h<0>(vf[CUR][0], vf[CUR][1], vf[CUR][2], vf[CUR][3]);
     f16x8 v8[2];
 #pragma unroll
@@ -1002,15 +921,9 @@ __device__ __forceinline__ void ring_attend(const uint32_t (&ka)[4], const uint3
       v8[dt] = f16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
     }
     CLIPMI_VALU_TO_MFMA_FENCE3(pf, v8[0], v8[1]);   // ONE fence: P comes from conversions, the V halves may have been moved together by VALU copies
-    if constexpr (NO_MFMA) {
-      oacc[0][STEP] += (float)pf[0] * (float)v8[0][0] + (float)pf[2] * (float)v8[0][5];
-      oacc[1][STEP] += (float)pf[4] * (float)v8[1][0] + (float)pf[6] * (float)v8[1][5];
-      lacc[STEP] += (float)pf[1] + (float)pf[3] + (float)pf[5] + (float)pf[7];
-    } else {
-      oacc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(v8[0], pf, oacc[0], 0, 0, 0);
-      oacc[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(v8[1], pf, oacc[1], 0, 0, 0);
-      lacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ones, pf, lacc, 0, 0, 0);
-    }
+    oacc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(v8[0], pf, oacc[0], 0, 0, 0);
+    oacc[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(v8[1], pf, oacc[1], 0, 0, 0);
+    lacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ones, pf, lacc, 0, 0, 0);
   };
   pv_step(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
   pv_step(std::integral_constant<int, 0>{}, std::integral_constant<int, 1>{});
@@ -1085,7 +998,6 @@ __global__ __launch_bounds__(RTHREADS) void attention_ring_kernel(const half_t* 
       return make_rsrc(qkv + (int64_t)u.n * L * ld + u.h * 64, ((int64_t)L * ld - u.h * 64) * 2);   // rows >= L: outside the descriptor, read as zero
     };
     auto dma_block = [&](const Cur& u, int slot) {   // 32 pieces: K | V of 128 keys
-      if constexpr (CLIPMI_RING_ABLATE & 64) return;
       const __amdgpu_buffer_rsrc_t rs = item_rsrc(u);
       char* B = smem + slot * RSLOT;
       const int boff = u.b * RKEYS * ld * 2;
@@ -1096,7 +1008,6 @@ __global__ __launch_bounds__(RTHREADS) void attention_ring_kernel(const half_t* 
       }
     };
     auto dma_q = [&](const Cur& u) {   // the Q tiles of pass u.p, tile of wave w into region w: 4 pieces per wave
-      if constexpr (CLIPMI_RING_ABLATE & 64) return;
       const __amdgpu_buffer_rsrc_t rs = item_rsrc(u);
       char* Q = smem + RNSLOT * RSLOT;
       for (int w = 0; w < RNW; ++w) {
@@ -1132,7 +1043,7 @@ __global__ __launch_bounds__(RTHREADS) void attention_ring_kernel(const half_t* 
 #ifdef CLIPMI_TUNING
       if (sp) sp[1] = (long long)__builtin_amdgcn_s_memtime();
 #endif
-      if constexpr (!(CLIPMI_RING_ABLATE & 32)) __builtin_amdgcn_s_barrier();   // block g is in LDS for every wave; every wave is done with block g - 1, whose slot block g + 2 takes
+      __builtin_amdgcn_s_barrier();   // block g is in LDS for every wave; every wave is done with block g - 1, whose slot block g + 2 takes
 #ifdef CLIPMI_TUNING
       if (sp) sp[2] = (long long)__builtin_amdgcn_s_memtime();
 #endif
@@ -1180,7 +1091,7 @@ __global__ __launch_bounds__(RTHREADS) void attention_ring_kernel(const half_t* 
     long long* sp = (stamps != nullptr && lane == 0 && blockIdx.x < 8 && g < 64) ? stamps + (((size_t)blockIdx.x * 64 + g) * (RNW + 1) + wave) * 8 : nullptr;
     if (sp) sp[0] = (long long)__builtin_amdgcn_s_memtime();
 #endif
-    if constexpr (!(CLIPMI_RING_ABLATE & 32)) __builtin_amdgcn_s_barrier();   // the loader's vmcnt wait came first: block g (and at a pass start this wave's Q tile) is in LDS
+    __builtin_amdgcn_s_barrier();   // the loader's vmcnt wait came first: block g (and at a pass start this wave's Q tile) is in LDS
 #ifdef CLIPMI_TUNING
     if (sp) sp[2] = (long long)__builtin_amdgcn_s_memtime();
     if (sp) sp[1] = (long long)__builtin_amdgcn_s_getreg(4 | (4 << 6) | (1 << 11));   // HW_ID.SIMD_ID of this wave (compute waves have no stamp 1)

@@ -71,7 +71,6 @@ std::atomic<int> g_cus[64];
 
 #ifdef CLIPMI_TUNING
 std::atomic<long long*> g_tuning_stamps{nullptr};
-std::atomic<int> g_tuning_knob{0};
 #endif
 
 Options& options() {
@@ -425,13 +424,6 @@ int clipmi_set_option(const char* name, int value) {
 #ifdef CLIPMI_TUNING
 int clipmi_tuning_set_stamps(void* device_buffer) {   // tuning build only; not part of include/clipmi.h
   g_tuning_stamps.store(static_cast<long long*>(device_buffer), std::memory_order_relaxed);
-  return CLIPMI_OK;
-}
-#endif
-
-#ifdef CLIPMI_TUNING
-int clipmi_tuning_set_knob(int bits) {   // tuning build only
-  g_tuning_knob.store(bits, std::memory_order_relaxed);
   return CLIPMI_OK;
 }
 #endif

@@ -34,11 +34,6 @@ __device__ __forceinline__ void buffer_load_lds16(__amdgpu_buffer_rsrc_t rsrc, c
   __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, CLIPMI_LDS_PTR(lds), 16, voff, soff, 0, 0);
 }
 #define CLIPMI_BUFFER_LOAD_LDS16(rsrc, lds, voff, soff) ::clipmi::buffer_load_lds16((rsrc), (lds), (voff), (soff))
-// the same with cache-policy bits (1 = sc0, 2 = sc1, 4? = nt on gfx950's buffer instructions: 2 is what __builtin_nontemporal_load emits); build-time A/Bs only
-template <int AUX>
-__device__ __forceinline__ void buffer_load_lds16_aux(__amdgpu_buffer_rsrc_t rsrc, const void* lds, int voff, int soff) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, CLIPMI_LDS_PTR(lds), 16, voff, soff, 0, AUX);
-}
 
 // A register that VALU instructions have just written (conversions, transcendentals: the softmax's P, the tail's hi / lo split) and that
 // an MFMA reads as a SOURCE operand right behind them needs wait states that hipcc does not insert on gfx950 for these sequences (it
@@ -170,7 +165,6 @@ Options& options();
 // Diagnostic build only (make TUNING=1): device buffer of 8 int64 per workgroup that the GEMM kernels stamp with
 // s_memrealtime at their phase boundaries (clipmi_tuning_set_stamps, tools/gemm_stamps.py).  Absent from the product build.
 extern std::atomic<long long*> g_tuning_stamps;
-extern std::atomic<int> g_tuning_knob;   // ablation bits (clipmi_tuning_set_knob)
 #endif
 
 // Per-device state.  One process may drive several GPUs: kernel attributes (dynamic LDS size) are set once per

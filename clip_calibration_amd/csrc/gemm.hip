@@ -319,8 +319,7 @@ __device__ __forceinline__ void epilogue_residual_fold(f32x4 (&acc)[T::TN][T::TM
       const f16x8 val = *reinterpret_cast<const f16x8*>(patch + row * ROWB + rcol * 16);
       const int m = m0 + wave_m * T::WTM + jc * 32 + row;
       if (m < a.M && n_st < a.N) {
-        if constexpr (CLIPMI_STORE_AUX & 2) __builtin_nontemporal_store(val, reinterpret_cast<f16x8*>(a.x16 + (int64_t)m * a.ldo + n_st));
-        else *reinterpret_cast<f16x8*>(a.x16 + (int64_t)m * a.ldo + n_st) = val;
+        *reinterpret_cast<f16x8*>(a.x16 + (int64_t)m * a.ldo + n_st) = val;
       }
     }
     __builtin_amdgcn_sched_barrier(0);
@@ -448,8 +447,7 @@ __device__ __forceinline__ void epilogue_residual_fold16_dma(f32x4 (&acc)[T::TN]
       const int m = row0 + c * 32 + rl;
       const int n_st = col0 + ((dslot ^ ((rl >> 1) & 7)) << 3);
       if (m < a.M && n_st < a.N) {
-        if constexpr (CLIPMI_STORE_AUX & 2) __builtin_nontemporal_store(val, reinterpret_cast<f16x8*>(a.x16 + (int64_t)m * a.ldo + n_st));
-        else *reinterpret_cast<f16x8*>(a.x16 + (int64_t)m * a.ldo + n_st) = val;
+        *reinterpret_cast<f16x8*>(a.x16 + (int64_t)m * a.ldo + n_st) = val;
       }
     }
     __builtin_amdgcn_sched_barrier(0);
@@ -839,7 +837,7 @@ __global__ __launch_bounds__(256) void ln_finalize_kernel(const KArgs a, float2*
 //     other stage is during the K-step before it (round 6; until then: between the slices of the conversion, with a vmcnt wait and a workgroup
 //     barrier behind it); the row parameters (rstd, mean * rstd) are finalised from the producer's row partials at the tile start (RAW mode) or come
 //     from ln_finalize_kernel.
-// Ablations on MI355X (tools/stream_ablate.py): a first version that sent each slice through a wave-private LDS patch at
+// Ablations on MI355X (round 2, tuning build): a first version that sent each slice through a wave-private LDS patch at
 // the top of its K-step paid 0.9 us per slice (nothing else runs on the SIMD while both of its waves wait for that
 // round trip), computed the parameters of the next tile with ordinary loads (their vmcnt wait also waits for the 64 KB
 // stage) and ended 10 % SLOWER than the one-tile-per-workgroup kernel; without those three costs the loop runs at
@@ -849,23 +847,6 @@ __global__ __launch_bounds__(256) void ln_finalize_kernel(const KArgs a, float2*
 // unrolled (straight-line code: hipcc's waitcnt pass keeps counted lgkmcnt waits), the remaining ones run in a loop.
 // Needs K >= 8 * 64 (K-steps 1 .. 6 and the last one carry the held slices of the previous tile), a matrix below 2 GiB per launch (one descriptor: launch_one cuts longer ones into row ranges), an 8-column-aligned fp16 output and, with the LayerNorm fold, the finalised row parameters.
 // ---------------------------------------------------------------------------------------------------------------
-#ifndef CLIPMI_STREAM_HD
-#define CLIPMI_STREAM_HD 2
-#endif
-// build-time A/B of the cache policy of the two operands' LDS-DMA (profiles/r06_stream_dma_policy.txt): an activation panel is read by the four
-// workgroups of a band at about the same time and never again in that band, a weight panel by every m-tile of the band
-#ifndef CLIPMI_STREAM_BIAS_SWAP
-#define CLIPMI_STREAM_BIAS_SWAP 1   // build-time A/B: the bias / plain epilogues' store interleave inside the next K loop (1) or in the tile change (0)
-#endif
-#ifndef CLIPMI_STREAM_A_AUX
-#define CLIPMI_STREAM_A_AUX 0
-#endif
-#ifndef CLIPMI_STREAM_W_AUX
-#define CLIPMI_STREAM_W_AUX 0
-#endif
-#ifndef CLIPMI_STREAM_PREFETCH
-#define CLIPMI_STREAM_PREFETCH 1
-#endif
 using TStream = Tile<256, 256, 2, 4, 2>;
 constexpr int STREAM_RAW_PARTS = 4;   // row-partial slots of gemm_stream_kernel's LDS table (D <= 1024 with 256-column producer tiles)
 // the streamed kernel finalises the LayerNorm row partials itself (RAW mode) while they fit its LDS table; wider producers
@@ -972,8 +953,8 @@ __global__ __launch_bounds__(512, 2) void gemm_stream_kernel(const KArgs a, cons
     constexpr int P = decltype(p_tag)::value;
     char* xs = smem + buf * T::STAGE + lds_wave_off;
     const int k0 = kt * BK * 2;
-    if constexpr (P < T::XI) buffer_load_lds16_aux<CLIPMI_STREAM_A_AUX>(xrs, xs + P * (NT * 16), row_off(xoff0, xo + P * xstep), k0);
-    else buffer_load_lds16_aux<CLIPMI_STREAM_W_AUX>(wrs, xs + T::XBYTES + (P - T::XI) * (NT * 16), row_off(woff0, wo + (P - T::XI) * wstep), k0);
+    if constexpr (P < T::XI) CLIPMI_BUFFER_LOAD_LDS16(xrs, xs + P * (NT * 16), row_off(xoff0, xo + P * xstep), k0);
+    else CLIPMI_BUFFER_LOAD_LDS16(wrs, xs + T::XBYTES + (P - T::XI) * (NT * 16), row_off(woff0, wo + (P - T::XI) * wstep), k0);
   };
   static_assert(T::XI + T::WI == 8, "eight DMA pieces per wave and stage");
   auto stage = [&](int buf, int kt, int xo, int wo) {
@@ -1024,14 +1005,7 @@ __global__ __launch_bounds__(512, 2) void gemm_stream_kernel(const KArgs a, cons
   int vb = blockIdx.x;
   int m0, n0;
   coords(vb, m0, n0);
-#ifdef CLIPMI_TUNING
-  // energy ablation (tuning build, knob 64): every tile reads the FIRST 256 activation rows -- the panel stays in L2, nothing of A
-  // comes from beyond it (results wrong)
-#define STREAM_A_ROW(m) ((a.knob & 64) ? 0 : (m))
-#else
-#define STREAM_A_ROW(m) (m)
-#endif
-  int txo = STREAM_A_ROW(m0) * (int)a.lda * 2, two = n0 * (int)a.ldw * 2;   // byte offsets of the tile's operand panels
+  int txo = m0 * (int)a.lda * 2, two = n0 * (int)a.ldw * 2;   // byte offsets of the tile's operand panels
   int first_buf = 0, par = 0;
   stage(first_buf, 0, txo, two);
   params(m0, n0, 0);
@@ -1045,7 +1019,8 @@ __global__ __launch_bounds__(512, 2) void gemm_stream_kernel(const KArgs a, cons
   // parts (stream_gelu_op / stream_store_slice above).  What the tile change still has to do per element is the fold and a conversion (3
   // instructions) instead of those and the activation (8.5): 4.6 -> 1.4 us per c_fc tile with nothing else running on the CU.
   constexpr bool GELU = EPI == CLIPMI_EPI_BIAS_QUICKGELU;
-  constexpr int HD = GELU ? 0 : CLIPMI_STREAM_HD, NHELD = TM - HD;
+  // bias / plain epilogues: HD = 2, the fewest slices the tile change can store -- K-steps 1 .. 6 carry the six held ones
+  constexpr int HD = GELU ? 0 : 2, NHELD = TM - HD;
   static_assert(GELU ? NHELD == 8 : (NHELD >= 1 && NHELD <= 6), "K-steps 1 .. 6 carry held slices; QuickGELU: two more behind them");
   const float neg_k = -GELU_K;
   float ga_l, ga_h, gb_l, gb_h;   // the two temporaries of each of the two registers the activation stream is working on
@@ -1086,8 +1061,7 @@ __global__ __launch_bounds__(512, 2) void gemm_stream_kernel(const KArgs a, cons
     const int col = hn0 + wave_n * 64 + lcol + p * 32;
     const int in_range = row_off(st_lane, tso + j * slice_bytes + p * 64);
     const int voff = col < a.N ? in_range : (int)0xFFFFFFF0;
-    if constexpr (CLIPMI_ABLATE & 1) asm volatile("" ::"v"(v), "v"(voff));   // (energy ablation: no output stores at all)
-    else __builtin_amdgcn_raw_buffer_store_b128(v, ors, voff, 0, CLIPMI_STORE_AUX);
+    __builtin_amdgcn_raw_buffer_store_b128(v, ors, voff, 0, 0);
   };
   constexpr int SPS = 2;   // stores per slice and wave
 
@@ -1126,7 +1100,7 @@ __global__ __launch_bounds__(512, 2) void gemm_stream_kernel(const KArgs a, cons
     constexpr int GSLOT = !GELU || KSI < 0 ? -1 : (KSI == STREAM_LAST ? 7 * 64 : KSI * 64);
     constexpr bool FIRSTK = decltype(first_tag)::value;   // the accumulators start at 0
     constexpr bool MORE = decltype(more_tag)::value;      // a stage is DMA'd during this K-step: K-step knext of the tile at (nxo, nwo)
-    constexpr int NST = (SLICE >= 0 && !(CLIPMI_ABLATE & 1)) ? SPS : 0;   // stores issued behind this K-step's DMA pieces
+    constexpr int NST = SLICE >= 0 ? SPS : 0;   // stores issued behind this K-step's DMA pieces
     const int buf = (first_buf + kt) & 1;
     const uint32_t sb = lds_base + (uint32_t)(buf * T::STAGE);
     uint32_t xa0 = sb + xo[0], xa1 = sb + xo[1], wa0 = sb + wo[0], wa1 = sb + wo[1];
@@ -1149,7 +1123,7 @@ __global__ __launch_bounds__(512, 2) void gemm_stream_kernel(const KArgs a, cons
           ds_read128<6144>(wf[3], wa);
         }
       }
-      if constexpr (MORE && !(CLIPMI_ABLATE & 2)) {
+      if constexpr (MORE) {
         if constexpr (P == 0) {
           stage_piece(std::integral_constant<int, 0>{}, buf ^ 1, knext, nxo, nwo);
           stage_piece(std::integral_constant<int, 1>{}, buf ^ 1, knext, nxo, nwo);
@@ -1177,62 +1151,58 @@ __global__ __launch_bounds__(512, 2) void gemm_stream_kernel(const KArgs a, cons
       __builtin_amdgcn_sched_barrier(0);
       // ---- compute part: registers only
       __builtin_amdgcn_s_setprio(1);
-      if constexpr (CLIPMI_ABLATE & 4) {
-        asm volatile("" :: "v"(wf[0]), "v"(wf[1]), "v"(wf[2]), "v"(wf[3]), "v"(xf[0]), "v"(xf[1]), "v"(xf[2]), "v"(xf[3]));
-      } else {
-        // MFMAs as asm with the accumulator TIED to the destination: left to the builtin, hipcc's allocator sends the results of
-        // the first k-half to 64 fresh registers and brings them back in the second (v_mfma v[192:195], .., v[12:15] ...), which
-        // this kernel does not have -- it spilled the held outputs to scratch.  Back-to-back MFMAs on different accumulators, or
-        // accumulating in place, need no wait states; nothing but MFMAs reads an accumulator before the tile's epilogue.
-        auto mfma = [&](auto m_tag) {
-          constexpr int M = decltype(m_tag)::value, j = M >> 2, i = M & 3;
-          mfma_tied<(FIRSTK && KS == 0)>(acc[i][JH * 4 + j], wf[i], xf[j]);
+      // MFMAs as asm with the accumulator TIED to the destination: left to the builtin, hipcc's allocator sends the results of
+      // the first k-half to 64 fresh registers and brings them back in the second (v_mfma v[192:195], .., v[12:15] ...), which
+      // this kernel does not have -- it spilled the held outputs to scratch.  Back-to-back MFMAs on different accumulators, or
+      // accumulating in place, need no wait states; nothing but MFMAs reads an accumulator before the tile's epilogue.
+      auto mfma = [&](auto m_tag) {
+        constexpr int M = decltype(m_tag)::value, j = M >> 2, i = M & 3;
+        mfma_tied<(FIRSTK && KS == 0)>(acc[i][JH * 4 + j], wf[i], xf[j]);
+      };
+      if constexpr (GSLOT >= 0) {
+        // instruction n of the stream: register pair n / 22, registers 2 k (even n) and 2 k + 1 (odd n) alternate, step (n % 22) / 2
+        auto uop = [&](auto n_tag) {
+          constexpr int N = decltype(n_tag)::value, G = N / GELU_GROUP_OPS, W = N % GELU_GROUP_OPS;   // group G = block pair G % 2 of slice G / 2
+          if constexpr (W >= 44) {
+            gelu_swap<W - 44>(held[G % 2][G / 2]);
+          } else {
+            constexpr int C = gelu_pair_seq(W % 22), E = 2 * (W / 22) + (C >> 4), Q = C & 15;
+            if constexpr (C >> 4) gelu_uop<Q, E>(held[G % 2][G / 2], gb_l, gb_h, neg_k);
+            else gelu_uop<Q, E>(held[G % 2][G / 2], ga_l, ga_h, neg_k);
+          }
         };
-        if constexpr (GSLOT >= 0) {
-          // instruction n of the stream: register pair n / 22, registers 2 k (even n) and 2 k + 1 (odd n) alternate, step (n % 22) / 2
-          auto uop = [&](auto n_tag) {
-            constexpr int N = decltype(n_tag)::value, G = N / GELU_GROUP_OPS, W = N % GELU_GROUP_OPS;   // group G = block pair G % 2 of slice G / 2
-            if constexpr (W >= 44) {
-              gelu_swap<W - 44>(held[G % 2][G / 2]);
-            } else {
-              constexpr int C = gelu_pair_seq(W % 22), E = 2 * (W / 22) + (C >> 4), Q = C & 15;
-              if constexpr (C >> 4) gelu_uop<Q, E>(held[G % 2][G / 2], gb_l, gb_h, neg_k);
-              else gelu_uop<Q, E>(held[G % 2][G / 2], ga_l, ga_h, neg_k);
-            }
-          };
-          auto group = [&](auto m_tag) {
-            constexpr int M = decltype(m_tag)::value;
-            mfma(m_tag);
-            constexpr int S0 = stream_gelu_op(GSLOT + P * 16 + M), S1 = stream_gelu_op(GSLOT + P * 16 + M + 1);
-            static_assert(S1 - S0 <= 2, "at most two instructions of the activation behind an MFMA");
-            if constexpr (S1 - S0 >= 1) uop(std::integral_constant<int, S0>{});
-            if constexpr (S1 - S0 == 2) uop(std::integral_constant<int, S0 + 1>{});
-          };
-          group(std::integral_constant<int, 0>{});  group(std::integral_constant<int, 1>{});  group(std::integral_constant<int, 2>{});
-          group(std::integral_constant<int, 3>{});  group(std::integral_constant<int, 4>{});  group(std::integral_constant<int, 5>{});
-          group(std::integral_constant<int, 6>{});  group(std::integral_constant<int, 7>{});  group(std::integral_constant<int, 8>{});
-          group(std::integral_constant<int, 9>{});  group(std::integral_constant<int, 10>{}); group(std::integral_constant<int, 11>{});
-          group(std::integral_constant<int, 12>{}); group(std::integral_constant<int, 13>{}); group(std::integral_constant<int, 14>{});
-          group(std::integral_constant<int, 15>{});
-        } else if constexpr (CLIPMI_STREAM_BIAS_SWAP && !GELU && KSI >= 0 && KSI < NHELD) {
-          // bias / plain epilogues: held slice KSI (stored in the next K-step) is interleaved for its 16-byte stores here -- one v_permlane16_swap
-          // per compute part, behind the eighth MFMA -- instead of in the tile change (pack_slice: 24 swaps of 18 cycles per wave and tile)
-          mfma(std::integral_constant<int, 0>{});  mfma(std::integral_constant<int, 1>{});  mfma(std::integral_constant<int, 2>{});
-          mfma(std::integral_constant<int, 3>{});  mfma(std::integral_constant<int, 4>{});  mfma(std::integral_constant<int, 5>{});
-          mfma(std::integral_constant<int, 6>{});  mfma(std::integral_constant<int, 7>{});
-          gelu_swap<(P & 1)>(held[P >> 1][KSI]);
-          mfma(std::integral_constant<int, 8>{});
-          mfma(std::integral_constant<int, 9>{});  mfma(std::integral_constant<int, 10>{}); mfma(std::integral_constant<int, 11>{});
-          mfma(std::integral_constant<int, 12>{}); mfma(std::integral_constant<int, 13>{}); mfma(std::integral_constant<int, 14>{});
-          mfma(std::integral_constant<int, 15>{});
-        } else {
-          mfma(std::integral_constant<int, 0>{});  mfma(std::integral_constant<int, 1>{});  mfma(std::integral_constant<int, 2>{});
-          mfma(std::integral_constant<int, 3>{});  mfma(std::integral_constant<int, 4>{});  mfma(std::integral_constant<int, 5>{});
-          mfma(std::integral_constant<int, 6>{});  mfma(std::integral_constant<int, 7>{});  mfma(std::integral_constant<int, 8>{});
-          mfma(std::integral_constant<int, 9>{});  mfma(std::integral_constant<int, 10>{}); mfma(std::integral_constant<int, 11>{});
-          mfma(std::integral_constant<int, 12>{}); mfma(std::integral_constant<int, 13>{}); mfma(std::integral_constant<int, 14>{});
-          mfma(std::integral_constant<int, 15>{});
-        }
+        auto group = [&](auto m_tag) {
+          constexpr int M = decltype(m_tag)::value;
+          mfma(m_tag);
+          constexpr int S0 = stream_gelu_op(GSLOT + P * 16 + M), S1 = stream_gelu_op(GSLOT + P * 16 + M + 1);
+          static_assert(S1 - S0 <= 2, "at most two instructions of the activation behind an MFMA");
+          if constexpr (S1 - S0 >= 1) uop(std::integral_constant<int, S0>{});
+          if constexpr (S1 - S0 == 2) uop(std::integral_constant<int, S0 + 1>{});
+        };
+        group(std::integral_constant<int, 0>{});  group(std::integral_constant<int, 1>{});  group(std::integral_constant<int, 2>{});
+        group(std::integral_constant<int, 3>{});  group(std::integral_constant<int, 4>{});  group(std::integral_constant<int, 5>{});
+        group(std::integral_constant<int, 6>{});  group(std::integral_constant<int, 7>{});  group(std::integral_constant<int, 8>{});
+        group(std::integral_constant<int, 9>{});  group(std::integral_constant<int, 10>{}); group(std::integral_constant<int, 11>{});
+        group(std::integral_constant<int, 12>{}); group(std::integral_constant<int, 13>{}); group(std::integral_constant<int, 14>{});
+        group(std::integral_constant<int, 15>{});
+      } else if constexpr (!GELU && KSI >= 0 && KSI < NHELD) {
+        // bias / plain epilogues: held slice KSI (stored in the next K-step) is interleaved for its 16-byte stores here -- one v_permlane16_swap
+        // per compute part, behind the eighth MFMA -- instead of in the tile change (pack_slice: 24 swaps of 18 cycles per wave and tile)
+        mfma(std::integral_constant<int, 0>{});  mfma(std::integral_constant<int, 1>{});  mfma(std::integral_constant<int, 2>{});
+        mfma(std::integral_constant<int, 3>{});  mfma(std::integral_constant<int, 4>{});  mfma(std::integral_constant<int, 5>{});
+        mfma(std::integral_constant<int, 6>{});  mfma(std::integral_constant<int, 7>{});
+        gelu_swap<(P & 1)>(held[P >> 1][KSI]);
+        mfma(std::integral_constant<int, 8>{});
+        mfma(std::integral_constant<int, 9>{});  mfma(std::integral_constant<int, 10>{}); mfma(std::integral_constant<int, 11>{});
+        mfma(std::integral_constant<int, 12>{}); mfma(std::integral_constant<int, 13>{}); mfma(std::integral_constant<int, 14>{});
+        mfma(std::integral_constant<int, 15>{});
+      } else {
+        mfma(std::integral_constant<int, 0>{});  mfma(std::integral_constant<int, 1>{});  mfma(std::integral_constant<int, 2>{});
+        mfma(std::integral_constant<int, 3>{});  mfma(std::integral_constant<int, 4>{});  mfma(std::integral_constant<int, 5>{});
+        mfma(std::integral_constant<int, 6>{});  mfma(std::integral_constant<int, 7>{});  mfma(std::integral_constant<int, 8>{});
+        mfma(std::integral_constant<int, 9>{});  mfma(std::integral_constant<int, 10>{}); mfma(std::integral_constant<int, 11>{});
+        mfma(std::integral_constant<int, 12>{}); mfma(std::integral_constant<int, 13>{}); mfma(std::integral_constant<int, 14>{});
+        mfma(std::integral_constant<int, 15>{});
       }
       __builtin_amdgcn_s_setprio(0);
       if constexpr (P == 3) {
@@ -1308,7 +1278,7 @@ __global__ __launch_bounds__(512, 2) void gemm_stream_kernel(const KArgs a, cons
     if (has_next) {
       vb = nvb;
       coords(vb, m0, n0);
-      txo = STREAM_A_ROW(m0) * (int)a.lda * 2;
+      txo = m0 * (int)a.lda * 2;
       two = n0 * (int)a.ldw * 2;
       params(m0, n0, par ^ 1);
     }
@@ -1351,9 +1321,6 @@ __global__ __launch_bounds__(512, 2) void gemm_stream_kernel(const KArgs a, cons
       for (int j = 0; j < (GELU ? 1 : TM); ++j) pr[j] = lnp[wave_m * T::WTM + j * 16 + er16];
 #pragma unroll
       for (int j = 0; j < TM; ++j) {
-#ifdef CLIPMI_TUNING
-        if (a.knob & 8) break;
-#endif
         if constexpr (GELU) {
           if (j + 1 < TM) pr[(j + 1) & 1] = lnp[wave_m * T::WTM + (j + 1) * 16 + er16];
         }
@@ -1369,7 +1336,7 @@ __global__ __launch_bounds__(512, 2) void gemm_stream_kernel(const KArgs a, cons
           }
         }
         u32x4 pk[2];
-        if (j >= HD && (GELU || CLIPMI_STREAM_BIAS_SWAP)) {   // held slices as they are: the next K loop interleaves them for the stores (QuickGELU: behind the activation)
+        if (j >= HD) {   // held slices as they are: the next K loop interleaves them for the stores (QuickGELU: behind the activation)
 #pragma unroll
           for (int p = 0; p < 2; ++p) {
             const u32x2 lo = __builtin_bit_cast(u32x2, cv[2 * p]), hi = __builtin_bit_cast(u32x2, cv[2 * p + 1]);
@@ -1408,7 +1375,7 @@ __global__ __launch_bounds__(512, 2) void gemm_stream_kernel(const KArgs a, cons
       pack_slice(cvl, pkl);
       held[0][j] = pkl[0];
       held[1][j] = pkl[1];
-    } else if constexpr (CLIPMI_STREAM_BIAS_SWAP) {
+    } else {
       gelu_swap<0>(held[0][j]); gelu_swap<1>(held[0][j]);
       gelu_swap<0>(held[1][j]); gelu_swap<1>(held[1][j]);
     }
@@ -1416,8 +1383,6 @@ __global__ __launch_bounds__(512, 2) void gemm_stream_kernel(const KArgs a, cons
     store_piece(HD + j, 1, held[1][j]);
   }
 }
-
-#undef STREAM_A_ROW
 
 template <int EPI>
 int launch_stream(KArgs k, float2* ln_rows, hipStream_t s) {
@@ -1612,7 +1577,7 @@ __global__ __launch_bounds__(T::NT, T::OCC) void gemm_pp_kernel(const KArgs a) {
           ds_read128<6144>(wf[3], wa);
         }
       }
-      if constexpr (MORE && P < 3 && !(CLIPMI_ABLATE & 2)) {
+      if constexpr (MORE && P < 3) {
         stage_piece(std::integral_constant<int, P * PPP + 0>{}, buf ^ 1, kt + 1);
         stage_piece(std::integral_constant<int, P * PPP + 1>{}, buf ^ 1, kt + 1);
         stage_piece(std::integral_constant<int, P * PPP + 2>{}, buf ^ 1, kt + 1);
@@ -1632,10 +1597,7 @@ __global__ __launch_bounds__(T::NT, T::OCC) void gemm_pp_kernel(const KArgs a) {
       for (int j = 0; j < H; ++j) {
 #pragma unroll
         for (int i = 0; i < TN; ++i) {
-          if constexpr (CLIPMI_ABLATE & 4) {   // (energy ablation: the loop without its MFMAs; the accumulators are only defined)
-            if constexpr (FIRSTK && KS == 0) asm volatile("" : "=v"(acc[i][JH * H + j]) : "v"(wf[i]), "v"(xf[j]));
-            else asm volatile("" : "+v"(acc[i][JH * H + j]) : "v"(wf[i]), "v"(xf[j]));
-          } else if constexpr (FIRSTK && KS == 0)
+          if constexpr (FIRSTK && KS == 0)
             asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, 0" : "=&v"(acc[i][JH * H + j]) : "v"(wf[i]), "v"(xf[j]));
           else
             asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(acc[i][JH * H + j]) : "v"(wf[i]), "v"(xf[j]));
@@ -1990,7 +1952,6 @@ int launch_gemm(const GemmArgs& a, hipStream_t s) {
   CLIPMI_REQUIRE(a.ln_row_stride >= 1 && a.ln_plane >= 0 && a.ln_plane < (1ll << 31), CLIPMI_ERR_ARG, "gemm: bad LayerNorm statistics stride");
 #ifdef CLIPMI_TUNING
   k.stamps = g_tuning_stamps.load(std::memory_order_relaxed);   // clipmi_tuning_set_stamps (tools/gemm_stamps.py), tuning build only
-  k.knob = g_tuning_knob.load(std::memory_order_relaxed);
 #endif
   CLIPMI_REQUIRE(!a.ln_stats || (a.ln_g && a.ln_dim > 0 && a.ln_parts >= 1 && a.ln_parts <= LN_MAX_PARTS &&
                                  (a.epilogue == CLIPMI_EPI_BIAS || a.epilogue == CLIPMI_EPI_BIAS_QUICKGELU)),

@@ -6,16 +6,6 @@
 
 #include "common.h"
 
-#ifndef CLIPMI_STORE_AUX
-#define CLIPMI_STORE_AUX 0   // cache policy bits of the big output stores (2 = nt); build-time A/B: make libclipmi_gemmnt.so
-#endif
-
-// CLIPMI_ABLATE (build-time, diagnostic builds only: results are wrong with any bit set): 2 no LDS-DMA pieces inside the K loop of
-// the streamed-epilogue kernel, 4 no MFMAs, 16 no fragment reads (the registers are left as they are)
-#ifndef CLIPMI_ABLATE
-#define CLIPMI_ABLATE 0
-#endif
-
 namespace clipmi {
 namespace gemm {
 
@@ -40,7 +30,6 @@ struct KArgs {
   half_t* x16; float* stats_out;
 #ifdef CLIPMI_TUNING
   long long* stamps;   // diagnostic build only (make tuning, tools/gemm_stamps.py): per-workgroup s_memrealtime stamps
-  int knob;            // diagnostic build only: ablation bits of the streamed-epilogue kernel (timing only, results wrong)
 #endif
 };
 
@@ -94,8 +83,7 @@ template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_
 // that a generic lambda names only as an asm operand)
 template <int OFF>
 __device__ __forceinline__ void ds_read128(f16x8& dst, uint32_t addr) {
-  if constexpr (CLIPMI_ABLATE & 16) asm volatile("" : "=v"(dst) : "v"(addr));
-  else asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF));
+  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF));
 }
 template <int N>
 __device__ __forceinline__ void lgkm_wait1(f16x8& a) { asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(a) : "n"(N)); }

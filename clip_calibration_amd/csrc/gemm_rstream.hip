@@ -1,11 +1,6 @@
 // Persistent row-range kernel of the fp16-stream residual GEMMs (out-proj, c_proj; variant 16 of launch_gemm, gemm.hip).
 #include "gemm_common.h"
 
-// build-time A/B of the cache policy of the ACTIVATION operand's LDS-DMA (out-proj reads the attention rows exactly once: profiles/r06_attn_outproj_pair.txt)
-#ifndef CLIPMI_RSTREAM_A_AUX
-#define CLIPMI_RSTREAM_A_AUX 0
-#endif
-
 namespace clipmi {
 namespace gemm {
 namespace {
@@ -100,7 +95,7 @@ __global__ __launch_bounds__(512, 2) void gemm_rstream_kernel(const KArgs a, con
     constexpr int P = decltype(p_tag)::value;
     if constexpr (P < 5) {
       if (64 * P + wave * 8 < 32 * nbx)   // uniform
-        buffer_load_lds16_aux<CLIPMI_RSTREAM_A_AUX>(xrs, smem + buf * R::STAGE + P * 8192 + wave * 1024, row_off(xoff0, P * xstep), kt * BK * 2);
+        CLIPMI_BUFFER_LOAD_LDS16(xrs, smem + buf * R::STAGE + P * 8192 + wave * 1024, row_off(xoff0, P * xstep), kt * BK * 2);
     } else {
       CLIPMI_BUFFER_LOAD_LDS16(wrs, smem + buf * R::STAGE + R::XB + (P - 5) * 8192 + wave * 1024, row_off(woff0, (P - 5) * wstep), kt * BK * 2);
     }
@@ -355,8 +350,8 @@ __global__ __launch_bounds__(512, 2) void gemm_rstream_kernel(const KArgs a, con
         }
         u32x4 o[2];
         pack_slice(cv, o);
-        __builtin_amdgcn_raw_buffer_store_b128(o[0], ors, slice_voff(cnb, b, 0), 0, CLIPMI_STORE_AUX);
-        __builtin_amdgcn_raw_buffer_store_b128(o[1], ors, slice_voff(cnb, b, 1), 0, CLIPMI_STORE_AUX);
+        __builtin_amdgcn_raw_buffer_store_b128(o[0], ors, slice_voff(cnb, b, 0), 0, 0);
+        __builtin_amdgcn_raw_buffer_store_b128(o[1], ors, slice_voff(cnb, b, 1), 0, 0);
       } else {
         const u32x4 z = u32x4{0u, 0u, 0u, 0u};
         __builtin_amdgcn_raw_buffer_store_b128(z, ors, (int)0xFFFFFFF0, 0, 0);   // out of range: dropped

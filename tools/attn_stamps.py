@@ -2,7 +2,7 @@
 """Diagnostic (tuning build): where an item of the vision attention kernel spends its time.
 query wave: 0 arrive at the barrier, 1 past it, 4 S of key tiles 0-3 done, 5 their softmax + P.V done, 6 S of key tiles 4-6 done, 2 their
 softmax + P.V done, 3 outputs stored;  loader (wave 7): 0 arrive at its wait, 1 operands landed (vmcnt 0), 2 past the barrier, 3 next
-item's DMA issued.  CLIPMI_LIBRARY = libclipmi_tuning.so or one of the `make attn_ablate` builds (tools/attn_ablate.sh)."""
+item's DMA issued.  CLIPMI_LIBRARY = libclipmi_tuning.so."""
 import ctypes, os, sys, numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from clip_calibration_amd import _lib, ops
