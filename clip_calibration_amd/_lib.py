@@ -66,6 +66,15 @@ class ProcalModel(C.Structure):
                 ("scale", (C.c_double * 2) * 2), ("norm", C.c_double * 2), ("ratio", C.c_double)]
 
 
+ISOTONIC_MAX_TABLES = 8
+
+
+class IsotonicModel(C.Structure):
+    """clipmi_isotonic_model: the packed threshold tables and the inner proximity-bin edges (include/clipmi.h)."""
+    _fields_ = [("table", C.c_void_p), ("n_tables", C.c_int32), ("offset", C.c_int32 * (ISOTONIC_MAX_TABLES + 1)),
+                ("edges", C.c_double * (ISOTONIC_MAX_TABLES - 1))]
+
+
 class PromptHook(C.Structure):
     _fields_ = [("n_ctx", C.c_int32), ("n_deep", C.c_int32), ("shallow", C.c_void_p), ("deep", C.c_void_p)]
 
@@ -123,6 +132,10 @@ _SIGNATURES = {
     "clipmi_ece_accumulate": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp]),
     "clipmi_procal_kde": (_i, [C.POINTER(ProcalModel), _vp, _vp, _vp, _i, _vp]),
     "clipmi_procal_rows": (_i, [C.POINTER(ProcalModel), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
+    "clipmi_isotonic_pack": (_i, [_vp, _vp, _vp, _i, _vp]),
+    "clipmi_isotonic_rows": (_i, [C.POINTER(IsotonicModel), _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp]),
+    "clipmi_isotonic_keys": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
+    "clipmi_isotonic_gap_stats": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp]),
     "clipmi_create": (_i, [C.POINTER(Geometry), C.POINTER(_vp)]),
     "clipmi_destroy": (_i, [_vp]),
     "clipmi_set_vision_weights": (_i, [_vp, C.POINTER(VisionWeights)]),

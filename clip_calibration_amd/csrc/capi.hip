@@ -572,6 +572,25 @@ int clipmi_procal_rows(const clipmi_procal_model* model, const float* logits, co
   return launch_procal_rows(model, logits, dac_conf, proximity, probs, conf, pred, cstar, n, C, (hipStream_t)stream);
 }
 
+int clipmi_isotonic_pack(const double* x, const double* y, const int32_t* counts, int n_tables, double* packed) {
+  return isotonic_pack(x, y, counts, n_tables, packed);
+}
+
+int clipmi_isotonic_rows(const clipmi_isotonic_model* model, const float* logits, const float* dac_conf, const float* proximity,
+                         int from_probs, float* probs, float* xs, float* conf, int32_t* pred, int n, int C, clipmi_stream_t stream) {
+  return launch_isotonic_rows(model, logits, dac_conf, proximity, from_probs, probs, xs, conf, pred, n, C, (hipStream_t)stream);
+}
+
+int clipmi_isotonic_keys(const float* logits, const int64_t* labels, float* keys, int n, int C, int from_probs, clipmi_stream_t stream) {
+  return launch_isotonic_keys(logits, labels, keys, n, C, from_probs, (hipStream_t)stream);
+}
+
+int clipmi_isotonic_gap_stats(const float* logits, const int64_t* labels, const int32_t* bin, const float* keys,
+                              const int32_t* key_offset, int n_bins, int32_t* stats, int32_t* status, int n, int C, int from_probs,
+                              clipmi_stream_t stream) {
+  return launch_isotonic_gap_stats(logits, labels, bin, keys, key_offset, n_bins, stats, status, n, C, from_probs, (hipStream_t)stream);
+}
+
 int clipmi_ece_accumulate(const float* conf, const int32_t* pred, const int64_t* labels, int n, double* bins, int n_bins,
                           clipmi_stream_t stream) {
   return launch_ece_accumulate(conf, pred, labels, n, bins, n_bins, (hipStream_t)stream);

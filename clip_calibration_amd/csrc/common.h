@@ -296,6 +296,12 @@ int launch_knn(const float* q, const float* refs, float* out, int Nq, int Nr, in
 int launch_procal_kde(const clipmi_procal_model* model, const float* conf, const float* proximity, float* cstar, int n, hipStream_t s);
 int launch_procal_rows(const clipmi_procal_model* model, const float* logits, const float* dac_conf, const float* proximity, float* probs,
                        float* conf, int32_t* pred, float* cstar, int n, int C, hipStream_t s);
+int isotonic_pack(const double* x, const double* y, const int32_t* counts, int n_tables, double* packed);
+int launch_isotonic_rows(const clipmi_isotonic_model* model, const float* logits, const float* dac_conf, const float* proximity,
+                         int from_probs, float* probs, float* xs, float* conf, int32_t* pred, int n, int C, hipStream_t s);
+int launch_isotonic_keys(const float* logits, const int64_t* labels, float* keys, int n, int C, int from_probs, hipStream_t s);
+int launch_isotonic_gap_stats(const float* logits, const int64_t* labels, const int32_t* bin, const float* keys, const int32_t* key_offset,
+                              int n_bins, int32_t* stats, int32_t* status, int n, int C, int from_probs, hipStream_t s);
 
 static inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 static inline size_t align256(size_t x) { return (x + 255) & ~size_t(255); }

@@ -7,6 +7,7 @@ preparation: fold_layernorm_linear).
 from __future__ import annotations
 
 import collections
+import ctypes
 from typing import Optional, Tuple
 
 import torch
@@ -355,6 +356,70 @@ def procal_rows(model: "_lib.ProcalModel", logits: torch.Tensor, proximity: torc
                                  conf.data_ptr(), pred.data_ptr(), None if cstar is None else cstar.data_ptr(), N, Cn, _stream()),
           "clipmi_procal_rows")
     return probs, conf, pred, cstar
+
+
+def isotonic_rows(model: "_lib.IsotonicModel", logits: torch.Tensor, proximity: Optional[torch.Tensor] = None,
+                  dac_conf: Optional[torch.Tensor] = None, want_probs: bool = False, want_x: bool = False, from_probs: bool = False):
+    """softmax(DAC(logits)) -> second softmax -> isotonic table of the row's proximity bin -> the evaluator's top-1
+    (vl_calibrator.py:83-109 on 'bin_based' / 'multi_isotonic_regression', vl_evaluator.py:68,83), one launch: returns (calibrated rows
+    fp32 [N,C] or None, conf fp32 [N], pred int32 [N], x fp32 [N,C] or None); logits untouched."""
+    logits = _dev(logits, "logits", (torch.float32,))
+    if logits.dim() != 2:
+        raise ValueError(f"isotonic_rows: logits {tuple(logits.shape)} must be [N, C]")
+    N, Cn = logits.shape
+    proximity, pp = _opt(proximity, "proximity", (torch.float32,))
+    if proximity is not None and (proximity.dim() != 1 or proximity.shape[0] != N):
+        raise ValueError(f"isotonic_rows: logits {tuple(logits.shape)} need a proximity of one entry per row, got {tuple(proximity.shape)}")
+    dac_conf, pd = _opt(dac_conf, "dac_conf", (torch.float32,))
+    if dac_conf is not None and dac_conf.numel() != Cn:
+        raise ValueError("isotonic_rows: dac_conf must have one entry per class")
+    probs = torch.empty_like(logits) if want_probs else None
+    xs = torch.empty_like(logits) if want_x else None
+    conf = torch.empty(N, dtype=torch.float32, device=logits.device)
+    pred = torch.empty(N, dtype=torch.int32, device=logits.device)
+    check(lib.clipmi_isotonic_rows(model, logits.data_ptr(), pd, pp, int(from_probs), None if probs is None else probs.data_ptr(),
+                                   None if xs is None else xs.data_ptr(), conf.data_ptr(), pred.data_ptr(), N, Cn, _stream()),
+          "clipmi_isotonic_rows")
+    return probs, conf, pred, xs
+
+
+def isotonic_keys(logits: torch.Tensor, labels: torch.Tensor, from_probs: bool = False) -> torch.Tensor:
+    """The positive keys of the isotonic fit: x[i, labels[i]] fp32 [N] (NaN where a label is outside the classes)."""
+    logits = _dev(logits, "logits", (torch.float32,))
+    labels = _dev(labels, "labels", (torch.int64,))
+    if logits.dim() != 2 or labels.shape != (logits.shape[0],):
+        raise ValueError(f"isotonic_keys: logits {tuple(logits.shape)} need one label per row, got {tuple(labels.shape)}")
+    keys = torch.empty(logits.shape[0], dtype=torch.float32, device=logits.device)
+    check(lib.clipmi_isotonic_keys(logits.data_ptr(), labels.data_ptr(), keys.data_ptr(), logits.shape[0], logits.shape[1],
+                                   int(from_probs), _stream()), "clipmi_isotonic_keys")
+    return keys
+
+
+def isotonic_gap_stats(logits: torch.Tensor, labels: torch.Tensor, keys: torch.Tensor, key_offset, bin_index: Optional[torch.Tensor] = None,
+                       from_probs: bool = False):
+    """The per-gap statistics of the isotonic fit (include/clipmi.h, clipmi_isotonic_gap_stats): ``keys`` fp32 holds each bin's sorted
+    distinct positive keys, ``key_offset`` (host ints, n_bins + 1) where each bin's start.  Returns (stats int32 [3, total], status
+    int32 [1]), both on the device."""
+    logits = _dev(logits, "logits", (torch.float32,))
+    labels = _dev(labels, "labels", (torch.int64,))
+    keys = _dev(keys, "keys", (torch.float32,))
+    if logits.dim() != 2 or labels.shape != (logits.shape[0],):
+        raise ValueError(f"isotonic_gap_stats: logits {tuple(logits.shape)} need one label per row, got {tuple(labels.shape)}")
+    bin_index, pb = _opt(bin_index, "bin_index", (torch.int32,))
+    if bin_index is not None and bin_index.shape != (logits.shape[0],):
+        raise ValueError("isotonic_gap_stats: bin_index must have one entry per row")
+    off = [int(o) for o in key_offset]
+    n_bins = len(off) - 1
+    if n_bins < 1 or off[-1] != keys.numel():
+        raise ValueError(f"isotonic_gap_stats: key_offset {off} does not describe {keys.numel()} keys")
+    total = 3 * off[-1] + n_bins
+    stats = torch.empty(3, total, dtype=torch.int32, device=logits.device)
+    status = torch.empty(1, dtype=torch.int32, device=logits.device)
+    c_off = (ctypes.c_int32 * len(off))(*off)
+    check(lib.clipmi_isotonic_gap_stats(logits.data_ptr(), labels.data_ptr(), pb, keys.data_ptr(), c_off, n_bins, stats.data_ptr(),
+                                        status.data_ptr(), logits.shape[0], logits.shape[1], int(from_probs), _stream()),
+          "clipmi_isotonic_gap_stats")
+    return stats, status
 
 
 # ---- CoCoOp glue (cocoop.py:154-199) -------------------------------------------------------------------------------

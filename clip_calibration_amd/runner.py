@@ -141,13 +141,14 @@ def test(infer: Callable, loader: Iterable[Tuple[torch.Tensor, torch.Tensor]], v
     """VLBaseLearner.test (base_learner.py:59-152): inference over the split, DAC, softmax top-1, proximity of every test
     image to the base-class val images (exp(-mean K-NN distance), :121-137), then the evaluator's metrics.  Under
     torch.distributed each rank passes its own shard of the loader; samples are gathered before the sample-level metrics.
-    With ProCal on (``calibrator.procal_active``) the evaluator sees the top-1 of the ProCal-calibrated rows instead: the
-    (DAC-scaled) logits of the split are kept on the device until the proximity is known, then one ``clipmi_procal_rows`` launch
-    per rank -- before the gather, as proximity is per sample -- yields (conf', pred')."""
+    With a base calibrator on (``calibrator.row_calibrator_device()``: ProCal, multi-class isotonic regression or Bin-Mean-Shift) the
+    evaluator sees the top-1 of the calibrated rows instead: the (DAC-scaled) logits of the split are kept on the device until the
+    proximity is known, then one ``clipmi_procal_rows`` / ``clipmi_isotonic_rows`` launch per rank -- before the gather, as proximity
+    is per sample -- yields (conf', pred')."""
     ev = DeviceCalibrationEvaluator(ece_bins, device=device, keep_samples=True, piece_bins=piece_bins)
     dac = calibrator.class_confidence_device(device) if calibrator is not None else None
-    procal = calibrator.procal_device() if calibrator is not None else None
-    if procal is not None and val_dict is None:
+    procal, needs_proximity = calibrator.row_calibrator_device() if calibrator is not None else (None, False)
+    if needs_proximity and val_dict is None:
         raise ValueError("test: ProCal needs val_dict for the test-image proximity")
     feats, kept_logits, kept_labels = [], [], []
     for image, label in device_batches(loader, device):

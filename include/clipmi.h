@@ -333,6 +333,53 @@ int clipmi_procal_kde(const clipmi_procal_model* model, const float* conf, const
 int clipmi_procal_rows(const clipmi_procal_model* model, const float* logits, const float* dac_conf, const float* proximity,
                        float* probs, float* conf, int32_t* pred, float* cstar, int n, int C, clipmi_stream_t stream);
 
+/* Multi-class isotonic calibration and Bin-Mean-Shift (trainers/calibration/multi_isotonic_regression.py,
+ * multi_proximity_isotonic.py:130-247; vl_calibrator.py:121-147 on base_calibration_mode "bin_based" with base_bin_calibrator_name
+ * "multi_isotonic_regression").  Per row: p = softmax(DAC(logits)) in clipmi_softmax_rows' lane-strided form, x = exp(p) / sum_j exp(p_j)
+ * in fp32 (a second softmax, of the probabilities), out = g(x) + 1e-9 x with g the fitted isotonic function: linear interpolation
+ * through the thresholds, clipped outside them.  Rows are not renormalised.  from_probs != 0: the input rows already hold p (the
+ * reference's numpy interface takes probabilities); the first softmax is skipped and a DAC factor is refused.
+ * These exports are additive: the ABI version does not change with them. */
+#define CLIPMI_ISOTONIC_MAX_TABLES 8
+
+/* Host only: check thresholds (finite, X strictly ascending inside a table) and pack them as the kernel reads them.  x, y: the
+ * n_tables tables one after the other, counts[t] >= 1 thresholds each; packed receives 3 * sum(counts) fp64: per table X | Y | slope
+ * (slope[i] = (Y[i+1] - Y[i]) / (X[i+1] - X[i]) as numpy.interp forms it, 0 for the last).  Upload `packed` as it is. */
+int clipmi_isotonic_pack(const double* x, const double* y, const int32_t* counts, int n_tables, double* packed);
+
+/* Host struct.  table: device fp64, the output of clipmi_isotonic_pack, 8-byte aligned; table t owns thresholds offset[t] ..
+ * offset[t+1] (offset[0] = 0, every table >= 1 threshold).  A row's table is the number of edges[e] <= proximity (e < n_tables - 1;
+ * np.searchsorted(bin_edges[1:-1], proximity, side="right")); the edges are finite and ascending. */
+typedef struct clipmi_isotonic_model {
+  const double* table;
+  int32_t n_tables;
+  int32_t offset[CLIPMI_ISOTONIC_MAX_TABLES + 1];
+  double edges[CLIPMI_ISOTONIC_MAX_TABLES - 1];
+} clipmi_isotonic_model;
+
+/* One launch, no host synchronisation.  logits fp32 [n, C] (not modified), dac_conf fp32 [C] or NULL, proximity fp32 [n] (required
+ * when n_tables > 1, else optional and ignored).  Outputs: pred[i] = argmax of the calibrated row (int32, lowest index among equal
+ * maxima), conf[i] the value there (both required); probs fp32 [n, C] the calibrated rows and xs fp32 [n, C] the x values, both
+ * optional (NULL).  n == 0: CLIPMI_OK. */
+int clipmi_isotonic_rows(const clipmi_isotonic_model* model, const float* logits, const float* dac_conf, const float* proximity,
+                         int from_probs, float* probs, float* xs, float* conf, int32_t* pred, int n, int C, clipmi_stream_t stream);
+
+/* The fit's two device passes.  An isotonic fit to 0/1 targets is determined by the positive keys (x at the label) and per-gap
+ * statistics of the zeros; the host pools the resulting <= 2 m + 1 weighted points per bin in float64.
+ * clipmi_isotonic_keys: keys[i] = x[i, labels[i]] (NaN when the label is outside [0, C)).  labels int64 [n], keys fp32 [n].
+ * clipmi_isotonic_gap_stats: keys fp32 (device) holds, bin after bin, each bin's sorted distinct positive keys; key_offset int32
+ * [n_bins + 1] (HOST): bin b owns keys[key_offset[b] .. key_offset[b+1]), m_b >= 1 of them.  bin int32 [n] (device) the bin of
+ * each row, NULL when n_bins == 1.  stats int32 [3][total] (device), total = 3 * key_offset[n_bins] + n_bins: plane 0 counts, plane 1
+ * the smallest and plane 2 the largest fp32 bit pattern seen; bin b's slots start at 3 * key_offset[b] + b:
+ *   slot g (0 <= g <= m_b): the zeros strictly between key g-1 and key g (count, min, max);  slot m_b + 1 + k: the zeros equal to
+ *   key k (count);  slot 2 m_b + 1 + k: the positives equal to key k (count).
+ * status int32 [1] (device): 0, or bits 1 (a positive x is not among the keys), 2 (an x outside (0, 1]: non-finite input),
+ * 4 (a bin index outside [0, n_bins)).  Both are initialised by the call.  n * C < 2^31. */
+int clipmi_isotonic_keys(const float* logits, const int64_t* labels, float* keys, int n, int C, int from_probs, clipmi_stream_t stream);
+int clipmi_isotonic_gap_stats(const float* logits, const int64_t* labels, const int32_t* bin, const float* keys,
+                              const int32_t* key_offset, int n_bins, int32_t* stats, int32_t* status, int n, int C, int from_probs,
+                              clipmi_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------------
  * Multi-GPU exchange: one process per GPU, the image batch sharded over the ranks, weights and text
  * features replicated and resident; per step ONE all-gather of the per-GPU L2-normalised image embeddings (fp16 [B/G,E])
