@@ -140,6 +140,7 @@ int launch_im2col3x3_nchw(const void* image, int dtype, half_t* col, int B, int 
   CLIPMI_REQUIRE(image && col, CLIPMI_ERR_ARG, "im2col3x3_nchw: null pointer");
   CLIPMI_REQUIRE(B > 0 && Cin > 0 && H > 0 && W > 0 && (stride == 1 || stride == 2) && Kpad >= Cin * 9 && Kpad % 64 == 0, CLIPMI_ERR_SHAPE,
                  "im2col3x3_nchw: B=%d Cin=%d H=%d W=%d stride=%d Kpad=%d", B, Cin, H, W, stride, Kpad);
+  CLIPMI_REQUIRE((uintptr_t)col % 16 == 0, CLIPMI_ERR_ARG, "im2col3x3_nchw: col must be 16-byte aligned");
   const int Ho = (H + 2 - 3) / stride + 1, Wo = (W + 2 - 3) / stride + 1;
   const int64_t total = (int64_t)B * Ho * Wo * (Kpad / 8);
   const unsigned grid = (unsigned)((total + 255) / 256);

@@ -236,9 +236,10 @@ int clipmi_softmax_rows(const float* logits, const float* dac_conf, float* probs
 /* ModifiedResNet image tower (clip/model.py:10-150) -- SURVEY f-4.  Activations NHWC fp16; a 1x1 convolution is
  * clipmi_gemm_f16 on the [B*H*W, C] rows with the folded BatchNorm as bias (CLIPMI_EPI_BIAS_RELU / _RESIDUAL16_RELU).
  *  clipmi_im2col3x3_nchw   stem conv1 (clip/model.py:106, stride 2, pad 1) from the NCHW image (fp32|fp16):
- *                          col fp16 [B*Ho*Wo, Kpad], column c*9 + ky*3 + kx, zero padded (Kpad % 64 == 0)
+ *                          col fp16 [B*Ho*Wo, Kpad], column c*9 + ky*3 + kx, zero padded (Kpad % 64 == 0); col 16-byte aligned
  *  clipmi_im2col3x3_nhwc   every other 3x3 convolution (stride 1, pad 1; clip/model.py:20,108,110):
- *                          col[(b,y,x), (ky*3+kx)*C + c] = x[b, y+ky-1, x+kx-1, c]; C % 8 == 0
+ *                          col[(b,y,x), (ky*3+kx)*C + c] = x[b, y+ky-1, x+kx-1, c]; C % 8 == 0, Kpad % 64 == 0, x and col
+ *                          16-byte aligned (CLIPMI_ERR_ARG otherwise: both are moved 16 bytes at a time)
  *  clipmi_avgpool_nhwc     nn.AvgPool2d(k) (clip/model.py:23,33,112): x [B,H,W,C] -> y [B,H/k,W/k,C]
  *  clipmi_attnpool_tokens  AttentionPool2d token build (clip/model.py:69-71): tokens fp16 [B, HW+1, C] = [mean | x] + pos (fp32 [HW+1, C])
  *  clipmi_attnpool         its attention with the mean token as the only query (clip/model.py:72-90): q fp16 [B,C] (projected,
