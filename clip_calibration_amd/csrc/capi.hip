@@ -460,6 +460,10 @@ int clipmi_attention(const void* qkv, void* out, int N, int L, int H, int causal
   return launch_attention((const half_t*)qkv, (half_t*)out, N, L, H, causal, (hipStream_t)stream);
 }
 
+int clipmi_attention_cls(const void* qkv, void* out, int N, int L, int H, clipmi_stream_t stream) {
+  return launch_attention_cls((const half_t*)qkv, (half_t*)out, N, L, H, (hipStream_t)stream);
+}
+
 int clipmi_patchify(const void* image, int image_dtype, void* col, int B, int R, int P, int Kpad, clipmi_stream_t stream) {
   return launch_patchify(image, image_dtype, (half_t*)col, B, R, P, Kpad, (hipStream_t)stream);
 }

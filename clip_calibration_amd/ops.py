@@ -192,6 +192,23 @@ def attention(qkv: torch.Tensor, n_seq: int, seq_len: int, n_head: int, causal: 
     return out
 
 
+def attention_cls(qkv: torch.Tensor, n_seq: int, seq_len: int, n_head: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """qkv fp16 [n_seq*seq_len, 3*64*n_head] -> fp16 [n_seq*seq_len, 64*n_head] of which only row 0 of every sequence (the class
+    token's, never masked) is written; ``out`` (same shape) keeps its other rows, a fresh one has them zero."""
+    qkv = _dev(qkv, "qkv", (torch.float16,))
+    D = 64 * n_head
+    if qkv.shape != (n_seq * seq_len, 3 * D):
+        raise ValueError(f"attention_cls: qkv shape {tuple(qkv.shape)} != {(n_seq * seq_len, 3 * D)}")
+    if out is None:
+        out = torch.zeros(n_seq * seq_len, D, dtype=torch.float16, device=qkv.device)
+    else:
+        out = _dev(out, "out", (torch.float16,))
+        if out.shape != (n_seq * seq_len, D):
+            raise ValueError(f"attention_cls: out shape {tuple(out.shape)} != {(n_seq * seq_len, D)}")
+    check(lib.clipmi_attention_cls(qkv.data_ptr(), out.data_ptr(), n_seq, seq_len, n_head, _stream()), "clipmi_attention_cls")
+    return out
+
+
 def patchify(image: torch.Tensor, patch: int, kpad: Optional[int] = None) -> torch.Tensor:
     image = _dev(image, "image", (torch.float16, torch.float32))
     B, ch, R, R2 = image.shape

@@ -151,8 +151,14 @@ int clipmi_layernorm(const void* x, int x_dtype, int64_t in_stride, const int32_
 /* nn.MultiheadAttention core after the packed in-projection (clip/model.py:181-183; SURVEY a-5a):
  * qkv fp16 [N*L, 3*D] (q | k | v, head h at columns h*64..h*64+63 of each third), out fp16 [N*L, D] =
  * merge_heads(softmax(q k^T / 8 + mask) v).  head_dim is 64 (D == 64*H).  causal != 0 applies the text
- * tower's mask (clip/model.py:585-591). */
+ * tower's mask (clip/model.py:585-591).  qkv 16-byte aligned, out 8-byte aligned; N == 0 is OK (nothing is read or written). */
 int clipmi_attention(const void* qkv, void* out, int N, int L, int H, int causal, clipmi_stream_t stream);
+
+/* The same attention for ONE query per sequence, token 0 (the class token of the image tower's last block, whose other rows never reach
+ * ln_post: clip/model.py:419), never masked: qkv fp16 [N*L, 3*64*H] packed q | k | v as above; out fp16 [N*L, 64*H], of which only row n*L
+ * of every sequence n is written -- every other row is left as it was.  fp32 scores, probabilities and accumulation, one fp16 rounding of
+ * the output.  Both pointers 16-byte aligned; N == 0 is OK (nothing is read or written). */
+int clipmi_attention_cls(const void* qkv, void* out, int N, int L, int H, clipmi_stream_t stream);
 
 /* image.type(dtype) + the im2col half of conv1 (clip/model.py:598,395-397): image [B,3,R,R] (fp32 or fp16,
  * NCHW) -> col fp16 [B*(R/P)^2, Kpad], column c*P*P + ky*P + kx, zero padded up to Kpad (a multiple of 64). */
