@@ -5,7 +5,9 @@
 // 256-B row segments in, padded rows out -> conflict-free column reads).  Thread t accumulates sum_e (q - r)^2 -- the
 // difference form, like the reference, no |q|^2+|r|^2-2qr cancellation -- for reference row (t & 63) against queries
 // 2*(t >> 6) and 2*(t >> 6) + 1, keeps a sorted K-list per query in registers, and the 64 lists of a query are merged
-// through LDS at the end.  fp32 VALU bound: 3 * Nq * Nr * E flop; the reference set is re-read from L2 once per 8 queries.
+// through LDS at the end.  A NaN distance (a reference or query row with a NaN, e.g. a zero-norm image after normalisation)
+// enters the lists as +inf, so such a row is never a neighbour -- torch.topk(largest=False) of the reference sorts NaN last.
+// fp32 VALU bound: 3 * Nq * Nr * E flop; the reference set is re-read from L2 once per 8 queries.
 #include "common.h"
 
 namespace clipmi {
@@ -53,7 +55,7 @@ __global__ __launch_bounds__(256) void knn_kernel(const float* __restrict__ q, c
       }
     }
     if (r0 + r < Nr) {   // sorted insertion (ascending), K <= KMAX
-      float v0 = d0, v1 = d1;
+      float v0 = d0 == d0 ? d0 : INFINITY, v1 = d1 == d1 ? d1 : INFINITY;   // NaN: fminf / fmaxf would both return the list entry and double it
 #pragma unroll
       for (int k = 0; k < KMAX; ++k) {
         if (k < K) {

@@ -157,15 +157,23 @@ __device__ __forceinline__ void calibrate_row(float* lr, const float* __restrict
   const float f = dac[bi];
   const float mx = best * f;
   float se = 0.f;
-  for (int c = lane; c < C; c += 64) {
-    const float v = lr[c] * f;
-    if (!pr) lr[c] = v;
-    se += __expf(v - mx);
-  }
-  se = wave_sum(se);
-  if (pr) {
-    const float inv = 1.0f / se;
-    for (int c = lane; c < C; c += 64) pr[c] = __expf(lr[c] * f - mx) * inv;   // same lane reads then writes element c
+  {   // contraction off for both loops: x * f is ROUNDED before mx is subtracted, in the sum and in the probabilities alike.  Fused into one
+      // fma, the exponent keeps the rounding residual of the product (up to 2^-24 |x f|): with the probability loop contracted and the sum
+      // not, a numerator differed from its own term of the denominator by that much, and probs[pred] from conf.
+#pragma clang fp contract(off)
+    for (int c = lane; c < C; c += 64) {
+      const float v = lr[c] * f;
+      if (!pr) lr[c] = v;
+      se += __expf(v - mx);
+    }
+    se = wave_sum(se);
+    if (pr) {
+      const float inv = 1.0f / se;
+      for (int c = lane; c < C; c += 64) {   // same lane reads then writes element c
+        const float v = lr[c] * f;
+        pr[c] = __expf(v - mx) * inv;
+      }
+    }
   }
   conf_out = 1.0f / se;
   pred_out = bi;
@@ -194,7 +202,7 @@ __device__ __forceinline__ int ece_bin(double x, int n_bins) {
   auto edge = [&](int k) { return k >= n_bins ? 1.0 : (double)k * step; };
   while (b < n_bins && edge(b + 1) <= x) ++b;
   while (b > 0 && edge(b) > x) --b;
-  if (x >= 1.0) b = n_bins;
+  if (!(x < 1.0)) b = n_bins;   // 1.0, and NaN: np.digitize puts it behind the last edge
   return b;
 }
 
