@@ -137,6 +137,9 @@ _SIGNATURES = {
     "clipmi_isotonic_rows": (_i, [C.POINTER(IsotonicModel), _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     "clipmi_isotonic_keys": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     "clipmi_isotonic_gap_stats": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp]),
+    "clipmi_tempscale_workspace_bytes": (_sz, [_i]),
+    "clipmi_tempscale_batch": (_i, [_vp, _i64, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "clipmi_tempscale_fit": (_i, [_vp, _i64, _vp, _vp, _i, _i, _i, _i, _i, _vp, _f, _f, _f, _i, _vp, _vp, _vp, _sz, _vp]),
     "clipmi_create": (_i, [C.POINTER(Geometry), C.POINTER(_vp)]),
     "clipmi_destroy": (_i, [_vp]),
     "clipmi_set_vision_weights": (_i, [_vp, C.POINTER(VisionWeights)]),

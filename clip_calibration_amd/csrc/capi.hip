@@ -595,6 +595,20 @@ int clipmi_isotonic_gap_stats(const float* logits, const int64_t* labels, const 
   return launch_isotonic_gap_stats(logits, labels, bin, keys, key_offset, n_bins, stats, status, n, C, from_probs, (hipStream_t)stream);
 }
 
+size_t clipmi_tempscale_workspace_bytes(int rows) { return tempscale_workspace_bytes(rows); }
+
+int clipmi_tempscale_batch(const float* cosine, int64_t ld, const int64_t* labels, const int32_t* order, int rows, int n, int C,
+                           const float* theta, float* out, void* workspace, size_t workspace_bytes, clipmi_stream_t stream) {
+  return launch_tempscale_batch(cosine, ld, labels, order, rows, n, C, theta, out, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int clipmi_tempscale_fit(const float* cosine, int64_t ld, const int64_t* labels, const int32_t* order, int n, int C, int batch, int epochs,
+                         int drop_last, const float* lr, float momentum, float dampening, float weight_decay, int nesterov, float* state,
+                         float* losses, void* workspace, size_t workspace_bytes, clipmi_stream_t stream) {
+  return launch_tempscale_fit(cosine, ld, labels, order, n, C, batch, epochs, drop_last, lr, momentum, dampening, weight_decay, nesterov,
+                              state, losses, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
 int clipmi_ece_accumulate(const float* conf, const int32_t* pred, const int64_t* labels, int n, double* bins, int n_bins,
                           clipmi_stream_t stream) {
   return launch_ece_accumulate(conf, pred, labels, n, bins, n_bins, (hipStream_t)stream);

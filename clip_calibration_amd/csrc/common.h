@@ -306,4 +306,12 @@ int launch_isotonic_gap_stats(const float* logits, const int64_t* labels, const 
 static inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 static inline size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
 
+// tempscale.hip: the one-parameter TempScaling fit from cached cosine logits (trainers/calibration/tempscaling.py:146-169)
+size_t tempscale_workspace_bytes(int rows);   // 0 on rows < 1
+int launch_tempscale_batch(const float* cosine, int64_t ld, const int64_t* labels, const int32_t* order, int rows, int n, int C,
+                           const float* theta, float* out, void* workspace, size_t workspace_bytes, hipStream_t s);
+int launch_tempscale_fit(const float* cosine, int64_t ld, const int64_t* labels, const int32_t* order, int n, int C, int batch, int epochs,
+                         int drop_last, const float* lr, float momentum, float dampening, float weight_decay, int nesterov, float* state,
+                         float* losses, void* workspace, size_t workspace_bytes, hipStream_t s);
+
 }  // namespace clipmi

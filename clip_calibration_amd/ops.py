@@ -439,6 +439,76 @@ def isotonic_gap_stats(logits: torch.Tensor, labels: torch.Tensor, keys: torch.T
     return stats, status
 
 
+# ---- TempScaling fit (tempscaling.py:146-169) ----------------------------------------------------------------------
+def _cosine_rows(cosine: torch.Tensor, labels: torch.Tensor, who: str):
+    """fp32 [N, C] whose rows are contiguous (a column slice of a wider matrix keeps its row stride: ld > C) and int64 labels [N]."""
+    if (isinstance(cosine, torch.Tensor) and cosine.dim() == 2 and cosine.shape[0] > 0 and cosine.stride(1) == 1
+            and cosine.stride(0) >= cosine.shape[1]):
+        _dev(cosine[:1], "cosine_logits", (torch.float32,))     # read in place with its row stride: the device and dtype checks only
+    else:
+        cosine = _dev(cosine, "cosine_logits", (torch.float32,))
+    labels = _dev(labels, "labels", (torch.int64,))
+    if cosine.dim() != 2 or labels.shape != (cosine.shape[0],):
+        raise ValueError(f"{who}: cosine logits {tuple(cosine.shape)} must be [N, C] with one label per row, got labels {tuple(labels.shape)}")
+    if cosine.shape[0] < 1 or cosine.shape[1] < 2:
+        raise ValueError(f"{who}: cosine logits {tuple(cosine.shape)} need at least one row and two classes")
+    return cosine, labels
+
+
+def _tempscale_workspace(rows: int, device) -> torch.Tensor:
+    return torch.empty(lib.clipmi_tempscale_workspace_bytes(rows), dtype=torch.uint8, device=device)
+
+
+def tempscale_batch(cosine: torch.Tensor, labels: torch.Tensor, theta: torch.Tensor, rows: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One batch of TempScaling's loss at the device-resident ``theta`` (fp32, one element): fp32 [2] on the device,
+    (mean cross-entropy of exp(theta) * cosine, its derivative by theta) over the samples ``rows`` (int32 indices; None = every row)."""
+    cosine, labels = _cosine_rows(cosine, labels, "tempscale_batch")
+    theta = _dev(theta, "theta", (torch.float32,))
+    if theta.numel() != 1:
+        raise ValueError(f"tempscale_batch: theta {tuple(theta.shape)} must hold one element")
+    rows, pr = _opt(rows, "rows", (torch.int32,))
+    if rows is not None and (rows.dim() != 1 or rows.numel() < 1):
+        raise ValueError(f"tempscale_batch: rows {tuple(rows.shape)} must be a non-empty index vector")
+    N, Cn = cosine.shape
+    n_rows = N if rows is None else rows.numel()
+    out = torch.empty(2, dtype=torch.float32, device=cosine.device)
+    ws = _tempscale_workspace(n_rows, cosine.device)
+    check(lib.clipmi_tempscale_batch(cosine.data_ptr(), cosine.stride(0), labels.data_ptr(), pr, n_rows, N, Cn, theta.data_ptr(),
+                                     out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "clipmi_tempscale_batch")
+    return out
+
+
+def tempscale_fit(cosine: torch.Tensor, labels: torch.Tensor, state: torch.Tensor, lr: torch.Tensor, batch_size: int, epochs: int,
+                  momentum: float = 0.0, dampening: float = 0.0, weight_decay: float = 0.0, nesterov: bool = False,
+                  order: Optional[torch.Tensor] = None, drop_last: bool = False, want_losses: bool = False) -> Optional[torch.Tensor]:
+    """The whole SGD run on the scalar, enqueued without a host synchronisation (include/clipmi.h, clipmi_tempscale_fit).  ``state``
+    fp32 [4] on the device is updated in place: (theta, momentum buffer, steps taken as int32 bits, last batch loss) -- (init, 0, 0, 0)
+    starts a fresh fit.  ``lr`` fp32 [steps], one rate per step; ``order`` int32 [epochs, N] or None (0 .. N-1 every epoch).  Returns
+    the per-step batch losses fp32 [steps] when ``want_losses``."""
+    cosine, labels = _cosine_rows(cosine, labels, "tempscale_fit")
+    N, Cn = cosine.shape
+    batch_size, epochs = int(batch_size), int(epochs)
+    if batch_size < 1 or epochs < 0:
+        raise ValueError(f"tempscale_fit: batch_size={batch_size} (>= 1), epochs={epochs} (>= 0)")
+    steps = epochs * (N // batch_size if drop_last else -(-N // batch_size))
+    state = _dev(state, "state", (torch.float32,))
+    if state.shape != (4,):
+        raise ValueError(f"tempscale_fit: state {tuple(state.shape)} must be fp32 [4]")
+    lr = _dev(lr, "lr", (torch.float32,))
+    if lr.shape != (steps,):
+        raise ValueError(f"tempscale_fit: lr {tuple(lr.shape)} must hold one rate per step ({steps})")
+    order, po = _opt(order, "order", (torch.int32,))
+    if order is not None and order.shape != (epochs, N):
+        raise ValueError(f"tempscale_fit: order {tuple(order.shape)} must be [epochs, N] = [{epochs}, {N}]")
+    losses = torch.empty(steps, dtype=torch.float32, device=cosine.device) if want_losses else None
+    ws = _tempscale_workspace(min(batch_size, N), cosine.device)
+    check(lib.clipmi_tempscale_fit(cosine.data_ptr(), cosine.stride(0), labels.data_ptr(), po, N, Cn, batch_size, epochs, int(bool(drop_last)),
+                                   lr.data_ptr(), float(momentum), float(dampening), float(weight_decay), int(bool(nesterov)),
+                                   state.data_ptr(), None if losses is None else losses.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+          "clipmi_tempscale_fit")
+    return losses
+
+
 # ---- CoCoOp glue (cocoop.py:154-199) -------------------------------------------------------------------------------
 def cocoop_ctx(img_n: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor,
                ctx: torch.Tensor) -> torch.Tensor:

@@ -122,6 +122,21 @@ def collect_base_val_features(infer: Callable, loader: Iterable[Tuple[torch.Tens
             "val_image_knn_dists": knn.cpu().numpy()}
 
 
+@torch.no_grad()
+def fit_temperature(infer: Callable, loader: Iterable[Tuple[torch.Tensor, torch.Tensor]], device="cuda", **fit_args):
+    """TempScaling's training run (trainers/calibration/tempscaling.py:146-169) for any ``infer`` whose 3-tuple starts with COSINE logits
+    (a base model built with logit_scale 1.0, base_model/coop.py:222-224): one pass of ``loader`` through it, logits and labels kept on
+    the device, then ``tempfit.fit_logit_scale(cosine, labels, **fit_args)``.  Returns what that returns: the fitted ``logit_scale``."""
+    from .tempfit import fit_logit_scale
+    logits, labels = [], []
+    for image, label in device_batches(loader, device):
+        logits.append(_call(infer, image)[0].float())
+        labels.append(label)
+    if not logits:
+        raise ValueError("empty loader")
+    return fit_logit_scale(torch.cat(logits), torch.cat(labels), **fit_args)
+
+
 def text_feature_dict(base_zs: Dict[str, np.ndarray], current_text_features_zs, base_tuned: Dict[str, np.ndarray],
                       current_text_features_tuned) -> Dict[str, np.ndarray]:
     """get_text_features (base_learner.py:241-300): the four matrices DAC.fit consumes.  ``base_zs`` / ``base_tuned`` are

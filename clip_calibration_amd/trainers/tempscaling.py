@@ -1,7 +1,11 @@
-"""TempScaling (reference trainers/calibration/tempscaling.py:31-59) -- the forward, and the hand-off to the 1-parameter
-SGD fit, which stays in torch autograd on the caller's side: ``forward_train`` returns
-``scale_learner() * cosine_logits`` with the cosine logits from the HIP path as a constant and the scalar as the only
-leaf, so ``F.cross_entropy(logits, label).backward()`` is exactly the reference's step (tempscaling.py:146-158)."""
+"""TempScaling (reference trainers/calibration/tempscaling.py:31-59) -- the forward, and the 1-parameter SGD fit both ways:
+
+* ``fit_scale`` runs the loader through the frozen base model ONCE, keeps the cosine logits on the device and fits the scalar there
+  (clip_calibration_amd/tempfit.py, csrc/tempscale.hip): every epoch of the reference's loop (tempscaling.py:146-169) sees the same
+  cosine matrix, so the 20 epochs need the towers once, not 20 times;
+* ``forward_train`` keeps the step under torch autograd for a caller who drives the loop: it returns
+  ``scale_learner() * cosine_logits`` with the cosine logits from the HIP path as a constant and the scalar as the only leaf, so
+  ``F.cross_entropy(logits, label).backward()`` is exactly the reference's step (tempscaling.py:146-158)."""
 from __future__ import annotations
 
 import torch
@@ -40,6 +44,26 @@ class CustomCLIPCalibration(nn.Module):
             _, image_features, text_features = self.logits_encoder(image)[:3]
             cosine, _, _ = ops.logits_fused(image_features, text_features, 1.0, None, False)
         return self.scale_learner() * cosine, image_features, text_features
+
+    @torch.no_grad()
+    def cosine_logits(self, image):
+        """The constant of ``forward_train``, formed the same way: (cosine logits fp32 [B, C], image_features, text_features)."""
+        _, image_features, text_features = self.logits_encoder(image)[:3]
+        cosine, _, _ = ops.logits_fused(image_features, text_features, 1.0, None, False)
+        return cosine, image_features, text_features
+
+    def fit_scale(self, loader, **fit_args) -> float:
+        """The reference's training run (tempscaling.py:146-169) with the towers run once: one pass of ``loader`` (an iterable of
+        (image, label) batches) through ``logits_encoder``, the cosine logits kept on the device, then
+        ``tempfit.fit_logit_scale(cosine, labels, **fit_args)`` starting from the current ``logit_scale`` unless ``init`` says otherwise.
+        The fitted scalar is written into ``scale_learner.logit_scale`` and returned."""
+        from ..runner import fit_temperature
+        fit_args.setdefault("init", float(self.scale_learner.logit_scale.detach()))
+        fitted = fit_temperature(self.cosine_logits, loader, **fit_args)
+        theta = fitted[0] if isinstance(fitted, tuple) else fitted
+        with torch.no_grad():
+            self.scale_learner.logit_scale.fill_(theta)
+        return fitted
 
     @torch.no_grad()
     def forward(self, image, label=None, dac_conf=None, want_conf_pred: bool = False):

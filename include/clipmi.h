@@ -387,6 +387,38 @@ int clipmi_isotonic_gap_stats(const float* logits, const int64_t* labels, const 
                               const int32_t* key_offset, int n_bins, int32_t* stats, int32_t* status, int n, int C, int from_probs,
                               clipmi_stream_t stream);
 
+/* TempScaling's fit of its one parameter (trainers/calibration/tempscaling.py:146-169: F.cross_entropy(exp(logit_scale) * cosine
+ * logits, label), torch.optim.SGD on the scalar) from cosine logits computed ONCE: the base model is frozen and the val loader is
+ * sequential, so every epoch of the reference's loop sees the same matrix.  cosine fp32 [n, C] with row stride ld >= C (elements),
+ * labels int64 [n], C >= 2.  With theta = logit_scale, s = exp(theta), p = softmax(s * cosine[i, :]):
+ *   loss_i = logsumexp_j(s c_ij) - s c_iy,   d loss_i / d theta = s (sum_j p_ij c_ij - c_iy),
+ * the row maximum subtracted before the exponential, fp32 throughout; a batch's loss and gradient are the means over its rows, summed
+ * in float64 in a fixed order (no atomics): the same inputs give the same bits.  A label outside [0, C) or a sample index outside
+ * [0, n) is never dereferenced; it makes the batch's loss and gradient NaN.  Two short launches per batch; workspace (device, 8-byte
+ * aligned) of clipmi_tempscale_workspace_bytes(rows of the widest batch) bytes.  These exports are additive: the ABI version does not
+ * change with them.
+ *
+ * clipmi_tempscale_batch: one batch at the theta held in device memory (theta fp32 [1]): out fp32 [2] (device) = {mean loss, mean
+ * d loss / d theta} over the samples order[0 .. rows) (int32, device), or 0 .. rows-1 when order is NULL.
+ *
+ * clipmi_tempscale_fit: the whole run, epochs * ceil(n / batch) steps (floor with drop_last), enqueued on `stream` without a host
+ * synchronisation; step k of epoch e takes the samples order[e * n + k * batch ..] (order int32 [epochs, n], device; NULL = 0 .. n-1
+ * in every epoch, the reference's sequential loader), the last batch of an epoch may be short.  state (device, four 32-bit words):
+ * {theta fp32, momentum buffer fp32, steps taken int32, loss of the last batch fp32}; the caller sets {init, 0, 0, 0} for a fresh
+ * fit, and every kernel reads theta from there.  Each step applies torch.optim.SGD's rule in fp32 with lr[step] (lr fp32 [steps],
+ * device, filled once by the host):
+ *   g += weight_decay * theta;  buf = g on the state's first step, else momentum * buf + (1 - dampening) * g;
+ *   g = nesterov ? g + momentum * buf : buf  (momentum != 0 only);  theta -= lr * g.
+ * losses fp32 [steps] (device) receives every step's batch loss, or NULL.  epochs == 0: CLIPMI_OK, nothing is launched.
+ * CLIPMI_ERR_ARG: a null pointer, epochs < 0, momentum or dampening outside [0, 1), a negative or non-finite weight decay, nesterov
+ * with zero momentum or non-zero dampening.  CLIPMI_ERR_SHAPE: n < 1, C < 2, batch < 1, rows < 1, ld < C. */
+size_t clipmi_tempscale_workspace_bytes(int rows);
+int clipmi_tempscale_batch(const float* cosine, int64_t ld, const int64_t* labels, const int32_t* order, int rows, int n, int C,
+                           const float* theta, float* out, void* workspace, size_t workspace_bytes, clipmi_stream_t stream);
+int clipmi_tempscale_fit(const float* cosine, int64_t ld, const int64_t* labels, const int32_t* order, int n, int C, int batch, int epochs,
+                         int drop_last, const float* lr, float momentum, float dampening, float weight_decay, int nesterov, float* state,
+                         float* losses, void* workspace, size_t workspace_bytes, clipmi_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------------
  * Multi-GPU exchange: one process per GPU, the image batch sharded over the ranks, weights and text
  * features replicated and resident; per step ONE all-gather of the per-GPU L2-normalised image embeddings (fp16 [B/G,E])
