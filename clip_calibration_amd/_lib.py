@@ -67,6 +67,8 @@ class ProcalModel(C.Structure):
 
 
 ISOTONIC_MAX_TABLES = 8
+ORDER_STATS_MAX_RANKS = 64     # CLIPMI_ORDER_STATS_MAX_RANKS
+GROUP_GAP_MAX_GROUPS = 1024    # CLIPMI_GROUP_GAP_MAX_GROUPS
 
 
 class IsotonicModel(C.Structure):
@@ -140,6 +142,10 @@ _SIGNATURES = {
     "clipmi_tempscale_workspace_bytes": (_sz, [_i]),
     "clipmi_tempscale_batch": (_i, [_vp, _i64, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "clipmi_tempscale_fit": (_i, [_vp, _i64, _vp, _vp, _i, _i, _i, _i, _i, _vp, _f, _f, _f, _i, _vp, _vp, _vp, _sz, _vp]),
+    "clipmi_order_stats_workspace_bytes": (_sz, [_i, _i]),
+    "clipmi_order_stats": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
+    "clipmi_group_gap_accumulate": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _vp]),
+    "clipmi_class_counts": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "clipmi_create": (_i, [C.POINTER(Geometry), C.POINTER(_vp)]),
     "clipmi_destroy": (_i, [_vp]),
     "clipmi_set_vision_weights": (_i, [_vp, C.POINTER(VisionWeights)]),

@@ -614,6 +614,23 @@ int clipmi_ece_accumulate(const float* conf, const int32_t* pred, const int64_t*
   return launch_ece_accumulate(conf, pred, labels, n, bins, n_bins, (hipStream_t)stream);
 }
 
+size_t clipmi_order_stats_workspace_bytes(int n, int k) { return order_stats_workspace_bytes(n, k); }
+
+int clipmi_order_stats(const float* x, int n, const int32_t* ranks, int k, float* out, int32_t* nan_count, void* workspace,
+                       size_t workspace_bytes, clipmi_stream_t stream) {
+  return launch_order_stats(x, n, ranks, k, out, nan_count, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int clipmi_group_gap_accumulate(const float* conf, const int32_t* pred, const int64_t* labels, const float* key, const double* key_edges,
+                                int n_key_edges, const double* conf_edges, int n_conf_edges, double* groups, int n, clipmi_stream_t stream) {
+  return launch_group_gap_accumulate(conf, pred, labels, key, key_edges, n_key_edges, conf_edges, n_conf_edges, groups, n,
+                                     (hipStream_t)stream);
+}
+
+int clipmi_class_counts(const int32_t* pred, const int64_t* labels, int n, int C, int64_t* counts, clipmi_stream_t stream) {
+  return launch_class_counts(pred, labels, n, C, counts, (hipStream_t)stream);
+}
+
 // The fp16-stream residual GEMM of a block as an operator (out-proj / c_proj of the image tower, clip/model.py:186-187):
 // x16[m,n] = fp16(x16[m,n] + A[m,:] . W[n,:] + bias[n]) in place, plus the per-row (sum, sum of squares) partials of the ROUNDED
 // values, one pair per 256-column tile: stats[(t * M + m) * 2 ..].  *parts (host) receives the number of column tiles.

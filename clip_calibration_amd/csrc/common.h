@@ -314,4 +314,13 @@ int launch_tempscale_fit(const float* cosine, int64_t ld, const int64_t* labels,
                          int drop_last, const float* lr, float momentum, float dampening, float weight_decay, int nesterov, float* state,
                          float* losses, void* workspace, size_t workspace_bytes, hipStream_t s);
 
+
+// sample_metrics.hip: the evaluator's sample-level metrics (order statistics by radix select, grouped calibration gaps, per-class counts)
+size_t order_stats_workspace_bytes(int n, int k);   // 0 on arguments launch_order_stats refuses
+int launch_order_stats(const float* x, int n, const int32_t* ranks, int k, float* out, int32_t* nan_count, void* workspace,
+                       size_t workspace_bytes, hipStream_t s);
+int launch_group_gap_accumulate(const float* conf, const int32_t* pred, const int64_t* labels, const float* key, const double* key_edges,
+                                int n_key_edges, const double* conf_edges, int n_conf_edges, double* groups, int n, hipStream_t s);
+int launch_class_counts(const int32_t* pred, const int64_t* labels, int n, int C, int64_t* counts, hipStream_t s);
+
 }  // namespace clipmi

@@ -5,7 +5,9 @@ The reference copies logits, labels and both feature matrices to python lists ev
 here (conf, pred) come out of the logits kernel and only 3*(n_bins+1) float64 accumulators live on the device until
 ``evaluate``.  With ``keep_samples=True`` the per-sample (conf, pred, label) vectors -- 16 B per sample -- are kept on
 the device as well and copied to the host ONCE in ``evaluate`` for the metrics that need the samples themselves
-(macro-F1, AdaptiveECE's equal-mass bins, PIECE's proximity bins)."""
+(macro-F1, AdaptiveECE's equal-mass bins, PIECE's proximity bins).  With ``sample_metrics="device"`` those three come from kernels too
+(csrc/sample_metrics.hip: per-class counts, order statistics by radix select, grouped gap sums) and only the selected order
+statistics, the [3, G] group sums and the [3 C + 1] counts are copied -- nothing of O(N)."""
 from __future__ import annotations
 
 from collections import OrderedDict
@@ -15,14 +17,24 @@ import numpy as np
 import torch
 
 from . import ops
-from .metrics import AdaptiveECE, PIECE, ece_from_bins, macro_f1, mce_from_bins
+from .metrics import (AdaptiveECE, PIECE, ece_from_bins, gap_from_groups, macro_f1, macro_f1_from_counts, mce_from_bins,
+                      quantile_edges_from_order_stats, quantile_ranks)
 
 
 class DeviceCalibrationEvaluator:
-    def __init__(self, n_bins: int = 10, device="cuda", keep_samples: bool = False, piece_bins: int = 10):
+    def __init__(self, n_bins: int = 10, device="cuda", keep_samples: bool = False, piece_bins: int = 10,
+                 sample_metrics: str = "host", n_classes: Optional[int] = None):
+        """``sample_metrics``: where macro-F1, ACE and PIECE are computed from the kept samples -- "host" (numpy, after one copy of the
+        vectors) or "device" (kernels; needs ``keep_samples`` and ``n_classes``, the width of the logits the predictions index)."""
+        if sample_metrics not in ("host", "device"):
+            raise ValueError(f"sample_metrics={sample_metrics!r} (\"host\" or \"device\")")
+        if sample_metrics == "device" and not (keep_samples and n_classes is not None and int(n_classes) >= 1):
+            raise ValueError("sample_metrics=\"device\" needs keep_samples=True and n_classes >= 1")
         self.n_bins = n_bins
         self.piece_bins = piece_bins
         self.keep_samples = keep_samples
+        self.sample_metrics = sample_metrics
+        self.n_classes = None if n_classes is None else int(n_classes)
         self.bins = torch.zeros(3 * (n_bins + 1), dtype=torch.float64, device=device)
         self._conf: List[torch.Tensor] = []
         self._pred: List[torch.Tensor] = []
@@ -60,9 +72,52 @@ class DeviceCalibrationEvaluator:
         return (torch.cat(self._conf).cpu().numpy(), torch.cat(self._pred).cpu().numpy().astype(np.int64),
                 torch.cat(self._gt).cpu().numpy())
 
-    def evaluate(self, proximity: Optional[np.ndarray] = None) -> "OrderedDict[str, float]":
+    def _device_sample_metrics(self, proximity) -> "OrderedDict[str, float]":
+        """macro_f1, ace and (with a proximity) piece as fractions, from the kept device vectors: every launch first, then the copies
+        of the selected order statistics, then the two group launches whose edges the host derives from them."""
+        if not self._conf:
+            raise ValueError("sample_metrics=\"device\": no samples were processed")
+        conf = torch.cat(self._conf).to(torch.float32)
+        pred = torch.cat(self._pred).to(torch.int32)
+        gt = torch.cat(self._gt).to(torch.int64)
+        n = conf.shape[0]
+        if proximity is not None:
+            proximity = torch.as_tensor(proximity).to(device=conf.device, dtype=torch.float32)
+            if proximity.dim() != 1 or proximity.shape[0] != n:
+                raise ValueError(f"proximity has {tuple(proximity.shape)} entries for {n} samples")
+        counts = ops.class_counts(pred, gt, self.n_classes)
+
+        def select(x, n_bins):
+            ranks = quantile_ranks(n, n_bins)
+            distinct = np.unique(ranks)            # ascending, as the kernel wants them; at most 2 * (n_bins + 1)
+            return ranks, distinct, ops.order_stats(x, distinct)
+
+        def edges(selected, n_bins):
+            ranks, distinct, (values, nans) = selected
+            stats = values.cpu().numpy()[np.searchsorted(distinct, ranks)]
+            return quantile_edges_from_order_stats(stats, n, n_bins, nan_count=int(nans.item()))
+
+        sel_conf = select(conf, self.n_bins)
+        sel_prox = select(proximity, self.piece_bins) if proximity is not None else None
+        ace = ops.group_gap_accumulate(conf, pred, gt, key=conf, key_edges=edges(sel_conf, self.n_bins))
+        piece = None
+        if sel_prox is not None:
+            piece = ops.group_gap_accumulate(conf, pred, gt, key=proximity, key_edges=edges(sel_prox, self.piece_bins),
+                                             conf_edges=np.linspace(0, 1, self.n_bins + 1)[1:-1])
+        counts = counts.cpu().numpy()
+        if counts[-1]:
+            raise ValueError(f"{int(counts[-1])} samples have a label or a prediction outside [0, {self.n_classes})")
+        res = OrderedDict(macro_f1=macro_f1_from_counts(counts), ace=gap_from_groups(ace.cpu().numpy()))
+        if piece is not None:
+            res["piece"] = gap_from_groups(piece.cpu().numpy())
+        return res
+
+    def evaluate(self, proximity=None) -> "OrderedDict[str, float]":
         """Keys and scaling follow vl_evaluator.py:59-102 (percentages except ``confidence``).  ``macro_f1`` and ``ace``
-        need keep_samples; ``piece`` additionally needs the per-sample proximity (base_learner.py:136-137)."""
+        need keep_samples; ``piece`` additionally needs the per-sample proximity (base_learner.py:136-137): a numpy vector, or with
+        ``sample_metrics="device"`` a device tensor that stays there."""
+        if self.keep_samples and self.sample_metrics == "device":
+            return self._evaluate_device(proximity)
         b = self.bins.cpu().numpy().reshape(3, self.n_bins + 1)
         total = b[0].sum()
         res = OrderedDict()
@@ -81,5 +136,23 @@ class DeviceCalibrationEvaluator:
                 if proximity.shape[0] != conf.shape[0]:
                     raise ValueError(f"proximity has {proximity.shape[0]} rows for {conf.shape[0]} samples")
                 res["piece"] = 100.0 * PIECE(conf, proximity, pred, gt, self.piece_bins, self.n_bins)
+        res["total"] = int(total)
+        return res
+
+    def _evaluate_device(self, proximity) -> "OrderedDict[str, float]":
+        """``evaluate`` with the sample-level metrics from the device: the same keys in the same order with the same scaling."""
+        sample = self._device_sample_metrics(proximity)
+        b = self.bins.cpu().numpy().reshape(3, self.n_bins + 1)
+        total = b[0].sum()
+        res = OrderedDict()
+        res["accuracy"] = 100.0 * b[2].sum() / total
+        res["error_rate"] = 100.0 - res["accuracy"]
+        res["macro_f1"] = 100.0 * sample["macro_f1"]
+        res["confidence"] = b[1].sum() / total
+        res["ece"] = 100.0 * ece_from_bins(b, self.n_bins)
+        res["mce"] = 100.0 * mce_from_bins(b, self.n_bins)
+        res["ace"] = 100.0 * sample["ace"]
+        if "piece" in sample:
+            res["piece"] = 100.0 * sample["piece"]
         res["total"] = int(total)
         return res

@@ -122,3 +122,87 @@ def macro_f1(pred, gt) -> float:
     denom = (n_pred + n_gt)[classes]                      # 2 tp + fp + fn
     f1 = np.where(denom > 0, 2 * tp[classes] / np.where(denom > 0, denom, 1), 0.0)
     return float(f1.mean())
+
+
+# ---- the same three metrics from what the device kernels return (csrc/sample_metrics.hip): a few order statistics, the per-group
+# sums and the per-class counts -- no per-sample vector reaches the host ------------------------------------------------------------
+
+def _virtual_indexes(n: int, n_bins: int) -> np.ndarray:
+    """The float64 positions in the sorted array that np.percentile(x, linspace(0, 100, n_bins + 1), method="linear") interpolates
+    at for n values: numpy's own expression for the method, (n - 1) * (q / 100), operation for operation."""
+    return (n - 1) * np.true_divide(np.linspace(0, 100, n_bins + 1), 100)
+
+
+def quantile_ranks(n: int, n_bins: int) -> np.ndarray:
+    """int32 [2 * (n_bins + 1)]: the n_bins + 1 floor indexes, then the n_bins + 1 (clipped) ceil indexes, of the sorted-array
+    elements np.percentile reads for the edges of ``quantile_bin_index`` -- numpy's _get_indexes: a position at or beyond n - 1
+    reads the last element twice, one below 0 the first."""
+    if n < 1 or n_bins < 1:
+        raise ValueError(f"quantile_ranks: n={n}, n_bins={n_bins} (both >= 1)")
+    v = _virtual_indexes(n, n_bins)
+    lo = np.floor(v)
+    hi = lo + 1
+    above, below = v >= n - 1, v < 0
+    lo[above] = hi[above] = n - 1
+    lo[below] = hi[below] = 0
+    return np.concatenate([lo, hi]).astype(np.int32)
+
+
+def percentiles_from_order_stats(stats, n: int, n_bins: int) -> np.ndarray:
+    """np.percentile(x, linspace(0, 100, n_bins + 1)) from ``stats = np.sort(x)[quantile_ranks(n, n_bins)]``, bit for bit: numpy's
+    _get_gamma and _lerp restated (a + (b - a) t, and b - (b - a)(1 - t) from t = 0.5 on; the difference in the dtype of x, the
+    rest in float64), with the weight taken against the index numpy takes it against (-1 at the upper bound)."""
+    stats = np.asarray(stats)
+    if stats.shape != (2 * (n_bins + 1),):
+        raise ValueError(f"percentiles_from_order_stats: stats {stats.shape} for {n_bins} bins")
+    a, b = stats[:n_bins + 1], stats[n_bins + 1:]
+    v = _virtual_indexes(n, n_bins)
+    prev = np.floor(v)
+    prev[v >= n - 1] = -1
+    prev[v < 0] = 0
+    t = v - prev
+    with np.errstate(invalid="ignore"):   # inf - inf: numpy's own lerp answers NaN there, with the same warning silenced here
+        diff = np.subtract(b, a)
+        out = np.asanyarray(np.add(a, diff * t))
+        np.subtract(b, diff * (1 - t), out=out, where=t >= 0.5, casting="unsafe", dtype=type(out.dtype))
+    return out
+
+
+def quantile_edges_from_order_stats(stats, n: int, n_bins: int, nan_count: int = 0) -> np.ndarray:
+    """The inner bin edges of ``quantile_bin_index(x, n_bins)`` as float64, from the order statistics of x at
+    ``quantile_ranks(n, n_bins)``: bin index = np.searchsorted(edges, x, side="right").  Empty -- every sample in bin 0, as
+    quantile_bin_index answers -- when x holds a NaN (``nan_count``, or a NaN among the statistics: NaNs sort last and the last
+    element is always read) or when all values are equal."""
+    stats = np.asarray(stats)
+    if stats.dtype not in (np.float32, np.float64):
+        stats = stats.astype(np.float64)
+    none = np.zeros(0, dtype=np.float64)
+    if stats.shape != (2 * (n_bins + 1),):
+        raise ValueError(f"quantile_edges_from_order_stats: stats {stats.shape} for {n_bins} bins")
+    if nan_count or np.isnan(stats).any() or stats[0] == stats[-1]:   # stats[0] = min (rank 0), stats[-1] = max (rank n - 1)
+        return none
+    edges = np.asarray(percentiles_from_order_stats(stats, n, n_bins), dtype=np.float64)
+    edges = edges[np.ediff1d(edges, to_begin=np.inf) > 1e-8]
+    return edges[1:-1]
+
+
+def gap_from_groups(groups) -> float:
+    """``_grouped_gap`` from float64 [3, G] = (count, sum_conf, sum_correct) per group: sum_g |sum_correct_g - sum_conf_g| / N
+    (an empty group adds nothing)."""
+    g = np.asarray(groups, dtype=np.float64)
+    g = g.reshape(3, -1)
+    return float(np.abs(g[2] - g[1]).sum() / g[0].sum())
+
+
+def macro_f1_from_counts(counts) -> float:
+    """``macro_f1`` from int [3 C + 1] = true positives | predicted | labelled per class (| samples outside the classes, not used
+    here): the mean F1 over the classes with a label count."""
+    c = np.asarray(counts)
+    C = (c.shape[0] - 1) // 3
+    if c.ndim != 1 or c.shape[0] != 3 * C + 1 or C < 1:
+        raise ValueError(f"macro_f1_from_counts: counts {c.shape} is not [3 C + 1]")
+    tp, n_pred, n_gt = (c[i * C:(i + 1) * C].astype(np.float64) for i in range(3))
+    classes = n_gt > 0
+    denom = (n_pred + n_gt)[classes]                      # 2 tp + fp + fn
+    f1 = np.where(denom > 0, 2 * tp[classes] / np.where(denom > 0, denom, 1), 0.0)
+    return float(f1.mean())

@@ -439,6 +439,91 @@ def isotonic_gap_stats(logits: torch.Tensor, labels: torch.Tensor, keys: torch.T
     return stats, status
 
 
+# ---- sample-level metrics (vl_evaluator.py:77-82, tools/metrics.py:132-178, 212-236) --------------------------------
+def order_stats(x: torch.Tensor, ranks) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``np.sort(x)[ranks]`` without a sort (include/clipmi.h, clipmi_order_stats): ``x`` fp32 [n] on the device, ``ranks`` host ints,
+    non-decreasing, each in [0, n), at most 64 of them.  Returns (values fp32 [k], NaN count int32 [1]), both on the device; nothing is
+    synchronised."""
+    x = _dev(x, "x", (torch.float32,))
+    if x.dim() != 1 or x.numel() < 1:
+        raise ValueError(f"order_stats: x {tuple(x.shape)} must be a non-empty vector")
+    r = [int(v) for v in ranks]
+    if not 1 <= len(r) <= _lib.ORDER_STATS_MAX_RANKS:
+        raise ValueError(f"order_stats: {len(r)} ranks (1 .. {_lib.ORDER_STATS_MAX_RANKS})")
+    n, k = x.numel(), len(r)
+    if any(not 0 <= v < n for v in r) or any(b < a for a, b in zip(r, r[1:])):
+        raise ValueError(f"order_stats: ranks {r} must ascend inside [0, {n})")
+    out = torch.empty(k, dtype=torch.float32, device=x.device)
+    nans = torch.empty(1, dtype=torch.int32, device=x.device)
+    ws = torch.empty(lib.clipmi_order_stats_workspace_bytes(n, k), dtype=torch.uint8, device=x.device)
+    c_ranks = (ctypes.c_int32 * k)(*r)
+    check(lib.clipmi_order_stats(x.data_ptr(), n, c_ranks, k, out.data_ptr(), nans.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+          "clipmi_order_stats")
+    return out, nans
+
+
+def _edges(edges, name: str, device) -> Tuple[Optional[torch.Tensor], Optional[int], int]:
+    """Host float64 edges (numpy / list) -> device float64; a device float64 tensor is taken as it is.  (tensor, pointer, count)."""
+    if edges is None:
+        return None, None, 0
+    if not isinstance(edges, torch.Tensor):
+        import numpy as np
+        edges = torch.from_numpy(np.ascontiguousarray(np.asarray(edges, dtype=np.float64))).to(device)
+    if edges.numel() == 0:
+        return None, None, 0
+    edges = _dev(edges, name, (torch.float64,))
+    if edges.dim() != 1:
+        raise ValueError(f"group_gap_accumulate: {name} {tuple(edges.shape)} must be a vector")
+    return edges, edges.data_ptr(), edges.numel()
+
+
+def group_gap_accumulate(conf: torch.Tensor, pred: torch.Tensor, labels: torch.Tensor, key: Optional[torch.Tensor] = None, key_edges=None,
+                         conf_edges=None, groups: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(count, sum_conf, sum_correct) per group = key bin * (len(conf_edges) + 1) + confidence bin, a bin being the number of edges <= the
+    value in float64 (include/clipmi.h, clipmi_group_gap_accumulate).  The edge lists are host float64 arrays (uploaded as they are) or
+    device float64 tensors, ascending; None or empty = one bin.  Adds into ``groups`` float64 [3, G] when given, else into zeros."""
+    conf = _dev(conf, "conf", (torch.float32,))
+    pred = _dev(pred, "pred", (torch.int32,))
+    labels = _dev(labels, "labels", (torch.int64,))
+    if conf.dim() != 1 or pred.shape != conf.shape or labels.shape != conf.shape:
+        raise ValueError(f"group_gap_accumulate: conf {tuple(conf.shape)}, pred {tuple(pred.shape)}, labels {tuple(labels.shape)} must be equal vectors")
+    key_edges, pke, nk = _edges(key_edges, "key_edges", conf.device)
+    conf_edges, pce, nc = _edges(conf_edges, "conf_edges", conf.device)
+    key, pk = _opt(key, "key", (torch.float32,))
+    if nk and key is None:
+        raise ValueError("group_gap_accumulate: key_edges need a key")
+    if key is not None and key.shape != conf.shape:
+        raise ValueError(f"group_gap_accumulate: key {tuple(key.shape)} must have one entry per sample")
+    G = (nk + 1) * (nc + 1)
+    if G > _lib.GROUP_GAP_MAX_GROUPS:
+        raise ValueError(f"group_gap_accumulate: {G} groups (at most {_lib.GROUP_GAP_MAX_GROUPS})")
+    if groups is None:
+        groups = torch.zeros(3, G, dtype=torch.float64, device=conf.device)
+    else:
+        if not (isinstance(groups, torch.Tensor) and groups.is_cuda and groups.dtype == torch.float64 and groups.is_contiguous()
+                and groups.numel() == 3 * G):
+            raise ValueError(f"group_gap_accumulate: groups must be a contiguous float64 GPU tensor of 3 * {G} (it is updated in place)")
+    check(lib.clipmi_group_gap_accumulate(conf.data_ptr(), pred.data_ptr(), labels.data_ptr(), pk, pke, nk, pce, nc, groups.data_ptr(),
+                                          conf.numel(), _stream()), "clipmi_group_gap_accumulate")
+    return groups
+
+
+def class_counts(pred: torch.Tensor, labels: torch.Tensor, n_classes: int) -> torch.Tensor:
+    """int64 [3 C + 1] on the device: true positives | predicted | labelled per class, then the number of samples whose label or
+    prediction lies outside [0, C) -- those count nowhere else (include/clipmi.h, clipmi_class_counts)."""
+    pred = _dev(pred, "pred", (torch.int32,))
+    labels = _dev(labels, "labels", (torch.int64,))
+    if pred.dim() != 1 or labels.shape != pred.shape:
+        raise ValueError(f"class_counts: pred {tuple(pred.shape)} and labels {tuple(labels.shape)} must be equal vectors")
+    n_classes = int(n_classes)
+    if n_classes < 1:
+        raise ValueError(f"class_counts: n_classes={n_classes} (>= 1)")
+    counts = torch.zeros(3 * n_classes + 1, dtype=torch.int64, device=pred.device)
+    check(lib.clipmi_class_counts(pred.data_ptr(), labels.data_ptr(), pred.numel(), n_classes, counts.data_ptr(), _stream()),
+          "clipmi_class_counts")
+    return counts
+
+
 # ---- TempScaling fit (tempscaling.py:146-169) ----------------------------------------------------------------------
 def _cosine_rows(cosine: torch.Tensor, labels: torch.Tensor, who: str):
     """fp32 [N, C] whose rows are contiguous (a column slice of a wider matrix keeps its row stride: ld > C) and int64 labels [N]."""

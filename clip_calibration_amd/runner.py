@@ -152,15 +152,20 @@ def text_feature_dict(base_zs: Dict[str, np.ndarray], current_text_features_zs, 
 @torch.no_grad()
 def test(infer: Callable, loader: Iterable[Tuple[torch.Tensor, torch.Tensor]], val_dict: Optional[Dict[str, np.ndarray]] = None,
          calibrator: Optional[VLCalibration] = None, image_k: int = 10, ece_bins: int = 10, piece_bins: int = 10,
-         device="cuda", group=None) -> "OrderedDict[str, float]":
+         device="cuda", group=None, sample_metrics: str = "host") -> "OrderedDict[str, float]":
     """VLBaseLearner.test (base_learner.py:59-152): inference over the split, DAC, softmax top-1, proximity of every test
     image to the base-class val images (exp(-mean K-NN distance), :121-137), then the evaluator's metrics.  Under
     torch.distributed each rank passes its own shard of the loader; samples are gathered before the sample-level metrics.
     With a base calibrator on (``calibrator.row_calibrator_device()``: ProCal, multi-class isotonic regression or Bin-Mean-Shift) the
     evaluator sees the top-1 of the calibrated rows instead: the (DAC-scaled) logits of the split are kept on the device until the
     proximity is known, then one ``clipmi_procal_rows`` / ``clipmi_isotonic_rows`` launch per rank -- before the gather, as proximity
-    is per sample -- yields (conf', pred')."""
-    ev = DeviceCalibrationEvaluator(ece_bins, device=device, keep_samples=True, piece_bins=piece_bins)
+    is per sample -- yields (conf', pred').
+    ``sample_metrics="device"`` computes macro-F1, ACE and PIECE with kernels from the kept (and, across ranks, gathered) device vectors
+    and leaves the proximity on the device; "host" (default) copies the vectors once and uses numpy.  The class count the device
+    metrics need is the width of the logits, so an empty split (no batch, hence no width) is evaluated the host way."""
+    if sample_metrics not in ("host", "device"):
+        raise ValueError(f"sample_metrics={sample_metrics!r} (\"host\" or \"device\")")
+    ev = None   # built at the first batch, which tells the class count
     dac = calibrator.class_confidence_device(device) if calibrator is not None else None
     procal, needs_proximity = calibrator.row_calibrator_device() if calibrator is not None else (None, False)
     if needs_proximity and val_dict is None:
@@ -168,12 +173,17 @@ def test(infer: Callable, loader: Iterable[Tuple[torch.Tensor, torch.Tensor]], v
     feats, kept_logits, kept_labels = [], [], []
     for image, label in device_batches(loader, device):
         out = _call(infer, image, dac_conf=dac, want_conf_pred=True)
+        if ev is None:
+            ev = DeviceCalibrationEvaluator(ece_bins, device=device, keep_samples=True, piece_bins=piece_bins, sample_metrics=sample_metrics,
+                                            n_classes=int(out[0].shape[1]))
         if procal is None:
             ev.process(out[3], out[4], label)
         else:   # out[0] already holds the DAC-scaled logits (the fused logits kernels scale in place): no DAC again below
             kept_logits.append(out[0])
             kept_labels.append(label)
         feats.append(out[1])
+    if ev is None:
+        ev = DeviceCalibrationEvaluator(ece_bins, device=device, keep_samples=True, piece_bins=piece_bins)
     proximity = None
     if val_dict is not None and feats:
         refs = torch.as_tensor(np.asarray(val_dict["val_image_features"]), dtype=torch.float32, device=device)
@@ -186,4 +196,6 @@ def test(infer: Callable, loader: Iterable[Tuple[torch.Tensor, torch.Tensor]], v
                              and torch.distributed.get_world_size() > 1):
         from .parallel import gather_samples
         proximity = gather_samples(ev, proximity, group, has_proximity=val_dict is not None)   # rank-uniform, not data-dependent
+    if ev.sample_metrics == "device":
+        return ev.evaluate(proximity)
     return ev.evaluate(None if proximity is None else proximity.cpu().numpy())

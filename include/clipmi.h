@@ -419,6 +419,45 @@ int clipmi_tempscale_fit(const float* cosine, int64_t ld, const int64_t* labels,
                          int drop_last, const float* lr, float momentum, float dampening, float weight_decay, int nesterov, float* state,
                          float* losses, void* workspace, size_t workspace_bytes, clipmi_stream_t stream);
 
+/* The sample-level metrics of the evaluator on the device (vl_evaluator.py:77-82 macro-F1; tools/metrics.py:132-178 PIECE, :212-236
+ * AdaptiveECE) -- SURVEY f-1.  Three small kernels; the host turns their outputs into the scalars (clip_calibration_amd.metrics:
+ * quantile_edges_from_order_stats, gap_from_groups, macro_f1_from_counts).  These exports are additive: the ABI version does not
+ * change with them.
+ *
+ * clipmi_order_stats: exact order statistics without a sort.  x fp32 [n] (device, not modified); ranks int32 [k] (HOST), 0-based,
+ * non-decreasing, each in [0, n), 1 <= k <= CLIPMI_ORDER_STATS_MAX_RANKS.  out fp32 [k] (device): out[j] == np.sort(x)[ranks[j]] --
+ * every NaN sorts behind +inf, as in numpy, and comes back as a NaN; -0.0 sorts before +0.0.  nan_count int32 [1] (device): the
+ * number of NaNs in x.  A most-significant-digit radix select on the order-preserving integer image of the floats: four 8-bit passes,
+ * each one histogram launch (per distinct prefix among the targets, 256 digit counts: LDS partials, then integer global atomics) and
+ * one one-workgroup launch that narrows every target's prefix and residual rank; nine enqueues, no host synchronisation, integer
+ * counts only -- the same input gives the same bits.  workspace (device, 16-byte aligned) of clipmi_order_stats_workspace_bytes(n, k)
+ * bytes (0 for arguments the call would refuse); the call initialises it.
+ * CLIPMI_ERR_ARG: a null pointer, a rank outside [0, n) or below its predecessor.  CLIPMI_ERR_SHAPE: n < 1, k < 1,
+ * k > CLIPMI_ORDER_STATS_MAX_RANKS.  CLIPMI_ERR_WORKSPACE: a workspace that is too small. */
+#define CLIPMI_ORDER_STATS_MAX_RANKS 64
+size_t clipmi_order_stats_workspace_bytes(int n, int k);
+int clipmi_order_stats(const float* x, int n, const int32_t* ranks, int k, float* out, int32_t* nan_count, void* workspace,
+                       size_t workspace_bytes, clipmi_stream_t stream);
+
+/* clipmi_group_gap_accumulate: per sample i, key_bin = the number of key_edges <= key[i] and conf_bin = the number of conf_edges <=
+ * conf[i] (np.searchsorted(edges, v, side="right"): compared in float64, a NaN value lands behind the last edge);
+ * group = key_bin * (n_conf_edges + 1) + conf_bin;  groups float64 [3][G] (device), G = (n_key_edges + 1) * (n_conf_edges + 1) <=
+ * CLIPMI_GROUP_GAP_MAX_GROUPS (what the LDS partials hold): plane 0 += 1, plane 1 += conf[i], plane 2 += (labels[i] == pred[i]).
+ * Accumulates over calls; the caller zeroes it.  conf, key fp32 [n], pred int32 [n], labels int64 [n]; both edge lists float64
+ * (device), ascending, NULL when their count is 0; key may be NULL when n_key_edges == 0.  n == 0: CLIPMI_OK.  One launch.
+ * AdaptiveECE: key = conf with the inner quantile edges and no conf_edges.  PIECE: key = proximity with its inner quantile edges,
+ * conf_edges = np.linspace(0, 1, n_bins + 1)[1:-1] uploaded as the host computed them. */
+#define CLIPMI_GROUP_GAP_MAX_GROUPS 1024
+int clipmi_group_gap_accumulate(const float* conf, const int32_t* pred, const int64_t* labels, const float* key,
+                                const double* key_edges, int n_key_edges, const double* conf_edges, int n_conf_edges, double* groups,
+                                int n, clipmi_stream_t stream);
+
+/* clipmi_class_counts: counts int64 [3 * C + 1] (device): counts[c] += samples with pred == labels == c (true positives),
+ * counts[C + c] += samples predicted c, counts[2 C + c] += samples labelled c; a sample whose label or prediction lies outside
+ * [0, C) adds to counts[3 C] and to nothing else.  Accumulates over calls; the caller zeroes it.  pred int32 [n], labels int64 [n].
+ * Integer atomics (LDS partials per workgroup while 3 C + 1 counters fit, global atomics alone beyond).  n == 0: CLIPMI_OK. */
+int clipmi_class_counts(const int32_t* pred, const int64_t* labels, int n, int C, int64_t* counts, clipmi_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------------
  * Multi-GPU exchange: one process per GPU, the image batch sharded over the ranks, weights and text
  * features replicated and resident; per step ONE all-gather of the per-GPU L2-normalised image embeddings (fp16 [B/G,E])
