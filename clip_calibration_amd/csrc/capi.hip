@@ -1,6 +1,9 @@
 // C ABI of libclipmi.so (include/clipmi.h): error plumbing, the model handle and the tower drivers, i.e. the
 // sequence of kernel launches that stands in for VisionTransformer.forward / Transformer.forward / encode_text
 // (reference clip/model.py:394-424, 334-359, 600-613).  Host-side C++ only; kernels live in the other .hip files.
+// An operator's clipmi_* entry point is defined beside its kernel, in that kernel's .hip file.  Only the operators that
+// the tower drivers or another translation unit also launch have a typed launch_* in common.h and their entry point
+// here ("operator level" below).
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -439,7 +442,7 @@ int clipmi_get_option(const char* name, int* value) {
   return CLIPMI_ERR_ARG;
 }
 
-// ---------------------------------------------------------------- operator level
+// ---------------------------------------------------------------- operator level (the launch_* of common.h; every other operator: its kernel's file)
 int clipmi_gemm_f16(const void* A, int64_t lda, const void* W, int64_t ldw, const float* bias, const void* residual,
                     void* out, int64_t ldo, int out_dtype, int M, int N, int K, int epilogue, clipmi_stream_t stream) {
   CLIPMI_REQUIRE(epilogue >= CLIPMI_EPI_NONE && epilogue <= CLIPMI_EPI_BIAS_RESIDUAL16_RELU, CLIPMI_ERR_ARG, "gemm: bad epilogue %d", epilogue);
@@ -484,151 +487,8 @@ int clipmi_l2_normalize(const void* in, int in_dtype, float* out, int rows, int 
   return launch_l2_normalize(in, in_dtype, out, rows, E, (hipStream_t)stream);
 }
 
-int clipmi_l2_normalize_to(const void* in, int in_dtype, void* out, int out_dtype, int rows, int E, clipmi_stream_t stream) {
-  return launch_l2_normalize_to(in, in_dtype, out, out_dtype, rows, E, (hipStream_t)stream);
-}
-
-int clipmi_logits(const float* img_n, const float* txt_n, float scale, const float* dac_conf, float* logits, float* conf,
-                  int32_t* pred, int B, int C, int E, clipmi_stream_t stream) {
-  return launch_logits(img_n, txt_n, scale, dac_conf, logits, conf, pred, B, C, E, (hipStream_t)stream);
-}
-
-size_t clipmi_preprocess_workspace_bytes(const clipmi_image_desc* images, int B, int n_px, int filter) {
-  return preprocess_workspace_bytes(images, B, n_px, filter);
-}
-
-int clipmi_preprocess(const void* pixels, int64_t pixels_bytes, const clipmi_image_desc* images, int B, int n_px, int filter,
-                      const float* table, void* out, int out_dtype, void* workspace, size_t workspace_bytes, clipmi_stream_t stream) {
-  return launch_preprocess(pixels, pixels_bytes, images, B, n_px, filter, table, out, out_dtype, workspace, workspace_bytes,
-                           (hipStream_t)stream);
-}
-
-size_t clipmi_fused_tail_workspace_bytes(int B, int C) { return (B < 0 || C < 0) ? 0 : fused_tail_workspace_bytes(B, C); }
-
-int clipmi_fused_tail(const void* img, int img_dtype, int normalize, const float* txt_n, float scale, const float* dac_conf, float* logits,
-                      float* img_n_out, float* conf, int32_t* pred, const int64_t* labels, double* bins, int n_bins,
-                      void* workspace, size_t workspace_bytes, int B, int C, int E, clipmi_stream_t stream) {
-  return launch_fused_tail(img, img_dtype, normalize, txt_n, scale, dac_conf, logits, img_n_out, conf, pred, labels, bins, n_bins, workspace,
-                           workspace_bytes, B, C, E, (hipStream_t)stream);
-}
-
 int clipmi_calibrate_rows(float* logits, const float* dac_conf, float* conf, int32_t* pred, int B, int C, clipmi_stream_t stream) {
   return launch_calibrate_rows(logits, dac_conf, conf, pred, B, C, (hipStream_t)stream);
-}
-int clipmi_conv3x3_nhwc(const void* x, const void* w, const float* bias, void* out, int B, int H, int W, int C, int Cout, int relu,
-                        clipmi_stream_t stream) {
-  return launch_conv3x3((const half_t*)x, (const half_t*)w, bias, (half_t*)out, B, H, W, C, Cout, relu, (hipStream_t)stream);
-}
-int clipmi_im2col3x3_nchw(const void* image, int image_dtype, void* col, int B, int Cin, int H, int W, int stride, int Kpad,
-                          clipmi_stream_t stream) {
-  return launch_im2col3x3_nchw(image, image_dtype, (half_t*)col, B, Cin, H, W, stride, Kpad, (hipStream_t)stream);
-}
-int clipmi_im2col3x3_nhwc(const void* x, void* col, int B, int H, int W, int C, int Kpad, clipmi_stream_t stream) {
-  return launch_im2col3x3_nhwc((const half_t*)x, (half_t*)col, B, H, W, C, Kpad, (hipStream_t)stream);
-}
-int clipmi_avgpool_nhwc(const void* x, void* y, int B, int H, int W, int C, int k, clipmi_stream_t stream) {
-  return launch_avgpool_nhwc((const half_t*)x, (half_t*)y, B, H, W, C, k, (hipStream_t)stream);
-}
-int clipmi_attnpool_tokens(const void* x, const float* pos, void* tokens, int B, int HW, int C, clipmi_stream_t stream) {
-  return launch_attnpool_tokens((const half_t*)x, pos, (half_t*)tokens, B, HW, C, (hipStream_t)stream);
-}
-int clipmi_attnpool(const void* q, const void* kv, void* out, int B, int T, int heads, clipmi_stream_t stream) {
-  return launch_attnpool((const half_t*)q, (const half_t*)kv, (half_t*)out, B, T, heads, (hipStream_t)stream);
-}
-int clipmi_adapter_blend(const float* feats, const float* w1, const float* w2, float ratio, float* out, int B, int E, int H,
-                         clipmi_stream_t stream) {
-  return launch_adapter_blend(feats, w1, w2, ratio, out, B, E, H, (hipStream_t)stream);
-}
-int clipmi_scale_add(const float* a, const float* b, float alpha, float* out, long long n, clipmi_stream_t stream) {
-  return launch_scale_add(a, b, alpha, out, (int64_t)n, (hipStream_t)stream);
-}
-int clipmi_group_mean(const float* in, float* out, int G, int P, int E, clipmi_stream_t stream) {
-  return launch_group_mean(in, out, G, P, E, (hipStream_t)stream);
-}
-int clipmi_cocoop_ctx(const float* img_n, const float* w1, const float* b1, const float* w2, const float* b2, const float* ctx,
-                      float* ctx_shifted, int B, int E, int H, int D, int n_ctx, clipmi_stream_t stream) {
-  return launch_cocoop_ctx(img_n, w1, b1, w2, b2, ctx, ctx_shifted, B, E, H, D, n_ctx, (hipStream_t)stream);
-}
-int clipmi_cocoop_prompts(const void* base, int base_dtype, const float* ctx_shifted, void* prompts, int n_images, int C, int L,
-                          int D, int n_ctx, clipmi_stream_t stream) {
-  return launch_cocoop_prompts(base, base_dtype, ctx_shifted, (half_t*)prompts, n_images, C, L, D, n_ctx, (hipStream_t)stream);
-}
-int clipmi_logits_per_image(const float* img_n, const float* txt, float scale, const float* dac_conf, float* logits, float* conf,
-                            int32_t* pred, float* txt_n_last, int B, int C, int E, clipmi_stream_t stream) {
-  return launch_logits_per_image(img_n, txt, scale, dac_conf, logits, conf, pred, txt_n_last, B, C, E, (hipStream_t)stream);
-}
-int clipmi_softmax_rows(const float* logits, const float* dac_conf, float* probs, float* conf, int32_t* pred, int B, int C,
-                        clipmi_stream_t stream) {
-  return launch_softmax_rows(logits, dac_conf, probs, conf, pred, B, C, (hipStream_t)stream);
-}
-
-int clipmi_knn_dists(const float* queries, const float* refs, float* out, int Nq, int Nr, int E, int K, clipmi_stream_t stream) {
-  return launch_knn(queries, refs, out, Nq, Nr, E, K, (hipStream_t)stream);
-}
-
-int clipmi_procal_kde(const clipmi_procal_model* model, const float* conf, const float* proximity, float* cstar, int n,
-                      clipmi_stream_t stream) {
-  return launch_procal_kde(model, conf, proximity, cstar, n, (hipStream_t)stream);
-}
-
-int clipmi_procal_rows(const clipmi_procal_model* model, const float* logits, const float* dac_conf, const float* proximity,
-                       float* probs, float* conf, int32_t* pred, float* cstar, int n, int C, clipmi_stream_t stream) {
-  return launch_procal_rows(model, logits, dac_conf, proximity, probs, conf, pred, cstar, n, C, (hipStream_t)stream);
-}
-
-int clipmi_isotonic_pack(const double* x, const double* y, const int32_t* counts, int n_tables, double* packed) {
-  return isotonic_pack(x, y, counts, n_tables, packed);
-}
-
-int clipmi_isotonic_rows(const clipmi_isotonic_model* model, const float* logits, const float* dac_conf, const float* proximity,
-                         int from_probs, float* probs, float* xs, float* conf, int32_t* pred, int n, int C, clipmi_stream_t stream) {
-  return launch_isotonic_rows(model, logits, dac_conf, proximity, from_probs, probs, xs, conf, pred, n, C, (hipStream_t)stream);
-}
-
-int clipmi_isotonic_keys(const float* logits, const int64_t* labels, float* keys, int n, int C, int from_probs, clipmi_stream_t stream) {
-  return launch_isotonic_keys(logits, labels, keys, n, C, from_probs, (hipStream_t)stream);
-}
-
-int clipmi_isotonic_gap_stats(const float* logits, const int64_t* labels, const int32_t* bin, const float* keys,
-                              const int32_t* key_offset, int n_bins, int32_t* stats, int32_t* status, int n, int C, int from_probs,
-                              clipmi_stream_t stream) {
-  return launch_isotonic_gap_stats(logits, labels, bin, keys, key_offset, n_bins, stats, status, n, C, from_probs, (hipStream_t)stream);
-}
-
-size_t clipmi_tempscale_workspace_bytes(int rows) { return tempscale_workspace_bytes(rows); }
-
-int clipmi_tempscale_batch(const float* cosine, int64_t ld, const int64_t* labels, const int32_t* order, int rows, int n, int C,
-                           const float* theta, float* out, void* workspace, size_t workspace_bytes, clipmi_stream_t stream) {
-  return launch_tempscale_batch(cosine, ld, labels, order, rows, n, C, theta, out, workspace, workspace_bytes, (hipStream_t)stream);
-}
-
-int clipmi_tempscale_fit(const float* cosine, int64_t ld, const int64_t* labels, const int32_t* order, int n, int C, int batch, int epochs,
-                         int drop_last, const float* lr, float momentum, float dampening, float weight_decay, int nesterov, float* state,
-                         float* losses, void* workspace, size_t workspace_bytes, clipmi_stream_t stream) {
-  return launch_tempscale_fit(cosine, ld, labels, order, n, C, batch, epochs, drop_last, lr, momentum, dampening, weight_decay, nesterov,
-                              state, losses, workspace, workspace_bytes, (hipStream_t)stream);
-}
-
-int clipmi_ece_accumulate(const float* conf, const int32_t* pred, const int64_t* labels, int n, double* bins, int n_bins,
-                          clipmi_stream_t stream) {
-  return launch_ece_accumulate(conf, pred, labels, n, bins, n_bins, (hipStream_t)stream);
-}
-
-size_t clipmi_order_stats_workspace_bytes(int n, int k) { return order_stats_workspace_bytes(n, k); }
-
-int clipmi_order_stats(const float* x, int n, const int32_t* ranks, int k, float* out, int32_t* nan_count, void* workspace,
-                       size_t workspace_bytes, clipmi_stream_t stream) {
-  return launch_order_stats(x, n, ranks, k, out, nan_count, workspace, workspace_bytes, (hipStream_t)stream);
-}
-
-int clipmi_group_gap_accumulate(const float* conf, const int32_t* pred, const int64_t* labels, const float* key, const double* key_edges,
-                                int n_key_edges, const double* conf_edges, int n_conf_edges, double* groups, int n, clipmi_stream_t stream) {
-  return launch_group_gap_accumulate(conf, pred, labels, key, key_edges, n_key_edges, conf_edges, n_conf_edges, groups, n,
-                                     (hipStream_t)stream);
-}
-
-int clipmi_class_counts(const int32_t* pred, const int64_t* labels, int n, int C, int64_t* counts, clipmi_stream_t stream) {
-  return launch_class_counts(pred, labels, n, C, counts, (hipStream_t)stream);
 }
 
 // The fp16-stream residual GEMM of a block as an operator (out-proj / c_proj of the image tower, clip/model.py:186-187):

@@ -123,8 +123,14 @@ __global__ __launch_bounds__(256) void scale_add_kernel(const float* __restrict_
 }
 
 }  // namespace
+}  // namespace clipmi
 
-int launch_adapter_blend(const float* f, const float* w1, const float* w2, float ratio, float* out, int B, int E, int H, hipStream_t s) {
+using namespace clipmi;
+
+extern "C" {
+
+int clipmi_adapter_blend(const float* f, const float* w1, const float* w2, float ratio, float* out, int B, int E, int H, clipmi_stream_t stream) {
+  hipStream_t s = (hipStream_t)stream;
   if (B == 0) return CLIPMI_OK;
   CLIPMI_REQUIRE(f && w1 && w2 && out, CLIPMI_ERR_ARG, "adapter_blend: null pointer");
   CLIPMI_REQUIRE(B > 0 && E > 0 && H > 0 && H <= 8192, CLIPMI_ERR_SHAPE, "adapter_blend: B=%d E=%d H=%d", B, E, H);
@@ -132,15 +138,17 @@ int launch_adapter_blend(const float* f, const float* w1, const float* w2, float
   return check_launch("adapter_blend_kernel");
 }
 
-int launch_scale_add(const float* a, const float* b, float alpha, float* out, int64_t n, hipStream_t s) {
+int clipmi_scale_add(const float* a, const float* b, float alpha, float* out, long long n, clipmi_stream_t stream) {
+  hipStream_t s = (hipStream_t)stream;
   if (n == 0) return CLIPMI_OK;
   CLIPMI_REQUIRE(a && b && out && n > 0, CLIPMI_ERR_ARG, "scale_add: null pointer");
   hipLaunchKernelGGL(scale_add_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a, b, alpha, out, n);
   return check_launch("scale_add_kernel");
 }
 
-int launch_cocoop_ctx(const float* img_n, const float* w1, const float* b1, const float* w2, const float* b2, const float* ctx,
-                      float* ctx_shifted, int B, int E, int H, int D, int n_ctx, hipStream_t s) {
+int clipmi_cocoop_ctx(const float* img_n, const float* w1, const float* b1, const float* w2, const float* b2, const float* ctx,
+                      float* ctx_shifted, int B, int E, int H, int D, int n_ctx, clipmi_stream_t stream) {
+  hipStream_t s = (hipStream_t)stream;
   if (B == 0) return CLIPMI_OK;
   CLIPMI_REQUIRE(img_n && w1 && b1 && w2 && b2 && ctx && ctx_shifted, CLIPMI_ERR_ARG, "cocoop_ctx: null pointer");
   CLIPMI_REQUIRE(B > 0 && E > 0 && H > 0 && H <= 4096 && D > 0 && n_ctx > 0, CLIPMI_ERR_SHAPE,
@@ -149,8 +157,10 @@ int launch_cocoop_ctx(const float* img_n, const float* w1, const float* b1, cons
   return check_launch("cocoop_ctx_kernel");
 }
 
-int launch_cocoop_prompts(const void* base, int base_dtype, const float* ctx_shifted, half_t* prompts, int nb, int C, int L, int D,
-                          int n_ctx, hipStream_t s) {
+int clipmi_cocoop_prompts(const void* base, int base_dtype, const float* ctx_shifted, void* prompts_, int nb, int C, int L, int D,
+                          int n_ctx, clipmi_stream_t stream) {
+  hipStream_t s = (hipStream_t)stream;
+  half_t* prompts = (half_t*)prompts_;
   if (nb == 0 || C == 0) return CLIPMI_OK;
   CLIPMI_REQUIRE(base && ctx_shifted && prompts, CLIPMI_ERR_ARG, "cocoop_prompts: null pointer");
   CLIPMI_REQUIRE(nb > 0 && C > 0 && L > 1 && D > 0 && D % 8 == 0 && n_ctx > 0 && n_ctx < L - 1, CLIPMI_ERR_SHAPE,
@@ -169,8 +179,9 @@ int launch_cocoop_prompts(const void* base, int base_dtype, const float* ctx_shi
   return check_launch("cocoop_prompts_kernel");
 }
 
-int launch_logits_per_image(const float* img_n, const float* txt, float scale, const float* dac_conf, float* logits, float* conf,
-                            int32_t* pred, float* txt_n_last, int B, int C, int E, hipStream_t s) {
+int clipmi_logits_per_image(const float* img_n, const float* txt, float scale, const float* dac_conf, float* logits, float* conf,
+                            int32_t* pred, float* txt_n_last, int B, int C, int E, clipmi_stream_t stream) {
+  hipStream_t s = (hipStream_t)stream;
   if (B == 0) return CLIPMI_OK;
   CLIPMI_REQUIRE(img_n && txt && logits, CLIPMI_ERR_ARG, "logits_per_image: null pointer (img_n, txt and logits are required)");
   CLIPMI_REQUIRE(B > 0 && C > 0 && E > 0, CLIPMI_ERR_SHAPE, "logits_per_image: B=%d C=%d E=%d", B, C, E);
@@ -182,4 +193,4 @@ int launch_logits_per_image(const float* img_n, const float* txt, float scale, c
   return rc;
 }
 
-}  // namespace clipmi
+}  // extern "C"

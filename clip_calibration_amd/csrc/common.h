@@ -259,68 +259,11 @@ int launch_eot_rows(const int32_t* eot, int32_t* rows, int C, int L, hipStream_t
 int launch_cast_f32(const float* src, void* dst, int dtype, int64_t n, hipStream_t s);
 int launch_cast_f16(const half_t* src, void* dst, int dtype, int64_t n, hipStream_t s);
 int launch_rows_out(const void* src, int src_dtype, void* dst, int dst_dtype, int C, int rows, int L, int D, hipStream_t s);   // [C*rows, D] -> [C, L, D], zeros behind `rows`
-int launch_group_mean(const float* in, float* out, int G, int P, int E, hipStream_t s);
-int launch_l2_normalize(const void* in, int in_dtype, float* out, int rows, int E, hipStream_t s);
-int launch_l2_normalize_to(const void* in, int in_dtype, void* out, int out_dtype, int rows, int E, hipStream_t s);
-int launch_logits(const float* img_n, const float* txt_n, float scale, const float* dac_conf, float* logits,
-                  float* conf, int32_t* pred, int B, int C, int E, hipStream_t s);
-size_t fused_tail_workspace_bytes(int B, int C);
-int launch_fused_tail(const void* img, int img_dtype, int normalize, const float* txt_n, float scale, const float* dac_conf, float* logits,
-                      float* img_n_out, float* conf, int32_t* pred, const int64_t* labels, double* bins, int n_bins, void* workspace,
-                      size_t workspace_bytes, int B, int C, int E, hipStream_t s);
+int launch_l2_normalize(const void* in, int in_dtype, float* out, int rows, int E, hipStream_t s);   // also the unfused tail's first step (logits.hip)
+// logits.hip: the DAC / softmax top-1 row pass of clipmi_logits, also behind clipmi_logits_per_image (cocoop.hip)
 int launch_calibrate_rows(float* logits, const float* dac_conf, float* conf, int32_t* pred, int B, int C, hipStream_t s);
-int launch_softmax_rows(const float* logits, const float* dac_conf, float* probs, float* conf, int32_t* pred, int B, int C,
-                        hipStream_t s);
-int launch_conv3x3(const half_t* x, const half_t* w, const float* bias, half_t* out, int B, int H, int W, int C, int Cout, int relu,
-                   hipStream_t s);
-int launch_im2col3x3_nchw(const void* image, int dtype, half_t* col, int B, int Cin, int H, int W, int stride, int Kpad, hipStream_t s);
-int launch_im2col3x3_nhwc(const half_t* x, half_t* col, int B, int H, int W, int C, int Kpad, hipStream_t s);
-int launch_avgpool_nhwc(const half_t* x, half_t* y, int B, int H, int W, int C, int k, hipStream_t s);
-int launch_attnpool_tokens(const half_t* x, const float* pos, half_t* tokens, int B, int HW, int C, hipStream_t s);
-int launch_attnpool(const half_t* q, const half_t* kv, half_t* out, int B, int T, int heads, hipStream_t s);
-int launch_adapter_blend(const float* f, const float* w1, const float* w2, float ratio, float* out, int B, int E, int H, hipStream_t s);
-int launch_scale_add(const float* a, const float* b, float alpha, float* out, int64_t n, hipStream_t s);
-int launch_cocoop_ctx(const float* img_n, const float* w1, const float* b1, const float* w2, const float* b2, const float* ctx,
-                      float* ctx_shifted, int B, int E, int H, int D, int n_ctx, hipStream_t s);
-int launch_cocoop_prompts(const void* base, int base_dtype, const float* ctx_shifted, half_t* prompts, int nb, int C, int L, int D,
-                          int n_ctx, hipStream_t s);
-int launch_logits_per_image(const float* img_n, const float* txt, float scale, const float* dac_conf, float* logits, float* conf,
-                            int32_t* pred, float* txt_n_last, int B, int C, int E, hipStream_t s);
-int launch_ece_accumulate(const float* conf, const int32_t* pred, const int64_t* labels, int n, double* bins,
-                          int n_bins, hipStream_t s);
-
-size_t preprocess_workspace_bytes(const clipmi_image_desc* images, int B, int n_px, int filter);   // 0 on bad arguments
-int launch_preprocess(const void* pixels, int64_t pixels_bytes, const clipmi_image_desc* images, int B, int n_px, int filter,
-                      const float* table, void* out, int out_dtype, void* workspace, size_t workspace_bytes, hipStream_t s);
-int launch_knn(const float* q, const float* refs, float* out, int Nq, int Nr, int E, int K, hipStream_t s);
-int launch_procal_kde(const clipmi_procal_model* model, const float* conf, const float* proximity, float* cstar, int n, hipStream_t s);
-int launch_procal_rows(const clipmi_procal_model* model, const float* logits, const float* dac_conf, const float* proximity, float* probs,
-                       float* conf, int32_t* pred, float* cstar, int n, int C, hipStream_t s);
-int isotonic_pack(const double* x, const double* y, const int32_t* counts, int n_tables, double* packed);
-int launch_isotonic_rows(const clipmi_isotonic_model* model, const float* logits, const float* dac_conf, const float* proximity,
-                         int from_probs, float* probs, float* xs, float* conf, int32_t* pred, int n, int C, hipStream_t s);
-int launch_isotonic_keys(const float* logits, const int64_t* labels, float* keys, int n, int C, int from_probs, hipStream_t s);
-int launch_isotonic_gap_stats(const float* logits, const int64_t* labels, const int32_t* bin, const float* keys, const int32_t* key_offset,
-                              int n_bins, int32_t* stats, int32_t* status, int n, int C, int from_probs, hipStream_t s);
 
 static inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 static inline size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
-
-// tempscale.hip: the one-parameter TempScaling fit from cached cosine logits (trainers/calibration/tempscaling.py:146-169)
-size_t tempscale_workspace_bytes(int rows);   // 0 on rows < 1
-int launch_tempscale_batch(const float* cosine, int64_t ld, const int64_t* labels, const int32_t* order, int rows, int n, int C,
-                           const float* theta, float* out, void* workspace, size_t workspace_bytes, hipStream_t s);
-int launch_tempscale_fit(const float* cosine, int64_t ld, const int64_t* labels, const int32_t* order, int n, int C, int batch, int epochs,
-                         int drop_last, const float* lr, float momentum, float dampening, float weight_decay, int nesterov, float* state,
-                         float* losses, void* workspace, size_t workspace_bytes, hipStream_t s);
-
-
-// sample_metrics.hip: the evaluator's sample-level metrics (order statistics by radix select, grouped calibration gaps, per-class counts)
-size_t order_stats_workspace_bytes(int n, int k);   // 0 on arguments launch_order_stats refuses
-int launch_order_stats(const float* x, int n, const int32_t* ranks, int k, float* out, int32_t* nan_count, void* workspace,
-                       size_t workspace_bytes, hipStream_t s);
-int launch_group_gap_accumulate(const float* conf, const int32_t* pred, const int64_t* labels, const float* key, const double* key_edges,
-                                int n_key_edges, const double* conf_edges, int n_conf_edges, double* groups, int n, hipStream_t s);
-int launch_class_counts(const int32_t* pred, const int64_t* labels, int n, int C, int64_t* counts, hipStream_t s);
 
 }  // namespace clipmi

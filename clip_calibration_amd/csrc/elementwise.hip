@@ -264,15 +264,6 @@ __global__ __launch_bounds__(256) void group_mean_kernel(const float* __restrict
 
 }  // namespace
 
-int launch_group_mean(const float* in, float* out, int G, int P, int E, hipStream_t s) {
-  if (G == 0) return CLIPMI_OK;
-  CLIPMI_REQUIRE(in && out, CLIPMI_ERR_ARG, "group_mean: null pointer");
-  CLIPMI_REQUIRE(G > 0 && P > 0 && E > 0, CLIPMI_ERR_SHAPE, "group_mean: G=%d P=%d E=%d", G, P, E);
-  const int64_t total = (int64_t)G * E;
-  hipLaunchKernelGGL(group_mean_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, in, out, G, P, E);
-  return check_launch("group_mean_kernel");
-}
-
 int launch_patchify(const void* image, int image_dtype, half_t* col, int B, int R, int P, int Kpad, hipStream_t s) {
   if (B == 0) return CLIPMI_OK;
   CLIPMI_REQUIRE(image && col, CLIPMI_ERR_ARG, "patchify: null pointer");
@@ -416,10 +407,27 @@ int launch_rows_out(const void* src, int src_dtype, void* dst, int dst_dtype, in
 }
 
 int launch_l2_normalize(const void* in, int in_dtype, float* out, int rows, int E, hipStream_t s) {
-  return launch_l2_normalize_to(in, in_dtype, out, CLIPMI_F32, rows, E, s);
+  return clipmi_l2_normalize_to(in, in_dtype, out, CLIPMI_F32, rows, E, s);
 }
 
-int launch_l2_normalize_to(const void* in, int in_dtype, void* out_, int out_dtype, int rows, int E, hipStream_t s) {
+}  // namespace clipmi
+
+using namespace clipmi;
+
+extern "C" {
+
+int clipmi_group_mean(const float* in, float* out, int G, int P, int E, clipmi_stream_t stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (G == 0) return CLIPMI_OK;
+  CLIPMI_REQUIRE(in && out, CLIPMI_ERR_ARG, "group_mean: null pointer");
+  CLIPMI_REQUIRE(G > 0 && P > 0 && E > 0, CLIPMI_ERR_SHAPE, "group_mean: G=%d P=%d E=%d", G, P, E);
+  const int64_t total = (int64_t)G * E;
+  hipLaunchKernelGGL(group_mean_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, in, out, G, P, E);
+  return check_launch("group_mean_kernel");
+}
+
+int clipmi_l2_normalize_to(const void* in, int in_dtype, void* out_, int out_dtype, int rows, int E, clipmi_stream_t stream) {
+  hipStream_t s = (hipStream_t)stream;
   if (rows == 0) return CLIPMI_OK;
   CLIPMI_REQUIRE(in && out_, CLIPMI_ERR_ARG, "l2_normalize: null pointer");
   CLIPMI_REQUIRE(rows > 0 && E > 0, CLIPMI_ERR_SHAPE, "l2_normalize: bad shape");
@@ -450,4 +458,4 @@ int launch_l2_normalize_to(const void* in, int in_dtype, void* out_, int out_dty
   return check_launch("l2norm_kernel");
 }
 
-}  // namespace clipmi
+}  // extern "C"

@@ -2004,8 +2004,15 @@ int launch_gemm(const GemmArgs& a, hipStream_t s) {
   }
 }
 
-int launch_conv3x3(const half_t* x, const half_t* w, const float* bias, half_t* out, int B, int H, int W, int C, int Cout, int relu,
-                   hipStream_t s) {
+}  // namespace clipmi
+
+using namespace clipmi;
+
+extern "C" int clipmi_conv3x3_nhwc(const void* x_, const void* w_, const float* bias, void* out_, int B, int H, int W, int C, int Cout, int relu,
+                                   clipmi_stream_t stream) {
+  hipStream_t s = (hipStream_t)stream;
+  const half_t *x = (const half_t*)x_, *w = (const half_t*)w_;
+  half_t* out = (half_t*)out_;
   if (B == 0) return CLIPMI_OK;
   CLIPMI_REQUIRE(x && w && bias && out, CLIPMI_ERR_ARG, "conv3x3: null pointer");
   CLIPMI_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0 && C % 64 == 0 && Cout > 0 && Cout % 8 == 0, CLIPMI_ERR_SHAPE,
@@ -2022,5 +2029,3 @@ int launch_conv3x3(const half_t* x, const half_t* w, const float* bias, half_t* 
   }
   return relu ? launch_conv_tile<T256w8, CLIPMI_EPI_BIAS_RELU>(k, cv, s) : launch_conv_tile<T256w8, CLIPMI_EPI_BIAS>(k, cv, s);
 }
-
-}  // namespace clipmi

@@ -241,8 +241,13 @@ int check_model(const clipmi_isotonic_model* m, RowsArgs& a, bool has_proximity)
 }
 
 }  // namespace
+}  // namespace clipmi
 
-int isotonic_pack(const double* x, const double* y, const int32_t* counts, int n_tables, double* packed) {
+using namespace clipmi;
+
+extern "C" {
+
+int clipmi_isotonic_pack(const double* x, const double* y, const int32_t* counts, int n_tables, double* packed) {
   CLIPMI_REQUIRE(x && y && counts && packed, CLIPMI_ERR_ARG, "isotonic_pack: null pointer");
   CLIPMI_REQUIRE(n_tables >= 1 && n_tables <= MAXT, CLIPMI_ERR_SHAPE, "isotonic_pack: n_tables=%d (1 .. %d)", n_tables, MAXT);
   int64_t total = 0;
@@ -273,7 +278,8 @@ int isotonic_pack(const double* x, const double* y, const int32_t* counts, int n
   return CLIPMI_OK;
 }
 
-int launch_isotonic_keys(const float* logits, const int64_t* labels, float* keys, int n, int C, int from_probs, hipStream_t s) {
+int clipmi_isotonic_keys(const float* logits, const int64_t* labels, float* keys, int n, int C, int from_probs, clipmi_stream_t stream) {
+  hipStream_t s = (hipStream_t)stream;
   if (n == 0) return CLIPMI_OK;
   CLIPMI_REQUIRE(n > 0 && C > 0, CLIPMI_ERR_SHAPE, "isotonic_keys: n=%d C=%d", n, C);
   CLIPMI_REQUIRE(logits && labels && keys, CLIPMI_ERR_ARG, "isotonic_keys: null pointer (logits, labels and keys are required)");
@@ -281,8 +287,9 @@ int launch_isotonic_keys(const float* logits, const int64_t* labels, float* keys
   return check_launch("isotonic_keys_kernel");
 }
 
-int launch_isotonic_gap_stats(const float* logits, const int64_t* labels, const int32_t* bin, const float* keys, const int32_t* key_offset,
-                              int n_bins, int32_t* stats, int32_t* status, int n, int C, int from_probs, hipStream_t s) {
+int clipmi_isotonic_gap_stats(const float* logits, const int64_t* labels, const int32_t* bin, const float* keys, const int32_t* key_offset,
+                              int n_bins, int32_t* stats, int32_t* status, int n, int C, int from_probs, clipmi_stream_t stream) {
+  hipStream_t s = (hipStream_t)stream;
   CLIPMI_REQUIRE(n >= 0 && C > 0, CLIPMI_ERR_SHAPE, "isotonic_gap_stats: n=%d C=%d", n, C);
   CLIPMI_REQUIRE(n_bins >= 1 && n_bins <= MAXT, CLIPMI_ERR_SHAPE, "isotonic_gap_stats: n_bins=%d (1 .. %d)", n_bins, MAXT);
   CLIPMI_REQUIRE(key_offset && keys && stats && status, CLIPMI_ERR_ARG,
@@ -310,8 +317,9 @@ int launch_isotonic_gap_stats(const float* logits, const int64_t* labels, const 
   return check_launch("isotonic_stats_kernel");
 }
 
-int launch_isotonic_rows(const clipmi_isotonic_model* model, const float* logits, const float* dac_conf, const float* proximity,
-                         int from_probs, float* probs, float* xs, float* conf, int32_t* pred, int n, int C, hipStream_t s) {
+int clipmi_isotonic_rows(const clipmi_isotonic_model* model, const float* logits, const float* dac_conf, const float* proximity,
+                         int from_probs, float* probs, float* xs, float* conf, int32_t* pred, int n, int C, clipmi_stream_t stream) {
+  hipStream_t s = (hipStream_t)stream;
   if (n == 0) return CLIPMI_OK;
   CLIPMI_REQUIRE(n > 0 && C > 0, CLIPMI_ERR_SHAPE, "isotonic_rows: n=%d C=%d", n, C);
   CLIPMI_REQUIRE(logits && conf && pred, CLIPMI_ERR_ARG, "isotonic_rows: null pointer (logits, conf and pred are required)");
@@ -329,4 +337,4 @@ int launch_isotonic_rows(const clipmi_isotonic_model* model, const float* logits
   return check_launch("isotonic_rows_kernel");
 }
 
-}  // namespace clipmi
+}  // extern "C"

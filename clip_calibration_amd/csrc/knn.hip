@@ -95,8 +95,14 @@ __global__ __launch_bounds__(256) void knn_kernel(const float* __restrict__ q, c
 }
 
 }  // namespace
+}  // namespace clipmi
 
-int launch_knn(const float* q, const float* refs, float* out, int Nq, int Nr, int E, int K, hipStream_t s) {
+using namespace clipmi;
+
+extern "C" {
+
+int clipmi_knn_dists(const float* q, const float* refs, float* out, int Nq, int Nr, int E, int K, clipmi_stream_t stream) {
+  hipStream_t s = (hipStream_t)stream;
   if (Nq == 0) return CLIPMI_OK;
   CLIPMI_REQUIRE(q && refs && out, CLIPMI_ERR_ARG, "knn: null pointer");
   CLIPMI_REQUIRE(Nq > 0 && Nr > 0 && E > 0 && E % EC == 0, CLIPMI_ERR_SHAPE, "knn: Nq=%d Nr=%d E=%d (E %% 64 == 0)", Nq, Nr, E);
@@ -106,4 +112,4 @@ int launch_knn(const float* q, const float* refs, float* out, int Nq, int Nr, in
   return check_launch("knn_kernel");
 }
 
-}  // namespace clipmi
+}  // extern "C"

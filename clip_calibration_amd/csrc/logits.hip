@@ -637,8 +637,24 @@ __global__ __launch_bounds__(256, 2) void fused_tail_kernel(const TI* __restrict
 
 }  // namespace
 
-int launch_logits(const float* img_n, const float* txt_n, float scale, const float* dac_conf, float* logits, float* conf,
-                  int32_t* pred, int B, int C, int E, hipStream_t s) {
+// the row pass behind clipmi_logits and clipmi_logits_per_image (cocoop.hip)
+int launch_calibrate_rows(float* logits, const float* dac_conf, float* conf, int32_t* pred, int B, int C, hipStream_t s) {
+  if (B == 0) return CLIPMI_OK;
+  CLIPMI_REQUIRE(logits, CLIPMI_ERR_ARG, "calibrate_rows: null logits");
+  CLIPMI_REQUIRE(B > 0 && C > 0, CLIPMI_ERR_SHAPE, "calibrate_rows: B=%d C=%d", B, C);
+  hipLaunchKernelGGL(row_calibrate_kernel, dim3((B + 3) / 4), dim3(256), 0, s, logits, dac_conf, conf, pred, B, C, (float*)nullptr);
+  return check_launch("row_calibrate_kernel");
+}
+
+}  // namespace clipmi
+
+using namespace clipmi;
+
+extern "C" {
+
+int clipmi_logits(const float* img_n, const float* txt_n, float scale, const float* dac_conf, float* logits, float* conf,
+                  int32_t* pred, int B, int C, int E, clipmi_stream_t stream) {
+  hipStream_t s = (hipStream_t)stream;
   if (B == 0) return CLIPMI_OK;
   CLIPMI_REQUIRE(img_n && txt_n && logits, CLIPMI_ERR_ARG, "logits: null pointer (img_n, txt_n and logits are required)");
   CLIPMI_REQUIRE(B > 0 && C > 0 && E > 0 && E % 16 == 0, CLIPMI_ERR_SHAPE, "logits: B=%d C=%d E=%d unsupported (E %% 16 == 0)", B, C, E);
@@ -654,11 +670,14 @@ int launch_logits(const float* img_n, const float* txt_n, float scale, const flo
 // then [B][ceil(C/64)] 16-byte row-pass partials (need no initialisation).  The counter region does not move with B: a caller may
 // reuse one buffer for calls of different sizes, and a region that held another call's partials must never be read as counters.
 constexpr size_t TAIL_COUNTER_BYTES = 64 * 1024;
-size_t fused_tail_workspace_bytes(int B, int C) { return TAIL_COUNTER_BYTES + align256((size_t)B * ((C + 63) / 64) * sizeof(TailPartial)); }
+size_t clipmi_fused_tail_workspace_bytes(int B, int C) {
+  return (B < 0 || C < 0) ? 0 : TAIL_COUNTER_BYTES + align256((size_t)B * ((C + 63) / 64) * sizeof(TailPartial));
+}
 
-int launch_fused_tail(const void* img_, int img_dtype, int normalize, const float* txt_n, float scale, const float* dac_conf, float* logits,
+int clipmi_fused_tail(const void* img_, int img_dtype, int normalize, const float* txt_n, float scale, const float* dac_conf, float* logits,
                       float* img_n_out, float* conf, int32_t* pred, const int64_t* labels, double* bins, int n_bins, void* workspace,
-                      size_t workspace_bytes, int B, int C, int E, hipStream_t s) {
+                      size_t workspace_bytes, int B, int C, int E, clipmi_stream_t stream) {
+  hipStream_t s = (hipStream_t)stream;
   if (B == 0) return CLIPMI_OK;
   CLIPMI_REQUIRE(img_ && txt_n && logits, CLIPMI_ERR_ARG, "fused_tail: null pointer (img, txt_n and logits are required)");
   CLIPMI_REQUIRE(img_dtype == CLIPMI_F32 || img_dtype == CLIPMI_F16, CLIPMI_ERR_ARG, "fused_tail: bad image-feature dtype %d", img_dtype);
@@ -685,15 +704,15 @@ int launch_fused_tail(const void* img_, int img_dtype, int normalize, const floa
     } else {
       CLIPMI_REQUIRE(img_dtype == CLIPMI_F32, CLIPMI_ERR_ARG, "fused_tail: the unfused path takes fp32 normalised features");
     }
-    if ((rc = launch_logits(in, txt_n, scale, dac_conf, logits, conf, pred, B, C, E, s))) return rc;
+    if ((rc = clipmi_logits(in, txt_n, scale, dac_conf, logits, conf, pred, B, C, E, s))) return rc;
     if (bins) {
       CLIPMI_REQUIRE(conf && pred, CLIPMI_ERR_ARG, "fused_tail: the unfused path needs conf and pred buffers for the ECE bins");
-      return launch_ece_accumulate(conf, pred, labels, B, bins, n_bins, s);
+      return clipmi_ece_accumulate(conf, pred, labels, B, bins, n_bins, s);
     }
     return CLIPMI_OK;
   }
-  CLIPMI_REQUIRE(workspace && workspace_bytes >= fused_tail_workspace_bytes(B, C), CLIPMI_ERR_WORKSPACE,
-                 "fused_tail: workspace too small (%zu < %zu)", workspace_bytes, fused_tail_workspace_bytes(B, C));
+  CLIPMI_REQUIRE(workspace && workspace_bytes >= clipmi_fused_tail_workspace_bytes(B, C), CLIPMI_ERR_WORKSPACE,
+                 "fused_tail: workspace too small (%zu < %zu)", workspace_bytes, clipmi_fused_tail_workspace_bytes(B, C));
   const dim3 grid((B + rb - 1) / rb, (C + 63) / 64);
   CLIPMI_REQUIRE(grid.y <= 65535, CLIPMI_ERR_SHAPE, "fused_tail: too many classes");
   int* counters = static_cast<int*>(workspace);
@@ -724,16 +743,9 @@ int launch_fused_tail(const void* img_, int img_dtype, int normalize, const floa
   return check_launch("fused_tail_kernel");
 }
 
-int launch_calibrate_rows(float* logits, const float* dac_conf, float* conf, int32_t* pred, int B, int C, hipStream_t s) {
-  if (B == 0) return CLIPMI_OK;
-  CLIPMI_REQUIRE(logits, CLIPMI_ERR_ARG, "calibrate_rows: null logits");
-  CLIPMI_REQUIRE(B > 0 && C > 0, CLIPMI_ERR_SHAPE, "calibrate_rows: B=%d C=%d", B, C);
-  hipLaunchKernelGGL(row_calibrate_kernel, dim3((B + 3) / 4), dim3(256), 0, s, logits, dac_conf, conf, pred, B, C, (float*)nullptr);
-  return check_launch("row_calibrate_kernel");
-}
-
-int launch_softmax_rows(const float* logits, const float* dac_conf, float* probs, float* conf, int32_t* pred, int B, int C,
-                        hipStream_t s) {
+int clipmi_softmax_rows(const float* logits, const float* dac_conf, float* probs, float* conf, int32_t* pred, int B, int C,
+                        clipmi_stream_t stream) {
+  hipStream_t s = (hipStream_t)stream;
   if (B == 0) return CLIPMI_OK;   // an empty batch has no storage to point at
   CLIPMI_REQUIRE(logits && probs, CLIPMI_ERR_ARG, "softmax_rows: null pointer (logits and probs are required)");
   CLIPMI_REQUIRE(B > 0 && C > 0, CLIPMI_ERR_SHAPE, "softmax_rows: B=%d C=%d", B, C);
@@ -741,8 +753,9 @@ int launch_softmax_rows(const float* logits, const float* dac_conf, float* probs
   return check_launch("row_calibrate_kernel");
 }
 
-int launch_ece_accumulate(const float* conf, const int32_t* pred, const int64_t* labels, int n, double* bins, int n_bins,
-                          hipStream_t s) {
+int clipmi_ece_accumulate(const float* conf, const int32_t* pred, const int64_t* labels, int n, double* bins, int n_bins,
+                          clipmi_stream_t stream) {
+  hipStream_t s = (hipStream_t)stream;
   if (n == 0) return CLIPMI_OK;
   CLIPMI_REQUIRE(conf && pred && labels && bins, CLIPMI_ERR_ARG, "ece: null pointer");
   CLIPMI_REQUIRE(n_bins > 0 && n_bins <= 1024, CLIPMI_ERR_SHAPE, "ece: n_bins=%d unsupported", n_bins);
@@ -753,4 +766,4 @@ int launch_ece_accumulate(const float* conf, const int32_t* pred, const int64_t*
   return check_launch("ece_accumulate_kernel");
 }
 
-}  // namespace clipmi
+}  // extern "C"

@@ -245,14 +245,20 @@ int plan_preprocess(const clipmi_image_desc* images, int B, int n_px, int filter
 }
 
 }  // namespace
+}  // namespace clipmi
 
-size_t preprocess_workspace_bytes(const clipmi_image_desc* images, int B, int n_px, int filter) {
+using namespace clipmi;
+
+extern "C" {
+
+size_t clipmi_preprocess_workspace_bytes(const clipmi_image_desc* images, int B, int n_px, int filter) {
   Plan p;
   return plan_preprocess(images, B, n_px, filter, 0, false, &p) == CLIPMI_OK ? p.total() : 0;
 }
 
-int launch_preprocess(const void* pixels, int64_t pixels_bytes, const clipmi_image_desc* images, int B, int n_px, int filter,
-                      const float* table, void* out, int out_dtype, void* workspace, size_t workspace_bytes, hipStream_t s) {
+int clipmi_preprocess(const void* pixels, int64_t pixels_bytes, const clipmi_image_desc* images, int B, int n_px, int filter,
+                      const float* table, void* out, int out_dtype, void* workspace, size_t workspace_bytes, clipmi_stream_t stream) {
+  hipStream_t s = (hipStream_t)stream;
   CLIPMI_REQUIRE(pixels && table && out && workspace, CLIPMI_ERR_ARG, "preprocess: null pointer");
   CLIPMI_REQUIRE(out_dtype == CLIPMI_F16 || out_dtype == CLIPMI_F32, CLIPMI_ERR_ARG, "preprocess: bad out dtype %d", out_dtype);
   CLIPMI_REQUIRE(pixels_bytes >= 1, CLIPMI_ERR_ARG, "preprocess: empty pixel buffer");
@@ -285,4 +291,4 @@ int launch_preprocess(const void* pixels, int64_t pixels_bytes, const clipmi_ima
   return check_launch("preprocess resample_kernel");
 }
 
-}  // namespace clipmi
+}  // extern "C"

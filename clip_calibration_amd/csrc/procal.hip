@@ -201,8 +201,14 @@ int check_model(const clipmi_procal_model* m, ProcalArgs& a) {
 }
 
 }  // namespace
+}  // namespace clipmi
 
-int launch_procal_kde(const clipmi_procal_model* model, const float* conf, const float* proximity, float* cstar, int n, hipStream_t s) {
+using namespace clipmi;
+
+extern "C" {
+
+int clipmi_procal_kde(const clipmi_procal_model* model, const float* conf, const float* proximity, float* cstar, int n, clipmi_stream_t stream) {
+  hipStream_t s = (hipStream_t)stream;
   if (n == 0) return CLIPMI_OK;
   CLIPMI_REQUIRE(n > 0, CLIPMI_ERR_SHAPE, "procal_kde: n=%d", n);
   CLIPMI_REQUIRE(conf && proximity && cstar, CLIPMI_ERR_ARG, "procal_kde: null pointer (conf, proximity and cstar are required)");
@@ -213,8 +219,9 @@ int launch_procal_kde(const clipmi_procal_model* model, const float* conf, const
   return check_launch("procal_kernel<kde>");
 }
 
-int launch_procal_rows(const clipmi_procal_model* model, const float* logits, const float* dac_conf, const float* proximity, float* probs,
-                       float* conf, int32_t* pred, float* cstar, int n, int C, hipStream_t s) {
+int clipmi_procal_rows(const clipmi_procal_model* model, const float* logits, const float* dac_conf, const float* proximity, float* probs,
+                       float* conf, int32_t* pred, float* cstar, int n, int C, clipmi_stream_t stream) {
+  hipStream_t s = (hipStream_t)stream;
   if (n == 0) return CLIPMI_OK;
   CLIPMI_REQUIRE(n > 0 && C > 0, CLIPMI_ERR_SHAPE, "procal_rows: n=%d C=%d", n, C);
   CLIPMI_REQUIRE(logits && proximity && conf && pred, CLIPMI_ERR_ARG,
@@ -226,4 +233,4 @@ int launch_procal_rows(const clipmi_procal_model* model, const float* logits, co
   return check_launch("procal_kernel<rows>");
 }
 
-}  // namespace clipmi
+}  // extern "C"

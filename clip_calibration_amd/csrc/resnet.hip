@@ -134,8 +134,15 @@ __global__ __launch_bounds__(256) void attnpool_kernel(const half_t* __restrict_
 }
 
 }  // namespace
+}  // namespace clipmi
 
-int launch_im2col3x3_nchw(const void* image, int dtype, half_t* col, int B, int Cin, int H, int W, int stride, int Kpad, hipStream_t s) {
+using namespace clipmi;
+
+extern "C" {
+
+int clipmi_im2col3x3_nchw(const void* image, int dtype, void* col_, int B, int Cin, int H, int W, int stride, int Kpad, clipmi_stream_t stream) {
+  hipStream_t s = (hipStream_t)stream;
+  half_t* col = (half_t*)col_;
   if (B == 0) return CLIPMI_OK;
   CLIPMI_REQUIRE(image && col, CLIPMI_ERR_ARG, "im2col3x3_nchw: null pointer");
   CLIPMI_REQUIRE(B > 0 && Cin > 0 && H > 0 && W > 0 && (stride == 1 || stride == 2) && Kpad >= Cin * 9 && Kpad % 64 == 0, CLIPMI_ERR_SHAPE,
@@ -155,7 +162,10 @@ int launch_im2col3x3_nchw(const void* image, int dtype, half_t* col, int B, int 
   return check_launch("im2col3x3_nchw_kernel");
 }
 
-int launch_im2col3x3_nhwc(const half_t* x, half_t* col, int B, int H, int W, int C, int Kpad, hipStream_t s) {
+int clipmi_im2col3x3_nhwc(const void* x_, void* col_, int B, int H, int W, int C, int Kpad, clipmi_stream_t stream) {
+  hipStream_t s = (hipStream_t)stream;
+  const half_t* x = (const half_t*)x_;
+  half_t* col = (half_t*)col_;
   if (B == 0) return CLIPMI_OK;
   CLIPMI_REQUIRE(x && col, CLIPMI_ERR_ARG, "im2col3x3_nhwc: null pointer");
   CLIPMI_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0 && Kpad >= 9 * C && Kpad % 64 == 0, CLIPMI_ERR_SHAPE,
@@ -166,7 +176,10 @@ int launch_im2col3x3_nhwc(const half_t* x, half_t* col, int B, int H, int W, int
   return check_launch("im2col3x3_nhwc_kernel");
 }
 
-int launch_avgpool_nhwc(const half_t* x, half_t* y, int B, int H, int W, int C, int k, hipStream_t s) {
+int clipmi_avgpool_nhwc(const void* x_, void* y_, int B, int H, int W, int C, int k, clipmi_stream_t stream) {
+  hipStream_t s = (hipStream_t)stream;
+  const half_t* x = (const half_t*)x_;
+  half_t* y = (half_t*)y_;
   if (B == 0) return CLIPMI_OK;
   CLIPMI_REQUIRE(x && y, CLIPMI_ERR_ARG, "avgpool: null pointer");
   CLIPMI_REQUIRE(B > 0 && C > 0 && k >= 1 && H % k == 0 && W % k == 0, CLIPMI_ERR_SHAPE, "avgpool: B=%d H=%d W=%d C=%d k=%d", B, H, W, C, k);
@@ -180,14 +193,20 @@ int launch_avgpool_nhwc(const half_t* x, half_t* y, int B, int H, int W, int C, 
   return check_launch("avgpool_nhwc_kernel");
 }
 
-int launch_attnpool_tokens(const half_t* x, const float* pos, half_t* tokens, int B, int HW, int C, hipStream_t s) {
+int clipmi_attnpool_tokens(const void* x_, const float* pos, void* tokens_, int B, int HW, int C, clipmi_stream_t stream) {
+  hipStream_t s = (hipStream_t)stream;
+  const half_t* x = (const half_t*)x_;
+  half_t* tokens = (half_t*)tokens_;
   if (B == 0) return CLIPMI_OK;
   CLIPMI_REQUIRE(x && pos && tokens && B > 0 && HW > 0 && C > 0, CLIPMI_ERR_ARG, "attnpool_tokens: bad argument");
   hipLaunchKernelGGL(attnpool_tokens_kernel, dim3(B), dim3(256), 0, s, x, pos, tokens, HW, C);
   return check_launch("attnpool_tokens_kernel");
 }
 
-int launch_attnpool(const half_t* q, const half_t* kv, half_t* out, int B, int T, int heads, hipStream_t s) {
+int clipmi_attnpool(const void* q_, const void* kv_, void* out_, int B, int T, int heads, clipmi_stream_t stream) {
+  hipStream_t s = (hipStream_t)stream;
+  const half_t *q = (const half_t*)q_, *kv = (const half_t*)kv_;
+  half_t* out = (half_t*)out_;
   if (B == 0) return CLIPMI_OK;
   CLIPMI_REQUIRE(q && kv && out && B > 0 && T > 0 && heads > 0, CLIPMI_ERR_ARG, "attnpool: bad argument");
   const int64_t items = (int64_t)B * heads;
@@ -195,4 +214,4 @@ int launch_attnpool(const half_t* q, const half_t* kv, half_t* out, int B, int T
   return check_launch("attnpool_kernel");
 }
 
-}  // namespace clipmi
+}  // extern "C"

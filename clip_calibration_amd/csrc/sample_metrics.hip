@@ -218,14 +218,20 @@ int grid_for(int n, int per_thread, int cap) {
 size_t select_state_bytes() { return align256(sizeof(SelectState)); }
 
 }  // namespace
+}  // namespace clipmi
 
-size_t order_stats_workspace_bytes(int n, int k) {
+using namespace clipmi;
+
+extern "C" {
+
+size_t clipmi_order_stats_workspace_bytes(int n, int k) {
   if (n < 1 || k < 1 || k > MAXK) return 0;
   return select_state_bytes() + align256((size_t)4 * k * RADIX * sizeof(uint32_t));
 }
 
-int launch_order_stats(const float* x, int n, const int32_t* ranks, int k, float* out, int32_t* nan_count, void* workspace,
-                       size_t workspace_bytes, hipStream_t s) {
+int clipmi_order_stats(const float* x, int n, const int32_t* ranks, int k, float* out, int32_t* nan_count, void* workspace,
+                       size_t workspace_bytes, clipmi_stream_t stream) {
+  hipStream_t s = (hipStream_t)stream;
   CLIPMI_REQUIRE(n >= 1, CLIPMI_ERR_SHAPE, "order_stats: n=%d (>= 1)", n);
   CLIPMI_REQUIRE(k >= 1 && k <= MAXK, CLIPMI_ERR_SHAPE, "order_stats: k=%d (1 .. %d)", k, MAXK);
   CLIPMI_REQUIRE(x && ranks && out && nan_count, CLIPMI_ERR_ARG, "order_stats: null pointer (x, ranks, out and nan_count are required)");
@@ -238,7 +244,7 @@ int launch_order_stats(const float* x, int n, const int32_t* ranks, int k, float
   }
   CLIPMI_REQUIRE(workspace, CLIPMI_ERR_ARG, "order_stats: null workspace");
   CLIPMI_REQUIRE((uintptr_t)workspace % 16 == 0, CLIPMI_ERR_ARG, "order_stats: the workspace must be 16-byte aligned");
-  const size_t need = order_stats_workspace_bytes(n, k);
+  const size_t need = clipmi_order_stats_workspace_bytes(n, k);
   CLIPMI_REQUIRE(workspace_bytes >= need, CLIPMI_ERR_WORKSPACE, "order_stats: workspace of %zu bytes, %zu needed", workspace_bytes, need);
   if (const hipError_t e = hipMemsetAsync(workspace, 0, need, s); e != hipSuccess) {
     (void)hipGetLastError();
@@ -261,8 +267,9 @@ int launch_order_stats(const float* x, int n, const int32_t* ranks, int k, float
   return CLIPMI_OK;
 }
 
-int launch_group_gap_accumulate(const float* conf, const int32_t* pred, const int64_t* labels, const float* key, const double* key_edges,
-                                int n_key_edges, const double* conf_edges, int n_conf_edges, double* groups, int n, hipStream_t s) {
+int clipmi_group_gap_accumulate(const float* conf, const int32_t* pred, const int64_t* labels, const float* key, const double* key_edges,
+                                int n_key_edges, const double* conf_edges, int n_conf_edges, double* groups, int n, clipmi_stream_t stream) {
+  hipStream_t s = (hipStream_t)stream;
   CLIPMI_REQUIRE(n >= 0, CLIPMI_ERR_SHAPE, "group_gap_accumulate: n=%d", n);
   CLIPMI_REQUIRE(n_key_edges >= 0 && n_conf_edges >= 0, CLIPMI_ERR_SHAPE, "group_gap_accumulate: %d key edges, %d confidence edges",
                  n_key_edges, n_conf_edges);
@@ -278,7 +285,8 @@ int launch_group_gap_accumulate(const float* conf, const int32_t* pred, const in
   return check_launch("group_gap_kernel");
 }
 
-int launch_class_counts(const int32_t* pred, const int64_t* labels, int n, int C, int64_t* counts, hipStream_t s) {
+int clipmi_class_counts(const int32_t* pred, const int64_t* labels, int n, int C, int64_t* counts, clipmi_stream_t stream) {
+  hipStream_t s = (hipStream_t)stream;
   CLIPMI_REQUIRE(n >= 0, CLIPMI_ERR_SHAPE, "class_counts: n=%d", n);
   CLIPMI_REQUIRE(C >= 1 && C <= (0x7fffffff - 1) / 3, CLIPMI_ERR_SHAPE, "class_counts: C=%d", C);
   if (n == 0) return CLIPMI_OK;
@@ -294,4 +302,4 @@ int launch_class_counts(const int32_t* pred, const int64_t* labels, int n, int C
   return check_launch("class_counts_kernel");
 }
 
-}  // namespace clipmi
+}  // extern "C"

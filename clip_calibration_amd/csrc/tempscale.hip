@@ -117,8 +117,8 @@ int check_matrix(const char* who, const float* cosine, int64_t ld, const int64_t
 int check_workspace(const char* who, const void* workspace, size_t bytes, int rows) {
   CLIPMI_REQUIRE(workspace, CLIPMI_ERR_ARG, "%s: null workspace", who);
   CLIPMI_REQUIRE((uintptr_t)workspace % 8 == 0, CLIPMI_ERR_ARG, "%s: the workspace must be 8-byte aligned", who);
-  CLIPMI_REQUIRE(bytes >= tempscale_workspace_bytes(rows), CLIPMI_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, bytes,
-                 tempscale_workspace_bytes(rows));
+  CLIPMI_REQUIRE(bytes >= clipmi_tempscale_workspace_bytes(rows), CLIPMI_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, bytes,
+                 clipmi_tempscale_workspace_bytes(rows));
   return CLIPMI_OK;
 }
 
@@ -129,11 +129,17 @@ int launch_rows(const float* cosine, int64_t ld, const int64_t* labels, const in
 }
 
 }  // namespace
+}  // namespace clipmi
 
-size_t tempscale_workspace_bytes(int rows) { return rows < 1 ? 0 : align256((size_t)rows * sizeof(float2)); }
+using namespace clipmi;
 
-int launch_tempscale_batch(const float* cosine, int64_t ld, const int64_t* labels, const int32_t* order, int rows, int n, int C,
-                           const float* theta, float* out, void* workspace, size_t workspace_bytes, hipStream_t s) {
+extern "C" {
+
+size_t clipmi_tempscale_workspace_bytes(int rows) { return rows < 1 ? 0 : align256((size_t)rows * sizeof(float2)); }
+
+int clipmi_tempscale_batch(const float* cosine, int64_t ld, const int64_t* labels, const int32_t* order, int rows, int n, int C,
+                           const float* theta, float* out, void* workspace, size_t workspace_bytes, clipmi_stream_t stream) {
+  hipStream_t s = (hipStream_t)stream;
   if (int rc = check_matrix("tempscale_batch", cosine, ld, labels, n, C)) return rc;
   CLIPMI_REQUIRE(theta && out, CLIPMI_ERR_ARG, "tempscale_batch: null pointer (theta and out are required)");
   CLIPMI_REQUIRE(rows >= 1, CLIPMI_ERR_SHAPE, "tempscale_batch: rows=%d (>= 1)", rows);
@@ -145,9 +151,10 @@ int launch_tempscale_batch(const float* cosine, int64_t ld, const int64_t* label
   return check_launch("tempscale_finish_kernel");
 }
 
-int launch_tempscale_fit(const float* cosine, int64_t ld, const int64_t* labels, const int32_t* order, int n, int C, int batch, int epochs,
+int clipmi_tempscale_fit(const float* cosine, int64_t ld, const int64_t* labels, const int32_t* order, int n, int C, int batch, int epochs,
                          int drop_last, const float* lr, float momentum, float dampening, float weight_decay, int nesterov, float* state,
-                         float* losses, void* workspace, size_t workspace_bytes, hipStream_t s) {
+                         float* losses, void* workspace, size_t workspace_bytes, clipmi_stream_t stream) {
+  hipStream_t s = (hipStream_t)stream;
   if (int rc = check_matrix("tempscale_fit", cosine, ld, labels, n, C)) return rc;
   CLIPMI_REQUIRE(lr && state, CLIPMI_ERR_ARG, "tempscale_fit: null pointer (lr and state are required)");
   CLIPMI_REQUIRE((uintptr_t)state % 4 == 0, CLIPMI_ERR_ARG, "tempscale_fit: the state must be 4-byte aligned");
@@ -179,4 +186,4 @@ int launch_tempscale_fit(const float* cosine, int64_t ld, const int64_t* labels,
   return CLIPMI_OK;
 }
 
-}  // namespace clipmi
+}  // extern "C"

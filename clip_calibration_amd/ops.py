@@ -43,6 +43,29 @@ def _opt(t: Optional[torch.Tensor], name: str, dtypes) -> Tuple[Optional[torch.T
     return t, t.data_ptr()
 
 
+def _in_place(t, dtype: torch.dtype, message: str, exc=TypeError, numel: Optional[int] = None) -> None:
+    """A tensor the kernel works on where it lies (no ``.contiguous()`` copy may stand in for it): contiguous, on the GPU, of ``dtype``."""
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and t.is_contiguous() and (numel is None or t.numel() == numel)):
+        raise exc(message)
+
+
+def _dac(dac_conf: Optional[torch.Tensor], classes: int, who: str) -> Tuple[Optional[torch.Tensor], Optional[int]]:
+    """The optional DAC factors, fp32 with one entry per class: (tensor, pointer)."""
+    dac_conf, pd = _opt(dac_conf, "dac_conf", (torch.float32,))
+    if dac_conf is not None and dac_conf.numel() != classes:
+        raise ValueError(f"{who}: dac_conf must have one entry per class")
+    return dac_conf, pd
+
+
+def _conf_pred(want: bool, rows: int, device):
+    """The optional top-1 outputs: (conf fp32 [rows], pred int32 [rows], their pointers), or four None."""
+    if not want:
+        return None, None, None, None
+    conf = torch.empty(rows, dtype=torch.float32, device=device)
+    pred = torch.empty(rows, dtype=torch.int32, device=device)
+    return conf, pred, conf.data_ptr(), pred.data_ptr()
+
+
 def gemm_f16(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None,
              residual: Optional[torch.Tensor] = None, epilogue: int = _lib.EPI_NONE,
              out_dtype: torch.dtype = torch.float16, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -68,20 +91,18 @@ def gemm_residual_f16(a: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, x16:
     """``x16 <- fp16(x16 + a @ w^T + bias)`` in place (one rounding of the fp32 sum): the residual GEMM of a block on the fp16
     stream (reference clip/model.py:186-187).  Returns (stats fp32 [8, M, 2], parts): the LayerNorm-fold row partials
     ``stats[t, m] = (sum, sum of squares)`` over the t-th column tile of the rounded row m, ``parts`` tiles of them."""
-    import ctypes as C
     a = _dev(a, "a", (torch.float16,))
     w = _dev(w, "w", (torch.float16,))
     bias = _dev(bias, "bias", (torch.float32,))
-    if not (isinstance(x16, torch.Tensor) and x16.is_cuda and x16.dtype == torch.float16 and x16.is_contiguous()):
-        raise TypeError("gemm_residual_f16: x16 must be a contiguous fp16 GPU tensor (it is updated in place)")
+    _in_place(x16, torch.float16, "gemm_residual_f16: x16 must be a contiguous fp16 GPU tensor (it is updated in place)")
     M, K = a.shape
     N = w.shape[0]
     if w.shape[1] != K or tuple(x16.shape) != (M, N) or bias.numel() != N:
         raise ValueError(f"gemm_residual_f16: a {tuple(a.shape)}, w {tuple(w.shape)}, bias {tuple(bias.shape)}, x16 {tuple(x16.shape)}")
     stats = torch.empty(8, M, 2, dtype=torch.float32, device=a.device)
-    parts = C.c_int(0)
+    parts = ctypes.c_int(0)
     check(lib.clipmi_gemm_residual_f16(a.data_ptr(), K, w.data_ptr(), K, bias.data_ptr(), x16.data_ptr(), N, stats.data_ptr(),
-                                       C.byref(parts), M, N, K, _stream()), "clipmi_gemm_residual_f16")
+                                       ctypes.byref(parts), M, N, K, _stream()), "clipmi_gemm_residual_f16")
     return stats, parts.value
 
 
@@ -100,12 +121,10 @@ def gemm_residual_fold(a: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, x: 
     """``x <- x + a @ w^T + bias`` in place on the fp32 stream (reference clip/model.py:186-187), plus the LayerNorm-fold outputs:
     x16 = fp16(x) and the row partials ``stats[t, m] = (sum, sum of squares)`` of the fp32 row m over column tile t.
     Returns (x16, stats fp32 [8, M, 2], parts)."""
-    import ctypes as C
     a = _dev(a, "a", (torch.float16,))
     w = _dev(w, "w", (torch.float16,))
     bias = _dev(bias, "bias", (torch.float32,))
-    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()):
-        raise TypeError("gemm_residual_fold: x must be a contiguous fp32 GPU tensor (it is updated in place)")
+    _in_place(x, torch.float32, "gemm_residual_fold: x must be a contiguous fp32 GPU tensor (it is updated in place)")
     M, K = a.shape
     N = w.shape[0]
     if w.shape[1] != K or tuple(x.shape) != (M, N) or bias.numel() != N:
@@ -116,9 +135,9 @@ def gemm_residual_fold(a: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, x: 
     if tuple(x16.shape) != (M, N):
         raise ValueError(f"gemm_residual_fold: x16 {tuple(x16.shape)}, expected [{M},{N}]")
     stats = torch.empty(8, M, 2, dtype=torch.float32, device=a.device)
-    parts = C.c_int(0)
+    parts = ctypes.c_int(0)
     check(lib.clipmi_gemm_residual_fold(a.data_ptr(), K, w.data_ptr(), K, bias.data_ptr(), x.data_ptr(), N, x16.data_ptr(),
-                                        stats.data_ptr(), C.byref(parts), M, N, K, _stream()), "clipmi_gemm_residual_fold")
+                                        stats.data_ptr(), ctypes.byref(parts), M, N, K, _stream()), "clipmi_gemm_residual_fold")
     return x16, stats, parts.value
 
 
@@ -133,8 +152,7 @@ def gemm_ln_fold(a: torch.Tensor, w_f: torch.Tensor, c: torch.Tensor, g: torch.T
     w_f = _dev(w_f, "w_f", (torch.float16,))
     c = _dev(c, "c", (torch.float32,))
     g = _dev(g, "g", (torch.float32,))
-    if not (isinstance(stats, torch.Tensor) and stats.is_cuda and stats.dtype == torch.float32 and stats.is_contiguous()):
-        raise TypeError("gemm_ln_fold: stats must be a contiguous fp32 GPU tensor")
+    _in_place(stats, torch.float32, "gemm_ln_fold: stats must be a contiguous fp32 GPU tensor")
     N, K = w_f.shape
     M = a.shape[0]
     if a.shape[1] != K:
@@ -282,9 +300,7 @@ def fused_tail(img: torch.Tensor, txt_n: torch.Tensor, scale: float, dac_conf: O
     Cn = txt_n.shape[0]
     if txt_n.shape[1] != E:
         raise ValueError("fused_tail: feature widths differ")
-    dac_conf, pd = _opt(dac_conf, "dac_conf", (torch.float32,))
-    if dac_conf is not None and dac_conf.numel() != Cn:
-        raise ValueError("fused_tail: dac_conf must have one entry per class")
+    dac_conf, pd = _dac(dac_conf, Cn, "fused_tail")
     labels, pl = _opt(labels, "labels", (torch.int64,))
     bins, pb = _opt(bins, "bins", (torch.float64,))
     if (pb is None) != (pl is None):
@@ -293,12 +309,7 @@ def fused_tail(img: torch.Tensor, txt_n: torch.Tensor, scale: float, dac_conf: O
         raise ValueError("fused_tail: bins must hold 3*(n_bins+1) float64 and labels one entry per image")
     logits = torch.empty(B, Cn, dtype=torch.float32, device=img.device)
     img_n = torch.empty(B, E, dtype=torch.float32, device=img.device) if normalize else img
-    conf = pred = None
-    pc = pp = None
-    if want_conf_pred or bins is not None:
-        conf = torch.empty(B, dtype=torch.float32, device=img.device)
-        pred = torch.empty(B, dtype=torch.int32, device=img.device)
-        pc, pp = conf.data_ptr(), pred.data_ptr()
+    conf, pred, pc, pp = _conf_pred(want_conf_pred or bins is not None, B, img.device)
     key, ws = _tail_workspace(img.device, B, Cn)
     try:
         with torch.cuda.device(img.device):
@@ -315,16 +326,9 @@ def softmax_rows(logits: torch.Tensor, dac_conf: Optional[torch.Tensor] = None, 
     """probs = softmax(logits * dac_conf[argmax]) row-wise (vl_calibrator.py:83-109, DAC / plain branches); logits untouched."""
     logits = _dev(logits, "logits", (torch.float32,))
     B, Cn = logits.shape
-    dac_conf, pd = _opt(dac_conf, "dac_conf", (torch.float32,))
-    if dac_conf is not None and dac_conf.numel() != Cn:
-        raise ValueError("softmax_rows: dac_conf must have one entry per class")
+    dac_conf, pd = _dac(dac_conf, Cn, "softmax_rows")
     probs = torch.empty_like(logits)
-    conf = pred = None
-    pc = pp = None
-    if want_conf_pred:
-        conf = torch.empty(B, dtype=torch.float32, device=logits.device)
-        pred = torch.empty(B, dtype=torch.int32, device=logits.device)
-        pc, pp = conf.data_ptr(), pred.data_ptr()
+    conf, pred, pc, pp = _conf_pred(want_conf_pred, B, logits.device)
     check(lib.clipmi_softmax_rows(logits.data_ptr(), pd, probs.data_ptr(), pc, pp, B, Cn, _stream()), "clipmi_softmax_rows")
     return (probs, conf, pred) if want_conf_pred else probs
 
@@ -362,9 +366,7 @@ def procal_rows(model: "_lib.ProcalModel", logits: torch.Tensor, proximity: torc
     if logits.dim() != 2 or proximity.dim() != 1 or proximity.shape[0] != logits.shape[0]:
         raise ValueError(f"procal_rows: logits {tuple(logits.shape)} need a proximity of one entry per row, got {tuple(proximity.shape)}")
     N, Cn = logits.shape
-    dac_conf, pd = _opt(dac_conf, "dac_conf", (torch.float32,))
-    if dac_conf is not None and dac_conf.numel() != Cn:
-        raise ValueError("procal_rows: dac_conf must have one entry per class")
+    dac_conf, pd = _dac(dac_conf, Cn, "procal_rows")
     probs = torch.empty_like(logits) if want_probs else None
     cstar = torch.empty(N, dtype=torch.float32, device=logits.device) if want_cstar else None
     conf = torch.empty(N, dtype=torch.float32, device=logits.device)
@@ -387,9 +389,7 @@ def isotonic_rows(model: "_lib.IsotonicModel", logits: torch.Tensor, proximity: 
     proximity, pp = _opt(proximity, "proximity", (torch.float32,))
     if proximity is not None and (proximity.dim() != 1 or proximity.shape[0] != N):
         raise ValueError(f"isotonic_rows: logits {tuple(logits.shape)} need a proximity of one entry per row, got {tuple(proximity.shape)}")
-    dac_conf, pd = _opt(dac_conf, "dac_conf", (torch.float32,))
-    if dac_conf is not None and dac_conf.numel() != Cn:
-        raise ValueError("isotonic_rows: dac_conf must have one entry per class")
+    dac_conf, pd = _dac(dac_conf, Cn, "isotonic_rows")
     probs = torch.empty_like(logits) if want_probs else None
     xs = torch.empty_like(logits) if want_x else None
     conf = torch.empty(N, dtype=torch.float32, device=logits.device)
@@ -500,9 +500,8 @@ def group_gap_accumulate(conf: torch.Tensor, pred: torch.Tensor, labels: torch.T
     if groups is None:
         groups = torch.zeros(3, G, dtype=torch.float64, device=conf.device)
     else:
-        if not (isinstance(groups, torch.Tensor) and groups.is_cuda and groups.dtype == torch.float64 and groups.is_contiguous()
-                and groups.numel() == 3 * G):
-            raise ValueError(f"group_gap_accumulate: groups must be a contiguous float64 GPU tensor of 3 * {G} (it is updated in place)")
+        _in_place(groups, torch.float64, f"group_gap_accumulate: groups must be a contiguous float64 GPU tensor of 3 * {G} (it is updated in place)",
+                  exc=ValueError, numel=3 * G)
     check(lib.clipmi_group_gap_accumulate(conf.data_ptr(), pred.data_ptr(), labels.data_ptr(), pk, pke, nk, pce, nc, groups.data_ptr(),
                                           conf.numel(), _stream()), "clipmi_group_gap_accumulate")
     return groups
@@ -633,16 +632,10 @@ def logits_per_image(img_n: torch.Tensor, txt: torch.Tensor, scale: float, dac_c
     if txt.dim() != 3 or txt.shape[0] != B or txt.shape[2] != E:
         raise ValueError(f"logits_per_image: txt must be [B={B}, C, E={E}], got {tuple(txt.shape)}")
     Cn = txt.shape[1]
-    dac_conf, pd = _opt(dac_conf, "dac_conf", (torch.float32,))
-    if dac_conf is not None and dac_conf.numel() != Cn:
-        raise ValueError("logits_per_image: dac_conf must have one entry per class")
+    dac_conf, pd = _dac(dac_conf, Cn, "logits_per_image")
     logits = torch.empty(B, Cn, dtype=torch.float32, device=img_n.device)
-    conf = pred = last = None
-    pc = pp = pl = None
-    if want_conf_pred:
-        conf = torch.empty(B, dtype=torch.float32, device=img_n.device)
-        pred = torch.empty(B, dtype=torch.int32, device=img_n.device)
-        pc, pp = conf.data_ptr(), pred.data_ptr()
+    conf, pred, pc, pp = _conf_pred(want_conf_pred, B, img_n.device)
+    last = pl = None
     if want_last_text:
         last = torch.empty(Cn, E, dtype=torch.float32, device=img_n.device)
         pl = last.data_ptr()

@@ -20,6 +20,78 @@ def _header_functions():
     return sorted(set(re.findall(r"\b(clipmi_[a-z0-9_]+)\s*\(", src)))
 
 
+_C_SCALARS = {"int": ("int", 4), "unsigned": ("int", 4), "int32_t": ("int", 4), "int64_t": ("int", 8), "long long": ("int", 8),
+              "unsigned long long": ("int", 8), "size_t": ("int", 8), "float": ("float", 4), "double": ("float", 8)}
+
+
+def _c_class(decl, named):
+    """(class, bytes) of a C return type (named=False) or of one parameter declaration with its name (named=True)."""
+    if "*" in decl or "clipmi_stream_t" in decl.split():
+        return ("pointer", 8)
+    words = [w for w in decl.split() if w != "const"]
+    if named:
+        assert len(words) >= 2, f"parameter without a name: {decl!r}"
+        words = words[:-1]
+    return _C_SCALARS[" ".join(words)]      # KeyError: a type this parser does not know -- extend it, do not skip the prototype
+
+
+def _header_prototypes():
+    """{name: (return class, [parameter classes])} of every clipmi_* prototype of include/clipmi.h."""
+    src = re.sub(r"/\*.*?\*/", "", open(_lib.HEADER_PATH).read(), flags=re.S)
+    src = re.sub(r"^\s*#.*$", "", src, flags=re.M).replace('extern "C" {', "")
+    src = re.sub(r"\{[^{}]*\}", "", src)                      # struct and enum bodies
+    protos = {}
+    for stmt in src.split(";"):
+        if not re.search(r"\bclipmi_[a-z0-9_]+\s*\(", stmt):
+            continue
+        m = re.fullmatch(r"\s*([\w\s*]+?)\s*\b(clipmi_[a-z0-9_]+)\s*\(([^()]*)\)\s*", stmt)
+        assert m, f"cannot parse the prototype {stmt.strip()!r}"
+        ret, name, params = m.groups()
+        assert name not in protos, name
+        params = [] if params.strip() == "void" else [a.strip() for a in params.split(",")]
+        protos[name] = (_c_class(ret, False), [_c_class(a, True) for a in params])
+    return protos
+
+
+def _ctypes_class(t):
+    if t in (ctypes.c_void_p, ctypes.c_char_p) or issubclass(t, ctypes._Pointer):
+        return ("pointer", ctypes.sizeof(t))
+    assert issubclass(t, ctypes._SimpleCData), t
+    return ("float" if t._type_ in "fd" else "int", ctypes.sizeof(t))
+
+
+def _header_constants():
+    src = re.sub(r"/\*.*?\*/", "", open(_lib.HEADER_PATH).read(), flags=re.S)
+    found = re.findall(r"^\s*#define\s+(CLIPMI_\w+)\s+(-?\d+)u?\s*$", src, flags=re.M)
+    for body in re.findall(r"\benum\s*\{([^{}]*)\}", src):
+        found += re.findall(r"\b(CLIPMI_\w+)\s*=\s*(-?\d+)", body)
+    names = [n for n, _ in found]
+    assert len(names) == len(set(names)), names
+    return {n: int(v) for n, v in found}
+
+
+def test_ctypes_signatures_and_constants_match_the_header():
+    """_lib._SIGNATURES is typed by hand: every clipmi_* prototype of include/clipmi.h must have an entry of the same arity with the same
+    class (pointer, integer, float) and width as the return type and at every argument, and the constants _lib restates must be the
+    header's.  A prototype that cannot be parsed fails the test; none is skipped."""
+    protos = _header_prototypes()
+    assert sorted(protos) == _header_functions() == sorted(_lib._SIGNATURES)
+    for name, (ret, params) in protos.items():
+        res, args = _lib._SIGNATURES[name]
+        assert _ctypes_class(res) == ret, f"{name}: returns {ret} in the header, {res.__name__} in _lib"
+        assert len(args) == len(params), f"{name}: {len(params)} parameters in the header, {len(args)} in _lib"
+        for i, (a, want) in enumerate(zip(args, params)):
+            assert _ctypes_class(a) == want, f"{name}: argument {i} is {want} in the header, {a.__name__} in _lib"
+    consts = _header_constants()
+    restated = ["ABI_VERSION", "OK", "ERR_ARG", "ERR_SHAPE", "ERR_HIP", "ERR_WORKSPACE", "ERR_STATE", "F16", "F32", "EPI_NONE", "EPI_BIAS",
+                "EPI_BIAS_QUICKGELU", "EPI_BIAS_RESIDUAL", "EPI_BIAS_RELU", "EPI_BIAS_RESIDUAL16_RELU", "CALL_DEFAULT", "CALL_STREAM_F32",
+                "CALL_STREAM_F16", "FILTER_BILINEAR", "FILTER_BICUBIC", "COMM_ID_BYTES", "ISOTONIC_MAX_TABLES", "ORDER_STATS_MAX_RANKS",
+                "GROUP_GAP_MAX_GROUPS"]
+    assert sorted(consts) == sorted("CLIPMI_" + n for n in restated), "a header constant _lib does not restate, or the reverse"
+    for n in restated:
+        assert getattr(_lib, n) == consts["CLIPMI_" + n], n
+
+
 def test_library_exports_every_declared_symbol():
     declared = _header_functions()
     assert len(declared) >= 20

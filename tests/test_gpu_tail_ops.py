@@ -102,7 +102,7 @@ def fused_tail(clipmi_option, d_img, dtype, d_txt, scale, dac, normalize, unfuse
 
 def _paths(dtype, normalize, E):
     """(unfused?) settings clipmi_fused_tail takes for these features: the separate launches refuse fp16 features that they do not normalise,
-    so fp16 pre-normalised rows run fused only.  Every shape sent through fused_tail() must satisfy launch_fused_tail's `fits` (E % 64 == 0 and
+    so fp16 pre-normalised rows run fused only.  Every shape sent through fused_tail() must satisfy clipmi_fused_tail's `fits` (E % 64 == 0 and
     2 RB (2 E + 16) + 16 <= 160 KiB of LDS, RB = 16 up to B = 512 and 32 above): otherwise the library runs the separate launches under
     tail_unfused = 0 as well, and the fused kernel is not tested."""
     assert fused_fits(1, E) and fused_fits(513, E), f"E = {E}: clipmi_fused_tail would fall back to the separate launches"
