@@ -142,6 +142,10 @@ _SIGNATURES = {
     "clipmi_tempscale_workspace_bytes": (_sz, [_i]),
     "clipmi_tempscale_batch": (_i, [_vp, _i64, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "clipmi_tempscale_fit": (_i, [_vp, _i64, _vp, _vp, _i, _i, _i, _i, _i, _vp, _f, _f, _f, _i, _vp, _vp, _vp, _sz, _vp]),
+    "clipmi_adapter_train_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "clipmi_adapter_train_step": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _vp, _i, _f, _f, _f, _i, _vp, _vp, _sz, _vp]),
+    "clipmi_adapter_fit": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _f, _vp, _i, _f, _f, _f, _i, _vp,
+                                _vp, _sz, _vp]),
     "clipmi_order_stats_workspace_bytes": (_sz, [_i, _i]),
     "clipmi_order_stats": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
     "clipmi_group_gap_accumulate": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _vp]),

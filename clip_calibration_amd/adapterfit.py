@@ -1,0 +1,170 @@
+"""CLIP-Adapter's bottleneck trained on the GPU (reference trainers/classification/clip_adapter.py:138-187).
+
+The reference trains the bias-free bottleneck E -> E/4 -> E with Dassl's epoch loop: every step runs both frozen towers, blends the
+adapter's output with the raw image features by ``ratio``, normalises, takes ``F.cross_entropy`` of ``exp(logit_scale)`` times the cosine
+against the frozen text features and one ``torch.optim.SGD`` step on the two matrices.  The towers are frozen and, with the shipped
+config, so is the context: a step is a function of the image features, the labels, the text features and the optimiser settings.
+csrc/adapter_train.hip computes forward, backward and the SGD step in two launches per step, with no autograd graph.
+
+Two ways in.  ``fit_adapter`` trains from a cached [N, E] feature matrix and enqueues every step of every epoch on the current stream with
+no synchronisation between the steps and one at the end (labels that arrive on the GPU are copied to the host once, before the first
+launch, for their range check): that equals the reference's loop only when the train transform is deterministic, since the reference's
+``random_resized_crop`` + ``random_flip`` change the features every epoch.  ``AdapterFitState.step`` takes one batch of features at a time,
+for callers that run the image tower on every step.
+
+Dassl is not part of this repository's environment.  The defaults below -- SGD at 0.002 with momentum 0.9 and weight decay 5e-4, no
+dampening, no Nesterov; 200 epochs in batches of 32, the last short batch dropped; a constant warm-up epoch that hands over to a cosine
+schedule; ratio 0.2 -- restate configs/trainers/CLIP_Adapter/vit_b16_c4_ep200_batch32.yaml and Dassl's public defaults and are UNVERIFIED
+here; that is why each of them is an argument.  Dassl's random sampler is the caller's ``order``.
+"""
+from __future__ import annotations
+
+import math
+from typing import Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import ops
+from .tempfit import cosine_warmup_schedule, steps_per_epoch
+
+
+def _host_int_array(x, name: str) -> np.ndarray:
+    a = x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+    if a.dtype.kind not in "iu":
+        raise TypeError(f"fit_adapter: {name} must be integers, got {a.dtype}")
+    return a
+
+
+def _check_optimiser(who: str, momentum: float, dampening: float, weight_decay: float, nesterov: bool) -> None:
+    if not (0.0 <= momentum < 1.0 and 0.0 <= dampening < 1.0 and weight_decay >= 0.0):
+        raise ValueError(f"{who}: momentum={momentum}, dampening={dampening} (both in [0, 1)), weight_decay={weight_decay} (>= 0)")
+    if nesterov and (momentum <= 0.0 or dampening != 0.0):
+        raise ValueError(f"{who}: Nesterov momentum requires a momentum and zero dampening")
+
+
+def _check_shapes(who: str, features, text_features, w1, w2):
+    if not isinstance(features, torch.Tensor) or features.dim() != 2 or features.shape[0] < 1:
+        raise ValueError(f"{who}: features must be a [N >= 1, E] tensor")
+    N, E = features.shape
+    if not isinstance(text_features, torch.Tensor) or text_features.dim() != 2 or text_features.shape[1] != E or text_features.shape[0] < 2:
+        raise ValueError(f"{who}: text features {tuple(getattr(text_features, 'shape', ()))} must be [C >= 2, E = {E}]")
+    if (not isinstance(w1, torch.Tensor) or not isinstance(w2, torch.Tensor) or w1.dim() != 2 or w1.shape[0] < 1 or w1.shape[1] != E
+            or tuple(w2.shape) != (E, w1.shape[0])):
+        raise ValueError(f"{who}: adapter shapes do not chain (E = {E}, w1 {tuple(getattr(w1, 'shape', ()))}, w2 {tuple(getattr(w2, 'shape', ()))})")
+    return N, E, w1.shape[0], text_features.shape[0]
+
+
+def _labels(who: str, labels, N: int, C: int) -> np.ndarray:
+    lab = _host_int_array(labels, "labels")
+    if lab.shape != (N,):
+        raise ValueError(f"{who}: {N} rows need {N} labels, got {lab.shape}")
+    if lab.min() < 0 or lab.max() >= C:
+        raise ValueError(f"{who}: labels span [{int(lab.min())}, {int(lab.max())}], outside the {C} classes [0, {C})")
+    return lab
+
+
+def _need_gpu(t: torch.Tensor, name: str) -> None:
+    if not t.is_cuda:
+        raise RuntimeError(f"clipmi: `{name}` must be a tensor on the GPU (got {t.device}); the HIP path has no CPU fallback")
+
+
+def _labels_on(labels, lab: np.ndarray, dev) -> torch.Tensor:
+    if isinstance(labels, torch.Tensor) and labels.is_cuda and labels.dtype == torch.int64:
+        return labels
+    return torch.from_numpy(lab.astype(np.int64)).to(dev)
+
+
+def _master(w: torch.Tensor, dev) -> torch.Tensor:
+    """A fresh contiguous fp32 copy on the device: the master weights the kernels update in place."""
+    return w.detach().to(device=dev, dtype=torch.float32, copy=True).contiguous()
+
+
+def fit_adapter(features: torch.Tensor, labels, text_features: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor, ratio: float = 0.2,
+                logit_scale: float = 4.6052, epochs: int = 200, lr: float = 0.002, batch_size: int = 32, momentum: float = 0.9,
+                dampening: float = 0.0, weight_decay: float = 5e-4, nesterov: bool = False, lr_per_epoch: Optional[Sequence[float]] = None,
+                order=None, drop_last: bool = True, return_history: bool = False):
+    """Train CLIP-Adapter's bottleneck on cached ``features`` fp32 [N, E] (raw, un-normalised image features on the GPU; the rows may be a
+    column slice of a wider matrix), ``labels`` [N] and the frozen L2-normalised ``text_features`` fp32 [C, E], starting from ``w1``
+    [H, E] and ``w2`` [E, H] (not modified): ``epochs`` passes of ``torch.optim.SGD(lr, momentum, dampening, weight_decay, nesterov)`` on
+    ``F.cross_entropy(exp(logit_scale) * normalise(ratio * adapter(f) + (1 - ratio) * f) @ text_features.T, labels)`` over batches of
+    ``batch_size``, all in fp32.
+
+    ``lr_per_epoch`` gives every epoch's rate; None takes ``cosine_warmup_schedule(lr, epochs)``.  ``order`` is an integer [epochs, N]
+    array of sample indices, batch k of epoch e being ``order[e, k * batch_size : (k + 1) * batch_size]``; None is 0 .. N-1 in every
+    epoch.  The last batch of an epoch is short unless ``drop_last`` drops it.
+
+    Labels (and ``order``) are checked against their ranges on the host before anything is launched -- a label tensor on the GPU is
+    copied to the host for that, which waits for whatever produced it; from the first launch on nothing synchronises until the one wait
+    at the end.  Returns the fitted fp32 ``(w1, w2)`` on the device, or ``(w1, w2, per-step batch losses as a float32 numpy array)`` with
+    ``return_history``.  The defaults are unverified restatements of the reference's config and Dassl's (module docstring)."""
+    N, E, H, C = _check_shapes("fit_adapter", features, text_features, w1, w2)
+    epochs, batch_size = int(epochs), int(batch_size)
+    if epochs < 0 or batch_size < 1:
+        raise ValueError(f"fit_adapter: epochs={epochs} (>= 0), batch_size={batch_size} (>= 1)")
+    _check_optimiser("fit_adapter", momentum, dampening, weight_decay, nesterov)
+    if not (math.isfinite(ratio) and math.isfinite(logit_scale)):
+        raise ValueError(f"fit_adapter: ratio={ratio}, logit_scale={logit_scale} (both finite)")
+    lab = _labels("fit_adapter", labels, N, C)
+    if order is not None:
+        order = _host_int_array(order, "order")
+        if order.shape != (epochs, N):
+            raise ValueError(f"fit_adapter: order {order.shape} must be [epochs, N] = [{epochs}, {N}]")
+        if order.size and (order.min() < 0 or order.max() >= N):
+            raise ValueError(f"fit_adapter: order holds sample indices outside [0, {N})")
+    rates = cosine_warmup_schedule(lr, epochs) if lr_per_epoch is None else [float(r) for r in lr_per_epoch]
+    if len(rates) != epochs:
+        raise ValueError(f"fit_adapter: {len(rates)} learning rates for {epochs} epochs")
+    per_epoch = steps_per_epoch(N, batch_size, drop_last)
+    _need_gpu(features, "features")
+    dev = features.device
+    w1, w2 = _master(w1, dev), _master(w2, dev)
+    if epochs * per_epoch == 0:
+        return (w1, w2, np.zeros(0, np.float32)) if return_history else (w1, w2)
+    m1, m2 = (torch.zeros_like(w1), torch.zeros_like(w2)) if momentum != 0.0 else (None, None)
+    lr_steps = torch.from_numpy(np.repeat(np.asarray(rates, np.float64), per_epoch).astype(np.float32)).to(dev)
+    order_d = None if order is None else torch.from_numpy(np.ascontiguousarray(order, dtype=np.int32)).to(dev)
+    losses = ops.adapter_fit(features, _labels_on(labels, lab, dev), text_features, w1, w2, m1, m2, lr_steps, ratio,
+                             float(np.float32(math.exp(logit_scale))), batch_size, epochs, momentum, dampening, weight_decay, nesterov, order_d,
+                             drop_last, first_step=True, want_losses=return_history)
+    torch.cuda.current_stream().synchronize()   # the run's one synchronisation
+    return (w1, w2, losses.cpu().numpy()) if return_history else (w1, w2)
+
+
+class AdapterFitState:
+    """The training state of CLIP-Adapter's bottleneck for callers that produce the image features step by step (a random train
+    transform: the image tower runs on every batch): fp32 master weights ``w1`` [H, E], ``w2`` [E, H], their momentum buffers and the
+    number of steps taken.  ``step`` enqueues one forward, backward and SGD update and does not synchronise."""
+
+    def __init__(self, text_features: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor, ratio: float = 0.2, logit_scale: float = 4.6052,
+                 momentum: float = 0.9, dampening: float = 0.0, weight_decay: float = 5e-4, nesterov: bool = False):
+        _check_optimiser("AdapterFitState", momentum, dampening, weight_decay, nesterov)
+        if not isinstance(text_features, torch.Tensor) or text_features.dim() != 2 or text_features.shape[0] < 2:
+            raise ValueError("AdapterFitState: text features must be a [C >= 2, E] tensor")
+        _need_gpu(text_features, "text_features")
+        dev = text_features.device
+        self.text_features = text_features
+        self.w1, self.w2 = _master(w1, dev), _master(w2, dev)
+        _check_shapes("AdapterFitState", text_features[:1], text_features, self.w1, self.w2)
+        self.m1, self.m2 = (torch.zeros_like(self.w1), torch.zeros_like(self.w2)) if momentum != 0.0 else (None, None)
+        self.ratio, self.scale = float(ratio), float(np.float32(math.exp(logit_scale)))
+        self.momentum, self.dampening, self.weight_decay, self.nesterov = momentum, dampening, weight_decay, nesterov
+        self.steps = 0
+
+    def step(self, features: torch.Tensor, labels, lr, want_loss: bool = False) -> Optional[torch.Tensor]:
+        """One SGD step on the batch ``features`` fp32 [B, E] (raw image features on the GPU) and ``labels`` [B] at the rate ``lr``: an fp32
+        tensor of one element on the device is read where it lies (slice a per-step rate array filled once: ``rates[k:k + 1]``); a Python
+        number is uploaded on every call, a host-to-device copy the per-step path is better off without.  A label tensor on the GPU is taken as it is -- a label
+        outside [0, C) then makes the weights NaN, it is never used as an address; host labels are range-checked.  Returns the batch
+        loss, fp32 [1] on the device, when ``want_loss``."""
+        N, _, _, C = _check_shapes("AdapterFitState.step", features, self.text_features, self.w1, self.w2)
+        _need_gpu(features, "features")
+        if isinstance(labels, torch.Tensor) and labels.is_cuda and labels.dtype == torch.int64:
+            labels_d = labels
+        else:
+            labels_d = torch.from_numpy(_labels("AdapterFitState.step", labels, N, C).astype(np.int64)).to(features.device)
+        lr_d = lr if isinstance(lr, torch.Tensor) else torch.tensor([float(lr)], dtype=torch.float32).to(features.device)
+        loss = ops.adapter_train_step(features, labels_d, self.text_features, self.w1, self.w2, self.m1, self.m2, lr_d, self.ratio, self.scale,
+                                      self.steps == 0, self.momentum, self.dampening, self.weight_decay, self.nesterov, want_loss=want_loss)
+        self.steps += 1
+        return loss

@@ -593,6 +593,90 @@ def tempscale_fit(cosine: torch.Tensor, labels: torch.Tensor, state: torch.Tenso
     return losses
 
 
+# ---- CLIP-Adapter training (clip_adapter.py:138-187) ---------------------------------------------------------------
+def _adapter_problem(features, labels, text, w1, w2, m1, m2, momentum: float, who: str):
+    """The tensors of one adapter training call, checked: raw features fp32 [N, E] (contiguous rows, row stride kept), labels int64 [N],
+    text fp32 [C, E], and the weights and momentum buffers fp32, contiguous, updated where they lie.  Returns (features, labels, text)."""
+    if (isinstance(features, torch.Tensor) and features.dim() == 2 and features.shape[0] > 0 and features.stride(1) == 1
+            and features.stride(0) >= features.shape[1]):
+        _dev(features[:1], "features", (torch.float32,))     # read in place with its row stride: the device and dtype checks only
+    else:
+        features = _dev(features, "features", (torch.float32,))
+    labels = _dev(labels, "labels", (torch.int64,))
+    text = _dev(text, "text_features", (torch.float32,))
+    if features.dim() != 2 or features.shape[0] < 1 or labels.shape != (features.shape[0],):
+        raise ValueError(f"{who}: features {tuple(features.shape)} must be [N >= 1, E] with one label per row, got labels {tuple(labels.shape)}")
+    E = features.shape[1]
+    if text.dim() != 2 or text.shape[1] != E or text.shape[0] < 2:
+        raise ValueError(f"{who}: text features {tuple(text.shape)} must be [C >= 2, E = {E}]")
+    if not isinstance(w1, torch.Tensor) or w1.dim() != 2 or w1.shape[1] != E or w1.shape[0] < 1 or tuple(getattr(w2, "shape", ())) != (E, w1.shape[0]):
+        raise ValueError(f"{who}: adapter shapes do not chain (E = {E}, w1 {tuple(getattr(w1, 'shape', ()))}, w2 {tuple(getattr(w2, 'shape', ()))})")
+    for t, name in ((w1, "w1"), (w2, "w2")) + (((m1, "m1"), (m2, "m2")) if momentum != 0.0 else ()):
+        _dev(t, name, (torch.float32,))
+        _in_place(t, torch.float32, f"{who}: {name} is updated in place: a contiguous fp32 tensor on the GPU")
+    if momentum != 0.0 and (m1.shape != w1.shape or m2.shape != w2.shape):
+        raise ValueError(f"{who}: the momentum buffers {tuple(m1.shape)}, {tuple(m2.shape)} must have the weights' shapes")
+    return features, labels, text
+
+
+def _adapter_workspace(rows: int, E: int, H: int, Cn: int, device) -> torch.Tensor:
+    return torch.empty(lib.clipmi_adapter_train_workspace_bytes(rows, E, H, Cn), dtype=torch.uint8, device=device)
+
+
+def adapter_train_step(features: torch.Tensor, labels: torch.Tensor, text: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor,
+                       m1: Optional[torch.Tensor], m2: Optional[torch.Tensor], lr: torch.Tensor, ratio: float, scale: float, first_step: bool,
+                       momentum: float = 0.0, dampening: float = 0.0, weight_decay: float = 0.0, nesterov: bool = False,
+                       want_loss: bool = False) -> Optional[torch.Tensor]:
+    """One SGD step of CLIP-Adapter's bottleneck on the batch ``features`` fp32 [B, E] (raw image features), enqueued without a host
+    synchronisation (include/clipmi.h, clipmi_adapter_train_step).  ``w1`` [H, E], ``w2`` [E, H] and the momentum buffers are updated in
+    place; ``lr`` fp32 [1] on the device; ``scale`` = exp(logit_scale); ``first_step`` initialises the buffers from this step's gradient.
+    Returns the batch loss fp32 [1] on the device when ``want_loss``."""
+    features, labels, text = _adapter_problem(features, labels, text, w1, w2, m1, m2, momentum, "adapter_train_step")
+    lr = _dev(lr, "lr", (torch.float32,))
+    if lr.numel() != 1:
+        raise ValueError(f"adapter_train_step: lr {tuple(lr.shape)} must hold one rate")
+    (B, E), H, Cn = features.shape, w1.shape[0], text.shape[0]
+    loss = torch.empty(1, dtype=torch.float32, device=features.device) if want_loss else None
+    ws = _adapter_workspace(B, E, H, Cn, features.device)
+    pm1, pm2 = (m1.data_ptr(), m2.data_ptr()) if momentum != 0.0 else (None, None)
+    check(lib.clipmi_adapter_train_step(features.data_ptr(), features.stride(0), labels.data_ptr(), text.data_ptr(), w1.data_ptr(), w2.data_ptr(),
+                                        pm1, pm2, B, E, H, Cn, float(ratio), float(scale), lr.data_ptr(), int(bool(first_step)), float(momentum),
+                                        float(dampening), float(weight_decay), int(bool(nesterov)), None if loss is None else loss.data_ptr(),
+                                        ws.data_ptr(), ws.numel(), _stream()), "clipmi_adapter_train_step")
+    return loss
+
+
+def adapter_fit(features: torch.Tensor, labels: torch.Tensor, text: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor,
+                m1: Optional[torch.Tensor], m2: Optional[torch.Tensor], lr: torch.Tensor, ratio: float, scale: float, batch_size: int, epochs: int,
+                momentum: float = 0.0, dampening: float = 0.0, weight_decay: float = 0.0, nesterov: bool = False,
+                order: Optional[torch.Tensor] = None, drop_last: bool = False, first_step: bool = True,
+                want_losses: bool = False) -> Optional[torch.Tensor]:
+    """The whole SGD run of CLIP-Adapter's bottleneck from the cached ``features`` fp32 [N, E], enqueued without a host synchronisation
+    (include/clipmi.h, clipmi_adapter_fit).  ``w1``, ``w2`` and the momentum buffers are updated in place; ``lr`` fp32 [steps], one rate
+    per step; ``order`` int32 [epochs, N] or None (0 .. N-1 every epoch).  Returns the per-step batch losses fp32 [steps] when
+    ``want_losses``."""
+    features, labels, text = _adapter_problem(features, labels, text, w1, w2, m1, m2, momentum, "adapter_fit")
+    (N, E), H, Cn = features.shape, w1.shape[0], text.shape[0]
+    batch_size, epochs = int(batch_size), int(epochs)
+    if batch_size < 1 or epochs < 0:
+        raise ValueError(f"adapter_fit: batch_size={batch_size} (>= 1), epochs={epochs} (>= 0)")
+    steps = epochs * (N // batch_size if drop_last else -(-N // batch_size))
+    lr = _dev(lr, "lr", (torch.float32,))
+    if lr.shape != (steps,):
+        raise ValueError(f"adapter_fit: lr {tuple(lr.shape)} must hold one rate per step ({steps})")
+    order, po = _opt(order, "order", (torch.int32,))
+    if order is not None and order.shape != (epochs, N):
+        raise ValueError(f"adapter_fit: order {tuple(order.shape)} must be [epochs, N] = [{epochs}, {N}]")
+    losses = torch.empty(steps, dtype=torch.float32, device=features.device) if want_losses else None
+    ws = _adapter_workspace(min(batch_size, N), E, H, Cn, features.device)
+    pm1, pm2 = (m1.data_ptr(), m2.data_ptr()) if momentum != 0.0 else (None, None)
+    check(lib.clipmi_adapter_fit(features.data_ptr(), features.stride(0), labels.data_ptr(), po, text.data_ptr(), w1.data_ptr(), w2.data_ptr(),
+                                 pm1, pm2, N, E, H, Cn, batch_size, epochs, int(bool(drop_last)), float(ratio), float(scale), lr.data_ptr(),
+                                 int(bool(first_step)), float(momentum), float(dampening), float(weight_decay), int(bool(nesterov)),
+                                 None if losses is None else losses.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "clipmi_adapter_fit")
+    return losses
+
+
 # ---- CoCoOp glue (cocoop.py:154-199) -------------------------------------------------------------------------------
 def cocoop_ctx(img_n: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor,
                ctx: torch.Tensor) -> torch.Tensor:

@@ -419,6 +419,46 @@ int clipmi_tempscale_fit(const float* cosine, int64_t ld, const int64_t* labels,
                          int drop_last, const float* lr, float momentum, float dampening, float weight_decay, int nesterov, float* state,
                          float* losses, void* workspace, size_t workspace_bytes, clipmi_stream_t stream);
 
+/* CLIP-Adapter's bottleneck trained on the device (trainers/classification/clip_adapter.py:138-187: both towers frozen, the text
+ * features constant under the shipped config): forward, backward and torch.optim.SGD's step on the two bias-free matrices, all fp32
+ * with fp32 master weights.  feats fp32 [n, E] raw (un-normalised) image features with row stride ld >= E (elements), labels int64
+ * [n], text fp32 [C, E] L2-normalised, w1 [H, E], w2 [E, H] and their momentum buffers m1, m2 of the same shapes (may be NULL when
+ * momentum == 0), ratio as clipmi_adapter_blend takes it, scale = exp(logit_scale).  Per batch of B rows:
+ *   h = relu(f W1^T);  a = relu(h W2^T);  g = ratio a + (1 - ratio) f;  u = g / |g|;  z = scale u T^T;  loss = mean CE(z, y)
+ *   dz = (softmax(z) - onehot(y)) / B;  du = scale dz T;  dg = (du - u (u . du)) / |g|;  da = ratio dg [a > 0];  dW2 = da^T h;
+ *   dh = (da W2) [h > 0];  dW1 = dh^T f;   then on every element of W2 and W1, with the step's rate *lr (device):
+ *   g += weight_decay * w;  buf = g on a first step, else momentum * buf + (1 - dampening) * g;
+ *   g = nesterov ? g + momentum * buf : buf  (momentum != 0 only);  w -= lr * g.
+ * Two launches per step: one workgroup per sample (forward, loss, backward down to da and dh), then one thread per weight element
+ * (the gradient summed over the batch rows in row order, the update in place; the row losses averaged in float64).  Fixed summation
+ * orders, no atomics: the same inputs give the same bits.  A label outside [0, C) or a sample index outside [0, n) is never
+ * dereferenced; it makes the step's loss and the weights NaN.  workspace (device, 8-byte aligned) of
+ * clipmi_adapter_train_workspace_bytes(rows of the widest batch, E, H, C) bytes (0 for shapes the calls refuse outright).  These
+ * exports are additive: the ABI version does not change with them.
+ *
+ * clipmi_adapter_train_step: one step on the batch feats[0 .. rows) -- for callers that run the image tower on every step.  first_step
+ * != 0 initialises the momentum buffers from this step's gradient (torch's first step); loss fp32 [1] (device) or NULL.
+ *
+ * clipmi_adapter_fit: the whole run from a cached feature matrix, epochs * ceil(n / batch) steps (floor with drop_last), enqueued on
+ * `stream` without a host synchronisation; step k of epoch e takes the samples order[e * n + k * batch ..] (order int32 [epochs, n],
+ * device; NULL = 0 .. n-1 in every epoch), the last batch of an epoch may be short.  lr fp32 [steps] (device), one rate per step;
+ * first_step applies to the run's first step; losses fp32 [steps] (device) receives every step's batch loss, or NULL.  epochs == 0:
+ * CLIPMI_OK, nothing is launched.
+ * CLIPMI_ERR_ARG: a null or misaligned pointer, epochs < 0, momentum or dampening outside [0, 1), a negative or non-finite weight
+ * decay, nesterov with zero momentum or non-zero dampening, a non-finite ratio or scale.  CLIPMI_ERR_SHAPE: n or rows < 1, C < 2,
+ * E < 1, H < 1, batch < 1, ld < E, or 4 E + 2 H beyond
+ * the 64 KiB of LDS a sample's workgroup holds (4 E + 2 H + 1056 floats: E = 512, H = 128 need 13 KiB; H may exceed E).
+ * CLIPMI_ERR_WORKSPACE: a workspace that is too small. */
+size_t clipmi_adapter_train_workspace_bytes(int rows, int E, int H, int C);
+int clipmi_adapter_train_step(const float* feats, int64_t ld, const int64_t* labels, const float* text, float* w1, float* w2, float* m1,
+                              float* m2, int rows, int E, int H, int C, float ratio, float scale, const float* lr, int first_step,
+                              float momentum, float dampening, float weight_decay, int nesterov, float* loss, void* workspace,
+                              size_t workspace_bytes, clipmi_stream_t stream);
+int clipmi_adapter_fit(const float* feats, int64_t ld, const int64_t* labels, const int32_t* order, const float* text, float* w1, float* w2,
+                       float* m1, float* m2, int n, int E, int H, int C, int batch, int epochs, int drop_last, float ratio, float scale,
+                       const float* lr, int first_step, float momentum, float dampening, float weight_decay, int nesterov, float* losses,
+                       void* workspace, size_t workspace_bytes, clipmi_stream_t stream);
+
 /* The sample-level metrics of the evaluator on the device (vl_evaluator.py:77-82 macro-F1; tools/metrics.py:132-178 PIECE, :212-236
  * AdaptiveECE) -- SURVEY f-1.  Three small kernels; the host turns their outputs into the scalars (clip_calibration_amd.metrics:
  * quantile_edges_from_order_stats, gap_from_groups, macro_f1_from_counts).  These exports are additive: the ABI version does not
