@@ -22,6 +22,7 @@ COMM_ID_BYTES = 128
 EPI_NONE, EPI_BIAS, EPI_BIAS_QUICKGELU, EPI_BIAS_RESIDUAL, EPI_BIAS_RELU, EPI_BIAS_RESIDUAL16_RELU = 0, 1, 2, 3, 4, 5
 CALL_DEFAULT, CALL_STREAM_F32, CALL_STREAM_F16 = 0, 1, 2   # per-call flags of the tower calls (include/clipmi.h)
 FILTER_BILINEAR, FILTER_BICUBIC = 2, 3                      # clipmi_preprocess filters (Pillow's numbers)
+OPTIM_SGD, OPTIM_ADAM = 0, 1                                # clipmi_taskres_train_step / clipmi_taskres_fit optimisers
 
 
 class ClipmiError(RuntimeError):
@@ -146,6 +147,11 @@ _SIGNATURES = {
     "clipmi_adapter_train_step": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _vp, _i, _f, _f, _f, _i, _vp, _vp, _sz, _vp]),
     "clipmi_adapter_fit": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _f, _vp, _i, _f, _f, _f, _i, _vp,
                                 _vp, _sz, _vp]),
+    "clipmi_taskres_train_workspace_bytes": (_sz, [_i, _i, _i]),
+    "clipmi_taskres_train_step": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _vp, _i, _i64, _f, _f, _f, _i, C.c_double,
+                                       C.c_double, C.c_double, _vp, _vp, _sz, _vp]),
+    "clipmi_taskres_fit": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _f, _vp, _i, _i64, _f, _f, _f, _i,
+                                C.c_double, C.c_double, C.c_double, _vp, _vp, _sz, _vp]),
     "clipmi_order_stats_workspace_bytes": (_sz, [_i, _i]),
     "clipmi_order_stats": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
     "clipmi_group_gap_accumulate": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _vp]),

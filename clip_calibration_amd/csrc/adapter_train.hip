@@ -20,6 +20,7 @@
 #include <cmath>
 
 #include "common.h"
+#include "train_rules.h"   // SgdArgs, sgd_element, mean_loss_256
 
 namespace clipmi {
 namespace {
@@ -27,11 +28,6 @@ namespace {
 constexpr int ROWS_THREADS = 1024;            // 16 waves per sample: the 2 C dots over E are the long pole
 constexpr int ROWS_WAVES = ROWS_THREADS / 64;
 constexpr size_t ROWS_LDS_MAX = 64 * 1024;    // what a launch gets without raising the kernel's dynamic LDS attribute
-
-struct SgdArgs {
-  float momentum, one_minus_dampening, weight_decay;
-  int nesterov, first_step;   // first_step: the momentum buffers are initialised from this step's gradient (torch's buf is None)
-};
 
 // workspace of one batch of `rows`: h [rows, H] | da [rows, E] | dh [rows, H] | z [rows, C] | loss [rows], fp32
 struct Workspace {
@@ -196,19 +192,6 @@ __global__ __launch_bounds__(ROWS_THREADS) void adapter_rows_kernel(const float*
   for (int k = t; k < H; k += ROWS_THREADS) out_dh[k] = sh[k] > 0.f ? sdh[k] : 0.f;
 }
 
-// torch.optim.SGD's rule on one element (torch rounds the products of add(other, alpha) before it adds)
-__device__ __forceinline__ void sgd_element(float* __restrict__ w, float* __restrict__ buf, int64_t idx, float grad, float lr, const SgdArgs& a) {
-#pragma clang fp contract(off)
-  const float v = w[idx];
-  if (a.weight_decay != 0.f) grad = grad + a.weight_decay * v;
-  if (a.momentum != 0.f) {
-    const float b = a.first_step ? grad : a.momentum * buf[idx] + a.one_minus_dampening * grad;
-    buf[idx] = b;
-    grad = a.nesterov ? grad + a.momentum * b : b;
-  }
-  w[idx] = v - lr * grad;
-}
-
 // Elements [0, E H) are W2 [E, H], elements [E H, 2 E H) are W1 [H, E].  The weights a step's rows kernel read are final before this launch
 // starts, and this launch is final before the next step's rows kernel starts: the stream orders them.
 __global__ __launch_bounds__(256) void adapter_update_kernel(const float* __restrict__ feats, int64_t ld, const int32_t* __restrict__ order, int first,
@@ -234,17 +217,7 @@ __global__ __launch_bounds__(256) void adapter_update_kernel(const float* __rest
     sgd_element(w1, m1, j, g, *lr, a);
   }
   if (blockIdx.x != 0 || !loss_out) return;   // the same for every thread of the workgroup
-  __shared__ double sl[256];
-  const int t = threadIdx.x;
-  double l = 0.0;
-  for (int b = t; b < rows; b += 256) l += (double)ws.loss[b];
-  sl[t] = l;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if (t < w) sl[t] += sl[t + w];
-    __syncthreads();
-  }
-  if (t == 0) *loss_out = (float)(sl[0] / (double)rows);
+  mean_loss_256(ws.loss, rows, loss_out);
 }
 
 struct Problem {

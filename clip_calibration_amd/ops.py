@@ -677,6 +677,103 @@ def adapter_fit(features: torch.Tensor, labels: torch.Tensor, text: torch.Tensor
     return losses
 
 
+# ---- TaskRes training (taskres.py:96-210) --------------------------------------------------------------------------
+_OPTIMISERS = {"sgd": _lib.OPTIM_SGD, "adam": _lib.OPTIM_ADAM}
+
+
+def _taskres_problem(features, labels, base, residuals, state1, state2, optimizer: str, momentum: float, who: str):
+    """The tensors of one TaskRes training call, checked: raw features fp32 [N, E] (contiguous rows, row stride kept), labels int64 [N],
+    base text features fp32 [C, E], and the residuals and the optimiser's state fp32 [C, E], contiguous, updated where they lie.
+    Returns (features, labels, base, optimiser code, state1 pointer, state2 pointer)."""
+    if optimizer not in _OPTIMISERS:
+        raise ValueError(f"{who}: optimizer {optimizer!r} must be 'adam' or 'sgd'")
+    if (isinstance(features, torch.Tensor) and features.dim() == 2 and features.shape[0] > 0 and features.stride(1) == 1
+            and features.stride(0) >= features.shape[1]):
+        _dev(features[:1], "features", (torch.float32,))     # read in place with its row stride: the device and dtype checks only
+    else:
+        features = _dev(features, "features", (torch.float32,))
+    labels = _dev(labels, "labels", (torch.int64,))
+    base = _dev(base, "base_text_features", (torch.float32,))
+    if features.dim() != 2 or features.shape[0] < 1 or labels.shape != (features.shape[0],):
+        raise ValueError(f"{who}: features {tuple(features.shape)} must be [N >= 1, E] with one label per row, got labels {tuple(labels.shape)}")
+    E = features.shape[1]
+    if base.dim() != 2 or base.shape[1] != E or base.shape[0] < 2:
+        raise ValueError(f"{who}: base text features {tuple(base.shape)} must be [C >= 2, E = {E}]")
+    used = [(residuals, "residuals")]
+    if optimizer == "adam":
+        used += [(state1, "state1"), (state2, "state2")]
+    elif momentum != 0.0:
+        used += [(state1, "state1")]
+    for t, name in used:
+        _dev(t, name, (torch.float32,))
+        _in_place(t, torch.float32, f"{who}: {name} is updated in place: a contiguous fp32 tensor on the GPU")
+        if t.shape != base.shape:
+            raise ValueError(f"{who}: {name} {tuple(t.shape)} must have the base text features' shape {tuple(base.shape)}")
+    p1 = used[1][0].data_ptr() if len(used) > 1 else None
+    p2 = used[2][0].data_ptr() if len(used) > 2 else None
+    return features, labels, base, _OPTIMISERS[optimizer], p1, p2
+
+
+def _taskres_workspace(rows: int, E: int, Cn: int, device) -> torch.Tensor:
+    return torch.empty(lib.clipmi_taskres_train_workspace_bytes(rows, E, Cn), dtype=torch.uint8, device=device)
+
+
+def taskres_train_step(features: torch.Tensor, labels: torch.Tensor, base: torch.Tensor, residuals: torch.Tensor,
+                       state1: Optional[torch.Tensor], state2: Optional[torch.Tensor], lr: torch.Tensor, alpha: float, scale: float,
+                       steps_done: int, optimizer: str = "adam", weight_decay: float = 0.0, momentum: float = 0.0, dampening: float = 0.0,
+                       nesterov: bool = False, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
+                       want_loss: bool = False) -> Optional[torch.Tensor]:
+    """One optimiser step of TaskRes' residuals on the batch ``features`` fp32 [B, E] (raw image features), enqueued without a host
+    synchronisation (include/clipmi.h, clipmi_taskres_train_step).  ``residuals`` [C, E] and the state are updated in place: ``state1``
+    is SGD's momentum buffer or Adam's first moment, ``state2`` Adam's second moment; ``lr`` fp32 [1] on the device; ``scale`` =
+    exp(logit_scale); ``steps_done`` counts the steps taken before this one.  Returns the batch loss fp32 [1] on the device when
+    ``want_loss``."""
+    features, labels, base, kind, p1, p2 = _taskres_problem(features, labels, base, residuals, state1, state2, optimizer, momentum,
+                                                            "taskres_train_step")
+    lr = _dev(lr, "lr", (torch.float32,))
+    if lr.numel() != 1:
+        raise ValueError(f"taskres_train_step: lr {tuple(lr.shape)} must hold one rate")
+    (B, E), Cn = features.shape, base.shape[0]
+    loss = torch.empty(1, dtype=torch.float32, device=features.device) if want_loss else None
+    ws = _taskres_workspace(B, E, Cn, features.device)
+    check(lib.clipmi_taskres_train_step(features.data_ptr(), features.stride(0), labels.data_ptr(), base.data_ptr(), residuals.data_ptr(), p1, p2,
+                                        B, E, Cn, float(alpha), float(scale), lr.data_ptr(), kind, int(steps_done), float(weight_decay),
+                                        float(momentum), float(dampening), int(bool(nesterov)), float(betas[0]), float(betas[1]), float(eps),
+                                        None if loss is None else loss.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+          "clipmi_taskres_train_step")
+    return loss
+
+
+def taskres_fit(features: torch.Tensor, labels: torch.Tensor, base: torch.Tensor, residuals: torch.Tensor, state1: Optional[torch.Tensor],
+                state2: Optional[torch.Tensor], lr: torch.Tensor, alpha: float, scale: float, batch_size: int, epochs: int,
+                optimizer: str = "adam", weight_decay: float = 0.0, momentum: float = 0.0, dampening: float = 0.0, nesterov: bool = False,
+                betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8, order: Optional[torch.Tensor] = None, drop_last: bool = False,
+                steps_done: int = 0, want_losses: bool = False) -> Optional[torch.Tensor]:
+    """The whole training run of TaskRes' residuals from the cached ``features`` fp32 [N, E], enqueued without a host synchronisation
+    (include/clipmi.h, clipmi_taskres_fit).  ``residuals`` and the state are updated in place; ``lr`` fp32 [steps], one rate per step;
+    ``order`` int32 [epochs, N] or None (0 .. N-1 every epoch).  Returns the per-step batch losses fp32 [steps] when ``want_losses``."""
+    features, labels, base, kind, p1, p2 = _taskres_problem(features, labels, base, residuals, state1, state2, optimizer, momentum, "taskres_fit")
+    (N, E), Cn = features.shape, base.shape[0]
+    batch_size, epochs = int(batch_size), int(epochs)
+    if batch_size < 1 or epochs < 0:
+        raise ValueError(f"taskres_fit: batch_size={batch_size} (>= 1), epochs={epochs} (>= 0)")
+    steps = epochs * (N // batch_size if drop_last else -(-N // batch_size))
+    lr = _dev(lr, "lr", (torch.float32,))
+    if lr.shape != (steps,):
+        raise ValueError(f"taskres_fit: lr {tuple(lr.shape)} must hold one rate per step ({steps})")
+    order, po = _opt(order, "order", (torch.int32,))
+    if order is not None and order.shape != (epochs, N):
+        raise ValueError(f"taskres_fit: order {tuple(order.shape)} must be [epochs, N] = [{epochs}, {N}]")
+    losses = torch.empty(steps, dtype=torch.float32, device=features.device) if want_losses else None
+    ws = _taskres_workspace(min(batch_size, N), E, Cn, features.device)
+    check(lib.clipmi_taskres_fit(features.data_ptr(), features.stride(0), labels.data_ptr(), po, base.data_ptr(), residuals.data_ptr(), p1, p2,
+                                 N, E, Cn, batch_size, epochs, int(bool(drop_last)), float(alpha), float(scale), lr.data_ptr(), kind,
+                                 int(steps_done), float(weight_decay), float(momentum), float(dampening), int(bool(nesterov)), float(betas[0]),
+                                 float(betas[1]), float(eps), None if losses is None else losses.data_ptr(), ws.data_ptr(), ws.numel(),
+                                 _stream()), "clipmi_taskres_fit")
+    return losses
+
+
 # ---- CoCoOp glue (cocoop.py:154-199) -------------------------------------------------------------------------------
 def cocoop_ctx(img_n: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor,
                ctx: torch.Tensor) -> torch.Tensor:

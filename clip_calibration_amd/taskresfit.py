@@ -1,0 +1,193 @@
+"""TaskRes' text residuals trained on the GPU (reference trainers/classification/taskres.py:96-210).
+
+The reference trains one tensor, the residual matrix ``text_feature_residuals`` [C, E] of the classifier ``base_text_features + alpha *
+residuals``, with Dassl's epoch loop: every step runs the frozen image tower, normalises both sides, takes ``F.cross_entropy`` of
+``exp(logit_scale)`` times the cosine and one optimiser step on the residuals.  Both towers and ``logit_scale`` are frozen and the base
+text features are computed once: a step is a function of the image features, the labels, the base text features, ``alpha`` and the
+optimiser state.  csrc/taskres_train.hip computes forward, backward and the optimiser's step (``torch.optim.Adam``'s rule, or
+``torch.optim.SGD``'s) in three launches per step, all in fp32 as the reference's ``model.float()`` has it, with no autograd graph.
+
+Two ways in.  ``fit_residuals`` trains from a cached [N, E] feature matrix and enqueues every step of every epoch on the current stream
+with no synchronisation between the steps and one at the end (labels that arrive on the GPU are copied to the host once, before the first
+launch, for their range check): that equals the reference's loop only when the train transform is deterministic, since the reference's
+``random_resized_crop`` + ``random_flip`` change the features every epoch.  ``TaskResFitState.step`` takes one batch of features at a
+time, for callers that run the image tower on every step.
+
+Dassl is not part of this repository's environment.  The defaults below -- Adam at 2e-4 with betas (0.9, 0.999), eps 1e-8 and weight
+decay 5e-4 (for SGD: momentum 0.9, no dampening, no Nesterov); 200 epochs in batches of 256, the last short batch dropped; a constant
+warm-up epoch at 1e-5 that hands over to a cosine schedule -- restate configs/trainers/TaskRes/vit_b16_c16_ep200_batch256.yaml and
+Dassl's public defaults and are UNVERIFIED here; that is why each of them is an argument.  ``alpha`` defaults to the mirror trainer's
+0.5 (the reference's train.py sets RESIDUAL_SCALE 1.0; ``CustomCLIP.fit_residuals`` passes the model's own).  Dassl's random sampler is
+the caller's ``order``.
+"""
+from __future__ import annotations
+
+import math
+from typing import Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import ops
+from .tempfit import cosine_warmup_schedule, steps_per_epoch
+
+
+def _host_int_array(x, name: str) -> np.ndarray:
+    a = x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+    if a.dtype.kind not in "iu":
+        raise TypeError(f"fit_residuals: {name} must be integers, got {a.dtype}")
+    return a
+
+
+def _check_optimiser(who: str, optimizer: str, betas, eps: float, weight_decay: float, momentum: float, dampening: float, nesterov: bool) -> None:
+    if optimizer not in ("adam", "sgd"):
+        raise ValueError(f"{who}: optimizer {optimizer!r} must be 'adam' or 'sgd'")
+    if not weight_decay >= 0.0 or not math.isfinite(weight_decay):
+        raise ValueError(f"{who}: weight_decay={weight_decay} (finite, >= 0)")
+    if optimizer == "adam":
+        if len(betas) != 2 or not all(0.0 <= float(b) < 1.0 for b in betas):
+            raise ValueError(f"{who}: betas={tuple(betas)} (two values in [0, 1))")
+        if not eps >= 0.0 or not math.isfinite(eps):
+            raise ValueError(f"{who}: eps={eps} (finite, >= 0)")
+        return
+    if not (0.0 <= momentum < 1.0 and 0.0 <= dampening < 1.0):
+        raise ValueError(f"{who}: momentum={momentum}, dampening={dampening} (both in [0, 1))")
+    if nesterov and (momentum <= 0.0 or dampening != 0.0):
+        raise ValueError(f"{who}: Nesterov momentum requires a momentum and zero dampening")
+
+
+def _check_shapes(who: str, features, base, residuals) -> Tuple[int, int, int]:
+    if not isinstance(features, torch.Tensor) or features.dim() != 2 or features.shape[0] < 1:
+        raise ValueError(f"{who}: features must be a [N >= 1, E] tensor")
+    N, E = features.shape
+    if not isinstance(base, torch.Tensor) or base.dim() != 2 or base.shape[1] != E or base.shape[0] < 2:
+        raise ValueError(f"{who}: base text features {tuple(getattr(base, 'shape', ()))} must be [C >= 2, E = {E}]")
+    if residuals is not None and (not isinstance(residuals, torch.Tensor) or residuals.shape != base.shape):
+        raise ValueError(f"{who}: residuals {tuple(getattr(residuals, 'shape', ()))} must have the base text features' shape {tuple(base.shape)}")
+    return N, E, base.shape[0]
+
+
+def _labels(who: str, labels, N: int, C: int) -> np.ndarray:
+    lab = _host_int_array(labels, "labels")
+    if lab.shape != (N,):
+        raise ValueError(f"{who}: {N} rows need {N} labels, got {lab.shape}")
+    if lab.min() < 0 or lab.max() >= C:
+        raise ValueError(f"{who}: labels span [{int(lab.min())}, {int(lab.max())}], outside the {C} classes [0, {C})")
+    return lab
+
+
+def _need_gpu(t: torch.Tensor, name: str) -> None:
+    if not t.is_cuda:
+        raise RuntimeError(f"clipmi: `{name}` must be a tensor on the GPU (got {t.device}); the HIP path has no CPU fallback")
+
+
+def _master(base: torch.Tensor, residuals: Optional[torch.Tensor], dev) -> torch.Tensor:
+    """A fresh contiguous fp32 copy on the device (zeros without ``residuals``): the master values the kernels update in place."""
+    if residuals is None:
+        return torch.zeros(tuple(base.shape), dtype=torch.float32, device=dev)
+    return residuals.detach().to(device=dev, dtype=torch.float32, copy=True).contiguous()
+
+
+def _state(r: torch.Tensor, optimizer: str, momentum: float):
+    if optimizer == "adam":
+        return torch.zeros_like(r), torch.zeros_like(r)
+    return (torch.zeros_like(r) if momentum != 0.0 else None), None
+
+
+def fit_residuals(features: torch.Tensor, labels, base_text_features: torch.Tensor, residuals: Optional[torch.Tensor] = None, alpha: float = 0.5,
+                  logit_scale: float = 4.6052, optimizer: str = "adam", lr: float = 2e-4, epochs: int = 200, batch_size: int = 256,
+                  betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8, weight_decay: float = 5e-4, momentum: float = 0.9,
+                  dampening: float = 0.0, nesterov: bool = False, lr_per_epoch: Optional[Sequence[float]] = None, order=None,
+                  drop_last: bool = True, return_history: bool = False):
+    """Train TaskRes' residuals on cached ``features`` fp32 [N, E] (raw, un-normalised image features on the GPU; the rows may be a
+    column slice of a wider matrix), ``labels`` [N] and the frozen ``base_text_features`` fp32 [C, E] (not normalised), starting from
+    ``residuals`` [C, E] (not modified; None = zeros, the reference's initialisation): ``epochs`` passes of ``torch.optim.Adam(lr, betas,
+    eps, weight_decay)`` -- or, with ``optimizer="sgd"``, ``torch.optim.SGD(lr, momentum, dampening, weight_decay, nesterov)`` -- on
+    ``F.cross_entropy(exp(logit_scale) * normalise(f) @ normalise(base + alpha * residuals).T, labels)`` over batches of ``batch_size``,
+    all in fp32.
+
+    ``lr_per_epoch`` gives every epoch's rate; None takes ``cosine_warmup_schedule(lr, epochs)``.  ``order`` is an integer [epochs, N]
+    array of sample indices, batch k of epoch e being ``order[e, k * batch_size : (k + 1) * batch_size]``; None is 0 .. N-1 in every
+    epoch.  The last batch of an epoch is short unless ``drop_last`` drops it.
+
+    Labels (and ``order``) are checked against their ranges on the host before anything is launched -- a label tensor on the GPU is
+    copied to the host for that, which waits for whatever produced it; from the first launch on nothing synchronises until the one wait
+    at the end.  Returns the fitted fp32 residuals on the device, or ``(residuals, per-step batch losses as a float32 numpy array)`` with
+    ``return_history``.  The defaults are unverified restatements of the reference's config and Dassl's (module docstring)."""
+    N, E, C = _check_shapes("fit_residuals", features, base_text_features, residuals)
+    epochs, batch_size = int(epochs), int(batch_size)
+    if epochs < 0 or batch_size < 1:
+        raise ValueError(f"fit_residuals: epochs={epochs} (>= 0), batch_size={batch_size} (>= 1)")
+    _check_optimiser("fit_residuals", optimizer, betas, eps, weight_decay, momentum, dampening, nesterov)
+    if not (math.isfinite(alpha) and math.isfinite(logit_scale)):
+        raise ValueError(f"fit_residuals: alpha={alpha}, logit_scale={logit_scale} (both finite)")
+    lab = _labels("fit_residuals", labels, N, C)
+    if order is not None:
+        order = _host_int_array(order, "order")
+        if order.shape != (epochs, N):
+            raise ValueError(f"fit_residuals: order {order.shape} must be [epochs, N] = [{epochs}, {N}]")
+        if order.size and (order.min() < 0 or order.max() >= N):
+            raise ValueError(f"fit_residuals: order holds sample indices outside [0, {N})")
+    rates = cosine_warmup_schedule(lr, epochs) if lr_per_epoch is None else [float(r) for r in lr_per_epoch]
+    if len(rates) != epochs:
+        raise ValueError(f"fit_residuals: {len(rates)} learning rates for {epochs} epochs")
+    per_epoch = steps_per_epoch(N, batch_size, drop_last)
+    _need_gpu(features, "features")
+    dev = features.device
+    r = _master(base_text_features, residuals, dev)
+    if epochs * per_epoch == 0:
+        return (r, np.zeros(0, np.float32)) if return_history else r
+    s1, s2 = _state(r, optimizer, momentum)
+    lr_steps = torch.from_numpy(np.repeat(np.asarray(rates, np.float64), per_epoch).astype(np.float32)).to(dev)
+    order_d = None if order is None else torch.from_numpy(np.ascontiguousarray(order, dtype=np.int32)).to(dev)
+    labels_d = labels if isinstance(labels, torch.Tensor) and labels.is_cuda and labels.dtype == torch.int64 else torch.from_numpy(
+        lab.astype(np.int64)).to(dev)
+    losses = ops.taskres_fit(features, labels_d, base_text_features, r, s1, s2, lr_steps, alpha, float(np.float32(math.exp(logit_scale))),
+                             batch_size, epochs, optimizer, weight_decay, momentum, dampening, nesterov, betas, eps, order_d, drop_last,
+                             steps_done=0, want_losses=return_history)
+    torch.cuda.current_stream().synchronize()   # the run's one synchronisation
+    return (r, losses.cpu().numpy()) if return_history else r
+
+
+class TaskResFitState:
+    """The training state of TaskRes' residuals for callers that produce the image features step by step (a random train transform: the
+    image tower runs on every batch): the fp32 master ``residuals`` [C, E], the optimiser's state (``state1``: Adam's first moment or
+    SGD's momentum buffer, ``state2``: Adam's second moment) and the number of steps taken.  ``step`` enqueues one forward, backward and
+    optimiser update and does not synchronise."""
+
+    def __init__(self, base_text_features: torch.Tensor, residuals: Optional[torch.Tensor] = None, alpha: float = 0.5,
+                 logit_scale: float = 4.6052, optimizer: str = "adam", betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
+                 weight_decay: float = 5e-4, momentum: float = 0.9, dampening: float = 0.0, nesterov: bool = False):
+        _check_optimiser("TaskResFitState", optimizer, betas, eps, weight_decay, momentum, dampening, nesterov)
+        if not isinstance(base_text_features, torch.Tensor) or base_text_features.dim() != 2 or base_text_features.shape[0] < 2:
+            raise ValueError("TaskResFitState: base text features must be a [C >= 2, E] tensor")
+        _check_shapes("TaskResFitState", base_text_features[:1], base_text_features, residuals)
+        if not (math.isfinite(alpha) and math.isfinite(logit_scale)):
+            raise ValueError(f"TaskResFitState: alpha={alpha}, logit_scale={logit_scale} (both finite)")
+        _need_gpu(base_text_features, "base_text_features")
+        self.base_text_features = base_text_features
+        self.residuals = _master(base_text_features, residuals, base_text_features.device)
+        self.state1, self.state2 = _state(self.residuals, optimizer, momentum)
+        self.alpha, self.scale = float(alpha), float(np.float32(math.exp(logit_scale)))
+        self.optimizer, self.betas, self.eps, self.weight_decay = optimizer, (float(betas[0]), float(betas[1])), eps, weight_decay
+        self.momentum, self.dampening, self.nesterov = momentum, dampening, nesterov
+        self.steps = 0
+
+    def step(self, features: torch.Tensor, labels, lr, want_loss: bool = False) -> Optional[torch.Tensor]:
+        """One optimiser step on the batch ``features`` fp32 [B, E] (raw image features on the GPU) and ``labels`` [B] at the rate
+        ``lr``: an fp32 tensor of one element on the device is read where it lies (slice a per-step rate array filled once:
+        ``rates[k:k + 1]``); a Python number is uploaded on every call, a host-to-device copy the per-step path is better off without.
+        A label tensor on the GPU is taken as it is -- a label outside [0, C) then makes the residuals NaN, it is never used as an
+        address; host labels are range-checked.  Returns the batch loss, fp32 [1] on the device, when ``want_loss``."""
+        N, _, C = _check_shapes("TaskResFitState.step", features, self.base_text_features, None)
+        _need_gpu(features, "features")
+        if isinstance(labels, torch.Tensor) and labels.is_cuda and labels.dtype == torch.int64:
+            labels_d = labels
+        else:
+            labels_d = torch.from_numpy(_labels("TaskResFitState.step", labels, N, C).astype(np.int64)).to(features.device)
+        lr_d = lr if isinstance(lr, torch.Tensor) else torch.tensor([float(lr)], dtype=torch.float32).to(features.device)
+        loss = ops.taskres_train_step(features, labels_d, self.base_text_features, self.residuals, self.state1, self.state2, lr_d, self.alpha,
+                                      self.scale, self.steps, self.optimizer, self.weight_decay, self.momentum, self.dampening, self.nesterov,
+                                      self.betas, self.eps, want_loss=want_loss)
+        self.steps += 1
+        return loss

@@ -1,4 +1,5 @@
-"""TaskRes (reference trainers/classification/taskres.py:96-210) -- inference forward only.
+"""TaskRes (reference trainers/classification/taskres.py:96-210): the inference forward, and the training of the residuals on the GPU
+from cached image features (``CustomCLIP.fit_residuals``; clip_calibration_amd/taskresfit.py, csrc/taskres_train.hip).
 
 The classifier is ``base_text_features + alpha * text_feature_residuals`` (taskres.py:105-106), where the base features are
 the text-encoder outputs of the hand-written templates averaged per class (taskres.py:109-135, NOT normalised before the
@@ -6,6 +7,7 @@ mean) and the residual is the only learned tensor.  ``forward`` normalises both 
 the reference returns the logits alone, the mirror the trainer-level 3-tuple)."""
 from __future__ import annotations
 
+import math
 from typing import Optional
 
 import torch
@@ -55,3 +57,31 @@ class CustomCLIP(nn.Module):
         if want_conf_pred:
             return logits, image_features, text_features, conf, pred
         return logits, image_features, text_features
+
+    def fit_residuals(self, loader, **fit_args):
+        """Train the residuals on the GPU: one pass of ``loader`` (an iterable of (image, label) batches) through the frozen image tower
+        (``image_features_f32``), the raw features and the labels kept on the device, then ``taskresfit.fit_residuals(features, labels,
+        base_text_features, residuals, **fit_args)`` starting from the module's residuals, with ``alpha`` and ``logit_scale`` taken from
+        this model unless ``fit_args`` say otherwise.  The fitted matrix is copied into ``prompt_learner.text_feature_residuals`` in the
+        parameter's dtype (the fit itself keeps fp32 master values) and returned as ``fit_residuals`` returns it.
+
+        Caching the features equals the reference's loop only for a DETERMINISTIC train transform: the reference's config trains with
+        ``random_resized_crop`` + ``random_flip``, which give every epoch other features.  For such a transform run the tower on every
+        batch and hand its features to ``taskresfit.TaskResFitState.step``."""
+        from ..taskresfit import fit_residuals
+        feats, labels = [], []
+        with torch.no_grad():
+            for image, label in loader:
+                f = self.clip_model.image_features_f32(image)
+                feats.append(f)
+                labels.append(torch.as_tensor(label).to(device=f.device, dtype=torch.int64))
+        if not feats:
+            raise ValueError("fit_residuals: the loader gave no batch")
+        fit_args.setdefault("alpha", self.prompt_learner.alpha)
+        fit_args.setdefault("logit_scale", math.log(self.scale))
+        res = self.prompt_learner.text_feature_residuals
+        fitted = fit_residuals(torch.cat(feats), torch.cat(labels), self.prompt_learner.base_text_features.float(), res.detach().float(),
+                               **fit_args)
+        with torch.no_grad():
+            res.copy_(fitted[0] if isinstance(fitted, tuple) else fitted)
+        return fitted

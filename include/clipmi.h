@@ -459,6 +459,48 @@ int clipmi_adapter_fit(const float* feats, int64_t ld, const int64_t* labels, co
                        const float* lr, int first_step, float momentum, float dampening, float weight_decay, int nesterov, float* losses,
                        void* workspace, size_t workspace_bytes, clipmi_stream_t stream);
 
+/* TaskRes' text residuals trained on the device (trainers/classification/taskres.py:96-210: both towers and logit_scale frozen, the
+ * base text features computed once): forward, backward and the optimiser's step on the residual matrix, all fp32 with fp32 master
+ * values.  feats fp32 [n, E] raw (un-normalised) image features with row stride ld >= E (elements), labels int64 [n], base fp32
+ * [C, E] the base text features (not normalised), residuals fp32 [C, E] updated in place, scale = exp(logit_scale).  Per batch of B:
+ *   x_b = f_b / |f_b|;  t_c = base_c + alpha r_c;  n_c = |t_c|;  u_c = t_c / n_c;  z = scale X U^T;  loss = mean CE(z, y)
+ *   dz = (softmax(z) - onehot(y)) / B;  du_c = scale sum_b dz[b, c] x_b;  dr_c = alpha (du_c - u_c (u_c . du_c)) / n_c
+ * then on every element of r, with the step's rate *lr (device), the rule `optimizer` selects:
+ *   optimizer == 0    torch.optim.SGD: the rule of clipmi_adapter_train_step; state1 is the momentum buffer (may be NULL when
+ *                      momentum == 0), state2 is not used; a step with steps_done == 0 initialises the buffer from its gradient.
+ *   optimizer == 1    torch.optim.Adam without amsgrad, step number t = steps_done + 1: g += weight_decay * r;
+ *                      m += (g - m) (1 - beta1);  v = beta2 v + ((1 - beta2) g) g;
+ *                      r -= (lr / (1 - beta1^t)) m / (sqrt(v) / sqrt(1 - beta2^t) + eps);  state1 = m, state2 = v, both [C, E] and zero
+ *                      before the first step; the two bias corrections are formed in double on the host.  momentum, dampening and
+ *                      nesterov are not looked at.
+ * Three launches per step: z in 64 x 64 tiles (the tiles sum the squares of the rows they stream and divide the raw dot by both
+ * norms), one workgroup per sample (row loss, dz), dU in 64 x 64 tiles with the projection and the optimiser's rule in the epilogue
+ * (u_c . du_c is taken as sum_b dz[b, c] z[b, c]; the row losses averaged in float64).  Every product is one fmaf chain in depth
+ * order, no atomics: the same inputs give the same bits.  A label outside [0, C) or a sample index outside [0, n) is never
+ * dereferenced; it makes the step's loss and the residuals NaN.  workspace (device, 8-byte aligned) of
+ * clipmi_taskres_train_workspace_bytes(rows of the widest batch, E, C) bytes (0 for shapes the calls refuse outright).  These
+ * exports are additive: the ABI version does not change with them.
+ *
+ * clipmi_taskres_train_step: one step on the batch feats[0 .. rows) -- for callers that run the image tower on every step; loss fp32
+ * [1] (device) or NULL.
+ *
+ * clipmi_taskres_fit: the whole run from a cached feature matrix, epochs * ceil(n / batch) steps (floor with drop_last), enqueued on
+ * `stream` without a host synchronisation; batches, order, lr and losses as clipmi_adapter_fit takes them; steps_done counts the steps
+ * taken before the run's first.  epochs == 0: CLIPMI_OK, nothing is launched.
+ * CLIPMI_ERR_ARG: a null or misaligned pointer, an unknown optimizer, steps_done < 0, epochs < 0, a negative or non-finite weight decay
+ * or eps, momentum, dampening or a beta outside [0, 1), nesterov with zero momentum or non-zero dampening, a non-finite alpha or scale.
+ * CLIPMI_ERR_SHAPE: n or rows < 1, C < 2, E < 1, batch < 1, ld < E, or C or the rows of a batch above 4 194 240 (65 535 tiles of 64).
+ * CLIPMI_ERR_WORKSPACE: a workspace that is too small. */
+size_t clipmi_taskres_train_workspace_bytes(int rows, int E, int C);
+int clipmi_taskres_train_step(const float* feats, int64_t ld, const int64_t* labels, const float* base, float* residuals, float* state1,
+                              float* state2, int rows, int E, int C, float alpha, float scale, const float* lr, int optimizer,
+                              int64_t steps_done, float weight_decay, float momentum, float dampening, int nesterov, double beta1, double beta2,
+                              double eps, float* loss, void* workspace, size_t workspace_bytes, clipmi_stream_t stream);
+int clipmi_taskres_fit(const float* feats, int64_t ld, const int64_t* labels, const int32_t* order, const float* base, float* residuals,
+                       float* state1, float* state2, int n, int E, int C, int batch, int epochs, int drop_last, float alpha, float scale,
+                       const float* lr, int optimizer, int64_t steps_done, float weight_decay, float momentum, float dampening, int nesterov,
+                       double beta1, double beta2, double eps, float* losses, void* workspace, size_t workspace_bytes, clipmi_stream_t stream);
+
 /* The sample-level metrics of the evaluator on the device (vl_evaluator.py:77-82 macro-F1; tools/metrics.py:132-178 PIECE, :212-236
  * AdaptiveECE) -- SURVEY f-1.  Three small kernels; the host turns their outputs into the scalars (clip_calibration_amd.metrics:
  * quantile_edges_from_order_stats, gap_from_groups, macro_f1_from_counts).  These exports are additive: the ABI version does not
