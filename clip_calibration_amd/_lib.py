@@ -61,6 +61,11 @@ class ImageDesc(C.Structure):
                 ("stride_y", C.c_int64), ("stride_x", C.c_int64), ("stride_c", C.c_int64)]
 
 
+class ViewDesc(C.Structure):
+    """clipmi_view_desc: the box (top, left, height, width) of image ``image``, stretched to one output image; ``flip`` mirrors it."""
+    _fields_ = [(n, C.c_int32) for n in ("image", "top", "left", "height", "width", "flip")]
+
+
 class ProcalModel(C.Structure):
     """clipmi_procal_model: the fitted ProCal point sets as the kernels take them (include/clipmi.h)."""
     _fields_ = [("points_true", C.c_void_p), ("points_false", C.c_void_p), ("n_true", C.c_int32), ("n_false", C.c_int32),
@@ -172,6 +177,8 @@ _SIGNATURES = {
     "clipmi_encode_image_timed": (_i, [_vp, _vp, _i, _i, _vp, _vp, _sz, _u, C.POINTER(_f), _i, C.POINTER(_i), _vp]),
     "clipmi_preprocess_workspace_bytes": (_sz, [_vp, _i, _i, _i]),
     "clipmi_preprocess": (_i, [_vp, _i64, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _sz, _vp]),
+    "clipmi_augment_workspace_bytes": (_sz, [_vp, _i, _vp, _i, _i, _i]),
+    "clipmi_augment": (_i, [_vp, _i64, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _sz, _vp]),
     "clipmi_probe_mfma_f16": (_i, [_vp, _vp, _vp, _i, _i, C.POINTER(_i), _vp]),
 }
 

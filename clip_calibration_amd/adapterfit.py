@@ -10,7 +10,8 @@ Two ways in.  ``fit_adapter`` trains from a cached [N, E] feature matrix and enq
 no synchronisation between the steps and one at the end (labels that arrive on the GPU are copied to the host once, before the first
 launch, for their range check): that equals the reference's loop only when the train transform is deterministic, since the reference's
 ``random_resized_crop`` + ``random_flip`` change the features every epoch.  ``AdapterFitState.step`` takes one batch of features at a time,
-for callers that run the image tower on every step.
+for callers that run the image tower on every step: ``CLIPAdapterCLIP.fit_adapter(loader, transform=TrainPreprocess(...))`` is that
+caller, with the reference's train transform computed on the device (clip_calibration_amd/augment.py).
 
 Dassl is not part of this repository's environment.  The defaults below -- SGD at 0.002 with momentum 0.9 and weight decay 5e-4, no
 dampening, no Nesterov; 200 epochs in batches of 32, the last short batch dropped; a constant warm-up epoch that hands over to a cosine

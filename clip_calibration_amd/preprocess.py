@@ -158,10 +158,14 @@ class Preprocess:
 
     def __call__(self, images) -> torch.Tensor:
         dev = torch.device("cuda", torch.cuda.current_device())
+        return self._run(*self._gather(images, dev), dev)
+
+    def _gather(self, images, dev: torch.device):
+        """Any input form -> (device uint8 buffer, host descriptors int64 [B, 5] laid out as clipmi_image_desc, B)."""
         if isinstance(images, PackedImages):
             if not images.is_cuda:
                 images = images.to(dev, non_blocking=images.is_pinned())
-            return self._run(images.data, self._packed_descs(images), len(images), dev)
+            return images.data, self._packed_descs(images), len(images)
         if isinstance(images, torch.Tensor):
             return self._dense(images, dev)
         if isinstance(images, (list, tuple)):
@@ -177,7 +181,7 @@ class Preprocess:
                 raise TypeError("Preprocess: a list mixes host and device images")
             else:
                 packed = _pack_host(imgs, pin=True).to(dev, non_blocking=True)   # one pinned buffer, one copy
-            return self._run(packed.data, self._packed_descs(packed), len(packed), dev)
+            return packed.data, self._packed_descs(packed), len(packed)
         raise TypeError(f"Preprocess: unsupported input {type(images)}")
 
     @staticmethod
@@ -190,7 +194,7 @@ class Preprocess:
         d[:, 2], d[:, 3], d[:, 4] = 3 * s[:, 2], 3, 1
         return d
 
-    def _dense(self, t: torch.Tensor, dev: torch.device) -> torch.Tensor:
+    def _dense(self, t: torch.Tensor, dev: torch.device):
         if t.dtype != torch.uint8 or t.dim() != 4 or not (t.shape[3] == 3 or t.shape[1] == 3):
             raise TypeError(f"Preprocess: expected a uint8 [B,H,W,3] or [B,3,H,W] tensor, got {t.dtype} {tuple(t.shape)}")
         if not t.is_cuda:
@@ -209,7 +213,7 @@ class Preprocess:
         d32 = d.view(np.int32)
         d32[:, 2], d32[:, 3] = H, W
         d[:, 2], d[:, 3], d[:, 4] = sy, sx, sc
-        return self._run(t, d, B, dev)
+        return t, d, B
 
     def _run(self, buf: torch.Tensor, descs: np.ndarray, B: int, dev: torch.device) -> torch.Tensor:
         if buf.device != dev:

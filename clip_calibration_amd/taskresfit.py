@@ -11,7 +11,8 @@ Two ways in.  ``fit_residuals`` trains from a cached [N, E] feature matrix and e
 with no synchronisation between the steps and one at the end (labels that arrive on the GPU are copied to the host once, before the first
 launch, for their range check): that equals the reference's loop only when the train transform is deterministic, since the reference's
 ``random_resized_crop`` + ``random_flip`` change the features every epoch.  ``TaskResFitState.step`` takes one batch of features at a
-time, for callers that run the image tower on every step.
+time, for callers that run the image tower on every step: ``TaskResCLIP.fit_residuals(loader, transform=TrainPreprocess(...))`` is that
+caller, with the reference's train transform computed on the device (clip_calibration_amd/augment.py).
 
 Dassl is not part of this repository's environment.  The defaults below -- Adam at 2e-4 with betas (0.9, 0.999), eps 1e-8 and weight
 decay 5e-4 (for SGD: momentum 0.9, no dampening, no Nesterov); 200 epochs in batches of 256, the last short batch dropped; a constant

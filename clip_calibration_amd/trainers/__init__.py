@@ -4,7 +4,8 @@ Same class names, constructor roles, ``forward`` / ``model_inference`` return co
 ``trainers/classification/{zsclip,coop,cocoop,kgcoop,maple,proda,prograd,promptsrc,vpt,clip_adapter,taskres}.py`` and ``trainers/calibration/{tempscaling,
 distanse_aware_calibration,vl_calibrator}.py``; the Dassl engine, datasets and the training loops around them are
 out of scope, with two exceptions that run on the GPU from cached tower outputs: ``CustomCLIPCalibration.fit_scale``
-(TempScaling's scalar) and ``CLIPAdapterCLIP.fit_adapter`` (CLIP-Adapter's bottleneck); every other class is an inference mirror.  Class names are tokenised upstream (tokenizer = SURVEY f-3), so constructors take token
+(TempScaling's scalar) and ``CLIPAdapterCLIP.fit_adapter`` (CLIP-Adapter's bottleneck; with ``transform=`` under the reference's random train transform instead, as
+``TaskResCLIP.fit_residuals``); every other class is an inference mirror.  Class names are tokenised upstream (tokenizer = SURVEY f-3), so constructors take token
 ids where the reference takes class-name strings.
 """
 from .zsclip import ZeroshotCLIP  # noqa: F401

@@ -1,5 +1,6 @@
 """CLIP-Adapter (reference trainers/classification/clip_adapter.py:138-187): the inference forward, and the training of the bottleneck
-on the GPU from cached image features (``CustomCLIP.fit_adapter``; clip_calibration_amd/adapterfit.py, csrc/adapter_train.hip).
+on the GPU (``CustomCLIP.fit_adapter``; clip_calibration_amd/adapterfit.py, csrc/adapter_train.hip) from cached image features or, with a
+``TrainPreprocess``, under the reference's random train transform (clip_calibration_amd/augment.py, csrc/augment.hip).
 
 A two-layer bias-free bottleneck (E -> E/4 -> E, ReLU after each) on the un-normalised image features, blended with them
 by ``ratio`` (clip_adapter.py:170-172); the text side is CoOp's prompt splice through the text tower (clip_adapter.py:174-176;
@@ -33,30 +34,46 @@ class CustomCLIP(_CoOpCLIP):
         f = self.clip_model.image_features_f32(image)
         return ops.adapter_blend(f, self.adapter.fc[0].weight.float(), self.adapter.fc[2].weight.float(), self.ratio)
 
-    def fit_adapter(self, loader, **fit_args):
-        """Train the bottleneck on the GPU: one pass of ``loader`` (an iterable of (image, label) batches) through the frozen image tower
-        (``image_features_f32``), the raw features and the labels kept on the device, then ``adapterfit.fit_adapter(features, labels,
-        self.text_features(), w1, w2, **fit_args)`` starting from the module's weights, with ``ratio`` and ``logit_scale`` taken from this
-        model unless ``fit_args`` say otherwise.  The fitted matrices are copied into ``adapter.fc[0].weight`` and ``adapter.fc[2].weight``
-        in the module's dtype (the fit itself keeps fp32 master weights) and returned as ``fit_adapter`` returns them.
+    def fit_adapter(self, loader, transform=None, **fit_args):
+        """Train the bottleneck on the GPU, starting from the module's weights, with ``ratio`` and ``logit_scale`` taken from this model
+        unless ``fit_args`` say otherwise.  The fitted matrices are copied into ``adapter.fc[0].weight`` and ``adapter.fc[2].weight`` in
+        the module's dtype (the fit itself keeps fp32 master weights) and returned as ``adapterfit.fit_adapter`` returns them.
 
-        Caching the features equals the reference's loop only for a DETERMINISTIC train transform: the reference's config trains with
-        ``random_resized_crop`` + ``random_flip``, which give every epoch other features.  For such a transform run the tower on every
-        batch and hand its features to ``adapterfit.AdapterFitState.step``."""
-        from ..adapterfit import fit_adapter
-        feats, labels = [], []
-        with torch.no_grad():
-            for image, label in loader:
-                f = self.clip_model.image_features_f32(image)
-                feats.append(f)
-                labels.append(torch.as_tensor(label).to(device=f.device, dtype=torch.int64))
-            text = self.text_features()
-        if not feats:
-            raise ValueError("fit_adapter: the loader gave no batch")
+        ``transform=None``: one pass of ``loader`` (an iterable of (image, label) batches of preprocessed images) through the frozen
+        image tower (``image_features_f32``), the raw features and the labels kept on the device, then ``adapterfit.fit_adapter(features,
+        labels, self.text_features(), w1, w2, **fit_args)``.  Caching the features equals the reference's loop only for a DETERMINISTIC
+        train transform; the reference's config trains with ``random_resized_crop`` + ``random_flip``, which give every epoch other
+        features.
+
+        ``transform=TrainPreprocess(...)`` is that regime: ``loader`` yields (decoded uint8 images, labels) and is iterated once per
+        epoch, every batch going transform -> image tower -> ``AdapterFitState.step`` with nothing synchronising until the end
+        (``augment.fit_with_transform``).  ``fit_args``: ``epochs`` (200), ``lr`` (0.002), ``lr_per_epoch``, the optimiser's ``momentum``,
+        ``dampening``, ``weight_decay``, ``nesterov``, ``views`` (explicit boxes and flips per batch) and ``return_history``; the batch size
+        and the order are the loader's."""
         fit_args.setdefault("ratio", self.ratio)
         fit_args.setdefault("logit_scale", math.log(self.scale))
         fc1, fc2 = self.adapter.fc[0].weight, self.adapter.fc[2].weight
-        fitted = fit_adapter(torch.cat(feats), torch.cat(labels), text, fc1.detach().float(), fc2.detach().float(), **fit_args)
+        with torch.no_grad():
+            text = self.text_features()
+        if transform is not None:
+            from ..adapterfit import AdapterFitState
+            from ..augment import fit_with_transform
+            run = {k: fit_args.pop(k) for k in ("lr_per_epoch", "views", "return_history") if k in fit_args}
+            epochs, lr = fit_args.pop("epochs", 200), fit_args.pop("lr", 0.002)
+            state = AdapterFitState(text, fc1.detach().float(), fc2.detach().float(), **fit_args)
+            losses = fit_with_transform(state, self.clip_model.image_features_f32, text.shape[0], loader, transform, epochs, lr, **run)
+            fitted = (state.w1, state.w2) if losses is None else (state.w1, state.w2, losses)
+        else:
+            from ..adapterfit import fit_adapter
+            feats, labels = [], []
+            with torch.no_grad():
+                for image, label in loader:
+                    f = self.clip_model.image_features_f32(image)
+                    feats.append(f)
+                    labels.append(torch.as_tensor(label).to(device=f.device, dtype=torch.int64))
+            if not feats:
+                raise ValueError("fit_adapter: the loader gave no batch")
+            fitted = fit_adapter(torch.cat(feats), torch.cat(labels), text, fc1.detach().float(), fc2.detach().float(), **fit_args)
         with torch.no_grad():
             fc1.copy_(fitted[0])
             fc2.copy_(fitted[1])

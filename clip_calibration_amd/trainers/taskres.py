@@ -1,5 +1,6 @@
 """TaskRes (reference trainers/classification/taskres.py:96-210): the inference forward, and the training of the residuals on the GPU
-from cached image features (``CustomCLIP.fit_residuals``; clip_calibration_amd/taskresfit.py, csrc/taskres_train.hip).
+(``CustomCLIP.fit_residuals``; clip_calibration_amd/taskresfit.py, csrc/taskres_train.hip) from cached image features or, with a
+``TrainPreprocess``, under the reference's random train transform (clip_calibration_amd/augment.py, csrc/augment.hip).
 
 The classifier is ``base_text_features + alpha * text_feature_residuals`` (taskres.py:105-106), where the base features are
 the text-encoder outputs of the hand-written templates averaged per class (taskres.py:109-135, NOT normalised before the
@@ -58,30 +59,44 @@ class CustomCLIP(nn.Module):
             return logits, image_features, text_features, conf, pred
         return logits, image_features, text_features
 
-    def fit_residuals(self, loader, **fit_args):
-        """Train the residuals on the GPU: one pass of ``loader`` (an iterable of (image, label) batches) through the frozen image tower
-        (``image_features_f32``), the raw features and the labels kept on the device, then ``taskresfit.fit_residuals(features, labels,
-        base_text_features, residuals, **fit_args)`` starting from the module's residuals, with ``alpha`` and ``logit_scale`` taken from
-        this model unless ``fit_args`` say otherwise.  The fitted matrix is copied into ``prompt_learner.text_feature_residuals`` in the
-        parameter's dtype (the fit itself keeps fp32 master values) and returned as ``fit_residuals`` returns it.
+    def fit_residuals(self, loader, transform=None, **fit_args):
+        """Train the residuals on the GPU, starting from the module's residuals, with ``alpha`` and ``logit_scale`` taken from this model
+        unless ``fit_args`` say otherwise.  The fitted matrix is copied into ``prompt_learner.text_feature_residuals`` in the parameter's
+        dtype (the fit itself keeps fp32 master values) and returned as ``taskresfit.fit_residuals`` returns it.
 
-        Caching the features equals the reference's loop only for a DETERMINISTIC train transform: the reference's config trains with
-        ``random_resized_crop`` + ``random_flip``, which give every epoch other features.  For such a transform run the tower on every
-        batch and hand its features to ``taskresfit.TaskResFitState.step``."""
-        from ..taskresfit import fit_residuals
-        feats, labels = [], []
-        with torch.no_grad():
-            for image, label in loader:
-                f = self.clip_model.image_features_f32(image)
-                feats.append(f)
-                labels.append(torch.as_tensor(label).to(device=f.device, dtype=torch.int64))
-        if not feats:
-            raise ValueError("fit_residuals: the loader gave no batch")
+        ``transform=None``: one pass of ``loader`` (an iterable of (image, label) batches of preprocessed images) through the frozen
+        image tower (``image_features_f32``), the raw features and the labels kept on the device, then ``taskresfit.fit_residuals(
+        features, labels, base_text_features, residuals, **fit_args)``.  Caching the features equals the reference's loop only for a
+        DETERMINISTIC train transform; the reference's config trains with ``random_resized_crop`` + ``random_flip``, which give every
+        epoch other features.
+
+        ``transform=TrainPreprocess(...)`` is that regime: ``loader`` yields (decoded uint8 images, labels) and is iterated once per
+        epoch, every batch going transform -> image tower -> ``TaskResFitState.step`` with nothing synchronising until the end
+        (``augment.fit_with_transform``).  ``fit_args``: ``epochs`` (200), ``lr`` (2e-4), ``lr_per_epoch``, ``optimizer`` and its settings,
+        ``views`` (explicit boxes and flips per batch) and ``return_history``; the batch size and the order are the loader's."""
         fit_args.setdefault("alpha", self.prompt_learner.alpha)
         fit_args.setdefault("logit_scale", math.log(self.scale))
         res = self.prompt_learner.text_feature_residuals
-        fitted = fit_residuals(torch.cat(feats), torch.cat(labels), self.prompt_learner.base_text_features.float(), res.detach().float(),
-                               **fit_args)
+        base = self.prompt_learner.base_text_features.float()
+        if transform is not None:
+            from ..augment import fit_with_transform
+            from ..taskresfit import TaskResFitState
+            run = {k: fit_args.pop(k) for k in ("lr_per_epoch", "views", "return_history") if k in fit_args}
+            epochs, lr = fit_args.pop("epochs", 200), fit_args.pop("lr", 2e-4)
+            state = TaskResFitState(base, res.detach().float(), **fit_args)
+            losses = fit_with_transform(state, self.clip_model.image_features_f32, base.shape[0], loader, transform, epochs, lr, **run)
+            fitted = state.residuals if losses is None else (state.residuals, losses)
+        else:
+            from ..taskresfit import fit_residuals
+            feats, labels = [], []
+            with torch.no_grad():
+                for image, label in loader:
+                    f = self.clip_model.image_features_f32(image)
+                    feats.append(f)
+                    labels.append(torch.as_tensor(label).to(device=f.device, dtype=torch.int64))
+            if not feats:
+                raise ValueError("fit_residuals: the loader gave no batch")
+            fitted = fit_residuals(torch.cat(feats), torch.cat(labels), base, res.detach().float(), **fit_args)
         with torch.no_grad():
             res.copy_(fitted[0] if isinstance(fitted, tuple) else fitted)
         return fitted

@@ -745,6 +745,38 @@ size_t clipmi_preprocess_workspace_bytes(const clipmi_image_desc* images, int B,
 int clipmi_preprocess(const void* pixels, int64_t pixels_bytes, const clipmi_image_desc* images, int B, int n_px, int filter,
                       const float* table, void* out, int out_dtype, void* workspace, size_t workspace_bytes, clipmi_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------
+ * The reference's train transform (every training config: INPUT.TRANSFORMS random_resized_crop, random_flip, normalize) on the
+ * device, the random draws left to the host: one VIEW is one output image, a box of one input image stretched to n_px x n_px.
+ * ---------------------------------------------------------------------------------------------------- */
+
+/* One view: the box rows top .. top + height - 1, columns left .. left + width - 1 of images[image]; flip != 0 mirrors the OUTPUT
+ * left to right.  Several views may name the same image. */
+typedef struct {
+  int32_t image;
+  int32_t top, left, height, width;
+  int32_t flip;
+} clipmi_view_desc;
+
+/* Device workspace clipmi_augment needs for these images and views (host descriptors): both descriptor copies plus the tap tables
+ * (2 * V * n_px * kmax int32, kmax = Pillow's largest kernel size over the views' box sides).  0 when an argument is bad. */
+size_t clipmi_augment_workspace_bytes(const clipmi_image_desc* images, int B, const clipmi_view_desc* views, int V, int n_px, int filter);
+
+/* torchvision's PIL path of RandomResizedCrop + RandomHorizontalFlip + ToTensor + Normalize for V given views of B uint8 RGB images:
+ *   1. img.crop(box).resize((n_px, n_px), filter): Pillow's 8-bit resampler as in clipmi_preprocess, bit-exact, but as a STRETCH of the
+ *      box -- on each axis the coefficients are computed with in_size = the box's side and out_size = n_px, so no tap reaches past the
+ *      box edge and no pixel outside the box is read; a pass whose in and out sizes are equal is skipped, as Pillow skips it;
+ *   2. transpose(FLIP_LEFT_RIGHT) of the resized image when the view's flip is set;
+ *   3. out[v, c, y, x] = table[c * 256 + u], the table of clipmi_preprocess.
+ * images and views are HOST descriptors; every field is checked before anything is launched: the image checks of clipmi_preprocess,
+ * 1 <= V <= 65535 (CLIPMI_ERR_SHAPE), box sides >= 1 (CLIPMI_ERR_SHAPE), view.image in [0, B) and the box inside its image
+ * (CLIPMI_ERR_ARG).  Both descriptor arrays are copied into the workspace on `stream` under clipmi_preprocess's rule for page-locked
+ * memory; no synchronisation.  out: [V, 3, n_px, n_px] contiguous, out_dtype CLIPMI_F16 or CLIPMI_F32.  workspace: 256-byte aligned,
+ * at least clipmi_augment_workspace_bytes(...) bytes; one workspace serves one call in flight.  Two launches. */
+int clipmi_augment(const void* pixels, int64_t pixels_bytes, const clipmi_image_desc* images, int B, const clipmi_view_desc* views, int V,
+                   int n_px, int filter, const float* table, void* out, int out_dtype, void* workspace, size_t workspace_bytes,
+                   clipmi_stream_t stream);
+
 /* Ceiling probe for bench.py (`ceiling.mfma_only`; not on any product path): a register-only loop of v_mfma_f32_16x16x32_f16 -- no LDS, no
  * memory inside the loop -- on one workgroup of `waves` waves (1..8: two per SIMD, 256 registers each) per CU, every wave holding two register-resident sets of 4 + 4
  * operand fragments loaded once from `operands` (fp16 [16][waves * 64][8]: whatever distribution the caller wants the matrix pipe to
