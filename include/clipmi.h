@@ -675,7 +675,8 @@ int clipmi_text_blocks(clipmi_model* m, const void* x, void* y, int dtype, int n
  * their [C,L,..] layout; rows >= seq_rows are never read): identical features, L / seq_rows times fewer rows through every GEMM
  * ("X X X X a photo of a <name>." ends at token ~22 of 77).  The CALLER guarantees max(eot) < seq_rows -- it holds the tokenised prompts on the
  * host side and computes the bound once, without a per-call device sync -- and 1 + hook->n_ctx <= seq_rows; an EOT index outside is clamped
- * to seq_rows - 1 as it is to L - 1 today.  A VIOLATION IS NOT DETECTED: with a bound that is too small the call returns CLIPMI_OK and the
+ * to seq_rows - 1 as it is to L - 1 today, and a negative one to 0: eot[c] is read as clamp(eot[c], 0, rows - 1) with rows the token rows that are
+ * computed, so the feature is finite and is that of the clamped row (tests/test_gpu_text_ops.py).  A VIOLATION IS NOT DETECTED: with a bound that is too small the call returns CLIPMI_OK and the
  * features of token row seq_rows - 1 for every prompt whose EOT lies behind it (the EOT indices live on the device; checking them would cost the
  * sync this argument exists to avoid).  Callers that cannot vouch for the bound pass 0.  seq_rows <= 0 or >= L: the whole context. */
 int clipmi_text_encoder(clipmi_model* m, const void* prompts, int dtype, const int32_t* eot, int n_prompts, int seq_rows,
