@@ -87,6 +87,16 @@ class PromptHook(C.Structure):
     _fields_ = [("n_ctx", C.c_int32), ("n_deep", C.c_int32), ("shallow", C.c_void_p), ("deep", C.c_void_p)]
 
 
+class BlockDgrad(C.Structure):
+    """clipmi_block_dgrad: the transposed fp16 weights of one text block (include/clipmi.h)."""
+    _fields_ = [("w_qkv_t", C.c_void_p), ("w_out_t", C.c_void_p), ("w_fc_t", C.c_void_p), ("w_proj_t", C.c_void_p)]
+
+
+class TextDgrad(C.Structure):
+    """clipmi_text_dgrad: text_projection as fp16 [Dt, E] and the blocks' transposed weights."""
+    _fields_ = [("proj", C.c_void_p), ("blocks", C.POINTER(BlockDgrad))]
+
+
 if not os.path.exists(LIB_PATH):
     raise ImportError(
         f"{LIB_PATH} is missing: the HIP extension has not been built. Run `python -c 'import __graft_entry__ as g; "
@@ -157,6 +167,18 @@ _SIGNATURES = {
                                        C.c_double, C.c_double, _vp, _vp, _sz, _vp]),
     "clipmi_taskres_fit": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _f, _vp, _i, _i64, _f, _f, _f, _i,
                                 C.c_double, C.c_double, C.c_double, _vp, _vp, _sz, _vp]),
+    "clipmi_layernorm_backward": (_i, [_vp, _i64, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _f, _vp]),
+    "clipmi_quickgelu_backward": (_i, [_vp, _vp, _vp, _i64, _vp]),
+    "clipmi_attention_backward": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
+    "clipmi_coop_head_workspace_bytes": (_sz, [_i, _i, _i]),
+    "clipmi_coop_head": (_i, [_vp, _i64, _vp, _vp, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "clipmi_ctx_step": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _i, _f, _f, _f, _i, _vp]),
+    "clipmi_text_train_bytes": (_i, [_vp, _i, _i, C.POINTER(_sz), C.POINTER(_sz)]),
+    "clipmi_text_encoder_train": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp, _i, _i, C.POINTER(PromptHook), _vp, _vp, _sz, _vp, _sz, _u, _vp]),
+    "clipmi_text_encoder_backward": (_i, [_vp, C.POINTER(TextDgrad), _vp, _i, _i, _vp, _vp, _sz, _vp, _sz, _vp, _vp]),
+    "clipmi_coop_train_step_bytes": (_sz, [_vp, _i, _i, _i]),
+    "clipmi_coop_train_step": (_i, [_vp, C.POINTER(TextDgrad), _vp, _i, _vp, _vp, _i, _i, _vp, _i, _i, _vp, _i64, _vp, _i, _f, _f, _vp, _i, _f,
+                                    _f, _f, _i, _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
     "clipmi_order_stats_workspace_bytes": (_sz, [_i, _i]),
     "clipmi_order_stats": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
     "clipmi_group_gap_accumulate": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _vp]),

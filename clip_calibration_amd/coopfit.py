@@ -1,0 +1,356 @@
+"""CoOp's context vectors trained on the GPU (reference trainers/classification/coop.py:70-144, 192-222, 282-309).
+
+The reference trains one tensor, the prompt learner's ``ctx`` ([n_ctx, D], or [C, n_ctx, D] with class-specific contexts), with Dassl's
+epoch loop: every step builds the prompts ``[SOS | ctx | class tokens, EOS, padding]``, runs the frozen text tower on them and the frozen
+image tower on the batch, normalises both sides, takes ``F.cross_entropy`` of ``exp(logit_scale)`` times the cosine and one
+``torch.optim.SGD`` step on ``ctx``.  ``ctx`` reaches the loss only through the text tower, so a step needs the gradient of the text
+features with respect to the tower's input embeddings.  csrc/text_backward.hip computes it with the tower frozen: a training forward that
+keeps what the backward needs in a stash, the loss head, the backward (every Linear's backward is the forward's fp16 GEMM on a transposed
+copy of the weight, packed once per bound model), and the context's gradient with the optimiser's rule -- no autograd graph.  fp16 GEMM
+operands, fp32 accumulation, fp32 residual and gradient streams, an fp32 master copy of ``ctx``.  DESIGN.md "CoOp fit" has the data flow.
+
+``grad_scale``: fp16 operands flush small gradients, so the whole backward carries ``grad_scale`` times the gradient (a power of two: the
+scaling itself is exact); the loss head multiplies and the context step divides.  The default, 2^12, comes from the measurement in
+profiles/coopfit_parity.txt (ViT-B/16 text geometry); a model with much larger gradients needs a smaller one.
+
+Three ways in.  ``context_gradient`` returns one batch's loss and gradient (the diagnostic entry point of the tests).  ``fit_context``
+trains from a cached [N, E] matrix of image features and enqueues every step of every epoch with one synchronisation at the end: that
+equals the reference's loop only when the train transform is deterministic.  ``CoOpFitState.step`` takes one batch of features at a time,
+for callers that run the image tower on every step (``CustomCLIP.fit_context(loader, transform=TrainPreprocess(...))``).
+
+Dassl is not part of this repository's environment.  The defaults below -- SGD at 0.002 with momentum 0.9 and weight decay 5e-4, no
+dampening, no Nesterov; 200 epochs in batches of 32; a constant warm-up epoch at 1e-5 that hands over to a cosine schedule; 16 context
+vectors drawn from N(0, 0.02^2) -- restate configs/trainers/CoOp/vit_b16_c16_ep200_batch32.yaml and Dassl's public defaults and are
+UNVERIFIED here; that is why each of them is an argument.  Dassl's random sampler is the caller's ``order``.
+
+Not covered: ``nn.DataParallel`` (one process drives one GPU), class token positions other than ``end``, models whose text tower carries
+deep prompts, and the extra loss terms of KgCoOp, ProGrad and ProDA (follow-ups on this backward).
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+from typing import Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib, ops
+from ._lib import check, lib
+from .taskresfit import _host_int_array, _labels, _need_gpu
+from .tempfit import cosine_warmup_schedule, steps_per_epoch
+
+# 2^12, measured on the ViT-B/16 text geometry with synthetic weights (profiles/coopfit_parity.txt, "grad_scale"): the smallest of 2^0, 2^4,
+# 2^8, 2^12, 2^16 that leaves under 1 % of the fp16 dgrad-GEMM operand elements subnormal (0.76 %; 6.8 % at 2^8, 52 % at 2^0) with at least
+# 2^4 of headroom below fp16's largest value (2^5.9; 2^1.9 at 2^16).  A model whose gradients are much larger than that model's overflows
+# fp16 at this scale -- the context then turns NaN, it does not go wrong silently; pass a smaller power of two.
+DEFAULT_GRAD_SCALE = 4096.0
+
+_DT = {torch.float16: _lib.F16, torch.float32: _lib.F32}
+
+
+def _check_grad_scale(who: str, grad_scale: float) -> float:
+    g = float(grad_scale)
+    if not (math.isfinite(g) and g > 0.0 and math.frexp(g)[0] == 0.5):
+        raise ValueError(f"{who}: grad_scale={grad_scale} must be a power of two (the scaling has to be exact)")
+    return g
+
+
+def _check_sgd(who: str, momentum: float, dampening: float, weight_decay: float, nesterov: bool) -> None:
+    if not (0.0 <= momentum < 1.0 and 0.0 <= dampening < 1.0):
+        raise ValueError(f"{who}: momentum={momentum}, dampening={dampening} (both in [0, 1))")
+    if not weight_decay >= 0.0 or not math.isfinite(weight_decay):
+        raise ValueError(f"{who}: weight_decay={weight_decay} (finite, >= 0)")
+    if nesterov and (momentum <= 0.0 or dampening != 0.0):
+        raise ValueError(f"{who}: Nesterov momentum requires a momentum and zero dampening")
+
+
+def _check_prompts(who: str, clip_model, tokenized_prompts, ctx) -> Tuple[int, int, bool, int]:
+    """(C, n_ctx, per_class, last EOT position) after the host-side checks of the prompt set against the model and the context."""
+    L, D = int(clip_model.context_length), int(clip_model.ln_final.weight.shape[0])
+    if getattr(clip_model, "ivlp_text_prompts", None) is not None and clip_model.ivlp_text_prompts()[0]:
+        raise ValueError(f"{who}: the model's text tower carries deep prompts; the training forward does not support them")
+    ids = _host_int_array(tokenized_prompts, "tokenized_prompts")
+    if ids.ndim != 2 or ids.shape[1] != L or ids.shape[0] < 2:
+        raise ValueError(f"{who}: tokenized_prompts {ids.shape} must be [C >= 2, {L}]")
+    if not isinstance(ctx, torch.Tensor) or ctx.dim() not in (2, 3) or ctx.shape[-1] != D or not ctx.dtype.is_floating_point:
+        raise ValueError(f"{who}: ctx {tuple(getattr(ctx, 'shape', ()))} must be [n_ctx, {D}] or [C, n_ctx, {D}]")
+    per_class = ctx.dim() == 3
+    if per_class and ctx.shape[0] != ids.shape[0]:
+        raise ValueError(f"{who}: a class-specific ctx {tuple(ctx.shape)} needs one context per prompt ({ids.shape[0]})")
+    n_ctx = int(ctx.shape[-2])
+    eot = ids.argmax(axis=1)
+    if n_ctx < 1 or not 1 + n_ctx < L or int(eot.min()) <= n_ctx:
+        raise ValueError(f"{who}: n_ctx={n_ctx} does not fit the prompts (context of {L} tokens, first EOT at {int(eot.min())}): the layout is "
+                         "[SOS | ctx | class tokens, EOS]")
+    return ids.shape[0], n_ctx, per_class, int(eot.max())
+
+
+def _check_batch(who: str, features, labels, C: int, E: int):
+    if not isinstance(features, torch.Tensor) or features.dim() != 2 or features.shape[0] < 1 or features.shape[1] != E:
+        raise ValueError(f"{who}: features {tuple(getattr(features, 'shape', ()))} must be [B >= 1, E = {E}]")
+    if isinstance(labels, torch.Tensor) and labels.is_cuda and labels.dtype == torch.int64:
+        if labels.shape != (features.shape[0],):
+            raise ValueError(f"{who}: {features.shape[0]} rows need {features.shape[0]} labels, got {tuple(labels.shape)}")
+        return labels
+    return _labels(who, labels, features.shape[0], C)
+
+
+def _dgrad(model):
+    """The transposed fp16 copies of the frozen text weights (clipmi_text_dgrad), packed once per bound model and again when a text
+    weight's version moves."""
+    model._ensure_bound()
+    blocks = list(model.transformer.resblocks)
+    ws = [model.text_projection] + [w for b in blocks for w in (b.attn.in_proj_weight, b.attn.out_proj.weight, b.mlp.c_fc.weight, b.mlp.c_proj.weight)]
+    key = (id(model._bound),) + tuple((w.data_ptr(), w._version) for w in ws)
+    hit = model.__dict__.get("_coop_dgrad")
+    if hit is not None and hit[0] == key:
+        return hit[1]
+    keep = []
+
+    def t16(w):
+        t = w.detach().to(torch.float16).t().contiguous()
+        keep.append(t)
+        return t.data_ptr()
+
+    arr = (_lib.BlockDgrad * len(blocks))()
+    for i, b in enumerate(blocks):
+        arr[i] = _lib.BlockDgrad(t16(b.attn.in_proj_weight), t16(b.attn.out_proj.weight), t16(b.mlp.c_fc.weight), t16(b.mlp.c_proj.weight))
+    proj = model.text_projection.detach().to(torch.float16).contiguous()
+    keep.append(proj)
+    td = _lib.TextDgrad(proj.data_ptr(), arr)
+    model.__dict__["_coop_dgrad"] = (key, (td, arr, keep))
+    return td, arr, keep
+
+
+class _Tower:
+    """The frozen text tower in training mode for one prompt set: base embeddings, EOT indices, workspace, stash and the gradient stream."""
+
+    def __init__(self, who: str, clip_model, tokenized_prompts, n_cls: int, n_ctx: int, per_class: bool, last_eot: int, seq_rows: Optional[int]):
+        dev = clip_model.device
+        if dev.type != "cuda":
+            raise RuntimeError(f"clipmi: {who} needs the model on a ROCm GPU (model.to('cuda')); the HIP path has no CPU fallback")
+        if dev.index != torch.cuda.current_device():
+            raise RuntimeError(f"clipmi: the model is on {dev} but the current device is cuda:{torch.cuda.current_device()}")
+        self.model, self.C, self.n_ctx, self.per_class = clip_model, n_cls, n_ctx, per_class
+        g = clip_model.geometry
+        self.Lc, self.D, self.E = g.context_length, g.transformer_width, g.embed_dim
+        ids = torch.as_tensor(tokenized_prompts).to(dev)
+        with torch.no_grad():
+            self.base = clip_model.token_embedding(ids).type(clip_model.dtype).contiguous()   # [C, Lc, D]; rows 1 .. n_ctx are placeholders
+        if self.base.dtype not in _DT:
+            raise TypeError(f"{who}: the model's dtype {self.base.dtype} is not fp16 or fp32")
+        self.eot = ids.argmax(dim=-1).to(torch.int32).contiguous()
+        if seq_rows is None:
+            rows = min(self.Lc, (last_eot + 1 + 7) // 8 * 8) if clip_model.text_dead_row_elimination else self.Lc
+        else:
+            rows = int(seq_rows)
+            if rows and rows <= last_eot:
+                raise ValueError(f"{who}: seq_rows={rows} cuts the EOT row {last_eot}")
+        self.rows = rows if 0 < rows < self.Lc else 0
+        self.L = self.rows or self.Lc
+        clip_model._ensure_bound()
+        self.dgrad = _dgrad(clip_model)
+        wsb, stb = C.c_size_t(0), C.c_size_t(0)
+        check(lib.clipmi_text_train_bytes(clip_model._handle, self.C, self.rows, C.byref(wsb), C.byref(stb)), "clipmi_text_train_bytes")
+        self.stash_bytes = stb.value
+        self.ws = torch.empty(max(wsb.value, 256), dtype=torch.uint8, device=dev)
+        self.stash = torch.empty(max(stb.value, 256), dtype=torch.uint8, device=dev)
+        self.text = torch.empty(self.C, self.E, dtype=torch.float32, device=dev)
+        self.d_embed = torch.empty(self.C * self.L, self.D, dtype=torch.float32, device=dev)
+        self.step_ws = None
+
+    def forward(self, ctx: torch.Tensor) -> torch.Tensor:
+        m = self.model
+        with m._launch_lock:
+            check(lib.clipmi_text_encoder_train(m._handle, self.base.data_ptr(), _DT[self.base.dtype], ctx.data_ptr(), self.n_ctx, int(self.per_class),
+                                                self.eot.data_ptr(), self.C, self.rows, None, self.text.data_ptr(), self.ws.data_ptr(),
+                                                self.ws.numel(), self.stash.data_ptr(), self.stash.numel(), _lib.CALL_DEFAULT, ops._stream()),
+                  "clipmi_text_encoder_train")
+        return self.text
+
+    def backward(self, d_text: torch.Tensor, stats: Optional[torch.Tensor] = None) -> torch.Tensor:
+        m = self.model
+        with m._launch_lock:
+            check(lib.clipmi_text_encoder_backward(m._handle, C.byref(self.dgrad[0]), d_text.data_ptr(), self.C, self.rows, self.d_embed.data_ptr(),
+                                                   self.ws.data_ptr(), self.ws.numel(), self.stash.data_ptr(), self.stash.numel(),
+                                                   None if stats is None else stats.data_ptr(), ops._stream()), "clipmi_text_encoder_backward")
+        return self.d_embed
+
+    def one_call_workspace(self, B: int) -> torch.Tensor:
+        need = lib.clipmi_coop_train_step_bytes(self.model._handle, self.C, self.rows, B)
+        if self.step_ws is None or self.step_ws.numel() < need:
+            self.step_ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.ws.device)
+        return self.step_ws
+
+
+def _master_ctx(ctx: torch.Tensor, dev) -> torch.Tensor:
+    return ctx.detach().to(device=dev, dtype=torch.float32, copy=True).contiguous()
+
+
+def context_gradient(clip_model, tokenized_prompts, ctx: torch.Tensor, features: torch.Tensor, labels, logit_scale: float = 4.6052,
+                     grad_scale: float = DEFAULT_GRAD_SCALE, seq_rows: Optional[int] = None, return_operand_stats: bool = False):
+    """``(loss, grad)`` of ``F.cross_entropy(exp(logit_scale) * normalise(features) @ normalise(text_encoder(prompts(ctx))).T, labels)``
+    with respect to ``ctx`` ([n_ctx, D] generic or [C, n_ctx, D] class-specific), on the GPU: loss fp32 [1], grad fp32 of ctx's shape.
+    ``features`` fp32 [B, E] raw image features (the rows may be a column slice), ``tokenized_prompts`` [C, context_length] the ids of
+    ``"X .. X name."``.  ``seq_rows``: the live token rows per prompt (None: behind the last EOT, rounded up to a multiple of 8; 0: the
+    whole context).  ``return_operand_stats`` adds a dict over every fp16 dgrad-GEMM operand element: ``elements``, ``zeros``,
+    ``subnormals``, ``max`` -- the measurement behind the default ``grad_scale``."""
+    who = "context_gradient"
+    Cn, n_ctx, per_class, last = _check_prompts(who, clip_model, tokenized_prompts, ctx)
+    gs = _check_grad_scale(who, grad_scale)
+    if not math.isfinite(logit_scale):
+        raise ValueError(f"{who}: logit_scale={logit_scale} (finite)")
+    lab = _check_batch(who, features, labels, Cn, int(clip_model.geometry.embed_dim))
+    _need_gpu(features, "features")
+    tower = _Tower(who, clip_model, tokenized_prompts, Cn, n_ctx, per_class, last, seq_rows)
+    dev = features.device
+    labels_d = lab if isinstance(lab, torch.Tensor) else torch.from_numpy(lab.astype(np.int64)).to(dev)
+    master = _master_ctx(ctx, dev)
+    text = tower.forward(master)
+    loss, d_text = ops.coop_head(features, labels_d, text, float(np.float32(math.exp(logit_scale))), gs)
+    stats = torch.zeros(4, dtype=torch.int64, device=dev) if return_operand_stats else None
+    d_embed = tower.backward(d_text, stats)
+    grad = ops.ctx_step(d_embed, Cn, n_ctx, per_class, gs)
+    if not return_operand_stats:
+        return loss, grad
+    s = stats.cpu().numpy()
+    top = float(np.array([int(s[3])], dtype=np.uint16).view(np.float16)[0])
+    return loss, grad, {"elements": int(s[0]), "zeros": int(s[1]), "subnormals": int(s[2]), "max": top}
+
+
+class CoOpFitState:
+    """The training state of CoOp's context: the fp32 master ``ctx``, SGD's momentum buffer, the tower's stash and the number of steps
+    taken.  ``step`` enqueues one forward, backward and update and does not synchronise."""
+
+    def __init__(self, clip_model, tokenized_prompts, ctx: torch.Tensor, logit_scale: float = 4.6052, momentum: float = 0.9,
+                 dampening: float = 0.0, nesterov: bool = False, weight_decay: float = 5e-4, grad_scale: float = DEFAULT_GRAD_SCALE,
+                 seq_rows: Optional[int] = None):
+        who = "CoOpFitState"
+        self.C, self.n_ctx, self.per_class, last = _check_prompts(who, clip_model, tokenized_prompts, ctx)
+        self.grad_scale = _check_grad_scale(who, grad_scale)
+        _check_sgd(who, momentum, dampening, weight_decay, nesterov)
+        if not math.isfinite(logit_scale):
+            raise ValueError(f"{who}: logit_scale={logit_scale} (finite)")
+        self.tower = _Tower(who, clip_model, tokenized_prompts, self.C, self.n_ctx, self.per_class, last, seq_rows)
+        dev = clip_model.device
+        self.ctx = _master_ctx(ctx, dev)
+        self.buf = torch.zeros_like(self.ctx) if momentum != 0.0 else None
+        self.scale = float(np.float32(math.exp(logit_scale)))
+        self.momentum, self.dampening, self.nesterov, self.weight_decay = momentum, dampening, nesterov, weight_decay
+        self.steps = 0
+
+    def step(self, features: torch.Tensor, labels, lr, want_loss: bool = False, one_call: bool = False) -> Optional[torch.Tensor]:
+        """One optimiser step on the batch ``features`` fp32 [B, E] (raw image features on the GPU) and ``labels`` [B] at the rate ``lr``:
+        an fp32 tensor of one element on the device is read where it lies (``rates[k:k + 1]``); a Python number is uploaded on every call.
+        A label tensor on the GPU is taken as it is -- a label outside [0, C) then makes the context NaN, it is never used as an address;
+        host labels are range-checked.  ``one_call``: the same launches through the library's one-call step (clipmi_coop_train_step).
+        Returns the batch loss, fp32 [1] on the device, when ``want_loss``."""
+        t = self.tower
+        lab = _check_batch("CoOpFitState.step", features, labels, self.C, t.E)
+        _need_gpu(features, "features")
+        if features.dtype != torch.float32 or features.stride(1) != 1:
+            raise TypeError("CoOpFitState.step: features must be fp32 with unit column stride")
+        dev = features.device
+        labels_d = lab if isinstance(lab, torch.Tensor) else torch.from_numpy(lab.astype(np.int64)).to(dev)
+        lr_d = ops._dev(lr, "lr", (torch.float32,)) if isinstance(lr, torch.Tensor) else torch.tensor([float(lr)], dtype=torch.float32).to(dev)
+        first = self.steps == 0
+        if one_call:
+            loss = torch.empty(1, dtype=torch.float32, device=dev) if want_loss else None
+            ws = t.one_call_workspace(features.shape[0])
+            m = t.model
+            with m._launch_lock:
+                check(lib.clipmi_coop_train_step(m._handle, C.byref(t.dgrad[0]), t.base.data_ptr(), _DT[t.base.dtype], self.ctx.data_ptr(),
+                                                 None if self.buf is None else self.buf.data_ptr(), t.n_ctx, int(t.per_class), t.eot.data_ptr(), t.C,
+                                                 t.rows, features.data_ptr(), features.stride(0), labels_d.data_ptr(), features.shape[0], self.scale,
+                                                 self.grad_scale, lr_d.data_ptr(), int(first), float(self.momentum), float(self.dampening),
+                                                 float(self.weight_decay), int(bool(self.nesterov)), None if loss is None else loss.data_ptr(), None,
+                                                 ws.data_ptr(), ws.numel(), t.stash.data_ptr(), t.stash.numel(), ops._stream()),
+                      "clipmi_coop_train_step")
+        else:
+            text = t.forward(self.ctx)
+            loss, d_text = ops.coop_head(features, labels_d, text, self.scale, self.grad_scale)
+            d_embed = t.backward(d_text)
+            ops.ctx_step(d_embed, t.C, t.n_ctx, t.per_class, self.grad_scale, self.ctx, self.buf, lr_d, first, self.momentum, self.dampening,
+                         self.weight_decay, self.nesterov, want_grad=False)
+            loss = loss if want_loss else None
+        self.steps += 1
+        return loss
+
+
+def init_context(clip_model, n_ctx: int = 16, n_cls: Optional[int] = None, seed: int = 0) -> torch.Tensor:
+    """The reference's random initialisation (coop.py:92-99): N(0, 0.02^2), [n_ctx, D] or, with ``n_cls``, class-specific [n_cls, n_ctx, D]."""
+    D = int(clip_model.ln_final.weight.shape[0])
+    g = torch.Generator().manual_seed(seed)
+    shape = (n_ctx, D) if n_cls is None else (n_cls, n_ctx, D)
+    return 0.02 * torch.randn(*shape, generator=g)
+
+
+def fit_context(features: torch.Tensor, labels, clip_model, tokenized_prompts, ctx: Optional[torch.Tensor] = None, n_ctx: int = 16,
+                csc: bool = False, logit_scale: float = 4.6052, lr: float = 0.002, epochs: int = 200, batch_size: int = 32,
+                momentum: float = 0.9, dampening: float = 0.0, weight_decay: float = 5e-4, nesterov: bool = False,
+                grad_scale: float = DEFAULT_GRAD_SCALE, seq_rows: Optional[int] = None, lr_per_epoch: Optional[Sequence[float]] = None,
+                order=None, drop_last: bool = False, return_history: bool = False):
+    """Train CoOp's context on cached ``features`` fp32 [N, E] (raw image features on the GPU; the rows may be a column slice) and
+    ``labels`` [N], starting from ``ctx`` (not modified; None = ``init_context(clip_model, n_ctx, C if csc else None)``): ``epochs``
+    passes of ``torch.optim.SGD(lr, momentum, dampening, weight_decay, nesterov)`` over batches of ``batch_size``.
+
+    ``lr_per_epoch`` gives every epoch's rate; None takes ``cosine_warmup_schedule(lr, epochs)``.  ``order`` is an integer [epochs, N]
+    array of sample indices, batch k of epoch e being ``order[e, k * batch_size : (k + 1) * batch_size]``; None is 0 .. N-1 in every
+    epoch.  The last batch of an epoch is short unless ``drop_last`` drops it.  Labels and ``order`` are checked on the host before
+    anything is launched; from the first launch on nothing synchronises until the one wait at the end.  Returns the fitted fp32 context
+    on the device, or ``(ctx, per-step batch losses as a float32 numpy array)`` with ``return_history``.  The defaults are unverified
+    restatements of the reference's config and Dassl's (module docstring)."""
+    who = "fit_context"
+    ids = _host_int_array(tokenized_prompts, "tokenized_prompts")
+    if ctx is None:
+        ctx = init_context(clip_model, n_ctx, ids.shape[0] if csc else None)
+    Cn, n_ctx, per_class, _ = _check_prompts(who, clip_model, tokenized_prompts, ctx)
+    E = int(clip_model.geometry.embed_dim)
+    if not isinstance(features, torch.Tensor) or features.dim() != 2 or features.shape[0] < 1 or features.shape[1] != E:
+        raise ValueError(f"{who}: features must be a [N >= 1, E = {E}] tensor")
+    N = features.shape[0]
+    epochs, batch_size = int(epochs), int(batch_size)
+    if epochs < 0 or batch_size < 1:
+        raise ValueError(f"{who}: epochs={epochs} (>= 0), batch_size={batch_size} (>= 1)")
+    _check_sgd(who, momentum, dampening, weight_decay, nesterov)
+    _check_grad_scale(who, grad_scale)
+    lab = _labels(who, labels, N, Cn)
+    if order is not None:
+        order = _host_int_array(order, "order")
+        if order.shape != (epochs, N):
+            raise ValueError(f"{who}: order {order.shape} must be [epochs, N] = [{epochs}, {N}]")
+        if order.size and (order.min() < 0 or order.max() >= N):
+            raise ValueError(f"{who}: order holds sample indices outside [0, {N})")
+    rates = cosine_warmup_schedule(lr, epochs) if lr_per_epoch is None else [float(r) for r in lr_per_epoch]
+    if len(rates) != epochs:
+        raise ValueError(f"{who}: {len(rates)} learning rates for {epochs} epochs")
+    per_epoch = steps_per_epoch(N, batch_size, drop_last)
+    if epochs * per_epoch == 0:
+        out = ctx.detach().to(torch.float32).clone()
+        out = out.to(features.device) if features.is_cuda else out
+        return (out, np.zeros(0, np.float32)) if return_history else out
+    _need_gpu(features, "features")
+    dev = features.device
+    state = CoOpFitState(clip_model, tokenized_prompts, ctx, logit_scale, momentum, dampening, nesterov, weight_decay, grad_scale, seq_rows)
+    lr_steps = torch.from_numpy(np.repeat(np.asarray(rates, np.float64), per_epoch).astype(np.float32)).to(dev)
+    labels_d = torch.from_numpy(lab.astype(np.int64)).to(dev)
+    order_d = None if order is None else torch.from_numpy(np.ascontiguousarray(order, dtype=np.int64)).to(dev)
+    losses = []
+    step = 0
+    for e in range(epochs):
+        for k in range(per_epoch):
+            lo, hi = k * batch_size, min((k + 1) * batch_size, N)
+            if order_d is None:
+                f, y = features[lo:hi], labels_d[lo:hi]
+            else:
+                idx = order_d[e, lo:hi]
+                f, y = features.index_select(0, idx), labels_d.index_select(0, idx)   # index plumbing
+            loss = state.step(f, y, lr_steps[step:step + 1], want_loss=return_history)
+            if return_history:
+                losses.append(loss)
+            step += 1
+    torch.cuda.current_stream(dev).synchronize()   # the run's one synchronisation
+    if return_history:
+        return state.ctx, torch.cat(losses).cpu().numpy()
+    return state.ctx

@@ -1368,3 +1368,193 @@ int launch_attention(const half_t* qkv, half_t* out, int N, int L, int H, int ca
 }
 
 }  // namespace clipmi
+
+namespace clipmi {
+namespace ab {
+namespace {
+
+// --------------------------------------------------------------------------------------------------------------- attention backward
+// One workgroup of four waves per (prompt, head) item.  LDS: Q, K, V, dO as [96][72] fp16 (rows >= L zero: the products over token rows
+// run in k-steps of 32), P and dS as [96][104] fp16 (zero outside the causal triangle and in rows >= L).
+//   phase A  a wave owns 16 query rows: S = Q K^T and dP = dO V^T for the key tiles up to the diagonal (fp32 accumulators), the masked
+//            softmax and dS = P o (dP - rowsum(dP o P)) in fp32 (the 16 lanes of a DPP row hold one query row's 16 keys of a tile);
+//   phase B  the 3 x ceil(L / 16) x 4 output tiles of dV = P^T dO, dK = dS^T Q / 8, dQ = dS K / 8 dealt round-robin to the waves.
+// v_mfma_f32_16x16x32_f16: lane l holds A[row l & 15][k = 8 (l >> 4) + j] and B[k = 8 (l >> 4) + j][col l & 15], j < 8, and the results
+// C[row 4 (l >> 4) + i][col l & 15], i < 4.  An operand whose k runs along an LDS row is one 16-byte read; one whose k runs down a column
+// is gathered half by half.  Every fragment passes CLIPMI_VALU_TO_MFMA_FENCE (the gathers are packed by vector instructions).
+// the sum / maximum over the 16 lanes of a DPP row (lanes 16 q .. 16 q + 15), by the same tree in every lane
+__device__ __forceinline__ float row16_sum(float v) {
+  v += dpp_f<0xB1>(v);
+  v += dpp_f<0x4E>(v);
+  v += dpp_f<0x141>(v);
+  v += dpp_f<0x140>(v);
+  return v;
+}
+__device__ __forceinline__ float row16_max(float v) {
+  v = fmaxf(v, dpp_f<0xB1>(v));
+  v = fmaxf(v, dpp_f<0x4E>(v));
+  v = fmaxf(v, dpp_f<0x141>(v));
+  v = fmaxf(v, dpp_f<0x140>(v));
+  return v;
+}
+constexpr int THREADS = 256, WAVES = THREADS / 64;   // of this kernel
+constexpr int AB_ROWS = 96, AB_LDH = 72, AB_LDP = 104, AB_TILES = AB_MAX_L / 16;
+constexpr int AB_LDS_BYTES = (4 * AB_ROWS * AB_LDH + 2 * AB_ROWS * AB_LDP) * 2;
+
+__device__ __forceinline__ f16x8 frag_row(const half_t* p) { return *reinterpret_cast<const f16x8*>(p); }
+__device__ __forceinline__ f16x8 frag_col(const half_t* p, int ld) {
+  f16x8 v;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) v[j] = p[j * ld];
+  return v;
+}
+__device__ __forceinline__ f32x4 mma(f16x8 a, f16x8 b, f32x4 c) {
+  CLIPMI_VALU_TO_MFMA_FENCE2(a, b);
+  return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
+}
+__device__ __forceinline__ f32x4 mma0(f16x8 a, f16x8 b) {   // the first of a chain: a constant zero accumulator, no VALU-written SrcC
+  CLIPMI_VALU_TO_MFMA_FENCE2(a, b);
+  return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+}
+#define AB_MFMA_TO_VALU_FENCE(x) asm volatile("s_nop 15\n\ts_nop 15" : "+v"(x))
+
+__global__ __launch_bounds__(THREADS) void attention_backward_kernel(const half_t* __restrict__ qkv, const half_t* __restrict__ d_out,
+                                                                     half_t* __restrict__ dqkv, int L, int H) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char ab_smem[];
+  half_t* sq = reinterpret_cast<half_t*>(ab_smem);
+  half_t* sk = sq + AB_ROWS * AB_LDH;
+  half_t* sv = sk + AB_ROWS * AB_LDH;
+  half_t* sdo = sv + AB_ROWS * AB_LDH;
+  half_t* sp = sdo + AB_ROWS * AB_LDH;
+  half_t* sds = sp + AB_ROWS * AB_LDP;
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, lr = lane & 15, lq = lane >> 4;
+  const int n = blockIdx.x / H, h = blockIdx.x % H, D = 64 * H;
+  const int64_t row0 = (int64_t)n * L;
+  const f16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
+  for (int i = t; i < AB_ROWS * 8; i += THREADS) {
+    const int r = i >> 3, c = (i & 7) * 8;
+    f16x8 q = zero8, k = zero8, v = zero8, o = zero8;
+    if (r < L) {
+      const half_t* row = qkv + (row0 + r) * 3 * D + h * 64 + c;
+      q = *reinterpret_cast<const f16x8*>(row);
+      k = *reinterpret_cast<const f16x8*>(row + D);
+      v = *reinterpret_cast<const f16x8*>(row + 2 * D);
+      o = *reinterpret_cast<const f16x8*>(d_out + (row0 + r) * D + h * 64 + c);
+    }
+    *reinterpret_cast<f16x8*>(sq + r * AB_LDH + c) = q;
+    *reinterpret_cast<f16x8*>(sk + r * AB_LDH + c) = k;
+    *reinterpret_cast<f16x8*>(sv + r * AB_LDH + c) = v;
+    *reinterpret_cast<f16x8*>(sdo + r * AB_LDH + c) = o;
+  }
+  for (int i = t; i < 2 * AB_ROWS * AB_LDP / 8; i += THREADS) *reinterpret_cast<f16x8*>(sp + i * 8) = zero8;   // P and dS, contiguous
+  __syncthreads();
+
+  const int NT = (L + 15) / 16;
+  // ---- phase A
+  for (int qt = wave; qt < NT; qt += WAVES) {
+    f16x8 qa[2], oa[2];
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      qa[ks] = frag_row(sq + (qt * 16 + lr) * AB_LDH + ks * 32 + lq * 8);
+      oa[ks] = frag_row(sdo + (qt * 16 + lr) * AB_LDH + ks * 32 + lq * 8);
+    }
+    f32x4 s[AB_TILES], dp[AB_TILES];
+#pragma unroll
+    for (int kt = 0; kt < AB_TILES; ++kt) {
+      if (kt <= qt) {   // wave-uniform
+        const half_t* kr = sk + (kt * 16 + lr) * AB_LDH + lq * 8;
+        const half_t* vr = sv + (kt * 16 + lr) * AB_LDH + lq * 8;
+        s[kt] = mma0(qa[0], frag_row(kr));
+        s[kt] = mma(qa[1], frag_row(kr + 32), s[kt]);
+        dp[kt] = mma0(oa[0], frag_row(vr));
+        dp[kt] = mma(oa[1], frag_row(vr + 32), dp[kt]);
+        AB_MFMA_TO_VALU_FENCE(s[kt]);
+        AB_MFMA_TO_VALU_FENCE(dp[kt]);
+      } else {
+        s[kt] = f32x4{0.f, 0.f, 0.f, 0.f};
+        dp[kt] = f32x4{0.f, 0.f, 0.f, 0.f};
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int q = qt * 16 + lq * 4 + i;   // this lane's query row of register i; its keys are kt * 16 + lr
+      float m = -INFINITY;
+#pragma unroll
+      for (int kt = 0; kt < AB_TILES; ++kt)
+        if (kt <= qt && kt * 16 + lr <= q) m = fmaxf(m, s[kt][i] * 0.125f);
+      m = row16_max(m);   // key 0 is live for every query: finite
+      float p[AB_TILES], sum = 0.f;
+#pragma unroll
+      for (int kt = 0; kt < AB_TILES; ++kt) {
+        p[kt] = (kt <= qt && kt * 16 + lr <= q) ? __expf(s[kt][i] * 0.125f - m) : 0.f;
+        sum += p[kt];
+      }
+      const float inv = 1.f / row16_sum(sum);
+      float rs = 0.f;
+#pragma unroll
+      for (int kt = 0; kt < AB_TILES; ++kt) {
+        p[kt] *= inv;
+        rs = fmaf(p[kt], dp[kt][i], rs);
+      }
+      rs = row16_sum(rs);
+      if (q < L) {
+#pragma unroll
+        for (int kt = 0; kt < AB_TILES; ++kt)
+          if (kt <= qt) {
+            sp[q * AB_LDP + kt * 16 + lr] = (half_t)p[kt];
+            sds[q * AB_LDP + kt * 16 + lr] = (half_t)(p[kt] * (dp[kt][i] - rs));
+          }
+      }
+    }
+  }
+  __syncthreads();
+
+  // ---- phase B
+  const int KS = (L + 31) / 32;
+  for (int id = wave; id < 3 * NT * 4; id += WAVES) {
+    const int which = id / (NT * 4), rt = (id % (NT * 4)) >> 2, dt = id & 3;   // 0: dV, 1: dK, 2: dQ
+    const half_t* am = which == 0 ? sp : sds;                 // A from P (dV) or dS
+    const half_t* bm = which == 0 ? sdo : (which == 1 ? sq : sk);
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    for (int ks = 0; ks < KS; ++ks) {
+      const int k0 = ks * 32 + lq * 8;
+      // dV, dK: A[row = key][k = query] = M[query][key], down a column of P / dS;  dQ: A[row = query][k = key] along a row of dS
+      const f16x8 a = which == 2 ? frag_row(am + (rt * 16 + lr) * AB_LDP + k0) : frag_col(am + k0 * AB_LDP + rt * 16 + lr, AB_LDP);
+      const f16x8 b = frag_col(bm + k0 * AB_LDH + dt * 16 + lr, AB_LDH);   // B[k = token][col = d]
+      acc = ks == 0 ? mma0(a, b) : mma(a, b, acc);
+    }
+    AB_MFMA_TO_VALU_FENCE(acc);
+    const float sc = which == 0 ? 1.f : 0.125f;
+    const int col = (which == 0 ? 2 * D : (which == 1 ? D : 0)) + h * 64 + dt * 16 + lr;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int row = rt * 16 + lq * 4 + i;
+      if (row < L) dqkv[(row0 + row) * 3 * D + col] = (half_t)(acc[i] * sc);
+    }
+  }
+}
+
+DeviceOnce g_ab_once;
+}  // namespace
+
+int launch_attention_backward(const half_t* qkv, const half_t* d_out, half_t* dqkv, int N, int L, int H, hipStream_t s) {
+  CLIPMI_REQUIRE(N >= 0 && H >= 1 && L >= 1, CLIPMI_ERR_SHAPE, "attention_backward: N=%d L=%d H=%d", N, L, H);
+  CLIPMI_REQUIRE(L <= AB_MAX_L, CLIPMI_ERR_SHAPE, "attention_backward: L=%d (at most %d token rows)", L, AB_MAX_L);
+  CLIPMI_REQUIRE((int64_t)N * H < (1ll << 31) && (int64_t)N * L < (1ll << 31), CLIPMI_ERR_SHAPE, "attention_backward: too many items");
+  if (N == 0) return CLIPMI_OK;
+  CLIPMI_REQUIRE(qkv && d_out && dqkv, CLIPMI_ERR_ARG, "attention_backward: null pointer");
+  CLIPMI_REQUIRE((uintptr_t)qkv % 16 == 0 && (uintptr_t)d_out % 16 == 0 && (uintptr_t)dqkv % 16 == 0, CLIPMI_ERR_ARG,
+                 "attention_backward: pointers must be 16-byte aligned");
+  ensure_dynamic_lds(attention_backward_kernel, AB_LDS_BYTES, g_ab_once);
+  hipLaunchKernelGGL(attention_backward_kernel, dim3((unsigned)(N * H)), dim3(THREADS), AB_LDS_BYTES, s, qkv, d_out, dqkv, L, H);
+  return check_launch("attention_backward_kernel");
+}
+
+
+}  // namespace ab
+
+int launch_attention_backward(const half_t* qkv, const half_t* d_out, half_t* dqkv, int N, int L, int H, hipStream_t s) {
+  return ab::launch_attention_backward(qkv, d_out, dqkv, N, L, H, s);
+}
+
+}  // namespace clipmi

@@ -234,6 +234,9 @@ int launch_layernorm(const void* x, int x_dtype, int64_t in_stride, const int32_
 // n*L + first + j, j < n_ctx.  M = N*L is the partial stride.
 int launch_row_stats(const float* x, half_t* x16, float* stats, int parts, int N, int L, int D, int first, int n_ctx, hipStream_t s);
 int launch_attention(const half_t* qkv, half_t* out, int N, int L, int H, int causal, hipStream_t s);
+// the backward of the causal attention for L <= 80 token rows (CoOp's training path, text_backward.hip): dqkv in qkv's layout from the gradient of `out`
+constexpr int AB_MAX_L = 80;   // token rows per sequence the kernel holds
+int launch_attention_backward(const half_t* qkv, const half_t* d_out, half_t* dqkv, int N, int L, int H, hipStream_t s);
 // attention_cls.hip: the output row of token 0 of every sequence only (the image tower's last block: clip/model.py:419 reads nothing else)
 int launch_attention_cls(const half_t* qkv, half_t* out, int N, int L, int H, hipStream_t s);
 int launch_patchify(const void* image, int image_dtype, half_t* col, int B, int R, int P, int Kpad, hipStream_t s);

@@ -31,6 +31,21 @@ __device__ __forceinline__ void sgd_element(float* __restrict__ w, float* __rest
   w[idx] = v - lr * grad;
 }
 
+// The same rule as torch's foreach kernels on the GPU evaluate it, for a caller that is held to torch.optim.SGD bit for bit (ctx_step_kernel,
+// text_backward.hip): every add(other, alpha) is ONE fused multiply-add there -- g + wd w, mul_(momentum) rounded and then
+// buf + (1 - dampening) g, g + momentum buf, w + (-lr) g -- as measured on the MI355X (tests/test_gpu_text_backward.py).
+__device__ __forceinline__ void sgd_element_fma(float* __restrict__ w, float* __restrict__ buf, int64_t idx, float grad, float lr, const SgdArgs& a) {
+#pragma clang fp contract(off)
+  const float v = w[idx];
+  if (a.weight_decay != 0.f) grad = fmaf(a.weight_decay, v, grad);
+  if (a.momentum != 0.f) {
+    const float b = a.first_step ? grad : fmaf(a.one_minus_dampening, grad, a.momentum * buf[idx]);
+    buf[idx] = b;
+    grad = a.nesterov ? fmaf(a.momentum, b, grad) : b;
+  }
+  w[idx] = fmaf(-lr, grad, v);
+}
+
 // torch.optim.Adam's rule on one element: g += wd w;  m += (g - m)(1 - b1)  (lerp_ with a weight below one half);
 // v = b2 v + ((1 - b2) g) g  (mul_, addcmul_);  w -= (lr / (1 - b1^t)) m / (sqrt(v) / sqrt(1 - b2^t) + eps)  (addcdiv_)
 __device__ __forceinline__ void adam_element(float* __restrict__ w, float* __restrict__ m, float* __restrict__ v, int64_t idx, float grad, float lr,

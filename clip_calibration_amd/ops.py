@@ -857,3 +857,110 @@ def scale_add(a: torch.Tensor, b: torch.Tensor, alpha: float) -> torch.Tensor:
     out = torch.empty_like(a)
     check(lib.clipmi_scale_add(a.data_ptr(), b.data_ptr(), float(alpha), out.data_ptr(), a.numel(), _stream()), "clipmi_scale_add")
     return out
+
+
+# ---- CoOp's training path at operator level (include/clipmi.h "CoOp's context trained on the device", csrc/text_backward.hip) ----------
+def layernorm_backward(x: torch.Tensor, gamma: torch.Tensor, dy: torch.Tensor, g: torch.Tensor, g16: Optional[torch.Tensor] = None,
+                       row_idx: Optional[torch.Tensor] = None, eps: float = 1e-5) -> None:
+    """LayerNorm's backward from the saved fp32 rows ``x`` [R, D] (the rows may be a column slice): ``g[row(r)] += dX(r)`` in place and
+    ``g16[row(r)] = fp16(g[row(r)])``; ``dy`` fp32 or fp16 [rows, D] dense, ``row(r) = row_idx[r]`` (int32) or r."""
+    if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 2 or x.stride(1) != 1:
+        raise TypeError("layernorm_backward: x must be an fp32 [R, D] tensor on the GPU with unit column stride")
+    gamma = _dev(gamma, "gamma", (torch.float32,))
+    dy = _dev(dy, "dy", (torch.float16, torch.float32))
+    rows, D = dy.shape
+    _in_place(g, torch.float32, "layernorm_backward: g must be a contiguous fp32 tensor on the GPU")
+    if g16 is not None:
+        _in_place(g16, torch.float16, "layernorm_backward: g16 must be a contiguous fp16 tensor on the GPU", numel=g.numel())
+    if x.dim() != 2 or x.shape[1] != D or gamma.shape != (D,) or g.dim() != 2 or g.shape[1] != D:
+        raise ValueError("layernorm_backward: x [R, D], gamma [D], dy [rows, D] and g [R, D] do not agree")
+    row_idx, pi = _opt(row_idx, "row_idx", (torch.int32,))
+    if row_idx is None and (x.shape[0] < rows or g.shape[0] < rows):
+        raise ValueError("layernorm_backward: fewer rows in x or g than in dy")
+    if row_idx is not None and row_idx.shape != (rows,):
+        raise ValueError("layernorm_backward: one row index per row of dy")
+    check(lib.clipmi_layernorm_backward(x.data_ptr(), x.stride(0), pi, gamma.data_ptr(), dy.data_ptr(), _DTC[dy.dtype], g.data_ptr(),
+                                        None if g16 is None else g16.data_ptr(), rows, D, float(eps), _stream()), "clipmi_layernorm_backward")
+
+
+_DTC = {torch.float16: F16, torch.float32: F32}
+
+
+def quickgelu_backward(h: torch.Tensor, d_a: torch.Tensor) -> torch.Tensor:
+    """``d_a * d/dh (h sigmoid(1.702 h))`` from the saved fp16 pre-activation ``h``; fp16 in and out."""
+    h, d_a = _dev(h, "h", (torch.float16,)), _dev(d_a, "d_a", (torch.float16,))
+    if h.shape != d_a.shape:
+        raise ValueError("quickgelu_backward: shapes differ")
+    out = torch.empty_like(h)
+    check(lib.clipmi_quickgelu_backward(h.data_ptr(), d_a.data_ptr(), out.data_ptr(), h.numel(), _stream()), "clipmi_quickgelu_backward")
+    return out
+
+
+def attention_backward(qkv: torch.Tensor, d_out: torch.Tensor, n_seq: int, n_head: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The backward of the causal ``attention``: ``qkv`` fp16 [N * L, 3 * 64 * H], ``d_out`` fp16 [N * L, 64 * H] -> dqkv fp16 in qkv's
+    layout (written into ``out`` when given: only its first N * L rows are touched)."""
+    qkv, d_out = _dev(qkv, "qkv", (torch.float16,)), _dev(d_out, "d_out", (torch.float16,))
+    M, D3 = qkv.shape
+    if n_seq < 0 or n_head < 1 or D3 != 3 * 64 * n_head or (n_seq and M % n_seq) or d_out.shape != (M, 64 * n_head):
+        raise ValueError(f"attention_backward: qkv {tuple(qkv.shape)} / d_out {tuple(d_out.shape)} do not fit {n_seq} sequences of {n_head} heads")
+    if out is None:
+        out = torch.empty_like(qkv)
+    else:
+        _in_place(out, torch.float16, "attention_backward: out must be a contiguous fp16 tensor on the GPU")
+        if out.numel() < qkv.numel():
+            raise ValueError("attention_backward: out is too small")
+    L = M // n_seq if n_seq else 1
+    check(lib.clipmi_attention_backward(qkv.data_ptr(), d_out.data_ptr(), out.data_ptr(), n_seq, L, n_head, _stream()), "clipmi_attention_backward")
+    return out
+
+
+def coop_head(features: torch.Tensor, labels: torch.Tensor, text: torch.Tensor, scale: float, grad_scale: float = 1.0, want16: bool = False):
+    """CoOp's loss head: (loss fp32 [1], grad_scale * d loss / d text fp32 [C, E][, the same in fp16]) for raw image ``features`` fp32
+    [B, E] (the rows may be a column slice), ``labels`` int64 [B] and raw ``text`` features fp32 [C, E]; ``scale`` = exp(logit_scale)."""
+    if not isinstance(features, torch.Tensor) or features.dim() != 2 or features.stride(1) != 1:
+        raise ValueError("coop_head: features must be a [B, E] tensor with unit column stride")
+    if not features.is_cuda or features.dtype != torch.float32:
+        raise TypeError("coop_head: features must be fp32 on the GPU")
+    labels, text = _dev(labels, "labels", (torch.int64,)), _dev(text, "text", (torch.float32,))
+    (B, E), Cn = features.shape, text.shape[0]
+    if text.dim() != 2 or text.shape[1] != E or labels.shape != (B,):
+        raise ValueError(f"coop_head: features {tuple(features.shape)}, labels {tuple(labels.shape)}, text {tuple(text.shape)} do not agree")
+    loss = torch.empty(1, dtype=torch.float32, device=text.device)
+    d_text = torch.empty_like(text)
+    d16 = torch.empty(Cn, E, dtype=torch.float16, device=text.device) if want16 else None
+    ws = torch.empty(max(lib.clipmi_coop_head_workspace_bytes(B, E, Cn), 8), dtype=torch.uint8, device=text.device)
+    check(lib.clipmi_coop_head(features.data_ptr(), features.stride(0), labels.data_ptr(), text.data_ptr(), B, E, Cn, float(scale),
+                               float(grad_scale), loss.data_ptr(), d_text.data_ptr(), None if d16 is None else d16.data_ptr(), ws.data_ptr(),
+                               ws.numel(), _stream()), "clipmi_coop_head")
+    return (loss, d_text, d16) if want16 else (loss, d_text)
+
+
+def ctx_step(d_embed: torch.Tensor, n_prompts: int, n_ctx: int, per_class: bool, grad_scale: float, ctx: Optional[torch.Tensor] = None,
+             buf: Optional[torch.Tensor] = None, lr: Optional[torch.Tensor] = None, first_step: bool = False, momentum: float = 0.0,
+             dampening: float = 0.0, weight_decay: float = 0.0, nesterov: bool = False, want_grad: bool = True) -> Optional[torch.Tensor]:
+    """The context's gradient from ``d_embed`` fp32 [C * L, D] (the classes summed in ascending order unless ``per_class``, divided by
+    ``grad_scale``) and, with ``ctx``, torch.optim.SGD's step on it in place at the rate ``lr`` fp32 [1] (``buf``: momentum buffer).
+    Returns the gradient (ctx's shape) when ``want_grad``."""
+    d_embed = _dev(d_embed, "d_embed", (torch.float32,))
+    M, D = d_embed.shape
+    if n_prompts < 1 or M % n_prompts:
+        raise ValueError(f"ctx_step: {M} rows do not split into {n_prompts} prompts")
+    shape = (n_prompts, n_ctx, D) if per_class else (n_ctx, D)
+    pc = pb = pl = None
+    if ctx is not None:
+        _in_place(ctx, torch.float32, "ctx_step: ctx must be a contiguous fp32 tensor on the GPU")
+        if tuple(ctx.shape) != shape:
+            raise ValueError(f"ctx_step: ctx {tuple(ctx.shape)} must be {shape}")
+        pc = ctx.data_ptr()
+        if buf is not None:
+            _in_place(buf, torch.float32, "ctx_step: buf must be a contiguous fp32 tensor on the GPU", numel=ctx.numel())
+            pb = buf.data_ptr()
+        lr = _dev(lr, "lr", (torch.float32,))
+        if lr.numel() != 1:
+            raise ValueError("ctx_step: lr must hold one rate")
+        pl = lr.data_ptr()
+    grad = torch.empty(shape, dtype=torch.float32, device=d_embed.device) if want_grad else None
+    check(lib.clipmi_ctx_step(d_embed.data_ptr(), pc, pb, None if grad is None else grad.data_ptr(), n_prompts, M // n_prompts, D, int(n_ctx),
+                              int(bool(per_class)), float(grad_scale), pl, int(bool(first_step)), float(momentum), float(dampening),
+                              float(weight_decay), int(bool(nesterov)), _stream()), "clipmi_ctx_step")
+    return grad

@@ -1,4 +1,5 @@
-"""CoOp (reference trainers/classification/coop.py:47-222) -- inference forward only."""
+"""CoOp (reference trainers/classification/coop.py:47-222): the inference forward, and the context's training on the GPU
+(``CustomCLIP.fit_context``, clip_calibration_amd/coopfit.py)."""
 from __future__ import annotations
 
 from typing import Optional
@@ -144,6 +145,49 @@ class CustomCLIP(nn.Module):
 
     def _image_features(self, image: torch.Tensor) -> torch.Tensor:
         return self.clip_model.image_features_f32(image)
+
+    def fit_context(self, train_loader, transform=None, **fit_args):
+        """Train ``prompt_learner.ctx`` on the GPU, starting from the parameter's values, with ``logit_scale`` taken from this model
+        unless ``fit_args`` say otherwise (coop.py:282-309 with both towers frozen).  The fitted context is copied into
+        ``prompt_learner.ctx`` in the parameter's dtype (the fit itself keeps an fp32 master copy) -- that moves the parameter's
+        version, so the cached text features retire on their own -- and returned as ``coopfit.fit_context`` returns it.
+
+        ``transform=None``: one pass of ``train_loader`` (an iterable of (image, label) batches of preprocessed images) through the
+        frozen image tower, the raw features and the labels kept on the device, then ``coopfit.fit_context(features, labels, clip_model,
+        tokenized_prompts, ctx, **fit_args)``.  Caching the features equals the reference's loop only for a DETERMINISTIC train
+        transform; the reference's config trains with ``random_resized_crop`` + ``random_flip``.
+
+        ``transform=TrainPreprocess(...)`` is that regime: ``train_loader`` yields (decoded uint8 images, labels) and is iterated once
+        per epoch, every batch going transform -> image tower -> ``CoOpFitState.step`` with nothing synchronising until the end
+        (``augment.fit_with_transform``).  ``fit_args``: ``epochs`` (200), ``lr`` (0.002), ``lr_per_epoch``, the optimiser's
+        ``momentum``, ``dampening``, ``weight_decay``, ``nesterov``, ``grad_scale``, ``seq_rows``, ``views`` and ``return_history``;
+        the batch size and the order are the loader's."""
+        import math
+        fit_args.setdefault("logit_scale", math.log(self.scale))
+        ctx = self.prompt_learner.ctx
+        ids = self.prompt_learner.tokenized_prompts
+        if transform is not None:
+            from ..augment import fit_with_transform
+            from ..coopfit import CoOpFitState
+            run = {k: fit_args.pop(k) for k in ("lr_per_epoch", "views", "return_history") if k in fit_args}
+            epochs, lr = fit_args.pop("epochs", 200), fit_args.pop("lr", 0.002)
+            state = CoOpFitState(self.clip_model, ids, ctx.detach(), **fit_args)
+            losses = fit_with_transform(state, self.clip_model.image_features_f32, ids.shape[0], train_loader, transform, epochs, lr, **run)
+            fitted = state.ctx if losses is None else (state.ctx, losses)
+        else:
+            from ..coopfit import fit_context
+            feats, labels = [], []
+            with torch.no_grad():
+                for image, label in train_loader:
+                    f = self.clip_model.image_features_f32(image)
+                    feats.append(f)
+                    labels.append(torch.as_tensor(label).to(device=f.device, dtype=torch.int64))
+            if not feats:
+                raise ValueError("fit_context: the loader gave no batch")
+            fitted = fit_context(torch.cat(feats), torch.cat(labels), self.clip_model, ids, ctx.detach(), **fit_args)
+        with torch.no_grad():
+            ctx.copy_(fitted[0] if isinstance(fitted, tuple) else fitted)
+        return fitted
 
     overlap_towers: bool = True   # per-batch text tower (cache_text_features=False): run it on a side stream beside the image tower
 

@@ -688,6 +688,108 @@ int clipmi_text_encoder(clipmi_model* m, const void* prompts, int dtype, const i
 int clipmi_encode_text(clipmi_model* m, const int64_t* ids, int n_prompts, int seq_rows, float* out, void* workspace,
                        size_t workspace_bytes, unsigned flags, clipmi_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------
+ * CoOp's context trained on the device (trainers/classification/coop.py:70-144, 192-222, 282-309): the gradient of the text features
+ * with respect to the text tower's INPUT EMBEDDINGS with the tower frozen, CoOp's cross-entropy head and torch.optim.SGD's step on the
+ * context vectors (csrc/text_backward.hip, DESIGN.md "CoOp fit").  No weight gradient exists: every Linear's backward is dX = dY W,
+ * clipmi_gemm_f16 on a transposed copy of the weight that the caller packs once.  The whole backward carries grad_scale * gradient
+ * (a power of two: fp16 operands flush small values); only clipmi_coop_head and clipmi_ctx_step know the factor.
+ * These exports are additive: the ABI version does not change with them.
+ * ---------------------------------------------------------------------------------------------------- */
+
+/* Operator level.
+ * clipmi_layernorm_backward: per row r, with xs = x[row(r)] (fp32, row stride x_stride elements), row(r) = row_idx ? row_idx[r] : r:
+ *   mean / rstd recomputed in fp32 (eps inside the square root);  xhat = (xs - mean) rstd;  t = dy[r, :] * gamma;
+ *   dX = rstd (t - mean(t) - xhat mean(t xhat));   g[row(r), :] += dX (fp32, row stride D);   g16[row(r), :] = fp16(g[row(r), :]).
+ *   dy fp32 or fp16 [rows, D] dense (dy_dtype); g16 may be NULL.  One launch does the residual add and the fp16 operand copy of the
+ *   next GEMM.  D % 4 == 0, D <= 4096, x_stride % 4 == 0; 16-byte aligned x, gamma, g, 8-byte aligned dy, g16.  rows == 0: CLIPMI_OK.
+ * clipmi_quickgelu_backward: d_h = d_a (s + 1.702 h s (1 - s)), s = sigmoid(1.702 h), from the saved fp16 pre-activation h; fp32
+ *   arithmetic, fp16 in and out, n elements; d_h may alias d_a.
+ * clipmi_attention_backward: the backward of clipmi_attention with the causal mask, head dim 64, 1 <= L <= 80 token rows per sequence.
+ *   qkv fp16 [N*L, 3*64*H] as clipmi_attention takes it, d_out fp16 [N*L, 64*H] the gradient of its output, dqkv fp16 [N*L, 3*64*H] the
+ *   gradient in qkv's layout.  One workgroup per (sequence, head) holds Q, K, V and dO in LDS, recomputes S = Q K^T / 8 and the causal
+ *   softmax P in fp32, then dV = P^T dO, dP = dO V^T, dS = P o (dP - rowsum(dP o P)), dQ = dS K / 8, dK = dS^T Q / 8 on the fp16 matrix
+ *   cores with P and dS rounded to fp16; no atomics, the same inputs give the same bits.  16-byte aligned pointers. */
+int clipmi_layernorm_backward(const float* x, int64_t x_stride, const int32_t* row_idx, const float* gamma, const void* dy, int dy_dtype,
+                              float* g, void* g16, int rows, int D, float eps, clipmi_stream_t stream);
+int clipmi_quickgelu_backward(const void* h, const void* d_a, void* d_h, int64_t n, clipmi_stream_t stream);
+int clipmi_attention_backward(const void* qkv, const void* d_out, void* dqkv, int N, int L, int H, clipmi_stream_t stream);
+
+/* CoOp's loss head (coop.py:205-222 + F.cross_entropy): feats fp32 [B, E] raw image features with row stride ld >= E, labels int64 [B],
+ * text fp32 [C, E] raw text features, scale = exp(logit_scale):
+ *   x_b = f_b / |f_b|;  u_c = t_c / |t_c|;  z = scale X U^T;  loss = mean_b CE(z_b, y_b);  dz = grad_scale (softmax(z) - onehot(y)) / B
+ *   du_c = scale sum_b dz[b, c] x_b;  d_text[c, :] = (du_c - u_c (u_c . du_c)) / |t_c|
+ * all fp32, fixed summation orders, the batch loss the float64 mean of the row losses.  loss fp32 [1] or NULL; d_text fp32 [C, E]
+ * (= grad_scale * d loss / d text); d_text16 fp16 [C, E], the same rounded, or NULL.  A label outside [0, C) is never used as an address:
+ * it makes the loss and the gradient NaN.  workspace (8-byte aligned): clipmi_coop_head_workspace_bytes(B, E, C) bytes.  Four launches.
+ * CLIPMI_ERR_SHAPE: B < 1, C < 2, E < 1, ld < E.  CLIPMI_ERR_ARG: a null pointer, a non-finite scale or grad_scale. */
+size_t clipmi_coop_head_workspace_bytes(int B, int E, int C);
+int clipmi_coop_head(const float* feats, int64_t ld, const int64_t* labels, const float* text, int B, int E, int C, float scale,
+                     float grad_scale, float* loss, float* d_text, void* d_text16, void* workspace, size_t workspace_bytes,
+                     clipmi_stream_t stream);
+
+/* The context's gradient and torch.optim.SGD's step.  d_embed fp32 [C * L, D]: grad_scale * d loss / d (input embedding row), L rows per
+ * prompt.  grad[j, :] = (sum_c d_embed[c * L + 1 + j, :]) / grad_scale for j < n_ctx, the classes added in ascending order (generic
+ * context, ctx [n_ctx, D]); with per_class != 0 there is no sum and ctx is [C, n_ctx, D].  Then torch.optim.SGD's rule (the steps of
+ * clipmi_adapter_train_step, each add(other, alpha) as ONE fused multiply-add, which is how torch's GPU kernels round it: the step equals
+ * torch.optim.SGD on the GPU bit for bit) on every element of ctx with the rate *lr (device); buf: the momentum buffer (NULL when momentum == 0); first_step != 0 initialises
+ * it from this gradient.  grad_out (ctx's shape, may be NULL) receives the gradient before weight decay.  ctx == NULL: only grad_out is
+ * written (no step; lr may be NULL).  1 + n_ctx <= L.  One launch, no atomics. */
+int clipmi_ctx_step(const float* d_embed, float* ctx, float* buf, float* grad_out, int C, int L, int D, int n_ctx, int per_class,
+                    float grad_scale, const float* lr, int first_step, float momentum, float dampening, float weight_decay, int nesterov,
+                    clipmi_stream_t stream);
+
+/* The transposed weight copies of the frozen text tower, packed once by the caller: fp16, contiguous, 16-byte aligned.  w_*_t is the
+ * transpose of the clipmi_block_weights member of the same name ([in, out] row-major); proj is text_projection itself, fp16 [Dt, E]. */
+typedef struct clipmi_block_dgrad {
+  const void* w_qkv_t;   /* [D, 3D] */
+  const void* w_out_t;   /* [D, D]  */
+  const void* w_fc_t;    /* [D, 4D] */
+  const void* w_proj_t;  /* [4D, D] */
+} clipmi_block_dgrad;
+typedef struct clipmi_text_dgrad {
+  const void* proj;                  /* [Dt, E] */
+  const clipmi_block_dgrad* blocks;  /* host array [text_layers] */
+} clipmi_text_dgrad;
+
+/* Bytes of the workspace and of the stash the three calls below need for n_prompts prompts of seq_rows live token rows (0 = the whole
+ * context).  Either pointer may be NULL.  Both are 0 for arguments the calls refuse. */
+int clipmi_text_train_bytes(const clipmi_model* m, int n_prompts, int seq_rows, size_t* workspace_bytes, size_t* stash_bytes);
+
+/* clipmi_text_encoder with everything its backward needs kept in `stash`.  prompts (fp16 | fp32) [C, context_length, Dt] without the
+ * positional embedding; ctx fp32 (NULL = none): the context vectors that replace token rows 1 .. n_ctx of every prompt, [n_ctx, Dt], or
+ * [C, n_ctx, Dt] with ctx_per_class != 0, taken in fp32 as they are.  The blocks run LayerNorm, GEMM and attention as separate launches
+ * on the fp32 residual stream (the unfolded path of clipmi_text_encoder), and c_fc keeps its fp16 pre-activation: QuickGELU is an
+ * element-wise launch on that rounded value.  Per block the stash keeps the fp32 input rows, the fp32 rows before ln_2, the fp16 qkv
+ * and the fp16 c_fc pre-activation (22 Dt bytes per token row and layer), plus the last block's output rows (the input of ln_final)
+ * and the gathered EOT row indices.  seq_rows as clipmi_text_encoder takes it.  A hook with deep prompts: CLIPMI_ERR_ARG;
+ * CLIPMI_CALL_STREAM_F16: CLIPMI_ERR_STATE.  workspace and stash 256-byte aligned. */
+int clipmi_text_encoder_train(clipmi_model* m, const void* prompts, int dtype, const float* ctx, int n_ctx, int ctx_per_class,
+                              const int32_t* eot, int n_prompts, int seq_rows, const clipmi_prompt_hook* hook, float* out,
+                              void* workspace, size_t workspace_bytes, void* stash, size_t stash_bytes, unsigned flags,
+                              clipmi_stream_t stream);
+
+/* The backward of the call above from the stash it left: d_out fp32 [C, E] (the gradient of `out`, e.g. clipmi_coop_head's d_text) ->
+ * d_embed fp32 [C * L, Dt], the gradient of the input embedding rows (L = the live rows), overwritten.  Tail: d_out text_projection^T,
+ * ln_final's backward on the EOT rows scattered into the zeroed stream; then per block, last to first: c_proj's dgrad, QuickGELU's
+ * backward, c_fc's dgrad, ln_2's backward, out-proj's dgrad, the attention backward, in-proj's dgrad, ln_1's backward.  GEMM operands
+ * fp16, accumulation and the gradient stream fp32.  operand_stats (device, NULL or 4 x uint64, zeroed by the caller): over every fp16
+ * dgrad-GEMM operand element of the call {elements, exact zeros, fp16 subnormals, the largest magnitude's fp16 bits} -- the measurement
+ * behind grad_scale's default (profiles/coopfit_parity.txt); it costs one launch per operand. */
+int clipmi_text_encoder_backward(clipmi_model* m, const clipmi_text_dgrad* wt, const float* d_out, int n_prompts, int seq_rows,
+                                 float* d_embed, void* workspace, size_t workspace_bytes, const void* stash, size_t stash_bytes,
+                                 unsigned long long* operand_stats, clipmi_stream_t stream);
+
+/* One training step of CoOp as ONE call: clipmi_text_encoder_train, clipmi_coop_head, clipmi_text_encoder_backward and clipmi_ctx_step
+ * enqueued in this order on `stream` -- the same launches, the same bits.  ctx is the fp32 master, updated in place.  workspace of
+ * clipmi_coop_train_step_bytes(...) bytes (256-byte aligned), stash as clipmi_text_train_bytes reports it. */
+size_t clipmi_coop_train_step_bytes(const clipmi_model* m, int n_prompts, int seq_rows, int B);
+int clipmi_coop_train_step(clipmi_model* m, const clipmi_text_dgrad* wt, const void* prompts, int dtype, float* ctx, float* buf, int n_ctx,
+                           int ctx_per_class, const int32_t* eot, int n_prompts, int seq_rows, const float* feats, int64_t ld,
+                           const int64_t* labels, int B, float scale, float grad_scale, const float* lr, int first_step, float momentum,
+                           float dampening, float weight_decay, int nesterov, float* loss, float* grad_out, void* workspace,
+                           size_t workspace_bytes, void* stash, size_t stash_bytes, clipmi_stream_t stream);
+
 /* Timing aid for bench.py (the per-kernel roofline of its JSON line): the five launches of the vision tower's residual
  * block 0 -- 0 in-proj, 1 attention, 2 out-proj + residual, 3 c_fc + QuickGELU, 4 c_proj + residual (clip/model.py:181-188)
  * -- issued exactly as clipmi_encode_image issues them (LayerNorm fold, fp16 stream, tile selection) on the operands the
