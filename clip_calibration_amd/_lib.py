@@ -22,6 +22,7 @@ COMM_ID_BYTES = 128
 EPI_NONE, EPI_BIAS, EPI_BIAS_QUICKGELU, EPI_BIAS_RESIDUAL, EPI_BIAS_RELU, EPI_BIAS_RESIDUAL16_RELU = 0, 1, 2, 3, 4, 5
 CALL_DEFAULT, CALL_STREAM_F32, CALL_STREAM_F16 = 0, 1, 2   # per-call flags of the tower calls (include/clipmi.h)
 FILTER_BILINEAR, FILTER_BICUBIC = 2, 3                      # clipmi_preprocess filters (Pillow's numbers)
+PROMPT_COOP, PROMPT_KGCOOP, PROMPT_PROGRAD = 0, 1, 2        # `mode` of clipmi_prompt_head / clipmi_prompt_train_step (plain integers there)
 OPTIM_SGD, OPTIM_ADAM = 0, 1                                # clipmi_taskres_train_step / clipmi_taskres_fit optimisers
 
 
@@ -179,6 +180,13 @@ _SIGNATURES = {
     "clipmi_coop_train_step_bytes": (_sz, [_vp, _i, _i, _i]),
     "clipmi_coop_train_step": (_i, [_vp, C.POINTER(TextDgrad), _vp, _i, _vp, _vp, _i, _i, _vp, _i, _i, _vp, _i64, _vp, _i, _f, _f, _vp, _i, _f,
                                     _f, _f, _i, _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
+    "clipmi_prompt_head_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "clipmi_prompt_head": (_i, [_vp, _i64, _vp, _vp, _i, _i, _i, _f, _f, _i, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "clipmi_prograd_step_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "clipmi_prograd_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _vp, _i, _f, _f, _f, _i, _vp, _sz, _vp]),
+    "clipmi_prompt_train_step_bytes": (_sz, [_vp, _i, _i, _i, _i, _i, _i]),
+    "clipmi_prompt_train_step": (_i, [_vp, C.POINTER(TextDgrad), _vp, _i, _vp, _vp, _i, _i, _vp, _i, _i, _vp, _i64, _vp, _i, _f, _f, _i, _vp, _f, _f,
+                                      _f, _vp, _i, _f, _f, _f, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
     "clipmi_order_stats_workspace_bytes": (_sz, [_i, _i]),
     "clipmi_order_stats": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
     "clipmi_group_gap_accumulate": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _vp]),

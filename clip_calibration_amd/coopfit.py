@@ -1,4 +1,5 @@
-"""CoOp's context vectors trained on the GPU (reference trainers/classification/coop.py:70-144, 192-222, 282-309).
+"""CoOp's context vectors trained on the GPU (reference trainers/classification/coop.py:70-144, 192-222, 282-309), and KgCoOp's and
+ProGrad's on the same forward and backward (kgcoop.py:246-269, prograd.py:291-304, 371-409).
 
 The reference trains one tensor, the prompt learner's ``ctx`` ([n_ctx, D], or [C, n_ctx, D] with class-specific contexts), with Dassl's
 epoch loop: every step builds the prompts ``[SOS | ctx | class tokens, EOS, padding]``, runs the frozen text tower on them and the frozen
@@ -23,8 +24,18 @@ dampening, no Nesterov; 200 epochs in batches of 32; a constant warm-up epoch at
 vectors drawn from N(0, 0.02^2) -- restate configs/trainers/CoOp/vit_b16_c16_ep200_batch32.yaml and Dassl's public defaults and are
 UNVERIFIED here; that is why each of them is an argument.  Dassl's random sampler is the caller's ``order``.
 
+``method``: "coop" (the default, everything above), "kgcoop" or "prograd"; the latter two need ``teacher``, the frozen zero-shot text
+features fp32 [C, E] on the device (the head normalises the rows).  KgCoOp adds ``w (1 - mean_c cos(u_c, teacher_c))`` to the loss
+(``w`` = 8.0, the reference's TRAINER.KGCOOP.W) and costs what CoOp costs.  ProGrad takes two losses of one forward -- the
+cross-entropy and ``T^2`` times the cross-entropy of ``softmax(z / T)`` against ``softmax(z_teacher / T)`` --, runs the backward once
+for each (one after the other: they share the tower's workspace), and applies the cross-entropy's gradient ``a`` with its component
+along the other one, ``b``, taken out when they conflict: ``a - lam (a.b / b.b) b`` if ``a.b < 0``, else ``a``; then the same SGD step.
+``T`` = 1.0 and ``lam`` = 1.0 are what every shipped config sets.  DESIGN.md "KgCoOp / ProGrad fit" has the formulas and the
+rounding points.  Unverified, besides Dassl's defaults above: the reference's ``amp`` branch of ProGrad (prograd.py:415-424) hands
+``GradScaler.scale`` a tuple and is not mirrored.
+
 Not covered: ``nn.DataParallel`` (one process drives one GPU), class token positions other than ``end``, models whose text tower carries
-deep prompts, and the extra loss terms of KgCoOp, ProGrad and ProDA (follow-ups on this backward).
+deep prompts, and ProDA (a set of prompts with a forward of its own, not an extra term on this one).
 """
 from __future__ import annotations
 
@@ -96,6 +107,27 @@ def _check_batch(who: str, features, labels, C: int, E: int):
     return _labels(who, labels, features.shape[0], C)
 
 
+METHODS = ("coop", "kgcoop", "prograd")
+
+
+def _check_method(who: str, method: str, teacher, w: float, T: float, lam: float, C: int, E: int) -> None:
+    """The host-side checks of the method's own arguments; nothing is launched before they pass."""
+    if method not in METHODS:
+        raise ValueError(f"{who}: method={method!r} must be one of {METHODS}")
+    if method == "coop":
+        return
+    if not isinstance(teacher, torch.Tensor) or teacher.dtype != torch.float32 or tuple(teacher.shape) != (C, E):
+        raise ValueError(f"{who}: method={method!r} needs teacher, the frozen text features fp32 [C, E] = [{C}, {E}], got "
+                         f"{tuple(teacher.shape) if isinstance(teacher, torch.Tensor) else type(teacher).__name__}"
+                         f"{' ' + str(teacher.dtype) if isinstance(teacher, torch.Tensor) else ''}")
+    if not (math.isfinite(w) and w >= 0.0):
+        raise ValueError(f"{who}: w={w} (finite, >= 0)")
+    if not (math.isfinite(T) and T > 0.0):
+        raise ValueError(f"{who}: T={T} (finite, > 0)")
+    if not math.isfinite(lam):
+        raise ValueError(f"{who}: lam={lam} (finite)")
+
+
 def _dgrad(model):
     """The transposed fp16 copies of the frozen text weights (clipmi_text_dgrad), packed once per bound model and again when a text
     weight's version moves."""
@@ -158,6 +190,7 @@ class _Tower:
         self.stash = torch.empty(max(stb.value, 256), dtype=torch.uint8, device=dev)
         self.text = torch.empty(self.C, self.E, dtype=torch.float32, device=dev)
         self.d_embed = torch.empty(self.C * self.L, self.D, dtype=torch.float32, device=dev)
+        self.d_embed_kl = None    # ProGrad's second gradient stream, made on first use
         self.step_ws = None
 
     def forward(self, ctx: torch.Tensor) -> torch.Tensor:
@@ -169,16 +202,23 @@ class _Tower:
                   "clipmi_text_encoder_train")
         return self.text
 
-    def backward(self, d_text: torch.Tensor, stats: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def backward(self, d_text: torch.Tensor, stats: Optional[torch.Tensor] = None, second: bool = False) -> torch.Tensor:
+        """``second``: into ProGrad's second stream.  The stash is only read, the workspace is reused: the calls run one after the other."""
         m = self.model
+        if second and self.d_embed_kl is None:
+            self.d_embed_kl = torch.empty_like(self.d_embed)
+        out = self.d_embed_kl if second else self.d_embed
         with m._launch_lock:
-            check(lib.clipmi_text_encoder_backward(m._handle, C.byref(self.dgrad[0]), d_text.data_ptr(), self.C, self.rows, self.d_embed.data_ptr(),
+            check(lib.clipmi_text_encoder_backward(m._handle, C.byref(self.dgrad[0]), d_text.data_ptr(), self.C, self.rows, out.data_ptr(),
                                                    self.ws.data_ptr(), self.ws.numel(), self.stash.data_ptr(), self.stash.numel(),
                                                    None if stats is None else stats.data_ptr(), ops._stream()), "clipmi_text_encoder_backward")
-        return self.d_embed
+        return out
 
-    def one_call_workspace(self, B: int) -> torch.Tensor:
-        need = lib.clipmi_coop_train_step_bytes(self.model._handle, self.C, self.rows, B)
+    def one_call_workspace(self, B: int, method: str = "coop") -> torch.Tensor:
+        if method == "coop":
+            need = lib.clipmi_coop_train_step_bytes(self.model._handle, self.C, self.rows, B)
+        else:
+            need = lib.clipmi_prompt_train_step_bytes(self.model._handle, self.C, self.rows, B, ops.PROMPT_MODES[method], self.n_ctx, int(self.per_class))
         if self.step_ws is None or self.step_ws.numel() < need:
             self.step_ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.ws.device)
         return self.step_ws
@@ -189,34 +229,71 @@ def _master_ctx(ctx: torch.Tensor, dev) -> torch.Tensor:
 
 
 def context_gradient(clip_model, tokenized_prompts, ctx: torch.Tensor, features: torch.Tensor, labels, logit_scale: float = 4.6052,
-                     grad_scale: float = DEFAULT_GRAD_SCALE, seq_rows: Optional[int] = None, return_operand_stats: bool = False):
+                     grad_scale: float = DEFAULT_GRAD_SCALE, seq_rows: Optional[int] = None, return_operand_stats: bool = False,
+                     method: str = "coop", teacher: Optional[torch.Tensor] = None, w: float = 8.0, T: float = 1.0, lam: float = 1.0,
+                     return_parts: bool = False):
     """``(loss, grad)`` of ``F.cross_entropy(exp(logit_scale) * normalise(features) @ normalise(text_encoder(prompts(ctx))).T, labels)``
     with respect to ``ctx`` ([n_ctx, D] generic or [C, n_ctx, D] class-specific), on the GPU: loss fp32 [1], grad fp32 of ctx's shape.
     ``features`` fp32 [B, E] raw image features (the rows may be a column slice), ``tokenized_prompts`` [C, context_length] the ids of
     ``"X .. X name."``.  ``seq_rows``: the live token rows per prompt (None: behind the last EOT, rounded up to a multiple of 8; 0: the
     whole context).  ``return_operand_stats`` adds a dict over every fp16 dgrad-GEMM operand element: ``elements``, ``zeros``,
-    ``subnormals``, ``max`` -- the measurement behind the default ``grad_scale``."""
+    ``subnormals``, ``max`` -- the measurement behind the default ``grad_scale``.
+
+    ``method`` "kgcoop": the loss is the total ``CE + w score`` and the gradient its gradient; "prograd": the loss is ``xe`` and the
+    gradient the one ProGrad applies (module docstring; ``teacher``, ``w``, ``T``, ``lam``).  ``return_parts`` adds a dict (before the
+    operand statistics): KgCoOp ``ce``, ``score`` (fp32 [1] each); ProGrad ``xe``, ``kl``, ``grad_xe``, ``grad_kl``, ``projected``
+    (int32 [1]) and ``dots`` (float64 [3]: a.a, b.b, a.b of a = grad_xe, b = grad_kl); CoOp an empty one."""
     who = "context_gradient"
     Cn, n_ctx, per_class, last = _check_prompts(who, clip_model, tokenized_prompts, ctx)
     gs = _check_grad_scale(who, grad_scale)
     if not math.isfinite(logit_scale):
         raise ValueError(f"{who}: logit_scale={logit_scale} (finite)")
-    lab = _check_batch(who, features, labels, Cn, int(clip_model.geometry.embed_dim))
+    E = int(clip_model.geometry.embed_dim)
+    _check_method(who, method, teacher, w, T, lam, Cn, E)
+    lab = _check_batch(who, features, labels, Cn, E)
     _need_gpu(features, "features")
+    if method != "coop":
+        _need_gpu(teacher, "teacher")
     tower = _Tower(who, clip_model, tokenized_prompts, Cn, n_ctx, per_class, last, seq_rows)
     dev = features.device
     labels_d = lab if isinstance(lab, torch.Tensor) else torch.from_numpy(lab.astype(np.int64)).to(dev)
     master = _master_ctx(ctx, dev)
     text = tower.forward(master)
-    loss, d_text = ops.coop_head(features, labels_d, text, float(np.float32(math.exp(logit_scale))), gs)
+    scale = float(np.float32(math.exp(logit_scale)))
     stats = torch.zeros(4, dtype=torch.int64, device=dev) if return_operand_stats else None
-    d_embed = tower.backward(d_text, stats)
-    grad = ops.ctx_step(d_embed, Cn, n_ctx, per_class, gs)
+    parts = {}
+    if method == "coop":
+        loss, d_text = ops.coop_head(features, labels_d, text, scale, gs)
+        d_embed = tower.backward(d_text, stats)
+        grad = ops.ctx_step(d_embed, Cn, n_ctx, per_class, gs)
+    else:
+        losses, d_text, d_kl = ops.prompt_head(features, labels_d, text, scale, gs, method, teacher, w, T)
+        loss = losses[0:1]
+        d_embed = tower.backward(d_text, stats)
+        if method == "kgcoop":
+            grad = ops.ctx_step(d_embed, Cn, n_ctx, per_class, gs)
+            parts = {"ce": losses[1:2], "score": losses[2:3]}
+        else:
+            d_embed_kl = tower.backward(d_kl, stats, second=True)
+            grad, projected, dots = ops.prograd_step(d_embed, d_embed_kl, Cn, n_ctx, per_class, gs, lam)
+            parts = {"xe": losses[0:1], "kl": losses[1:2], "projected": projected, "dots": dots}
+            if return_parts:
+                parts["grad_xe"] = ops.ctx_step(d_embed, Cn, n_ctx, per_class, gs)
+                parts["grad_kl"] = ops.ctx_step(d_embed_kl, Cn, n_ctx, per_class, gs)
+    out = (loss, grad) + ((parts,) if return_parts else ())
     if not return_operand_stats:
-        return loss, grad
+        return out
     s = stats.cpu().numpy()
     top = float(np.array([int(s[3])], dtype=np.uint16).view(np.float16)[0])
-    return loss, grad, {"elements": int(s[0]), "zeros": int(s[1]), "subnormals": int(s[2]), "max": top}
+    return out + ({"elements": int(s[0]), "zeros": int(s[1]), "subnormals": int(s[2]), "max": top},)
+
+
+def text_features(clip_model, tokenized_prompts, ctx: torch.Tensor, seq_rows: Optional[int] = None) -> torch.Tensor:
+    """The raw text features fp32 [C, E] of the training forward at ``ctx``: what the loss head is given."""
+    who = "text_features"
+    Cn, n_ctx, per_class, last = _check_prompts(who, clip_model, tokenized_prompts, ctx)
+    tower = _Tower(who, clip_model, tokenized_prompts, Cn, n_ctx, per_class, last, seq_rows)
+    return tower.forward(_master_ctx(ctx, clip_model.device)).clone()
 
 
 class CoOpFitState:
@@ -225,13 +302,20 @@ class CoOpFitState:
 
     def __init__(self, clip_model, tokenized_prompts, ctx: torch.Tensor, logit_scale: float = 4.6052, momentum: float = 0.9,
                  dampening: float = 0.0, nesterov: bool = False, weight_decay: float = 5e-4, grad_scale: float = DEFAULT_GRAD_SCALE,
-                 seq_rows: Optional[int] = None):
+                 seq_rows: Optional[int] = None, method: str = "coop", teacher: Optional[torch.Tensor] = None, w: float = 8.0, T: float = 1.0,
+                 lam: float = 1.0):
         who = "CoOpFitState"
         self.C, self.n_ctx, self.per_class, last = _check_prompts(who, clip_model, tokenized_prompts, ctx)
         self.grad_scale = _check_grad_scale(who, grad_scale)
         _check_sgd(who, momentum, dampening, weight_decay, nesterov)
         if not math.isfinite(logit_scale):
             raise ValueError(f"{who}: logit_scale={logit_scale} (finite)")
+        _check_method(who, method, teacher, w, T, lam, self.C, int(clip_model.geometry.embed_dim))
+        self.method, self.w, self.T, self.lam = method, float(w), float(T), float(lam)
+        self.teacher = None
+        if method != "coop":
+            _need_gpu(teacher, "teacher")
+            self.teacher = teacher.detach().contiguous()
         self.tower = _Tower(who, clip_model, tokenized_prompts, self.C, self.n_ctx, self.per_class, last, seq_rows)
         dev = clip_model.device
         self.ctx = _master_ctx(ctx, dev)
@@ -244,8 +328,9 @@ class CoOpFitState:
         """One optimiser step on the batch ``features`` fp32 [B, E] (raw image features on the GPU) and ``labels`` [B] at the rate ``lr``:
         an fp32 tensor of one element on the device is read where it lies (``rates[k:k + 1]``); a Python number is uploaded on every call.
         A label tensor on the GPU is taken as it is -- a label outside [0, C) then makes the context NaN, it is never used as an address;
-        host labels are range-checked.  ``one_call``: the same launches through the library's one-call step (clipmi_coop_train_step).
-        Returns the batch loss, fp32 [1] on the device, when ``want_loss``."""
+        host labels are range-checked.  ``one_call``: the same launches through the library's one-call step (clipmi_coop_train_step, or
+        clipmi_prompt_train_step for KgCoOp and ProGrad).  Returns the batch loss, fp32 [1] on the device, when ``want_loss``: the
+        total for KgCoOp, ``xe`` for ProGrad."""
         t = self.tower
         lab = _check_batch("CoOpFitState.step", features, labels, self.C, t.E)
         _need_gpu(features, "features")
@@ -255,7 +340,10 @@ class CoOpFitState:
         labels_d = lab if isinstance(lab, torch.Tensor) else torch.from_numpy(lab.astype(np.int64)).to(dev)
         lr_d = ops._dev(lr, "lr", (torch.float32,)) if isinstance(lr, torch.Tensor) else torch.tensor([float(lr)], dtype=torch.float32).to(dev)
         first = self.steps == 0
-        if one_call:
+        if self.method != "coop":
+            loss = self._step_with_teacher(features, labels_d, lr_d, first, one_call)
+            loss = loss if want_loss else None
+        elif one_call:
             loss = torch.empty(1, dtype=torch.float32, device=dev) if want_loss else None
             ws = t.one_call_workspace(features.shape[0])
             m = t.model
@@ -277,6 +365,33 @@ class CoOpFitState:
         self.steps += 1
         return loss
 
+    def _step_with_teacher(self, features, labels_d, lr_d, first: bool, one_call: bool) -> torch.Tensor:
+        """KgCoOp's or ProGrad's step; returns the first of the head's losses, fp32 [1]."""
+        t, m = self.tower, self.tower.model
+        sgd = (float(self.momentum), float(self.dampening), float(self.weight_decay), int(bool(self.nesterov)))
+        if one_call:
+            losses = torch.zeros(3, dtype=torch.float32, device=features.device)
+            ws = t.one_call_workspace(features.shape[0], self.method)
+            with m._launch_lock:
+                check(lib.clipmi_prompt_train_step(m._handle, C.byref(t.dgrad[0]), t.base.data_ptr(), _DT[t.base.dtype], self.ctx.data_ptr(),
+                                                   None if self.buf is None else self.buf.data_ptr(), t.n_ctx, int(t.per_class), t.eot.data_ptr(), t.C,
+                                                   t.rows, features.data_ptr(), features.stride(0), labels_d.data_ptr(), features.shape[0], self.scale,
+                                                   self.grad_scale, ops.PROMPT_MODES[self.method], self.teacher.data_ptr(), self.w, self.T, self.lam,
+                                                   lr_d.data_ptr(), int(first), *sgd, losses.data_ptr(), None, None, None, ws.data_ptr(), ws.numel(),
+                                                   t.stash.data_ptr(), t.stash.numel(), ops._stream()), "clipmi_prompt_train_step")
+            return losses[0:1]
+        text = t.forward(self.ctx)
+        losses, d_text, d_kl = ops.prompt_head(features, labels_d, text, self.scale, self.grad_scale, self.method, self.teacher, self.w, self.T)
+        d_embed = t.backward(d_text)
+        if self.method == "kgcoop":
+            ops.ctx_step(d_embed, t.C, t.n_ctx, t.per_class, self.grad_scale, self.ctx, self.buf, lr_d, first, self.momentum, self.dampening,
+                         self.weight_decay, self.nesterov, want_grad=False)
+        else:
+            d_embed_kl = t.backward(d_kl, second=True)
+            ops.prograd_step(d_embed, d_embed_kl, t.C, t.n_ctx, t.per_class, self.grad_scale, self.lam, self.ctx, self.buf, lr_d, first, self.momentum,
+                             self.dampening, self.weight_decay, self.nesterov, want_report=False)
+        return losses[0:1]
+
 
 def init_context(clip_model, n_ctx: int = 16, n_cls: Optional[int] = None, seed: int = 0) -> torch.Tensor:
     """The reference's random initialisation (coop.py:92-99): N(0, 0.02^2), [n_ctx, D] or, with ``n_cls``, class-specific [n_cls, n_ctx, D]."""
@@ -290,7 +405,8 @@ def fit_context(features: torch.Tensor, labels, clip_model, tokenized_prompts, c
                 csc: bool = False, logit_scale: float = 4.6052, lr: float = 0.002, epochs: int = 200, batch_size: int = 32,
                 momentum: float = 0.9, dampening: float = 0.0, weight_decay: float = 5e-4, nesterov: bool = False,
                 grad_scale: float = DEFAULT_GRAD_SCALE, seq_rows: Optional[int] = None, lr_per_epoch: Optional[Sequence[float]] = None,
-                order=None, drop_last: bool = False, return_history: bool = False):
+                order=None, drop_last: bool = False, return_history: bool = False, method: str = "coop", teacher: Optional[torch.Tensor] = None,
+                w: float = 8.0, T: float = 1.0, lam: float = 1.0):
     """Train CoOp's context on cached ``features`` fp32 [N, E] (raw image features on the GPU; the rows may be a column slice) and
     ``labels`` [N], starting from ``ctx`` (not modified; None = ``init_context(clip_model, n_ctx, C if csc else None)``): ``epochs``
     passes of ``torch.optim.SGD(lr, momentum, dampening, weight_decay, nesterov)`` over batches of ``batch_size``.
@@ -300,7 +416,8 @@ def fit_context(features: torch.Tensor, labels, clip_model, tokenized_prompts, c
     epoch.  The last batch of an epoch is short unless ``drop_last`` drops it.  Labels and ``order`` are checked on the host before
     anything is launched; from the first launch on nothing synchronises until the one wait at the end.  Returns the fitted fp32 context
     on the device, or ``(ctx, per-step batch losses as a float32 numpy array)`` with ``return_history``.  The defaults are unverified
-    restatements of the reference's config and Dassl's (module docstring)."""
+    restatements of the reference's config and Dassl's (module docstring).  ``method``, ``teacher``, ``w``, ``T``, ``lam``: KgCoOp's
+    or ProGrad's step in CoOp's place (module docstring); the history then holds KgCoOp's total loss or ProGrad's ``xe``."""
     who = "fit_context"
     ids = _host_int_array(tokenized_prompts, "tokenized_prompts")
     if ctx is None:
@@ -315,6 +432,7 @@ def fit_context(features: torch.Tensor, labels, clip_model, tokenized_prompts, c
         raise ValueError(f"{who}: epochs={epochs} (>= 0), batch_size={batch_size} (>= 1)")
     _check_sgd(who, momentum, dampening, weight_decay, nesterov)
     _check_grad_scale(who, grad_scale)
+    _check_method(who, method, teacher, w, T, lam, Cn, E)
     lab = _labels(who, labels, N, Cn)
     if order is not None:
         order = _host_int_array(order, "order")
@@ -332,7 +450,8 @@ def fit_context(features: torch.Tensor, labels, clip_model, tokenized_prompts, c
         return (out, np.zeros(0, np.float32)) if return_history else out
     _need_gpu(features, "features")
     dev = features.device
-    state = CoOpFitState(clip_model, tokenized_prompts, ctx, logit_scale, momentum, dampening, nesterov, weight_decay, grad_scale, seq_rows)
+    state = CoOpFitState(clip_model, tokenized_prompts, ctx, logit_scale, momentum, dampening, nesterov, weight_decay, grad_scale, seq_rows,
+                         method, teacher, w, T, lam)
     lr_steps = torch.from_numpy(np.repeat(np.asarray(rates, np.float64), per_epoch).astype(np.float32)).to(dev)
     labels_d = torch.from_numpy(lab.astype(np.int64)).to(dev)
     order_d = None if order is None else torch.from_numpy(np.ascontiguousarray(order, dtype=np.int64)).to(dev)

@@ -964,3 +964,86 @@ def ctx_step(d_embed: torch.Tensor, n_prompts: int, n_ctx: int, per_class: bool,
                               int(bool(per_class)), float(grad_scale), pl, int(bool(first_step)), float(momentum), float(dampening),
                               float(weight_decay), int(bool(nesterov)), _stream()), "clipmi_ctx_step")
     return grad
+
+
+PROMPT_MODES = {"coop": _lib.PROMPT_COOP, "kgcoop": _lib.PROMPT_KGCOOP, "prograd": _lib.PROMPT_PROGRAD}
+
+
+def prompt_head(features: torch.Tensor, labels: torch.Tensor, text: torch.Tensor, scale: float, grad_scale: float = 1.0, method: str = "coop",
+                teacher: Optional[torch.Tensor] = None, w: float = 8.0, T: float = 1.0):
+    """The loss head of CoOp, KgCoOp or ProGrad (``method``): ``(losses fp32 [3], d_text fp32 [C, E], d_text_kl fp32 [C, E] or None)``,
+    the gradients times ``grad_scale``.  Inputs as ``coop_head``'s; ``teacher`` fp32 [C, E]: the frozen zero-shot text features (the head
+    normalises the rows).  ``losses``: [loss, 0, 0] for CoOp, [CE + w score, CE, score = 1 - mean cosine to the teacher] for KgCoOp,
+    [xe, kl, 0] for ProGrad, whose two gradients are those of xe and of kl (``T``: the distillation temperature)."""
+    if method not in PROMPT_MODES:
+        raise ValueError(f"prompt_head: method={method!r} (one of {sorted(PROMPT_MODES)})")
+    if not isinstance(features, torch.Tensor) or features.dim() != 2 or features.stride(1) != 1:
+        raise ValueError("prompt_head: features must be a [B, E] tensor with unit column stride")
+    if not features.is_cuda or features.dtype != torch.float32:
+        raise TypeError("prompt_head: features must be fp32 on the GPU")
+    labels, text = _dev(labels, "labels", (torch.int64,)), _dev(text, "text", (torch.float32,))
+    (B, E), Cn = features.shape, text.shape[0]
+    if text.dim() != 2 or text.shape[1] != E or labels.shape != (B,):
+        raise ValueError(f"prompt_head: features {tuple(features.shape)}, labels {tuple(labels.shape)}, text {tuple(text.shape)} do not agree")
+    pt = None
+    if method != "coop":
+        if teacher is None:
+            raise ValueError(f"prompt_head: method={method!r} needs the teacher")
+        teacher = _dev(teacher, "teacher", (torch.float32,))
+        if teacher.shape != text.shape:
+            raise ValueError(f"prompt_head: teacher {tuple(teacher.shape)} must be {tuple(text.shape)}")
+        pt = teacher.data_ptr()
+    mode = PROMPT_MODES[method]
+    losses = torch.zeros(3, dtype=torch.float32, device=text.device)
+    d_text = torch.empty_like(text)
+    d_kl = torch.empty_like(text) if method == "prograd" else None
+    ws = torch.empty(max(lib.clipmi_prompt_head_workspace_bytes(B, E, Cn, mode), 8), dtype=torch.uint8, device=text.device)
+    check(lib.clipmi_prompt_head(features.data_ptr(), features.stride(0), labels.data_ptr(), text.data_ptr(), B, E, Cn, float(scale),
+                                 float(grad_scale), mode, pt, float(w), float(T), losses.data_ptr(), d_text.data_ptr(), None,
+                                 None if d_kl is None else d_kl.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "clipmi_prompt_head")
+    return losses, d_text, d_kl
+
+
+def prograd_step(d_embed_xe: torch.Tensor, d_embed_kl: torch.Tensor, n_prompts: int, n_ctx: int, per_class: bool, grad_scale: float,
+                 lam: float = 1.0, ctx: Optional[torch.Tensor] = None, buf: Optional[torch.Tensor] = None, lr: Optional[torch.Tensor] = None,
+                 first_step: bool = False, momentum: float = 0.0, dampening: float = 0.0, weight_decay: float = 0.0, nesterov: bool = False,
+                 want_report: bool = True):
+    """ProGrad's projection and step from the two ``d_embed`` fp32 [C * L, D] (of xe and of kl): a and b are formed as ``ctx_step`` forms
+    its gradient; the gradient applied is ``a - lam (a.b / b.b) b`` when ``a.b < 0`` (both norms non-zero, everything finite), else ``a``;
+    with ``ctx`` torch.optim.SGD's step on it in place.  Returns ``(grad, projected int32 [1], dots float64 [3] = a.a, b.b, a.b)`` on
+    the device when ``want_report``."""
+    d_embed_xe, d_embed_kl = _dev(d_embed_xe, "d_embed_xe", (torch.float32,)), _dev(d_embed_kl, "d_embed_kl", (torch.float32,))
+    M, D = d_embed_xe.shape
+    if d_embed_kl.shape != d_embed_xe.shape:
+        raise ValueError("prograd_step: the two d_embed differ in shape")
+    if n_prompts < 1 or M % n_prompts:
+        raise ValueError(f"prograd_step: {M} rows do not split into {n_prompts} prompts")
+    shape = (n_prompts, n_ctx, D) if per_class else (n_ctx, D)
+    pc = pb = pl = None
+    if ctx is not None:
+        _in_place(ctx, torch.float32, "prograd_step: ctx must be a contiguous fp32 tensor on the GPU")
+        if tuple(ctx.shape) != shape:
+            raise ValueError(f"prograd_step: ctx {tuple(ctx.shape)} must be {shape}")
+        pc = ctx.data_ptr()
+        if buf is not None:
+            _in_place(buf, torch.float32, "prograd_step: buf must be a contiguous fp32 tensor on the GPU", numel=ctx.numel())
+            pb = buf.data_ptr()
+        lr = _dev(lr, "lr", (torch.float32,))
+        if lr.numel() != 1:
+            raise ValueError("prograd_step: lr must hold one rate")
+        pl = lr.data_ptr()
+    elif not want_report:
+        raise ValueError("prograd_step: nothing to do (no ctx and no report)")
+    dev = d_embed_xe.device
+    grad = proj = dots = None
+    if want_report:
+        grad = torch.empty(shape, dtype=torch.float32, device=dev)
+        proj = torch.empty(1, dtype=torch.int32, device=dev)
+        dots = torch.empty(3, dtype=torch.float64, device=dev)
+    ws = torch.empty(max(lib.clipmi_prograd_step_workspace_bytes(n_prompts, D, int(n_ctx), int(bool(per_class))), 256), dtype=torch.uint8, device=dev)
+    check(lib.clipmi_prograd_step(d_embed_xe.data_ptr(), d_embed_kl.data_ptr(), pc, pb, None if grad is None else grad.data_ptr(),
+                                  None if proj is None else proj.data_ptr(), None if dots is None else dots.data_ptr(), n_prompts,
+                                  M // n_prompts, D, int(n_ctx), int(bool(per_class)), float(grad_scale), float(lam), pl, int(bool(first_step)),
+                                  float(momentum), float(dampening), float(weight_decay), int(bool(nesterov)), ws.data_ptr(), ws.numel(),
+                                  _stream()), "clipmi_prograd_step")
+    return (grad, proj, dots) if want_report else None

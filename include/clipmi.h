@@ -790,6 +790,58 @@ int clipmi_coop_train_step(clipmi_model* m, const clipmi_text_dgrad* wt, const v
                            float dampening, float weight_decay, int nesterov, float* loss, float* grad_out, void* workspace,
                            size_t workspace_bytes, void* stash, size_t stash_bytes, clipmi_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------
+ * KgCoOp's and ProGrad's context trained on the device (trainers/classification/kgcoop.py:246-269, prograd.py:291-304, 371-409): CoOp's
+ * forward and backward with another loss head and, for ProGrad, a projection between the backward and the optimiser (DESIGN.md
+ * "KgCoOp / ProGrad fit").  `mode` is a plain integer: 0 CoOp, 1 KgCoOp, 2 ProGrad.  `teacher` fp32 [C, E]: the frozen zero-shot text
+ * features; the head normalises its rows itself (normalised rows pass unchanged up to rounding).  Additive exports: the ABI version stays.
+ * ---------------------------------------------------------------------------------------------------- */
+
+/* The loss head of the three methods.  Arguments as clipmi_coop_head's, and: losses fp32 [3] (required), d_text_kl fp32 [C, E] (ProGrad).
+ *   mode 0: clipmi_coop_head; losses[0] = the loss.
+ *   mode 1: loss = CE + w (1 - mean_c u_c . o_c), o_c = teacher_c / |teacher_c|; losses = [total, CE, 1 - mean_c u_c . o_c], the mean
+ *           over the classes in float64 in a fixed order.  d_text = CoOp's d_text + (-grad_scale w / C) (o_c - u_c (u_c . o_c)) / |t_c|:
+ *           with w = 0 CoOp's d_text bit for bit.  w finite, >= 0.  The reference's eps = 1e-7 guards unit vectors and is left out: a
+ *           zero teacher row makes that class's loss and gradient NaN.  Five launches.
+ *   mode 2: z_tea = scale X O^T;  losses = [xe, kl, not written], xe = mean_b CE(z_b, y_b),
+ *           kl = mean_b sum_c -softmax(z_tea / T)[b, c] log_softmax(z / T)[b, c] T^2;
+ *           dz_xe = grad_scale (softmax(z) - onehot(y)) / B -> d_text;  dz_kl = grad_scale T (softmax(z / T) - softmax(z_tea / T)) / B
+ *           -> d_text_kl, both through CoOp's projection.  T finite, > 0.  The labels reach xe only.  Six launches.
+ * d_text16 (may be NULL): d_text rounded to fp16.  A label outside [0, C) makes the cross-entropy and its gradient NaN and is never used
+ * as an address.  No float atomics, fixed summation orders: the same input gives the same bits.  workspace (8-byte aligned):
+ * clipmi_prompt_head_workspace_bytes(B, E, C, mode) bytes (0 for a bad argument).
+ * CLIPMI_ERR_ARG: a bad mode, a null pointer, a non-finite scale or grad_scale, w or T outside its range. */
+size_t clipmi_prompt_head_workspace_bytes(int B, int E, int C, int mode);
+int clipmi_prompt_head(const float* feats, int64_t ld, const int64_t* labels, const float* text, int B, int E, int C, float scale,
+                       float grad_scale, int mode, const float* teacher, float w, float T, float* losses, float* d_text, void* d_text16,
+                       float* d_text_kl, void* workspace, size_t workspace_bytes, clipmi_stream_t stream);
+
+/* ProGrad's projection and torch.optim.SGD's step (prograd.py:371-409).  d_embed_xe, d_embed_kl fp32 [C * L, D]: the two outputs of
+ * clipmi_text_encoder_backward for clipmi_prompt_head's d_text and d_text_kl.  a and b, the context's two gradients, are formed as
+ * clipmi_ctx_step forms its gradient; a.a, b.b and a.b are accumulated in float64 over a partition that depends on the context's size
+ * alone.  If a.b < 0, both norms are non-zero and the three sums are finite, the gradient is g = a - lambda (a.b / b.b) b (the scalar in
+ * float64, the element in fp32), otherwise g = a -- the reference's `dot(a / |a|, b / |b|) < 0`, which is false for a zero or NaN norm.
+ * Then clipmi_ctx_step's SGD rule on ctx.  Optional outputs (device, may be NULL): grad_out (ctx's shape) the gradient applied,
+ * projected int [1], dots float64 [3] = {a.a, b.b, a.b}.  ctx == NULL: only the outputs are written (lr may be NULL).  workspace
+ * (256-byte aligned): clipmi_prograd_step_workspace_bytes(C, D, n_ctx, per_class) bytes.  Two launches, no atomics. */
+size_t clipmi_prograd_step_workspace_bytes(int C, int D, int n_ctx, int per_class);
+int clipmi_prograd_step(const float* d_embed_xe, const float* d_embed_kl, float* ctx, float* buf, float* grad_out, int* projected,
+                        double* dots, int C, int L, int D, int n_ctx, int per_class, float grad_scale, float lambda, const float* lr,
+                        int first_step, float momentum, float dampening, float weight_decay, int nesterov, void* workspace,
+                        size_t workspace_bytes, clipmi_stream_t stream);
+
+/* One training step of CoOp, KgCoOp or ProGrad as ONE call: clipmi_text_encoder_train, clipmi_prompt_head, clipmi_text_encoder_backward
+ * (twice for ProGrad, one after the other: they share the tower's workspace and read the same stash) and clipmi_ctx_step or
+ * clipmi_prograd_step, enqueued in this order on `stream` -- the same launches, the same bits as the calls one by one.  losses fp32 [3]
+ * as clipmi_prompt_head writes them; projected and dots as clipmi_prograd_step's (ProGrad; may be NULL). */
+size_t clipmi_prompt_train_step_bytes(const clipmi_model* m, int n_prompts, int seq_rows, int B, int mode, int n_ctx, int ctx_per_class);
+int clipmi_prompt_train_step(clipmi_model* m, const clipmi_text_dgrad* wt, const void* prompts, int dtype, float* ctx, float* buf, int n_ctx,
+                             int ctx_per_class, const int32_t* eot, int n_prompts, int seq_rows, const float* feats, int64_t ld,
+                             const int64_t* labels, int B, float scale, float grad_scale, int mode, const float* teacher, float w, float T,
+                             float lambda, const float* lr, int first_step, float momentum, float dampening, float weight_decay,
+                             int nesterov, float* losses, float* grad_out, int* projected, double* dots, void* workspace,
+                             size_t workspace_bytes, void* stash, size_t stash_bytes, clipmi_stream_t stream);
+
 /* Timing aid for bench.py (the per-kernel roofline of its JSON line): the five launches of the vision tower's residual
  * block 0 -- 0 in-proj, 1 attention, 2 out-proj + residual, 3 c_fc + QuickGELU, 4 c_proj + residual (clip/model.py:181-188)
  * -- issued exactly as clipmi_encode_image issues them (LayerNorm fold, fp16 stream, tile selection) on the operands the

@@ -1,0 +1,185 @@
+"""Reference of KgCoOp's and ProGrad's training path (clip_calibration_amd/coopfit.py with ``method=``, csrc/text_backward.hip).  It does
+not import the package's kernels.
+
+(1) A no-autograd restatement, in whatever dtype it is given, of both loss heads and of ProGrad's projection rule, on top of
+``coopfit_ref``'s restatement of the tower.  (2) The truth: torch autograd through ``oracle.clip_oracle`` for KgCoOp's loss, ProGrad's two
+losses and the context gradients.  The case builders of the three test files are at the bottom."""
+import functools
+import math
+
+import torch
+
+import coopfit_ref as ref
+from oracle import clip_oracle as orc
+
+LOGIT_SCALE = ref.LOGIT_SCALE
+
+
+def unit(t):
+    return t / t.norm(dim=-1, keepdim=True)
+
+
+# ------------------------------------------------------------------------------------------------------------------ (1) the restatement
+def project_through_norm(du, text):
+    """d text of a gradient du with respect to u = text / |text|."""
+    nt = text.norm(dim=-1, keepdim=True)
+    u = text / nt
+    return (du - u * (u * du).sum(-1, keepdim=True)) / nt
+
+
+def kgcoop_head(feats, labels, text, teacher, scale, w):
+    """(total, ce, score, d total / d text): the cross-entropy head plus w (1 - mean_c u_c . o_c)."""
+    ce, d_ce, _ = ref.head(feats, labels, text, scale)
+    o = unit(teacher)
+    score = 1.0 - (unit(text) * o).sum(-1).mean()
+    d_text = d_ce + project_through_norm(-(w / text.shape[0]) * o, text)
+    return ce + w * score, ce, score, d_text
+
+
+def prograd_head(feats, labels, text, teacher, scale, T):
+    """(xe, kl, d xe / d text, d kl / d text); kl = mean_b sum_c -softmax(z_tea / T) log_softmax(z / T) T^2."""
+    xe, d_xe, _ = ref.head(feats, labels, text, scale)
+    x = unit(feats)
+    z, z_tea = scale * x @ unit(text).t(), scale * x @ unit(teacher).t()
+    p_tea = torch.softmax(z_tea / T, dim=-1)
+    kl = (-(p_tea * torch.log_softmax(z / T, dim=-1)).sum(-1) * T * T).mean()
+    dz = T * (torch.softmax(z / T, dim=-1) - p_tea) / z.shape[0]
+    return xe, kl, d_xe, project_through_norm(scale * dz.t() @ x, text)
+
+
+def project(a, b, lam):
+    """(the gradient ProGrad applies, whether it projected) from a = d xe, b = d kl: the rule of the device's step."""
+    aa, bb, ab = float((a * a).sum()), float((b * b).sum()), float((a * b).sum())
+    if all(math.isfinite(v) for v in (aa, bb, ab)) and ab < 0 and aa > 0 and bb > 0:
+        return a - lam * (ab / bb) * b, True
+    return a, False
+
+
+def cosine(a, b):
+    return float((a * b).sum() / (a.norm() * b.norm()))
+
+
+def text_and_backward(sd, ids, ctx, dtype=torch.float64):
+    """(text features [C, E], a function d_text -> d ctx) by coopfit_ref's restatement of the tower, forward with a stash."""
+    C, L = ids.shape
+    D = sd["ln_final.weight"].shape[0]
+    H, n_ctx, layers = D // 64, ctx.shape[-2], ref.n_layers(sd)
+    x = (ref.prompts_of(sd, ids, ctx, dtype) + sd["positional_embedding"].to(dtype)).reshape(C * L, D)
+    ws = [ref.block_weights(sd, i, dtype) for i in range(layers)]
+    stashes = []
+    for i in range(layers):
+        x, st = ref.block_forward(x, ws[i], C, L, H)
+        stashes.append(st)
+    eot_rows = torch.arange(C) * L + ids.argmax(dim=-1)
+    gamma, beta, proj = sd["ln_final.weight"].to(dtype), sd["ln_final.bias"].to(dtype), sd["text_projection"].to(dtype)
+    text = ref.ln_forward(x[eot_rows], gamma, beta) @ proj
+
+    def backward(d_text):
+        g = torch.zeros_like(x)
+        g[eot_rows] = ref.ln_backward(x[eot_rows], gamma, d_text @ proj.t())
+        for i in reversed(range(layers)):
+            g = ref.block_backward(g, stashes[i], ws[i], C, L, H)
+        return ref.ctx_gradient(g, C, L, n_ctx, ctx.dim() == 3)
+
+    return text, backward
+
+
+def restated(sd, ids, ctx, feats, labels, teacher, w=8.0, T=1.0, logit_scale=LOGIT_SCALE, dtype=torch.float64):
+    """What ``oracle_parts`` returns, by the restatement."""
+    text, backward = text_and_backward(sd, ids, ctx, dtype)
+    scale = math.exp(logit_scale)
+    f, t = feats.to(dtype), teacher.to(dtype)
+    total, ce, score, d_kg = kgcoop_head(f, labels, text, t, scale, w)
+    xe, kl, d_xe, d_kl = prograd_head(f, labels, text, t, scale, T)
+    return {"kgcoop": float(total), "ce": float(ce), "score": float(score), "grad_kgcoop": backward(d_kg), "xe": float(xe), "kl": float(kl),
+            "grad_xe": backward(d_xe), "grad_kl": backward(d_kl)}
+
+
+# ------------------------------------------------------------------------------------------------------------------------- (2) the truth
+def kgcoop_loss(logits, labels, text, teacher, w):
+    """kgcoop.py:261-269 without the eps of CosineSimilarity (both arguments are unit vectors)."""
+    score = 1.0 - (unit(text) * unit(teacher)).sum(-1).mean()
+    ce = torch.nn.functional.cross_entropy(logits, labels)
+    return ce + w * score, ce, score
+
+
+def prograd_losses(logits, teacher_logits, labels, T):
+    """prograd.py:296-304."""
+    xe = torch.nn.functional.cross_entropy(logits, labels)
+    p_tea = torch.softmax(teacher_logits / T, dim=-1)
+    kl = (-p_tea * torch.log_softmax(logits / T, dim=-1) * T * T).sum(1).mean()
+    return xe, kl
+
+
+def oracle_text(sd, ids, ctx, dtype=torch.float64):
+    """The oracle's text features at ``ctx`` (no gradient)."""
+    sd_c, ids_c = ref.cut(sd, ids)
+    with torch.no_grad():
+        return orc.text_encoder(sd_c, orc.coop_prompts(sd_c, ids_c, ctx.to(dtype), dtype), ids_c, dtype)
+
+
+def oracle_parts(sd, ids, ctx, feats, labels, teacher, w=8.0, T=1.0, logit_scale=LOGIT_SCALE, dtype=torch.float64, which=("kgcoop", "prograd")):
+    """Losses and context gradients by torch autograd through the oracle in ``dtype``: kgcoop, ce, score, grad_kgcoop; xe, kl, grad_xe,
+    grad_kl.  In float16 the loss functions are evaluated on the fp32 copy of the logits, as coopfit_ref.oracle_loss_grad does."""
+    sd_c, ids_c = ref.cut(sd, ids)
+    c = ctx.detach().to(dtype).clone().requires_grad_(True)
+    tf = orc.text_encoder(sd_c, orc.coop_prompts(sd_c, ids_c, c, dtype), ids_c, dtype)
+    up = (lambda t: t.float()) if dtype == torch.float16 else (lambda t: t)
+    x, o = unit(feats.to(dtype)), unit(teacher.to(dtype))
+    scale = math.exp(logit_scale)
+    logits = up(scale * x @ unit(tf).t())
+    out = {}
+    if "kgcoop" in which:
+        total, ce, score = kgcoop_loss(logits, labels, up(tf), up(o), w)
+        (g,) = torch.autograd.grad(total, c, retain_graph=True)
+        out.update(kgcoop=float(total.detach()), ce=float(ce.detach()), score=float(score.detach()), grad_kgcoop=g.detach())
+    if "prograd" in which:
+        xe, kl = prograd_losses(logits, up(scale * x @ o.t()).detach(), labels, T)
+        (ga,) = torch.autograd.grad(xe, c, retain_graph=True)
+        (gb,) = torch.autograd.grad(kl, c)
+        out.update(xe=float(xe.detach()), kl=float(kl.detach()), grad_xe=ga.detach(), grad_kl=gb.detach())
+    return out
+
+
+def yardstick_parts(sd, ids, ctx, feats, labels, teacher, w=8.0, T=1.0, logit_scale=LOGIT_SCALE, which=("kgcoop", "prograd")):
+    """The same at the reference's own precision, as coopfit_ref.yardstick_grad makes it: the oracle's autograd at float16 on the CPU or,
+    where this torch build lacks an fp16 CPU op of that backward, the fp32 oracle with weights and inputs rounded through fp16.
+    Returns (parts, how)."""
+    try:
+        got = oracle_parts(sd, ids, ctx.half(), feats.half(), labels, teacher.half(), w, T, logit_scale, torch.float16, which)
+        if all(torch.isfinite(v.float()).all() for k, v in got.items() if k.startswith("grad_")):
+            return {k: (v.double() if k.startswith("grad_") else v) for k, v in got.items()}, "fp16"
+    except RuntimeError:
+        pass
+    sd16 = {k: (v.half().float() if v.is_floating_point() else v) for k, v in sd.items()}
+    got = oracle_parts(sd16, ids, ctx.half().float(), feats.half().float(), labels, teacher.half().float(), w, T, logit_scale, torch.float32, which)
+    return {k: (v.double() if k.startswith("grad_") else v) for k, v in got.items()}, "fp32-rounded"
+
+
+# ------------------------------------------------------------------------------------------------------------------------------- cases
+def random_teacher(C, E, seed=0):
+    """A seeded random normalised teacher: the two ProGrad gradients agree on every case of this file (cos +0.44 .. +0.90 in float64)."""
+    return unit(torch.randn(C, E, generator=torch.Generator().manual_seed(900 + seed))).float()
+
+
+@functools.lru_cache(maxsize=None)
+def case(key, teacher="random", eta=0.05):
+    """coopfit_ref.make_case(*key) plus ``teacher`` fp32 [C, E].  "random": random_teacher.  "conflict": normalise(u_c + eta d_c / |d_c|),
+    u the float64 student text features at the initial context and d coopfit_ref.head's d_text there -- a teacher that sits where the
+    cross-entropy's gradient ascent would take the student, so that the two context gradients conflict."""
+    c = dict(ref.make_case(*key))
+    C, E = c["ids"].shape[0], c["feats"].shape[1]
+    if teacher == "random":
+        c["teacher"] = random_teacher(C, E)
+    else:
+        text = oracle_text(c["sd"], c["ids"], c["ctx"])
+        _, d, _ = ref.head(c["feats"].double(), c["labels"], text, math.exp(LOGIT_SCALE))
+        c["teacher"] = unit(unit(text) + eta * unit(d)).float()
+    return c
+
+
+# (key, eta): the conflict branch, cos(a, b) in float64 -0.27, -0.66, -0.13
+CONFLICT_CASES = [(("tiny", 3, 4, 8, False), 0.05), (("tiny3", 3, 16, 33, False), 0.05), (("tiny", 37, 4, 33, False), 0.2)]
+# the agreeing branch: the same three and the class-specific ones
+AGREE_CASES = [k for k, _ in CONFLICT_CASES] + [("tiny", 3, 16, 8, True), ("tiny3", 37, 4, 1, True)]
+MIN_ABS_COS = 0.1
