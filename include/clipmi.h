@@ -763,7 +763,17 @@ int clipmi_text_train_bytes(const clipmi_model* m, int n_prompts, int seq_rows, 
  * element-wise launch on that rounded value.  Per block the stash keeps the fp32 input rows, the fp32 rows before ln_2, the fp16 qkv
  * and the fp16 c_fc pre-activation (22 Dt bytes per token row and layer), plus the last block's output rows (the input of ln_final)
  * and the gathered EOT row indices.  seq_rows as clipmi_text_encoder takes it.  A hook with deep prompts: CLIPMI_ERR_ARG;
- * CLIPMI_CALL_STREAM_F16: CLIPMI_ERR_STATE.  workspace and stash 256-byte aligned. */
+ * CLIPMI_CALL_STREAM_F16: CLIPMI_ERR_STATE.  workspace and stash 256-byte aligned.
+ *
+ * Byte layout of the stash, with M = C * L token rows (L = the live rows), layers = text_layers and align256(n) = n rounded up to a
+ * multiple of 256; every slab is row-major over the M rows and starts where the one before it ends:
+ *   2 * layers + 1 fp32 slabs [M, Dt] of align256(M * Dt * 4) bytes each, in the order x_in(0), x_mid(0), x_in(1), x_mid(1), ...,
+ *       x_in(layers - 1), x_mid(layers - 1), the input of ln_final -- x_in(i): the input rows of block i (x_in(0): prompts with the
+ *       context in place plus the positional embedding), x_mid(i): its rows before ln_2; x_in(i + 1) is the output of block i;
+ *   layers fp16 slabs [M, 3 Dt] of align256(M * Dt * 6) bytes each: qkv(0), ..., qkv(layers - 1), the in-projection's output with its bias;
+ *   layers fp16 slabs [M, 4 Dt] of align256(M * Dt * 8) bytes each: c_fc's pre-activation with its bias, block 0 first;
+ *   C int32: the EOT row indices c * L + eot[c], eot clamped into [0, L - 1] (the stash reserves align256(C * 8) bytes for them).
+ * clipmi_text_train_bytes reports the sum.  The backward only reads the stash. */
 int clipmi_text_encoder_train(clipmi_model* m, const void* prompts, int dtype, const float* ctx, int n_ctx, int ctx_per_class,
                               const int32_t* eot, int n_prompts, int seq_rows, const clipmi_prompt_hook* hook, float* out,
                               void* workspace, size_t workspace_bytes, void* stash, size_t stash_bytes, unsigned flags,
@@ -775,7 +785,9 @@ int clipmi_text_encoder_train(clipmi_model* m, const void* prompts, int dtype, c
  * backward, c_fc's dgrad, ln_2's backward, out-proj's dgrad, the attention backward, in-proj's dgrad, ln_1's backward.  GEMM operands
  * fp16, accumulation and the gradient stream fp32.  operand_stats (device, NULL or 4 x uint64, zeroed by the caller): over every fp16
  * dgrad-GEMM operand element of the call {elements, exact zeros, fp16 subnormals, the largest magnitude's fp16 bits} -- the measurement
- * behind grad_scale's default (profiles/coopfit_parity.txt); it costs one launch per operand. */
+ * behind grad_scale's default (profiles/coopfit_parity.txt); it costs one launch per operand.  The counts are added into the four
+ * words and the magnitude is kept as a maximum; +0 and -0 both count as zeros, 0x0400 (2^-14) is the smallest pattern that is not a
+ * subnormal, infinity reads 0x7c00, and a NaN operand element makes the largest-magnitude statistic read 0x7fff. */
 int clipmi_text_encoder_backward(clipmi_model* m, const clipmi_text_dgrad* wt, const float* d_out, int n_prompts, int seq_rows,
                                  float* d_embed, void* workspace, size_t workspace_bytes, const void* stash, size_t stash_bytes,
                                  unsigned long long* operand_stats, clipmi_stream_t stream);
