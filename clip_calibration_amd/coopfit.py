@@ -6,8 +6,9 @@ epoch loop: every step builds the prompts ``[SOS | ctx | class tokens, EOS, padd
 image tower on the batch, normalises both sides, takes ``F.cross_entropy`` of ``exp(logit_scale)`` times the cosine and one
 ``torch.optim.SGD`` step on ``ctx``.  ``ctx`` reaches the loss only through the text tower, so a step needs the gradient of the text
 features with respect to the tower's input embeddings.  csrc/text_backward.hip computes it with the tower frozen: a training forward that
-keeps what the backward needs in a stash, the loss head, the backward (every Linear's backward is the forward's fp16 GEMM on a transposed
-copy of the weight, packed once per bound model), and the context's gradient with the optimiser's rule -- no autograd graph.  fp16 GEMM
+keeps what the backward needs in a stash and the backward (every Linear's backward is the forward's fp16 GEMM on a transposed copy of
+the weight, packed once per bound model); csrc/prompt_train.hip has the loss head and the context's gradient with the optimiser's rule
+-- no autograd graph.  fp16 GEMM
 operands, fp32 accumulation, fp32 residual and gradient streams, an fp32 master copy of ``ctx``.  DESIGN.md "CoOp fit" has the data flow.
 
 ``grad_scale``: fp16 operands flush small gradients, so the whole backward carries ``grad_scale`` times the gradient (a power of two: the
@@ -215,13 +216,15 @@ class _Tower:
         return out
 
     def one_call_workspace(self, B: int, method: str = "coop") -> torch.Tensor:
-        if method == "coop":
-            need = lib.clipmi_coop_train_step_bytes(self.model._handle, self.C, self.rows, B)
-        else:
-            need = lib.clipmi_prompt_train_step_bytes(self.model._handle, self.C, self.rows, B, ops.PROMPT_MODES[method], self.n_ctx, int(self.per_class))
+        need = lib.clipmi_prompt_train_step_bytes(self.model._handle, self.C, self.rows, B, ops.PROMPT_MODES[method], self.n_ctx, int(self.per_class))
         if self.step_ws is None or self.step_ws.numel() < need:
             self.step_ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.ws.device)
         return self.step_ws
+
+
+def _new_losses(method: str, dev) -> torch.Tensor:
+    """The head's losses fp32 [3].  CoOp's head writes the first alone and nothing here reads the others: no fill launch for it."""
+    return (torch.empty if method == "coop" else torch.zeros)(3, dtype=torch.float32, device=dev)
 
 
 def _master_ctx(ctx: torch.Tensor, dev) -> torch.Tensor:
@@ -261,25 +264,19 @@ def context_gradient(clip_model, tokenized_prompts, ctx: torch.Tensor, features:
     text = tower.forward(master)
     scale = float(np.float32(math.exp(logit_scale)))
     stats = torch.zeros(4, dtype=torch.int64, device=dev) if return_operand_stats else None
-    parts = {}
-    if method == "coop":
-        loss, d_text = ops.coop_head(features, labels_d, text, scale, gs)
-        d_embed = tower.backward(d_text, stats)
+    losses, d_text, d_kl = ops.prompt_head(features, labels_d, text, scale, gs, method, teacher, w, T, _new_losses(method, dev))
+    loss = losses[0:1]
+    d_embed = tower.backward(d_text, stats)
+    if method != "prograd":
         grad = ops.ctx_step(d_embed, Cn, n_ctx, per_class, gs)
+        parts = {"ce": losses[1:2], "score": losses[2:3]} if method == "kgcoop" else {}
     else:
-        losses, d_text, d_kl = ops.prompt_head(features, labels_d, text, scale, gs, method, teacher, w, T)
-        loss = losses[0:1]
-        d_embed = tower.backward(d_text, stats)
-        if method == "kgcoop":
-            grad = ops.ctx_step(d_embed, Cn, n_ctx, per_class, gs)
-            parts = {"ce": losses[1:2], "score": losses[2:3]}
-        else:
-            d_embed_kl = tower.backward(d_kl, stats, second=True)
-            grad, projected, dots = ops.prograd_step(d_embed, d_embed_kl, Cn, n_ctx, per_class, gs, lam)
-            parts = {"xe": losses[0:1], "kl": losses[1:2], "projected": projected, "dots": dots}
-            if return_parts:
-                parts["grad_xe"] = ops.ctx_step(d_embed, Cn, n_ctx, per_class, gs)
-                parts["grad_kl"] = ops.ctx_step(d_embed_kl, Cn, n_ctx, per_class, gs)
+        d_embed_kl = tower.backward(d_kl, stats, second=True)
+        grad, projected, dots = ops.prograd_step(d_embed, d_embed_kl, Cn, n_ctx, per_class, gs, lam)
+        parts = {"xe": losses[0:1], "kl": losses[1:2], "projected": projected, "dots": dots}
+        if return_parts:
+            parts["grad_xe"] = ops.ctx_step(d_embed, Cn, n_ctx, per_class, gs)
+            parts["grad_kl"] = ops.ctx_step(d_embed_kl, Cn, n_ctx, per_class, gs)
     out = (loss, grad) + ((parts,) if return_parts else ())
     if not return_operand_stats:
         return out
@@ -328,69 +325,42 @@ class CoOpFitState:
         """One optimiser step on the batch ``features`` fp32 [B, E] (raw image features on the GPU) and ``labels`` [B] at the rate ``lr``:
         an fp32 tensor of one element on the device is read where it lies (``rates[k:k + 1]``); a Python number is uploaded on every call.
         A label tensor on the GPU is taken as it is -- a label outside [0, C) then makes the context NaN, it is never used as an address;
-        host labels are range-checked.  ``one_call``: the same launches through the library's one-call step (clipmi_coop_train_step, or
-        clipmi_prompt_train_step for KgCoOp and ProGrad).  Returns the batch loss, fp32 [1] on the device, when ``want_loss``: the
+        host labels are range-checked.  ``one_call``: the same launches through the library's one-call step
+        (clipmi_prompt_train_step).  Returns the batch loss, fp32 [1] on the device, when ``want_loss``: the
         total for KgCoOp, ``xe`` for ProGrad."""
-        t = self.tower
-        lab = _check_batch("CoOpFitState.step", features, labels, self.C, t.E)
+        lab = _check_batch("CoOpFitState.step", features, labels, self.C, self.tower.E)
         _need_gpu(features, "features")
         if features.dtype != torch.float32 or features.stride(1) != 1:
             raise TypeError("CoOpFitState.step: features must be fp32 with unit column stride")
         dev = features.device
         labels_d = lab if isinstance(lab, torch.Tensor) else torch.from_numpy(lab.astype(np.int64)).to(dev)
         lr_d = ops._dev(lr, "lr", (torch.float32,)) if isinstance(lr, torch.Tensor) else torch.tensor([float(lr)], dtype=torch.float32).to(dev)
-        first = self.steps == 0
-        if self.method != "coop":
-            loss = self._step_with_teacher(features, labels_d, lr_d, first, one_call)
-            loss = loss if want_loss else None
-        elif one_call:
-            loss = torch.empty(1, dtype=torch.float32, device=dev) if want_loss else None
-            ws = t.one_call_workspace(features.shape[0])
-            m = t.model
-            with m._launch_lock:
-                check(lib.clipmi_coop_train_step(m._handle, C.byref(t.dgrad[0]), t.base.data_ptr(), _DT[t.base.dtype], self.ctx.data_ptr(),
-                                                 None if self.buf is None else self.buf.data_ptr(), t.n_ctx, int(t.per_class), t.eot.data_ptr(), t.C,
-                                                 t.rows, features.data_ptr(), features.stride(0), labels_d.data_ptr(), features.shape[0], self.scale,
-                                                 self.grad_scale, lr_d.data_ptr(), int(first), float(self.momentum), float(self.dampening),
-                                                 float(self.weight_decay), int(bool(self.nesterov)), None if loss is None else loss.data_ptr(), None,
-                                                 ws.data_ptr(), ws.numel(), t.stash.data_ptr(), t.stash.numel(), ops._stream()),
-                      "clipmi_coop_train_step")
-        else:
-            text = t.forward(self.ctx)
-            loss, d_text = ops.coop_head(features, labels_d, text, self.scale, self.grad_scale)
-            d_embed = t.backward(d_text)
-            ops.ctx_step(d_embed, t.C, t.n_ctx, t.per_class, self.grad_scale, self.ctx, self.buf, lr_d, first, self.momentum, self.dampening,
-                         self.weight_decay, self.nesterov, want_grad=False)
-            loss = loss if want_loss else None
-        self.steps += 1
-        return loss
-
-    def _step_with_teacher(self, features, labels_d, lr_d, first: bool, one_call: bool) -> torch.Tensor:
-        """KgCoOp's or ProGrad's step; returns the first of the head's losses, fp32 [1]."""
-        t, m = self.tower, self.tower.model
-        sgd = (float(self.momentum), float(self.dampening), float(self.weight_decay), int(bool(self.nesterov)))
+        t, m, first = self.tower, self.tower.model, self.steps == 0
+        sgd = (self.momentum, self.dampening, self.weight_decay, self.nesterov)
+        losses = _new_losses(self.method, dev)
         if one_call:
-            losses = torch.zeros(3, dtype=torch.float32, device=features.device)
             ws = t.one_call_workspace(features.shape[0], self.method)
             with m._launch_lock:
                 check(lib.clipmi_prompt_train_step(m._handle, C.byref(t.dgrad[0]), t.base.data_ptr(), _DT[t.base.dtype], self.ctx.data_ptr(),
                                                    None if self.buf is None else self.buf.data_ptr(), t.n_ctx, int(t.per_class), t.eot.data_ptr(), t.C,
                                                    t.rows, features.data_ptr(), features.stride(0), labels_d.data_ptr(), features.shape[0], self.scale,
-                                                   self.grad_scale, ops.PROMPT_MODES[self.method], self.teacher.data_ptr(), self.w, self.T, self.lam,
-                                                   lr_d.data_ptr(), int(first), *sgd, losses.data_ptr(), None, None, None, ws.data_ptr(), ws.numel(),
-                                                   t.stash.data_ptr(), t.stash.numel(), ops._stream()), "clipmi_prompt_train_step")
-            return losses[0:1]
-        text = t.forward(self.ctx)
-        losses, d_text, d_kl = ops.prompt_head(features, labels_d, text, self.scale, self.grad_scale, self.method, self.teacher, self.w, self.T)
-        d_embed = t.backward(d_text)
-        if self.method == "kgcoop":
-            ops.ctx_step(d_embed, t.C, t.n_ctx, t.per_class, self.grad_scale, self.ctx, self.buf, lr_d, first, self.momentum, self.dampening,
-                         self.weight_decay, self.nesterov, want_grad=False)
+                                                   self.grad_scale, ops.PROMPT_MODES[self.method], None if self.teacher is None else self.teacher.data_ptr(),
+                                                   self.w, self.T, self.lam, lr_d.data_ptr(), int(first), *map(float, sgd[:3]), int(bool(sgd[3])),
+                                                   losses.data_ptr(), None, None, None, ws.data_ptr(), ws.numel(), t.stash.data_ptr(), t.stash.numel(),
+                                                   ops._stream()),
+                      "clipmi_prompt_train_step")
         else:
-            d_embed_kl = t.backward(d_kl, second=True)
-            ops.prograd_step(d_embed, d_embed_kl, t.C, t.n_ctx, t.per_class, self.grad_scale, self.lam, self.ctx, self.buf, lr_d, first, self.momentum,
-                             self.dampening, self.weight_decay, self.nesterov, want_report=False)
-        return losses[0:1]
+            text = t.forward(self.ctx)
+            _, d_text, d_kl = ops.prompt_head(features, labels_d, text, self.scale, self.grad_scale, self.method, self.teacher, self.w, self.T, losses)
+            d_embed = t.backward(d_text)
+            if self.method != "prograd":
+                ops.ctx_step(d_embed, t.C, t.n_ctx, t.per_class, self.grad_scale, self.ctx, self.buf, lr_d, first, *sgd, want_grad=False)
+            else:
+                d_embed_kl = t.backward(d_kl, second=True)
+                ops.prograd_step(d_embed, d_embed_kl, t.C, t.n_ctx, t.per_class, self.grad_scale, self.lam, self.ctx, self.buf, lr_d, first, *sgd,
+                                 want_report=False)
+        self.steps += 1
+        return losses[0:1] if want_loss else None
 
 
 def init_context(clip_model, n_ctx: int = 16, n_cls: Optional[int] = None, seed: int = 0) -> torch.Tensor:

@@ -20,7 +20,7 @@
 #include <cmath>
 
 #include "common.h"
-#include "train_rules.h"   // SgdArgs, sgd_element, mean_loss_256
+#include "train_rules.h"   // SgdArgs, check_sgd, sgd_element, waves_max, xent_row, mean_loss_256
 
 namespace clipmi {
 namespace {
@@ -101,7 +101,7 @@ __global__ __launch_bounds__(ROWS_THREADS) void adapter_rows_kernel(const float*
   float* sh = sd + E;         // h = relu(p1): the first mask
   float* sdh = sh + H;        // da W2, before the first mask
   float* sparts = sdh + H;    // columns_sum's partial sums
-  float* swave = sparts + ROWS_THREADS;   // one value per wave, twice
+  float* swave = sparts + ROWS_THREADS;   // one value per wave, twice: the maximum's and the sum's
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int r = blockIdx.x;
   float* out_h = ws.h + (size_t)r * H;
@@ -149,26 +149,9 @@ __global__ __launch_bounds__(ROWS_THREADS) void adapter_rows_kernel(const float*
     if (lane == 0) z[c] = zc;
     m = fmaxf(m, zc);
   }
-  if (lane == 0) swave[wave] = m;
-  __syncthreads();            // also orders the stores to z before the loads below (workgroup scope)
-  m = swave[0];
-  for (int w = 1; w < ROWS_WAVES; ++w) m = fmaxf(m, swave[w]);
-  // S = sum_c exp(z_c - m): thread-strided, the wave tree, then the waves' sums in wave order
-  float S = 0.f;
-  for (int c = t; c < C; c += ROWS_THREADS) S += __expf(z[c] - m);
-  S = wave_sum(S);
-  if (lane == 0) swave[ROWS_WAVES + wave] = S;
-  __syncthreads();
-  S = swave[ROWS_WAVES];
-  for (int w = 1; w < ROWS_WAVES; ++w) S += swave[ROWS_WAVES + w];
-  if (t == 0) ws.loss[r] = logf(S) - (z[y] - m);
-  __syncthreads();            // z[y] has been read
+  m = waves_max<ROWS_WAVES>(m, swave);   // its barrier also orders the stores to z before the loads below (workgroup scope)
   // dz_c = (softmax_c - [c == y]) / B, in place of z
-  const float inv_rows = 1.f / (float)rows;
-  for (int c = t; c < C; c += ROWS_THREADS) {
-    const float p = __expf(z[c] - m) / S;
-    z[c] = (c == y ? p - 1.f : p) * inv_rows;
-  }
+  xent_row<ROWS_WAVES>(z, z, C, m, y, 1.f / (float)rows, swave + ROWS_WAVES, ws.loss + r);
   __syncthreads();
   // du = s dz T: the features across the threads, the classes in consecutive parts
   columns_sum(text, E, z, C, E, sparts, sd);
@@ -232,11 +215,7 @@ bool aligned(const void* p, size_t a) { return (uintptr_t)p % a == 0; }
 int check_problem(const char* who, const Problem& p, const float* lr, float momentum, float dampening, float weight_decay, int nesterov) {
   CLIPMI_REQUIRE(p.feats && p.labels && p.text && p.w1 && p.w2 && lr, CLIPMI_ERR_ARG,
                  "%s: null pointer (feats, labels, text, w1, w2 and lr are required)", who);
-  CLIPMI_REQUIRE(momentum >= 0.f && momentum < 1.f, CLIPMI_ERR_ARG, "%s: momentum=%g (in [0, 1))", who, momentum);
-  CLIPMI_REQUIRE(dampening >= 0.f && dampening < 1.f, CLIPMI_ERR_ARG, "%s: dampening=%g (in [0, 1))", who, dampening);
-  CLIPMI_REQUIRE(weight_decay >= 0.f && std::isfinite(weight_decay), CLIPMI_ERR_ARG, "%s: weight_decay=%g (finite, >= 0)", who, weight_decay);
-  CLIPMI_REQUIRE(!nesterov || (momentum > 0.f && dampening == 0.f), CLIPMI_ERR_ARG,
-                 "%s: nesterov needs a momentum and zero dampening (momentum=%g, dampening=%g)", who, momentum, dampening);
+  if (int rc = check_sgd(who, momentum, dampening, weight_decay, nesterov)) return rc;
   CLIPMI_REQUIRE(momentum == 0.f || (p.m1 && p.m2), CLIPMI_ERR_ARG, "%s: null pointer (a momentum needs the buffers m1 and m2)", who);
   CLIPMI_REQUIRE(aligned(p.feats, 4) && aligned(p.text, 4) && aligned(p.w1, 4) && aligned(p.w2, 4) && aligned(p.m1, 4) && aligned(p.m2, 4) &&
                      aligned(lr, 4) && aligned(p.labels, 8),
@@ -291,7 +270,7 @@ int clipmi_adapter_train_step(const float* feats, int64_t ld, const int64_t* lab
   const Problem p{feats, ld, labels, text, w1, w2, m1, m2, rows, E, H, C, ratio, scale};
   if (int rc = check_problem("adapter_train_step", p, lr, momentum, dampening, weight_decay, nesterov)) return rc;
   if (int rc = check_workspace("adapter_train_step", workspace, workspace_bytes, rows, p)) return rc;
-  const SgdArgs a{momentum, (float)(1.0 - (double)dampening), weight_decay, nesterov ? 1 : 0, first_step ? 1 : 0};
+  const SgdArgs a = make_sgd_args(momentum, dampening, weight_decay, nesterov, first_step);
   return launch_step(p, nullptr, 0, rows, lr, a, loss, workspace, (hipStream_t)stream);
 }
 
@@ -306,7 +285,7 @@ int clipmi_adapter_fit(const float* feats, int64_t ld, const int64_t* labels, co
   const int width = batch < n ? batch : n;   // the widest batch of the run
   if (int rc = check_workspace("adapter_fit", workspace, workspace_bytes, width, p)) return rc;
   const int per_epoch = drop_last ? n / batch : (int)(((int64_t)n + batch - 1) / batch);
-  SgdArgs a{momentum, (float)(1.0 - (double)dampening), weight_decay, nesterov ? 1 : 0, first_step ? 1 : 0};
+  SgdArgs a = make_sgd_args(momentum, dampening, weight_decay, nesterov, first_step);
   int64_t step = 0;
   for (int e = 0; e < epochs; ++e) {
     const int32_t* epoch_order = order ? order + (int64_t)e * n : nullptr;

@@ -353,9 +353,6 @@ int run_text_tail(clipmi_model* m, const TowerWs& w, int C, float* out, bool f16
   return launch_gemm(a, s);
 }
 
-// rows of a prompt the tower works on: the caller's bound on the last live token (dead-row elimination), else the whole context
-int live_rows(const clipmi_model* m, int seq_rows) { return seq_rows > 0 && seq_rows < m->g.context_length ? seq_rows : m->g.context_length; }
-
 int text_prologue(clipmi_model* m, int n_prompts, int seq_rows, const clipmi_prompt_hook* hook, void* ws, size_t ws_bytes, unsigned flags, TowerWs* w,
                   bool* folded, bool* f16res) {
   CLIPMI_REQUIRE(m, CLIPMI_ERR_ARG, "null model");

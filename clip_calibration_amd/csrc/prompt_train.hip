@@ -1,0 +1,553 @@
+// CoOp's, KgCoOp's and ProGrad's context trained on the device (reference trainers/classification/coop.py:192-222, 282-309,
+// kgcoop.py:246-269, prograd.py:291-304, 371-409): the loss heads on the raw text features, the context's gradient with torch.optim.SGD's
+// step, ProGrad's projection, and the one-call step that puts the frozen text tower's training forward and backward (text_backward.hip)
+// between them.  DESIGN.md "CoOp fit" and "KgCoOp / ProGrad fit" have the data flow and the rounding points.
+//   coop_head_*_kernel         both normalisations, logits, softmax, cross-entropy and the gradient w.r.t. the raw text features
+//   prograd_softmax_kernel,    the heads of KgCoOp (cross-entropy + w (1 - mean cosine to the frozen zero-shot features)) and ProGrad (cross-entropy
+//   kgcoop_loss_kernel         and the distillation loss against the zero-shot logits, one gradient each) on the same per-class workgroup
+//   ctx_step_kernel            the context's gradient (a fixed-order sum over the classes) and the SGD rule
+//   prograd_dots_kernel,       ProGrad's two context gradients, their three inner products in float64, the projection rule and the SGD step
+//   prograd_step_kernel
+// The cross-entropy row, the workgroup reductions and the optimiser's rules are train_rules.h's.  No float atomics and no workgroup waits
+// for another: the same inputs give the same bits.
+#include <cmath>
+
+#include "common.h"
+#include "model.h"
+#include "train_rules.h"
+
+namespace clipmi {
+namespace {
+
+constexpr int THREADS = 256;
+constexpr int WAVES = THREADS / 64;
+
+// ------------------------------------------------------------------------------------------------------------------------ the heads
+// (reference coop.py:205-222, kgcoop.py:246-269, prograd.py:291-304).  mode: 0 CoOp, 1 KgCoOp, 2 ProGrad (include/clipmi.h); the latter two
+// take a frozen teacher [C, E], the zero-shot text features, whose rows are normalised here.
+enum { MODE_COOP = 0, MODE_KGCOOP = 1, MODE_PROGRAD = 2 };
+
+// workspace of one batch: z [B, C] | dz [B, C] | loss [B] | 1/|f_b| [B] | 1/|t_c| [C], fp32
+struct HeadWs {
+  float *z, *dz, *loss, *inf, *intx;
+};
+inline size_t head_floats(int B, int C) { return 2 * (size_t)B * (size_t)C + 2 * (size_t)B + (size_t)C; }
+inline HeadWs head_carve(void* ws, int B, int C) {
+  HeadWs w;
+  w.z = static_cast<float*>(ws);
+  w.dz = w.z + (size_t)B * C;
+  w.loss = w.dz + (size_t)B * C;
+  w.inf = w.loss + B;
+  w.intx = w.inf + B;
+  return w;
+}
+
+// one wave per row of feats (rows 0 .. B), of text (rows B .. B + C) or, with a teacher, of the teacher (rows B + C .. B + 2 C): the
+// reciprocal of its L2 norm
+__global__ __launch_bounds__(THREADS) void coop_head_norm_kernel(const float* __restrict__ feats, int64_t ld, const float* __restrict__ text, int B, int E, int C,
+                                                                 HeadWs ws, const float* __restrict__ teacher, float* __restrict__ inty) {
+  const int lane = threadIdx.x & 63, r = blockIdx.x * WAVES + (threadIdx.x >> 6);
+  if (r >= B + C + (teacher ? C : 0)) return;
+  const float* row = r < B ? feats + (int64_t)r * ld : r < B + C ? text + (int64_t)(r - B) * E : teacher + (int64_t)(r - B - C) * E;
+  float s = 0.f;
+  for (int e = lane; e < E; e += 64) s = fmaf(row[e], row[e], s);
+  s = 1.f / sqrtf(wave_sum(s));
+  if (lane == 0) (r < B ? ws.inf[r] : r < B + C ? ws.intx[r - B] : inty[r - B - C]) = s;
+}
+
+// one wave per (b, c): z = scale (f_b . t_c) / (|f_b| |t_c|), lane-strided fmaf chains and the wave tree
+__global__ __launch_bounds__(THREADS) void coop_head_logits_kernel(const float* __restrict__ feats, int64_t ld, const float* __restrict__ text, int B, int E, int C,
+                                                                   float scale, HeadWs ws) {
+  const int lane = threadIdx.x & 63;
+  const int64_t item = (int64_t)blockIdx.x * WAVES + (threadIdx.x >> 6);
+  if (item >= (int64_t)B * C) return;
+  const int b = (int)(item / C), c = (int)(item % C);
+  const float* f = feats + (int64_t)b * ld;
+  const float* tx = text + (int64_t)c * E;
+  float s = 0.f;
+  for (int e = lane; e < E; e += 64) s = fmaf(f[e], tx[e], s);
+  s = wave_sum(s);
+  if (lane == 0) ws.z[item] = scale * ((s * ws.inf[b]) * ws.intx[c]);
+}
+
+// grid (B): row loss and dz = grad_scale (softmax(z) - onehot(y)) / B of one sample
+__global__ __launch_bounds__(THREADS) void coop_head_softmax_kernel(const int64_t* __restrict__ labels, int B, int C, float grad_scale, HeadWs ws) {
+#pragma clang fp contract(off)
+  __shared__ float sw[2 * WAVES];   // the maximum's, the sum's
+  const int t = threadIdx.x, r = blockIdx.x;
+  const float* z = ws.z + (size_t)r * C;
+  float* dz = ws.dz + (size_t)r * C;
+  const int64_t y = labels[r];
+  if (y < 0 || y >= C) {      // the same for every thread of the workgroup: nobody waits at a barrier below
+    for (int c = t; c < C; c += THREADS) dz[c] = NAN;
+    if (t == 0) ws.loss[r] = NAN;
+    return;
+  }
+  float m = -INFINITY;
+  for (int c = t; c < C; c += THREADS) m = fmaxf(m, z[c]);
+  m = block_max<WAVES>(m, sw);
+  xent_row<WAVES>(z, dz, C, m, y, grad_scale / (float)B, sw + WAVES, ws.loss + r);
+}
+
+// grid (C): du_c = scale sum_b dz[b, c] x_b (b ascending), q = u_c . du_c, d_text[c] = (du_c - u_c q) / |t_c|.  Workgroup 0 also averages
+// the row losses in float64.  KG (KgCoOp): du_c carries the extra term kg o_c, kg = -grad_scale w / C and o_c the normalised teacher row;
+// the projection is linear, so its image k ((o_c - u_c (u_c . o_c)) / |t_c|) is added to the cross-entropy's d_text, whose arithmetic is
+// CoOp's own (kg = -0 leaves those bits as they are).  u_c . o_c goes to cosv[c] for kgcoop_loss_kernel.
+template <bool KG>
+__global__ __launch_bounds__(THREADS) void coop_head_grad_kernel(const float* __restrict__ feats, int64_t ld, const float* __restrict__ text, int B, int E, int C,
+                                                                 float scale, HeadWs ws, float* __restrict__ d_text, half_t* __restrict__ d_text16,
+                                                                 float* __restrict__ loss_out, const float* __restrict__ teacher,
+                                                                 const float* __restrict__ inty, float* __restrict__ cosv, float kg) {
+  __shared__ float sw[2 * WAVES];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, c = blockIdx.x;
+  const float* tx = text + (int64_t)c * E;
+  const float itn = ws.intx[c];
+  float q = 0.f, uo = 0.f;
+  for (int e = t; e < E; e += THREADS) {   // pass 1: q
+    float du = 0.f;
+    for (int b = 0; b < B; ++b) du = fmaf(ws.dz[(size_t)b * C + c], feats[(int64_t)b * ld + e] * ws.inf[b], du);
+    q = fmaf(tx[e] * itn, scale * du, q);
+    if constexpr (KG) uo = fmaf(tx[e] * itn, teacher[(int64_t)c * E + e] * inty[c], uo);
+  }
+  q = wave_sum(q);               // q and, for KgCoOp, u_c . o_c in block_sum's order, under one barrier
+  if (lane == 0) sw[wave] = q;
+  if constexpr (KG) {
+    uo = wave_sum(uo);
+    if (lane == 0) sw[WAVES + wave] = uo;
+  }
+  __syncthreads();
+  q = sw[0];
+  for (int w = 1; w < WAVES; ++w) q += sw[w];
+  if constexpr (KG) {
+    uo = sw[WAVES];
+    for (int w = 1; w < WAVES; ++w) uo += sw[WAVES + w];
+    if (t == 0) cosv[c] = uo;
+  }
+  for (int e = t; e < E; e += THREADS) {   // pass 2: the same du again, then the projection
+    float du = 0.f;
+    for (int b = 0; b < B; ++b) du = fmaf(ws.dz[(size_t)b * C + c], feats[(int64_t)b * ld + e] * ws.inf[b], du);
+    float d = (scale * du - (tx[e] * itn) * q) * itn;
+    if constexpr (KG) d = fmaf(kg * itn, fmaf(-(tx[e] * itn), uo, teacher[(int64_t)c * E + e] * inty[c]), d);
+    d_text[(int64_t)c * E + e] = d;
+    if (d_text16) d_text16[(int64_t)c * E + e] = (half_t)d;
+  }
+  if (c != 0 || !loss_out) return;   // the same for every thread of the workgroup
+  mean_loss_256(ws.loss, B, loss_out);
+}
+
+// behind the CoOp head's workspace: 1/|o_c| [C] | u_c . o_c [C] | and for ProGrad z_tea [B, C] | dz_kl [B, C] | kl row loss [B], fp32
+struct TeacherWs {
+  float *inty, *cosv, *z_tea, *dz_kl, *loss_kl;
+};
+inline size_t prompt_head_floats(int B, int C, int mode) {
+  size_t n = head_floats(B, C);
+  if (mode != MODE_COOP) n += 2 * (size_t)C;
+  if (mode == MODE_PROGRAD) n += 2 * (size_t)B * (size_t)C + (size_t)B;
+  return n;
+}
+inline TeacherWs teacher_carve(void* ws, int B, int C) {
+  TeacherWs w;
+  w.inty = static_cast<float*>(ws) + head_floats(B, C);
+  w.cosv = w.inty + C;
+  w.z_tea = w.cosv + C;
+  w.dz_kl = w.z_tea + (size_t)B * C;
+  w.loss_kl = w.dz_kl + (size_t)B * C;
+  return w;
+}
+
+// grid (B), ProGrad: the cross-entropy's row loss and dz by the function coop_head_softmax_kernel forms them with, and beside them the
+// distillation term at the temperature T = 1 / inv_t: p = softmax(z / T), p_tea = softmax(z_tea / T), kl row loss = T^2 sum_c p_tea (log S - (z - m) / T),
+// dz_kl = grad_scale T (p - p_tea) / B.  The label reaches the cross-entropy only: a bad one makes that half NaN and leaves the other.
+// Student and teacher go through the same expressions: equal logits give dz_kl = 0 exactly.
+__global__ __launch_bounds__(THREADS) void prograd_softmax_kernel(const int64_t* __restrict__ labels, int B, int C, float grad_scale, float T, float inv_t,
+                                                                  HeadWs ws, TeacherWs tw) {
+#pragma clang fp contract(off)
+  __shared__ float sw[6][WAVES];   // one row per reduction: none waits for the readers of another
+  const int t = threadIdx.x, r = blockIdx.x;
+  const float* z = ws.z + (size_t)r * C;
+  const float* __restrict__ zt = tw.z_tea + (size_t)r * C;
+  float* dz = ws.dz + (size_t)r * C;
+  float* __restrict__ dzk = tw.dz_kl + (size_t)r * C;
+  const int64_t y = labels[r];
+  const bool bad = y < 0 || y >= C;      // the same for every thread of the workgroup
+  float m = -INFINITY, mt = -INFINITY;
+  for (int c = t; c < C; c += THREADS) {
+    m = fmaxf(m, z[c]);
+    mt = fmaxf(mt, zt[c]);
+  }
+  m = block_max<WAVES>(m, sw[0]);
+  mt = block_max<WAVES>(mt, sw[1]);
+  const float k = grad_scale / (float)B, kt = k * T;
+  xent_row<WAVES>(z, dz, C, m, bad ? 0 : y, k, sw[2], ws.loss + r);
+  if (bad) {                             // each thread over the elements it has just written
+    for (int c = t; c < C; c += THREADS) dz[c] = NAN;
+    if (t == 0) ws.loss[r] = NAN;
+  }
+  float Ss = 0.f, St = 0.f;
+  for (int c = t; c < C; c += THREADS) {
+    Ss += __expf((z[c] - m) * inv_t);
+    St += __expf((zt[c] - mt) * inv_t);
+  }
+  Ss = block_sum<WAVES>(Ss, sw[3]);
+  St = block_sum<WAVES>(St, sw[4]);
+  const float log_ss = logf(Ss);
+  float kl = 0.f;
+  for (int c = t; c < C; c += THREADS) {
+    const float ps = __expf((z[c] - m) * inv_t) / Ss, pt = __expf((zt[c] - mt) * inv_t) / St;
+    dzk[c] = (ps - pt) * kt;
+    kl += pt * (log_ss - (z[c] - m) * inv_t);
+  }
+  kl = block_sum<WAVES>(kl, sw[5]);
+  if (t == 0) tw.loss_kl[r] = kl * (T * T);
+}
+
+// one workgroup, KgCoOp: losses = [ce + w score, ce, score], ce the float64 mean of the row losses and score = 1 - the float64 mean of
+// u_c . o_c, both in mean_loss_256's order
+__global__ __launch_bounds__(256) void kgcoop_loss_kernel(HeadWs ws, TeacherWs tw, int B, int C, float w, float* __restrict__ losses) {
+#pragma clang fp contract(off)
+  __shared__ double sl[1][256];
+  mean_loss_256(ws.loss, B, losses + 1);
+  const double s = sum_f64_256(tw.cosv, C, sl);
+  if (threadIdx.x == 0) {
+    const float score = (float)(1.0 - s / (double)C);
+    losses[2] = score;
+    losses[0] = losses[1] + w * score;
+  }
+}
+
+// The head of every mode.  losses: [3] for KgCoOp and ProGrad; CoOp writes losses[0] alone and, where the caller allows it, takes none.
+int launch_head(const char* who, bool need_losses, const float* feats, int64_t ld, const int64_t* labels, const float* text, int B, int E, int C, float scale,
+                float grad_scale, int mode, const float* teacher, float w, float T, float* losses, float* d_text, half_t* d_text16, float* d_text_kl,
+                void* workspace, size_t workspace_bytes, hipStream_t s) {
+  CLIPMI_REQUIRE(mode == MODE_COOP || mode == MODE_KGCOOP || mode == MODE_PROGRAD, CLIPMI_ERR_ARG, "%s: bad mode %d", who, mode);
+  CLIPMI_REQUIRE(feats && labels && text && d_text && workspace && (losses || (mode == MODE_COOP && !need_losses)), CLIPMI_ERR_ARG, "%s: null pointer", who);
+  CLIPMI_REQUIRE(mode == MODE_COOP || teacher, CLIPMI_ERR_ARG, "%s: null pointer (KgCoOp and ProGrad need the teacher)", who);
+  CLIPMI_REQUIRE(mode != MODE_PROGRAD || d_text_kl, CLIPMI_ERR_ARG, "%s: null pointer (ProGrad writes two gradients)", who);
+  CLIPMI_REQUIRE(std::isfinite(scale) && std::isfinite(grad_scale), CLIPMI_ERR_ARG, "%s: scale=%g, grad_scale=%g (both finite)", who, scale, grad_scale);
+  CLIPMI_REQUIRE(mode != MODE_KGCOOP || (std::isfinite(w) && w >= 0.f), CLIPMI_ERR_ARG, "%s: w=%g (finite, >= 0)", who, w);
+  CLIPMI_REQUIRE(mode != MODE_PROGRAD || (std::isfinite(T) && T > 0.f), CLIPMI_ERR_ARG, "%s: T=%g (finite, > 0)", who, T);
+  CLIPMI_REQUIRE(B >= 1 && C >= 2 && E >= 1 && ld >= E, CLIPMI_ERR_SHAPE, "%s: B=%d C=%d E=%d ld=%lld", who, B, C, E, (long long)ld);
+  CLIPMI_REQUIRE((int64_t)B * C < (1ll << 31), CLIPMI_ERR_SHAPE, "%s: B * C too large", who);
+  CLIPMI_REQUIRE((uintptr_t)workspace % 8 == 0, CLIPMI_ERR_ARG, "%s: the workspace must be 8-byte aligned", who);
+  const size_t need = clipmi_prompt_head_workspace_bytes(B, E, C, mode);
+  CLIPMI_REQUIRE(workspace_bytes >= need, CLIPMI_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, need);
+  const HeadWs ws = head_carve(workspace, B, C);
+  const TeacherWs tw = mode == MODE_COOP ? TeacherWs{} : teacher_carve(workspace, B, C);
+  if (mode == MODE_COOP) teacher = nullptr;   // CoOp's head has none: a pointer passed anyway is not read
+  const dim3 threads(THREADS), per_bc((unsigned)(((int64_t)B * C + WAVES - 1) / WAVES)), per_c((unsigned)C);
+  const float *no_tea = nullptr, *no_inty = nullptr;
+  float* none = nullptr;
+  hipLaunchKernelGGL(coop_head_norm_kernel, dim3((unsigned)((B + (teacher ? 2 : 1) * C + WAVES - 1) / WAVES)), threads, 0, s, feats, ld, text, B, E, C, ws,
+                     teacher, tw.inty);
+  if (int rc = check_launch("coop_head_norm_kernel")) return rc;
+  hipLaunchKernelGGL(coop_head_logits_kernel, per_bc, threads, 0, s, feats, ld, text, B, E, C, scale, ws);
+  if (int rc = check_launch("coop_head_logits_kernel")) return rc;
+  if (mode != MODE_PROGRAD) {
+    hipLaunchKernelGGL(coop_head_softmax_kernel, dim3((unsigned)B), threads, 0, s, labels, B, C, grad_scale, ws);
+    if (int rc = check_launch("coop_head_softmax_kernel")) return rc;
+    if (mode == MODE_COOP) {
+      hipLaunchKernelGGL(coop_head_grad_kernel<false>, per_c, threads, 0, s, feats, ld, text, B, E, C, scale, ws, d_text, d_text16, losses, no_tea, no_inty,
+                         none, 0.f);
+      return check_launch("coop_head_grad_kernel");
+    }
+    hipLaunchKernelGGL(coop_head_grad_kernel<true>, per_c, threads, 0, s, feats, ld, text, B, E, C, scale, ws, d_text, d_text16, none, teacher,
+                       (const float*)tw.inty, tw.cosv, -(grad_scale * w / (float)C));
+    if (int rc = check_launch("coop_head_grad_kernel")) return rc;
+    hipLaunchKernelGGL(kgcoop_loss_kernel, dim3(1), dim3(256), 0, s, ws, tw, B, C, w, losses);
+    return check_launch("kgcoop_loss_kernel");
+  }
+  HeadWs wt = ws, wk = ws;   // the teacher's logits with the teacher's norms; the distillation term's dz and row losses
+  wt.z = tw.z_tea;
+  wt.intx = tw.inty;
+  wk.dz = tw.dz_kl;
+  wk.loss = tw.loss_kl;
+  hipLaunchKernelGGL(coop_head_logits_kernel, per_bc, threads, 0, s, feats, ld, teacher, B, E, C, scale, wt);
+  if (int rc = check_launch("coop_head_logits_kernel")) return rc;
+  hipLaunchKernelGGL(prograd_softmax_kernel, dim3((unsigned)B), threads, 0, s, labels, B, C, grad_scale, T, 1.f / T, ws, tw);
+  if (int rc = check_launch("prograd_softmax_kernel")) return rc;
+  hipLaunchKernelGGL(coop_head_grad_kernel<false>, per_c, threads, 0, s, feats, ld, text, B, E, C, scale, ws, d_text, d_text16, losses, no_tea, no_inty, none,
+                     0.f);
+  if (int rc = check_launch("coop_head_grad_kernel")) return rc;
+  hipLaunchKernelGGL(coop_head_grad_kernel<false>, per_c, threads, 0, s, feats, ld, text, B, E, C, scale, wk, d_text_kl, (half_t*)nullptr, losses + 1, no_tea,
+                     no_inty, none, 0.f);
+  return check_launch("coop_head_grad_kernel");
+}
+
+// --------------------------------------------------------------------------------------------------------------------- context step
+// one thread per element of ctx: the classes' rows added in ascending order (generic context), 1 / grad_scale, torch.optim.SGD's rule as
+// torch's GPU kernels round it (sgd_element_fma, train_rules.h)
+__device__ __forceinline__ float ctx_grad_element(const float* __restrict__ d_embed, int64_t idx, int C, int L, int D, int n_ctx, int per_class,
+                                                  float inv_scale) {
+  const int64_t per = (int64_t)n_ctx * D;
+  const int d = (int)(idx % D), j = (int)((idx / D) % n_ctx);
+  float g = 0.f;
+  if (per_class) {
+    const int64_t c = idx / per;
+    g = d_embed[((c * L) + 1 + j) * D + d];
+  } else {
+    for (int64_t c = 0; c < C; ++c) g += d_embed[((c * L) + 1 + j) * D + d];
+  }
+  return g * inv_scale;
+}
+
+__global__ __launch_bounds__(THREADS) void ctx_step_kernel(const float* __restrict__ d_embed, float* __restrict__ ctx, float* __restrict__ buf,
+                                                           float* __restrict__ grad_out, int C, int L, int D, int n_ctx, int per_class, float inv_scale,
+                                                           const float* __restrict__ lr, SgdArgs sgd) {
+  const int64_t idx = (int64_t)blockIdx.x * THREADS + threadIdx.x;
+  const int64_t per = (int64_t)n_ctx * D, total = per_class ? per * C : per;
+  if (idx >= total) return;
+  const float g = ctx_grad_element(d_embed, idx, C, L, D, n_ctx, per_class, inv_scale);
+  if (grad_out) grad_out[idx] = g;
+  if (ctx) sgd_element_fma(ctx, buf, idx, g, *lr, sgd);
+}
+
+// what clipmi_ctx_step and clipmi_prograd_step ask of the context and the optimiser alike; *total: the elements of ctx
+int check_ctx_step(const char* who, const float* ctx, const float* buf, const float* lr, int C, int L, int D, int n_ctx, int per_class, float grad_scale,
+                   float momentum, float dampening, float weight_decay, int nesterov, int64_t* total) {
+  CLIPMI_REQUIRE(!ctx || lr, CLIPMI_ERR_ARG, "%s: null pointer (a step needs lr)", who);
+  CLIPMI_REQUIRE(C >= 1 && D >= 1 && n_ctx >= 1 && 1 + n_ctx <= L, CLIPMI_ERR_SHAPE, "%s: C=%d L=%d D=%d n_ctx=%d", who, C, L, D, n_ctx);
+  CLIPMI_REQUIRE(std::isfinite(grad_scale) && grad_scale > 0.f, CLIPMI_ERR_ARG, "%s: grad_scale=%g (finite, > 0)", who, grad_scale);
+  if (int rc = check_sgd(who, momentum, dampening, weight_decay, nesterov)) return rc;
+  CLIPMI_REQUIRE(!ctx || momentum == 0.f || buf, CLIPMI_ERR_ARG, "%s: null pointer (a momentum needs the buffer)", who);
+  *total = (int64_t)n_ctx * D * (per_class ? C : 1);
+  CLIPMI_REQUIRE(*total < (1ll << 31) * THREADS, CLIPMI_ERR_SHAPE, "%s: context too large", who);
+  return CLIPMI_OK;
+}
+
+int launch_ctx_step(const float* d_embed, float* ctx, float* buf, float* grad_out, int C, int L, int D, int n_ctx, int per_class, float grad_scale,
+                    const float* lr, int first_step, float momentum, float dampening, float weight_decay, int nesterov, hipStream_t s) {
+  CLIPMI_REQUIRE(d_embed && (ctx || grad_out), CLIPMI_ERR_ARG, "ctx_step: null pointer (d_embed and one of ctx, grad_out are required)");
+  int64_t total;
+  if (int rc = check_ctx_step("ctx_step", ctx, buf, lr, C, L, D, n_ctx, per_class, grad_scale, momentum, dampening, weight_decay, nesterov, &total)) return rc;
+  hipLaunchKernelGGL(ctx_step_kernel, dim3((unsigned)((total + THREADS - 1) / THREADS)), dim3(THREADS), 0, s, d_embed, ctx, buf, grad_out, C, L, D, n_ctx,
+                     per_class ? 1 : 0, 1.f / grad_scale, lr, make_sgd_args(momentum, dampening, weight_decay, nesterov, first_step));
+  return check_launch("ctx_step_kernel");
+}
+
+// ------------------------------------------------------------------------------------------------------------------ ProGrad's step
+// (reference prograd.py:371-409).  a and b are the context gradients of the cross-entropy and of the distillation loss, each formed as
+// ctx_step_kernel forms its gradient.  Two launches: the first keeps a and b and writes every workgroup's partial sums of a.a, b.b and a.b
+// in float64 (a grid of at most DOT_BLOCKS workgroups, a function of the context's size alone); the second adds the partials in a fixed
+// order in every workgroup, decides, and steps.  The reference compares dot(a / |a|, b / |b|) with 0: that is a.b < 0 unless a norm is
+// zero or something is not finite, where the reference's comparison is false and the plain a is applied.
+constexpr int DOT_BLOCKS = 256;
+
+// workspace: partial sums [3, DOT_BLOCKS] float64 | a [total] | b [total] fp32
+struct ProgradWs {
+  double* part;
+  float *a, *b;
+};
+inline size_t prograd_step_bytes(int64_t total) { return align256(3 * DOT_BLOCKS * sizeof(double)) + 2 * align256((size_t)total * 4); }
+inline ProgradWs prograd_carve(void* ws, int64_t total) {
+  ProgradWs w;
+  char* p = static_cast<char*>(ws);
+  w.part = reinterpret_cast<double*>(p);
+  w.a = reinterpret_cast<float*>(p + align256(3 * DOT_BLOCKS * sizeof(double)));
+  w.b = reinterpret_cast<float*>(p + align256(3 * DOT_BLOCKS * sizeof(double)) + align256((size_t)total * 4));
+  return w;
+}
+
+__global__ __launch_bounds__(256) void prograd_dots_kernel(const float* __restrict__ d_embed_a, const float* __restrict__ d_embed_b, int C, int L, int D,
+                                                           int n_ctx, int per_class, float inv_scale, int64_t total, ProgradWs w) {
+  __shared__ double sl[3][256];
+  double d[3] = {0.0, 0.0, 0.0};   // a.a, b.b, a.b
+  for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * 256) {
+    const float a = ctx_grad_element(d_embed_a, idx, C, L, D, n_ctx, per_class, inv_scale);
+    const float b = ctx_grad_element(d_embed_b, idx, C, L, D, n_ctx, per_class, inv_scale);
+    w.a[idx] = a;
+    w.b[idx] = b;
+    d[0] += (double)a * (double)a;
+    d[1] += (double)b * (double)b;
+    d[2] += (double)a * (double)b;
+  }
+  block_sum_f64(d, sl);
+  if (threadIdx.x == 0)
+    for (int i = 0; i < 3; ++i) w.part[i * DOT_BLOCKS + blockIdx.x] = d[i];
+}
+
+// one thread per element of ctx; n_part: the first launch's grid.  g = a - lambda (a.b / b.b) b when a.b < 0, else a; then the SGD rule
+__global__ __launch_bounds__(256) void prograd_step_kernel(ProgradWs w, int n_part, float lambda, float* __restrict__ ctx, float* __restrict__ buf,
+                                                           float* __restrict__ grad_out, int* __restrict__ projected, double* __restrict__ dots,
+                                                           int64_t total, const float* __restrict__ lr, SgdArgs sgd) {
+#pragma clang fp contract(off)
+  __shared__ double sl[3][256];
+  const int t = threadIdx.x;
+  double d[3];
+  for (int i = 0; i < 3; ++i) d[i] = t < n_part ? w.part[i * DOT_BLOCKS + t] : 0.0;
+  block_sum_f64(d, sl);
+  const double aa = d[0], bb = d[1], ab = d[2];
+  const bool finite = isfinite(aa) && isfinite(bb) && isfinite(ab);
+  const bool project = finite && ab < 0.0 && aa > 0.0 && bb > 0.0;
+  if (blockIdx.x == 0 && t == 0) {
+    if (projected) *projected = project ? 1 : 0;
+    if (dots) { dots[0] = aa; dots[1] = bb; dots[2] = ab; }
+  }
+  const int64_t idx = (int64_t)blockIdx.x * 256 + t;
+  if (idx >= total) return;
+  float g = w.a[idx];
+  if (project) {
+    const float k = (float)((double)lambda * (ab / bb));
+    g = g - k * w.b[idx];
+  }
+  if (grad_out) grad_out[idx] = g;
+  if (ctx) sgd_element_fma(ctx, buf, idx, g, *lr, sgd);
+}
+
+int launch_prograd_step(const float* d_embed_xe, const float* d_embed_kl, float* ctx, float* buf, float* grad_out, int* projected, double* dots, int C, int L,
+                        int D, int n_ctx, int per_class, float grad_scale, float lambda, const float* lr, int first_step, float momentum, float dampening,
+                        float weight_decay, int nesterov, void* workspace, size_t workspace_bytes, hipStream_t s) {
+  CLIPMI_REQUIRE(d_embed_xe && d_embed_kl && workspace, CLIPMI_ERR_ARG, "prograd_step: null pointer (both d_embed and the workspace are required)");
+  CLIPMI_REQUIRE(ctx || grad_out || projected || dots, CLIPMI_ERR_ARG, "prograd_step: null pointer (nothing to write)");
+  CLIPMI_REQUIRE(std::isfinite(lambda), CLIPMI_ERR_ARG, "prograd_step: lambda=%g (finite)", lambda);
+  int64_t total;
+  if (int rc = check_ctx_step("prograd_step", ctx, buf, lr, C, L, D, n_ctx, per_class, grad_scale, momentum, dampening, weight_decay, nesterov, &total))
+    return rc;
+  CLIPMI_REQUIRE((uintptr_t)workspace % 256 == 0, CLIPMI_ERR_ARG, "prograd_step: the workspace must be 256-byte aligned");
+  CLIPMI_REQUIRE(workspace_bytes >= prograd_step_bytes(total), CLIPMI_ERR_WORKSPACE, "prograd_step: workspace of %zu bytes, %zu needed", workspace_bytes,
+                 prograd_step_bytes(total));
+  const ProgradWs w = prograd_carve(workspace, total);
+  const int64_t blocks = (total + 255) / 256;
+  const int n_part = (int)(blocks < DOT_BLOCKS ? blocks : DOT_BLOCKS);
+  hipLaunchKernelGGL(prograd_dots_kernel, dim3((unsigned)n_part), dim3(256), 0, s, d_embed_xe, d_embed_kl, C, L, D, n_ctx, per_class ? 1 : 0, 1.f / grad_scale,
+                     total, w);
+  if (int rc = check_launch("prograd_dots_kernel")) return rc;
+  hipLaunchKernelGGL(prograd_step_kernel, dim3((unsigned)blocks), dim3(256), 0, s, w, n_part, lambda, ctx, buf, grad_out, projected, dots, total, lr,
+                     make_sgd_args(momentum, dampening, weight_decay, nesterov, first_step));
+  return check_launch("prograd_step_kernel");
+}
+
+// ------------------------------------------------------------------------------------------------------------------ the one-call step
+// The tower's training forward, the head, the backward (twice for ProGrad: the stash is read-only in it and the tower's workspace is reused, so
+// the second follows the first on the stream) and the step.  workspace: the tower's workspace | text features [C, E] | their gradient
+// [C, E] | d_embed [M, D] | the head's workspace and, for ProGrad, | the second gradient [C, E] | the second d_embed [M, D] |
+// clipmi_prograd_step's workspace.  need: what the calling symbol's sizing function reports.
+int train_step(const char* who, bool need_losses, size_t need, clipmi_model* m, const clipmi_text_dgrad* wt, const void* prompts, int dtype, float* ctx,
+               float* buf, int n_ctx, int per_class, const int32_t* eot, int C, int seq_rows, const float* feats, int64_t ld, const int64_t* labels, int B,
+               float scale, float grad_scale, int mode, const float* teacher, float w, float T, float lambda, const float* lr, int first_step, float momentum,
+               float dampening, float weight_decay, int nesterov, float* losses, float* grad_out, int* projected, double* dots, void* workspace,
+               size_t workspace_bytes, void* stash, size_t stash_bytes, hipStream_t s) {
+  CLIPMI_REQUIRE(m, CLIPMI_ERR_ARG, "%s: null model", who);
+  CLIPMI_REQUIRE(mode == MODE_COOP || mode == MODE_KGCOOP || mode == MODE_PROGRAD, CLIPMI_ERR_ARG, "%s: bad mode %d", who, mode);
+  CLIPMI_REQUIRE(C >= 2 && B >= 1, CLIPMI_ERR_SHAPE, "%s: n_prompts=%d (>= 2), B=%d (>= 1)", who, C, B);
+  CLIPMI_REQUIRE(ctx && lr && (losses || !need_losses), CLIPMI_ERR_ARG, "%s: null pointer (ctx and lr%s are required)", who, need_losses ? " and losses" : "");
+  CLIPMI_REQUIRE(need > 0 && workspace_bytes >= need, CLIPMI_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, need);
+  size_t tower = 0;
+  clipmi_text_train_bytes(m, C, seq_rows, &tower, nullptr);
+  if (int rc = check_train_call(who, m, C, workspace, tower, stash, stash_bytes, seq_rows)) return rc;
+  if (int rc = check_train_inputs(who, m, prompts, dtype, ctx, n_ctx, eot, seq_rows, nullptr, 0)) return rc;
+  if (int rc = check_dgrad(who, m, wt)) return rc;
+  const int L = live_rows(m, seq_rows), D = m->g.text_width, E = m->g.embed_dim;
+  CLIPMI_REQUIRE(L <= AB_MAX_L, CLIPMI_ERR_SHAPE, "%s: %d token rows per prompt (at most %d)", who, L, AB_MAX_L);
+  const size_t head_bytes = clipmi_prompt_head_workspace_bytes(B, E, C, mode);
+  size_t step_bytes = 0;
+  Carver c(static_cast<char*>(workspace) + tower);
+  float* text = c.take<float>((size_t)C * E * 4);
+  float* d_text = c.take<float>((size_t)C * E * 4);
+  float* d_embed = c.take<float>((size_t)C * L * D * 4);
+  void* head_ws = c.take<char>(head_bytes);
+  float *d_text_kl = nullptr, *d_embed_kl = nullptr;
+  void* step_ws = nullptr;
+  if (mode == MODE_PROGRAD) {
+    d_text_kl = c.take<float>((size_t)C * E * 4);
+    d_embed_kl = c.take<float>((size_t)C * L * D * 4);
+    step_bytes = clipmi_prograd_step_workspace_bytes(C, D, n_ctx, per_class);
+    step_ws = c.take<char>(step_bytes);
+  }
+  if (int rc = run_train_forward(m, prompts, dtype, ctx, n_ctx, per_class, eot, C, seq_rows, text, workspace, stash, s)) return rc;
+  if (int rc = launch_head(who, need_losses, feats, ld, labels, text, B, E, C, scale, grad_scale, mode, teacher, w, T, losses, d_text, nullptr, d_text_kl, head_ws,
+                           head_bytes, s))
+    return rc;
+  if (int rc = run_backward(m, wt, d_text, C, seq_rows, d_embed, workspace, stash, nullptr, s)) return rc;
+  if (mode != MODE_PROGRAD)
+    return launch_ctx_step(d_embed, ctx, buf, grad_out, C, L, D, n_ctx, per_class, grad_scale, lr, first_step, momentum, dampening, weight_decay, nesterov, s);
+  if (int rc = run_backward(m, wt, d_text_kl, C, seq_rows, d_embed_kl, workspace, stash, nullptr, s)) return rc;
+  return launch_prograd_step(d_embed, d_embed_kl, ctx, buf, grad_out, projected, dots, C, L, D, n_ctx, per_class, grad_scale, lambda, lr, first_step, momentum,
+                             dampening, weight_decay, nesterov, step_ws, step_bytes, s);
+}
+
+}  // namespace
+}  // namespace clipmi
+
+using namespace clipmi;
+
+extern "C" {
+
+size_t clipmi_prompt_head_workspace_bytes(int B, int E, int C, int mode) {
+  if (B < 1 || E < 1 || C < 2 || mode < MODE_COOP || mode > MODE_PROGRAD) return 0;
+  return align256(prompt_head_floats(B, C, mode) * sizeof(float));
+}
+
+int clipmi_prompt_head(const float* feats, int64_t ld, const int64_t* labels, const float* text, int B, int E, int C, float scale, float grad_scale,
+                       int mode, const float* teacher, float w, float T, float* losses, float* d_text, void* d_text16, float* d_text_kl,
+                       void* workspace, size_t workspace_bytes, clipmi_stream_t stream) {
+  return launch_head("prompt_head", true, feats, ld, labels, text, B, E, C, scale, grad_scale, mode, teacher, w, T, losses, d_text,
+                     static_cast<half_t*>(d_text16), d_text_kl, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+// CoOp's own symbols: mode 0 of the above, except that the loss may be NULL
+size_t clipmi_coop_head_workspace_bytes(int B, int E, int C) { return clipmi_prompt_head_workspace_bytes(B, E, C, MODE_COOP); }
+
+int clipmi_coop_head(const float* feats, int64_t ld, const int64_t* labels, const float* text, int B, int E, int C, float scale, float grad_scale,
+                     float* loss, float* d_text, void* d_text16, void* workspace, size_t workspace_bytes, clipmi_stream_t stream) {
+  return launch_head("coop_head", false, feats, ld, labels, text, B, E, C, scale, grad_scale, MODE_COOP, nullptr, 0.f, 0.f, loss, d_text,
+                     static_cast<half_t*>(d_text16), nullptr, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int clipmi_ctx_step(const float* d_embed, float* ctx, float* buf, float* grad_out, int C, int L, int D, int n_ctx, int per_class, float grad_scale,
+                    const float* lr, int first_step, float momentum, float dampening, float weight_decay, int nesterov, clipmi_stream_t stream) {
+  return launch_ctx_step(d_embed, ctx, buf, grad_out, C, L, D, n_ctx, per_class, grad_scale, lr, first_step, momentum, dampening, weight_decay, nesterov,
+                         (hipStream_t)stream);
+}
+
+size_t clipmi_prograd_step_workspace_bytes(int C, int D, int n_ctx, int per_class) {
+  if (C < 1 || D < 1 || n_ctx < 1) return 0;
+  return prograd_step_bytes((int64_t)n_ctx * D * (per_class ? C : 1));
+}
+
+int clipmi_prograd_step(const float* d_embed_xe, const float* d_embed_kl, float* ctx, float* buf, float* grad_out, int* projected, double* dots, int C,
+                        int L, int D, int n_ctx, int per_class, float grad_scale, float lambda, const float* lr, int first_step, float momentum,
+                        float dampening, float weight_decay, int nesterov, void* workspace, size_t workspace_bytes, clipmi_stream_t stream) {
+  return launch_prograd_step(d_embed_xe, d_embed_kl, ctx, buf, grad_out, projected, dots, C, L, D, n_ctx, per_class, grad_scale, lambda, lr, first_step,
+                             momentum, dampening, weight_decay, nesterov, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+size_t clipmi_prompt_train_step_bytes(const clipmi_model* m, int n_prompts, int seq_rows, int B, int mode, int n_ctx, int ctx_per_class) {
+  size_t ws = 0;
+  if (!m || n_prompts < 2 || B < 1 || n_ctx < 1 || mode < MODE_COOP || mode > MODE_PROGRAD ||
+      clipmi_text_train_bytes(m, n_prompts, seq_rows, &ws, nullptr) != CLIPMI_OK)
+    return 0;
+  const size_t feat = align256((size_t)n_prompts * m->g.embed_dim * 4);
+  const size_t embed = align256((size_t)n_prompts * live_rows(m, seq_rows) * m->g.text_width * 4);
+  size_t n = ws + 2 * feat + embed + clipmi_prompt_head_workspace_bytes(B, m->g.embed_dim, n_prompts, mode);
+  if (mode == MODE_PROGRAD) n += feat + embed + clipmi_prograd_step_workspace_bytes(n_prompts, m->g.text_width, n_ctx, ctx_per_class);
+  return n;
+}
+
+int clipmi_prompt_train_step(clipmi_model* m, const clipmi_text_dgrad* wt, const void* prompts, int dtype, float* ctx, float* buf, int n_ctx,
+                             int ctx_per_class, const int32_t* eot, int n_prompts, int seq_rows, const float* feats, int64_t ld, const int64_t* labels,
+                             int B, float scale, float grad_scale, int mode, const float* teacher, float w, float T, float lambda, const float* lr,
+                             int first_step, float momentum, float dampening, float weight_decay, int nesterov, float* losses, float* grad_out,
+                             int* projected, double* dots, void* workspace, size_t workspace_bytes, void* stash, size_t stash_bytes,
+                             clipmi_stream_t stream) {
+  return train_step("prompt_train_step", true, clipmi_prompt_train_step_bytes(m, n_prompts, seq_rows, B, mode, n_ctx, ctx_per_class), m, wt, prompts, dtype, ctx,
+                    buf, n_ctx, ctx_per_class, eot, n_prompts, seq_rows, feats, ld, labels, B, scale, grad_scale, mode, teacher, w, T, lambda, lr, first_step,
+                    momentum, dampening, weight_decay, nesterov, losses, grad_out, projected, dots, workspace, workspace_bytes, stash, stash_bytes,
+                    (hipStream_t)stream);
+}
+
+// CoOp's own symbols: mode 0 of the above (whose size does not depend on the context), except that the loss may be NULL
+size_t clipmi_coop_train_step_bytes(const clipmi_model* m, int n_prompts, int seq_rows, int B) {
+  return clipmi_prompt_train_step_bytes(m, n_prompts, seq_rows, B, MODE_COOP, 1, 0);
+}
+
+int clipmi_coop_train_step(clipmi_model* m, const clipmi_text_dgrad* wt, const void* prompts, int dtype, float* ctx, float* buf, int n_ctx,
+                           int ctx_per_class, const int32_t* eot, int n_prompts, int seq_rows, const float* feats, int64_t ld, const int64_t* labels, int B,
+                           float scale, float grad_scale, const float* lr, int first_step, float momentum, float dampening, float weight_decay,
+                           int nesterov, float* loss, float* grad_out, void* workspace, size_t workspace_bytes, void* stash, size_t stash_bytes,
+                           clipmi_stream_t stream) {
+  return train_step("coop_train_step", false, clipmi_coop_train_step_bytes(m, n_prompts, seq_rows, B), m, wt, prompts, dtype, ctx, buf, n_ctx, ctx_per_class, eot,
+                    n_prompts, seq_rows, feats, ld, labels, B, scale, grad_scale, MODE_COOP, nullptr, 0.f, 0.f, 0.f, lr, first_step, momentum, dampening,
+                    weight_decay, nesterov, loss, grad_out, nullptr, nullptr, workspace, workspace_bytes, stash, stash_bytes, (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -160,11 +160,11 @@ __global__ __launch_bounds__(THREADS) void taskres_logits_kernel(Batch bt, const
 // grid (rows): row loss and dz = (softmax(z) - onehot(y)) / B of one sample
 __global__ __launch_bounds__(THREADS) void taskres_softmax_kernel(Batch bt, int C, Workspace ws) {
 #pragma clang fp contract(off)
-  __shared__ float swave[2 * THREADS / 64];
   constexpr int WAVES = THREADS / 64;
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, r = blockIdx.x;
-  const float* __restrict__ z = ws.z + (size_t)r * C;
-  float* __restrict__ dz = ws.dz + (size_t)r * C;
+  __shared__ float swave[2 * WAVES];   // the maximum's, the sum's
+  const int t = threadIdx.x, r = blockIdx.x;
+  const float* z = ws.z + (size_t)r * C;
+  float* dz = ws.dz + (size_t)r * C;
   const int i = sample_of(bt, r);
   const int64_t y = i >= 0 ? bt.labels[i] : -1;
   if (y < 0 || y >= C) {      // the same for every thread of the workgroup: nobody waits at a barrier below
@@ -174,25 +174,8 @@ __global__ __launch_bounds__(THREADS) void taskres_softmax_kernel(Batch bt, int 
   }
   float m = -INFINITY;
   for (int c = t; c < C; c += THREADS) m = fmaxf(m, z[c]);
-  m = wave_max(m);
-  if (lane == 0) swave[wave] = m;
-  __syncthreads();
-  m = swave[0];
-  for (int w = 1; w < WAVES; ++w) m = fmaxf(m, swave[w]);
-  // S = sum_c exp(z_c - m): thread-strided, the wave tree, then the waves' sums in wave order
-  float S = 0.f;
-  for (int c = t; c < C; c += THREADS) S += __expf(z[c] - m);
-  S = wave_sum(S);
-  if (lane == 0) swave[WAVES + wave] = S;
-  __syncthreads();
-  S = swave[WAVES];
-  for (int w = 1; w < WAVES; ++w) S += swave[WAVES + w];
-  if (t == 0) ws.loss[r] = logf(S) - (z[y] - m);
-  const float inv_rows = 1.f / (float)bt.rows;
-  for (int c = t; c < C; c += THREADS) {
-    const float p = __expf(z[c] - m) / S;
-    dz[c] = (c == y ? p - 1.f : p) * inv_rows;
-  }
+  m = block_max<WAVES>(m, swave);
+  xent_row<WAVES>(z, dz, C, m, y, 1.f / (float)bt.rows, swave + WAVES, ws.loss + r);
 }
 
 // grid (ceil(E / 64), ceil(C / 64)).  Both operands are depth-strided (dz [b, c] along c, x [b, e] along e): thread t loads element
@@ -290,14 +273,11 @@ int check_problem(const char* who, const Problem& p, const float* lr, const Opti
                  "%s: null pointer (feats, labels, base, residuals and lr are required)", who);
   CLIPMI_REQUIRE(o.kind == OPT_SGD || o.kind == OPT_ADAM, CLIPMI_ERR_ARG, "%s: optimizer=%d (0 = SGD, 1 = Adam)", who, o.kind);
   CLIPMI_REQUIRE(o.steps_done >= 0, CLIPMI_ERR_ARG, "%s: steps_done=%lld (>= 0)", who, (long long)o.steps_done);
-  CLIPMI_REQUIRE(o.weight_decay >= 0.f && std::isfinite(o.weight_decay), CLIPMI_ERR_ARG, "%s: weight_decay=%g (finite, >= 0)", who, o.weight_decay);
   if (o.kind == OPT_SGD) {
-    CLIPMI_REQUIRE(o.momentum >= 0.f && o.momentum < 1.f, CLIPMI_ERR_ARG, "%s: momentum=%g (in [0, 1))", who, o.momentum);
-    CLIPMI_REQUIRE(o.dampening >= 0.f && o.dampening < 1.f, CLIPMI_ERR_ARG, "%s: dampening=%g (in [0, 1))", who, o.dampening);
-    CLIPMI_REQUIRE(!o.nesterov || (o.momentum > 0.f && o.dampening == 0.f), CLIPMI_ERR_ARG,
-                   "%s: nesterov needs a momentum and zero dampening (momentum=%g, dampening=%g)", who, o.momentum, o.dampening);
+    if (int rc = check_sgd(who, o.momentum, o.dampening, o.weight_decay, o.nesterov)) return rc;
     CLIPMI_REQUIRE(o.momentum == 0.f || p.state1, CLIPMI_ERR_ARG, "%s: null pointer (a momentum needs the buffer state1)", who);
   } else {
+    CLIPMI_REQUIRE(o.weight_decay >= 0.f && std::isfinite(o.weight_decay), CLIPMI_ERR_ARG, "%s: weight_decay=%g (finite, >= 0)", who, o.weight_decay);
     CLIPMI_REQUIRE(o.beta1 >= 0.0 && o.beta1 < 1.0, CLIPMI_ERR_ARG, "%s: beta1=%g (in [0, 1))", who, o.beta1);
     CLIPMI_REQUIRE(o.beta2 >= 0.0 && o.beta2 < 1.0, CLIPMI_ERR_ARG, "%s: beta2=%g (in [0, 1))", who, o.beta2);
     CLIPMI_REQUIRE(o.eps >= 0.0 && std::isfinite(o.eps), CLIPMI_ERR_ARG, "%s: eps=%g (finite, >= 0)", who, o.eps);
@@ -327,7 +307,7 @@ int check_workspace(const char* who, const void* workspace, size_t bytes, int ro
 OptArgs opt_args(const Optimiser& o, int64_t t) {
   OptArgs a{};
   a.kind = o.kind;
-  a.sgd = SgdArgs{o.momentum, (float)(1.0 - (double)o.dampening), o.weight_decay, o.nesterov ? 1 : 0, t == 1 ? 1 : 0};
+  a.sgd = make_sgd_args(o.momentum, o.dampening, o.weight_decay, o.nesterov, t == 1);
   a.adam = AdamArgs{(float)(1.0 - o.beta1), (float)o.beta2, (float)(1.0 - o.beta2), (float)o.eps, o.weight_decay,
                     1.0 - std::pow(o.beta1, (double)t), std::sqrt(1.0 - std::pow(o.beta2, (double)t))};
   return a;

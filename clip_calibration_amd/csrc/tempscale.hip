@@ -16,14 +16,10 @@
 #include <cmath>
 
 #include "common.h"
+#include "train_rules.h"   // SgdArgs (the first step is state[2] == 0 here, not first_step), check_sgd, block_sum_f64
 
 namespace clipmi {
 namespace {
-
-struct SgdArgs {
-  float momentum, one_minus_dampening, weight_decay;
-  int nesterov;
-};
 
 // rows[r] for batch position r: sample order[r], or first + r without an order.  A sample index outside [0, N) or a label outside
 // [0, C) is never used as an address: the pair is NaN (the host checks both before it launches anything).
@@ -66,27 +62,18 @@ __global__ __launch_bounds__(256) void tempscale_finish_kernel(const float2* __r
                                                                const float* __restrict__ lr, SgdArgs a, float* __restrict__ loss_out,
                                                                float* __restrict__ batch_out) {
 #pragma clang fp contract(off)   // torch's add(other, alpha) rounds the product
-  __shared__ double sl[256], sg[256];
+  __shared__ double sl[2][256];
   const int t = threadIdx.x;
-  double l = 0.0, g = 0.0;
+  double lg[2] = {0.0, 0.0};   // the losses, the gradients
   for (int r = t; r < n; r += 256) {
     const float2 v = rows[r];
-    l += (double)v.x;
-    g += (double)v.y;
+    lg[0] += (double)v.x;
+    lg[1] += (double)v.y;
   }
-  sl[t] = l;
-  sg[t] = g;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if (t < w) {
-      sl[t] += sl[t + w];
-      sg[t] += sg[t + w];
-    }
-    __syncthreads();
-  }
+  block_sum_f64(lg, sl);
   if (t != 0) return;
-  const float loss = (float)(sl[0] / (double)n);
-  float grad = (float)(sg[0] / (double)n);
+  const float loss = (float)(lg[0] / (double)n);
+  float grad = (float)(lg[1] / (double)n);
   if (batch_out) {
     batch_out[0] = loss;
     batch_out[1] = grad;
@@ -160,16 +147,11 @@ int clipmi_tempscale_fit(const float* cosine, int64_t ld, const int64_t* labels,
   CLIPMI_REQUIRE((uintptr_t)state % 4 == 0, CLIPMI_ERR_ARG, "tempscale_fit: the state must be 4-byte aligned");
   CLIPMI_REQUIRE(batch >= 1, CLIPMI_ERR_SHAPE, "tempscale_fit: batch=%d (>= 1)", batch);
   CLIPMI_REQUIRE(epochs >= 0, CLIPMI_ERR_ARG, "tempscale_fit: epochs=%d (>= 0)", epochs);
-  CLIPMI_REQUIRE(momentum >= 0.f && momentum < 1.f, CLIPMI_ERR_ARG, "tempscale_fit: momentum=%g (in [0, 1))", momentum);
-  CLIPMI_REQUIRE(dampening >= 0.f && dampening < 1.f, CLIPMI_ERR_ARG, "tempscale_fit: dampening=%g (in [0, 1))", dampening);
-  CLIPMI_REQUIRE(weight_decay >= 0.f && std::isfinite(weight_decay), CLIPMI_ERR_ARG, "tempscale_fit: weight_decay=%g (finite, >= 0)",
-                 weight_decay);
-  CLIPMI_REQUIRE(!nesterov || (momentum > 0.f && dampening == 0.f), CLIPMI_ERR_ARG,
-                 "tempscale_fit: nesterov needs a momentum and zero dampening (momentum=%g, dampening=%g)", momentum, dampening);
+  if (int rc = check_sgd("tempscale_fit", momentum, dampening, weight_decay, nesterov)) return rc;
   const int width = batch < n ? batch : n;   // the widest batch of the run
   if (int rc = check_workspace("tempscale_fit", workspace, workspace_bytes, width)) return rc;
   const int per_epoch = drop_last ? n / batch : (int)(((int64_t)n + batch - 1) / batch);
-  const SgdArgs a{momentum, (float)(1.0 - (double)dampening), weight_decay, nesterov ? 1 : 0};
+  const SgdArgs a = make_sgd_args(momentum, dampening, weight_decay, nesterov, 0);
   float2* pairs = static_cast<float2*>(workspace);
   int64_t step = 0;
   for (int e = 0; e < epochs; ++e) {

@@ -1,7 +1,10 @@
-// What the training translation units share (adapter_train.hip, taskres_train.hip): torch's optimiser rules on one fp32 element and the
-// batch loss as the float64 mean of the fp32 row losses.  Device code only; every rule is compiled with contraction off, so each product
-// is rounded before it is added, as torch's own kernels round it.
+// What the training translation units share (adapter_train.hip, taskres_train.hip, tempscale.hip, prompt_train.hip): torch.optim.SGD's
+// hyper-parameter rules on the host, torch's optimiser rules on one fp32 element, the workgroup reductions, the cross-entropy row and the
+// batch loss as the float64 mean of the fp32 row losses.  Every device rule is compiled with contraction off, so each product is rounded
+// before it is added, as torch's own kernels round it.
 #pragma once
+#include <cmath>
+
 #include "common.h"
 
 namespace clipmi {
@@ -16,6 +19,19 @@ struct AdamArgs {
   float one_minus_beta1, beta2, one_minus_beta2, eps, weight_decay;
   double bias_correction1, bias_correction2_sqrt;   // 1 - beta1^t, sqrt(1 - beta2^t) of this step's t (1 on the first)
 };
+
+// torch.optim.SGD's own refusals (torch/optim/sgd.py); a momentum's buffer is the caller's to check, since the buffers differ
+inline int check_sgd(const char* who, float momentum, float dampening, float weight_decay, int nesterov) {
+  CLIPMI_REQUIRE(momentum >= 0.f && momentum < 1.f, CLIPMI_ERR_ARG, "%s: momentum=%g (in [0, 1))", who, momentum);
+  CLIPMI_REQUIRE(dampening >= 0.f && dampening < 1.f, CLIPMI_ERR_ARG, "%s: dampening=%g (in [0, 1))", who, dampening);
+  CLIPMI_REQUIRE(weight_decay >= 0.f && std::isfinite(weight_decay), CLIPMI_ERR_ARG, "%s: weight_decay=%g (finite, >= 0)", who, weight_decay);
+  CLIPMI_REQUIRE(!nesterov || (momentum > 0.f && dampening == 0.f), CLIPMI_ERR_ARG,
+                 "%s: nesterov needs a momentum and zero dampening (momentum=%g, dampening=%g)", who, momentum, dampening);
+  return CLIPMI_OK;
+}
+inline SgdArgs make_sgd_args(float momentum, float dampening, float weight_decay, int nesterov, int first_step) {
+  return SgdArgs{momentum, (float)(1.0 - (double)dampening), weight_decay, nesterov ? 1 : 0, first_step ? 1 : 0};
+}
 
 #ifdef __HIPCC__
 // torch.optim.SGD's rule on one element (torch rounds the products of add(other, alpha) before it adds)
@@ -32,7 +48,7 @@ __device__ __forceinline__ void sgd_element(float* __restrict__ w, float* __rest
 }
 
 // The same rule as torch's foreach kernels on the GPU evaluate it, for a caller that is held to torch.optim.SGD bit for bit (ctx_step_kernel,
-// text_backward.hip): every add(other, alpha) is ONE fused multiply-add there -- g + wd w, mul_(momentum) rounded and then
+// prompt_train.hip): every add(other, alpha) is ONE fused multiply-add there -- g + wd w, mul_(momentum) rounded and then
 // buf + (1 - dampening) g, g + momentum buf, w + (-lr) g -- as measured on the MI355X (tests/test_gpu_text_backward.py).
 __device__ __forceinline__ void sgd_element_fma(float* __restrict__ w, float* __restrict__ buf, int64_t idx, float grad, float lr, const SgdArgs& a) {
 #pragma clang fp contract(off)
@@ -63,20 +79,83 @@ __device__ __forceinline__ void adam_element(float* __restrict__ w, float* __res
   w[idx] = p - step_size * m1 / denom;
 }
 
-// *loss_out = float(float64 mean of loss[0 .. rows)) by the 256 threads of one workgroup: thread-strided float64 partial sums, then a
-// binary tree over LDS -- a fixed order.  Every thread of the workgroup calls it.
-__device__ __forceinline__ void mean_loss_256(const float* __restrict__ loss, int rows, float* __restrict__ loss_out) {
-  __shared__ double sl[256];
-  const int t = threadIdx.x;
-  double l = 0.0;
-  for (int b = t; b < rows; b += 256) l += (double)loss[b];
-  sl[t] = l;
+// One value per wave (the same in every lane) to the sum / maximum over the workgroup's WAVES waves, in ascending wave order through sw
+// (WAVES floats of LDS): one barrier.  Every thread of the workgroup calls it and holds the result.  There is no barrier in front: a
+// caller that reduces twice gives each reduction WAVES floats of its own, or puts a barrier between the two.
+template <int WAVES>
+__device__ __forceinline__ float waves_sum(float v, float* sw) {
+#pragma clang fp contract(off)
+  if ((threadIdx.x & 63) == 0) sw[threadIdx.x >> 6] = v;
   __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if (t < w) sl[t] += sl[t + w];
+  v = sw[0];
+  for (int w = 1; w < WAVES; ++w) v += sw[w];
+  return v;
+}
+template <int WAVES>
+__device__ __forceinline__ float waves_max(float v, float* sw) {
+  if ((threadIdx.x & 63) == 0) sw[threadIdx.x >> 6] = v;
+  __syncthreads();
+  v = sw[0];
+  for (int w = 1; w < WAVES; ++w) v = fmaxf(v, sw[w]);
+  return v;
+}
+// the same over the WAVES * 64 threads' own values: the wave tree first
+template <int WAVES>
+__device__ __forceinline__ float block_sum(float v, float* sw) { return waves_sum<WAVES>(wave_sum(v), sw); }
+template <int WAVES>
+__device__ __forceinline__ float block_max(float v, float* sw) { return waves_max<WAVES>(wave_max(v), sw); }
+
+// N float64 sums over the 256 threads of a workgroup by one binary tree over LDS -- a fixed order.  Every thread calls it and holds the
+// results.  No barrier in front either: a second use of the same sl waits for a barrier behind the first.
+template <int N>
+__device__ __forceinline__ void block_sum_f64(double (&v)[N], double (*sl)[256]) {
+  const int t = threadIdx.x;
+#pragma unroll
+  for (int i = 0; i < N; ++i) sl[i][t] = v[i];
+  __syncthreads();
+  for (int h = 128; h > 0; h >>= 1) {
+    if (t < h) {
+#pragma unroll
+      for (int i = 0; i < N; ++i) sl[i][t] += sl[i][t + h];
+    }
     __syncthreads();
   }
-  if (t == 0) *loss_out = (float)(sl[0] / (double)rows);
+#pragma unroll
+  for (int i = 0; i < N; ++i) v[i] = sl[i][0];
+}
+
+// float64 sum of x[0 .. n) by the 256 threads of one workgroup: thread-strided float64 partial sums, then the tree over sl
+__device__ __forceinline__ double sum_f64_256(const float* __restrict__ x, int n, double (*sl)[256]) {
+  double s[1] = {0.0};
+  for (int i = threadIdx.x; i < n; i += 256) s[0] += (double)x[i];
+  block_sum_f64(s, sl);
+  return s[0];
+}
+
+// *loss_out = float(float64 mean of loss[0 .. rows)).  Every thread of the 256-thread workgroup calls it.
+__device__ __forceinline__ void mean_loss_256(const float* __restrict__ loss, int rows, float* __restrict__ loss_out) {
+  __shared__ double sl[1][256];
+  const double s = sum_f64_256(loss, rows, sl);
+  if (threadIdx.x == 0) *loss_out = (float)(s / (double)rows);
+}
+
+// The cross-entropy of one row of C logits z with the row maximum m and the label y in [0, C): S = sum_c exp(z_c - m) thread-strided, then
+// block_sum through sw (WAVES floats no earlier reduction still reads); *loss = log S - (z_y - m); dz_c = (exp(z_c - m) / S - [c == y]) k,
+// the caller's factor k already formed.  dz may be z itself (z_y is read before the barrier, the stores follow it), so neither is
+// __restrict__.  One barrier.  Every thread of the WAVES * 64 calls it, the logits final and visible to the workgroup.
+template <int WAVES>
+__device__ __forceinline__ void xent_row(const float* z, float* dz, int C, float m, int64_t y, float k, float* sw, float* loss) {
+#pragma clang fp contract(off)
+  const int t = threadIdx.x;
+  const float zy = t == 0 ? z[y] : 0.f;   // thread 0 writes the loss
+  float S = 0.f;
+  for (int c = t; c < C; c += WAVES * 64) S += __expf(z[c] - m);
+  S = block_sum<WAVES>(S, sw);
+  if (t == 0) *loss = logf(S) - (zy - m);
+  for (int c = t; c < C; c += WAVES * 64) {
+    const float p = __expf(z[c] - m) / S;
+    dz[c] = (c == y ? p - 1.f : p) * k;
+  }
 }
 #endif
 

@@ -859,7 +859,7 @@ def scale_add(a: torch.Tensor, b: torch.Tensor, alpha: float) -> torch.Tensor:
     return out
 
 
-# ---- CoOp's training path at operator level (include/clipmi.h "CoOp's context trained on the device", csrc/text_backward.hip) ----------
+# ---- CoOp's training path at operator level (include/clipmi.h "CoOp's context trained on the device", csrc/text_backward.hip, csrc/prompt_train.hip) ----
 def layernorm_backward(x: torch.Tensor, gamma: torch.Tensor, dy: torch.Tensor, g: torch.Tensor, g16: Optional[torch.Tensor] = None,
                        row_idx: Optional[torch.Tensor] = None, eps: float = 1e-5) -> None:
     """LayerNorm's backward from the saved fp32 rows ``x`` [R, D] (the rows may be a column slice): ``g[row(r)] += dX(r)`` in place and
@@ -914,17 +914,23 @@ def attention_backward(qkv: torch.Tensor, d_out: torch.Tensor, n_seq: int, n_hea
     return out
 
 
+def _head_inputs(who: str, features, labels, text):
+    """(labels, text, B, E, C) of a loss head after the checks coop_head and prompt_head share."""
+    if not isinstance(features, torch.Tensor) or features.dim() != 2 or features.stride(1) != 1:
+        raise ValueError(f"{who}: features must be a [B, E] tensor with unit column stride")
+    if not features.is_cuda or features.dtype != torch.float32:
+        raise TypeError(f"{who}: features must be fp32 on the GPU")
+    labels, text = _dev(labels, "labels", (torch.int64,)), _dev(text, "text", (torch.float32,))
+    B, E = features.shape
+    if text.dim() != 2 or text.shape[1] != E or labels.shape != (B,):
+        raise ValueError(f"{who}: features {tuple(features.shape)}, labels {tuple(labels.shape)}, text {tuple(text.shape)} do not agree")
+    return labels, text, B, E, text.shape[0]
+
+
 def coop_head(features: torch.Tensor, labels: torch.Tensor, text: torch.Tensor, scale: float, grad_scale: float = 1.0, want16: bool = False):
     """CoOp's loss head: (loss fp32 [1], grad_scale * d loss / d text fp32 [C, E][, the same in fp16]) for raw image ``features`` fp32
     [B, E] (the rows may be a column slice), ``labels`` int64 [B] and raw ``text`` features fp32 [C, E]; ``scale`` = exp(logit_scale)."""
-    if not isinstance(features, torch.Tensor) or features.dim() != 2 or features.stride(1) != 1:
-        raise ValueError("coop_head: features must be a [B, E] tensor with unit column stride")
-    if not features.is_cuda or features.dtype != torch.float32:
-        raise TypeError("coop_head: features must be fp32 on the GPU")
-    labels, text = _dev(labels, "labels", (torch.int64,)), _dev(text, "text", (torch.float32,))
-    (B, E), Cn = features.shape, text.shape[0]
-    if text.dim() != 2 or text.shape[1] != E or labels.shape != (B,):
-        raise ValueError(f"coop_head: features {tuple(features.shape)}, labels {tuple(labels.shape)}, text {tuple(text.shape)} do not agree")
+    labels, text, B, E, Cn = _head_inputs("coop_head", features, labels, text)
     loss = torch.empty(1, dtype=torch.float32, device=text.device)
     d_text = torch.empty_like(text)
     d16 = torch.empty(Cn, E, dtype=torch.float16, device=text.device) if want16 else None
@@ -935,6 +941,28 @@ def coop_head(features: torch.Tensor, labels: torch.Tensor, text: torch.Tensor, 
     return (loss, d_text, d16) if want16 else (loss, d_text)
 
 
+def _ctx_step_inputs(who: str, d_embed: torch.Tensor, n_prompts: int, n_ctx: int, per_class: bool, ctx, buf, lr):
+    """(rows per prompt, D, ctx's shape, the pointers of ctx, buf and lr or None) after the checks ctx_step and prograd_step share."""
+    M, D = d_embed.shape
+    if n_prompts < 1 or M % n_prompts:
+        raise ValueError(f"{who}: {M} rows do not split into {n_prompts} prompts")
+    shape = (n_prompts, n_ctx, D) if per_class else (n_ctx, D)
+    pc = pb = pl = None
+    if ctx is not None:
+        _in_place(ctx, torch.float32, f"{who}: ctx must be a contiguous fp32 tensor on the GPU")
+        if tuple(ctx.shape) != shape:
+            raise ValueError(f"{who}: ctx {tuple(ctx.shape)} must be {shape}")
+        pc = ctx.data_ptr()
+        if buf is not None:
+            _in_place(buf, torch.float32, f"{who}: buf must be a contiguous fp32 tensor on the GPU", numel=ctx.numel())
+            pb = buf.data_ptr()
+        lr = _dev(lr, "lr", (torch.float32,))
+        if lr.numel() != 1:
+            raise ValueError(f"{who}: lr must hold one rate")
+        pl = lr.data_ptr()
+    return M // n_prompts, D, shape, pc, pb, pl
+
+
 def ctx_step(d_embed: torch.Tensor, n_prompts: int, n_ctx: int, per_class: bool, grad_scale: float, ctx: Optional[torch.Tensor] = None,
              buf: Optional[torch.Tensor] = None, lr: Optional[torch.Tensor] = None, first_step: bool = False, momentum: float = 0.0,
              dampening: float = 0.0, weight_decay: float = 0.0, nesterov: bool = False, want_grad: bool = True) -> Optional[torch.Tensor]:
@@ -942,25 +970,9 @@ def ctx_step(d_embed: torch.Tensor, n_prompts: int, n_ctx: int, per_class: bool,
     ``grad_scale``) and, with ``ctx``, torch.optim.SGD's step on it in place at the rate ``lr`` fp32 [1] (``buf``: momentum buffer).
     Returns the gradient (ctx's shape) when ``want_grad``."""
     d_embed = _dev(d_embed, "d_embed", (torch.float32,))
-    M, D = d_embed.shape
-    if n_prompts < 1 or M % n_prompts:
-        raise ValueError(f"ctx_step: {M} rows do not split into {n_prompts} prompts")
-    shape = (n_prompts, n_ctx, D) if per_class else (n_ctx, D)
-    pc = pb = pl = None
-    if ctx is not None:
-        _in_place(ctx, torch.float32, "ctx_step: ctx must be a contiguous fp32 tensor on the GPU")
-        if tuple(ctx.shape) != shape:
-            raise ValueError(f"ctx_step: ctx {tuple(ctx.shape)} must be {shape}")
-        pc = ctx.data_ptr()
-        if buf is not None:
-            _in_place(buf, torch.float32, "ctx_step: buf must be a contiguous fp32 tensor on the GPU", numel=ctx.numel())
-            pb = buf.data_ptr()
-        lr = _dev(lr, "lr", (torch.float32,))
-        if lr.numel() != 1:
-            raise ValueError("ctx_step: lr must hold one rate")
-        pl = lr.data_ptr()
+    L, D, shape, pc, pb, pl = _ctx_step_inputs("ctx_step", d_embed, n_prompts, n_ctx, per_class, ctx, buf, lr)
     grad = torch.empty(shape, dtype=torch.float32, device=d_embed.device) if want_grad else None
-    check(lib.clipmi_ctx_step(d_embed.data_ptr(), pc, pb, None if grad is None else grad.data_ptr(), n_prompts, M // n_prompts, D, int(n_ctx),
+    check(lib.clipmi_ctx_step(d_embed.data_ptr(), pc, pb, None if grad is None else grad.data_ptr(), n_prompts, L, D, int(n_ctx),
                               int(bool(per_class)), float(grad_scale), pl, int(bool(first_step)), float(momentum), float(dampening),
                               float(weight_decay), int(bool(nesterov)), _stream()), "clipmi_ctx_step")
     return grad
@@ -970,21 +982,15 @@ PROMPT_MODES = {"coop": _lib.PROMPT_COOP, "kgcoop": _lib.PROMPT_KGCOOP, "prograd
 
 
 def prompt_head(features: torch.Tensor, labels: torch.Tensor, text: torch.Tensor, scale: float, grad_scale: float = 1.0, method: str = "coop",
-                teacher: Optional[torch.Tensor] = None, w: float = 8.0, T: float = 1.0):
+                teacher: Optional[torch.Tensor] = None, w: float = 8.0, T: float = 1.0, losses: Optional[torch.Tensor] = None):
     """The loss head of CoOp, KgCoOp or ProGrad (``method``): ``(losses fp32 [3], d_text fp32 [C, E], d_text_kl fp32 [C, E] or None)``,
     the gradients times ``grad_scale``.  Inputs as ``coop_head``'s; ``teacher`` fp32 [C, E]: the frozen zero-shot text features (the head
     normalises the rows).  ``losses``: [loss, 0, 0] for CoOp, [CE + w score, CE, score = 1 - mean cosine to the teacher] for KgCoOp,
-    [xe, kl, 0] for ProGrad, whose two gradients are those of xe and of kl (``T``: the distillation temperature)."""
+    [xe, kl, 0] for ProGrad, whose two gradients are those of xe and of kl (``T``: the distillation temperature).  A caller's own
+    ``losses`` (fp32 [3] on the GPU) is written where it lies instead -- the elements the method does not write keep what they held."""
     if method not in PROMPT_MODES:
         raise ValueError(f"prompt_head: method={method!r} (one of {sorted(PROMPT_MODES)})")
-    if not isinstance(features, torch.Tensor) or features.dim() != 2 or features.stride(1) != 1:
-        raise ValueError("prompt_head: features must be a [B, E] tensor with unit column stride")
-    if not features.is_cuda or features.dtype != torch.float32:
-        raise TypeError("prompt_head: features must be fp32 on the GPU")
-    labels, text = _dev(labels, "labels", (torch.int64,)), _dev(text, "text", (torch.float32,))
-    (B, E), Cn = features.shape, text.shape[0]
-    if text.dim() != 2 or text.shape[1] != E or labels.shape != (B,):
-        raise ValueError(f"prompt_head: features {tuple(features.shape)}, labels {tuple(labels.shape)}, text {tuple(text.shape)} do not agree")
+    labels, text, B, E, Cn = _head_inputs("prompt_head", features, labels, text)
     pt = None
     if method != "coop":
         if teacher is None:
@@ -994,7 +1000,10 @@ def prompt_head(features: torch.Tensor, labels: torch.Tensor, text: torch.Tensor
             raise ValueError(f"prompt_head: teacher {tuple(teacher.shape)} must be {tuple(text.shape)}")
         pt = teacher.data_ptr()
     mode = PROMPT_MODES[method]
-    losses = torch.zeros(3, dtype=torch.float32, device=text.device)
+    if losses is None:
+        losses = torch.zeros(3, dtype=torch.float32, device=text.device)
+    else:
+        _in_place(losses, torch.float32, "prompt_head: losses must be a contiguous fp32 tensor on the GPU", numel=3)
     d_text = torch.empty_like(text)
     d_kl = torch.empty_like(text) if method == "prograd" else None
     ws = torch.empty(max(lib.clipmi_prompt_head_workspace_bytes(B, E, Cn, mode), 8), dtype=torch.uint8, device=text.device)
@@ -1013,26 +1022,10 @@ def prograd_step(d_embed_xe: torch.Tensor, d_embed_kl: torch.Tensor, n_prompts: 
     with ``ctx`` torch.optim.SGD's step on it in place.  Returns ``(grad, projected int32 [1], dots float64 [3] = a.a, b.b, a.b)`` on
     the device when ``want_report``."""
     d_embed_xe, d_embed_kl = _dev(d_embed_xe, "d_embed_xe", (torch.float32,)), _dev(d_embed_kl, "d_embed_kl", (torch.float32,))
-    M, D = d_embed_xe.shape
     if d_embed_kl.shape != d_embed_xe.shape:
         raise ValueError("prograd_step: the two d_embed differ in shape")
-    if n_prompts < 1 or M % n_prompts:
-        raise ValueError(f"prograd_step: {M} rows do not split into {n_prompts} prompts")
-    shape = (n_prompts, n_ctx, D) if per_class else (n_ctx, D)
-    pc = pb = pl = None
-    if ctx is not None:
-        _in_place(ctx, torch.float32, "prograd_step: ctx must be a contiguous fp32 tensor on the GPU")
-        if tuple(ctx.shape) != shape:
-            raise ValueError(f"prograd_step: ctx {tuple(ctx.shape)} must be {shape}")
-        pc = ctx.data_ptr()
-        if buf is not None:
-            _in_place(buf, torch.float32, "prograd_step: buf must be a contiguous fp32 tensor on the GPU", numel=ctx.numel())
-            pb = buf.data_ptr()
-        lr = _dev(lr, "lr", (torch.float32,))
-        if lr.numel() != 1:
-            raise ValueError("prograd_step: lr must hold one rate")
-        pl = lr.data_ptr()
-    elif not want_report:
+    L, D, shape, pc, pb, pl = _ctx_step_inputs("prograd_step", d_embed_xe, n_prompts, n_ctx, per_class, ctx, buf, lr)
+    if ctx is None and not want_report:
         raise ValueError("prograd_step: nothing to do (no ctx and no report)")
     dev = d_embed_xe.device
     grad = proj = dots = None
@@ -1043,7 +1036,7 @@ def prograd_step(d_embed_xe: torch.Tensor, d_embed_kl: torch.Tensor, n_prompts: 
     ws = torch.empty(max(lib.clipmi_prograd_step_workspace_bytes(n_prompts, D, int(n_ctx), int(bool(per_class))), 256), dtype=torch.uint8, device=dev)
     check(lib.clipmi_prograd_step(d_embed_xe.data_ptr(), d_embed_kl.data_ptr(), pc, pb, None if grad is None else grad.data_ptr(),
                                   None if proj is None else proj.data_ptr(), None if dots is None else dots.data_ptr(), n_prompts,
-                                  M // n_prompts, D, int(n_ctx), int(bool(per_class)), float(grad_scale), float(lam), pl, int(bool(first_step)),
+                                  L, D, int(n_ctx), int(bool(per_class)), float(grad_scale), float(lam), pl, int(bool(first_step)),
                                   float(momentum), float(dampening), float(weight_decay), int(bool(nesterov)), ws.data_ptr(), ws.numel(),
                                   _stream()), "clipmi_prograd_step")
     return (grad, proj, dots) if want_report else None

@@ -691,7 +691,7 @@ int clipmi_encode_text(clipmi_model* m, const int64_t* ids, int n_prompts, int s
 /* ------------------------------------------------------------------------------------------------------
  * CoOp's context trained on the device (trainers/classification/coop.py:70-144, 192-222, 282-309): the gradient of the text features
  * with respect to the text tower's INPUT EMBEDDINGS with the tower frozen, CoOp's cross-entropy head and torch.optim.SGD's step on the
- * context vectors (csrc/text_backward.hip, DESIGN.md "CoOp fit").  No weight gradient exists: every Linear's backward is dX = dY W,
+ * context vectors (csrc/text_backward.hip, csrc/prompt_train.hip, DESIGN.md "CoOp fit").  No weight gradient exists: every Linear's backward is dX = dY W,
  * clipmi_gemm_f16 on a transposed copy of the weight that the caller packs once.  The whole backward carries grad_scale * gradient
  * (a power of two: fp16 operands flush small values); only clipmi_coop_head and clipmi_ctx_step know the factor.
  * These exports are additive: the ABI version does not change with them.

@@ -1,4 +1,4 @@
-"""Reference of CoOp's training path (clip_calibration_amd/coopfit.py, csrc/text_backward.hip).  It does not import the package.
+"""Reference of CoOp's training path (clip_calibration_amd/coopfit.py, csrc/text_backward.hip, csrc/prompt_train.hip).  It does not import the package.
 
 Two things live here.  (1) A hand-written torch restatement, in whatever dtype it is given (float64 in the tests), of every backward
 formula the kernels implement: LayerNorm, QuickGELU, causal attention, the loss head through both normalisations, the tail (projection,

@@ -1,4 +1,4 @@
-"""Reference of KgCoOp's and ProGrad's training path (clip_calibration_amd/coopfit.py with ``method=``, csrc/text_backward.hip).  It does
+"""Reference of KgCoOp's and ProGrad's training path (clip_calibration_amd/coopfit.py with ``method=``, csrc/prompt_train.hip).  It does
 not import the package's kernels.
 
 (1) A no-autograd restatement, in whatever dtype it is given, of both loss heads and of ProGrad's projection rule, on top of

@@ -1,4 +1,4 @@
-"""CPU checks of CoOp's training path (clip_calibration_amd/coopfit.py, csrc/text_backward.hip): the hand-written restatement of every
+"""CPU checks of CoOp's training path (clip_calibration_amd/coopfit.py, csrc/text_backward.hip, csrc/prompt_train.hip): the hand-written restatement of every
 backward formula (tests/coopfit_ref.py) equals float64 autograd through the oracle, the host-side argument checks, the header."""
 import functools
 import os
@@ -148,6 +148,29 @@ def test_header_declares_the_entries_with_the_abi_at_16():
     for n in names:
         assert re.search(r"\b(int|size_t) " + n + r"\(", text), n
         assert n in _lib.exported_symbols() and hasattr(_lib.lib, n)
+
+
+@pytest.mark.parametrize("geom", ["tiny", "tiny3"])
+def test_coop_sizes_are_mode_0_of_the_prompt_sizes(geom):
+    """clipmi_coop_head_workspace_bytes and clipmi_coop_train_step_bytes wrap the prompt learners' sizing functions at mode 0, whose size
+    depends on neither n_ctx nor ctx_per_class; shapes either refuses keep their zero."""
+    lib = _lib.lib
+    m = build_model(dict(ref.state_dict(geom)), {"trainer": "CoOp"})
+    m._ensure_handle()
+    h, E = m._handle, int(m.geometry.embed_dim)
+    for Cn in (2, 3, 37, 257):
+        for B in (1, 4):
+            head = lib.clipmi_coop_head_workspace_bytes(B, E, Cn)
+            assert head >= (2 * B * Cn + 2 * B + Cn) * 4 and head == lib.clipmi_prompt_head_workspace_bytes(B, E, Cn, _lib.PROMPT_COOP)
+            for rows in (0, 16):
+                step = lib.clipmi_coop_train_step_bytes(h, Cn, rows, B)
+                assert step > head
+                for n_ctx, per_class in ((1, 0), (4, 0), (16, 1)):
+                    assert step == lib.clipmi_prompt_train_step_bytes(h, Cn, rows, B, _lib.PROMPT_COOP, n_ctx, per_class)
+    assert lib.clipmi_coop_head_workspace_bytes(0, E, 3) == 0 and lib.clipmi_coop_head_workspace_bytes(4, 0, 3) == 0
+    assert lib.clipmi_coop_head_workspace_bytes(4, E, 1) == 0
+    assert lib.clipmi_coop_train_step_bytes(None, 3, 0, 4) == 0 and lib.clipmi_coop_train_step_bytes(h, 1, 0, 4) == 0
+    assert lib.clipmi_coop_train_step_bytes(h, 3, 0, 0) == 0 and lib.clipmi_coop_train_step_bytes(h, -1, 0, 4) == 0
 
 
 def test_library_refuses_bad_calls_without_a_device():

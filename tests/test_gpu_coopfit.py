@@ -1,4 +1,4 @@
-"""CoOp's training on the GPU end to end (clip_calibration_amd/coopfit.py, csrc/text_backward.hip) on the `tiny` and `tiny3` geometries
+"""CoOp's training on the GPU end to end (clip_calibration_amd/coopfit.py, csrc/text_backward.hip, csrc/prompt_train.hip) on the `tiny` and `tiny3` geometries
 against float64 autograd through the oracle (tests/coopfit_ref.py).
 
 The parity bound is computed here, at run time: the error measure is the relative Frobenius error of the context's gradient against
@@ -111,6 +111,46 @@ def test_three_steps_same_bits_every_way(key):
     assert torch.equal(a, b) and np.array_equal(la, lb)
     assert torch.equal(a, d) and np.array_equal(la, ld)
     assert torch.equal(a, e) and np.array_equal(la, le)          # two runs, the same bits
+
+
+def two_one_call_steps(c, geom, symbol, want_loss=True):
+    """Two steps through one of the library's one-call symbols from a fresh state: (ctx, buf, losses [2], grad_out [2, ...])."""
+    import ctypes
+
+    from clip_calibration_amd import _lib, ops
+    lib, m = _lib.lib, model(geom)
+    st = coopfit.CoOpFitState(m, c["ids"], c["ctx"], ref.LOGIT_SCALE, momentum=0.9, dampening=0.0, nesterov=False, weight_decay=5e-4,
+                              grad_scale=GRAD_SCALE)
+    t, f, y = st.tower, c["feats"].cuda(), c["labels"].cuda()
+    lr = torch.tensor([2e-3, 1e-3], dtype=torch.float32).cuda()
+    losses, grads = torch.zeros(2, 3).cuda(), torch.zeros(2, *st.ctx.shape).cuda()
+    ws = t.one_call_workspace(f.shape[0])
+    for k in range(2):
+        head = (m._handle, ctypes.byref(t.dgrad[0]), t.base.data_ptr(), coopfit._DT[t.base.dtype], st.ctx.data_ptr(), st.buf.data_ptr(), t.n_ctx,
+                int(t.per_class), t.eot.data_ptr(), t.C, t.rows, f.data_ptr(), f.stride(0), y.data_ptr(), f.shape[0], st.scale, GRAD_SCALE)
+        sgd = (lr[k:k + 1].data_ptr(), int(k == 0), 0.9, 0.0, 5e-4, 0)
+        tail = (ws.data_ptr(), ws.numel(), t.stash.data_ptr(), t.stash.numel(), ops._stream())
+        with m._launch_lock:
+            if symbol == "coop":
+                rc = lib.clipmi_coop_train_step(*head, *sgd, losses[k].data_ptr() if want_loss else None, grads[k].data_ptr(), *tail)
+            else:
+                rc = lib.clipmi_prompt_train_step(*head, _lib.PROMPT_COOP, None, 0.0, 0.0, 0.0, *sgd, losses[k].data_ptr(), grads[k].data_ptr(), None,
+                                                  None, *tail)
+        assert rc == _lib.OK, _lib.last_error()
+    return st.ctx.cpu(), st.buf.cpu(), losses[:, 0].cpu(), grads.cpu()
+
+
+@pytest.mark.parametrize("key", [("tiny", 3, 4, 4, False), ("tiny3", 37, 4, 4, True)], ids=lambda k: "-".join(str(v) for v in k))
+def test_coop_train_step_is_mode_0_of_prompt_train_step(key):
+    """coopfit steps through clipmi_prompt_train_step alone; CoOp's own symbol is held to it here: the same bits in the context, the momentum
+    buffer, the losses and grad_out over two steps with momentum, and a NULL loss (which only the CoOp symbol takes) changes no other bit."""
+    c = ref.make_case(*key)
+    ctx, buf, losses, grads = two_one_call_steps(c, key[0], "coop")
+    ctx_p, buf_p, losses_p, grads_p = two_one_call_steps(c, key[0], "prompt")
+    assert torch.isfinite(ctx).all() and not torch.equal(ctx, c["ctx"]) and torch.isfinite(losses).all() and bool((losses > 0).all())
+    assert torch.equal(ctx, ctx_p) and torch.equal(buf, buf_p) and torch.equal(losses, losses_p) and torch.equal(grads, grads_p)
+    ctx_n, buf_n, losses_n, grads_n = two_one_call_steps(c, key[0], "coop", want_loss=False)
+    assert torch.equal(ctx_n, ctx) and torch.equal(buf_n, buf) and torch.equal(grads_n, grads) and not losses_n.any()
 
 
 def test_three_steps_against_float64_sgd():

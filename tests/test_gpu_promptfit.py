@@ -1,4 +1,4 @@
-"""KgCoOp's and ProGrad's training on the GPU (clip_calibration_amd/coopfit.py with ``method=``, csrc/text_backward.hip) on the `tiny` and
+"""KgCoOp's and ProGrad's training on the GPU (clip_calibration_amd/coopfit.py with ``method=``, csrc/prompt_train.hip) on the `tiny` and
 `tiny3` geometries against the float64 restatement and float64 autograd through the oracle (tests/promptfit_ref.py).
 
 The bounds are computed here, at run time, by the rules of the CoOp tests.  Operator level: 4 x the distance of torch's own fp32

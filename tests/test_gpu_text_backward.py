@@ -1,4 +1,4 @@
-"""The kernels of CoOp's training path at operator level (csrc/text_backward.hip through clip_calibration_amd.ops), one entry point at a
+"""The kernels of CoOp's training path at operator level (csrc/text_backward.hip and csrc/prompt_train.hip through clip_calibration_amd.ops), one entry point at a
 time against the float64 formulas of tests/coopfit_ref.py.  Every tolerance is derived where it is used, from the number formats and the
 kernel's summation, never from what the kernel returns."""
 import numpy as np

@@ -1,4 +1,4 @@
-"""CPU checks of KgCoOp's and ProGrad's training path (clip_calibration_amd/coopfit.py with ``method=``, csrc/text_backward.hip): the
+"""CPU checks of KgCoOp's and ProGrad's training path (clip_calibration_amd/coopfit.py with ``method=``, csrc/prompt_train.hip): the
 restatement of both heads and of the projection rule (tests/promptfit_ref.py) equals float64 autograd through the oracle and the
 reference's own arithmetic, the host-side argument checks, the library's refusals without a device, the header."""
 import ctypes

@@ -1,4 +1,4 @@
-"""Time of one CoOp training step on the device (clip_calibration_amd.coopfit, csrc/text_backward.hip) against a torch fp16 autograd +
+"""Time of one CoOp training step on the device (clip_calibration_amd.coopfit, csrc/text_backward.hip, csrc/prompt_train.hip) against a torch fp16 autograd +
 SGD step over the same model, and the measurement behind ``grad_scale``'s default.  Measurement only; bench.py does not run it.
 
 1. step: ViT-B/16 text geometry with synthetic weights, batch 32 of cached image features, n_ctx 16, C = 100 and C = 1000 classes, the

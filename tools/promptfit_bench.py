@@ -1,5 +1,5 @@
 """Time of one KgCoOp and one ProGrad training step on the device (clip_calibration_amd.coopfit with ``method=``,
-csrc/text_backward.hip) against our CoOp step and against a torch fp16 autograd + SGD step over the torch mirror of the same method.
+csrc/prompt_train.hip) against our CoOp step and against a torch fp16 autograd + SGD step over the torch mirror of the same method.
 Measurement only; bench.py does not run it.
 
 ViT-B/16 text geometry with synthetic weights, batch 32 of cached image features, C = 100 and C = 1000 classes, the live-row cut on;
