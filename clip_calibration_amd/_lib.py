@@ -187,6 +187,13 @@ _SIGNATURES = {
     "clipmi_prompt_train_step_bytes": (_sz, [_vp, _i, _i, _i, _i, _i, _i]),
     "clipmi_prompt_train_step": (_i, [_vp, C.POINTER(TextDgrad), _vp, _i, _vp, _vp, _i, _i, _vp, _i, _i, _vp, _i64, _vp, _i, _f, _f, _i, _vp, _f, _f,
                                       _f, _vp, _i, _f, _f, _f, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
+    "clipmi_proda_embed": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "clipmi_proda_head_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "clipmi_proda_head": (_i, [_vp, _i64, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _f, _vp, _vp, _vp, _sz, _vp]),
+    "clipmi_proda_ctx_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _i, _f, _f, _f, _i, _vp]),
+    "clipmi_proda_train_step_bytes": (_sz, [_vp, _i, _i, _i, _i, _i]),
+    "clipmi_proda_train_step": (_i, [_vp, C.POINTER(TextDgrad), _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i64, _vp, _i, _f, _f,
+                                     _f, _vp, _i, _f, _f, _f, _i, _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
     "clipmi_order_stats_workspace_bytes": (_sz, [_i, _i]),
     "clipmi_order_stats": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
     "clipmi_group_gap_accumulate": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _vp]),

@@ -35,8 +35,8 @@ along the other one, ``b``, taken out when they conflict: ``a - lam (a.b / b.b) 
 rounding points.  Unverified, besides Dassl's defaults above: the reference's ``amp`` branch of ProGrad (prograd.py:415-424) hands
 ``GradScaler.scale`` a tuple and is not mirrored.
 
-Not covered: ``nn.DataParallel`` (one process drives one GPU), class token positions other than ``end``, models whose text tower carries
-deep prompts, and ProDA (a set of prompts with a forward of its own, not an extra term on this one).
+Not covered: ``nn.DataParallel`` (one process drives one GPU), class token positions other than ``end`` (ProDA's three positions train
+through ``prodafit``, on this backward with a head of its own), and models whose text tower carries deep prompts.
 """
 from __future__ import annotations
 
@@ -108,6 +108,20 @@ def _check_batch(who: str, features, labels, C: int, E: int):
     return _labels(who, labels, features.shape[0], C)
 
 
+MAX_LIVE_ROWS = 80     # token rows per prompt that clipmi_text_encoder_backward takes (include/clipmi.h; the attention backward's limit)
+
+
+def _live_rows(clip_model, last_eot: int, seq_rows: Optional[int]) -> int:
+    """The ``seq_rows`` handed to the library (0: the whole context) for a prompt set whose last EOT sits on row ``last_eot``: None cuts
+    behind it, rounded up to a multiple of 8, unless the model runs every row; a number is taken as it is when it cuts anything."""
+    Lc = int(clip_model.context_length)
+    if seq_rows is None:
+        rows = min(Lc, (last_eot + 1 + 7) // 8 * 8) if clip_model.text_dead_row_elimination else Lc
+    else:
+        rows = int(seq_rows)
+    return rows if 0 < rows < Lc else 0
+
+
 METHODS = ("coop", "kgcoop", "prograd")
 
 
@@ -174,13 +188,9 @@ class _Tower:
         if self.base.dtype not in _DT:
             raise TypeError(f"{who}: the model's dtype {self.base.dtype} is not fp16 or fp32")
         self.eot = ids.argmax(dim=-1).to(torch.int32).contiguous()
-        if seq_rows is None:
-            rows = min(self.Lc, (last_eot + 1 + 7) // 8 * 8) if clip_model.text_dead_row_elimination else self.Lc
-        else:
-            rows = int(seq_rows)
-            if rows and rows <= last_eot:
-                raise ValueError(f"{who}: seq_rows={rows} cuts the EOT row {last_eot}")
-        self.rows = rows if 0 < rows < self.Lc else 0
+        if seq_rows is not None and int(seq_rows) and int(seq_rows) <= last_eot:
+            raise ValueError(f"{who}: seq_rows={int(seq_rows)} cuts the EOT row {last_eot}")
+        self.rows = _live_rows(clip_model, last_eot, seq_rows)
         self.L = self.rows or self.Lc
         clip_model._ensure_bound()
         self.dgrad = _dgrad(clip_model)

@@ -1040,3 +1040,90 @@ def prograd_step(d_embed_xe: torch.Tensor, d_embed_kl: torch.Tensor, n_prompts: 
                                   float(momentum), float(dampening), float(weight_decay), int(bool(nesterov)), ws.data_ptr(), ws.numel(),
                                   _stream()), "clipmi_prograd_step")
     return (grad, proj, dots) if want_report else None
+
+
+def _proda_index(t: torch.Tensor, name: str, n: int) -> torch.Tensor:
+    t = _dev(t, name, (torch.int32,))
+    if t.shape != (n,):
+        raise ValueError(f"clipmi: `{name}` {tuple(t.shape)} must be int32 [{n}]")
+    return t
+
+
+def proda_embed(base: torch.Tensor, nc_base: torch.Tensor, ctx: torch.Tensor, sel: torch.Tensor, pos: torch.Tensor, name_lens: torch.Tensor,
+                cls_eot: torch.Tensor, rows: int = 0, prompts: Optional[torch.Tensor] = None, eot: Optional[torch.Tensor] = None):
+    """ProDA's prompt assembly: ``(prompts fp32 [C * Pb + P, Lc, D], eot int32 [C * Pb + P])`` from the class embeddings ``base``
+    [C, Lc, D] and the no-class embedding ``nc_base`` [1, Lc, D] (fp16 or fp32), the fp32 master ``ctx`` [P, n_ctx, D] and the int32
+    device vectors ``sel`` [Pb] (in the reference's end | middle | front order), ``pos`` [P] (0 front, 1 middle, 2 end), ``name_lens``
+    [C] and ``cls_eot`` [C] (the classes' EOT rows, which every prompt of a class keeps): the class prompts class-major, then the P no-class prompts.  Only the first ``rows`` token rows of each prompt are written (0:
+    all of them).  A caller's own ``prompts`` and ``eot`` are written where they lie."""
+    base = _dev(base, "base", (torch.float16, torch.float32))
+    nc_base = _dev(nc_base, "nc_base", (base.dtype,))
+    ctx = _dev(ctx, "ctx", (torch.float32,))
+    if base.dim() != 3 or ctx.dim() != 3 or nc_base.shape != (1,) + tuple(base.shape[1:]) or ctx.shape[2] != base.shape[2]:
+        raise ValueError(f"proda_embed: base {tuple(base.shape)}, nc_base {tuple(nc_base.shape)} and ctx {tuple(ctx.shape)} do not agree")
+    Cn, Lc, D = base.shape
+    P, n_ctx = int(ctx.shape[0]), int(ctx.shape[1])
+    sel = _dev(sel, "sel", (torch.int32,))
+    Pb = int(sel.numel())
+    sel, pos, name_lens = _proda_index(sel, "sel", Pb), _proda_index(pos, "pos", P), _proda_index(name_lens, "name_lens", Cn)
+    cls_eot = _proda_index(cls_eot, "cls_eot", Cn)
+    N = Cn * Pb + P
+    L = int(rows) if 0 < int(rows) < Lc else Lc
+    if prompts is None:
+        prompts = torch.empty(N, Lc, D, dtype=torch.float32, device=base.device)
+    else:
+        _in_place(prompts, torch.float32, "proda_embed: prompts must be a contiguous fp32 tensor on the GPU", numel=N * Lc * D)
+    if eot is None:
+        eot = torch.empty(N, dtype=torch.int32, device=base.device)
+    else:
+        _in_place(eot, torch.int32, "proda_embed: eot must be a contiguous int32 tensor on the GPU", numel=N)
+    check(lib.clipmi_proda_embed(base.data_ptr(), nc_base.data_ptr(), _DT[base.dtype], ctx.data_ptr(), sel.data_ptr(), pos.data_ptr(),
+                                 name_lens.data_ptr(), cls_eot.data_ptr(), prompts.data_ptr(), eot.data_ptr(), Cn, Pb, P, L, Lc, D, n_ctx, _stream()), "clipmi_proda_embed")
+    return prompts, eot
+
+
+def proda_head(features: torch.Tensor, labels: torch.Tensor, text: torch.Tensor, n_cls: int, n_sel: int, scale: float, grad_scale: float = 1.0,
+               alpha: float = 0.1, losses: Optional[torch.Tensor] = None):
+    """ProDA's loss head: ``(losses fp32 [3] = [upper + alpha m, upper, m], d_text fp32 [N, E])``, the gradient times ``grad_scale``.
+    ``text`` fp32 [N = n_cls * n_sel + P, E]: the raw features of the class prompts (class-major, ``n_sel`` per class) and of the P
+    no-class prompts; ``features`` and ``labels`` as ``coop_head``'s.  upper is the cross-entropy of
+    ``s x_b . m_c + 0.5 s^2 sigma[b, c]`` (include/clipmi.h), m the mean absolute cosine between two different no-class features."""
+    labels, text, B, E, N = _head_inputs("proda_head", features, labels, text)
+    Cn, Pb = int(n_cls), int(n_sel)
+    P = N - Cn * Pb
+    if Cn < 2 or Pb < 1 or P < 2 or Pb > P:
+        raise ValueError(f"proda_head: {N} text rows do not split into {Cn} classes of {Pb} prompts and at least max(2, {Pb}) no-class prompts")
+    if losses is None:
+        losses = torch.empty(3, dtype=torch.float32, device=text.device)
+    else:
+        _in_place(losses, torch.float32, "proda_head: losses must be a contiguous fp32 tensor on the GPU", numel=3)
+    d_text = torch.empty_like(text)
+    ws = torch.empty(max(lib.clipmi_proda_head_workspace_bytes(B, E, Cn, Pb, P), 8), dtype=torch.uint8, device=text.device)
+    check(lib.clipmi_proda_head(features.data_ptr(), features.stride(0), labels.data_ptr(), text.data_ptr(), B, E, Cn, Pb, P, float(scale),
+                                float(grad_scale), float(alpha), losses.data_ptr(), d_text.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+          "clipmi_proda_head")
+    return losses, d_text
+
+
+def proda_ctx_step(d_embed: torch.Tensor, sel: torch.Tensor, pos: torch.Tensor, name_lens: torch.Tensor, n_ctx: int, grad_scale: float,
+                   ctx: Optional[torch.Tensor] = None, buf: Optional[torch.Tensor] = None, lr: Optional[torch.Tensor] = None, first_step: bool = False,
+                   momentum: float = 0.0, dampening: float = 0.0, weight_decay: float = 0.0, nesterov: bool = False,
+                   want_grad: bool = True) -> Optional[torch.Tensor]:
+    """The gradient of ProDA's contexts [P, n_ctx, D] from ``d_embed`` fp32 [(C * Pb + P) * L, D]: for a selected context the classes'
+    rows in ascending order, then -- for every context -- its no-class prompt's row, divided by ``grad_scale``; with ``ctx``,
+    torch.optim.SGD's step on it in place as ``ctx_step`` takes it.  ``sel`` [Pb], ``pos`` [P], ``name_lens`` [C]: int32 on the device.
+    Returns the gradient when ``want_grad``."""
+    d_embed = _dev(d_embed, "d_embed", (torch.float32,))
+    sel, pos, name_lens = (_dev(t, n, (torch.int32,)) for t, n in ((sel, "sel"), (pos, "pos"), (name_lens, "name_lens")))
+    Pb, P, Cn = int(sel.numel()), int(pos.numel()), int(name_lens.numel())
+    N = Cn * Pb + P
+    if d_embed.dim() != 2 or d_embed.shape[0] % N:
+        raise ValueError(f"proda_ctx_step: d_embed {tuple(d_embed.shape)} does not split into {N} prompts")
+    L = d_embed.shape[0] // N
+    # the no-class prompts are the last P of the N: to _ctx_step_inputs they are P prompts with one context each
+    _, D, _, pc, pb, pl = _ctx_step_inputs("proda_ctx_step", d_embed[(N - P) * L:], P, n_ctx, True, ctx, buf, lr)
+    grad = torch.empty(P, int(n_ctx), D, dtype=torch.float32, device=d_embed.device) if want_grad else None
+    check(lib.clipmi_proda_ctx_step(d_embed.data_ptr(), pc, pb, None if grad is None else grad.data_ptr(), sel.data_ptr(), pos.data_ptr(),
+                                    name_lens.data_ptr(), Cn, Pb, P, L, D, int(n_ctx), float(grad_scale), pl, int(bool(first_step)), float(momentum),
+                                    float(dampening), float(weight_decay), int(bool(nesterov)), _stream()), "clipmi_proda_ctx_step")
+    return grad

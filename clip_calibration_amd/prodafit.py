@@ -1,0 +1,382 @@
+"""ProDA's collection of contexts trained on the GPU (reference trainers/classification/proda.py:76-228, 258-304).
+
+ProDA learns ``n_prompt`` contexts ``ctx`` [P, n_ctx, D].  Context p puts the class name in front of its vectors (p < P // 4), in their
+middle (P // 4 <= p < 2 (P // 4)) or behind them (the rest).  A training step draws ``prompt_bs`` = Pb of them, runs the frozen text
+tower on the C Pb class prompts -- class-major, a class's prompts ordered end | middle | front -- and on the P no-class prompts
+``[SOS | ctx_p | '.' EOT]``, and takes one ``torch.optim.SGD`` step on the whole ``ctx`` for
+
+    loss = CE(s x_b . m_c + 0.5 s^2 sigma[b, c], y) + alpha mean_{p != q} |n_p . n_q|
+
+with m_c the mean of a class's normalised features, sigma the image-weighted variance of the difference to the label's class around
+those means, and n_p the normalised no-class features (include/clipmi.h and DESIGN.md "ProDA fit" have the formulas).  csrc/proda_train.hip
+has the prompt assembly, that head with its backward and the gather-reduce of the tower's input gradient back into ``ctx`` with the
+optimiser's rule; between them runs the frozen-tower forward and backward of csrc/text_backward.hip that CoOp trains on, once, over
+N = C Pb + P prompts.  The contexts outside a step's selection still receive the no-class term's gradient, weight decay and momentum.
+
+The entry points mirror ``coopfit``'s: ``context_gradient`` (one batch's loss parts and gradient; the tests' diagnostic entry),
+``ProDAFitState.step`` (one batch of image features at a time) and ``fit_context`` (cached features, every step enqueued, one
+synchronisation at the end).  The selection schedule is the reference's, drawn on the HOST from a ``torch.Generator``: a fresh
+``randperm(P)`` every P / Pb steps, consumed in slices of Pb (the reference draws on the device from the global generator; the stream
+of numbers differs, the scheme does not).
+
+Refused: ``n_prompt`` that is no multiple of 4 (the reference's position list then has fewer than ``n_prompt`` entries and indexing it
+fails; with one prompt the no-class loss is the mean of nothing), ``n_prompt`` that is no multiple of ``prompt_bs``, models with deep
+prompts, more than 80 live token rows (the backward's limit).
+
+UNVERIFIED, as for CoOp: Dassl is not part of this environment, so the defaults -- SGD at 0.002 with momentum 0.9 and weight decay 5e-4,
+batches of 32, 32 prompts in slices of 4, 16 context vectors from N(0, 0.02^2), alpha = 0.1 -- restate the reference's configs and
+Dassl's public defaults without a run of the reference behind them; each is an argument.  Not covered: the reference's ``amp`` branch
+and ``nn.DataParallel`` over the text encoder (one process drives one GPU).
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+from typing import Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import _lib, ops
+from ._lib import check, lib
+from .coopfit import DEFAULT_GRAD_SCALE, MAX_LIVE_ROWS, _DT, _Tower, _check_batch, _check_grad_scale, _check_sgd, _live_rows, _master_ctx
+from .taskresfit import _host_int_array, _labels, _need_gpu
+from .tempfit import cosine_warmup_schedule, steps_per_epoch
+
+
+def positions(n_prompt: int) -> np.ndarray:
+    """proda.py:110-114: 0 (front) for the first quarter, 1 (middle) for the second, 2 (end) for the rest."""
+    q = n_prompt // 4
+    return np.array([0] * q + [1] * q + [2] * (n_prompt - 2 * q), np.int32)
+
+
+def reference_order(sel, pos: np.ndarray) -> np.ndarray:
+    """``sel`` as the reference's forward orders a class's prompts: the end-position contexts, then the middle, then the front ones, the
+    order inside a group kept (proda.py:167-213)."""
+    sel = np.asarray(sel, np.int64)
+    return np.concatenate([sel[pos[sel] == k] for k in (2, 1, 0)]).astype(np.int32)
+
+
+def draw_selections(n_prompt: int, prompt_bs: int, steps: int, generator: torch.Generator) -> np.ndarray:
+    """The reference's schedule (proda.py:148-157) for ``steps`` steps, int32 [steps, prompt_bs]: a ``randperm(n_prompt)`` from
+    ``generator`` every n_prompt / prompt_bs steps, consumed in slices of ``prompt_bs``, each slice in ``reference_order``.  With
+    ``prompt_bs == n_prompt`` nothing is drawn: every step uses all contexts in their natural order."""
+    pos, n_iter = positions(n_prompt), n_prompt // prompt_bs
+    out = np.empty((steps, prompt_bs), np.int32)
+    perm = None
+    for k in range(steps):
+        if n_iter == 1:
+            batch = np.arange(n_prompt)
+        else:
+            if k % n_iter == 0:
+                perm = torch.randperm(n_prompt, generator=generator).numpy()
+            batch = perm[(k % n_iter) * prompt_bs:(k % n_iter + 1) * prompt_bs]
+        out[k] = reference_order(batch, pos)
+    return out
+
+
+def _check_collection(who: str, n_prompt: int, prompt_bs: int) -> None:
+    if n_prompt < 4 or n_prompt % 4:
+        raise ValueError(f"{who}: n_prompt={n_prompt} must be a positive multiple of 4: the reference's position list [front] * (n // 4) + [middle] * (n // 4) "
+                         "+ [end] * (n // 2) has fewer than n_prompt entries otherwise, and with one prompt the no-class loss is the mean of nothing")
+    if prompt_bs < 1 or n_prompt % prompt_bs:
+        raise ValueError(f"{who}: prompt_bs={prompt_bs} must divide n_prompt={n_prompt}")
+
+
+def _check_alpha(who: str, alpha: float) -> float:
+    if not (math.isfinite(alpha) and alpha >= 0.0):
+        raise ValueError(f"{who}: alpha={alpha} (finite, >= 0)")
+    return float(alpha)
+
+
+def _check_sel(who: str, sel, P: int, pos: np.ndarray, name: str = "sel") -> np.ndarray:
+    """One selection [Pb] or a schedule [steps, Pb] in the reference's order, after the range and repeat checks."""
+    a = _host_int_array(sel, name)
+    if a.ndim not in (1, 2) or a.shape[-1] < 1 or P % a.shape[-1]:
+        raise ValueError(f"{who}: {name} {a.shape} must hold prompt_bs indices (a divisor of n_prompt={P}) per step")
+    if a.size and (a.min() < 0 or a.max() >= P):
+        raise ValueError(f"{who}: {name} holds indices outside the {P} contexts [0, {P})")
+    rows = a.reshape(-1, a.shape[-1])
+    if any(len(set(r.tolist())) != len(r) for r in rows):
+        raise ValueError(f"{who}: {name} names a context twice in one step")
+    out = np.stack([reference_order(r, pos) for r in rows]) if len(rows) else np.zeros((0, a.shape[-1]), np.int32)
+    return out[0] if a.ndim == 1 else out
+
+
+def _check_prompts(who: str, clip_model, tokenized_prompts, ctx, name_lens, seq_rows):
+    """(ids with the no-class prompt appended [C + 1, Lc], C, P, n_ctx, name_lens int32 [C], last EOT) after the host-side checks."""
+    L, D = int(clip_model.context_length), int(clip_model.ln_final.weight.shape[0])
+    if getattr(clip_model, "ivlp_text_prompts", None) is not None and clip_model.ivlp_text_prompts()[0]:
+        raise ValueError(f"{who}: the model's text tower carries deep prompts; the training forward does not support them")
+    ids = _host_int_array(tokenized_prompts, "tokenized_prompts")
+    if ids.ndim != 2 or ids.shape[1] != L or ids.shape[0] < 2:
+        raise ValueError(f"{who}: tokenized_prompts {ids.shape} must be [C >= 2, {L}]")
+    if not isinstance(ctx, torch.Tensor) or ctx.dim() != 3 or ctx.shape[-1] != D or not ctx.dtype.is_floating_point:
+        raise ValueError(f"{who}: ctx {tuple(getattr(ctx, 'shape', ()))} must be [n_prompt, n_ctx, {D}]")
+    P, n_ctx = int(ctx.shape[0]), int(ctx.shape[1])
+    eot = ids.argmax(axis=1)
+    if n_ctx < 1 or int(eot.min()) < n_ctx + 2:
+        raise ValueError(f"{who}: n_ctx={n_ctx} does not fit the prompts (first EOT at {int(eot.min())}): the layout is [SOS | X * n_ctx | name | '.' | EOT]")
+    own = eot - n_ctx - 2
+    if name_lens is None:
+        nl = own
+    else:
+        nl = _host_int_array(name_lens, "name_lens")
+        if nl.shape != (ids.shape[0],):
+            raise ValueError(f"{who}: name_lens {nl.shape} must hold one length per class ({ids.shape[0]})")
+        if nl.min() < 0:
+            raise ValueError(f"{who}: name_lens holds a negative length")
+        if (nl > own).any():
+            c = int(np.argmax(nl > own))
+            raise ValueError(f"{who}: name_lens[{c}]={int(nl[c])} pushes a context row past the live rows of its prompt (EOT at {int(eot[c])}, n_ctx={n_ctx}: at "
+                             f"most {int(own[c])})")
+    last = int(eot.max())
+    if seq_rows is not None and int(seq_rows) and int(seq_rows) <= last:
+        raise ValueError(f"{who}: seq_rows={int(seq_rows)} cuts the EOT row {last}")
+    live = _live_rows(clip_model, last, seq_rows) or L
+    if live > MAX_LIVE_ROWS:
+        raise ValueError(f"{who}: seq_rows gives {live} live token rows per prompt; the backward holds at most {MAX_LIVE_ROWS}")
+    # the no-class prompt "X .. X ." from a class prompt with its name taken out: [SOS, X * n_ctx, '.', EOT, 0 ..]
+    c0 = int(np.argmin(own))
+    nc = np.zeros((1, L), ids.dtype)
+    nc[0, :1 + n_ctx] = ids[c0, :1 + n_ctx]
+    nc[0, 1 + n_ctx:L - int(own[c0])] = ids[c0, 1 + n_ctx + int(own[c0]):]
+    return np.concatenate([ids, nc]), ids.shape[0], P, n_ctx, nl.astype(np.int32), last
+
+
+class _ProDATower(_Tower):
+    """``coopfit._Tower`` over ProDA's N = C Pb + P assembled prompts: ``base`` holds the C class embeddings and, last, the no-class one."""
+
+    def __init__(self, who, clip_model, ids_all, n_cls, P, Pb, n_ctx, name_lens, last_eot, seq_rows):
+        super().__init__(who, clip_model, ids_all, n_cls * Pb + P, n_ctx, False, last_eot, seq_rows)
+        dev = clip_model.device
+        self.n_cls, self.P, self.Pb = n_cls, P, Pb
+        self.N = self.C                       # _Tower sizes workspace, stash, text and d_embed by the number of prompts
+        self.cls_base, self.nc_base = self.base[:n_cls], self.base[n_cls:]
+        self.cls_eot = self.eot[:n_cls].contiguous()      # of the ids: every prompt of a class keeps its class's EOT row
+        self.pos = torch.from_numpy(positions(P)).to(dev)
+        self.name_lens = torch.from_numpy(name_lens).to(dev)
+        self.prompts = torch.empty(self.N, self.Lc, self.D, dtype=torch.float32, device=dev)
+        self.eot = torch.empty(self.N, dtype=torch.int32, device=dev)
+
+    def forward(self, ctx: torch.Tensor, sel: torch.Tensor) -> torch.Tensor:
+        m = self.model
+        ops.proda_embed(self.cls_base, self.nc_base, ctx, sel, self.pos, self.name_lens, self.cls_eot, self.rows, self.prompts, self.eot)
+        with m._launch_lock:
+            check(lib.clipmi_text_encoder_train(m._handle, self.prompts.data_ptr(), _lib.F32, None, 0, 0, self.eot.data_ptr(), self.N, self.rows, None,
+                                                self.text.data_ptr(), self.ws.data_ptr(), self.ws.numel(), self.stash.data_ptr(), self.stash.numel(),
+                                                _lib.CALL_DEFAULT, ops._stream()), "clipmi_text_encoder_train")
+        return self.text
+
+    def one_call_workspace(self, B: int) -> torch.Tensor:
+        need = lib.clipmi_proda_train_step_bytes(self.model._handle, self.n_cls, self.Pb, self.P, self.rows, B)
+        if self.step_ws is None or self.step_ws.numel() < need:
+            self.step_ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.ws.device)
+        return self.step_ws
+
+
+def _scale(logit_scale: float) -> float:
+    return float(np.float32(math.exp(logit_scale)))
+
+
+def context_gradient(clip_model, tokenized_prompts, ctx: torch.Tensor, features: torch.Tensor, labels, sel=None, name_lens=None, alpha: float = 0.1,
+                     logit_scale: float = 4.6052, grad_scale: float = DEFAULT_GRAD_SCALE, seq_rows: Optional[int] = None, return_parts: bool = False):
+    """``(loss, grad)`` of ProDA's training loss (module docstring) with respect to ``ctx`` [P, n_ctx, D] on the GPU: loss fp32 [1], grad
+    fp32 [P, n_ctx, D].  ``tokenized_prompts`` [C, context_length]: the ids of ``"X .. X name."``; ``features`` fp32 [B, E] raw image
+    features (the rows may be a column slice).  ``sel``: the contexts this step uses (None: all of them; any order -- it is put into the
+    reference's end | middle | front order); ``name_lens``: the classes' name lengths in tokens (None: EOT - n_ctx - 2, as the inference
+    mirror derives them; a shorter one moves fewer tokens in front of or between the context vectors, as in the reference, and the
+    EOT row stays the prompt's own).  ``return_parts`` adds a dict: ``upper``, ``m`` (fp32 [1] each), ``text`` (the raw text features fp32
+    [C Pb + P, E], class prompts first) and ``sel`` (int32, as used)."""
+    who = "context_gradient"
+    ids_all, Cn, P, n_ctx, nl, last = _check_prompts(who, clip_model, tokenized_prompts, ctx, name_lens, seq_rows)
+    pos = positions(P)
+    sel_h = _check_sel(who, np.arange(P) if sel is None else sel, P, pos)
+    if sel_h.ndim != 1:
+        raise ValueError(f"{who}: sel {sel_h.shape} must be one selection [prompt_bs]")
+    _check_collection(who, P, len(sel_h))
+    alpha = _check_alpha(who, alpha)
+    gs = _check_grad_scale(who, grad_scale)
+    if not math.isfinite(logit_scale):
+        raise ValueError(f"{who}: logit_scale={logit_scale} (finite)")
+    E = int(clip_model.geometry.embed_dim)
+    lab = _check_batch(who, features, labels, Cn, E)
+    _need_gpu(features, "features")
+    tower = _ProDATower(who, clip_model, ids_all, Cn, P, len(sel_h), n_ctx, nl, last, seq_rows)
+    dev = features.device
+    labels_d = lab if isinstance(lab, torch.Tensor) else torch.from_numpy(lab.astype(np.int64)).to(dev)
+    sel_d = torch.from_numpy(sel_h).to(dev)
+    text = tower.forward(_master_ctx(ctx, dev), sel_d)
+    losses, d_text = ops.proda_head(features, labels_d, text, Cn, len(sel_h), _scale(logit_scale), gs, alpha)
+    d_embed = tower.backward(d_text)
+    grad = ops.proda_ctx_step(d_embed, sel_d, tower.pos, tower.name_lens, n_ctx, gs)
+    if not return_parts:
+        return losses[0:1], grad
+    return losses[0:1], grad, {"upper": losses[1:2], "m": losses[2:3], "text": text.clone(), "sel": sel_d}
+
+
+class ProDAFitState:
+    """The training state of ProDA's contexts: the fp32 master ``ctx`` [P, n_ctx, D], SGD's momentum buffer, the tower's stash, the
+    selection schedule's generator and the number of steps taken.  ``step`` enqueues one forward, backward and update and does not
+    synchronise."""
+
+    def __init__(self, clip_model, tokenized_prompts, ctx: torch.Tensor, prompt_bs: int = 4, alpha: float = 0.1, logit_scale: float = 4.6052,
+                 momentum: float = 0.9, dampening: float = 0.0, nesterov: bool = False, weight_decay: float = 5e-4,
+                 grad_scale: float = DEFAULT_GRAD_SCALE, seq_rows: Optional[int] = None, name_lens=None, generator: Optional[torch.Generator] = None):
+        who = "ProDAFitState"
+        ids_all, self.C, self.P, self.n_ctx, nl, last = _check_prompts(who, clip_model, tokenized_prompts, ctx, name_lens, seq_rows)
+        self.Pb = int(prompt_bs)
+        _check_collection(who, self.P, self.Pb)
+        self.alpha = _check_alpha(who, alpha)
+        self.grad_scale = _check_grad_scale(who, grad_scale)
+        _check_sgd(who, momentum, dampening, weight_decay, nesterov)
+        if not math.isfinite(logit_scale):
+            raise ValueError(f"{who}: logit_scale={logit_scale} (finite)")
+        self.tower = _ProDATower(who, clip_model, ids_all, self.C, self.P, self.Pb, self.n_ctx, nl, last, seq_rows)
+        dev = clip_model.device
+        self.ctx = _master_ctx(ctx, dev)
+        self.buf = torch.zeros_like(self.ctx) if momentum != 0.0 else None
+        self.scale = _scale(logit_scale)
+        self.momentum, self.dampening, self.nesterov, self.weight_decay = momentum, dampening, nesterov, weight_decay
+        self.generator = generator if generator is not None else torch.Generator().manual_seed(0)
+        self.pos_host = positions(self.P)
+        self._perm = None
+        self.steps = 0
+
+    def next_selection(self) -> np.ndarray:
+        """The schedule's next slice (``draw_selections``, one step at a time)."""
+        n_iter = self.P // self.Pb
+        k = self.steps % n_iter
+        if n_iter == 1:
+            return reference_order(np.arange(self.P), self.pos_host)
+        if k == 0 or self._perm is None:
+            self._perm = torch.randperm(self.P, generator=self.generator).numpy()
+        return reference_order(self._perm[k * self.Pb:(k + 1) * self.Pb], self.pos_host)
+
+    def step(self, features: torch.Tensor, labels, lr, sel=None, want_loss: bool = False, one_call: bool = False) -> Optional[torch.Tensor]:
+        """One optimiser step on the batch ``features`` fp32 [B, E] and ``labels`` [B] at the rate ``lr``, as ``CoOpFitState.step`` takes
+        them.  ``sel``: this step's contexts -- None draws the schedule's next slice on the host; an int32 tensor [prompt_bs] on the
+        GPU is taken as it is, already in the reference's order (a bad entry then poisons the context with NaN, it is never an
+        address); anything else is checked and ordered on the host.  ``one_call``: the same launches through
+        clipmi_proda_train_step.  Returns the batch loss, fp32 [1] on the device, when ``want_loss``."""
+        who = "ProDAFitState.step"
+        lab = _check_batch(who, features, labels, self.C, self.tower.E)
+        _need_gpu(features, "features")
+        if features.dtype != torch.float32 or features.stride(1) != 1:
+            raise TypeError(f"{who}: features must be fp32 with unit column stride")
+        dev = features.device
+        if isinstance(sel, torch.Tensor) and sel.is_cuda and sel.dtype == torch.int32:
+            if sel.shape != (self.Pb,):
+                raise ValueError(f"{who}: sel {tuple(sel.shape)} must be [prompt_bs] = [{self.Pb}]")
+            sel_d = sel.contiguous()
+        else:
+            sel_h = self.next_selection() if sel is None else _check_sel(who, sel, self.P, self.pos_host)
+            if sel_h.shape != (self.Pb,):
+                raise ValueError(f"{who}: sel {sel_h.shape} must be [prompt_bs] = [{self.Pb}]")
+            sel_d = torch.from_numpy(sel_h).to(dev)
+        labels_d = lab if isinstance(lab, torch.Tensor) else torch.from_numpy(lab.astype(np.int64)).to(dev)
+        lr_d = ops._dev(lr, "lr", (torch.float32,)) if isinstance(lr, torch.Tensor) else torch.tensor([float(lr)], dtype=torch.float32).to(dev)
+        t, m, first = self.tower, self.tower.model, self.steps == 0
+        sgd = (self.momentum, self.dampening, self.weight_decay, self.nesterov)
+        losses = torch.empty(3, dtype=torch.float32, device=dev)
+        if one_call:
+            ws = t.one_call_workspace(features.shape[0])
+            with m._launch_lock:
+                check(lib.clipmi_proda_train_step(m._handle, C.byref(t.dgrad[0]), t.cls_base.data_ptr(), t.nc_base.data_ptr(), _DT[t.base.dtype],
+                                                  self.ctx.data_ptr(), None if self.buf is None else self.buf.data_ptr(), t.n_ctx, sel_d.data_ptr(),
+                                                  t.pos.data_ptr(), t.name_lens.data_ptr(), t.cls_eot.data_ptr(), t.n_cls, t.Pb, t.P, t.rows, features.data_ptr(),
+                                                  features.stride(0), labels_d.data_ptr(), features.shape[0], self.scale, self.grad_scale, self.alpha,
+                                                  lr_d.data_ptr(), int(first), *map(float, sgd[:3]), int(bool(sgd[3])), losses.data_ptr(), None,
+                                                  ws.data_ptr(), ws.numel(), t.stash.data_ptr(), t.stash.numel(), ops._stream()),
+                      "clipmi_proda_train_step")
+        else:
+            text = t.forward(self.ctx, sel_d)
+            _, d_text = ops.proda_head(features, labels_d, text, t.n_cls, t.Pb, self.scale, self.grad_scale, self.alpha, losses)
+            d_embed = t.backward(d_text)
+            ops.proda_ctx_step(d_embed, sel_d, t.pos, t.name_lens, t.n_ctx, self.grad_scale, self.ctx, self.buf, lr_d, first, *sgd, want_grad=False)
+        self.steps += 1
+        return losses[0:1] if want_loss else None
+
+
+def init_context(clip_model, n_ctx: int = 16, n_prompt: int = 32, seed: int = 0) -> torch.Tensor:
+    """The reference's random initialisation (proda.py:93-94): N(0, 0.02^2), [n_prompt, n_ctx, D]."""
+    D = int(clip_model.ln_final.weight.shape[0])
+    return 0.02 * torch.randn(n_prompt, n_ctx, D, generator=torch.Generator().manual_seed(seed))
+
+
+def fit_context(features: torch.Tensor, labels, clip_model, tokenized_prompts, ctx: Optional[torch.Tensor] = None, n_ctx: int = 16, n_prompt: int = 32,
+                prompt_bs: int = 4, alpha: float = 0.1, logit_scale: float = 4.6052, lr: float = 0.002, epochs: int = 200, batch_size: int = 32,
+                momentum: float = 0.9, dampening: float = 0.0, weight_decay: float = 5e-4, nesterov: bool = False,
+                grad_scale: float = DEFAULT_GRAD_SCALE, seq_rows: Optional[int] = None, lr_per_epoch: Optional[Sequence[float]] = None, order=None,
+                drop_last: bool = False, name_lens=None, selections=None, generator: Optional[torch.Generator] = None, return_history: bool = False):
+    """Train ProDA's contexts on cached ``features`` fp32 [N, E] and ``labels`` [N], starting from ``ctx`` [n_prompt, n_ctx, D] (not
+    modified; None = ``init_context(clip_model, n_ctx, n_prompt)``).  The loop and its arguments are ``coopfit.fit_context``'s:
+    ``epochs`` passes of ``torch.optim.SGD`` over batches of ``batch_size``, ``lr_per_epoch`` (None: ``cosine_warmup_schedule``),
+    ``order`` [epochs, N], ``drop_last``; everything is checked on the host before the first launch and nothing synchronises until the
+    one wait at the end.  ``selections``: an int array [steps, prompt_bs] that replaces the schedule drawn from ``generator`` (None: a
+    generator seeded with 0).  Returns the fitted fp32 contexts on the device, or ``(ctx, per-step total losses)`` with
+    ``return_history``.  The defaults are unverified restatements of the reference's config (module docstring)."""
+    who = "fit_context"
+    if ctx is None:
+        _check_collection(who, int(n_prompt), int(prompt_bs))
+        ctx = init_context(clip_model, n_ctx, n_prompt)
+    _, Cn, P, n_ctx, _, _ = _check_prompts(who, clip_model, tokenized_prompts, ctx, name_lens, seq_rows)
+    _check_collection(who, P, int(prompt_bs))
+    E = int(clip_model.geometry.embed_dim)
+    if not isinstance(features, torch.Tensor) or features.dim() != 2 or features.shape[0] < 1 or features.shape[1] != E:
+        raise ValueError(f"{who}: features must be a [N >= 1, E = {E}] tensor")
+    N = features.shape[0]
+    epochs, batch_size = int(epochs), int(batch_size)
+    if epochs < 0 or batch_size < 1:
+        raise ValueError(f"{who}: epochs={epochs} (>= 0), batch_size={batch_size} (>= 1)")
+    _check_sgd(who, momentum, dampening, weight_decay, nesterov)
+    _check_grad_scale(who, grad_scale)
+    _check_alpha(who, alpha)
+    lab = _labels(who, labels, N, Cn)
+    if order is not None:
+        order = _host_int_array(order, "order")
+        if order.shape != (epochs, N):
+            raise ValueError(f"{who}: order {order.shape} must be [epochs, N] = [{epochs}, {N}]")
+        if order.size and (order.min() < 0 or order.max() >= N):
+            raise ValueError(f"{who}: order holds sample indices outside [0, {N})")
+    rates = cosine_warmup_schedule(lr, epochs) if lr_per_epoch is None else [float(r) for r in lr_per_epoch]
+    if len(rates) != epochs:
+        raise ValueError(f"{who}: {len(rates)} learning rates for {epochs} epochs")
+    per_epoch = steps_per_epoch(N, batch_size, drop_last)
+    steps = epochs * per_epoch
+    if selections is None:
+        sels = draw_selections(P, int(prompt_bs), steps, generator if generator is not None else torch.Generator().manual_seed(0))
+    else:
+        sels = _check_sel(who, selections, P, positions(P), "selections")
+        if sels.ndim != 2 or sels.shape != (steps, int(prompt_bs)):
+            raise ValueError(f"{who}: selections {sels.shape} must be [steps, prompt_bs] = [{steps}, {int(prompt_bs)}]")
+    if steps == 0:
+        out = ctx.detach().to(torch.float32).clone()
+        out = out.to(features.device) if features.is_cuda else out
+        return (out, np.zeros(0, np.float32)) if return_history else out
+    _need_gpu(features, "features")
+    dev = features.device
+    state = ProDAFitState(clip_model, tokenized_prompts, ctx, prompt_bs, alpha, logit_scale, momentum, dampening, nesterov, weight_decay, grad_scale,
+                          seq_rows, name_lens)
+    lr_steps = torch.from_numpy(np.repeat(np.asarray(rates, np.float64), per_epoch).astype(np.float32)).to(dev)
+    labels_d = torch.from_numpy(lab.astype(np.int64)).to(dev)
+    order_d = None if order is None else torch.from_numpy(np.ascontiguousarray(order, dtype=np.int64)).to(dev)
+    sels_d = torch.from_numpy(np.ascontiguousarray(sels, dtype=np.int32)).to(dev)
+    losses = []
+    step = 0
+    for e in range(epochs):
+        for k in range(per_epoch):
+            lo, hi = k * batch_size, min((k + 1) * batch_size, N)
+            if order_d is None:
+                f, y = features[lo:hi], labels_d[lo:hi]
+            else:
+                idx = order_d[e, lo:hi]
+                f, y = features.index_select(0, idx), labels_d.index_select(0, idx)   # index plumbing
+            loss = state.step(f, y, lr_steps[step:step + 1], sel=sels_d[step], want_loss=return_history)
+            if return_history:
+                losses.append(loss)
+            step += 1
+    torch.cuda.current_stream(dev).synchronize()   # the run's one synchronisation
+    if return_history:
+        return state.ctx, torch.cat(losses).cpu().numpy()
+    return state.ctx

@@ -854,6 +854,60 @@ int clipmi_prompt_train_step(clipmi_model* m, const clipmi_text_dgrad* wt, const
                              int nesterov, float* losses, float* grad_out, int* projected, double* dots, void* workspace,
                              size_t workspace_bytes, void* stash, size_t stash_bytes, clipmi_stream_t stream);
 
+/* ProDA's collection of contexts trained on the same frozen-tower backward (reference trainers/classification/proda.py:146-228, 258-304;
+ * csrc/proda_train.hip, DESIGN.md "ProDA fit").  ctx fp32 [P, n_ctx, D] is the master of all P contexts; pos int32 [P] gives each one's
+ * class-token position (0 front, 1 middle, 2 end); a step uses the Pb contexts sel int32 [Pb] names, the caller having put them into
+ * the reference's end | middle | front order; name_lens int32 [C] is every class's name length in tokens.  sel, pos and name_lens live
+ * on the device.  N = C Pb + P prompts go through the tower: prompt c Pb + q is class c with context sel[q], prompt C Pb + p the
+ * no-class prompt [SOS | ctx_p | '.' EOT] of context p.  These exports are additive: the ABI version does not change with them.
+ *
+ * clipmi_proda_embed: the N prompts as fp32 embeddings [N, Lc, D] (rows [0, L) of each written, L <= Lc the live rows; the positional
+ *   embedding is the tower's to add) and their EOT indices int32 [N] (cls_eot[c], int32 [C] on the device, for every prompt of class c,
+ *   whatever its position and name length -- the reference takes it from the token ids; n_ctx + 2 for a no-class prompt).  base
+ *   [C, Lc, D] and nc_base [1, Lc, D] (dtype: CLIPMI_F16 or CLIPMI_F32) are the token embeddings of "X .. X name ." and of "X .. X .".
+ *   With nl the name length and h = n_ctx / 2, context vector j sits on row 1 + j (end), 1 + nl + j (front), or 1 + j for j < h and
+ *   1 + nl + j otherwise (middle); the name tokens take the rows left free in [1, 1 + n_ctx + nl); every other row is the base's.  A
+ *   context row is copied from the fp32 master unchanged.  A name length is read clamped to [0, L - 3 - n_ctx] and a selection outside
+ *   [0, P) poisons its prompts with NaN: neither is used as an address.  One launch.  16-byte aligned pointers, D a multiple of 4.
+ *   The tower then runs on it unchanged: clipmi_text_encoder_train(m, prompts, CLIPMI_F32, NULL, 0, 0, eot, N, seq_rows, ...).
+ *
+ * clipmi_proda_head: text fp32 [N, E] the tower's raw features.  x_b = unit(feats_b), u_{c,q} = unit(text_{c Pb + q}), m_c = mean_q u_{c,q},
+ *   v = u - m, s = scale, n_p = unit(text_{C Pb + p}):
+ *     z[b,c] = s x_b . m_c + 0.5 s^2 / (Pb + 1) sum_q sum_e x_be^2 (v_{y_b,q,e} - v_{c,q,e})^2;   upper = CE(z, y);
+ *     m = mean_{p != q} |n_p . n_q| over all P contexts;   losses fp32 [3] = {upper + alpha m, upper, m}
+ *   (upper the float64 mean of the fp32 row losses, m a float64 mean in a fixed order, the total in fp32).  d_text fp32 [N, E] =
+ *   grad_scale d total / d text, ready for clipmi_text_encoder_backward.  The [E, C, C] covariance of the reference is never formed.
+ *   A label outside [0, C) makes upper, the total and the class rows of d_text NaN and is never used as an address.  alpha finite, >= 0;
+ *   alpha == 0 leaves exact zeros in the no-class rows of d_text.  Seven launches, no float atomics, fixed summation orders.  workspace
+ *   (8-byte aligned): clipmi_proda_head_workspace_bytes(B, E, C, Pb, P) bytes (0 for a bad argument).
+ *
+ * clipmi_proda_ctx_step: d_embed fp32 [N L, D] as the backward wrote it.  The gradient of ctx[p, j, :] is, if p == sel[q], the sum over
+ *   c = 0 .. C-1 (ascending) of the row of prompt c Pb + q that holds context vector j, plus -- always, and last -- row 1 + j of the
+ *   no-class prompt C Pb + p; times 1 / grad_scale.  Then clipmi_ctx_step's SGD rule with the same arguments; grad_out (ctx's shape, may
+ *   be NULL) receives the gradient; ctx == NULL: only grad_out is written.  One launch, no atomics.
+ *
+ * clipmi_proda_train_step: the three above around clipmi_text_encoder_train and clipmi_text_encoder_backward as ONE call on `stream`
+ *   -- the same launches, the same bits as the calls one by one.  workspace of clipmi_proda_train_step_bytes(...) bytes (256-byte
+ *   aligned), stash as clipmi_text_train_bytes(m, C Pb + P, seq_rows, ...) reports it.  At most 80 live rows (the backward's limit).
+ *   Every argument check of the five stages is made before the first launch: a refused call enqueues nothing. */
+int clipmi_proda_embed(const void* base, const void* nc_base, int dtype, const float* ctx, const int32_t* sel, const int32_t* pos,
+                       const int32_t* name_lens, const int32_t* cls_eot, float* prompts, int32_t* eot, int C, int Pb, int P, int L, int Lc, int D, int n_ctx,
+                       clipmi_stream_t stream);
+size_t clipmi_proda_head_workspace_bytes(int B, int E, int C, int Pb, int P);
+int clipmi_proda_head(const float* feats, int64_t ld, const int64_t* labels, const float* text, int B, int E, int C, int Pb, int P,
+                      float scale, float grad_scale, float alpha, float* losses, float* d_text, void* workspace, size_t workspace_bytes,
+                      clipmi_stream_t stream);
+int clipmi_proda_ctx_step(const float* d_embed, float* ctx, float* buf, float* grad_out, const int32_t* sel, const int32_t* pos,
+                          const int32_t* name_lens, int C, int Pb, int P, int L, int D, int n_ctx, float grad_scale, const float* lr,
+                          int first_step, float momentum, float dampening, float weight_decay, int nesterov, clipmi_stream_t stream);
+size_t clipmi_proda_train_step_bytes(const clipmi_model* m, int C, int Pb, int P, int seq_rows, int B);
+int clipmi_proda_train_step(clipmi_model* m, const clipmi_text_dgrad* wt, const void* base, const void* nc_base, int dtype, float* ctx,
+                            float* buf, int n_ctx, const int32_t* sel, const int32_t* pos, const int32_t* name_lens, const int32_t* cls_eot, int C, int Pb,
+                            int P, int seq_rows, const float* feats, int64_t ld, const int64_t* labels, int B, float scale, float grad_scale,
+                            float alpha, const float* lr, int first_step, float momentum, float dampening, float weight_decay,
+                            int nesterov, float* losses, float* grad_out, void* workspace, size_t workspace_bytes, void* stash,
+                            size_t stash_bytes, clipmi_stream_t stream);
+
 /* Timing aid for bench.py (the per-kernel roofline of its JSON line): the five launches of the vision tower's residual
  * block 0 -- 0 in-proj, 1 attention, 2 out-proj + residual, 3 c_fc + QuickGELU, 4 c_proj + residual (clip/model.py:181-188)
  * -- issued exactly as clipmi_encode_image issues them (LayerNorm fold, fp16 stream, tile selection) on the operands the
