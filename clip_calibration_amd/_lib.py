@@ -194,6 +194,17 @@ _SIGNATURES = {
     "clipmi_proda_train_step_bytes": (_sz, [_vp, _i, _i, _i, _i, _i]),
     "clipmi_proda_train_step": (_i, [_vp, C.POINTER(TextDgrad), _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i64, _vp, _i, _f, _f,
                                      _f, _vp, _i, _f, _f, _f, _i, _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
+    "clipmi_cocoop_block_floats": (_sz, [_i, _i, _i, _i]),
+    "clipmi_cocoop_meta": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "clipmi_cocoop_embed": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "clipmi_cocoop_head_workspace_bytes": (_sz, [_i, _i]),
+    "clipmi_cocoop_head": (_i, [_vp, _i64, _vp, _vp, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "clipmi_cocoop_reduce_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "clipmi_cocoop_reduce": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _sz, _vp]),
+    "clipmi_cocoop_step": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _f, _f, _f, _i, _vp]),
+    "clipmi_cocoop_train_step_bytes": (_sz, [_vp, _i, _i, _i, _i, _i]),
+    "clipmi_cocoop_train_step": (_i, [_vp, C.POINTER(TextDgrad), _vp, _i, _vp, _vp, _i, _i, _vp, _i, _i, _vp, _i64, _vp, _i, _f, _f, _vp, _i, _f, _f, _f, _i,
+                                      _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
     "clipmi_order_stats_workspace_bytes": (_sz, [_i, _i]),
     "clipmi_order_stats": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
     "clipmi_group_gap_accumulate": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _vp]),

@@ -1,0 +1,320 @@
+"""CoCoOp's context and meta-net trained on the GPU (reference trainers/classification/cocoop.py:71-202, 259-278).
+
+CoCoOp learns ``ctx`` [n_ctx, D] and ``meta_net`` = Linear(E, H) - ReLU - Linear(H, D) (H = E // 16 in the reference).  Every image gets
+its own context ``ctx + meta_net(x_b)``, x_b its normalised feature, hence its own C prompts: a step runs the frozen text tower on
+N = B C prompts, takes the cross-entropy of ``exp(logit_scale) x_b . u_{b,c}`` per image and one ``torch.optim.SGD`` step on the five
+tensors, all with one set of hyper-parameters (the reference hands the whole prompt learner to one optimiser: weight decay falls on the
+biases too).  The image tower is frozen, and the learned tensors reach the loss only through the text tower's input rows, so the step
+stands on the frozen-tower forward and backward of csrc/text_backward.hip that CoOp trains on, once over the N prompts.  Around them,
+csrc/cocoop_train.hip: the meta-net's forward with its ReLU output and the unit features kept, the fp32 prompt assembly, the per-pair
+loss head, the reduce of the tower's input gradient into the five gradients, and one SGD launch over one contiguous fp32 master block
+``[ctx | W1 | b1 | W2 | b2]`` (include/clipmi.h and DESIGN.md "CoCoOp fit" have the formulas).
+
+The entry points mirror ``coopfit``'s and ``prodafit``'s: ``gradients`` (one batch's loss and the five gradients; the tests' diagnostic
+entry), ``CoCoOpFitState.step`` (one batch of image features at a time) and ``fit_prompt_learner`` (cached features, every step
+enqueued, one synchronisation at the end).  The five tensors travel as a dict under the names of the reference's ``state_dict``:
+``ctx`` and ``meta_net.linear{1,2}.{weight,bias}``.
+
+Refused: a class-specific context, models with deep prompts, more than 80 live token rows (the backward's limit), a meta-net whose
+shapes do not chain.
+
+UNVERIFIED, as for CoOp: Dassl is not part of this environment, so the defaults -- SGD at 0.002, batches of 1, 10 epochs, 4 context
+vectors (``CTX_INIT "a photo of a"`` in the shipped config) -- restate the reference's config and Dassl's public defaults without a run of
+the reference behind them; each is an argument.  Not covered: the reference's ``amp`` branch, ``nn.DataParallel`` over the text encoder
+(one process drives one GPU), class-token positions other than ``end``.
+"""
+from __future__ import annotations
+
+import collections
+import ctypes as C
+import math
+from typing import Dict, Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import _lib, ops
+from ._lib import check, lib
+from .coopfit import MAX_LIVE_ROWS, _DT, _Tower, _check_batch, _check_grad_scale, _check_sgd, _live_rows
+from .coopfit import _check_prompts as _check_coop_prompts
+from .taskresfit import _host_int_array, _labels, _need_gpu
+from .tempfit import cosine_warmup_schedule, steps_per_epoch
+
+# 2^10, measured on the ViT-B/16 text geometry with synthetic weights at the reference's batch of 1 (profiles/cocoopfit_parity.txt,
+# "grad_scale"): with one image dz is not divided down by a batch, and CoOp's 2^12 leaves the largest fp16 dgrad-GEMM operand only 2^1.9
+# below fp16's largest value; 2^10 leaves 2^3.9.  A model whose gradients are much larger overflows fp16 at this scale -- the parameters
+# then turn NaN, they do not go wrong silently; pass a smaller power of two.
+DEFAULT_GRAD_SCALE = 1024.0
+
+NAMES = ("ctx", "meta_net.linear1.weight", "meta_net.linear1.bias", "meta_net.linear2.weight", "meta_net.linear2.bias")
+
+
+def _check_params(who: str, clip_model, params) -> int:
+    """The hidden width H after the shape checks of the five tensors against the model."""
+    if not isinstance(params, dict) or any(k not in params for k in NAMES):
+        raise ValueError(f"{who}: params must be a dict with the keys {NAMES}")
+    for k in NAMES:
+        if not isinstance(params[k], torch.Tensor) or not params[k].dtype.is_floating_point:
+            raise ValueError(f"{who}: params[{k!r}] must be a floating-point tensor")
+    D, E = int(clip_model.ln_final.weight.shape[0]), int(clip_model.geometry.embed_dim)
+    ctx, w1, b1, w2, b2 = (params[k] for k in NAMES)
+    if ctx.dim() != 2:
+        raise ValueError(f"{who}: ctx {tuple(ctx.shape)} must be [n_ctx, {D}]: CoCoOp has no class-specific context")
+    H = int(w1.shape[0]) if w1.dim() == 2 else 0
+    if w1.dim() != 2 or w1.shape[1] != E or not 1 <= H <= 4096 or tuple(b1.shape) != (H,) or tuple(w2.shape) != (D, H) or tuple(b2.shape) != (D,):
+        raise ValueError(f"{who}: meta_net shapes W1 {tuple(w1.shape)}, b1 {tuple(b1.shape)}, W2 {tuple(w2.shape)}, b2 {tuple(b2.shape)} must be "
+                         f"[H, {E}], [H], [{D}, H], [{D}] with 1 <= H <= 4096")
+    return H
+
+
+def _check_prompts(who: str, clip_model, tokenized_prompts, params, seq_rows):
+    """(C, n_ctx, H, last EOT) after the host-side checks."""
+    H = _check_params(who, clip_model, params)
+    Cn, n_ctx, _, last = _check_coop_prompts(who, clip_model, tokenized_prompts, params["ctx"])
+    if seq_rows is not None and int(seq_rows) and int(seq_rows) <= last:
+        raise ValueError(f"{who}: seq_rows={int(seq_rows)} cuts the EOT row {last}")
+    live = _live_rows(clip_model, last, seq_rows) or int(clip_model.context_length)
+    if live > MAX_LIVE_ROWS:
+        raise ValueError(f"{who}: seq_rows gives {live} live token rows per prompt; the backward holds at most {MAX_LIVE_ROWS}")
+    return Cn, n_ctx, H, last
+
+
+def _master_block(params, n_ctx: int, D: int, E: int, H: int, dev) -> torch.Tensor:
+    """The five tensors as one contiguous fp32 block on the device (a copy)."""
+    layout, total = ops.cocoop_block_layout(n_ctx, D, E, H)
+    block = torch.empty(total, dtype=torch.float32, device=dev)
+    for k, (off, shape) in layout.items():
+        block[off:off + params[k].numel()].copy_(params[k].detach().reshape(-1))
+    return block
+
+
+class _CoCoOpTower(_Tower):
+    """``coopfit._Tower`` over CoCoOp's N = B C assembled prompts of one batch size, with the meta-net's kept outputs."""
+
+    def __init__(self, who, clip_model, tokenized_prompts, n_cls, B, n_ctx, H, last_eot, seq_rows):
+        super().__init__(who, clip_model, tokenized_prompts, n_cls * B, n_ctx, False, last_eot, seq_rows)
+        dev = clip_model.device
+        self.n_cls, self.B, self.H = n_cls, B, H
+        self.N = self.C                       # _Tower sizes workspace, stash, text and d_embed by the number of prompts
+        self.cls_eot = self.eot               # of the ids: every image's prompt of a class keeps the class's EOT row
+        self.prompts = torch.empty(self.N, self.Lc, self.D, dtype=torch.float32, device=dev)
+        self.eot = torch.empty(self.N, dtype=torch.int32, device=dev)
+        self.meta = tuple(torch.empty(B, n, dtype=torch.float32, device=dev) for n in (self.E, H, self.D))     # x_n, hid, pi
+        self.grad = torch.empty(lib.clipmi_cocoop_block_floats(n_ctx, self.D, self.E, H), dtype=torch.float32, device=dev)
+
+    def forward(self, views: Dict[str, torch.Tensor], features: torch.Tensor) -> torch.Tensor:
+        m = self.model
+        ops.cocoop_meta(features, *(views[k] for k in NAMES[1:]), out=self.meta)
+        ops.cocoop_embed(self.base, views["ctx"], self.meta[2], self.cls_eot, self.rows, self.prompts, self.eot)
+        with m._launch_lock:
+            check(lib.clipmi_text_encoder_train(m._handle, self.prompts.data_ptr(), _lib.F32, None, 0, 0, self.eot.data_ptr(), self.N, self.rows, None,
+                                                self.text.data_ptr(), self.ws.data_ptr(), self.ws.numel(), self.stash.data_ptr(), self.stash.numel(),
+                                                _lib.CALL_DEFAULT, ops._stream()), "clipmi_text_encoder_train")
+        return self.text
+
+    def reduce(self, d_embed: torch.Tensor, w2: torch.Tensor, grad_scale: float) -> torch.Tensor:
+        return ops.cocoop_reduce(d_embed, self.meta[0], self.meta[1], w2, self.n_cls, self.n_ctx, grad_scale, self.grad)
+
+    def one_call_workspace(self) -> torch.Tensor:
+        need = lib.clipmi_cocoop_train_step_bytes(self.model._handle, self.n_cls, self.rows, self.B, self.H, self.n_ctx)
+        if need == 0:
+            raise ValueError(f"cocoopfit: {self.N} prompts are more than the tower takes in one call")
+        if self.step_ws is None or self.step_ws.numel() < need:
+            self.step_ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.ws.device)
+        return self.step_ws
+
+
+def _scale(logit_scale: float) -> float:
+    return float(np.float32(math.exp(logit_scale)))
+
+
+def gradients(clip_model, tokenized_prompts, params, features: torch.Tensor, labels, logit_scale: float = 4.6052,
+              grad_scale: float = DEFAULT_GRAD_SCALE, seq_rows: Optional[int] = None, return_parts: bool = False, return_operand_stats: bool = False):
+    """``(loss, grads)`` of CoCoOp's training loss (module docstring) on the GPU: loss fp32 [1], grads a dict of the five fp32 gradients
+    under the names of ``params`` (the reference's ``state_dict`` names).  ``tokenized_prompts`` [C, context_length]: the ids of
+    ``"X .. X name."``; ``features`` fp32 [B, E] raw image features (the rows may be a column slice).  ``return_parts`` adds a dict:
+    ``text`` (raw text features fp32 [B C, E]), ``x_n``, ``hid``, ``pi`` and the row losses ``rows``; ``return_operand_stats`` the
+    dict ``coopfit.context_gradient`` returns."""
+    who = "gradients"
+    Cn, n_ctx, H, last = _check_prompts(who, clip_model, tokenized_prompts, params, seq_rows)
+    gs = _check_grad_scale(who, grad_scale)
+    if not math.isfinite(logit_scale):
+        raise ValueError(f"{who}: logit_scale={logit_scale} (finite)")
+    E = int(clip_model.geometry.embed_dim)
+    lab = _check_batch(who, features, labels, Cn, E)
+    _need_gpu(features, "features")
+    if features.dtype != torch.float32 or features.stride(1) != 1:
+        raise TypeError(f"{who}: features must be fp32 with unit column stride")
+    tower = _CoCoOpTower(who, clip_model, tokenized_prompts, Cn, features.shape[0], n_ctx, H, last, seq_rows)
+    dev = features.device
+    labels_d = lab if isinstance(lab, torch.Tensor) else torch.from_numpy(lab.astype(np.int64)).to(dev)
+    views = ops.cocoop_block_views(_master_block(params, n_ctx, tower.D, E, H, dev), n_ctx, tower.D, E, H)
+    text = tower.forward(views, features)
+    loss, d_text, rows = ops.cocoop_head(features, labels_d, text, _scale(logit_scale), gs, want_rows=True)
+    stats = torch.zeros(4, dtype=torch.int64, device=dev) if return_operand_stats else None
+    d_embed = tower.backward(d_text, stats)
+    grads = {k: v.clone() for k, v in ops.cocoop_block_views(tower.reduce(d_embed, views[NAMES[3]], gs), n_ctx, tower.D, E, H).items()}
+    out = (loss, grads)
+    if return_parts:
+        out += ({"text": text.clone(), "x_n": tower.meta[0].clone(), "hid": tower.meta[1].clone(), "pi": tower.meta[2].clone(), "rows": rows},)
+    if return_operand_stats:
+        s = stats.cpu().numpy()
+        top = float(np.array([int(s[3])], dtype=np.uint16).view(np.float16)[0])
+        out += ({"elements": int(s[0]), "zeros": int(s[1]), "subnormals": int(s[2]), "max": top},)
+    return out
+
+
+class CoCoOpFitState:
+    """The training state of CoCoOp's prompt learner: the fp32 master block ``[ctx | W1 | b1 | W2 | b2]``, SGD's momentum block, the
+    tower's stash (one per batch size seen) and the number of steps taken.  ``step`` enqueues one forward, backward and update and does
+    not synchronise."""
+
+    def __init__(self, clip_model, tokenized_prompts, params, logit_scale: float = 4.6052, momentum: float = 0.9, dampening: float = 0.0,
+                 weight_decay: float = 5e-4, nesterov: bool = False, grad_scale: float = DEFAULT_GRAD_SCALE, seq_rows: Optional[int] = None):
+        who = "CoCoOpFitState"
+        self.C, self.n_ctx, self.H, self._last = _check_prompts(who, clip_model, tokenized_prompts, params, seq_rows)
+        self.grad_scale = _check_grad_scale(who, grad_scale)
+        _check_sgd(who, momentum, dampening, weight_decay, nesterov)
+        if not math.isfinite(logit_scale):
+            raise ValueError(f"{who}: logit_scale={logit_scale} (finite)")
+        dev = clip_model.device
+        if dev.type != "cuda":
+            raise RuntimeError(f"clipmi: {who} needs the model on a ROCm GPU (model.to('cuda')); the HIP path has no CPU fallback")
+        self.model, self.ids, self.seq_rows = clip_model, tokenized_prompts, seq_rows
+        self.D, self.E = int(clip_model.ln_final.weight.shape[0]), int(clip_model.geometry.embed_dim)
+        self.block = _master_block(params, self.n_ctx, self.D, self.E, self.H, dev)
+        self.buf = torch.zeros_like(self.block) if momentum != 0.0 else None
+        self._views = ops.cocoop_block_views(self.block, self.n_ctx, self.D, self.E, self.H)
+        self.scale = _scale(logit_scale)
+        self.momentum, self.dampening, self.nesterov, self.weight_decay = momentum, dampening, nesterov, weight_decay
+        self._towers: Dict[int, _CoCoOpTower] = {}
+        self.steps = 0
+
+    def params(self) -> Dict[str, torch.Tensor]:
+        """The five tensors as views of the master block (fp32, on the device), under the reference's ``state_dict`` names."""
+        return collections.OrderedDict(self._views)
+
+    def tower(self, B: int) -> _CoCoOpTower:
+        if B not in self._towers:
+            self._towers[B] = _CoCoOpTower("CoCoOpFitState.step", self.model, self.ids, self.C, B, self.n_ctx, self.H, self._last, self.seq_rows)
+        return self._towers[B]
+
+    def step(self, features: torch.Tensor, labels, lr, want_loss: bool = False, one_call: bool = False) -> Optional[torch.Tensor]:
+        """One optimiser step on the batch ``features`` fp32 [B, E] and ``labels`` [B] at the rate ``lr``, as ``CoOpFitState.step`` takes
+        them (a device scalar is read where it lies; a label tensor on the GPU is taken as it is -- a label outside [0, C) then makes
+        the parameters NaN, it is never used as an address).  ``one_call``: the same launches through clipmi_cocoop_train_step.
+        Returns the batch loss, fp32 [1] on the device, when ``want_loss``."""
+        who = "CoCoOpFitState.step"
+        lab = _check_batch(who, features, labels, self.C, self.E)
+        _need_gpu(features, "features")
+        if features.dtype != torch.float32 or features.stride(1) != 1:
+            raise TypeError(f"{who}: features must be fp32 with unit column stride")
+        dev = features.device
+        labels_d = lab if isinstance(lab, torch.Tensor) else torch.from_numpy(lab.astype(np.int64)).to(dev)
+        lr_d = ops._dev(lr, "lr", (torch.float32,)) if isinstance(lr, torch.Tensor) else torch.tensor([float(lr)], dtype=torch.float32).to(dev)
+        t, m, first = self.tower(int(features.shape[0])), self.model, self.steps == 0
+        sgd = (self.momentum, self.dampening, self.weight_decay, self.nesterov)
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        if one_call:
+            ws = t.one_call_workspace()
+            with m._launch_lock:
+                check(lib.clipmi_cocoop_train_step(m._handle, C.byref(t.dgrad[0]), t.base.data_ptr(), _DT[t.base.dtype], self.block.data_ptr(),
+                                                   None if self.buf is None else self.buf.data_ptr(), t.n_ctx, t.H, t.cls_eot.data_ptr(), t.n_cls, t.rows,
+                                                   features.data_ptr(), features.stride(0), labels_d.data_ptr(), features.shape[0], self.scale,
+                                                   self.grad_scale, lr_d.data_ptr(), int(first), *map(float, sgd[:3]), int(bool(sgd[3])), loss.data_ptr(),
+                                                   None, ws.data_ptr(), ws.numel(), t.stash.data_ptr(), t.stash.numel(), ops._stream()),
+                      "clipmi_cocoop_train_step")
+        else:
+            text = t.forward(self._views, features)
+            _, d_text = ops.cocoop_head(features, labels_d, text, self.scale, self.grad_scale, loss)
+            d_embed = t.backward(d_text)
+            grad = t.reduce(d_embed, self._views[NAMES[3]], self.grad_scale)
+            ops.cocoop_step(grad, self.block, self.buf, lr_d, self.n_ctx, self.D, self.E, self.H, first, *sgd)
+        self.steps += 1
+        return loss if want_loss else None
+
+
+def init_params(clip_model, n_ctx: int = 4, ctx_init_ids: Optional[torch.Tensor] = None, seed: int = 0) -> Dict[str, torch.Tensor]:
+    """The reference's initialisation (cocoop.py:82-108) as fp32 tensors on the host: ``ctx`` from N(0, 0.02^2) [n_ctx, D], or, with
+    ``ctx_init_ids`` (the ids of e.g. "a photo of a", [1, context_length]), the embeddings of its words; ``meta_net`` as ``nn.Linear``
+    initialises Linear(E, E // 16) and Linear(E // 16, D) under ``seed``."""
+    D, E = int(clip_model.ln_final.weight.shape[0]), int(clip_model.geometry.embed_dim)
+    g = torch.Generator().manual_seed(seed)
+    if ctx_init_ids is not None:
+        ids = torch.as_tensor(ctx_init_ids).reshape(1, -1)
+        n = int(ids[0].argmax()) - 1
+        if n < 1:
+            raise ValueError("init_params: ctx_init_ids holds no word between SOS and EOT")
+        with torch.no_grad():
+            ctx = clip_model.token_embedding(ids.to(clip_model.device))[0, 1:1 + n].detach().float().cpu().clone()
+    else:
+        ctx = 0.02 * torch.randn(int(n_ctx), D, generator=g)
+    H = max(E // 16, 1)
+    with torch.random.fork_rng(devices=[]):
+        torch.manual_seed(seed)
+        l1, l2 = torch.nn.Linear(E, H), torch.nn.Linear(H, D)
+    return collections.OrderedDict(zip(NAMES, (ctx, l1.weight.detach().clone(), l1.bias.detach().clone(), l2.weight.detach().clone(),
+                                               l2.bias.detach().clone())))
+
+
+def fit_prompt_learner(features: torch.Tensor, labels, clip_model, tokenized_prompts, params=None, n_ctx: int = 4, logit_scale: float = 4.6052,
+                       lr: float = 0.002, epochs: int = 10, batch_size: int = 1, momentum: float = 0.9, dampening: float = 0.0,
+                       weight_decay: float = 5e-4, nesterov: bool = False, grad_scale: float = DEFAULT_GRAD_SCALE, seq_rows: Optional[int] = None,
+                       lr_per_epoch: Optional[Sequence[float]] = None, order=None, drop_last: bool = False, return_history: bool = False):
+    """Train CoCoOp's prompt learner on cached ``features`` fp32 [N, E] and ``labels`` [N], starting from ``params`` (a dict of the five
+    tensors, not modified; None = ``init_params(clip_model, n_ctx)``).  The loop and its arguments are ``coopfit.fit_context``'s:
+    ``epochs`` passes of ``torch.optim.SGD`` over batches of ``batch_size``, ``lr_per_epoch`` (None: ``cosine_warmup_schedule``),
+    ``order`` [epochs, N], ``drop_last``; everything is checked on the host before the first launch and nothing synchronises until the
+    one wait at the end.  Returns the fitted fp32 tensors on the device as a dict (views of one block), or ``(dict, per-step batch
+    losses)`` with ``return_history``.  The defaults are unverified restatements of the reference's config (module docstring)."""
+    who = "fit_prompt_learner"
+    if params is None:
+        params = init_params(clip_model, n_ctx)
+    Cn, n_ctx, H, _ = _check_prompts(who, clip_model, tokenized_prompts, params, seq_rows)
+    E, D = int(clip_model.geometry.embed_dim), int(clip_model.ln_final.weight.shape[0])
+    if not isinstance(features, torch.Tensor) or features.dim() != 2 or features.shape[0] < 1 or features.shape[1] != E:
+        raise ValueError(f"{who}: features must be a [N >= 1, E = {E}] tensor")
+    N = features.shape[0]
+    epochs, batch_size = int(epochs), int(batch_size)
+    if epochs < 0 or batch_size < 1:
+        raise ValueError(f"{who}: epochs={epochs} (>= 0), batch_size={batch_size} (>= 1)")
+    _check_sgd(who, momentum, dampening, weight_decay, nesterov)
+    _check_grad_scale(who, grad_scale)
+    lab = _labels(who, labels, N, Cn)
+    if order is not None:
+        order = _host_int_array(order, "order")
+        if order.shape != (epochs, N):
+            raise ValueError(f"{who}: order {order.shape} must be [epochs, N] = [{epochs}, {N}]")
+        if order.size and (order.min() < 0 or order.max() >= N):
+            raise ValueError(f"{who}: order holds sample indices outside [0, {N})")
+    rates = cosine_warmup_schedule(lr, epochs) if lr_per_epoch is None else [float(r) for r in lr_per_epoch]
+    if len(rates) != epochs:
+        raise ValueError(f"{who}: {len(rates)} learning rates for {epochs} epochs")
+    per_epoch = steps_per_epoch(N, batch_size, drop_last)
+    if epochs * per_epoch == 0:
+        out = collections.OrderedDict((k, params[k].detach().to(torch.float32).clone().to(features.device if features.is_cuda else "cpu")) for k in NAMES)
+        return (out, np.zeros(0, np.float32)) if return_history else out
+    _need_gpu(features, "features")
+    dev = features.device
+    state = CoCoOpFitState(clip_model, tokenized_prompts, params, logit_scale, momentum, dampening, weight_decay, nesterov, grad_scale, seq_rows)
+    lr_steps = torch.from_numpy(np.repeat(np.asarray(rates, np.float64), per_epoch).astype(np.float32)).to(dev)
+    labels_d = torch.from_numpy(lab.astype(np.int64)).to(dev)
+    order_d = None if order is None else torch.from_numpy(np.ascontiguousarray(order, dtype=np.int64)).to(dev)
+    losses = []
+    step = 0
+    for e in range(epochs):
+        for k in range(per_epoch):
+            lo, hi = k * batch_size, min((k + 1) * batch_size, N)
+            if order_d is None:
+                f, y = features[lo:hi], labels_d[lo:hi]
+            else:
+                idx = order_d[e, lo:hi]
+                f, y = features.index_select(0, idx), labels_d.index_select(0, idx)   # index plumbing
+            loss = state.step(f, y, lr_steps[step:step + 1], want_loss=return_history)
+            if return_history:
+                losses.append(loss)
+            step += 1
+    torch.cuda.current_stream(dev).synchronize()   # the run's one synchronisation
+    if return_history:
+        return state.params(), torch.cat(losses).cpu().numpy()
+    return state.params()

@@ -1127,3 +1127,144 @@ def proda_ctx_step(d_embed: torch.Tensor, sel: torch.Tensor, pos: torch.Tensor, 
                                     name_lens.data_ptr(), Cn, Pb, P, L, D, int(n_ctx), float(grad_scale), pl, int(bool(first_step)), float(momentum),
                                     float(dampening), float(weight_decay), int(bool(nesterov)), _stream()), "clipmi_proda_ctx_step")
     return grad
+
+
+def cocoop_block_layout(n_ctx: int, D: int, E: int, H: int):
+    """The offsets, in floats, of ``ctx | W1 | b1 | W2 | b2`` in CoCoOp's parameter block, and its size: a dict name -> (offset, shape),
+    the names those of the reference's ``state_dict``, and the total (clipmi_cocoop_block_floats)."""
+    n_ctx, D, E, H = int(n_ctx), int(D), int(E), int(H)
+    total = lib.clipmi_cocoop_block_floats(n_ctx, D, E, H)
+    if total == 0:
+        raise ValueError(f"cocoop_block_layout: n_ctx={n_ctx} D={D} E={E} H={H} (all >= 1, H <= 4096)")
+    out, off = collections.OrderedDict(), 0
+    for name, shape in (("ctx", (n_ctx, D)), ("meta_net.linear1.weight", (H, E)), ("meta_net.linear1.bias", (H,)), ("meta_net.linear2.weight", (D, H)),
+                        ("meta_net.linear2.bias", (D,))):
+        out[name] = (off, shape)
+        n = 1
+        for s in shape:
+            n *= s
+        off += n
+    assert off == total
+    return out, total
+
+
+def cocoop_block_views(block: torch.Tensor, n_ctx: int, D: int, E: int, H: int):
+    """The five tensors of a parameter, momentum or gradient block fp32 [clipmi_cocoop_block_floats] as views of it."""
+    layout, total = cocoop_block_layout(n_ctx, D, E, H)
+    if block.numel() != total or block.dim() != 1:
+        raise ValueError(f"cocoop_block_views: a block of {block.numel()} floats, {total} expected")
+    return collections.OrderedDict((k, block[off:off + int(torch.Size(shape).numel())].view(shape)) for k, (off, shape) in layout.items())
+
+
+def cocoop_meta(features: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor, out=None):
+    """CoCoOp's meta-net with what its backward needs kept: ``(x_n fp32 [B, E], hid fp32 [B, H], pi fp32 [B, D])`` for raw image
+    ``features`` fp32 [B, E] (the rows may be a column slice): x = f / |f|, hid = relu(W1 x + b1), pi = W2 hid + b2.  ``out``: the
+    caller's own three tensors, written where they lie."""
+    if not isinstance(features, torch.Tensor) or features.dim() != 2 or features.stride(1) != 1:
+        raise ValueError("cocoop_meta: features must be a [B, E] tensor with unit column stride")
+    if not features.is_cuda or features.dtype != torch.float32:
+        raise TypeError("cocoop_meta: features must be fp32 on the GPU")
+    w1, b1, w2, b2 = (_dev(t, n, (torch.float32,)) for t, n in ((w1, "w1"), (b1, "b1"), (w2, "w2"), (b2, "b2")))
+    B, E = features.shape
+    if w1.dim() != 2 or w2.dim() != 2 or w1.shape[1] != E or b1.shape != (w1.shape[0],) or w2.shape[1] != w1.shape[0] or b2.shape != (w2.shape[0],):
+        raise ValueError(f"cocoop_meta: features {tuple(features.shape)}, W1 {tuple(w1.shape)}, b1 {tuple(b1.shape)}, W2 {tuple(w2.shape)}, b2 "
+                         f"{tuple(b2.shape)} do not agree")
+    H, D = int(w1.shape[0]), int(w2.shape[0])
+    if out is None:
+        out = tuple(torch.empty(B, n, dtype=torch.float32, device=features.device) for n in (E, H, D))
+    else:
+        for t, n in zip(out, (E, H, D)):
+            _in_place(t, torch.float32, "cocoop_meta: x_n, hid and pi must be contiguous fp32 tensors on the GPU", numel=B * n)
+    x_n, hid, pi = out
+    check(lib.clipmi_cocoop_meta(features.data_ptr(), features.stride(0), w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), x_n.data_ptr(),
+                                 hid.data_ptr(), pi.data_ptr(), B, E, H, D, _stream()), "clipmi_cocoop_meta")
+    return x_n, hid, pi
+
+
+def cocoop_embed(base: torch.Tensor, ctx: torch.Tensor, pi: torch.Tensor, cls_eot: torch.Tensor, rows: int = 0, prompts: Optional[torch.Tensor] = None,
+                 eot: Optional[torch.Tensor] = None):
+    """CoCoOp's training prompts: ``(prompts fp32 [B * C, Lc, D], eot int32 [B * C])`` from the class embeddings ``base`` [C, Lc, D] (fp16
+    or fp32), the fp32 master ``ctx`` [n_ctx, D], the images' shifts ``pi`` fp32 [B, D] and the classes' EOT rows ``cls_eot`` int32 [C]:
+    image-major, context rows ``ctx[j] + pi[b]``.  Only the first ``rows`` token rows of each prompt are written (0: all of them).  A
+    caller's own ``prompts`` and ``eot`` are written where they lie."""
+    base = _dev(base, "base", (torch.float16, torch.float32))
+    ctx, pi = _dev(ctx, "ctx", (torch.float32,)), _dev(pi, "pi", (torch.float32,))
+    cls_eot = _dev(cls_eot, "cls_eot", (torch.int32,))
+    if base.dim() != 3 or ctx.dim() != 2 or pi.dim() != 2 or ctx.shape[1] != base.shape[2] or pi.shape[1] != base.shape[2] or cls_eot.shape != (base.shape[0],):
+        raise ValueError(f"cocoop_embed: base {tuple(base.shape)}, ctx {tuple(ctx.shape)}, pi {tuple(pi.shape)} and cls_eot {tuple(cls_eot.shape)} do not agree")
+    Cn, Lc, D = base.shape
+    B, n_ctx = int(pi.shape[0]), int(ctx.shape[0])
+    N = B * Cn
+    L = int(rows) if 0 < int(rows) < Lc else Lc
+    if prompts is None:
+        prompts = torch.empty(N, Lc, D, dtype=torch.float32, device=base.device)
+    else:
+        _in_place(prompts, torch.float32, "cocoop_embed: prompts must be a contiguous fp32 tensor on the GPU", numel=N * Lc * D)
+    if eot is None:
+        eot = torch.empty(N, dtype=torch.int32, device=base.device)
+    else:
+        _in_place(eot, torch.int32, "cocoop_embed: eot must be a contiguous int32 tensor on the GPU", numel=N)
+    check(lib.clipmi_cocoop_embed(base.data_ptr(), _DT[base.dtype], ctx.data_ptr(), pi.data_ptr(), cls_eot.data_ptr(), prompts.data_ptr(), eot.data_ptr(),
+                                  B, Cn, L, Lc, D, n_ctx, _stream()), "clipmi_cocoop_embed")
+    return prompts, eot
+
+
+def cocoop_head(features: torch.Tensor, labels: torch.Tensor, text: torch.Tensor, scale: float, grad_scale: float = 1.0,
+                loss: Optional[torch.Tensor] = None, want_rows: bool = False):
+    """CoCoOp's loss head: ``(loss fp32 [1], d_text fp32 [B * C, E])``, the gradient times ``grad_scale``; ``text`` fp32 [B * C, E] the
+    raw features of the image-major prompts, ``features`` and ``labels`` as ``coop_head``'s.  ``want_rows`` adds the row losses fp32 [B]."""
+    labels, text, B, E, N = _head_inputs("cocoop_head", features, labels, text)
+    if N % B or N // B < 2:
+        raise ValueError(f"cocoop_head: {N} text rows do not split into {B} images of at least 2 classes")
+    if loss is None:
+        loss = torch.empty(1, dtype=torch.float32, device=text.device)
+    else:
+        _in_place(loss, torch.float32, "cocoop_head: loss must be a contiguous fp32 tensor on the GPU", numel=1)
+    rows = torch.empty(B, dtype=torch.float32, device=text.device) if want_rows else None
+    d_text = torch.empty_like(text)
+    ws = torch.empty(max(lib.clipmi_cocoop_head_workspace_bytes(B, N // B), 8), dtype=torch.uint8, device=text.device)
+    check(lib.clipmi_cocoop_head(features.data_ptr(), features.stride(0), labels.data_ptr(), text.data_ptr(), B, E, N // B, float(scale), float(grad_scale),
+                                 loss.data_ptr(), None if rows is None else rows.data_ptr(), d_text.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+          "clipmi_cocoop_head")
+    return (loss, d_text, rows) if want_rows else (loss, d_text)
+
+
+def cocoop_reduce(d_embed: torch.Tensor, x_n: torch.Tensor, hid: torch.Tensor, w2: torch.Tensor, n_cls: int, n_ctx: int, grad_scale: float,
+                  grad: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """CoCoOp's five gradients from ``d_embed`` fp32 [B * C * L, D] as one block fp32 ``[ctx | W1 | b1 | W2 | b2]`` (``cocoop_block_views``
+    splits it): the classes of an image in ascending order, divided by ``grad_scale``, then the meta-net's backward from ``x_n`` [B, E],
+    ``hid`` [B, H] (its zeros are the ReLU's mask) and ``w2`` [D, H].  A caller's own ``grad`` is written where it lies."""
+    d_embed, x_n, hid, w2 = (_dev(t, n, (torch.float32,)) for t, n in ((d_embed, "d_embed"), (x_n, "x_n"), (hid, "hid"), (w2, "w2")))
+    if d_embed.dim() != 2 or x_n.dim() != 2 or hid.dim() != 2 or w2.dim() != 2 or hid.shape[0] != x_n.shape[0] or w2.shape != (d_embed.shape[1], hid.shape[1]):
+        raise ValueError(f"cocoop_reduce: d_embed {tuple(d_embed.shape)}, x_n {tuple(x_n.shape)}, hid {tuple(hid.shape)}, w2 {tuple(w2.shape)} do not agree")
+    (B, E), H, D, Cn = x_n.shape, int(hid.shape[1]), int(d_embed.shape[1]), int(n_cls)
+    if Cn < 2 or d_embed.shape[0] % (B * Cn):
+        raise ValueError(f"cocoop_reduce: {d_embed.shape[0]} rows do not split into {B} x {Cn} prompts")
+    L = d_embed.shape[0] // (B * Cn)
+    total = lib.clipmi_cocoop_block_floats(int(n_ctx), D, E, H)
+    if grad is None:
+        grad = torch.empty(max(total, 1), dtype=torch.float32, device=d_embed.device)
+    else:
+        _in_place(grad, torch.float32, "cocoop_reduce: grad must be a contiguous fp32 tensor on the GPU", numel=total)
+    ws = torch.empty(max(lib.clipmi_cocoop_reduce_workspace_bytes(B, int(n_ctx), D, H), 8), dtype=torch.uint8, device=d_embed.device)
+    check(lib.clipmi_cocoop_reduce(d_embed.data_ptr(), x_n.data_ptr(), hid.data_ptr(), w2.data_ptr(), grad.data_ptr(), B, Cn, L, D, E, H, int(n_ctx),
+                                   float(grad_scale), ws.data_ptr(), ws.numel(), _stream()), "clipmi_cocoop_reduce")
+    return grad
+
+
+def cocoop_step(grad: torch.Tensor, params: torch.Tensor, buf: Optional[torch.Tensor], lr: torch.Tensor, n_ctx: int, D: int, E: int, H: int,
+                first_step: bool = False, momentum: float = 0.0, dampening: float = 0.0, weight_decay: float = 0.0, nesterov: bool = False) -> None:
+    """torch.optim.SGD's step on CoCoOp's parameter block ``params`` fp32 in place, with the gradient block ``grad`` and the momentum block
+    ``buf`` (None without a momentum), at the rate ``lr`` fp32 [1] on the device: one rule and one set of hyper-parameters for the five
+    tensors."""
+    total = lib.clipmi_cocoop_block_floats(int(n_ctx), int(D), int(E), int(H))
+    _in_place(params, torch.float32, "cocoop_step: params must be a contiguous fp32 tensor on the GPU", numel=total)
+    _in_place(grad, torch.float32, "cocoop_step: grad must be a contiguous fp32 tensor on the GPU", numel=total)
+    if buf is not None:
+        _in_place(buf, torch.float32, "cocoop_step: buf must be a contiguous fp32 tensor on the GPU", numel=total)
+    lr = _dev(lr, "lr", (torch.float32,))
+    if lr.numel() != 1:
+        raise ValueError("cocoop_step: lr must hold one rate")
+    check(lib.clipmi_cocoop_step(grad.data_ptr(), params.data_ptr(), None if buf is None else buf.data_ptr(), int(n_ctx), int(D), int(E), int(H),
+                                 lr.data_ptr(), int(bool(first_step)), float(momentum), float(dampening), float(weight_decay), int(bool(nesterov)),
+                                 _stream()), "clipmi_cocoop_step")

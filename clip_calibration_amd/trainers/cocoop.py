@@ -1,4 +1,5 @@
-"""CoCoOp (reference trainers/classification/cocoop.py:71-199) -- inference forward only.
+"""CoCoOp (reference trainers/classification/cocoop.py:71-199): the inference forward, and ``CustomCLIP.fit_prompt_learner``, which trains
+``ctx`` and ``meta_net`` on the GPU through ``cocoopfit`` (cocoop.py:186-202, 259-278 with both towers frozen).
 
 Every image gets its own context: ``ctx + meta_net(image_features)`` (cocoop.py:154-161), hence its own C prompts and its
 own pass through the text tower -- B*C prompts per batch, which makes the TEXT tower the dominant cost (5.96 GFLOP per
@@ -104,6 +105,49 @@ class CustomCLIP(nn.Module):
             ids = self.tokenized_prompts.repeat(nb, 1)                       # EOT index plumbing
             out[lo:lo + nb] = self.text_encoder(prompts, ids, flags=flags, seq_rows=rows).view(nb, Cn, -1)
         return out
+
+    def fit_prompt_learner(self, train_loader, transform=None, **fit_args):
+        """Train ``prompt_learner.ctx`` and ``prompt_learner.meta_net`` on the GPU, starting from the module's values, with ``logit_scale``
+        taken from this model unless ``fit_args`` say otherwise.  The fitted tensors are copied into the module in its dtype (the fit
+        keeps one fp32 master block), so the next ``forward`` uses them; returned as ``cocoopfit.fit_prompt_learner`` returns them.
+
+        ``transform=None``: one pass of ``train_loader`` (an iterable of (image, label) batches of preprocessed images) through the
+        frozen image tower, then ``cocoopfit.fit_prompt_learner(features, labels, clip_model, tokenized_prompts, params, **fit_args)`` --
+        equal to the reference's loop only for a deterministic train transform.  ``transform=TrainPreprocess(...)``: ``train_loader``
+        yields (decoded uint8 images, labels) and is iterated once per epoch, every batch going transform -> image tower ->
+        ``CoCoOpFitState.step`` (``augment.fit_with_transform``); ``fit_args`` are then ``epochs``, ``lr``, ``lr_per_epoch``, ``views``,
+        ``return_history`` and ``CoCoOpFitState``'s own."""
+        import math
+        from ..cocoopfit import NAMES
+        fit_args.setdefault("logit_scale", math.log(self.scale))
+        pl = self.prompt_learner
+        params = {k: v.detach() for k, v in pl.state_dict().items() if k in NAMES}
+        ids = pl.tokenized_prompts
+        if transform is not None:
+            from ..augment import fit_with_transform
+            from ..cocoopfit import CoCoOpFitState
+            run = {k: fit_args.pop(k) for k in ("lr_per_epoch", "views", "return_history") if k in fit_args}
+            epochs, lr = fit_args.pop("epochs", 10), fit_args.pop("lr", 0.002)
+            state = CoCoOpFitState(self.clip_model, ids, params, **fit_args)
+            losses = fit_with_transform(state, self.clip_model.image_features_f32, ids.shape[0], train_loader, transform, epochs, lr, **run)
+            fitted = state.params() if losses is None else (state.params(), losses)
+        else:
+            from ..cocoopfit import fit_prompt_learner
+            feats, labels = [], []
+            with torch.no_grad():
+                for image, label in train_loader:
+                    f = self.clip_model.image_features_f32(image)
+                    feats.append(f)
+                    labels.append(torch.as_tensor(label).to(device=f.device, dtype=torch.int64))
+            if not feats:
+                raise ValueError("fit_prompt_learner: the loader gave no batch")
+            fitted = fit_prompt_learner(torch.cat(feats), torch.cat(labels), self.clip_model, ids, params, **fit_args)
+        values = fitted[0] if isinstance(fitted, tuple) else fitted
+        target = dict(pl.named_parameters())
+        with torch.no_grad():
+            for k in NAMES:
+                target[k].copy_(values[k])
+        return fitted
 
     @torch.no_grad()
     def forward(self, image: torch.Tensor, label=None, dac_conf: Optional[torch.Tensor] = None, want_conf_pred: bool = False):

@@ -908,6 +908,61 @@ int clipmi_proda_train_step(clipmi_model* m, const clipmi_text_dgrad* wt, const 
                             int nesterov, float* losses, float* grad_out, void* workspace, size_t workspace_bytes, void* stash,
                             size_t stash_bytes, clipmi_stream_t stream);
 
+/* CoCoOp's context and meta-net trained on the same frozen-tower backward (reference trainers/classification/cocoop.py:153-202, 259-278;
+ * csrc/cocoop_train.hip, DESIGN.md "CoCoOp fit").  The five learned tensors live in ONE fp32 block of clipmi_cocoop_block_floats(n_ctx, D,
+ * E, H) floats laid out as ctx [n_ctx, D] | W1 [H, E] | b1 [H] | W2 [D, H] | b2 [D] (D the text width, E the embedding width, H the
+ * meta-net's hidden width, 1 <= H <= 4096; the reference uses E / 16, which is not required); the momentum block and the gradient block
+ * have the same layout.  N = B C prompts go through the tower: prompt b C + c is image b with class c.  These exports are additive: the
+ * ABI version does not change with them.
+ *
+ * clipmi_cocoop_meta: x_b = feats_b / |feats_b| (feats fp32 [B, E] with the row stride ld), hid_b = max(W1 x_b + b1, 0), pi_b = W2 hid_b
+ *   + b2 -> x_n fp32 [B, E], hid fp32 [B, H], pi fp32 [B, D].  One workgroup per image, fixed-order sums.  One launch.
+ * clipmi_cocoop_embed: the N prompts as fp32 embeddings [N, Lc, D] (rows [0, L) of each written, L <= Lc the live rows; the positional
+ *   embedding is the tower's to add) and their EOT indices int32 [N] = cls_eot[c] (int32 [C] on the device).  Row 1 + j (j < n_ctx) is the
+ *   single fp32 addition ctx[j] + pi[b]; every other row is base [C, Lc, D] (dtype: CLIPMI_F16 or CLIPMI_F32) widened.  One launch.
+ *   16-byte aligned base, ctx, pi and prompts, D a multiple of 4, 1 + n_ctx <= L, B C Lc < 2^31.  The tower then runs on it unchanged:
+ *   clipmi_text_encoder_train(m, prompts, CLIPMI_F32, NULL, 0, 0, eot, N, seq_rows, ...).
+ * clipmi_cocoop_head: text fp32 [N, E] the tower's raw features, u_n = unit(text_n): z[b, c] = scale x_b . u_{b C + c};
+ *   loss fp32 [1] = the float64 mean of the fp32 row losses CE(z[b, :], labels[b]) (row_losses fp32 [B], may be NULL, receives them);
+ *   d_text fp32 [N, E] = grad_scale d loss / d text: with dz = grad_scale (softmax(z) - onehot) / B and v = scale dz[b, c] x_b,
+ *   d_text_n = (v - u_n (u_n . v)) / |text_n| -- no sum over the images, every pair has its own text row.  A label outside [0, C) makes
+ *   that image's row loss, its d_text rows and the batch loss NaN and is never used as an address; the other images' rows stay finite.
+ *   Four launches, no float atomics.  workspace (8-byte aligned): clipmi_cocoop_head_workspace_bytes(B, C) bytes (0 for a bad argument).
+ * clipmi_cocoop_reduce: d_embed fp32 [N L, D] as the backward wrote it -> the gradient block `grad`:
+ *     dcs[b, j] = (1 / grad_scale) sum_c d_embed[(b C + c) L + 1 + j] (c ascending; the only place 1 / grad_scale is applied);
+ *     dctx[j] = sum_b dcs[b, j];  dpi[b] = sum_j dcs[b, j];  db2 = sum_b dpi[b];  dW2[d, h] = sum_b dpi[b, d] hid[b, h];
+ *     dhid[b, h] = [hid[b, h] > 0] sum_d W2[d, h] dpi[b, d];  db1 = sum_b dhid[b];  dW1[h, e] = sum_b dhid[b, h] x_n[b, e]
+ *   (b and j ascending).  x_n, hid as clipmi_cocoop_meta wrote them, w2 fp32 [D, H].  No gradient with respect to x_n is formed: the
+ *   image tower is frozen.  Four launches, no float atomics.  workspace: clipmi_cocoop_reduce_workspace_bytes(B, n_ctx, D, H) bytes.
+ * clipmi_cocoop_step: torch.optim.SGD's rule as clipmi_ctx_step applies it, over every element of the parameter block `params` with the
+ *   gradient block `grad` and the momentum block `buf` (required with a momentum): one set of hyper-parameters for the five tensors, weight
+ *   decay on the biases too, as the reference's single optimiser has it.  lr fp32 [1] on the device.  One launch.
+ * clipmi_cocoop_train_step: all of the above around clipmi_text_encoder_train and clipmi_text_encoder_backward as ONE call on `stream`
+ *   -- the same launches, the same bits as the calls one by one.  workspace of clipmi_cocoop_train_step_bytes(m, C, seq_rows, B, H, n_ctx)
+ *   bytes (256-byte aligned; 0 for arguments the call refuses), stash as clipmi_text_train_bytes(m, B C, seq_rows, ...) reports it.
+ *   grad_out (may be NULL): the gradient block is formed there instead of in the workspace.  At most 80 live rows (the backward's
+ *   limit).  Every argument check of the seven stages is made before the first launch: a refused call enqueues nothing. */
+size_t clipmi_cocoop_block_floats(int n_ctx, int D, int E, int H);
+int clipmi_cocoop_meta(const float* feats, int64_t ld, const float* w1, const float* b1, const float* w2, const float* b2, float* x_n, float* hid,
+                       float* pi, int B, int E, int H, int D, clipmi_stream_t stream);
+int clipmi_cocoop_embed(const void* base, int dtype, const float* ctx, const float* pi, const int32_t* cls_eot, float* prompts, int32_t* eot,
+                        int B, int C, int L, int Lc, int D, int n_ctx, clipmi_stream_t stream);
+size_t clipmi_cocoop_head_workspace_bytes(int B, int C);
+int clipmi_cocoop_head(const float* feats, int64_t ld, const int64_t* labels, const float* text, int B, int E, int C, float scale,
+                       float grad_scale, float* loss, float* row_losses, float* d_text, void* workspace, size_t workspace_bytes,
+                       clipmi_stream_t stream);
+size_t clipmi_cocoop_reduce_workspace_bytes(int B, int n_ctx, int D, int H);
+int clipmi_cocoop_reduce(const float* d_embed, const float* x_n, const float* hid, const float* w2, float* grad, int B, int C, int L, int D,
+                         int E, int H, int n_ctx, float grad_scale, void* workspace, size_t workspace_bytes, clipmi_stream_t stream);
+int clipmi_cocoop_step(const float* grad, float* params, float* buf, int n_ctx, int D, int E, int H, const float* lr, int first_step,
+                       float momentum, float dampening, float weight_decay, int nesterov, clipmi_stream_t stream);
+size_t clipmi_cocoop_train_step_bytes(const clipmi_model* m, int C, int seq_rows, int B, int H, int n_ctx);
+int clipmi_cocoop_train_step(clipmi_model* m, const clipmi_text_dgrad* wt, const void* base, int dtype, float* params, float* buf, int n_ctx,
+                             int H, const int32_t* cls_eot, int C, int seq_rows, const float* feats, int64_t ld, const int64_t* labels, int B,
+                             float scale, float grad_scale, const float* lr, int first_step, float momentum, float dampening,
+                             float weight_decay, int nesterov, float* loss, float* grad_out, void* workspace, size_t workspace_bytes,
+                             void* stash, size_t stash_bytes, clipmi_stream_t stream);
+
 /* Timing aid for bench.py (the per-kernel roofline of its JSON line): the five launches of the vision tower's residual
  * block 0 -- 0 in-proj, 1 attention, 2 out-proj + residual, 3 c_fc + QuickGELU, 4 c_proj + residual (clip/model.py:181-188)
  * -- issued exactly as clipmi_encode_image issues them (LayerNorm fold, fp16 stream, tile selection) on the operands the
