@@ -98,6 +98,11 @@ class TextDgrad(C.Structure):
     _fields_ = [("proj", C.c_void_p), ("blocks", C.POINTER(BlockDgrad))]
 
 
+class VisionDgrad(C.Structure):
+    """clipmi_vision_dgrad: visual.proj as fp16 [Dv, E] and the image blocks' transposed weights."""
+    _fields_ = [("proj", C.c_void_p), ("blocks", C.POINTER(BlockDgrad))]
+
+
 if not os.path.exists(LIB_PATH):
     raise ImportError(
         f"{LIB_PATH} is missing: the HIP extension has not been built. Run `python -c 'import __graft_entry__ as g; "
@@ -171,6 +176,7 @@ _SIGNATURES = {
     "clipmi_layernorm_backward": (_i, [_vp, _i64, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _f, _vp]),
     "clipmi_quickgelu_backward": (_i, [_vp, _vp, _vp, _i64, _vp]),
     "clipmi_attention_backward": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
+    "clipmi_attention_backward_full": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     "clipmi_coop_head_workspace_bytes": (_sz, [_i, _i, _i]),
     "clipmi_coop_head": (_i, [_vp, _i64, _vp, _vp, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
     "clipmi_ctx_step": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _i, _f, _f, _f, _i, _vp]),
@@ -180,6 +186,15 @@ _SIGNATURES = {
     "clipmi_coop_train_step_bytes": (_sz, [_vp, _i, _i, _i]),
     "clipmi_coop_train_step": (_i, [_vp, C.POINTER(TextDgrad), _vp, _i, _vp, _vp, _i, _i, _vp, _i, _i, _vp, _i64, _vp, _i, _f, _f, _vp, _i, _f,
                                     _f, _f, _i, _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
+    "clipmi_vision_train_bytes": (_i, [_vp, _i, _i, C.POINTER(_sz), C.POINTER(_sz)]),
+    "clipmi_vision_encoder_train": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _vp, _vp, _sz, _vp, _sz, _u, _vp]),
+    "clipmi_vision_encoder_backward": (_i, [_vp, C.POINTER(VisionDgrad), _vp, _i, _i, _i, _vp, _vp, _sz, _vp, _sz, _vp, _vp]),
+    "clipmi_vpt_head_workspace_bytes": (_sz, [_i, _i, _i]),
+    "clipmi_vpt_head": (_i, [_vp, _i64, _vp, _vp, _i, _i, _i, _f, _f, _vp, _vp, _vp, _sz, _vp]),
+    "clipmi_vpt_step": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _i, _f, _f, _f, _i, _vp]),
+    "clipmi_vpt_train_step_bytes": (_sz, [_vp, _i, _i, _i]),
+    "clipmi_vpt_train_step": (_i, [_vp, C.POINTER(VisionDgrad), _vp, _i, _i, _vp, _vp, _i, _i, _vp, _i, _vp, _f, _f, _vp, _i, _f, _f, _f, _i, _vp, _vp,
+                                   _vp, _sz, _vp, _sz, _vp]),
     "clipmi_prompt_head_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "clipmi_prompt_head": (_i, [_vp, _i64, _vp, _vp, _i, _i, _i, _f, _f, _i, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "clipmi_prograd_step_workspace_bytes": (_sz, [_i, _i, _i, _i]),

@@ -1535,7 +1535,236 @@ __global__ __launch_bounds__(THREADS) void attention_backward_kernel(const half_
 }
 
 DeviceOnce g_ab_once;
+
+// ------------------------------------------------------------------------------------------- attention backward without a mask, L <= 224
+// The image tower's lengths (197 tokens + prompt rows).  One workgroup of four waves per (image, head) item again, with Q, K, V and dO
+// as [224][72] fp16 in LDS (rows >= L zero up to an even number of 16-row tiles) and three floats of statistics per query row: P and dS
+// do not fit beside them, so neither is ever stored -- each is formed in the accumulator layout of the product that made it and IS the
+// next product's operand (the summation index of that product runs over two tiles' worth of accumulator registers, in the order the
+// lanes hold them; the other operand is gathered in the same order).  Two phases:
+//   phase 1, query-owned  a wave takes 16 query rows: S^T = K Q^T and dP^T = V dO^T for every key tile (a lane holds ONE query, column
+//            l & 15, and the keys 16 kt + 4 (l >> 4) + i), the softmax and rowsum(dP o P) over the registers and the four lanes of the
+//            column, dS^T in place, dQ^T = K^T dS^T / 8; the row's maximum, 1 / sum and rowsum go to LDS;
+//   phase 2, key-owned    a wave takes 16 keys: per pair of query tiles S = Q K^T and dP = dO V^T again, P and dS from the saved
+//            statistics by phase 1's expressions, dV += P^T dO and dK += dS^T Q / 8 in registers.
+// A workgroup owns every row it writes; a key column >= L has P = dS = 0 exactly and a query row >= L likewise.
+constexpr int ABF_TILES = ABF_MAX_L / 16, ABF_LDH = 72;
+constexpr int ABF_LDS_BYTES = 4 * ABF_MAX_L * ABF_LDH * 2 + 3 * ABF_MAX_L * 4;
+
+// the operand whose summation index runs over the accumulator registers of tiles t0 and t0 + 1: element j of lane (lr, lq) is
+// m[(16 (t0 + (j >> 2)) + 4 lq + (j & 3)) * ABF_LDH + col]
+__device__ __forceinline__ f16x8 frag_pair(const half_t* m, int t0, int lq, int col) {
+  f16x8 v;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) v[j] = m[((t0 + (j >> 2)) * 16 + 4 * lq + (j & 3)) * ABF_LDH + col];
+  return v;
+}
+__device__ __forceinline__ float col4_sum(float v) {   // over the four lanes l & 15, the same bits in each
+  v += __shfl_xor(v, 16);
+  v += __shfl_xor(v, 32);
+  return v;
+}
+__device__ __forceinline__ float col4_max(float v) {
+  v = fmaxf(v, __shfl_xor(v, 16));
+  v = fmaxf(v, __shfl_xor(v, 32));
+  return v;
+}
+
+__global__ __launch_bounds__(THREADS) void attention_backward_full_kernel(const half_t* __restrict__ qkv, const half_t* __restrict__ d_out,
+                                                                          half_t* __restrict__ dqkv, int L, int H) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char abf_smem[];
+  half_t* sq = reinterpret_cast<half_t*>(abf_smem);
+  half_t* sk = sq + ABF_MAX_L * ABF_LDH;
+  half_t* sv = sk + ABF_MAX_L * ABF_LDH;
+  half_t* sdo = sv + ABF_MAX_L * ABF_LDH;
+  float* smax = reinterpret_cast<float*>(sdo + ABF_MAX_L * ABF_LDH);
+  float* sinv = smax + ABF_MAX_L;
+  float* srs = sinv + ABF_MAX_L;
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, lr = lane & 15, lq = lane >> 4;
+  const int n = blockIdx.x / H, h = blockIdx.x % H, D = 64 * H;
+  const int64_t row0 = (int64_t)n * L;
+  const int NT = (L + 15) / 16, NTP = (NT + 1) & ~1;   // NTP * 16 <= 224
+  const f16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
+  for (int i = t; i < NTP * 16 * 8; i += THREADS) {
+    const int r = i >> 3, c = (i & 7) * 8;
+    f16x8 q = zero8, k = zero8, v = zero8, o = zero8;
+    if (r < L) {
+      const half_t* row = qkv + (row0 + r) * 3 * D + h * 64 + c;
+      q = *reinterpret_cast<const f16x8*>(row);
+      k = *reinterpret_cast<const f16x8*>(row + D);
+      v = *reinterpret_cast<const f16x8*>(row + 2 * D);
+      o = *reinterpret_cast<const f16x8*>(d_out + (row0 + r) * D + h * 64 + c);
+    }
+    *reinterpret_cast<f16x8*>(sq + r * ABF_LDH + c) = q;
+    *reinterpret_cast<f16x8*>(sk + r * ABF_LDH + c) = k;
+    *reinterpret_cast<f16x8*>(sv + r * ABF_LDH + c) = v;
+    *reinterpret_cast<f16x8*>(sdo + r * ABF_LDH + c) = o;
+  }
+  __syncthreads();
+
+  // ---- phase 1: the statistics and dQ of 16 query rows
+  for (int qt = wave; qt < NT; qt += WAVES) {
+    f16x8 qb[2], ob[2];
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      qb[ks] = frag_row(sq + (qt * 16 + lr) * ABF_LDH + ks * 32 + lq * 8);
+      ob[ks] = frag_row(sdo + (qt * 16 + lr) * ABF_LDH + ks * 32 + lq * 8);
+    }
+    f32x4 s[ABF_TILES], dp[ABF_TILES];   // [key tile][key 4 lq + i] of query qt * 16 + lr; P and dS in place below
+#pragma unroll
+    for (int kt = 0; kt < ABF_TILES; ++kt) {
+      if (kt < NT) {   // wave-uniform
+        const half_t* kr = sk + (kt * 16 + lr) * ABF_LDH + lq * 8;
+        const half_t* vr = sv + (kt * 16 + lr) * ABF_LDH + lq * 8;
+        s[kt] = mma0(frag_row(kr), qb[0]);
+        s[kt] = mma(frag_row(kr + 32), qb[1], s[kt]);
+        dp[kt] = mma0(frag_row(vr), ob[0]);
+        dp[kt] = mma(frag_row(vr + 32), ob[1], dp[kt]);
+        AB_MFMA_TO_VALU_FENCE(s[kt]);
+        AB_MFMA_TO_VALU_FENCE(dp[kt]);
+      } else {
+        s[kt] = f32x4{0.f, 0.f, 0.f, 0.f};
+        dp[kt] = f32x4{0.f, 0.f, 0.f, 0.f};
+      }
+    }
+    float m = -INFINITY;
+#pragma unroll
+    for (int kt = 0; kt < ABF_TILES; ++kt)
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        if (kt * 16 + 4 * lq + i < L) m = fmaxf(m, s[kt][i] * 0.125f);
+    m = col4_max(m);   // key 0 is live: finite
+    float sum = 0.f;
+#pragma unroll
+    for (int kt = 0; kt < ABF_TILES; ++kt)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        s[kt][i] = kt * 16 + 4 * lq + i < L ? __expf(s[kt][i] * 0.125f - m) : 0.f;
+        sum += s[kt][i];
+      }
+    const float inv = 1.f / col4_sum(sum);
+    float rs = 0.f;
+#pragma unroll
+    for (int kt = 0; kt < ABF_TILES; ++kt)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        s[kt][i] *= inv;
+        rs = fmaf(s[kt][i], dp[kt][i], rs);
+      }
+    rs = col4_sum(rs);
+    const int q = qt * 16 + lr;
+    if (lq == 0 && q < L) {
+      smax[q] = m;
+      sinv[q] = inv;
+      srs[q] = rs;
+    }
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) {
+      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int u = 0; u < ABF_TILES / 2; ++u) {
+        if (2 * u < NT) {   // wave-uniform; tile 2 u + 1 == NT holds zeros on both sides
+          f16x8 b;
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            const int kt = 2 * u + (j >> 2), i = j & 3;
+            b[j] = kt * 16 + 4 * lq + i < L ? (half_t)(s[kt][i] * (dp[kt][i] - rs)) : (half_t)0.f;
+          }
+          const f16x8 a = frag_pair(sk, 2 * u, lq, dt * 16 + lr);   // A[row d = lr][k] = K[key(k)][d]
+          acc = u == 0 ? mma0(a, b) : mma(a, b, acc);
+        }
+      }
+      AB_MFMA_TO_VALU_FENCE(acc);
+      if (q < L)   // dQ^T[d = dt * 16 + 4 lq + i][q]
+        *reinterpret_cast<f16x4*>(dqkv + (row0 + q) * 3 * D + h * 64 + dt * 16 + 4 * lq) =
+            f16x4{(half_t)(acc[0] * 0.125f), (half_t)(acc[1] * 0.125f), (half_t)(acc[2] * 0.125f), (half_t)(acc[3] * 0.125f)};
+    }
+  }
+  __syncthreads();
+
+  // ---- phase 2: dK and dV of 16 keys
+  for (int kt = wave; kt < NT; kt += WAVES) {
+    f16x8 kb[2], vb[2];
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      kb[ks] = frag_row(sk + (kt * 16 + lr) * ABF_LDH + ks * 32 + lq * 8);
+      vb[ks] = frag_row(sv + (kt * 16 + lr) * ABF_LDH + ks * 32 + lq * 8);
+    }
+    const bool key_live = kt * 16 + lr < L;
+    f32x4 dk[4], dv[4];
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) {
+      dk[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+      dv[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    for (int u = 0; 2 * u < NT; ++u) {
+      f16x8 pa, dsa;   // A[row key = lr][k] = P[query(k)][key], dS[query(k)][key]
+#pragma unroll
+      for (int hf = 0; hf < 2; ++hf) {
+        const int qt = 2 * u + hf;
+        f32x4 s = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
+        if (qt < NT) {   // wave-uniform
+          const half_t* qr = sq + (qt * 16 + lr) * ABF_LDH + lq * 8;
+          const half_t* orow = sdo + (qt * 16 + lr) * ABF_LDH + lq * 8;
+          s = mma0(frag_row(qr), kb[0]);
+          s = mma(frag_row(qr + 32), kb[1], s);
+          dp = mma0(frag_row(orow), vb[0]);
+          dp = mma(frag_row(orow + 32), vb[1], dp);
+          AB_MFMA_TO_VALU_FENCE(s);
+          AB_MFMA_TO_VALU_FENCE(dp);
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int q = qt * 16 + 4 * lq + i;
+          float p = 0.f, ds = 0.f;
+          if (key_live && q < L) {
+            p = __expf(s[i] * 0.125f - smax[q]) * sinv[q];
+            ds = p * (dp[i] - srs[q]);
+          }
+          pa[hf * 4 + i] = (half_t)p;
+          dsa[hf * 4 + i] = (half_t)ds;
+        }
+      }
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt) {
+        const f16x8 bo = frag_pair(sdo, 2 * u, lq, dt * 16 + lr);   // B[k][col d = lr] = dO[query(k)][d]
+        const f16x8 bq = frag_pair(sq, 2 * u, lq, dt * 16 + lr);
+        dv[dt] = u == 0 ? mma0(pa, bo) : mma(pa, bo, dv[dt]);
+        dk[dt] = u == 0 ? mma0(dsa, bq) : mma(dsa, bq, dk[dt]);
+      }
+    }
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) {
+      AB_MFMA_TO_VALU_FENCE(dk[dt]);
+      AB_MFMA_TO_VALU_FENCE(dv[dt]);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int key = kt * 16 + 4 * lq + i;
+        if (key < L) {
+          half_t* o = dqkv + (row0 + key) * 3 * D + h * 64 + dt * 16 + lr;
+          o[D] = (half_t)(dk[dt][i] * 0.125f);
+          o[2 * D] = (half_t)dv[dt][i];
+        }
+      }
+    }
+  }
+}
+
+DeviceOnce g_abf_once;
 }  // namespace
+
+int launch_attention_backward_full(const half_t* qkv, const half_t* d_out, half_t* dqkv, int N, int L, int H, hipStream_t s) {
+  CLIPMI_REQUIRE(N >= 0 && H >= 1 && L >= 1, CLIPMI_ERR_SHAPE, "attention_backward_full: N=%d L=%d H=%d", N, L, H);
+  CLIPMI_REQUIRE(L <= ABF_MAX_L, CLIPMI_ERR_SHAPE, "attention_backward_full: L=%d (at most %d token rows)", L, ABF_MAX_L);
+  CLIPMI_REQUIRE((int64_t)N * H < (1ll << 31) && (int64_t)N * L < (1ll << 31), CLIPMI_ERR_SHAPE, "attention_backward_full: too many items");
+  if (N == 0) return CLIPMI_OK;
+  CLIPMI_REQUIRE(qkv && d_out && dqkv, CLIPMI_ERR_ARG, "attention_backward_full: null pointer");
+  CLIPMI_REQUIRE((uintptr_t)qkv % 16 == 0 && (uintptr_t)d_out % 16 == 0 && (uintptr_t)dqkv % 16 == 0, CLIPMI_ERR_ARG,
+                 "attention_backward_full: pointers must be 16-byte aligned");
+  ensure_dynamic_lds(attention_backward_full_kernel, ABF_LDS_BYTES, g_abf_once);
+  hipLaunchKernelGGL(attention_backward_full_kernel, dim3((unsigned)(N * H)), dim3(THREADS), ABF_LDS_BYTES, s, qkv, d_out, dqkv, L, H);
+  return check_launch("attention_backward_full_kernel");
+}
 
 int launch_attention_backward(const half_t* qkv, const half_t* d_out, half_t* dqkv, int N, int L, int H, hipStream_t s) {
   CLIPMI_REQUIRE(N >= 0 && H >= 1 && L >= 1, CLIPMI_ERR_SHAPE, "attention_backward: N=%d L=%d H=%d", N, L, H);
@@ -1556,5 +1785,13 @@ int launch_attention_backward(const half_t* qkv, const half_t* d_out, half_t* dq
 int launch_attention_backward(const half_t* qkv, const half_t* d_out, half_t* dqkv, int N, int L, int H, hipStream_t s) {
   return ab::launch_attention_backward(qkv, d_out, dqkv, N, L, H, s);
 }
+int launch_attention_backward_full(const half_t* qkv, const half_t* d_out, half_t* dqkv, int N, int L, int H, hipStream_t s) {
+  return ab::launch_attention_backward_full(qkv, d_out, dqkv, N, L, H, s);
+}
 
 }  // namespace clipmi
+
+extern "C" int clipmi_attention_backward_full(const void* qkv, const void* d_out, void* dqkv, int N, int L, int H, clipmi_stream_t stream) {
+  return clipmi::launch_attention_backward_full(static_cast<const clipmi::half_t*>(qkv), static_cast<const clipmi::half_t*>(d_out),
+                                                static_cast<clipmi::half_t*>(dqkv), N, L, H, (hipStream_t)stream);
+}

@@ -237,6 +237,9 @@ int launch_attention(const half_t* qkv, half_t* out, int N, int L, int H, int ca
 // the backward of the causal attention for L <= 80 token rows (CoOp's training path, text_backward.hip): dqkv in qkv's layout from the gradient of `out`
 constexpr int AB_MAX_L = 80;   // token rows per sequence the kernel holds
 int launch_attention_backward(const half_t* qkv, const half_t* d_out, half_t* dqkv, int N, int L, int H, hipStream_t s);
+// the same without a mask for L <= 224 token rows, the lengths of the one-key-block forward (the image tower's training path, vision_backward.hip)
+constexpr int ABF_MAX_L = 224;
+int launch_attention_backward_full(const half_t* qkv, const half_t* d_out, half_t* dqkv, int N, int L, int H, hipStream_t s);
 // attention_cls.hip: the output row of token 0 of every sequence only (the image tower's last block: clip/model.py:419 reads nothing else)
 int launch_attention_cls(const half_t* qkv, half_t* out, int N, int L, int H, hipStream_t s);
 int launch_patchify(const void* image, int image_dtype, half_t* col, int B, int R, int P, int Kpad, hipStream_t s);

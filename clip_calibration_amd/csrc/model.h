@@ -39,6 +39,77 @@ struct Carver {
 // rows of a prompt the tower works on: the caller's bound on the last live token (dead-row elimination), else the whole context
 inline int live_rows(const clipmi_model* m, int seq_rows) { return seq_rows > 0 && seq_rows < m->g.context_length ? seq_rows : m->g.context_length; }
 
+// ---- what the two training towers share (text_backward.hip defines the launchers; vision_backward.hip drives the image tower with them)
+int launch_ln_backward(const float* x, int64_t x_stride, const int32_t* row_idx, const float* gamma, const void* dy, int dy_dtype, float* g,
+                       half_t* g16, int64_t rows, int D, float eps, hipStream_t s);
+int launch_quickgelu_forward(const half_t* h, half_t* a, int64_t n, hipStream_t s);
+int launch_quickgelu_backward(const half_t* h, const half_t* d_a, half_t* d_h, int64_t n, hipStream_t s);
+int launch_operand_stats(const half_t* x, int64_t n, unsigned long long* stats, hipStream_t s);
+
+// workspace shared by a tower's training forward and its backward over M = C * L token rows: C sequences (prompts of the text tower,
+// images of the image tower) of L token rows, D the tower's width, E the embedding
+struct TrainWs {
+  half_t* xn;      // [M, D]   LayerNorm output (forward) / fp16 copy of the gradient stream (backward)
+  half_t* att;     // [M, D]   attention output / its gradient
+  half_t* hid;     // [M, 4D]  QuickGELU output / the gradient of c_fc's output
+  half_t* qkv;     // [M, 3D]  backward: dqkv
+  float* dy;       // [M, D]   backward: the fp32 output of the dgrad GEMM in front of a LayerNorm backward
+  half_t* rows16;  // [C, D]   the output rows of the last LayerNorm (ln_final / ln_post)
+  half_t* dfeat16; // [C, E]
+  float* dxf;      // [C, D]   d_out projection^T (text_projection / visual.proj)
+  size_t bytes;
+};
+inline TrainWs carve_ws(void* p, int64_t M, int64_t C, int D, int E) {
+  Carver c(p);
+  TrainWs w;
+  w.xn = c.take<half_t>((size_t)M * D * 2);
+  w.att = c.take<half_t>((size_t)M * D * 2);
+  w.hid = c.take<half_t>((size_t)M * D * 8);
+  w.qkv = c.take<half_t>((size_t)M * D * 6);
+  w.dy = c.take<float>((size_t)M * D * 4);
+  w.rows16 = c.take<half_t>((size_t)C * D * 2);
+  w.dfeat16 = c.take<half_t>((size_t)C * E * 2);
+  w.dxf = c.take<float>((size_t)C * D * 4);
+  w.bytes = c.off;
+  return w;
+}
+
+// the stash of either tower: x[2 i] = block i's input rows, x[2 i + 1] = its rows before ln_2, x[2 layers] = the last LayerNorm's input
+// (ln_final / ln_post); per block qkv and h; idx: the C gathered row indices (EOT rows / class rows)
+struct Stash {
+  char* base; int64_t M; int D, layers; size_t x_bytes, qkv_bytes, h_bytes;
+  float* x(int k) const { return reinterpret_cast<float*>(base + (size_t)k * x_bytes); }
+  half_t* qkv(int i) const { return reinterpret_cast<half_t*>(base + (size_t)(2 * layers + 1) * x_bytes + (size_t)i * qkv_bytes); }
+  half_t* h(int i) const { return reinterpret_cast<half_t*>(base + (size_t)(2 * layers + 1) * x_bytes + (size_t)layers * qkv_bytes + (size_t)i * h_bytes); }
+  int32_t* idx() const { return reinterpret_cast<int32_t*>(base + (size_t)(2 * layers + 1) * x_bytes + (size_t)layers * (qkv_bytes + h_bytes)); }
+  size_t bytes(int64_t C) const { return (size_t)(2 * layers + 1) * x_bytes + (size_t)layers * (qkv_bytes + h_bytes) + align256((size_t)C * 8); }
+};
+inline Stash carve_stash(void* p, int64_t M, int D, int layers) {
+  Stash st;
+  st.base = static_cast<char*>(p); st.M = M; st.D = D; st.layers = layers;
+  st.x_bytes = align256((size_t)M * D * 4);
+  st.qkv_bytes = align256((size_t)M * D * 6);
+  st.h_bytes = align256((size_t)M * D * 8);
+  return st;
+}
+
+inline int tower_gemm(const half_t* A, int64_t lda, const void* W, int64_t ldw, const float* bias, const float* residual, void* out, int64_t ldo,
+                      int out_dtype, int64_t M, int N, int K, int epilogue, hipStream_t s) {
+  GemmArgs a{};
+  a.A = A; a.lda = lda; a.W = static_cast<const half_t*>(W); a.ldw = ldw; a.bias = bias; a.residual = residual; a.out = out; a.ldo = ldo;
+  a.out_dtype = out_dtype; a.M = (int)M; a.N = N; a.K = K; a.epilogue = epilogue;
+  return launch_gemm(a, s);
+}
+
+// vision_backward.hip: the image tower's training forward and backward (VPT), for the one-call step of prompt_train.hip
+int check_vision_train_call(const char* who, const clipmi_model* m, int B, int n_ctx, int depth, const void* ws, size_t ws_bytes, const void* stash,
+                            size_t stash_bytes);
+int check_vision_dgrad(const char* who, const clipmi_model* m, const clipmi_vision_dgrad* wt);
+int run_vision_train_forward(clipmi_model* m, const void* image, int image_dtype, int B, const float* prompts, int n_ctx, int depth, float* out,
+                             void* workspace, void* stash_p, hipStream_t s);
+int run_vision_backward(clipmi_model* m, const clipmi_vision_dgrad* wt, const float* d_out, int B, int n_ctx, int depth, float* d_prompts,
+                        void* workspace, const void* stash_p, unsigned long long* stats, hipStream_t s);
+
 // text_backward.hip: the training tower's checks and drivers, for the one-call step of prompt_train.hip
 int check_train_call(const char* who, const clipmi_model* m, int n_prompts, const void* ws, size_t ws_bytes, const void* stash, size_t stash_bytes,
                      int seq_rows);

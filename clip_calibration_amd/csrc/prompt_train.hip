@@ -465,6 +465,83 @@ int train_step(const char* who, bool need_losses, size_t need, clipmi_model* m, 
                              dampening, weight_decay, nesterov, step_ws, step_bytes, s);
 }
 
+// ------------------------------------------------------------------------------------------------------------------------------ VPT
+// (reference trainers/classification/vpt.py: the text features are fixed, the image features carry the gradient).  The head is CoOp's
+// with the two sides exchanged: the same norms, logits and cross-entropy rows, then one workgroup per IMAGE.
+// grid (B): dx_b = scale sum_c dz[b, c] u_c (c ascending), q = x_b . dx_b, d_feats[b] = (dx_b - x_b q) / |f_b|.  Workgroup 0 also averages
+// the row losses in float64.
+__global__ __launch_bounds__(THREADS) void vpt_head_grad_kernel(const float* __restrict__ feats, int64_t ld, const float* __restrict__ text, int B, int E, int C,
+                                                                float scale, HeadWs ws, float* __restrict__ d_feats, float* __restrict__ loss_out) {
+  __shared__ float sw[WAVES];
+  const int t = threadIdx.x, b = blockIdx.x;
+  const float* f = feats + (int64_t)b * ld;
+  const float ifn = ws.inf[b];
+  const float* dz = ws.dz + (size_t)b * C;
+  float q = 0.f;
+  for (int e = t; e < E; e += THREADS) {   // pass 1: q
+    float dx = 0.f;
+    for (int c = 0; c < C; ++c) dx = fmaf(dz[c], text[(int64_t)c * E + e] * ws.intx[c], dx);
+    q = fmaf(f[e] * ifn, scale * dx, q);
+  }
+  q = block_sum<WAVES>(q, sw);
+  for (int e = t; e < E; e += THREADS) {   // pass 2: the same dx again, then the projection
+    float dx = 0.f;
+    for (int c = 0; c < C; ++c) dx = fmaf(dz[c], text[(int64_t)c * E + e] * ws.intx[c], dx);
+    d_feats[(int64_t)b * E + e] = (scale * dx - (f[e] * ifn) * q) * ifn;
+  }
+  if (b != 0 || !loss_out) return;   // the same for every thread of the workgroup
+  mean_loss_256(ws.loss, B, loss_out);
+}
+
+int launch_vpt_head(const char* who, const float* feats, int64_t ld, const int64_t* labels, const float* text, int B, int E, int C, float scale,
+                    float grad_scale, float* loss, float* d_feats, void* workspace, size_t workspace_bytes, hipStream_t s) {
+  CLIPMI_REQUIRE(feats && labels && text && d_feats && workspace, CLIPMI_ERR_ARG, "%s: null pointer", who);
+  CLIPMI_REQUIRE(std::isfinite(scale) && std::isfinite(grad_scale), CLIPMI_ERR_ARG, "%s: scale=%g, grad_scale=%g (both finite)", who, scale, grad_scale);
+  CLIPMI_REQUIRE(B >= 1 && C >= 2 && E >= 1 && ld >= E, CLIPMI_ERR_SHAPE, "%s: B=%d C=%d E=%d ld=%lld", who, B, C, E, (long long)ld);
+  CLIPMI_REQUIRE((int64_t)B * C < (1ll << 31), CLIPMI_ERR_SHAPE, "%s: B * C too large", who);
+  CLIPMI_REQUIRE((uintptr_t)workspace % 8 == 0, CLIPMI_ERR_ARG, "%s: the workspace must be 8-byte aligned", who);
+  const size_t need = clipmi_vpt_head_workspace_bytes(B, E, C);
+  CLIPMI_REQUIRE(workspace_bytes >= need, CLIPMI_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, need);
+  const HeadWs ws = head_carve(workspace, B, C);
+  const dim3 threads(THREADS);
+  const float* no_tea = nullptr;
+  float* none = nullptr;
+  hipLaunchKernelGGL(coop_head_norm_kernel, dim3((unsigned)((B + C + WAVES - 1) / WAVES)), threads, 0, s, feats, ld, text, B, E, C, ws, no_tea, none);
+  if (int rc = check_launch("coop_head_norm_kernel")) return rc;
+  hipLaunchKernelGGL(coop_head_logits_kernel, dim3((unsigned)(((int64_t)B * C + WAVES - 1) / WAVES)), threads, 0, s, feats, ld, text, B, E, C, scale, ws);
+  if (int rc = check_launch("coop_head_logits_kernel")) return rc;
+  hipLaunchKernelGGL(coop_head_softmax_kernel, dim3((unsigned)B), threads, 0, s, labels, B, C, grad_scale, ws);
+  if (int rc = check_launch("coop_head_softmax_kernel")) return rc;
+  hipLaunchKernelGGL(vpt_head_grad_kernel, dim3((unsigned)B), threads, 0, s, feats, ld, text, B, E, C, scale, ws, d_feats, loss);
+  return check_launch("vpt_head_grad_kernel");
+}
+
+// one thread per element of the [depth, n_ctx, D] master block: 1 / grad_scale, torch.optim.SGD's rule as torch's GPU kernels round it
+__global__ __launch_bounds__(THREADS) void vpt_step_kernel(const float* __restrict__ d_prompts, float* __restrict__ prompts, float* __restrict__ buf,
+                                                           float* __restrict__ grad_out, int64_t total, float inv_scale, const float* __restrict__ lr,
+                                                           SgdArgs sgd) {
+  const int64_t idx = (int64_t)blockIdx.x * THREADS + threadIdx.x;
+  if (idx >= total) return;
+  const float g = d_prompts[idx] * inv_scale;
+  if (grad_out) grad_out[idx] = g;
+  if (prompts) sgd_element_fma(prompts, buf, idx, g, *lr, sgd);
+}
+
+int launch_vpt_step(const char* who, const float* d_prompts, float* prompts, float* buf, float* grad_out, int depth, int n_ctx, int D, float grad_scale,
+                    const float* lr, int first_step, float momentum, float dampening, float weight_decay, int nesterov, hipStream_t s) {
+  CLIPMI_REQUIRE(d_prompts && (prompts || grad_out), CLIPMI_ERR_ARG, "%s: null pointer (d_prompts and one of prompts, grad_out are required)", who);
+  CLIPMI_REQUIRE(!prompts || lr, CLIPMI_ERR_ARG, "%s: null pointer (a step needs lr)", who);
+  CLIPMI_REQUIRE(depth >= 1 && n_ctx >= 1 && D >= 1, CLIPMI_ERR_SHAPE, "%s: depth=%d n_ctx=%d D=%d", who, depth, n_ctx, D);
+  CLIPMI_REQUIRE(std::isfinite(grad_scale) && grad_scale > 0.f, CLIPMI_ERR_ARG, "%s: grad_scale=%g (finite, > 0)", who, grad_scale);
+  if (int rc = check_sgd(who, momentum, dampening, weight_decay, nesterov)) return rc;
+  CLIPMI_REQUIRE(!prompts || momentum == 0.f || buf, CLIPMI_ERR_ARG, "%s: null pointer (a momentum needs the buffer)", who);
+  const int64_t total = (int64_t)depth * n_ctx * D;
+  CLIPMI_REQUIRE(total < (1ll << 31) * THREADS, CLIPMI_ERR_SHAPE, "%s: prompts too large", who);
+  hipLaunchKernelGGL(vpt_step_kernel, dim3((unsigned)((total + THREADS - 1) / THREADS)), dim3(THREADS), 0, s, d_prompts, prompts, buf, grad_out, total,
+                     1.f / grad_scale, lr, make_sgd_args(momentum, dampening, weight_decay, nesterov, first_step));
+  return check_launch("vpt_step_kernel");
+}
+
 }  // namespace
 }  // namespace clipmi
 
@@ -548,6 +625,55 @@ int clipmi_coop_train_step(clipmi_model* m, const clipmi_text_dgrad* wt, const v
   return train_step("coop_train_step", false, clipmi_coop_train_step_bytes(m, n_prompts, seq_rows, B), m, wt, prompts, dtype, ctx, buf, n_ctx, ctx_per_class, eot,
                     n_prompts, seq_rows, feats, ld, labels, B, scale, grad_scale, MODE_COOP, nullptr, 0.f, 0.f, 0.f, lr, first_step, momentum, dampening,
                     weight_decay, nesterov, loss, grad_out, nullptr, nullptr, workspace, workspace_bytes, stash, stash_bytes, (hipStream_t)stream);
+}
+
+// ---- VPT
+size_t clipmi_vpt_head_workspace_bytes(int B, int E, int C) { return clipmi_prompt_head_workspace_bytes(B, E, C, MODE_COOP); }
+
+int clipmi_vpt_head(const float* feats, int64_t ld, const int64_t* labels, const float* text, int B, int E, int C, float scale, float grad_scale,
+                    float* loss, float* d_feats, void* workspace, size_t workspace_bytes, clipmi_stream_t stream) {
+  return launch_vpt_head("vpt_head", feats, ld, labels, text, B, E, C, scale, grad_scale, loss, d_feats, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int clipmi_vpt_step(const float* d_prompts, float* prompts, float* buf, float* grad_out, int depth, int n_ctx, int D, float grad_scale, const float* lr,
+                    int first_step, float momentum, float dampening, float weight_decay, int nesterov, clipmi_stream_t stream) {
+  return launch_vpt_step("vpt_step", d_prompts, prompts, buf, grad_out, depth, n_ctx, D, grad_scale, lr, first_step, momentum, dampening, weight_decay,
+                         nesterov, (hipStream_t)stream);
+}
+
+size_t clipmi_vpt_train_step_bytes(const clipmi_model* m, int B, int n_ctx, int C) {
+  size_t ws = 0;
+  if (!m || B < 1 || C < 2 || clipmi_vision_train_bytes(m, B, n_ctx, &ws, nullptr) != CLIPMI_OK) return 0;
+  return ws + 2 * align256((size_t)B * m->g.embed_dim * 4) + align256((size_t)m->g.vision_layers * n_ctx * m->g.vision_width * 4) +
+         clipmi_vpt_head_workspace_bytes(B, m->g.embed_dim, C);
+}
+
+int clipmi_vpt_train_step(clipmi_model* m, const clipmi_vision_dgrad* wt, const void* image, int image_dtype, int B, float* prompts, float* buf, int n_ctx,
+                          int depth, const float* text, int C, const int64_t* labels, float scale, float grad_scale, const float* lr, int first_step,
+                          float momentum, float dampening, float weight_decay, int nesterov, float* loss, float* grad_out, void* workspace,
+                          size_t workspace_bytes, void* stash, size_t stash_bytes, clipmi_stream_t stream) {
+  const char* who = "vpt_train_step";
+  hipStream_t s = (hipStream_t)stream;
+  CLIPMI_REQUIRE(B >= 1 && C >= 2, CLIPMI_ERR_SHAPE, "%s: B=%d C=%d", who, B, C);
+  const size_t need = clipmi_vpt_train_step_bytes(m, B, n_ctx, C);
+  size_t tower = 0;
+  if (int rc = clipmi_vision_train_bytes(m, B, n_ctx, &tower, nullptr)) return rc;
+  CLIPMI_REQUIRE(workspace_bytes >= need, CLIPMI_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, need);
+  if (int rc = check_vision_train_call(who, m, B, n_ctx, depth, workspace, tower, stash, stash_bytes)) return rc;
+  if (int rc = check_vision_dgrad(who, m, wt)) return rc;
+  CLIPMI_REQUIRE(image && prompts && text && labels, CLIPMI_ERR_ARG, "%s: null pointer", who);
+  CLIPMI_REQUIRE(image_dtype == CLIPMI_F16 || image_dtype == CLIPMI_F32, CLIPMI_ERR_ARG, "%s: image dtype %d", who, image_dtype);
+  const int E = m->g.embed_dim, D = m->g.vision_width;
+  const size_t head_bytes = clipmi_vpt_head_workspace_bytes(B, E, C);
+  Carver c(static_cast<char*>(workspace) + tower);
+  float* feats = c.take<float>((size_t)B * E * 4);
+  float* d_feats = c.take<float>((size_t)B * E * 4);
+  float* d_prompts = c.take<float>((size_t)m->g.vision_layers * n_ctx * D * 4);
+  void* head_ws = c.take<char>(head_bytes);
+  if (int rc = run_vision_train_forward(m, image, image_dtype, B, prompts, n_ctx, depth, feats, workspace, stash, s)) return rc;
+  if (int rc = launch_vpt_head(who, feats, E, labels, text, B, E, C, scale, grad_scale, loss, d_feats, head_ws, head_bytes, s)) return rc;
+  if (int rc = run_vision_backward(m, wt, d_feats, B, n_ctx, depth, d_prompts, workspace, stash, nullptr, s)) return rc;
+  return launch_vpt_step(who, d_prompts, prompts, buf, grad_out, depth, n_ctx, D, grad_scale, lr, first_step, momentum, dampening, weight_decay, nesterov, s);
 }
 
 }  // extern "C"

@@ -77,6 +77,8 @@ __global__ __launch_bounds__(THREADS) void ln_backward_kernel(const float* __res
   }
 }
 
+}  // namespace
+
 int launch_ln_backward(const float* x, int64_t x_stride, const int32_t* row_idx, const float* gamma, const void* dy, int dy_dtype, float* g,
                        half_t* g16, int64_t rows, int D, float eps, hipStream_t s) {
   if (rows == 0) return CLIPMI_OK;
@@ -87,6 +89,8 @@ int launch_ln_backward(const float* x, int64_t x_stride, const int32_t* row_idx,
     hipLaunchKernelGGL(ln_backward_kernel<half_t>, dim3(grid), dim3(THREADS), 0, s, x, x_stride, row_idx, gamma, (const half_t*)dy, g, g16, (int)rows, D, eps);
   return check_launch("ln_backward_kernel");
 }
+
+namespace {
 
 // ------------------------------------------------------------------------------------------------------------------------ QuickGELU
 __device__ __forceinline__ float sigmoid1702(float h) { return 1.f / (1.f + __expf(-1.702f * h)); }
@@ -124,6 +128,8 @@ __global__ __launch_bounds__(THREADS) void quickgelu_backward_kernel(const half_
 
 inline unsigned grid8(int64_t n) { return (unsigned)((n + 8 * THREADS - 1) / (8 * THREADS)); }
 
+}  // namespace
+
 int launch_quickgelu_forward(const half_t* h, half_t* a, int64_t n, hipStream_t s) {
   if (n == 0) return CLIPMI_OK;
   hipLaunchKernelGGL(quickgelu_forward_kernel, dim3(grid8(n)), dim3(THREADS), 0, s, h, a, n);
@@ -134,6 +140,8 @@ int launch_quickgelu_backward(const half_t* h, const half_t* d_a, half_t* d_h, i
   hipLaunchKernelGGL(quickgelu_backward_kernel, dim3(grid8(n)), dim3(THREADS), 0, s, h, d_a, d_h, n);
   return check_launch("quickgelu_backward_kernel");
 }
+
+namespace {
 
 // ------------------------------------------------------------------------------------------------------------- embedding, statistics
 // xres[c, l, :] = (ctx && 1 <= l <= n_ctx ? ctx[(per_class ? c : 0), l - 1, :] : float(prompts[c, l, :])) + pos[l, :],  l < L of src_L rows
@@ -181,61 +189,14 @@ __global__ __launch_bounds__(THREADS) void operand_stats_kernel(const uint16_t* 
   }
 }
 
+}  // namespace
+
 int launch_operand_stats(const half_t* x, int64_t n, unsigned long long* stats, hipStream_t s) {
   if (!stats || n == 0) return CLIPMI_OK;
   const int64_t blocks = (n + THREADS - 1) / THREADS;
   hipLaunchKernelGGL(operand_stats_kernel, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(THREADS), 0, s, reinterpret_cast<const uint16_t*>(x), n, stats);
   return check_launch("operand_stats_kernel");
 }
-
-// ----------------------------------------------------------------------------------------------------------------- the tower drivers
-
-// workspace shared by the training forward and the backward over M = C * L token rows
-struct TrainWs {
-  half_t* xn;      // [M, D]   LayerNorm output (forward) / fp16 copy of the gradient stream (backward)
-  half_t* att;     // [M, D]   attention output / its gradient
-  half_t* hid;     // [M, 4D]  QuickGELU output / the gradient of c_fc's output
-  half_t* qkv;     // [M, 3D]  backward: dqkv
-  float* dy;       // [M, D]   backward: the fp32 output of the dgrad GEMM in front of a LayerNorm backward
-  half_t* rows16;  // [C, D]   ln_final's output rows
-  half_t* dfeat16; // [C, E]
-  float* dxf;      // [C, D]   d_out text_projection^T
-  size_t bytes;
-};
-TrainWs carve_ws(void* p, int64_t M, int64_t C, int D, int E) {
-  Carver c(p);
-  TrainWs w;
-  w.xn = c.take<half_t>((size_t)M * D * 2);
-  w.att = c.take<half_t>((size_t)M * D * 2);
-  w.hid = c.take<half_t>((size_t)M * D * 8);
-  w.qkv = c.take<half_t>((size_t)M * D * 6);
-  w.dy = c.take<float>((size_t)M * D * 4);
-  w.rows16 = c.take<half_t>((size_t)C * D * 2);
-  w.dfeat16 = c.take<half_t>((size_t)C * E * 2);
-  w.dxf = c.take<float>((size_t)C * D * 4);
-  w.bytes = c.off;
-  return w;
-}
-
-// the stash: x[2 i] = block i's input rows, x[2 i + 1] = its rows before ln_2, x[2 layers] = ln_final's input; per block qkv and h
-struct Stash {
-  char* base; int64_t M; int D, layers; size_t x_bytes, qkv_bytes, h_bytes;
-  float* x(int k) const { return reinterpret_cast<float*>(base + (size_t)k * x_bytes); }
-  half_t* qkv(int i) const { return reinterpret_cast<half_t*>(base + (size_t)(2 * layers + 1) * x_bytes + (size_t)i * qkv_bytes); }
-  half_t* h(int i) const { return reinterpret_cast<half_t*>(base + (size_t)(2 * layers + 1) * x_bytes + (size_t)layers * qkv_bytes + (size_t)i * h_bytes); }
-  int32_t* idx() const { return reinterpret_cast<int32_t*>(base + (size_t)(2 * layers + 1) * x_bytes + (size_t)layers * (qkv_bytes + h_bytes)); }
-  size_t bytes(int64_t C) const { return (size_t)(2 * layers + 1) * x_bytes + (size_t)layers * (qkv_bytes + h_bytes) + align256((size_t)C * 8); }
-};
-Stash carve_stash(void* p, int64_t M, int D, int layers) {
-  Stash st;
-  st.base = static_cast<char*>(p); st.M = M; st.D = D; st.layers = layers;
-  st.x_bytes = align256((size_t)M * D * 4);
-  st.qkv_bytes = align256((size_t)M * D * 6);
-  st.h_bytes = align256((size_t)M * D * 8);
-  return st;
-}
-
-}  // namespace
 
 int check_train_call(const char* who, const clipmi_model* m, int n_prompts, const void* ws, size_t ws_bytes, const void* stash, size_t stash_bytes,
                      int seq_rows) {
@@ -256,15 +217,7 @@ int check_train_call(const char* who, const clipmi_model* m, int n_prompts, cons
 }
 
 namespace {
-
-int gemm(const half_t* A, int64_t lda, const void* W, int64_t ldw, const float* bias, const float* residual, void* out, int64_t ldo, int out_dtype,
-         int64_t M, int N, int K, int epilogue, hipStream_t s) {
-  GemmArgs a{};
-  a.A = A; a.lda = lda; a.W = static_cast<const half_t*>(W); a.ldw = ldw; a.bias = bias; a.residual = residual; a.out = out; a.ldo = ldo;
-  a.out_dtype = out_dtype; a.M = (int)M; a.N = N; a.K = K; a.epilogue = epilogue;
-  return launch_gemm(a, s);
-}
-
+constexpr auto& gemm = tower_gemm;   // model.h: shared with vision_backward.hip
 }  // namespace
 
 int run_train_forward(clipmi_model* m, const void* prompts, int dtype, const float* ctx, int n_ctx, int per_class, const int32_t* eot, int C, int seq_rows,

@@ -6,7 +6,7 @@ distanse_aware_calibration,vl_calibrator}.py``; the Dassl engine, datasets and t
 out of scope, with two exceptions that run on the GPU from cached tower outputs: ``CustomCLIPCalibration.fit_scale``
 (TempScaling's scalar) and ``CLIPAdapterCLIP.fit_adapter`` (CLIP-Adapter's bottleneck; with ``transform=`` under the reference's random train transform instead, as
 ``TaskResCLIP.fit_residuals``), and the prompt learners whose context trains on the GPU through the frozen text tower's backward (``fit_context`` of ``CoOpCLIP``,
-``KgCoOpCLIP``, ``ProGradFitCLIP`` and ``ProDACLIP``; ``fit_prompt_learner`` of ``CoCoOpCLIP``, which trains the context and the meta-net); every other class is an inference mirror.  Class names are tokenised upstream (tokenizer = SURVEY f-3), so constructors take token
+``KgCoOpCLIP``, ``ProGradFitCLIP`` and ``ProDACLIP``; ``fit_prompt_learner`` of ``CoCoOpCLIP``, which trains the context and the meta-net), and ``VPTCLIP.fit_prompts``, which trains the visual prompts through the frozen image tower's backward on every batch; every other class is an inference mirror.  Class names are tokenised upstream (tokenizer = SURVEY f-3), so constructors take token
 ids where the reference takes class-name strings.
 """
 from .zsclip import ZeroshotCLIP  # noqa: F401

@@ -1,4 +1,5 @@
-"""VPT (reference trainers/classification/vpt.py:70-116) -- inference forward only.
+"""VPT (reference trainers/classification/vpt.py:70-116): the inference forward, and ``fit_prompts``, the reference's training of the visual
+prompts on the GPU (``vptfit``).
 
 Vision-side prompting: the CLIP is built with design_details trainer='VPT' (prompt tokens inside the image tower,
 clip/model.py:361-424), the text side is the fixed hand-written prompts "a photo of a {name}." encoded once
@@ -20,3 +21,36 @@ class CustomCLIP(ZeroshotCLIP):
     @property
     def fixed_embeddings(self) -> torch.Tensor:
         return self.text_features
+
+    def fit_prompts(self, train_loader, transform=None, **fit_args):
+        """Train ``visual.VPT`` and ``visual.transformer.resblocks.{i}.VPT_shallow`` on the GPU, starting from the parameters' values,
+        against this model's fixed text features and ``logit_scale`` unless ``fit_args`` say otherwise (vpt.py with both towers' weights
+        frozen).  The fitted prompts are copied into the parameters in place, in their dtype (the fit keeps an fp32 master block) -- that
+        moves their versions, so the next inference forward uses them -- and returned as ``vptfit.fit_prompts`` returns them:
+        fp32 [depth, n_ctx, Dv], slot 0 ``visual.VPT``.  The image tower runs on every step: no features are cached.
+
+        ``transform=None``: ``train_loader`` is a sized iterable of (preprocessed images, labels) batches, iterated once per epoch.
+        ``transform=TrainPreprocess.for_model(model)``: it yields (decoded uint8 images, labels) and every batch goes transform ->
+        ``VPTFitState.step`` with nothing synchronising until the end (``augment.fit_with_transform``).  ``fit_args``: ``epochs`` (5),
+        ``lr`` (0.0025), ``lr_per_epoch``, the optimiser's ``momentum``, ``dampening``, ``weight_decay``, ``nesterov``, ``grad_scale``,
+        ``views`` (with a transform) and ``return_history``; the batch size and the order are the loader's.  The defaults restate the
+        reference's VPT config (SGD, lr 0.0025, 5 epochs)."""
+        import math
+        from .. import vptfit
+        fit_args.setdefault("logit_scale", math.log(self.scale))
+        text = self.text_features.float()
+        if transform is not None:
+            from ..augment import fit_with_transform
+            run = {k: fit_args.pop(k) for k in ("lr_per_epoch", "views", "return_history") if k in fit_args}
+            epochs, lr = fit_args.pop("epochs", 5), fit_args.pop("lr", 0.0025)
+            state = vptfit.VPTFitState(self.clip_model, text, **fit_args)
+            losses = fit_with_transform(state, lambda x: x, text.shape[0], train_loader, transform, epochs, lr, **run)
+            fitted = state.prompts if losses is None else (state.prompts, losses)
+        else:
+            fitted = vptfit.fit_prompts(train_loader, None, self.clip_model, text, **fit_args)
+        block = fitted[0] if isinstance(fitted, tuple) else fitted
+        shallow, deep = self.clip_model.ivlp_vision_prompts()
+        with torch.no_grad():
+            for p, v in zip([shallow] + list(deep), block):
+                p.copy_(v)
+        return fitted

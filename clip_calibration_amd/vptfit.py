@@ -1,0 +1,356 @@
+"""VPT's visual prompts trained on the GPU (reference trainers/classification/vpt.py; clip/model.py VisionTransformer with prompt rows).
+
+The reference trains the prompt tokens inside the image tower -- ``visual.VPT`` [n_ctx, Dv], appended behind the patch rows after the
+positional embedding, and ``visual.transformer.resblocks.{i}.VPT_shallow`` [n_ctx, Dv] for 1 <= i < depth, which overwrite the last
+``n_ctx`` token rows before block i -- against fixed text features: every step runs the image tower on the batch, normalises, takes
+``F.cross_entropy`` of ``exp(logit_scale)`` times the cosine and one ``torch.optim.SGD`` step on the prompts.  The prompts reach the loss
+only through the image tower, so a step needs that tower's backward.  csrc/vision_backward.hip computes it with the tower frozen: a
+training forward that keeps what the backward needs in a stash, and the backward (every Linear's backward is the forward's fp16 GEMM on
+a transposed copy of the weight, packed once per bound model; the attention backward is ``clipmi_attention_backward_full``);
+csrc/prompt_train.hip has the image-side loss head and the SGD step -- no autograd graph.  fp16 GEMM operands, fp32 accumulation, fp32
+residual and gradient streams, an fp32 master block ``[depth, n_ctx, Dv]`` of the prompts (slot 0 is ``visual.VPT``); the forward reads
+the masters rounded through fp16, the reference's ``.half()``.  DESIGN.md "VPT fit" has the data flow.
+
+``grad_scale``: as in ``coopfit`` -- the whole backward carries ``grad_scale`` times the gradient (a power of two), the head multiplies
+and the step divides.  profiles/vptfit_parity.txt has the measurement behind the default.
+
+``prompt_gradient`` returns one batch's loss and gradient (the diagnostic entry point of the tests).  ``VPTFitState.step`` takes one
+batch of preprocessed images; ``fit_prompts`` runs epochs over a tensor of images or a loader of (images, labels) batches and enqueues
+every step with one synchronisation at the end.  The image tower runs on every step: nothing is cached.
+
+The defaults -- SGD at 0.0025 with momentum 0.9 and weight decay 5e-4, 5 epochs, a constant warm-up epoch handing over to a cosine
+schedule -- restate the reference's VPT config and Dassl's public defaults and are UNVERIFIED here; each is an argument.
+
+Not covered: MaPLe, PromptSRC and IVLP training (text-side deep prompts and coupling functions on top of this), ViT-L lengths (more
+than 224 token rows per image), ``nn.DataParallel``, the reference's ``amp`` branch, the ResNet towers.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+from typing import Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import _lib, ops
+from ._lib import check, lib
+from .coopfit import _check_grad_scale, _check_sgd
+from .taskresfit import _labels, _need_gpu
+from .tempfit import cosine_warmup_schedule, steps_per_epoch
+
+# 2^12: CoOp's value (profiles/coopfit_parity.txt) holds for the image tower's backward at the ViT-B/16 geometry as well
+# (profiles/vptfit_parity.txt, "grad_scale").  A model with much larger gradients overflows fp16 at this scale -- the prompts then turn
+# NaN, they do not go wrong silently; pass a smaller power of two.
+DEFAULT_GRAD_SCALE = 4096.0
+MAX_ROWS = 224         # token rows per image that clipmi_vision_encoder_backward takes (the attention backward's limit)
+
+_DT = {torch.float16: _lib.F16, torch.float32: _lib.F32}
+
+
+def model_prompts(model) -> torch.Tensor:
+    """The model's own prompt parameters as one fp32 block [depth, n_ctx, Dv] (slot 0: ``visual.VPT``), after the checks of the design."""
+    who = "vptfit"
+    if getattr(model, "is_resnet", False):
+        raise ValueError(f"{who}: prompt tokens apply to the ViT towers only (the ResNet tower has none)")
+    dd = model.design_details
+    if dd.get("trainer") != "VPT" or int(dd.get("vision_depth", 0)) < 1:
+        raise ValueError(f"{who}: needs a CLIP built with design_details trainer='VPT' and vision_depth >= 1, got trainer={dd.get('trainer')!r}")
+    shallow, deep = model.ivlp_vision_prompts()
+    if shallow is None:
+        raise ValueError(f"{who}: the model carries no visual.VPT")
+    return torch.stack([shallow.detach().float()] + [p.detach().float() for p in deep])
+
+
+def _check_prompts(who: str, model, prompts: torch.Tensor):
+    model_prompts(model)     # the design's checks
+    g = model.geometry
+    own, _ = model.ivlp_vision_prompts()
+    if not isinstance(prompts, torch.Tensor) or prompts.dim() != 3 or prompts.shape[2] != g.vision_width or not prompts.dtype.is_floating_point:
+        raise ValueError(f"{who}: prompts {tuple(getattr(prompts, 'shape', ()))} must be [depth, n_ctx, {g.vision_width}]")
+    depth, n_ctx = int(prompts.shape[0]), int(prompts.shape[1])
+    if n_ctx != int(own.shape[0]):
+        raise ValueError(f"{who}: n_ctx={n_ctx} does not match the model's visual.VPT ({int(own.shape[0])} rows)")
+    if not 1 <= depth <= g.vision_layers:
+        raise ValueError(f"{who}: depth={depth} for {g.vision_layers} layers")
+    tokens = (g.image_resolution // g.vision_patch_size) ** 2 + 1
+    if tokens + n_ctx > MAX_ROWS:
+        raise ValueError(f"{who}: {tokens} tokens + {n_ctx} prompt rows = {tokens + n_ctx} rows per image; the backward takes at most {MAX_ROWS}")
+    return depth, n_ctx
+
+
+def _dgrad(model):
+    """The transposed fp16 copies of the frozen image tower's weights (clipmi_vision_dgrad), packed once per bound model and again when a
+    vision weight's version moves."""
+    model._ensure_bound()
+    blocks = list(model.visual.transformer.resblocks)
+    ws = [model.visual.proj] + [w for b in blocks for w in (b.attn.in_proj_weight, b.attn.out_proj.weight, b.mlp.c_fc.weight, b.mlp.c_proj.weight)]
+    key = (id(model._bound),) + tuple((w.data_ptr(), w._version) for w in ws)
+    hit = model.__dict__.get("_vpt_dgrad")
+    if hit is not None and hit[0] == key:
+        return hit[1]
+    keep = []
+
+    def t16(w):
+        t = w.detach().to(torch.float16).t().contiguous()
+        keep.append(t)
+        return t.data_ptr()
+
+    arr = (_lib.BlockDgrad * len(blocks))()
+    for i, b in enumerate(blocks):
+        arr[i] = _lib.BlockDgrad(t16(b.attn.in_proj_weight), t16(b.attn.out_proj.weight), t16(b.mlp.c_fc.weight), t16(b.mlp.c_proj.weight))
+    proj = model.visual.proj.detach().to(torch.float16).contiguous()
+    keep.append(proj)
+    vd = _lib.VisionDgrad(proj.data_ptr(), arr)
+    model.__dict__["_vpt_dgrad"] = (key, (vd, arr, keep))
+    return vd, arr, keep
+
+
+def _check_text(who: str, model, text_features) -> torch.Tensor:
+    E = int(model.geometry.embed_dim)
+    if not isinstance(text_features, torch.Tensor) or text_features.dim() != 2 or text_features.shape[0] < 2 or text_features.shape[1] != E:
+        raise ValueError(f"{who}: text_features {tuple(getattr(text_features, 'shape', ()))} must be [C >= 2, E = {E}]")
+    _need_gpu(text_features, "text_features")
+    return text_features.detach().to(torch.float32).contiguous()
+
+
+class _Tower:
+    """The frozen image tower in training mode: workspace, stash, features and the prompts' gradient for batches of up to ``B`` images."""
+
+    def __init__(self, who: str, model, depth: int, n_ctx: int):
+        dev = model.device
+        if dev.type != "cuda":
+            raise RuntimeError(f"clipmi: {who} needs the model on a ROCm GPU (model.to('cuda')); the HIP path has no CPU fallback")
+        if dev.index != torch.cuda.current_device():
+            raise RuntimeError(f"clipmi: the model is on {dev} but the current device is cuda:{torch.cuda.current_device()}")
+        self.model, self.depth, self.n_ctx = model, depth, n_ctx
+        g = model.geometry
+        self.D, self.E, self.R = g.vision_width, g.embed_dim, g.image_resolution
+        model._ensure_bound()
+        self.dgrad = _dgrad(model)
+        self.B = self.ws_B = 0
+        self.ws = self.stash = self.feats = self.step_ws = None
+        self.step_key = None
+        self.d_prompts = torch.empty(depth, n_ctx, self.D, dtype=torch.float32, device=dev)
+
+    def images(self, who: str, images) -> torch.Tensor:
+        images = ops._dev(images, "images", (torch.float16, torch.float32))
+        if images.dim() != 4 or tuple(images.shape[1:]) != (3, self.R, self.R) or images.shape[0] < 1:
+            raise ValueError(f"{who}: expected images [B >= 1, 3, {self.R}, {self.R}], got {tuple(images.shape)}")
+        return images
+
+    def size(self, B: int, tower_ws: bool = True) -> None:
+        """Room for a batch of ``B``: the stash always, the separate calls' workspace and feature rows only with ``tower_ws``."""
+        dev = self.model.device
+        wsb, stb = C.c_size_t(0), C.c_size_t(0)
+        if B > self.B or (tower_ws and B > self.ws_B):
+            check(lib.clipmi_vision_train_bytes(self.model._handle, B, self.n_ctx, C.byref(wsb), C.byref(stb)), "clipmi_vision_train_bytes")
+        if B > self.B:
+            self.stash = torch.empty(max(stb.value, 256), dtype=torch.uint8, device=dev)
+            self.B = B
+        if tower_ws and B > self.ws_B:
+            self.ws = torch.empty(max(wsb.value, 256), dtype=torch.uint8, device=dev)
+            self.feats = torch.empty(B, self.E, dtype=torch.float32, device=dev)
+            self.ws_B = B
+
+    def forward(self, images: torch.Tensor, prompts: torch.Tensor, flags: int = _lib.CALL_DEFAULT) -> torch.Tensor:
+        m, B = self.model, images.shape[0]
+        self.size(B)
+        with m._launch_lock:
+            check(lib.clipmi_vision_encoder_train(m._handle, images.data_ptr(), _DT[images.dtype], B, prompts.data_ptr(), self.n_ctx, self.depth,
+                                                  self.feats.data_ptr(), self.ws.data_ptr(), self.ws.numel(), self.stash.data_ptr(), self.stash.numel(),
+                                                  int(flags), ops._stream()), "clipmi_vision_encoder_train")
+        return self.feats[:B]
+
+    def backward(self, d_feats: torch.Tensor, stats: Optional[torch.Tensor] = None) -> torch.Tensor:
+        m, B = self.model, d_feats.shape[0]
+        with m._launch_lock:
+            check(lib.clipmi_vision_encoder_backward(m._handle, C.byref(self.dgrad[0]), d_feats.data_ptr(), B, self.n_ctx, self.depth,
+                                                     self.d_prompts.data_ptr(), self.ws.data_ptr(), self.ws.numel(), self.stash.data_ptr(),
+                                                     self.stash.numel(), None if stats is None else stats.data_ptr(), ops._stream()),
+                  "clipmi_vision_encoder_backward")
+        return self.d_prompts
+
+    def one_call_workspace(self, B: int, n_cls: int) -> torch.Tensor:
+        need = lib.clipmi_vpt_train_step_bytes(self.model._handle, B, self.n_ctx, n_cls)
+        if self.step_ws is None or self.step_ws.numel() < need:
+            self.step_ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.model.device)
+        return self.step_ws
+
+
+def vpt_head(feats: torch.Tensor, labels: torch.Tensor, text: torch.Tensor, scale: float, grad_scale: float, loss: Optional[torch.Tensor] = None):
+    """clipmi_vpt_head: ``(loss fp32 [1], d_feats fp32 [B, E])`` of the batch (include/clipmi.h)."""
+    B, E = feats.shape
+    Cn = text.shape[0]
+    need = lib.clipmi_vpt_head_workspace_bytes(B, E, Cn)
+    ws = torch.empty(max(need, 8), dtype=torch.uint8, device=feats.device)
+    loss = torch.empty(1, dtype=torch.float32, device=feats.device) if loss is None else loss
+    d_feats = torch.empty(B, E, dtype=torch.float32, device=feats.device)
+    check(lib.clipmi_vpt_head(feats.data_ptr(), feats.stride(0), labels.data_ptr(), text.data_ptr(), B, E, Cn, scale, grad_scale, loss.data_ptr(),
+                              d_feats.data_ptr(), ws.data_ptr(), ws.numel(), ops._stream()), "clipmi_vpt_head")
+    return loss, d_feats
+
+
+def vpt_step(d_prompts: torch.Tensor, grad_scale: float, prompts: Optional[torch.Tensor] = None, buf: Optional[torch.Tensor] = None, lr=None,
+             first_step: bool = True, momentum: float = 0.0, dampening: float = 0.0, weight_decay: float = 0.0, nesterov: bool = False,
+             want_grad: bool = True) -> Optional[torch.Tensor]:
+    """clipmi_vpt_step: the gradient ``d_prompts / grad_scale`` (returned with ``want_grad``) and, with ``prompts``, SGD's step in place."""
+    depth, n_ctx, D = d_prompts.shape
+    grad = torch.empty_like(d_prompts) if want_grad else None
+    check(lib.clipmi_vpt_step(d_prompts.data_ptr(), None if prompts is None else prompts.data_ptr(), None if buf is None else buf.data_ptr(),
+                              None if grad is None else grad.data_ptr(), depth, n_ctx, D, grad_scale, None if lr is None else lr.data_ptr(),
+                              int(first_step), float(momentum), float(dampening), float(weight_decay), int(bool(nesterov)), ops._stream()),
+          "clipmi_vpt_step")
+    return grad
+
+
+def _labels_dev(who: str, labels, B: int, n_cls: int, dev) -> torch.Tensor:
+    if isinstance(labels, torch.Tensor) and labels.is_cuda and labels.dtype == torch.int64:
+        if labels.shape != (B,):
+            raise ValueError(f"{who}: {B} images need {B} labels, got {tuple(labels.shape)}")
+        return labels
+    return torch.from_numpy(_labels(who, labels, B, n_cls).astype(np.int64)).to(dev)
+
+
+def prompt_gradient(model, prompts: torch.Tensor, images: torch.Tensor, labels, text_features: torch.Tensor, logit_scale: float = 4.6052,
+                    grad_scale: float = DEFAULT_GRAD_SCALE, return_operand_stats: bool = False, flags: int = _lib.CALL_DEFAULT):
+    """``(loss, grad)`` of ``F.cross_entropy(exp(logit_scale) * normalise(encode_image(images; prompts)) @ normalise(text_features).T,
+    labels)`` with respect to ``prompts`` [depth, n_ctx, Dv] (slot 0: ``visual.VPT``), on the GPU: loss fp32 [1], grad fp32 of the block's
+    shape.  ``return_operand_stats`` adds a dict over every fp16 dgrad-GEMM operand element: ``elements``, ``zeros``, ``subnormals``,
+    ``max`` -- the measurement behind the default ``grad_scale``.  A diagnostic entry point: every call allocates a workspace and a stash
+    of its own (41.6 MB per image at ViT-B/16 with 8 prompt rows); a training loop keeps a ``VPTFitState``."""
+    who = "prompt_gradient"
+    depth, n_ctx = _check_prompts(who, model, prompts)
+    gs = _check_grad_scale(who, grad_scale)
+    if not math.isfinite(logit_scale):
+        raise ValueError(f"{who}: logit_scale={logit_scale} (finite)")
+    text = _check_text(who, model, text_features)
+    tower = _Tower(who, model, depth, n_ctx)
+    images = tower.images(who, images)
+    dev = images.device
+    labels_d = _labels_dev(who, labels, images.shape[0], text.shape[0], dev)
+    master = prompts.detach().to(device=dev, dtype=torch.float32, copy=True).contiguous()
+    feats = tower.forward(images, master, flags)
+    scale = float(np.float32(math.exp(logit_scale)))
+    stats = torch.zeros(4, dtype=torch.int64, device=dev) if return_operand_stats else None
+    loss, d_feats = vpt_head(feats, labels_d, text, scale, gs)
+    grad = vpt_step(tower.backward(d_feats, stats), gs)
+    if not return_operand_stats:
+        return loss, grad
+    s = stats.cpu().numpy()
+    top = float(np.array([int(s[3])], dtype=np.uint16).view(np.float16)[0])
+    return loss, grad, {"elements": int(s[0]), "zeros": int(s[1]), "subnormals": int(s[2]), "max": top}
+
+
+def image_features(model, prompts: torch.Tensor, images: torch.Tensor) -> torch.Tensor:
+    """The raw image features fp32 [B, E] of the training forward at ``prompts``: what the loss head is given.  Allocates a workspace and
+    a stash per call, as ``prompt_gradient`` does."""
+    who = "image_features"
+    depth, n_ctx = _check_prompts(who, model, prompts)
+    tower = _Tower(who, model, depth, n_ctx)
+    images = tower.images(who, images)
+    return tower.forward(images, prompts.detach().to(device=images.device, dtype=torch.float32, copy=True).contiguous()).clone()
+
+
+class VPTFitState:
+    """The training state of VPT's prompts: the fp32 master block ``prompts`` [depth, n_ctx, Dv] (None: the model's own parameters), SGD's
+    momentum buffer, the tower's stash and the number of steps taken.  ``step`` enqueues one forward, backward and update and does not
+    synchronise."""
+
+    def __init__(self, model, text_features: torch.Tensor, logit_scale: float = 4.6052, prompts: Optional[torch.Tensor] = None,
+                 momentum: float = 0.9, dampening: float = 0.0, nesterov: bool = False, weight_decay: float = 5e-4,
+                 grad_scale: float = DEFAULT_GRAD_SCALE):
+        who = "VPTFitState"
+        if prompts is None:
+            prompts = model_prompts(model)
+        self.depth, self.n_ctx = _check_prompts(who, model, prompts)
+        self.grad_scale = _check_grad_scale(who, grad_scale)
+        _check_sgd(who, momentum, dampening, weight_decay, nesterov)
+        if not math.isfinite(logit_scale):
+            raise ValueError(f"{who}: logit_scale={logit_scale} (finite)")
+        self.text = _check_text(who, model, text_features)
+        self.C = int(self.text.shape[0])
+        self.tower = _Tower(who, model, self.depth, self.n_ctx)
+        self.prompts = prompts.detach().to(device=model.device, dtype=torch.float32, copy=True).contiguous()
+        self.buf = torch.zeros_like(self.prompts) if momentum != 0.0 else None
+        self.scale = float(np.float32(math.exp(logit_scale)))
+        self.momentum, self.dampening, self.nesterov, self.weight_decay = momentum, dampening, nesterov, weight_decay
+        self.steps = 0
+
+    def step(self, images: torch.Tensor, labels, lr, want_loss: bool = False, one_call: bool = False) -> Optional[torch.Tensor]:
+        """One optimiser step on the batch ``images`` [B, 3, R, R] (preprocessed, fp16 or fp32, on the GPU) and ``labels`` [B] at the rate
+        ``lr``: an fp32 tensor of one element on the device is read where it lies; a Python number is uploaded on every call.  A label
+        tensor on the GPU is taken as it is -- a label outside [0, C) then makes the prompts NaN, it is never used as an address; host
+        labels are range-checked.  ``one_call``: the same launches through clipmi_vpt_train_step, whose workspace holds the tower's (the
+        separate calls' workspace is then not allocated; the stash is the same).  Returns the batch loss, fp32 [1] on the device, when
+        ``want_loss``."""
+        who = "VPTFitState.step"
+        t, m = self.tower, self.tower.model
+        images = t.images(who, images)
+        dev, B = images.device, images.shape[0]
+        labels_d = _labels_dev(who, labels, B, self.C, dev)
+        lr_d = ops._dev(lr, "lr", (torch.float32,)) if isinstance(lr, torch.Tensor) else torch.tensor([float(lr)], dtype=torch.float32).to(dev)
+        first = self.steps == 0
+        sgd = (float(self.momentum), float(self.dampening), float(self.weight_decay), int(bool(self.nesterov)))
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        if one_call:
+            t.size(B, tower_ws=False)
+            ws = t.one_call_workspace(B, self.C)
+            with m._launch_lock:
+                check(lib.clipmi_vpt_train_step(m._handle, C.byref(t.dgrad[0]), images.data_ptr(), _DT[images.dtype], B, self.prompts.data_ptr(),
+                                                None if self.buf is None else self.buf.data_ptr(), self.n_ctx, self.depth, self.text.data_ptr(), self.C,
+                                                labels_d.data_ptr(), self.scale, self.grad_scale, lr_d.data_ptr(), int(first), *sgd, loss.data_ptr(),
+                                                None, ws.data_ptr(), ws.numel(), t.stash.data_ptr(), t.stash.numel(), ops._stream()),
+                      "clipmi_vpt_train_step")
+        else:
+            feats = t.forward(images, self.prompts)
+            _, d_feats = vpt_head(feats, labels_d, self.text, self.scale, self.grad_scale, loss)
+            vpt_step(t.backward(d_feats), self.grad_scale, self.prompts, self.buf, lr_d, first, *sgd, want_grad=False)
+        self.steps += 1
+        return loss if want_loss else None
+
+
+def fit_prompts(images_or_loader, labels, model, text_features: torch.Tensor, prompts: Optional[torch.Tensor] = None, logit_scale: float = 4.6052,
+                lr: float = 0.0025, epochs: int = 5, batch_size: int = 32, momentum: float = 0.9, dampening: float = 0.0,
+                weight_decay: float = 5e-4, nesterov: bool = False, grad_scale: float = DEFAULT_GRAD_SCALE,
+                lr_per_epoch: Optional[Sequence[float]] = None, drop_last: bool = False, return_history: bool = False):
+    """Train VPT's prompts starting from ``prompts`` (not modified; None = the model's own parameters): ``epochs`` passes of
+    ``torch.optim.SGD(lr, momentum, dampening, weight_decay, nesterov)``.  ``images_or_loader`` is a tensor of preprocessed images
+    [N, 3, R, R] with ``labels`` [N], cut into batches of ``batch_size`` in order (the last one short unless ``drop_last``), or a sized
+    iterable of (images, labels) batches iterated once per epoch (``labels`` None, ``batch_size`` unused).  ``lr_per_epoch`` gives every
+    epoch's rate; None takes ``cosine_warmup_schedule(lr, epochs)``.  The image tower runs on every step; nothing synchronises until the
+    one wait at the end.  Returns the fitted fp32 block [depth, n_ctx, Dv] on the device, or ``(prompts, per-step batch losses)`` with
+    ``return_history``.  The model's parameters are NOT written: ``trainers.vpt.CustomCLIP.fit_prompts`` does that."""
+    who = "fit_prompts"
+    epochs = int(epochs)
+    if epochs < 0:
+        raise ValueError(f"{who}: epochs={epochs} (>= 0)")
+    state = VPTFitState(model, text_features, logit_scale, prompts, momentum, dampening, nesterov, weight_decay, grad_scale)
+    if isinstance(images_or_loader, torch.Tensor):
+        N, bs = images_or_loader.shape[0], int(batch_size)
+        if bs < 1:
+            raise ValueError(f"{who}: batch_size={batch_size} (>= 1)")
+        per_epoch = steps_per_epoch(N, bs, drop_last)
+        lab = _labels_dev(who, labels, N, state.C, model.device)
+        batches = [(images_or_loader[k * bs:min((k + 1) * bs, N)], lab[k * bs:min((k + 1) * bs, N)]) for k in range(per_epoch)]
+    else:
+        batches = images_or_loader
+        per_epoch = len(batches)
+    rates = cosine_warmup_schedule(lr, epochs) if lr_per_epoch is None else [float(r) for r in lr_per_epoch]
+    if len(rates) != epochs:
+        raise ValueError(f"{who}: {len(rates)} learning rates for {epochs} epochs")
+    losses = []
+    if epochs * per_epoch:
+        dev = model.device
+        lr_steps = torch.from_numpy(np.repeat(np.asarray(rates, np.float64), per_epoch).astype(np.float32)).to(dev)
+        step = 0
+        for _ in range(epochs):
+            for x, y in batches:
+                loss = state.step(x, y, lr_steps[step:step + 1], want_loss=return_history)
+                if return_history:
+                    losses.append(loss)
+                step += 1
+        torch.cuda.current_stream(dev).synchronize()   # the run's one synchronisation
+    if return_history:
+        return state.prompts, (torch.cat(losses).cpu().numpy() if losses else np.zeros(0, np.float32))
+    return state.prompts

@@ -714,6 +714,12 @@ int clipmi_layernorm_backward(const float* x, int64_t x_stride, const int32_t* r
                               float* g, void* g16, int rows, int D, float eps, clipmi_stream_t stream);
 int clipmi_quickgelu_backward(const void* h, const void* d_a, void* d_h, int64_t n, clipmi_stream_t stream);
 int clipmi_attention_backward(const void* qkv, const void* d_out, void* dqkv, int N, int L, int H, clipmi_stream_t stream);
+/* clipmi_attention_backward_full: the same backward WITHOUT a mask for 1 <= L <= 224 token rows per sequence, the lengths of the image
+ *   towers at 224 px with their prompt rows (the lengths clipmi_attention serves with one key block); layouts, rounding points and
+ *   refusals as above (L > 224: CLIPMI_ERR_SHAPE).  One workgroup per (sequence, head) holds Q, K, V and dO in LDS; P and dS are
+ *   never stored: a query-owned phase forms the row statistics (maximum, 1 / sum, rowsum(dP o P)) and dQ, a key-owned phase recomputes
+ *   S and dP per pair of query tiles and accumulates dK and dV in registers.  No atomics, the same inputs give the same bits. */
+int clipmi_attention_backward_full(const void* qkv, const void* d_out, void* dqkv, int N, int L, int H, clipmi_stream_t stream);
 
 /* CoOp's loss head (coop.py:205-222 + F.cross_entropy): feats fp32 [B, E] raw image features with row stride ld >= E, labels int64 [B],
  * text fp32 [C, E] raw text features, scale = exp(logit_scale):
@@ -801,6 +807,84 @@ int clipmi_coop_train_step(clipmi_model* m, const clipmi_text_dgrad* wt, const v
                            const int64_t* labels, int B, float scale, float grad_scale, const float* lr, int first_step, float momentum,
                            float dampening, float weight_decay, int nesterov, float* loss, float* grad_out, void* workspace,
                            size_t workspace_bytes, void* stash, size_t stash_bytes, clipmi_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------
+ * VPT's visual prompts trained on the device (trainers/classification/vpt.py; clip/model.py VisionTransformer with prompt rows): the
+ * gradient of the image features with respect to the prompt rows `visual.VPT` and `visual.transformer.resblocks.{i}.VPT_shallow`
+ * with the image tower frozen, the image-side cross-entropy head and torch.optim.SGD's step on the prompts (csrc/vision_backward.hip,
+ * csrc/prompt_train.hip, DESIGN.md "VPT fit").  The blocks' backward is the text tower's without a mask (clipmi_attention_backward_full).
+ * The whole backward carries grad_scale * gradient; only clipmi_vpt_head and clipmi_vpt_step know the factor.
+ * These exports are additive: the ABI version does not change with them.
+ * ---------------------------------------------------------------------------------------------------- */
+
+/* The transposed weight copies of the frozen image tower, packed once by the caller like clipmi_text_dgrad: proj is visual.proj itself,
+ * fp16 [Dv, E]; blocks a host array [vision_layers]. */
+typedef struct clipmi_vision_dgrad {
+  const void* proj;                  /* [Dv, E] */
+  const clipmi_block_dgrad* blocks;  /* host array [vision_layers] */
+} clipmi_vision_dgrad;
+
+/* Bytes of the workspace and of the stash the calls below need for B images with n_ctx prompt rows each.  Either pointer may be NULL.
+ * Both are 0 for arguments the calls refuse (tokens + n_ctx > 224: CLIPMI_ERR_SHAPE). */
+int clipmi_vision_train_bytes(const clipmi_model* m, int B, int n_ctx, size_t* workspace_bytes, size_t* stash_bytes);
+
+/* clipmi_encode_image with VPT's prompts and everything its backward needs kept in `stash`.  image [B, 3, R, R] fp16 | fp32; prompts fp32
+ * [depth, n_ctx, Dv], the masters: slot 0 is visual.VPT, whose rows are appended behind the patch rows after the positional embedding and
+ * pass through ln_pre; slot i (1 <= i < depth) overwrites the LAST n_ctx token rows of every image before block i.  The values the
+ * forward reads are the masters rounded through fp16 (the reference's .half()).  L = tokens + n_ctx rows per image.  The blocks run
+ * LayerNorm, GEMM, attention (no mask) as separate launches on the fp32 residual stream, c_fc keeps its fp16 pre-activation and
+ * QuickGELU is an element-wise launch on that rounded value; then ln_post on the class rows and the projection: out fp32 [B, E].
+ * Requires a patch size of 8, 16 or 32, Dv % 64 == 0, E % 64 == 0, L <= 224 (CLIPMI_ERR_SHAPE), 1 <= depth <= vision_layers.
+ * CLIPMI_CALL_STREAM_F16: CLIPMI_ERR_STATE.  workspace and stash 256-byte aligned.
+ *
+ * Byte layout of the stash: clipmi_text_encoder_train's with M = B * L token rows, Dt = Dv and layers = vision_layers --
+ *   2 * layers + 1 fp32 slabs [M, Dv] of align256(M * Dv * 4) bytes: x_in(0), x_mid(0), ..., x_in(layers - 1), x_mid(layers - 1), the input
+ *       of ln_post; x_in(0) is ln_pre's output, x_in(i) the output of block i - 1 with block i's prompt rows in place;
+ *   layers fp16 slabs [M, 3 Dv] of align256(M * Dv * 6) bytes: qkv(i);  layers fp16 slabs [M, 4 Dv] of align256(M * Dv * 8) bytes: c_fc's
+ *       pre-activation;
+ *   B int32: the class row indices b * L (align256(B * 8) bytes reserved; the B words behind them are zero);
+ * and behind it the rounded prompts fp32 [depth, n_ctx, Dv] (align256(layers * n_ctx * Dv * 4) bytes reserved).  The backward only reads
+ * the stash. */
+int clipmi_vision_encoder_train(clipmi_model* m, const void* image, int image_dtype, int B, const float* prompts, int n_ctx, int depth,
+                                float* out, void* workspace, size_t workspace_bytes, void* stash, size_t stash_bytes, unsigned flags,
+                                clipmi_stream_t stream);
+
+/* The backward of the call above from the stash it left: d_out fp32 [B, E] -> d_prompts fp32 [depth, n_ctx, Dv] = the gradient of the
+ * prompts (the rounding passes it straight through), overwritten.  Tail: d_out proj^T, ln_post's backward on the class rows scattered into
+ * the zeroed stream; per block, last to first, clipmi_text_encoder_backward's sequence with clipmi_attention_backward_full; after block
+ * i's ln_1 backward (1 <= i < depth) d_prompts[i][j] = sum_b g[b * L + tokens + j] (b ascending) and those rows of the stream are zeroed;
+ * after block 0 the batch sum of the prompt rows goes through ln_pre's backward on n_ctx rows (LayerNorm's backward is linear in dy and
+ * every image's pre-LN row is the prompt).  Nothing below ln_pre is differentiated.  operand_stats as clipmi_text_encoder_backward's. */
+int clipmi_vision_encoder_backward(clipmi_model* m, const clipmi_vision_dgrad* wt, const float* d_out, int B, int n_ctx, int depth,
+                                   float* d_prompts, void* workspace, size_t workspace_bytes, const void* stash, size_t stash_bytes,
+                                   unsigned long long* operand_stats, clipmi_stream_t stream);
+
+/* VPT's loss head: clipmi_coop_head with the gradient on the image side.  feats fp32 [B, E] (row stride ld), text fp32 [C, E]:
+ *   x_b = f_b / |f_b|;  u_c = t_c / |t_c|;  z = scale X U^T;  loss = mean_b CE(z_b, y_b);  dz = grad_scale (softmax(z) - onehot(y)) / B
+ *   dx_b = scale sum_c dz[b, c] u_c (c ascending);  d_feats[b, :] = (dx_b - x_b (x_b . dx_b)) / |f_b|
+ * loss fp32 [1] or NULL, the float64 mean of the row losses; d_feats fp32 [B, E] dense.  A label outside [0, C) is never used as an
+ * address: it makes the loss and that row's gradient NaN.  workspace (8-byte aligned) of clipmi_vpt_head_workspace_bytes bytes.  Four
+ * launches.  Refusals as clipmi_coop_head's. */
+size_t clipmi_vpt_head_workspace_bytes(int B, int E, int C);
+int clipmi_vpt_head(const float* feats, int64_t ld, const int64_t* labels, const float* text, int B, int E, int C, float scale,
+                    float grad_scale, float* loss, float* d_feats, void* workspace, size_t workspace_bytes, clipmi_stream_t stream);
+
+/* torch.optim.SGD's step on the [depth, n_ctx, D] master block, one launch: grad = d_prompts / grad_scale, then clipmi_ctx_step's rule on
+ * every element (the same arguments; equal to torch.optim.SGD on the GPU bit for bit).  grad_out (the block's shape, may be NULL)
+ * receives the gradient before weight decay.  prompts == NULL: only grad_out is written. */
+int clipmi_vpt_step(const float* d_prompts, float* prompts, float* buf, float* grad_out, int depth, int n_ctx, int D, float grad_scale,
+                    const float* lr, int first_step, float momentum, float dampening, float weight_decay, int nesterov,
+                    clipmi_stream_t stream);
+
+/* One training step of VPT as ONE call: clipmi_vision_encoder_train, clipmi_vpt_head, clipmi_vision_encoder_backward and clipmi_vpt_step
+ * enqueued in this order on `stream` -- the same launches, the same bits.  prompts is the fp32 master, updated in place.  workspace of
+ * clipmi_vpt_train_step_bytes(m, B, n_ctx, C) bytes (256-byte aligned), stash as clipmi_vision_train_bytes reports it. */
+size_t clipmi_vpt_train_step_bytes(const clipmi_model* m, int B, int n_ctx, int C);
+int clipmi_vpt_train_step(clipmi_model* m, const clipmi_vision_dgrad* wt, const void* image, int image_dtype, int B, float* prompts, float* buf,
+                          int n_ctx, int depth, const float* text, int C, const int64_t* labels, float scale, float grad_scale,
+                          const float* lr, int first_step, float momentum, float dampening, float weight_decay, int nesterov, float* loss,
+                          float* grad_out, void* workspace, size_t workspace_bytes, void* stash, size_t stash_bytes,
+                          clipmi_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------
  * KgCoOp's and ProGrad's context trained on the device (trainers/classification/kgcoop.py:246-269, prograd.py:291-304, 371-409): CoOp's
