@@ -195,6 +195,17 @@ _SIGNATURES = {
     "clipmi_vpt_train_step_bytes": (_sz, [_vp, _i, _i, _i]),
     "clipmi_vpt_train_step": (_i, [_vp, C.POINTER(VisionDgrad), _vp, _i, _i, _vp, _vp, _i, _i, _vp, _i, _vp, _f, _f, _vp, _i, _f, _f, _f, _i, _vp, _vp,
                                    _vp, _sz, _vp, _sz, _vp]),
+    "clipmi_text_encoder_train_deep": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp, _i, _i, _vp, _i, _vp, _vp, _sz, _vp, _sz, _u, _vp]),
+    "clipmi_text_encoder_backward_deep": (_i, [_vp, C.POINTER(TextDgrad), _vp, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp]),
+    "clipmi_maple_block_floats": (_sz, [_i, _i, _i, _i]),
+    "clipmi_maple_couple": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
+    "clipmi_maple_head_workspace_bytes": (_sz, [_i, _i, _i]),
+    "clipmi_maple_head": (_i, [_vp, _i64, _vp, _vp, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "clipmi_maple_step_workspace_bytes": (_sz, [_i, _i, _i]),
+    "clipmi_maple_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _i, _f, _f, _f, _i, _vp, _sz, _vp]),
+    "clipmi_maple_train_step_bytes": (_sz, [_vp, _i, _i, _i, _i, _i]),
+    "clipmi_maple_train_step": (_i, [_vp, C.POINTER(TextDgrad), C.POINTER(VisionDgrad), _vp, _i, _vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _i, _i,
+                                     _f, _f, _vp, _i, _f, _f, _f, _i, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp]),
     "clipmi_prompt_head_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "clipmi_prompt_head": (_i, [_vp, _i64, _vp, _vp, _i, _i, _i, _f, _f, _i, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "clipmi_prograd_step_workspace_bytes": (_sz, [_i, _i, _i, _i]),

@@ -35,7 +35,7 @@ import torch
 
 from . import _lib, ops
 from ._lib import check, lib
-from .coopfit import MAX_LIVE_ROWS, _DT, _Tower, _check_batch, _check_grad_scale, _check_sgd, _live_rows
+from .coopfit import MAX_LIVE_ROWS, _DT, _Tower, _check_batch, _check_grad_scale, _check_sgd, _live_rows, operand_stats_dict
 from .coopfit import _check_prompts as _check_coop_prompts
 from .taskresfit import _host_int_array, _labels, _need_gpu
 from .tempfit import cosine_warmup_schedule, steps_per_epoch
@@ -158,9 +158,7 @@ def gradients(clip_model, tokenized_prompts, params, features: torch.Tensor, lab
     if return_parts:
         out += ({"text": text.clone(), "x_n": tower.meta[0].clone(), "hid": tower.meta[1].clone(), "pi": tower.meta[2].clone(), "rows": rows},)
     if return_operand_stats:
-        s = stats.cpu().numpy()
-        top = float(np.array([int(s[3])], dtype=np.uint16).view(np.float16)[0])
-        out += ({"elements": int(s[0]), "zeros": int(s[1]), "subnormals": int(s[2]), "max": top},)
+        out += (operand_stats_dict(stats),)
     return out
 
 

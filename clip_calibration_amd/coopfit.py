@@ -232,6 +232,14 @@ class _Tower:
         return self.step_ws
 
 
+def operand_stats_dict(stats: torch.Tensor) -> dict:
+    """The four words a backward's ``operand_stats`` leaves (include/clipmi.h) as ``elements``, ``zeros``, ``subnormals`` and ``max``, the
+    largest magnitude decoded from its fp16 bits.  One read-back."""
+    s = stats.cpu().numpy()
+    top = float(np.array([int(s[3])], dtype=np.uint16).view(np.float16)[0])
+    return {"elements": int(s[0]), "zeros": int(s[1]), "subnormals": int(s[2]), "max": top}
+
+
 def _new_losses(method: str, dev) -> torch.Tensor:
     """The head's losses fp32 [3].  CoOp's head writes the first alone and nothing here reads the others: no fill launch for it."""
     return (torch.empty if method == "coop" else torch.zeros)(3, dtype=torch.float32, device=dev)
@@ -290,9 +298,7 @@ def context_gradient(clip_model, tokenized_prompts, ctx: torch.Tensor, features:
     out = (loss, grad) + ((parts,) if return_parts else ())
     if not return_operand_stats:
         return out
-    s = stats.cpu().numpy()
-    top = float(np.array([int(s[3])], dtype=np.uint16).view(np.float16)[0])
-    return out + ({"elements": int(s[0]), "zeros": int(s[1]), "subnormals": int(s[2]), "max": top},)
+    return out + (operand_stats_dict(stats),)
 
 
 def text_features(clip_model, tokenized_prompts, ctx: torch.Tensor, seq_rows: Optional[int] = None) -> torch.Tensor:

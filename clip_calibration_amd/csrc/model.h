@@ -105,6 +105,8 @@ inline int tower_gemm(const half_t* A, int64_t lda, const void* W, int64_t ldw, 
 int check_vision_train_call(const char* who, const clipmi_model* m, int B, int n_ctx, int depth, const void* ws, size_t ws_bytes, const void* stash,
                             size_t stash_bytes);
 int check_vision_dgrad(const char* who, const clipmi_model* m, const clipmi_vision_dgrad* wt);
+// out[j, :] = sum_b g[b L + first + j, :], b ascending; with `zero` those rows of g and g16 are cleared behind the sum
+int launch_splice_reduce(float* g, half_t* g16, float* out, int B, int L, int D, int first, int n_ctx, int zero, hipStream_t s);
 int run_vision_train_forward(clipmi_model* m, const void* image, int image_dtype, int B, const float* prompts, int n_ctx, int depth, float* out,
                              void* workspace, void* stash_p, hipStream_t s);
 int run_vision_backward(clipmi_model* m, const clipmi_vision_dgrad* wt, const float* d_out, int B, int n_ctx, int depth, float* d_prompts,
@@ -116,9 +118,16 @@ int check_train_call(const char* who, const clipmi_model* m, int n_prompts, cons
 int check_train_inputs(const char* who, const clipmi_model* m, const void* prompts, int dtype, const float* ctx, int n_ctx, const int32_t* eot,
                        int seq_rows, const clipmi_prompt_hook* hook, unsigned flags);
 int check_dgrad(const char* who, const clipmi_model* m, const clipmi_text_dgrad* wt);
+// deep, n_deep (MaPLe): fp32 [n_deep, n_ctx, Dt], rounded through fp16 over the rows 1 .. n_ctx of every prompt in front of block i = 1 .. n_deep;
+// the backward then writes d_deep of that shape (the prompts' rows summed in ascending order) and zeroes those rows of the stream
 int run_train_forward(clipmi_model* m, const void* prompts, int dtype, const float* ctx, int n_ctx, int per_class, const int32_t* eot, int C, int seq_rows,
-                      float* out, void* workspace, void* stash_p, hipStream_t s);
+                      float* out, void* workspace, void* stash_p, hipStream_t s, const float* deep = nullptr, int n_deep = 0);
 int run_backward(clipmi_model* m, const clipmi_text_dgrad* wt, const float* d_out, int C, int seq_rows, float* g, void* workspace, const void* stash_p,
-                 unsigned long long* stats, hipStream_t s);
+                 unsigned long long* stats, hipStream_t s, int n_ctx = 0, int n_deep = 0, float* d_deep = nullptr);
+int check_deep(const char* who, const clipmi_model* m, int n_ctx, int n_deep, const void* deep, int seq_rows);
+
+// prompt_train.hip: MaPLe's joint head (the loss, d_feats [B, E] and d_text [C, E] of one logits matrix), for maple_train.hip
+int launch_maple_head(const char* who, const float* feats, int64_t ld, const int64_t* labels, const float* text, int B, int E, int C, float scale,
+                      float grad_scale, float* loss, float* d_feats, float* d_text, half_t* d_text16, void* workspace, size_t workspace_bytes, hipStream_t s);
 
 }  // namespace clipmi

@@ -8,6 +8,7 @@
 //   ctx_step_kernel            the context's gradient (a fixed-order sum over the classes) and the SGD rule
 //   prograd_dots_kernel,       ProGrad's two context gradients, their three inner products in float64, the projection rule and the SGD step
 //   prograd_step_kernel
+//   (MaPLe's joint head, launch_maple_head, is these kernels: CoOp's and VPT's gradient kernels behind one softmax; maple_train.hip drives it)
 // The cross-entropy row, the workgroup reductions and the optimiser's rules are train_rules.h's.  No float atomics and no workgroup waits
 // for another: the same inputs give the same bits.
 #include <cmath>
@@ -543,11 +544,49 @@ int launch_vpt_step(const char* who, const float* d_prompts, float* prompts, flo
 }
 
 }  // namespace
+
+// --------------------------------------------------------------------------------------------------------------------------- MaPLe
+// (reference trainers/classification/maple.py:190-216: both sides of the logits carry a gradient).  CoOp's norms, logits and cross-entropy
+// rows once, then CoOp's gradient kernel for the text side and VPT's for the image side on the same dz: each side's bits are its own head's.
+int launch_maple_head(const char* who, const float* feats, int64_t ld, const int64_t* labels, const float* text, int B, int E, int C, float scale,
+                      float grad_scale, float* loss, float* d_feats, float* d_text, half_t* d_text16, void* workspace, size_t workspace_bytes, hipStream_t s) {
+  CLIPMI_REQUIRE(feats && labels && text && d_feats && d_text && workspace, CLIPMI_ERR_ARG, "%s: null pointer", who);
+  CLIPMI_REQUIRE(std::isfinite(scale) && std::isfinite(grad_scale), CLIPMI_ERR_ARG, "%s: scale=%g, grad_scale=%g (both finite)", who, scale, grad_scale);
+  CLIPMI_REQUIRE(B >= 1 && C >= 2 && E >= 1 && ld >= E, CLIPMI_ERR_SHAPE, "%s: B=%d C=%d E=%d ld=%lld", who, B, C, E, (long long)ld);
+  CLIPMI_REQUIRE((int64_t)B * C < (1ll << 31), CLIPMI_ERR_SHAPE, "%s: B * C too large", who);
+  CLIPMI_REQUIRE((uintptr_t)workspace % 8 == 0, CLIPMI_ERR_ARG, "%s: the workspace must be 8-byte aligned", who);
+  const size_t need = clipmi_prompt_head_workspace_bytes(B, E, C, MODE_COOP);
+  CLIPMI_REQUIRE(workspace_bytes >= need, CLIPMI_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, need);
+  const HeadWs ws = head_carve(workspace, B, C);
+  const dim3 threads(THREADS);
+  const float *no_tea = nullptr, *no_inty = nullptr;
+  float* none = nullptr;
+  hipLaunchKernelGGL(coop_head_norm_kernel, dim3((unsigned)((B + C + WAVES - 1) / WAVES)), threads, 0, s, feats, ld, text, B, E, C, ws, no_tea, none);
+  if (int rc = check_launch("coop_head_norm_kernel")) return rc;
+  hipLaunchKernelGGL(coop_head_logits_kernel, dim3((unsigned)(((int64_t)B * C + WAVES - 1) / WAVES)), threads, 0, s, feats, ld, text, B, E, C, scale, ws);
+  if (int rc = check_launch("coop_head_logits_kernel")) return rc;
+  hipLaunchKernelGGL(coop_head_softmax_kernel, dim3((unsigned)B), threads, 0, s, labels, B, C, grad_scale, ws);
+  if (int rc = check_launch("coop_head_softmax_kernel")) return rc;
+  hipLaunchKernelGGL(coop_head_grad_kernel<false>, dim3((unsigned)C), threads, 0, s, feats, ld, text, B, E, C, scale, ws, d_text, d_text16, loss, no_tea, no_inty,
+                     none, 0.f);
+  if (int rc = check_launch("coop_head_grad_kernel")) return rc;
+  hipLaunchKernelGGL(vpt_head_grad_kernel, dim3((unsigned)B), threads, 0, s, feats, ld, text, B, E, C, scale, ws, d_feats, none);
+  return check_launch("vpt_head_grad_kernel");
+}
+
 }  // namespace clipmi
 
 using namespace clipmi;
 
 extern "C" {
+
+size_t clipmi_maple_head_workspace_bytes(int B, int E, int C) { return clipmi_prompt_head_workspace_bytes(B, E, C, MODE_COOP); }
+
+int clipmi_maple_head(const float* feats, int64_t ld, const int64_t* labels, const float* text, int B, int E, int C, float scale, float grad_scale,
+                      float* loss, float* d_feats, float* d_text, void* d_text16, void* workspace, size_t workspace_bytes, clipmi_stream_t stream) {
+  return launch_maple_head("maple_head", feats, ld, labels, text, B, E, C, scale, grad_scale, loss, d_feats, d_text, static_cast<half_t*>(d_text16), workspace,
+                           workspace_bytes, (hipStream_t)stream);
+}
 
 size_t clipmi_prompt_head_workspace_bytes(int B, int E, int C, int mode) {
   if (B < 1 || E < 1 || C < 2 || mode < MODE_COOP || mode > MODE_PROGRAD) return 0;

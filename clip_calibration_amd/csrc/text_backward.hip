@@ -10,6 +10,7 @@
 //   (attention_backward_kernel, causal attention's backward on the matrix cores, lives with the other attention kernels: attention.hip)
 //   coop_embed_kernel          prompts with the fp32 context rows in place, plus the positional embedding
 //   operand_stats_kernel       zeros, subnormals and the largest magnitude of the fp16 dgrad-GEMM operands
+//   deep_splice_kernel         MaPLe's deep text prompts: rows 1 .. n_ctx of every prompt overwritten in the stash, rounded through fp16
 // No float atomics and no workgroup waits for another: the same inputs give the same bits.
 #include <cmath>
 
@@ -158,6 +159,16 @@ __global__ __launch_bounds__(THREADS) void coop_embed_kernel(const T* __restrict
   xres[idx] = v + pos[(int64_t)l * D + d];
 }
 
+// x[c, 1 + j, :] = float(half(deep[j, :])) for every prompt c: the reference's .half() of a deep prompt, no positional embedding
+// (clip/model.py:313-328).  In place in the stash slab, so the stash holds what the block read.
+__global__ __launch_bounds__(THREADS) void deep_splice_kernel(float* __restrict__ x, const float* __restrict__ deep, int C, int L, int D, int n_ctx) {
+  const int64_t idx = (int64_t)blockIdx.x * THREADS + threadIdx.x;
+  if (idx >= (int64_t)C * n_ctx * D) return;
+  const int d = (int)(idx % D), j = (int)((idx / D) % n_ctx);
+  const int64_t c = idx / ((int64_t)D * n_ctx);
+  x[(c * L + 1 + j) * D + d] = (float)(half_t)deep[(int64_t)j * D + d];
+}
+
 // {elements, exact zeros, fp16 subnormals, largest magnitude (fp16 bits)} of an fp16 operand, added into stats (integer atomics)
 __global__ __launch_bounds__(THREADS) void operand_stats_kernel(const uint16_t* __restrict__ x, int64_t n, unsigned long long* __restrict__ stats) {
   __shared__ unsigned long long sz[WAVES], ss[WAVES];
@@ -221,7 +232,7 @@ constexpr auto& gemm = tower_gemm;   // model.h: shared with vision_backward.hip
 }  // namespace
 
 int run_train_forward(clipmi_model* m, const void* prompts, int dtype, const float* ctx, int n_ctx, int per_class, const int32_t* eot, int C, int seq_rows,
-                      float* out, void* workspace, void* stash_p, hipStream_t s) {
+                      float* out, void* workspace, void* stash_p, hipStream_t s, const float* deep, int n_deep) {
   const int L = live_rows(m, seq_rows), D = m->g.text_width, E = m->g.embed_dim, H = m->g.text_heads, layers = m->g.text_layers;
   const int64_t M = (int64_t)C * L;
   const TrainWs w = carve_ws(workspace, M, C, D, E);
@@ -241,6 +252,12 @@ int run_train_forward(clipmi_model* m, const void* prompts, int dtype, const flo
   for (int i = 0; i < layers; ++i) {
     const clipmi_block_weights& b = m->tblocks[i];
     float *x_in = st.x(2 * i), *x_mid = st.x(2 * i + 1), *x_out = st.x(2 * i + 2);
+    if (i >= 1 && i <= n_deep) {   // MaPLe: block i reads deep[i - 1] on the rows 1 .. n_ctx, whatever block i - 1 left there
+      const int64_t n = (int64_t)C * n_ctx * D;
+      hipLaunchKernelGGL(deep_splice_kernel, dim3((unsigned)((n + THREADS - 1) / THREADS)), dim3(THREADS), 0, s, x_in, deep + (int64_t)(i - 1) * n_ctx * D, C, L, D,
+                         n_ctx);
+      if ((rc = check_launch("deep_splice_kernel"))) return rc;
+    }
     if ((rc = launch_layernorm(x_in, CLIPMI_F32, D, nullptr, b.ln1_g, b.ln1_b, w.xn, CLIPMI_F16, D, (int)M, D, 1e-5f, s))) return rc;
     if ((rc = gemm(w.xn, D, b.w_qkv, D, b.b_qkv, nullptr, st.qkv(i), 3 * D, CLIPMI_F16, M, 3 * D, D, CLIPMI_EPI_BIAS, s))) return rc;
     if ((rc = launch_attention(st.qkv(i), w.att, C, L, H, 1, s))) return rc;
@@ -255,7 +272,7 @@ int run_train_forward(clipmi_model* m, const void* prompts, int dtype, const flo
 }
 
 int run_backward(clipmi_model* m, const clipmi_text_dgrad* wt, const float* d_out, int C, int seq_rows, float* g, void* workspace, const void* stash_p,
-                 unsigned long long* stats, hipStream_t s) {
+                 unsigned long long* stats, hipStream_t s, int n_ctx, int n_deep, float* d_deep) {
   const int L = live_rows(m, seq_rows), D = m->g.text_width, E = m->g.embed_dim, H = m->g.text_heads, layers = m->g.text_layers;
   const int64_t M = (int64_t)C * L;
   const TrainWs w = carve_ws(workspace, M, C, D, E);
@@ -283,7 +300,20 @@ int run_backward(clipmi_model* m, const clipmi_text_dgrad* wt, const float* d_ou
     if ((rc = launch_operand_stats(w.qkv, M * 3 * D, stats, s))) return rc;
     if ((rc = gemm(w.qkv, 3 * D, t.w_qkv_t, 3 * D, nullptr, nullptr, w.dy, D, CLIPMI_F32, M, D, 3 * D, CLIPMI_EPI_NONE, s))) return rc;   // dqkv W_qkv
     if ((rc = launch_ln_backward(st.x(2 * i), D, nullptr, b.ln1_g, w.dy, CLIPMI_F32, g, g16, M, D, 1e-5f, s))) return rc;
+    // block i read deep[i - 1] on the rows 1 .. n_ctx: their gradient leaves the stream (block i - 1's outputs there were discarded)
+    if (i >= 1 && i <= n_deep && (rc = launch_splice_reduce(g, g16, d_deep + (int64_t)(i - 1) * n_ctx * D, C, L, D, 1, n_ctx, 1, s))) return rc;
   }
+  return CLIPMI_OK;
+}
+
+// what the _deep entry points ask on top of the plain ones: n_deep prompts [n_ctx, Dt] for the blocks 1 .. n_deep
+int check_deep(const char* who, const clipmi_model* m, int n_ctx, int n_deep, const void* deep, int seq_rows) {
+  CLIPMI_REQUIRE(n_deep >= 0, CLIPMI_ERR_SHAPE, "%s: n_deep=%d", who, n_deep);
+  if (n_deep == 0) return CLIPMI_OK;
+  CLIPMI_REQUIRE(1 + n_deep <= m->g.text_layers, CLIPMI_ERR_SHAPE, "%s: depth %d for %d text layers", who, 1 + n_deep, m->g.text_layers);
+  CLIPMI_REQUIRE(n_ctx >= 1 && 1 + n_ctx <= live_rows(m, seq_rows), CLIPMI_ERR_SHAPE, "%s: n_ctx=%d does not fit the %d token rows that are computed", who,
+                 n_ctx, live_rows(m, seq_rows));
+  CLIPMI_REQUIRE(deep, CLIPMI_ERR_ARG, "%s: null pointer (n_deep=%d needs the deep prompts)", who, n_deep);
   return CLIPMI_OK;
 }
 
@@ -373,6 +403,32 @@ int clipmi_text_encoder_backward(clipmi_model* m, const clipmi_text_dgrad* wt, c
   CLIPMI_REQUIRE(live_rows(m, seq_rows) <= AB_MAX_L, CLIPMI_ERR_SHAPE, "text_encoder_backward: %d token rows per prompt (at most %d)", live_rows(m, seq_rows),
                  AB_MAX_L);
   return run_backward(m, wt, d_out, n_prompts, seq_rows, d_embed, workspace, stash, operand_stats, (hipStream_t)stream);
+}
+
+int clipmi_text_encoder_train_deep(clipmi_model* m, const void* prompts, int dtype, const float* ctx, int n_ctx, int ctx_per_class, const int32_t* eot,
+                                   int n_prompts, int seq_rows, const float* deep, int n_deep, float* out, void* workspace, size_t workspace_bytes,
+                                   void* stash, size_t stash_bytes, unsigned flags, clipmi_stream_t stream) {
+  const char* who = "text_encoder_train_deep";
+  if (int rc = check_train_call(who, m, n_prompts, workspace, workspace_bytes, stash, stash_bytes, seq_rows)) return rc;
+  if (int rc = check_deep(who, m, n_ctx, n_deep, deep, seq_rows)) return rc;
+  if (n_prompts == 0) return CLIPMI_OK;
+  if (int rc = check_train_inputs(who, m, prompts, dtype, ctx, n_ctx, eot, seq_rows, nullptr, flags)) return rc;
+  CLIPMI_REQUIRE(out, CLIPMI_ERR_ARG, "%s: null pointer", who);
+  return run_train_forward(m, prompts, dtype, ctx, n_ctx, ctx_per_class, eot, n_prompts, seq_rows, out, workspace, stash, (hipStream_t)stream, deep, n_deep);
+}
+
+int clipmi_text_encoder_backward_deep(clipmi_model* m, const clipmi_text_dgrad* wt, const float* d_out, int n_prompts, int seq_rows, int n_ctx, int n_deep,
+                                      float* d_embed, float* d_deep, void* workspace, size_t workspace_bytes, const void* stash, size_t stash_bytes,
+                                      unsigned long long* operand_stats, clipmi_stream_t stream) {
+  const char* who = "text_encoder_backward_deep";
+  if (int rc = check_train_call(who, m, n_prompts, workspace, workspace_bytes, stash, stash_bytes, seq_rows)) return rc;
+  if (int rc = check_deep(who, m, n_ctx, n_deep, d_deep, seq_rows)) return rc;
+  if (n_prompts == 0) return CLIPMI_OK;
+  if (int rc = check_dgrad(who, m, wt)) return rc;
+  CLIPMI_REQUIRE(d_out && d_embed, CLIPMI_ERR_ARG, "%s: null pointer", who);
+  CLIPMI_REQUIRE((uintptr_t)d_embed % 16 == 0, CLIPMI_ERR_ARG, "%s: d_embed must be 16-byte aligned", who);
+  CLIPMI_REQUIRE(live_rows(m, seq_rows) <= AB_MAX_L, CLIPMI_ERR_SHAPE, "%s: %d token rows per prompt (at most %d)", who, live_rows(m, seq_rows), AB_MAX_L);
+  return run_backward(m, wt, d_out, n_prompts, seq_rows, d_embed, workspace, stash, operand_stats, (hipStream_t)stream, n_ctx, n_deep, d_deep);
 }
 
 }  // extern "C"

@@ -38,11 +38,15 @@ __global__ __launch_bounds__(THREADS) void splice_reduce_kernel(float* __restric
   out[idx] = s;
 }
 
+}  // namespace
+
 int launch_splice_reduce(float* g, half_t* g16, float* out, int B, int L, int D, int first, int n_ctx, int zero, hipStream_t s) {
   hipLaunchKernelGGL(splice_reduce_kernel, dim3((unsigned)(((int64_t)n_ctx * D + THREADS - 1) / THREADS)), dim3(THREADS), 0, s, g, g16, out, B, L, D, first,
                      n_ctx, zero);
   return check_launch("splice_reduce_kernel");
 }
+
+namespace {
 
 // behind the text tower's workspace: the fp32 gradient stream, the fp16 copy of an fp32 image batch, the prompts as fp16, slot 0's batch sum
 struct VisionWs {

@@ -1,4 +1,5 @@
-"""MaPLe (reference trainers/classification/maple.py:51-216) -- inference forward only."""
+"""MaPLe (reference trainers/classification/maple.py:51-216): the inference forward, and ``CustomCLIP.fit_prompt_learner``, the prompt
+learner's training on the GPU through both towers (clip_calibration_amd/maplefit.py)."""
 from __future__ import annotations
 
 import torch
@@ -67,3 +68,40 @@ class CustomCLIP(_CoOpCLIP):
     def _image_features(self, image: torch.Tensor) -> torch.Tensor:
         _, shared_ctx, _, deep_v = self.prompt_learner()
         return self.clip_model.image_features_f32(image, shared_ctx, deep_v)
+
+    def learner_params(self):
+        """The prompt learner's trained parameters under their ``state_dict`` names (the buffers left out)."""
+        return {k: v for k, v in self.prompt_learner.named_parameters()}
+
+    def fit_prompt_learner(self, train_loader, transform=None, **fit_args):
+        """Train the prompt learner -- ``ctx``, ``compound_prompts_text``, ``proj`` and ``compound_prompt_projections`` -- on the GPU,
+        starting from the parameters' values, with ``logit_scale`` taken from this model unless ``fit_args`` say otherwise (maple.py:279-300
+        with both towers frozen).  The fitted block is copied into the parameters in place, each in its own dtype (the fit keeps fp32
+        masters; ``proj`` is a half Linear) -- that moves their versions, so the cached text features retire on their own; the cache is
+        dropped as well -- and returned as ``maplefit.fit_prompt_learner`` returns it.  Both towers run on every step: nothing is cached.
+
+        ``transform=None``: ``train_loader`` is a sized iterable of (preprocessed images, labels) batches, iterated once per epoch.
+        ``transform=TrainPreprocess.for_model(model)``: it yields (decoded uint8 images, labels) and every batch goes transform ->
+        ``MaPLeFitState.step`` with nothing synchronising until the end (``augment.fit_with_transform``).  ``fit_args``: ``epochs`` (5),
+        ``lr`` (0.0035), ``lr_per_epoch``, the optimiser's ``momentum``, ``dampening``, ``weight_decay``, ``nesterov``, ``grad_scale``,
+        ``seq_rows``, ``views`` (with a transform) and ``return_history``; the batch size and the order are the loader's."""
+        import math
+        from .. import maplefit
+        fit_args.setdefault("logit_scale", math.log(self.scale))
+        fit_args.setdefault("class_token_position", getattr(self.prompt_learner, "class_token_position", "end"))
+        ids, params = self.prompt_learner.tokenized_prompts, self.learner_params()
+        if transform is not None:
+            from ..augment import fit_with_transform
+            run = {k: fit_args.pop(k) for k in ("lr_per_epoch", "views", "return_history") if k in fit_args}
+            epochs, lr = fit_args.pop("epochs", 5), fit_args.pop("lr", 0.0035)
+            state = maplefit.MaPLeFitState(self.clip_model, ids, params, **fit_args)
+            losses = fit_with_transform(state, lambda x: x, ids.shape[0], train_loader, transform, epochs, lr, **run)
+            fitted = state.params() if losses is None else (state.params(), losses)
+        else:
+            fitted = maplefit.fit_prompt_learner(train_loader, None, self.clip_model, ids, params, **fit_args)
+        block = fitted[0] if isinstance(fitted, tuple) else fitted
+        with torch.no_grad():
+            for name, p in params.items():
+                p.copy_(block[name])
+        self._cache_key = self._cache = None
+        return fitted

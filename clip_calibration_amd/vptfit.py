@@ -21,7 +21,7 @@ every step with one synchronisation at the end.  The image tower runs on every s
 The defaults -- SGD at 0.0025 with momentum 0.9 and weight decay 5e-4, 5 epochs, a constant warm-up epoch handing over to a cosine
 schedule -- restate the reference's VPT config and Dassl's public defaults and are UNVERIFIED here; each is an argument.
 
-Not covered: MaPLe, PromptSRC and IVLP training (text-side deep prompts and coupling functions on top of this), ViT-L lengths (more
+Not covered: PromptSRC and IVLP training (MaPLe trains through ``maplefit``, on this tower), ViT-L lengths (more
 than 224 token rows per image), ``nn.DataParallel``, the reference's ``amp`` branch, the ResNet towers.
 """
 from __future__ import annotations
@@ -35,7 +35,7 @@ import torch
 
 from . import _lib, ops
 from ._lib import check, lib
-from .coopfit import _check_grad_scale, _check_sgd
+from .coopfit import _check_grad_scale, _check_sgd, operand_stats_dict
 from .taskresfit import _labels, _need_gpu
 from .tempfit import cosine_warmup_schedule, steps_per_epoch
 
@@ -237,9 +237,7 @@ def prompt_gradient(model, prompts: torch.Tensor, images: torch.Tensor, labels, 
     grad = vpt_step(tower.backward(d_feats, stats), gs)
     if not return_operand_stats:
         return loss, grad
-    s = stats.cpu().numpy()
-    top = float(np.array([int(s[3])], dtype=np.uint16).view(np.float16)[0])
-    return loss, grad, {"elements": int(s[0]), "zeros": int(s[1]), "subnormals": int(s[2]), "max": top}
+    return loss, grad, operand_stats_dict(stats)
 
 
 def image_features(model, prompts: torch.Tensor, images: torch.Tensor) -> torch.Tensor:

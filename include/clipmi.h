@@ -887,6 +887,76 @@ int clipmi_vpt_train_step(clipmi_model* m, const clipmi_vision_dgrad* wt, const 
                           clipmi_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------
+ * MaPLe's multi-modal prompts trained on the device (trainers/classification/maple.py:77-216; clip/model.py:259-331): the loss reaches the
+ * learned parameters through BOTH frozen towers.  The text tower's training forward and backward with deep prompts, the coupling
+ * functions (Linear Dt -> Dv) that make the image tower's prompt rows, a joint loss head and torch.optim.SGD's step over one fp32 master
+ * block (csrc/text_backward.hip, csrc/maple_train.hip, csrc/prompt_train.hip, DESIGN.md "MaPLe fit").  The master block, d = the depth:
+ *   [ ctx [n_ctx, Dt] | compound_prompts_text [d - 1, n_ctx, Dt] | proj.weight [Dv, Dt] | proj.bias [Dv] |
+ *     compound_prompt_projections.weight [d - 1, Dv, Dt] | compound_prompt_projections.bias [d - 1, Dv] ]
+ * Both backwards carry grad_scale * gradient; only clipmi_maple_head and clipmi_maple_step know the factor.
+ * These exports are additive: the ABI version does not change with them.
+ * ---------------------------------------------------------------------------------------------------- */
+
+/* clipmi_text_encoder_train with MaPLe's deep text prompts: deep fp32 [n_deep, n_ctx, Dt] (NULL with n_deep == 0).  Before block i
+ * (1 <= i <= n_deep) the rows 1 .. n_ctx of every prompt in the stash slab x_in(i) are overwritten with deep[i - 1] rounded through fp16
+ * (the reference's .half(); no positional embedding) -- in place, so the stash holds what block i read; workspace and stash sizes are
+ * clipmi_text_train_bytes's.  n_deep == 0: the plain call, bit for bit.  1 + n_deep > text_layers or 1 + n_ctx > the live rows:
+ * CLIPMI_ERR_SHAPE, nothing written. */
+int clipmi_text_encoder_train_deep(clipmi_model* m, const void* prompts, int dtype, const float* ctx, int n_ctx, int ctx_per_class,
+                                   const int32_t* eot, int n_prompts, int seq_rows, const float* deep, int n_deep, float* out,
+                                   void* workspace, size_t workspace_bytes, void* stash, size_t stash_bytes, unsigned flags,
+                                   clipmi_stream_t stream);
+
+/* Its backward: clipmi_text_encoder_backward, and after block i's ln_1 backward (1 <= i <= n_deep) d_deep[i - 1][j] = sum_c g[c L + 1 + j]
+ * (c ascending) with those rows of the gradient stream zeroed behind the sum (block i - 1's outputs there were discarded).  d_deep fp32
+ * [n_deep, n_ctx, Dt], overwritten; ctx's gradient comes from d_embed rows 1 .. n_ctx as clipmi_ctx_step forms it.  No float atomics. */
+int clipmi_text_encoder_backward_deep(clipmi_model* m, const clipmi_text_dgrad* wt, const float* d_out, int n_prompts, int seq_rows,
+                                      int n_ctx, int n_deep, float* d_embed, float* d_deep, void* workspace, size_t workspace_bytes,
+                                      const void* stash, size_t stash_bytes, unsigned long long* operand_stats, clipmi_stream_t stream);
+
+/* Floats of the master block (0 for arguments the calls refuse). */
+size_t clipmi_maple_block_floats(int n_ctx, int depth, int Dt, int Dv);
+
+/* The coupling functions, one launch: vis fp32 [depth, n_ctx, Dv], the prompt block clipmi_vision_encoder_train takes (slot 0 is
+ * shared_ctx).  vis[0] = h(ctx) h(proj.weight)^T + h(proj.bias), h = rounding through fp16 (proj is a half Linear); vis[i] = t_i W_i^T + b_i
+ * in fp32 for i >= 1.  fp32 accumulation: 64 interleaved chains over k ascending, then a fixed tree. */
+int clipmi_maple_couple(const float* block, int n_ctx, int depth, int Dt, int Dv, float* vis, clipmi_stream_t stream);
+
+/* The joint head: clipmi_coop_head's d_text [C, E] (and its fp16 copy d_text16, may be NULL) and clipmi_vpt_head's d_feats [B, E] and
+ * loss from ONE logits matrix -- norms, logits and softmax once, then both heads' gradient kernels: each output equals its own head's
+ * bit for bit.  workspace as clipmi_coop_head's.  Five launches. */
+size_t clipmi_maple_head_workspace_bytes(int B, int E, int C);
+int clipmi_maple_head(const float* feats, int64_t ld, const int64_t* labels, const float* text, int B, int E, int C, float scale,
+                      float grad_scale, float* loss, float* d_feats, float* d_text, void* d_text16, void* workspace,
+                      size_t workspace_bytes, clipmi_stream_t stream);
+
+/* The coupling functions' backward and torch.optim.SGD's step on every element of the master block, two launches whatever the depth.
+ * d_embed fp32 [C * L, Dt] and d_deep fp32 [depth - 1, n_ctx, Dt] from clipmi_text_encoder_backward_deep, d_vis fp32 [depth, n_ctx, Dv]
+ * from clipmi_vision_encoder_backward.  First launch: the text-side prompts' gradient d_t_i = (text tower's) + d_vis[i] W_i into the
+ * workspace, beside a copy of the prompts.  Second launch, one thread per element: dW_i[v, k] = sum_j d_vis[i][j][v] t_i[j][k] and
+ * db_i[v] = sum_j d_vis[i][j][v] formed in registers from that copy (slot 0 multiplies h(ctx) and h(proj.weight)); every gradient times
+ * 1 / grad_scale, then clipmi_ctx_step's rule (equal to torch.optim.SGD on the GPU bit for bit given grad_out).  grad_out (the block's
+ * shape, may be NULL) receives the gradient before weight decay.  apply == 0: only grad_out is written.  workspace (256-byte aligned) of
+ * clipmi_maple_step_workspace_bytes bytes. */
+size_t clipmi_maple_step_workspace_bytes(int n_ctx, int depth, int Dt);
+int clipmi_maple_step(const float* d_embed, const float* d_deep, const float* d_vis, float* block, float* buf, float* grad_out, int apply,
+                      int C, int L, int n_ctx, int depth, int Dt, int Dv, float grad_scale, const float* lr, int first_step,
+                      float momentum, float dampening, float weight_decay, int nesterov, void* workspace, size_t workspace_bytes,
+                      clipmi_stream_t stream);
+
+/* One training step of MaPLe as ONE call: clipmi_maple_couple, clipmi_text_encoder_train_deep, clipmi_vision_encoder_train,
+ * clipmi_maple_head, clipmi_text_encoder_backward_deep, clipmi_vision_encoder_backward and clipmi_maple_step enqueued in this order on
+ * `stream` -- the same launches, the same bits.  block is the fp32 master, updated in place.  workspace of
+ * clipmi_maple_train_step_bytes(...) bytes (256-byte aligned); the stashes as clipmi_text_train_bytes / clipmi_vision_train_bytes report. */
+size_t clipmi_maple_train_step_bytes(const clipmi_model* m, int n_prompts, int seq_rows, int B, int n_ctx, int depth);
+int clipmi_maple_train_step(clipmi_model* m, const clipmi_text_dgrad* wt, const clipmi_vision_dgrad* wv, const void* prompts, int dtype,
+                            const int32_t* eot, int n_prompts, int seq_rows, const void* image, int image_dtype, int B,
+                            const int64_t* labels, float* block, float* buf, int n_ctx, int depth, float scale, float grad_scale,
+                            const float* lr, int first_step, float momentum, float dampening, float weight_decay, int nesterov,
+                            float* loss, float* grad_out, void* workspace, size_t workspace_bytes, void* text_stash,
+                            size_t text_stash_bytes, void* vision_stash, size_t vision_stash_bytes, clipmi_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------
  * KgCoOp's and ProGrad's context trained on the device (trainers/classification/kgcoop.py:246-269, prograd.py:291-304, 371-409): CoOp's
  * forward and backward with another loss head and, for ProGrad, a projection between the backward and the optimiser (DESIGN.md
  * "KgCoOp / ProGrad fit").  `mode` is a plain integer: 0 CoOp, 1 KgCoOp, 2 ProGrad.  `teacher` fp32 [C, E]: the frozen zero-shot text
