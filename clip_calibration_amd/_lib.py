@@ -206,6 +206,14 @@ _SIGNATURES = {
     "clipmi_maple_train_step_bytes": (_sz, [_vp, _i, _i, _i, _i, _i]),
     "clipmi_maple_train_step": (_i, [_vp, C.POINTER(TextDgrad), C.POINTER(VisionDgrad), _vp, _i, _vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _i, _i,
                                      _f, _f, _vp, _i, _f, _f, _f, _i, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp]),
+    "clipmi_promptsrc_head_workspace_bytes": (_sz, [_i, _i, _i]),
+    "clipmi_promptsrc_head": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _f, _f, _f, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "clipmi_promptsrc_block_floats": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "clipmi_promptsrc_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _i, _f, _f, _f, _i, _vp]),
+    "clipmi_gpa_accumulate": (_i, [_vp, _vp, _i64, _f, _i, _vp]),
+    "clipmi_promptsrc_train_step_bytes": (_sz, [_vp, _i, _i, _i, _i, _i, _i]),
+    "clipmi_promptsrc_train_step": (_i, [_vp, C.POINTER(TextDgrad), C.POINTER(VisionDgrad), _vp, _i, _vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i,
+                                         _i, _i, _f, _f, _f, _f, _f, _vp, _i, _f, _f, _f, _i, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp]),
     "clipmi_prompt_head_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "clipmi_prompt_head": (_i, [_vp, _i64, _vp, _vp, _i, _i, _i, _f, _f, _i, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "clipmi_prograd_step_workspace_bytes": (_sz, [_i, _i, _i, _i]),

@@ -148,7 +148,7 @@ class TrainPreprocess(Preprocess):
 
 def fit_with_transform(state, image_features: Callable[[torch.Tensor], torch.Tensor], n_classes: int, loader, transform: TrainPreprocess,
                        epochs: int, lr: float, lr_per_epoch: Optional[Sequence[float]] = None, views: Optional[Callable] = None,
-                       return_history: bool = False) -> Optional[np.ndarray]:
+                       return_history: bool = False, end_epoch: Optional[Callable[[int], None]] = None) -> Optional[np.ndarray]:
     """The reference's training regime for a head trained on frozen towers: ``epochs`` passes over ``loader`` -- a sized iterable of
     (decoded uint8 images in any form ``transform`` takes, labels [B]) iterated once per epoch --, every batch going ``transform`` ->
     ``image_features`` (the frozen tower, fp32 [B, E]) -> ``state.step`` (an ``AdapterFitState`` or ``TaskResFitState``).  The rate of a
@@ -156,7 +156,9 @@ def fit_with_transform(state, image_features: Callable[[torch.Tensor], torch.Ten
     repeated ``len(loader)`` times.  ``views(epoch, batch_index, shapes)`` supplies explicit views for a batch; None samples one view per
     image from the transform's generator.  Labels on the host are range-checked there and cross from page-locked memory; labels on the
     GPU are taken as ``state.step`` takes them.  Nothing synchronises between the first launch and the one wait at the end; host images
-    cross as ``transform`` moves them (page-locked batches without a wait).  Returns the per-step losses with ``return_history``."""
+    cross as ``transform`` moves them (page-locked batches without a wait).  ``end_epoch(e)``, when given, is called behind the last step
+    of every epoch e (0-based) and must not synchronise (PromptSRC's prompt aggregation).  Returns the per-step losses with
+    ``return_history``."""
     if not isinstance(transform, TrainPreprocess):
         raise TypeError(f"transform must be a TrainPreprocess, got {type(transform)}")
     epochs = int(epochs)
@@ -196,5 +198,7 @@ def fit_with_transform(state, image_features: Callable[[torch.Tensor], torch.Ten
                     losses.append(loss)
             if k + 1 != per_epoch:
                 raise RuntimeError(f"the loader gave {k + 1} batches in epoch {e}, its length says {per_epoch}")
+            if end_epoch is not None:
+                end_epoch(e)
     torch.cuda.current_stream(dev).synchronize()   # the run's one synchronisation
     return torch.cat(losses).cpu().numpy() if return_history else None

@@ -130,4 +130,13 @@ int check_deep(const char* who, const clipmi_model* m, int n_ctx, int n_deep, co
 int launch_maple_head(const char* who, const float* feats, int64_t ld, const int64_t* labels, const float* text, int B, int E, int C, float scale,
                       float grad_scale, float* loss, float* d_feats, float* d_text, half_t* d_text16, void* workspace, size_t workspace_bytes, hipStream_t s);
 
+// prompt_train.hip: PromptSRC's head (the joint head plus the two L1 terms and the logit KL against a frozen teacher), for promptsrc_train.hip
+size_t promptsrc_head_bytes(int B, int E, int C);
+int check_promptsrc_head(const char* who, const float* feats, int64_t ld, const float* zs_feats, const int64_t* labels, const float* text, const float* teacher,
+                         int B, int E, int C, float scale, float grad_scale, float w_text, float w_image, float w_logit, const float* losses,
+                         const float* d_feats, const float* d_text, const void* workspace, size_t workspace_bytes);
+int launch_promptsrc_head(const char* who, const float* feats, int64_t ld, const float* zs_feats, const int64_t* labels, const float* text,
+                          const float* teacher, int B, int E, int C, float scale, float grad_scale, float w_text, float w_image, float w_logit,
+                          float* losses, float* d_feats, float* d_text, half_t* d_text16, void* workspace, size_t workspace_bytes, hipStream_t s);
+
 }  // namespace clipmi

@@ -9,6 +9,7 @@
 //   prograd_dots_kernel,       ProGrad's two context gradients, their three inner products in float64, the projection rule and the SGD step
 //   prograd_step_kernel
 //   (MaPLe's joint head, launch_maple_head, is these kernels: CoOp's and VPT's gradient kernels behind one softmax; maple_train.hip drives it)
+//   promptsrc_*_kernel         PromptSRC's additions to that joint head: the logit KL rows, the two L1 terms, the five losses (promptsrc_train.hip drives it)
 // The cross-entropy row, the workgroup reductions and the optimiser's rules are train_rules.h's.  No float atomics and no workgroup waits
 // for another: the same inputs give the same bits.
 #include <cmath>
@@ -543,6 +544,142 @@ int launch_vpt_step(const char* who, const float* d_prompts, float* prompts, flo
   return check_launch("vpt_step_kernel");
 }
 
+// ------------------------------------------------------------------------------------------------------------------------ PromptSRC
+// (reference trainers/classification/promptsrc.py:186-210, 298-317).  The joint head's launches and, beside them, the three
+// self-regularising terms against a frozen teacher: the second logits matrix zz = s Y O^T by coop_head_logits_kernel on the teacher's
+// norms, the KL rows in the softmax launch, and the two L1 terms added to the joint head's d_text and d_feats by a launch of their own
+// (the projection is linear, as for KgCoOp: the cross-entropy's arithmetic stays CoOp's and VPT's own).
+// behind the CoOp head's workspace: 1/|o_c| [C] | 1/|y_b| [B] | zz [B, C] | kl row [B] | l1 row [C + B] (text rows, then image rows), fp32
+struct SrcWs {
+  float *inty, *inzs, *zz, *kl, *l1;
+};
+inline size_t promptsrc_head_floats(int B, int C) { return head_floats(B, C) + (size_t)B * (size_t)C + 2 * ((size_t)B + (size_t)C) + (size_t)B; }
+inline SrcWs src_carve(void* ws, int B, int C) {
+  SrcWs w;
+  w.inty = static_cast<float*>(ws) + head_floats(B, C);
+  w.inzs = w.inty + C;
+  w.zz = w.inzs + B;
+  w.kl = w.zz + (size_t)B * C;
+  w.l1 = w.kl + B;
+  return w;
+}
+
+// grid (B): coop_head_softmax_kernel's row loss and dz by the same function, and beside them the logit term: p = softmax(z), q = softmax(zz),
+// kl row = sum_c q (log q - log p), dz += kk (p - q) with kk = grad_scale w_logit / (B C).  The label reaches the cross-entropy only.
+// Student and teacher go through the same expressions: equal logits give p - q = 0 exactly.
+__global__ __launch_bounds__(THREADS) void promptsrc_softmax_kernel(const int64_t* __restrict__ labels, int B, int C, float grad_scale, float kk, HeadWs ws,
+                                                                    SrcWs sw_) {
+#pragma clang fp contract(off)
+  __shared__ float sw[6][WAVES];   // one row per reduction: none waits for the readers of another
+  const int t = threadIdx.x, r = blockIdx.x;
+  const float* z = ws.z + (size_t)r * C;
+  const float* __restrict__ zt = sw_.zz + (size_t)r * C;
+  float* dz = ws.dz + (size_t)r * C;
+  const int64_t y = labels[r];
+  const bool bad = y < 0 || y >= C;      // the same for every thread of the workgroup
+  float m = -INFINITY, mt = -INFINITY;
+  for (int c = t; c < C; c += THREADS) {
+    m = fmaxf(m, z[c]);
+    mt = fmaxf(mt, zt[c]);
+  }
+  m = block_max<WAVES>(m, sw[0]);
+  mt = block_max<WAVES>(mt, sw[1]);
+  xent_row<WAVES>(z, dz, C, m, bad ? 0 : y, grad_scale / (float)B, sw[2], ws.loss + r);
+  if (bad) {                             // each thread over the elements it has just written
+    for (int c = t; c < C; c += THREADS) dz[c] = NAN;
+    if (t == 0) ws.loss[r] = NAN;
+  }
+  float Ss = 0.f, St = 0.f;
+  for (int c = t; c < C; c += THREADS) {
+    Ss += __expf(z[c] - m);
+    St += __expf(zt[c] - mt);
+  }
+  Ss = block_sum<WAVES>(Ss, sw[3]);
+  St = block_sum<WAVES>(St, sw[4]);
+  const float log_ss = logf(Ss), log_st = logf(St);
+  float kl = 0.f;
+  for (int c = t; c < C; c += THREADS) {
+    const float ps = __expf(z[c] - m) / Ss, pt = __expf(zt[c] - mt) / St;
+    dz[c] = dz[c] + (ps - pt) * kk;
+    kl += pt * (((zt[c] - mt) - log_st) - ((z[c] - m) - log_ss));
+  }
+  kl = block_sum<WAVES>(kl, sw[5]);
+  if (t == 0) sw_.kl[r] = kl;
+}
+
+// sign with sign(0) = 0; a NaN stays a NaN
+__device__ __forceinline__ float sign_or_nan(float d) { return d > 0.f ? 1.f : d < 0.f ? -1.f : d; }
+
+// grid (C + B): workgroup r < C is the text row c = r (a = u_c, o = the normalised teacher row, k = grad_scale w_text / (C E)), the others
+// the image row b = r - C (a = x_b, o = the normalised frozen feature, k = grad_scale w_image / (B E)).  s = sign(a - o), the row's
+// sum |a - o| to l1[r], and k (s - a (a . s)) / |raw row| added to the joint head's gradient row (and rounded again into the fp16 copy).
+// An addend of exactly 0 is not added: a row that equals its teacher leaves the cross-entropy's bits.  k == 0: the side is skipped.
+__global__ __launch_bounds__(THREADS) void promptsrc_l1_kernel(const float* __restrict__ feats, int64_t ld, const float* __restrict__ zs,
+                                                               const float* __restrict__ text, const float* __restrict__ teacher, int E, int C, HeadWs ws,
+                                                               SrcWs sw_, float kt, float ki, float* __restrict__ d_text, half_t* __restrict__ d_text16,
+                                                               float* __restrict__ d_feats) {
+#pragma clang fp contract(off)
+  __shared__ float sw[2][WAVES];
+  const int t = threadIdx.x, r = blockIdx.x;
+  const bool text_side = r < C;          // the same for every thread of the workgroup, as is k
+  const float k = text_side ? kt : ki;
+  if (k == 0.f) return;
+  const int b = r - C;
+  const float* a = text_side ? text + (int64_t)r * E : feats + (int64_t)b * ld;
+  const float* o = text_side ? teacher + (int64_t)r * E : zs + (int64_t)b * E;
+  const float ia = text_side ? ws.intx[r] : ws.inf[b], io = text_side ? sw_.inty[r] : sw_.inzs[b];
+  float* out = text_side ? d_text + (int64_t)r * E : d_feats + (int64_t)b * E;
+  half_t* out16 = text_side && d_text16 ? d_text16 + (int64_t)r * E : nullptr;
+  float l1 = 0.f, qs = 0.f;
+  for (int e = t; e < E; e += THREADS) {
+    const float u = a[e] * ia, d = u - o[e] * io;
+    l1 += fabsf(d);
+    qs += u * sign_or_nan(d);
+  }
+  l1 = block_sum<WAVES>(l1, sw[0]);
+  qs = block_sum<WAVES>(qs, sw[1]);
+  if (t == 0) sw_.l1[r] = l1;
+  const float kia = k * ia;
+  for (int e = t; e < E; e += THREADS) {
+    const float u = a[e] * ia;
+    const float add = kia * (sign_or_nan(u - o[e] * io) - u * qs);
+    if (add != 0.f) {
+      const float v = out[e] + add;
+      out[e] = v;
+      if (out16) out16[e] = (half_t)v;
+    }
+  }
+}
+
+// one workgroup: losses = [total, CE, text L1, image L1, logit KL], each the float64 mean of its fp32 rows in sum_f64_256's order and each
+// unweighted but the total; a term whose weight is 0 was skipped and reads 0
+__global__ __launch_bounds__(256) void promptsrc_loss_kernel(HeadWs ws, SrcWs sw_, int B, int E, int C, float w_text, float w_image, float w_logit,
+                                                             float* __restrict__ losses) {
+#pragma clang fp contract(off)
+  __shared__ double sl[4][256];
+  const double ce = sum_f64_256(ws.loss, B, sl) / (double)B;
+  double total = ce, lt = 0.0, li = 0.0, kl = 0.0;
+  if (w_text != 0.f) {
+    lt = sum_f64_256(sw_.l1, C, sl + 1) / ((double)C * (double)E);
+    total += (double)w_text * lt;
+  }
+  if (w_image != 0.f) {
+    li = sum_f64_256(sw_.l1 + C, B, sl + 2) / ((double)B * (double)E);
+    total += (double)w_image * li;
+  }
+  if (w_logit != 0.f) {
+    kl = sum_f64_256(sw_.kl, B, sl + 3) / ((double)B * (double)C);
+    total += (double)w_logit * kl;
+  }
+  if (threadIdx.x == 0) {
+    losses[0] = (float)total;
+    losses[1] = (float)ce;
+    losses[2] = (float)lt;
+    losses[3] = (float)li;
+    losses[4] = (float)kl;
+  }
+}
+
 }  // namespace
 
 // --------------------------------------------------------------------------------------------------------------------------- MaPLe
@@ -572,6 +709,79 @@ int launch_maple_head(const char* who, const float* feats, int64_t ld, const int
   if (int rc = check_launch("coop_head_grad_kernel")) return rc;
   hipLaunchKernelGGL(vpt_head_grad_kernel, dim3((unsigned)B), threads, 0, s, feats, ld, text, B, E, C, scale, ws, d_feats, none);
   return check_launch("vpt_head_grad_kernel");
+}
+
+// --------------------------------------------------------------------------------------------------------------------- PromptSRC
+// The joint head's five launches on the cross-entropy (with all three weights 0 they are all but the loss: the same bits), the teacher's
+// norms and logits, the KL rows inside the softmax launch, the L1 launch and the losses.  A zero-weight term is skipped, not multiplied in.
+size_t promptsrc_head_bytes(int B, int E, int C) {
+  if (B < 1 || E < 1 || C < 2) return 0;
+  return align256(promptsrc_head_floats(B, C) * sizeof(float));
+}
+
+int check_promptsrc_head(const char* who, const float* feats, int64_t ld, const float* zs_feats, const int64_t* labels, const float* text, const float* teacher,
+                         int B, int E, int C, float scale, float grad_scale, float w_text, float w_image, float w_logit, const float* losses,
+                         const float* d_feats, const float* d_text, const void* workspace, size_t workspace_bytes) {
+  CLIPMI_REQUIRE(feats && zs_feats && labels && text && teacher && losses && d_feats && d_text && workspace, CLIPMI_ERR_ARG, "%s: null pointer", who);
+  CLIPMI_REQUIRE(std::isfinite(scale) && std::isfinite(grad_scale), CLIPMI_ERR_ARG, "%s: scale=%g, grad_scale=%g (both finite)", who, scale, grad_scale);
+  CLIPMI_REQUIRE(std::isfinite(w_text) && w_text >= 0.f && std::isfinite(w_image) && w_image >= 0.f && std::isfinite(w_logit) && w_logit >= 0.f, CLIPMI_ERR_ARG,
+                 "%s: w_text=%g, w_image=%g, w_logit=%g (each finite, >= 0)", who, w_text, w_image, w_logit);
+  CLIPMI_REQUIRE(B >= 1 && C >= 2 && E >= 1 && ld >= E, CLIPMI_ERR_SHAPE, "%s: B=%d C=%d E=%d ld=%lld", who, B, C, E, (long long)ld);
+  CLIPMI_REQUIRE((int64_t)B * C < (1ll << 31) && B + C < (1 << 30), CLIPMI_ERR_SHAPE, "%s: B * C too large", who);
+  CLIPMI_REQUIRE((uintptr_t)workspace % 8 == 0, CLIPMI_ERR_ARG, "%s: the workspace must be 8-byte aligned", who);
+  const size_t need = promptsrc_head_bytes(B, E, C);
+  CLIPMI_REQUIRE(workspace_bytes >= need, CLIPMI_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, need);
+  return CLIPMI_OK;
+}
+
+int launch_promptsrc_head(const char* who, const float* feats, int64_t ld, const float* zs_feats, const int64_t* labels, const float* text,
+                          const float* teacher, int B, int E, int C, float scale, float grad_scale, float w_text, float w_image, float w_logit,
+                          float* losses, float* d_feats, float* d_text, half_t* d_text16, void* workspace, size_t workspace_bytes, hipStream_t s) {
+  if (int rc = check_promptsrc_head(who, feats, ld, zs_feats, labels, text, teacher, B, E, C, scale, grad_scale, w_text, w_image, w_logit, losses, d_feats,
+                                    d_text, workspace, workspace_bytes))
+    return rc;
+  const HeadWs ws = head_carve(workspace, B, C);
+  const SrcWs sw = src_carve(workspace, B, C);
+  const dim3 threads(THREADS), per_bc((unsigned)(((int64_t)B * C + WAVES - 1) / WAVES)), per_row((unsigned)((B + C + WAVES - 1) / WAVES));
+  const float *no_tea = nullptr, *no_inty = nullptr;
+  float* none = nullptr;
+  const bool regularised = w_text != 0.f || w_image != 0.f || w_logit != 0.f;
+  hipLaunchKernelGGL(coop_head_norm_kernel, per_row, threads, 0, s, feats, ld, text, B, E, C, ws, no_tea, none);
+  if (int rc = check_launch("coop_head_norm_kernel")) return rc;
+  if (regularised) {   // the teacher's side by the same kernel: 1/|y_b| and 1/|o_c|
+    HeadWs wn = ws;
+    wn.inf = sw.inzs;
+    wn.intx = sw.inty;
+    hipLaunchKernelGGL(coop_head_norm_kernel, per_row, threads, 0, s, zs_feats, (int64_t)E, teacher, B, E, C, wn, no_tea, none);
+    if (int rc = check_launch("coop_head_norm_kernel")) return rc;
+  }
+  hipLaunchKernelGGL(coop_head_logits_kernel, per_bc, threads, 0, s, feats, ld, text, B, E, C, scale, ws);
+  if (int rc = check_launch("coop_head_logits_kernel")) return rc;
+  if (w_logit != 0.f) {
+    HeadWs wt = ws;   // the teacher's logits with the teacher's norms
+    wt.z = sw.zz;
+    wt.inf = sw.inzs;
+    wt.intx = sw.inty;
+    hipLaunchKernelGGL(coop_head_logits_kernel, per_bc, threads, 0, s, zs_feats, (int64_t)E, teacher, B, E, C, scale, wt);
+    if (int rc = check_launch("coop_head_logits_kernel")) return rc;
+    hipLaunchKernelGGL(promptsrc_softmax_kernel, dim3((unsigned)B), threads, 0, s, labels, B, C, grad_scale, grad_scale * w_logit / ((float)B * (float)C), ws, sw);
+    if (int rc = check_launch("promptsrc_softmax_kernel")) return rc;
+  } else {
+    hipLaunchKernelGGL(coop_head_softmax_kernel, dim3((unsigned)B), threads, 0, s, labels, B, C, grad_scale, ws);
+    if (int rc = check_launch("coop_head_softmax_kernel")) return rc;
+  }
+  hipLaunchKernelGGL(coop_head_grad_kernel<false>, dim3((unsigned)C), threads, 0, s, feats, ld, text, B, E, C, scale, ws, d_text, d_text16, none, no_tea, no_inty,
+                     none, 0.f);
+  if (int rc = check_launch("coop_head_grad_kernel")) return rc;
+  hipLaunchKernelGGL(vpt_head_grad_kernel, dim3((unsigned)B), threads, 0, s, feats, ld, text, B, E, C, scale, ws, d_feats, none);
+  if (int rc = check_launch("vpt_head_grad_kernel")) return rc;
+  if (w_text != 0.f || w_image != 0.f) {
+    hipLaunchKernelGGL(promptsrc_l1_kernel, dim3((unsigned)(C + B)), threads, 0, s, feats, ld, zs_feats, text, teacher, E, C, ws, sw,
+                       grad_scale * w_text / ((float)C * (float)E), grad_scale * w_image / ((float)B * (float)E), d_text, d_text16, d_feats);
+    if (int rc = check_launch("promptsrc_l1_kernel")) return rc;
+  }
+  hipLaunchKernelGGL(promptsrc_loss_kernel, dim3(1), dim3(256), 0, s, ws, sw, B, E, C, w_text, w_image, w_logit, losses);
+  return check_launch("promptsrc_loss_kernel");
 }
 
 }  // namespace clipmi

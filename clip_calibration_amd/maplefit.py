@@ -25,7 +25,7 @@ The defaults -- SGD at 0.0035 with momentum 0.9 and weight decay 5e-4, 5 epochs 
 a cosine schedule, n_ctx 2, depth 9 -- restate configs/trainers/MaPLe/vit_b16_c2_ep5_batch4.yaml; the momentum and the weight decay
 are Dassl's public defaults and are UNVERIFIED here; each is an argument.
 
-Not covered: IVLP and PromptSRC training, the reference's ``amp`` branch, ``nn.DataParallel``, ViT-L lengths (more than 224 token rows
+Not covered (IVLP and PromptSRC train through ``promptsrcfit``): the reference's ``amp`` branch, ``nn.DataParallel``, ViT-L lengths (more than 224 token rows
 per image), the ResNet towers, class-token positions other than ``end``.
 """
 from __future__ import annotations

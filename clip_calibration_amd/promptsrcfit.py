@@ -1,0 +1,492 @@
+"""PromptSRC's and IVLP's independent prompts trained on the GPU (reference trainers/classification/promptsrc.py:73-317;
+clip/model.py:191-256).
+
+The reference builds CLIP with ``design_details trainer='IVLP'`` and trains, with both towers frozen, the learner's ``ctx`` [nt, Dt]
+(token rows 1 .. nt of every class prompt), the text blocks' ``transformer.resblocks.{i}.VPT_shallow`` [nt, Dt] (1 <= i < language_depth,
+which overwrite those rows in front of block i), ``visual.VPT`` [nv, Dv] (appended behind the patch rows) and the image blocks'
+``visual.transformer.resblocks.{i}.VPT_shallow`` [nv, Dv] (1 <= i < vision_depth, which overwrite the last nv token rows in front of block
+i).  Every step runs both prompted towers and a second, frozen plain image tower on the batch and takes one ``torch.optim.SGD`` step on
+
+    loss = mean_b CE(z_b, label_b) + w_text mean |u - o| + w_image mean |x - y| + w_logit sum q (log q - log p) / (B C)
+
+with u, x the normalised prompted text / image features, o the normalised ``teacher`` (the reference's ``fixed_embeddings``), y the frozen
+tower's normalised features, z = s X U^T, zz = s Y O^T, p = softmax(z), q = softmax(zz).  At the end of epoch e the parameters times
+``gpa_weights(...)[e - 1]`` are added to a running sum (Gaussian-weighted prompt aggregation, GPA), which replaces them after the last
+epoch.  IVLP (``method="ivlp"``) is the same path with the three weights 0 and no GPA: plain cross-entropy.
+
+A step here is: the frozen forward (``clipmi_encode_image`` with no hook on the same model handle, fp32 residual stream), the text tower's
+training forward with deep prompts, the image tower's, the four-term head (csrc/prompt_train.hip, ``clipmi_promptsrc_head``), both
+backwards and one step over one fp32 master block ``[ctx | text deep | visual.VPT and image deep]`` (csrc/promptsrc_train.hip) -- no
+autograd graph.  DESIGN.md "PromptSRC fit" has the data flow and the deviations from the reference.
+
+The parameters travel as a dict under the reference's names (``param_names``).  ``gradients`` returns one batch's five loss terms and every
+parameter's gradient (the diagnostic entry point of the tests).  ``PromptSRCFitState.step`` takes one batch of preprocessed images,
+``.end_epoch(weight)`` accumulates GPA; ``fit_prompts`` runs epochs over a tensor of images or a loader of (images, labels) batches and
+enqueues everything with one synchronisation at the end.
+
+The defaults -- SGD at 0.0025, 50 epochs in batches of 4, a constant warm-up epoch handing over to a cosine schedule, weights 25 / 10 / 1,
+GPA mean 30 and std 30 -- restate configs/trainers/PromptSRC/vit_b16_c4_ep50_batch4.yaml (w_logit is fixed at 1 in the reference's
+code); momentum 0.9 and weight decay 5e-4 are Dassl's public defaults and are UNVERIFIED here; each is an argument.
+
+Not covered: the reference's ``amp`` branch, ``nn.DataParallel``, ViT-L lengths (more than 224 token rows per image), the ResNet towers,
+class-token positions other than ``end``.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+from typing import Dict, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib, ops
+from ._lib import check, lib
+from . import coopfit, vptfit
+from .coopfit import _check_grad_scale, _check_sgd
+from .taskresfit import _need_gpu
+from .tempfit import cosine_warmup_schedule, steps_per_epoch
+from .vptfit import _labels_dev
+
+# 2^10, one power of two for both towers' backwards, measured at ViT-B/16 with synthetic weights, nt = nv = 4, depths 9 / 9, batch 4, 100
+# classes and the weights 25 / 10 / 1 (profiles/promptsrcfit_parity.txt, "grad_scale"): the text tower's dgrad-GEMM operands reach 1556
+# there (2^5.4 of headroom below fp16's largest value; the image tower's 94, 2^9.4) with 1.3 % / 2.1 % of the elements subnormal.  2^12
+# leaves the text tower 2^3.4 only (0.44 % / 0.64 % subnormal) and 2^16 overflows it; the gradients' norms agree to three digits from 2^0
+# to 2^14.  A model with much larger gradients overflows fp16 at this
+# scale -- the parameters then turn NaN, they do not go wrong silently; pass a smaller power of two.
+DEFAULT_GRAD_SCALE = 1024.0
+METHODS = ("promptsrc", "ivlp")
+LOSS_NAMES = ("total", "ce", "text_l1", "image_l1", "logit_kl")
+
+_DT = {torch.float16: _lib.F16, torch.float32: _lib.F32}
+
+
+def param_names(dt: int, dv: int):
+    """The parameter names in the master block's order: the text depth ``dt`` and the image depth ``dv`` count ctx / visual.VPT as 1."""
+    return (["ctx"] + [f"transformer.resblocks.{i}.VPT_shallow" for i in range(1, dt)] + ["visual.VPT"]
+            + [f"visual.transformer.resblocks.{i}.VPT_shallow" for i in range(1, dv)])
+
+
+def _shapes(nt: int, dt: int, Dt: int, nv: int, dv: int, Dv: int):
+    return [(nt, Dt)] * dt + [(nv, Dv)] * dv
+
+
+def _depths(params) -> Tuple[int, int]:
+    dt = 1 + len([k for k in params if k.startswith("transformer.resblocks.")])
+    dv = 1 + len([k for k in params if k.startswith("visual.transformer.resblocks.")])
+    return dt, dv
+
+
+def model_params(model, ctx: torch.Tensor) -> Dict[str, torch.Tensor]:
+    """The model's own prompt parameters and the learner's ``ctx`` under the master block's names (the tensors themselves, not copies)."""
+    deep_t, _ = model.ivlp_text_prompts()
+    shallow, deep_v = model.ivlp_vision_prompts()
+    if shallow is None:
+        raise ValueError("promptsrcfit: the model carries no visual.VPT (needs design_details trainer='IVLP' with vision_depth >= 1)")
+    tensors = [ctx] + list(deep_t or []) + [shallow] + list(deep_v)
+    return dict(zip(param_names(1 + len(deep_t or []), 1 + len(deep_v)), tensors))
+
+
+def _check_design(who: str, model, params, class_token_position: str = "end"):
+    """(nt, dt, nv, dv) after the refusals of the design."""
+    if getattr(model, "is_resnet", False):
+        raise ValueError(f"{who}: prompt tokens apply to the ViT towers only (the ResNet tower has none)")
+    dd = model.design_details
+    if dd.get("trainer") != "IVLP":
+        raise ValueError(f"{who}: needs a CLIP built with design_details trainer='IVLP', got trainer={dd.get('trainer')!r}")
+    if int(dd.get("vision_depth", 0)) < 1:
+        raise ValueError(f"{who}: vision_depth={dd.get('vision_depth', 0)}; the image prompts need vision_depth >= 1")
+    if class_token_position != "end":
+        raise ValueError(f"{who}: class_token_position={class_token_position!r}; only 'end' is trained (the layout is [SOS | ctx | class tokens, EOS])")
+    if not isinstance(params, dict) or "ctx" not in params or "visual.VPT" not in params:
+        raise ValueError(f"{who}: params must be a dict with the names 'ctx', 'visual.VPT', 'transformer.resblocks.1.VPT_shallow', ...")
+    g = model.geometry
+    Dt, Dv = int(g.transformer_width), int(g.vision_width)
+    if int(dd.get("language_depth", 0)) > g.transformer_layers or int(dd.get("vision_depth", 0)) > g.vision_layers:
+        raise ValueError(f"{who}: language_depth={dd.get('language_depth')} / vision_depth={dd.get('vision_depth')} for {g.transformer_layers} text and "
+                         f"{g.vision_layers} image layers")
+    ctx, vpt = params["ctx"], params["visual.VPT"]
+    if not isinstance(ctx, torch.Tensor) or ctx.dim() != 2 or ctx.shape[1] != Dt:
+        raise ValueError(f"{who}: ctx {tuple(getattr(ctx, 'shape', ()))} must be [n_ctx, {Dt}] (a generic context)")
+    if not isinstance(vpt, torch.Tensor) or vpt.dim() != 2 or vpt.shape[1] != Dv:
+        raise ValueError(f"{who}: visual.VPT {tuple(getattr(vpt, 'shape', ()))} must be [n_ctx, {Dv}]")
+    nt, nv = int(ctx.shape[0]), int(vpt.shape[0])
+    dt, dv = _depths(params)
+    if dt > g.transformer_layers or dv > g.vision_layers:
+        raise ValueError(f"{who}: text depth {dt} / image depth {dv} for {g.transformer_layers} text and {g.vision_layers} image layers")
+    if len(params) != dt + dv:
+        raise ValueError(f"{who}: unknown parameter names {sorted(set(params) - set(param_names(dt, dv)))}")
+    for name, shape in zip(param_names(dt, dv), _shapes(nt, dt, Dt, nv, dv, Dv)):
+        t = params.get(name)
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or not t.dtype.is_floating_point:
+            raise ValueError(f"{who}: {name} {tuple(getattr(t, 'shape', ()))} must be a floating-point tensor {shape}")
+    if nt != int(dd.get("language_ctx", nt)):
+        raise ValueError(f"{who}: ctx has {nt} rows but the model's language_ctx is {dd.get('language_ctx')}")
+    if nv != int(dd.get("vision_ctx", nv)):
+        raise ValueError(f"{who}: visual.VPT has {nv} rows but the model's vision_ctx is {dd.get('vision_ctx')}")
+    tokens = (g.image_resolution // g.vision_patch_size) ** 2 + 1
+    if tokens + nv > vptfit.MAX_ROWS:
+        raise ValueError(f"{who}: {tokens} tokens + {nv} prompt rows = {tokens + nv} rows per image; the backward takes at most {vptfit.MAX_ROWS}")
+    return nt, dt, nv, dv
+
+
+def _check_ids(who: str, model, tokenized_prompts, nt: int):
+    """(C, last EOT position): coopfit's checks of the prompt set, without its refusal of a model that carries deep text prompts."""
+    L = int(model.context_length)
+    ids = coopfit._host_int_array(tokenized_prompts, "tokenized_prompts")
+    if ids.ndim != 2 or ids.shape[1] != L or ids.shape[0] < 2:
+        raise ValueError(f"{who}: tokenized_prompts {ids.shape} must be [C >= 2, {L}]")
+    eot = ids.argmax(axis=1)
+    if not 1 + nt < L or int(eot.min()) <= nt:
+        raise ValueError(f"{who}: n_ctx={nt} does not fit the prompts (context of {L} tokens, first EOT at {int(eot.min())}): the layout is "
+                         "[SOS | ctx | class tokens, EOS]")
+    return int(ids.shape[0]), int(eot.max())
+
+
+def _check_weights(who: str, w_text: float, w_image: float, w_logit: float):
+    for name, w in (("w_text", w_text), ("w_image", w_image), ("w_logit", w_logit)):
+        if not (math.isfinite(w) and w >= 0.0):
+            raise ValueError(f"{who}: {name}={w} (finite, >= 0)")
+    return float(w_text), float(w_image), float(w_logit)
+
+
+def _check_teacher(who: str, model, teacher, Cn: int) -> torch.Tensor:
+    E = int(model.geometry.embed_dim)
+    if not isinstance(teacher, torch.Tensor) or tuple(teacher.shape) != (Cn, E) or not teacher.dtype.is_floating_point:
+        raise ValueError(f"{who}: teacher {tuple(getattr(teacher, 'shape', ()))} must be the frozen text features [C, E] = [{Cn}, {E}]")
+    _need_gpu(teacher, "teacher")
+    return teacher.detach().to(torch.float32).contiguous()
+
+
+def pack_block(params: Dict[str, torch.Tensor], dev) -> torch.Tensor:
+    """The fp32 master block of the parameters, on ``dev`` (a copy)."""
+    return torch.cat([params[n].detach().to(device=dev, dtype=torch.float32).reshape(-1) for n in param_names(*_depths(params))]).contiguous()
+
+
+def unpack_block(block: torch.Tensor, nt: int, dt: int, Dt: int, nv: int, dv: int, Dv: int) -> Dict[str, torch.Tensor]:
+    """Views of a block (or of a gradient of its shape) under the parameter names."""
+    out, at = {}, 0
+    for name, shape in zip(param_names(dt, dv), _shapes(nt, dt, Dt, nv, dv, Dv)):
+        n = int(np.prod(shape))
+        out[name] = block[at:at + n].view(shape)
+        at += n
+    assert at == block.numel()
+    return out
+
+
+def gpa_weights(epochs: int, mean: float = 30.0, std: float = 30.0) -> np.ndarray:
+    """The Gaussian density of (mean, std) at the epochs 1 .. ``epochs``, normalised to sum 1: float64 [epochs] (promptsrc.py:267-271)."""
+    epochs = int(epochs)
+    if epochs < 1 or not (math.isfinite(mean) and math.isfinite(std) and std > 0.0):
+        raise ValueError(f"gpa_weights: epochs={epochs} (>= 1), mean={mean}, std={std} (finite, std > 0)")
+    e = np.arange(1, epochs + 1, dtype=np.float64)
+    g = (1.0 / (std * np.sqrt(2.0 * np.pi))) * np.exp(-0.5 * ((e - mean) / std) ** 2)
+    return g / g.sum()
+
+
+def promptsrc_head(feats: torch.Tensor, zs_feats: torch.Tensor, text: torch.Tensor, teacher: torch.Tensor, labels: torch.Tensor, scale: float,
+                   grad_scale: float, w_text: float, w_image: float, w_logit: float, losses: Optional[torch.Tensor] = None, want_f16: bool = False,
+                   ws: Optional[torch.Tensor] = None):
+    """clipmi_promptsrc_head: ``(losses fp32 [5] = total, CE, text L1, image L1, logit KL; d_feats fp32 [B, E]; d_text fp32 [C, E])`` and, with
+    ``want_f16``, d_text's fp16 copy."""
+    B, E = feats.shape
+    Cn = text.shape[0]
+    dev = feats.device
+    if ws is None:
+        ws = torch.empty(max(lib.clipmi_promptsrc_head_workspace_bytes(B, E, Cn), 8), dtype=torch.uint8, device=dev)
+    losses = torch.empty(5, dtype=torch.float32, device=dev) if losses is None else losses
+    d_feats = torch.empty(B, E, dtype=torch.float32, device=dev)
+    d_text = torch.empty(Cn, E, dtype=torch.float32, device=dev)
+    d16 = torch.empty(Cn, E, dtype=torch.float16, device=dev) if want_f16 else None
+    check(lib.clipmi_promptsrc_head(feats.data_ptr(), feats.stride(0), zs_feats.data_ptr(), text.data_ptr(), teacher.data_ptr(), labels.data_ptr(), B, E, Cn,
+                                    scale, grad_scale, w_text, w_image, w_logit, losses.data_ptr(), d_feats.data_ptr(), d_text.data_ptr(),
+                                    None if d16 is None else d16.data_ptr(), ws.data_ptr(), ws.numel(), ops._stream()), "clipmi_promptsrc_head")
+    return (losses, d_feats, d_text) + ((d16,) if want_f16 else ())
+
+
+def promptsrc_step(d_embed: torch.Tensor, d_deep: Optional[torch.Tensor], d_vis: torch.Tensor, block: torch.Tensor, Cn: int, L: int, nt: int, dt: int,
+                   Dt: int, nv: int, dv: int, Dv: int, grad_scale: float, buf: Optional[torch.Tensor] = None, lr=None, first_step: bool = True,
+                   momentum: float = 0.0, dampening: float = 0.0, weight_decay: float = 0.0, nesterov: bool = False, apply: bool = True,
+                   want_grad: bool = True) -> Optional[torch.Tensor]:
+    """clipmi_promptsrc_step: the whole block's gradient (returned with ``want_grad``) and, with ``apply``, SGD's step on ``block`` in place."""
+    grad = torch.empty_like(block) if want_grad else None
+    check(lib.clipmi_promptsrc_step(d_embed.data_ptr(), None if d_deep is None else d_deep.data_ptr(), d_vis.data_ptr(), block.data_ptr(),
+                                    None if buf is None else buf.data_ptr(), None if grad is None else grad.data_ptr(), int(bool(apply)), Cn, L, nt, dt, Dt,
+                                    nv, dv, Dv, grad_scale, None if lr is None else lr.data_ptr(), int(first_step), float(momentum), float(dampening),
+                                    float(weight_decay), int(bool(nesterov)), ops._stream()), "clipmi_promptsrc_step")
+    return grad
+
+
+def gpa_accumulate(block: torch.Tensor, gpa: torch.Tensor, weight: float, first: bool) -> torch.Tensor:
+    """clipmi_gpa_accumulate: ``gpa = weight * block`` (``first``) or ``fma(weight, block, gpa)``, in place on ``gpa``."""
+    check(lib.clipmi_gpa_accumulate(block.data_ptr(), gpa.data_ptr(), block.numel(), float(weight), int(bool(first)), ops._stream()), "clipmi_gpa_accumulate")
+    return gpa
+
+
+class _Towers:
+    """Both frozen towers in training mode for one prompt set -- coopfit's text tower driven with deep prompts and vptfit's image tower --
+    and the frozen plain image forward on the same handle."""
+
+    def __init__(self, who: str, model, tokenized_prompts, params, seq_rows: Optional[int], class_token_position: str = "end"):
+        self.nt, self.dt, self.nv, self.dv = _check_design(who, model, params, class_token_position)
+        Cn, last = _check_ids(who, model, tokenized_prompts, self.nt)
+        self.model, self.C = model, Cn
+        self.text = coopfit._Tower(who, model, tokenized_prompts, Cn, self.nt, False, last, seq_rows)
+        self.vision = vptfit._Tower(who, model, self.dv, self.nv)
+        g = model.geometry
+        self.Dt, self.Dv, self.E = int(g.transformer_width), int(g.vision_width), int(g.embed_dim)
+        dev = model.device
+        self.text_floats = self.dt * self.nt * self.Dt
+        self.d_deep = torch.empty(max(self.dt - 1, 1), self.nt, self.Dt, dtype=torch.float32, device=dev)
+        self.one_ws = self.zs = self.head_ws = None
+
+    def shape(self):
+        return self.nt, self.dt, self.Dt, self.nv, self.dv, self.Dv
+
+    def frozen(self, images: torch.Tensor) -> torch.Tensor:
+        """The frozen plain tower's features fp32 [B, E]: no prompt hook whatever the model carries, fp32 residual stream."""
+        m, B = self.model, images.shape[0]
+        if self.zs is None or self.zs.shape[0] < B:
+            self.zs = torch.empty(B, self.E, dtype=torch.float32, device=images.device)
+        nbytes = lib.clipmi_vision_workspace_bytes(m._handle, B, 0)
+        with m._launch_lock:
+            ws = m._workspace("vision", max(nbytes, 256))
+            check(lib.clipmi_encode_image(m._handle, images.data_ptr(), _DT[images.dtype], B, None, self.zs.data_ptr(), ws.data_ptr(), ws.numel(),
+                                          _lib.CALL_STREAM_F32, ops._stream()), "clipmi_encode_image")
+        return self.zs[:B]
+
+    def forward(self, block: torch.Tensor, images: torch.Tensor):
+        """(text features [C, E], image features [B, E]) at the block: text forward with deep prompts, image forward."""
+        t, m = self.text, self.model
+        deep = block.data_ptr() + 4 * self.nt * self.Dt if self.dt > 1 else None
+        with m._launch_lock:
+            check(lib.clipmi_text_encoder_train_deep(m._handle, t.base.data_ptr(), _DT[t.base.dtype], block.data_ptr(), self.nt, 0, t.eot.data_ptr(), t.C,
+                                                     t.rows, deep, self.dt - 1, t.text.data_ptr(), t.ws.data_ptr(), t.ws.numel(), t.stash.data_ptr(),
+                                                     t.stash.numel(), _lib.CALL_DEFAULT, ops._stream()), "clipmi_text_encoder_train_deep")
+        return t.text, self.vision.forward(images, block[self.text_floats:])
+
+    def backward(self, d_text: torch.Tensor, d_feats: torch.Tensor, stats_text: Optional[torch.Tensor] = None, stats_vision: Optional[torch.Tensor] = None):
+        """(d_embed, d_deep, d_vis): the text tower's backward, then the image tower's."""
+        t, m = self.text, self.model
+        with m._launch_lock:
+            check(lib.clipmi_text_encoder_backward_deep(m._handle, C.byref(t.dgrad[0]), d_text.data_ptr(), t.C, t.rows, self.nt, self.dt - 1,
+                                                        t.d_embed.data_ptr(), self.d_deep.data_ptr() if self.dt > 1 else None, t.ws.data_ptr(),
+                                                        t.ws.numel(), t.stash.data_ptr(), t.stash.numel(),
+                                                        None if stats_text is None else stats_text.data_ptr(), ops._stream()),
+                  "clipmi_text_encoder_backward_deep")
+        return t.d_embed, (self.d_deep if self.dt > 1 else None), self.vision.backward(d_feats, stats_vision)
+
+    def head_workspace(self, B: int) -> torch.Tensor:
+        need = lib.clipmi_promptsrc_head_workspace_bytes(B, self.E, self.C)
+        if self.head_ws is None or self.head_ws.numel() < need:
+            self.head_ws = torch.empty(max(need, 8), dtype=torch.uint8, device=self.model.device)
+        return self.head_ws
+
+    def one_call_workspace(self, B: int) -> torch.Tensor:
+        need = lib.clipmi_promptsrc_train_step_bytes(self.model._handle, self.C, self.text.rows, B, self.nt, self.dt, self.nv)
+        if self.one_ws is None or self.one_ws.numel() < need:
+            self.one_ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.model.device)
+        return self.one_ws
+
+
+def _method_weights(who: str, method: str, w_text: float, w_image: float, w_logit: float):
+    if method not in METHODS:
+        raise ValueError(f"{who}: method={method!r} must be one of {METHODS}")
+    return (0.0, 0.0, 0.0) if method == "ivlp" else _check_weights(who, w_text, w_image, w_logit)
+
+
+def gradients(model, params: Dict[str, torch.Tensor], images: torch.Tensor, labels, tokenized_prompts, teacher: torch.Tensor, logit_scale: float = 4.6052,
+              w_text: float = 25.0, w_image: float = 10.0, w_logit: float = 1.0, grad_scale: float = DEFAULT_GRAD_SCALE, seq_rows: Optional[int] = None,
+              return_operand_stats: bool = False, return_features: bool = False, method: str = "promptsrc", class_token_position: str = "end"):
+    """``(losses, grads)`` of PromptSRC's loss on one batch with respect to every prompt parameter, on the GPU: losses fp32 [5] (total, CE,
+    text L1, image L1, logit KL; the last three unweighted), grads a dict of fp32 tensors under ``params``' names.  ``images`` [B, 3, R, R]
+    preprocessed, ``tokenized_prompts`` [C, context_length] the ids of ``"X .. X name."``, ``teacher`` [C, E] the frozen text features;
+    ``seq_rows`` as ``coopfit.context_gradient`` takes it.  ``return_operand_stats`` adds ``{"text": {...}, "vision": {...}}`` as
+    ``maplefit.gradients`` does; ``return_features`` adds ``{"text", "feats", "zs"}``, the raw features the head was given.  A diagnostic
+    entry point: every call allocates both towers' workspaces and stashes."""
+    who = "promptsrcfit.gradients"
+    gs = _check_grad_scale(who, grad_scale)
+    wt, wi, wl = _method_weights(who, method, w_text, w_image, w_logit)
+    if not math.isfinite(logit_scale):
+        raise ValueError(f"{who}: logit_scale={logit_scale} (finite)")
+    tw = _Towers(who, model, tokenized_prompts, params, seq_rows, class_token_position)
+    teacher = _check_teacher(who, model, teacher, tw.C)
+    images = tw.vision.images(who, images)
+    dev = images.device
+    labels_d = _labels_dev(who, labels, images.shape[0], tw.C, dev)
+    block = pack_block(params, dev)
+    zs = tw.frozen(images)
+    text, feats = tw.forward(block, images)
+    scale = float(np.float32(math.exp(logit_scale)))
+    st = torch.zeros(4, dtype=torch.int64, device=dev) if return_operand_stats else None
+    sv = torch.zeros(4, dtype=torch.int64, device=dev) if return_operand_stats else None
+    losses, d_feats, d_text = promptsrc_head(feats, zs, text, teacher, labels_d, scale, gs, wt, wi, wl)
+    d_embed, d_deep, d_vis = tw.backward(d_text, d_feats, st, sv)
+    grad = promptsrc_step(d_embed, d_deep, d_vis, block, tw.C, tw.text.L, *tw.shape(), gs, apply=False)
+    out = (losses, {k: v.clone() for k, v in unpack_block(grad, *tw.shape()).items()})
+    if return_operand_stats:
+        out += ({"text": coopfit.operand_stats_dict(st), "vision": coopfit.operand_stats_dict(sv)},)
+    if return_features:
+        out += ({"text": text.clone(), "feats": feats.clone(), "zs": zs.clone()},)
+    return out
+
+
+class PromptSRCFitState:
+    """The training state of PromptSRC's (or IVLP's) prompts: the fp32 master ``block``, SGD's momentum buffer, GPA's running sum, both
+    towers' stashes and the number of steps taken.  ``step`` enqueues one forward, backward and update, ``end_epoch`` one accumulation;
+    neither synchronises.  ``params()`` names the block's views."""
+
+    def __init__(self, model, tokenized_prompts, params: Dict[str, torch.Tensor], teacher: torch.Tensor, logit_scale: float = 4.6052,
+                 w_text: float = 25.0, w_image: float = 10.0, w_logit: float = 1.0, momentum: float = 0.9, dampening: float = 0.0, nesterov: bool = False,
+                 weight_decay: float = 5e-4, grad_scale: float = DEFAULT_GRAD_SCALE, seq_rows: Optional[int] = None, method: str = "promptsrc",
+                 class_token_position: str = "end"):
+        who = "PromptSRCFitState"
+        self.grad_scale = _check_grad_scale(who, grad_scale)
+        _check_sgd(who, momentum, dampening, weight_decay, nesterov)
+        self.weights = _method_weights(who, method, w_text, w_image, w_logit)
+        if not math.isfinite(logit_scale):
+            raise ValueError(f"{who}: logit_scale={logit_scale} (finite)")
+        self.towers = _Towers(who, model, tokenized_prompts, params, seq_rows, class_token_position)
+        self.C = self.towers.C
+        self.teacher = _check_teacher(who, model, teacher, self.C)
+        self.block = pack_block(params, model.device)
+        self.buf = torch.zeros_like(self.block) if momentum != 0.0 else None
+        self.gpa = None
+        self.epochs_seen = 0
+        self.scale = float(np.float32(math.exp(logit_scale)))
+        self.momentum, self.dampening, self.nesterov, self.weight_decay = momentum, dampening, nesterov, weight_decay
+        self.steps = 0
+
+    def params(self, block: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+        return unpack_block(self.block if block is None else block, *self.towers.shape())
+
+    def step(self, images: torch.Tensor, labels, lr, want_loss: bool = False, one_call: bool = False) -> Optional[torch.Tensor]:
+        """One optimiser step on the batch ``images`` [B, 3, R, R] (preprocessed, fp16 or fp32, on the GPU) and ``labels`` [B] at the rate
+        ``lr``: an fp32 tensor of one element on the device is read where it lies; a Python number is uploaded on every call.  A label
+        tensor on the GPU is taken as it is -- a label outside [0, C) then makes the parameters NaN, it is never used as an address; host
+        labels are range-checked.  ``one_call``: the same launches through clipmi_promptsrc_train_step, whose workspace holds both
+        towers'.  Returns the batch's total loss, fp32 [1] on the device (a view of the five terms kept in ``last_losses``), when
+        ``want_loss``."""
+        who = "PromptSRCFitState.step"
+        tw = self.towers
+        t, v, m = tw.text, tw.vision, tw.model
+        images = v.images(who, images)
+        dev, B = images.device, images.shape[0]
+        labels_d = _labels_dev(who, labels, B, self.C, dev)
+        lr_d = ops._dev(lr, "lr", (torch.float32,)) if isinstance(lr, torch.Tensor) else torch.tensor([float(lr)], dtype=torch.float32).to(dev)
+        first = self.steps == 0
+        sgd = (float(self.momentum), float(self.dampening), float(self.weight_decay), int(bool(self.nesterov)))
+        losses = torch.empty(5, dtype=torch.float32, device=dev)
+        if one_call:
+            v.size(B, tower_ws=False)
+            ws = tw.one_call_workspace(B)
+            with m._launch_lock:
+                check(lib.clipmi_promptsrc_train_step(m._handle, C.byref(t.dgrad[0]), C.byref(v.dgrad[0]), t.base.data_ptr(), _DT[t.base.dtype],
+                                                      t.eot.data_ptr(), t.C, t.rows, images.data_ptr(), _DT[images.dtype], B, labels_d.data_ptr(),
+                                                      self.teacher.data_ptr(), self.block.data_ptr(), None if self.buf is None else self.buf.data_ptr(),
+                                                      tw.nt, tw.dt, tw.nv, tw.dv, self.scale, self.grad_scale, *self.weights, lr_d.data_ptr(), int(first),
+                                                      *sgd, losses.data_ptr(), None, ws.data_ptr(), ws.numel(), t.stash.data_ptr(), t.stash.numel(),
+                                                      v.stash.data_ptr(), v.stash.numel(), ops._stream()), "clipmi_promptsrc_train_step")
+        else:
+            zs = tw.frozen(images)
+            text, feats = tw.forward(self.block, images)
+            _, d_feats, d_text = promptsrc_head(feats, zs, text, self.teacher, labels_d, self.scale, self.grad_scale, *self.weights, losses=losses,
+                                                ws=tw.head_workspace(B))
+            d_embed, d_deep, d_vis = tw.backward(d_text, d_feats)
+            promptsrc_step(d_embed, d_deep, d_vis, self.block, t.C, t.L, *tw.shape(), self.grad_scale, self.buf, lr_d, first, *sgd, want_grad=False)
+        self.steps += 1
+        self.last_losses = losses
+        return losses[:1] if want_loss else None
+
+    def end_epoch(self, weight: float) -> None:
+        """GPA: add ``weight`` times the block as it stands to the running sum (one launch; the first call initialises the sum)."""
+        if self.gpa is None:
+            self.gpa = torch.empty_like(self.block)
+        gpa_accumulate(self.block, self.gpa, weight, self.epochs_seen == 0)
+        self.epochs_seen += 1
+
+    def apply_gpa(self) -> None:
+        """The running sum replaces the parameters (after the last epoch)."""
+        if self.gpa is not None:
+            self.block.copy_(self.gpa)
+
+
+def _gpa_for(who: str, gpa, epochs: int) -> Optional[np.ndarray]:
+    if gpa is None or epochs < 1:
+        return None
+    if isinstance(gpa, (tuple, list)) and len(gpa) == 2:
+        return gpa_weights(epochs, float(gpa[0]), float(gpa[1]))
+    w = np.asarray(gpa, np.float64)
+    if w.shape != (epochs,):
+        raise ValueError(f"{who}: gpa must be None, (mean, std) or {epochs} weights, got {gpa!r}")
+    return w
+
+
+def init_params(model, seed: int = 0) -> Dict[str, torch.Tensor]:
+    """The model's own prompt tokens (copies) and a ``ctx`` from N(0, 0.02^2) of the model's ``language_ctx`` rows."""
+    nt = int(model.design_details.get("language_ctx", 0))
+    if nt < 1:
+        raise ValueError("promptsrcfit: the model's design_details carry no language_ctx")
+    ctx = 0.02 * torch.randn(nt, int(model.geometry.transformer_width), generator=torch.Generator().manual_seed(seed))
+    return {k: v.detach().float().clone() for k, v in model_params(model, ctx).items()}
+
+
+def fit_prompts(images_or_loader, labels, model, tokenized_prompts, teacher: torch.Tensor, params: Optional[Dict[str, torch.Tensor]] = None,
+                method: str = "promptsrc", logit_scale: float = 4.6052, lr: float = 0.0025, epochs: int = 50, batch_size: int = 4, momentum: float = 0.9,
+                dampening: float = 0.0, weight_decay: float = 5e-4, nesterov: bool = False, w_text: float = 25.0, w_image: float = 10.0,
+                w_logit: float = 1.0, gpa=(30.0, 30.0), grad_scale: float = DEFAULT_GRAD_SCALE, seq_rows: Optional[int] = None,
+                lr_per_epoch: Optional[Sequence[float]] = None, drop_last: bool = False, return_history: bool = False, one_call: bool = False,
+                class_token_position: str = "end"):
+    """Train the prompts starting from ``params`` (not modified; None = ``init_params(model)``): ``epochs`` passes of
+    ``torch.optim.SGD(lr, momentum, dampening, weight_decay, nesterov)`` over the whole parameter list on PromptSRC's loss.
+    ``images_or_loader`` is a tensor of preprocessed images [N, 3, R, R] with ``labels`` [N], cut into batches of ``batch_size`` in order
+    (the last one short unless ``drop_last``), or a sized iterable of (images, labels) batches iterated once per epoch (``labels`` None,
+    ``batch_size`` unused).  ``lr_per_epoch`` gives every epoch's rate; None takes ``cosine_warmup_schedule(lr, epochs)``.  ``gpa``:
+    ``(mean, std)`` of ``gpa_weights``, or the epochs' weights themselves, or None for the last epoch's parameters;
+    ``method="ivlp"`` sets the three weights to 0 and ``gpa`` to None.  Three towers run on every step; nothing synchronises until the one
+    wait at the end.  Returns the fitted parameters, a dict of fp32 tensors on the device (views of one block), or ``(params, per-step
+    total losses)`` with ``return_history``.  The model's parameters are NOT written: ``trainers.promptsrc.CustomCLIP.fit_prompts`` does
+    that."""
+    who = "fit_prompts"
+    epochs = int(epochs)
+    if epochs < 0:
+        raise ValueError(f"{who}: epochs={epochs} (>= 0)")
+    if method not in METHODS:
+        raise ValueError(f"{who}: method={method!r} must be one of {METHODS}")
+    if params is None:
+        params = init_params(model)
+    state = PromptSRCFitState(model, tokenized_prompts, params, teacher, logit_scale, w_text, w_image, w_logit, momentum, dampening, nesterov, weight_decay,
+                              grad_scale, seq_rows, method, class_token_position)
+    weights = None if method == "ivlp" else _gpa_for(who, gpa, epochs)
+    if isinstance(images_or_loader, torch.Tensor):
+        N, bs = images_or_loader.shape[0], int(batch_size)
+        if bs < 1:
+            raise ValueError(f"{who}: batch_size={batch_size} (>= 1)")
+        per_epoch = steps_per_epoch(N, bs, drop_last)
+        lab = _labels_dev(who, labels, N, state.C, model.device)
+        batches = [(images_or_loader[k * bs:min((k + 1) * bs, N)], lab[k * bs:min((k + 1) * bs, N)]) for k in range(per_epoch)]
+    else:
+        batches = images_or_loader
+        per_epoch = len(batches)
+    rates = cosine_warmup_schedule(lr, epochs) if lr_per_epoch is None else [float(r) for r in lr_per_epoch]
+    if len(rates) != epochs:
+        raise ValueError(f"{who}: {len(rates)} learning rates for {epochs} epochs")
+    losses = []
+    if epochs * per_epoch:
+        dev = model.device
+        lr_steps = torch.from_numpy(np.repeat(np.asarray(rates, np.float64), per_epoch).astype(np.float32)).to(dev)
+        step = 0
+        for e in range(epochs):
+            for x, y in batches:
+                loss = state.step(x, y, lr_steps[step:step + 1], want_loss=return_history, one_call=one_call)
+                if return_history:
+                    losses.append(loss)
+                step += 1
+            if weights is not None:
+                state.end_epoch(float(weights[e]))
+        if weights is not None:
+            state.apply_gpa()
+        torch.cuda.current_stream(dev).synchronize()   # the run's one synchronisation
+    if return_history:
+        return state.params(), (torch.cat(losses).cpu().numpy() if losses else np.zeros(0, np.float32))
+    return state.params()

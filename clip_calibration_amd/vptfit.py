@@ -21,7 +21,7 @@ every step with one synchronisation at the end.  The image tower runs on every s
 The defaults -- SGD at 0.0025 with momentum 0.9 and weight decay 5e-4, 5 epochs, a constant warm-up epoch handing over to a cosine
 schedule -- restate the reference's VPT config and Dassl's public defaults and are UNVERIFIED here; each is an argument.
 
-Not covered: PromptSRC and IVLP training (MaPLe trains through ``maplefit``, on this tower), ViT-L lengths (more
+Not covered (MaPLe trains through ``maplefit`` and PromptSRC / IVLP through ``promptsrcfit``, on this tower): ViT-L lengths (more
 than 224 token rows per image), ``nn.DataParallel``, the reference's ``amp`` branch, the ResNet towers.
 """
 from __future__ import annotations

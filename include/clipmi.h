@@ -957,6 +957,71 @@ int clipmi_maple_train_step(clipmi_model* m, const clipmi_text_dgrad* wt, const 
                             size_t text_stash_bytes, void* vision_stash, size_t vision_stash_bytes, clipmi_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------
+ * PromptSRC's and IVLP's independent prompts trained on the device (trainers/classification/promptsrc.py:73-317; clip/model.py:191-256):
+ * MaPLe's two training towers without the coupling functions -- the text prompts (ctx and the blocks' VPT_shallow) and the image prompts
+ * (visual.VPT and the image blocks' VPT_shallow) are parameters of their own -- and a head of four terms against a frozen teacher: the
+ * cross-entropy, two L1 distances (text features to the teacher's text features, image features to the frozen plain tower's) and the KL
+ * divergence of the prompted logits from the teacher's (csrc/promptsrc_train.hip, csrc/prompt_train.hip, DESIGN.md "PromptSRC fit").
+ * The master block, dt / dv = the text / image prompt depth:
+ *   [ ctx [nt, Dt] | text deep [dt - 1, nt, Dt] | visual.VPT and image deep [dv, nv, Dv] ]
+ * Its text part is the [ctx; deep] pair of clipmi_text_encoder_train_deep, its image part the block of clipmi_vision_encoder_train.
+ * IVLP is the same path with the three weights 0.  These exports are additive: the ABI version does not change with them.
+ * ---------------------------------------------------------------------------------------------------- */
+
+/* The head.  feats fp32 [B, E] (row stride ld) the prompted image features, zs_feats fp32 [B, E] (dense) the frozen plain tower's,
+ * text fp32 [C, E] the prompted text features, teacher fp32 [C, E] the frozen text features; all four are normalised here:
+ *   x_b = f_b / |f_b|;  y_b = zs_b / |zs_b|;  u_c = t_c / |t_c|;  o_c = teacher_c / |teacher_c|;  z = scale X U^T;  zz = scale Y O^T
+ *   p = softmax(z_b);  q = softmax(zz_b)
+ *   loss = mean_b CE(z_b, label_b) + w_text mean_{c,e} |u - o| + w_image mean_{b,e} |x - y| + w_logit sum_{b,c} q (log q - log p) / (B C)
+ *   dz = grad_scale ((p - onehot) / B + w_logit (p - q) / (B C))
+ * d_text [C, E] (and its fp16 copy d_text16, may be NULL) and d_feats [B, E] are clipmi_maple_head's on that dz, plus the images of
+ * grad_scale w_text sign(u - o) / (C E) and grad_scale w_image sign(x - y) / (B E) under the two normalisation backwards; sign(0) = 0 and
+ * an addend of exactly 0 is not added.  losses fp32 [5] = {total, CE, text L1, image L1, logit KL}: each the float64 mean of fp32 row
+ * sums in a fixed order, each unweighted but the total.  A term whose weight is 0 is SKIPPED, not multiplied in: its loss reads 0, its
+ * operand is not read beyond the pointer check, and with all three weights 0 d_text, d_feats and losses[0] are clipmi_maple_head's bit
+ * for bit.  w_text, w_image, w_logit: finite, >= 0.  A label outside [0, C) is never used as an address: it makes the cross-entropy,
+ * the total and that row's gradient NaN.  A zero row of teacher or zs_feats has no direction: with a non-zero weight that reads it, that
+ * row's terms, and through the means the losses they enter, are NaN (as clipmi_prompt_head documents for KgCoOp's teacher).
+ * workspace (8-byte aligned) of clipmi_promptsrc_head_workspace_bytes bytes.  Six launches with all weights 0, nine with none 0 (two norm, two logits, the softmax, the two gradient kernels, the L1 kernel, the losses).
+ * No float atomics: the same inputs give the same bits.  Every refusal comes ahead of the first launch. */
+size_t clipmi_promptsrc_head_workspace_bytes(int B, int E, int C);
+int clipmi_promptsrc_head(const float* feats, int64_t ld, const float* zs_feats, const float* text, const float* teacher, const int64_t* labels,
+                          int B, int E, int C, float scale, float grad_scale, float w_text, float w_image, float w_logit, float* losses,
+                          float* d_feats, float* d_text, void* d_text16, void* workspace, size_t workspace_bytes, clipmi_stream_t stream);
+
+/* Floats of the master block (0 for arguments the calls refuse). */
+size_t clipmi_promptsrc_block_floats(int nt, int dt, int Dt, int nv, int dv, int Dv);
+
+/* torch.optim.SGD's step on every element of the master block, one launch.  d_embed fp32 [C * L, Dt] and d_deep fp32 [dt - 1, nt, Dt]
+ * (NULL with dt == 1) from clipmi_text_encoder_backward_deep, d_vis fp32 [dv, nv, Dv] from clipmi_vision_encoder_backward.  ctx's gradient
+ * is d_embed's rows 1 .. nt summed over the classes in ascending order, as clipmi_ctx_step sums them; every gradient times 1 / grad_scale,
+ * then clipmi_ctx_step's rule.  The ctx part equals clipmi_ctx_step and the image part clipmi_vpt_step on the same inputs bit for bit.
+ * grad_out (the block's shape, may be NULL) receives the gradient before weight decay.  apply == 0: only grad_out is written. */
+int clipmi_promptsrc_step(const float* d_embed, const float* d_deep, const float* d_vis, float* block, float* buf, float* grad_out, int apply,
+                          int C, int L, int nt, int dt, int Dt, int nv, int dv, int Dv, float grad_scale, const float* lr, int first_step,
+                          float momentum, float dampening, float weight_decay, int nesterov, clipmi_stream_t stream);
+
+/* Gaussian-weighted prompt aggregation, one launch over n floats: gpa = first ? weight * block : fmaf(weight, block, gpa). */
+int clipmi_gpa_accumulate(const float* block, float* gpa, int64_t n, float weight, int first, clipmi_stream_t stream);
+
+/* One training step as ONE call: clipmi_encode_image (no hook, CLIPMI_CALL_STREAM_F32, on this handle: no second copy of the weights),
+ * clipmi_text_encoder_train_deep, clipmi_vision_encoder_train, clipmi_promptsrc_head, clipmi_text_encoder_backward_deep,
+ * clipmi_vision_encoder_backward and clipmi_promptsrc_step enqueued in this order on `stream` -- the same launches, the same bits.  The
+ * frozen forward runs the fp32 residual stream, as the training forward does; it keeps its fused kernels, which apply QuickGELU to c_fc's
+ * fp32 accumulator where the training forward rounds the pre-activation to fp16 first: a model whose image prompts change nothing gives
+ * x = y up to that rounding point, not bit for bit.  teacher fp32 [C, E]; block is the fp32 master, updated in place; losses fp32 [5].
+ * workspace of clipmi_promptsrc_train_step_bytes(...) bytes (256-byte aligned; the frozen forward shares the image tower's part); the
+ * stashes as clipmi_text_train_bytes / clipmi_vision_train_bytes (with nv) report.  Every refusal comes ahead of the first launch. */
+size_t clipmi_promptsrc_train_step_bytes(const clipmi_model* m, int n_prompts, int seq_rows, int B, int nt, int dt, int nv);
+int clipmi_promptsrc_train_step(clipmi_model* m, const clipmi_text_dgrad* wt, const clipmi_vision_dgrad* wv, const void* prompts, int dtype,
+                                const int32_t* eot, int n_prompts, int seq_rows, const void* image, int image_dtype, int B,
+                                const int64_t* labels, const float* teacher, float* block, float* buf, int nt, int dt, int nv, int dv,
+                                float scale, float grad_scale, float w_text, float w_image, float w_logit, const float* lr, int first_step,
+                                float momentum, float dampening, float weight_decay, int nesterov, float* losses, float* grad_out,
+                                void* workspace, size_t workspace_bytes, void* text_stash, size_t text_stash_bytes, void* vision_stash,
+                                size_t vision_stash_bytes, clipmi_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------
  * KgCoOp's and ProGrad's context trained on the device (trainers/classification/kgcoop.py:246-269, prograd.py:291-304, 371-409): CoOp's
  * forward and backward with another loss head and, for ProGrad, a projection between the backward and the optimiser (DESIGN.md
  * "KgCoOp / ProGrad fit").  `mode` is a plain integer: 0 CoOp, 1 KgCoOp, 2 ProGrad.  `teacher` fp32 [C, E]: the frozen zero-shot text
