@@ -98,6 +98,12 @@ class TextDgrad(C.Structure):
     _fields_ = [("proj", C.c_void_p), ("blocks", C.POINTER(BlockDgrad))]
 
 
+class ScalerState(C.Structure):
+    """clipmi_scaler_state: the dynamic loss scale's device block, 20 bytes (include/clipmi.h)."""
+    _fields_ = [("scale", C.c_float), ("growth_tracker", C.c_int32), ("skipped_steps", C.c_int32), ("applied_steps", C.c_int32),
+                ("found_inf", C.c_int32)]
+
+
 class VisionDgrad(C.Structure):
     """clipmi_vision_dgrad: visual.proj as fp16 [Dv, E] and the image blocks' transposed weights."""
     _fields_ = [("proj", C.c_void_p), ("blocks", C.POINTER(BlockDgrad))]
@@ -221,6 +227,12 @@ _SIGNATURES = {
     "clipmi_prompt_train_step_bytes": (_sz, [_vp, _i, _i, _i, _i, _i, _i]),
     "clipmi_prompt_train_step": (_i, [_vp, C.POINTER(TextDgrad), _vp, _i, _vp, _vp, _i, _i, _vp, _i, _i, _vp, _i64, _vp, _i, _f, _f, _i, _vp, _f, _f,
                                       _f, _vp, _i, _f, _f, _f, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
+    "clipmi_grad_scale_rows": (_i, [_vp, _i, _i, _vp, _vp]),
+    "clipmi_ctx_step_scaled_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "clipmi_ctx_step_scaled": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _f, _f, _i, _vp, _f, _f, _f, _i, _vp, _sz, _vp]),
+    "clipmi_prompt_train_step_scaled_bytes": (_sz, [_vp, _i, _i, _i, _i, _i, _i]),
+    "clipmi_prompt_train_step_scaled": (_i, [_vp, C.POINTER(TextDgrad), _vp, _i, _vp, _vp, _i, _i, _vp, _i, _i, _vp, _i64, _vp, _i, _f, _vp, _f, _f, _i,
+                                             _i, _vp, _f, _vp, _f, _f, _f, _i, _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
     "clipmi_proda_embed": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "clipmi_proda_head_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "clipmi_proda_head": (_i, [_vp, _i64, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _f, _vp, _vp, _vp, _sz, _vp]),

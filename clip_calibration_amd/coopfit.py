@@ -13,7 +13,14 @@ operands, fp32 accumulation, fp32 residual and gradient streams, an fp32 master 
 
 ``grad_scale``: fp16 operands flush small gradients, so the whole backward carries ``grad_scale`` times the gradient (a power of two: the
 scaling itself is exact); the loss head multiplies and the context step divides.  The default, 2^12, comes from the measurement in
-profiles/coopfit_parity.txt (ViT-B/16 text geometry); a model with much larger gradients needs a smaller one.
+profiles/coopfit_parity.txt (ViT-B/16 text geometry); a model with much larger gradients needs a smaller one -- or
+``grad_scale="dynamic"``, the reference's ``prec == "amp"`` branch (coop.py:286-291, ``torch.cuda.amp.GradScaler``) for CoOp and KgCoOp:
+the scale lives in a small block on the device, a step whose context gradient holds an inf or a NaN is skipped (neither the context nor the
+momentum buffer changes, and the buffer starts on the first step that is applied), the scale is multiplied by ``backoff_factor`` after a
+skipped step and by ``growth_factor`` after ``growth_interval`` clean steps in a row.  ``scaler`` is a dict of ``init_scale``,
+``growth_factor``, ``backoff_factor`` and ``growth_interval`` (torch's defaults: 2^16, 2, 0.5, 2000; the scale and both factors powers
+of two, so the scaling stays exact).  No step reads anything back; ``CoOpFitState.scaler_state()`` does, once.  With a scale that never
+changes the dynamic path gives the static path's bits.  DESIGN.md "Dynamic loss scale".
 
 Three ways in.  ``context_gradient`` returns one batch's loss and gradient (the diagnostic entry point of the tests).  ``fit_context``
 trains from a cached [N, E] matrix of image features and enqueues every step of every epoch with one synchronisation at the end: that
@@ -55,7 +62,7 @@ from .tempfit import cosine_warmup_schedule, steps_per_epoch
 # 2^12, measured on the ViT-B/16 text geometry with synthetic weights (profiles/coopfit_parity.txt, "grad_scale"): the smallest of 2^0, 2^4,
 # 2^8, 2^12, 2^16 that leaves under 1 % of the fp16 dgrad-GEMM operand elements subnormal (0.76 %; 6.8 % at 2^8, 52 % at 2^0) with at least
 # 2^4 of headroom below fp16's largest value (2^5.9; 2^1.9 at 2^16).  A model whose gradients are much larger than that model's overflows
-# fp16 at this scale -- the context then turns NaN, it does not go wrong silently; pass a smaller power of two.
+# fp16 at this scale -- the context then turns NaN, it does not go wrong silently; pass a smaller power of two, or grad_scale="dynamic".
 DEFAULT_GRAD_SCALE = 4096.0
 
 _DT = {torch.float16: _lib.F16, torch.float32: _lib.F32}
@@ -66,6 +73,41 @@ def _check_grad_scale(who: str, grad_scale: float) -> float:
     if not (math.isfinite(g) and g > 0.0 and math.frexp(g)[0] == 0.5):
         raise ValueError(f"{who}: grad_scale={grad_scale} must be a power of two (the scaling has to be exact)")
     return g
+
+
+DYNAMIC = "dynamic"
+
+
+def _is_dynamic(who: str, grad_scale) -> bool:
+    """True for ``grad_scale="dynamic"``; any other string is refused, a number is the static path's."""
+    if isinstance(grad_scale, str):
+        if grad_scale != DYNAMIC:
+            raise ValueError(f"{who}: grad_scale={grad_scale!r} must be a power of two or {DYNAMIC!r}")
+        return True
+    return False
+
+
+def _check_scaler(who: str, scaler) -> dict:
+    """torch.cuda.amp.GradScaler's arguments with its defaults filled in; the scale and both factors must be powers of two."""
+    if scaler is not None and not isinstance(scaler, dict):
+        raise ValueError(f"{who}: scaler must be a dict of {sorted(ops.SCALER_DEFAULTS)} or None")
+    cfg = dict(ops.SCALER_DEFAULTS)
+    for k, v in (scaler or {}).items():
+        if k not in cfg:
+            raise ValueError(f"{who}: scaler has no option {k!r} (one of {sorted(cfg)})")
+        cfg[k] = v
+    for k in ("init_scale", "growth_factor", "backoff_factor"):
+        g = float(cfg[k])
+        if not (math.isfinite(g) and 2.0 ** -126 <= g <= 2.0 ** 127 and math.frexp(g)[0] == 0.5):
+            raise ValueError(f"{who}: scaler[{k!r}]={cfg[k]} must be a finite, positive power of two of fp32's range (the scaling has to be exact)")
+        cfg[k] = g
+    if cfg["growth_factor"] < 1.0 or cfg["backoff_factor"] > 1.0:
+        raise ValueError(f"{who}: scaler growth_factor={cfg['growth_factor']} (>= 1), backoff_factor={cfg['backoff_factor']} (<= 1)")
+    gi = cfg["growth_interval"]
+    if isinstance(gi, bool) or int(gi) != gi or not 1 <= int(gi) < 2 ** 31:
+        raise ValueError(f"{who}: scaler growth_interval={gi} must be an integer >= 1")
+    cfg["growth_interval"] = int(gi)
+    return cfg
 
 
 def _check_sgd(who: str, momentum: float, dampening: float, weight_decay: float, nesterov: bool) -> None:
@@ -225,8 +267,9 @@ class _Tower:
                                                    None if stats is None else stats.data_ptr(), ops._stream()), "clipmi_text_encoder_backward")
         return out
 
-    def one_call_workspace(self, B: int, method: str = "coop") -> torch.Tensor:
-        need = lib.clipmi_prompt_train_step_bytes(self.model._handle, self.C, self.rows, B, ops.PROMPT_MODES[method], self.n_ctx, int(self.per_class))
+    def one_call_workspace(self, B: int, method: str = "coop", scaled: bool = False) -> torch.Tensor:
+        sizer = lib.clipmi_prompt_train_step_scaled_bytes if scaled else lib.clipmi_prompt_train_step_bytes
+        need = sizer(self.model._handle, self.C, self.rows, B, ops.PROMPT_MODES[method], self.n_ctx, int(self.per_class))
         if self.step_ws is None or self.step_ws.numel() < need:
             self.step_ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.ws.device)
         return self.step_ws
@@ -266,6 +309,8 @@ def context_gradient(clip_model, tokenized_prompts, ctx: torch.Tensor, features:
     (int32 [1]) and ``dots`` (float64 [3]: a.a, b.b, a.b of a = grad_xe, b = grad_kl); CoOp an empty one."""
     who = "context_gradient"
     Cn, n_ctx, per_class, last = _check_prompts(who, clip_model, tokenized_prompts, ctx)
+    if _is_dynamic(who, grad_scale):
+        raise ValueError(f"{who}: grad_scale={DYNAMIC!r} belongs to a fit (CoOpFitState, fit_context); one gradient needs a number")
     gs = _check_grad_scale(who, grad_scale)
     if not math.isfinite(logit_scale):
         raise ValueError(f"{who}: logit_scale={logit_scale} (finite)")
@@ -316,10 +361,19 @@ class CoOpFitState:
     def __init__(self, clip_model, tokenized_prompts, ctx: torch.Tensor, logit_scale: float = 4.6052, momentum: float = 0.9,
                  dampening: float = 0.0, nesterov: bool = False, weight_decay: float = 5e-4, grad_scale: float = DEFAULT_GRAD_SCALE,
                  seq_rows: Optional[int] = None, method: str = "coop", teacher: Optional[torch.Tensor] = None, w: float = 8.0, T: float = 1.0,
-                 lam: float = 1.0):
+                 lam: float = 1.0, scaler: Optional[dict] = None):
         who = "CoOpFitState"
         self.C, self.n_ctx, self.per_class, last = _check_prompts(who, clip_model, tokenized_prompts, ctx)
-        self.grad_scale = _check_grad_scale(who, grad_scale)
+        self.dynamic = _is_dynamic(who, grad_scale)
+        if self.dynamic:
+            if method == "prograd":
+                raise ValueError(f"{who}: grad_scale={DYNAMIC!r} covers method 'coop' and 'kgcoop'; ProGrad keeps a static scale")
+            self.scaler = _check_scaler(who, scaler)
+            self.grad_scale = None
+        else:
+            if scaler is not None:
+                raise ValueError(f"{who}: scaler is an argument of grad_scale={DYNAMIC!r}")
+            self.grad_scale = _check_grad_scale(who, grad_scale)
         _check_sgd(who, momentum, dampening, weight_decay, nesterov)
         if not math.isfinite(logit_scale):
             raise ValueError(f"{who}: logit_scale={logit_scale} (finite)")
@@ -336,14 +390,53 @@ class CoOpFitState:
         self.scale = float(np.float32(math.exp(logit_scale)))
         self.momentum, self.dampening, self.nesterov, self.weight_decay = momentum, dampening, nesterov, weight_decay
         self.steps = 0
+        if self.dynamic:
+            self.scaler_block = ops.new_scaler_state(self.scaler["init_scale"], dev)   # clipmi_scaler_state; only the kernels touch it from here on
+            self.scaled_ws = None
+
+    def scaler_state(self) -> dict:
+        """The dynamic scale's block as ``dict(scale, growth_tracker, skipped_steps, applied_steps, found_inf)`` (``found_inf``: of the
+        last step).  It waits for the steps enqueued so far: one synchronisation."""
+        if not self.dynamic:
+            raise ValueError(f"CoOpFitState.scaler_state: the state was made with a static grad_scale={self.grad_scale}")
+        return ops.scaler_state_dict(self.scaler_block)
+
+    def _step_scaled(self, features, labels_d, lr_d, losses, one_call: bool) -> None:
+        """``step`` under the dynamic scale: the head at grad_scale = 1, its d_text times the block's scale, the backward, and
+        clipmi_ctx_step_scaled, which decides on the device whether the step is applied."""
+        t, m, sc = self.tower, self.tower.model, self.scaler
+        sgd = (float(self.momentum), float(self.dampening), float(self.weight_decay), int(bool(self.nesterov)))
+        if one_call:
+            ws = t.one_call_workspace(features.shape[0], self.method, scaled=True)
+            with m._launch_lock:
+                check(lib.clipmi_prompt_train_step_scaled(m._handle, C.byref(t.dgrad[0]), t.base.data_ptr(), _DT[t.base.dtype], self.ctx.data_ptr(),
+                                                          None if self.buf is None else self.buf.data_ptr(), t.n_ctx, int(t.per_class),
+                                                          t.eot.data_ptr(), t.C, t.rows, features.data_ptr(), features.stride(0), labels_d.data_ptr(),
+                                                          features.shape[0], self.scale, self.scaler_block.data_ptr(), sc["growth_factor"],
+                                                          sc["backoff_factor"], sc["growth_interval"], ops.PROMPT_MODES[self.method],
+                                                          None if self.teacher is None else self.teacher.data_ptr(), self.w, lr_d.data_ptr(), *sgd,
+                                                          losses.data_ptr(), None, ws.data_ptr(), ws.numel(), t.stash.data_ptr(), t.stash.numel(),
+                                                          ops._stream()),
+                      "clipmi_prompt_train_step_scaled")
+            return
+        text = t.forward(self.ctx)
+        _, d_text, _ = ops.prompt_head(features, labels_d, text, self.scale, 1.0, self.method, self.teacher, self.w, 1.0, losses)
+        ops.grad_scale_rows(d_text, self.scaler_block)
+        d_embed = t.backward(d_text)
+        if self.scaled_ws is None:
+            need = lib.clipmi_ctx_step_scaled_workspace_bytes(t.C, t.D, t.n_ctx, int(t.per_class))
+            self.scaled_ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.ctx.device)
+        ops.ctx_step_scaled(d_embed, t.C, t.n_ctx, t.per_class, self.scaler_block, self.ctx, self.buf, lr_d, sc["growth_factor"], sc["backoff_factor"],
+                            sc["growth_interval"], *sgd[:3], bool(sgd[3]), want_grad=False, workspace=self.scaled_ws)
 
     def step(self, features: torch.Tensor, labels, lr, want_loss: bool = False, one_call: bool = False) -> Optional[torch.Tensor]:
         """One optimiser step on the batch ``features`` fp32 [B, E] (raw image features on the GPU) and ``labels`` [B] at the rate ``lr``:
         an fp32 tensor of one element on the device is read where it lies (``rates[k:k + 1]``); a Python number is uploaded on every call.
         A label tensor on the GPU is taken as it is -- a label outside [0, C) then makes the context NaN, it is never used as an address;
         host labels are range-checked.  ``one_call``: the same launches through the library's one-call step
-        (clipmi_prompt_train_step).  Returns the batch loss, fp32 [1] on the device, when ``want_loss``: the
-        total for KgCoOp, ``xe`` for ProGrad."""
+        (clipmi_prompt_train_step; clipmi_prompt_train_step_scaled under the dynamic scale).  Returns the batch loss, fp32 [1] on the
+        device, when ``want_loss``: the total for KgCoOp, ``xe`` for ProGrad.  Under the dynamic scale a skipped step still counts in
+        ``steps`` and still returns its loss; whether it was applied is in ``scaler_state()``."""
         lab = _check_batch("CoOpFitState.step", features, labels, self.C, self.tower.E)
         _need_gpu(features, "features")
         if features.dtype != torch.float32 or features.stride(1) != 1:
@@ -354,7 +447,9 @@ class CoOpFitState:
         t, m, first = self.tower, self.tower.model, self.steps == 0
         sgd = (self.momentum, self.dampening, self.weight_decay, self.nesterov)
         losses = _new_losses(self.method, dev)
-        if one_call:
+        if self.dynamic:
+            self._step_scaled(features, labels_d, lr_d, losses, one_call)
+        elif one_call:
             ws = t.one_call_workspace(features.shape[0], self.method)
             with m._launch_lock:
                 check(lib.clipmi_prompt_train_step(m._handle, C.byref(t.dgrad[0]), t.base.data_ptr(), _DT[t.base.dtype], self.ctx.data_ptr(),
@@ -392,7 +487,7 @@ def fit_context(features: torch.Tensor, labels, clip_model, tokenized_prompts, c
                 momentum: float = 0.9, dampening: float = 0.0, weight_decay: float = 5e-4, nesterov: bool = False,
                 grad_scale: float = DEFAULT_GRAD_SCALE, seq_rows: Optional[int] = None, lr_per_epoch: Optional[Sequence[float]] = None,
                 order=None, drop_last: bool = False, return_history: bool = False, method: str = "coop", teacher: Optional[torch.Tensor] = None,
-                w: float = 8.0, T: float = 1.0, lam: float = 1.0):
+                w: float = 8.0, T: float = 1.0, lam: float = 1.0, scaler: Optional[dict] = None):
     """Train CoOp's context on cached ``features`` fp32 [N, E] (raw image features on the GPU; the rows may be a column slice) and
     ``labels`` [N], starting from ``ctx`` (not modified; None = ``init_context(clip_model, n_ctx, C if csc else None)``): ``epochs``
     passes of ``torch.optim.SGD(lr, momentum, dampening, weight_decay, nesterov)`` over batches of ``batch_size``.
@@ -403,7 +498,9 @@ def fit_context(features: torch.Tensor, labels, clip_model, tokenized_prompts, c
     anything is launched; from the first launch on nothing synchronises until the one wait at the end.  Returns the fitted fp32 context
     on the device, or ``(ctx, per-step batch losses as a float32 numpy array)`` with ``return_history``.  The defaults are unverified
     restatements of the reference's config and Dassl's (module docstring).  ``method``, ``teacher``, ``w``, ``T``, ``lam``: KgCoOp's
-    or ProGrad's step in CoOp's place (module docstring); the history then holds KgCoOp's total loss or ProGrad's ``xe``."""
+    or ProGrad's step in CoOp's place (module docstring); the history then holds KgCoOp's total loss or ProGrad's ``xe``.
+    ``grad_scale="dynamic"`` with ``scaler`` (module docstring; CoOp and KgCoOp): a step that overflows fp16 is skipped on the device and
+    the scale adapts; the history keeps one loss per step, skipped steps included, and the run still synchronises once."""
     who = "fit_context"
     ids = _host_int_array(tokenized_prompts, "tokenized_prompts")
     if ctx is None:
@@ -417,7 +514,14 @@ def fit_context(features: torch.Tensor, labels, clip_model, tokenized_prompts, c
     if epochs < 0 or batch_size < 1:
         raise ValueError(f"{who}: epochs={epochs} (>= 0), batch_size={batch_size} (>= 1)")
     _check_sgd(who, momentum, dampening, weight_decay, nesterov)
-    _check_grad_scale(who, grad_scale)
+    if _is_dynamic(who, grad_scale):
+        if method == "prograd":
+            raise ValueError(f"{who}: grad_scale={DYNAMIC!r} covers method 'coop' and 'kgcoop'; ProGrad keeps a static scale")
+        _check_scaler(who, scaler)
+    else:
+        if scaler is not None:
+            raise ValueError(f"{who}: scaler is an argument of grad_scale={DYNAMIC!r}")
+        _check_grad_scale(who, grad_scale)
     _check_method(who, method, teacher, w, T, lam, Cn, E)
     lab = _labels(who, labels, N, Cn)
     if order is not None:
@@ -437,7 +541,7 @@ def fit_context(features: torch.Tensor, labels, clip_model, tokenized_prompts, c
     _need_gpu(features, "features")
     dev = features.device
     state = CoOpFitState(clip_model, tokenized_prompts, ctx, logit_scale, momentum, dampening, nesterov, weight_decay, grad_scale, seq_rows,
-                         method, teacher, w, T, lam)
+                         method, teacher, w, T, lam, scaler)
     lr_steps = torch.from_numpy(np.repeat(np.asarray(rates, np.float64), per_epoch).astype(np.float32)).to(dev)
     labels_d = torch.from_numpy(lab.astype(np.int64)).to(dev)
     order_d = None if order is None else torch.from_numpy(np.ascontiguousarray(order, dtype=np.int64)).to(dev)

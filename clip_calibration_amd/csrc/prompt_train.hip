@@ -277,21 +277,7 @@ int launch_head(const char* who, bool need_losses, const float* feats, int64_t l
 
 // --------------------------------------------------------------------------------------------------------------------- context step
 // one thread per element of ctx: the classes' rows added in ascending order (generic context), 1 / grad_scale, torch.optim.SGD's rule as
-// torch's GPU kernels round it (sgd_element_fma, train_rules.h)
-__device__ __forceinline__ float ctx_grad_element(const float* __restrict__ d_embed, int64_t idx, int C, int L, int D, int n_ctx, int per_class,
-                                                  float inv_scale) {
-  const int64_t per = (int64_t)n_ctx * D;
-  const int d = (int)(idx % D), j = (int)((idx / D) % n_ctx);
-  float g = 0.f;
-  if (per_class) {
-    const int64_t c = idx / per;
-    g = d_embed[((c * L) + 1 + j) * D + d];
-  } else {
-    for (int64_t c = 0; c < C; ++c) g += d_embed[((c * L) + 1 + j) * D + d];
-  }
-  return g * inv_scale;
-}
-
+// torch's GPU kernels round it (ctx_grad_element, sgd_element_fma: train_rules.h)
 __global__ __launch_bounds__(THREADS) void ctx_step_kernel(const float* __restrict__ d_embed, float* __restrict__ ctx, float* __restrict__ buf,
                                                            float* __restrict__ grad_out, int C, int L, int D, int n_ctx, int per_class, float inv_scale,
                                                            const float* __restrict__ lr, SgdArgs sgd) {

@@ -62,6 +62,23 @@ __device__ __forceinline__ void sgd_element_fma(float* __restrict__ w, float* __
   w[idx] = fmaf(-lr, grad, v);
 }
 
+// Element idx of the context's gradient from d_embed fp32 [C * L, D] (prompt_train.hip's ctx_step_kernel and ProGrad's step, grad_scaler.hip):
+// row 1 + j of every prompt belongs to context vector j; the classes' rows added in ascending order (generic context) or the class's own
+// row (per_class), times inv_scale
+__device__ __forceinline__ float ctx_grad_element(const float* __restrict__ d_embed, int64_t idx, int C, int L, int D, int n_ctx, int per_class,
+                                                  float inv_scale) {
+  const int64_t per = (int64_t)n_ctx * D;
+  const int d = (int)(idx % D), j = (int)((idx / D) % n_ctx);
+  float g = 0.f;
+  if (per_class) {
+    const int64_t c = idx / per;
+    g = d_embed[((c * L) + 1 + j) * D + d];
+  } else {
+    for (int64_t c = 0; c < C; ++c) g += d_embed[((c * L) + 1 + j) * D + d];
+  }
+  return g * inv_scale;
+}
+
 // torch.optim.Adam's rule on one element: g += wd w;  m += (g - m)(1 - b1)  (lerp_ with a weight below one half);
 // v = b2 v + ((1 - b2) g) g  (mul_, addcmul_);  w -= (lr / (1 - b1^t)) m / (sqrt(v) / sqrt(1 - b2^t) + eps)  (addcdiv_)
 __device__ __forceinline__ void adam_element(float* __restrict__ w, float* __restrict__ m, float* __restrict__ v, int64_t idx, float grad, float lr,

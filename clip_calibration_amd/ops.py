@@ -10,6 +10,7 @@ import collections
 import ctypes
 from typing import Optional, Tuple
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -978,7 +979,64 @@ def ctx_step(d_embed: torch.Tensor, n_prompts: int, n_ctx: int, per_class: bool,
     return grad
 
 
-PROMPT_MODES = {"coop": _lib.PROMPT_COOP, "kgcoop": _lib.PROMPT_KGCOOP, "prograd": _lib.PROMPT_PROGRAD}
+SCALER_DEFAULTS = {"init_scale": 2.0 ** 16, "growth_factor": 2.0, "backoff_factor": 0.5, "growth_interval": 2000}   # torch.cuda.amp.GradScaler's
+
+
+def new_scaler_state(init_scale: float, device) -> torch.Tensor:
+    """clipmi_scaler_state on ``device``: int32 [5] = {the fp32 bits of ``init_scale``, 0, 0, 0, 0}, one upload."""
+    words = np.zeros(5, np.int32)
+    words[:1].view(np.float32)[0] = init_scale
+    return torch.from_numpy(words).to(device)
+
+
+def scaler_state_dict(state: torch.Tensor) -> dict:
+    """The block as ``dict(scale, growth_tracker, skipped_steps, applied_steps, found_inf)``.  One read-back (it synchronises)."""
+    words = state.cpu().numpy()
+    return {"scale": float(words[:1].view(np.float32)[0]), "growth_tracker": int(words[1]), "skipped_steps": int(words[2]),
+            "applied_steps": int(words[3]), "found_inf": int(words[4])}
+
+
+def _scaler_state(who: str, state) -> int:
+    _in_place(state, torch.int32, f"{who}: state must be a contiguous int32 [5] tensor on the GPU (new_scaler_state)", numel=5)
+    return state.data_ptr()
+
+
+def grad_scale_rows(x: torch.Tensor, state: torch.Tensor) -> torch.Tensor:
+    """``x`` (contiguous fp32 matrix on the GPU) times the scale of the scaler's ``state`` block, in place; the scale is read on the device."""
+    _in_place(x, torch.float32, "grad_scale_rows: x must be a contiguous fp32 tensor on the GPU")
+    if x.dim() != 2:
+        raise ValueError(f"grad_scale_rows: x {tuple(x.shape)} must be a matrix")
+    check(lib.clipmi_grad_scale_rows(x.data_ptr(), x.shape[0], x.shape[1], _scaler_state("grad_scale_rows", state), _stream()),
+          "clipmi_grad_scale_rows")
+    return x
+
+
+def ctx_step_scaled(d_embed: torch.Tensor, n_prompts: int, n_ctx: int, per_class: bool, state: torch.Tensor, ctx: torch.Tensor,
+                    buf: Optional[torch.Tensor], lr: torch.Tensor, growth_factor: float = 2.0, backoff_factor: float = 0.5,
+                    growth_interval: int = 2000, momentum: float = 0.0, dampening: float = 0.0, weight_decay: float = 0.0,
+                    nesterov: bool = False, want_grad: bool = True, workspace: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
+    """``ctx_step`` under the dynamic loss scale of ``state`` (``new_scaler_state``): the gradient is ``d_embed``'s context rows divided
+    by the block's scale; a gradient with an inf or a NaN leaves ``ctx`` and ``buf`` as they are and backs the scale off, a clean one is
+    applied (the momentum buffer starts on the first applied step) and counts towards the next growth.  Nothing is read back.
+    ``workspace``: a uint8 tensor to reuse between steps.  Returns the unscaled gradient (ctx's shape) when ``want_grad``."""
+    who = "ctx_step_scaled"
+    d_embed = _dev(d_embed, "d_embed", (torch.float32,))
+    if ctx is None:
+        raise ValueError(f"{who}: ctx is required (the step decides whether to write it)")
+    L, D, shape, pc, pb, pl = _ctx_step_inputs(who, d_embed, n_prompts, n_ctx, per_class, ctx, buf, lr)
+    ps = _scaler_state(who, state)
+    grad = torch.empty(shape, dtype=torch.float32, device=d_embed.device) if want_grad else None
+    need = lib.clipmi_ctx_step_scaled_workspace_bytes(n_prompts, D, int(n_ctx), int(bool(per_class)))
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=d_embed.device)
+    check(lib.clipmi_ctx_step_scaled(d_embed.data_ptr(), pc, pb, None if grad is None else grad.data_ptr(), n_prompts, L, D, int(n_ctx),
+                                     int(bool(per_class)), ps, float(growth_factor), float(backoff_factor), int(growth_interval), pl,
+                                     float(momentum), float(dampening), float(weight_decay), int(bool(nesterov)), workspace.data_ptr(),
+                                     workspace.numel(), _stream()), "clipmi_ctx_step_scaled")
+    return grad
+
+
+PROMPT_MODES ={"coop": _lib.PROMPT_COOP, "kgcoop": _lib.PROMPT_KGCOOP, "prograd": _lib.PROMPT_PROGRAD}
 
 
 def prompt_head(features: torch.Tensor, labels: torch.Tensor, text: torch.Tensor, scale: float, grad_scale: float = 1.0, method: str = "coop",

@@ -161,7 +161,9 @@ class CustomCLIP(nn.Module):
         per epoch, every batch going transform -> image tower -> ``CoOpFitState.step`` with nothing synchronising until the end
         (``augment.fit_with_transform``).  ``fit_args``: ``epochs`` (200), ``lr`` (0.002), ``lr_per_epoch``, the optimiser's
         ``momentum``, ``dampening``, ``weight_decay``, ``nesterov``, ``grad_scale``, ``seq_rows``, ``views`` and ``return_history``;
-        the batch size and the order are the loader's."""
+        the batch size and the order are the loader's.  ``grad_scale="dynamic"`` with ``scaler=dict(init_scale, growth_factor,
+        backoff_factor, growth_interval)`` is the reference's ``amp`` branch on either route (``coopfit``'s module docstring): a step
+        that overflows fp16 is skipped on the device and the scale adapts, with no read-back per step."""
         import math
         fit_args.setdefault("logit_scale", math.log(self.scale))
         ctx = self.prompt_learner.ctx

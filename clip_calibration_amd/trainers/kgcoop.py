@@ -26,7 +26,8 @@ class CustomCLIP(_CoOpCLIP):
 
     def fit_context(self, train_loader, transform=None, **fit_args):
         """``coop.CustomCLIP.fit_context`` with KgCoOp's loss: ``method="kgcoop"``, ``teacher=self.ori_embedding`` and ``w=self.w``
-        unless ``fit_args`` say otherwise.  Needs the ``zeroshot_tokenized_prompts`` the model was built with."""
+        unless ``fit_args`` say otherwise.  Needs the ``zeroshot_tokenized_prompts`` the model was built with.  ``grad_scale="dynamic"``
+        and ``scaler`` (the reference's ``amp`` branch, kgcoop.py) pass through on both routes as they do for CoOp."""
         if fit_args.get("teacher", self.ori_embedding) is None:
             raise ValueError("kgcoop.CustomCLIP.fit_context: no ori_embedding -- build the model with zeroshot_tokenized_prompts")
         fit_args.setdefault("method", "kgcoop")

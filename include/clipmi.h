@@ -1073,6 +1073,66 @@ int clipmi_prompt_train_step(clipmi_model* m, const clipmi_text_dgrad* wt, const
                              int nesterov, float* losses, float* grad_out, int* projected, double* dots, void* workspace,
                              size_t workspace_bytes, void* stash, size_t stash_bytes, clipmi_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------
+ * A dynamic loss scale for the fits that step through clipmi_ctx_step (CoOp, KgCoOp): torch.cuda.amp.GradScaler's rule on the device
+ * (reference trainers/classification/coop.py:286-291; csrc/grad_scaler.hip, DESIGN.md "Dynamic loss scale").  The backward carries
+ * scale * gradient with the scale read from a device block, a step whose gradient holds an inf or a NaN changes neither the context nor the
+ * momentum buffer, and the scale backs off and grows again; nothing is read back to the host.  Additive exports: the ABI version stays.
+ *
+ * The scaler's state: 20 bytes on the device, 4-byte aligned, owned by the caller, who writes {init_scale, 0, 0, 0, 0} into it before the
+ * first step (on the stream or before it) and may read it after a synchronisation.  Only the calls below write it.
+ * ---------------------------------------------------------------------------------------------------- */
+typedef struct clipmi_scaler_state {
+  float scale;            /* the backward of the next step carries scale * gradient */
+  int32_t growth_tracker; /* clean steps in a row since the scale last changed, < growth_interval */
+  int32_t skipped_steps;  /* steps that found an inf or a NaN and were not applied */
+  int32_t applied_steps;  /* steps whose SGD update was applied */
+  int32_t found_inf;      /* 1 when the last step was skipped, else 0 */
+} clipmi_scaler_state;
+
+/* x[r, c] *= state->scale over a dense fp32 [rows, cols] matrix: clipmi_prompt_head run at grad_scale = 1 followed by this launch gives
+ * scale * d_text.  For a power-of-two scale the product is exact, so the result equals the head run at grad_scale = scale bit for bit --
+ * unless an fp32 intermediate of the head at grad_scale = 1 is a subnormal (or overflows at grad_scale = scale), where the two round
+ * differently.  One launch. */
+int clipmi_grad_scale_rows(float* x, int rows, int cols, const clipmi_scaler_state* state, clipmi_stream_t stream);
+
+/* clipmi_ctx_step under the scaler's rule.  d_embed, ctx ([n_ctx, D], or [C, n_ctx, D] with per_class != 0), buf, grad_out, lr (device) and
+ * the SGD rule as clipmi_ctx_step's, with four differences:
+ *   grad_scale is state->scale, read on the device;
+ *   found = any element of the gradient (a context row's sum over the classes, divided by the scale) is an inf or a NaN -- every element is
+ *     looked at, rows outside 1 .. n_ctx are not (torch._amp_foreach_non_finite_check_and_unscale_);
+ *   ctx and buf are written only when found is clear; grad_out (may be NULL) receives the unscaled gradient either way;
+ *   the momentum buffer is initialised from the gradient of the first APPLIED step (state->applied_steps == 0), not of the first call, as
+ *     torch.optim.SGD does when GradScaler.step skips the first steps: there is no first_step argument.
+ * Then torch._amp_update_scale_ on the block: found: scale *= backoff_factor, growth_tracker = 0, skipped_steps += 1; otherwise
+ * applied_steps += 1 and growth_tracker += 1, and when it reaches growth_interval the scale is multiplied by growth_factor (unless the
+ * product is not finite) and the tracker starts again.  found_inf = found.  ctx, lr and state are required.  Three launches: the gradient
+ * with one integer flag per workgroup, one workgroup that decides and updates the block, the step; no atomics, no workgroup reads what another
+ * of the same launch writes, the same inputs give the same bits.  With found clear ctx, buf and grad_out equal clipmi_ctx_step's at
+ * grad_scale = scale and first_step = (applied_steps == 0) bit for bit.  workspace (256-byte aligned):
+ * clipmi_ctx_step_scaled_workspace_bytes(C, D, n_ctx, per_class) bytes, 0 for arguments the call refuses.  Every check precedes the first
+ * launch.  CLIPMI_ERR_ARG: a null pointer, a factor that is not finite or not positive, growth_interval < 1, SGD's own refusals;
+ * CLIPMI_ERR_SHAPE: C < 1, D < 1, n_ctx < 1, 1 + n_ctx > L. */
+size_t clipmi_ctx_step_scaled_workspace_bytes(int C, int D, int n_ctx, int per_class);
+int clipmi_ctx_step_scaled(const float* d_embed, float* ctx, float* buf, float* grad_out, int C, int L, int D, int n_ctx, int per_class,
+                           clipmi_scaler_state* state, float growth_factor, float backoff_factor, int growth_interval, const float* lr,
+                           float momentum, float dampening, float weight_decay, int nesterov, void* workspace, size_t workspace_bytes,
+                           clipmi_stream_t stream);
+
+/* One training step of CoOp or KgCoOp under the scaler as ONE call: clipmi_text_encoder_train, clipmi_prompt_head at grad_scale = 1,
+ * clipmi_grad_scale_rows on its d_text, clipmi_text_encoder_backward and clipmi_ctx_step_scaled, enqueued in this order on `stream` --
+ * the same launches, the same bits as the calls one by one.  Arguments as clipmi_prompt_train_step's; mode 2 (ProGrad): CLIPMI_ERR_ARG
+ * (the reference's own amp branch hands GradScaler.scale a tuple there).  The scalar, shape and pointer checks of every stage precede
+ * the first launch.  workspace of clipmi_prompt_train_step_scaled_bytes(...) bytes (256-byte aligned; 0 for arguments the call refuses). */
+size_t clipmi_prompt_train_step_scaled_bytes(const clipmi_model* m, int n_prompts, int seq_rows, int B, int mode, int n_ctx,
+                                             int ctx_per_class);
+int clipmi_prompt_train_step_scaled(clipmi_model* m, const clipmi_text_dgrad* wt, const void* prompts, int dtype, float* ctx, float* buf,
+                                    int n_ctx, int ctx_per_class, const int32_t* eot, int n_prompts, int seq_rows, const float* feats,
+                                    int64_t ld, const int64_t* labels, int B, float scale, clipmi_scaler_state* state, float growth_factor,
+                                    float backoff_factor, int growth_interval, int mode, const float* teacher, float w, const float* lr,
+                                    float momentum, float dampening, float weight_decay, int nesterov, float* losses, float* grad_out,
+                                    void* workspace, size_t workspace_bytes, void* stash, size_t stash_bytes, clipmi_stream_t stream);
+
 /* ProDA's collection of contexts trained on the same frozen-tower backward (reference trainers/classification/proda.py:146-228, 258-304;
  * csrc/proda_train.hip, DESIGN.md "ProDA fit").  ctx fp32 [P, n_ctx, D] is the master of all P contexts; pos int32 [P] gives each one's
  * class-token position (0 front, 1 middle, 2 end); a step uses the Pb contexts sel int32 [Pb] names, the caller having put them into
