@@ -8,6 +8,10 @@ document (fp32 scores from exact fp16 products, P rounded to fp16 before the PV 
 accumulation, one fp16 rounding of the output); every term is stated with its source in ``_tolerance``.  ``emulate`` is that arithmetic on the
 CPU (and three deliberately wrong variants of it); the constructed inputs (selection, uniform) need no tolerance at all; the case lists at
 the end are shared by the CPU test and the GPU test: same seeds, same tensors.
+
+The second half is the same for the two backward entry points, clipmi_attention_backward and clipmi_attention_backward_full:
+``attention_backward`` (reference and per-element tolerance), ``emulate_backward`` (and seven wrong variants), the backward selection and
+uniform inputs and the case lists of tests/test_gpu_attention_backward_ops.py.
 """
 from __future__ import annotations
 
@@ -392,3 +396,278 @@ def poison_like(t, g):
     """A tensor of t's shape filled with NaN and +-inf fp16 patterns."""
     pat = np.array([0x7E00, 0x7C00, 0xFC00, 0x7C01, 0xFE00], dtype=np.uint16)
     return torch.from_numpy(pat[torch.randint(0, len(pat), tuple(t.shape), generator=g).numpy()].view(np.float16).copy())
+
+
+# ====================================================================================================================== the backward
+# clipmi_attention_backward (causal, L <= 80) and clipmi_attention_backward_full (no mask, L <= 224) of csrc/attention.hip: d_out [N L, 64 H]
+# -> dqkv [N L, 3 * 64 H] (dq | dk | dv).  The oracle of the backward half of tests/test_attention_ref_cpu.py, of
+# tests/test_gpu_attention_backward_ops.py and of the attention test of tests/test_gpu_text_backward.py.
+AB_MAX_L = {True: 80, False: 224}
+
+
+def _heads(t, N, L, H):
+    return t.reshape(N, L, H, 64).transpose(1, 2)          # [N, H, L, 64]
+
+
+def _rows(t, N, L, H):
+    return t.transpose(1, 2).reshape(N * L, 64 * H)
+
+
+def attention_backward(qkv, d_out, N, L, H, causal, fp32_terms=True):
+    """-> (want, tol), float64 [N L, 3 * 64 H], per element.  ``want`` is the restatement of tests/coopfit_ref.py (causal) or
+    tests/vptfit_ref.py (no mask) on the exact values of the fp16 inputs.  ``tol``: P and dS reach the matrix cores rounded to fp16 (u16
+    relative each, 2^-25 absolute -- half a subnormal step -- where they are subnormal), the products are accumulated in fp32 and the result
+    is rounded to fp16 once.  Per element of a product sum_t a_t b_t with a rounded:
+        u16 sum |a| |b|      the rounded operand (P in dV = P^T dO; dS in dQ = dS K / 8 and dK = dS^T Q / 8),
+        2^-25 sum |b|        the flushed tail of that operand,
+        u16 |want|           the output rounding;
+    dS itself is formed in fp32 from fp32 P and dP (errors of order u32).  The project's factor 2 for the fast exponential and the fp32 sums,
+    and 2^-24 (a subnormal step of the output).  The tail term runs over every (query, key) pair under either mask: a masked pair is an exact
+    zero on the device, so under the causal mask the term is up to twice what the kernel can use.
+
+    ``fp32_terms`` (False: the bound as tests/test_gpu_text_backward.py has always asserted it, sufficient where every softmax row is flat)
+    adds what fp32 leaves on P and dS before they are rounded, which is what carries the error of a peaked row: there
+    dP_t - rowsum = sum_j p_j (dP_t - dP_j) is a small difference of two numbers of the size of dP, and one fp32 rounding of the row sum is
+    an error u32 |dP| of it -- relative u32 / (1 - p_t), beyond u16 once 1 - p_t < 2^-13.  With n allowed keys of row q, written per row:
+      eps   relative error of an unnormalised probability: the exponent s / 8 - max carries the fp32 score (64 products in some order,
+            64 u32 sum_i |q_i k_i| / 8, Higham gamma_64), its own rounding and that of the product with log2(e) in the fast exponential
+            (2 u32 |s / 8 - max|), and the hardware exp2 (2^-22, as in ``_tolerance``); the maximum over the row's allowed keys;
+      eta   (n + 2) u32: the sum of n terms in any order, its reciprocal and the product -- common to the row;
+      T     sum_j p_j |dP_j| >= |rowsum|;      B_qk = sum_i |dO_qi| |V_ki|, so that 64 u32 B_qk bounds the error of dP_qk.
+    Probabilities p_k (1 + e_k) renormalise to p_k (1 + e_k - sum_j p_j e_j): |dp_k| <= 2 eps p_k, and because these changes sum to zero,
+    the row sum moves by sum_j dp_j (dP_j - rowsum), at most 2 eps sum_j |dS_j|.  The common factor eta does not cancel: P no longer sums to
+    one, dS_k moves by eta (|dS_k| + p_k |rowsum|).  The row sum is n fused multiply-adds and a tree in any order, (n + 1) u32 T, of inexact
+    dP; the error d_k of dP_k enters dS_k as p_k ((1 - p_k) d_k - sum_{j != k} p_j d_j): where p_k is one, it cancels.  Together
+        |d dS_qk| <= (2 eps + eta + 2 u32) |dS_qk| + p_qk (2 eps sum_j |dS_qj| + (2 n + 3) u32 T_q + 64 u32 ((1 - 2 p_qk) B_qk + sum_j p_qj B_qj)),
+        |d P_qk|  <= (2 eps + eta) p_qk,
+    carried through |K| / 8, |Q| / 8 and |dO| like the fp16 roundings and under the same factor 2."""
+    import coopfit_ref as cref
+    import vptfit_ref as vref
+    D = 64 * H
+    x, g = _f64(qkv).reshape(N * L, 3 * D), _f64(d_out).reshape(N * L, D)
+    want = cref.attention_backward(x, g, N, L, H) if causal else vref.attention_backward_full(x, g, N, L, H)
+    q, k, v = (_heads(t, N, L, H) for t in x.split(D, dim=-1))
+    d = _heads(g, N, L, H)
+    p = cref.attention_probs(q, k) if causal else vref.attention_probs_full(q, k)
+    dp = d @ v.transpose(-1, -2)
+    ds = p * (dp - (dp * p).sum(-1, keepdim=True))
+    ones = torch.ones_like(p)
+    bq = (ds.abs() @ k.abs()) / 8 * U16 + 2.0 ** -25 * (ones @ k.abs()) / 8
+    bk = (ds.abs().transpose(-1, -2) @ q.abs()) / 8 * U16 + 2.0 ** -25 * (ones @ q.abs()) / 8
+    bv = (p.transpose(-1, -2) @ d.abs()) * U16 + 2.0 ** -25 * (ones @ d.abs())
+    if fp32_terms:
+        ok = _allowed(L, L, causal)
+        n = ok.sum(dim=1, keepdim=True).to(torch.float64)
+        x8 = (q @ k.transpose(-1, -2) / 8).masked_fill(~ok, float("-inf"))
+        spread = (x8.amax(-1, keepdim=True) - x8.masked_fill(~ok, float("inf")).amin(-1, keepdim=True))
+        sacc = (q.abs() @ k.abs().transpose(-1, -2)).masked_fill(~ok, 0.0).amax(-1, keepdim=True)
+        eps = U32 * (64.0 * sacc / 8 + 2.0 * spread) + 2.0 ** -22
+        eta = (n + 2) * U32
+        B = d.abs() @ v.abs().transpose(-1, -2)
+        T = (p * dp.abs()).sum(-1, keepdim=True)
+        row = 2 * eps * ds.abs().sum(-1, keepdim=True) + (2 * n + 3) * U32 * T + 64 * U32 * (p * B).sum(-1, keepdim=True)
+        dds = (2 * eps + eta + 2 * U32) * ds.abs() + p * (row + 64 * U32 * (1 - 2 * p) * B)
+        bq = bq + (dds @ k.abs()) / 8
+        bk = bk + (dds.transpose(-1, -2) @ q.abs()) / 8
+        bv = bv + ((2 * eps + eta) * p).transpose(-1, -2) @ d.abs()
+    bound = torch.cat([_rows(t, N, L, H) for t in (bq, bk, bv)], dim=-1)
+    return want, 2 * (bound + U16 * want.abs()) + 2.0 ** -24
+
+
+WRONG_BACKWARD = ("drop_last", "admit_next", "next_seq", "no_rowsum", "dk_unscaled", "stale_stats", "swap_pair")
+
+
+def wrong_backward_applies(wrong, N, L, causal):
+    if wrong == "drop_last":
+        return L >= 2
+    if wrong == "admit_next":
+        return causal and L >= 2
+    if wrong == "next_seq":
+        return N >= 2
+    if wrong == "stale_stats":
+        return not causal and L >= 17          # only the kernel without a mask recomputes P and dS from saved statistics
+    if wrong == "swap_pair":
+        return L >= 17
+    return L >= 2                              # no_rowsum, dk_unscaled: with one key dS, dq and dk are zero either way
+
+
+def _swap16(t, L):
+    """Rows q <-> q ^ 16 (the two 16-row tiles of a 32-row pair); the partner of a row past L is a zero row."""
+    idx = torch.arange(L) ^ 16
+    out = torch.zeros_like(t)
+    ok = idx < L
+    out[ok] = t[idx[ok]]
+    return out
+
+
+def emulate_backward(qkv, d_out, N, L, H, causal, wrong=None):
+    """The kernels' arithmetic in torch on the CPU: float32 throughout, P = exp(s / 8 - max) * (1 / sum), dS = P (dP - rowsum(dP P)),
+    .half() on P and dS in front of their products, one .half() on dqkv -> fp16 [N L, 3 * 64 H].  ``wrong`` makes it wrong in one way, each a
+    mistake these kernels could make:
+      drop_last    the last key a row may see is dropped: key L-1 (no mask), key q of row q >= 1 (causal);
+      admit_next   the causal mask admits key q + 1;
+      next_seq     query row 0 of the next sequence of the batch (cyclically) is one more query row in dK and dV (a padding row not zeroed);
+      no_rowsum    dS = P dP, without the row-sum term;
+      dk_unscaled  the 1 / 8 is missing from dK;
+      stale_stats  dK and dV recompute P and dS of query q from the maximum, 1 / sum and row sum of query q + 16 (where that exists);
+      swap_pair    the token-row operand of every product is gathered with the two tiles of a 32-row pair swapped (row q ^ 16)."""
+    D = 64 * H
+    x = qkv.detach().cpu().reshape(N, L, 3, H, 64).float()
+    g = d_out.detach().cpu().reshape(N, L, H, 64).float()
+    allowed = _allowed(L, L, causal)
+    if wrong == "drop_last":
+        if causal:
+            i = torch.arange(1, L)
+            allowed[i, i] = False
+        else:
+            allowed[:, L - 1] = False
+    elif wrong == "admit_next":
+        i = torch.arange(0, L - 1)
+        allowed[i, i + 1] = True
+    out = torch.empty(N, L, 3, H, 64, dtype=torch.float16)
+    r16 = lambda t: t.half().float()
+    for n in range(N):
+        for h in range(H):
+            q, k, v, do = x[n, :, 0, h], x[n, :, 1, h], x[n, :, 2, h], g[n, :, h]
+            ok = allowed
+            if wrong == "next_seq":
+                q = torch.cat([q, x[(n + 1) % N, :1, 0, h]])
+                do = torch.cat([do, g[(n + 1) % N, :1, h]])
+                ok = torch.cat([allowed, torch.ones(1, L, dtype=torch.bool)])
+            s = ((q @ k.t()) * 0.125).masked_fill(~ok, float("-inf"))
+            m = s.amax(dim=1, keepdim=True)
+            e = torch.exp(s - m)
+            inv = 1.0 / e.sum(dim=1, keepdim=True)
+            p = e * inv
+            dp = do @ v.t()
+            rs = (p * dp).sum(dim=1, keepdim=True)
+            ds = p * dp if wrong == "no_rowsum" else p * (dp - rs)
+            p2, ds2 = p, ds
+            if wrong == "stale_stats":
+                j = torch.arange(L) + 16
+                j = torch.where(j < L, j, torch.arange(L))
+                p2 = torch.exp(s - m[j]) * inv[j]
+                ds2 = p2 * (dp - rs[j])
+            kb, qb, dob = k, q, do
+            if wrong == "swap_pair":
+                kb, qb, dob = _swap16(k, L), _swap16(q, L), _swap16(do, L)
+            dq = (r16(ds) @ kb) * 0.125
+            dk = r16(ds2).t() @ qb
+            if wrong != "dk_unscaled":
+                dk = dk * 0.125
+            dv = r16(p2).t() @ dob
+            out[n, :, 0, h], out[n, :, 1, h], out[n, :, 2, h] = dq[:L].half(), dk.half(), dv.half()
+    return out.reshape(N * L, 3 * D)
+
+
+# ---- random and peaked inputs
+# d_out: N(0, 0.5^2) as in the trainers' operator tests; that scaled by 2^-10 (dS moves into fp16's subnormals and the 2^-25 terms carry the
+# bound); N(0, 2^-6 ^2) scaled by 2^10 (the larger base would take dS = P (dP - rowsum) past 65504 at qkv scale 3: dP is a sum of 64 products)
+DOUT_SCALES = {"1": 0.5, "2^-10": 0.5 * 2.0 ** -10, "2^10": 2.0 ** -6 * 2.0 ** 10}
+BCase = namedtuple("BCase", "N L H causal distinct scale dout late")
+
+
+def backward_batch(case):
+    """N sequences built from ``distinct`` different ones in a shuffled order, qkv ~ N(0, scale^2), d_out ~ N(0, DOUT_SCALES[dout]^2);
+    ``late``: a common offset on every query and on the keys of the last 16-row tile, so that the rows that see them have their maximum there.
+    -> (qkv [N L, 3 D], d_out [N L, D], order, seq_qkv [distinct L, 3 D], seq_d_out [distinct L, D]), fp16."""
+    N, L, H, causal, S, scale, dout, late = case
+    D = 64 * H
+    g = _gen(N, L, H, int(causal), S, int(scale * 10), sorted(DOUT_SCALES).index(dout), int(late), 4242)
+    seqs = torch.randn(S, L, 3 * D, generator=g) * scale
+    if late:
+        seqs[:, :, :D] += 0.75
+        seqs[:, (L - 1) // 16 * 16:, D:2 * D] += 1.5          # 64 * 0.75 * 1.5 / 8 = 9 on the score, four of its standard deviations
+    seqs = seqs.half()
+    do = (torch.randn(S, L, D, generator=g) * DOUT_SCALES[dout]).half()
+    order = torch.cat([torch.arange(S), torch.randint(0, S, (N - S,), generator=g)])
+    order = order[torch.randperm(N, generator=g)]
+    return seqs[order].reshape(N * L, 3 * D), do[order].reshape(N * L, D), order.tolist(), seqs.reshape(S * L, 3 * D), do.reshape(S * L, D)
+
+
+# both sides of every seam: 16-row tiles, the 32-row k-steps of the causal kernel's phase B and its 96 zeroed rows behind L = 80; without a
+# mask NT odd against even (the padding tile of NTP live at 33..48, 65..80, 97..112, 193..208) and NT no multiple of the four waves
+BACKWARD_LENGTHS = {True: (1, 2, 15, 16, 17, 31, 32, 33, 47, 48, 49, 63, 64, 65, 77, 79, 80),
+                    False: (1, 15, 16, 17, 31, 32, 33, 48, 49, 64, 65, 96, 97, 112, 113, 197, 205, 207, 208, 209, 223, 224)}
+BACKWARD_SEAMS = {True: (17, 33, 64, 77, 80), False: (17, 49, 113, 197, 224)}          # the H and N sweep, the d_out scales
+BACKWARD_ISOLATION = {True: (17, 33, 77, 80), False: (17, 33, 197, 209, 224)}
+BACKWARD_SHAPES = ((1, 1), (1, 8), (3, 1), (3, 12))                                     # (N, H) of the sweep; (3, 2) is the shape of every length
+BACKWARD_WIDE = {True: (37, 8, 77), False: (37, 8, 197)}                                 # N H = 296 items: wider than the device once
+
+
+def _backward_cases():
+    flat, peaked = [], []
+    for causal in (True, False):
+        for L in BACKWARD_LENGTHS[causal]:
+            flat.append(BCase(3, L, 2, causal, 2, 0.7, "1", False))
+            peaked += [BCase(3, L, 2, causal, 2, 1.5, "1", False), BCase(3, L, 2, causal, 2, 3.0, "1", False), BCase(3, L, 2, causal, 2, 1.5, "1", True)]
+        for L in BACKWARD_SEAMS[causal]:
+            flat += [BCase(N, L, H, causal, min(N, 2), 0.7, "1", False) for N, H in BACKWARD_SHAPES]
+            peaked += [BCase(1, L, 2, causal, 1, s, d, s == 1.5) for s in (1.5, 3.0) for d in ("2^10", "2^-10")]
+        N, H, L = BACKWARD_WIDE[causal]
+        flat.append(BCase(N, L, H, causal, 3, 0.7, "1", False))
+    return flat, peaked
+
+
+BACKWARD_RANDOM, BACKWARD_PEAKED = _backward_cases()
+
+
+# ---- constructed: selection
+def selection_backward_batch(N, L, H, kind):
+    """Q and K of ``selection_batch``: the target pi(q) leads every other key of row q by 64 natural units, so P16 is exactly one-hot.
+    V holds integers of -3..3 and d_out integers of -8..8, so every dP is an exact integer in fp32: at the target rowsum(dP o P) == dP and dS
+    is exactly zero; everywhere else p < e^-64 and |dP - rowsum| < 2^25, so dS < 2^-67 flushes to zero in fp16.  Hence dq == 0 and dk == 0 in
+    every element, and dv[j] = sum over the queries with pi(q) = j of d_out[q]: at most 224 integers of magnitude <= 8, exact in fp32 and,
+    below 2048, in fp16.  kind "perm": pi is a permutation, dv is a row permutation of d_out bit for bit, and d_out instead holds fp16 values
+    with random sign, exponent 1..30 and mantissa (dP is then no integer, but the target's dS is the difference of a value and itself, and
+    the others' |dP - rowsum| < 2^25 still).  -> (qkv fp16 [N L, 3 D], d_out fp16 [N L, D], dv fp16 [N L, D], pi [N, H, L])."""
+    qkv, _, pis = selection_batch(N, L, H, kind)
+    g = _gen(N, L, H, sorted(sum(SELECT_KINDS.values(), ())).index(kind), 78)
+    D = 64 * H
+    qkv = qkv.reshape(N, L, 3, H, 64).clone()
+    qkv[:, :, 2] = torch.randint(-3, 4, (N, L, H, 64), generator=g).half()
+    if kind == "perm":
+        b = (torch.randint(0, 2, (N, L, H, 64), generator=g) << 15) | (torch.randint(1, 31, (N, L, H, 64), generator=g) << 10) | \
+            torch.randint(0, 1024, (N, L, H, 64), generator=g)
+        do = torch.from_numpy(b.numpy().astype(np.uint16).view(np.float16).copy())
+    else:
+        do = torch.randint(-8, 9, (N, L, H, 64), generator=g).half()
+    dv = torch.zeros(N, L, H, 64, dtype=torch.float64)
+    for n in range(N):
+        for h in range(H):
+            dv[n, :, h].index_add_(0, pis[n, h], do[n, :, h].double())
+    assert dv.abs().max() <= (65504 if kind == "perm" else 2048)
+    return qkv.reshape(N * L, 3 * D), do.reshape(N * L, D), dv.half().reshape(N * L, D), pis
+
+
+# ---- constructed: uniform
+def uniform_backward_batch(N, L, H, causal):
+    """q == 0: every allowed key of row q has the probability fp32(1 / n_q), n_q the number of its allowed keys (q + 1 under the causal mask);
+    K and V are random, d_out holds integers of -8..8.  dk = dS^T q is exactly zero; dv[j] = sum over the queries that may see key j of
+    fp16(fp32(1 / n_q)) d_out[q], every (query, key) pair counted once; dq is an ordinary result (``attention_backward``).
+    -> (qkv fp16, d_out fp16, dv float64 [N L, D], dv_tol float64).  dv_tol per element:
+        u16 |dv|                    the one rounding of the output to fp16,
+        2^-20 sum_q P16 |d_out|     the fp32 sum: at most 224 terms summed in k-steps of 32 and a chain of 7, < 16 roundings of 2^-24 each,
+        2^-25                       half a subnormal step of the output."""
+    g = _gen(N, L, H, int(causal), 98)
+    D = 64 * H
+    qkv = torch.zeros(N, L, 3, D)
+    qkv[:, :, 1] = torch.randn(N, L, D, generator=g) * 1.5
+    qkv[:, :, 2] = torch.randn(N, L, D, generator=g)
+    do = torch.randint(-8, 9, (N, L, D), generator=g).double()
+    allowed = _allowed(L, L, causal).double()
+    n_q = allowed.sum(dim=1)
+    p16 = (1.0 / n_q.float()).half().double()[:, None] * allowed                      # [q, key]
+    dv = torch.einsum("qk,nqd->nkd", p16, do)
+    tol = U16 * dv.abs() + 2.0 ** -20 * torch.einsum("qk,nqd->nkd", p16, do.abs()) + 2.0 ** -25
+    return qkv.half().reshape(N * L, 3 * D), do.half().reshape(N * L, D), dv.reshape(N * L, D), tol.reshape(N * L, D)
+
+
+BACKWARD_CONSTRUCTED_SHAPE = (3, 2)          # (N, H) of the selection and uniform batches
+
+
+def poison_one(d_out, N, L, H, n, r, h, value):
+    """d_out with ``value`` in one element of row r, head h of item n."""
+    out = d_out.clone().reshape(N, L, H, 64)
+    out[n, r, h, 5] = value
+    return out.reshape(N * L, 64 * H)

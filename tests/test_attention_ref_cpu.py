@@ -288,3 +288,185 @@ def test_class_row_output_needs_16_byte_alignment():
     """include/clipmi.h: clipmi_attention_cls stores 16 bytes per lane (both pointers 16-byte aligned); clipmi_attention's rows need 8."""
     p = ctypes.c_void_p(4096)
     assert _lib.lib.clipmi_attention_cls(p, ctypes.c_void_p(8192 + 8), 1, 8, 1, None) == _lib.ERR_ARG
+
+
+# ======================================================================================================================= the backward
+# clipmi_attention_backward and clipmi_attention_backward_full: the reference against autograd, the emulation inside the tolerance at every
+# random and peaked case the GPU test runs, every mutation of WRONG_BACKWARD outside it (or breaking an exact claim), and the exact claims of
+# the constructed inputs on the emulation, before anything is asked of the device.
+BACKWARD_EMULATION_WORST = {}
+
+
+@functools.lru_cache(maxsize=None)
+def _backward(case):
+    _, _, _, sq, sd = ref.backward_batch(case)
+    return (sq, sd) + ref.attention_backward(sq, sd, case.distinct, case.L, case.H, case.causal)
+
+
+def _bkind(case):
+    return "flat" if case.scale < 1.0 else "peaked"
+
+
+@pytest.mark.parametrize("causal", [False, True])
+@pytest.mark.parametrize("N,L,H", [(1, 1, 1), (2, 17, 2), (3, 33, 1), (1, 80, 2)])
+def test_backward_reference_is_the_gradient_of_the_forward_reference(N, L, H, causal):
+    qkv = ref.random_batch(N, L, H, causal, N)[0].double().requires_grad_()
+    g = torch.randn(N, L, 64 * H, generator=torch.Generator().manual_seed(L), dtype=torch.float64)
+    q, k, v = (t.reshape(N, L, H, 64).transpose(1, 2) for t in qkv.reshape(N, L, 3, 64 * H).unbind(2))
+    out = torch.nn.functional.scaled_dot_product_attention(q, k, v, is_causal=causal).transpose(1, 2).reshape(N, L, 64 * H)
+    out.backward(g)
+    want, tol = ref.attention_backward(qkv.detach(), g, N, L, H, causal)
+    assert (want - qkv.grad).abs().max() < 1e-12
+    assert (tol > 0).all() and torch.isfinite(tol).all()
+    flat = ref.attention_backward(qkv.detach(), g, N, L, H, causal, fp32_terms=False)[1]
+    assert (flat <= tol).all()
+
+
+@pytest.mark.parametrize("case", ref.BACKWARD_RANDOM + ref.BACKWARD_PEAKED, ids=str)
+def test_backward_emulation_inside_tolerance(case):
+    """The condition that keeps the tolerance honest: worst |err| / tol of the unmutated emulation <= 1, at every case the device is held to."""
+    sq, sd, want, tol = _backward(case)
+    got = ref.emulate_backward(sq, sd, case.distinct, case.L, case.H, case.causal)
+    assert torch.isfinite(got.float()).all()          # nothing overflows fp16: dS, dq at d_out 2^10
+    r = ref.worst_ratio(got, want, tol)
+    key = ("causal" if case.causal else "full") + " " + _bkind(case)
+    BACKWARD_EMULATION_WORST[key] = max(BACKWARD_EMULATION_WORST.get(key, 0.0), r)
+    print(f"attention-backward-parity: {tuple(case)}: emulation worst |err| / tol = {r:.3f}")
+    assert r <= 1.0
+
+
+def test_backward_subnormal_and_large_cases_are_what_they_say():
+    """d_out 2^-10: most of dS is subnormal in fp16 (or flushed); d_out 2^10: dS reaches past 2^5; late: the rows that see the last key tile peak there."""
+    late = {}
+    for case in ref.BACKWARD_PEAKED:
+        sq, sd, _, _ = _backward(case)
+        S, L, H, D = case.distinct, case.L, case.H, 64 * case.H
+        x, g = sq.double().reshape(S, L, 3, H, 64), sd.double().reshape(S, L, H, 64)
+        s = torch.einsum("nqhd,nkhd->nhqk", x[:, :, 0], x[:, :, 1]) / 8
+        s = s.masked_fill(~ref._allowed(L, L, case.causal), float("-inf"))
+        p = torch.softmax(s, dim=-1)
+        dp = torch.einsum("nqhd,nkhd->nhqk", g, x[:, :, 2])
+        ds = p * (dp - (dp * p).sum(-1, keepdim=True))
+        if case.dout == "2^-10" and L >= 17:
+            assert (ds.abs() < 2.0 ** -14).double().mean() > 0.5
+        if case.dout == "2^10" and L >= 17:
+            assert ds.abs().max() > 2.0 ** 5
+        if case.late and L >= 17:
+            rows = torch.arange(L) >= (L - 1) // 16 * 16 if case.causal else torch.ones(L, dtype=torch.bool)
+            hit = (s.argmax(-1)[..., rows] >= (L - 1) // 16 * 16).double()
+            late[case.causal] = late.get(case.causal, []) + [hit.flatten()]
+    for causal in (True, False):
+        assert torch.cat(late[causal]).mean() > 0.9
+
+
+@pytest.mark.parametrize("wrong", ref.WRONG_BACKWARD)
+@pytest.mark.parametrize("case", [c for c in ref.BACKWARD_RANDOM + ref.BACKWARD_PEAKED if c.H <= 2], ids=str)
+def test_wrong_backward_emulations_leave_the_tolerance(case, wrong):
+    if not ref.wrong_backward_applies(wrong, case.distinct, case.L, case.causal):
+        return
+    sq, sd, want, tol = _backward(case)
+    r = ref.worst_ratio(ref.emulate_backward(sq, sd, case.distinct, case.L, case.H, case.causal, wrong=wrong), want, tol)
+    print(f"{tuple(case)} {wrong}: worst |err| / tol = {r:.1f}")
+    assert r > 1.0
+
+
+def test_every_wrong_backward_emulation_applies_somewhere():
+    cases = [c for c in ref.BACKWARD_RANDOM + ref.BACKWARD_PEAKED if c.H <= 2]
+    for wrong in ref.WRONG_BACKWARD:
+        for causal in ((True,) if wrong == "admit_next" else (False,) if wrong == "stale_stats" else (True, False)):
+            assert sum(ref.wrong_backward_applies(wrong, c.distinct, c.L, c.causal) for c in cases if c.causal == causal) >= 10, (wrong, causal)
+
+
+def _zero(t):
+    return bool((t.float() == 0).all())          # values: -0 passes
+
+
+# which exact claim of the selection input every mutation breaks (dk_unscaled: none -- dk is zero with or without the 1 / 8; the tolerance
+# catches it at every random case with two keys or more)
+SELECTION_CATCHES = {"drop_last": ("last", "diag"), "admit_next": ("decoy",), "next_seq": ("perm", "first", "below"),
+                     "no_rowsum": ("perm", "last", "diag", "below"), "stale_stats": ("perm", "last"), "swap_pair": ("perm", "diag", "below")}
+
+
+@pytest.mark.parametrize("causal", [False, True], ids=["full", "causal"])
+def test_backward_selection_construction_and_sensitivity(causal):
+    """On the fp32 emulation, at every length of the GPU test: dq == 0 and dk == 0 in every element, dv the exact answer bit for bit; every
+    mutation listed in SELECTION_CATCHES breaks one of the three at the kinds listed, wherever it applies."""
+    N, H = ref.BACKWARD_CONSTRUCTED_SHAPE
+    D = 64 * H
+    caught = set()
+    for L in ref.BACKWARD_LENGTHS[causal]:
+        for kind in ref.SELECT_KINDS[causal]:
+            qkv, do, dv, pi = ref.selection_backward_batch(N, L, H, kind)
+            x = qkv.double().reshape(N, L, 3, H, 64)
+            dp = torch.einsum("nqhd,nkhd->nhqk", do.double().reshape(N, L, H, 64), x[:, :, 2])
+            assert dp.abs().max() < 2.0 ** 25
+            if kind != "perm":
+                assert (dp == dp.round()).all() and (x[:, :, 2] == x[:, :, 2].round()).all()
+            else:
+                srt = pi.sort(dim=-1).values
+                assert (srt == torch.arange(L)).all()
+                e = do.view(torch.int16).to(torch.int32) >> 10 & 31
+                assert e.min() == 1 and (e.max() == 30 or L < 8)                       # fp16's whole exponent range
+            got = ref.emulate_backward(qkv, do, N, L, H, causal)
+            assert _zero(got[:, :D]) and _zero(got[:, D:2 * D]), (kind, L)
+            assert torch.equal(got[:, 2 * D:].contiguous().view(torch.int16), dv.view(torch.int16)), (kind, L)
+            for wrong, kinds in SELECTION_CATCHES.items():
+                if kind in kinds and ref.wrong_backward_applies(wrong, N, L, causal):
+                    off = ref.emulate_backward(qkv, do, N, L, H, causal, wrong=wrong)
+                    broke = not (_zero(off[:, :D]) and _zero(off[:, D:2 * D]) and torch.equal(off[:, 2 * D:].float(), dv.float()))
+                    assert broke, (wrong, kind, L)
+                    caught.add(wrong)
+    want = set(SELECTION_CATCHES) - ({"stale_stats"} if causal else {"admit_next"})
+    assert caught == want
+
+
+@pytest.mark.parametrize("causal", [False, True], ids=["full", "causal"])
+def test_backward_uniform_construction_and_sensitivity(causal):
+    """The emulation: dk == 0, dv within the uniform allowance, dq within the general tolerance, at every length.  At the longest length,
+    dropping or double-counting any single (query, key) pair moves some dv element of that key beyond the allowance."""
+    N, H = ref.BACKWARD_CONSTRUCTED_SHAPE
+    D = 64 * H
+    for L in ref.BACKWARD_LENGTHS[causal]:
+        qkv, do, dv, dv_tol = ref.uniform_backward_batch(N, L, H, causal)
+        got = ref.emulate_backward(qkv, do, N, L, H, causal)
+        want, tol = ref.attention_backward(qkv, do, N, L, H, causal)
+        assert _zero(got[:, D:2 * D])
+        assert ((got[:, 2 * D:].double() - dv).abs() <= dv_tol).all(), L
+        weight = (dv_tol - ref.U16 * dv.abs() - 2.0 ** -25) * 2.0 ** 20                                 # sum_q P16 |d_out|
+        assert ((dv - want[:, 2 * D:]).abs() <= ref.U16 * weight + 1e-12).all()                        # the two references: fp16(1 / n) against 1 / n
+        assert ((got[:, :D].double() - want[:, :D]).abs() <= tol[:, :D]).all(), L
+    # the longest length is the last of the loop: one pair (q, key) more or less moves dv[key, d] by p16[q] |d_out[q, d]|
+    ok = ref._allowed(L, L, causal)
+    p16 = (1.0 / ok.sum(dim=1).float()).half().double()
+    step = p16[:, None] * do.double().reshape(N, L, D)[0].abs()                                       # [q, d]
+    moved = (step[:, None, :] / dv_tol.reshape(N, L, D)[0][None, :, :]).amax(dim=-1)                  # [q, key]: the best column
+    assert (moved[ok] > 2.5).all()                                                                    # beyond the allowance after its own rounding
+
+
+def test_backward_case_lists_cover_the_issue():
+    T, F = ref.BACKWARD_LENGTHS[True], ref.BACKWARD_LENGTHS[False]
+    assert T == (1, 2, 15, 16, 17, 31, 32, 33, 47, 48, 49, 63, 64, 65, 77, 79, 80)
+    assert F == (1, 15, 16, 17, 31, 32, 33, 48, 49, 64, 65, 96, 97, 112, 113, 197, 205, 207, 208, 209, 223, 224)
+    for causal in (True, False):
+        for cases in (ref.BACKWARD_RANDOM, ref.BACKWARD_PEAKED):
+            assert {c.L for c in cases if c.causal == causal} == set(ref.BACKWARD_LENGTHS[causal])
+        flat = [c for c in ref.BACKWARD_RANDOM if c.causal == causal]
+        assert {c.H for c in flat} == {1, 2, 8, 12} and {c.N for c in flat} == {1, 3, 37}
+        assert max(c.N * c.H for c in flat) > 256
+        assert set(ref.BACKWARD_SEAMS[causal]) <= set(ref.BACKWARD_LENGTHS[causal]) and max(ref.BACKWARD_SEAMS[causal]) == ref.AB_MAX_L[causal]
+        assert set(ref.BACKWARD_ISOLATION[causal]) <= set(ref.BACKWARD_LENGTHS[causal])
+        peaked = [c for c in ref.BACKWARD_PEAKED if c.causal == causal]
+        assert {c.scale for c in peaked} == {1.5, 3.0} and {c.dout for c in peaked} == set(ref.DOUT_SCALES) and any(c.late for c in peaked)
+    assert all(c.distinct < c.N for c in ref.BACKWARD_RANDOM if c.N >= 3)             # a copy of a sequence in every batch of three or more
+
+
+def test_backward_entries_validate_arguments_without_a_gpu():
+    p = ctypes.c_void_p(4096)
+    for f, most in ((_lib.lib.clipmi_attention_backward, 80), (_lib.lib.clipmi_attention_backward_full, 224)):
+        assert f(p, p, p, 1, most + 1, 1, None) == _lib.ERR_SHAPE
+        for N, L, H in [(1, 0, 1), (-1, 8, 1), (1, 8, 0), (1 << 30, 8, 2)]:
+            assert f(p, p, p, N, L, H, None) == _lib.ERR_SHAPE, (N, L, H)
+        for a in ((None, p, p), (p, None, p), (p, p, None), (ctypes.c_void_p(4096 + 2), p, p), (p, ctypes.c_void_p(4096 + 8), p),
+                  (p, p, ctypes.c_void_p(4096 + 4))):
+            assert f(*a, 1, most, 1, None) == _lib.ERR_ARG
+        assert f(None, None, None, 0, 8, 1, None) == _lib.OK
