@@ -26,22 +26,8 @@ from typing import Optional, Sequence
 import numpy as np
 import torch
 
-from . import ops
-from .tempfit import cosine_warmup_schedule, steps_per_epoch
-
-
-def _host_int_array(x, name: str) -> np.ndarray:
-    a = x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
-    if a.dtype.kind not in "iu":
-        raise TypeError(f"fit_adapter: {name} must be integers, got {a.dtype}")
-    return a
-
-
-def _check_optimiser(who: str, momentum: float, dampening: float, weight_decay: float, nesterov: bool) -> None:
-    if not (0.0 <= momentum < 1.0 and 0.0 <= dampening < 1.0 and weight_decay >= 0.0):
-        raise ValueError(f"{who}: momentum={momentum}, dampening={dampening} (both in [0, 1)), weight_decay={weight_decay} (>= 0)")
-    if nesterov and (momentum <= 0.0 or dampening != 0.0):
-        raise ValueError(f"{who}: Nesterov momentum requires a momentum and zero dampening")
+from . import fitloop, ops
+from .fitloop import _need_gpu, steps_per_epoch
 
 
 def _check_shapes(who: str, features, text_features, w1, w2):
@@ -54,31 +40,6 @@ def _check_shapes(who: str, features, text_features, w1, w2):
             or tuple(w2.shape) != (E, w1.shape[0])):
         raise ValueError(f"{who}: adapter shapes do not chain (E = {E}, w1 {tuple(getattr(w1, 'shape', ()))}, w2 {tuple(getattr(w2, 'shape', ()))})")
     return N, E, w1.shape[0], text_features.shape[0]
-
-
-def _labels(who: str, labels, N: int, C: int) -> np.ndarray:
-    lab = _host_int_array(labels, "labels")
-    if lab.shape != (N,):
-        raise ValueError(f"{who}: {N} rows need {N} labels, got {lab.shape}")
-    if lab.min() < 0 or lab.max() >= C:
-        raise ValueError(f"{who}: labels span [{int(lab.min())}, {int(lab.max())}], outside the {C} classes [0, {C})")
-    return lab
-
-
-def _need_gpu(t: torch.Tensor, name: str) -> None:
-    if not t.is_cuda:
-        raise RuntimeError(f"clipmi: `{name}` must be a tensor on the GPU (got {t.device}); the HIP path has no CPU fallback")
-
-
-def _labels_on(labels, lab: np.ndarray, dev) -> torch.Tensor:
-    if isinstance(labels, torch.Tensor) and labels.is_cuda and labels.dtype == torch.int64:
-        return labels
-    return torch.from_numpy(lab.astype(np.int64)).to(dev)
-
-
-def _master(w: torch.Tensor, dev) -> torch.Tensor:
-    """A fresh contiguous fp32 copy on the device: the master weights the kernels update in place."""
-    return w.detach().to(device=dev, dtype=torch.float32, copy=True).contiguous()
 
 
 def fit_adapter(features: torch.Tensor, labels, text_features: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor, ratio: float = 0.2,
@@ -99,35 +60,25 @@ def fit_adapter(features: torch.Tensor, labels, text_features: torch.Tensor, w1:
     copied to the host for that, which waits for whatever produced it; from the first launch on nothing synchronises until the one wait
     at the end.  Returns the fitted fp32 ``(w1, w2)`` on the device, or ``(w1, w2, per-step batch losses as a float32 numpy array)`` with
     ``return_history``.  The defaults are unverified restatements of the reference's config and Dassl's (module docstring)."""
-    N, E, H, C = _check_shapes("fit_adapter", features, text_features, w1, w2)
-    epochs, batch_size = int(epochs), int(batch_size)
-    if epochs < 0 or batch_size < 1:
-        raise ValueError(f"fit_adapter: epochs={epochs} (>= 0), batch_size={batch_size} (>= 1)")
-    _check_optimiser("fit_adapter", momentum, dampening, weight_decay, nesterov)
+    who = "fit_adapter"
+    N, E, H, C = _check_shapes(who, features, text_features, w1, w2)
+    epochs, batch_size = fitloop.check_run(who, epochs, batch_size)
+    fitloop.check_sgd(who, momentum, dampening, weight_decay, nesterov)
     if not (math.isfinite(ratio) and math.isfinite(logit_scale)):
-        raise ValueError(f"fit_adapter: ratio={ratio}, logit_scale={logit_scale} (both finite)")
-    lab = _labels("fit_adapter", labels, N, C)
-    if order is not None:
-        order = _host_int_array(order, "order")
-        if order.shape != (epochs, N):
-            raise ValueError(f"fit_adapter: order {order.shape} must be [epochs, N] = [{epochs}, {N}]")
-        if order.size and (order.min() < 0 or order.max() >= N):
-            raise ValueError(f"fit_adapter: order holds sample indices outside [0, {N})")
-    rates = cosine_warmup_schedule(lr, epochs) if lr_per_epoch is None else [float(r) for r in lr_per_epoch]
-    if len(rates) != epochs:
-        raise ValueError(f"fit_adapter: {len(rates)} learning rates for {epochs} epochs")
+        raise ValueError(f"{who}: ratio={ratio}, logit_scale={logit_scale} (both finite)")
+    lab = fitloop._labels(who, labels, N, C)
+    order = fitloop.check_order(who, order, epochs, N)
     per_epoch = steps_per_epoch(N, batch_size, drop_last)
-    _need_gpu(features, "features")
     dev = features.device
-    w1, w2 = _master(w1, dev), _master(w2, dev)
+    _, lr_steps = fitloop.schedule(who, lr, epochs, lr_per_epoch, per_epoch, dev)
+    _need_gpu(features, "features")
+    w1, w2 = fitloop.master(w1, dev), fitloop.master(w2, dev)
     if epochs * per_epoch == 0:
         return (w1, w2, np.zeros(0, np.float32)) if return_history else (w1, w2)
     m1, m2 = (torch.zeros_like(w1), torch.zeros_like(w2)) if momentum != 0.0 else (None, None)
-    lr_steps = torch.from_numpy(np.repeat(np.asarray(rates, np.float64), per_epoch).astype(np.float32)).to(dev)
-    order_d = None if order is None else torch.from_numpy(np.ascontiguousarray(order, dtype=np.int32)).to(dev)
-    losses = ops.adapter_fit(features, _labels_on(labels, lab, dev), text_features, w1, w2, m1, m2, lr_steps, ratio,
-                             float(np.float32(math.exp(logit_scale))), batch_size, epochs, momentum, dampening, weight_decay, nesterov, order_d,
-                             drop_last, first_step=True, want_losses=return_history)
+    losses = ops.adapter_fit(features, fitloop.labels_on(labels, lab, dev), text_features, w1, w2, m1, m2, lr_steps, ratio,
+                             float(np.float32(math.exp(logit_scale))), batch_size, epochs, momentum, dampening, weight_decay, nesterov,
+                             fitloop.order_on(order, np.int32, dev), drop_last, first_step=True, want_losses=return_history)
     torch.cuda.current_stream().synchronize()   # the run's one synchronisation
     return (w1, w2, losses.cpu().numpy()) if return_history else (w1, w2)
 
@@ -139,13 +90,13 @@ class AdapterFitState:
 
     def __init__(self, text_features: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor, ratio: float = 0.2, logit_scale: float = 4.6052,
                  momentum: float = 0.9, dampening: float = 0.0, weight_decay: float = 5e-4, nesterov: bool = False):
-        _check_optimiser("AdapterFitState", momentum, dampening, weight_decay, nesterov)
+        fitloop.check_sgd("AdapterFitState", momentum, dampening, weight_decay, nesterov)
         if not isinstance(text_features, torch.Tensor) or text_features.dim() != 2 or text_features.shape[0] < 2:
             raise ValueError("AdapterFitState: text features must be a [C >= 2, E] tensor")
         _need_gpu(text_features, "text_features")
         dev = text_features.device
         self.text_features = text_features
-        self.w1, self.w2 = _master(w1, dev), _master(w2, dev)
+        self.w1, self.w2 = fitloop.master(w1, dev), fitloop.master(w2, dev)
         _check_shapes("AdapterFitState", text_features[:1], text_features, self.w1, self.w2)
         self.m1, self.m2 = (torch.zeros_like(self.w1), torch.zeros_like(self.w2)) if momentum != 0.0 else (None, None)
         self.ratio, self.scale = float(ratio), float(np.float32(math.exp(logit_scale)))
@@ -160,12 +111,9 @@ class AdapterFitState:
         loss, fp32 [1] on the device, when ``want_loss``."""
         N, _, _, C = _check_shapes("AdapterFitState.step", features, self.text_features, self.w1, self.w2)
         _need_gpu(features, "features")
-        if isinstance(labels, torch.Tensor) and labels.is_cuda and labels.dtype == torch.int64:
-            labels_d = labels
-        else:
-            labels_d = torch.from_numpy(_labels("AdapterFitState.step", labels, N, C).astype(np.int64)).to(features.device)
-        lr_d = lr if isinstance(lr, torch.Tensor) else torch.tensor([float(lr)], dtype=torch.float32).to(features.device)
-        loss = ops.adapter_train_step(features, labels_d, self.text_features, self.w1, self.w2, self.m1, self.m2, lr_d, self.ratio, self.scale,
+        labels_d = fitloop.step_labels("AdapterFitState.step", labels, N, C, features.device)
+        loss = ops.adapter_train_step(features, labels_d, self.text_features, self.w1, self.w2, self.m1, self.m2,
+                                      fitloop.lr_operand(lr, features.device), self.ratio, self.scale,
                                       self.steps == 0, self.momentum, self.dampening, self.weight_decay, self.nesterov, want_loss=want_loss)
         self.steps += 1
         return loss

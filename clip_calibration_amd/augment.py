@@ -24,10 +24,9 @@ from typing import Callable, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, fitloop
 from ._lib import check, lib
 from .preprocess import CLIP_MEAN, CLIP_STD, Preprocess, _DTYPES, _FILTERS
-from .tempfit import cosine_warmup_schedule
 
 Views = Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray, np.ndarray, np.ndarray]
 
@@ -164,41 +163,26 @@ def fit_with_transform(state, image_features: Callable[[torch.Tensor], torch.Ten
     epochs = int(epochs)
     if epochs < 0:
         raise ValueError(f"epochs={epochs} (>= 0)")
-    rates = cosine_warmup_schedule(lr, epochs) if lr_per_epoch is None else [float(r) for r in lr_per_epoch]
-    if len(rates) != epochs:
-        raise ValueError(f"{len(rates)} learning rates for {epochs} epochs")
     try:
         per_epoch = len(loader)
     except TypeError as e:
         raise TypeError("with a transform the loader is iterated once per epoch and must have a length (a DataLoader or a list)") from e
-    if epochs * per_epoch == 0:
-        return np.zeros(0, np.float32) if return_history else None
-    dev = torch.device("cuda", torch.cuda.current_device())
-    lr_steps = torch.from_numpy(np.repeat(np.asarray(rates, np.float64), per_epoch).astype(np.float32)).to(dev)
-    losses = []
+    dev = torch.device("cuda", torch.cuda.current_device()) if epochs * per_epoch else None
+    _, lr_steps = fitloop.schedule("fit_with_transform", lr, epochs, lr_per_epoch, per_epoch, dev)
+
+    def step(e: int, k: int, batch, lr_d: torch.Tensor, want_loss: bool):
+        images, labels = batch
+        labels = torch.as_tensor(labels)
+        if not labels.is_cuda:
+            if labels.dtype.is_floating_point or (labels.numel() and (labels.min() < 0 or labels.max() >= n_classes)):
+                raise ValueError(f"labels must be integers in the {n_classes} classes [0, {n_classes})")
+            labels = labels.to(torch.int64).pin_memory().to(dev, non_blocking=True)
+        else:
+            labels = labels.to(torch.int64)
+        buf, descs, B = transform._gather(images, dev)
+        vw = transform.sample(descs.view(np.int32)[:, 2:4]) if views is None else views(e, k, descs.view(np.int32)[:, 2:4].copy())
+        x = transform._run_views(buf, descs, B, _view_table(vw), dev)
+        return state.step(image_features(x), labels, lr_d, want_loss=want_loss)
+
     with torch.no_grad():
-        for e in range(epochs):
-            k = -1
-            for k, (images, labels) in enumerate(loader):
-                if k >= per_epoch:
-                    raise RuntimeError(f"the loader gave more than its length of {per_epoch} batches")
-                labels = torch.as_tensor(labels)
-                if not labels.is_cuda:
-                    if labels.dtype.is_floating_point or (labels.numel() and (labels.min() < 0 or labels.max() >= n_classes)):
-                        raise ValueError(f"labels must be integers in the {n_classes} classes [0, {n_classes})")
-                    labels = labels.to(torch.int64).pin_memory().to(dev, non_blocking=True)
-                else:
-                    labels = labels.to(torch.int64)
-                buf, descs, B = transform._gather(images, dev)
-                vw = transform.sample(descs.view(np.int32)[:, 2:4]) if views is None else views(e, k, descs.view(np.int32)[:, 2:4].copy())
-                x = transform._run_views(buf, descs, B, _view_table(vw), dev)
-                step = e * per_epoch + k
-                loss = state.step(image_features(x), labels, lr_steps[step:step + 1], want_loss=return_history)
-                if return_history:
-                    losses.append(loss)
-            if k + 1 != per_epoch:
-                raise RuntimeError(f"the loader gave {k + 1} batches in epoch {e}, its length says {per_epoch}")
-            if end_epoch is not None:
-                end_epoch(e)
-    torch.cuda.current_stream(dev).synchronize()   # the run's one synchronisation
-    return torch.cat(losses).cpu().numpy() if return_history else None
+        return fitloop.run_batches(step, loader, epochs, lr_steps, return_history, end_epoch)

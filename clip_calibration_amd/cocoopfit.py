@@ -33,12 +33,11 @@ from typing import Dict, Optional, Sequence
 import numpy as np
 import torch
 
-from . import _lib, ops
+from . import _lib, fitloop, ops
 from ._lib import check, lib
-from .coopfit import MAX_LIVE_ROWS, _DT, _Tower, _check_batch, _check_grad_scale, _check_sgd, _live_rows, operand_stats_dict
+from .coopfit import MAX_LIVE_ROWS, _DT, _Tower, _check_batch, _check_grad_scale, _live_rows, operand_stats_dict
 from .coopfit import _check_prompts as _check_coop_prompts
-from .taskresfit import _host_int_array, _labels, _need_gpu
-from .tempfit import cosine_warmup_schedule, steps_per_epoch
+from .fitloop import _need_gpu, steps_per_epoch
 
 # 2^10, measured on the ViT-B/16 text geometry with synthetic weights at the reference's batch of 1 (profiles/cocoopfit_parity.txt,
 # "grad_scale"): with one image dz is not divided down by a batch, and CoOp's 2^12 leaves the largest fp16 dgrad-GEMM operand only 2^1.9
@@ -141,13 +140,12 @@ def gradients(clip_model, tokenized_prompts, params, features: torch.Tensor, lab
     if not math.isfinite(logit_scale):
         raise ValueError(f"{who}: logit_scale={logit_scale} (finite)")
     E = int(clip_model.geometry.embed_dim)
-    lab = _check_batch(who, features, labels, Cn, E)
+    labels_d = _check_batch(who, features, labels, Cn, E)
     _need_gpu(features, "features")
     if features.dtype != torch.float32 or features.stride(1) != 1:
         raise TypeError(f"{who}: features must be fp32 with unit column stride")
     tower = _CoCoOpTower(who, clip_model, tokenized_prompts, Cn, features.shape[0], n_ctx, H, last, seq_rows)
     dev = features.device
-    labels_d = lab if isinstance(lab, torch.Tensor) else torch.from_numpy(lab.astype(np.int64)).to(dev)
     views = ops.cocoop_block_views(_master_block(params, n_ctx, tower.D, E, H, dev), n_ctx, tower.D, E, H)
     text = tower.forward(views, features)
     loss, d_text, rows = ops.cocoop_head(features, labels_d, text, _scale(logit_scale), gs, want_rows=True)
@@ -172,7 +170,7 @@ class CoCoOpFitState:
         who = "CoCoOpFitState"
         self.C, self.n_ctx, self.H, self._last = _check_prompts(who, clip_model, tokenized_prompts, params, seq_rows)
         self.grad_scale = _check_grad_scale(who, grad_scale)
-        _check_sgd(who, momentum, dampening, weight_decay, nesterov)
+        fitloop.check_sgd(who, momentum, dampening, weight_decay, nesterov)
         if not math.isfinite(logit_scale):
             raise ValueError(f"{who}: logit_scale={logit_scale} (finite)")
         dev = clip_model.device
@@ -203,13 +201,12 @@ class CoCoOpFitState:
         the parameters NaN, it is never used as an address).  ``one_call``: the same launches through clipmi_cocoop_train_step.
         Returns the batch loss, fp32 [1] on the device, when ``want_loss``."""
         who = "CoCoOpFitState.step"
-        lab = _check_batch(who, features, labels, self.C, self.E)
+        labels_d = _check_batch(who, features, labels, self.C, self.E)
         _need_gpu(features, "features")
         if features.dtype != torch.float32 or features.stride(1) != 1:
             raise TypeError(f"{who}: features must be fp32 with unit column stride")
         dev = features.device
-        labels_d = lab if isinstance(lab, torch.Tensor) else torch.from_numpy(lab.astype(np.int64)).to(dev)
-        lr_d = ops._dev(lr, "lr", (torch.float32,)) if isinstance(lr, torch.Tensor) else torch.tensor([float(lr)], dtype=torch.float32).to(dev)
+        lr_d = ops._dev(fitloop.lr_operand(lr, dev), "lr", (torch.float32,))
         t, m, first = self.tower(int(features.shape[0])), self.model, self.steps == 0
         sgd = (self.momentum, self.dampening, self.weight_decay, self.nesterov)
         loss = torch.empty(1, dtype=torch.float32, device=dev)
@@ -273,46 +270,19 @@ def fit_prompt_learner(features: torch.Tensor, labels, clip_model, tokenized_pro
     if not isinstance(features, torch.Tensor) or features.dim() != 2 or features.shape[0] < 1 or features.shape[1] != E:
         raise ValueError(f"{who}: features must be a [N >= 1, E = {E}] tensor")
     N = features.shape[0]
-    epochs, batch_size = int(epochs), int(batch_size)
-    if epochs < 0 or batch_size < 1:
-        raise ValueError(f"{who}: epochs={epochs} (>= 0), batch_size={batch_size} (>= 1)")
-    _check_sgd(who, momentum, dampening, weight_decay, nesterov)
+    epochs, batch_size = fitloop.check_run(who, epochs, batch_size)
+    fitloop.check_sgd(who, momentum, dampening, weight_decay, nesterov)
     _check_grad_scale(who, grad_scale)
-    lab = _labels(who, labels, N, Cn)
-    if order is not None:
-        order = _host_int_array(order, "order")
-        if order.shape != (epochs, N):
-            raise ValueError(f"{who}: order {order.shape} must be [epochs, N] = [{epochs}, {N}]")
-        if order.size and (order.min() < 0 or order.max() >= N):
-            raise ValueError(f"{who}: order holds sample indices outside [0, {N})")
-    rates = cosine_warmup_schedule(lr, epochs) if lr_per_epoch is None else [float(r) for r in lr_per_epoch]
-    if len(rates) != epochs:
-        raise ValueError(f"{who}: {len(rates)} learning rates for {epochs} epochs")
+    lab = fitloop._labels(who, labels, N, Cn)
+    order = fitloop.check_order(who, order, epochs, N)
     per_epoch = steps_per_epoch(N, batch_size, drop_last)
+    dev = features.device
+    _, lr_steps = fitloop.schedule(who, lr, epochs, lr_per_epoch, per_epoch, dev)
     if epochs * per_epoch == 0:
-        out = collections.OrderedDict((k, params[k].detach().to(torch.float32).clone().to(features.device if features.is_cuda else "cpu")) for k in NAMES)
+        out = collections.OrderedDict((k, params[k].detach().to(torch.float32).clone().to(dev if features.is_cuda else "cpu")) for k in NAMES)
         return (out, np.zeros(0, np.float32)) if return_history else out
     _need_gpu(features, "features")
-    dev = features.device
     state = CoCoOpFitState(clip_model, tokenized_prompts, params, logit_scale, momentum, dampening, weight_decay, nesterov, grad_scale, seq_rows)
-    lr_steps = torch.from_numpy(np.repeat(np.asarray(rates, np.float64), per_epoch).astype(np.float32)).to(dev)
-    labels_d = torch.from_numpy(lab.astype(np.int64)).to(dev)
-    order_d = None if order is None else torch.from_numpy(np.ascontiguousarray(order, dtype=np.int64)).to(dev)
-    losses = []
-    step = 0
-    for e in range(epochs):
-        for k in range(per_epoch):
-            lo, hi = k * batch_size, min((k + 1) * batch_size, N)
-            if order_d is None:
-                f, y = features[lo:hi], labels_d[lo:hi]
-            else:
-                idx = order_d[e, lo:hi]
-                f, y = features.index_select(0, idx), labels_d.index_select(0, idx)   # index plumbing
-            loss = state.step(f, y, lr_steps[step:step + 1], want_loss=return_history)
-            if return_history:
-                losses.append(loss)
-            step += 1
-    torch.cuda.current_stream(dev).synchronize()   # the run's one synchronisation
-    if return_history:
-        return state.params(), torch.cat(losses).cpu().numpy()
-    return state.params()
+    history = fitloop.run_cached(lambda f, y, r, want: state.step(f, y, r, want_loss=want), features, fitloop.labels_on(labels, lab, dev),
+                                 fitloop.order_on(order, np.int64, dev), batch_size, per_epoch, epochs, lr_steps, return_history)
+    return (state.params(), history) if return_history else state.params()

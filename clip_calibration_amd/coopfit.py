@@ -54,10 +54,9 @@ from typing import Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import _lib, ops
+from . import _lib, fitloop, ops
 from ._lib import check, lib
-from .taskresfit import _host_int_array, _labels, _need_gpu
-from .tempfit import cosine_warmup_schedule, steps_per_epoch
+from .fitloop import _host_int_array, _need_gpu, steps_per_epoch
 
 # 2^12, measured on the ViT-B/16 text geometry with synthetic weights (profiles/coopfit_parity.txt, "grad_scale"): the smallest of 2^0, 2^4,
 # 2^8, 2^12, 2^16 that leaves under 1 % of the fp16 dgrad-GEMM operand elements subnormal (0.76 %; 6.8 % at 2^8, 52 % at 2^0) with at least
@@ -110,21 +109,12 @@ def _check_scaler(who: str, scaler) -> dict:
     return cfg
 
 
-def _check_sgd(who: str, momentum: float, dampening: float, weight_decay: float, nesterov: bool) -> None:
-    if not (0.0 <= momentum < 1.0 and 0.0 <= dampening < 1.0):
-        raise ValueError(f"{who}: momentum={momentum}, dampening={dampening} (both in [0, 1))")
-    if not weight_decay >= 0.0 or not math.isfinite(weight_decay):
-        raise ValueError(f"{who}: weight_decay={weight_decay} (finite, >= 0)")
-    if nesterov and (momentum <= 0.0 or dampening != 0.0):
-        raise ValueError(f"{who}: Nesterov momentum requires a momentum and zero dampening")
-
-
 def _check_prompts(who: str, clip_model, tokenized_prompts, ctx) -> Tuple[int, int, bool, int]:
     """(C, n_ctx, per_class, last EOT position) after the host-side checks of the prompt set against the model and the context."""
     L, D = int(clip_model.context_length), int(clip_model.ln_final.weight.shape[0])
     if getattr(clip_model, "ivlp_text_prompts", None) is not None and clip_model.ivlp_text_prompts()[0]:
         raise ValueError(f"{who}: the model's text tower carries deep prompts; the training forward does not support them")
-    ids = _host_int_array(tokenized_prompts, "tokenized_prompts")
+    ids = _host_int_array(who, tokenized_prompts, "tokenized_prompts")
     if ids.ndim != 2 or ids.shape[1] != L or ids.shape[0] < 2:
         raise ValueError(f"{who}: tokenized_prompts {ids.shape} must be [C >= 2, {L}]")
     if not isinstance(ctx, torch.Tensor) or ctx.dim() not in (2, 3) or ctx.shape[-1] != D or not ctx.dtype.is_floating_point:
@@ -140,14 +130,11 @@ def _check_prompts(who: str, clip_model, tokenized_prompts, ctx) -> Tuple[int, i
     return ids.shape[0], n_ctx, per_class, int(eot.max())
 
 
-def _check_batch(who: str, features, labels, C: int, E: int):
+def _check_batch(who: str, features, labels, C: int, E: int) -> torch.Tensor:
+    """The batch's labels on the features' device after the checks of both (``fitloop.step_labels``)."""
     if not isinstance(features, torch.Tensor) or features.dim() != 2 or features.shape[0] < 1 or features.shape[1] != E:
         raise ValueError(f"{who}: features {tuple(getattr(features, 'shape', ()))} must be [B >= 1, E = {E}]")
-    if isinstance(labels, torch.Tensor) and labels.is_cuda and labels.dtype == torch.int64:
-        if labels.shape != (features.shape[0],):
-            raise ValueError(f"{who}: {features.shape[0]} rows need {features.shape[0]} labels, got {tuple(labels.shape)}")
-        return labels
-    return _labels(who, labels, features.shape[0], C)
+    return fitloop.step_labels(who, labels, features.shape[0], C, features.device)
 
 
 MAX_LIVE_ROWS = 80     # token rows per prompt that clipmi_text_encoder_backward takes (include/clipmi.h; the attention backward's limit)
@@ -288,10 +275,6 @@ def _new_losses(method: str, dev) -> torch.Tensor:
     return (torch.empty if method == "coop" else torch.zeros)(3, dtype=torch.float32, device=dev)
 
 
-def _master_ctx(ctx: torch.Tensor, dev) -> torch.Tensor:
-    return ctx.detach().to(device=dev, dtype=torch.float32, copy=True).contiguous()
-
-
 def context_gradient(clip_model, tokenized_prompts, ctx: torch.Tensor, features: torch.Tensor, labels, logit_scale: float = 4.6052,
                      grad_scale: float = DEFAULT_GRAD_SCALE, seq_rows: Optional[int] = None, return_operand_stats: bool = False,
                      method: str = "coop", teacher: Optional[torch.Tensor] = None, w: float = 8.0, T: float = 1.0, lam: float = 1.0,
@@ -316,14 +299,13 @@ def context_gradient(clip_model, tokenized_prompts, ctx: torch.Tensor, features:
         raise ValueError(f"{who}: logit_scale={logit_scale} (finite)")
     E = int(clip_model.geometry.embed_dim)
     _check_method(who, method, teacher, w, T, lam, Cn, E)
-    lab = _check_batch(who, features, labels, Cn, E)
+    labels_d = _check_batch(who, features, labels, Cn, E)
     _need_gpu(features, "features")
     if method != "coop":
         _need_gpu(teacher, "teacher")
     tower = _Tower(who, clip_model, tokenized_prompts, Cn, n_ctx, per_class, last, seq_rows)
     dev = features.device
-    labels_d = lab if isinstance(lab, torch.Tensor) else torch.from_numpy(lab.astype(np.int64)).to(dev)
-    master = _master_ctx(ctx, dev)
+    master = fitloop.master(ctx, dev)
     text = tower.forward(master)
     scale = float(np.float32(math.exp(logit_scale)))
     stats = torch.zeros(4, dtype=torch.int64, device=dev) if return_operand_stats else None
@@ -351,7 +333,7 @@ def text_features(clip_model, tokenized_prompts, ctx: torch.Tensor, seq_rows: Op
     who = "text_features"
     Cn, n_ctx, per_class, last = _check_prompts(who, clip_model, tokenized_prompts, ctx)
     tower = _Tower(who, clip_model, tokenized_prompts, Cn, n_ctx, per_class, last, seq_rows)
-    return tower.forward(_master_ctx(ctx, clip_model.device)).clone()
+    return tower.forward(fitloop.master(ctx, clip_model.device)).clone()
 
 
 class CoOpFitState:
@@ -374,7 +356,7 @@ class CoOpFitState:
             if scaler is not None:
                 raise ValueError(f"{who}: scaler is an argument of grad_scale={DYNAMIC!r}")
             self.grad_scale = _check_grad_scale(who, grad_scale)
-        _check_sgd(who, momentum, dampening, weight_decay, nesterov)
+        fitloop.check_sgd(who, momentum, dampening, weight_decay, nesterov)
         if not math.isfinite(logit_scale):
             raise ValueError(f"{who}: logit_scale={logit_scale} (finite)")
         _check_method(who, method, teacher, w, T, lam, self.C, int(clip_model.geometry.embed_dim))
@@ -385,7 +367,7 @@ class CoOpFitState:
             self.teacher = teacher.detach().contiguous()
         self.tower = _Tower(who, clip_model, tokenized_prompts, self.C, self.n_ctx, self.per_class, last, seq_rows)
         dev = clip_model.device
-        self.ctx = _master_ctx(ctx, dev)
+        self.ctx = fitloop.master(ctx, dev)
         self.buf = torch.zeros_like(self.ctx) if momentum != 0.0 else None
         self.scale = float(np.float32(math.exp(logit_scale)))
         self.momentum, self.dampening, self.nesterov, self.weight_decay = momentum, dampening, nesterov, weight_decay
@@ -437,13 +419,12 @@ class CoOpFitState:
         (clipmi_prompt_train_step; clipmi_prompt_train_step_scaled under the dynamic scale).  Returns the batch loss, fp32 [1] on the
         device, when ``want_loss``: the total for KgCoOp, ``xe`` for ProGrad.  Under the dynamic scale a skipped step still counts in
         ``steps`` and still returns its loss; whether it was applied is in ``scaler_state()``."""
-        lab = _check_batch("CoOpFitState.step", features, labels, self.C, self.tower.E)
+        labels_d = _check_batch("CoOpFitState.step", features, labels, self.C, self.tower.E)
         _need_gpu(features, "features")
         if features.dtype != torch.float32 or features.stride(1) != 1:
             raise TypeError("CoOpFitState.step: features must be fp32 with unit column stride")
         dev = features.device
-        labels_d = lab if isinstance(lab, torch.Tensor) else torch.from_numpy(lab.astype(np.int64)).to(dev)
-        lr_d = ops._dev(lr, "lr", (torch.float32,)) if isinstance(lr, torch.Tensor) else torch.tensor([float(lr)], dtype=torch.float32).to(dev)
+        lr_d = ops._dev(fitloop.lr_operand(lr, dev), "lr", (torch.float32,))
         t, m, first = self.tower, self.tower.model, self.steps == 0
         sgd = (self.momentum, self.dampening, self.weight_decay, self.nesterov)
         losses = _new_losses(self.method, dev)
@@ -502,7 +483,7 @@ def fit_context(features: torch.Tensor, labels, clip_model, tokenized_prompts, c
     ``grad_scale="dynamic"`` with ``scaler`` (module docstring; CoOp and KgCoOp): a step that overflows fp16 is skipped on the device and
     the scale adapts; the history keeps one loss per step, skipped steps included, and the run still synchronises once."""
     who = "fit_context"
-    ids = _host_int_array(tokenized_prompts, "tokenized_prompts")
+    ids = _host_int_array(who, tokenized_prompts, "tokenized_prompts")
     if ctx is None:
         ctx = init_context(clip_model, n_ctx, ids.shape[0] if csc else None)
     Cn, n_ctx, per_class, _ = _check_prompts(who, clip_model, tokenized_prompts, ctx)
@@ -510,10 +491,8 @@ def fit_context(features: torch.Tensor, labels, clip_model, tokenized_prompts, c
     if not isinstance(features, torch.Tensor) or features.dim() != 2 or features.shape[0] < 1 or features.shape[1] != E:
         raise ValueError(f"{who}: features must be a [N >= 1, E = {E}] tensor")
     N = features.shape[0]
-    epochs, batch_size = int(epochs), int(batch_size)
-    if epochs < 0 or batch_size < 1:
-        raise ValueError(f"{who}: epochs={epochs} (>= 0), batch_size={batch_size} (>= 1)")
-    _check_sgd(who, momentum, dampening, weight_decay, nesterov)
+    epochs, batch_size = fitloop.check_run(who, epochs, batch_size)
+    fitloop.check_sgd(who, momentum, dampening, weight_decay, nesterov)
     if _is_dynamic(who, grad_scale):
         if method == "prograd":
             raise ValueError(f"{who}: grad_scale={DYNAMIC!r} covers method 'coop' and 'kgcoop'; ProGrad keeps a static scale")
@@ -523,43 +502,18 @@ def fit_context(features: torch.Tensor, labels, clip_model, tokenized_prompts, c
             raise ValueError(f"{who}: scaler is an argument of grad_scale={DYNAMIC!r}")
         _check_grad_scale(who, grad_scale)
     _check_method(who, method, teacher, w, T, lam, Cn, E)
-    lab = _labels(who, labels, N, Cn)
-    if order is not None:
-        order = _host_int_array(order, "order")
-        if order.shape != (epochs, N):
-            raise ValueError(f"{who}: order {order.shape} must be [epochs, N] = [{epochs}, {N}]")
-        if order.size and (order.min() < 0 or order.max() >= N):
-            raise ValueError(f"{who}: order holds sample indices outside [0, {N})")
-    rates = cosine_warmup_schedule(lr, epochs) if lr_per_epoch is None else [float(r) for r in lr_per_epoch]
-    if len(rates) != epochs:
-        raise ValueError(f"{who}: {len(rates)} learning rates for {epochs} epochs")
+    lab = fitloop._labels(who, labels, N, Cn)
+    order = fitloop.check_order(who, order, epochs, N)
     per_epoch = steps_per_epoch(N, batch_size, drop_last)
+    dev = features.device
+    _, lr_steps = fitloop.schedule(who, lr, epochs, lr_per_epoch, per_epoch, dev)
     if epochs * per_epoch == 0:
         out = ctx.detach().to(torch.float32).clone()
-        out = out.to(features.device) if features.is_cuda else out
+        out = out.to(dev) if features.is_cuda else out
         return (out, np.zeros(0, np.float32)) if return_history else out
     _need_gpu(features, "features")
-    dev = features.device
     state = CoOpFitState(clip_model, tokenized_prompts, ctx, logit_scale, momentum, dampening, nesterov, weight_decay, grad_scale, seq_rows,
                          method, teacher, w, T, lam, scaler)
-    lr_steps = torch.from_numpy(np.repeat(np.asarray(rates, np.float64), per_epoch).astype(np.float32)).to(dev)
-    labels_d = torch.from_numpy(lab.astype(np.int64)).to(dev)
-    order_d = None if order is None else torch.from_numpy(np.ascontiguousarray(order, dtype=np.int64)).to(dev)
-    losses = []
-    step = 0
-    for e in range(epochs):
-        for k in range(per_epoch):
-            lo, hi = k * batch_size, min((k + 1) * batch_size, N)
-            if order_d is None:
-                f, y = features[lo:hi], labels_d[lo:hi]
-            else:
-                idx = order_d[e, lo:hi]
-                f, y = features.index_select(0, idx), labels_d.index_select(0, idx)   # index plumbing
-            loss = state.step(f, y, lr_steps[step:step + 1], want_loss=return_history)
-            if return_history:
-                losses.append(loss)
-            step += 1
-    torch.cuda.current_stream(dev).synchronize()   # the run's one synchronisation
-    if return_history:
-        return state.ctx, torch.cat(losses).cpu().numpy()
-    return state.ctx
+    history = fitloop.run_cached(lambda f, y, r, want: state.step(f, y, r, want_loss=want), features, fitloop.labels_on(labels, lab, dev),
+                                 fitloop.order_on(order, np.int64, dev), batch_size, per_epoch, epochs, lr_steps, return_history)
+    return (state.ctx, history) if return_history else state.ctx

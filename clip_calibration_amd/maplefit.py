@@ -37,12 +37,10 @@ from typing import Dict, Optional, Sequence
 import numpy as np
 import torch
 
-from . import _lib, ops
+from . import _lib, fitloop, ops
 from ._lib import check, lib
 from . import coopfit, vptfit
-from .coopfit import _check_grad_scale, _check_sgd
-from .tempfit import cosine_warmup_schedule, steps_per_epoch
-from .vptfit import _labels_dev
+from .coopfit import _check_grad_scale
 
 # 2^10, one power of two for both towers' backwards, measured at ViT-B/16 with synthetic weights, n_ctx 2, depth 9, batch 4, 100 classes
 # (profiles/maplefit_parity.txt, "grad_scale"): the text tower's dgrad-GEMM operands reach 1413 there (2^5.5 of headroom below fp16's
@@ -217,7 +215,7 @@ def gradients(model, learner_params: Dict[str, torch.Tensor], images: torch.Tens
     tw = _Towers(who, model, tokenized_prompts, learner_params, seq_rows, class_token_position)
     images = tw.vision.images(who, images)
     dev = images.device
-    labels_d = _labels_dev(who, labels, images.shape[0], tw.C, dev)
+    labels_d = fitloop.step_labels(who, labels, images.shape[0], tw.C, dev, "images")
     block = pack_block(learner_params, tw.depth, dev)
     text, feats = tw.forward(block, images)
     scale = float(np.float32(math.exp(logit_scale)))
@@ -251,7 +249,7 @@ class MaPLeFitState:
                  seq_rows: Optional[int] = None, class_token_position: str = "end"):
         who = "MaPLeFitState"
         self.grad_scale = _check_grad_scale(who, grad_scale)
-        _check_sgd(who, momentum, dampening, weight_decay, nesterov)
+        fitloop.check_sgd(who, momentum, dampening, weight_decay, nesterov)
         if not math.isfinite(logit_scale):
             raise ValueError(f"{who}: logit_scale={logit_scale} (finite)")
         self.towers = _Towers(who, model, tokenized_prompts, learner_params, seq_rows, class_token_position)
@@ -277,8 +275,8 @@ class MaPLeFitState:
         t, v, m = tw.text, tw.vision, tw.model
         images = v.images(who, images)
         dev, B = images.device, images.shape[0]
-        labels_d = _labels_dev(who, labels, B, self.C, dev)
-        lr_d = ops._dev(lr, "lr", (torch.float32,)) if isinstance(lr, torch.Tensor) else torch.tensor([float(lr)], dtype=torch.float32).to(dev)
+        labels_d = fitloop.step_labels(who, labels, B, self.C, dev, "images")
+        lr_d = ops._dev(fitloop.lr_operand(lr, dev), "lr", (torch.float32,))
         first = self.steps == 0
         sgd = (float(self.momentum), float(self.dampening), float(self.weight_decay), int(bool(self.nesterov)))
         loss = torch.empty(1, dtype=torch.float32, device=dev)
@@ -340,31 +338,7 @@ def fit_prompt_learner(images_or_loader, labels, model, tokenized_prompts, learn
         learner_params = init_learner_params(model, n_ctx, depth)
     state = MaPLeFitState(model, tokenized_prompts, learner_params, logit_scale, momentum, dampening, nesterov, weight_decay, grad_scale, seq_rows,
                           class_token_position)
-    if isinstance(images_or_loader, torch.Tensor):
-        N, bs = images_or_loader.shape[0], int(batch_size)
-        if bs < 1:
-            raise ValueError(f"{who}: batch_size={batch_size} (>= 1)")
-        per_epoch = steps_per_epoch(N, bs, drop_last)
-        lab = _labels_dev(who, labels, N, state.C, model.device)
-        batches = [(images_or_loader[k * bs:min((k + 1) * bs, N)], lab[k * bs:min((k + 1) * bs, N)]) for k in range(per_epoch)]
-    else:
-        batches = images_or_loader
-        per_epoch = len(batches)
-    rates = cosine_warmup_schedule(lr, epochs) if lr_per_epoch is None else [float(r) for r in lr_per_epoch]
-    if len(rates) != epochs:
-        raise ValueError(f"{who}: {len(rates)} learning rates for {epochs} epochs")
-    losses = []
-    if epochs * per_epoch:
-        dev = model.device
-        lr_steps = torch.from_numpy(np.repeat(np.asarray(rates, np.float64), per_epoch).astype(np.float32)).to(dev)
-        step = 0
-        for _ in range(epochs):
-            for x, y in batches:
-                loss = state.step(x, y, lr_steps[step:step + 1], want_loss=return_history)
-                if return_history:
-                    losses.append(loss)
-                step += 1
-        torch.cuda.current_stream(dev).synchronize()   # the run's one synchronisation
-    if return_history:
-        return state.params(), (torch.cat(losses).cpu().numpy() if losses else np.zeros(0, np.float32))
-    return state.params()
+    batches = fitloop.cut_batches(who, images_or_loader, labels, state.C, batch_size, drop_last, model.device)
+    _, lr_steps = fitloop.schedule(who, lr, epochs, lr_per_epoch, len(batches), model.device)
+    history = fitloop.run_batches(lambda e, k, b, r, want: state.step(b[0], b[1], r, want_loss=want), batches, epochs, lr_steps, return_history)
+    return (state.params(), history) if return_history else state.params()

@@ -37,11 +37,10 @@ from typing import Optional, Sequence
 import numpy as np
 import torch
 
-from . import _lib, ops
+from . import _lib, fitloop, ops
 from ._lib import check, lib
-from .coopfit import DEFAULT_GRAD_SCALE, MAX_LIVE_ROWS, _DT, _Tower, _check_batch, _check_grad_scale, _check_sgd, _live_rows, _master_ctx
-from .taskresfit import _host_int_array, _labels, _need_gpu
-from .tempfit import cosine_warmup_schedule, steps_per_epoch
+from .coopfit import DEFAULT_GRAD_SCALE, MAX_LIVE_ROWS, _DT, _Tower, _check_batch, _check_grad_scale, _live_rows
+from .fitloop import _host_int_array, _need_gpu, steps_per_epoch
 
 
 def positions(n_prompt: int) -> np.ndarray:
@@ -91,7 +90,7 @@ def _check_alpha(who: str, alpha: float) -> float:
 
 def _check_sel(who: str, sel, P: int, pos: np.ndarray, name: str = "sel") -> np.ndarray:
     """One selection [Pb] or a schedule [steps, Pb] in the reference's order, after the range and repeat checks."""
-    a = _host_int_array(sel, name)
+    a = _host_int_array(who, sel, name)
     if a.ndim not in (1, 2) or a.shape[-1] < 1 or P % a.shape[-1]:
         raise ValueError(f"{who}: {name} {a.shape} must hold prompt_bs indices (a divisor of n_prompt={P}) per step")
     if a.size and (a.min() < 0 or a.max() >= P):
@@ -108,7 +107,7 @@ def _check_prompts(who: str, clip_model, tokenized_prompts, ctx, name_lens, seq_
     L, D = int(clip_model.context_length), int(clip_model.ln_final.weight.shape[0])
     if getattr(clip_model, "ivlp_text_prompts", None) is not None and clip_model.ivlp_text_prompts()[0]:
         raise ValueError(f"{who}: the model's text tower carries deep prompts; the training forward does not support them")
-    ids = _host_int_array(tokenized_prompts, "tokenized_prompts")
+    ids = _host_int_array(who, tokenized_prompts, "tokenized_prompts")
     if ids.ndim != 2 or ids.shape[1] != L or ids.shape[0] < 2:
         raise ValueError(f"{who}: tokenized_prompts {ids.shape} must be [C >= 2, {L}]")
     if not isinstance(ctx, torch.Tensor) or ctx.dim() != 3 or ctx.shape[-1] != D or not ctx.dtype.is_floating_point:
@@ -121,7 +120,7 @@ def _check_prompts(who: str, clip_model, tokenized_prompts, ctx, name_lens, seq_
     if name_lens is None:
         nl = own
     else:
-        nl = _host_int_array(name_lens, "name_lens")
+        nl = _host_int_array(who, name_lens, "name_lens")
         if nl.shape != (ids.shape[0],):
             raise ValueError(f"{who}: name_lens {nl.shape} must hold one length per class ({ids.shape[0]})")
         if nl.min() < 0:
@@ -200,13 +199,12 @@ def context_gradient(clip_model, tokenized_prompts, ctx: torch.Tensor, features:
     if not math.isfinite(logit_scale):
         raise ValueError(f"{who}: logit_scale={logit_scale} (finite)")
     E = int(clip_model.geometry.embed_dim)
-    lab = _check_batch(who, features, labels, Cn, E)
+    labels_d = _check_batch(who, features, labels, Cn, E)
     _need_gpu(features, "features")
     tower = _ProDATower(who, clip_model, ids_all, Cn, P, len(sel_h), n_ctx, nl, last, seq_rows)
     dev = features.device
-    labels_d = lab if isinstance(lab, torch.Tensor) else torch.from_numpy(lab.astype(np.int64)).to(dev)
     sel_d = torch.from_numpy(sel_h).to(dev)
-    text = tower.forward(_master_ctx(ctx, dev), sel_d)
+    text = tower.forward(fitloop.master(ctx, dev), sel_d)
     losses, d_text = ops.proda_head(features, labels_d, text, Cn, len(sel_h), _scale(logit_scale), gs, alpha)
     d_embed = tower.backward(d_text)
     grad = ops.proda_ctx_step(d_embed, sel_d, tower.pos, tower.name_lens, n_ctx, gs)
@@ -229,12 +227,12 @@ class ProDAFitState:
         _check_collection(who, self.P, self.Pb)
         self.alpha = _check_alpha(who, alpha)
         self.grad_scale = _check_grad_scale(who, grad_scale)
-        _check_sgd(who, momentum, dampening, weight_decay, nesterov)
+        fitloop.check_sgd(who, momentum, dampening, weight_decay, nesterov)
         if not math.isfinite(logit_scale):
             raise ValueError(f"{who}: logit_scale={logit_scale} (finite)")
         self.tower = _ProDATower(who, clip_model, ids_all, self.C, self.P, self.Pb, self.n_ctx, nl, last, seq_rows)
         dev = clip_model.device
-        self.ctx = _master_ctx(ctx, dev)
+        self.ctx = fitloop.master(ctx, dev)
         self.buf = torch.zeros_like(self.ctx) if momentum != 0.0 else None
         self.scale = _scale(logit_scale)
         self.momentum, self.dampening, self.nesterov, self.weight_decay = momentum, dampening, nesterov, weight_decay
@@ -260,7 +258,7 @@ class ProDAFitState:
         address); anything else is checked and ordered on the host.  ``one_call``: the same launches through
         clipmi_proda_train_step.  Returns the batch loss, fp32 [1] on the device, when ``want_loss``."""
         who = "ProDAFitState.step"
-        lab = _check_batch(who, features, labels, self.C, self.tower.E)
+        labels_d = _check_batch(who, features, labels, self.C, self.tower.E)
         _need_gpu(features, "features")
         if features.dtype != torch.float32 or features.stride(1) != 1:
             raise TypeError(f"{who}: features must be fp32 with unit column stride")
@@ -274,8 +272,7 @@ class ProDAFitState:
             if sel_h.shape != (self.Pb,):
                 raise ValueError(f"{who}: sel {sel_h.shape} must be [prompt_bs] = [{self.Pb}]")
             sel_d = torch.from_numpy(sel_h).to(dev)
-        labels_d = lab if isinstance(lab, torch.Tensor) else torch.from_numpy(lab.astype(np.int64)).to(dev)
-        lr_d = ops._dev(lr, "lr", (torch.float32,)) if isinstance(lr, torch.Tensor) else torch.tensor([float(lr)], dtype=torch.float32).to(dev)
+        lr_d = ops._dev(fitloop.lr_operand(lr, dev), "lr", (torch.float32,))
         t, m, first = self.tower, self.tower.model, self.steps == 0
         sgd = (self.momentum, self.dampening, self.weight_decay, self.nesterov)
         losses = torch.empty(3, dtype=torch.float32, device=dev)
@@ -326,23 +323,15 @@ def fit_context(features: torch.Tensor, labels, clip_model, tokenized_prompts, c
     if not isinstance(features, torch.Tensor) or features.dim() != 2 or features.shape[0] < 1 or features.shape[1] != E:
         raise ValueError(f"{who}: features must be a [N >= 1, E = {E}] tensor")
     N = features.shape[0]
-    epochs, batch_size = int(epochs), int(batch_size)
-    if epochs < 0 or batch_size < 1:
-        raise ValueError(f"{who}: epochs={epochs} (>= 0), batch_size={batch_size} (>= 1)")
-    _check_sgd(who, momentum, dampening, weight_decay, nesterov)
+    epochs, batch_size = fitloop.check_run(who, epochs, batch_size)
+    fitloop.check_sgd(who, momentum, dampening, weight_decay, nesterov)
     _check_grad_scale(who, grad_scale)
     _check_alpha(who, alpha)
-    lab = _labels(who, labels, N, Cn)
-    if order is not None:
-        order = _host_int_array(order, "order")
-        if order.shape != (epochs, N):
-            raise ValueError(f"{who}: order {order.shape} must be [epochs, N] = [{epochs}, {N}]")
-        if order.size and (order.min() < 0 or order.max() >= N):
-            raise ValueError(f"{who}: order holds sample indices outside [0, {N})")
-    rates = cosine_warmup_schedule(lr, epochs) if lr_per_epoch is None else [float(r) for r in lr_per_epoch]
-    if len(rates) != epochs:
-        raise ValueError(f"{who}: {len(rates)} learning rates for {epochs} epochs")
+    lab = fitloop._labels(who, labels, N, Cn)
+    order = fitloop.check_order(who, order, epochs, N)
     per_epoch = steps_per_epoch(N, batch_size, drop_last)
+    dev = features.device
+    _, lr_steps = fitloop.schedule(who, lr, epochs, lr_per_epoch, per_epoch, dev)
     steps = epochs * per_epoch
     if selections is None:
         sels = draw_selections(P, int(prompt_bs), steps, generator if generator is not None else torch.Generator().manual_seed(0))
@@ -352,31 +341,13 @@ def fit_context(features: torch.Tensor, labels, clip_model, tokenized_prompts, c
             raise ValueError(f"{who}: selections {sels.shape} must be [steps, prompt_bs] = [{steps}, {int(prompt_bs)}]")
     if steps == 0:
         out = ctx.detach().to(torch.float32).clone()
-        out = out.to(features.device) if features.is_cuda else out
+        out = out.to(dev) if features.is_cuda else out
         return (out, np.zeros(0, np.float32)) if return_history else out
     _need_gpu(features, "features")
-    dev = features.device
     state = ProDAFitState(clip_model, tokenized_prompts, ctx, prompt_bs, alpha, logit_scale, momentum, dampening, nesterov, weight_decay, grad_scale,
                           seq_rows, name_lens)
-    lr_steps = torch.from_numpy(np.repeat(np.asarray(rates, np.float64), per_epoch).astype(np.float32)).to(dev)
-    labels_d = torch.from_numpy(lab.astype(np.int64)).to(dev)
-    order_d = None if order is None else torch.from_numpy(np.ascontiguousarray(order, dtype=np.int64)).to(dev)
     sels_d = torch.from_numpy(np.ascontiguousarray(sels, dtype=np.int32)).to(dev)
-    losses = []
-    step = 0
-    for e in range(epochs):
-        for k in range(per_epoch):
-            lo, hi = k * batch_size, min((k + 1) * batch_size, N)
-            if order_d is None:
-                f, y = features[lo:hi], labels_d[lo:hi]
-            else:
-                idx = order_d[e, lo:hi]
-                f, y = features.index_select(0, idx), labels_d.index_select(0, idx)   # index plumbing
-            loss = state.step(f, y, lr_steps[step:step + 1], sel=sels_d[step], want_loss=return_history)
-            if return_history:
-                losses.append(loss)
-            step += 1
-    torch.cuda.current_stream(dev).synchronize()   # the run's one synchronisation
-    if return_history:
-        return state.ctx, torch.cat(losses).cpu().numpy()
-    return state.ctx
+    history = fitloop.run_cached(lambda f, y, r, want: state.step(f, y, r, sel=sels_d[state.steps], want_loss=want), features,
+                                 fitloop.labels_on(labels, lab, dev), fitloop.order_on(order, np.int64, dev), batch_size, per_epoch, epochs, lr_steps,
+                                 return_history)
+    return (state.ctx, history) if return_history else state.ctx

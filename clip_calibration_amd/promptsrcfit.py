@@ -40,13 +40,11 @@ from typing import Dict, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import _lib, ops
+from . import _lib, fitloop, ops
 from ._lib import check, lib
 from . import coopfit, vptfit
-from .coopfit import _check_grad_scale, _check_sgd
-from .taskresfit import _need_gpu
-from .tempfit import cosine_warmup_schedule, steps_per_epoch
-from .vptfit import _labels_dev
+from .coopfit import _check_grad_scale
+from .fitloop import _need_gpu
 
 # 2^10, one power of two for both towers' backwards, measured at ViT-B/16 with synthetic weights, nt = nv = 4, depths 9 / 9, batch 4, 100
 # classes and the weights 25 / 10 / 1 (profiles/promptsrcfit_parity.txt, "grad_scale"): the text tower's dgrad-GEMM operands reach 1556
@@ -133,7 +131,7 @@ def _check_design(who: str, model, params, class_token_position: str = "end"):
 def _check_ids(who: str, model, tokenized_prompts, nt: int):
     """(C, last EOT position): coopfit's checks of the prompt set, without its refusal of a model that carries deep text prompts."""
     L = int(model.context_length)
-    ids = coopfit._host_int_array(tokenized_prompts, "tokenized_prompts")
+    ids = fitloop._host_int_array(who, tokenized_prompts, "tokenized_prompts")
     if ids.ndim != 2 or ids.shape[1] != L or ids.shape[0] < 2:
         raise ValueError(f"{who}: tokenized_prompts {ids.shape} must be [C >= 2, {L}]")
     eot = ids.argmax(axis=1)
@@ -313,7 +311,7 @@ def gradients(model, params: Dict[str, torch.Tensor], images: torch.Tensor, labe
     teacher = _check_teacher(who, model, teacher, tw.C)
     images = tw.vision.images(who, images)
     dev = images.device
-    labels_d = _labels_dev(who, labels, images.shape[0], tw.C, dev)
+    labels_d = fitloop.step_labels(who, labels, images.shape[0], tw.C, dev, "images")
     block = pack_block(params, dev)
     zs = tw.frozen(images)
     text, feats = tw.forward(block, images)
@@ -342,7 +340,7 @@ class PromptSRCFitState:
                  class_token_position: str = "end"):
         who = "PromptSRCFitState"
         self.grad_scale = _check_grad_scale(who, grad_scale)
-        _check_sgd(who, momentum, dampening, weight_decay, nesterov)
+        fitloop.check_sgd(who, momentum, dampening, weight_decay, nesterov)
         self.weights = _method_weights(who, method, w_text, w_image, w_logit)
         if not math.isfinite(logit_scale):
             raise ValueError(f"{who}: logit_scale={logit_scale} (finite)")
@@ -372,8 +370,8 @@ class PromptSRCFitState:
         t, v, m = tw.text, tw.vision, tw.model
         images = v.images(who, images)
         dev, B = images.device, images.shape[0]
-        labels_d = _labels_dev(who, labels, B, self.C, dev)
-        lr_d = ops._dev(lr, "lr", (torch.float32,)) if isinstance(lr, torch.Tensor) else torch.tensor([float(lr)], dtype=torch.float32).to(dev)
+        labels_d = fitloop.step_labels(who, labels, B, self.C, dev, "images")
+        lr_d = ops._dev(fitloop.lr_operand(lr, dev), "lr", (torch.float32,))
         first = self.steps == 0
         sgd = (float(self.momentum), float(self.dampening), float(self.weight_decay), int(bool(self.nesterov)))
         losses = torch.empty(5, dtype=torch.float32, device=dev)
@@ -458,35 +456,15 @@ def fit_prompts(images_or_loader, labels, model, tokenized_prompts, teacher: tor
     state = PromptSRCFitState(model, tokenized_prompts, params, teacher, logit_scale, w_text, w_image, w_logit, momentum, dampening, nesterov, weight_decay,
                               grad_scale, seq_rows, method, class_token_position)
     weights = None if method == "ivlp" else _gpa_for(who, gpa, epochs)
-    if isinstance(images_or_loader, torch.Tensor):
-        N, bs = images_or_loader.shape[0], int(batch_size)
-        if bs < 1:
-            raise ValueError(f"{who}: batch_size={batch_size} (>= 1)")
-        per_epoch = steps_per_epoch(N, bs, drop_last)
-        lab = _labels_dev(who, labels, N, state.C, model.device)
-        batches = [(images_or_loader[k * bs:min((k + 1) * bs, N)], lab[k * bs:min((k + 1) * bs, N)]) for k in range(per_epoch)]
-    else:
-        batches = images_or_loader
-        per_epoch = len(batches)
-    rates = cosine_warmup_schedule(lr, epochs) if lr_per_epoch is None else [float(r) for r in lr_per_epoch]
-    if len(rates) != epochs:
-        raise ValueError(f"{who}: {len(rates)} learning rates for {epochs} epochs")
-    losses = []
-    if epochs * per_epoch:
-        dev = model.device
-        lr_steps = torch.from_numpy(np.repeat(np.asarray(rates, np.float64), per_epoch).astype(np.float32)).to(dev)
-        step = 0
-        for e in range(epochs):
-            for x, y in batches:
-                loss = state.step(x, y, lr_steps[step:step + 1], want_loss=return_history, one_call=one_call)
-                if return_history:
-                    losses.append(loss)
-                step += 1
-            if weights is not None:
-                state.end_epoch(float(weights[e]))
-        if weights is not None:
+
+    def end_epoch(e: int) -> None:
+        """GPA: the epoch's weighted block joins the running sum; behind the last epoch the sum replaces the parameters."""
+        state.end_epoch(float(weights[e]))
+        if e == epochs - 1:
             state.apply_gpa()
-        torch.cuda.current_stream(dev).synchronize()   # the run's one synchronisation
-    if return_history:
-        return state.params(), (torch.cat(losses).cpu().numpy() if losses else np.zeros(0, np.float32))
-    return state.params()
+
+    batches = fitloop.cut_batches(who, images_or_loader, labels, state.C, batch_size, drop_last, model.device)
+    _, lr_steps = fitloop.schedule(who, lr, epochs, lr_per_epoch, len(batches), model.device)
+    history = fitloop.run_batches(lambda e, k, b, r, want: state.step(b[0], b[1], r, want_loss=want, one_call=one_call), batches, epochs, lr_steps, return_history,
+                                  None if weights is None else end_epoch)
+    return (state.params(), history) if return_history else state.params()

@@ -29,32 +29,22 @@ from typing import Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import ops
-from .tempfit import cosine_warmup_schedule, steps_per_epoch
-
-
-def _host_int_array(x, name: str) -> np.ndarray:
-    a = x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
-    if a.dtype.kind not in "iu":
-        raise TypeError(f"fit_residuals: {name} must be integers, got {a.dtype}")
-    return a
+from . import fitloop, ops
+from .fitloop import _need_gpu, steps_per_epoch
 
 
 def _check_optimiser(who: str, optimizer: str, betas, eps: float, weight_decay: float, momentum: float, dampening: float, nesterov: bool) -> None:
     if optimizer not in ("adam", "sgd"):
         raise ValueError(f"{who}: optimizer {optimizer!r} must be 'adam' or 'sgd'")
-    if not weight_decay >= 0.0 or not math.isfinite(weight_decay):
-        raise ValueError(f"{who}: weight_decay={weight_decay} (finite, >= 0)")
     if optimizer == "adam":
+        if not weight_decay >= 0.0 or not math.isfinite(weight_decay):
+            raise ValueError(f"{who}: weight_decay={weight_decay} (finite, >= 0)")
         if len(betas) != 2 or not all(0.0 <= float(b) < 1.0 for b in betas):
             raise ValueError(f"{who}: betas={tuple(betas)} (two values in [0, 1))")
         if not eps >= 0.0 or not math.isfinite(eps):
             raise ValueError(f"{who}: eps={eps} (finite, >= 0)")
         return
-    if not (0.0 <= momentum < 1.0 and 0.0 <= dampening < 1.0):
-        raise ValueError(f"{who}: momentum={momentum}, dampening={dampening} (both in [0, 1))")
-    if nesterov and (momentum <= 0.0 or dampening != 0.0):
-        raise ValueError(f"{who}: Nesterov momentum requires a momentum and zero dampening")
+    fitloop.check_sgd(who, momentum, dampening, weight_decay, nesterov)
 
 
 def _check_shapes(who: str, features, base, residuals) -> Tuple[int, int, int]:
@@ -68,25 +58,11 @@ def _check_shapes(who: str, features, base, residuals) -> Tuple[int, int, int]:
     return N, E, base.shape[0]
 
 
-def _labels(who: str, labels, N: int, C: int) -> np.ndarray:
-    lab = _host_int_array(labels, "labels")
-    if lab.shape != (N,):
-        raise ValueError(f"{who}: {N} rows need {N} labels, got {lab.shape}")
-    if lab.min() < 0 or lab.max() >= C:
-        raise ValueError(f"{who}: labels span [{int(lab.min())}, {int(lab.max())}], outside the {C} classes [0, {C})")
-    return lab
-
-
-def _need_gpu(t: torch.Tensor, name: str) -> None:
-    if not t.is_cuda:
-        raise RuntimeError(f"clipmi: `{name}` must be a tensor on the GPU (got {t.device}); the HIP path has no CPU fallback")
-
-
 def _master(base: torch.Tensor, residuals: Optional[torch.Tensor], dev) -> torch.Tensor:
     """A fresh contiguous fp32 copy on the device (zeros without ``residuals``): the master values the kernels update in place."""
     if residuals is None:
         return torch.zeros(tuple(base.shape), dtype=torch.float32, device=dev)
-    return residuals.detach().to(device=dev, dtype=torch.float32, copy=True).contiguous()
+    return fitloop.master(residuals, dev)
 
 
 def _state(r: torch.Tensor, optimizer: str, momentum: float):
@@ -115,37 +91,25 @@ def fit_residuals(features: torch.Tensor, labels, base_text_features: torch.Tens
     copied to the host for that, which waits for whatever produced it; from the first launch on nothing synchronises until the one wait
     at the end.  Returns the fitted fp32 residuals on the device, or ``(residuals, per-step batch losses as a float32 numpy array)`` with
     ``return_history``.  The defaults are unverified restatements of the reference's config and Dassl's (module docstring)."""
-    N, E, C = _check_shapes("fit_residuals", features, base_text_features, residuals)
-    epochs, batch_size = int(epochs), int(batch_size)
-    if epochs < 0 or batch_size < 1:
-        raise ValueError(f"fit_residuals: epochs={epochs} (>= 0), batch_size={batch_size} (>= 1)")
-    _check_optimiser("fit_residuals", optimizer, betas, eps, weight_decay, momentum, dampening, nesterov)
+    who = "fit_residuals"
+    N, E, C = _check_shapes(who, features, base_text_features, residuals)
+    epochs, batch_size = fitloop.check_run(who, epochs, batch_size)
+    _check_optimiser(who, optimizer, betas, eps, weight_decay, momentum, dampening, nesterov)
     if not (math.isfinite(alpha) and math.isfinite(logit_scale)):
-        raise ValueError(f"fit_residuals: alpha={alpha}, logit_scale={logit_scale} (both finite)")
-    lab = _labels("fit_residuals", labels, N, C)
-    if order is not None:
-        order = _host_int_array(order, "order")
-        if order.shape != (epochs, N):
-            raise ValueError(f"fit_residuals: order {order.shape} must be [epochs, N] = [{epochs}, {N}]")
-        if order.size and (order.min() < 0 or order.max() >= N):
-            raise ValueError(f"fit_residuals: order holds sample indices outside [0, {N})")
-    rates = cosine_warmup_schedule(lr, epochs) if lr_per_epoch is None else [float(r) for r in lr_per_epoch]
-    if len(rates) != epochs:
-        raise ValueError(f"fit_residuals: {len(rates)} learning rates for {epochs} epochs")
+        raise ValueError(f"{who}: alpha={alpha}, logit_scale={logit_scale} (both finite)")
+    lab = fitloop._labels(who, labels, N, C)
+    order = fitloop.check_order(who, order, epochs, N)
     per_epoch = steps_per_epoch(N, batch_size, drop_last)
-    _need_gpu(features, "features")
     dev = features.device
+    _, lr_steps = fitloop.schedule(who, lr, epochs, lr_per_epoch, per_epoch, dev)
+    _need_gpu(features, "features")
     r = _master(base_text_features, residuals, dev)
     if epochs * per_epoch == 0:
         return (r, np.zeros(0, np.float32)) if return_history else r
     s1, s2 = _state(r, optimizer, momentum)
-    lr_steps = torch.from_numpy(np.repeat(np.asarray(rates, np.float64), per_epoch).astype(np.float32)).to(dev)
-    order_d = None if order is None else torch.from_numpy(np.ascontiguousarray(order, dtype=np.int32)).to(dev)
-    labels_d = labels if isinstance(labels, torch.Tensor) and labels.is_cuda and labels.dtype == torch.int64 else torch.from_numpy(
-        lab.astype(np.int64)).to(dev)
-    losses = ops.taskres_fit(features, labels_d, base_text_features, r, s1, s2, lr_steps, alpha, float(np.float32(math.exp(logit_scale))),
-                             batch_size, epochs, optimizer, weight_decay, momentum, dampening, nesterov, betas, eps, order_d, drop_last,
-                             steps_done=0, want_losses=return_history)
+    losses = ops.taskres_fit(features, fitloop.labels_on(labels, lab, dev), base_text_features, r, s1, s2, lr_steps, alpha,
+                             float(np.float32(math.exp(logit_scale))), batch_size, epochs, optimizer, weight_decay, momentum, dampening, nesterov,
+                             betas, eps, fitloop.order_on(order, np.int32, dev), drop_last, steps_done=0, want_losses=return_history)
     torch.cuda.current_stream().synchronize()   # the run's one synchronisation
     return (r, losses.cpu().numpy()) if return_history else r
 
@@ -182,13 +146,9 @@ class TaskResFitState:
         address; host labels are range-checked.  Returns the batch loss, fp32 [1] on the device, when ``want_loss``."""
         N, _, C = _check_shapes("TaskResFitState.step", features, self.base_text_features, None)
         _need_gpu(features, "features")
-        if isinstance(labels, torch.Tensor) and labels.is_cuda and labels.dtype == torch.int64:
-            labels_d = labels
-        else:
-            labels_d = torch.from_numpy(_labels("TaskResFitState.step", labels, N, C).astype(np.int64)).to(features.device)
-        lr_d = lr if isinstance(lr, torch.Tensor) else torch.tensor([float(lr)], dtype=torch.float32).to(features.device)
-        loss = ops.taskres_train_step(features, labels_d, self.base_text_features, self.residuals, self.state1, self.state2, lr_d, self.alpha,
-                                      self.scale, self.steps, self.optimizer, self.weight_decay, self.momentum, self.dampening, self.nesterov,
+        labels_d = fitloop.step_labels("TaskResFitState.step", labels, N, C, features.device)
+        loss = ops.taskres_train_step(features, labels_d, self.base_text_features, self.residuals, self.state1, self.state2,
+                                      fitloop.lr_operand(lr, features.device), self.alpha, self.scale, self.steps, self.optimizer, self.weight_decay, self.momentum, self.dampening, self.nesterov,
                                       self.betas, self.eps, want_loss=want_loss)
         self.steps += 1
         return loss

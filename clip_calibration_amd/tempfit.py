@@ -14,44 +14,13 @@ an argument.
 """
 from __future__ import annotations
 
-import math
-from typing import List, Optional, Sequence
+from typing import Optional, Sequence
 
 import numpy as np
 import torch
 
-from . import ops
-
-
-def cosine_warmup_schedule(lr: float, epochs: int, warmup_epochs: int = 1, warmup_lr: float = 1e-5) -> List[float]:
-    """The learning rate of every epoch under OPTIM.LR_SCHEDULER "cosine" with WARMUP_TYPE "constant": ``warmup_lr`` for the first
-    ``warmup_epochs`` epochs, then ``torch.optim.lr_scheduler.CosineAnnealingLR(T_max=epochs)``.  The hand-over rule (Dassl's
-    ConstantWarmupScheduler as publicly documented, unverified here): the cosine scheduler is not stepped while the warm-up lasts and is
-    stepped once at the end of every epoch from the last warm-up epoch on, so epoch ``e >= warmup_epochs`` runs at the cosine value of
-    index ``e - warmup_epochs + 1``: ``lr * (1 + cos(pi * (e - warmup_epochs + 1) / epochs)) / 2``.  Without a warm-up epoch ``e`` runs at
-    index ``e``."""
-    epochs, warmup_epochs = int(epochs), int(warmup_epochs)
-    if epochs < 0 or warmup_epochs < 0:
-        raise ValueError(f"cosine_warmup_schedule: epochs={epochs}, warmup_epochs={warmup_epochs} (both >= 0)")
-    out = []
-    for e in range(epochs):
-        if e < warmup_epochs:
-            out.append(float(warmup_lr))
-        else:
-            t = e - warmup_epochs + 1 if warmup_epochs > 0 else e
-            out.append(float(lr) * (1.0 + math.cos(math.pi * t / epochs)) / 2.0)
-    return out
-
-
-def steps_per_epoch(n: int, batch_size: int, drop_last: bool = False) -> int:
-    return n // batch_size if drop_last else -(-n // batch_size)
-
-
-def _host_int_array(x, name: str) -> np.ndarray:
-    a = x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
-    if a.dtype.kind not in "iu":
-        raise TypeError(f"fit_logit_scale: {name} must be integers, got {a.dtype}")
-    return a
+from . import fitloop, ops
+from .fitloop import cosine_warmup_schedule, steps_per_epoch   # re-exported: tools and tests reach both through this module
 
 
 def fit_logit_scale(cosine_logits: torch.Tensor, labels, init: float = 4.6052, epochs: int = 20, lr: float = 0.05, batch_size: int = 100,
@@ -68,44 +37,24 @@ def fit_logit_scale(cosine_logits: torch.Tensor, labels, init: float = 4.6052, e
     Labels (and ``order``) are checked against their ranges on the host before anything is launched.  Returns the fitted scalar, or
     (scalar, per-step batch losses as a float32 numpy array) with ``return_history``.  The defaults are unverified restatements of
     Dassl's (module docstring)."""
+    who = "fit_logit_scale"
     if not isinstance(cosine_logits, torch.Tensor) or cosine_logits.dim() != 2:
-        raise ValueError("fit_logit_scale: cosine_logits must be a [N, C] tensor")
+        raise ValueError(f"{who}: cosine_logits must be a [N, C] tensor")
     N, C = cosine_logits.shape
-    epochs, batch_size = int(epochs), int(batch_size)
     if N < 1 or C < 2:
-        raise ValueError(f"fit_logit_scale: cosine_logits {(N, C)} need at least one row and two classes")
-    if epochs < 0 or batch_size < 1:
-        raise ValueError(f"fit_logit_scale: epochs={epochs} (>= 0), batch_size={batch_size} (>= 1)")
-    if not (0.0 <= momentum < 1.0 and 0.0 <= dampening < 1.0 and weight_decay >= 0.0):
-        raise ValueError(f"fit_logit_scale: momentum={momentum}, dampening={dampening} (both in [0, 1)), weight_decay={weight_decay} (>= 0)")
-    if nesterov and (momentum <= 0.0 or dampening != 0.0):
-        raise ValueError("fit_logit_scale: Nesterov momentum requires a momentum and zero dampening")
-    lab = _host_int_array(labels, "labels")
-    if lab.shape != (N,):
-        raise ValueError(f"fit_logit_scale: {N} rows need {N} labels, got {lab.shape}")
-    if lab.min() < 0 or lab.max() >= C:
-        raise ValueError(f"fit_logit_scale: labels span [{int(lab.min())}, {int(lab.max())}], outside the {C} classes [0, {C})")
-    if order is not None:
-        order = _host_int_array(order, "order")
-        if order.shape != (epochs, N):
-            raise ValueError(f"fit_logit_scale: order {order.shape} must be [epochs, N] = [{epochs}, {N}]")
-        if order.size and (order.min() < 0 or order.max() >= N):
-            raise ValueError(f"fit_logit_scale: order holds sample indices outside [0, {N})")
-    rates = cosine_warmup_schedule(lr, epochs) if lr_per_epoch is None else [float(r) for r in lr_per_epoch]
-    if len(rates) != epochs:
-        raise ValueError(f"fit_logit_scale: {len(rates)} learning rates for {epochs} epochs")
+        raise ValueError(f"{who}: cosine_logits {(N, C)} need at least one row and two classes")
+    epochs, batch_size = fitloop.check_run(who, epochs, batch_size)
+    fitloop.check_sgd(who, momentum, dampening, weight_decay, nesterov)
+    lab = fitloop._labels(who, labels, N, C)
+    order = fitloop.check_order(who, order, epochs, N)
     per_epoch = steps_per_epoch(N, batch_size, drop_last)
-    if not cosine_logits.is_cuda:
-        raise RuntimeError(f"clipmi: `cosine_logits` must be a tensor on the GPU (got {cosine_logits.device}); the HIP path has no CPU fallback")
     dev = cosine_logits.device
+    _, lr_steps = fitloop.schedule(who, lr, epochs, lr_per_epoch, per_epoch, dev)
+    fitloop._need_gpu(cosine_logits, "cosine_logits")
     if epochs * per_epoch == 0:
         return (float(np.float32(init)), np.zeros(0, np.float32)) if return_history else float(np.float32(init))
     state = torch.tensor([float(init), 0.0, 0.0, 0.0], dtype=torch.float32).to(dev)
-    lr_steps = torch.from_numpy(np.repeat(np.asarray(rates, np.float64), per_epoch).astype(np.float32)).to(dev)
-    labels_d = torch.from_numpy(lab.astype(np.int64)).to(dev) if not (isinstance(labels, torch.Tensor) and labels.is_cuda
-                                                                      and labels.dtype == torch.int64) else labels
-    order_d = None if order is None else torch.from_numpy(np.ascontiguousarray(order, dtype=np.int32)).to(dev)
-    losses = ops.tempscale_fit(cosine_logits, labels_d, state, lr_steps, batch_size, epochs, momentum, dampening, weight_decay, nesterov,
-                               order_d, drop_last, want_losses=return_history)
+    losses = ops.tempscale_fit(cosine_logits, fitloop.labels_on(labels, lab, dev), state, lr_steps, batch_size, epochs, momentum, dampening,
+                               weight_decay, nesterov, fitloop.order_on(order, np.int32, dev), drop_last, want_losses=return_history)
     theta = float(state[0].item())   # the run's one synchronisation
     return (theta, losses.cpu().numpy()) if return_history else theta

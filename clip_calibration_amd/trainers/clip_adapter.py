@@ -14,6 +14,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
+from . import _fit
 from .coop import CustomCLIP as _CoOpCLIP
 
 
@@ -58,22 +59,14 @@ class CustomCLIP(_CoOpCLIP):
         if transform is not None:
             from ..adapterfit import AdapterFitState
             from ..augment import fit_with_transform
-            run = {k: fit_args.pop(k) for k in ("lr_per_epoch", "views", "return_history") if k in fit_args}
-            epochs, lr = fit_args.pop("epochs", 200), fit_args.pop("lr", 0.002)
+            run, epochs, lr = _fit.split_fit_args(fit_args, 200, 0.002)
             state = AdapterFitState(text, fc1.detach().float(), fc2.detach().float(), **fit_args)
             losses = fit_with_transform(state, self.clip_model.image_features_f32, text.shape[0], loader, transform, epochs, lr, **run)
-            fitted = (state.w1, state.w2) if losses is None else (state.w1, state.w2, losses)
+            fitted = _fit.pack((state.w1, state.w2), losses)
         else:
             from ..adapterfit import fit_adapter
-            feats, labels = [], []
-            with torch.no_grad():
-                for image, label in loader:
-                    f = self.clip_model.image_features_f32(image)
-                    feats.append(f)
-                    labels.append(torch.as_tensor(label).to(device=f.device, dtype=torch.int64))
-            if not feats:
-                raise ValueError("fit_adapter: the loader gave no batch")
-            fitted = fit_adapter(torch.cat(feats), torch.cat(labels), text, fc1.detach().float(), fc2.detach().float(), **fit_args)
+            feats, labels = _fit.cached_features("fit_adapter", self.clip_model, loader)
+            fitted = fit_adapter(feats, labels, text, fc1.detach().float(), fc2.detach().float(), **fit_args)
         with torch.no_grad():
             fc1.copy_(fitted[0])
             fc2.copy_(fitted[1])

@@ -17,6 +17,7 @@ import torch.nn as nn
 
 from .. import ops
 from ..model import CLIP
+from . import _fit
 from .coop import TextEncoder
 
 
@@ -126,22 +127,14 @@ class CustomCLIP(nn.Module):
         if transform is not None:
             from ..augment import fit_with_transform
             from ..cocoopfit import CoCoOpFitState
-            run = {k: fit_args.pop(k) for k in ("lr_per_epoch", "views", "return_history") if k in fit_args}
-            epochs, lr = fit_args.pop("epochs", 10), fit_args.pop("lr", 0.002)
+            run, epochs, lr = _fit.split_fit_args(fit_args, 10, 0.002)
             state = CoCoOpFitState(self.clip_model, ids, params, **fit_args)
             losses = fit_with_transform(state, self.clip_model.image_features_f32, ids.shape[0], train_loader, transform, epochs, lr, **run)
-            fitted = state.params() if losses is None else (state.params(), losses)
+            fitted = _fit.pack(state.params(), losses)
         else:
             from ..cocoopfit import fit_prompt_learner
-            feats, labels = [], []
-            with torch.no_grad():
-                for image, label in train_loader:
-                    f = self.clip_model.image_features_f32(image)
-                    feats.append(f)
-                    labels.append(torch.as_tensor(label).to(device=f.device, dtype=torch.int64))
-            if not feats:
-                raise ValueError("fit_prompt_learner: the loader gave no batch")
-            fitted = fit_prompt_learner(torch.cat(feats), torch.cat(labels), self.clip_model, ids, params, **fit_args)
+            feats, labels = _fit.cached_features("fit_prompt_learner", self.clip_model, train_loader)
+            fitted = fit_prompt_learner(feats, labels, self.clip_model, ids, params, **fit_args)
         values = fitted[0] if isinstance(fitted, tuple) else fitted
         target = dict(pl.named_parameters())
         with torch.no_grad():

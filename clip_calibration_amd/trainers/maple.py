@@ -7,6 +7,7 @@ import torch.nn as nn
 
 from .. import ops
 from ..model import CLIP
+from . import _fit
 from .coop import CustomCLIP as _CoOpCLIP, TextEncoder  # noqa: F401
 
 
@@ -92,11 +93,10 @@ class CustomCLIP(_CoOpCLIP):
         ids, params = self.prompt_learner.tokenized_prompts, self.learner_params()
         if transform is not None:
             from ..augment import fit_with_transform
-            run = {k: fit_args.pop(k) for k in ("lr_per_epoch", "views", "return_history") if k in fit_args}
-            epochs, lr = fit_args.pop("epochs", 5), fit_args.pop("lr", 0.0035)
+            run, epochs, lr = _fit.split_fit_args(fit_args, 5, 0.0035)
             state = maplefit.MaPLeFitState(self.clip_model, ids, params, **fit_args)
             losses = fit_with_transform(state, lambda x: x, ids.shape[0], train_loader, transform, epochs, lr, **run)
-            fitted = state.params() if losses is None else (state.params(), losses)
+            fitted = _fit.pack(state.params(), losses)
         else:
             fitted = maplefit.fit_prompt_learner(train_loader, None, self.clip_model, ids, params, **fit_args)
         block = fitted[0] if isinstance(fitted, tuple) else fitted

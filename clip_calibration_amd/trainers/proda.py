@@ -18,6 +18,7 @@ import torch.nn as nn
 
 from .. import ops
 from ..model import CLIP
+from . import _fit
 from .coop import TextEncoder
 
 
@@ -114,22 +115,14 @@ class CustomCLIP(nn.Module):
         if transform is not None:
             from ..augment import fit_with_transform
             from ..prodafit import ProDAFitState
-            run = {k: fit_args.pop(k) for k in ("lr_per_epoch", "views", "return_history") if k in fit_args}
-            epochs, lr = fit_args.pop("epochs", 200), fit_args.pop("lr", 0.002)
+            run, epochs, lr = _fit.split_fit_args(fit_args, 200, 0.002)
             state = ProDAFitState(self.clip_model, ids, ctx.detach(), **fit_args)
             losses = fit_with_transform(state, self.clip_model.image_features_f32, ids.shape[0], train_loader, transform, epochs, lr, **run)
-            fitted = state.ctx if losses is None else (state.ctx, losses)
+            fitted = _fit.pack(state.ctx, losses)
         else:
             from ..prodafit import fit_context
-            feats, labels = [], []
-            with torch.no_grad():
-                for image, label in train_loader:
-                    f = self.clip_model.image_features_f32(image)
-                    feats.append(f)
-                    labels.append(torch.as_tensor(label).to(device=f.device, dtype=torch.int64))
-            if not feats:
-                raise ValueError("fit_context: the loader gave no batch")
-            fitted = fit_context(torch.cat(feats), torch.cat(labels), self.clip_model, ids, ctx.detach(), **fit_args)
+            feats, labels = _fit.cached_features("fit_context", self.clip_model, train_loader)
+            fitted = fit_context(feats, labels, self.clip_model, ids, ctx.detach(), **fit_args)
         with torch.no_grad():
             ctx.copy_(fitted[0] if isinstance(fitted, tuple) else fitted)
         self.text_features = None

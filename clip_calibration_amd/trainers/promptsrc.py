@@ -12,6 +12,7 @@ from __future__ import annotations
 
 import torch
 
+from . import _fit
 from .coop import CustomCLIP as _CoOpCLIP
 
 
@@ -82,8 +83,8 @@ class CustomCLIP(_CoOpCLIP):
                 if k in fit_args:
                     raise ValueError(f"fit_prompts: {k} belongs to a tensor of images; with a transform the batches are the loader's")
             one_call = bool(fit_args.pop("one_call", False))
-            run = {k: fit_args.pop(k) for k in ("lr_per_epoch", "views", "return_history") if k in fit_args}
-            epochs, lr = int(fit_args.pop("epochs", 50)), fit_args.pop("lr", 0.0025)
+            run, epochs, lr = _fit.split_fit_args(fit_args, 50, 0.0025)
+            epochs = int(epochs)
             gpa = fit_args.pop("gpa", (30.0, 30.0))
             state = promptsrcfit.PromptSRCFitState(self.clip_model, ids, params, teacher_text_features, **fit_args)
             weights = None if fit_args.get("method", "promptsrc") == "ivlp" else promptsrcfit._gpa_for("fit_prompts", gpa, epochs)
@@ -93,7 +94,7 @@ class CustomCLIP(_CoOpCLIP):
             losses = fit_with_transform(stepper, lambda x: x, ids.shape[0], train_loader, transform, epochs, lr, end_epoch=end, **run)
             if weights is not None and epochs * len(train_loader):
                 state.apply_gpa()
-            fitted = state.params() if losses is None else (state.params(), losses)
+            fitted = _fit.pack(state.params(), losses)
         else:
             fitted = promptsrcfit.fit_prompts(train_loader, None, self.clip_model, ids, teacher_text_features, params, **fit_args)
         block = fitted[0] if isinstance(fitted, tuple) else fitted

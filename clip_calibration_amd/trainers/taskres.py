@@ -16,6 +16,7 @@ import torch.nn as nn
 
 from .. import ops
 from ..model import CLIP
+from . import _fit
 
 
 class TaskResLearner(nn.Module):
@@ -81,22 +82,14 @@ class CustomCLIP(nn.Module):
         if transform is not None:
             from ..augment import fit_with_transform
             from ..taskresfit import TaskResFitState
-            run = {k: fit_args.pop(k) for k in ("lr_per_epoch", "views", "return_history") if k in fit_args}
-            epochs, lr = fit_args.pop("epochs", 200), fit_args.pop("lr", 2e-4)
+            run, epochs, lr = _fit.split_fit_args(fit_args, 200, 2e-4)
             state = TaskResFitState(base, res.detach().float(), **fit_args)
             losses = fit_with_transform(state, self.clip_model.image_features_f32, base.shape[0], loader, transform, epochs, lr, **run)
-            fitted = state.residuals if losses is None else (state.residuals, losses)
+            fitted = _fit.pack(state.residuals, losses)
         else:
             from ..taskresfit import fit_residuals
-            feats, labels = [], []
-            with torch.no_grad():
-                for image, label in loader:
-                    f = self.clip_model.image_features_f32(image)
-                    feats.append(f)
-                    labels.append(torch.as_tensor(label).to(device=f.device, dtype=torch.int64))
-            if not feats:
-                raise ValueError("fit_residuals: the loader gave no batch")
-            fitted = fit_residuals(torch.cat(feats), torch.cat(labels), base, res.detach().float(), **fit_args)
+            feats, labels = _fit.cached_features("fit_residuals", self.clip_model, loader)
+            fitted = fit_residuals(feats, labels, base, res.detach().float(), **fit_args)
         with torch.no_grad():
             res.copy_(fitted[0] if isinstance(fitted, tuple) else fitted)
         return fitted

@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import torch
 
+from . import _fit
 from .zsclip import ZeroshotCLIP
 
 
@@ -41,11 +42,10 @@ class CustomCLIP(ZeroshotCLIP):
         text = self.text_features.float()
         if transform is not None:
             from ..augment import fit_with_transform
-            run = {k: fit_args.pop(k) for k in ("lr_per_epoch", "views", "return_history") if k in fit_args}
-            epochs, lr = fit_args.pop("epochs", 5), fit_args.pop("lr", 0.0025)
+            run, epochs, lr = _fit.split_fit_args(fit_args, 5, 0.0025)
             state = vptfit.VPTFitState(self.clip_model, text, **fit_args)
             losses = fit_with_transform(state, lambda x: x, text.shape[0], train_loader, transform, epochs, lr, **run)
-            fitted = state.prompts if losses is None else (state.prompts, losses)
+            fitted = _fit.pack(state.prompts, losses)
         else:
             fitted = vptfit.fit_prompts(train_loader, None, self.clip_model, text, **fit_args)
         block = fitted[0] if isinstance(fitted, tuple) else fitted

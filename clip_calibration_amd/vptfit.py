@@ -33,11 +33,10 @@ from typing import Optional, Sequence
 import numpy as np
 import torch
 
-from . import _lib, ops
+from . import _lib, fitloop, ops
 from ._lib import check, lib
-from .coopfit import _check_grad_scale, _check_sgd, operand_stats_dict
-from .taskresfit import _labels, _need_gpu
-from .tempfit import cosine_warmup_schedule, steps_per_epoch
+from .coopfit import _check_grad_scale, operand_stats_dict
+from .fitloop import _need_gpu
 
 # 2^12: CoOp's value (profiles/coopfit_parity.txt) holds for the image tower's backward at the ViT-B/16 geometry as well
 # (profiles/vptfit_parity.txt, "grad_scale").  A model with much larger gradients overflows fp16 at this scale -- the prompts then turn
@@ -204,14 +203,6 @@ def vpt_step(d_prompts: torch.Tensor, grad_scale: float, prompts: Optional[torch
     return grad
 
 
-def _labels_dev(who: str, labels, B: int, n_cls: int, dev) -> torch.Tensor:
-    if isinstance(labels, torch.Tensor) and labels.is_cuda and labels.dtype == torch.int64:
-        if labels.shape != (B,):
-            raise ValueError(f"{who}: {B} images need {B} labels, got {tuple(labels.shape)}")
-        return labels
-    return torch.from_numpy(_labels(who, labels, B, n_cls).astype(np.int64)).to(dev)
-
-
 def prompt_gradient(model, prompts: torch.Tensor, images: torch.Tensor, labels, text_features: torch.Tensor, logit_scale: float = 4.6052,
                     grad_scale: float = DEFAULT_GRAD_SCALE, return_operand_stats: bool = False, flags: int = _lib.CALL_DEFAULT):
     """``(loss, grad)`` of ``F.cross_entropy(exp(logit_scale) * normalise(encode_image(images; prompts)) @ normalise(text_features).T,
@@ -228,8 +219,8 @@ def prompt_gradient(model, prompts: torch.Tensor, images: torch.Tensor, labels, 
     tower = _Tower(who, model, depth, n_ctx)
     images = tower.images(who, images)
     dev = images.device
-    labels_d = _labels_dev(who, labels, images.shape[0], text.shape[0], dev)
-    master = prompts.detach().to(device=dev, dtype=torch.float32, copy=True).contiguous()
+    labels_d = fitloop.step_labels(who, labels, images.shape[0], text.shape[0], dev, "images")
+    master = fitloop.master(prompts, dev)
     feats = tower.forward(images, master, flags)
     scale = float(np.float32(math.exp(logit_scale)))
     stats = torch.zeros(4, dtype=torch.int64, device=dev) if return_operand_stats else None
@@ -247,7 +238,7 @@ def image_features(model, prompts: torch.Tensor, images: torch.Tensor) -> torch.
     depth, n_ctx = _check_prompts(who, model, prompts)
     tower = _Tower(who, model, depth, n_ctx)
     images = tower.images(who, images)
-    return tower.forward(images, prompts.detach().to(device=images.device, dtype=torch.float32, copy=True).contiguous()).clone()
+    return tower.forward(images, fitloop.master(prompts, images.device)).clone()
 
 
 class VPTFitState:
@@ -263,13 +254,13 @@ class VPTFitState:
             prompts = model_prompts(model)
         self.depth, self.n_ctx = _check_prompts(who, model, prompts)
         self.grad_scale = _check_grad_scale(who, grad_scale)
-        _check_sgd(who, momentum, dampening, weight_decay, nesterov)
+        fitloop.check_sgd(who, momentum, dampening, weight_decay, nesterov)
         if not math.isfinite(logit_scale):
             raise ValueError(f"{who}: logit_scale={logit_scale} (finite)")
         self.text = _check_text(who, model, text_features)
         self.C = int(self.text.shape[0])
         self.tower = _Tower(who, model, self.depth, self.n_ctx)
-        self.prompts = prompts.detach().to(device=model.device, dtype=torch.float32, copy=True).contiguous()
+        self.prompts = fitloop.master(prompts, model.device)
         self.buf = torch.zeros_like(self.prompts) if momentum != 0.0 else None
         self.scale = float(np.float32(math.exp(logit_scale)))
         self.momentum, self.dampening, self.nesterov, self.weight_decay = momentum, dampening, nesterov, weight_decay
@@ -286,8 +277,8 @@ class VPTFitState:
         t, m = self.tower, self.tower.model
         images = t.images(who, images)
         dev, B = images.device, images.shape[0]
-        labels_d = _labels_dev(who, labels, B, self.C, dev)
-        lr_d = ops._dev(lr, "lr", (torch.float32,)) if isinstance(lr, torch.Tensor) else torch.tensor([float(lr)], dtype=torch.float32).to(dev)
+        labels_d = fitloop.step_labels(who, labels, B, self.C, dev, "images")
+        lr_d = ops._dev(fitloop.lr_operand(lr, dev), "lr", (torch.float32,))
         first = self.steps == 0
         sgd = (float(self.momentum), float(self.dampening), float(self.weight_decay), int(bool(self.nesterov)))
         loss = torch.empty(1, dtype=torch.float32, device=dev)
@@ -324,31 +315,7 @@ def fit_prompts(images_or_loader, labels, model, text_features: torch.Tensor, pr
     if epochs < 0:
         raise ValueError(f"{who}: epochs={epochs} (>= 0)")
     state = VPTFitState(model, text_features, logit_scale, prompts, momentum, dampening, nesterov, weight_decay, grad_scale)
-    if isinstance(images_or_loader, torch.Tensor):
-        N, bs = images_or_loader.shape[0], int(batch_size)
-        if bs < 1:
-            raise ValueError(f"{who}: batch_size={batch_size} (>= 1)")
-        per_epoch = steps_per_epoch(N, bs, drop_last)
-        lab = _labels_dev(who, labels, N, state.C, model.device)
-        batches = [(images_or_loader[k * bs:min((k + 1) * bs, N)], lab[k * bs:min((k + 1) * bs, N)]) for k in range(per_epoch)]
-    else:
-        batches = images_or_loader
-        per_epoch = len(batches)
-    rates = cosine_warmup_schedule(lr, epochs) if lr_per_epoch is None else [float(r) for r in lr_per_epoch]
-    if len(rates) != epochs:
-        raise ValueError(f"{who}: {len(rates)} learning rates for {epochs} epochs")
-    losses = []
-    if epochs * per_epoch:
-        dev = model.device
-        lr_steps = torch.from_numpy(np.repeat(np.asarray(rates, np.float64), per_epoch).astype(np.float32)).to(dev)
-        step = 0
-        for _ in range(epochs):
-            for x, y in batches:
-                loss = state.step(x, y, lr_steps[step:step + 1], want_loss=return_history)
-                if return_history:
-                    losses.append(loss)
-                step += 1
-        torch.cuda.current_stream(dev).synchronize()   # the run's one synchronisation
-    if return_history:
-        return state.prompts, (torch.cat(losses).cpu().numpy() if losses else np.zeros(0, np.float32))
-    return state.prompts
+    batches = fitloop.cut_batches(who, images_or_loader, labels, state.C, batch_size, drop_last, model.device)
+    _, lr_steps = fitloop.schedule(who, lr, epochs, lr_per_epoch, len(batches), model.device)
+    history = fitloop.run_batches(lambda e, k, b, r, want: state.step(b[0], b[1], r, want_loss=want), batches, epochs, lr_steps, return_history)
+    return (state.prompts, history) if return_history else state.prompts
