@@ -233,6 +233,21 @@ _SIGNATURES = {
     "clipmi_prompt_train_step_scaled_bytes": (_sz, [_vp, _i, _i, _i, _i, _i, _i]),
     "clipmi_prompt_train_step_scaled": (_i, [_vp, C.POINTER(TextDgrad), _vp, _i, _vp, _vp, _i, _i, _vp, _i, _i, _vp, _i64, _vp, _i, _f, _vp, _f, _f, _i,
                                              _i, _vp, _f, _vp, _f, _f, _f, _i, _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
+    "clipmi_block_step_scaled_workspace_bytes": (_sz, [_i64]),
+    "clipmi_block_step_scaled": (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _f, _f, _i, _vp, _f, _f, _f, _i, _vp, _sz, _vp]),
+    "clipmi_cocoop_train_step_scaled_bytes": (_sz, [_vp, _i, _i, _i, _i, _i]),
+    "clipmi_cocoop_train_step_scaled": (_i, [_vp, C.POINTER(TextDgrad), _vp, _i, _vp, _vp, _i, _i, _vp, _i, _i, _vp, _i64, _vp, _i, _f, _vp, _f, _f, _i,
+                                             _vp, _f, _f, _f, _i, _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
+    "clipmi_vpt_train_step_scaled_bytes": (_sz, [_vp, _i, _i, _i, _i]),
+    "clipmi_vpt_train_step_scaled": (_i, [_vp, C.POINTER(VisionDgrad), _vp, _i, _i, _vp, _vp, _i, _i, _vp, _i, _vp, _f, _vp, _f, _f, _i, _vp, _f, _f, _f,
+                                          _i, _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
+    "clipmi_maple_train_step_scaled_bytes": (_sz, [_vp, _i, _i, _i, _i, _i]),
+    "clipmi_maple_train_step_scaled": (_i, [_vp, C.POINTER(TextDgrad), C.POINTER(VisionDgrad), _vp, _i, _vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _i, _i,
+                                            _f, _vp, _f, _f, _i, _vp, _f, _f, _f, _i, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp]),
+    "clipmi_promptsrc_train_step_scaled_bytes": (_sz, [_vp, _i, _i, _i, _i, _i, _i, _i]),
+    "clipmi_promptsrc_train_step_scaled": (_i, [_vp, C.POINTER(TextDgrad), C.POINTER(VisionDgrad), _vp, _i, _vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp,
+                                                _i, _i, _i, _i, _f, _vp, _f, _f, _i, _f, _f, _f, _vp, _f, _f, _f, _i, _vp, _vp, _vp, _sz, _vp, _sz, _vp,
+                                                _sz, _vp]),
     "clipmi_proda_embed": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "clipmi_proda_head_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "clipmi_proda_head": (_i, [_vp, _i64, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _f, _vp, _vp, _vp, _sz, _vp]),

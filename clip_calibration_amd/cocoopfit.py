@@ -20,7 +20,13 @@ shapes do not chain.
 
 UNVERIFIED, as for CoOp: Dassl is not part of this environment, so the defaults -- SGD at 0.002, batches of 1, 10 epochs, 4 context
 vectors (``CTX_INIT "a photo of a"`` in the shipped config) -- restate the reference's config and Dassl's public defaults without a run of
-the reference behind them; each is an argument.  Not covered: the reference's ``amp`` branch, ``nn.DataParallel`` over the text encoder
+the reference behind them; each is an argument.
+
+``grad_scale="dynamic"`` with ``scaler=dict(init_scale, growth_factor, backoff_factor, growth_interval)`` is the reference's ``prec ==
+"amp"`` branch (cocoop.py:249, ``torch.cuda.amp.GradScaler``) as ``coopfit`` has it: the scale lives in a block on the device, a step whose
+gradient block holds an inf or a NaN changes neither the parameters nor the momentum block, and the scale backs off and grows again.  No
+step reads anything back; ``CoCoOpFitState.scaler_state()`` does, once.  DESIGN.md "Dynamic loss scale for the block fits".  The
+reference's ``autocast`` casts differ from this path's fixed fp16 operand points (unverified).  Not covered: ``nn.DataParallel`` over the text encoder
 (one process drives one GPU), class-token positions other than ``end``.
 """
 from __future__ import annotations
@@ -35,7 +41,7 @@ import torch
 
 from . import _lib, fitloop, ops
 from ._lib import check, lib
-from .coopfit import MAX_LIVE_ROWS, _DT, _Tower, _check_batch, _check_grad_scale, _live_rows, operand_stats_dict
+from .coopfit import DYNAMIC, MAX_LIVE_ROWS, _DT, _BlockScaler, _Tower, _check_batch, _check_grad_scale, _is_dynamic, _live_rows, _scale_args, operand_stats_dict
 from .coopfit import _check_prompts as _check_coop_prompts
 from .fitloop import _need_gpu, steps_per_epoch
 
@@ -114,8 +120,9 @@ class _CoCoOpTower(_Tower):
     def reduce(self, d_embed: torch.Tensor, w2: torch.Tensor, grad_scale: float) -> torch.Tensor:
         return ops.cocoop_reduce(d_embed, self.meta[0], self.meta[1], w2, self.n_cls, self.n_ctx, grad_scale, self.grad)
 
-    def one_call_workspace(self) -> torch.Tensor:
-        need = lib.clipmi_cocoop_train_step_bytes(self.model._handle, self.n_cls, self.rows, self.B, self.H, self.n_ctx)
+    def one_call_workspace(self, scaled: bool = False) -> torch.Tensor:
+        sizer = lib.clipmi_cocoop_train_step_scaled_bytes if scaled else lib.clipmi_cocoop_train_step_bytes
+        need = sizer(self.model._handle, self.n_cls, self.rows, self.B, self.H, self.n_ctx)
         if need == 0:
             raise ValueError(f"cocoopfit: {self.N} prompts are more than the tower takes in one call")
         if self.step_ws is None or self.step_ws.numel() < need:
@@ -136,6 +143,8 @@ def gradients(clip_model, tokenized_prompts, params, features: torch.Tensor, lab
     dict ``coopfit.context_gradient`` returns."""
     who = "gradients"
     Cn, n_ctx, H, last = _check_prompts(who, clip_model, tokenized_prompts, params, seq_rows)
+    if _is_dynamic(who, grad_scale):
+        raise ValueError(f"{who}: grad_scale={DYNAMIC!r} belongs to a fit (CoCoOpFitState, fit_prompt_learner); one gradient needs a number")
     gs = _check_grad_scale(who, grad_scale)
     if not math.isfinite(logit_scale):
         raise ValueError(f"{who}: logit_scale={logit_scale} (finite)")
@@ -166,10 +175,11 @@ class CoCoOpFitState:
     not synchronise."""
 
     def __init__(self, clip_model, tokenized_prompts, params, logit_scale: float = 4.6052, momentum: float = 0.9, dampening: float = 0.0,
-                 weight_decay: float = 5e-4, nesterov: bool = False, grad_scale: float = DEFAULT_GRAD_SCALE, seq_rows: Optional[int] = None):
+                 weight_decay: float = 5e-4, nesterov: bool = False, grad_scale: float = DEFAULT_GRAD_SCALE, seq_rows: Optional[int] = None,
+                 scaler: Optional[dict] = None):
         who = "CoCoOpFitState"
         self.C, self.n_ctx, self.H, self._last = _check_prompts(who, clip_model, tokenized_prompts, params, seq_rows)
-        self.grad_scale = _check_grad_scale(who, grad_scale)
+        self.dynamic, self.grad_scale, self.scaler = _scale_args(who, grad_scale, scaler)
         fitloop.check_sgd(who, momentum, dampening, weight_decay, nesterov)
         if not math.isfinite(logit_scale):
             raise ValueError(f"{who}: logit_scale={logit_scale} (finite)")
@@ -185,6 +195,14 @@ class CoCoOpFitState:
         self.momentum, self.dampening, self.nesterov, self.weight_decay = momentum, dampening, nesterov, weight_decay
         self._towers: Dict[int, _CoCoOpTower] = {}
         self.steps = 0
+        self._scaler = _BlockScaler(self.scaler, dev) if self.dynamic else None
+
+    def scaler_state(self) -> dict:
+        """The dynamic scale's block as ``dict(scale, growth_tracker, skipped_steps, applied_steps, found_inf)`` (``found_inf``: of the
+        last step).  It waits for the steps enqueued so far: one synchronisation, the only read-back of the dynamic path."""
+        if not self.dynamic:
+            raise ValueError(f"CoCoOpFitState.scaler_state: the state was made with a static grad_scale={self.grad_scale}")
+        return self._scaler.state()
 
     def params(self) -> Dict[str, torch.Tensor]:
         """The five tensors as views of the master block (fp32, on the device), under the reference's ``state_dict`` names."""
@@ -199,7 +217,10 @@ class CoCoOpFitState:
         """One optimiser step on the batch ``features`` fp32 [B, E] and ``labels`` [B] at the rate ``lr``, as ``CoOpFitState.step`` takes
         them (a device scalar is read where it lies; a label tensor on the GPU is taken as it is -- a label outside [0, C) then makes
         the parameters NaN, it is never used as an address).  ``one_call``: the same launches through clipmi_cocoop_train_step.
-        Returns the batch loss, fp32 [1] on the device, when ``want_loss``."""
+        Returns the batch loss, fp32 [1] on the device, when ``want_loss``.  Under ``grad_scale="dynamic"`` the head and the reduce run at
+        ``grad_scale = 1``, ``d_text`` is multiplied by the device block's scale in between and clipmi_block_step_scaled decides on the
+        device whether the step is applied (one call: clipmi_cocoop_train_step_scaled); a skipped step still counts in ``steps`` and still
+        returns its loss; whether it was applied is in ``scaler_state()``."""
         who = "CoCoOpFitState.step"
         labels_d = _check_batch(who, features, labels, self.C, self.E)
         _need_gpu(features, "features")
@@ -210,7 +231,23 @@ class CoCoOpFitState:
         t, m, first = self.tower(int(features.shape[0])), self.model, self.steps == 0
         sgd = (self.momentum, self.dampening, self.weight_decay, self.nesterov)
         loss = torch.empty(1, dtype=torch.float32, device=dev)
-        if one_call:
+        if self.dynamic and one_call:
+            ws, sc = t.one_call_workspace(scaled=True), self._scaler
+            with m._launch_lock:
+                check(lib.clipmi_cocoop_train_step_scaled(m._handle, C.byref(t.dgrad[0]), t.base.data_ptr(), _DT[t.base.dtype], self.block.data_ptr(),
+                                                          None if self.buf is None else self.buf.data_ptr(), t.n_ctx, t.H, t.cls_eot.data_ptr(), t.n_cls,
+                                                          t.rows, features.data_ptr(), features.stride(0), labels_d.data_ptr(), features.shape[0],
+                                                          self.scale, sc.block.data_ptr(), *sc.args(), lr_d.data_ptr(), *map(float, sgd[:3]),
+                                                          int(bool(sgd[3])), loss.data_ptr(), None, ws.data_ptr(), ws.numel(), t.stash.data_ptr(),
+                                                          t.stash.numel(), ops._stream()),
+                      "clipmi_cocoop_train_step_scaled")
+        elif self.dynamic:
+            text = t.forward(self._views, features)
+            _, d_text = ops.cocoop_head(features, labels_d, text, self.scale, 1.0, loss)
+            ops.grad_scale_rows(d_text, self._scaler.block)
+            grad = t.reduce(t.backward(d_text), self._views[NAMES[3]], 1.0)
+            self._scaler.step(grad, self.block, self.buf, lr_d, *sgd)
+        elif one_call:
             ws = t.one_call_workspace()
             with m._launch_lock:
                 check(lib.clipmi_cocoop_train_step(m._handle, C.byref(t.dgrad[0]), t.base.data_ptr(), _DT[t.base.dtype], self.block.data_ptr(),
@@ -255,13 +292,16 @@ def init_params(clip_model, n_ctx: int = 4, ctx_init_ids: Optional[torch.Tensor]
 def fit_prompt_learner(features: torch.Tensor, labels, clip_model, tokenized_prompts, params=None, n_ctx: int = 4, logit_scale: float = 4.6052,
                        lr: float = 0.002, epochs: int = 10, batch_size: int = 1, momentum: float = 0.9, dampening: float = 0.0,
                        weight_decay: float = 5e-4, nesterov: bool = False, grad_scale: float = DEFAULT_GRAD_SCALE, seq_rows: Optional[int] = None,
-                       lr_per_epoch: Optional[Sequence[float]] = None, order=None, drop_last: bool = False, return_history: bool = False):
+                       lr_per_epoch: Optional[Sequence[float]] = None, order=None, drop_last: bool = False, return_history: bool = False,
+                       scaler: Optional[dict] = None):
     """Train CoCoOp's prompt learner on cached ``features`` fp32 [N, E] and ``labels`` [N], starting from ``params`` (a dict of the five
     tensors, not modified; None = ``init_params(clip_model, n_ctx)``).  The loop and its arguments are ``coopfit.fit_context``'s:
     ``epochs`` passes of ``torch.optim.SGD`` over batches of ``batch_size``, ``lr_per_epoch`` (None: ``cosine_warmup_schedule``),
     ``order`` [epochs, N], ``drop_last``; everything is checked on the host before the first launch and nothing synchronises until the
     one wait at the end.  Returns the fitted fp32 tensors on the device as a dict (views of one block), or ``(dict, per-step batch
-    losses)`` with ``return_history``.  The defaults are unverified restatements of the reference's config (module docstring)."""
+    losses)`` with ``return_history``.  The defaults are unverified restatements of the reference's config (module docstring).
+    ``grad_scale="dynamic"`` with ``scaler`` (module docstring): a step that overflows fp16 is skipped on the device and the scale adapts;
+    the history keeps one loss per step, skipped steps included, and the run still synchronises once."""
     who = "fit_prompt_learner"
     if params is None:
         params = init_params(clip_model, n_ctx)
@@ -272,7 +312,7 @@ def fit_prompt_learner(features: torch.Tensor, labels, clip_model, tokenized_pro
     N = features.shape[0]
     epochs, batch_size = fitloop.check_run(who, epochs, batch_size)
     fitloop.check_sgd(who, momentum, dampening, weight_decay, nesterov)
-    _check_grad_scale(who, grad_scale)
+    _scale_args(who, grad_scale, scaler)
     lab = fitloop._labels(who, labels, N, Cn)
     order = fitloop.check_order(who, order, epochs, N)
     per_epoch = steps_per_epoch(N, batch_size, drop_last)
@@ -282,7 +322,8 @@ def fit_prompt_learner(features: torch.Tensor, labels, clip_model, tokenized_pro
         out = collections.OrderedDict((k, params[k].detach().to(torch.float32).clone().to(dev if features.is_cuda else "cpu")) for k in NAMES)
         return (out, np.zeros(0, np.float32)) if return_history else out
     _need_gpu(features, "features")
-    state = CoCoOpFitState(clip_model, tokenized_prompts, params, logit_scale, momentum, dampening, weight_decay, nesterov, grad_scale, seq_rows)
+    state = CoCoOpFitState(clip_model, tokenized_prompts, params, logit_scale, momentum, dampening, weight_decay, nesterov, grad_scale, seq_rows,
+                           scaler)
     history = fitloop.run_cached(lambda f, y, r, want: state.step(f, y, r, want_loss=want), features, fitloop.labels_on(labels, lab, dev),
                                  fitloop.order_on(order, np.int64, dev), batch_size, per_epoch, epochs, lr_steps, return_history)
     return (state.params(), history) if return_history else state.params()

@@ -109,6 +109,41 @@ def _check_scaler(who: str, scaler) -> dict:
     return cfg
 
 
+def _scale_args(who: str, grad_scale, scaler):
+    """``(dynamic, grad_scale, scaler)`` after the checks every fit makes of the pair: a number with no ``scaler`` (the static path; the
+    dict is then None), or ``"dynamic"`` with the scaler's dict filled in (the number is then None)."""
+    if _is_dynamic(who, grad_scale):
+        return True, None, _check_scaler(who, scaler)
+    if scaler is not None:
+        raise ValueError(f"{who}: scaler is an argument of grad_scale={DYNAMIC!r}")
+    return False, _check_grad_scale(who, grad_scale), None
+
+
+class _BlockScaler:
+    """The dynamic loss scale of a fit whose parameters are one fp32 master block (CoCoOp, VPT, MaPLe, PromptSRC): the device block
+    (clipmi_scaler_state; only the kernels touch it once it is made), the scaler's arguments and the block step's workspace."""
+
+    def __init__(self, cfg: dict, dev):
+        self.cfg = cfg
+        self.block = ops.new_scaler_state(cfg["init_scale"], dev)
+        self.ws = None
+
+    def args(self):
+        """The three arguments every ``_scaled`` call takes behind the state block."""
+        return self.cfg["growth_factor"], self.cfg["backoff_factor"], self.cfg["growth_interval"]
+
+    def step(self, grad: torch.Tensor, params: torch.Tensor, buf: Optional[torch.Tensor], lr_d: torch.Tensor, momentum: float, dampening: float,
+             weight_decay: float, nesterov: bool) -> None:
+        """``ops.block_step_scaled`` on ``grad`` = scale * gradient: unscale, decide on the device, apply when clean."""
+        if self.ws is None:
+            self.ws = torch.empty(max(lib.clipmi_block_step_scaled_workspace_bytes(params.numel()), 256), dtype=torch.uint8, device=params.device)
+        ops.block_step_scaled(grad, self.block, params, buf, lr_d, *self.args(), momentum, dampening, weight_decay, nesterov, want_grad=False,
+                              workspace=self.ws)
+
+    def state(self) -> dict:
+        return ops.scaler_state_dict(self.block)
+
+
 def _check_prompts(who: str, clip_model, tokenized_prompts, ctx) -> Tuple[int, int, bool, int]:
     """(C, n_ctx, per_class, last EOT position) after the host-side checks of the prompt set against the model and the context."""
     L, D = int(clip_model.context_length), int(clip_model.ln_final.weight.shape[0])

@@ -467,19 +467,26 @@ size_t clipmi_cocoop_train_step_bytes(const clipmi_model* m, int C, int seq_rows
          clipmi_cocoop_head_workspace_bytes(B, C) + clipmi_cocoop_reduce_workspace_bytes(B, n_ctx, D, H);
 }
 
-int clipmi_cocoop_train_step(clipmi_model* m, const clipmi_text_dgrad* wt, const void* base, int dtype, float* params, float* buf, int n_ctx, int H,
-                             const int32_t* cls_eot, int C, int seq_rows, const float* feats, int64_t ld, const int64_t* labels, int B, float scale,
-                             float grad_scale, const float* lr, int first_step, float momentum, float dampening, float weight_decay, int nesterov, float* loss,
-                             float* grad_out, void* workspace, size_t workspace_bytes, void* stash, size_t stash_bytes, clipmi_stream_t stream) {
-  const char* who = "cocoop_train_step";
-  hipStream_t s = (hipStream_t)stream;
+size_t clipmi_cocoop_train_step_scaled_bytes(const clipmi_model* m, int C, int seq_rows, int B, int H, int n_ctx) {
+  const size_t base = clipmi_cocoop_train_step_bytes(m, C, seq_rows, B, H, n_ctx);
+  return base ? base + block_step_scaled_bytes(block_of(n_ctx, m->g.text_width, m->g.embed_dim, H).total) : 0;
+}
+
+}  // extern "C"
+
+// the one-call step, static (sc == NULL: grad_scale and first_step as given) or under the dynamic loss scale (sc: the head and the reduce run at
+// grad_scale = 1, d_text is multiplied by the block's scale in between, and the block step divides, decides and applies)
+static int cocoop_train_step(const char* who, const ScalerCall* sc, size_t need, clipmi_model* m, const clipmi_text_dgrad* wt, const void* base, int dtype,
+                             float* params, float* buf, int n_ctx, int H, const int32_t* cls_eot, int C, int seq_rows, const float* feats, int64_t ld,
+                             const int64_t* labels, int B, float scale, float grad_scale, const float* lr, int first_step, float momentum, float dampening,
+                             float weight_decay, int nesterov, float* loss, float* grad_out, void* workspace, size_t workspace_bytes, void* stash,
+                             size_t stash_bytes, hipStream_t s) {
   CLIPMI_REQUIRE(m, CLIPMI_ERR_ARG, "%s: null model", who);
   CLIPMI_REQUIRE(params && lr && loss, CLIPMI_ERR_ARG, "%s: null pointer (params, lr and loss are required)", who);
   CLIPMI_REQUIRE(H >= 1 && H <= MAX_H, CLIPMI_ERR_SHAPE, "%s: H=%d (1 .. %d)", who, H, MAX_H);
   CLIPMI_REQUIRE(n_ctx >= 1, CLIPMI_ERR_SHAPE, "%s: n_ctx=%d (>= 1)", who, n_ctx);
   CLIPMI_REQUIRE(C >= 2 && B >= 1, CLIPMI_ERR_SHAPE, "%s: C=%d (>= 2), B=%d (>= 1)", who, C, B);
   CLIPMI_REQUIRE((int64_t)B * C < (1ll << 31) / m->g.context_length, CLIPMI_ERR_SHAPE, "%s: too many prompt tokens (B * C = %lld prompts)", who, (long long)B * C);
-  const size_t need = clipmi_cocoop_train_step_bytes(m, C, seq_rows, B, H, n_ctx);
   CLIPMI_REQUIRE(need > 0, CLIPMI_ERR_SHAPE, "%s: B * C = %d prompts of %d rows are more than the tower takes", who, B * C, seq_rows);
   CLIPMI_REQUIRE(workspace_bytes >= need, CLIPMI_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, need);
   const int N = B * C;
@@ -503,7 +510,10 @@ int clipmi_cocoop_train_step(clipmi_model* m, const clipmi_text_dgrad* wt, const
   float* grad_ws = c.take<float>((size_t)k.total * 4);
   void* head_ws = c.take<char>(head_bytes);
   void* reduce_ws = c.take<char>(reduce_bytes);
-  float* grad = grad_out ? grad_out : grad_ws;
+  const size_t scaled_bytes = sc ? block_step_scaled_bytes(k.total) : 0;
+  void* scaled_ws = c.take<char>(scaled_bytes);
+  float* grad = grad_out && !sc ? grad_out : grad_ws;   // under the scaler the reduce's block is scale * gradient: grad_out gets the block step's
+  if (sc) grad_scale = 1.f;
   const float *w1 = params + k.w1, *b1 = params + k.b1, *w2 = params + k.w2, *b2 = params + k.b2;
   // every refusal of the seven stages comes before the first launch: a refused call enqueues nothing
   if (int rc = check_meta(who, feats, ld, w1, b1, w2, b2, x_n, hid, pi, B, E, H, D)) return rc;
@@ -511,14 +521,47 @@ int clipmi_cocoop_train_step(clipmi_model* m, const clipmi_text_dgrad* wt, const
   if (int rc = check_train_inputs(who, m, prompts, CLIPMI_F32, nullptr, 0, eot, seq_rows, nullptr, 0)) return rc;
   if (int rc = check_head(who, feats, ld, labels, text, B, E, C, scale, grad_scale, loss, d_text, head_ws, head_bytes)) return rc;
   if (int rc = check_reduce(who, d_embed, x_n, hid, w2, grad, B, C, L, D, E, H, n_ctx, grad_scale, reduce_ws, reduce_bytes)) return rc;
-  if (int rc = check_step(who, grad, params, buf, lr, n_ctx, D, E, H, momentum, dampening, weight_decay, nesterov)) return rc;
+  if (sc) {
+    if (int rc = check_block_step_scaled(who, grad, params, buf, grad_out, lr, k.total, sc->state, sc->growth, sc->backoff, sc->interval, momentum, dampening,
+                                         weight_decay, nesterov, scaled_ws, scaled_bytes))
+      return rc;
+  } else if (int rc = check_step(who, grad, params, buf, lr, n_ctx, D, E, H, momentum, dampening, weight_decay, nesterov)) {
+    return rc;
+  }
   if (int rc = enqueue_meta(feats, ld, w1, b1, w2, b2, x_n, hid, pi, B, E, H, D, s)) return rc;
   if (int rc = enqueue_embed(base, dtype, params, pi, cls_eot, prompts, eot, B, C, L, Lc, D, n_ctx, s)) return rc;
   if (int rc = run_train_forward(m, prompts, CLIPMI_F32, nullptr, 0, 0, eot, N, seq_rows, text, workspace, stash, s)) return rc;
   if (int rc = enqueue_head(feats, ld, labels, text, B, E, C, scale, grad_scale, loss, nullptr, d_text, head_ws, s)) return rc;
+  if (sc)
+    if (int rc = launch_grad_scale_rows(who, d_text, N, E, sc->state, s)) return rc;
   if (int rc = run_backward(m, wt, d_text, N, seq_rows, d_embed, workspace, stash, nullptr, s)) return rc;
   if (int rc = enqueue_reduce(d_embed, x_n, hid, w2, grad, B, C, L, D, E, H, n_ctx, grad_scale, reduce_ws, s)) return rc;
+  if (sc)
+    return launch_block_step_scaled(grad, params, buf, grad_out, k.total, sc->state, sc->growth, sc->backoff, sc->interval, lr, momentum, dampening,
+                                    weight_decay, nesterov, scaled_ws, s);
   return enqueue_step(grad, params, buf, n_ctx, D, E, H, lr, first_step, momentum, dampening, weight_decay, nesterov, s);
+}
+
+extern "C" {
+
+int clipmi_cocoop_train_step(clipmi_model* m, const clipmi_text_dgrad* wt, const void* base, int dtype, float* params, float* buf, int n_ctx, int H,
+                             const int32_t* cls_eot, int C, int seq_rows, const float* feats, int64_t ld, const int64_t* labels, int B, float scale,
+                             float grad_scale, const float* lr, int first_step, float momentum, float dampening, float weight_decay, int nesterov, float* loss,
+                             float* grad_out, void* workspace, size_t workspace_bytes, void* stash, size_t stash_bytes, clipmi_stream_t stream) {
+  return cocoop_train_step("cocoop_train_step", nullptr, clipmi_cocoop_train_step_bytes(m, C, seq_rows, B, H, n_ctx), m, wt, base, dtype, params, buf, n_ctx, H,
+                           cls_eot, C, seq_rows, feats, ld, labels, B, scale, grad_scale, lr, first_step, momentum, dampening, weight_decay, nesterov, loss,
+                           grad_out, workspace, workspace_bytes, stash, stash_bytes, (hipStream_t)stream);
+}
+
+int clipmi_cocoop_train_step_scaled(clipmi_model* m, const clipmi_text_dgrad* wt, const void* base, int dtype, float* params, float* buf, int n_ctx, int H,
+                                    const int32_t* cls_eot, int C, int seq_rows, const float* feats, int64_t ld, const int64_t* labels, int B, float scale,
+                                    clipmi_scaler_state* state, float growth_factor, float backoff_factor, int growth_interval, const float* lr,
+                                    float momentum, float dampening, float weight_decay, int nesterov, float* loss, float* grad_out, void* workspace,
+                                    size_t workspace_bytes, void* stash, size_t stash_bytes, clipmi_stream_t stream) {
+  const ScalerCall sc{state, growth_factor, backoff_factor, growth_interval};
+  return cocoop_train_step("cocoop_train_step_scaled", &sc, clipmi_cocoop_train_step_scaled_bytes(m, C, seq_rows, B, H, n_ctx), m, wt, base, dtype, params, buf,
+                           n_ctx, H, cls_eot, C, seq_rows, feats, ld, labels, B, scale, 1.f, lr, 0, momentum, dampening, weight_decay, nesterov, loss, grad_out,
+                           workspace, workspace_bytes, stash, stash_bytes, (hipStream_t)stream);
 }
 
 }  // extern "C"

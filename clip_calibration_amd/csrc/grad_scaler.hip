@@ -3,6 +3,7 @@
 // holds an inf or a NaN is skipped, and the scale backs off and grows again -- without a host read.  DESIGN.md "Dynamic loss scale".
 //   grad_scale_rows_kernel    x *= state->scale: the head runs at grad_scale = 1 and its d_text is multiplied here (exact for a power of two)
 //   scaled_grad_kernel        the context's unscaled gradient (ctx_step_kernel's arithmetic) into the workspace, one found-non-finite flag per workgroup
+//   block_unscale_kernel      the same for a fit whose own launches formed scale * gradient of a whole master block (clipmi_block_step_scaled)
 //   scaler_update_kernel      ONE workgroup: ORs the flags, writes the decision record of this step, applies _amp_update_scale_'s rule to the block
 //   scaled_apply_kernel       torch.optim.SGD's rule (sgd_element_fma) on every element, only when the decision record says the step is clean
 // The state block is read by the first launch and written by the second alone; the third reads the decision record only: no workgroup
@@ -50,6 +51,23 @@ __global__ __launch_bounds__(THREADS) void scaled_grad_kernel(const float* __res
   int bad = 0;
   if (idx < total) {
     const float g = ctx_grad_element(d_embed, idx, C, L, D, n_ctx, per_class, 1.f / st->scale);
+    w.grad[idx] = g;
+    if (grad_out) grad_out[idx] = g;
+    bad = !isfinite(g);
+  }
+  bad = __syncthreads_or(bad);
+  if (threadIdx.x == 0) w.flags[blockIdx.x] = bad ? 1 : 0;
+}
+
+// one thread per element of a master block: g = grad / scale for a gradient that the fit's own launches formed at grad_scale = 1 from a
+// backward carrying scale * gradient (CoCoOp, VPT, MaPLe, PromptSRC); the flag as above.  grad_out may be grad itself: an element is read
+// and written by one thread
+__global__ __launch_bounds__(THREADS) void block_unscale_kernel(const float* grad, float* grad_out, int64_t total, const clipmi_scaler_state* __restrict__ st,
+                                                                ScaledWs w) {
+  const int64_t idx = (int64_t)blockIdx.x * THREADS + threadIdx.x;
+  int bad = 0;
+  if (idx < total) {
+    const float g = grad[idx] * (1.f / st->scale);
     w.grad[idx] = g;
     if (grad_out) grad_out[idx] = g;
     bad = !isfinite(g);
@@ -138,6 +156,9 @@ int launch_scaled_step(const float* d_embed, float* ctx, float* buf, float* grad
   return check_launch("scaled_apply_kernel");
 }
 
+}  // namespace
+
+// ---- what the fits' one-call steps share (model.h)
 int launch_grad_scale_rows(const char* who, float* x, int rows, int cols, const clipmi_scaler_state* st, hipStream_t s) {
   CLIPMI_REQUIRE(x && st, CLIPMI_ERR_ARG, "%s: null pointer", who);
   CLIPMI_REQUIRE(rows >= 1 && cols >= 1, CLIPMI_ERR_SHAPE, "%s: rows=%d cols=%d", who, rows, cols);
@@ -146,7 +167,41 @@ int launch_grad_scale_rows(const char* who, float* x, int rows, int cols, const 
   return check_launch("grad_scale_rows_kernel");
 }
 
-}  // namespace
+size_t block_step_scaled_bytes(int64_t total) { return total >= 1 && total < (1ll << 31) * THREADS ? scaled_step_bytes(total) : 0; }
+
+// everything clipmi_block_step_scaled refuses, before anything is launched
+int check_block_step_scaled(const char* who, const float* grad, const float* params, const float* buf, const float* grad_out, const float* lr, int64_t total,
+                            const clipmi_scaler_state* st, float growth, float backoff, int growth_interval, float momentum, float dampening,
+                            float weight_decay, int nesterov, const void* workspace, size_t workspace_bytes) {
+  CLIPMI_REQUIRE(grad && params && lr && workspace, CLIPMI_ERR_ARG, "%s: null pointer (grad, params, lr and the workspace are required)", who);
+  CLIPMI_REQUIRE(((uintptr_t)grad | (uintptr_t)params | (uintptr_t)buf | (uintptr_t)grad_out | (uintptr_t)lr) % 4 == 0, CLIPMI_ERR_ARG,
+                 "%s: grad, params, buf, grad_out and lr must be 4-byte aligned", who);
+  if (int rc = check_scaler(who, st, growth, backoff, growth_interval)) return rc;
+  CLIPMI_REQUIRE(total >= 1, CLIPMI_ERR_SHAPE, "%s: total=%lld (>= 1)", who, (long long)total);
+  if (int rc = check_sgd(who, momentum, dampening, weight_decay, nesterov)) return rc;
+  CLIPMI_REQUIRE(momentum == 0.f || buf, CLIPMI_ERR_ARG, "%s: null pointer (a momentum needs the buffer)", who);
+  CLIPMI_REQUIRE(total < (1ll << 31) * THREADS, CLIPMI_ERR_SHAPE, "%s: block too large", who);
+  CLIPMI_REQUIRE((uintptr_t)workspace % 256 == 0, CLIPMI_ERR_ARG, "%s: the workspace must be 256-byte aligned", who);
+  CLIPMI_REQUIRE(workspace_bytes >= scaled_step_bytes(total), CLIPMI_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes,
+                 scaled_step_bytes(total));
+  return CLIPMI_OK;
+}
+
+// the three launches; every argument has been checked
+int launch_block_step_scaled(const float* grad, float* params, float* buf, float* grad_out, int64_t total, clipmi_scaler_state* st, float growth, float backoff,
+                             int growth_interval, const float* lr, float momentum, float dampening, float weight_decay, int nesterov, void* workspace,
+                             hipStream_t s) {
+  const ScaledWs w = scaled_carve(workspace, total);
+  const int64_t blocks = grad_blocks(total);
+  hipLaunchKernelGGL(block_unscale_kernel, dim3((unsigned)blocks), dim3(THREADS), 0, s, grad, grad_out, total, (const clipmi_scaler_state*)st, w);
+  if (int rc = check_launch("block_unscale_kernel")) return rc;
+  hipLaunchKernelGGL(scaler_update_kernel, dim3(1), dim3(THREADS), 0, s, w, blocks, st, growth, backoff, growth_interval);
+  if (int rc = check_launch("scaler_update_kernel")) return rc;
+  hipLaunchKernelGGL(scaled_apply_kernel, dim3((unsigned)blocks), dim3(THREADS), 0, s, w, params, buf, total, lr,
+                     make_sgd_args(momentum, dampening, weight_decay, nesterov, 0));
+  return check_launch("scaled_apply_kernel");
+}
+
 }  // namespace clipmi
 
 using namespace clipmi;
@@ -173,6 +228,18 @@ int clipmi_ctx_step_scaled(const float* d_embed, float* ctx, float* buf, float* 
     return rc;
   return launch_scaled_step(d_embed, ctx, buf, grad_out, C, L, D, n_ctx, per_class, total, state, growth_factor, backoff_factor, growth_interval, lr, momentum,
                             dampening, weight_decay, nesterov, workspace, (hipStream_t)stream);
+}
+
+size_t clipmi_block_step_scaled_workspace_bytes(int64_t total) { return block_step_scaled_bytes(total); }
+
+int clipmi_block_step_scaled(const float* grad, float* params, float* buf, float* grad_out, int64_t total, clipmi_scaler_state* state, float growth_factor,
+                             float backoff_factor, int growth_interval, const float* lr, float momentum, float dampening, float weight_decay, int nesterov,
+                             void* workspace, size_t workspace_bytes, clipmi_stream_t stream) {
+  if (int rc = check_block_step_scaled("block_step_scaled", grad, params, buf, grad_out, lr, total, state, growth_factor, backoff_factor, growth_interval,
+                                       momentum, dampening, weight_decay, nesterov, workspace, workspace_bytes))
+    return rc;
+  return launch_block_step_scaled(grad, params, buf, grad_out, total, state, growth_factor, backoff_factor, growth_interval, lr, momentum, dampening,
+                                  weight_decay, nesterov, workspace, (hipStream_t)stream);
 }
 
 size_t clipmi_prompt_train_step_scaled_bytes(const clipmi_model* m, int n_prompts, int seq_rows, int B, int mode, int n_ctx, int ctx_per_class) {

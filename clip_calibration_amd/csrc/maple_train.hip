@@ -198,13 +198,24 @@ size_t clipmi_maple_train_step_bytes(const clipmi_model* m, int n_prompts, int s
          clipmi_maple_head_workspace_bytes(B, E, n_prompts) + step_bytes(n_ctx, depth, Dt);
 }
 
-int clipmi_maple_train_step(clipmi_model* m, const clipmi_text_dgrad* wt, const clipmi_vision_dgrad* wv, const void* prompts, int dtype, const int32_t* eot,
-                            int n_prompts, int seq_rows, const void* image, int image_dtype, int B, const int64_t* labels, float* block, float* buf,
-                            int n_ctx, int depth, float scale, float grad_scale, const float* lr, int first_step, float momentum, float dampening,
-                            float weight_decay, int nesterov, float* loss, float* grad_out, void* workspace, size_t workspace_bytes, void* text_stash,
-                            size_t text_stash_bytes, void* vision_stash, size_t vision_stash_bytes, clipmi_stream_t stream) {
-  const char* who = "maple_train_step";
-  hipStream_t s = (hipStream_t)stream;
+// the static call's workspace | the block of scale * gradient that clipmi_maple_step leaves with apply = 0 | clipmi_block_step_scaled's
+size_t clipmi_maple_train_step_scaled_bytes(const clipmi_model* m, int n_prompts, int seq_rows, int B, int n_ctx, int depth) {
+  const size_t base = clipmi_maple_train_step_bytes(m, n_prompts, seq_rows, B, n_ctx, depth);
+  if (!base) return 0;
+  const int64_t total = MapleShape{n_ctx, depth, m->g.text_width, m->g.vision_width}.total();
+  const size_t step = block_step_scaled_bytes(total);
+  return step ? base + align256((size_t)total * 4) + step : 0;
+}
+
+}  // extern "C"
+
+// MaPLe's one-call step, static (sc == NULL) or under the dynamic loss scale (sc: the head at grad_scale = 1, d_text and d_feats times the block's
+// scale, both backwards, the step's two launches at grad_scale = 1 without applying, and the block step on the gradient they leave)
+static int maple_train_step(const char* who, const ScalerCall* sc, size_t need, clipmi_model* m, const clipmi_text_dgrad* wt, const clipmi_vision_dgrad* wv,
+                            const void* prompts, int dtype, const int32_t* eot, int n_prompts, int seq_rows, const void* image, int image_dtype, int B,
+                            const int64_t* labels, float* block, float* buf, int n_ctx, int depth, float scale, float grad_scale, const float* lr,
+                            int first_step, float momentum, float dampening, float weight_decay, int nesterov, float* loss, float* grad_out, void* workspace,
+                            size_t workspace_bytes, void* text_stash, size_t text_stash_bytes, void* vision_stash, size_t vision_stash_bytes, hipStream_t s) {
   const int C = n_prompts;
   CLIPMI_REQUIRE(m, CLIPMI_ERR_ARG, "%s: null model", who);
   CLIPMI_REQUIRE(C >= 2 && B >= 1, CLIPMI_ERR_SHAPE, "%s: n_prompts=%d (>= 2), B=%d (>= 1)", who, C, B);
@@ -214,7 +225,6 @@ int clipmi_maple_train_step(clipmi_model* m, const clipmi_text_dgrad* wt, const 
   size_t tws = 0, vws = 0;
   if (int rc = clipmi_text_train_bytes(m, C, seq_rows, &tws, nullptr)) return rc;
   if (int rc = clipmi_vision_train_bytes(m, B, n_ctx, &vws, nullptr)) return rc;
-  const size_t need = clipmi_maple_train_step_bytes(m, C, seq_rows, B, n_ctx, depth);
   CLIPMI_REQUIRE(need > 0 && workspace_bytes >= need, CLIPMI_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, need);
   char* vision_ws = static_cast<char*>(workspace) + tws;
   if (int rc = check_train_call(who, m, C, workspace, tws, text_stash, text_stash_bytes, seq_rows)) return rc;
@@ -226,7 +236,8 @@ int clipmi_maple_train_step(clipmi_model* m, const clipmi_text_dgrad* wt, const 
   if (int rc = check_vision_dgrad(who, m, wv)) return rc;
   CLIPMI_REQUIRE(image_dtype == CLIPMI_F16 || image_dtype == CLIPMI_F32, CLIPMI_ERR_ARG, "%s: image dtype %d", who, image_dtype);
   CLIPMI_REQUIRE(std::isfinite(scale), CLIPMI_ERR_ARG, "%s: scale=%g (finite)", who, scale);
-  if (int rc = check_step_args(who, block, buf, grad_out, 1, lr, grad_scale, momentum, dampening, weight_decay, nesterov)) return rc;
+  if (!sc)
+    if (int rc = check_step_args(who, block, buf, grad_out, 1, lr, grad_scale, momentum, dampening, weight_decay, nesterov)) return rc;
   const size_t head_bytes = clipmi_maple_head_workspace_bytes(B, E, C), st_bytes = step_bytes(n_ctx, depth, Dt);
   Carver c(vision_ws + vws);
   float* text = c.take<float>((size_t)C * E * 4);
@@ -239,15 +250,60 @@ int clipmi_maple_train_step(clipmi_model* m, const clipmi_text_dgrad* wt, const 
   float* d_vis = c.take<float>((size_t)m->g.vision_layers * n_ctx * Dv * 4);
   void* head_ws = c.take<char>(head_bytes);
   void* step_ws = c.take<char>(st_bytes);
+  const int64_t total = MapleShape{n_ctx, depth, Dt, Dv}.total();
+  const size_t scaled_bytes = sc ? block_step_scaled_bytes(total) : 0;
+  float* scaled_grad = c.take<float>(sc ? (size_t)total * 4 : 0);
+  void* scaled_ws = c.take<char>(scaled_bytes);
+  if (sc)   // the scaler's and the optimiser's refusals come ahead of the first launch
+    if (int rc = check_block_step_scaled(who, scaled_grad, block, buf, grad_out, lr, total, sc->state, sc->growth, sc->backoff, sc->interval, momentum,
+                                         dampening, weight_decay, nesterov, scaled_ws, scaled_bytes))
+      return rc;
   const float* deep = block + (int64_t)n_ctx * Dt;
   if (int rc = launch_couple(who, block, n_ctx, depth, Dt, Dv, vis, s)) return rc;
   if (int rc = run_train_forward(m, prompts, dtype, block, n_ctx, 0, eot, C, seq_rows, text, workspace, text_stash, s, deep, depth - 1)) return rc;
   if (int rc = run_vision_train_forward(m, image, image_dtype, B, vis, n_ctx, depth, feats, vision_ws, vision_stash, s)) return rc;
   if (int rc = launch_maple_head(who, feats, E, labels, text, B, E, C, scale, grad_scale, loss, d_feats, d_text, nullptr, head_ws, head_bytes, s)) return rc;
+  if (sc) {
+    if (int rc = launch_grad_scale_rows(who, d_text, C, E, sc->state, s)) return rc;
+    if (int rc = launch_grad_scale_rows(who, d_feats, B, E, sc->state, s)) return rc;
+  }
   if (int rc = run_backward(m, wt, d_text, C, seq_rows, d_embed, workspace, text_stash, nullptr, s, n_ctx, depth - 1, d_deep)) return rc;
   if (int rc = run_vision_backward(m, wv, d_feats, B, n_ctx, depth, d_vis, vision_ws, vision_stash, nullptr, s)) return rc;
+  if (sc) {
+    if (int rc = launch_step(who, d_embed, d_deep, d_vis, block, nullptr, scaled_grad, 0, C, L, n_ctx, depth, Dt, Dv, 1.f, nullptr, 0, momentum, dampening,
+                             weight_decay, nesterov, step_ws, st_bytes, s))
+      return rc;
+    return launch_block_step_scaled(scaled_grad, block, buf, grad_out, total, sc->state, sc->growth, sc->backoff, sc->interval, lr, momentum, dampening,
+                                    weight_decay, nesterov, scaled_ws, s);
+  }
   return launch_step(who, d_embed, d_deep, d_vis, block, buf, grad_out, 1, C, L, n_ctx, depth, Dt, Dv, grad_scale, lr, first_step, momentum, dampening,
                      weight_decay, nesterov, step_ws, st_bytes, s);
+}
+
+extern "C" {
+
+int clipmi_maple_train_step(clipmi_model* m, const clipmi_text_dgrad* wt, const clipmi_vision_dgrad* wv, const void* prompts, int dtype, const int32_t* eot,
+                            int n_prompts, int seq_rows, const void* image, int image_dtype, int B, const int64_t* labels, float* block, float* buf,
+                            int n_ctx, int depth, float scale, float grad_scale, const float* lr, int first_step, float momentum, float dampening,
+                            float weight_decay, int nesterov, float* loss, float* grad_out, void* workspace, size_t workspace_bytes, void* text_stash,
+                            size_t text_stash_bytes, void* vision_stash, size_t vision_stash_bytes, clipmi_stream_t stream) {
+  return maple_train_step("maple_train_step", nullptr, clipmi_maple_train_step_bytes(m, n_prompts, seq_rows, B, n_ctx, depth), m, wt, wv, prompts, dtype, eot,
+                          n_prompts, seq_rows, image, image_dtype, B, labels, block, buf, n_ctx, depth, scale, grad_scale, lr, first_step, momentum, dampening,
+                          weight_decay, nesterov, loss, grad_out, workspace, workspace_bytes, text_stash, text_stash_bytes, vision_stash, vision_stash_bytes,
+                          (hipStream_t)stream);
+}
+
+int clipmi_maple_train_step_scaled(clipmi_model* m, const clipmi_text_dgrad* wt, const clipmi_vision_dgrad* wv, const void* prompts, int dtype,
+                                   const int32_t* eot, int n_prompts, int seq_rows, const void* image, int image_dtype, int B, const int64_t* labels,
+                                   float* block, float* buf, int n_ctx, int depth, float scale, clipmi_scaler_state* state, float growth_factor,
+                                   float backoff_factor, int growth_interval, const float* lr, float momentum, float dampening, float weight_decay,
+                                   int nesterov, float* loss, float* grad_out, void* workspace, size_t workspace_bytes, void* text_stash,
+                                   size_t text_stash_bytes, void* vision_stash, size_t vision_stash_bytes, clipmi_stream_t stream) {
+  const ScalerCall sc{state, growth_factor, backoff_factor, growth_interval};
+  return maple_train_step("maple_train_step_scaled", &sc, clipmi_maple_train_step_scaled_bytes(m, n_prompts, seq_rows, B, n_ctx, depth), m, wt, wv, prompts,
+                          dtype, eot, n_prompts, seq_rows, image, image_dtype, B, labels, block, buf, n_ctx, depth, scale, 1.f, lr, 0, momentum, dampening,
+                          weight_decay, nesterov, loss, grad_out, workspace, workspace_bytes, text_stash, text_stash_bytes, vision_stash, vision_stash_bytes,
+                          (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -139,4 +139,20 @@ int launch_promptsrc_head(const char* who, const float* feats, int64_t ld, const
                           const float* teacher, int B, int E, int C, float scale, float grad_scale, float w_text, float w_image, float w_logit,
                           float* losses, float* d_feats, float* d_text, half_t* d_text16, void* workspace, size_t workspace_bytes, hipStream_t s);
 
+// grad_scaler.hip: the dynamic loss scale's launches for the fits' one-call steps.  A ScalerCall is what a `_scaled` step is given in
+// grad_scale's place: the device block and torch.cuda.amp.GradScaler's three arguments
+struct ScalerCall {
+  clipmi_scaler_state* state;
+  float growth, backoff;
+  int interval;
+};
+int launch_grad_scale_rows(const char* who, float* x, int rows, int cols, const clipmi_scaler_state* st, hipStream_t s);
+size_t block_step_scaled_bytes(int64_t total);   // 0 for a total the step refuses
+int check_block_step_scaled(const char* who, const float* grad, const float* params, const float* buf, const float* grad_out, const float* lr, int64_t total,
+                            const clipmi_scaler_state* st, float growth, float backoff, int growth_interval, float momentum, float dampening,
+                            float weight_decay, int nesterov, const void* workspace, size_t workspace_bytes);
+int launch_block_step_scaled(const float* grad, float* params, float* buf, float* grad_out, int64_t total, clipmi_scaler_state* st, float growth, float backoff,
+                             int growth_interval, const float* lr, float momentum, float dampening, float weight_decay, int nesterov, void* workspace,
+                             hipStream_t s);
+
 }  // namespace clipmi

@@ -883,14 +883,21 @@ size_t clipmi_vpt_train_step_bytes(const clipmi_model* m, int B, int n_ctx, int 
          clipmi_vpt_head_workspace_bytes(B, m->g.embed_dim, C);
 }
 
-int clipmi_vpt_train_step(clipmi_model* m, const clipmi_vision_dgrad* wt, const void* image, int image_dtype, int B, float* prompts, float* buf, int n_ctx,
-                          int depth, const float* text, int C, const int64_t* labels, float scale, float grad_scale, const float* lr, int first_step,
-                          float momentum, float dampening, float weight_decay, int nesterov, float* loss, float* grad_out, void* workspace,
-                          size_t workspace_bytes, void* stash, size_t stash_bytes, clipmi_stream_t stream) {
-  const char* who = "vpt_train_step";
-  hipStream_t s = (hipStream_t)stream;
+size_t clipmi_vpt_train_step_scaled_bytes(const clipmi_model* m, int B, int n_ctx, int depth, int C) {
+  const size_t base = clipmi_vpt_train_step_bytes(m, B, n_ctx, C);
+  const size_t step = base && depth >= 1 && depth <= m->g.vision_layers ? block_step_scaled_bytes((int64_t)depth * n_ctx * m->g.vision_width) : 0;
+  return base && step ? base + step : 0;
+}
+
+}  // extern "C"
+
+// VPT's one-call step, static (sc == NULL) or under the dynamic loss scale (sc: the head at grad_scale = 1, d_feats times the block's scale, the
+// backward, and the block step on d_prompts, which is scale * gradient as it stands)
+static int vpt_train_step(const char* who, const ScalerCall* sc, size_t need, clipmi_model* m, const clipmi_vision_dgrad* wt, const void* image, int image_dtype,
+                          int B, float* prompts, float* buf, int n_ctx, int depth, const float* text, int C, const int64_t* labels, float scale,
+                          float grad_scale, const float* lr, int first_step, float momentum, float dampening, float weight_decay, int nesterov, float* loss,
+                          float* grad_out, void* workspace, size_t workspace_bytes, void* stash, size_t stash_bytes, hipStream_t s) {
   CLIPMI_REQUIRE(B >= 1 && C >= 2, CLIPMI_ERR_SHAPE, "%s: B=%d C=%d", who, B, C);
-  const size_t need = clipmi_vpt_train_step_bytes(m, B, n_ctx, C);
   size_t tower = 0;
   if (int rc = clipmi_vision_train_bytes(m, B, n_ctx, &tower, nullptr)) return rc;
   CLIPMI_REQUIRE(workspace_bytes >= need, CLIPMI_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, need);
@@ -905,10 +912,47 @@ int clipmi_vpt_train_step(clipmi_model* m, const clipmi_vision_dgrad* wt, const 
   float* d_feats = c.take<float>((size_t)B * E * 4);
   float* d_prompts = c.take<float>((size_t)m->g.vision_layers * n_ctx * D * 4);
   void* head_ws = c.take<char>(head_bytes);
+  const int64_t total = (int64_t)depth * n_ctx * D;
+  const size_t scaled_bytes = sc ? block_step_scaled_bytes(total) : 0;
+  void* scaled_ws = c.take<char>(scaled_bytes);
+  if (sc) {   // the scaler's and the optimiser's refusals come ahead of the first launch
+    CLIPMI_REQUIRE(need > 0, CLIPMI_ERR_SHAPE, "%s: B=%d n_ctx=%d depth=%d C=%d", who, B, n_ctx, depth, C);
+    CLIPMI_REQUIRE(std::isfinite(scale), CLIPMI_ERR_ARG, "%s: scale=%g (finite)", who, scale);
+    if (int rc = check_block_step_scaled(who, d_prompts, prompts, buf, grad_out, lr, total, sc->state, sc->growth, sc->backoff, sc->interval, momentum,
+                                         dampening, weight_decay, nesterov, scaled_ws, scaled_bytes))
+      return rc;
+  }
   if (int rc = run_vision_train_forward(m, image, image_dtype, B, prompts, n_ctx, depth, feats, workspace, stash, s)) return rc;
   if (int rc = launch_vpt_head(who, feats, E, labels, text, B, E, C, scale, grad_scale, loss, d_feats, head_ws, head_bytes, s)) return rc;
+  if (sc)
+    if (int rc = launch_grad_scale_rows(who, d_feats, B, E, sc->state, s)) return rc;
   if (int rc = run_vision_backward(m, wt, d_feats, B, n_ctx, depth, d_prompts, workspace, stash, nullptr, s)) return rc;
+  if (sc)
+    return launch_block_step_scaled(d_prompts, prompts, buf, grad_out, total, sc->state, sc->growth, sc->backoff, sc->interval, lr, momentum, dampening,
+                                    weight_decay, nesterov, scaled_ws, s);
   return launch_vpt_step(who, d_prompts, prompts, buf, grad_out, depth, n_ctx, D, grad_scale, lr, first_step, momentum, dampening, weight_decay, nesterov, s);
+}
+
+extern "C" {
+
+int clipmi_vpt_train_step(clipmi_model* m, const clipmi_vision_dgrad* wt, const void* image, int image_dtype, int B, float* prompts, float* buf, int n_ctx,
+                          int depth, const float* text, int C, const int64_t* labels, float scale, float grad_scale, const float* lr, int first_step,
+                          float momentum, float dampening, float weight_decay, int nesterov, float* loss, float* grad_out, void* workspace,
+                          size_t workspace_bytes, void* stash, size_t stash_bytes, clipmi_stream_t stream) {
+  return vpt_train_step("vpt_train_step", nullptr, clipmi_vpt_train_step_bytes(m, B, n_ctx, C), m, wt, image, image_dtype, B, prompts, buf, n_ctx, depth, text, C,
+                        labels, scale, grad_scale, lr, first_step, momentum, dampening, weight_decay, nesterov, loss, grad_out, workspace, workspace_bytes, stash,
+                        stash_bytes, (hipStream_t)stream);
+}
+
+int clipmi_vpt_train_step_scaled(clipmi_model* m, const clipmi_vision_dgrad* wt, const void* image, int image_dtype, int B, float* prompts, float* buf,
+                                 int n_ctx, int depth, const float* text, int C, const int64_t* labels, float scale, clipmi_scaler_state* state,
+                                 float growth_factor, float backoff_factor, int growth_interval, const float* lr, float momentum, float dampening,
+                                 float weight_decay, int nesterov, float* loss, float* grad_out, void* workspace, size_t workspace_bytes, void* stash,
+                                 size_t stash_bytes, clipmi_stream_t stream) {
+  const ScalerCall sc{state, growth_factor, backoff_factor, growth_interval};
+  return vpt_train_step("vpt_train_step_scaled", &sc, clipmi_vpt_train_step_scaled_bytes(m, B, n_ctx, depth, C), m, wt, image, image_dtype, B, prompts, buf, n_ctx,
+                        depth, text, C, labels, scale, 1.f, lr, 0, momentum, dampening, weight_decay, nesterov, loss, grad_out, workspace, workspace_bytes, stash,
+                        stash_bytes, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -169,13 +169,25 @@ size_t clipmi_promptsrc_train_step_bytes(const clipmi_model* m, int n_prompts, i
   return w.bytes;
 }
 
-int clipmi_promptsrc_train_step(clipmi_model* m, const clipmi_text_dgrad* wt, const clipmi_vision_dgrad* wv, const void* prompts, int dtype, const int32_t* eot,
-                                int n_prompts, int seq_rows, const void* image, int image_dtype, int B, const int64_t* labels, const float* teacher,
-                                float* block, float* buf, int nt, int dt, int nv, int dv, float scale, float grad_scale, float w_text, float w_image,
-                                float w_logit, const float* lr, int first_step, float momentum, float dampening, float weight_decay, int nesterov,
-                                float* losses, float* grad_out, void* workspace, size_t workspace_bytes, void* text_stash, size_t text_stash_bytes,
-                                void* vision_stash, size_t vision_stash_bytes, clipmi_stream_t stream) {
-  const char* who = "promptsrc_train_step";
+// the static call's workspace | the block of scale * gradient that clipmi_promptsrc_step leaves with apply = 0 | clipmi_block_step_scaled's
+size_t clipmi_promptsrc_train_step_scaled_bytes(const clipmi_model* m, int n_prompts, int seq_rows, int B, int nt, int dt, int nv, int dv) {
+  const size_t base = clipmi_promptsrc_train_step_bytes(m, n_prompts, seq_rows, B, nt, dt, nv);
+  if (!base || dv < 1) return 0;
+  const int64_t total = SrcShape{nt, dt, m->g.text_width, nv, dv, m->g.vision_width}.total();
+  const size_t step = block_step_scaled_bytes(total);
+  return step ? base + align256((size_t)total * 4) + step : 0;
+}
+
+}  // extern "C"
+
+// PromptSRC's and IVLP's one-call step, static (sc == NULL) or under the dynamic loss scale (sc: the head at grad_scale = 1, d_text and d_feats
+// times the block's scale, both backwards, the step's launch at grad_scale = 1 without applying, and the block step on the gradient it leaves)
+static int promptsrc_train_step(const char* who, const ScalerCall* sc, clipmi_model* m, const clipmi_text_dgrad* wt, const clipmi_vision_dgrad* wv,
+                                const void* prompts, int dtype, const int32_t* eot, int n_prompts, int seq_rows, const void* image, int image_dtype, int B,
+                                const int64_t* labels, const float* teacher, float* block, float* buf, int nt, int dt, int nv, int dv, float scale,
+                                float grad_scale, float w_text, float w_image, float w_logit, const float* lr, int first_step, float momentum, float dampening,
+                                float weight_decay, int nesterov, float* losses, float* grad_out, void* workspace, size_t workspace_bytes, void* text_stash,
+                                size_t text_stash_bytes, void* vision_stash, size_t vision_stash_bytes, clipmi_stream_t stream) {
   hipStream_t s = (hipStream_t)stream;
   const int C = n_prompts;
   CLIPMI_REQUIRE(m, CLIPMI_ERR_ARG, "%s: null model", who);
@@ -185,7 +197,13 @@ int clipmi_promptsrc_train_step(clipmi_model* m, const clipmi_text_dgrad* wt, co
   if (int rc = check_shape(who, nt, dt, Dt, nv, dv, Dv)) return rc;
   StepWs w;
   if (int rc = carve_step(m, workspace, C, seq_rows, B, nt, dt, nv, &w)) return rc;
-  CLIPMI_REQUIRE(workspace && workspace_bytes >= w.bytes, CLIPMI_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, w.bytes);
+  const int64_t total = SrcShape{nt, dt, Dt, nv, dv, Dv}.total();
+  const size_t scaled_bytes = sc ? block_step_scaled_bytes(total) : 0;
+  Carver behind(workspace ? static_cast<char*>(workspace) + w.bytes : nullptr);
+  float* scaled_grad = behind.take<float>(sc ? (size_t)total * 4 : 0);
+  void* scaled_ws = behind.take<char>(scaled_bytes);
+  const size_t need = w.bytes + behind.off;
+  CLIPMI_REQUIRE(workspace && workspace_bytes >= need, CLIPMI_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, need);
   if (int rc = check_train_call(who, m, C, workspace, w.tws, text_stash, text_stash_bytes, seq_rows)) return rc;
   if (int rc = check_deep(who, m, nt, dt - 1, block, seq_rows)) return rc;
   if (int rc = check_train_inputs(who, m, prompts, dtype, block, nt, eot, seq_rows, nullptr, 0)) return rc;
@@ -194,7 +212,13 @@ int clipmi_promptsrc_train_step(clipmi_model* m, const clipmi_text_dgrad* wt, co
   if (int rc = check_vision_train_call(who, m, B, nv, dv, w.vision, w.vws, vision_stash, vision_stash_bytes)) return rc;
   if (int rc = check_vision_dgrad(who, m, wv)) return rc;
   CLIPMI_REQUIRE(image_dtype == CLIPMI_F16 || image_dtype == CLIPMI_F32, CLIPMI_ERR_ARG, "%s: image dtype %d", who, image_dtype);
-  if (int rc = check_step_args(who, block, buf, grad_out, 1, lr, grad_scale, momentum, dampening, weight_decay, nesterov)) return rc;
+  if (sc) {
+    if (int rc = check_block_step_scaled(who, scaled_grad, block, buf, grad_out, lr, total, sc->state, sc->growth, sc->backoff, sc->interval, momentum,
+                                         dampening, weight_decay, nesterov, scaled_ws, scaled_bytes))
+      return rc;
+  } else if (int rc = check_step_args(who, block, buf, grad_out, 1, lr, grad_scale, momentum, dampening, weight_decay, nesterov)) {
+    return rc;
+  }
   if (int rc = check_promptsrc_head(who, w.feats, E, w.zs, labels, w.text, teacher, B, E, C, scale, grad_scale, w_text, w_image, w_logit, losses, w.d_feats,
                                     w.d_text, w.head, w.head_bytes))
     return rc;
@@ -208,10 +232,47 @@ int clipmi_promptsrc_train_step(clipmi_model* m, const clipmi_text_dgrad* wt, co
   if (int rc = launch_promptsrc_head(who, w.feats, E, w.zs, labels, w.text, teacher, B, E, C, scale, grad_scale, w_text, w_image, w_logit, losses, w.d_feats,
                                      w.d_text, nullptr, w.head, w.head_bytes, s))
     return rc;
+  if (sc) {
+    if (int rc = launch_grad_scale_rows(who, w.d_text, C, E, sc->state, s)) return rc;
+    if (int rc = launch_grad_scale_rows(who, w.d_feats, B, E, sc->state, s)) return rc;
+  }
   if (int rc = run_backward(m, wt, w.d_text, C, seq_rows, w.d_embed, workspace, text_stash, nullptr, s, nt, dt - 1, w.d_deep)) return rc;
   if (int rc = run_vision_backward(m, wv, w.d_feats, B, nv, dv, w.d_vis, w.vision, vision_stash, nullptr, s)) return rc;
+  if (sc) {
+    if (int rc = launch_step(who, w.d_embed, w.d_deep, w.d_vis, block, nullptr, scaled_grad, 0, C, L, nt, dt, Dt, nv, dv, Dv, 1.f, nullptr, 0, momentum,
+                             dampening, weight_decay, nesterov, s))
+      return rc;
+    return launch_block_step_scaled(scaled_grad, block, buf, grad_out, total, sc->state, sc->growth, sc->backoff, sc->interval, lr, momentum, dampening,
+                                    weight_decay, nesterov, scaled_ws, s);
+  }
   return launch_step(who, w.d_embed, w.d_deep, w.d_vis, block, buf, grad_out, 1, C, L, nt, dt, Dt, nv, dv, Dv, grad_scale, lr, first_step, momentum, dampening,
                      weight_decay, nesterov, s);
+}
+
+extern "C" {
+
+int clipmi_promptsrc_train_step(clipmi_model* m, const clipmi_text_dgrad* wt, const clipmi_vision_dgrad* wv, const void* prompts, int dtype, const int32_t* eot,
+                                int n_prompts, int seq_rows, const void* image, int image_dtype, int B, const int64_t* labels, const float* teacher,
+                                float* block, float* buf, int nt, int dt, int nv, int dv, float scale, float grad_scale, float w_text, float w_image,
+                                float w_logit, const float* lr, int first_step, float momentum, float dampening, float weight_decay, int nesterov,
+                                float* losses, float* grad_out, void* workspace, size_t workspace_bytes, void* text_stash, size_t text_stash_bytes,
+                                void* vision_stash, size_t vision_stash_bytes, clipmi_stream_t stream) {
+  return promptsrc_train_step("promptsrc_train_step", nullptr, m, wt, wv, prompts, dtype, eot, n_prompts, seq_rows, image, image_dtype, B, labels, teacher, block,
+                              buf, nt, dt, nv, dv, scale, grad_scale, w_text, w_image, w_logit, lr, first_step, momentum, dampening, weight_decay, nesterov,
+                              losses, grad_out, workspace, workspace_bytes, text_stash, text_stash_bytes, vision_stash, vision_stash_bytes, stream);
+}
+
+int clipmi_promptsrc_train_step_scaled(clipmi_model* m, const clipmi_text_dgrad* wt, const clipmi_vision_dgrad* wv, const void* prompts, int dtype,
+                                       const int32_t* eot, int n_prompts, int seq_rows, const void* image, int image_dtype, int B, const int64_t* labels,
+                                       const float* teacher, float* block, float* buf, int nt, int dt, int nv, int dv, float scale,
+                                       clipmi_scaler_state* state, float growth_factor, float backoff_factor, int growth_interval, float w_text,
+                                       float w_image, float w_logit, const float* lr, float momentum, float dampening, float weight_decay, int nesterov,
+                                       float* losses, float* grad_out, void* workspace, size_t workspace_bytes, void* text_stash, size_t text_stash_bytes,
+                                       void* vision_stash, size_t vision_stash_bytes, clipmi_stream_t stream) {
+  const ScalerCall sc{state, growth_factor, backoff_factor, growth_interval};
+  return promptsrc_train_step("promptsrc_train_step_scaled", &sc, m, wt, wv, prompts, dtype, eot, n_prompts, seq_rows, image, image_dtype, B, labels, teacher,
+                              block, buf, nt, dt, nv, dv, scale, 1.f, w_text, w_image, w_logit, lr, 0, momentum, dampening, weight_decay, nesterov, losses,
+                              grad_out, workspace, workspace_bytes, text_stash, text_stash_bytes, vision_stash, vision_stash_bytes, stream);
 }
 
 }  // extern "C"

@@ -15,7 +15,12 @@ The parameters travel as a dict under the prompt learner's own ``state_dict`` na
 ``proj.weight``, ``proj.bias``, ``compound_prompt_projections.{i}.weight``, ``compound_prompt_projections.{i}.bias``.
 
 ``grad_scale``: as in ``coopfit`` / ``vptfit`` -- one power of two covers both towers' backwards, the head multiplies both gradients by
-it and the step divides.  profiles/maplefit_parity.txt has the measurement behind the default.
+it and the step divides.  profiles/maplefit_parity.txt has the measurement behind the default.  ``grad_scale="dynamic"`` with
+``scaler=dict(init_scale, growth_factor, backoff_factor, growth_interval)`` is the reference's ``prec == "amp"`` branch (maple.py:269,
+``torch.cuda.amp.GradScaler``) as ``coopfit`` has it: the scale lives in a block on the device, a step whose gradient block holds an inf
+or a NaN changes neither the parameters nor the momentum buffer, and the scale backs off and grows again.  No step reads anything back;
+``MaPLeFitState.scaler_state()`` does, once.  DESIGN.md "Dynamic loss scale for the block fits"; the reference's ``autocast`` casts
+differ from this path's fixed fp16 operand points (unverified).
 
 ``gradients`` returns one batch's loss and every parameter's gradient (the diagnostic entry point of the tests).
 ``MaPLeFitState.step`` takes one batch of preprocessed images; ``fit_prompt_learner`` runs epochs over a tensor of images or a loader of
@@ -25,7 +30,7 @@ The defaults -- SGD at 0.0035 with momentum 0.9 and weight decay 5e-4, 5 epochs 
 a cosine schedule, n_ctx 2, depth 9 -- restate configs/trainers/MaPLe/vit_b16_c2_ep5_batch4.yaml; the momentum and the weight decay
 are Dassl's public defaults and are UNVERIFIED here; each is an argument.
 
-Not covered (IVLP and PromptSRC train through ``promptsrcfit``): the reference's ``amp`` branch, ``nn.DataParallel``, ViT-L lengths (more than 224 token rows
+Not covered (IVLP and PromptSRC train through ``promptsrcfit``): ``nn.DataParallel``, ViT-L lengths (more than 224 token rows
 per image), the ResNet towers, class-token positions other than ``end``.
 """
 from __future__ import annotations
@@ -40,7 +45,7 @@ import torch
 from . import _lib, fitloop, ops
 from ._lib import check, lib
 from . import coopfit, vptfit
-from .coopfit import _check_grad_scale
+from .coopfit import DYNAMIC, _BlockScaler, _check_grad_scale, _is_dynamic, _scale_args
 
 # 2^10, one power of two for both towers' backwards, measured at ViT-B/16 with synthetic weights, n_ctx 2, depth 9, batch 4, 100 classes
 # (profiles/maplefit_parity.txt, "grad_scale"): the text tower's dgrad-GEMM operands reach 1413 there (2^5.5 of headroom below fp16's
@@ -192,8 +197,9 @@ class _Towers:
                   "clipmi_text_encoder_backward_deep")
         return t.d_embed, (self.d_deep if self.depth > 1 else None), self.vision.backward(d_feats, stats_vision)
 
-    def one_call_workspace(self, B: int) -> torch.Tensor:
-        need = lib.clipmi_maple_train_step_bytes(self.model._handle, self.C, self.text.rows, B, self.n_ctx, self.depth)
+    def one_call_workspace(self, B: int, scaled: bool = False) -> torch.Tensor:
+        sizer = lib.clipmi_maple_train_step_scaled_bytes if scaled else lib.clipmi_maple_train_step_bytes
+        need = sizer(self.model._handle, self.C, self.text.rows, B, self.n_ctx, self.depth)
         if self.one_ws is None or self.one_ws.numel() < need:
             self.one_ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.model.device)
         return self.one_ws
@@ -209,6 +215,8 @@ def gradients(model, learner_params: Dict[str, torch.Tensor], images: torch.Tens
     fp16 dgrad-GEMM operand element, ``elements``, ``zeros``, ``subnormals``, ``max`` -- the measurement behind the default
     ``grad_scale``.  A diagnostic entry point: every call allocates both towers' workspaces and stashes."""
     who = "maplefit.gradients"
+    if _is_dynamic(who, grad_scale):
+        raise ValueError(f"{who}: grad_scale={DYNAMIC!r} belongs to a fit (MaPLeFitState, fit_prompt_learner); one gradient needs a number")
     gs = _check_grad_scale(who, grad_scale)
     if not math.isfinite(logit_scale):
         raise ValueError(f"{who}: logit_scale={logit_scale} (finite)")
@@ -246,9 +254,9 @@ class MaPLeFitState:
 
     def __init__(self, model, tokenized_prompts, learner_params: Dict[str, torch.Tensor], logit_scale: float = 4.6052, momentum: float = 0.9,
                  dampening: float = 0.0, nesterov: bool = False, weight_decay: float = 5e-4, grad_scale: float = DEFAULT_GRAD_SCALE,
-                 seq_rows: Optional[int] = None, class_token_position: str = "end"):
+                 seq_rows: Optional[int] = None, class_token_position: str = "end", scaler: Optional[dict] = None):
         who = "MaPLeFitState"
-        self.grad_scale = _check_grad_scale(who, grad_scale)
+        self.dynamic, self.grad_scale, self.scaler = _scale_args(who, grad_scale, scaler)
         fitloop.check_sgd(who, momentum, dampening, weight_decay, nesterov)
         if not math.isfinite(logit_scale):
             raise ValueError(f"{who}: logit_scale={logit_scale} (finite)")
@@ -259,17 +267,30 @@ class MaPLeFitState:
         self.scale = float(np.float32(math.exp(logit_scale)))
         self.momentum, self.dampening, self.nesterov, self.weight_decay = momentum, dampening, nesterov, weight_decay
         self.steps = 0
+        self._scaler = _BlockScaler(self.scaler, model.device) if self.dynamic else None
+        self._scaled_grad = torch.empty_like(self.block) if self.dynamic else None    # scale * gradient, as clipmi_maple_step leaves it
 
     def params(self) -> Dict[str, torch.Tensor]:
         t = self.towers
         return unpack_block(self.block, t.n_ctx, t.depth, t.Dt, t.Dv)
+
+    def scaler_state(self) -> dict:
+        """The dynamic scale's block as ``dict(scale, growth_tracker, skipped_steps, applied_steps, found_inf)`` (``found_inf``: of the
+        last step).  It waits for the steps enqueued so far: one synchronisation, the only read-back of the dynamic path."""
+        if not self.dynamic:
+            raise ValueError(f"MaPLeFitState.scaler_state: the state was made with a static grad_scale={self.grad_scale}")
+        return self._scaler.state()
 
     def step(self, images: torch.Tensor, labels, lr, want_loss: bool = False, one_call: bool = False) -> Optional[torch.Tensor]:
         """One optimiser step on the batch ``images`` [B, 3, R, R] (preprocessed, fp16 or fp32, on the GPU) and ``labels`` [B] at the rate
         ``lr``: an fp32 tensor of one element on the device is read where it lies; a Python number is uploaded on every call.  A label
         tensor on the GPU is taken as it is -- a label outside [0, C) then makes the parameters NaN, it is never used as an address; host
         labels are range-checked.  ``one_call``: the same launches through clipmi_maple_train_step, whose workspace holds both towers'.
-        Returns the batch loss, fp32 [1] on the device, when ``want_loss``."""
+        Returns the batch loss, fp32 [1] on the device, when ``want_loss``.  Under ``grad_scale="dynamic"`` the head runs at
+        ``grad_scale = 1``, ``d_text`` and ``d_feats`` are multiplied by the device block's scale, clipmi_maple_step forms the gradient
+        without applying it and clipmi_block_step_scaled decides on the device whether the step is applied (one call:
+        clipmi_maple_train_step_scaled); a skipped step still counts in ``steps`` and still returns its loss; whether it was applied is in
+        ``scaler_state()``."""
         who = "MaPLeFitState.step"
         tw = self.towers
         t, v, m = tw.text, tw.vision, tw.model
@@ -280,7 +301,28 @@ class MaPLeFitState:
         first = self.steps == 0
         sgd = (float(self.momentum), float(self.dampening), float(self.weight_decay), int(bool(self.nesterov)))
         loss = torch.empty(1, dtype=torch.float32, device=dev)
-        if one_call:
+        if self.dynamic and one_call:
+            v.size(B, tower_ws=False)
+            ws, sc = tw.one_call_workspace(B, scaled=True), self._scaler
+            with m._launch_lock:
+                check(lib.clipmi_maple_train_step_scaled(m._handle, C.byref(t.dgrad[0]), C.byref(v.dgrad[0]), t.base.data_ptr(), _DT[t.base.dtype],
+                                                         t.eot.data_ptr(), t.C, t.rows, images.data_ptr(), _DT[images.dtype], B, labels_d.data_ptr(),
+                                                         self.block.data_ptr(), None if self.buf is None else self.buf.data_ptr(), tw.n_ctx, tw.depth,
+                                                         self.scale, sc.block.data_ptr(), *sc.args(), lr_d.data_ptr(), *sgd, loss.data_ptr(), None,
+                                                         ws.data_ptr(), ws.numel(), t.stash.data_ptr(), t.stash.numel(), v.stash.data_ptr(),
+                                                         v.stash.numel(), ops._stream()),
+                      "clipmi_maple_train_step_scaled")
+        elif self.dynamic:
+            text, feats = tw.forward(self.block, images)
+            _, d_feats, d_text = maple_head(feats, labels_d, text, self.scale, 1.0, loss)
+            ops.grad_scale_rows(d_text, self._scaler.block)
+            ops.grad_scale_rows(d_feats, self._scaler.block)
+            d_embed, d_deep, d_vis = tw.backward(d_text, d_feats)
+            check(lib.clipmi_maple_step(d_embed.data_ptr(), None if d_deep is None else d_deep.data_ptr(), d_vis.data_ptr(), self.block.data_ptr(), None,
+                                        self._scaled_grad.data_ptr(), 0, t.C, t.L, tw.n_ctx, tw.depth, tw.Dt, tw.Dv, 1.0, None, 0, *sgd,
+                                        tw.step_ws.data_ptr(), tw.step_ws.numel(), ops._stream()), "clipmi_maple_step")
+            self._scaler.step(self._scaled_grad, self.block, self.buf, lr_d, *sgd)
+        elif one_call:
             v.size(B, tower_ws=False)
             ws = tw.one_call_workspace(B)
             with m._launch_lock:
@@ -321,7 +363,7 @@ def fit_prompt_learner(images_or_loader, labels, model, tokenized_prompts, learn
                        depth: int = 9, logit_scale: float = 4.6052, lr: float = 0.0035, epochs: int = 5, batch_size: int = 4, momentum: float = 0.9,
                        dampening: float = 0.0, weight_decay: float = 5e-4, nesterov: bool = False, grad_scale: float = DEFAULT_GRAD_SCALE,
                        seq_rows: Optional[int] = None, lr_per_epoch: Optional[Sequence[float]] = None, drop_last: bool = False,
-                       return_history: bool = False, class_token_position: str = "end"):
+                       return_history: bool = False, class_token_position: str = "end", scaler: Optional[dict] = None):
     """Train MaPLe's prompt learner starting from ``learner_params`` (not modified; None = ``init_learner_params(model, n_ctx, depth)``):
     ``epochs`` passes of ``torch.optim.SGD(lr, momentum, dampening, weight_decay, nesterov)`` over the whole parameter list.
     ``images_or_loader`` is a tensor of preprocessed images [N, 3, R, R] with ``labels`` [N], cut into batches of ``batch_size`` in order
@@ -329,7 +371,9 @@ def fit_prompt_learner(images_or_loader, labels, model, tokenized_prompts, learn
     ``batch_size`` unused).  ``lr_per_epoch`` gives every epoch's rate; None takes ``cosine_warmup_schedule(lr, epochs)``.  Both towers
     run on every step; nothing synchronises until the one wait at the end.  Returns the fitted parameters, a dict of fp32 tensors on the
     device (views of one block), or ``(params, per-step batch losses)`` with ``return_history``.  The model's prompt learner is NOT
-    written: ``trainers.maple.CustomCLIP.fit_prompt_learner`` does that."""
+    written: ``trainers.maple.CustomCLIP.fit_prompt_learner`` does that.  ``grad_scale="dynamic"`` with ``scaler`` (module docstring): a
+    step that overflows fp16 is skipped on the device and the scale adapts; the history keeps one loss per step, skipped steps included,
+    and the run still synchronises once."""
     who = "fit_prompt_learner"
     epochs = int(epochs)
     if epochs < 0:
@@ -337,7 +381,7 @@ def fit_prompt_learner(images_or_loader, labels, model, tokenized_prompts, learn
     if learner_params is None:
         learner_params = init_learner_params(model, n_ctx, depth)
     state = MaPLeFitState(model, tokenized_prompts, learner_params, logit_scale, momentum, dampening, nesterov, weight_decay, grad_scale, seq_rows,
-                          class_token_position)
+                          class_token_position, scaler)
     batches = fitloop.cut_batches(who, images_or_loader, labels, state.C, batch_size, drop_last, model.device)
     _, lr_steps = fitloop.schedule(who, lr, epochs, lr_per_epoch, len(batches), model.device)
     history = fitloop.run_batches(lambda e, k, b, r, want: state.step(b[0], b[1], r, want_loss=want), batches, epochs, lr_steps, return_history)

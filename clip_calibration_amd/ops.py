@@ -1036,6 +1036,38 @@ def ctx_step_scaled(d_embed: torch.Tensor, n_prompts: int, n_ctx: int, per_class
     return grad
 
 
+def block_step_scaled(grad: torch.Tensor, state: torch.Tensor, params: torch.Tensor, buf: Optional[torch.Tensor], lr: torch.Tensor,
+                      growth_factor: float = 2.0, backoff_factor: float = 0.5, growth_interval: int = 2000, momentum: float = 0.0,
+                      dampening: float = 0.0, weight_decay: float = 0.0, nesterov: bool = False, want_grad: bool = True,
+                      workspace: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
+    """clipmi_block_step_scaled: the scaler's rule (``ctx_step_scaled``) over a whole fp32 master block ``params``.  ``grad``, of as many
+    elements, is the block's gradient times the scale of ``state``, as a fit's own launches leave it at ``grad_scale = 1`` behind
+    ``grad_scale_rows``; it is divided by the scale on the device, a gradient with an inf or a NaN leaves ``params`` and ``buf`` as they
+    are and backs the scale off, a clean one is applied.  Nothing is read back.  ``workspace``: a uint8 tensor to reuse between steps.
+    Returns the unscaled gradient (``params``' shape) when ``want_grad``."""
+    who = "block_step_scaled"
+    _in_place(grad, torch.float32, f"{who}: grad must be a contiguous fp32 tensor on the GPU")
+    _in_place(params, torch.float32, f"{who}: params must be a contiguous fp32 tensor on the GPU")
+    total = params.numel()
+    if total < 1 or grad.numel() != total:
+        raise ValueError(f"{who}: grad {tuple(grad.shape)} and params {tuple(params.shape)} must hold the same number of elements (>= 1)")
+    if buf is not None:
+        _in_place(buf, torch.float32, f"{who}: buf must be a contiguous fp32 tensor on the GPU", numel=total)
+    lr = _dev(lr, "lr", (torch.float32,))
+    if lr.numel() != 1:
+        raise ValueError(f"{who}: lr {tuple(lr.shape)} must hold one element")
+    ps = _scaler_state(who, state)
+    out = torch.empty_like(params) if want_grad else None
+    need = lib.clipmi_block_step_scaled_workspace_bytes(total)
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=params.device)
+    check(lib.clipmi_block_step_scaled(grad.data_ptr(), params.data_ptr(), None if buf is None else buf.data_ptr(),
+                                       None if out is None else out.data_ptr(), total, ps, float(growth_factor), float(backoff_factor),
+                                       int(growth_interval), lr.data_ptr(), float(momentum), float(dampening), float(weight_decay),
+                                       int(bool(nesterov)), workspace.data_ptr(), workspace.numel(), _stream()), "clipmi_block_step_scaled")
+    return out
+
+
 PROMPT_MODES ={"coop": _lib.PROMPT_COOP, "kgcoop": _lib.PROMPT_KGCOOP, "prograd": _lib.PROMPT_PROGRAD}
 
 

@@ -28,7 +28,14 @@ The defaults -- SGD at 0.0025, 50 epochs in batches of 4, a constant warm-up epo
 GPA mean 30 and std 30 -- restate configs/trainers/PromptSRC/vit_b16_c4_ep50_batch4.yaml (w_logit is fixed at 1 in the reference's
 code); momentum 0.9 and weight decay 5e-4 are Dassl's public defaults and are UNVERIFIED here; each is an argument.
 
-Not covered: the reference's ``amp`` branch, ``nn.DataParallel``, ViT-L lengths (more than 224 token rows per image), the ResNet towers,
+``grad_scale="dynamic"`` with ``scaler=dict(init_scale, growth_factor, backoff_factor, growth_interval)`` (both methods) is the
+reference's ``prec == "amp"`` branch (promptsrc.py:272, ``torch.cuda.amp.GradScaler``) as ``coopfit`` has it: the scale lives in a block
+on the device, a step whose gradient block holds an inf or a NaN changes neither the parameters nor the momentum buffer, and the scale
+backs off and grows again; ``end_epoch`` aggregates whatever the block holds.  No step reads anything back;
+``PromptSRCFitState.scaler_state()`` does, once.  DESIGN.md "Dynamic loss scale for the block fits"; the reference's ``autocast`` casts
+differ from this path's fixed fp16 operand points (unverified).
+
+Not covered: ``nn.DataParallel``, ViT-L lengths (more than 224 token rows per image), the ResNet towers,
 class-token positions other than ``end``.
 """
 from __future__ import annotations
@@ -43,7 +50,7 @@ import torch
 from . import _lib, fitloop, ops
 from ._lib import check, lib
 from . import coopfit, vptfit
-from .coopfit import _check_grad_scale
+from .coopfit import DYNAMIC, _BlockScaler, _check_grad_scale, _is_dynamic, _scale_args
 from .fitloop import _need_gpu
 
 # 2^10, one power of two for both towers' backwards, measured at ViT-B/16 with synthetic weights, nt = nv = 4, depths 9 / 9, batch 4, 100
@@ -280,8 +287,11 @@ class _Towers:
             self.head_ws = torch.empty(max(need, 8), dtype=torch.uint8, device=self.model.device)
         return self.head_ws
 
-    def one_call_workspace(self, B: int) -> torch.Tensor:
-        need = lib.clipmi_promptsrc_train_step_bytes(self.model._handle, self.C, self.text.rows, B, self.nt, self.dt, self.nv)
+    def one_call_workspace(self, B: int, scaled: bool = False) -> torch.Tensor:
+        if scaled:
+            need = lib.clipmi_promptsrc_train_step_scaled_bytes(self.model._handle, self.C, self.text.rows, B, self.nt, self.dt, self.nv, self.dv)
+        else:
+            need = lib.clipmi_promptsrc_train_step_bytes(self.model._handle, self.C, self.text.rows, B, self.nt, self.dt, self.nv)
         if self.one_ws is None or self.one_ws.numel() < need:
             self.one_ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.model.device)
         return self.one_ws
@@ -303,6 +313,8 @@ def gradients(model, params: Dict[str, torch.Tensor], images: torch.Tensor, labe
     ``maplefit.gradients`` does; ``return_features`` adds ``{"text", "feats", "zs"}``, the raw features the head was given.  A diagnostic
     entry point: every call allocates both towers' workspaces and stashes."""
     who = "promptsrcfit.gradients"
+    if _is_dynamic(who, grad_scale):
+        raise ValueError(f"{who}: grad_scale={DYNAMIC!r} belongs to a fit (PromptSRCFitState, fit_prompts); one gradient needs a number")
     gs = _check_grad_scale(who, grad_scale)
     wt, wi, wl = _method_weights(who, method, w_text, w_image, w_logit)
     if not math.isfinite(logit_scale):
@@ -337,9 +349,9 @@ class PromptSRCFitState:
     def __init__(self, model, tokenized_prompts, params: Dict[str, torch.Tensor], teacher: torch.Tensor, logit_scale: float = 4.6052,
                  w_text: float = 25.0, w_image: float = 10.0, w_logit: float = 1.0, momentum: float = 0.9, dampening: float = 0.0, nesterov: bool = False,
                  weight_decay: float = 5e-4, grad_scale: float = DEFAULT_GRAD_SCALE, seq_rows: Optional[int] = None, method: str = "promptsrc",
-                 class_token_position: str = "end"):
+                 class_token_position: str = "end", scaler: Optional[dict] = None):
         who = "PromptSRCFitState"
-        self.grad_scale = _check_grad_scale(who, grad_scale)
+        self.dynamic, self.grad_scale, self.scaler = _scale_args(who, grad_scale, scaler)
         fitloop.check_sgd(who, momentum, dampening, weight_decay, nesterov)
         self.weights = _method_weights(who, method, w_text, w_image, w_logit)
         if not math.isfinite(logit_scale):
@@ -354,9 +366,18 @@ class PromptSRCFitState:
         self.scale = float(np.float32(math.exp(logit_scale)))
         self.momentum, self.dampening, self.nesterov, self.weight_decay = momentum, dampening, nesterov, weight_decay
         self.steps = 0
+        self._scaler = _BlockScaler(self.scaler, model.device) if self.dynamic else None
+        self._scaled_grad = torch.empty_like(self.block) if self.dynamic else None    # scale * gradient, as clipmi_promptsrc_step leaves it
 
     def params(self, block: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
         return unpack_block(self.block if block is None else block, *self.towers.shape())
+
+    def scaler_state(self) -> dict:
+        """The dynamic scale's block as ``dict(scale, growth_tracker, skipped_steps, applied_steps, found_inf)`` (``found_inf``: of the
+        last step).  It waits for the steps enqueued so far: one synchronisation, the only read-back of the dynamic path."""
+        if not self.dynamic:
+            raise ValueError(f"PromptSRCFitState.scaler_state: the state was made with a static grad_scale={self.grad_scale}")
+        return self._scaler.state()
 
     def step(self, images: torch.Tensor, labels, lr, want_loss: bool = False, one_call: bool = False) -> Optional[torch.Tensor]:
         """One optimiser step on the batch ``images`` [B, 3, R, R] (preprocessed, fp16 or fp32, on the GPU) and ``labels`` [B] at the rate
@@ -364,7 +385,10 @@ class PromptSRCFitState:
         tensor on the GPU is taken as it is -- a label outside [0, C) then makes the parameters NaN, it is never used as an address; host
         labels are range-checked.  ``one_call``: the same launches through clipmi_promptsrc_train_step, whose workspace holds both
         towers'.  Returns the batch's total loss, fp32 [1] on the device (a view of the five terms kept in ``last_losses``), when
-        ``want_loss``."""
+        ``want_loss``.  Under ``grad_scale="dynamic"`` the head runs at ``grad_scale = 1``, ``d_text`` and ``d_feats`` are multiplied by
+        the device block's scale, clipmi_promptsrc_step forms the gradient without applying it and clipmi_block_step_scaled decides on the
+        device whether the step is applied (one call: clipmi_promptsrc_train_step_scaled); a skipped step still counts in ``steps`` and
+        still returns its losses; whether it was applied is in ``scaler_state()``."""
         who = "PromptSRCFitState.step"
         tw = self.towers
         t, v, m = tw.text, tw.vision, tw.model
@@ -375,7 +399,30 @@ class PromptSRCFitState:
         first = self.steps == 0
         sgd = (float(self.momentum), float(self.dampening), float(self.weight_decay), int(bool(self.nesterov)))
         losses = torch.empty(5, dtype=torch.float32, device=dev)
-        if one_call:
+        if self.dynamic and one_call:
+            v.size(B, tower_ws=False)
+            ws, sc = tw.one_call_workspace(B, scaled=True), self._scaler
+            with m._launch_lock:
+                check(lib.clipmi_promptsrc_train_step_scaled(m._handle, C.byref(t.dgrad[0]), C.byref(v.dgrad[0]), t.base.data_ptr(), _DT[t.base.dtype],
+                                                             t.eot.data_ptr(), t.C, t.rows, images.data_ptr(), _DT[images.dtype], B, labels_d.data_ptr(),
+                                                             self.teacher.data_ptr(), self.block.data_ptr(),
+                                                             None if self.buf is None else self.buf.data_ptr(), tw.nt, tw.dt, tw.nv, tw.dv, self.scale,
+                                                             sc.block.data_ptr(), *sc.args(), *self.weights, lr_d.data_ptr(), *sgd, losses.data_ptr(), None,
+                                                             ws.data_ptr(), ws.numel(), t.stash.data_ptr(), t.stash.numel(), v.stash.data_ptr(),
+                                                             v.stash.numel(), ops._stream()), "clipmi_promptsrc_train_step_scaled")
+        elif self.dynamic:
+            zs = tw.frozen(images)
+            text, feats = tw.forward(self.block, images)
+            _, d_feats, d_text = promptsrc_head(feats, zs, text, self.teacher, labels_d, self.scale, 1.0, *self.weights, losses=losses,
+                                                ws=tw.head_workspace(B))
+            ops.grad_scale_rows(d_text, self._scaler.block)
+            ops.grad_scale_rows(d_feats, self._scaler.block)
+            d_embed, d_deep, d_vis = tw.backward(d_text, d_feats)
+            check(lib.clipmi_promptsrc_step(d_embed.data_ptr(), None if d_deep is None else d_deep.data_ptr(), d_vis.data_ptr(), self.block.data_ptr(),
+                                            None, self._scaled_grad.data_ptr(), 0, t.C, t.L, *tw.shape(), 1.0, None, 0, *sgd, ops._stream()),
+                  "clipmi_promptsrc_step")
+            self._scaler.step(self._scaled_grad, self.block, self.buf, lr_d, *sgd)
+        elif one_call:
             v.size(B, tower_ws=False)
             ws = tw.one_call_workspace(B)
             with m._launch_lock:
@@ -434,7 +481,7 @@ def fit_prompts(images_or_loader, labels, model, tokenized_prompts, teacher: tor
                 dampening: float = 0.0, weight_decay: float = 5e-4, nesterov: bool = False, w_text: float = 25.0, w_image: float = 10.0,
                 w_logit: float = 1.0, gpa=(30.0, 30.0), grad_scale: float = DEFAULT_GRAD_SCALE, seq_rows: Optional[int] = None,
                 lr_per_epoch: Optional[Sequence[float]] = None, drop_last: bool = False, return_history: bool = False, one_call: bool = False,
-                class_token_position: str = "end"):
+                class_token_position: str = "end", scaler: Optional[dict] = None):
     """Train the prompts starting from ``params`` (not modified; None = ``init_params(model)``): ``epochs`` passes of
     ``torch.optim.SGD(lr, momentum, dampening, weight_decay, nesterov)`` over the whole parameter list on PromptSRC's loss.
     ``images_or_loader`` is a tensor of preprocessed images [N, 3, R, R] with ``labels`` [N], cut into batches of ``batch_size`` in order
@@ -444,7 +491,9 @@ def fit_prompts(images_or_loader, labels, model, tokenized_prompts, teacher: tor
     ``method="ivlp"`` sets the three weights to 0 and ``gpa`` to None.  Three towers run on every step; nothing synchronises until the one
     wait at the end.  Returns the fitted parameters, a dict of fp32 tensors on the device (views of one block), or ``(params, per-step
     total losses)`` with ``return_history``.  The model's parameters are NOT written: ``trainers.promptsrc.CustomCLIP.fit_prompts`` does
-    that."""
+    that.  ``grad_scale="dynamic"`` with ``scaler`` (module docstring; both methods): a step that overflows fp16 is skipped on the device
+    and the scale adapts; the history keeps one loss per step, skipped steps included, GPA aggregates whatever the block holds at the end
+    of an epoch, and the run still synchronises once."""
     who = "fit_prompts"
     epochs = int(epochs)
     if epochs < 0:
@@ -454,7 +503,7 @@ def fit_prompts(images_or_loader, labels, model, tokenized_prompts, teacher: tor
     if params is None:
         params = init_params(model)
     state = PromptSRCFitState(model, tokenized_prompts, params, teacher, logit_scale, w_text, w_image, w_logit, momentum, dampening, nesterov, weight_decay,
-                              grad_scale, seq_rows, method, class_token_position)
+                              grad_scale, seq_rows, method, class_token_position, scaler)
     weights = None if method == "ivlp" else _gpa_for(who, gpa, epochs)
 
     def end_epoch(e: int) -> None:

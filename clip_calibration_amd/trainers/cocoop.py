@@ -117,7 +117,8 @@ class CustomCLIP(nn.Module):
         equal to the reference's loop only for a deterministic train transform.  ``transform=TrainPreprocess(...)``: ``train_loader``
         yields (decoded uint8 images, labels) and is iterated once per epoch, every batch going transform -> image tower ->
         ``CoCoOpFitState.step`` (``augment.fit_with_transform``); ``fit_args`` are then ``epochs``, ``lr``, ``lr_per_epoch``, ``views``,
-        ``return_history`` and ``CoCoOpFitState``'s own."""
+        ``return_history`` and ``CoCoOpFitState``'s own.  ``grad_scale="dynamic"`` with ``scaler=dict(init_scale, growth_factor,
+        backoff_factor, growth_interval)`` on either route: the device-side loss scale (``cocoopfit``'s module docstring)."""
         import math
         from ..cocoopfit import NAMES
         fit_args.setdefault("logit_scale", math.log(self.scale))

@@ -85,7 +85,9 @@ class CustomCLIP(_CoOpCLIP):
         ``transform=TrainPreprocess.for_model(model)``: it yields (decoded uint8 images, labels) and every batch goes transform ->
         ``MaPLeFitState.step`` with nothing synchronising until the end (``augment.fit_with_transform``).  ``fit_args``: ``epochs`` (5),
         ``lr`` (0.0035), ``lr_per_epoch``, the optimiser's ``momentum``, ``dampening``, ``weight_decay``, ``nesterov``, ``grad_scale``,
-        ``seq_rows``, ``views`` (with a transform) and ``return_history``; the batch size and the order are the loader's."""
+        ``seq_rows``, ``views`` (with a transform) and ``return_history``; the batch size and the order are the loader's.
+        ``grad_scale="dynamic"`` with ``scaler=dict(init_scale, growth_factor, backoff_factor, growth_interval)``: the device-side loss
+        scale (``maplefit``'s module docstring)."""
         import math
         from .. import maplefit
         fit_args.setdefault("logit_scale", math.log(self.scale))

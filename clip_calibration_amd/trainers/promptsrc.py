@@ -71,7 +71,9 @@ class CustomCLIP(_CoOpCLIP):
         ``PromptSRCFitState.step`` with nothing synchronising until the end (``augment.fit_with_transform``).  ``fit_args``: ``epochs``
         (50), ``lr`` (0.0025), ``lr_per_epoch``, ``method``, ``w_text``, ``w_image``, ``w_logit``, ``gpa``, the optimiser's ``momentum``,
         ``dampening``, ``weight_decay``, ``nesterov``, ``grad_scale``, ``seq_rows``, ``views`` (with a transform) and
-        ``return_history`` and ``one_call``; the batch size and the order are the loader's (``batch_size`` / ``drop_last`` are refused)."""
+        ``return_history`` and ``one_call``; the batch size and the order are the loader's (``batch_size`` / ``drop_last`` are refused).
+        ``grad_scale="dynamic"`` with ``scaler=dict(init_scale, growth_factor, backoff_factor, growth_interval)``, for ``method="ivlp"``
+        as well: the device-side loss scale (``promptsrcfit``'s module docstring)."""
         import math
         from .. import promptsrcfit
         fit_args.setdefault("logit_scale", math.log(self.scale))

@@ -35,7 +35,8 @@ class CustomCLIP(ZeroshotCLIP):
         ``VPTFitState.step`` with nothing synchronising until the end (``augment.fit_with_transform``).  ``fit_args``: ``epochs`` (5),
         ``lr`` (0.0025), ``lr_per_epoch``, the optimiser's ``momentum``, ``dampening``, ``weight_decay``, ``nesterov``, ``grad_scale``,
         ``views`` (with a transform) and ``return_history``; the batch size and the order are the loader's.  The defaults restate the
-        reference's VPT config (SGD, lr 0.0025, 5 epochs)."""
+        reference's VPT config (SGD, lr 0.0025, 5 epochs).  ``grad_scale="dynamic"`` with ``scaler=dict(init_scale, growth_factor,
+        backoff_factor, growth_interval)``: the device-side loss scale (``vptfit``'s module docstring)."""
         import math
         from .. import vptfit
         fit_args.setdefault("logit_scale", math.log(self.scale))

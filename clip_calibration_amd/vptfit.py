@@ -12,7 +12,12 @@ residual and gradient streams, an fp32 master block ``[depth, n_ctx, Dv]`` of th
 the masters rounded through fp16, the reference's ``.half()``.  DESIGN.md "VPT fit" has the data flow.
 
 ``grad_scale``: as in ``coopfit`` -- the whole backward carries ``grad_scale`` times the gradient (a power of two), the head multiplies
-and the step divides.  profiles/vptfit_parity.txt has the measurement behind the default.
+and the step divides.  profiles/vptfit_parity.txt has the measurement behind the default.  ``grad_scale="dynamic"`` with
+``scaler=dict(init_scale, growth_factor, backoff_factor, growth_interval)`` is the reference's ``prec == "amp"`` branch (vpt.py:164,
+``torch.cuda.amp.GradScaler``) as ``coopfit`` has it: the scale lives in a block on the device, a step whose gradient holds an inf or a
+NaN changes neither the prompts nor the momentum buffer, and the scale backs off and grows again.  No step reads anything back;
+``VPTFitState.scaler_state()`` does, once.  DESIGN.md "Dynamic loss scale for the block fits"; the reference's ``autocast`` casts differ
+from this path's fixed fp16 operand points (unverified).
 
 ``prompt_gradient`` returns one batch's loss and gradient (the diagnostic entry point of the tests).  ``VPTFitState.step`` takes one
 batch of preprocessed images; ``fit_prompts`` runs epochs over a tensor of images or a loader of (images, labels) batches and enqueues
@@ -22,7 +27,7 @@ The defaults -- SGD at 0.0025 with momentum 0.9 and weight decay 5e-4, 5 epochs,
 schedule -- restate the reference's VPT config and Dassl's public defaults and are UNVERIFIED here; each is an argument.
 
 Not covered (MaPLe trains through ``maplefit`` and PromptSRC / IVLP through ``promptsrcfit``, on this tower): ViT-L lengths (more
-than 224 token rows per image), ``nn.DataParallel``, the reference's ``amp`` branch, the ResNet towers.
+than 224 token rows per image), ``nn.DataParallel``, the ResNet towers.
 """
 from __future__ import annotations
 
@@ -35,7 +40,7 @@ import torch
 
 from . import _lib, fitloop, ops
 from ._lib import check, lib
-from .coopfit import _check_grad_scale, operand_stats_dict
+from .coopfit import DYNAMIC, _BlockScaler, _check_grad_scale, _is_dynamic, _scale_args, operand_stats_dict
 from .fitloop import _need_gpu
 
 # 2^12: CoOp's value (profiles/coopfit_parity.txt) holds for the image tower's backward at the ViT-B/16 geometry as well
@@ -170,8 +175,11 @@ class _Tower:
                   "clipmi_vision_encoder_backward")
         return self.d_prompts
 
-    def one_call_workspace(self, B: int, n_cls: int) -> torch.Tensor:
-        need = lib.clipmi_vpt_train_step_bytes(self.model._handle, B, self.n_ctx, n_cls)
+    def one_call_workspace(self, B: int, n_cls: int, scaled: bool = False) -> torch.Tensor:
+        if scaled:
+            need = lib.clipmi_vpt_train_step_scaled_bytes(self.model._handle, B, self.n_ctx, self.depth, n_cls)
+        else:
+            need = lib.clipmi_vpt_train_step_bytes(self.model._handle, B, self.n_ctx, n_cls)
         if self.step_ws is None or self.step_ws.numel() < need:
             self.step_ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.model.device)
         return self.step_ws
@@ -212,6 +220,8 @@ def prompt_gradient(model, prompts: torch.Tensor, images: torch.Tensor, labels, 
     of its own (41.6 MB per image at ViT-B/16 with 8 prompt rows); a training loop keeps a ``VPTFitState``."""
     who = "prompt_gradient"
     depth, n_ctx = _check_prompts(who, model, prompts)
+    if _is_dynamic(who, grad_scale):
+        raise ValueError(f"{who}: grad_scale={DYNAMIC!r} belongs to a fit (VPTFitState, fit_prompts); one gradient needs a number")
     gs = _check_grad_scale(who, grad_scale)
     if not math.isfinite(logit_scale):
         raise ValueError(f"{who}: logit_scale={logit_scale} (finite)")
@@ -248,12 +258,12 @@ class VPTFitState:
 
     def __init__(self, model, text_features: torch.Tensor, logit_scale: float = 4.6052, prompts: Optional[torch.Tensor] = None,
                  momentum: float = 0.9, dampening: float = 0.0, nesterov: bool = False, weight_decay: float = 5e-4,
-                 grad_scale: float = DEFAULT_GRAD_SCALE):
+                 grad_scale: float = DEFAULT_GRAD_SCALE, scaler: Optional[dict] = None):
         who = "VPTFitState"
         if prompts is None:
             prompts = model_prompts(model)
         self.depth, self.n_ctx = _check_prompts(who, model, prompts)
-        self.grad_scale = _check_grad_scale(who, grad_scale)
+        self.dynamic, self.grad_scale, self.scaler = _scale_args(who, grad_scale, scaler)
         fitloop.check_sgd(who, momentum, dampening, weight_decay, nesterov)
         if not math.isfinite(logit_scale):
             raise ValueError(f"{who}: logit_scale={logit_scale} (finite)")
@@ -265,6 +275,14 @@ class VPTFitState:
         self.scale = float(np.float32(math.exp(logit_scale)))
         self.momentum, self.dampening, self.nesterov, self.weight_decay = momentum, dampening, nesterov, weight_decay
         self.steps = 0
+        self._scaler = _BlockScaler(self.scaler, model.device) if self.dynamic else None
+
+    def scaler_state(self) -> dict:
+        """The dynamic scale's block as ``dict(scale, growth_tracker, skipped_steps, applied_steps, found_inf)`` (``found_inf``: of the
+        last step).  It waits for the steps enqueued so far: one synchronisation, the only read-back of the dynamic path."""
+        if not self.dynamic:
+            raise ValueError(f"VPTFitState.scaler_state: the state was made with a static grad_scale={self.grad_scale}")
+        return self._scaler.state()
 
     def step(self, images: torch.Tensor, labels, lr, want_loss: bool = False, one_call: bool = False) -> Optional[torch.Tensor]:
         """One optimiser step on the batch ``images`` [B, 3, R, R] (preprocessed, fp16 or fp32, on the GPU) and ``labels`` [B] at the rate
@@ -272,7 +290,9 @@ class VPTFitState:
         tensor on the GPU is taken as it is -- a label outside [0, C) then makes the prompts NaN, it is never used as an address; host
         labels are range-checked.  ``one_call``: the same launches through clipmi_vpt_train_step, whose workspace holds the tower's (the
         separate calls' workspace is then not allocated; the stash is the same).  Returns the batch loss, fp32 [1] on the device, when
-        ``want_loss``."""
+        ``want_loss``.  Under ``grad_scale="dynamic"`` the head runs at ``grad_scale = 1``, ``d_feats`` is multiplied by the device block's
+        scale and clipmi_block_step_scaled decides on the device whether the step is applied (one call: clipmi_vpt_train_step_scaled); a
+        skipped step still counts in ``steps`` and still returns its loss; whether it was applied is in ``scaler_state()``."""
         who = "VPTFitState.step"
         t, m = self.tower, self.tower.model
         images = t.images(who, images)
@@ -282,7 +302,22 @@ class VPTFitState:
         first = self.steps == 0
         sgd = (float(self.momentum), float(self.dampening), float(self.weight_decay), int(bool(self.nesterov)))
         loss = torch.empty(1, dtype=torch.float32, device=dev)
-        if one_call:
+        if self.dynamic and one_call:
+            t.size(B, tower_ws=False)
+            ws, sc = t.one_call_workspace(B, self.C, scaled=True), self._scaler
+            with m._launch_lock:
+                check(lib.clipmi_vpt_train_step_scaled(m._handle, C.byref(t.dgrad[0]), images.data_ptr(), _DT[images.dtype], B, self.prompts.data_ptr(),
+                                                       None if self.buf is None else self.buf.data_ptr(), self.n_ctx, self.depth, self.text.data_ptr(),
+                                                       self.C, labels_d.data_ptr(), self.scale, sc.block.data_ptr(), *sc.args(), lr_d.data_ptr(), *sgd,
+                                                       loss.data_ptr(), None, ws.data_ptr(), ws.numel(), t.stash.data_ptr(), t.stash.numel(),
+                                                       ops._stream()),
+                      "clipmi_vpt_train_step_scaled")
+        elif self.dynamic:
+            feats = t.forward(images, self.prompts)
+            _, d_feats = vpt_head(feats, labels_d, self.text, self.scale, 1.0, loss)
+            ops.grad_scale_rows(d_feats, self._scaler.block)
+            self._scaler.step(t.backward(d_feats), self.prompts, self.buf, lr_d, *sgd)
+        elif one_call:
             t.size(B, tower_ws=False)
             ws = t.one_call_workspace(B, self.C)
             with m._launch_lock:
@@ -302,19 +337,22 @@ class VPTFitState:
 def fit_prompts(images_or_loader, labels, model, text_features: torch.Tensor, prompts: Optional[torch.Tensor] = None, logit_scale: float = 4.6052,
                 lr: float = 0.0025, epochs: int = 5, batch_size: int = 32, momentum: float = 0.9, dampening: float = 0.0,
                 weight_decay: float = 5e-4, nesterov: bool = False, grad_scale: float = DEFAULT_GRAD_SCALE,
-                lr_per_epoch: Optional[Sequence[float]] = None, drop_last: bool = False, return_history: bool = False):
+                lr_per_epoch: Optional[Sequence[float]] = None, drop_last: bool = False, return_history: bool = False,
+                scaler: Optional[dict] = None):
     """Train VPT's prompts starting from ``prompts`` (not modified; None = the model's own parameters): ``epochs`` passes of
     ``torch.optim.SGD(lr, momentum, dampening, weight_decay, nesterov)``.  ``images_or_loader`` is a tensor of preprocessed images
     [N, 3, R, R] with ``labels`` [N], cut into batches of ``batch_size`` in order (the last one short unless ``drop_last``), or a sized
     iterable of (images, labels) batches iterated once per epoch (``labels`` None, ``batch_size`` unused).  ``lr_per_epoch`` gives every
     epoch's rate; None takes ``cosine_warmup_schedule(lr, epochs)``.  The image tower runs on every step; nothing synchronises until the
     one wait at the end.  Returns the fitted fp32 block [depth, n_ctx, Dv] on the device, or ``(prompts, per-step batch losses)`` with
-    ``return_history``.  The model's parameters are NOT written: ``trainers.vpt.CustomCLIP.fit_prompts`` does that."""
+    ``return_history``.  The model's parameters are NOT written: ``trainers.vpt.CustomCLIP.fit_prompts`` does that.
+    ``grad_scale="dynamic"`` with ``scaler`` (module docstring): a step that overflows fp16 is skipped on the device and the scale adapts;
+    the history keeps one loss per step, skipped steps included, and the run still synchronises once."""
     who = "fit_prompts"
     epochs = int(epochs)
     if epochs < 0:
         raise ValueError(f"{who}: epochs={epochs} (>= 0)")
-    state = VPTFitState(model, text_features, logit_scale, prompts, momentum, dampening, nesterov, weight_decay, grad_scale)
+    state = VPTFitState(model, text_features, logit_scale, prompts, momentum, dampening, nesterov, weight_decay, grad_scale, scaler)
     batches = fitloop.cut_batches(who, images_or_loader, labels, state.C, batch_size, drop_last, model.device)
     _, lr_steps = fitloop.schedule(who, lr, epochs, lr_per_epoch, len(batches), model.device)
     history = fitloop.run_batches(lambda e, k, b, r, want: state.step(b[0], b[1], r, want_loss=want), batches, epochs, lr_steps, return_history)

@@ -1133,6 +1133,67 @@ int clipmi_prompt_train_step_scaled(clipmi_model* m, const clipmi_text_dgrad* wt
                                     float momentum, float dampening, float weight_decay, int nesterov, float* losses, float* grad_out,
                                     void* workspace, size_t workspace_bytes, void* stash, size_t stash_bytes, clipmi_stream_t stream);
 
+/* The scaler's rule for the fits whose parameters are ONE fp32 master block stepped element by element (CoCoOp, VPT, MaPLe, PromptSRC and
+ * IVLP; DESIGN.md "Dynamic loss scale for the block fits").  grad fp32 [total] is scale * the gradient of the block: what the fit's own
+ * gradient-forming launches leave at grad_scale = 1 once the head's outputs have been multiplied by the block's scale
+ * (clipmi_grad_scale_rows).  Three launches:
+ *   one thread per element, workgroups of 256: g = grad[i] * (1 / state->scale) into the workspace and into grad_out (may be NULL; may be
+ *     grad itself), and one integer flag per workgroup, set when any g of the workgroup is an inf or a NaN;
+ *   clipmi_ctx_step_scaled's second launch: one workgroup ORs the flags, writes the decision and updates the state block by its rule;
+ *   clipmi_ctx_step_scaled's third launch: clipmi_ctx_step's SGD rule on params and buf with the unscaled gradient, only on a clean step.
+ * A skipped step writes neither params nor buf; the momentum buffer starts from the gradient of the first APPLIED step; there is no
+ * first_step argument.  No atomics, no workgroup reads what another of the same launch writes, the same inputs give the same bits.  With
+ * the flags clear params, buf and grad_out equal a static step at grad_scale = scale and first_step = (applied_steps == 0) bit for bit.
+ * workspace (256-byte aligned): clipmi_block_step_scaled_workspace_bytes(total) bytes, 0 for a total the call refuses.  Every check
+ * precedes the first launch.  CLIPMI_ERR_ARG: a null pointer (grad, params, lr, state, the workspace; buf with a momentum), a pointer that
+ * is not 4-byte aligned, a factor that is not finite or not positive, growth_interval < 1, SGD's own refusals; CLIPMI_ERR_SHAPE: total < 1
+ * or total >= 2^39; CLIPMI_ERR_WORKSPACE. */
+size_t clipmi_block_step_scaled_workspace_bytes(int64_t total);
+int clipmi_block_step_scaled(const float* grad, float* params, float* buf, float* grad_out, int64_t total, clipmi_scaler_state* state,
+                             float growth_factor, float backoff_factor, int growth_interval, const float* lr, float momentum, float dampening,
+                             float weight_decay, int nesterov, void* workspace, size_t workspace_bytes, clipmi_stream_t stream);
+
+/* The four one-call steps under the scaler.  Each is its static call with `state` and the scaler's three arguments in grad_scale's place
+ * and without first_step (the state block knows the first applied step), and enqueues, in order: the static call's launches up to the
+ * head, the head at grad_scale = 1, clipmi_grad_scale_rows on every fp32 gradient the head hands to a backward (d_text for CoCoOp; d_feats
+ * for VPT; d_text and d_feats for MaPLe and PromptSRC -- before anything rounds them to fp16), the backward(s), the fit's gradient
+ * formation at grad_scale = 1 without applying (clipmi_cocoop_reduce; VPT's d_prompts as they are; clipmi_maple_step and
+ * clipmi_promptsrc_step with apply = 0) and clipmi_block_step_scaled on the block.  grad_out (may be NULL) receives the unscaled gradient.
+ * The same launches, the same bits as the calls one by one; with a scale that never changes, the static call's bits at that scale.  The
+ * scaler's and the optimiser's refusals precede the first launch.  workspace: the static call's, then (MaPLe, PromptSRC) the block of
+ * scale * gradient, then clipmi_block_step_scaled's -- the matching _scaled_bytes function, 0 for arguments the call refuses (VPT's and
+ * PromptSRC's take the image prompt depth as well: the block's size depends on it). */
+size_t clipmi_cocoop_train_step_scaled_bytes(const clipmi_model* m, int C, int seq_rows, int B, int H, int n_ctx);
+int clipmi_cocoop_train_step_scaled(clipmi_model* m, const clipmi_text_dgrad* wt, const void* base, int dtype, float* params, float* buf,
+                                    int n_ctx, int H, const int32_t* cls_eot, int C, int seq_rows, const float* feats, int64_t ld,
+                                    const int64_t* labels, int B, float scale, clipmi_scaler_state* state, float growth_factor,
+                                    float backoff_factor, int growth_interval, const float* lr, float momentum, float dampening,
+                                    float weight_decay, int nesterov, float* loss, float* grad_out, void* workspace, size_t workspace_bytes,
+                                    void* stash, size_t stash_bytes, clipmi_stream_t stream);
+size_t clipmi_vpt_train_step_scaled_bytes(const clipmi_model* m, int B, int n_ctx, int depth, int C);
+int clipmi_vpt_train_step_scaled(clipmi_model* m, const clipmi_vision_dgrad* wt, const void* image, int image_dtype, int B, float* prompts,
+                                 float* buf, int n_ctx, int depth, const float* text, int C, const int64_t* labels, float scale,
+                                 clipmi_scaler_state* state, float growth_factor, float backoff_factor, int growth_interval, const float* lr,
+                                 float momentum, float dampening, float weight_decay, int nesterov, float* loss, float* grad_out,
+                                 void* workspace, size_t workspace_bytes, void* stash, size_t stash_bytes, clipmi_stream_t stream);
+size_t clipmi_maple_train_step_scaled_bytes(const clipmi_model* m, int n_prompts, int seq_rows, int B, int n_ctx, int depth);
+int clipmi_maple_train_step_scaled(clipmi_model* m, const clipmi_text_dgrad* wt, const clipmi_vision_dgrad* wv, const void* prompts, int dtype,
+                                   const int32_t* eot, int n_prompts, int seq_rows, const void* image, int image_dtype, int B,
+                                   const int64_t* labels, float* block, float* buf, int n_ctx, int depth, float scale,
+                                   clipmi_scaler_state* state, float growth_factor, float backoff_factor, int growth_interval, const float* lr,
+                                   float momentum, float dampening, float weight_decay, int nesterov, float* loss, float* grad_out,
+                                   void* workspace, size_t workspace_bytes, void* text_stash, size_t text_stash_bytes, void* vision_stash,
+                                   size_t vision_stash_bytes, clipmi_stream_t stream);
+size_t clipmi_promptsrc_train_step_scaled_bytes(const clipmi_model* m, int n_prompts, int seq_rows, int B, int nt, int dt, int nv, int dv);
+int clipmi_promptsrc_train_step_scaled(clipmi_model* m, const clipmi_text_dgrad* wt, const clipmi_vision_dgrad* wv, const void* prompts,
+                                       int dtype, const int32_t* eot, int n_prompts, int seq_rows, const void* image, int image_dtype, int B,
+                                       const int64_t* labels, const float* teacher, float* block, float* buf, int nt, int dt, int nv, int dv,
+                                       float scale, clipmi_scaler_state* state, float growth_factor, float backoff_factor, int growth_interval,
+                                       float w_text, float w_image, float w_logit, const float* lr, float momentum, float dampening,
+                                       float weight_decay, int nesterov, float* losses, float* grad_out, void* workspace,
+                                       size_t workspace_bytes, void* text_stash, size_t text_stash_bytes, void* vision_stash,
+                                       size_t vision_stash_bytes, clipmi_stream_t stream);
+
 /* ProDA's collection of contexts trained on the same frozen-tower backward (reference trainers/classification/proda.py:146-228, 258-304;
  * csrc/proda_train.hip, DESIGN.md "ProDA fit").  ctx fp32 [P, n_ctx, D] is the master of all P contexts; pos int32 [P] gives each one's
  * class-token position (0 front, 1 middle, 2 end); a step uses the Pb contexts sel int32 [Pb] names, the caller having put them into
