@@ -117,8 +117,9 @@ int clipmi_gemm_f16(const void* A, int64_t lda, const void* W, int64_t ldw, cons
 /* The residual GEMM of a block on the fp16 residual stream (out-proj / c_proj, clip/model.py:186-187: `x = x + f(x)` on fp16 tensors):
  * x16[m,n] = fp16(x16[m,n] + A[m,:] . W[n,:] + bias[n]) IN PLACE (one rounding of the fp32 sum), plus the LayerNorm-fold row
  * partials the next GEMM consumes: stats[(t * M + m) * 2 + {0,1}] = (sum, sum of squares) over the 256 columns of column tile t of
- * the ROUNDED row m; *parts (host int) receives the number of column tiles of the kernel that ran: (N + 255) / 256 with every default
- * dispatch, (N + 127) / 128 when gemm_variant = 0 is forced (partials are then per 128 columns); at most 8 either way.  A fp16 [M,K]
+ * the ROUNDED row m; *parts (host int) receives the number of column tiles of the kernel that ran: (N + 255) / 256, or (N + 127) / 128
+ * (partials are then per 128 columns) where the 128 x 128 tile kernel runs -- small problems, or gemm_variant = 0 forced -- and that
+ * count is at most 8; at most 8 either way.  A fp16 [M,K]
  * (lda), W fp16 [N,K] (ldw), bias fp32 [N], x16 fp16 [M,N] (ldx), stats fp32 [8 * M * 2] (room for the largest count).  K % 64 == 0, N % 8 == 0, ldx % 8 == 0, 16-byte aligned. */
 int clipmi_gemm_residual_f16(const void* A, int64_t lda, const void* W, int64_t ldw, const float* bias, void* x16, int64_t ldx,
                              float* stats, int* parts, int M, int N, int K, clipmi_stream_t stream);
