@@ -981,7 +981,8 @@ int clipmi_maple_train_step(clipmi_model* m, const clipmi_text_dgrad* wt, const 
  * sums in a fixed order, each unweighted but the total.  A term whose weight is 0 is SKIPPED, not multiplied in: its loss reads 0, its
  * operand is not read beyond the pointer check, and with all three weights 0 d_text, d_feats and losses[0] are clipmi_maple_head's bit
  * for bit.  w_text, w_image, w_logit: finite, >= 0.  A label outside [0, C) is never used as an address: it makes the cross-entropy,
- * the total and that row's gradient NaN.  A zero row of teacher or zs_feats has no direction: with a non-zero weight that reads it, that
+ * the total, that row of d_feats and -- du_c sums over the images -- every entry of d_text NaN; the two L1 terms and the logit KL keep
+ * the bits of the same call with good labels.  A zero row of teacher or zs_feats has no direction: with a non-zero weight that reads it, that
  * row's terms, and through the means the losses they enter, are NaN (as clipmi_prompt_head documents for KgCoOp's teacher).
  * workspace (8-byte aligned) of clipmi_promptsrc_head_workspace_bytes bytes.  Six launches with all weights 0, nine with none 0 (two norm, two logits, the softmax, the two gradient kernels, the L1 kernel, the losses).
  * No float atomics: the same inputs give the same bits.  Every refusal comes ahead of the first launch. */
