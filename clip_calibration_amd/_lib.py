@@ -233,6 +233,14 @@ _SIGNATURES = {
     "clipmi_prompt_train_step_scaled_bytes": (_sz, [_vp, _i, _i, _i, _i, _i, _i]),
     "clipmi_prompt_train_step_scaled": (_i, [_vp, C.POINTER(TextDgrad), _vp, _i, _vp, _vp, _i, _i, _vp, _i, _i, _vp, _i64, _vp, _i, _f, _vp, _f, _f, _i,
                                              _i, _vp, _f, _vp, _f, _f, _f, _i, _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
+    "clipmi_prompt_place": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "clipmi_prompt_unplace": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "clipmi_prompt_train_step_placed_bytes": (_sz, [_vp, _i, _i, _i, _i, _i, _i]),
+    "clipmi_prompt_train_step_placed": (_i, [_vp, C.POINTER(TextDgrad), _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _vp, _i64, _vp, _i, _f, _f,
+                                             _i, _vp, _f, _f, _f, _vp, _i, _f, _f, _f, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
+    "clipmi_prompt_train_step_scaled_placed_bytes": (_sz, [_vp, _i, _i, _i, _i, _i, _i]),
+    "clipmi_prompt_train_step_scaled_placed": (_i, [_vp, C.POINTER(TextDgrad), _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _vp, _i64, _vp, _i, _f,
+                                                    _vp, _f, _f, _i, _i, _vp, _f, _vp, _f, _f, _f, _i, _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
     "clipmi_block_step_scaled_workspace_bytes": (_sz, [_i64]),
     "clipmi_block_step_scaled": (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _f, _f, _i, _vp, _f, _f, _f, _i, _vp, _sz, _vp]),
     "clipmi_cocoop_train_step_scaled_bytes": (_sz, [_vp, _i, _i, _i, _i, _i]),

@@ -42,8 +42,16 @@ along the other one, ``b``, taken out when they conflict: ``a - lam (a.b / b.b) 
 rounding points.  Unverified, besides Dassl's defaults above: the reference's ``amp`` branch of ProGrad (prograd.py:415-424) hands
 ``GradScaler.scale`` a tuple and is not mirrored.
 
-Not covered: ``nn.DataParallel`` (one process drives one GPU), class token positions other than ``end`` (ProDA's three positions train
-through ``prodafit``, on this backward with a head of its own), and models whose text tower carries deep prompts.
+``class_token_position``: "end" (the default and every shipped config's), "middle" or "front", the reference's
+TRAINER.{COOP,KGCOOP,PROGRAD}.CLASS_TOKEN_POSITION (coop.py:128-192), for all three methods, generic and class-specific contexts, and both
+loss scales that a method has.  "end" is the route described above, untouched.  For the other two csrc/prompt_position.hip assembles
+the prompts in one launch in front of the tower (``ops.prompt_place``; the tower then takes them as they are) and one copy launch behind
+the backward gathers the rows that hold the context into the [C, 1 + n_ctx, D] layout the existing steps read (``ops.prompt_unplace``), so
+the class sums, the SGD rule, the scaler's rule and ProGrad's projection are the same code.  ``name_lens``: every class's name length in
+tokens; None derives ``eot - n_ctx - 2``, the reference's layout ``[SOT, X * n_ctx, name, '.', EOT]``.
+
+Not covered: ``nn.DataParallel`` (one process drives one GPU), ProGrad under a dynamic loss scale, and models whose text tower carries
+deep prompts.
 """
 from __future__ import annotations
 
@@ -172,6 +180,32 @@ def _check_batch(who: str, features, labels, C: int, E: int) -> torch.Tensor:
     return fitloop.step_labels(who, labels, features.shape[0], C, features.device)
 
 
+POSITIONS = ("end", "middle", "front")
+
+
+def _placement(who: str, tokenized_prompts, n_ctx: int, class_token_position, name_lens):
+    """The host-side checks of the class-token position and the name lengths: None for "end" (today's route: nothing is placed), else
+    ``(position code, name lengths as an int32 array [C])``.  ``name_lens=None`` derives ``eot - n_ctx - 2``; an explicit sequence must
+    have one entry per class with ``0 <= nl`` and ``1 + n_ctx + nl <= eot[c]``, so that the name stays in front of the EOT row."""
+    if not isinstance(class_token_position, str) or class_token_position not in POSITIONS:
+        raise ValueError(f"{who}: class_token_position={class_token_position!r} must be one of {POSITIONS}")
+    eot = _host_int_array(who, tokenized_prompts, "tokenized_prompts").argmax(axis=1)
+    if name_lens is None:
+        lens = np.maximum(eot - n_ctx - 2, 0)
+    else:
+        lens = np.asarray(name_lens.detach().cpu() if isinstance(name_lens, torch.Tensor) else name_lens)
+        if lens.ndim != 1 or lens.shape[0] != eot.shape[0] or lens.dtype.kind not in "iu":
+            raise ValueError(f"{who}: name_lens must be a sequence of {eot.shape[0]} integers (one per class)")
+        bad = np.nonzero((lens < 0) | (1 + n_ctx + lens.astype(np.int64) > eot))[0]
+        if bad.size:
+            c = int(bad[0])
+            raise ValueError(f"{who}: name_lens[{c}]={int(lens[c])} outside [0, {int(eot[c]) - 1 - n_ctx}]: the name of class {c} has to end in front of "
+                             f"its EOT on row {int(eot[c])}")
+    if class_token_position == "end":
+        return None
+    return ops.PROMPT_POSITIONS[class_token_position], np.ascontiguousarray(lens, dtype=np.int32)
+
+
 MAX_LIVE_ROWS = 80     # token rows per prompt that clipmi_text_encoder_backward takes (include/clipmi.h; the attention backward's limit)
 
 
@@ -237,7 +271,8 @@ def _dgrad(model):
 class _Tower:
     """The frozen text tower in training mode for one prompt set: base embeddings, EOT indices, workspace, stash and the gradient stream."""
 
-    def __init__(self, who: str, clip_model, tokenized_prompts, n_cls: int, n_ctx: int, per_class: bool, last_eot: int, seq_rows: Optional[int]):
+    def __init__(self, who: str, clip_model, tokenized_prompts, n_cls: int, n_ctx: int, per_class: bool, last_eot: int, seq_rows: Optional[int],
+                 placement=None):
         dev = clip_model.device
         if dev.type != "cuda":
             raise RuntimeError(f"clipmi: {who} needs the model on a ROCm GPU (model.to('cuda')); the HIP path has no CPU fallback")
@@ -267,15 +302,35 @@ class _Tower:
         self.d_embed = torch.empty(self.C * self.L, self.D, dtype=torch.float32, device=dev)
         self.d_embed_kl = None    # ProGrad's second gradient stream, made on first use
         self.step_ws = None
+        # a class-token position other than "end" (_placement): the placed prompts and the compact gradient streams [C (1 + n_ctx), D]
+        self.position = None
+        if placement is not None:
+            self.position = placement[0]
+            self.name_lens = torch.from_numpy(placement[1]).to(dev)
+            self.prompts = torch.empty(self.C, self.Lc, self.D, dtype=torch.float32, device=dev)
+            self.compact = torch.empty(self.C * (1 + n_ctx), self.D, dtype=torch.float32, device=dev)
+            self.compact_kl = None
 
     def forward(self, ctx: torch.Tensor) -> torch.Tensor:
         m = self.model
+        if self.position is None:
+            src = (self.base.data_ptr(), _DT[self.base.dtype], ctx.data_ptr(), self.n_ctx, int(self.per_class))
+        else:   # the context already lies on its rows of the fp32 prompts: the tower splices nothing
+            ops.prompt_place(self.base, ctx, self.position, self.name_lens, self.rows, self.prompts)
+            src = (self.prompts.data_ptr(), _lib.F32, None, 0, 0)
         with m._launch_lock:
-            check(lib.clipmi_text_encoder_train(m._handle, self.base.data_ptr(), _DT[self.base.dtype], ctx.data_ptr(), self.n_ctx, int(self.per_class),
-                                                self.eot.data_ptr(), self.C, self.rows, None, self.text.data_ptr(), self.ws.data_ptr(),
+            check(lib.clipmi_text_encoder_train(m._handle, *src, self.eot.data_ptr(), self.C, self.rows, None, self.text.data_ptr(), self.ws.data_ptr(),
                                                 self.ws.numel(), self.stash.data_ptr(), self.stash.numel(), _lib.CALL_DEFAULT, ops._stream()),
                   "clipmi_text_encoder_train")
         return self.text
+
+    def context_rows(self, d_embed: torch.Tensor, second: bool = False) -> torch.Tensor:
+        """What the context steps read: ``d_embed`` itself at "end", else its rows that hold the context, gathered into [C (1 + n_ctx), D]."""
+        if self.position is None:
+            return d_embed
+        if second and self.compact_kl is None:
+            self.compact_kl = torch.empty_like(self.compact)
+        return ops.prompt_unplace(d_embed, self.position, self.name_lens, self.n_ctx, self.compact_kl if second else self.compact)
 
     def backward(self, d_text: torch.Tensor, stats: Optional[torch.Tensor] = None, second: bool = False) -> torch.Tensor:
         """``second``: into ProGrad's second stream.  The stash is only read, the workspace is reused: the calls run one after the other."""
@@ -290,7 +345,10 @@ class _Tower:
         return out
 
     def one_call_workspace(self, B: int, method: str = "coop", scaled: bool = False) -> torch.Tensor:
-        sizer = lib.clipmi_prompt_train_step_scaled_bytes if scaled else lib.clipmi_prompt_train_step_bytes
+        if self.position is None:
+            sizer = lib.clipmi_prompt_train_step_scaled_bytes if scaled else lib.clipmi_prompt_train_step_bytes
+        else:
+            sizer = lib.clipmi_prompt_train_step_scaled_placed_bytes if scaled else lib.clipmi_prompt_train_step_placed_bytes
         need = sizer(self.model._handle, self.C, self.rows, B, ops.PROMPT_MODES[method], self.n_ctx, int(self.per_class))
         if self.step_ws is None or self.step_ws.numel() < need:
             self.step_ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.ws.device)
@@ -313,7 +371,7 @@ def _new_losses(method: str, dev) -> torch.Tensor:
 def context_gradient(clip_model, tokenized_prompts, ctx: torch.Tensor, features: torch.Tensor, labels, logit_scale: float = 4.6052,
                      grad_scale: float = DEFAULT_GRAD_SCALE, seq_rows: Optional[int] = None, return_operand_stats: bool = False,
                      method: str = "coop", teacher: Optional[torch.Tensor] = None, w: float = 8.0, T: float = 1.0, lam: float = 1.0,
-                     return_parts: bool = False):
+                     return_parts: bool = False, class_token_position: str = "end", name_lens=None):
     """``(loss, grad)`` of ``F.cross_entropy(exp(logit_scale) * normalise(features) @ normalise(text_encoder(prompts(ctx))).T, labels)``
     with respect to ``ctx`` ([n_ctx, D] generic or [C, n_ctx, D] class-specific), on the GPU: loss fp32 [1], grad fp32 of ctx's shape.
     ``features`` fp32 [B, E] raw image features (the rows may be a column slice), ``tokenized_prompts`` [C, context_length] the ids of
@@ -324,9 +382,11 @@ def context_gradient(clip_model, tokenized_prompts, ctx: torch.Tensor, features:
     ``method`` "kgcoop": the loss is the total ``CE + w score`` and the gradient its gradient; "prograd": the loss is ``xe`` and the
     gradient the one ProGrad applies (module docstring; ``teacher``, ``w``, ``T``, ``lam``).  ``return_parts`` adds a dict (before the
     operand statistics): KgCoOp ``ce``, ``score`` (fp32 [1] each); ProGrad ``xe``, ``kl``, ``grad_xe``, ``grad_kl``, ``projected``
-    (int32 [1]) and ``dots`` (float64 [3]: a.a, b.b, a.b of a = grad_xe, b = grad_kl); CoOp an empty one."""
+    (int32 [1]) and ``dots`` (float64 [3]: a.a, b.b, a.b of a = grad_xe, b = grad_kl); CoOp an empty one.
+    ``class_token_position``, ``name_lens``: the prompts' layout (module docstring)."""
     who = "context_gradient"
     Cn, n_ctx, per_class, last = _check_prompts(who, clip_model, tokenized_prompts, ctx)
+    placement = _placement(who, tokenized_prompts, n_ctx, class_token_position, name_lens)
     if _is_dynamic(who, grad_scale):
         raise ValueError(f"{who}: grad_scale={DYNAMIC!r} belongs to a fit (CoOpFitState, fit_context); one gradient needs a number")
     gs = _check_grad_scale(who, grad_scale)
@@ -338,7 +398,7 @@ def context_gradient(clip_model, tokenized_prompts, ctx: torch.Tensor, features:
     _need_gpu(features, "features")
     if method != "coop":
         _need_gpu(teacher, "teacher")
-    tower = _Tower(who, clip_model, tokenized_prompts, Cn, n_ctx, per_class, last, seq_rows)
+    tower = _Tower(who, clip_model, tokenized_prompts, Cn, n_ctx, per_class, last, seq_rows, placement)
     dev = features.device
     master = fitloop.master(ctx, dev)
     text = tower.forward(master)
@@ -346,12 +406,12 @@ def context_gradient(clip_model, tokenized_prompts, ctx: torch.Tensor, features:
     stats = torch.zeros(4, dtype=torch.int64, device=dev) if return_operand_stats else None
     losses, d_text, d_kl = ops.prompt_head(features, labels_d, text, scale, gs, method, teacher, w, T, _new_losses(method, dev))
     loss = losses[0:1]
-    d_embed = tower.backward(d_text, stats)
+    d_embed = tower.context_rows(tower.backward(d_text, stats))
     if method != "prograd":
         grad = ops.ctx_step(d_embed, Cn, n_ctx, per_class, gs)
         parts = {"ce": losses[1:2], "score": losses[2:3]} if method == "kgcoop" else {}
     else:
-        d_embed_kl = tower.backward(d_kl, stats, second=True)
+        d_embed_kl = tower.context_rows(tower.backward(d_kl, stats, second=True), second=True)
         grad, projected, dots = ops.prograd_step(d_embed, d_embed_kl, Cn, n_ctx, per_class, gs, lam)
         parts = {"xe": losses[0:1], "kl": losses[1:2], "projected": projected, "dots": dots}
         if return_parts:
@@ -363,11 +423,13 @@ def context_gradient(clip_model, tokenized_prompts, ctx: torch.Tensor, features:
     return out + (operand_stats_dict(stats),)
 
 
-def text_features(clip_model, tokenized_prompts, ctx: torch.Tensor, seq_rows: Optional[int] = None) -> torch.Tensor:
+def text_features(clip_model, tokenized_prompts, ctx: torch.Tensor, seq_rows: Optional[int] = None, class_token_position: str = "end",
+                  name_lens=None) -> torch.Tensor:
     """The raw text features fp32 [C, E] of the training forward at ``ctx``: what the loss head is given."""
     who = "text_features"
     Cn, n_ctx, per_class, last = _check_prompts(who, clip_model, tokenized_prompts, ctx)
-    tower = _Tower(who, clip_model, tokenized_prompts, Cn, n_ctx, per_class, last, seq_rows)
+    placement = _placement(who, tokenized_prompts, n_ctx, class_token_position, name_lens)
+    tower = _Tower(who, clip_model, tokenized_prompts, Cn, n_ctx, per_class, last, seq_rows, placement)
     return tower.forward(fitloop.master(ctx, clip_model.device)).clone()
 
 
@@ -378,9 +440,10 @@ class CoOpFitState:
     def __init__(self, clip_model, tokenized_prompts, ctx: torch.Tensor, logit_scale: float = 4.6052, momentum: float = 0.9,
                  dampening: float = 0.0, nesterov: bool = False, weight_decay: float = 5e-4, grad_scale: float = DEFAULT_GRAD_SCALE,
                  seq_rows: Optional[int] = None, method: str = "coop", teacher: Optional[torch.Tensor] = None, w: float = 8.0, T: float = 1.0,
-                 lam: float = 1.0, scaler: Optional[dict] = None):
+                 lam: float = 1.0, scaler: Optional[dict] = None, class_token_position: str = "end", name_lens=None):
         who = "CoOpFitState"
         self.C, self.n_ctx, self.per_class, last = _check_prompts(who, clip_model, tokenized_prompts, ctx)
+        placement = _placement(who, tokenized_prompts, self.n_ctx, class_token_position, name_lens)
         self.dynamic = _is_dynamic(who, grad_scale)
         if self.dynamic:
             if method == "prograd":
@@ -400,7 +463,7 @@ class CoOpFitState:
         if method != "coop":
             _need_gpu(teacher, "teacher")
             self.teacher = teacher.detach().contiguous()
-        self.tower = _Tower(who, clip_model, tokenized_prompts, self.C, self.n_ctx, self.per_class, last, seq_rows)
+        self.tower = _Tower(who, clip_model, tokenized_prompts, self.C, self.n_ctx, self.per_class, last, seq_rows, placement)
         dev = clip_model.device
         self.ctx = fitloop.master(ctx, dev)
         self.buf = torch.zeros_like(self.ctx) if momentum != 0.0 else None
@@ -425,21 +488,21 @@ class CoOpFitState:
         sgd = (float(self.momentum), float(self.dampening), float(self.weight_decay), int(bool(self.nesterov)))
         if one_call:
             ws = t.one_call_workspace(features.shape[0], self.method, scaled=True)
+            fn, placed = ((lib.clipmi_prompt_train_step_scaled, ()) if t.position is None else
+                          (lib.clipmi_prompt_train_step_scaled_placed, (t.position, t.name_lens.data_ptr())))
             with m._launch_lock:
-                check(lib.clipmi_prompt_train_step_scaled(m._handle, C.byref(t.dgrad[0]), t.base.data_ptr(), _DT[t.base.dtype], self.ctx.data_ptr(),
-                                                          None if self.buf is None else self.buf.data_ptr(), t.n_ctx, int(t.per_class),
-                                                          t.eot.data_ptr(), t.C, t.rows, features.data_ptr(), features.stride(0), labels_d.data_ptr(),
-                                                          features.shape[0], self.scale, self.scaler_block.data_ptr(), sc["growth_factor"],
-                                                          sc["backoff_factor"], sc["growth_interval"], ops.PROMPT_MODES[self.method],
-                                                          None if self.teacher is None else self.teacher.data_ptr(), self.w, lr_d.data_ptr(), *sgd,
-                                                          losses.data_ptr(), None, ws.data_ptr(), ws.numel(), t.stash.data_ptr(), t.stash.numel(),
-                                                          ops._stream()),
-                      "clipmi_prompt_train_step_scaled")
+                check(fn(m._handle, C.byref(t.dgrad[0]), t.base.data_ptr(), _DT[t.base.dtype], self.ctx.data_ptr(),
+                         None if self.buf is None else self.buf.data_ptr(), t.n_ctx, int(t.per_class), *placed, t.eot.data_ptr(), t.C, t.rows,
+                         features.data_ptr(), features.stride(0), labels_d.data_ptr(), features.shape[0], self.scale, self.scaler_block.data_ptr(),
+                         sc["growth_factor"], sc["backoff_factor"], sc["growth_interval"], ops.PROMPT_MODES[self.method],
+                         None if self.teacher is None else self.teacher.data_ptr(), self.w, lr_d.data_ptr(), *sgd, losses.data_ptr(), None,
+                         ws.data_ptr(), ws.numel(), t.stash.data_ptr(), t.stash.numel(), ops._stream()),
+                      "clipmi_prompt_train_step_scaled" + ("" if t.position is None else "_placed"))
             return
         text = t.forward(self.ctx)
         _, d_text, _ = ops.prompt_head(features, labels_d, text, self.scale, 1.0, self.method, self.teacher, self.w, 1.0, losses)
         ops.grad_scale_rows(d_text, self.scaler_block)
-        d_embed = t.backward(d_text)
+        d_embed = t.context_rows(t.backward(d_text))
         if self.scaled_ws is None:
             need = lib.clipmi_ctx_step_scaled_workspace_bytes(t.C, t.D, t.n_ctx, int(t.per_class))
             self.scaled_ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.ctx.device)
@@ -467,23 +530,24 @@ class CoOpFitState:
             self._step_scaled(features, labels_d, lr_d, losses, one_call)
         elif one_call:
             ws = t.one_call_workspace(features.shape[0], self.method)
+            fn, placed = ((lib.clipmi_prompt_train_step, ()) if t.position is None else
+                          (lib.clipmi_prompt_train_step_placed, (t.position, t.name_lens.data_ptr())))
             with m._launch_lock:
-                check(lib.clipmi_prompt_train_step(m._handle, C.byref(t.dgrad[0]), t.base.data_ptr(), _DT[t.base.dtype], self.ctx.data_ptr(),
-                                                   None if self.buf is None else self.buf.data_ptr(), t.n_ctx, int(t.per_class), t.eot.data_ptr(), t.C,
-                                                   t.rows, features.data_ptr(), features.stride(0), labels_d.data_ptr(), features.shape[0], self.scale,
-                                                   self.grad_scale, ops.PROMPT_MODES[self.method], None if self.teacher is None else self.teacher.data_ptr(),
-                                                   self.w, self.T, self.lam, lr_d.data_ptr(), int(first), *map(float, sgd[:3]), int(bool(sgd[3])),
-                                                   losses.data_ptr(), None, None, None, ws.data_ptr(), ws.numel(), t.stash.data_ptr(), t.stash.numel(),
-                                                   ops._stream()),
-                      "clipmi_prompt_train_step")
+                check(fn(m._handle, C.byref(t.dgrad[0]), t.base.data_ptr(), _DT[t.base.dtype], self.ctx.data_ptr(),
+                         None if self.buf is None else self.buf.data_ptr(), t.n_ctx, int(t.per_class), *placed, t.eot.data_ptr(), t.C, t.rows,
+                         features.data_ptr(), features.stride(0), labels_d.data_ptr(), features.shape[0], self.scale, self.grad_scale,
+                         ops.PROMPT_MODES[self.method], None if self.teacher is None else self.teacher.data_ptr(), self.w, self.T, self.lam,
+                         lr_d.data_ptr(), int(first), *map(float, sgd[:3]), int(bool(sgd[3])), losses.data_ptr(), None, None, None, ws.data_ptr(),
+                         ws.numel(), t.stash.data_ptr(), t.stash.numel(), ops._stream()),
+                      "clipmi_prompt_train_step" + ("" if t.position is None else "_placed"))
         else:
             text = t.forward(self.ctx)
             _, d_text, d_kl = ops.prompt_head(features, labels_d, text, self.scale, self.grad_scale, self.method, self.teacher, self.w, self.T, losses)
-            d_embed = t.backward(d_text)
+            d_embed = t.context_rows(t.backward(d_text))
             if self.method != "prograd":
                 ops.ctx_step(d_embed, t.C, t.n_ctx, t.per_class, self.grad_scale, self.ctx, self.buf, lr_d, first, *sgd, want_grad=False)
             else:
-                d_embed_kl = t.backward(d_kl, second=True)
+                d_embed_kl = t.context_rows(t.backward(d_kl, second=True), second=True)
                 ops.prograd_step(d_embed, d_embed_kl, t.C, t.n_ctx, t.per_class, self.grad_scale, self.lam, self.ctx, self.buf, lr_d, first, *sgd,
                                  want_report=False)
         self.steps += 1
@@ -503,7 +567,7 @@ def fit_context(features: torch.Tensor, labels, clip_model, tokenized_prompts, c
                 momentum: float = 0.9, dampening: float = 0.0, weight_decay: float = 5e-4, nesterov: bool = False,
                 grad_scale: float = DEFAULT_GRAD_SCALE, seq_rows: Optional[int] = None, lr_per_epoch: Optional[Sequence[float]] = None,
                 order=None, drop_last: bool = False, return_history: bool = False, method: str = "coop", teacher: Optional[torch.Tensor] = None,
-                w: float = 8.0, T: float = 1.0, lam: float = 1.0, scaler: Optional[dict] = None):
+                w: float = 8.0, T: float = 1.0, lam: float = 1.0, scaler: Optional[dict] = None, class_token_position: str = "end", name_lens=None):
     """Train CoOp's context on cached ``features`` fp32 [N, E] (raw image features on the GPU; the rows may be a column slice) and
     ``labels`` [N], starting from ``ctx`` (not modified; None = ``init_context(clip_model, n_ctx, C if csc else None)``): ``epochs``
     passes of ``torch.optim.SGD(lr, momentum, dampening, weight_decay, nesterov)`` over batches of ``batch_size``.
@@ -516,7 +580,8 @@ def fit_context(features: torch.Tensor, labels, clip_model, tokenized_prompts, c
     restatements of the reference's config and Dassl's (module docstring).  ``method``, ``teacher``, ``w``, ``T``, ``lam``: KgCoOp's
     or ProGrad's step in CoOp's place (module docstring); the history then holds KgCoOp's total loss or ProGrad's ``xe``.
     ``grad_scale="dynamic"`` with ``scaler`` (module docstring; CoOp and KgCoOp): a step that overflows fp16 is skipped on the device and
-    the scale adapts; the history keeps one loss per step, skipped steps included, and the run still synchronises once."""
+    the scale adapts; the history keeps one loss per step, skipped steps included, and the run still synchronises once.
+    ``class_token_position``, ``name_lens``: the prompts' layout (module docstring); checked, like everything else, before the first launch."""
     who = "fit_context"
     ids = _host_int_array(who, tokenized_prompts, "tokenized_prompts")
     if ctx is None:
@@ -537,6 +602,7 @@ def fit_context(features: torch.Tensor, labels, clip_model, tokenized_prompts, c
             raise ValueError(f"{who}: scaler is an argument of grad_scale={DYNAMIC!r}")
         _check_grad_scale(who, grad_scale)
     _check_method(who, method, teacher, w, T, lam, Cn, E)
+    _placement(who, tokenized_prompts, n_ctx, class_token_position, name_lens)
     lab = fitloop._labels(who, labels, N, Cn)
     order = fitloop.check_order(who, order, epochs, N)
     per_epoch = steps_per_epoch(N, batch_size, drop_last)
@@ -548,7 +614,7 @@ def fit_context(features: torch.Tensor, labels, clip_model, tokenized_prompts, c
         return (out, np.zeros(0, np.float32)) if return_history else out
     _need_gpu(features, "features")
     state = CoOpFitState(clip_model, tokenized_prompts, ctx, logit_scale, momentum, dampening, nesterov, weight_decay, grad_scale, seq_rows,
-                         method, teacher, w, T, lam, scaler)
+                         method, teacher, w, T, lam, scaler, class_token_position, name_lens)
     history = fitloop.run_cached(lambda f, y, r, want: state.step(f, y, r, want_loss=want), features, fitloop.labels_on(labels, lab, dev),
                                  fitloop.order_on(order, np.int64, dev), batch_size, per_epoch, epochs, lr_steps, return_history)
     return (state.ctx, history) if return_history else state.ctx

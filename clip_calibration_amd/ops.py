@@ -1132,6 +1132,63 @@ def prograd_step(d_embed_xe: torch.Tensor, d_embed_kl: torch.Tensor, n_prompts: 
     return (grad, proj, dots) if want_report else None
 
 
+PROMPT_POSITIONS = {"front": 0, "middle": 1, "end": 2}   # `position` of clipmi_prompt_place and clipmi_proda_embed's pos (plain integers there)
+
+
+def _position_code(who: str, position) -> int:
+    if position in PROMPT_POSITIONS:
+        return PROMPT_POSITIONS[position]
+    if isinstance(position, bool) or position not in PROMPT_POSITIONS.values():
+        raise ValueError(f"{who}: position={position!r} must be one of {tuple(PROMPT_POSITIONS)} (or its code {PROMPT_POSITIONS})")
+    return int(position)
+
+
+def prompt_place(base: torch.Tensor, ctx: torch.Tensor, position, name_lens: torch.Tensor, rows: int = 0,
+                 prompts: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """CoOp's prompt assembly at a class-token position: ``prompts`` fp32 [C, Lc, D] from the class embeddings ``base`` [C, Lc, D] (fp16 or
+    fp32, the tokens of ``"X .. X name."``), the fp32 master ``ctx`` ([n_ctx, D], or [C, n_ctx, D] class-specific), ``position``
+    ("front", "middle", "end" or ProDA's code 0, 1, 2) and the int32 device vector ``name_lens`` [C].  Only the first ``rows`` token rows
+    of each prompt are written (0: all of them).  A caller's own ``prompts`` is written where it lies.  One launch."""
+    who = "prompt_place"
+    ps = _position_code(who, position)
+    base = _dev(base, "base", (torch.float16, torch.float32))
+    ctx = _dev(ctx, "ctx", (torch.float32,))
+    if base.dim() != 3 or ctx.dim() not in (2, 3) or ctx.shape[-1] != base.shape[2] or (ctx.dim() == 3 and ctx.shape[0] != base.shape[0]):
+        raise ValueError(f"{who}: base {tuple(base.shape)} and ctx {tuple(ctx.shape)} do not agree")
+    Cn, Lc, D = base.shape
+    n_ctx = int(ctx.shape[-2])
+    name_lens = _proda_index(name_lens, "name_lens", Cn)
+    L = int(rows) if 0 < int(rows) < Lc else Lc
+    if prompts is None:
+        prompts = torch.empty(Cn, Lc, D, dtype=torch.float32, device=base.device)
+    else:
+        _in_place(prompts, torch.float32, f"{who}: prompts must be a contiguous fp32 tensor on the GPU", numel=Cn * Lc * D)
+    check(lib.clipmi_prompt_place(base.data_ptr(), _DT[base.dtype], ctx.data_ptr(), int(ctx.dim() == 3), ps, name_lens.data_ptr(), prompts.data_ptr(),
+                                  Cn, L, Lc, D, n_ctx, _stream()), "clipmi_prompt_place")
+    return prompts
+
+
+def prompt_unplace(d_embed: torch.Tensor, position, name_lens: torch.Tensor, n_ctx: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The inverse of ``prompt_place`` on the gradient stream: ``d_embed`` fp32 [C * L, D] as the backward wrote it -> fp32
+    [C * (1 + n_ctx), D], row 1 + j of class c the row of prompt c that holds context vector j and row 0 zeros -- what ``ctx_step``,
+    ``ctx_step_scaled`` and ``prograd_step`` read as a ``d_embed`` of 1 + n_ctx rows per prompt.  ``name_lens`` int32 [C] on the device.
+    A caller's own ``out`` is written where it lies.  One launch."""
+    who = "prompt_unplace"
+    ps = _position_code(who, position)
+    d_embed = _dev(d_embed, "d_embed", (torch.float32,))
+    name_lens = _dev(name_lens, "name_lens", (torch.int32,))
+    Cn, n_ctx = int(name_lens.numel()), int(n_ctx)
+    if d_embed.dim() != 2 or name_lens.dim() != 1 or Cn < 1 or d_embed.shape[0] % Cn:
+        raise ValueError(f"{who}: d_embed {tuple(d_embed.shape)} does not split into the {Cn} prompts of name_lens")
+    L, D = d_embed.shape[0] // Cn, int(d_embed.shape[1])
+    if out is None:
+        out = torch.empty(Cn * (1 + n_ctx), D, dtype=torch.float32, device=d_embed.device)
+    else:
+        _in_place(out, torch.float32, f"{who}: out must be a contiguous fp32 tensor on the GPU", numel=Cn * (1 + n_ctx) * D)
+    check(lib.clipmi_prompt_unplace(d_embed.data_ptr(), ps, name_lens.data_ptr(), out.data_ptr(), Cn, L, D, n_ctx, _stream()), "clipmi_prompt_unplace")
+    return out
+
+
 def _proda_index(t: torch.Tensor, name: str, n: int) -> torch.Tensor:
     t = _dev(t, name, (torch.int32,))
     if t.shape != (n,):

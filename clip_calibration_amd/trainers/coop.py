@@ -40,11 +40,17 @@ def n_ctx_from_init_ids(ctx_init_ids: torch.Tensor, context_length: int) -> int:
 
 
 class PromptLearner(nn.Module):
-    """coop.py:70-144 with CLASS_TOKEN_POSITION == 'end' (the shipped configs): prompts = [SOS | ctx | class tokens, EOS, pad].
-    ``tokenized_prompts`` are the ids of ``"X X ... X {classname}."`` (coop.py:107-112)."""
+    """coop.py:70-192.  ``tokenized_prompts`` are the ids of ``"X X ... X {classname}."`` (coop.py:107-112).
+
+    ``class_token_position`` (TRAINER.COOP.CLASS_TOKEN_POSITION): "end" (the shipped configs), prompts = [SOS | ctx | class tokens, EOS,
+    pad]; "middle", [SOS | ctx[:h] | name | ctx[h:] | '.', EOS, pad] with h = n_ctx // 2; "front", [SOS | name | ctx | '.', EOS, pad]
+    (coop.py:146-190).  ``name_lens``: every class's name length in tokens (the reference's ``self.name_lens``); None derives
+    ``eot - n_ctx - 2`` from the ids.  With the context on the GPU "middle" and "front" are assembled by one launch
+    (``ops.prompt_place``) into fp32 prompts, which the text tower takes as it takes the fp16 ones -- not by a Python loop over the
+    classes, which the reference runs on every batch."""
 
     def __init__(self, clip_model: CLIP, tokenized_prompts: torch.Tensor, n_ctx: int = 16, csc: bool = False,
-                 ctx_init_ids: Optional[torch.Tensor] = None, seed: int = 0):
+                 ctx_init_ids: Optional[torch.Tensor] = None, seed: int = 0, class_token_position: str = "end", name_lens=None):
         super().__init__()
         dtype = clip_model.dtype
         dev = clip_model.device
@@ -68,13 +74,30 @@ class PromptLearner(nn.Module):
         self.register_buffer("token_suffix", embedding[:, 1 + n_ctx:, :])    # class tokens, EOS, padding
         self.n_cls, self.n_ctx = n_cls, n_ctx
         self.tokenized_prompts = tokenized_prompts
-        self.class_token_position = "end"
+        from ..coopfit import _placement
+        placement = _placement("PromptLearner", tokenized_prompts, n_ctx, class_token_position, name_lens)
+        self.class_token_position = class_token_position
+        self.name_lens = None if name_lens is None else [int(n) for n in name_lens]   # as given: what fit_context hands to coopfit
+        if placement is not None:   # what ops.prompt_place reads; neither is part of the state dict
+            self.register_buffer("token_base", embedding.contiguous(), persistent=False)
+            self.register_buffer("name_lens_i32", torch.from_numpy(placement[1]).to(dev), persistent=False)
 
     def forward(self) -> torch.Tensor:
         ctx = self.ctx
+        if self.class_token_position != "end" and ctx.is_cuda:
+            return ops.prompt_place(self.token_base, ctx.detach().float(), self.class_token_position, self.name_lens_i32)
         if ctx.dim() == 2:
             ctx = ctx.unsqueeze(0).expand(self.n_cls, -1, -1)
-        return torch.cat([self.token_prefix, ctx.to(self.token_prefix.dtype), self.token_suffix], dim=1)  # layout only
+        ctx = ctx.to(self.token_prefix.dtype)
+        if self.class_token_position == "end":
+            return torch.cat([self.token_prefix, ctx, self.token_suffix], dim=1)  # layout only
+        # a model on the CPU: the reference's loop (coop.py:146-190), layout only
+        h = self.n_ctx // 2 if self.class_token_position == "middle" else 0
+        rows = []
+        for c, nl in enumerate(self.name_lens_i32.tolist()):
+            name, rest = self.token_suffix[c:c + 1, :nl], self.token_suffix[c:c + 1, nl:]
+            rows.append(torch.cat([self.token_prefix[c:c + 1], ctx[c:c + 1, :h], name, ctx[c:c + 1, h:], rest], dim=1))
+        return torch.cat(rows, dim=0)
 
 
 class CustomCLIP(nn.Module):
@@ -164,11 +187,14 @@ class CustomCLIP(nn.Module):
         ``momentum``, ``dampening``, ``weight_decay``, ``nesterov``, ``grad_scale``, ``seq_rows``, ``views`` and ``return_history``;
         the batch size and the order are the loader's.  ``grad_scale="dynamic"`` with ``scaler=dict(init_scale, growth_factor,
         backoff_factor, growth_interval)`` is the reference's ``amp`` branch on either route (``coopfit``'s module docstring): a step
-        that overflows fp16 is skipped on the device and the scale adapts, with no read-back per step."""
+        that overflows fp16 is skipped on the device and the scale adapts, with no read-back per step.  The prompt learner's
+        ``class_token_position`` and ``name_lens`` go to ``coopfit`` with it."""
         import math
         fit_args.setdefault("logit_scale", math.log(self.scale))
         ctx = self.prompt_learner.ctx
         ids = self.prompt_learner.tokenized_prompts
+        fit_args.setdefault("class_token_position", getattr(self.prompt_learner, "class_token_position", "end"))
+        fit_args.setdefault("name_lens", getattr(self.prompt_learner, "name_lens", None))
         if transform is not None:
             from ..augment import fit_with_transform
             from ..coopfit import CoOpFitState

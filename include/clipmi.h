@@ -1135,6 +1135,56 @@ int clipmi_prompt_train_step_scaled(clipmi_model* m, const clipmi_text_dgrad* wt
                                     float momentum, float dampening, float weight_decay, int nesterov, float* losses, float* grad_out,
                                     void* workspace, size_t workspace_bytes, void* stash, size_t stash_bytes, clipmi_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------
+ * The class token at the front or in the middle of a CoOp, KgCoOp or ProGrad prompt (reference trainers/classification/coop.py:128-192,
+ * kgcoop.py:172-230, prograd.py:150-210; csrc/prompt_position.hip, DESIGN.md "CoOp fit").  `position` is a plain int with ProDA's codes
+ * (0 front, 1 middle, 2 end) and the row rule is clipmi_proda_embed's: with nl the class's name length and h = n_ctx / 2, context vector j
+ * sits on row 1 + j (end), 1 + nl + j (front), or 1 + j for j < h and 1 + nl + j otherwise (middle); the name tokens take the rows left
+ * free in [1, 1 + n_ctx + nl), in order; every other row, SOS included, is the base prompt's.  name_lens int32 [C] lives on the device; a
+ * name length is read clamped to [0, L - 2 - n_ctx] and is never used as an unchecked address.  Additive exports: the ABI version stays.
+ *
+ * clipmi_prompt_place: base [C, Lc, D] (dtype: CLIPMI_F16 or CLIPMI_F32), the token embeddings of "X .. X name.", and ctx fp32 [n_ctx, D]
+ *   (or [C, n_ctx, D] with per_class != 0) -> prompts fp32 [C, Lc, D], rows [0, L) of each written (L <= Lc the live rows; the positional
+ *   embedding is the tower's to add).  A context row is copied from the fp32 master unchanged, a base row is widened, which is exact.
+ *   One launch, 16-byte loads and stores: 16-byte aligned pointers, D a multiple of 4.  The tower then runs on the result:
+ *   clipmi_text_encoder_train(m, prompts, CLIPMI_F32, NULL, 0, 0, eot, C, seq_rows, ...) with the token ids' own EOT indices, which do
+ *   not change with the position.
+ * clipmi_prompt_unplace: the inverse on the gradient stream.  d_embed fp32 [C L, D] as the backward wrote it -> out fp32
+ *   [C (1 + n_ctx), D]: row 1 + j of class c is the row of prompt c that holds context vector j, row 0 is zeros.  clipmi_ctx_step,
+ *   clipmi_ctx_step_scaled and clipmi_prograd_step then run on `out` unchanged with L = 1 + n_ctx.  One launch, plain copies, no atomics.
+ * Both: CLIPMI_ERR_ARG for a null pointer or a position outside {0, 1, 2}; CLIPMI_ERR_SHAPE for C < 1, n_ctx < 1, 2 + n_ctx > L, L > Lc
+ *   or D % 4 != 0.
+ *
+ * clipmi_prompt_train_step_placed, clipmi_prompt_train_step_scaled_placed: clipmi_prompt_train_step and clipmi_prompt_train_step_scaled
+ *   with clipmi_prompt_place in front of the tower's forward (which then takes ctx = NULL) and clipmi_prompt_unplace (twice for ProGrad,
+ *   behind the second backward) in front of the step, enqueued in this order on `stream` -- the same launches, the same bits as the calls
+ *   one by one.  Arguments as those steps' plus position and name_lens; prompts is the base.  Every argument check is made before the first
+ *   launch.  workspace of the `_bytes` function's size (256-byte aligned; 0 for arguments the call refuses).
+ * ---------------------------------------------------------------------------------------------------- */
+int clipmi_prompt_place(const void* base, int dtype, const float* ctx, int per_class, int position, const int32_t* name_lens, float* prompts,
+                        int C, int L, int Lc, int D, int n_ctx, clipmi_stream_t stream);
+int clipmi_prompt_unplace(const float* d_embed, int position, const int32_t* name_lens, float* out, int C, int L, int D, int n_ctx,
+                          clipmi_stream_t stream);
+size_t clipmi_prompt_train_step_placed_bytes(const clipmi_model* m, int n_prompts, int seq_rows, int B, int mode, int n_ctx,
+                                             int ctx_per_class);
+int clipmi_prompt_train_step_placed(clipmi_model* m, const clipmi_text_dgrad* wt, const void* prompts, int dtype, float* ctx, float* buf,
+                                    int n_ctx, int ctx_per_class, int position, const int32_t* name_lens, const int32_t* eot, int n_prompts,
+                                    int seq_rows, const float* feats, int64_t ld, const int64_t* labels, int B, float scale,
+                                    float grad_scale, int mode, const float* teacher, float w, float T, float lambda, const float* lr,
+                                    int first_step, float momentum, float dampening, float weight_decay, int nesterov, float* losses,
+                                    float* grad_out, int* projected, double* dots, void* workspace, size_t workspace_bytes, void* stash,
+                                    size_t stash_bytes, clipmi_stream_t stream);
+size_t clipmi_prompt_train_step_scaled_placed_bytes(const clipmi_model* m, int n_prompts, int seq_rows, int B, int mode, int n_ctx,
+                                                    int ctx_per_class);
+int clipmi_prompt_train_step_scaled_placed(clipmi_model* m, const clipmi_text_dgrad* wt, const void* prompts, int dtype, float* ctx,
+                                           float* buf, int n_ctx, int ctx_per_class, int position, const int32_t* name_lens,
+                                           const int32_t* eot, int n_prompts, int seq_rows, const float* feats, int64_t ld,
+                                           const int64_t* labels, int B, float scale, clipmi_scaler_state* state, float growth_factor,
+                                           float backoff_factor, int growth_interval, int mode, const float* teacher, float w,
+                                           const float* lr, float momentum, float dampening, float weight_decay, int nesterov,
+                                           float* losses, float* grad_out, void* workspace, size_t workspace_bytes, void* stash,
+                                           size_t stash_bytes, clipmi_stream_t stream);
+
 /* The scaler's rule for the fits whose parameters are ONE fp32 master block stepped element by element (CoCoOp, VPT, MaPLe, PromptSRC and
  * IVLP; DESIGN.md "Dynamic loss scale for the block fits").  grad fp32 [total] is scale * the gradient of the block: what the fit's own
  * gradient-forming launches leave at grad_scale = 1 once the head's outputs have been multiplied by the block's scale
