@@ -161,8 +161,9 @@ def _en(E):
     return (ceil_div(E, 64) + 6) / 2 + 2
 
 
-def _softmax_bound(z, tz, labels, k, C):
-    """(p, tp, dz, tdz, rows, trows) of the cross-entropy rows of float64 logits z [R, C] with the bound tz on them; k = grad_scale / B."""
+def _softmax_bound(z, tz, labels, k, C, nsum=None):
+    """(p, tp, dz, tdz, rows, trows) of the cross-entropy rows of float64 logits z [R, C] with the bound tz on them; k = grad_scale / B.
+    ``nsum``: the roundings of S's sum where it is not xent_row's over 256 threads and four waves (nC + 10)."""
     R = z.shape[0]
     ar = torch.arange(R)
     m = z.max(dim=-1, keepdim=True).values
@@ -170,8 +171,8 @@ def _softmax_bound(z, tz, labels, k, C):
     p = torch.softmax(z, dim=-1)
     w = tz + (3 * x.abs() + 4) * U
     W = (p * w).sum(-1, keepdim=True)
-    nC = ceil_div(C, 256)
-    tp = (1 + 1e-6) * p * ((1 - p).clamp(min=0) * w + (W - p * w).clamp(min=0)) + (nC + 10) * U * p + FLOOR
+    ns = ceil_div(C, 256) + 10 if nsum is None else nsum
+    tp = (1 + 1e-6) * p * ((1 - p).clamp(min=0) * w + (W - p * w).clamp(min=0)) + ns * U * p + FLOOR
     dz = p.clone()
     dz[ar, labels] -= 1.0
     tdz = abs(k) * tp + 3 * U * (dz * k).abs()
@@ -179,7 +180,7 @@ def _softmax_bound(z, tz, labels, k, C):
     lse = torch.logsumexp(z, dim=-1)
     rows = lse - z[ar, labels]
     log_s = lse - m[:, 0]
-    trows = (1 + 1e-6) * (W[:, 0] + tz[ar, labels]) + (nC + 10) * U + 2 * U * log_s.abs() + 2 * U * x[ar, labels].abs() + 2 * U
+    trows = (1 + 1e-6) * (W[:, 0] + tz[ar, labels]) + ns * U + 2 * U * log_s.abs() + 2 * U * x[ar, labels].abs() + 2 * U
     return p, tp, dz * k, tdz, rows, trows
 
 
