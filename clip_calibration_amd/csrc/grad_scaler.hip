@@ -17,30 +17,13 @@
 namespace clipmi {
 namespace {
 
-constexpr int THREADS = 256;
+constexpr int THREADS = SCALED_THREADS;   // one found-non-finite flag per workgroup (model.h)
 
 enum { MODE_COOP = 0, MODE_KGCOOP = 1, MODE_PROGRAD = 2 };   // `mode` of clipmi_prompt_head (include/clipmi.h)
 
 __global__ __launch_bounds__(THREADS) void grad_scale_rows_kernel(float* __restrict__ x, int64_t n, const clipmi_scaler_state* __restrict__ st) {
   const int64_t idx = (int64_t)blockIdx.x * THREADS + threadIdx.x;
   if (idx < n) x[idx] *= st->scale;
-}
-
-// workspace of one step: the decision record (found, first applied step) | one flag per workgroup of scaled_grad_kernel | the gradient
-struct ScaledWs {
-  int32_t* decision;   // [2]
-  int32_t* flags;      // [blocks]
-  float* grad;         // [total]
-};
-inline int64_t grad_blocks(int64_t total) { return (total + THREADS - 1) / THREADS; }
-inline size_t scaled_step_bytes(int64_t total) { return 256 + align256((size_t)grad_blocks(total) * 4) + align256((size_t)total * 4); }
-inline ScaledWs scaled_carve(void* ws, int64_t total) {
-  char* p = static_cast<char*>(ws);
-  ScaledWs w;
-  w.decision = reinterpret_cast<int32_t*>(p);
-  w.flags = reinterpret_cast<int32_t*>(p + 256);
-  w.grad = reinterpret_cast<float*>(p + 256 + align256((size_t)grad_blocks(total) * 4));
-  return w;
 }
 
 // one thread per element of ctx: g = (the context row's sum) / scale, as ctx_step_kernel forms it at grad_scale = scale; the workgroup's
@@ -114,15 +97,6 @@ __global__ __launch_bounds__(THREADS) void scaled_apply_kernel(ScaledWs w, float
   sgd_element_fma(ctx, buf, idx, w.grad[idx], *lr, sgd);
 }
 
-int check_scaler(const char* who, const clipmi_scaler_state* st, float growth, float backoff, int growth_interval) {
-  CLIPMI_REQUIRE(st, CLIPMI_ERR_ARG, "%s: null pointer (the scaler's state block)", who);
-  CLIPMI_REQUIRE((uintptr_t)st % 4 == 0, CLIPMI_ERR_ARG, "%s: the scaler's state block must be 4-byte aligned", who);
-  CLIPMI_REQUIRE(std::isfinite(growth) && growth > 0.f && std::isfinite(backoff) && backoff > 0.f, CLIPMI_ERR_ARG,
-                 "%s: growth_factor=%g, backoff_factor=%g (both finite, > 0)", who, growth, backoff);
-  CLIPMI_REQUIRE(growth_interval >= 1, CLIPMI_ERR_ARG, "%s: growth_interval=%d (>= 1)", who, growth_interval);
-  return CLIPMI_OK;
-}
-
 // everything clipmi_ctx_step_scaled refuses, before anything is launched; *total: the elements of ctx
 int check_scaled_step(const char* who, const float* d_embed, const float* ctx, const float* buf, const float* lr, int C, int L, int D, int n_ctx, int per_class,
                       const clipmi_scaler_state* st, float growth, float backoff, int growth_interval, float momentum, float dampening, float weight_decay,
@@ -145,18 +119,35 @@ int launch_scaled_step(const float* d_embed, float* ctx, float* buf, float* grad
                        clipmi_scaler_state* st, float growth, float backoff, int growth_interval, const float* lr, float momentum, float dampening,
                        float weight_decay, int nesterov, void* workspace, hipStream_t s) {
   const ScaledWs w = scaled_carve(workspace, total);
-  const int64_t blocks = grad_blocks(total);
+  const int64_t blocks = scaled_grad_blocks(total);
   hipLaunchKernelGGL(scaled_grad_kernel, dim3((unsigned)blocks), dim3(THREADS), 0, s, d_embed, grad_out, C, L, D, n_ctx, per_class ? 1 : 0, total,
                      (const clipmi_scaler_state*)st, w);
   if (int rc = check_launch("scaled_grad_kernel")) return rc;
-  hipLaunchKernelGGL(scaler_update_kernel, dim3(1), dim3(THREADS), 0, s, w, blocks, st, growth, backoff, growth_interval);
-  if (int rc = check_launch("scaler_update_kernel")) return rc;
-  hipLaunchKernelGGL(scaled_apply_kernel, dim3((unsigned)blocks), dim3(THREADS), 0, s, w, ctx, buf, total, lr,
-                     make_sgd_args(momentum, dampening, weight_decay, nesterov, 0));
-  return check_launch("scaled_apply_kernel");
+  return launch_scaled_decide_apply(w, total, ctx, buf, st, growth, backoff, growth_interval, lr, momentum, dampening, weight_decay, nesterov, s);
 }
 
 }  // namespace
+
+// ---- what every scaled step shares (model.h)
+int check_scaler(const char* who, const clipmi_scaler_state* st, float growth, float backoff, int growth_interval) {
+  CLIPMI_REQUIRE(st, CLIPMI_ERR_ARG, "%s: null pointer (the scaler's state block)", who);
+  CLIPMI_REQUIRE((uintptr_t)st % 4 == 0, CLIPMI_ERR_ARG, "%s: the scaler's state block must be 4-byte aligned", who);
+  CLIPMI_REQUIRE(std::isfinite(growth) && growth > 0.f && std::isfinite(backoff) && backoff > 0.f, CLIPMI_ERR_ARG,
+                 "%s: growth_factor=%g, backoff_factor=%g (both finite, > 0)", who, growth, backoff);
+  CLIPMI_REQUIRE(growth_interval >= 1, CLIPMI_ERR_ARG, "%s: growth_interval=%d (>= 1)", who, growth_interval);
+  return CLIPMI_OK;
+}
+
+// the decision launch and the step launch behind a first launch that has filled w.grad and w.flags; every argument has been checked
+int launch_scaled_decide_apply(const ScaledWs& w, int64_t total, float* params, float* buf, clipmi_scaler_state* st, float growth, float backoff,
+                               int growth_interval, const float* lr, float momentum, float dampening, float weight_decay, int nesterov, hipStream_t s) {
+  const int64_t blocks = scaled_grad_blocks(total);
+  hipLaunchKernelGGL(scaler_update_kernel, dim3(1), dim3(THREADS), 0, s, w, blocks, st, growth, backoff, growth_interval);
+  if (int rc = check_launch("scaler_update_kernel")) return rc;
+  hipLaunchKernelGGL(scaled_apply_kernel, dim3((unsigned)blocks), dim3(THREADS), 0, s, w, params, buf, total, lr,
+                     make_sgd_args(momentum, dampening, weight_decay, nesterov, 0));
+  return check_launch("scaled_apply_kernel");
+}
 
 // ---- what the fits' one-call steps share (model.h)
 int launch_grad_scale_rows(const char* who, float* x, int rows, int cols, const clipmi_scaler_state* st, hipStream_t s) {
@@ -192,14 +183,10 @@ int launch_block_step_scaled(const float* grad, float* params, float* buf, float
                              int growth_interval, const float* lr, float momentum, float dampening, float weight_decay, int nesterov, void* workspace,
                              hipStream_t s) {
   const ScaledWs w = scaled_carve(workspace, total);
-  const int64_t blocks = grad_blocks(total);
+  const int64_t blocks = scaled_grad_blocks(total);
   hipLaunchKernelGGL(block_unscale_kernel, dim3((unsigned)blocks), dim3(THREADS), 0, s, grad, grad_out, total, (const clipmi_scaler_state*)st, w);
   if (int rc = check_launch("block_unscale_kernel")) return rc;
-  hipLaunchKernelGGL(scaler_update_kernel, dim3(1), dim3(THREADS), 0, s, w, blocks, st, growth, backoff, growth_interval);
-  if (int rc = check_launch("scaler_update_kernel")) return rc;
-  hipLaunchKernelGGL(scaled_apply_kernel, dim3((unsigned)blocks), dim3(THREADS), 0, s, w, params, buf, total, lr,
-                     make_sgd_args(momentum, dampening, weight_decay, nesterov, 0));
-  return check_launch("scaled_apply_kernel");
+  return launch_scaled_decide_apply(w, total, params, buf, st, growth, backoff, growth_interval, lr, momentum, dampening, weight_decay, nesterov, s);
 }
 
 }  // namespace clipmi

@@ -147,6 +147,28 @@ struct ScalerCall {
   int interval;
 };
 int launch_grad_scale_rows(const char* who, float* x, int rows, int cols, const clipmi_scaler_state* st, hipStream_t s);
+// the workspace of one scaled step over `total` elements: the decision record (found, first applied step) | one flag per workgroup of
+// SCALED_THREADS elements of the step's first launch | the unscaled gradient
+constexpr int SCALED_THREADS = 256;
+struct ScaledWs {
+  int32_t* decision;   // [2]
+  int32_t* flags;      // [blocks]
+  float* grad;         // [total]
+};
+inline int64_t scaled_grad_blocks(int64_t total) { return (total + SCALED_THREADS - 1) / SCALED_THREADS; }
+inline size_t scaled_step_bytes(int64_t total) { return 256 + align256((size_t)scaled_grad_blocks(total) * 4) + align256((size_t)total * 4); }
+inline ScaledWs scaled_carve(void* ws, int64_t total) {
+  char* p = static_cast<char*>(ws);
+  ScaledWs w;
+  w.decision = reinterpret_cast<int32_t*>(p);
+  w.flags = reinterpret_cast<int32_t*>(p + 256);
+  w.grad = reinterpret_cast<float*>(p + 256 + align256((size_t)scaled_grad_blocks(total) * 4));
+  return w;
+}
+int check_scaler(const char* who, const clipmi_scaler_state* st, float growth, float backoff, int growth_interval);
+// the decision launch and the step launch of a scaled step whose own first launch has filled w.grad and w.flags (proda_train.hip)
+int launch_scaled_decide_apply(const ScaledWs& w, int64_t total, float* params, float* buf, clipmi_scaler_state* st, float growth, float backoff,
+                               int growth_interval, const float* lr, float momentum, float dampening, float weight_decay, int nesterov, hipStream_t s);
 size_t block_step_scaled_bytes(int64_t total);   // 0 for a total the step refuses
 int check_block_step_scaled(const char* who, const float* grad, const float* params, const float* buf, const float* grad_out, const float* lr, int64_t total,
                             const clipmi_scaler_state* st, float growth, float backoff, int growth_interval, float momentum, float dampening,

@@ -12,6 +12,8 @@
 //   proda_nc_grad_kernel
 //   proda_grad_kernel          d_text of one class's Pb rows; workgroup 0 also forms the three losses
 //   proda_ctx_step_kernel      the context's gradient (classes ascending, the no-class row last) and the SGD rule
+//   proda_scaled_grad_kernel   the same gradient under the dynamic loss scale: divided by the device scale, into the scaled step's workspace with
+//                              one found-non-finite flag per workgroup; grad_scaler.hip's decision and step launches follow it
 // Notation: N = C Pb + P text rows; row c Pb + q is class c with the q-th selected context, row C Pb + p the no-class prompt of context p.
 // No float atomics and no workgroup waits for another: the same inputs give the same bits.
 #include <cmath>
@@ -366,12 +368,9 @@ int enqueue_head(const float* feats, int64_t ld, const int64_t* labels, const fl
 // one thread per element (p, j, d) of ctx [P, n_ctx, D].  If p is selected at slot q: the rows of the C class prompts that hold context
 // vector j, c ascending; then, always, the no-class prompt's row 1 + j, added last; 1 / grad_scale; torch.optim.SGD's rule as torch's GPU
 // kernels round it (sgd_element_fma).  A context outside the selection still moves by the no-class term, weight decay and momentum.
-__global__ __launch_bounds__(THREADS) void proda_ctx_step_kernel(const float* __restrict__ d_embed, float* __restrict__ ctx, float* __restrict__ buf,
-                                                                 float* __restrict__ grad_out, const int32_t* __restrict__ sel, const int32_t* __restrict__ pos,
-                                                                 const int32_t* __restrict__ name_lens, int C, int Pb, int P, int L, int D, int n_ctx,
-                                                                 float inv_scale, const float* __restrict__ lr, SgdArgs sgd) {
-  const int64_t idx = (int64_t)blockIdx.x * THREADS + threadIdx.x;
-  if (idx >= (int64_t)P * n_ctx * D) return;
+__device__ __forceinline__ float proda_grad_element(const float* __restrict__ d_embed, int64_t idx, const int32_t* __restrict__ sel,
+                                                    const int32_t* __restrict__ pos, const int32_t* __restrict__ name_lens, int C, int Pb, int L, int D,
+                                                    int n_ctx, float inv_scale) {
   const int d = (int)(idx % D), j = (int)((idx / D) % n_ctx), p = (int)(idx / ((int64_t)n_ctx * D));
   int slot = -1;
   for (int q = 0; q < Pb; ++q)
@@ -385,9 +384,38 @@ __global__ __launch_bounds__(THREADS) void proda_ctx_step_kernel(const float* __
     }
   }
   g += d_embed[(((int64_t)C * Pb + p) * L + 1 + j) * D + d];
-  g *= inv_scale;
+  return g * inv_scale;
+}
+
+__global__ __launch_bounds__(THREADS) void proda_ctx_step_kernel(const float* __restrict__ d_embed, float* __restrict__ ctx, float* __restrict__ buf,
+                                                                 float* __restrict__ grad_out, const int32_t* __restrict__ sel, const int32_t* __restrict__ pos,
+                                                                 const int32_t* __restrict__ name_lens, int C, int Pb, int P, int L, int D, int n_ctx,
+                                                                 float inv_scale, const float* __restrict__ lr, SgdArgs sgd) {
+  const int64_t idx = (int64_t)blockIdx.x * THREADS + threadIdx.x;
+  if (idx >= (int64_t)P * n_ctx * D) return;
+  const float g = proda_grad_element(d_embed, idx, sel, pos, name_lens, C, Pb, L, D, n_ctx, inv_scale);
   if (grad_out) grad_out[idx] = g;
   if (ctx) sgd_element_fma(ctx, buf, idx, g, *lr, sgd);
+}
+
+// The same gradient under the dynamic loss scale (grad_scaler.hip, model.h): 1 / state->scale read on the device, the unscaled gradient into
+// the step's workspace and into grad_out, and the workgroup's flag set when any element it produced is an inf or a NaN.  Every context
+// takes part: an unselected one is its no-class row.  A row of d_embed that no context vector sits on is never read.
+static_assert(THREADS == SCALED_THREADS, "one found-non-finite flag per workgroup of the gradient launch");
+__global__ __launch_bounds__(THREADS) void proda_scaled_grad_kernel(const float* __restrict__ d_embed, float* __restrict__ grad_out,
+                                                                    const int32_t* __restrict__ sel, const int32_t* __restrict__ pos,
+                                                                    const int32_t* __restrict__ name_lens, int C, int Pb, int P, int L, int D, int n_ctx,
+                                                                    const clipmi_scaler_state* __restrict__ st, ScaledWs w) {
+  const int64_t idx = (int64_t)blockIdx.x * THREADS + threadIdx.x;
+  int bad = 0;
+  if (idx < (int64_t)P * n_ctx * D) {
+    const float g = proda_grad_element(d_embed, idx, sel, pos, name_lens, C, Pb, L, D, n_ctx, 1.f / st->scale);
+    w.grad[idx] = g;
+    if (grad_out) grad_out[idx] = g;
+    bad = !isfinite(g);
+  }
+  bad = __syncthreads_or(bad);
+  if (threadIdx.x == 0) w.flags[blockIdx.x] = bad ? 1 : 0;
 }
 
 int check_ctx_step(const char* who, const float* d_embed, float* ctx, float* buf, float* grad_out, const int32_t* sel, const int32_t* pos,
@@ -414,6 +442,34 @@ int enqueue_ctx_step(const float* d_embed, float* ctx, float* buf, float* grad_o
   hipLaunchKernelGGL(proda_ctx_step_kernel, dim3((unsigned)((total + THREADS - 1) / THREADS)), dim3(THREADS), 0, s, d_embed, ctx, buf, grad_out, sel, pos,
                      name_lens, C, Pb, P, L, D, n_ctx, 1.f / grad_scale, lr, make_sgd_args(momentum, dampening, weight_decay, nesterov, first_step));
   return check_launch("proda_ctx_step_kernel");
+}
+
+// everything clipmi_proda_ctx_step_scaled refuses, before anything is launched: clipmi_proda_ctx_step's refusals (at a scale of 1: the
+// real one lives on the device) together with clipmi_ctx_step_scaled's
+int check_ctx_step_scaled(const char* who, const float* d_embed, float* ctx, float* buf, float* grad_out, const int32_t* sel, const int32_t* pos,
+                          const int32_t* name_lens, int C, int Pb, int P, int L, int D, int n_ctx, const ScalerCall& sc, const float* lr, float momentum,
+                          float dampening, float weight_decay, int nesterov, const void* workspace, size_t workspace_bytes) {
+  CLIPMI_REQUIRE(ctx && lr && workspace, CLIPMI_ERR_ARG, "%s: null pointer (ctx, lr and the workspace are required)", who);
+  if (int rc = check_scaler(who, sc.state, sc.growth, sc.backoff, sc.interval)) return rc;
+  if (int rc = check_ctx_step(who, d_embed, ctx, buf, grad_out, sel, pos, name_lens, C, Pb, P, L, D, n_ctx, 1.f, lr, 0, momentum, dampening, weight_decay,
+                              nesterov))
+    return rc;
+  CLIPMI_REQUIRE((uintptr_t)workspace % 256 == 0, CLIPMI_ERR_ARG, "%s: the workspace must be 256-byte aligned", who);
+  const size_t need = scaled_step_bytes((int64_t)P * n_ctx * D);
+  CLIPMI_REQUIRE(workspace_bytes >= need, CLIPMI_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, need);
+  return CLIPMI_OK;
+}
+
+// the three launches: the caller has passed check_ctx_step_scaled
+int enqueue_ctx_step_scaled(const float* d_embed, float* ctx, float* buf, float* grad_out, const int32_t* sel, const int32_t* pos, const int32_t* name_lens,
+                            int C, int Pb, int P, int L, int D, int n_ctx, const ScalerCall& sc, const float* lr, float momentum, float dampening,
+                            float weight_decay, int nesterov, void* workspace, hipStream_t s) {
+  const int64_t total = (int64_t)P * n_ctx * D;
+  const ScaledWs w = scaled_carve(workspace, total);
+  hipLaunchKernelGGL(proda_scaled_grad_kernel, dim3((unsigned)scaled_grad_blocks(total)), dim3(THREADS), 0, s, d_embed, grad_out, sel, pos, name_lens, C, Pb, P,
+                     L, D, n_ctx, (const clipmi_scaler_state*)sc.state, w);
+  if (int rc = check_launch("proda_scaled_grad_kernel")) return rc;
+  return launch_scaled_decide_apply(w, total, ctx, buf, sc.state, sc.growth, sc.backoff, sc.interval, lr, momentum, dampening, weight_decay, nesterov, s);
 }
 
 }  // namespace
@@ -450,8 +506,25 @@ int clipmi_proda_ctx_step(const float* d_embed, float* ctx, float* buf, float* g
                           weight_decay, nesterov, (hipStream_t)stream);
 }
 
+size_t clipmi_proda_ctx_step_scaled_workspace_bytes(int P, int D, int n_ctx) {
+  if (P < 2 || D < 1 || n_ctx < 1 || (int64_t)P * n_ctx * D >= (1ll << 31)) return 0;
+  return scaled_step_bytes((int64_t)P * n_ctx * D);
+}
+
+int clipmi_proda_ctx_step_scaled(const float* d_embed, float* ctx, float* buf, float* grad_out, const int32_t* sel, const int32_t* pos,
+                                 const int32_t* name_lens, int C, int Pb, int P, int L, int D, int n_ctx, clipmi_scaler_state* state, float growth_factor,
+                                 float backoff_factor, int growth_interval, const float* lr, float momentum, float dampening, float weight_decay,
+                                 int nesterov, void* workspace, size_t workspace_bytes, clipmi_stream_t stream) {
+  const ScalerCall sc{state, growth_factor, backoff_factor, growth_interval};
+  if (int rc = check_ctx_step_scaled("proda_ctx_step_scaled", d_embed, ctx, buf, grad_out, sel, pos, name_lens, C, Pb, P, L, D, n_ctx, sc, lr, momentum,
+                                     dampening, weight_decay, nesterov, workspace, workspace_bytes))
+    return rc;
+  return enqueue_ctx_step_scaled(d_embed, ctx, buf, grad_out, sel, pos, name_lens, C, Pb, P, L, D, n_ctx, sc, lr, momentum, dampening, weight_decay, nesterov,
+                                 workspace, (hipStream_t)stream);
+}
+
 // workspace: the tower's workspace (N prompts) | prompts fp32 [N, Lc, D] | EOT int32 [N] | text features [N, E] | their gradient [N, E] |
-// d_embed [N L, D] | the head's workspace
+// d_embed [N L, D] | the head's workspace; the scaled step's own behind them
 size_t clipmi_proda_train_step_bytes(const clipmi_model* m, int C, int Pb, int P, int seq_rows, int B) {
   size_t ws = 0;
   if (!m || C < 2 || P < 2 || Pb < 1 || Pb > P || B < 1 || (int64_t)C * Pb + P >= (1ll << 31) / m->g.context_length) return 0;
@@ -462,17 +535,28 @@ size_t clipmi_proda_train_step_bytes(const clipmi_model* m, int C, int Pb, int P
          align256((size_t)N * live_rows(m, seq_rows) * m->g.text_width * 4) + clipmi_proda_head_workspace_bytes(B, m->g.embed_dim, C, Pb, P);
 }
 
-int clipmi_proda_train_step(clipmi_model* m, const clipmi_text_dgrad* wt, const void* base, const void* nc_base, int dtype, float* ctx, float* buf, int n_ctx,
-                            const int32_t* sel, const int32_t* pos, const int32_t* name_lens, const int32_t* cls_eot, int C, int Pb, int P, int seq_rows,
-                            const float* feats, int64_t ld, const int64_t* labels, int B, float scale, float grad_scale, float alpha, const float* lr, int first_step,
-                            float momentum, float dampening, float weight_decay, int nesterov, float* losses, float* grad_out, void* workspace,
-                            size_t workspace_bytes, void* stash, size_t stash_bytes, clipmi_stream_t stream) {
-  const char* who = "proda_train_step";
-  hipStream_t s = (hipStream_t)stream;
+size_t clipmi_proda_train_step_scaled_bytes(const clipmi_model* m, int C, int Pb, int P, int seq_rows, int B, int n_ctx) {
+  const size_t base = clipmi_proda_train_step_bytes(m, C, Pb, P, seq_rows, B);
+  const size_t step = m ? clipmi_proda_ctx_step_scaled_workspace_bytes(P, m->g.text_width, n_ctx) : 0;
+  return base && step ? base + step : 0;
+}
+
+}  // extern "C"
+
+namespace clipmi {
+namespace {
+
+// both one-call steps.  sc == nullptr: the static one at grad_scale.  Otherwise the head runs at grad_scale = 1, its d_text is multiplied
+// by the device scale before the backward rounds it to fp16, and the step is the scaled one (grad_scale and first_step are not used)
+int train_step(const char* who, clipmi_model* m, const clipmi_text_dgrad* wt, const void* base, const void* nc_base, int dtype, float* ctx, float* buf,
+               int n_ctx, const int32_t* sel, const int32_t* pos, const int32_t* name_lens, const int32_t* cls_eot, int C, int Pb, int P, int seq_rows,
+               const float* feats, int64_t ld, const int64_t* labels, int B, float scale, float grad_scale, const ScalerCall* sc, float alpha,
+               const float* lr, int first_step, float momentum, float dampening, float weight_decay, int nesterov, float* losses, float* grad_out,
+               void* workspace, size_t workspace_bytes, void* stash, size_t stash_bytes, hipStream_t s) {
   CLIPMI_REQUIRE(m, CLIPMI_ERR_ARG, "%s: null model", who);
   CLIPMI_REQUIRE(ctx && lr && losses, CLIPMI_ERR_ARG, "%s: null pointer (ctx, lr and losses are required)", who);
-  const size_t need = clipmi_proda_train_step_bytes(m, C, Pb, P, seq_rows, B);
-  CLIPMI_REQUIRE(need > 0, CLIPMI_ERR_SHAPE, "%s: C=%d (>= 2), Pb=%d (1 .. P), P=%d (>= 2), B=%d (>= 1)", who, C, Pb, P, B);
+  const size_t need = sc ? clipmi_proda_train_step_scaled_bytes(m, C, Pb, P, seq_rows, B, n_ctx) : clipmi_proda_train_step_bytes(m, C, Pb, P, seq_rows, B);
+  CLIPMI_REQUIRE(need > 0, CLIPMI_ERR_SHAPE, "%s: C=%d (>= 2), Pb=%d (1 .. P), P=%d (>= 2), B=%d (>= 1)%s", who, C, Pb, P, B, sc ? ", n_ctx >= 1" : "");
   CLIPMI_REQUIRE(workspace_bytes >= need, CLIPMI_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, need);
   const int N = C * Pb + P;
   size_t tower = 0;
@@ -482,6 +566,7 @@ int clipmi_proda_train_step(clipmi_model* m, const clipmi_text_dgrad* wt, const 
   const int Lc = m->g.context_length, L = live_rows(m, seq_rows), D = m->g.text_width, E = m->g.embed_dim;
   CLIPMI_REQUIRE(L <= AB_MAX_L, CLIPMI_ERR_SHAPE, "%s: %d token rows per prompt (at most %d)", who, L, AB_MAX_L);
   const size_t head_bytes = clipmi_proda_head_workspace_bytes(B, E, C, Pb, P);
+  const size_t step_bytes = sc ? clipmi_proda_ctx_step_scaled_workspace_bytes(P, D, n_ctx) : 0;
   Carver c(static_cast<char*>(workspace) + tower);
   float* prompts = c.take<float>((size_t)N * Lc * D * 4);
   int32_t* eot = c.take<int32_t>((size_t)N * 4);
@@ -489,19 +574,60 @@ int clipmi_proda_train_step(clipmi_model* m, const clipmi_text_dgrad* wt, const 
   float* d_text = c.take<float>((size_t)N * E * 4);
   float* d_embed = c.take<float>((size_t)N * L * D * 4);
   void* head_ws = c.take<char>(head_bytes);
-  // every refusal of the five stages comes before the first launch: a refused call enqueues nothing
+  void* step_ws = sc ? c.take<char>(step_bytes) : nullptr;
+  const float head_scale = sc ? 1.f : grad_scale;
+  // every refusal of every stage comes before the first launch: a refused call enqueues nothing
   if (int rc = check_embed(who, base, nc_base, dtype, ctx, sel, pos, name_lens, cls_eot, prompts, eot, C, Pb, P, L, Lc, D, n_ctx)) return rc;
   if (int rc = check_train_inputs(who, m, prompts, CLIPMI_F32, nullptr, 0, eot, seq_rows, nullptr, 0)) return rc;
-  if (int rc = check_head(who, feats, ld, labels, text, B, E, C, Pb, P, scale, grad_scale, alpha, losses, d_text, head_ws, head_bytes)) return rc;
-  if (int rc = check_ctx_step(who, d_embed, ctx, buf, grad_out, sel, pos, name_lens, C, Pb, P, L, D, n_ctx, grad_scale, lr, first_step, momentum, dampening,
-                              weight_decay, nesterov))
+  if (int rc = check_head(who, feats, ld, labels, text, B, E, C, Pb, P, scale, head_scale, alpha, losses, d_text, head_ws, head_bytes)) return rc;
+  if (sc) {
+    if (int rc = check_ctx_step_scaled(who, d_embed, ctx, buf, grad_out, sel, pos, name_lens, C, Pb, P, L, D, n_ctx, *sc, lr, momentum, dampening,
+                                       weight_decay, nesterov, step_ws, step_bytes))
+      return rc;
+  } else if (int rc = check_ctx_step(who, d_embed, ctx, buf, grad_out, sel, pos, name_lens, C, Pb, P, L, D, n_ctx, grad_scale, lr, first_step, momentum,
+                                     dampening, weight_decay, nesterov)) {
     return rc;
+  }
   if (int rc = enqueue_embed(base, nc_base, dtype, ctx, sel, pos, name_lens, cls_eot, prompts, eot, C, Pb, P, L, Lc, D, n_ctx, s)) return rc;
   if (int rc = run_train_forward(m, prompts, CLIPMI_F32, nullptr, 0, 0, eot, N, seq_rows, text, workspace, stash, s)) return rc;
-  if (int rc = enqueue_head(feats, ld, labels, text, B, E, C, Pb, P, scale, grad_scale, alpha, losses, d_text, head_ws, s)) return rc;
+  if (int rc = enqueue_head(feats, ld, labels, text, B, E, C, Pb, P, scale, head_scale, alpha, losses, d_text, head_ws, s)) return rc;
+  if (sc) {
+    if (int rc = launch_grad_scale_rows(who, d_text, N, E, sc->state, s)) return rc;
+  }
   if (int rc = run_backward(m, wt, d_text, N, seq_rows, d_embed, workspace, stash, nullptr, s)) return rc;
+  if (sc)
+    return enqueue_ctx_step_scaled(d_embed, ctx, buf, grad_out, sel, pos, name_lens, C, Pb, P, L, D, n_ctx, *sc, lr, momentum, dampening, weight_decay, nesterov,
+                                   step_ws, s);
   return enqueue_ctx_step(d_embed, ctx, buf, grad_out, sel, pos, name_lens, C, Pb, P, L, D, n_ctx, grad_scale, lr, first_step, momentum, dampening, weight_decay,
                           nesterov, s);
+}
+
+}  // namespace
+}  // namespace clipmi
+
+extern "C" {
+
+int clipmi_proda_train_step(clipmi_model* m, const clipmi_text_dgrad* wt, const void* base, const void* nc_base, int dtype, float* ctx, float* buf, int n_ctx,
+                            const int32_t* sel, const int32_t* pos, const int32_t* name_lens, const int32_t* cls_eot, int C, int Pb, int P, int seq_rows,
+                            const float* feats, int64_t ld, const int64_t* labels, int B, float scale, float grad_scale, float alpha, const float* lr, int first_step,
+                            float momentum, float dampening, float weight_decay, int nesterov, float* losses, float* grad_out, void* workspace,
+                            size_t workspace_bytes, void* stash, size_t stash_bytes, clipmi_stream_t stream) {
+  return train_step("proda_train_step", m, wt, base, nc_base, dtype, ctx, buf, n_ctx, sel, pos, name_lens, cls_eot, C, Pb, P, seq_rows, feats, ld, labels, B, scale,
+                    grad_scale, nullptr, alpha, lr, first_step, momentum, dampening, weight_decay, nesterov, losses, grad_out, workspace, workspace_bytes, stash,
+                    stash_bytes, (hipStream_t)stream);
+}
+
+int clipmi_proda_train_step_scaled(clipmi_model* m, const clipmi_text_dgrad* wt, const void* base, const void* nc_base, int dtype, float* ctx, float* buf,
+                                   int n_ctx, const int32_t* sel, const int32_t* pos, const int32_t* name_lens, const int32_t* cls_eot, int C, int Pb, int P,
+                                   int seq_rows, const float* feats, int64_t ld, const int64_t* labels, int B, float scale, clipmi_scaler_state* state,
+                                   float growth_factor, float backoff_factor, int growth_interval, float alpha, const float* lr, float momentum,
+                                   float dampening, float weight_decay, int nesterov, float* losses, float* grad_out, void* workspace, size_t workspace_bytes,
+                                   void* stash, size_t stash_bytes, clipmi_stream_t stream) {
+  const ScalerCall sc{state, growth_factor, backoff_factor, growth_interval};
+  if (int rc = check_scaler("proda_train_step_scaled", state, growth_factor, backoff_factor, growth_interval)) return rc;
+  return train_step("proda_train_step_scaled", m, wt, base, nc_base, dtype, ctx, buf, n_ctx, sel, pos, name_lens, cls_eot, C, Pb, P, seq_rows, feats, ld, labels, B,
+                    scale, 1.f, &sc, alpha, lr, 0, momentum, dampening, weight_decay, nesterov, losses, grad_out, workspace, workspace_bytes, stash, stash_bytes,
+                    (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -1276,6 +1276,38 @@ def proda_ctx_step(d_embed: torch.Tensor, sel: torch.Tensor, pos: torch.Tensor, 
     return grad
 
 
+def proda_ctx_step_scaled(d_embed: torch.Tensor, sel: torch.Tensor, pos: torch.Tensor, name_lens: torch.Tensor, n_ctx: int, state: torch.Tensor,
+                          ctx: torch.Tensor, buf: Optional[torch.Tensor], lr: torch.Tensor, growth_factor: float = 2.0, backoff_factor: float = 0.5,
+                          growth_interval: int = 2000, momentum: float = 0.0, dampening: float = 0.0, weight_decay: float = 0.0,
+                          nesterov: bool = False, want_grad: bool = True, workspace: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
+    """``proda_ctx_step`` under the dynamic loss scale of ``state`` (``new_scaler_state``), as ``ctx_step_scaled`` is ``ctx_step``'s: the
+    gather-reduce divided by the block's scale; a gradient with an inf or a NaN -- in a selected context's class rows or in any
+    context's no-class row -- leaves ``ctx`` and ``buf`` as they are and backs the scale off, a clean one is applied (the momentum
+    buffer starts on the first applied step) and counts towards the next growth.  Nothing is read back.  ``workspace``: a uint8 tensor
+    to reuse between steps.  Returns the unscaled gradient [P, n_ctx, D] when ``want_grad``."""
+    who = "proda_ctx_step_scaled"
+    d_embed = _dev(d_embed, "d_embed", (torch.float32,))
+    sel, pos, name_lens = (_dev(t, n, (torch.int32,)) for t, n in ((sel, "sel"), (pos, "pos"), (name_lens, "name_lens")))
+    Pb, P, Cn = int(sel.numel()), int(pos.numel()), int(name_lens.numel())
+    N = Cn * Pb + P
+    if d_embed.dim() != 2 or d_embed.shape[0] % N:
+        raise ValueError(f"{who}: d_embed {tuple(d_embed.shape)} does not split into {N} prompts")
+    if ctx is None:
+        raise ValueError(f"{who}: ctx is required (the step decides whether to write it)")
+    L = d_embed.shape[0] // N
+    _, D, _, pc, pb, pl = _ctx_step_inputs(who, d_embed[(N - P) * L:], P, n_ctx, True, ctx, buf, lr)
+    ps = _scaler_state(who, state)
+    grad = torch.empty(P, int(n_ctx), D, dtype=torch.float32, device=d_embed.device) if want_grad else None
+    need = lib.clipmi_proda_ctx_step_scaled_workspace_bytes(P, D, int(n_ctx))
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=d_embed.device)
+    check(lib.clipmi_proda_ctx_step_scaled(d_embed.data_ptr(), pc, pb, None if grad is None else grad.data_ptr(), sel.data_ptr(), pos.data_ptr(),
+                                           name_lens.data_ptr(), Cn, Pb, P, L, D, int(n_ctx), ps, float(growth_factor), float(backoff_factor),
+                                           int(growth_interval), pl, float(momentum), float(dampening), float(weight_decay), int(bool(nesterov)),
+                                           workspace.data_ptr(), workspace.numel(), _stream()), "clipmi_proda_ctx_step_scaled")
+    return grad
+
+
 def cocoop_block_layout(n_ctx: int, D: int, E: int, H: int):
     """The offsets, in floats, of ``ctx | W1 | b1 | W2 | b2`` in CoCoOp's parameter block, and its size: a dict name -> (offset, shape),
     the names those of the reference's ``state_dict``, and the total (clipmi_cocoop_block_floats)."""

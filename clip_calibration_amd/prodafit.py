@@ -25,8 +25,17 @@ prompts, more than 80 live token rows (the backward's limit).
 
 UNVERIFIED, as for CoOp: Dassl is not part of this environment, so the defaults -- SGD at 0.002 with momentum 0.9 and weight decay 5e-4,
 batches of 32, 32 prompts in slices of 4, 16 context vectors from N(0, 0.02^2), alpha = 0.1 -- restate the reference's configs and
-Dassl's public defaults without a run of the reference behind them; each is an argument.  Not covered: the reference's ``amp`` branch
-and ``nn.DataParallel`` over the text encoder (one process drives one GPU).
+Dassl's public defaults without a run of the reference behind them; each is an argument.  Not covered: ``nn.DataParallel`` over the text
+encoder (one process drives one GPU).
+
+``grad_scale="dynamic"`` with ``scaler=dict(init_scale, growth_factor, backoff_factor, growth_interval)`` is the reference's ``prec ==
+"amp"`` branch (proda.py:370, 388-394, ``torch.cuda.amp.GradScaler``) with the scale in a device block, as ``coopfit``'s: the head runs at
+``grad_scale = 1``, its fp32 ``d_text`` is multiplied by the block's scale before the backward rounds it to fp16, and
+clipmi_proda_ctx_step_scaled forms the unscaled gradient of all P contexts, skips the step when any element -- a selected context's
+class rows or any context's no-class row -- is an inf or a NaN, and updates the scale by torch's rule.  The selection schedule
+advances on a skipped step as on an applied one (the reference draws it in the forward, before ``GradScaler.step`` decides).  No step
+reads anything back; ``ProDAFitState.scaler_state()`` does, once.  With a scale that never changes the dynamic path gives the static
+path's bits.  DESIGN.md "Dynamic loss scale for ProDA".
 """
 from __future__ import annotations
 
@@ -39,7 +48,7 @@ import torch
 
 from . import _lib, fitloop, ops
 from ._lib import check, lib
-from .coopfit import DEFAULT_GRAD_SCALE, MAX_LIVE_ROWS, _DT, _Tower, _check_batch, _check_grad_scale, _live_rows
+from .coopfit import DEFAULT_GRAD_SCALE, DYNAMIC, MAX_LIVE_ROWS, _DT, _Tower, _check_batch, _check_grad_scale, _is_dynamic, _live_rows, _scale_args
 from .fitloop import _host_int_array, _need_gpu, steps_per_epoch
 
 
@@ -167,8 +176,11 @@ class _ProDATower(_Tower):
                                                 _lib.CALL_DEFAULT, ops._stream()), "clipmi_text_encoder_train")
         return self.text
 
-    def one_call_workspace(self, B: int) -> torch.Tensor:
-        need = lib.clipmi_proda_train_step_bytes(self.model._handle, self.n_cls, self.Pb, self.P, self.rows, B)
+    def one_call_workspace(self, B: int, scaled: bool = False) -> torch.Tensor:
+        if scaled:
+            need = lib.clipmi_proda_train_step_scaled_bytes(self.model._handle, self.n_cls, self.Pb, self.P, self.rows, B, self.n_ctx)
+        else:
+            need = lib.clipmi_proda_train_step_bytes(self.model._handle, self.n_cls, self.Pb, self.P, self.rows, B)
         if self.step_ws is None or self.step_ws.numel() < need:
             self.step_ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.ws.device)
         return self.step_ws
@@ -195,6 +207,8 @@ def context_gradient(clip_model, tokenized_prompts, ctx: torch.Tensor, features:
         raise ValueError(f"{who}: sel {sel_h.shape} must be one selection [prompt_bs]")
     _check_collection(who, P, len(sel_h))
     alpha = _check_alpha(who, alpha)
+    if _is_dynamic(who, grad_scale):
+        raise ValueError(f"{who}: grad_scale={DYNAMIC!r} belongs to a fit (ProDAFitState, fit_context); one gradient needs a number")
     gs = _check_grad_scale(who, grad_scale)
     if not math.isfinite(logit_scale):
         raise ValueError(f"{who}: logit_scale={logit_scale} (finite)")
@@ -220,13 +234,14 @@ class ProDAFitState:
 
     def __init__(self, clip_model, tokenized_prompts, ctx: torch.Tensor, prompt_bs: int = 4, alpha: float = 0.1, logit_scale: float = 4.6052,
                  momentum: float = 0.9, dampening: float = 0.0, nesterov: bool = False, weight_decay: float = 5e-4,
-                 grad_scale: float = DEFAULT_GRAD_SCALE, seq_rows: Optional[int] = None, name_lens=None, generator: Optional[torch.Generator] = None):
+                 grad_scale: float = DEFAULT_GRAD_SCALE, seq_rows: Optional[int] = None, name_lens=None, generator: Optional[torch.Generator] = None,
+                 scaler: Optional[dict] = None):
         who = "ProDAFitState"
         ids_all, self.C, self.P, self.n_ctx, nl, last = _check_prompts(who, clip_model, tokenized_prompts, ctx, name_lens, seq_rows)
         self.Pb = int(prompt_bs)
         _check_collection(who, self.P, self.Pb)
         self.alpha = _check_alpha(who, alpha)
-        self.grad_scale = _check_grad_scale(who, grad_scale)
+        self.dynamic, self.grad_scale, self.scaler = _scale_args(who, grad_scale, scaler)
         fitloop.check_sgd(who, momentum, dampening, weight_decay, nesterov)
         if not math.isfinite(logit_scale):
             raise ValueError(f"{who}: logit_scale={logit_scale} (finite)")
@@ -240,6 +255,16 @@ class ProDAFitState:
         self.pos_host = positions(self.P)
         self._perm = None
         self.steps = 0
+        if self.dynamic:
+            self.scaler_block = ops.new_scaler_state(self.scaler["init_scale"], dev)   # clipmi_scaler_state; only the kernels touch it from here on
+            self.scaled_ws = None
+
+    def scaler_state(self) -> dict:
+        """The dynamic scale's block as ``dict(scale, growth_tracker, skipped_steps, applied_steps, found_inf)`` (``found_inf``: of the
+        last step).  It waits for the steps enqueued so far: one synchronisation, the only read-back of the dynamic path."""
+        if not self.dynamic:
+            raise ValueError(f"ProDAFitState.scaler_state: the state was made with a static grad_scale={self.grad_scale}")
+        return ops.scaler_state_dict(self.scaler_block)
 
     def next_selection(self) -> np.ndarray:
         """The schedule's next slice (``draw_selections``, one step at a time)."""
@@ -256,7 +281,9 @@ class ProDAFitState:
         them.  ``sel``: this step's contexts -- None draws the schedule's next slice on the host; an int32 tensor [prompt_bs] on the
         GPU is taken as it is, already in the reference's order (a bad entry then poisons the context with NaN, it is never an
         address); anything else is checked and ordered on the host.  ``one_call``: the same launches through
-        clipmi_proda_train_step.  Returns the batch loss, fp32 [1] on the device, when ``want_loss``."""
+        clipmi_proda_train_step (clipmi_proda_train_step_scaled under the dynamic scale).  Returns the batch loss, fp32 [1] on the device,
+        when ``want_loss``.  Under the dynamic scale a skipped step still counts in ``steps`` -- the selection schedule moves on -- and
+        still returns its loss; whether it was applied is in ``scaler_state()``."""
         who = "ProDAFitState.step"
         labels_d = _check_batch(who, features, labels, self.C, self.tower.E)
         _need_gpu(features, "features")
@@ -276,7 +303,9 @@ class ProDAFitState:
         t, m, first = self.tower, self.tower.model, self.steps == 0
         sgd = (self.momentum, self.dampening, self.weight_decay, self.nesterov)
         losses = torch.empty(3, dtype=torch.float32, device=dev)
-        if one_call:
+        if self.dynamic:
+            self._step_scaled(features, labels_d, sel_d, lr_d, losses, one_call)
+        elif one_call:
             ws = t.one_call_workspace(features.shape[0])
             with m._launch_lock:
                 check(lib.clipmi_proda_train_step(m._handle, C.byref(t.dgrad[0]), t.cls_base.data_ptr(), t.nc_base.data_ptr(), _DT[t.base.dtype],
@@ -294,6 +323,33 @@ class ProDAFitState:
         self.steps += 1
         return losses[0:1] if want_loss else None
 
+    def _step_scaled(self, features, labels_d, sel_d, lr_d, losses, one_call: bool) -> None:
+        """``step`` under the dynamic scale: the head at grad_scale = 1, its d_text times the block's scale, the backward, and
+        clipmi_proda_ctx_step_scaled, which decides on the device whether the step is applied."""
+        t, m, sc = self.tower, self.tower.model, self.scaler
+        sgd = (float(self.momentum), float(self.dampening), float(self.weight_decay), int(bool(self.nesterov)))
+        if one_call:
+            ws = t.one_call_workspace(features.shape[0], scaled=True)
+            with m._launch_lock:
+                check(lib.clipmi_proda_train_step_scaled(m._handle, C.byref(t.dgrad[0]), t.cls_base.data_ptr(), t.nc_base.data_ptr(), _DT[t.base.dtype],
+                                                         self.ctx.data_ptr(), None if self.buf is None else self.buf.data_ptr(), t.n_ctx,
+                                                         sel_d.data_ptr(), t.pos.data_ptr(), t.name_lens.data_ptr(), t.cls_eot.data_ptr(), t.n_cls, t.Pb,
+                                                         t.P, t.rows, features.data_ptr(), features.stride(0), labels_d.data_ptr(), features.shape[0],
+                                                         self.scale, self.scaler_block.data_ptr(), sc["growth_factor"], sc["backoff_factor"],
+                                                         sc["growth_interval"], self.alpha, lr_d.data_ptr(), *sgd, losses.data_ptr(), None,
+                                                         ws.data_ptr(), ws.numel(), t.stash.data_ptr(), t.stash.numel(), ops._stream()),
+                      "clipmi_proda_train_step_scaled")
+            return
+        text = t.forward(self.ctx, sel_d)
+        _, d_text = ops.proda_head(features, labels_d, text, t.n_cls, t.Pb, self.scale, 1.0, self.alpha, losses)
+        ops.grad_scale_rows(d_text, self.scaler_block)
+        d_embed = t.backward(d_text)
+        if self.scaled_ws is None:
+            need = lib.clipmi_proda_ctx_step_scaled_workspace_bytes(t.P, t.D, t.n_ctx)
+            self.scaled_ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.ctx.device)
+        ops.proda_ctx_step_scaled(d_embed, sel_d, t.pos, t.name_lens, t.n_ctx, self.scaler_block, self.ctx, self.buf, lr_d, sc["growth_factor"],
+                                  sc["backoff_factor"], sc["growth_interval"], *sgd[:3], bool(sgd[3]), want_grad=False, workspace=self.scaled_ws)
+
 
 def init_context(clip_model, n_ctx: int = 16, n_prompt: int = 32, seed: int = 0) -> torch.Tensor:
     """The reference's random initialisation (proda.py:93-94): N(0, 0.02^2), [n_prompt, n_ctx, D]."""
@@ -305,14 +361,16 @@ def fit_context(features: torch.Tensor, labels, clip_model, tokenized_prompts, c
                 prompt_bs: int = 4, alpha: float = 0.1, logit_scale: float = 4.6052, lr: float = 0.002, epochs: int = 200, batch_size: int = 32,
                 momentum: float = 0.9, dampening: float = 0.0, weight_decay: float = 5e-4, nesterov: bool = False,
                 grad_scale: float = DEFAULT_GRAD_SCALE, seq_rows: Optional[int] = None, lr_per_epoch: Optional[Sequence[float]] = None, order=None,
-                drop_last: bool = False, name_lens=None, selections=None, generator: Optional[torch.Generator] = None, return_history: bool = False):
+                drop_last: bool = False, name_lens=None, selections=None, generator: Optional[torch.Generator] = None, return_history: bool = False,
+                scaler: Optional[dict] = None, return_scaler_state: bool = False):
     """Train ProDA's contexts on cached ``features`` fp32 [N, E] and ``labels`` [N], starting from ``ctx`` [n_prompt, n_ctx, D] (not
     modified; None = ``init_context(clip_model, n_ctx, n_prompt)``).  The loop and its arguments are ``coopfit.fit_context``'s:
     ``epochs`` passes of ``torch.optim.SGD`` over batches of ``batch_size``, ``lr_per_epoch`` (None: ``cosine_warmup_schedule``),
     ``order`` [epochs, N], ``drop_last``; everything is checked on the host before the first launch and nothing synchronises until the
     one wait at the end.  ``selections``: an int array [steps, prompt_bs] that replaces the schedule drawn from ``generator`` (None: a
-    generator seeded with 0).  Returns the fitted fp32 contexts on the device, or ``(ctx, per-step total losses)`` with
-    ``return_history``.  The defaults are unverified restatements of the reference's config (module docstring)."""
+    generator seeded with 0).  ``grad_scale="dynamic"`` with ``scaler`` (module docstring): a step that overflows fp16 is skipped on the
+    device and the scale adapts; the schedule of rates and selections moves on over a skipped step.  Returns the fitted fp32 contexts on the device, or ``(ctx, per-step total losses)`` with
+    ``return_history``; ``return_scaler_state`` (dynamic only) appends ``ProDAFitState.scaler_state()`` as read after the last step.  The defaults are unverified restatements of the reference's config (module docstring)."""
     who = "fit_context"
     if ctx is None:
         _check_collection(who, int(n_prompt), int(prompt_bs))
@@ -325,7 +383,9 @@ def fit_context(features: torch.Tensor, labels, clip_model, tokenized_prompts, c
     N = features.shape[0]
     epochs, batch_size = fitloop.check_run(who, epochs, batch_size)
     fitloop.check_sgd(who, momentum, dampening, weight_decay, nesterov)
-    _check_grad_scale(who, grad_scale)
+    dynamic, _, cfg = _scale_args(who, grad_scale, scaler)
+    if return_scaler_state and not dynamic:
+        raise ValueError(f"{who}: return_scaler_state is an argument of grad_scale={DYNAMIC!r}")
     _check_alpha(who, alpha)
     lab = fitloop._labels(who, labels, N, Cn)
     order = fitloop.check_order(who, order, epochs, N)
@@ -342,12 +402,19 @@ def fit_context(features: torch.Tensor, labels, clip_model, tokenized_prompts, c
     if steps == 0:
         out = ctx.detach().to(torch.float32).clone()
         out = out.to(dev) if features.is_cuda else out
-        return (out, np.zeros(0, np.float32)) if return_history else out
+        out = (out, np.zeros(0, np.float32)) if return_history else out
+        if return_scaler_state:
+            untouched = {"scale": cfg["init_scale"], "growth_tracker": 0, "skipped_steps": 0, "applied_steps": 0, "found_inf": 0}
+            return (out + (untouched,)) if return_history else (out, untouched)
+        return out
     _need_gpu(features, "features")
     state = ProDAFitState(clip_model, tokenized_prompts, ctx, prompt_bs, alpha, logit_scale, momentum, dampening, nesterov, weight_decay, grad_scale,
-                          seq_rows, name_lens)
+                          seq_rows, name_lens, scaler=scaler)
     sels_d = torch.from_numpy(np.ascontiguousarray(sels, dtype=np.int32)).to(dev)
     history = fitloop.run_cached(lambda f, y, r, want: state.step(f, y, r, sel=sels_d[state.steps], want_loss=want), features,
                                  fitloop.labels_on(labels, lab, dev), fitloop.order_on(order, np.int64, dev), batch_size, per_epoch, epochs, lr_steps,
                                  return_history)
-    return (state.ctx, history) if return_history else state.ctx
+    out = (state.ctx, history) if return_history else (state.ctx,)
+    if return_scaler_state:
+        out = out + (state.scaler_state(),)
+    return out if len(out) > 1 else out[0]

@@ -100,7 +100,8 @@ class CustomCLIP(nn.Module):
         """Train ``prompt_learner.ctx`` on the GPU, starting from the parameter's values, with ``logit_scale`` taken from this model
         unless ``fit_args`` say otherwise (proda.py:258-304 with both towers frozen).  The fitted contexts are copied into
         ``prompt_learner.ctx`` in the parameter's dtype (the fit keeps an fp32 master) and the cached classifier is cleared, so the
-        next ``forward`` / ``set_classifier`` uses them; returned as ``prodafit.fit_context`` returns them.
+        next ``forward`` / ``set_classifier`` uses them; returned as ``prodafit.fit_context`` returns them.  ``grad_scale="dynamic"`` with
+        ``scaler=dict(...)`` in ``fit_args`` is the reference's ``prec == "amp"`` branch (proda.py:370, 388-394) on either route.
 
         ``transform=None``: one pass of ``train_loader`` (an iterable of (image, label) batches of preprocessed images) through the
         frozen image tower, then ``prodafit.fit_context(features, labels, clip_model, tokenized_prompts, ctx, **fit_args)`` -- equal to
@@ -110,6 +111,8 @@ class CustomCLIP(nn.Module):
         ``return_history`` and ``ProDAFitState``'s own."""
         import math
         fit_args.setdefault("logit_scale", math.log(self.scale))
+        dynamic = fit_args.get("grad_scale") == "dynamic"
+        self._scaler_state = None
         ctx = self.prompt_learner.ctx
         ids = self.prompt_learner.tokenized_prompts
         if transform is not None:
@@ -119,14 +122,26 @@ class CustomCLIP(nn.Module):
             state = ProDAFitState(self.clip_model, ids, ctx.detach(), **fit_args)
             losses = fit_with_transform(state, self.clip_model.image_features_f32, ids.shape[0], train_loader, transform, epochs, lr, **run)
             fitted = _fit.pack(state.ctx, losses)
+            if dynamic:
+                self._scaler_state = state.scaler_state()
         else:
             from ..prodafit import fit_context
             feats, labels = _fit.cached_features("fit_context", self.clip_model, train_loader)
-            fitted = fit_context(feats, labels, self.clip_model, ids, ctx.detach(), **fit_args)
+            fitted = fit_context(feats, labels, self.clip_model, ids, ctx.detach(), return_scaler_state=dynamic, **fit_args)
+            if dynamic:
+                *fitted, self._scaler_state = fitted
+                fitted = tuple(fitted) if len(fitted) > 1 else fitted[0]
         with torch.no_grad():
             ctx.copy_(fitted[0] if isinstance(fitted, tuple) else fitted)
         self.text_features = None
         return fitted
+
+    def scaler_state(self) -> dict:
+        """``ProDAFitState.scaler_state()`` of the last ``fit_context(..., grad_scale="dynamic")``, as read after its last step: ``dict(scale,
+        growth_tracker, skipped_steps, applied_steps, found_inf)``."""
+        if getattr(self, "_scaler_state", None) is None:
+            raise ValueError("ProDA CustomCLIP.scaler_state: no fit_context under grad_scale='dynamic' has run")
+        return dict(self._scaler_state)
 
     @torch.no_grad()
     def forward(self, image: torch.Tensor, label=None, dac_conf: Optional[torch.Tensor] = None, want_conf_pred: bool = False):

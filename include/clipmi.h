@@ -1281,7 +1281,30 @@ int clipmi_promptsrc_train_step_scaled(clipmi_model* m, const clipmi_text_dgrad*
  * clipmi_proda_train_step: the three above around clipmi_text_encoder_train and clipmi_text_encoder_backward as ONE call on `stream`
  *   -- the same launches, the same bits as the calls one by one.  workspace of clipmi_proda_train_step_bytes(...) bytes (256-byte
  *   aligned), stash as clipmi_text_train_bytes(m, C Pb + P, seq_rows, ...) reports it.  At most 80 live rows (the backward's limit).
- *   Every argument check of the five stages is made before the first launch: a refused call enqueues nothing. */
+ *   Every argument check of the five stages is made before the first launch: a refused call enqueues nothing.
+ *
+ * clipmi_proda_ctx_step_scaled: clipmi_proda_ctx_step under the scaler's rule (DESIGN.md "Dynamic loss scale for ProDA"), with `state` and
+ *   the scaler's three arguments in grad_scale's place, no first_step and a workspace.  Three launches, in clipmi_ctx_step_scaled's shape:
+ *     one thread per element of ctx, workgroups of 256: clipmi_proda_ctx_step's sum in its order (c ascending where p == sel[q], the
+ *       no-class row last) times 1 / state->scale, read on the device, into the workspace and into grad_out (may be NULL), and one integer
+ *       flag per workgroup, set when any element the workgroup produced is an inf or a NaN.  Every context takes part: of one outside the
+ *       selection the no-class row is looked at.  A row of d_embed that holds no context vector is not read;
+ *     clipmi_ctx_step_scaled's second launch: one workgroup ORs the flags, writes the decision and updates the state block by its rule;
+ *     clipmi_ctx_step_scaled's third launch: the SGD rule on ctx and buf over all P n_ctx D elements, only on a clean step; the momentum
+ *       buffer starts from the first APPLIED step (state->applied_steps == 0).
+ *   No atomics, no workgroup reads what another of the same launch writes, the same inputs give the same bits.  With the flags clear ctx,
+ *   buf and grad_out equal clipmi_proda_ctx_step's at grad_scale = scale and first_step = (applied_steps == 0) bit for bit.  A selection
+ *   outside [0, P) and a name length are read as there and are never an address.  ctx, lr, state and the workspace are required.
+ *   workspace (256-byte aligned): clipmi_proda_ctx_step_scaled_workspace_bytes(P, D, n_ctx) bytes, 0 for arguments the call refuses.
+ *   Every check precedes the first launch.  CLIPMI_ERR_ARG: a null pointer, a factor that is not finite or not positive,
+ *   growth_interval < 1, SGD's own refusals; CLIPMI_ERR_SHAPE: clipmi_proda_ctx_step's; CLIPMI_ERR_WORKSPACE.
+ *
+ * clipmi_proda_train_step_scaled: one step under the scaler as ONE call: clipmi_proda_embed, clipmi_text_encoder_train, clipmi_proda_head
+ *   at grad_scale = 1, clipmi_grad_scale_rows on its d_text (before anything rounds it to fp16), clipmi_text_encoder_backward and
+ *   clipmi_proda_ctx_step_scaled, enqueued in this order on `stream` -- the same launches, the same bits as the calls one by one; with a
+ *   scale that never changes, clipmi_proda_train_step's bits at that scale.  Arguments as clipmi_proda_train_step's.  Every stage's checks
+ *   precede the first launch.  workspace of clipmi_proda_train_step_scaled_bytes(...) bytes (256-byte aligned; 0 for arguments the call
+ *   refuses): clipmi_proda_train_step's, then the scaled step's. */
 int clipmi_proda_embed(const void* base, const void* nc_base, int dtype, const float* ctx, const int32_t* sel, const int32_t* pos,
                        const int32_t* name_lens, const int32_t* cls_eot, float* prompts, int32_t* eot, int C, int Pb, int P, int L, int Lc, int D, int n_ctx,
                        clipmi_stream_t stream);
@@ -1299,6 +1322,19 @@ int clipmi_proda_train_step(clipmi_model* m, const clipmi_text_dgrad* wt, const 
                             float alpha, const float* lr, int first_step, float momentum, float dampening, float weight_decay,
                             int nesterov, float* losses, float* grad_out, void* workspace, size_t workspace_bytes, void* stash,
                             size_t stash_bytes, clipmi_stream_t stream);
+size_t clipmi_proda_ctx_step_scaled_workspace_bytes(int P, int D, int n_ctx);
+int clipmi_proda_ctx_step_scaled(const float* d_embed, float* ctx, float* buf, float* grad_out, const int32_t* sel, const int32_t* pos,
+                                 const int32_t* name_lens, int C, int Pb, int P, int L, int D, int n_ctx, clipmi_scaler_state* state,
+                                 float growth_factor, float backoff_factor, int growth_interval, const float* lr, float momentum, float dampening,
+                                 float weight_decay, int nesterov, void* workspace, size_t workspace_bytes, clipmi_stream_t stream);
+size_t clipmi_proda_train_step_scaled_bytes(const clipmi_model* m, int C, int Pb, int P, int seq_rows, int B, int n_ctx);
+int clipmi_proda_train_step_scaled(clipmi_model* m, const clipmi_text_dgrad* wt, const void* base, const void* nc_base, int dtype, float* ctx,
+                                   float* buf, int n_ctx, const int32_t* sel, const int32_t* pos, const int32_t* name_lens,
+                                   const int32_t* cls_eot, int C, int Pb, int P, int seq_rows, const float* feats, int64_t ld,
+                                   const int64_t* labels, int B, float scale, clipmi_scaler_state* state, float growth_factor,
+                                   float backoff_factor, int growth_interval, float alpha, const float* lr, float momentum, float dampening,
+                                   float weight_decay, int nesterov, float* losses, float* grad_out, void* workspace, size_t workspace_bytes,
+                                   void* stash, size_t stash_bytes, clipmi_stream_t stream);
 
 /* CoCoOp's context and meta-net trained on the same frozen-tower backward (reference trainers/classification/cocoop.py:153-202, 259-278;
  * csrc/cocoop_train.hip, DESIGN.md "CoCoOp fit").  The five learned tensors live in ONE fp32 block of clipmi_cocoop_block_floats(n_ctx, D,
