@@ -127,9 +127,16 @@ def _scale_args(who: str, grad_scale, scaler):
     return False, _check_grad_scale(who, grad_scale), None
 
 
+def _static_prograd(who: str, method: str, grad_scale) -> None:
+    """ProGrad has no dynamic loss scale: its two gradients share one step."""
+    if method == "prograd" and _is_dynamic(who, grad_scale):
+        raise ValueError(f"{who}: grad_scale={DYNAMIC!r} covers method 'coop' and 'kgcoop'; ProGrad keeps a static scale")
+
+
 class _BlockScaler:
-    """The dynamic loss scale of a fit whose parameters are one fp32 master block (CoCoOp, VPT, MaPLe, PromptSRC): the device block
-    (clipmi_scaler_state; only the kernels touch it once it is made), the scaler's arguments and the block step's workspace."""
+    """The dynamic loss scale of a fit: the device block (clipmi_scaler_state; only the kernels touch it once it is made), the scaler's
+    arguments and the scaled step's workspace.  ``step`` is for the fits whose parameters are one fp32 master block (CoCoOp, VPT, MaPLe,
+    PromptSRC); CoOp's and ProDA's scaled steps are their own."""
 
     def __init__(self, cfg: dict, dev):
         self.cfg = cfg
@@ -444,16 +451,8 @@ class CoOpFitState:
         who = "CoOpFitState"
         self.C, self.n_ctx, self.per_class, last = _check_prompts(who, clip_model, tokenized_prompts, ctx)
         placement = _placement(who, tokenized_prompts, self.n_ctx, class_token_position, name_lens)
-        self.dynamic = _is_dynamic(who, grad_scale)
-        if self.dynamic:
-            if method == "prograd":
-                raise ValueError(f"{who}: grad_scale={DYNAMIC!r} covers method 'coop' and 'kgcoop'; ProGrad keeps a static scale")
-            self.scaler = _check_scaler(who, scaler)
-            self.grad_scale = None
-        else:
-            if scaler is not None:
-                raise ValueError(f"{who}: scaler is an argument of grad_scale={DYNAMIC!r}")
-            self.grad_scale = _check_grad_scale(who, grad_scale)
+        _static_prograd(who, method, grad_scale)
+        self.dynamic, self.grad_scale, self.scaler = _scale_args(who, grad_scale, scaler)
         fitloop.check_sgd(who, momentum, dampening, weight_decay, nesterov)
         if not math.isfinite(logit_scale):
             raise ValueError(f"{who}: logit_scale={logit_scale} (finite)")
@@ -470,44 +469,48 @@ class CoOpFitState:
         self.scale = float(np.float32(math.exp(logit_scale)))
         self.momentum, self.dampening, self.nesterov, self.weight_decay = momentum, dampening, nesterov, weight_decay
         self.steps = 0
-        if self.dynamic:
-            self.scaler_block = ops.new_scaler_state(self.scaler["init_scale"], dev)   # clipmi_scaler_state; only the kernels touch it from here on
-            self.scaled_ws = None
+        self._scaler = _BlockScaler(self.scaler, dev) if self.dynamic else None
 
     def scaler_state(self) -> dict:
         """The dynamic scale's block as ``dict(scale, growth_tracker, skipped_steps, applied_steps, found_inf)`` (``found_inf``: of the
         last step).  It waits for the steps enqueued so far: one synchronisation."""
         if not self.dynamic:
             raise ValueError(f"CoOpFitState.scaler_state: the state was made with a static grad_scale={self.grad_scale}")
-        return ops.scaler_state_dict(self.scaler_block)
+        return self._scaler.state()
 
-    def _step_scaled(self, features, labels_d, lr_d, losses, one_call: bool) -> None:
+    def _one_call(self, features, labels_d, lr_d, losses, first: bool) -> None:
+        """``step`` through the library's one-call step: one of four symbols (static or scaled, the class token at the end or placed) on
+        one run of arguments, each with its own tail."""
+        t, m, sc = self.tower, self.tower.model, self._scaler
+        ws = t.one_call_workspace(features.shape[0], self.method, scaled=self.dynamic)
+        name = "clipmi_prompt_train_step" + ("_scaled" if self.dynamic else "") + ("" if t.position is None else "_placed")
+        buf, teacher = (None if x is None else x.data_ptr() for x in (self.buf, self.teacher))
+        head = (m._handle, C.byref(t.dgrad[0]), t.base.data_ptr(), _DT[t.base.dtype], self.ctx.data_ptr(), buf, t.n_ctx, int(t.per_class),
+                *(() if t.position is None else (t.position, t.name_lens.data_ptr())), t.eot.data_ptr(), t.C, t.rows, features.data_ptr(),
+                features.stride(0), labels_d.data_ptr(), features.shape[0], self.scale)
+        sgd = (float(self.momentum), float(self.dampening), float(self.weight_decay), int(bool(self.nesterov)))
+        tail = (ws.data_ptr(), ws.numel(), t.stash.data_ptr(), t.stash.numel(), ops._stream())
+        mode = ops.PROMPT_MODES[self.method]
+        if self.dynamic:
+            mid = (sc.block.data_ptr(), *sc.args(), mode, teacher, self.w, lr_d.data_ptr(), *sgd, losses.data_ptr(), None)
+        else:
+            mid = (self.grad_scale, mode, teacher, self.w, self.T, self.lam, lr_d.data_ptr(), int(first), *sgd, losses.data_ptr(), None, None, None)
+        with m._launch_lock:
+            check(getattr(lib, name)(*head, *mid, *tail), name)
+
+    def _step_scaled(self, features, labels_d, lr_d, losses) -> None:
         """``step`` under the dynamic scale: the head at grad_scale = 1, its d_text times the block's scale, the backward, and
         clipmi_ctx_step_scaled, which decides on the device whether the step is applied."""
-        t, m, sc = self.tower, self.tower.model, self.scaler
-        sgd = (float(self.momentum), float(self.dampening), float(self.weight_decay), int(bool(self.nesterov)))
-        if one_call:
-            ws = t.one_call_workspace(features.shape[0], self.method, scaled=True)
-            fn, placed = ((lib.clipmi_prompt_train_step_scaled, ()) if t.position is None else
-                          (lib.clipmi_prompt_train_step_scaled_placed, (t.position, t.name_lens.data_ptr())))
-            with m._launch_lock:
-                check(fn(m._handle, C.byref(t.dgrad[0]), t.base.data_ptr(), _DT[t.base.dtype], self.ctx.data_ptr(),
-                         None if self.buf is None else self.buf.data_ptr(), t.n_ctx, int(t.per_class), *placed, t.eot.data_ptr(), t.C, t.rows,
-                         features.data_ptr(), features.stride(0), labels_d.data_ptr(), features.shape[0], self.scale, self.scaler_block.data_ptr(),
-                         sc["growth_factor"], sc["backoff_factor"], sc["growth_interval"], ops.PROMPT_MODES[self.method],
-                         None if self.teacher is None else self.teacher.data_ptr(), self.w, lr_d.data_ptr(), *sgd, losses.data_ptr(), None,
-                         ws.data_ptr(), ws.numel(), t.stash.data_ptr(), t.stash.numel(), ops._stream()),
-                      "clipmi_prompt_train_step_scaled" + ("" if t.position is None else "_placed"))
-            return
+        t, sc = self.tower, self._scaler
         text = t.forward(self.ctx)
         _, d_text, _ = ops.prompt_head(features, labels_d, text, self.scale, 1.0, self.method, self.teacher, self.w, 1.0, losses)
-        ops.grad_scale_rows(d_text, self.scaler_block)
+        ops.grad_scale_rows(d_text, sc.block)
         d_embed = t.context_rows(t.backward(d_text))
-        if self.scaled_ws is None:
+        if sc.ws is None:
             need = lib.clipmi_ctx_step_scaled_workspace_bytes(t.C, t.D, t.n_ctx, int(t.per_class))
-            self.scaled_ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.ctx.device)
-        ops.ctx_step_scaled(d_embed, t.C, t.n_ctx, t.per_class, self.scaler_block, self.ctx, self.buf, lr_d, sc["growth_factor"], sc["backoff_factor"],
-                            sc["growth_interval"], *sgd[:3], bool(sgd[3]), want_grad=False, workspace=self.scaled_ws)
+            sc.ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.ctx.device)
+        ops.ctx_step_scaled(d_embed, t.C, t.n_ctx, t.per_class, sc.block, self.ctx, self.buf, lr_d, *sc.args(), float(self.momentum), float(self.dampening),
+                            float(self.weight_decay), bool(self.nesterov), want_grad=False, workspace=sc.ws)
 
     def step(self, features: torch.Tensor, labels, lr, want_loss: bool = False, one_call: bool = False) -> Optional[torch.Tensor]:
         """One optimiser step on the batch ``features`` fp32 [B, E] (raw image features on the GPU) and ``labels`` [B] at the rate ``lr``:
@@ -523,23 +526,13 @@ class CoOpFitState:
             raise TypeError("CoOpFitState.step: features must be fp32 with unit column stride")
         dev = features.device
         lr_d = ops._dev(fitloop.lr_operand(lr, dev), "lr", (torch.float32,))
-        t, m, first = self.tower, self.tower.model, self.steps == 0
+        t, first = self.tower, self.steps == 0
         sgd = (self.momentum, self.dampening, self.weight_decay, self.nesterov)
         losses = _new_losses(self.method, dev)
-        if self.dynamic:
-            self._step_scaled(features, labels_d, lr_d, losses, one_call)
-        elif one_call:
-            ws = t.one_call_workspace(features.shape[0], self.method)
-            fn, placed = ((lib.clipmi_prompt_train_step, ()) if t.position is None else
-                          (lib.clipmi_prompt_train_step_placed, (t.position, t.name_lens.data_ptr())))
-            with m._launch_lock:
-                check(fn(m._handle, C.byref(t.dgrad[0]), t.base.data_ptr(), _DT[t.base.dtype], self.ctx.data_ptr(),
-                         None if self.buf is None else self.buf.data_ptr(), t.n_ctx, int(t.per_class), *placed, t.eot.data_ptr(), t.C, t.rows,
-                         features.data_ptr(), features.stride(0), labels_d.data_ptr(), features.shape[0], self.scale, self.grad_scale,
-                         ops.PROMPT_MODES[self.method], None if self.teacher is None else self.teacher.data_ptr(), self.w, self.T, self.lam,
-                         lr_d.data_ptr(), int(first), *map(float, sgd[:3]), int(bool(sgd[3])), losses.data_ptr(), None, None, None, ws.data_ptr(),
-                         ws.numel(), t.stash.data_ptr(), t.stash.numel(), ops._stream()),
-                      "clipmi_prompt_train_step" + ("" if t.position is None else "_placed"))
+        if one_call:
+            self._one_call(features, labels_d, lr_d, losses, first)
+        elif self.dynamic:
+            self._step_scaled(features, labels_d, lr_d, losses)
         else:
             text = t.forward(self.ctx)
             _, d_text, d_kl = ops.prompt_head(features, labels_d, text, self.scale, self.grad_scale, self.method, self.teacher, self.w, self.T, losses)
@@ -593,14 +586,8 @@ def fit_context(features: torch.Tensor, labels, clip_model, tokenized_prompts, c
     N = features.shape[0]
     epochs, batch_size = fitloop.check_run(who, epochs, batch_size)
     fitloop.check_sgd(who, momentum, dampening, weight_decay, nesterov)
-    if _is_dynamic(who, grad_scale):
-        if method == "prograd":
-            raise ValueError(f"{who}: grad_scale={DYNAMIC!r} covers method 'coop' and 'kgcoop'; ProGrad keeps a static scale")
-        _check_scaler(who, scaler)
-    else:
-        if scaler is not None:
-            raise ValueError(f"{who}: scaler is an argument of grad_scale={DYNAMIC!r}")
-        _check_grad_scale(who, grad_scale)
+    _static_prograd(who, method, grad_scale)
+    _scale_args(who, grad_scale, scaler)
     _check_method(who, method, teacher, w, T, lam, Cn, E)
     _placement(who, tokenized_prompts, n_ctx, class_token_position, name_lens)
     lab = fitloop._labels(who, labels, N, Cn)

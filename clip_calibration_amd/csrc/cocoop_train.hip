@@ -522,7 +522,7 @@ static int cocoop_train_step(const char* who, const ScalerCall* sc, size_t need,
   if (int rc = check_head(who, feats, ld, labels, text, B, E, C, scale, grad_scale, loss, d_text, head_ws, head_bytes)) return rc;
   if (int rc = check_reduce(who, d_embed, x_n, hid, w2, grad, B, C, L, D, E, H, n_ctx, grad_scale, reduce_ws, reduce_bytes)) return rc;
   if (sc) {
-    if (int rc = check_block_step_scaled(who, grad, params, buf, grad_out, lr, k.total, sc->state, sc->growth, sc->backoff, sc->interval, momentum, dampening,
+    if (int rc = check_block_step_scaled(who, grad, params, buf, grad_out, lr, k.total, *sc, momentum, dampening,
                                          weight_decay, nesterov, scaled_ws, scaled_bytes))
       return rc;
   } else if (int rc = check_step(who, grad, params, buf, lr, n_ctx, D, E, H, momentum, dampening, weight_decay, nesterov)) {
@@ -537,7 +537,7 @@ static int cocoop_train_step(const char* who, const ScalerCall* sc, size_t need,
   if (int rc = run_backward(m, wt, d_text, N, seq_rows, d_embed, workspace, stash, nullptr, s)) return rc;
   if (int rc = enqueue_reduce(d_embed, x_n, hid, w2, grad, B, C, L, D, E, H, n_ctx, grad_scale, reduce_ws, s)) return rc;
   if (sc)
-    return launch_block_step_scaled(grad, params, buf, grad_out, k.total, sc->state, sc->growth, sc->backoff, sc->interval, lr, momentum, dampening,
+    return launch_block_step_scaled(grad, params, buf, grad_out, k.total, *sc, lr, momentum, dampening,
                                     weight_decay, nesterov, scaled_ws, s);
   return enqueue_step(grad, params, buf, n_ctx, D, E, H, lr, first_step, momentum, dampening, weight_decay, nesterov, s);
 }

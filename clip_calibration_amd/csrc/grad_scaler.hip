@@ -97,52 +97,36 @@ __global__ __launch_bounds__(THREADS) void scaled_apply_kernel(ScaledWs w, float
   sgd_element_fma(ctx, buf, idx, w.grad[idx], *lr, sgd);
 }
 
-// everything clipmi_ctx_step_scaled refuses, before anything is launched; *total: the elements of ctx
-int check_scaled_step(const char* who, const float* d_embed, const float* ctx, const float* buf, const float* lr, int C, int L, int D, int n_ctx, int per_class,
-                      const clipmi_scaler_state* st, float growth, float backoff, int growth_interval, float momentum, float dampening, float weight_decay,
-                      int nesterov, const void* workspace, size_t workspace_bytes, int64_t* total) {
-  CLIPMI_REQUIRE(d_embed && ctx && lr && workspace, CLIPMI_ERR_ARG, "%s: null pointer (d_embed, ctx, lr and the workspace are required)", who);
-  if (int rc = check_scaler(who, st, growth, backoff, growth_interval)) return rc;
-  CLIPMI_REQUIRE(C >= 1 && D >= 1 && n_ctx >= 1 && 1 + n_ctx <= L, CLIPMI_ERR_SHAPE, "%s: C=%d L=%d D=%d n_ctx=%d", who, C, L, D, n_ctx);
+// what every scaled step refuses behind its caller's own first lines (the required pointers and the shape), before anything is launched
+int check_scaled_common(const char* who, const ScalerCall& sc, const float* buf, int64_t total, float momentum, float dampening, float weight_decay,
+                        int nesterov, const void* workspace, size_t workspace_bytes) {
+  if (int rc = check_scaler(who, sc)) return rc;
   if (int rc = check_sgd(who, momentum, dampening, weight_decay, nesterov)) return rc;
   CLIPMI_REQUIRE(momentum == 0.f || buf, CLIPMI_ERR_ARG, "%s: null pointer (a momentum needs the buffer)", who);
-  *total = (int64_t)n_ctx * D * (per_class ? C : 1);
-  CLIPMI_REQUIRE(*total < (1ll << 31) * THREADS, CLIPMI_ERR_SHAPE, "%s: context too large", who);
+  CLIPMI_REQUIRE(total < (1ll << 31) * THREADS, CLIPMI_ERR_SHAPE, "%s: %lld elements are too many", who, (long long)total);
   CLIPMI_REQUIRE((uintptr_t)workspace % 256 == 0, CLIPMI_ERR_ARG, "%s: the workspace must be 256-byte aligned", who);
-  CLIPMI_REQUIRE(workspace_bytes >= scaled_step_bytes(*total), CLIPMI_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes,
-                 scaled_step_bytes(*total));
+  CLIPMI_REQUIRE(workspace_bytes >= scaled_step_bytes(total), CLIPMI_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes,
+                 scaled_step_bytes(total));
   return CLIPMI_OK;
-}
-
-// the three launches; every argument has been checked
-int launch_scaled_step(const float* d_embed, float* ctx, float* buf, float* grad_out, int C, int L, int D, int n_ctx, int per_class, int64_t total,
-                       clipmi_scaler_state* st, float growth, float backoff, int growth_interval, const float* lr, float momentum, float dampening,
-                       float weight_decay, int nesterov, void* workspace, hipStream_t s) {
-  const ScaledWs w = scaled_carve(workspace, total);
-  const int64_t blocks = scaled_grad_blocks(total);
-  hipLaunchKernelGGL(scaled_grad_kernel, dim3((unsigned)blocks), dim3(THREADS), 0, s, d_embed, grad_out, C, L, D, n_ctx, per_class ? 1 : 0, total,
-                     (const clipmi_scaler_state*)st, w);
-  if (int rc = check_launch("scaled_grad_kernel")) return rc;
-  return launch_scaled_decide_apply(w, total, ctx, buf, st, growth, backoff, growth_interval, lr, momentum, dampening, weight_decay, nesterov, s);
 }
 
 }  // namespace
 
 // ---- what every scaled step shares (model.h)
-int check_scaler(const char* who, const clipmi_scaler_state* st, float growth, float backoff, int growth_interval) {
-  CLIPMI_REQUIRE(st, CLIPMI_ERR_ARG, "%s: null pointer (the scaler's state block)", who);
-  CLIPMI_REQUIRE((uintptr_t)st % 4 == 0, CLIPMI_ERR_ARG, "%s: the scaler's state block must be 4-byte aligned", who);
-  CLIPMI_REQUIRE(std::isfinite(growth) && growth > 0.f && std::isfinite(backoff) && backoff > 0.f, CLIPMI_ERR_ARG,
-                 "%s: growth_factor=%g, backoff_factor=%g (both finite, > 0)", who, growth, backoff);
-  CLIPMI_REQUIRE(growth_interval >= 1, CLIPMI_ERR_ARG, "%s: growth_interval=%d (>= 1)", who, growth_interval);
+int check_scaler(const char* who, const ScalerCall& sc) {
+  CLIPMI_REQUIRE(sc.state, CLIPMI_ERR_ARG, "%s: null pointer (the scaler's state block)", who);
+  CLIPMI_REQUIRE((uintptr_t)sc.state % 4 == 0, CLIPMI_ERR_ARG, "%s: the scaler's state block must be 4-byte aligned", who);
+  CLIPMI_REQUIRE(std::isfinite(sc.growth) && sc.growth > 0.f && std::isfinite(sc.backoff) && sc.backoff > 0.f, CLIPMI_ERR_ARG,
+                 "%s: growth_factor=%g, backoff_factor=%g (both finite, > 0)", who, sc.growth, sc.backoff);
+  CLIPMI_REQUIRE(sc.interval >= 1, CLIPMI_ERR_ARG, "%s: growth_interval=%d (>= 1)", who, sc.interval);
   return CLIPMI_OK;
 }
 
 // the decision launch and the step launch behind a first launch that has filled w.grad and w.flags; every argument has been checked
-int launch_scaled_decide_apply(const ScaledWs& w, int64_t total, float* params, float* buf, clipmi_scaler_state* st, float growth, float backoff,
-                               int growth_interval, const float* lr, float momentum, float dampening, float weight_decay, int nesterov, hipStream_t s) {
+int launch_scaled_decide_apply(const ScaledWs& w, int64_t total, float* params, float* buf, const ScalerCall& sc, const float* lr, float momentum,
+                               float dampening, float weight_decay, int nesterov, hipStream_t s) {
   const int64_t blocks = scaled_grad_blocks(total);
-  hipLaunchKernelGGL(scaler_update_kernel, dim3(1), dim3(THREADS), 0, s, w, blocks, st, growth, backoff, growth_interval);
+  hipLaunchKernelGGL(scaler_update_kernel, dim3(1), dim3(THREADS), 0, s, w, blocks, sc.state, sc.growth, sc.backoff, sc.interval);
   if (int rc = check_launch("scaler_update_kernel")) return rc;
   hipLaunchKernelGGL(scaled_apply_kernel, dim3((unsigned)blocks), dim3(THREADS), 0, s, w, params, buf, total, lr,
                      make_sgd_args(momentum, dampening, weight_decay, nesterov, 0));
@@ -158,35 +142,48 @@ int launch_grad_scale_rows(const char* who, float* x, int rows, int cols, const 
   return check_launch("grad_scale_rows_kernel");
 }
 
+// everything clipmi_ctx_step_scaled refuses, before anything is launched; *total: the elements of ctx
+int check_ctx_step_scaled(const char* who, const float* d_embed, const float* ctx, const float* buf, const float* lr, int C, int L, int D, int n_ctx, int per_class,
+                          const ScalerCall& sc, float momentum, float dampening, float weight_decay, int nesterov, const void* workspace, size_t workspace_bytes,
+                          int64_t* total) {
+  CLIPMI_REQUIRE(d_embed && ctx && lr && workspace, CLIPMI_ERR_ARG, "%s: null pointer (d_embed, ctx, lr and the workspace are required)", who);
+  CLIPMI_REQUIRE(C >= 1 && D >= 1 && n_ctx >= 1 && 1 + n_ctx <= L, CLIPMI_ERR_SHAPE, "%s: C=%d L=%d D=%d n_ctx=%d", who, C, L, D, n_ctx);
+  *total = (int64_t)n_ctx * D * (per_class ? C : 1);
+  return check_scaled_common(who, sc, buf, *total, momentum, dampening, weight_decay, nesterov, workspace, workspace_bytes);
+}
+
+// the three launches; every argument has been checked
+int launch_ctx_step_scaled(const float* d_embed, float* ctx, float* buf, float* grad_out, int C, int L, int D, int n_ctx, int per_class, int64_t total,
+                           const ScalerCall& sc, const float* lr, float momentum, float dampening, float weight_decay, int nesterov, void* workspace,
+                           hipStream_t s) {
+  const ScaledWs w = scaled_carve(workspace, total);
+  hipLaunchKernelGGL(scaled_grad_kernel, dim3((unsigned)scaled_grad_blocks(total)), dim3(THREADS), 0, s, d_embed, grad_out, C, L, D, n_ctx, per_class ? 1 : 0,
+                     total, (const clipmi_scaler_state*)sc.state, w);
+  if (int rc = check_launch("scaled_grad_kernel")) return rc;
+  return launch_scaled_decide_apply(w, total, ctx, buf, sc, lr, momentum, dampening, weight_decay, nesterov, s);
+}
+
 size_t block_step_scaled_bytes(int64_t total) { return total >= 1 && total < (1ll << 31) * THREADS ? scaled_step_bytes(total) : 0; }
 
 // everything clipmi_block_step_scaled refuses, before anything is launched
 int check_block_step_scaled(const char* who, const float* grad, const float* params, const float* buf, const float* grad_out, const float* lr, int64_t total,
-                            const clipmi_scaler_state* st, float growth, float backoff, int growth_interval, float momentum, float dampening,
-                            float weight_decay, int nesterov, const void* workspace, size_t workspace_bytes) {
+                            const ScalerCall& sc, float momentum, float dampening, float weight_decay, int nesterov, const void* workspace,
+                            size_t workspace_bytes) {
   CLIPMI_REQUIRE(grad && params && lr && workspace, CLIPMI_ERR_ARG, "%s: null pointer (grad, params, lr and the workspace are required)", who);
   CLIPMI_REQUIRE(((uintptr_t)grad | (uintptr_t)params | (uintptr_t)buf | (uintptr_t)grad_out | (uintptr_t)lr) % 4 == 0, CLIPMI_ERR_ARG,
                  "%s: grad, params, buf, grad_out and lr must be 4-byte aligned", who);
-  if (int rc = check_scaler(who, st, growth, backoff, growth_interval)) return rc;
   CLIPMI_REQUIRE(total >= 1, CLIPMI_ERR_SHAPE, "%s: total=%lld (>= 1)", who, (long long)total);
-  if (int rc = check_sgd(who, momentum, dampening, weight_decay, nesterov)) return rc;
-  CLIPMI_REQUIRE(momentum == 0.f || buf, CLIPMI_ERR_ARG, "%s: null pointer (a momentum needs the buffer)", who);
-  CLIPMI_REQUIRE(total < (1ll << 31) * THREADS, CLIPMI_ERR_SHAPE, "%s: block too large", who);
-  CLIPMI_REQUIRE((uintptr_t)workspace % 256 == 0, CLIPMI_ERR_ARG, "%s: the workspace must be 256-byte aligned", who);
-  CLIPMI_REQUIRE(workspace_bytes >= scaled_step_bytes(total), CLIPMI_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes,
-                 scaled_step_bytes(total));
-  return CLIPMI_OK;
+  return check_scaled_common(who, sc, buf, total, momentum, dampening, weight_decay, nesterov, workspace, workspace_bytes);
 }
 
 // the three launches; every argument has been checked
-int launch_block_step_scaled(const float* grad, float* params, float* buf, float* grad_out, int64_t total, clipmi_scaler_state* st, float growth, float backoff,
-                             int growth_interval, const float* lr, float momentum, float dampening, float weight_decay, int nesterov, void* workspace,
-                             hipStream_t s) {
+int launch_block_step_scaled(const float* grad, float* params, float* buf, float* grad_out, int64_t total, const ScalerCall& sc, const float* lr, float momentum,
+                             float dampening, float weight_decay, int nesterov, void* workspace, hipStream_t s) {
   const ScaledWs w = scaled_carve(workspace, total);
-  const int64_t blocks = scaled_grad_blocks(total);
-  hipLaunchKernelGGL(block_unscale_kernel, dim3((unsigned)blocks), dim3(THREADS), 0, s, grad, grad_out, total, (const clipmi_scaler_state*)st, w);
+  hipLaunchKernelGGL(block_unscale_kernel, dim3((unsigned)scaled_grad_blocks(total)), dim3(THREADS), 0, s, grad, grad_out, total,
+                     (const clipmi_scaler_state*)sc.state, w);
   if (int rc = check_launch("block_unscale_kernel")) return rc;
-  return launch_scaled_decide_apply(w, total, params, buf, st, growth, backoff, growth_interval, lr, momentum, dampening, weight_decay, nesterov, s);
+  return launch_scaled_decide_apply(w, total, params, buf, sc, lr, momentum, dampening, weight_decay, nesterov, s);
 }
 
 }  // namespace clipmi
@@ -209,12 +206,13 @@ size_t clipmi_ctx_step_scaled_workspace_bytes(int C, int D, int n_ctx, int per_c
 int clipmi_ctx_step_scaled(const float* d_embed, float* ctx, float* buf, float* grad_out, int C, int L, int D, int n_ctx, int per_class,
                            clipmi_scaler_state* state, float growth_factor, float backoff_factor, int growth_interval, const float* lr, float momentum,
                            float dampening, float weight_decay, int nesterov, void* workspace, size_t workspace_bytes, clipmi_stream_t stream) {
+  const ScalerCall sc{state, growth_factor, backoff_factor, growth_interval};
   int64_t total;
-  if (int rc = check_scaled_step("ctx_step_scaled", d_embed, ctx, buf, lr, C, L, D, n_ctx, per_class, state, growth_factor, backoff_factor, growth_interval,
-                                 momentum, dampening, weight_decay, nesterov, workspace, workspace_bytes, &total))
+  if (int rc = check_ctx_step_scaled("ctx_step_scaled", d_embed, ctx, buf, lr, C, L, D, n_ctx, per_class, sc, momentum, dampening, weight_decay, nesterov,
+                                     workspace, workspace_bytes, &total))
     return rc;
-  return launch_scaled_step(d_embed, ctx, buf, grad_out, C, L, D, n_ctx, per_class, total, state, growth_factor, backoff_factor, growth_interval, lr, momentum,
-                            dampening, weight_decay, nesterov, workspace, (hipStream_t)stream);
+  return launch_ctx_step_scaled(d_embed, ctx, buf, grad_out, C, L, D, n_ctx, per_class, total, sc, lr, momentum, dampening, weight_decay, nesterov, workspace,
+                                (hipStream_t)stream);
 }
 
 size_t clipmi_block_step_scaled_workspace_bytes(int64_t total) { return block_step_scaled_bytes(total); }
@@ -222,11 +220,11 @@ size_t clipmi_block_step_scaled_workspace_bytes(int64_t total) { return block_st
 int clipmi_block_step_scaled(const float* grad, float* params, float* buf, float* grad_out, int64_t total, clipmi_scaler_state* state, float growth_factor,
                              float backoff_factor, int growth_interval, const float* lr, float momentum, float dampening, float weight_decay, int nesterov,
                              void* workspace, size_t workspace_bytes, clipmi_stream_t stream) {
-  if (int rc = check_block_step_scaled("block_step_scaled", grad, params, buf, grad_out, lr, total, state, growth_factor, backoff_factor, growth_interval,
-                                       momentum, dampening, weight_decay, nesterov, workspace, workspace_bytes))
+  const ScalerCall sc{state, growth_factor, backoff_factor, growth_interval};
+  if (int rc = check_block_step_scaled("block_step_scaled", grad, params, buf, grad_out, lr, total, sc, momentum, dampening, weight_decay, nesterov, workspace,
+                                       workspace_bytes))
     return rc;
-  return launch_block_step_scaled(grad, params, buf, grad_out, total, state, growth_factor, backoff_factor, growth_interval, lr, momentum, dampening,
-                                  weight_decay, nesterov, workspace, (hipStream_t)stream);
+  return launch_block_step_scaled(grad, params, buf, grad_out, total, sc, lr, momentum, dampening, weight_decay, nesterov, workspace, (hipStream_t)stream);
 }
 
 size_t clipmi_prompt_train_step_scaled_bytes(const clipmi_model* m, int n_prompts, int seq_rows, int B, int mode, int n_ctx, int ctx_per_class) {
@@ -236,56 +234,18 @@ size_t clipmi_prompt_train_step_scaled_bytes(const clipmi_model* m, int n_prompt
   return base && step ? base + step : 0;
 }
 
-// workspace: clipmi_prompt_train_step's of the same mode (the tower's workspace | text features | their gradient | d_embed | the head's
-// workspace) | clipmi_ctx_step_scaled's
+// workspace: clipmi_prompt_train_step's of the same mode | clipmi_ctx_step_scaled's
 int clipmi_prompt_train_step_scaled(clipmi_model* m, const clipmi_text_dgrad* wt, const void* prompts, int dtype, float* ctx, float* buf, int n_ctx,
                                     int ctx_per_class, const int32_t* eot, int n_prompts, int seq_rows, const float* feats, int64_t ld,
                                     const int64_t* labels, int B, float scale, clipmi_scaler_state* state, float growth_factor, float backoff_factor,
                                     int growth_interval, int mode, const float* teacher, float w, const float* lr, float momentum, float dampening,
                                     float weight_decay, int nesterov, float* losses, float* grad_out, void* workspace, size_t workspace_bytes, void* stash,
                                     size_t stash_bytes, clipmi_stream_t stream) {
-  const char* who = "prompt_train_step_scaled";
-  const int C = n_prompts;
-  hipStream_t s = (hipStream_t)stream;
-  CLIPMI_REQUIRE(mode != MODE_PROGRAD, CLIPMI_ERR_ARG, "%s: ProGrad's mode has no dynamic loss scale (its two gradients share one step)", who);
-  CLIPMI_REQUIRE(mode == MODE_COOP || mode == MODE_KGCOOP, CLIPMI_ERR_ARG, "%s: bad mode %d", who, mode);
-  if (int rc = check_scaler(who, state, growth_factor, backoff_factor, growth_interval)) return rc;
-  CLIPMI_REQUIRE(m, CLIPMI_ERR_ARG, "%s: null model", who);
-  CLIPMI_REQUIRE(C >= 2 && B >= 1, CLIPMI_ERR_SHAPE, "%s: n_prompts=%d (>= 2), B=%d (>= 1)", who, C, B);
-  CLIPMI_REQUIRE(feats && labels && losses, CLIPMI_ERR_ARG, "%s: null pointer (feats, labels and losses are required)", who);
-  CLIPMI_REQUIRE(mode == MODE_COOP || teacher, CLIPMI_ERR_ARG, "%s: null pointer (KgCoOp needs the teacher)", who);
-  CLIPMI_REQUIRE(std::isfinite(scale), CLIPMI_ERR_ARG, "%s: scale=%g (finite)", who, scale);
-  CLIPMI_REQUIRE(mode != MODE_KGCOOP || (std::isfinite(w) && w >= 0.f), CLIPMI_ERR_ARG, "%s: w=%g (finite, >= 0)", who, w);
-  const size_t need = clipmi_prompt_train_step_scaled_bytes(m, C, seq_rows, B, mode, n_ctx, ctx_per_class);
-  CLIPMI_REQUIRE(need > 0 && workspace_bytes >= need, CLIPMI_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, need);
-  size_t tower = 0;
-  clipmi_text_train_bytes(m, C, seq_rows, &tower, nullptr);
-  if (int rc = check_train_call(who, m, C, workspace, tower, stash, stash_bytes, seq_rows)) return rc;
-  if (int rc = check_train_inputs(who, m, prompts, dtype, ctx, n_ctx, eot, seq_rows, nullptr, 0)) return rc;
-  if (int rc = check_dgrad(who, m, wt)) return rc;
-  const int L = live_rows(m, seq_rows), D = m->g.text_width, E = m->g.embed_dim;
-  CLIPMI_REQUIRE(L <= AB_MAX_L, CLIPMI_ERR_SHAPE, "%s: %d token rows per prompt (at most %d)", who, L, AB_MAX_L);
-  CLIPMI_REQUIRE(ld >= E && (int64_t)B * C < (1ll << 31), CLIPMI_ERR_SHAPE, "%s: B=%d C=%d E=%d ld=%lld", who, B, C, E, (long long)ld);
-  const size_t head_bytes = clipmi_prompt_head_workspace_bytes(B, E, C, mode);
-  const size_t step_bytes = clipmi_ctx_step_scaled_workspace_bytes(C, D, n_ctx, ctx_per_class);
-  Carver c(static_cast<char*>(workspace) + tower);
-  float* text = c.take<float>((size_t)C * E * 4);
-  float* d_text = c.take<float>((size_t)C * E * 4);
-  float* d_embed = c.take<float>((size_t)C * L * D * 4);
-  void* head_ws = c.take<char>(head_bytes);
-  void* step_ws = c.take<char>(step_bytes);
-  int64_t total;
-  if (int rc = check_scaled_step(who, d_embed, ctx, buf, lr, C, L, D, n_ctx, ctx_per_class, state, growth_factor, backoff_factor, growth_interval, momentum,
-                                 dampening, weight_decay, nesterov, step_ws, step_bytes, &total))
-    return rc;
-  if (int rc = run_train_forward(m, prompts, dtype, ctx, n_ctx, ctx_per_class, eot, C, seq_rows, text, workspace, stash, s)) return rc;
-  if (int rc = clipmi_prompt_head(feats, ld, labels, text, B, E, C, scale, 1.f, mode, teacher, w, 1.f, losses, d_text, nullptr, nullptr, head_ws, head_bytes,
-                                  stream))
-    return rc;
-  if (int rc = launch_grad_scale_rows(who, d_text, C, E, state, s)) return rc;
-  if (int rc = run_backward(m, wt, d_text, C, seq_rows, d_embed, workspace, stash, nullptr, s)) return rc;
-  return launch_scaled_step(d_embed, ctx, buf, grad_out, C, L, D, n_ctx, ctx_per_class, total, state, growth_factor, backoff_factor, growth_interval, lr,
-                            momentum, dampening, weight_decay, nesterov, step_ws, s);
+  const ScalerCall sc{state, growth_factor, backoff_factor, growth_interval};
+  return prompt_train_step("prompt_train_step_scaled", true, clipmi_prompt_train_step_scaled_bytes(m, n_prompts, seq_rows, B, mode, n_ctx, ctx_per_class), &sc,
+                           nullptr, m, wt, prompts, dtype, ctx, buf, n_ctx, ctx_per_class, eot, n_prompts, seq_rows, feats, ld, labels, B, scale, 1.f, mode, teacher,
+                           w, 1.f, 0.f, lr, 0, momentum, dampening, weight_decay, nesterov, losses, grad_out, nullptr, nullptr, workspace, workspace_bytes, stash,
+                           stash_bytes, (hipStream_t)stream);
 }
 
 }  // extern "C"

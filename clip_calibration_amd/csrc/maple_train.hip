@@ -255,7 +255,7 @@ static int maple_train_step(const char* who, const ScalerCall* sc, size_t need, 
   float* scaled_grad = c.take<float>(sc ? (size_t)total * 4 : 0);
   void* scaled_ws = c.take<char>(scaled_bytes);
   if (sc)   // the scaler's and the optimiser's refusals come ahead of the first launch
-    if (int rc = check_block_step_scaled(who, scaled_grad, block, buf, grad_out, lr, total, sc->state, sc->growth, sc->backoff, sc->interval, momentum,
+    if (int rc = check_block_step_scaled(who, scaled_grad, block, buf, grad_out, lr, total, *sc, momentum,
                                          dampening, weight_decay, nesterov, scaled_ws, scaled_bytes))
       return rc;
   const float* deep = block + (int64_t)n_ctx * Dt;
@@ -273,7 +273,7 @@ static int maple_train_step(const char* who, const ScalerCall* sc, size_t need, 
     if (int rc = launch_step(who, d_embed, d_deep, d_vis, block, nullptr, scaled_grad, 0, C, L, n_ctx, depth, Dt, Dv, 1.f, nullptr, 0, momentum, dampening,
                              weight_decay, nesterov, step_ws, st_bytes, s))
       return rc;
-    return launch_block_step_scaled(scaled_grad, block, buf, grad_out, total, sc->state, sc->growth, sc->backoff, sc->interval, lr, momentum, dampening,
+    return launch_block_step_scaled(scaled_grad, block, buf, grad_out, total, *sc, lr, momentum, dampening,
                                     weight_decay, nesterov, scaled_ws, s);
   }
   return launch_step(who, d_embed, d_deep, d_vis, block, buf, grad_out, 1, C, L, n_ctx, depth, Dt, Dv, grad_scale, lr, first_step, momentum, dampening,

@@ -165,16 +165,43 @@ inline ScaledWs scaled_carve(void* ws, int64_t total) {
   w.grad = reinterpret_cast<float*>(p + 256 + align256((size_t)scaled_grad_blocks(total) * 4));
   return w;
 }
-int check_scaler(const char* who, const clipmi_scaler_state* st, float growth, float backoff, int growth_interval);
+int check_scaler(const char* who, const ScalerCall& sc);
 // the decision launch and the step launch of a scaled step whose own first launch has filled w.grad and w.flags (proda_train.hip)
-int launch_scaled_decide_apply(const ScaledWs& w, int64_t total, float* params, float* buf, clipmi_scaler_state* st, float growth, float backoff,
-                               int growth_interval, const float* lr, float momentum, float dampening, float weight_decay, int nesterov, hipStream_t s);
+int launch_scaled_decide_apply(const ScaledWs& w, int64_t total, float* params, float* buf, const ScalerCall& sc, const float* lr, float momentum,
+                               float dampening, float weight_decay, int nesterov, hipStream_t s);
 size_t block_step_scaled_bytes(int64_t total);   // 0 for a total the step refuses
 int check_block_step_scaled(const char* who, const float* grad, const float* params, const float* buf, const float* grad_out, const float* lr, int64_t total,
-                            const clipmi_scaler_state* st, float growth, float backoff, int growth_interval, float momentum, float dampening,
-                            float weight_decay, int nesterov, const void* workspace, size_t workspace_bytes);
-int launch_block_step_scaled(const float* grad, float* params, float* buf, float* grad_out, int64_t total, clipmi_scaler_state* st, float growth, float backoff,
-                             int growth_interval, const float* lr, float momentum, float dampening, float weight_decay, int nesterov, void* workspace,
-                             hipStream_t s);
+                            const ScalerCall& sc, float momentum, float dampening, float weight_decay, int nesterov, const void* workspace,
+                            size_t workspace_bytes);
+int launch_block_step_scaled(const float* grad, float* params, float* buf, float* grad_out, int64_t total, const ScalerCall& sc, const float* lr, float momentum,
+                             float dampening, float weight_decay, int nesterov, void* workspace, hipStream_t s);
+// clipmi_ctx_step_scaled's check (*total: the elements of ctx) and its three launches, for the CoOp family's one-call step
+int check_ctx_step_scaled(const char* who, const float* d_embed, const float* ctx, const float* buf, const float* lr, int C, int L, int D, int n_ctx, int per_class,
+                          const ScalerCall& sc, float momentum, float dampening, float weight_decay, int nesterov, const void* workspace, size_t workspace_bytes,
+                          int64_t* total);
+int launch_ctx_step_scaled(const float* d_embed, float* ctx, float* buf, float* grad_out, int C, int L, int D, int n_ctx, int per_class, int64_t total,
+                           const ScalerCall& sc, const float* lr, float momentum, float dampening, float weight_decay, int nesterov, void* workspace,
+                           hipStream_t s);
+
+// prompt_position.hip: the class token at the front or in the middle, for the CoOp family's one-call step.  check_place covers what
+// both copy launches ask of the position and the shape (the step's own gradient streams are the unplace launch's other arguments)
+struct PromptPlacement {
+  int position;
+  const int32_t* name_lens;
+};
+int check_place(const char* who, const void* base, int dtype, const float* ctx, int position, const int32_t* name_lens, const float* out, int C, int L, int Lc,
+                int D, int n_ctx);
+int enqueue_place(const void* base, int dtype, const float* ctx, int per_class, int position, const int32_t* name_lens, float* out, int C, int L, int Lc, int D,
+                  int n_ctx, hipStream_t s);
+int enqueue_unplace(const float* d_embed, int position, const int32_t* name_lens, float* out, int C, int L, int D, int n_ctx, hipStream_t s);
+
+// prompt_train.hip: the one-call step of CoOp, KgCoOp and ProGrad behind its six exported symbols.  sc == nullptr: the static step at
+// grad_scale; pl == nullptr: the class token at the end, nothing is placed.  need: what the calling symbol's sizing function reports
+int prompt_train_step(const char* who, bool need_losses, size_t need, const ScalerCall* sc, const PromptPlacement* pl, clipmi_model* m,
+                      const clipmi_text_dgrad* wt, const void* prompts, int dtype, float* ctx, float* buf, int n_ctx, int per_class, const int32_t* eot, int C,
+                      int seq_rows, const float* feats, int64_t ld, const int64_t* labels, int B, float scale, float grad_scale, int mode, const float* teacher,
+                      float w, float T, float lambda, const float* lr, int first_step, float momentum, float dampening, float weight_decay, int nesterov,
+                      float* losses, float* grad_out, int* projected, double* dots, void* workspace, size_t workspace_bytes, void* stash, size_t stash_bytes,
+                      hipStream_t s);
 
 }  // namespace clipmi

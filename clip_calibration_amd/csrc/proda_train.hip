@@ -450,7 +450,7 @@ int check_ctx_step_scaled(const char* who, const float* d_embed, float* ctx, flo
                           const int32_t* name_lens, int C, int Pb, int P, int L, int D, int n_ctx, const ScalerCall& sc, const float* lr, float momentum,
                           float dampening, float weight_decay, int nesterov, const void* workspace, size_t workspace_bytes) {
   CLIPMI_REQUIRE(ctx && lr && workspace, CLIPMI_ERR_ARG, "%s: null pointer (ctx, lr and the workspace are required)", who);
-  if (int rc = check_scaler(who, sc.state, sc.growth, sc.backoff, sc.interval)) return rc;
+  if (int rc = check_scaler(who, sc)) return rc;
   if (int rc = check_ctx_step(who, d_embed, ctx, buf, grad_out, sel, pos, name_lens, C, Pb, P, L, D, n_ctx, 1.f, lr, 0, momentum, dampening, weight_decay,
                               nesterov))
     return rc;
@@ -469,7 +469,7 @@ int enqueue_ctx_step_scaled(const float* d_embed, float* ctx, float* buf, float*
   hipLaunchKernelGGL(proda_scaled_grad_kernel, dim3((unsigned)scaled_grad_blocks(total)), dim3(THREADS), 0, s, d_embed, grad_out, sel, pos, name_lens, C, Pb, P,
                      L, D, n_ctx, (const clipmi_scaler_state*)sc.state, w);
   if (int rc = check_launch("proda_scaled_grad_kernel")) return rc;
-  return launch_scaled_decide_apply(w, total, ctx, buf, sc.state, sc.growth, sc.backoff, sc.interval, lr, momentum, dampening, weight_decay, nesterov, s);
+  return launch_scaled_decide_apply(w, total, ctx, buf, sc, lr, momentum, dampening, weight_decay, nesterov, s);
 }
 
 }  // namespace
@@ -624,7 +624,7 @@ int clipmi_proda_train_step_scaled(clipmi_model* m, const clipmi_text_dgrad* wt,
                                    float dampening, float weight_decay, int nesterov, float* losses, float* grad_out, void* workspace, size_t workspace_bytes,
                                    void* stash, size_t stash_bytes, clipmi_stream_t stream) {
   const ScalerCall sc{state, growth_factor, backoff_factor, growth_interval};
-  if (int rc = check_scaler("proda_train_step_scaled", state, growth_factor, backoff_factor, growth_interval)) return rc;
+  if (int rc = check_scaler("proda_train_step_scaled", sc)) return rc;
   return train_step("proda_train_step_scaled", m, wt, base, nc_base, dtype, ctx, buf, n_ctx, sel, pos, name_lens, cls_eot, C, Pb, P, seq_rows, feats, ld, labels, B,
                     scale, 1.f, &sc, alpha, lr, 0, momentum, dampening, weight_decay, nesterov, losses, grad_out, workspace, workspace_bytes, stash, stash_bytes,
                     (hipStream_t)stream);

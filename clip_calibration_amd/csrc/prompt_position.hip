@@ -96,6 +96,23 @@ int check_position(const char* who, int position, const int32_t* name_lens, int 
   return CLIPMI_OK;
 }
 
+int check_unplace(const char* who, const float* d_embed, int position, const int32_t* name_lens, const float* out, int C, int L, int D, int n_ctx) {
+  CLIPMI_REQUIRE(d_embed && out, CLIPMI_ERR_ARG, "%s: null pointer", who);
+  if (int rc = check_position(who, position, name_lens, C, L, L, D, n_ctx)) return rc;
+  CLIPMI_REQUIRE((uintptr_t)d_embed % 16 == 0 && (uintptr_t)out % 16 == 0, CLIPMI_ERR_ARG, "%s: d_embed and the output must be 16-byte aligned", who);
+  return CLIPMI_OK;
+}
+
+// the unplaced step's workspace of the same arguments | the placed prompts fp32 [C, Lc, D] | the compact gradient [C (1 + n_ctx), D] and,
+// for ProGrad, | the second one: what the placed sizers add (prompt_train.hip carves it)
+inline size_t placed_extra_bytes(const clipmi_model* m, int C, int mode, int n_ctx) {
+  const int D = m->g.text_width;
+  return align256((size_t)C * m->g.context_length * D * 4) + (mode == MODE_PROGRAD ? 2 : 1) * align256((size_t)C * (1 + n_ctx) * D * 4);
+}
+
+}  // namespace
+
+// ---- what the CoOp family's one-call step shares (model.h)
 int check_place(const char* who, const void* base, int dtype, const float* ctx, int position, const int32_t* name_lens, const float* out, int C, int L, int Lc,
                 int D, int n_ctx) {
   CLIPMI_REQUIRE(base && ctx && out, CLIPMI_ERR_ARG, "%s: null pointer", who);
@@ -103,13 +120,6 @@ int check_place(const char* who, const void* base, int dtype, const float* ctx, 
   if (int rc = check_position(who, position, name_lens, C, L, Lc, D, n_ctx)) return rc;
   CLIPMI_REQUIRE((uintptr_t)base % 16 == 0 && (uintptr_t)ctx % 16 == 0 && (uintptr_t)out % 16 == 0, CLIPMI_ERR_ARG,
                  "%s: base, ctx and the prompt buffer must be 16-byte aligned", who);
-  return CLIPMI_OK;
-}
-
-int check_unplace(const char* who, const float* d_embed, int position, const int32_t* name_lens, const float* out, int C, int L, int D, int n_ctx) {
-  CLIPMI_REQUIRE(d_embed && out, CLIPMI_ERR_ARG, "%s: null pointer", who);
-  if (int rc = check_position(who, position, name_lens, C, L, L, D, n_ctx)) return rc;
-  CLIPMI_REQUIRE((uintptr_t)d_embed % 16 == 0 && (uintptr_t)out % 16 == 0, CLIPMI_ERR_ARG, "%s: d_embed and the output must be 16-byte aligned", who);
   return CLIPMI_OK;
 }
 
@@ -133,74 +143,6 @@ int enqueue_unplace(const float* d_embed, int position, const int32_t* name_lens
   return check_launch("prompt_unplace_kernel");
 }
 
-// ------------------------------------------------------------------------------------------------------------ the one-call steps
-// workspace: the unplaced step's of the same arguments (clipmi_prompt_train_step's or clipmi_prompt_train_step_scaled's, carved as those
-// carve it) | the placed prompts fp32 [C, Lc, D] | the compact gradient [C (1 + n_ctx), D] and, for ProGrad, | the second one
-struct PlacedWs {
-  float *text, *d_text, *d_embed, *d_text_kl, *d_embed_kl, *prompts, *compact, *compact_kl;
-  void *head, *step;
-  size_t head_bytes, step_bytes;
-};
-inline size_t placed_extra_bytes(const clipmi_model* m, int C, int mode, int n_ctx) {
-  const int D = m->g.text_width;
-  return align256((size_t)C * m->g.context_length * D * 4) + (mode == MODE_PROGRAD ? 2 : 1) * align256((size_t)C * (1 + n_ctx) * D * 4);
-}
-inline PlacedWs placed_carve(void* workspace, size_t tower, size_t unplaced, const clipmi_model* m, int C, int L, int B, int mode, int n_ctx, int per_class,
-                             bool scaled) {
-  const int D = m->g.text_width, E = m->g.embed_dim;
-  PlacedWs w{};
-  w.head_bytes = clipmi_prompt_head_workspace_bytes(B, E, C, mode);
-  Carver c(static_cast<char*>(workspace) + tower);
-  w.text = c.take<float>((size_t)C * E * 4);
-  w.d_text = c.take<float>((size_t)C * E * 4);
-  w.d_embed = c.take<float>((size_t)C * L * D * 4);
-  w.head = c.take<char>(w.head_bytes);
-  if (scaled) {
-    w.step_bytes = clipmi_ctx_step_scaled_workspace_bytes(C, D, n_ctx, per_class);
-    w.step = c.take<char>(w.step_bytes);
-  } else if (mode == MODE_PROGRAD) {
-    w.d_text_kl = c.take<float>((size_t)C * E * 4);
-    w.d_embed_kl = c.take<float>((size_t)C * L * D * 4);
-    w.step_bytes = clipmi_prograd_step_workspace_bytes(C, D, n_ctx, per_class);
-    w.step = c.take<char>(w.step_bytes);
-  }
-  Carver x(static_cast<char*>(workspace) + unplaced);
-  w.prompts = x.take<float>((size_t)C * m->g.context_length * D * 4);
-  w.compact = x.take<float>((size_t)C * (1 + n_ctx) * D * 4);
-  if (mode == MODE_PROGRAD) w.compact_kl = x.take<float>((size_t)C * (1 + n_ctx) * D * 4);
-  return w;
-}
-
-// what the two placed steps refuse alike, before anything is launched: the tower's, the placement's and the head's checks (the step's own
-// follow in each caller).  need: the placed sizer's report; *tower: the tower's share of the workspace
-int check_placed_call(const char* who, const clipmi_model* m, const clipmi_text_dgrad* wt, const void* base, int dtype, const float* ctx, const float* buf,
-                      int n_ctx, const int32_t* eot, int C, int seq_rows, int position, const int32_t* name_lens, const float* feats, int64_t ld,
-                      const int64_t* labels, int B, float scale, int mode, const float* teacher, float w, const float* lr, float momentum, float dampening,
-                      float weight_decay, int nesterov, const float* losses, size_t need, const void* workspace, size_t workspace_bytes, const void* stash,
-                      size_t stash_bytes, size_t* tower) {
-  CLIPMI_REQUIRE(m, CLIPMI_ERR_ARG, "%s: null model", who);
-  CLIPMI_REQUIRE(C >= 2 && B >= 1, CLIPMI_ERR_SHAPE, "%s: n_prompts=%d (>= 2), B=%d (>= 1)", who, C, B);
-  CLIPMI_REQUIRE(base && ctx && lr && losses && feats && labels && eot && workspace && stash, CLIPMI_ERR_ARG,
-                 "%s: null pointer (prompts, ctx, lr, losses, feats, labels, eot, the workspace and the stash are required)", who);
-  CLIPMI_REQUIRE(mode == MODE_COOP || teacher, CLIPMI_ERR_ARG, "%s: null pointer (KgCoOp and ProGrad need the teacher)", who);
-  const int L = live_rows(m, seq_rows), Lc = m->g.context_length, D = m->g.text_width, E = m->g.embed_dim;
-  if (int rc = check_place(who, base, dtype, ctx, position, name_lens, static_cast<const float*>(workspace), C, L, Lc, D, n_ctx)) return rc;
-  CLIPMI_REQUIRE(std::isfinite(scale), CLIPMI_ERR_ARG, "%s: scale=%g (finite)", who, scale);
-  CLIPMI_REQUIRE(mode != MODE_KGCOOP || (std::isfinite(w) && w >= 0.f), CLIPMI_ERR_ARG, "%s: w=%g (finite, >= 0)", who, w);
-  CLIPMI_REQUIRE(ld >= E && (int64_t)B * C < (1ll << 31), CLIPMI_ERR_SHAPE, "%s: B=%d C=%d E=%d ld=%lld", who, B, C, E, (long long)ld);
-  if (int rc = check_sgd(who, momentum, dampening, weight_decay, nesterov)) return rc;
-  CLIPMI_REQUIRE(momentum == 0.f || buf, CLIPMI_ERR_ARG, "%s: null pointer (a momentum needs the buffer)", who);
-  CLIPMI_REQUIRE(need > 0 && workspace_bytes >= need, CLIPMI_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, need);
-  *tower = 0;
-  clipmi_text_train_bytes(m, C, seq_rows, tower, nullptr);
-  if (int rc = check_train_call(who, m, C, workspace, *tower, stash, stash_bytes, seq_rows)) return rc;
-  if (int rc = check_train_inputs(who, m, base, dtype, ctx, n_ctx, eot, seq_rows, nullptr, 0)) return rc;
-  if (int rc = check_dgrad(who, m, wt)) return rc;
-  CLIPMI_REQUIRE(L <= AB_MAX_L, CLIPMI_ERR_SHAPE, "%s: %d token rows per prompt (at most %d)", who, L, AB_MAX_L);
-  return CLIPMI_OK;
-}
-
-}  // namespace
 }  // namespace clipmi
 
 using namespace clipmi;
@@ -229,38 +171,11 @@ int clipmi_prompt_train_step_placed(clipmi_model* m, const clipmi_text_dgrad* wt
                                     const float* teacher, float w, float T, float lambda, const float* lr, int first_step, float momentum, float dampening,
                                     float weight_decay, int nesterov, float* losses, float* grad_out, int* projected, double* dots, void* workspace,
                                     size_t workspace_bytes, void* stash, size_t stash_bytes, clipmi_stream_t stream) {
-  const char* who = "prompt_train_step_placed";
-  const int C = n_prompts;
-  hipStream_t s = (hipStream_t)stream;
-  CLIPMI_REQUIRE(mode == MODE_COOP || mode == MODE_KGCOOP || mode == MODE_PROGRAD, CLIPMI_ERR_ARG, "%s: bad mode %d", who, mode);
-  CLIPMI_REQUIRE(std::isfinite(grad_scale) && grad_scale > 0.f, CLIPMI_ERR_ARG, "%s: grad_scale=%g (finite, > 0)", who, grad_scale);
-  CLIPMI_REQUIRE(mode != MODE_PROGRAD || (std::isfinite(T) && T > 0.f && std::isfinite(lambda)), CLIPMI_ERR_ARG, "%s: T=%g (finite, > 0), lambda=%g (finite)",
-                 who, T, lambda);
-  size_t tower = 0;
-  if (int rc = check_placed_call(who, m, wt, prompts, dtype, ctx, buf, n_ctx, eot, C, seq_rows, position, name_lens, feats, ld, labels, B, scale, mode, teacher, w,
-                                 lr, momentum, dampening, weight_decay, nesterov, losses,
-                                 clipmi_prompt_train_step_placed_bytes(m, C, seq_rows, B, mode, n_ctx, ctx_per_class), workspace, workspace_bytes, stash,
-                                 stash_bytes, &tower))
-    return rc;
-  const int L = live_rows(m, seq_rows), Lc = m->g.context_length, D = m->g.text_width, E = m->g.embed_dim, R = 1 + n_ctx;
-  const PlacedWs p = placed_carve(workspace, tower, clipmi_prompt_train_step_bytes(m, C, seq_rows, B, mode, n_ctx, ctx_per_class), m, C, L, B, mode, n_ctx,
-                                  ctx_per_class, false);
-  if (int rc = enqueue_place(prompts, dtype, ctx, ctx_per_class, position, name_lens, p.prompts, C, L, Lc, D, n_ctx, s)) return rc;
-  if (int rc = run_train_forward(m, p.prompts, CLIPMI_F32, nullptr, 0, 0, eot, C, seq_rows, p.text, workspace, stash, s)) return rc;
-  if (int rc = clipmi_prompt_head(feats, ld, labels, p.text, B, E, C, scale, grad_scale, mode, teacher, w, T, losses, p.d_text, nullptr, p.d_text_kl, p.head,
-                                  p.head_bytes, stream))
-    return rc;
-  if (int rc = run_backward(m, wt, p.d_text, C, seq_rows, p.d_embed, workspace, stash, nullptr, s)) return rc;
-  if (mode != MODE_PROGRAD) {
-    if (int rc = enqueue_unplace(p.d_embed, position, name_lens, p.compact, C, L, D, n_ctx, s)) return rc;
-    return clipmi_ctx_step(p.compact, ctx, buf, grad_out, C, R, D, n_ctx, ctx_per_class, grad_scale, lr, first_step, momentum, dampening, weight_decay, nesterov,
-                           stream);
-  }
-  if (int rc = run_backward(m, wt, p.d_text_kl, C, seq_rows, p.d_embed_kl, workspace, stash, nullptr, s)) return rc;
-  if (int rc = enqueue_unplace(p.d_embed, position, name_lens, p.compact, C, L, D, n_ctx, s)) return rc;
-  if (int rc = enqueue_unplace(p.d_embed_kl, position, name_lens, p.compact_kl, C, L, D, n_ctx, s)) return rc;
-  return clipmi_prograd_step(p.compact, p.compact_kl, ctx, buf, grad_out, projected, dots, C, R, D, n_ctx, ctx_per_class, grad_scale, lambda, lr, first_step,
-                             momentum, dampening, weight_decay, nesterov, p.step, p.step_bytes, stream);
+  const PromptPlacement pl{position, name_lens};
+  return prompt_train_step("prompt_train_step_placed", true, clipmi_prompt_train_step_placed_bytes(m, n_prompts, seq_rows, B, mode, n_ctx, ctx_per_class), nullptr,
+                           &pl, m, wt, prompts, dtype, ctx, buf, n_ctx, ctx_per_class, eot, n_prompts, seq_rows, feats, ld, labels, B, scale, grad_scale, mode,
+                           teacher, w, T, lambda, lr, first_step, momentum, dampening, weight_decay, nesterov, losses, grad_out, projected, dots, workspace,
+                           workspace_bytes, stash, stash_bytes, (hipStream_t)stream);
 }
 
 size_t clipmi_prompt_train_step_scaled_placed_bytes(const clipmi_model* m, int n_prompts, int seq_rows, int B, int mode, int n_ctx, int ctx_per_class) {
@@ -274,35 +189,13 @@ int clipmi_prompt_train_step_scaled_placed(clipmi_model* m, const clipmi_text_dg
                                            float growth_factor, float backoff_factor, int growth_interval, int mode, const float* teacher, float w,
                                            const float* lr, float momentum, float dampening, float weight_decay, int nesterov, float* losses, float* grad_out,
                                            void* workspace, size_t workspace_bytes, void* stash, size_t stash_bytes, clipmi_stream_t stream) {
-  const char* who = "prompt_train_step_scaled_placed";
-  const int C = n_prompts;
-  hipStream_t s = (hipStream_t)stream;
-  CLIPMI_REQUIRE(mode != MODE_PROGRAD, CLIPMI_ERR_ARG, "%s: ProGrad's mode has no dynamic loss scale (its two gradients share one step)", who);
-  CLIPMI_REQUIRE(mode == MODE_COOP || mode == MODE_KGCOOP, CLIPMI_ERR_ARG, "%s: bad mode %d", who, mode);
-  CLIPMI_REQUIRE(state, CLIPMI_ERR_ARG, "%s: null pointer (the scaler's state block)", who);
-  CLIPMI_REQUIRE((uintptr_t)state % 4 == 0, CLIPMI_ERR_ARG, "%s: the scaler's state block must be 4-byte aligned", who);
-  CLIPMI_REQUIRE(std::isfinite(growth_factor) && growth_factor > 0.f && std::isfinite(backoff_factor) && backoff_factor > 0.f, CLIPMI_ERR_ARG,
-                 "%s: growth_factor=%g, backoff_factor=%g (both finite, > 0)", who, growth_factor, backoff_factor);
-  CLIPMI_REQUIRE(growth_interval >= 1, CLIPMI_ERR_ARG, "%s: growth_interval=%d (>= 1)", who, growth_interval);
-  size_t tower = 0;
-  if (int rc = check_placed_call(who, m, wt, prompts, dtype, ctx, buf, n_ctx, eot, C, seq_rows, position, name_lens, feats, ld, labels, B, scale, mode, teacher, w,
-                                 lr, momentum, dampening, weight_decay, nesterov, losses,
-                                 clipmi_prompt_train_step_scaled_placed_bytes(m, C, seq_rows, B, mode, n_ctx, ctx_per_class), workspace, workspace_bytes,
-                                 stash, stash_bytes, &tower))
-    return rc;
-  const int L = live_rows(m, seq_rows), Lc = m->g.context_length, D = m->g.text_width, E = m->g.embed_dim, R = 1 + n_ctx;
-  const PlacedWs p = placed_carve(workspace, tower, clipmi_prompt_train_step_scaled_bytes(m, C, seq_rows, B, mode, n_ctx, ctx_per_class), m, C, L, B, mode,
-                                  n_ctx, ctx_per_class, true);
-  if (int rc = enqueue_place(prompts, dtype, ctx, ctx_per_class, position, name_lens, p.prompts, C, L, Lc, D, n_ctx, s)) return rc;
-  if (int rc = run_train_forward(m, p.prompts, CLIPMI_F32, nullptr, 0, 0, eot, C, seq_rows, p.text, workspace, stash, s)) return rc;
-  if (int rc = clipmi_prompt_head(feats, ld, labels, p.text, B, E, C, scale, 1.f, mode, teacher, w, 1.f, losses, p.d_text, nullptr, nullptr, p.head, p.head_bytes,
-                                  stream))
-    return rc;
-  if (int rc = launch_grad_scale_rows(who, p.d_text, C, E, state, s)) return rc;
-  if (int rc = run_backward(m, wt, p.d_text, C, seq_rows, p.d_embed, workspace, stash, nullptr, s)) return rc;
-  if (int rc = enqueue_unplace(p.d_embed, position, name_lens, p.compact, C, L, D, n_ctx, s)) return rc;
-  return clipmi_ctx_step_scaled(p.compact, ctx, buf, grad_out, C, R, D, n_ctx, ctx_per_class, state, growth_factor, backoff_factor, growth_interval, lr,
-                                momentum, dampening, weight_decay, nesterov, p.step, p.step_bytes, stream);
+  const ScalerCall sc{state, growth_factor, backoff_factor, growth_interval};
+  const PromptPlacement pl{position, name_lens};
+  return prompt_train_step("prompt_train_step_scaled_placed", true,
+                           clipmi_prompt_train_step_scaled_placed_bytes(m, n_prompts, seq_rows, B, mode, n_ctx, ctx_per_class), &sc, &pl, m, wt, prompts, dtype, ctx,
+                           buf, n_ctx, ctx_per_class, eot, n_prompts, seq_rows, feats, ld, labels, B, scale, 1.f, mode, teacher, w, 1.f, 0.f, lr, 0, momentum,
+                           dampening, weight_decay, nesterov, losses, grad_out, nullptr, nullptr, workspace, workspace_bytes, stash, stash_bytes,
+                           (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -218,9 +218,10 @@ __global__ __launch_bounds__(256) void kgcoop_loss_kernel(HeadWs ws, TeacherWs t
 }
 
 // The head of every mode.  losses: [3] for KgCoOp and ProGrad; CoOp writes losses[0] alone and, where the caller allows it, takes none.
-int launch_head(const char* who, bool need_losses, const float* feats, int64_t ld, const int64_t* labels, const float* text, int B, int E, int C, float scale,
-                float grad_scale, int mode, const float* teacher, float w, float T, float* losses, float* d_text, half_t* d_text16, float* d_text_kl,
-                void* workspace, size_t workspace_bytes, hipStream_t s) {
+// Everything the head refuses, before anything is launched
+int check_head(const char* who, bool need_losses, const float* feats, int64_t ld, const int64_t* labels, const float* text, int B, int E, int C, float scale,
+               float grad_scale, int mode, const float* teacher, float w, float T, const float* losses, const float* d_text, const float* d_text_kl,
+               const void* workspace, size_t workspace_bytes) {
   CLIPMI_REQUIRE(mode == MODE_COOP || mode == MODE_KGCOOP || mode == MODE_PROGRAD, CLIPMI_ERR_ARG, "%s: bad mode %d", who, mode);
   CLIPMI_REQUIRE(feats && labels && text && d_text && workspace && (losses || (mode == MODE_COOP && !need_losses)), CLIPMI_ERR_ARG, "%s: null pointer", who);
   CLIPMI_REQUIRE(mode == MODE_COOP || teacher, CLIPMI_ERR_ARG, "%s: null pointer (KgCoOp and ProGrad need the teacher)", who);
@@ -233,6 +234,12 @@ int launch_head(const char* who, bool need_losses, const float* feats, int64_t l
   CLIPMI_REQUIRE((uintptr_t)workspace % 8 == 0, CLIPMI_ERR_ARG, "%s: the workspace must be 8-byte aligned", who);
   const size_t need = clipmi_prompt_head_workspace_bytes(B, E, C, mode);
   CLIPMI_REQUIRE(workspace_bytes >= need, CLIPMI_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, need);
+  return CLIPMI_OK;
+}
+
+// the launches alone: the caller has passed check_head
+int enqueue_head(const float* feats, int64_t ld, const int64_t* labels, const float* text, int B, int E, int C, float scale, float grad_scale, int mode,
+                 const float* teacher, float w, float T, float* losses, float* d_text, half_t* d_text16, float* d_text_kl, void* workspace, hipStream_t s) {
   const HeadWs ws = head_carve(workspace, B, C);
   const TeacherWs tw = mode == MODE_COOP ? TeacherWs{} : teacher_carve(workspace, B, C);
   if (mode == MODE_COOP) teacher = nullptr;   // CoOp's head has none: a pointer passed anyway is not read
@@ -302,11 +309,9 @@ int check_ctx_step(const char* who, const float* ctx, const float* buf, const fl
   return CLIPMI_OK;
 }
 
-int launch_ctx_step(const float* d_embed, float* ctx, float* buf, float* grad_out, int C, int L, int D, int n_ctx, int per_class, float grad_scale,
-                    const float* lr, int first_step, float momentum, float dampening, float weight_decay, int nesterov, hipStream_t s) {
-  CLIPMI_REQUIRE(d_embed && (ctx || grad_out), CLIPMI_ERR_ARG, "ctx_step: null pointer (d_embed and one of ctx, grad_out are required)");
-  int64_t total;
-  if (int rc = check_ctx_step("ctx_step", ctx, buf, lr, C, L, D, n_ctx, per_class, grad_scale, momentum, dampening, weight_decay, nesterov, &total)) return rc;
+// the launch alone: the caller has passed check_ctx_step
+int enqueue_ctx_step(const float* d_embed, float* ctx, float* buf, float* grad_out, int C, int L, int D, int n_ctx, int per_class, int64_t total, float grad_scale,
+                     const float* lr, int first_step, float momentum, float dampening, float weight_decay, int nesterov, hipStream_t s) {
   hipLaunchKernelGGL(ctx_step_kernel, dim3((unsigned)((total + THREADS - 1) / THREADS)), dim3(THREADS), 0, s, d_embed, ctx, buf, grad_out, C, L, D, n_ctx,
                      per_class ? 1 : 0, 1.f / grad_scale, lr, make_sgd_args(momentum, dampening, weight_decay, nesterov, first_step));
   return check_launch("ctx_step_kernel");
@@ -381,18 +386,24 @@ __global__ __launch_bounds__(256) void prograd_step_kernel(ProgradWs w, int n_pa
   if (ctx) sgd_element_fma(ctx, buf, idx, g, *lr, sgd);
 }
 
-int launch_prograd_step(const float* d_embed_xe, const float* d_embed_kl, float* ctx, float* buf, float* grad_out, int* projected, double* dots, int C, int L,
-                        int D, int n_ctx, int per_class, float grad_scale, float lambda, const float* lr, int first_step, float momentum, float dampening,
-                        float weight_decay, int nesterov, void* workspace, size_t workspace_bytes, hipStream_t s) {
-  CLIPMI_REQUIRE(d_embed_xe && d_embed_kl && workspace, CLIPMI_ERR_ARG, "prograd_step: null pointer (both d_embed and the workspace are required)");
-  CLIPMI_REQUIRE(ctx || grad_out || projected || dots, CLIPMI_ERR_ARG, "prograd_step: null pointer (nothing to write)");
-  CLIPMI_REQUIRE(std::isfinite(lambda), CLIPMI_ERR_ARG, "prograd_step: lambda=%g (finite)", lambda);
-  int64_t total;
-  if (int rc = check_ctx_step("prograd_step", ctx, buf, lr, C, L, D, n_ctx, per_class, grad_scale, momentum, dampening, weight_decay, nesterov, &total))
-    return rc;
-  CLIPMI_REQUIRE((uintptr_t)workspace % 256 == 0, CLIPMI_ERR_ARG, "prograd_step: the workspace must be 256-byte aligned");
-  CLIPMI_REQUIRE(workspace_bytes >= prograd_step_bytes(total), CLIPMI_ERR_WORKSPACE, "prograd_step: workspace of %zu bytes, %zu needed", workspace_bytes,
-                 prograd_step_bytes(total));
+// everything clipmi_prograd_step refuses, before anything is launched; *total: the elements of ctx
+int check_prograd_step(const char* who, const float* d_embed_xe, const float* d_embed_kl, const float* ctx, const float* buf, const float* grad_out,
+                       const int* projected, const double* dots, int C, int L, int D, int n_ctx, int per_class, float grad_scale, float lambda, const float* lr,
+                       float momentum, float dampening, float weight_decay, int nesterov, const void* workspace, size_t workspace_bytes, int64_t* total) {
+  CLIPMI_REQUIRE(d_embed_xe && d_embed_kl && workspace, CLIPMI_ERR_ARG, "%s: null pointer (both d_embed and the workspace are required)", who);
+  CLIPMI_REQUIRE(ctx || grad_out || projected || dots, CLIPMI_ERR_ARG, "%s: null pointer (nothing to write)", who);
+  CLIPMI_REQUIRE(std::isfinite(lambda), CLIPMI_ERR_ARG, "%s: lambda=%g (finite)", who, lambda);
+  if (int rc = check_ctx_step(who, ctx, buf, lr, C, L, D, n_ctx, per_class, grad_scale, momentum, dampening, weight_decay, nesterov, total)) return rc;
+  CLIPMI_REQUIRE((uintptr_t)workspace % 256 == 0, CLIPMI_ERR_ARG, "%s: the workspace must be 256-byte aligned", who);
+  CLIPMI_REQUIRE(workspace_bytes >= prograd_step_bytes(*total), CLIPMI_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes,
+                 prograd_step_bytes(*total));
+  return CLIPMI_OK;
+}
+
+// the two launches: the caller has passed check_prograd_step
+int enqueue_prograd_step(const float* d_embed_xe, const float* d_embed_kl, float* ctx, float* buf, float* grad_out, int* projected, double* dots, int C, int L,
+                         int D, int n_ctx, int per_class, int64_t total, float grad_scale, float lambda, const float* lr, int first_step, float momentum,
+                         float dampening, float weight_decay, int nesterov, void* workspace, hipStream_t s) {
   const ProgradWs w = prograd_carve(workspace, total);
   const int64_t blocks = (total + 255) / 256;
   const int n_part = (int)(blocks < DOT_BLOCKS ? blocks : DOT_BLOCKS);
@@ -406,52 +417,115 @@ int launch_prograd_step(const float* d_embed_xe, const float* d_embed_kl, float*
 
 // ------------------------------------------------------------------------------------------------------------------ the one-call step
 // The tower's training forward, the head, the backward (twice for ProGrad: the stash is read-only in it and the tower's workspace is reused, so
-// the second follows the first on the stream) and the step.  workspace: the tower's workspace | text features [C, E] | their gradient
-// [C, E] | d_embed [M, D] | the head's workspace and, for ProGrad, | the second gradient [C, E] | the second d_embed [M, D] |
-// clipmi_prograd_step's workspace.  need: what the calling symbol's sizing function reports.
-int train_step(const char* who, bool need_losses, size_t need, clipmi_model* m, const clipmi_text_dgrad* wt, const void* prompts, int dtype, float* ctx,
-               float* buf, int n_ctx, int per_class, const int32_t* eot, int C, int seq_rows, const float* feats, int64_t ld, const int64_t* labels, int B,
-               float scale, float grad_scale, int mode, const float* teacher, float w, float T, float lambda, const float* lr, int first_step, float momentum,
-               float dampening, float weight_decay, int nesterov, float* losses, float* grad_out, int* projected, double* dots, void* workspace,
-               size_t workspace_bytes, void* stash, size_t stash_bytes, hipStream_t s) {
-  CLIPMI_REQUIRE(m, CLIPMI_ERR_ARG, "%s: null model", who);
+// the second follows the first on the stream) and the step: one body behind clipmi_prompt_train_step, clipmi_coop_train_step and their
+// _scaled, _placed and _scaled_placed variants (model.h).  workspace: the tower's workspace | text features [C, E] | their gradient [C, E] |
+// d_embed [M, D] | the head's workspace | the step's: clipmi_ctx_step_scaled's under a dynamic scale, for ProGrad the second gradient [C, E] |
+// the second d_embed [M, D] | clipmi_prograd_step's workspace.  Behind all that, at the offset the unplaced sizer reports, a placed step keeps
+// the placed prompts fp32 [C, Lc, D] | the compact gradient [C (1 + n_ctx), D] and, for ProGrad, | the second one.
+struct StepWs {
+  float *text, *d_text, *d_embed, *d_text_kl, *d_embed_kl, *prompts, *compact, *compact_kl;
+  void *head, *step;
+  size_t head_bytes, step_bytes;
+};
+StepWs step_carve(void* workspace, size_t tower, size_t unplaced, const clipmi_model* m, int C, int L, int B, int mode, int n_ctx, int per_class, bool scaled,
+                  bool placed) {
+  const int D = m->g.text_width, E = m->g.embed_dim;
+  StepWs w{};
+  w.head_bytes = clipmi_prompt_head_workspace_bytes(B, E, C, mode);
+  Carver c(static_cast<char*>(workspace) + tower);
+  w.text = c.take<float>((size_t)C * E * 4);
+  w.d_text = c.take<float>((size_t)C * E * 4);
+  w.d_embed = c.take<float>((size_t)C * L * D * 4);
+  w.head = c.take<char>(w.head_bytes);
+  if (scaled) {
+    w.step_bytes = clipmi_ctx_step_scaled_workspace_bytes(C, D, n_ctx, per_class);
+    w.step = c.take<char>(w.step_bytes);
+  } else if (mode == MODE_PROGRAD) {
+    w.d_text_kl = c.take<float>((size_t)C * E * 4);
+    w.d_embed_kl = c.take<float>((size_t)C * L * D * 4);
+    w.step_bytes = clipmi_prograd_step_workspace_bytes(C, D, n_ctx, per_class);
+    w.step = c.take<char>(w.step_bytes);
+  }
+  if (!placed) return w;
+  Carver x(static_cast<char*>(workspace) + unplaced);
+  w.prompts = x.take<float>((size_t)C * m->g.context_length * D * 4);
+  w.compact = x.take<float>((size_t)C * (1 + n_ctx) * D * 4);
+  if (mode == MODE_PROGRAD) w.compact_kl = x.take<float>((size_t)C * (1 + n_ctx) * D * 4);
+  return w;
+}
+
+}  // namespace
+
+int prompt_train_step(const char* who, bool need_losses, size_t need, const ScalerCall* sc, const PromptPlacement* pl, clipmi_model* m,
+                      const clipmi_text_dgrad* wt, const void* prompts, int dtype, float* ctx, float* buf, int n_ctx, int per_class, const int32_t* eot, int C,
+                      int seq_rows, const float* feats, int64_t ld, const int64_t* labels, int B, float scale, float grad_scale, int mode, const float* teacher,
+                      float w, float T, float lambda, const float* lr, int first_step, float momentum, float dampening, float weight_decay, int nesterov,
+                      float* losses, float* grad_out, int* projected, double* dots, void* workspace, size_t workspace_bytes, void* stash, size_t stash_bytes,
+                      hipStream_t s) {
+  // every refusal of every stage comes before the first launch: a refused call enqueues nothing.  The text weights are looked at last
+  CLIPMI_REQUIRE(!sc || mode != MODE_PROGRAD, CLIPMI_ERR_ARG, "%s: ProGrad's mode has no dynamic loss scale (its two gradients share one step)", who);
   CLIPMI_REQUIRE(mode == MODE_COOP || mode == MODE_KGCOOP || mode == MODE_PROGRAD, CLIPMI_ERR_ARG, "%s: bad mode %d", who, mode);
+  if (sc)
+    if (int rc = check_scaler(who, *sc)) return rc;
+  CLIPMI_REQUIRE(m, CLIPMI_ERR_ARG, "%s: null model", who);
   CLIPMI_REQUIRE(C >= 2 && B >= 1, CLIPMI_ERR_SHAPE, "%s: n_prompts=%d (>= 2), B=%d (>= 1)", who, C, B);
   CLIPMI_REQUIRE(ctx && lr && (losses || !need_losses), CLIPMI_ERR_ARG, "%s: null pointer (ctx and lr%s are required)", who, need_losses ? " and losses" : "");
+  const int L = live_rows(m, seq_rows), Lc = m->g.context_length, D = m->g.text_width, E = m->g.embed_dim;
+  const int R = pl ? 1 + n_ctx : L;   // the rows per class of the gradient stream the step reads
+  if (pl)   // the prompt buffer lies a multiple of 256 bytes behind the workspace's start
+    if (int rc = check_place(who, prompts, dtype, ctx, pl->position, pl->name_lens, static_cast<const float*>(workspace), C, L, Lc, D, n_ctx)) return rc;
   CLIPMI_REQUIRE(need > 0 && workspace_bytes >= need, CLIPMI_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, need);
   size_t tower = 0;
   clipmi_text_train_bytes(m, C, seq_rows, &tower, nullptr);
-  if (int rc = check_train_call(who, m, C, workspace, tower, stash, stash_bytes, seq_rows)) return rc;
-  if (int rc = check_train_inputs(who, m, prompts, dtype, ctx, n_ctx, eot, seq_rows, nullptr, 0)) return rc;
-  if (int rc = check_dgrad(who, m, wt)) return rc;
-  const int L = live_rows(m, seq_rows), D = m->g.text_width, E = m->g.embed_dim;
-  CLIPMI_REQUIRE(L <= AB_MAX_L, CLIPMI_ERR_SHAPE, "%s: %d token rows per prompt (at most %d)", who, L, AB_MAX_L);
-  const size_t head_bytes = clipmi_prompt_head_workspace_bytes(B, E, C, mode);
-  size_t step_bytes = 0;
-  Carver c(static_cast<char*>(workspace) + tower);
-  float* text = c.take<float>((size_t)C * E * 4);
-  float* d_text = c.take<float>((size_t)C * E * 4);
-  float* d_embed = c.take<float>((size_t)C * L * D * 4);
-  void* head_ws = c.take<char>(head_bytes);
-  float *d_text_kl = nullptr, *d_embed_kl = nullptr;
-  void* step_ws = nullptr;
-  if (mode == MODE_PROGRAD) {
-    d_text_kl = c.take<float>((size_t)C * E * 4);
-    d_embed_kl = c.take<float>((size_t)C * L * D * 4);
-    step_bytes = clipmi_prograd_step_workspace_bytes(C, D, n_ctx, per_class);
-    step_ws = c.take<char>(step_bytes);
-  }
-  if (int rc = run_train_forward(m, prompts, dtype, ctx, n_ctx, per_class, eot, C, seq_rows, text, workspace, stash, s)) return rc;
-  if (int rc = launch_head(who, need_losses, feats, ld, labels, text, B, E, C, scale, grad_scale, mode, teacher, w, T, losses, d_text, nullptr, d_text_kl, head_ws,
-                           head_bytes, s))
+  const size_t unplaced = !pl ? 0
+                          : sc ? clipmi_prompt_train_step_scaled_bytes(m, C, seq_rows, B, mode, n_ctx, per_class)
+                               : clipmi_prompt_train_step_bytes(m, C, seq_rows, B, mode, n_ctx, per_class);
+  const StepWs p = step_carve(workspace, tower, unplaced, m, C, L, B, mode, n_ctx, per_class, sc != nullptr, pl != nullptr);
+  if (int rc = check_head(who, need_losses, feats, ld, labels, p.text, B, E, C, scale, grad_scale, mode, teacher, w, T, losses, p.d_text, p.d_text_kl, p.head,
+                          p.head_bytes))
     return rc;
-  if (int rc = run_backward(m, wt, d_text, C, seq_rows, d_embed, workspace, stash, nullptr, s)) return rc;
+  const float *g = pl ? p.compact : p.d_embed, *g_kl = pl ? p.compact_kl : p.d_embed_kl;
+  int64_t total;
+  if (sc) {
+    if (int rc = check_ctx_step_scaled(who, g, ctx, buf, lr, C, R, D, n_ctx, per_class, *sc, momentum, dampening, weight_decay, nesterov, p.step, p.step_bytes,
+                                       &total))
+      return rc;
+  } else if (mode != MODE_PROGRAD) {
+    if (int rc = check_ctx_step(who, ctx, buf, lr, C, R, D, n_ctx, per_class, grad_scale, momentum, dampening, weight_decay, nesterov, &total)) return rc;
+  } else if (int rc = check_prograd_step(who, g, g_kl, ctx, buf, grad_out, projected, dots, C, R, D, n_ctx, per_class, grad_scale, lambda, lr, momentum,
+                                         dampening, weight_decay, nesterov, p.step, p.step_bytes, &total)) {
+    return rc;
+  }
+  if (int rc = check_train_inputs(who, m, prompts, dtype, ctx, n_ctx, eot, seq_rows, nullptr, 0)) return rc;
+  if (int rc = check_train_call(who, m, C, workspace, tower, stash, stash_bytes, seq_rows)) return rc;
+  if (int rc = check_dgrad(who, m, wt)) return rc;
+  CLIPMI_REQUIRE(L <= AB_MAX_L, CLIPMI_ERR_SHAPE, "%s: %d token rows per prompt (at most %d)", who, L, AB_MAX_L);
+  if (pl) {   // the context already lies on its rows of the fp32 prompts: the tower splices nothing
+    if (int rc = enqueue_place(prompts, dtype, ctx, per_class, pl->position, pl->name_lens, p.prompts, C, L, Lc, D, n_ctx, s)) return rc;
+    if (int rc = run_train_forward(m, p.prompts, CLIPMI_F32, nullptr, 0, 0, eot, C, seq_rows, p.text, workspace, stash, s)) return rc;
+  } else if (int rc = run_train_forward(m, prompts, dtype, ctx, n_ctx, per_class, eot, C, seq_rows, p.text, workspace, stash, s)) {
+    return rc;
+  }
+  if (int rc = enqueue_head(feats, ld, labels, p.text, B, E, C, scale, grad_scale, mode, teacher, w, T, losses, p.d_text, nullptr, p.d_text_kl, p.head, s)) return rc;
+  if (sc)
+    if (int rc = launch_grad_scale_rows(who, p.d_text, C, E, sc->state, s)) return rc;
+  if (int rc = run_backward(m, wt, p.d_text, C, seq_rows, p.d_embed, workspace, stash, nullptr, s)) return rc;
+  if (mode == MODE_PROGRAD)
+    if (int rc = run_backward(m, wt, p.d_text_kl, C, seq_rows, p.d_embed_kl, workspace, stash, nullptr, s)) return rc;
+  if (pl) {
+    if (int rc = enqueue_unplace(p.d_embed, pl->position, pl->name_lens, p.compact, C, L, D, n_ctx, s)) return rc;
+    if (mode == MODE_PROGRAD)
+      if (int rc = enqueue_unplace(p.d_embed_kl, pl->position, pl->name_lens, p.compact_kl, C, L, D, n_ctx, s)) return rc;
+  }
+  if (sc)
+    return launch_ctx_step_scaled(g, ctx, buf, grad_out, C, R, D, n_ctx, per_class, total, *sc, lr, momentum, dampening, weight_decay, nesterov, p.step, s);
   if (mode != MODE_PROGRAD)
-    return launch_ctx_step(d_embed, ctx, buf, grad_out, C, L, D, n_ctx, per_class, grad_scale, lr, first_step, momentum, dampening, weight_decay, nesterov, s);
-  if (int rc = run_backward(m, wt, d_text_kl, C, seq_rows, d_embed_kl, workspace, stash, nullptr, s)) return rc;
-  return launch_prograd_step(d_embed, d_embed_kl, ctx, buf, grad_out, projected, dots, C, L, D, n_ctx, per_class, grad_scale, lambda, lr, first_step, momentum,
-                             dampening, weight_decay, nesterov, step_ws, step_bytes, s);
+    return enqueue_ctx_step(g, ctx, buf, grad_out, C, R, D, n_ctx, per_class, total, grad_scale, lr, first_step, momentum, dampening, weight_decay, nesterov, s);
+  return enqueue_prograd_step(g, g_kl, ctx, buf, grad_out, projected, dots, C, R, D, n_ctx, per_class, total, grad_scale, lambda, lr, first_step, momentum,
+                              dampening, weight_decay, nesterov, p.step, s);
 }
+
+namespace {
 
 // ------------------------------------------------------------------------------------------------------------------------------ VPT
 // (reference trainers/classification/vpt.py: the text features are fixed, the image features carry the gradient).  The head is CoOp's
@@ -792,8 +866,11 @@ size_t clipmi_prompt_head_workspace_bytes(int B, int E, int C, int mode) {
 int clipmi_prompt_head(const float* feats, int64_t ld, const int64_t* labels, const float* text, int B, int E, int C, float scale, float grad_scale,
                        int mode, const float* teacher, float w, float T, float* losses, float* d_text, void* d_text16, float* d_text_kl,
                        void* workspace, size_t workspace_bytes, clipmi_stream_t stream) {
-  return launch_head("prompt_head", true, feats, ld, labels, text, B, E, C, scale, grad_scale, mode, teacher, w, T, losses, d_text,
-                     static_cast<half_t*>(d_text16), d_text_kl, workspace, workspace_bytes, (hipStream_t)stream);
+  if (int rc = check_head("prompt_head", true, feats, ld, labels, text, B, E, C, scale, grad_scale, mode, teacher, w, T, losses, d_text, d_text_kl, workspace,
+                          workspace_bytes))
+    return rc;
+  return enqueue_head(feats, ld, labels, text, B, E, C, scale, grad_scale, mode, teacher, w, T, losses, d_text, static_cast<half_t*>(d_text16), d_text_kl,
+                      workspace, (hipStream_t)stream);
 }
 
 // CoOp's own symbols: mode 0 of the above, except that the loss may be NULL
@@ -801,14 +878,20 @@ size_t clipmi_coop_head_workspace_bytes(int B, int E, int C) { return clipmi_pro
 
 int clipmi_coop_head(const float* feats, int64_t ld, const int64_t* labels, const float* text, int B, int E, int C, float scale, float grad_scale,
                      float* loss, float* d_text, void* d_text16, void* workspace, size_t workspace_bytes, clipmi_stream_t stream) {
-  return launch_head("coop_head", false, feats, ld, labels, text, B, E, C, scale, grad_scale, MODE_COOP, nullptr, 0.f, 0.f, loss, d_text,
-                     static_cast<half_t*>(d_text16), nullptr, workspace, workspace_bytes, (hipStream_t)stream);
+  if (int rc = check_head("coop_head", false, feats, ld, labels, text, B, E, C, scale, grad_scale, MODE_COOP, nullptr, 0.f, 0.f, loss, d_text, nullptr, workspace,
+                          workspace_bytes))
+    return rc;
+  return enqueue_head(feats, ld, labels, text, B, E, C, scale, grad_scale, MODE_COOP, nullptr, 0.f, 0.f, loss, d_text, static_cast<half_t*>(d_text16), nullptr,
+                      workspace, (hipStream_t)stream);
 }
 
 int clipmi_ctx_step(const float* d_embed, float* ctx, float* buf, float* grad_out, int C, int L, int D, int n_ctx, int per_class, float grad_scale,
                     const float* lr, int first_step, float momentum, float dampening, float weight_decay, int nesterov, clipmi_stream_t stream) {
-  return launch_ctx_step(d_embed, ctx, buf, grad_out, C, L, D, n_ctx, per_class, grad_scale, lr, first_step, momentum, dampening, weight_decay, nesterov,
-                         (hipStream_t)stream);
+  CLIPMI_REQUIRE(d_embed && (ctx || grad_out), CLIPMI_ERR_ARG, "ctx_step: null pointer (d_embed and one of ctx, grad_out are required)");
+  int64_t total;
+  if (int rc = check_ctx_step("ctx_step", ctx, buf, lr, C, L, D, n_ctx, per_class, grad_scale, momentum, dampening, weight_decay, nesterov, &total)) return rc;
+  return enqueue_ctx_step(d_embed, ctx, buf, grad_out, C, L, D, n_ctx, per_class, total, grad_scale, lr, first_step, momentum, dampening, weight_decay, nesterov,
+                          (hipStream_t)stream);
 }
 
 size_t clipmi_prograd_step_workspace_bytes(int C, int D, int n_ctx, int per_class) {
@@ -819,8 +902,12 @@ size_t clipmi_prograd_step_workspace_bytes(int C, int D, int n_ctx, int per_clas
 int clipmi_prograd_step(const float* d_embed_xe, const float* d_embed_kl, float* ctx, float* buf, float* grad_out, int* projected, double* dots, int C,
                         int L, int D, int n_ctx, int per_class, float grad_scale, float lambda, const float* lr, int first_step, float momentum,
                         float dampening, float weight_decay, int nesterov, void* workspace, size_t workspace_bytes, clipmi_stream_t stream) {
-  return launch_prograd_step(d_embed_xe, d_embed_kl, ctx, buf, grad_out, projected, dots, C, L, D, n_ctx, per_class, grad_scale, lambda, lr, first_step,
-                             momentum, dampening, weight_decay, nesterov, workspace, workspace_bytes, (hipStream_t)stream);
+  int64_t total;
+  if (int rc = check_prograd_step("prograd_step", d_embed_xe, d_embed_kl, ctx, buf, grad_out, projected, dots, C, L, D, n_ctx, per_class, grad_scale, lambda, lr,
+                                  momentum, dampening, weight_decay, nesterov, workspace, workspace_bytes, &total))
+    return rc;
+  return enqueue_prograd_step(d_embed_xe, d_embed_kl, ctx, buf, grad_out, projected, dots, C, L, D, n_ctx, per_class, total, grad_scale, lambda, lr, first_step,
+                              momentum, dampening, weight_decay, nesterov, workspace, (hipStream_t)stream);
 }
 
 size_t clipmi_prompt_train_step_bytes(const clipmi_model* m, int n_prompts, int seq_rows, int B, int mode, int n_ctx, int ctx_per_class) {
@@ -841,10 +928,10 @@ int clipmi_prompt_train_step(clipmi_model* m, const clipmi_text_dgrad* wt, const
                              int first_step, float momentum, float dampening, float weight_decay, int nesterov, float* losses, float* grad_out,
                              int* projected, double* dots, void* workspace, size_t workspace_bytes, void* stash, size_t stash_bytes,
                              clipmi_stream_t stream) {
-  return train_step("prompt_train_step", true, clipmi_prompt_train_step_bytes(m, n_prompts, seq_rows, B, mode, n_ctx, ctx_per_class), m, wt, prompts, dtype, ctx,
-                    buf, n_ctx, ctx_per_class, eot, n_prompts, seq_rows, feats, ld, labels, B, scale, grad_scale, mode, teacher, w, T, lambda, lr, first_step,
-                    momentum, dampening, weight_decay, nesterov, losses, grad_out, projected, dots, workspace, workspace_bytes, stash, stash_bytes,
-                    (hipStream_t)stream);
+  return prompt_train_step("prompt_train_step", true, clipmi_prompt_train_step_bytes(m, n_prompts, seq_rows, B, mode, n_ctx, ctx_per_class), nullptr, nullptr, m,
+                           wt, prompts, dtype, ctx, buf, n_ctx, ctx_per_class, eot, n_prompts, seq_rows, feats, ld, labels, B, scale, grad_scale, mode, teacher, w, T,
+                           lambda, lr, first_step, momentum, dampening, weight_decay, nesterov, losses, grad_out, projected, dots, workspace, workspace_bytes,
+                           stash, stash_bytes, (hipStream_t)stream);
 }
 
 // CoOp's own symbols: mode 0 of the above (whose size does not depend on the context), except that the loss may be NULL
@@ -857,9 +944,10 @@ int clipmi_coop_train_step(clipmi_model* m, const clipmi_text_dgrad* wt, const v
                            float scale, float grad_scale, const float* lr, int first_step, float momentum, float dampening, float weight_decay,
                            int nesterov, float* loss, float* grad_out, void* workspace, size_t workspace_bytes, void* stash, size_t stash_bytes,
                            clipmi_stream_t stream) {
-  return train_step("coop_train_step", false, clipmi_coop_train_step_bytes(m, n_prompts, seq_rows, B), m, wt, prompts, dtype, ctx, buf, n_ctx, ctx_per_class, eot,
-                    n_prompts, seq_rows, feats, ld, labels, B, scale, grad_scale, MODE_COOP, nullptr, 0.f, 0.f, 0.f, lr, first_step, momentum, dampening,
-                    weight_decay, nesterov, loss, grad_out, nullptr, nullptr, workspace, workspace_bytes, stash, stash_bytes, (hipStream_t)stream);
+  return prompt_train_step("coop_train_step", false, clipmi_coop_train_step_bytes(m, n_prompts, seq_rows, B), nullptr, nullptr, m, wt, prompts, dtype, ctx, buf,
+                           n_ctx, ctx_per_class, eot, n_prompts, seq_rows, feats, ld, labels, B, scale, grad_scale, MODE_COOP, nullptr, 0.f, 0.f, 0.f, lr,
+                           first_step, momentum, dampening, weight_decay, nesterov, loss, grad_out, nullptr, nullptr, workspace, workspace_bytes, stash,
+                           stash_bytes, (hipStream_t)stream);
 }
 
 // ---- VPT
@@ -918,8 +1006,8 @@ static int vpt_train_step(const char* who, const ScalerCall* sc, size_t need, cl
   if (sc) {   // the scaler's and the optimiser's refusals come ahead of the first launch
     CLIPMI_REQUIRE(need > 0, CLIPMI_ERR_SHAPE, "%s: B=%d n_ctx=%d depth=%d C=%d", who, B, n_ctx, depth, C);
     CLIPMI_REQUIRE(std::isfinite(scale), CLIPMI_ERR_ARG, "%s: scale=%g (finite)", who, scale);
-    if (int rc = check_block_step_scaled(who, d_prompts, prompts, buf, grad_out, lr, total, sc->state, sc->growth, sc->backoff, sc->interval, momentum,
-                                         dampening, weight_decay, nesterov, scaled_ws, scaled_bytes))
+    if (int rc = check_block_step_scaled(who, d_prompts, prompts, buf, grad_out, lr, total, *sc, momentum, dampening, weight_decay, nesterov, scaled_ws,
+                                         scaled_bytes))
       return rc;
   }
   if (int rc = run_vision_train_forward(m, image, image_dtype, B, prompts, n_ctx, depth, feats, workspace, stash, s)) return rc;
@@ -928,8 +1016,7 @@ static int vpt_train_step(const char* who, const ScalerCall* sc, size_t need, cl
     if (int rc = launch_grad_scale_rows(who, d_feats, B, E, sc->state, s)) return rc;
   if (int rc = run_vision_backward(m, wt, d_feats, B, n_ctx, depth, d_prompts, workspace, stash, nullptr, s)) return rc;
   if (sc)
-    return launch_block_step_scaled(d_prompts, prompts, buf, grad_out, total, sc->state, sc->growth, sc->backoff, sc->interval, lr, momentum, dampening,
-                                    weight_decay, nesterov, scaled_ws, s);
+    return launch_block_step_scaled(d_prompts, prompts, buf, grad_out, total, *sc, lr, momentum, dampening, weight_decay, nesterov, scaled_ws, s);
   return launch_vpt_step(who, d_prompts, prompts, buf, grad_out, depth, n_ctx, D, grad_scale, lr, first_step, momentum, dampening, weight_decay, nesterov, s);
 }
 

@@ -213,7 +213,7 @@ static int promptsrc_train_step(const char* who, const ScalerCall* sc, clipmi_mo
   if (int rc = check_vision_dgrad(who, m, wv)) return rc;
   CLIPMI_REQUIRE(image_dtype == CLIPMI_F16 || image_dtype == CLIPMI_F32, CLIPMI_ERR_ARG, "%s: image dtype %d", who, image_dtype);
   if (sc) {
-    if (int rc = check_block_step_scaled(who, scaled_grad, block, buf, grad_out, lr, total, sc->state, sc->growth, sc->backoff, sc->interval, momentum,
+    if (int rc = check_block_step_scaled(who, scaled_grad, block, buf, grad_out, lr, total, *sc, momentum,
                                          dampening, weight_decay, nesterov, scaled_ws, scaled_bytes))
       return rc;
   } else if (int rc = check_step_args(who, block, buf, grad_out, 1, lr, grad_scale, momentum, dampening, weight_decay, nesterov)) {
@@ -242,7 +242,7 @@ static int promptsrc_train_step(const char* who, const ScalerCall* sc, clipmi_mo
     if (int rc = launch_step(who, w.d_embed, w.d_deep, w.d_vis, block, nullptr, scaled_grad, 0, C, L, nt, dt, Dt, nv, dv, Dv, 1.f, nullptr, 0, momentum,
                              dampening, weight_decay, nesterov, s))
       return rc;
-    return launch_block_step_scaled(scaled_grad, block, buf, grad_out, total, sc->state, sc->growth, sc->backoff, sc->interval, lr, momentum, dampening,
+    return launch_block_step_scaled(scaled_grad, block, buf, grad_out, total, *sc, lr, momentum, dampening,
                                     weight_decay, nesterov, scaled_ws, s);
   }
   return launch_step(who, w.d_embed, w.d_deep, w.d_vis, block, buf, grad_out, 1, C, L, nt, dt, Dt, nv, dv, Dv, grad_scale, lr, first_step, momentum, dampening,

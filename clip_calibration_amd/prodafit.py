@@ -48,7 +48,7 @@ import torch
 
 from . import _lib, fitloop, ops
 from ._lib import check, lib
-from .coopfit import DEFAULT_GRAD_SCALE, DYNAMIC, MAX_LIVE_ROWS, _DT, _Tower, _check_batch, _check_grad_scale, _is_dynamic, _live_rows, _scale_args
+from .coopfit import DEFAULT_GRAD_SCALE, DYNAMIC, MAX_LIVE_ROWS, _DT, _BlockScaler, _Tower, _check_batch, _check_grad_scale, _is_dynamic, _live_rows, _scale_args
 from .fitloop import _host_int_array, _need_gpu, steps_per_epoch
 
 
@@ -255,16 +255,14 @@ class ProDAFitState:
         self.pos_host = positions(self.P)
         self._perm = None
         self.steps = 0
-        if self.dynamic:
-            self.scaler_block = ops.new_scaler_state(self.scaler["init_scale"], dev)   # clipmi_scaler_state; only the kernels touch it from here on
-            self.scaled_ws = None
+        self._scaler = _BlockScaler(self.scaler, dev) if self.dynamic else None
 
     def scaler_state(self) -> dict:
         """The dynamic scale's block as ``dict(scale, growth_tracker, skipped_steps, applied_steps, found_inf)`` (``found_inf``: of the
         last step).  It waits for the steps enqueued so far: one synchronisation, the only read-back of the dynamic path."""
         if not self.dynamic:
             raise ValueError(f"ProDAFitState.scaler_state: the state was made with a static grad_scale={self.grad_scale}")
-        return ops.scaler_state_dict(self.scaler_block)
+        return self._scaler.state()
 
     def next_selection(self) -> np.ndarray:
         """The schedule's next slice (``draw_selections``, one step at a time)."""
@@ -326,7 +324,7 @@ class ProDAFitState:
     def _step_scaled(self, features, labels_d, sel_d, lr_d, losses, one_call: bool) -> None:
         """``step`` under the dynamic scale: the head at grad_scale = 1, its d_text times the block's scale, the backward, and
         clipmi_proda_ctx_step_scaled, which decides on the device whether the step is applied."""
-        t, m, sc = self.tower, self.tower.model, self.scaler
+        t, m, sc = self.tower, self.tower.model, self._scaler
         sgd = (float(self.momentum), float(self.dampening), float(self.weight_decay), int(bool(self.nesterov)))
         if one_call:
             ws = t.one_call_workspace(features.shape[0], scaled=True)
@@ -335,20 +333,19 @@ class ProDAFitState:
                                                          self.ctx.data_ptr(), None if self.buf is None else self.buf.data_ptr(), t.n_ctx,
                                                          sel_d.data_ptr(), t.pos.data_ptr(), t.name_lens.data_ptr(), t.cls_eot.data_ptr(), t.n_cls, t.Pb,
                                                          t.P, t.rows, features.data_ptr(), features.stride(0), labels_d.data_ptr(), features.shape[0],
-                                                         self.scale, self.scaler_block.data_ptr(), sc["growth_factor"], sc["backoff_factor"],
-                                                         sc["growth_interval"], self.alpha, lr_d.data_ptr(), *sgd, losses.data_ptr(), None,
+                                                         self.scale, sc.block.data_ptr(), *sc.args(), self.alpha, lr_d.data_ptr(), *sgd, losses.data_ptr(), None,
                                                          ws.data_ptr(), ws.numel(), t.stash.data_ptr(), t.stash.numel(), ops._stream()),
                       "clipmi_proda_train_step_scaled")
             return
         text = t.forward(self.ctx, sel_d)
         _, d_text = ops.proda_head(features, labels_d, text, t.n_cls, t.Pb, self.scale, 1.0, self.alpha, losses)
-        ops.grad_scale_rows(d_text, self.scaler_block)
+        ops.grad_scale_rows(d_text, sc.block)
         d_embed = t.backward(d_text)
-        if self.scaled_ws is None:
+        if sc.ws is None:
             need = lib.clipmi_proda_ctx_step_scaled_workspace_bytes(t.P, t.D, t.n_ctx)
-            self.scaled_ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.ctx.device)
-        ops.proda_ctx_step_scaled(d_embed, sel_d, t.pos, t.name_lens, t.n_ctx, self.scaler_block, self.ctx, self.buf, lr_d, sc["growth_factor"],
-                                  sc["backoff_factor"], sc["growth_interval"], *sgd[:3], bool(sgd[3]), want_grad=False, workspace=self.scaled_ws)
+            sc.ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.ctx.device)
+        ops.proda_ctx_step_scaled(d_embed, sel_d, t.pos, t.name_lens, t.n_ctx, sc.block, self.ctx, self.buf, lr_d, *sc.args(), *sgd[:3], bool(sgd[3]),
+                                  want_grad=False, workspace=sc.ws)
 
 
 def init_context(clip_model, n_ctx: int = 16, n_prompt: int = 32, seed: int = 0) -> torch.Tensor:

@@ -75,7 +75,7 @@ def time_device(model, ids, ctx, feats, labels, cut, iters, warmup):
         torch.cuda.synchronize()
         phases.append([e[i].elapsed_time(e[i + 1]) for i in range(4)])
     med = [statistics.median(p[i] for p in phases) for i in range(4)]
-    return {"step_ms": statistics.median(ms), "forward_ms": med[0], "head_ms": med[1], "backward_ms": med[2], "ctx_step_ms": med[3],
+    return {"step_ms": statistics.median(ms), "step_ms_min": min(ms), "step_ms_max": max(ms), "forward_ms": med[0], "head_ms": med[1], "backward_ms": med[2], "ctx_step_ms": med[3],
             "token_rows_per_prompt": t.L, "stash_bytes": t.stash_bytes, "workspace_bytes": t.ws.numel()}
 
 

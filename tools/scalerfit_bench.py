@@ -60,9 +60,9 @@ def time_steps(model, ids, ctx, feats, labels, iters, warmup):
         e[1].record()
         torch.cuda.synchronize()
         e[2].record()
-        ops.grad_scale_rows(d_text, st_d.scaler_block)
-        ops.ctx_step_scaled(t.d_embed, t.C, t.n_ctx, t.per_class, st_d.scaler_block, st_d.ctx, st_d.buf, lr, 2.0, 0.5, SCALER["growth_interval"], *sgd,
-                            want_grad=False, workspace=st_d.scaled_ws)
+        ops.grad_scale_rows(d_text, st_d._scaler.block)
+        ops.ctx_step_scaled(t.d_embed, t.C, t.n_ctx, t.per_class, st_d._scaler.block, st_d.ctx, st_d.buf, lr, 2.0, 0.5, SCALER["growth_interval"], *sgd,
+                            want_grad=False, workspace=st_d._scaler.ws)
         e[3].record()
         torch.cuda.synchronize()
         if k >= warmup:

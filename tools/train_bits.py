@@ -1,6 +1,6 @@
 """SHA-256 of what the training kernels write, from fixed seeds: one case per kernel family that shares train_rules.h -- the TaskRes step
-(SGD and Adam), the adapter step, the loss heads of the three prompt learners, the context step, ProGrad's step, the one-call steps and
-the TempScaling fit.  Two builds of the library compute the same thing exactly when every digest is equal.
+(SGD and Adam), the adapter step, the loss heads of the three prompt learners, the context step, ProGrad's step, the one-call steps (static, under the
+dynamic loss scale and with the class token at the front or in the middle) and the TempScaling fit.  Two builds of the library compute the same thing exactly when every digest is equal.
 
 The library is whichever build CLIPMI_LIBRARY names (default: the in-tree one).  Run it once per build, each in a process of its own,
 and compare the files:
@@ -133,6 +133,41 @@ def cases():
                     check(lib.clipmi_prompt_train_step(*head, mode, tea.data_ptr(), 8.0, 2.0, 0.8, *sgd, losses[k].data_ptr(), grad[k].data_ptr(), None,
                                                        None, *tail), name)
         yield name, digest(st.ctx, st.buf, losses, grad)
+    # the scaled and the placed one-call steps at the same size: generic and class-specific context, uneven name lengths with a 0 among them
+    # (prompt_ids gives class c a name of c tokens), a first step that overflows fp16 and is skipped.  ProGrad's digests add projected and dots
+    ctx0c = 0.02 * torch.randn(3, 4, syn.GEOMETRIES["tiny"].transformer_width, generator=g)
+    plain, skip = {"init_scale": 256.0, "growth_interval": 1}, {"init_scale": 2.0 ** 40, "backoff_factor": 2.0 ** -28}
+    runs = [(f"prompt_train_step_scaled {method} per_class={pc}", method, pc, None, plain) for method in ("coop", "kgcoop") for pc in (0, 1)]
+    runs += [("prompt_train_step_scaled coop first step skipped", "coop", 0, None, skip)]
+    runs += [(f"prompt_train_step_placed {method} {pos}", method, 0, pos, None) for method in ("coop", "kgcoop", "prograd") for pos in ("middle", "front")]
+    runs += [(f"prompt_train_step_scaled_placed {method} {pos}", method, 0, pos, plain) for method in ("coop", "kgcoop") for pos in ("middle", "front")]
+    for name, method, pc, pos, scaler in runs:
+        kw = {"grad_scale": "dynamic", "scaler": scaler} if scaler else {"grad_scale": 256.0}
+        st = coopfit.CoOpFitState(model, ids, ctx0c if pc else ctx0, momentum=0.9, weight_decay=5e-4, method=method, teacher=None if method == "coop" else tea,
+                                  T=2.0, lam=0.8, class_token_position=pos or "end", name_lens=[0, 1, 2] if pos else None, **kw)
+        t, h, mode = st.tower, model._handle, ops.PROMPT_MODES[method]
+        block = ops.new_scaler_state(scaler["init_scale"], "cuda") if scaler else None
+        cfg = coopfit._check_scaler(name, scaler)
+        sizer = getattr(lib, "clipmi_prompt_train_step" + ("_scaled" if scaler else "") + ("_placed" if pos else "") + "_bytes")
+        ws = torch.empty(sizer(h, t.C, t.rows, 4, mode, t.n_ctx, pc), dtype=torch.uint8).cuda()
+        losses, grad = torch.zeros(2, 3).cuda(), torch.zeros(2, *st.ctx.shape).cuda()
+        projected, dots = torch.zeros(2, dtype=torch.int32).cuda(), torch.zeros(2, 3, dtype=torch.float64).cuda()
+        head = (h, C.byref(t.dgrad[0]), t.base.data_ptr(), coopfit._DT[t.base.dtype], st.ctx.data_ptr(), st.buf.data_ptr(), t.n_ctx, pc,
+                *((t.position, t.name_lens.data_ptr()) if pos else ()), t.eot.data_ptr(), t.C, t.rows, f.data_ptr(), f.stride(0), y.data_ptr(), 4, st.scale)
+        tail = (ws.data_ptr(), ws.numel(), t.stash.data_ptr(), t.stash.numel(), ops._stream())
+        for k in range(2):
+            out = (losses[k].data_ptr(), grad[k].data_ptr())
+            with model._launch_lock:
+                if scaler:
+                    fn = lib.clipmi_prompt_train_step_scaled_placed if pos else lib.clipmi_prompt_train_step_scaled
+                    check(fn(*head, block.data_ptr(), cfg["growth_factor"], cfg["backoff_factor"], cfg["growth_interval"], mode, tea.data_ptr(), 8.0,
+                             lr.data_ptr(), 0.9, 0.0, 5e-4, 0, *out, *tail), name)
+                else:
+                    check(lib.clipmi_prompt_train_step_placed(*head, 256.0, mode, tea.data_ptr(), 8.0, 2.0, 0.8, lr.data_ptr(), int(k == 0), 0.9, 0.0, 5e-4, 0,
+                                                              *out, projected[k:].data_ptr(), dots[k].data_ptr(), *tail), name)
+        if scaler is skip:
+            assert ops.scaler_state_dict(block)["skipped_steps"] == 1 and ops.scaler_state_dict(block)["applied_steps"] == 1, ops.scaler_state_dict(block)
+        yield name, digest(st.ctx, st.buf, losses, grad, *((block,) if scaler else ()), *((projected, dots) if method == "prograd" else ()))
     # TempScaling: 37 rows in batches of 16, two epochs, momentum and weight decay
     g = torch.Generator().manual_seed(6)
     cos = torch.tanh(randn(g, 37, 11))
