@@ -302,6 +302,10 @@ _SIGNATURES = {
     "clipmi_augment_workspace_bytes": (_sz, [_vp, _i, _vp, _i, _i, _i]),
     "clipmi_augment": (_i, [_vp, _i64, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _sz, _vp]),
     "clipmi_probe_mfma_f16": (_i, [_vp, _vp, _vp, _i, _i, C.POINTER(_i), _vp]),
+    "clipmi_val_score_workspace_bytes": (_sz, [_i, _i]),
+    "clipmi_val_score": (_i, [_vp, _i64, _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "clipmi_best_select_workspace_bytes": (_sz, [_i64]),
+    "clipmi_best_select": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i64, _vp, _sz, _vp]),
 }
 
 for _name, (_res, _args) in _SIGNATURES.items():

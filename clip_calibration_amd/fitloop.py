@@ -158,11 +158,13 @@ def _finish(losses: list, return_history: bool, dev) -> Optional[np.ndarray]:
 
 
 def run_cached(step: Callable, features: torch.Tensor, labels_d: torch.Tensor, order_d: Optional[torch.Tensor], batch_size: int, per_epoch: int,
-               epochs: int, lr_steps: torch.Tensor, return_history: bool = False) -> Optional[np.ndarray]:
+               epochs: int, lr_steps: torch.Tensor, return_history: bool = False,
+               end_epoch: Optional[Callable[[int], None]] = None) -> Optional[np.ndarray]:
     """``epochs`` passes over the cached ``features`` [N, E] and ``labels_d`` [N] in ``per_epoch`` batches of ``batch_size``: batch k of
     epoch e is the rows ``order_d[e, k * batch_size : (k + 1) * batch_size]`` (int64 [epochs, N] on the features' device), or that range
-    itself without an order.  Every batch goes to ``step(f, y, lr_steps[s:s + 1], want_loss)``.  Returns the per-step losses as a float32
-    numpy array with ``return_history``.  Nothing synchronises before the one wait at the end (none at all off the GPU or without steps)."""
+    itself without an order.  Every batch goes to ``step(f, y, lr_steps[s:s + 1], want_loss)``.  ``end_epoch(e)``, when given, is called
+    behind the last step of every epoch and must not synchronise.  Returns the per-step losses as a float32 numpy array with
+    ``return_history``.  Nothing synchronises before the one wait at the end (none at all off the GPU or without steps)."""
     if epochs * per_epoch == 0:
         return _no_steps(return_history)
     N = features.shape[0]
@@ -180,6 +182,8 @@ def run_cached(step: Callable, features: torch.Tensor, labels_d: torch.Tensor, o
             if return_history:
                 losses.append(loss)
             s += 1
+        if end_epoch is not None:
+            end_epoch(e)
     return _finish(losses, return_history, features.device)
 
 

@@ -1068,6 +1068,142 @@ def block_step_scaled(grad: torch.Tensor, state: torch.Tensor, params: torch.Ten
     return out
 
 
+# ---- fit monitor (csrc/fit_monitor.hip).  The helpers below are the only place that knows the byte layout of the epoch record and of the
+# best block (include/clipmi.h "Fit monitor").
+
+VAL_CRITERIA = {"accuracy": 0, "nll": 1}    # `criterion` of clipmi_best_select (plain integers there)
+VAL_MAX_BINS = 64
+_BEST_DTYPE = np.dtype([("best_epoch", "<i4"), ("best_correct", "<i4"), ("best_nll_sum", "<f8"), ("epochs_seen", "<i4"), ("pad", "<i4")])
+
+
+def _val_bins(who: str, n_bins) -> int:
+    if isinstance(n_bins, bool) or int(n_bins) != n_bins or not 1 <= int(n_bins) <= VAL_MAX_BINS:
+        raise ValueError(f"{who}: n_bins={n_bins} must be an integer in 1..{VAL_MAX_BINS}")
+    return int(n_bins)
+
+
+def _record_dtype(n_bins: int) -> np.dtype:
+    bins = np.dtype([("count", "<i4"), ("hits", "<i4"), ("conf_sum", "<f8")])
+    return np.dtype([("n", "<i4"), ("correct", "<i4"), ("nll_sum", "<f8"), ("bins", bins, (n_bins + 1,))])
+
+
+def val_record_bytes(n_bins: int) -> int:
+    """The size of one epoch record: 16 + 16 (n_bins + 1) bytes."""
+    return _record_dtype(_val_bins("val_record_bytes", n_bins)).itemsize
+
+
+def new_val_records(slots: int, n_bins: int, device) -> torch.Tensor:
+    """``slots`` zeroed epoch records on ``device``: uint8 [slots, val_record_bytes(n_bins)]; row ``e`` is what ``val_score`` takes as
+    ``record``."""
+    return torch.zeros(int(slots), val_record_bytes(n_bins), dtype=torch.uint8, device=device)
+
+
+def decode_val_records(records, n_bins: int) -> list:
+    """Every record of ``records`` (a uint8 tensor or array [slots, bytes] or [bytes]) as ``dict(n, correct, nll_sum, count, hits,
+    conf_sum)``: Python numbers and three arrays [n_bins + 1], bin ``b`` being ``metrics.digitize_bins``' bin ``b`` (the last holds
+    conf == 1.0).  A tensor on the GPU is read back: it synchronises."""
+    raw = records.detach().cpu().numpy() if isinstance(records, torch.Tensor) else np.asarray(records)
+    rec = np.ascontiguousarray(raw, dtype=np.uint8).reshape(-1, val_record_bytes(n_bins)).view(_record_dtype(n_bins))[:, 0]
+    return [{"n": int(r["n"]), "correct": int(r["correct"]), "nll_sum": float(r["nll_sum"]), "count": r["bins"]["count"].astype(np.int64),
+             "hits": r["bins"]["hits"].astype(np.int64), "conf_sum": r["bins"]["conf_sum"].astype(np.float64)} for r in rec]
+
+
+def encode_val_records(recs, n_bins: int) -> np.ndarray:
+    """The inverse of ``decode_val_records`` on the host: uint8 [len(recs), val_record_bytes(n_bins)] from dicts with ``n``, ``correct``,
+    ``nll_sum`` and, optionally, ``count``, ``hits``, ``conf_sum`` (zero when absent) -- records written by hand, for ``best_select``."""
+    out = np.zeros(len(recs), _record_dtype(_val_bins("encode_val_records", n_bins)))
+    for o, r in zip(out, recs):
+        o["n"], o["correct"], o["nll_sum"] = r.get("n", 0), r["correct"], r["nll_sum"]
+        for k in ("count", "hits", "conf_sum"):
+            if k in r:
+                o["bins"][k] = r[k]
+    return out.view(np.uint8).reshape(len(recs), -1)
+
+
+def val_record_bins(rec: dict) -> np.ndarray:
+    """A decoded record's bins as ``metrics.ece_from_bins`` takes them: float64 [3, n_bins + 1] = (count, sum_conf, sum_correct)."""
+    return np.stack([rec["count"].astype(np.float64), rec["conf_sum"], rec["hits"].astype(np.float64)])
+
+
+def new_best_block(device) -> torch.Tensor:
+    """The best block of ``best_select`` before the first epoch, uint8 [24] on ``device``: {-1, -1, +inf, 0}, one upload."""
+    b = np.zeros(1, _BEST_DTYPE)
+    b["best_epoch"], b["best_correct"], b["best_nll_sum"] = -1, -1, np.inf
+    return torch.from_numpy(b.view(np.uint8).copy()).to(device)
+
+
+def decode_best_block(block) -> dict:
+    """The best block as ``dict(best_epoch, best_correct, best_nll_sum, epochs_seen)``; ``best_epoch`` is -1 while no epoch has been
+    taken.  A tensor on the GPU is read back: it synchronises."""
+    raw = block.detach().cpu().numpy() if isinstance(block, torch.Tensor) else np.asarray(block)
+    b = np.ascontiguousarray(raw, dtype=np.uint8).reshape(-1).view(_BEST_DTYPE)[0]
+    return {"best_epoch": int(b["best_epoch"]), "best_correct": int(b["best_correct"]), "best_nll_sum": float(b["best_nll_sum"]),
+            "epochs_seen": int(b["epochs_seen"])}
+
+
+def _monitor_bytes(who: str, t, name: str, nbytes: int) -> int:
+    _in_place(t, torch.uint8, f"{who}: {name} must be a contiguous uint8 tensor of {nbytes} bytes on the GPU", numel=nbytes)
+    return t.data_ptr()
+
+
+def val_score(logits: torch.Tensor, labels: torch.Tensor, n_bins: int, record: Optional[torch.Tensor] = None,
+              workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """clipmi_val_score: the fp32 ``logits`` [N, C] (the rows may be a column slice) against ``labels`` int64 [N] into one epoch record --
+    n, the correct rows (arg-max with the lowest index on a tie), the sum of the rows' negative log-likelihoods and, per confidence bin of
+    ``metrics.digitize_bins(conf, n_bins)``, the rows, the correct rows and the sum of the confidences.  A label outside [0, C) counts
+    as wrong with a NaN nll and is never used as an address; a row that holds a NaN counts as wrong and its NaN reaches ``nll_sum``.
+    Nothing is read back; the same inputs give the same bytes.  ``record``: uint8 [val_record_bytes(n_bins)] on the GPU (a row of
+    ``new_val_records``), made when None; ``workspace``: a uint8 tensor to reuse.  Returns the record (``decode_val_records``)."""
+    who = "val_score"
+    n_bins = _val_bins(who, n_bins)
+    if not isinstance(logits, torch.Tensor) or logits.dim() != 2 or logits.shape[0] < 1 or logits.shape[1] < 1:
+        raise ValueError(f"{who}: logits {tuple(getattr(logits, 'shape', ()))} must be [N >= 1, C >= 1]")
+    if not logits.is_cuda:
+        raise RuntimeError(f"clipmi: `logits` must be a tensor on the GPU (got {logits.device}); the HIP path has no CPU fallback")
+    if logits.dtype != torch.float32:
+        raise TypeError(f"clipmi: `logits` has dtype {logits.dtype}, expected torch.float32")
+    if logits.stride(1) != 1 or logits.stride(0) < logits.shape[1] or logits.data_ptr() % 16:
+        logits = logits.contiguous()
+    labels = _dev(labels, "labels", (torch.int64,))
+    N, Cn = logits.shape
+    if labels.shape != (N,):
+        raise ValueError(f"{who}: {N} rows need {N} labels, got {tuple(labels.shape)}")
+    if record is None:
+        record = new_val_records(1, n_bins, logits.device)[0]
+    pr = _monitor_bytes(who, record, "record", val_record_bytes(n_bins))
+    need = lib.clipmi_val_score_workspace_bytes(N, n_bins)
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=logits.device)
+    check(lib.clipmi_val_score(logits.data_ptr(), logits.stride(0), labels.data_ptr(), N, Cn, n_bins, pr, workspace.data_ptr(), workspace.numel(),
+                               _stream()), "clipmi_val_score")
+    return record
+
+
+def best_select(record: torch.Tensor, best_block: torch.Tensor, criterion, epoch: int, params: torch.Tensor, best_params: torch.Tensor,
+                workspace: Optional[torch.Tensor] = None) -> None:
+    """clipmi_best_select: when the epoch ``record`` is strictly better than ``best_block``'s (``criterion`` "accuracy": more correct
+    rows; "nll": a finite, smaller ``nll_sum``), the block takes ``epoch`` and the record's figures and ``params`` is copied into
+    ``best_params`` (contiguous fp32 on the GPU, as many elements); otherwise ``best_params`` is not written.  The decision is made and
+    applied on the device: nothing is read back."""
+    who = "best_select"
+    if criterion not in VAL_CRITERIA:
+        raise ValueError(f"{who}: criterion={criterion!r} must be one of {sorted(VAL_CRITERIA)}")
+    if isinstance(epoch, bool) or int(epoch) != epoch or int(epoch) < 0:
+        raise ValueError(f"{who}: epoch={epoch} must be an integer >= 0")
+    _in_place(params, torch.float32, f"{who}: params must be a contiguous fp32 tensor on the GPU")
+    _in_place(best_params, torch.float32, f"{who}: best_params must be a contiguous fp32 tensor on the GPU of params' size", numel=params.numel())
+    if params.numel() < 1:
+        raise ValueError(f"{who}: params is empty")
+    if not (isinstance(record, torch.Tensor) and record.is_cuda and record.dtype == torch.uint8 and record.is_contiguous() and record.numel() >= 32):
+        raise TypeError(f"{who}: record must be a contiguous uint8 tensor on the GPU (val_score)")
+    pb = _monitor_bytes(who, best_block, "best_block", _BEST_DTYPE.itemsize)
+    need = lib.clipmi_best_select_workspace_bytes(params.numel())
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=params.device)
+    check(lib.clipmi_best_select(record.data_ptr(), pb, VAL_CRITERIA[criterion], int(epoch), params.data_ptr(), best_params.data_ptr(), params.numel(),
+                                 workspace.data_ptr(), workspace.numel(), _stream()), "clipmi_best_select")
+
+
 PROMPT_MODES ={"coop": _lib.PROMPT_COOP, "kgcoop": _lib.PROMPT_KGCOOP, "prograd": _lib.PROMPT_PROGRAD}
 
 

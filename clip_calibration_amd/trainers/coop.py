@@ -188,8 +188,21 @@ class CustomCLIP(nn.Module):
         the batch size and the order are the loader's.  ``grad_scale="dynamic"`` with ``scaler=dict(init_scale, growth_factor,
         backoff_factor, growth_interval)`` is the reference's ``amp`` branch on either route (``coopfit``'s module docstring): a step
         that overflows fp16 is skipped on the device and the scale adapts, with no read-back per step.  The prompt learner's
-        ``class_token_position`` and ``name_lens`` go to ``coopfit`` with it."""
+        ``class_token_position`` and ``name_lens`` go to ``coopfit`` with it.
+
+        Validation (the cached route): ``val_loader=`` (an iterable of (image, label) batches, run through the image tower once before the
+        first epoch, as the train features are) or ``val=(val_features, val_labels)``, with ``val_bins``, ``final_model`` ("last_step" or
+        "best_val", the reference's TEST.FINAL_MODEL), ``val_criterion`` and ``return_monitor`` as ``coopfit.fit_context`` takes them.
+        ``final_model="best_val"`` installs the best epoch's context into the prompt learner."""
         import math
+        val_loader = fit_args.pop("val_loader", None)
+        if val_loader is not None and fit_args.get("val") is not None:
+            raise ValueError("fit_context: val_loader and val are two ways to give one validation set")
+        monitored = val_loader is not None or any(k in fit_args for k in ("val", "val_bins", "final_model", "val_criterion", "return_monitor"))
+        if transform is not None and monitored:
+            raise ValueError("fit_context: validation and final_model belong to the cached route (transform=None)")
+        if val_loader is not None:
+            fit_args["val"] = _fit.cached_features("fit_context", self.clip_model, val_loader)
         fit_args.setdefault("logit_scale", math.log(self.scale))
         ctx = self.prompt_learner.ctx
         ids = self.prompt_learner.tokenized_prompts

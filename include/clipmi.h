@@ -1490,6 +1490,43 @@ int clipmi_augment(const void* pixels, int64_t pixels_bytes, const clipmi_image_
 int clipmi_probe_mfma_f16(const void* operands, float* sink, unsigned long long* clocks, int waves, int iters, int* n_cus_out,
                           clipmi_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------
+ * Fit monitor: per-epoch validation and best-epoch selection on the device (reference base_learner.py:41-47, Dassl's after_epoch;
+ * csrc/fit_monitor.hip, DESIGN.md "Fit monitor").  Nothing is read back to the host.  Additive exports: the ABI version stays.
+ *
+ * The epoch record, 8-byte aligned, 16 + 16 (n_bins + 1) bytes, written by clipmi_val_score alone:
+ *   {int32 n, int32 correct, float64 nll_sum, bins[n_bins + 1] x {int32 count, int32 hits, float64 conf_sum}}
+ * bin b holds the rows whose confidence falls into bin b of numpy.digitize(conf, numpy.linspace(0, 1, n_bins + 1)) - 1, so the last
+ * one, bin n_bins, holds conf == 1.0 (and a NaN confidence, which sorts behind every edge).
+ *
+ * clipmi_val_score: logits fp32 [N, C] with the row stride ld (elements), labels int64 [N].  Per row, in fp32: the maximum and its
+ * LOWEST index, sum = sum_c exp(z_c - max), nll = log(sum) - (z[label] - max), conf = 1 / sum (lse - z[label] and exp(max - lse) with the
+ * maximum cancelled before the rounding).  A label outside [0, C) is never used as an address: the row counts as wrong and its nll is NaN.  A row that
+ * holds a NaN counts as wrong, its nll and its confidence are NaN.  Launch 1: one wave per row, 64 rows per workgroup -- the partition
+ * depends on N alone --, whose results are added in ascending row order (int32 counts, float64 sums) into one partial record per workgroup;
+ * launch 2: one workgroup adds the partial records in ascending workgroup order into `record`.  No atomics: the same inputs give the same
+ * bits.  workspace (256-byte aligned): clipmi_val_score_workspace_bytes(N, n_bins) bytes, 0 for arguments the call refuses.  Every check
+ * precedes the first launch.  CLIPMI_ERR_ARG: a null pointer, logits not 16-byte aligned, labels or the record not 8-byte aligned, n_bins
+ * outside 1..64; CLIPMI_ERR_SHAPE: N < 1, C < 1, ld < C; CLIPMI_ERR_WORKSPACE.
+ *
+ * The best block, 8-byte aligned, 24 bytes: {int32 best_epoch, int32 best_correct, float64 best_nll_sum, int32 epochs_seen, int32 pad}.
+ * The caller writes {-1, -1, +inf, 0, 0} before the first call; only clipmi_best_select writes it afterwards.
+ *
+ * clipmi_best_select: criterion 0 (accuracy): better iff record.correct > best_correct, so the first epoch is taken unconditionally;
+ * criterion 1 (nll): better iff record.nll_sum is finite and < best_nll_sum, so a non-finite epoch is never taken.  Strictly better only
+ * (Dassl's `>`): on a tie the earlier epoch stays.  Launch 1 (one workgroup) decides, on "better" writes epoch, correct and nll_sum into
+ * the block, counts epochs_seen and writes the decision word into the workspace; launch 2 copies params to best_params (n_floats fp32,
+ * both 16-byte aligned, exactly n_floats floats are written) and returns at once when the word says "not better".  workspace (256-byte
+ * aligned): clipmi_best_select_workspace_bytes(n_floats), 0 for n_floats < 1.  CLIPMI_ERR_ARG: a null pointer, an alignment, a criterion
+ * other than 0 or 1, epoch < 0; CLIPMI_ERR_SHAPE: n_floats < 1; CLIPMI_ERR_WORKSPACE.
+ * ---------------------------------------------------------------------------------------------------- */
+size_t clipmi_val_score_workspace_bytes(int N, int n_bins);
+int clipmi_val_score(const float* logits, int64_t ld, const int64_t* labels, int N, int C, int n_bins, void* record, void* workspace,
+                     size_t workspace_bytes, clipmi_stream_t stream);
+size_t clipmi_best_select_workspace_bytes(int64_t n_floats);
+int clipmi_best_select(const void* record, void* best_block, int criterion, int epoch, const float* params, float* best_params, int64_t n_floats,
+                       void* workspace, size_t workspace_bytes, clipmi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
