@@ -306,6 +306,15 @@ _SIGNATURES = {
     "clipmi_val_score": (_i, [_vp, _i64, _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "clipmi_best_select_workspace_bytes": (_sz, [_i64]),
     "clipmi_best_select": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i64, _vp, _sz, _vp]),
+    "clipmi_adapter_val_logits": (_i, [_vp, _i64, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _vp, _vp]),
+    "clipmi_taskres_val_logits": (_i, [_vp, _i64, _vp, _vp, _i, _i, _i, _f, _f, _vp, _vp]),
+    "clipmi_adapter_fit_monitored_workspace_bytes": (_sz, [_i, _i, _i]),
+    "clipmi_adapter_fit_monitored": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _f, _vp, _i, _f, _f, _f, _i,
+                                          _vp, _vp, _sz, _vp, _i64, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
+    "clipmi_taskres_fit_monitored_workspace_bytes": (_sz, [_i, _i, _i]),
+    "clipmi_taskres_fit_monitored": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _f, _vp, _i, _i64, _f, _f, _f, _i,
+                                          C.c_double, C.c_double, C.c_double, _vp, _vp, _sz, _vp, _i64, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _sz,
+                                          _vp]),
 }
 
 for _name, (_res, _args) in _SIGNATURES.items():

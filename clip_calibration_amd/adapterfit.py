@@ -26,7 +26,7 @@ from typing import Optional, Sequence
 import numpy as np
 import torch
 
-from . import fitloop, ops
+from . import fitloop, fitmonitor, ops
 from .fitloop import _need_gpu, steps_per_epoch
 
 
@@ -45,7 +45,8 @@ def _check_shapes(who: str, features, text_features, w1, w2):
 def fit_adapter(features: torch.Tensor, labels, text_features: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor, ratio: float = 0.2,
                 logit_scale: float = 4.6052, epochs: int = 200, lr: float = 0.002, batch_size: int = 32, momentum: float = 0.9,
                 dampening: float = 0.0, weight_decay: float = 5e-4, nesterov: bool = False, lr_per_epoch: Optional[Sequence[float]] = None,
-                order=None, drop_last: bool = True, return_history: bool = False):
+                order=None, drop_last: bool = True, return_history: bool = False, val=None, val_bins: int = 10,
+                final_model: str = "last_step", val_criterion: str = "accuracy", return_monitor: bool = False):
     """Train CLIP-Adapter's bottleneck on cached ``features`` fp32 [N, E] (raw, un-normalised image features on the GPU; the rows may be a
     column slice of a wider matrix), ``labels`` [N] and the frozen L2-normalised ``text_features`` fp32 [C, E], starting from ``w1``
     [H, E] and ``w2`` [E, H] (not modified): ``epochs`` passes of ``torch.optim.SGD(lr, momentum, dampening, weight_decay, nesterov)`` on
@@ -59,8 +60,19 @@ def fit_adapter(features: torch.Tensor, labels, text_features: torch.Tensor, w1:
     Labels (and ``order``) are checked against their ranges on the host before anything is launched -- a label tensor on the GPU is
     copied to the host for that, which waits for whatever produced it; from the first launch on nothing synchronises until the one wait
     at the end.  Returns the fitted fp32 ``(w1, w2)`` on the device, or ``(w1, w2, per-step batch losses as a float32 numpy array)`` with
-    ``return_history``.  The defaults are unverified restatements of the reference's config and Dassl's (module docstring)."""
+    ``return_history``.  The defaults are unverified restatements of the reference's config and Dassl's (module docstring).
+
+    ``val=(val_features, val_labels)`` (raw image features [N_val, E] on the GPU and their labels): behind the last step of every epoch
+    the run scores the weights against them on the device, into ``val_bins`` confidence bins (clipmi_adapter_fit_monitored: the training
+    forward on the validation rows, ``clipmi_val_score``, ``clipmi_best_select``) -- the fitted weights are bit for bit those of the same
+    call without ``val``, and the run is still one library call and one wait.  ``final_model``: "last_step" returns the last epoch's
+    weights; "best_val" (the reference's TEST.FINAL_MODEL, base_learner.py:41-47) those of the epoch that was strictly better than every
+    earlier one under ``val_criterion`` -- "accuracy" (Dassl's rule) or "nll", where an epoch with a non-finite nll is never taken; the
+    starting weights when no epoch was taken.  "best_val" without ``val`` is refused.  ``return_monitor`` adds a dict behind everything
+    else, read once after the run's one wait: per-epoch ``accuracy``, ``nll`` and ``ece``, the raw ``bins``, ``records`` and
+    ``best_epoch`` (``AdapterFitState.monitor``); empty without ``val`` or without steps."""
     who = "fit_adapter"
+    fitmonitor.check_args(who, val, val_bins, final_model, val_criterion)
     N, E, H, C = _check_shapes(who, features, text_features, w1, w2)
     epochs, batch_size = fitloop.check_run(who, epochs, batch_size)
     fitloop.check_sgd(who, momentum, dampening, weight_decay, nesterov)
@@ -71,16 +83,32 @@ def fit_adapter(features: torch.Tensor, labels, text_features: torch.Tensor, w1:
     per_epoch = steps_per_epoch(N, batch_size, drop_last)
     dev = features.device
     _, lr_steps = fitloop.schedule(who, lr, epochs, lr_per_epoch, per_epoch, dev)
+    if val is not None:
+        vf, vl = fitmonitor.check_val(who, val, E, C)
     _need_gpu(features, "features")
-    w1, w2 = fitloop.master(w1, dev), fitloop.master(w2, dev)
+    if val is not None:
+        block, w1, w2 = ops.adapter_master_block(w1, w2, dev)      # one block [w1 | w2]: what the selection copies
+    else:
+        w1, w2 = fitloop.master(w1, dev), fitloop.master(w2, dev)
     if epochs * per_epoch == 0:
-        return (w1, w2, np.zeros(0, np.float32)) if return_history else (w1, w2)
+        return fitmonitor.pack((w1, w2), np.zeros(0, np.float32), fitmonitor.empty_monitor(val_bins), return_history, return_monitor)
     m1, m2 = (torch.zeros_like(w1), torch.zeros_like(w2)) if momentum != 0.0 else (None, None)
+    mon = monitor = None
+    if val is not None:
+        _need_gpu(vf, "val_features")
+        mon = fitmonitor.Monitor(who, epochs, val_bins, val_criterion, block if final_model == "best_val" else None, dev)
+        mon.seen = epochs
+        monitor = ops.fit_monitor(vf if vf.dtype == torch.float32 else vf.float(), vl.to(dev), mon.bins, mon.records, val_criterion, mon.block,
+                                  mon.best)
     losses = ops.adapter_fit(features, fitloop.labels_on(labels, lab, dev), text_features, w1, w2, m1, m2, lr_steps, ratio,
                              float(np.float32(math.exp(logit_scale))), batch_size, epochs, momentum, dampening, weight_decay, nesterov,
-                             fitloop.order_on(order, np.int32, dev), drop_last, first_step=True, want_losses=return_history)
+                             fitloop.order_on(order, np.int32, dev), drop_last, first_step=True, want_losses=return_history, monitor=monitor)
     torch.cuda.current_stream().synchronize()   # the run's one synchronisation
-    return (w1, w2, losses.cpu().numpy()) if return_history else (w1, w2)
+    if final_model == "best_val":
+        w1, w2 = mon.best[:w1.numel()].view(w1.shape), mon.best[w1.numel():].view(w2.shape)
+    return fitmonitor.pack((w1, w2), losses.cpu().numpy() if return_history else None,
+                           (mon.summary() if mon is not None else fitmonitor.empty_monitor(val_bins)) if return_monitor else None,
+                           return_history, return_monitor)
 
 
 class AdapterFitState:
@@ -96,12 +124,66 @@ class AdapterFitState:
         _need_gpu(text_features, "text_features")
         dev = text_features.device
         self.text_features = text_features
-        self.w1, self.w2 = fitloop.master(w1, dev), fitloop.master(w2, dev)
+        if not isinstance(w1, torch.Tensor) or not isinstance(w2, torch.Tensor):
+            raise ValueError("AdapterFitState: w1 and w2 must be tensors")
+        self._block, self.w1, self.w2 = ops.adapter_master_block(w1, w2, dev)     # one block [w1 | w2]: what the monitor's selection copies
         _check_shapes("AdapterFitState", text_features[:1], text_features, self.w1, self.w2)
         self.m1, self.m2 = (torch.zeros_like(self.w1), torch.zeros_like(self.w2)) if momentum != 0.0 else (None, None)
         self.ratio, self.scale = float(ratio), float(np.float32(math.exp(logit_scale)))
         self.momentum, self.dampening, self.weight_decay, self.nesterov = momentum, dampening, weight_decay, nesterov
         self.steps = 0
+        self._mon = None    # the fit monitor's device history, made by start_monitor or the first validate
+
+    # ---- per-epoch validation and best-epoch selection on the device (DESIGN.md "Fit monitor"), as CoOpFitState has them
+
+    def start_monitor(self, slots: int, val_bins: int = 10, select: bool = False, val_criterion: str = "accuracy") -> None:
+        """The device history ``validate`` writes: ``slots`` epoch records of ``val_bins`` confidence bins and, with ``select``, the best
+        block and the best slot (a copy of [w1 | w2] as they are now, replaced whenever an epoch is strictly better under
+        ``val_criterion``).  Allocations and one small upload; nothing synchronises."""
+        self._mon = fitmonitor.Monitor("AdapterFitState.start_monitor", slots, val_bins, val_criterion, self._block if select else None,
+                                       self._block.device)
+
+    def validate(self, val_features: torch.Tensor, val_labels, epoch: int) -> None:
+        """Enqueue one validation of the current master weights into slot ``epoch`` of the device history; no host read.
+        ``clipmi_adapter_val_logits`` runs the training step's forward on ``val_features`` (raw image features [N_val, E] on the GPU)
+        into fp32 [N_val, C] logits the state owns (4 N_val C bytes, kept for the next epoch); ``clipmi_val_score`` scores them into the
+        record and, when the monitor selects, ``clipmi_best_select`` compares the record with the best block and copies [w1 | w2] into
+        the best slot.  ``val_labels`` [N_val]: an int64 tensor on the GPU is taken as it is (a label outside [0, C) then counts as wrong
+        with a NaN nll), anything else is range-checked on the host, once per set.  Without ``start_monitor`` the history starts with
+        ``epoch + 1`` slots of 10 bins and no selection; it grows when ``epoch`` lies behind its end."""
+        who = "AdapterFitState.validate"
+        if self._mon is None:
+            self.start_monitor(int(epoch) + 1 if isinstance(epoch, int) and epoch >= 0 else 1)
+        mon = self._mon
+        epoch = mon.slot(who, epoch)
+        feats, labels_d = mon.operands(who, val_features, val_labels, self.w1.shape[1], self.text_features.shape[0])
+        ops.adapter_val_logits(feats, self.text_features, self.w1, self.w2, self.ratio, self.scale, out=mon.logits)
+        mon.score(epoch, labels_d, self._block)
+
+    def val_logits(self) -> torch.Tensor:
+        """The fp32 [N_val, C] logits of the last ``validate``, where the state keeps them (the next ``validate`` overwrites them)."""
+        if self._mon is None or self._mon.logits is None:
+            raise ValueError("AdapterFitState.val_logits: nothing has been validated")
+        return self._mon.logits
+
+    def best_weights(self):
+        """``(w1, w2)`` of the best slot on the device: the weights of the best epoch so far, or those ``start_monitor`` saw while no
+        epoch has been taken.  No read-back."""
+        if self._mon is None or self._mon.best is None:
+            raise ValueError("AdapterFitState.best_weights: the monitor does not select (start_monitor(..., select=True))")
+        k = self.w1.numel()
+        return self._mon.best[:k].view(self.w1.shape), self._mon.best[k:].view(self.w2.shape)
+
+    def monitor_records(self) -> torch.Tensor:
+        """The device history, uint8 [slots, ops.val_record_bytes(val_bins)]; no read-back."""
+        if self._mon is None:
+            raise ValueError("AdapterFitState.monitor_records: nothing has been validated")
+        return self._mon.records
+
+    def monitor(self) -> dict:
+        """The history as numbers (``fitmonitor.monitor_dict``, the dict ``CoOpFitState.monitor`` returns).  It reads the history back:
+        one synchronisation."""
+        return fitmonitor.empty_monitor() if self._mon is None else self._mon.summary()
 
     def step(self, features: torch.Tensor, labels, lr, want_loss: bool = False) -> Optional[torch.Tensor]:
         """One SGD step on the batch ``features`` fp32 [B, E] (raw image features on the GPU) and ``labels`` [B] at the rate ``lr``: an fp32

@@ -67,7 +67,7 @@ from typing import Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import _lib, fitloop, ops
+from . import _lib, fitloop, fitmonitor, ops
 from ._lib import check, lib
 from .fitloop import _host_int_array, _need_gpu, steps_per_epoch
 
@@ -580,16 +580,10 @@ class CoOpFitState:
         (``metrics.ece_from_bins`` of the record's bins), the raw ``bins`` (float64 [epochs, 3, val_bins + 1]: count, sum of confidences,
         correct), the decoded ``records`` and ``best_epoch`` (None without selection, -1 when no epoch was taken).  It reads the history
         back: one synchronisation."""
-        from . import metrics
         mon = self._mon
         if mon is None:
             return empty_monitor()
-        recs = ops.decode_val_records(mon["records"][:mon["seen"]], mon["bins"])
-        bins = np.stack([ops.val_record_bins(r) for r in recs]) if recs else np.zeros((0, 3, mon["bins"] + 1))
-        n = np.array([max(r["n"], 1) for r in recs], np.float64)
-        return {"accuracy": np.array([r["correct"] for r in recs], np.float64) / n, "nll": np.array([r["nll_sum"] for r in recs], np.float64) / n,
-                "ece": np.array([metrics.ece_from_bins(b, mon["bins"]) for b in bins], np.float64), "bins": bins, "records": recs,
-                "best_epoch": None if mon["block"] is None else ops.decode_best_block(mon["block"])["best_epoch"]}
+        return fitmonitor.monitor_dict(mon["records"][:mon["seen"]], mon["bins"], mon["block"])
 
     def _one_call(self, features, labels_d, lr_d, losses, first: bool) -> None:
         """``step`` through the library's one-call step: one of four symbols (static or scaled, the class token at the end or placed) on
@@ -660,13 +654,7 @@ class CoOpFitState:
         return losses[0:1] if want_loss else None
 
 
-FINAL_MODELS = ("last_step", "best_val")
-
-
-def empty_monitor(val_bins: int = 10) -> dict:
-    """What ``CoOpFitState.monitor`` returns when nothing has been validated."""
-    z = np.zeros(0, np.float64)
-    return {"accuracy": z, "nll": z.copy(), "ece": z.copy(), "bins": np.zeros((0, 3, int(val_bins) + 1)), "records": [], "best_epoch": None}
+FINAL_MODELS, empty_monitor = fitmonitor.FINAL_MODELS, fitmonitor.empty_monitor    # shared with the other monitored fits
 
 
 def init_context(clip_model, n_ctx: int = 16, n_cls: Optional[int] = None, seed: int = 0) -> torch.Tensor:

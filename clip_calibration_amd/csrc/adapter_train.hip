@@ -20,6 +20,7 @@
 #include <cmath>
 
 #include "common.h"
+#include "fit_monitor.h"
 #include "train_rules.h"   // SgdArgs, check_sgd, sgd_element, waves_max, xent_row, mean_loss_256
 
 namespace clipmi {
@@ -87,42 +88,41 @@ __device__ __forceinline__ void columns_sum(const float* __restrict__ mat, int64
   __syncthreads();
 }
 
-__global__ __launch_bounds__(ROWS_THREADS) void adapter_rows_kernel(const float* __restrict__ feats, int64_t ld, const int64_t* __restrict__ labels,
-                                                                    const int32_t* __restrict__ order, int first, int rows, int N,
-                                                                    const float* __restrict__ text, const float* __restrict__ w1,
-                                                                    const float* __restrict__ w2, int E, int H, int C, float ratio, float scale,
-                                                                    Workspace ws) {
+// The LDS of one sample, carved the same way by every kernel that runs the forward
+struct RowLds {
+  float *sf, *su, *sa, *sd, *sh, *sdh, *sparts, *swave;
+};
+__device__ __forceinline__ RowLds carve_lds(float* lds, int E, int H) {
+  RowLds s;
+  s.sf = lds;               // f, the raw features of the sample
+  s.su = s.sf + E;          // g, then u
+  s.sa = s.su + E;          // a = relu(p2): the second mask
+  s.sd = s.sa + E;          // du, then da
+  s.sh = s.sd + E;          // h = relu(p1): the first mask
+  s.sdh = s.sh + H;         // da W2, before the first mask
+  s.sparts = s.sdh + H;     // columns_sum's partial sums
+  s.swave = s.sparts + ROWS_THREADS;   // one value per wave, twice: the maximum's and the sum's
+  return s;
+}
+
+// The forward of one sample by its workgroup, the one body of the training step and of the validation logits: f -> h -> a -> g -> u in LDS
+// and z_c = s (u . T_c) to z[0 .. C).  out_h (null: not kept) receives h.  Returns n = |g|, the same bits in every thread, and leaves in `m`
+// the maximum over the classes of the thread's own wave; the stores to z are not yet ordered before other waves' loads.
+__device__ __forceinline__ float adapter_forward_row(const float* __restrict__ f, const float* __restrict__ text, const float* __restrict__ w1,
+                                                     const float* __restrict__ w2, int E, int H, int C, float ratio, float scale, const RowLds& s,
+                                                     float* __restrict__ out_h, float* __restrict__ z, float& m) {
 #pragma clang fp contract(off)   // z = s * (u . T_c) is rounded before the maximum is subtracted: the largest term is exp(0) exactly
-  extern __shared__ float lds[];
-  float* sf = lds;            // f, the raw features of the sample
-  float* su = sf + E;         // g, then u
-  float* sa = su + E;         // a = relu(p2): the second mask
-  float* sd = sa + E;         // du, then da
-  float* sh = sd + E;         // h = relu(p1): the first mask
-  float* sdh = sh + H;        // da W2, before the first mask
-  float* sparts = sdh + H;    // columns_sum's partial sums
-  float* swave = sparts + ROWS_THREADS;   // one value per wave, twice: the maximum's and the sum's
+  float *sf = s.sf, *su = s.su, *sa = s.sa, *sh = s.sh;
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int r = blockIdx.x;
-  float* out_h = ws.h + (size_t)r * H;
-  float* out_da = ws.da + (size_t)r * E;
-  float* out_dh = ws.dh + (size_t)r * H;
-  float* z = ws.z + (size_t)r * C;
-  const int i = order ? order[r] : first + r;
-  const int64_t y = i >= 0 && i < N ? labels[i] : -1;
-  if (y < 0 || y >= C) {      // the same for every thread of the workgroup: nobody waits at a barrier below
-    for (int e = t; e < E; e += ROWS_THREADS) out_da[e] = NAN;
-    for (int k = t; k < H; k += ROWS_THREADS) out_h[k] = out_dh[k] = NAN;
-    if (t == 0) ws.loss[r] = NAN;
-    return;
-  }
-  const float* __restrict__ f = feats + (int64_t)i * ld;
   for (int e = t; e < E; e += ROWS_THREADS) sf[e] = f[e];
   __syncthreads();
   // h = relu(f W1^T): one wave per hidden unit
   for (int k = wave; k < H; k += ROWS_WAVES) {
     const float p1 = wave_dot(w1 + (int64_t)k * E, sf, E, lane);
-    if (lane == 0) sh[k] = out_h[k] = fmaxf(p1, 0.f);
+    if (lane == 0) {
+      sh[k] = fmaxf(p1, 0.f);
+      if (out_h) out_h[k] = sh[k];
+    }
   }
   __syncthreads();
   // a = relu(h W2^T), g = r a + (1 - r) f: one wave per feature
@@ -143,12 +143,40 @@ __global__ __launch_bounds__(ROWS_THREADS) void adapter_rows_kernel(const float*
   for (int e = t; e < E; e += ROWS_THREADS) su[e] = su[e] / n;
   __syncthreads();
   // z_c = s (u . T_c): one wave per class; the row maximum on the way
-  float m = -INFINITY;
+  m = -INFINITY;
   for (int c = wave; c < C; c += ROWS_WAVES) {
     const float zc = scale * wave_dot(text + (int64_t)c * E, su, E, lane);
     if (lane == 0) z[c] = zc;
     m = fmaxf(m, zc);
   }
+  return n;
+}
+
+__global__ __launch_bounds__(ROWS_THREADS) void adapter_rows_kernel(const float* __restrict__ feats, int64_t ld, const int64_t* __restrict__ labels,
+                                                                    const int32_t* __restrict__ order, int first, int rows, int N,
+                                                                    const float* __restrict__ text, const float* __restrict__ w1,
+                                                                    const float* __restrict__ w2, int E, int H, int C, float ratio, float scale,
+                                                                    Workspace ws) {
+#pragma clang fp contract(off)
+  extern __shared__ float lds[];
+  const RowLds s = carve_lds(lds, E, H);
+  float *su = s.su, *sa = s.sa, *sd = s.sd, *sh = s.sh, *sdh = s.sdh, *sparts = s.sparts, *swave = s.swave;
+  const int t = threadIdx.x, lane = t & 63;
+  const int r = blockIdx.x;
+  float* out_h = ws.h + (size_t)r * H;
+  float* out_da = ws.da + (size_t)r * E;
+  float* out_dh = ws.dh + (size_t)r * H;
+  float* z = ws.z + (size_t)r * C;
+  const int i = order ? order[r] : first + r;
+  const int64_t y = i >= 0 && i < N ? labels[i] : -1;
+  if (y < 0 || y >= C) {      // the same for every thread of the workgroup: nobody waits at a barrier below
+    for (int e = t; e < E; e += ROWS_THREADS) out_da[e] = NAN;
+    for (int k = t; k < H; k += ROWS_THREADS) out_h[k] = out_dh[k] = NAN;
+    if (t == 0) ws.loss[r] = NAN;
+    return;
+  }
+  float m;
+  const float n = adapter_forward_row(feats + (int64_t)i * ld, text, w1, w2, E, H, C, ratio, scale, s, out_h, z, m);
   m = waves_max<ROWS_WAVES>(m, swave);   // its barrier also orders the stores to z before the loads below (workgroup scope)
   // dz_c = (softmax_c - [c == y]) / B, in place of z
   xent_row<ROWS_WAVES>(z, z, C, m, y, 1.f / (float)rows, swave + ROWS_WAVES, ws.loss + r);
@@ -173,6 +201,18 @@ __global__ __launch_bounds__(ROWS_THREADS) void adapter_rows_kernel(const float*
   // dh = (da W2) [p1 > 0]: the hidden units across the threads, the features in consecutive parts
   columns_sum(w2, H, sd, E, H, sparts, sdh);
   for (int k = t; k < H; k += ROWS_THREADS) out_dh[k] = sh[k] > 0.f ? sdh[k] : 0.f;
+}
+
+// grid (N_val): the validation logits of row r, the training forward on the weights as they are (DESIGN.md "Fit monitor"): every element
+// of out [N_val, C] is written by lane 0 of one wave of one workgroup; a non-finite feature makes g, n and with them the whole row non-finite
+__global__ __launch_bounds__(ROWS_THREADS) void adapter_val_logits_kernel(const float* __restrict__ feats, int64_t ld, const float* __restrict__ text,
+                                                                          const float* __restrict__ w1, const float* __restrict__ w2, int E, int H,
+                                                                          int C, float ratio, float scale, float* __restrict__ out) {
+  extern __shared__ float lds[];
+  const RowLds s = carve_lds(lds, E, H);
+  const int64_t r = blockIdx.x;
+  float m;
+  adapter_forward_row(feats + r * ld, text, w1, w2, E, H, C, ratio, scale, s, nullptr, out + r * C, m);
 }
 
 // Elements [0, E H) are W2 [E, H], elements [E H, 2 E H) are W1 [H, E].  The weights a step's rows kernel read are final before this launch
@@ -251,6 +291,69 @@ int launch_step(const Problem& p, const int32_t* order, int first, int rows, con
   return check_launch("adapter_update_kernel");
 }
 
+// the validation logits: what clipmi_adapter_val_logits refuses, in the vocabulary of check_problem
+int check_val(const char* who, const float* feats, int64_t ld, const float* text, const float* w1, const float* w2, int n_val, int E, int H, int C,
+              float ratio, float scale, const float* logits) {
+  CLIPMI_REQUIRE(feats && text && w1 && w2 && logits, CLIPMI_ERR_ARG, "%s: null pointer (feats, text, w1, w2 and the logits are required)", who);
+  CLIPMI_REQUIRE(aligned(feats, 4) && aligned(text, 4) && aligned(w1, 4) && aligned(w2, 4), CLIPMI_ERR_ARG, "%s: fp32 arrays must be 4-byte aligned",
+                 who);
+  CLIPMI_REQUIRE(aligned(logits, 16), CLIPMI_ERR_ARG, "%s: the logits must be 16-byte aligned (clipmi_val_score reads them)", who);
+  CLIPMI_REQUIRE(std::isfinite(ratio) && std::isfinite(scale), CLIPMI_ERR_ARG, "%s: ratio=%g, scale=%g (both finite)", who, ratio, scale);
+  CLIPMI_REQUIRE(n_val >= 1, CLIPMI_ERR_SHAPE, "%s: N_val=%d (>= 1)", who, n_val);
+  CLIPMI_REQUIRE(C >= 2, CLIPMI_ERR_SHAPE, "%s: C=%d (>= 2 classes)", who, C);
+  CLIPMI_REQUIRE(E >= 1 && H >= 1, CLIPMI_ERR_SHAPE, "%s: E=%d H=%d (both >= 1)", who, E, H);
+  CLIPMI_REQUIRE(rows_lds_bytes(E, H) <= ROWS_LDS_MAX, CLIPMI_ERR_SHAPE, "%s: E=%d H=%d need %zu bytes of LDS per sample, %zu at most", who, E, H,
+                 rows_lds_bytes(E, H), ROWS_LDS_MAX);
+  CLIPMI_REQUIRE(ld >= E, CLIPMI_ERR_SHAPE, "%s: ld=%lld < E=%d", who, (long long)ld, E);
+  return CLIPMI_OK;
+}
+
+int launch_val(const float* feats, int64_t ld, const float* text, const float* w1, const float* w2, int n_val, int E, int H, int C, float ratio,
+               float scale, float* logits, hipStream_t s) {
+  hipLaunchKernelGGL(adapter_val_logits_kernel, dim3((unsigned)n_val), dim3(ROWS_THREADS), rows_lds_bytes(E, H), s, feats, ld, text, w1, w2, E, H, C,
+                     ratio, scale, logits);
+  return check_launch("adapter_val_logits_kernel");
+}
+
+// The one body of clipmi_adapter_fit and clipmi_adapter_fit_monitored.  Without a monitor the steps are enqueued and nothing else; with one,
+// behind the last step of every epoch: the validation logits of the weights as they are, the epoch record and, with a best slot, the selection
+// of the block [w1 | w2] -- which is why the monitored run wants w2 == w1 + H E.
+int run_fit(const char* who, const Problem& p, const int32_t* order, int batch, int epochs, int drop_last, const float* lr, int first_step,
+            float momentum, float dampening, float weight_decay, int nesterov, float* losses, void* workspace, size_t workspace_bytes,
+            const FitMonitor* mon, hipStream_t stream) {
+  if (int rc = check_problem(who, p, lr, momentum, dampening, weight_decay, nesterov)) return rc;
+  CLIPMI_REQUIRE(batch >= 1, CLIPMI_ERR_SHAPE, "%s: batch=%d (>= 1)", who, batch);
+  CLIPMI_REQUIRE(epochs >= 0, CLIPMI_ERR_ARG, "%s: epochs=%d (>= 0)", who, epochs);
+  const int width = batch < p.n ? batch : p.n;   // the widest batch of the run
+  if (int rc = check_workspace(who, workspace, workspace_bytes, width, p)) return rc;
+  const int64_t EH = (int64_t)p.E * p.H;
+  if (mon) {
+    if (int rc = check_fit_monitor(who, *mon, p.E, p.C)) return rc;
+    CLIPMI_REQUIRE(!mon->best_block || (p.w2 == p.w1 + EH && aligned(p.w1, 16)), CLIPMI_ERR_ARG,
+                   "%s: a best slot needs w1 and w2 as one 16-byte aligned block [w1 | w2] (w2 == w1 + H E)", who);
+  }
+  const int per_epoch = drop_last ? p.n / batch : (int)(((int64_t)p.n + batch - 1) / batch);
+  SgdArgs a = make_sgd_args(momentum, dampening, weight_decay, nesterov, first_step);
+  int64_t step = 0;
+  for (int e = 0; e < epochs; ++e) {
+    const int32_t* epoch_order = order ? order + (int64_t)e * p.n : nullptr;
+    for (int k = 0; k < per_epoch; ++k, ++step) {
+      const int first = k * batch;   // k < per_epoch <= n: no overflow
+      const int rows = p.n - first < batch ? p.n - first : batch;
+      if (int rc = launch_step(p, epoch_order ? epoch_order + first : nullptr, first, rows, lr + step, a, losses ? losses + step : nullptr,
+                               workspace, stream))
+        return rc;
+      a.first_step = 0;
+    }
+    if (!mon) continue;
+    if (int rc = launch_val(mon->val_feats, mon->val_ld, p.text, p.w1, p.w2, mon->n_val, p.E, p.H, p.C, p.ratio, p.scale, fit_monitor_logits(*mon),
+                            stream))
+      return rc;
+    if (int rc = fit_monitor_score(*mon, e, p.C, p.w1, 2 * EH, (clipmi_stream_t)stream)) return rc;
+  }
+  return CLIPMI_OK;
+}
+
 }  // namespace
 }  // namespace clipmi
 
@@ -279,26 +382,29 @@ int clipmi_adapter_fit(const float* feats, int64_t ld, const int64_t* labels, co
                        const float* lr, int first_step, float momentum, float dampening, float weight_decay, int nesterov, float* losses,
                        void* workspace, size_t workspace_bytes, clipmi_stream_t stream) {
   const Problem p{feats, ld, labels, text, w1, w2, m1, m2, n, E, H, C, ratio, scale};
-  if (int rc = check_problem("adapter_fit", p, lr, momentum, dampening, weight_decay, nesterov)) return rc;
-  CLIPMI_REQUIRE(batch >= 1, CLIPMI_ERR_SHAPE, "adapter_fit: batch=%d (>= 1)", batch);
-  CLIPMI_REQUIRE(epochs >= 0, CLIPMI_ERR_ARG, "adapter_fit: epochs=%d (>= 0)", epochs);
-  const int width = batch < n ? batch : n;   // the widest batch of the run
-  if (int rc = check_workspace("adapter_fit", workspace, workspace_bytes, width, p)) return rc;
-  const int per_epoch = drop_last ? n / batch : (int)(((int64_t)n + batch - 1) / batch);
-  SgdArgs a = make_sgd_args(momentum, dampening, weight_decay, nesterov, first_step);
-  int64_t step = 0;
-  for (int e = 0; e < epochs; ++e) {
-    const int32_t* epoch_order = order ? order + (int64_t)e * n : nullptr;
-    for (int k = 0; k < per_epoch; ++k, ++step) {
-      const int first = k * batch;   // k < per_epoch <= n: no overflow
-      const int rows = n - first < batch ? n - first : batch;
-      if (int rc = launch_step(p, epoch_order ? epoch_order + first : nullptr, first, rows, lr + step, a, losses ? losses + step : nullptr,
-                               workspace, (hipStream_t)stream))
-        return rc;
-      a.first_step = 0;
-    }
-  }
-  return CLIPMI_OK;
+  return run_fit("adapter_fit", p, order, batch, epochs, drop_last, lr, first_step, momentum, dampening, weight_decay, nesterov, losses, workspace,
+                 workspace_bytes, nullptr, (hipStream_t)stream);
+}
+
+size_t clipmi_adapter_fit_monitored_workspace_bytes(int n_val, int C, int n_bins) { return C >= 2 ? fit_monitor_bytes(n_val, C, n_bins) : 0; }
+
+int clipmi_adapter_fit_monitored(const float* feats, int64_t ld, const int64_t* labels, const int32_t* order, const float* text, float* w1, float* w2,
+                                 float* m1, float* m2, int n, int E, int H, int C, int batch, int epochs, int drop_last, float ratio, float scale,
+                                 const float* lr, int first_step, float momentum, float dampening, float weight_decay, int nesterov, float* losses,
+                                 void* workspace, size_t workspace_bytes, const float* val_feats, int64_t val_ld, const int64_t* val_labels,
+                                 int n_val, int n_bins, void* records, int criterion, void* best_block, float* best_params,
+                                 void* monitor_workspace, size_t monitor_workspace_bytes, clipmi_stream_t stream) {
+  const Problem p{feats, ld, labels, text, w1, w2, m1, m2, n, E, H, C, ratio, scale};
+  const FitMonitor mon{val_feats, val_ld, val_labels, n_val, n_bins, records, criterion, best_block, best_params, monitor_workspace,
+                       monitor_workspace_bytes};
+  return run_fit("adapter_fit_monitored", p, order, batch, epochs, drop_last, lr, first_step, momentum, dampening, weight_decay, nesterov, losses,
+                 workspace, workspace_bytes, &mon, (hipStream_t)stream);
+}
+
+int clipmi_adapter_val_logits(const float* feats, int64_t ld, const float* text, const float* w1, const float* w2, int n_val, int E, int H, int C,
+                              float ratio, float scale, float* logits, clipmi_stream_t stream) {
+  if (int rc = check_val("adapter_val_logits", feats, ld, text, w1, w2, n_val, E, H, C, ratio, scale, logits)) return rc;
+  return launch_val(feats, ld, text, w1, w2, n_val, E, H, C, ratio, scale, logits, (hipStream_t)stream);
 }
 
 }  // extern "C"

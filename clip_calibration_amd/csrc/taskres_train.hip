@@ -22,6 +22,7 @@
 #include <cmath>
 
 #include "common.h"
+#include "fit_monitor.h"
 #include "train_rules.h"
 
 namespace clipmi {
@@ -90,6 +91,9 @@ __device__ __forceinline__ float row16_sum(float v) {
 
 // grid (ceil(C / 64), ceil(rows / 64)).  Both operands are depth-contiguous: thread t loads column t % 16 of the stage for the rows
 // t / 16 + 16 j, j < 4, of either operand -- and so meets every 16th element of each of its rows, whose squares it sums.
+// The validation logits (clipmi_taskres_val_logits) are this kernel on the validation rows with ws.z the caller's [N_val, C] and no place for
+// the norms (ws.nf == ws.nt == null): one code, so validation sees the logits a step on those rows would see.  A tile column normalises its 64
+// classifier rows once for the 64 validation rows it meets, on the way, not once per row.
 __global__ __launch_bounds__(THREADS) void taskres_logits_kernel(Batch bt, const float* __restrict__ base, const float* __restrict__ res, int E, int C,
                                                                  float alpha, float scale, Workspace ws) {
 #pragma clang fp contract(off)   // t = base + alpha r is rounded as the update kernel rounds it
@@ -140,8 +144,8 @@ __global__ __launch_bounds__(THREADS) void taskres_logits_kernel(Batch bt, const
       const int row = b0 + lr + 16 * j, c = c0 + lr + 16 * j;
       sna[lr + 16 * j] = na;
       snb[lr + 16 * j] = nb;
-      if (blockIdx.x == 0 && row < bt.rows) ws.nf[row] = na;
-      if (blockIdx.y == 0 && c < C) ws.nt[c] = nb;
+      if (ws.nf && blockIdx.x == 0 && row < bt.rows) ws.nf[row] = na;
+      if (ws.nt && blockIdx.y == 0 && c < C) ws.nt[c] = nb;
     }
   }
   __syncthreads();
@@ -328,6 +332,64 @@ int launch_step(const Problem& p, const int32_t* order, int first, int rows, con
   return check_launch("taskres_update_kernel");
 }
 
+// the validation logits: what clipmi_taskres_val_logits refuses, in the vocabulary of check_problem
+int check_val(const char* who, const float* feats, int64_t ld, const float* base, const float* res, int n_val, int E, int C, float alpha, float scale,
+              const float* logits) {
+  CLIPMI_REQUIRE(feats && base && res && logits, CLIPMI_ERR_ARG, "%s: null pointer (feats, base, residuals and the logits are required)", who);
+  CLIPMI_REQUIRE(aligned(feats, 4) && aligned(base, 4) && aligned(res, 4), CLIPMI_ERR_ARG, "%s: fp32 arrays must be 4-byte aligned", who);
+  CLIPMI_REQUIRE(aligned(logits, 16), CLIPMI_ERR_ARG, "%s: the logits must be 16-byte aligned (clipmi_val_score reads them)", who);
+  CLIPMI_REQUIRE(std::isfinite(alpha) && std::isfinite(scale), CLIPMI_ERR_ARG, "%s: alpha=%g, scale=%g (both finite)", who, alpha, scale);
+  CLIPMI_REQUIRE(n_val >= 1 && n_val <= MAX_DIM, CLIPMI_ERR_SHAPE, "%s: N_val=%d (1 .. %d)", who, n_val, MAX_DIM);
+  CLIPMI_REQUIRE(C >= 2 && C <= MAX_DIM, CLIPMI_ERR_SHAPE, "%s: C=%d (2 .. %d classes)", who, C, MAX_DIM);
+  CLIPMI_REQUIRE(E >= 1, CLIPMI_ERR_SHAPE, "%s: E=%d (>= 1)", who, E);
+  CLIPMI_REQUIRE(ld >= E, CLIPMI_ERR_SHAPE, "%s: ld=%lld < E=%d", who, (long long)ld, E);
+  return CLIPMI_OK;
+}
+
+// the training step's first launch on the validation rows: z goes to `logits` [n_val, C], the norms are not kept
+int launch_val(const float* feats, int64_t ld, const float* base, const float* res, int n_val, int E, int C, float alpha, float scale, float* logits,
+               hipStream_t s) {
+  const Workspace ws{logits, nullptr, nullptr, nullptr, nullptr};
+  const Batch bt{feats, ld, nullptr, nullptr, 0, n_val, n_val};
+  const unsigned tb = (unsigned)((n_val + TILE - 1) / TILE), tc = (unsigned)((C + TILE - 1) / TILE);
+  hipLaunchKernelGGL(taskres_logits_kernel, dim3(tc, tb), dim3(THREADS), 0, s, bt, base, res, E, C, alpha, scale, ws);
+  return check_launch("taskres_logits_kernel");
+}
+
+// The one body of clipmi_taskres_fit and clipmi_taskres_fit_monitored.  Without a monitor the steps are enqueued and nothing else; with one,
+// behind the last step of every epoch: the validation logits of the residuals as they are, the epoch record and, with a best slot, the
+// selection of the residual matrix (the optimiser's state is not part of it).
+int run_fit(const char* who, const Problem& p, const Optimiser& o, const int32_t* order, int batch, int epochs, int drop_last, const float* lr,
+            float* losses, void* workspace, size_t workspace_bytes, const FitMonitor* mon, hipStream_t stream) {
+  if (int rc = check_problem(who, p, lr, o)) return rc;
+  CLIPMI_REQUIRE(batch >= 1, CLIPMI_ERR_SHAPE, "%s: batch=%d (>= 1)", who, batch);
+  CLIPMI_REQUIRE(epochs >= 0, CLIPMI_ERR_ARG, "%s: epochs=%d (>= 0)", who, epochs);
+  const int width = batch < p.n ? batch : p.n;   // the widest batch of the run
+  if (int rc = check_workspace(who, workspace, workspace_bytes, width, p)) return rc;
+  if (mon) {
+    if (int rc = check_fit_monitor(who, *mon, p.E, p.C)) return rc;
+    CLIPMI_REQUIRE(mon->n_val <= MAX_DIM, CLIPMI_ERR_SHAPE, "%s: N_val=%d (%d at most)", who, mon->n_val, MAX_DIM);
+    CLIPMI_REQUIRE(!mon->best_block || aligned(p.res, 16), CLIPMI_ERR_ARG, "%s: a best slot needs the residuals 16-byte aligned", who);
+  }
+  const int per_epoch = drop_last ? p.n / batch : (int)(((int64_t)p.n + batch - 1) / batch);
+  int64_t step = 0;
+  for (int e = 0; e < epochs; ++e) {
+    const int32_t* epoch_order = order ? order + (int64_t)e * p.n : nullptr;
+    for (int k = 0; k < per_epoch; ++k, ++step) {
+      const int first = k * batch;   // k < per_epoch <= n: no overflow
+      const int rows = p.n - first < batch ? p.n - first : batch;
+      if (int rc = launch_step(p, epoch_order ? epoch_order + first : nullptr, first, rows, lr + step, opt_args(o, o.steps_done + step + 1),
+                               losses ? losses + step : nullptr, workspace, stream))
+        return rc;
+    }
+    if (!mon) continue;
+    if (int rc = launch_val(mon->val_feats, mon->val_ld, p.base, p.res, mon->n_val, p.E, p.C, p.alpha, p.scale, fit_monitor_logits(*mon), stream))
+      return rc;
+    if (int rc = fit_monitor_score(*mon, e, p.C, p.res, (int64_t)p.C * p.E, (clipmi_stream_t)stream)) return rc;
+  }
+  return CLIPMI_OK;
+}
+
 }  // namespace
 }  // namespace clipmi
 
@@ -357,24 +419,31 @@ int clipmi_taskres_fit(const float* feats, int64_t ld, const int64_t* labels, co
                        double beta1, double beta2, double eps, float* losses, void* workspace, size_t workspace_bytes, clipmi_stream_t stream) {
   const Problem p{feats, ld, labels, base, residuals, state1, state2, n, E, C, alpha, scale};
   const Optimiser o{optimizer, steps_done, weight_decay, momentum, dampening, nesterov, beta1, beta2, eps};
-  if (int rc = check_problem("taskres_fit", p, lr, o)) return rc;
-  CLIPMI_REQUIRE(batch >= 1, CLIPMI_ERR_SHAPE, "taskres_fit: batch=%d (>= 1)", batch);
-  CLIPMI_REQUIRE(epochs >= 0, CLIPMI_ERR_ARG, "taskres_fit: epochs=%d (>= 0)", epochs);
-  const int width = batch < n ? batch : n;   // the widest batch of the run
-  if (int rc = check_workspace("taskres_fit", workspace, workspace_bytes, width, p)) return rc;
-  const int per_epoch = drop_last ? n / batch : (int)(((int64_t)n + batch - 1) / batch);
-  int64_t step = 0;
-  for (int e = 0; e < epochs; ++e) {
-    const int32_t* epoch_order = order ? order + (int64_t)e * n : nullptr;
-    for (int k = 0; k < per_epoch; ++k, ++step) {
-      const int first = k * batch;   // k < per_epoch <= n: no overflow
-      const int rows = n - first < batch ? n - first : batch;
-      if (int rc = launch_step(p, epoch_order ? epoch_order + first : nullptr, first, rows, lr + step, opt_args(o, steps_done + step + 1),
-                               losses ? losses + step : nullptr, workspace, (hipStream_t)stream))
-        return rc;
-    }
-  }
-  return CLIPMI_OK;
+  return run_fit("taskres_fit", p, o, order, batch, epochs, drop_last, lr, losses, workspace, workspace_bytes, nullptr, (hipStream_t)stream);
+}
+
+size_t clipmi_taskres_fit_monitored_workspace_bytes(int n_val, int C, int n_bins) {
+  return C >= 2 && C <= MAX_DIM && n_val <= MAX_DIM ? fit_monitor_bytes(n_val, C, n_bins) : 0;
+}
+
+int clipmi_taskres_fit_monitored(const float* feats, int64_t ld, const int64_t* labels, const int32_t* order, const float* base, float* residuals,
+                                 float* state1, float* state2, int n, int E, int C, int batch, int epochs, int drop_last, float alpha, float scale,
+                                 const float* lr, int optimizer, int64_t steps_done, float weight_decay, float momentum, float dampening,
+                                 int nesterov, double beta1, double beta2, double eps, float* losses, void* workspace, size_t workspace_bytes,
+                                 const float* val_feats, int64_t val_ld, const int64_t* val_labels, int n_val, int n_bins, void* records,
+                                 int criterion, void* best_block, float* best_params, void* monitor_workspace, size_t monitor_workspace_bytes,
+                                 clipmi_stream_t stream) {
+  const Problem p{feats, ld, labels, base, residuals, state1, state2, n, E, C, alpha, scale};
+  const Optimiser o{optimizer, steps_done, weight_decay, momentum, dampening, nesterov, beta1, beta2, eps};
+  const FitMonitor mon{val_feats, val_ld, val_labels, n_val, n_bins, records, criterion, best_block, best_params, monitor_workspace,
+                       monitor_workspace_bytes};
+  return run_fit("taskres_fit_monitored", p, o, order, batch, epochs, drop_last, lr, losses, workspace, workspace_bytes, &mon, (hipStream_t)stream);
+}
+
+int clipmi_taskres_val_logits(const float* feats, int64_t ld, const float* base, const float* residuals, int n_val, int E, int C, float alpha,
+                              float scale, float* logits, clipmi_stream_t stream) {
+  if (int rc = check_val("taskres_val_logits", feats, ld, base, residuals, n_val, E, C, alpha, scale, logits)) return rc;
+  return launch_val(feats, ld, base, residuals, n_val, E, C, alpha, scale, logits, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -651,11 +651,15 @@ def adapter_fit(features: torch.Tensor, labels: torch.Tensor, text: torch.Tensor
                 m1: Optional[torch.Tensor], m2: Optional[torch.Tensor], lr: torch.Tensor, ratio: float, scale: float, batch_size: int, epochs: int,
                 momentum: float = 0.0, dampening: float = 0.0, weight_decay: float = 0.0, nesterov: bool = False,
                 order: Optional[torch.Tensor] = None, drop_last: bool = False, first_step: bool = True,
-                want_losses: bool = False) -> Optional[torch.Tensor]:
+                want_losses: bool = False, monitor: Optional[dict] = None) -> Optional[torch.Tensor]:
     """The whole SGD run of CLIP-Adapter's bottleneck from the cached ``features`` fp32 [N, E], enqueued without a host synchronisation
     (include/clipmi.h, clipmi_adapter_fit).  ``w1``, ``w2`` and the momentum buffers are updated in place; ``lr`` fp32 [steps], one rate
     per step; ``order`` int32 [epochs, N] or None (0 .. N-1 every epoch).  Returns the per-step batch losses fp32 [steps] when
-    ``want_losses``."""
+    ``want_losses``.
+
+    ``monitor`` (``fit_monitor(...)``): the monitored form, clipmi_adapter_fit_monitored -- behind every epoch the validation logits, the
+    epoch record and, with a best slot, the selection of the block [w1 | w2], which ``w1`` and ``w2`` must then be views of
+    (``adapter_master_block``).  The same steps, the same fitted bits; still nothing synchronises."""
     features, labels, text = _adapter_problem(features, labels, text, w1, w2, m1, m2, momentum, "adapter_fit")
     (N, E), H, Cn = features.shape, w1.shape[0], text.shape[0]
     batch_size, epochs = int(batch_size), int(epochs)
@@ -671,10 +675,15 @@ def adapter_fit(features: torch.Tensor, labels: torch.Tensor, text: torch.Tensor
     losses = torch.empty(steps, dtype=torch.float32, device=features.device) if want_losses else None
     ws = _adapter_workspace(min(batch_size, N), E, H, Cn, features.device)
     pm1, pm2 = (m1.data_ptr(), m2.data_ptr()) if momentum != 0.0 else (None, None)
-    check(lib.clipmi_adapter_fit(features.data_ptr(), features.stride(0), labels.data_ptr(), po, text.data_ptr(), w1.data_ptr(), w2.data_ptr(),
-                                 pm1, pm2, N, E, H, Cn, batch_size, epochs, int(bool(drop_last)), float(ratio), float(scale), lr.data_ptr(),
-                                 int(bool(first_step)), float(momentum), float(dampening), float(weight_decay), int(bool(nesterov)),
-                                 None if losses is None else losses.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "clipmi_adapter_fit")
+    args = (features.data_ptr(), features.stride(0), labels.data_ptr(), po, text.data_ptr(), w1.data_ptr(), w2.data_ptr(),
+            pm1, pm2, N, E, H, Cn, batch_size, epochs, int(bool(drop_last)), float(ratio), float(scale), lr.data_ptr(),
+            int(bool(first_step)), float(momentum), float(dampening), float(weight_decay), int(bool(nesterov)),
+            None if losses is None else losses.data_ptr(), ws.data_ptr(), ws.numel())
+    if monitor is None:
+        check(lib.clipmi_adapter_fit(*args, _stream()), "clipmi_adapter_fit")
+    else:
+        tail = _fit_monitor_args("adapter_fit", monitor, E, Cn, epochs, 2 * E * H, lib.clipmi_adapter_fit_monitored_workspace_bytes)
+        check(lib.clipmi_adapter_fit_monitored(*args, *tail, _stream()), "clipmi_adapter_fit_monitored")
     return losses
 
 
@@ -749,10 +758,13 @@ def taskres_fit(features: torch.Tensor, labels: torch.Tensor, base: torch.Tensor
                 state2: Optional[torch.Tensor], lr: torch.Tensor, alpha: float, scale: float, batch_size: int, epochs: int,
                 optimizer: str = "adam", weight_decay: float = 0.0, momentum: float = 0.0, dampening: float = 0.0, nesterov: bool = False,
                 betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8, order: Optional[torch.Tensor] = None, drop_last: bool = False,
-                steps_done: int = 0, want_losses: bool = False) -> Optional[torch.Tensor]:
+                steps_done: int = 0, want_losses: bool = False, monitor: Optional[dict] = None) -> Optional[torch.Tensor]:
     """The whole training run of TaskRes' residuals from the cached ``features`` fp32 [N, E], enqueued without a host synchronisation
     (include/clipmi.h, clipmi_taskres_fit).  ``residuals`` and the state are updated in place; ``lr`` fp32 [steps], one rate per step;
-    ``order`` int32 [epochs, N] or None (0 .. N-1 every epoch).  Returns the per-step batch losses fp32 [steps] when ``want_losses``."""
+    ``order`` int32 [epochs, N] or None (0 .. N-1 every epoch).  Returns the per-step batch losses fp32 [steps] when ``want_losses``.
+
+    ``monitor`` (``fit_monitor(...)``): the monitored form, clipmi_taskres_fit_monitored -- behind every epoch the validation logits, the
+    epoch record and, with a best slot, the selection of ``residuals``.  The same steps, the same fitted bits; still nothing synchronises."""
     features, labels, base, kind, p1, p2 = _taskres_problem(features, labels, base, residuals, state1, state2, optimizer, momentum, "taskres_fit")
     (N, E), Cn = features.shape, base.shape[0]
     batch_size, epochs = int(batch_size), int(epochs)
@@ -767,11 +779,15 @@ def taskres_fit(features: torch.Tensor, labels: torch.Tensor, base: torch.Tensor
         raise ValueError(f"taskres_fit: order {tuple(order.shape)} must be [epochs, N] = [{epochs}, {N}]")
     losses = torch.empty(steps, dtype=torch.float32, device=features.device) if want_losses else None
     ws = _taskres_workspace(min(batch_size, N), E, Cn, features.device)
-    check(lib.clipmi_taskres_fit(features.data_ptr(), features.stride(0), labels.data_ptr(), po, base.data_ptr(), residuals.data_ptr(), p1, p2,
-                                 N, E, Cn, batch_size, epochs, int(bool(drop_last)), float(alpha), float(scale), lr.data_ptr(), kind,
-                                 int(steps_done), float(weight_decay), float(momentum), float(dampening), int(bool(nesterov)), float(betas[0]),
-                                 float(betas[1]), float(eps), None if losses is None else losses.data_ptr(), ws.data_ptr(), ws.numel(),
-                                 _stream()), "clipmi_taskres_fit")
+    args = (features.data_ptr(), features.stride(0), labels.data_ptr(), po, base.data_ptr(), residuals.data_ptr(), p1, p2,
+            N, E, Cn, batch_size, epochs, int(bool(drop_last)), float(alpha), float(scale), lr.data_ptr(), kind,
+            int(steps_done), float(weight_decay), float(momentum), float(dampening), int(bool(nesterov)), float(betas[0]),
+            float(betas[1]), float(eps), None if losses is None else losses.data_ptr(), ws.data_ptr(), ws.numel())
+    if monitor is None:
+        check(lib.clipmi_taskres_fit(*args, _stream()), "clipmi_taskres_fit")
+    else:
+        tail = _fit_monitor_args("taskres_fit", monitor, E, Cn, epochs, Cn * E, lib.clipmi_taskres_fit_monitored_workspace_bytes)
+        check(lib.clipmi_taskres_fit_monitored(*args, *tail, _stream()), "clipmi_taskres_fit_monitored")
     return losses
 
 
@@ -1202,6 +1218,118 @@ def best_select(record: torch.Tensor, best_block: torch.Tensor, criterion, epoch
         workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=params.device)
     check(lib.clipmi_best_select(record.data_ptr(), pb, VAL_CRITERIA[criterion], int(epoch), params.data_ptr(), best_params.data_ptr(), params.numel(),
                                  workspace.data_ptr(), workspace.numel(), _stream()), "clipmi_best_select")
+
+
+# ---- validation inside the cached-feature fits (csrc/adapter_train.hip, csrc/taskres_train.hip; DESIGN.md "Fit monitor")
+
+def _val_rows(who: str, features, E: int) -> torch.Tensor:
+    """Validation features fp32 [N_val >= 1, E] on the GPU, read in place with their row stride when the rows are contiguous."""
+    if not isinstance(features, torch.Tensor) or features.dim() != 2 or features.shape[0] < 1 or features.shape[1] != E:
+        raise ValueError(f"{who}: features {tuple(getattr(features, 'shape', ()))} must be [N_val >= 1, E = {E}]")
+    if features.stride(1) == 1 and features.stride(0) >= E:
+        _dev(features[:1], "features", (torch.float32,))     # the device and dtype checks only
+        return features
+    return _dev(features, "features", (torch.float32,))
+
+
+def _val_out(who: str, out: Optional[torch.Tensor], N: int, Cn: int, device) -> torch.Tensor:
+    if out is None:
+        return torch.empty(N, Cn, dtype=torch.float32, device=device)
+    _in_place(out, torch.float32, f"{who}: out must be a contiguous fp32 [{N}, {Cn}] tensor on the GPU", numel=N * Cn)
+    return out
+
+
+def adapter_val_logits(features: torch.Tensor, text: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor, ratio: float, scale: float,
+                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """clipmi_adapter_val_logits: ``scale * normalise(ratio * relu(relu(f W1^T) W2^T) + (1 - ratio) * f) @ text.T`` for the validation
+    ``features`` fp32 [N_val, E] (raw image features; the rows may be a column slice), fp32 [N_val, C] -- the forward half of the training
+    step on the weights as they are, the same code in the same order, so the logits a step on those rows would see.  Enqueued; no
+    workspace; the same inputs give the same bytes.  ``out``: a contiguous fp32 [N_val, C] tensor to write into."""
+    who = "adapter_val_logits"
+    text, w1, w2 = (_dev(t, n, (torch.float32,)) for t, n in ((text, "text_features"), (w1, "w1"), (w2, "w2")))
+    if text.dim() != 2 or text.shape[0] < 2:
+        raise ValueError(f"{who}: text features {tuple(text.shape)} must be [C >= 2, E]")
+    Cn, E = text.shape
+    if w1.dim() != 2 or w1.shape[1] != E or w1.shape[0] < 1 or tuple(w2.shape) != (E, w1.shape[0]):
+        raise ValueError(f"{who}: adapter shapes do not chain (E = {E}, w1 {tuple(w1.shape)}, w2 {tuple(w2.shape)})")
+    features = _val_rows(who, features, E)
+    N = features.shape[0]
+    out = _val_out(who, out, N, Cn, features.device)
+    check(lib.clipmi_adapter_val_logits(features.data_ptr(), features.stride(0), text.data_ptr(), w1.data_ptr(), w2.data_ptr(), N, E, w1.shape[0], Cn,
+                                        float(ratio), float(scale), out.data_ptr(), _stream()), "clipmi_adapter_val_logits")
+    return out
+
+
+def taskres_val_logits(features: torch.Tensor, base: torch.Tensor, residuals: torch.Tensor, alpha: float, scale: float,
+                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """clipmi_taskres_val_logits: ``scale * normalise(f) @ normalise(base + alpha * residuals).T`` for the validation ``features`` fp32
+    [N_val, E] (raw image features; the rows may be a column slice), fp32 [N_val, C] -- the training step's own logits kernel on the
+    validation rows.  Enqueued; no workspace; the same inputs give the same bytes.  ``out``: a contiguous fp32 [N_val, C] tensor."""
+    who = "taskres_val_logits"
+    base, residuals = _dev(base, "base_text_features", (torch.float32,)), _dev(residuals, "residuals", (torch.float32,))
+    if base.dim() != 2 or base.shape[0] < 2 or residuals.shape != base.shape:
+        raise ValueError(f"{who}: base text features {tuple(base.shape)} must be [C >= 2, E] and the residuals {tuple(residuals.shape)} of that shape")
+    Cn, E = base.shape
+    features = _val_rows(who, features, E)
+    N = features.shape[0]
+    out = _val_out(who, out, N, Cn, features.device)
+    check(lib.clipmi_taskres_val_logits(features.data_ptr(), features.stride(0), base.data_ptr(), residuals.data_ptr(), N, E, Cn, float(alpha),
+                                        float(scale), out.data_ptr(), _stream()), "clipmi_taskres_val_logits")
+    return out
+
+
+def adapter_master_block(w1: torch.Tensor, w2: torch.Tensor, device) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """``(block, w1, w2)``: fresh fp32 master copies of the two matrices as views of one contiguous block [w1 | w2] on ``device`` -- what
+    ``clipmi_best_select`` copies in one piece."""
+    block = torch.empty(w1.numel() + w2.numel(), dtype=torch.float32, device=device)
+    m1, m2 = block[:w1.numel()].view(w1.shape), block[w1.numel():].view(w2.shape)
+    m1.copy_(w1.detach())
+    m2.copy_(w2.detach())
+    return block, m1, m2
+
+
+def fit_monitor(val_features: torch.Tensor, val_labels: torch.Tensor, n_bins: int, records: torch.Tensor, criterion: str = "accuracy",
+                best_block: Optional[torch.Tensor] = None, best_params: Optional[torch.Tensor] = None,
+                workspace: Optional[torch.Tensor] = None) -> dict:
+    """The ``monitor=`` of ``adapter_fit`` / ``taskres_fit``: validation features fp32 [N_val, E] and labels int64 [N_val] on the GPU,
+    ``records`` (``new_val_records(epochs, n_bins, device)``), and for the selection ``best_block`` (``new_best_block``) with
+    ``best_params`` (contiguous fp32 on the GPU, the size of the selected parameters) -- both or neither.  ``workspace``: a uint8 tensor to
+    reuse (4 N_val C bytes and the scoring's; made by the call when absent or short)."""
+    if criterion not in VAL_CRITERIA:
+        raise ValueError(f"fit_monitor: criterion={criterion!r} must be one of {sorted(VAL_CRITERIA)}")
+    if (best_block is None) != (best_params is None):
+        raise ValueError("fit_monitor: best_block and best_params come together")
+    return {"val_features": val_features, "val_labels": val_labels, "n_bins": _val_bins("fit_monitor", n_bins), "records": records,
+            "criterion": criterion, "best_block": best_block, "best_params": best_params, "workspace": workspace}
+
+
+def _fit_monitor_args(who: str, m: dict, E: int, Cn: int, epochs: int, n_floats: int, workspace_bytes) -> tuple:
+    """The monitored calls' extra arguments from a ``fit_monitor`` dict, checked; the workspace it makes stays in the dict."""
+    vf = _val_rows(who, m["val_features"], E)
+    N = vf.shape[0]
+    vl = _dev(m["val_labels"], "val_labels", (torch.int64,))
+    if vl.shape != (N,):
+        raise ValueError(f"{who}: {N} validation rows need {N} labels, got {tuple(vl.shape)}")
+    n_bins = _val_bins(who, m["n_bins"])
+    pr = _monitor_bytes(who, m["records"], "records", epochs * val_record_bytes(n_bins))
+    pb = pp = None
+    if m["best_block"] is not None:
+        pb = _monitor_bytes(who, m["best_block"], "best_block", _BEST_DTYPE.itemsize)
+        _in_place(m["best_params"], torch.float32, f"{who}: best_params must be a contiguous fp32 tensor of {n_floats} elements on the GPU",
+                  numel=n_floats)
+        pp = m["best_params"].data_ptr()
+    need = workspace_bytes(N, Cn, n_bins)
+    if m.get("workspace") is None or m["workspace"].numel() < need:
+        m["workspace"] = torch.empty(max(need, 256), dtype=torch.uint8, device=vf.device)
+    m["_keep"] = (vf, vl)     # alive until the caller has waited for the run
+    return (vf.data_ptr(), vf.stride(0), vl.data_ptr(), N, n_bins, pr, VAL_CRITERIA[m["criterion"]], pb, pp, m["workspace"].data_ptr(),
+            m["workspace"].numel())
+
+
+def fit_monitor_logits(m: dict, Cn: int) -> torch.Tensor:
+    """The fp32 [N_val, C] logits of the last validated epoch of a monitored run, where its workspace holds them."""
+    N = m["val_features"].shape[0]
+    return m["workspace"][:4 * N * Cn].view(torch.float32).view(N, Cn)
 
 
 PROMPT_MODES ={"coop": _lib.PROMPT_COOP, "kgcoop": _lib.PROMPT_KGCOOP, "prograd": _lib.PROMPT_PROGRAD}

@@ -29,7 +29,7 @@ from typing import Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import fitloop, ops
+from . import fitloop, fitmonitor, ops
 from .fitloop import _need_gpu, steps_per_epoch
 
 
@@ -75,7 +75,8 @@ def fit_residuals(features: torch.Tensor, labels, base_text_features: torch.Tens
                   logit_scale: float = 4.6052, optimizer: str = "adam", lr: float = 2e-4, epochs: int = 200, batch_size: int = 256,
                   betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8, weight_decay: float = 5e-4, momentum: float = 0.9,
                   dampening: float = 0.0, nesterov: bool = False, lr_per_epoch: Optional[Sequence[float]] = None, order=None,
-                  drop_last: bool = True, return_history: bool = False):
+                  drop_last: bool = True, return_history: bool = False, val=None, val_bins: int = 10, final_model: str = "last_step",
+                  val_criterion: str = "accuracy", return_monitor: bool = False):
     """Train TaskRes' residuals on cached ``features`` fp32 [N, E] (raw, un-normalised image features on the GPU; the rows may be a
     column slice of a wider matrix), ``labels`` [N] and the frozen ``base_text_features`` fp32 [C, E] (not normalised), starting from
     ``residuals`` [C, E] (not modified; None = zeros, the reference's initialisation): ``epochs`` passes of ``torch.optim.Adam(lr, betas,
@@ -90,8 +91,19 @@ def fit_residuals(features: torch.Tensor, labels, base_text_features: torch.Tens
     Labels (and ``order``) are checked against their ranges on the host before anything is launched -- a label tensor on the GPU is
     copied to the host for that, which waits for whatever produced it; from the first launch on nothing synchronises until the one wait
     at the end.  Returns the fitted fp32 residuals on the device, or ``(residuals, per-step batch losses as a float32 numpy array)`` with
-    ``return_history``.  The defaults are unverified restatements of the reference's config and Dassl's (module docstring)."""
+    ``return_history``.  The defaults are unverified restatements of the reference's config and Dassl's (module docstring).
+
+    ``val=(val_features, val_labels)`` (raw image features [N_val, E] on the GPU and their labels): behind the last step of every epoch
+    the run scores the residuals against them on the device, into ``val_bins`` confidence bins (clipmi_taskres_fit_monitored: the
+    training step's logits kernel on the validation rows, ``clipmi_val_score``, ``clipmi_best_select``) -- the fitted residuals are bit
+    for bit those of the same call without ``val``, and the run is still one library call and one wait.  ``final_model``: "last_step"
+    returns the last epoch's residuals; "best_val" (the reference's TEST.FINAL_MODEL, base_learner.py:41-47) those of the epoch that was
+    strictly better than every earlier one under ``val_criterion`` -- "accuracy" (Dassl's rule) or "nll", where an epoch with a
+    non-finite nll is never taken; the starting residuals when no epoch was taken.  "best_val" without ``val`` is refused.
+    ``return_monitor`` adds a dict behind everything else, read once after the run's one wait: per-epoch ``accuracy``, ``nll`` and
+    ``ece``, the raw ``bins``, ``records`` and ``best_epoch`` (``TaskResFitState.monitor``); empty without ``val`` or without steps."""
     who = "fit_residuals"
+    fitmonitor.check_args(who, val, val_bins, final_model, val_criterion)
     N, E, C = _check_shapes(who, features, base_text_features, residuals)
     epochs, batch_size = fitloop.check_run(who, epochs, batch_size)
     _check_optimiser(who, optimizer, betas, eps, weight_decay, momentum, dampening, nesterov)
@@ -102,16 +114,28 @@ def fit_residuals(features: torch.Tensor, labels, base_text_features: torch.Tens
     per_epoch = steps_per_epoch(N, batch_size, drop_last)
     dev = features.device
     _, lr_steps = fitloop.schedule(who, lr, epochs, lr_per_epoch, per_epoch, dev)
+    if val is not None:
+        vf, vl = fitmonitor.check_val(who, val, E, C)
     _need_gpu(features, "features")
     r = _master(base_text_features, residuals, dev)
     if epochs * per_epoch == 0:
-        return (r, np.zeros(0, np.float32)) if return_history else r
+        return fitmonitor.pack(r, np.zeros(0, np.float32), fitmonitor.empty_monitor(val_bins), return_history, return_monitor)
     s1, s2 = _state(r, optimizer, momentum)
+    mon = monitor = None
+    if val is not None:
+        _need_gpu(vf, "val_features")
+        mon = fitmonitor.Monitor(who, epochs, val_bins, val_criterion, r if final_model == "best_val" else None, dev)
+        mon.seen = epochs
+        monitor = ops.fit_monitor(vf if vf.dtype == torch.float32 else vf.float(), vl.to(dev), mon.bins, mon.records, val_criterion, mon.block,
+                                  mon.best)
     losses = ops.taskres_fit(features, fitloop.labels_on(labels, lab, dev), base_text_features, r, s1, s2, lr_steps, alpha,
                              float(np.float32(math.exp(logit_scale))), batch_size, epochs, optimizer, weight_decay, momentum, dampening, nesterov,
-                             betas, eps, fitloop.order_on(order, np.int32, dev), drop_last, steps_done=0, want_losses=return_history)
+                             betas, eps, fitloop.order_on(order, np.int32, dev), drop_last, steps_done=0, want_losses=return_history,
+                             monitor=monitor)
     torch.cuda.current_stream().synchronize()   # the run's one synchronisation
-    return (r, losses.cpu().numpy()) if return_history else r
+    return fitmonitor.pack(mon.best if final_model == "best_val" else r, losses.cpu().numpy() if return_history else None,
+                           (mon.summary() if mon is not None else fitmonitor.empty_monitor(val_bins)) if return_monitor else None,
+                           return_history, return_monitor)
 
 
 class TaskResFitState:
@@ -137,6 +161,58 @@ class TaskResFitState:
         self.optimizer, self.betas, self.eps, self.weight_decay = optimizer, (float(betas[0]), float(betas[1])), eps, weight_decay
         self.momentum, self.dampening, self.nesterov = momentum, dampening, nesterov
         self.steps = 0
+        self._mon = None    # the fit monitor's device history, made by start_monitor or the first validate
+
+    # ---- per-epoch validation and best-epoch selection on the device (DESIGN.md "Fit monitor"), as CoOpFitState has them
+
+    def start_monitor(self, slots: int, val_bins: int = 10, select: bool = False, val_criterion: str = "accuracy") -> None:
+        """The device history ``validate`` writes: ``slots`` epoch records of ``val_bins`` confidence bins and, with ``select``, the best
+        block and the best slot (a copy of the residuals as they are now, replaced whenever an epoch is strictly better under
+        ``val_criterion``; the optimiser's state is not part of it).  Allocations and one small upload; nothing synchronises."""
+        self._mon = fitmonitor.Monitor("TaskResFitState.start_monitor", slots, val_bins, val_criterion, self.residuals if select else None,
+                                       self.residuals.device)
+
+    def validate(self, val_features: torch.Tensor, val_labels, epoch: int) -> None:
+        """Enqueue one validation of the current master residuals into slot ``epoch`` of the device history; no host read.
+        ``clipmi_taskres_val_logits`` runs the training step's logits kernel on ``val_features`` (raw image features [N_val, E] on the
+        GPU) into fp32 [N_val, C] logits the state owns (4 N_val C bytes, kept for the next epoch); ``clipmi_val_score`` scores them into
+        the record and, when the monitor selects, ``clipmi_best_select`` compares the record with the best block and copies the
+        residuals into the best slot.  ``val_labels`` [N_val]: an int64 tensor on the GPU is taken as it is (a label outside [0, C) then
+        counts as wrong with a NaN nll), anything else is range-checked on the host, once per set.  Without ``start_monitor`` the history
+        starts with ``epoch + 1`` slots of 10 bins and no selection; it grows when ``epoch`` lies behind its end."""
+        who = "TaskResFitState.validate"
+        if self._mon is None:
+            self.start_monitor(int(epoch) + 1 if isinstance(epoch, int) and epoch >= 0 else 1)
+        mon = self._mon
+        epoch = mon.slot(who, epoch)
+        C, E = self.base_text_features.shape
+        feats, labels_d = mon.operands(who, val_features, val_labels, E, C)
+        ops.taskres_val_logits(feats, self.base_text_features, self.residuals, self.alpha, self.scale, out=mon.logits)
+        mon.score(epoch, labels_d, self.residuals)
+
+    def val_logits(self) -> torch.Tensor:
+        """The fp32 [N_val, C] logits of the last ``validate``, where the state keeps them (the next ``validate`` overwrites them)."""
+        if self._mon is None or self._mon.logits is None:
+            raise ValueError("TaskResFitState.val_logits: nothing has been validated")
+        return self._mon.logits
+
+    def best_residuals(self) -> torch.Tensor:
+        """The best slot on the device: the residuals of the best epoch so far, or those ``start_monitor`` saw while no epoch has been
+        taken.  No read-back."""
+        if self._mon is None or self._mon.best is None:
+            raise ValueError("TaskResFitState.best_residuals: the monitor does not select (start_monitor(..., select=True))")
+        return self._mon.best
+
+    def monitor_records(self) -> torch.Tensor:
+        """The device history, uint8 [slots, ops.val_record_bytes(val_bins)]; no read-back."""
+        if self._mon is None:
+            raise ValueError("TaskResFitState.monitor_records: nothing has been validated")
+        return self._mon.records
+
+    def monitor(self) -> dict:
+        """The history as numbers (``fitmonitor.monitor_dict``, the dict ``CoOpFitState.monitor`` returns).  It reads the history back:
+        one synchronisation."""
+        return fitmonitor.empty_monitor() if self._mon is None else self._mon.summary()
 
     def step(self, features: torch.Tensor, labels, lr, want_loss: bool = False) -> Optional[torch.Tensor]:
         """One optimiser step on the batch ``features`` fp32 [B, E] (raw image features on the GPU) and ``labels`` [B] at the rate

@@ -30,3 +30,44 @@ def cached_features(who: str, clip_model, loader):
     if not feats:
         raise ValueError(f"{who}: the loader gave no batch")
     return torch.cat(feats), torch.cat(labels)
+
+
+MONITOR_ARGS = ("val", "val_bins", "final_model", "val_criterion", "return_monitor")
+
+
+def validation_set(who: str, clip_model, fit_args: dict):
+    """``fit_args``' ``val_loader`` (an iterable of (preprocessed image, label) batches, run through the frozen image tower once) turned into
+    ``fit_args["val"]``, as ``trainers/coop.py`` does; ``val_loader`` together with ``val`` is refused."""
+    val_loader = fit_args.pop("val_loader", None)
+    if val_loader is not None and fit_args.get("val") is not None:
+        raise ValueError(f"{who}: val_loader and val are two ways to give one validation set")
+    if val_loader is not None:
+        fit_args["val"] = cached_features(who, clip_model, val_loader)
+
+
+def split_monitor_args(who: str, fit_args: dict, n_classes: int, E: int):
+    """The ``transform=`` route: the validation arguments popped out of ``fit_args`` and checked as the cached route checks them.  Returns
+    ``(val or None, val_bins, select, val_criterion, return_monitor)``."""
+    from .. import fitmonitor
+    val, val_bins = fit_args.pop("val", None), fit_args.pop("val_bins", 10)
+    final_model, criterion = fit_args.pop("final_model", "last_step"), fit_args.pop("val_criterion", "accuracy")
+    return_monitor = bool(fit_args.pop("return_monitor", False))
+    fitmonitor.check_args(who, val, val_bins, final_model, criterion)
+    if val is not None:
+        val = fitmonitor.check_val(who, val, E, n_classes)
+    return val, val_bins, final_model == "best_val", criterion, return_monitor
+
+
+def run_with_transform(who: str, state, clip_model, n_classes: int, E: int, loader, transform, epochs, lr, run: dict, fit_args_monitor):
+    """``augment.fit_with_transform`` with the state's ``validate`` behind every epoch when a validation set was given (its features
+    computed once, by the caller, with the test transform).  Returns ``(losses, monitor dict or None)``."""
+    from ..augment import fit_with_transform
+    val, val_bins, select, criterion, return_monitor = fit_args_monitor
+    end_epoch = None
+    if val is not None:
+        vf, vl = val
+        vl = vl.to(vf.device)
+        state.start_monitor(int(epochs), val_bins, select, criterion)
+        end_epoch = lambda e: state.validate(vf, vl, e)
+    losses = fit_with_transform(state, clip_model.image_features_f32, n_classes, loader, transform, epochs, lr, end_epoch=end_epoch, **run)
+    return losses, (state.monitor() if return_monitor else None)

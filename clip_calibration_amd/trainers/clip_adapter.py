@@ -50,7 +50,14 @@ class CustomCLIP(_CoOpCLIP):
         epoch, every batch going transform -> image tower -> ``AdapterFitState.step`` with nothing synchronising until the end
         (``augment.fit_with_transform``).  ``fit_args``: ``epochs`` (200), ``lr`` (0.002), ``lr_per_epoch``, the optimiser's ``momentum``,
         ``dampening``, ``weight_decay``, ``nesterov``, ``views`` (explicit boxes and flips per batch) and ``return_history``; the batch size
-        and the order are the loader's."""
+        and the order are the loader's.
+
+        Validation, on either route: ``val_loader=`` (an iterable of (image, label) batches of test-transformed images, run through the
+        image tower once before the first epoch) or ``val=(val_features, val_labels)``, with ``val_bins``, ``final_model`` ("last_step"
+        or "best_val", the reference's TEST.FINAL_MODEL), ``val_criterion`` and ``return_monitor`` as ``adapterfit.fit_adapter`` takes
+        them.  The cached route validates inside its one library call; with a ``transform`` ``AdapterFitState.validate`` runs behind
+        every epoch.  ``final_model="best_val"`` installs the best epoch's weights into the module."""
+        _fit.validation_set("fit_adapter", self.clip_model, fit_args)
         fit_args.setdefault("ratio", self.ratio)
         fit_args.setdefault("logit_scale", math.log(self.scale))
         fc1, fc2 = self.adapter.fc[0].weight, self.adapter.fc[2].weight
@@ -58,11 +65,13 @@ class CustomCLIP(_CoOpCLIP):
             text = self.text_features()
         if transform is not None:
             from ..adapterfit import AdapterFitState
-            from ..augment import fit_with_transform
             run, epochs, lr = _fit.split_fit_args(fit_args, 200, 0.002)
+            watch = _fit.split_monitor_args("fit_adapter", fit_args, text.shape[0], text.shape[1])
             state = AdapterFitState(text, fc1.detach().float(), fc2.detach().float(), **fit_args)
-            losses = fit_with_transform(state, self.clip_model.image_features_f32, text.shape[0], loader, transform, epochs, lr, **run)
-            fitted = _fit.pack((state.w1, state.w2), losses)
+            losses, monitor = _fit.run_with_transform("fit_adapter", state, self.clip_model, text.shape[0], text.shape[1], loader, transform,
+                                                      epochs, lr, run, watch)
+            fitted = _fit.pack(state.best_weights() if watch[2] else (state.w1, state.w2), losses)
+            fitted = fitted + (monitor,) if monitor is not None else fitted
         else:
             from ..adapterfit import fit_adapter
             feats, labels = _fit.cached_features("fit_adapter", self.clip_model, loader)

@@ -74,18 +74,28 @@ class CustomCLIP(nn.Module):
         ``transform=TrainPreprocess(...)`` is that regime: ``loader`` yields (decoded uint8 images, labels) and is iterated once per
         epoch, every batch going transform -> image tower -> ``TaskResFitState.step`` with nothing synchronising until the end
         (``augment.fit_with_transform``).  ``fit_args``: ``epochs`` (200), ``lr`` (2e-4), ``lr_per_epoch``, ``optimizer`` and its settings,
-        ``views`` (explicit boxes and flips per batch) and ``return_history``; the batch size and the order are the loader's."""
+        ``views`` (explicit boxes and flips per batch) and ``return_history``; the batch size and the order are the loader's.
+
+        Validation, on either route: ``val_loader=`` (an iterable of (image, label) batches of test-transformed images, run through the
+        image tower once before the first epoch) or ``val=(val_features, val_labels)``, with ``val_bins``, ``final_model`` ("last_step"
+        or "best_val", the reference's TEST.FINAL_MODEL), ``val_criterion`` and ``return_monitor`` as ``taskresfit.fit_residuals`` takes
+        them.  The cached route validates inside its one library call; with a ``transform`` ``TaskResFitState.validate`` runs behind
+        every epoch.  ``final_model="best_val"`` installs the best epoch's residuals into the module."""
+        _fit.validation_set("fit_residuals", self.clip_model, fit_args)
         fit_args.setdefault("alpha", self.prompt_learner.alpha)
         fit_args.setdefault("logit_scale", math.log(self.scale))
         res = self.prompt_learner.text_feature_residuals
         base = self.prompt_learner.base_text_features.float()
         if transform is not None:
-            from ..augment import fit_with_transform
             from ..taskresfit import TaskResFitState
             run, epochs, lr = _fit.split_fit_args(fit_args, 200, 2e-4)
+            watch = _fit.split_monitor_args("fit_residuals", fit_args, base.shape[0], base.shape[1])
             state = TaskResFitState(base, res.detach().float(), **fit_args)
-            losses = fit_with_transform(state, self.clip_model.image_features_f32, base.shape[0], loader, transform, epochs, lr, **run)
-            fitted = _fit.pack(state.residuals, losses)
+            losses, monitor = _fit.run_with_transform("fit_residuals", state, self.clip_model, base.shape[0], base.shape[1], loader, transform,
+                                                      epochs, lr, run, watch)
+            fitted = _fit.pack(state.best_residuals() if watch[2] else state.residuals, losses)
+            if monitor is not None:
+                fitted = fitted + (monitor,) if isinstance(fitted, tuple) else (fitted, monitor)
         else:
             from ..taskresfit import fit_residuals
             feats, labels = _fit.cached_features("fit_residuals", self.clip_model, loader)

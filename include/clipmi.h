@@ -502,6 +502,53 @@ int clipmi_taskres_fit(const float* feats, int64_t ld, const int64_t* labels, co
                        const float* lr, int optimizer, int64_t steps_done, float weight_decay, float momentum, float dampening, int nesterov,
                        double beta1, double beta2, double eps, float* losses, void* workspace, size_t workspace_bytes, clipmi_stream_t stream);
 
+/* Per-epoch validation inside the two one-call fits above (reference base_learner.py:41-47; DESIGN.md "Fit monitor").  Additive exports:
+ * the ABI version stays.
+ *
+ * clipmi_adapter_val_logits: logits[i, c] = scale * normalise(ratio relu(relu(f_i W1^T) W2^T) + (1 - ratio) f_i) . text_c for the
+ * validation features feats fp32 [n_val, E] with row stride ld >= E, fp32 [n_val, C] out (row stride C).  One workgroup per row runs the
+ * device function the training step's first launch runs (csrc/adapter_train.hip, adapter_forward_row): the same operations in the same
+ * order with the same rounding points, so these are the logits a training step on those rows would see.
+ * clipmi_taskres_val_logits: logits[i, c] = scale * normalise(f_i) . normalise(base_c + alpha residuals_c), by the training step's own
+ * first launch (taskres_logits_kernel) on the validation rows; a tile normalises its 64 classifier rows once for its 64 validation rows.
+ * Both: plain fp32 vector code, no atomics, a fixed summation order (the same inputs give the same bytes), every output element has one
+ * owner, nothing is read outside [n_val, ld] or written outside [n_val, C], no workspace.  A non-finite feature row gives a row of NaN
+ * and touches no other row.  CLIPMI_ERR_ARG: a null pointer, an fp32 array not 4-byte aligned, logits not 16-byte aligned (as
+ * clipmi_val_score takes them), a non-finite ratio / alpha / scale; CLIPMI_ERR_SHAPE: n_val < 1, C < 2, E < 1, H < 1, ld < E, the
+ * adapter's LDS limit, TaskRes' 4 194 240 rows or classes.
+ *
+ * clipmi_adapter_fit_monitored / clipmi_taskres_fit_monitored: clipmi_adapter_fit / clipmi_taskres_fit -- the same body, the same
+ * launches for the steps, the same fitted bits -- which behind the last step of every epoch e also enqueue: the validation logits of the
+ * weights as they are into monitor_workspace, clipmi_val_score's two launches into record e of `records` (epochs records of
+ * 16 + 16 (n_bins + 1) bytes each, 8-byte aligned) and, when best_block and best_params are given (both or neither), clipmi_best_select's
+ * two launches under `criterion` (0 accuracy, 1 nll).  Nothing waits, nothing is read back.  The selected block is n_floats = 2 E H
+ * floats at w1 for the adapter, which then requires w2 == w1 + H E (one master block [w1 | w2]), and the C E residuals for TaskRes;
+ * either 16-byte aligned, as best_params is.  The optimiser's state is not selected.  val_feats fp32 [n_val, E] with row stride val_ld
+ * >= E, val_labels int64 [n_val] (a label outside [0, C) counts as wrong with a NaN nll).  monitor_workspace (256-byte aligned):
+ * clipmi_*_fit_monitored_workspace_bytes(n_val, C, n_bins) = 4 n_val C for the logits, rounded up to 256, plus clipmi_val_score's and
+ * clipmi_best_select's; 0 for arguments the call refuses.  Every check precedes the first launch.  Beyond the unmonitored call's:
+ * CLIPMI_ERR_ARG: a null or misaligned pointer, n_bins outside 1..64, a criterion other than 0 or 1, a best block without a best slot
+ * or the reverse, a best slot with split or misaligned parameters; CLIPMI_ERR_SHAPE: n_val < 1, val_ld < E; CLIPMI_ERR_WORKSPACE. */
+int clipmi_adapter_val_logits(const float* feats, int64_t ld, const float* text, const float* w1, const float* w2, int n_val, int E, int H, int C,
+                              float ratio, float scale, float* logits, clipmi_stream_t stream);
+int clipmi_taskres_val_logits(const float* feats, int64_t ld, const float* base, const float* residuals, int n_val, int E, int C, float alpha,
+                              float scale, float* logits, clipmi_stream_t stream);
+size_t clipmi_adapter_fit_monitored_workspace_bytes(int n_val, int C, int n_bins);
+int clipmi_adapter_fit_monitored(const float* feats, int64_t ld, const int64_t* labels, const int32_t* order, const float* text, float* w1, float* w2,
+                                 float* m1, float* m2, int n, int E, int H, int C, int batch, int epochs, int drop_last, float ratio, float scale,
+                                 const float* lr, int first_step, float momentum, float dampening, float weight_decay, int nesterov, float* losses,
+                                 void* workspace, size_t workspace_bytes, const float* val_feats, int64_t val_ld, const int64_t* val_labels,
+                                 int n_val, int n_bins, void* records, int criterion, void* best_block, float* best_params,
+                                 void* monitor_workspace, size_t monitor_workspace_bytes, clipmi_stream_t stream);
+size_t clipmi_taskres_fit_monitored_workspace_bytes(int n_val, int C, int n_bins);
+int clipmi_taskres_fit_monitored(const float* feats, int64_t ld, const int64_t* labels, const int32_t* order, const float* base, float* residuals,
+                                 float* state1, float* state2, int n, int E, int C, int batch, int epochs, int drop_last, float alpha, float scale,
+                                 const float* lr, int optimizer, int64_t steps_done, float weight_decay, float momentum, float dampening,
+                                 int nesterov, double beta1, double beta2, double eps, float* losses, void* workspace, size_t workspace_bytes,
+                                 const float* val_feats, int64_t val_ld, const int64_t* val_labels, int n_val, int n_bins, void* records,
+                                 int criterion, void* best_block, float* best_params, void* monitor_workspace, size_t monitor_workspace_bytes,
+                                 clipmi_stream_t stream);
+
 /* The sample-level metrics of the evaluator on the device (vl_evaluator.py:77-82 macro-F1; tools/metrics.py:132-178 PIECE, :212-236
  * AdaptiveECE) -- SURVEY f-1.  Three small kernels; the host turns their outputs into the scalars (clip_calibration_amd.metrics:
  * quantile_edges_from_order_stats, gap_from_groups, macro_f1_from_counts).  These exports are additive: the ABI version does not
