@@ -315,6 +315,11 @@ _SIGNATURES = {
     "clipmi_taskres_fit_monitored": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _f, _vp, _i, _i64, _f, _f, _f, _i,
                                           C.c_double, C.c_double, C.c_double, _vp, _vp, _sz, _vp, _i64, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _sz,
                                           _vp]),
+    "clipmi_val_score_rows": (_i, [_vp, _i64, _vp, _i, _i, _i, _vp, _vp]),
+    "clipmi_val_score_finish_workspace_bytes": (_sz, [_i, _i]),
+    "clipmi_val_score_finish": (_i, [_vp, _i, _i, _vp, _vp, _sz, _vp]),
+    "clipmi_vision_val_chunk_bytes": (_sz, [_vp, _i, _i, _i]),
+    "clipmi_vision_val_chunk": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _vp, _i, _f, _vp, _i, _vp, _vp, _sz, _vp, _sz, _vp]),
 }
 
 for _name, (_res, _args) in _SIGNATURES.items():

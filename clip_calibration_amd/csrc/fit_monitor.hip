@@ -2,6 +2,8 @@
 // epoch record, compare with the best epoch so far and keep that epoch's parameters -- without a host read.  DESIGN.md "Fit monitor".
 //   val_score_rows_kernel     one wave per row, 64 rows per workgroup: max / arg-max (lowest index on a tie), log-sum-exp, nll, confidence and
 //                             its digitize bin; the workgroup's rows are then added in ascending row order into ONE partial record
+//   val_score_chunk_kernel    the same per-row code (score_row) on a chunk of rows, one 16-byte result per row: {conf, nll, hit, bin}
+//   val_score_partials_kernel the 64-row partial records from the row results, in val_score_rows_kernel's order
 //   val_score_reduce_kernel   ONE workgroup: one thread per field of the record adds the partial records in ascending workgroup order
 //   best_decide_kernel        ONE workgroup: strictly better than the best so far?  updates the best block, writes the decision word
 //   best_copy_kernel          grid-stride copy of params into best_params, only when the decision word says "better"
@@ -57,6 +59,55 @@ __device__ inline int conf_bin(float conf, int n_bins) {
   return b;
 }
 
+struct RowResult {    // 16 bytes: what clipmi_val_score_rows writes per row
+  float conf, nll;
+  int32_t hit, bin;
+};
+static_assert(sizeof(RowResult) == 16, "row result layout");
+
+// One wave scores one row `z` of C logits against the label y; every lane calls it, lane 0's return value is the row's result.
+__device__ inline RowResult score_row(const float* __restrict__ z, int64_t y, int C, int n_bins, int lane) {
+  // the maximum and its lowest index; a lane walks its columns in ascending order, so `>` keeps the first of equals
+  float m = -INFINITY;
+  int idx = INT32_MAX, has_nan = 0;
+  for (int c = lane; c < C; c += VS_WAVE) {
+    const float v = z[c];
+    has_nan |= v != v;
+    if (v > m || idx == INT32_MAX) {
+      m = v;
+      idx = c;
+    }
+  }
+  for (int off = 1; off < VS_WAVE; off <<= 1) {
+    const float om = __shfl_xor(m, off, VS_WAVE);
+    const int oi = __shfl_xor(idx, off, VS_WAVE);
+    has_nan |= __shfl_xor(has_nan, off, VS_WAVE);
+    if (om > m || (om == m && oi < idx)) {
+      m = om;
+      idx = oi;
+    }
+  }
+  float sum = 0.f;
+  for (int c = lane; c < C; c += VS_WAVE) sum += expf(z[c] - m);
+  for (int off = 1; off < VS_WAVE; off <<= 1) sum += __shfl_xor(sum, off, VS_WAVE);   // a + b == b + a: every lane holds the same bits
+  RowResult res{0.f, 0.f, 0, 0};
+  if (lane == 0) {
+    const bool in_range = y >= 0 && y < C;   // a label outside [0, C) is never used as an address
+    // lse = m + log(sum), nll = lse - z[y] and conf = exp(m - lse), with the maximum cancelled before the rounding: log(sum) - (z[y] - m), 1 / sum
+    const float log_sum = logf(sum);
+    float nll = in_range ? log_sum - (z[in_range ? y : 0] - m) : NAN;
+    float conf = 1.f / sum;
+    int hit = in_range && (int64_t)idx == y;
+    if (has_nan) {   // a row that holds a NaN counts as wrong, and its NaN reaches nll_sum
+      nll = NAN;
+      conf = NAN;
+      hit = 0;
+    }
+    res = RowResult{conf, nll, hit, conf_bin(conf, n_bins)};
+  }
+  return res;
+}
+
 __global__ __launch_bounds__(VS_THREADS) void val_score_rows_kernel(const float* __restrict__ logits, int64_t ld, const int64_t* __restrict__ labels, int N,
                                                                     int C, int n_bins, char* __restrict__ partials) {
   __shared__ float s_conf[VS_ROWS];
@@ -71,47 +122,12 @@ __global__ __launch_bounds__(VS_THREADS) void val_score_rows_kernel(const float*
       if (lane == 0) s_bin[r] = -1;
       continue;
     }
-    const float* z = logits + row * ld;
-    // the maximum and its lowest index; a lane walks its columns in ascending order, so `>` keeps the first of equals
-    float m = -INFINITY;
-    int idx = INT32_MAX, has_nan = 0;
-    for (int c = lane; c < C; c += VS_WAVE) {
-      const float v = z[c];
-      has_nan |= v != v;
-      if (v > m || idx == INT32_MAX) {
-        m = v;
-        idx = c;
-      }
-    }
-    for (int off = 1; off < VS_WAVE; off <<= 1) {
-      const float om = __shfl_xor(m, off, VS_WAVE);
-      const int oi = __shfl_xor(idx, off, VS_WAVE);
-      has_nan |= __shfl_xor(has_nan, off, VS_WAVE);
-      if (om > m || (om == m && oi < idx)) {
-        m = om;
-        idx = oi;
-      }
-    }
-    float sum = 0.f;
-    for (int c = lane; c < C; c += VS_WAVE) sum += expf(z[c] - m);
-    for (int off = 1; off < VS_WAVE; off <<= 1) sum += __shfl_xor(sum, off, VS_WAVE);   // a + b == b + a: every lane holds the same bits
+    const RowResult res = score_row(logits + row * ld, lane == 0 ? labels[row] : 0, C, n_bins, lane);
     if (lane == 0) {
-      const int64_t y = labels[row];
-      const bool in_range = y >= 0 && y < C;   // a label outside [0, C) is never used as an address
-      // lse = m + log(sum), nll = lse - z[y] and conf = exp(m - lse), with the maximum cancelled before the rounding: log(sum) - (z[y] - m), 1 / sum
-      const float log_sum = logf(sum);
-      float nll = in_range ? log_sum - (z[in_range ? y : 0] - m) : NAN;
-      float conf = 1.f / sum;
-      int hit = in_range && (int64_t)idx == y;
-      if (has_nan) {   // a row that holds a NaN counts as wrong, and its NaN reaches nll_sum
-        nll = NAN;
-        conf = NAN;
-        hit = 0;
-      }
-      s_conf[r] = conf;
-      s_nll[r] = nll;
-      s_hit[r] = hit;
-      s_bin[r] = conf_bin(conf, n_bins);
+      s_conf[r] = res.conf;
+      s_nll[r] = res.nll;
+      s_hit[r] = res.hit;
+      s_bin[r] = res.bin;
     }
   }
   __syncthreads();
@@ -134,6 +150,47 @@ __global__ __launch_bounds__(VS_THREADS) void val_score_rows_kernel(const float*
       q.count += 1;
       q.hits += s_hit[r];
       q.conf_sum += (double)s_conf[r];
+    }
+    ((RecordBin*)(out + sizeof(RecordHead)))[b] = q;
+  }
+}
+
+// A chunk of rows: one wave per row, VS_WAVES rows per workgroup; each row's result goes out as it is, nothing is added here
+__global__ __launch_bounds__(VS_THREADS) void val_score_chunk_kernel(const float* __restrict__ logits, int64_t ld, const int64_t* __restrict__ labels,
+                                                                     int rows, int C, int n_bins, RowResult* __restrict__ row_results) {
+  const int wave = threadIdx.x / VS_WAVE, lane = threadIdx.x % VS_WAVE;
+  const int64_t row = (int64_t)blockIdx.x * VS_WAVES + wave;
+  if (row >= rows) return;   // the same for every lane of the wave
+  const RowResult res = score_row(logits + row * ld, lane == 0 ? labels[row] : 0, C, n_bins, lane);
+  if (lane == 0) row_results[row] = res;
+}
+
+// The partial record of rows [64 k, 64 k + 64) of the N row results, added as val_score_rows_kernel adds its workgroup's rows: thread 0 the
+// head, thread 1 + b bin b, each over the rows in ascending order
+__global__ __launch_bounds__(VS_THREADS) void val_score_partials_kernel(const RowResult* __restrict__ row_results, int N, int n_bins,
+                                                                        char* __restrict__ partials) {
+  __shared__ RowResult s_row[VS_ROWS];
+  const int64_t row0 = (int64_t)blockIdx.x * VS_ROWS;
+  const int have = (int)((int64_t)N - row0 < VS_ROWS ? (int64_t)N - row0 : VS_ROWS);
+  if ((int)threadIdx.x < have) s_row[threadIdx.x] = row_results[row0 + threadIdx.x];
+  __syncthreads();
+  char* out = partials + (size_t)blockIdx.x * record_bytes(n_bins);
+  if (threadIdx.x == 0) {
+    RecordHead h{0, 0, 0.0};
+    for (int r = 0; r < have; ++r) {
+      h.n += 1;
+      h.correct += s_row[r].hit;
+      h.nll_sum += (double)s_row[r].nll;
+    }
+    *(RecordHead*)out = h;
+  } else if ((int)threadIdx.x <= n_bins + 1) {
+    const int b = (int)threadIdx.x - 1;
+    RecordBin q{0, 0, 0.0};
+    for (int r = 0; r < have; ++r) {
+      if (s_row[r].bin != b) continue;
+      q.count += 1;
+      q.hits += s_row[r].hit;
+      q.conf_sum += (double)s_row[r].conf;
     }
     ((RecordBin*)(out + sizeof(RecordHead)))[b] = q;
   }
@@ -216,6 +273,38 @@ int clipmi_val_score(const float* logits, int64_t ld, const int64_t* labels, int
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(val_score_rows_kernel, dim3((unsigned)blocks), dim3(VS_THREADS), 0, s, logits, ld, labels, N, C, n_bins, (char*)workspace);
   if (int rc = check_launch("val_score_rows_kernel")) return rc;
+  hipLaunchKernelGGL(val_score_reduce_kernel, dim3(1), dim3(VS_THREADS), 0, s, (const char*)workspace, blocks, n_bins, (char*)record);
+  return check_launch("val_score_reduce_kernel");
+}
+
+int clipmi_val_score_rows(const float* logits, int64_t ld, const int64_t* labels, int rows, int C, int n_bins, void* row_results, clipmi_stream_t stream) {
+  CLIPMI_REQUIRE(logits && labels && row_results, CLIPMI_ERR_ARG, "val_score_rows: null pointer (logits, labels and the row results are required)");
+  CLIPMI_REQUIRE(((uintptr_t)logits | (uintptr_t)row_results) % 16 == 0, CLIPMI_ERR_ARG, "val_score_rows: logits and the row results must be 16-byte aligned");
+  CLIPMI_REQUIRE((uintptr_t)labels % 8 == 0, CLIPMI_ERR_ARG, "val_score_rows: labels must be 8-byte aligned");
+  CLIPMI_REQUIRE(rows >= 1 && C >= 1 && ld >= C, CLIPMI_ERR_SHAPE, "val_score_rows: rows=%d C=%d ld=%lld (rows, C >= 1, ld >= C)", rows, C, (long long)ld);
+  CLIPMI_REQUIRE(n_bins >= 1 && n_bins <= VS_MAX_BINS, CLIPMI_ERR_ARG, "val_score_rows: n_bins=%d outside 1..%d", n_bins, VS_MAX_BINS);
+  const int64_t blocks = ((int64_t)rows + VS_WAVES - 1) / VS_WAVES;
+  hipLaunchKernelGGL(val_score_chunk_kernel, dim3((unsigned)blocks), dim3(VS_THREADS), 0, (hipStream_t)stream, logits, ld, labels, rows, C, n_bins,
+                     (RowResult*)row_results);
+  return check_launch("val_score_chunk_kernel");
+}
+
+size_t clipmi_val_score_finish_workspace_bytes(int N, int n_bins) { return val_score_bytes(N, n_bins); }
+
+int clipmi_val_score_finish(const void* row_results, int N, int n_bins, void* record, void* workspace, size_t workspace_bytes, clipmi_stream_t stream) {
+  CLIPMI_REQUIRE(row_results && record && workspace, CLIPMI_ERR_ARG,
+                 "val_score_finish: null pointer (the row results, the record and the workspace are required)");
+  CLIPMI_REQUIRE((uintptr_t)row_results % 16 == 0, CLIPMI_ERR_ARG, "val_score_finish: the row results must be 16-byte aligned");
+  CLIPMI_REQUIRE((uintptr_t)record % 8 == 0, CLIPMI_ERR_ARG, "val_score_finish: the record must be 8-byte aligned");
+  CLIPMI_REQUIRE((uintptr_t)workspace % 256 == 0, CLIPMI_ERR_ARG, "val_score_finish: the workspace must be 256-byte aligned");
+  CLIPMI_REQUIRE(N >= 1, CLIPMI_ERR_SHAPE, "val_score_finish: N=%d (>= 1)", N);
+  CLIPMI_REQUIRE(n_bins >= 1 && n_bins <= VS_MAX_BINS, CLIPMI_ERR_ARG, "val_score_finish: n_bins=%d outside 1..%d", n_bins, VS_MAX_BINS);
+  CLIPMI_REQUIRE(workspace_bytes >= val_score_bytes(N, n_bins), CLIPMI_ERR_WORKSPACE, "val_score_finish: workspace of %zu bytes, %zu needed", workspace_bytes,
+                 val_score_bytes(N, n_bins));
+  const int64_t blocks = score_blocks(N);
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(val_score_partials_kernel, dim3((unsigned)blocks), dim3(VS_THREADS), 0, s, (const RowResult*)row_results, N, n_bins, (char*)workspace);
+  if (int rc = check_launch("val_score_partials_kernel")) return rc;
   hipLaunchKernelGGL(val_score_reduce_kernel, dim3(1), dim3(VS_THREADS), 0, s, (const char*)workspace, blocks, n_bins, (char*)record);
   return check_launch("val_score_reduce_kernel");
 }

@@ -1042,4 +1042,41 @@ int clipmi_vpt_train_step_scaled(clipmi_model* m, const clipmi_vision_dgrad* wt,
                         stash_bytes, (hipStream_t)stream);
 }
 
+// ---- one chunk of validation images (DESIGN.md "Fit monitor", "The image-tower fits"): the training forward at `prompts`, clipmi_l2_normalize,
+// clipmi_logits against the normalised text features and clipmi_val_score_rows, the four calls enqueued by one.  Workspace: the tower's | features
+// fp32 [B, E] | normalised features fp32 [B, E] | logits fp32 [B, C], each part 256-byte aligned
+size_t clipmi_vision_val_chunk_bytes(const clipmi_model* m, int B, int n_ctx, int C) {
+  size_t ws = 0;
+  if (!m || B < 1 || C < 1 || clipmi_vision_train_bytes(m, B, n_ctx, &ws, nullptr) != CLIPMI_OK) return 0;
+  return ws + 2 * align256((size_t)B * m->g.embed_dim * 4) + align256((size_t)B * C * 4);
+}
+
+int clipmi_vision_val_chunk(clipmi_model* m, const void* image, int image_dtype, int B, const float* prompts, int n_ctx, int depth, const float* text_n, int C,
+                            float scale, const int64_t* labels, int n_bins, void* row_results, void* workspace, size_t workspace_bytes, void* stash,
+                            size_t stash_bytes, clipmi_stream_t stream) {
+  const char* who = "vision_val_chunk";
+  hipStream_t s = (hipStream_t)stream;
+  CLIPMI_REQUIRE(B >= 1 && C >= 1, CLIPMI_ERR_SHAPE, "%s: B=%d C=%d (both >= 1)", who, B, C);
+  size_t tower = 0;
+  if (int rc = clipmi_vision_train_bytes(m, B, n_ctx, &tower, nullptr)) return rc;
+  const size_t need = clipmi_vision_val_chunk_bytes(m, B, n_ctx, C);
+  CLIPMI_REQUIRE(workspace_bytes >= need, CLIPMI_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, need);
+  if (int rc = check_vision_train_call(who, m, B, n_ctx, depth, workspace, tower, stash, stash_bytes)) return rc;
+  CLIPMI_REQUIRE(image && prompts && text_n && labels && row_results, CLIPMI_ERR_ARG, "%s: null pointer", who);
+  CLIPMI_REQUIRE(image_dtype == CLIPMI_F16 || image_dtype == CLIPMI_F32, CLIPMI_ERR_ARG, "%s: image dtype %d", who, image_dtype);
+  CLIPMI_REQUIRE(((uintptr_t)text_n | (uintptr_t)row_results) % 16 == 0, CLIPMI_ERR_ARG, "%s: the text features and the row results must be 16-byte aligned", who);
+  CLIPMI_REQUIRE((uintptr_t)labels % 8 == 0, CLIPMI_ERR_ARG, "%s: labels must be 8-byte aligned", who);
+  CLIPMI_REQUIRE(n_bins >= 1 && n_bins <= 64, CLIPMI_ERR_ARG, "%s: n_bins=%d outside 1..64", who, n_bins);
+  CLIPMI_REQUIRE(std::isfinite(scale), CLIPMI_ERR_ARG, "%s: scale=%g (finite)", who, scale);
+  const int E = m->g.embed_dim;
+  Carver c(static_cast<char*>(workspace) + tower);
+  float* feats = c.take<float>((size_t)B * E * 4);
+  float* feats_n = c.take<float>((size_t)B * E * 4);
+  float* logits = c.take<float>((size_t)B * C * 4);
+  if (int rc = run_vision_train_forward(m, image, image_dtype, B, prompts, n_ctx, depth, feats, workspace, stash, s)) return rc;
+  if (int rc = launch_l2_normalize(feats, CLIPMI_F32, feats_n, B, E, s)) return rc;
+  if (int rc = clipmi_logits(feats_n, text_n, scale, nullptr, logits, nullptr, nullptr, B, C, E, stream)) return rc;
+  return clipmi_val_score_rows(logits, C, labels, B, C, n_bins, row_results, stream);
+}
+
 }  // extern "C"

@@ -42,7 +42,7 @@ from typing import Dict, Optional, Sequence
 import numpy as np
 import torch
 
-from . import _lib, fitloop, ops
+from . import _lib, fitloop, fitmonitor, ops
 from ._lib import check, lib
 from . import coopfit, vptfit
 from .coopfit import DYNAMIC, _BlockScaler, _check_grad_scale, _is_dynamic, _scale_args
@@ -175,8 +175,8 @@ class _Towers:
     def deep_ptr(self, block: torch.Tensor):
         return block.data_ptr() + 4 * self.n_ctx * self.Dt if self.depth > 1 else None
 
-    def forward(self, block: torch.Tensor, images: torch.Tensor):
-        """(text features [C, E], image features [B, E]) at the block: couple, text forward, image forward."""
+    def text_forward(self, block: torch.Tensor) -> torch.Tensor:
+        """The text half of ``forward``: couple (the image tower's prompts into ``self.vis``), then the text features [C, E]."""
         t, m = self.text, self.model
         couple(block, self.n_ctx, self.depth, self.Dt, self.Dv, self.vis)
         with m._launch_lock:
@@ -184,7 +184,11 @@ class _Towers:
                                                      t.rows, self.deep_ptr(block), self.depth - 1, t.text.data_ptr(), t.ws.data_ptr(), t.ws.numel(),
                                                      t.stash.data_ptr(), t.stash.numel(), _lib.CALL_DEFAULT, ops._stream()),
                   "clipmi_text_encoder_train_deep")
-        return t.text, self.vision.forward(images, self.vis)
+        return t.text
+
+    def forward(self, block: torch.Tensor, images: torch.Tensor):
+        """(text features [C, E], image features [B, E]) at the block: couple, text forward, image forward."""
+        return self.text_forward(block), self.vision.forward(images, self.vis)
 
     def backward(self, d_text: torch.Tensor, d_feats: torch.Tensor, stats_text: Optional[torch.Tensor] = None, stats_vision: Optional[torch.Tensor] = None):
         """(d_embed, d_deep, d_vis): the text tower's backward, then the image tower's."""
@@ -248,9 +252,12 @@ def features(model, learner_params: Dict[str, torch.Tensor], images: torch.Tenso
     return text.clone(), feats.clone()
 
 
-class MaPLeFitState:
+class MaPLeFitState(fitmonitor.ImageMonitored):
     """The training state of MaPLe's prompt learner: the fp32 master ``block``, SGD's momentum buffer, both towers' stashes and the number
-    of steps taken.  ``step`` enqueues one forward, backward and update and does not synchronise.  ``params()`` names the block's views."""
+    of steps taken.  ``step`` enqueues one forward, backward and update and does not synchronise.  ``params()`` names the block's views.
+    ``validate`` scores validation images on the device (``start_monitor``, ``monitor``, ``best_params``, ``val_row_results``; DESIGN.md
+    "Fit monitor", "The image-tower fits")."""
+    _who = "MaPLeFitState"
 
     def __init__(self, model, tokenized_prompts, learner_params: Dict[str, torch.Tensor], logit_scale: float = 4.6052, momentum: float = 0.9,
                  dampening: float = 0.0, nesterov: bool = False, weight_decay: float = 5e-4, grad_scale: float = DEFAULT_GRAD_SCALE,
@@ -270,9 +277,28 @@ class MaPLeFitState:
         self._scaler = _BlockScaler(self.scaler, model.device) if self.dynamic else None
         self._scaled_grad = torch.empty_like(self.block) if self.dynamic else None    # scale * gradient, as clipmi_maple_step leaves it
 
-    def params(self) -> Dict[str, torch.Tensor]:
+    def params(self, block: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
         t = self.towers
-        return unpack_block(self.block, t.n_ctx, t.depth, t.Dt, t.Dv)
+        return unpack_block(self.block if block is None else block, t.n_ctx, t.depth, t.Dt, t.Dv)
+
+    def _master(self) -> torch.Tensor:
+        return self.block
+
+    def validate(self, val_images_or_loader, val_labels, epoch: int, val_batch_size: int = 32, one_call: bool = True) -> None:
+        """Enqueue one validation of the current master block into slot ``epoch`` of the device history; no host read.  The text side's
+        training forward runs ONCE on the block (couple, deep text prompts), its features are normalised, and the validation images --
+        [N_val, 3, R, R] on the GPU with ``val_labels``, in chunks of ``val_batch_size``, or a sized iterable of (images, labels) batches
+        on the GPU with None -- run through the image tower's training forward at the coupled prompts, chunk by chunk
+        (``VPTFitState.validate`` has the rest: row results, finish, selection of the whole block, labels)."""
+        who = "MaPLeFitState.validate"
+        mon, tw = self._monitor_for(epoch), self.towers
+        text_n = ops.l2_normalize(tw.text_forward(self.block))
+        mon.validate(who, tw.vision, tw.vis, text_n, self.scale, val_images_or_loader, val_labels, epoch, val_batch_size, self.block, one_call)
+
+    def best_params(self) -> Dict[str, torch.Tensor]:
+        """The best slot on the device under ``params()``' names: the block of the best epoch so far, or the block ``start_monitor`` saw
+        while no epoch has been taken."""
+        return self.params(self._best_block("best_params"))
 
     def scaler_state(self) -> dict:
         """The dynamic scale's block as ``dict(scale, growth_tracker, skipped_steps, applied_steps, found_inf)`` (``found_inf``: of the
@@ -363,7 +389,9 @@ def fit_prompt_learner(images_or_loader, labels, model, tokenized_prompts, learn
                        depth: int = 9, logit_scale: float = 4.6052, lr: float = 0.0035, epochs: int = 5, batch_size: int = 4, momentum: float = 0.9,
                        dampening: float = 0.0, weight_decay: float = 5e-4, nesterov: bool = False, grad_scale: float = DEFAULT_GRAD_SCALE,
                        seq_rows: Optional[int] = None, lr_per_epoch: Optional[Sequence[float]] = None, drop_last: bool = False,
-                       return_history: bool = False, class_token_position: str = "end", scaler: Optional[dict] = None):
+                       return_history: bool = False, class_token_position: str = "end", scaler: Optional[dict] = None, val=None,
+                       val_batch_size: int = 32, val_bins: int = 10, final_model: str = "last_step", val_criterion: str = "accuracy",
+                       return_monitor: bool = False):
     """Train MaPLe's prompt learner starting from ``learner_params`` (not modified; None = ``init_learner_params(model, n_ctx, depth)``):
     ``epochs`` passes of ``torch.optim.SGD(lr, momentum, dampening, weight_decay, nesterov)`` over the whole parameter list.
     ``images_or_loader`` is a tensor of preprocessed images [N, 3, R, R] with ``labels`` [N], cut into batches of ``batch_size`` in order
@@ -373,8 +401,13 @@ def fit_prompt_learner(images_or_loader, labels, model, tokenized_prompts, learn
     device (views of one block), or ``(params, per-step batch losses)`` with ``return_history``.  The model's prompt learner is NOT
     written: ``trainers.maple.CustomCLIP.fit_prompt_learner`` does that.  ``grad_scale="dynamic"`` with ``scaler`` (module docstring): a
     step that overflows fp16 is skipped on the device and the scale adapts; the history keeps one loss per step, skipped steps included,
-    and the run still synchronises once."""
+    and the run still synchronises once.
+
+    ``val=(val_images_or_loader, val_labels)``, ``val_batch_size``, ``val_bins``, ``final_model``, ``val_criterion`` and
+    ``return_monitor`` as ``vptfit.fit_prompts`` takes them: behind every epoch ``MaPLeFitState.validate`` scores the block on the device;
+    the fitted parameters are bit for bit those of the same call without ``val``; "best_val" returns the best epoch's parameters."""
     who = "fit_prompt_learner"
+    fitmonitor.check_image_args(who, val, val_batch_size, val_bins, final_model, val_criterion)
     epochs = int(epochs)
     if epochs < 0:
         raise ValueError(f"{who}: epochs={epochs} (>= 0)")
@@ -384,5 +417,11 @@ def fit_prompt_learner(images_or_loader, labels, model, tokenized_prompts, learn
                           class_token_position, scaler)
     batches = fitloop.cut_batches(who, images_or_loader, labels, state.C, batch_size, drop_last, model.device)
     _, lr_steps = fitloop.schedule(who, lr, epochs, lr_per_epoch, len(batches), model.device)
-    history = fitloop.run_batches(lambda e, k, b, r, want: state.step(b[0], b[1], r, want_loss=want), batches, epochs, lr_steps, return_history)
-    return (state.params(), history) if return_history else state.params()
+    end_epoch = None
+    if val is not None and epochs * len(batches) > 0:
+        state.start_monitor(epochs, val_bins, val_criterion, final_model == "best_val")
+        end_epoch = lambda e: state.validate(val[0], val[1], e, val_batch_size)
+    history = fitloop.run_batches(lambda e, k, b, r, want: state.step(b[0], b[1], r, want_loss=want), batches, epochs, lr_steps, return_history, end_epoch)
+    out = state.best_params() if final_model == "best_val" and end_epoch is not None else state.params()
+    return fitmonitor.pack(out, history, (state.monitor() if end_epoch is not None else fitmonitor.empty_monitor(val_bins)) if return_monitor else None,
+                           return_history, return_monitor)

@@ -1195,6 +1195,80 @@ def val_score(logits: torch.Tensor, labels: torch.Tensor, n_bins: int, record: O
     return record
 
 
+VAL_ROW_BYTES = 16     # one row result of clipmi_val_score_rows: {float conf, float nll, int32 hit, int32 bin}
+_ROW_DTYPE = np.dtype([("conf", "<f4"), ("nll", "<f4"), ("hit", "<i4"), ("bin", "<i4")])
+
+
+def new_val_row_results(N: int, device) -> torch.Tensor:
+    """The row-result buffer of a validation set of ``N`` rows: zeroed uint8 [N, 16] on ``device``."""
+    return torch.zeros(int(N), VAL_ROW_BYTES, dtype=torch.uint8, device=device)
+
+
+def decode_val_row_results(row_results) -> np.ndarray:
+    """Row results (uint8 [N, 16] tensor or array) as a structured array with ``conf``, ``nll``, ``hit``, ``bin``.  A tensor on the GPU is
+    read back: it synchronises."""
+    raw = row_results.detach().cpu().numpy() if isinstance(row_results, torch.Tensor) else np.asarray(row_results)
+    return np.ascontiguousarray(raw, dtype=np.uint8).reshape(-1, VAL_ROW_BYTES).view(_ROW_DTYPE)[:, 0]
+
+
+def _row_results(who: str, row_results, N: int, row0: int = 0):
+    if not (isinstance(row_results, torch.Tensor) and row_results.is_cuda and row_results.dtype == torch.uint8 and row_results.is_contiguous()
+            and row_results.dim() == 2 and row_results.shape[1] == VAL_ROW_BYTES and row_results.data_ptr() % 16 == 0):
+        raise TypeError(f"{who}: row_results must be a contiguous uint8 [rows, {VAL_ROW_BYTES}] tensor on the GPU (new_val_row_results)")
+    if isinstance(row0, bool) or int(row0) != row0 or row0 < 0 or row0 + N > row_results.shape[0]:
+        raise ValueError(f"{who}: rows {row0} .. {row0 + N} lie outside the {row_results.shape[0]} row results")
+    return row_results.data_ptr() + VAL_ROW_BYTES * int(row0)
+
+
+def val_score_rows(logits: torch.Tensor, labels: torch.Tensor, n_bins: int, row_results: Optional[torch.Tensor] = None, row0: int = 0) -> torch.Tensor:
+    """clipmi_val_score_rows: a chunk of fp32 ``logits`` [rows, C] (the rows may be a column slice) against ``labels`` int64 [rows], the
+    chunk's own, into ``row_results[row0 : row0 + rows]`` (uint8 [N, 16] on the GPU, ``new_val_row_results``; made for the chunk alone when
+    None) -- per row ``val_score``'s code: confidence, nll, hit and confidence bin.  Nothing else is written and nothing is read back.
+    ``val_score_finish`` folds the rows of every chunk into the record.  Returns ``row_results``."""
+    who = "val_score_rows"
+    n_bins = _val_bins(who, n_bins)
+    if not isinstance(logits, torch.Tensor) or logits.dim() != 2 or logits.shape[0] < 1 or logits.shape[1] < 1:
+        raise ValueError(f"{who}: logits {tuple(getattr(logits, 'shape', ()))} must be [rows >= 1, C >= 1]")
+    if not logits.is_cuda:
+        raise RuntimeError(f"clipmi: `logits` must be a tensor on the GPU (got {logits.device}); the HIP path has no CPU fallback")
+    if logits.dtype != torch.float32:
+        raise TypeError(f"clipmi: `logits` has dtype {logits.dtype}, expected torch.float32")
+    if logits.stride(1) != 1 or logits.stride(0) < logits.shape[1]:
+        logits = logits.contiguous()
+    if logits.data_ptr() % 16:      # a row slice that starts off a 16-byte boundary: a copy of its own (contiguous() would return the slice)
+        logits = logits.clone(memory_format=torch.contiguous_format)
+    labels = _dev(labels, "labels", (torch.int64,))
+    N, Cn = logits.shape
+    if labels.shape != (N,):
+        raise ValueError(f"{who}: {N} rows need {N} labels, got {tuple(labels.shape)}")
+    if row_results is None:
+        row_results = new_val_row_results(row0 + N, logits.device)
+    pr = _row_results(who, row_results, N, row0)
+    check(lib.clipmi_val_score_rows(logits.data_ptr(), logits.stride(0), labels.data_ptr(), N, Cn, n_bins, pr, _stream()), "clipmi_val_score_rows")
+    return row_results
+
+
+def val_score_finish(row_results: torch.Tensor, n_bins: int, record: Optional[torch.Tensor] = None,
+                     workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """clipmi_val_score_finish: every row of ``row_results`` (uint8 [N, 16] on the GPU, filled by ``val_score_rows``) into one epoch record,
+    byte for byte the record ``val_score`` writes for the whole [N, C] logits, however the rows were cut into chunks.  ``record`` and
+    ``workspace`` as ``val_score`` takes them.  Returns the record."""
+    who = "val_score_finish"
+    n_bins = _val_bins(who, n_bins)
+    N = int(row_results.shape[0]) if isinstance(row_results, torch.Tensor) and row_results.dim() == 2 else 0
+    if N < 1:
+        raise ValueError(f"{who}: row_results {tuple(getattr(row_results, 'shape', ()))} must be [N >= 1, {VAL_ROW_BYTES}]")
+    pr = _row_results(who, row_results, N)
+    if record is None:
+        record = new_val_records(1, n_bins, row_results.device)[0]
+    prec = _monitor_bytes(who, record, "record", val_record_bytes(n_bins))
+    need = lib.clipmi_val_score_finish_workspace_bytes(N, n_bins)
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=row_results.device)
+    check(lib.clipmi_val_score_finish(pr, N, n_bins, prec, workspace.data_ptr(), workspace.numel(), _stream()), "clipmi_val_score_finish")
+    return record
+
+
 def best_select(record: torch.Tensor, best_block: torch.Tensor, criterion, epoch: int, params: torch.Tensor, best_params: torch.Tensor,
                 workspace: Optional[torch.Tensor] = None) -> None:
     """clipmi_best_select: when the epoch ``record`` is strictly better than ``best_block``'s (``criterion`` "accuracy": more correct

@@ -47,7 +47,7 @@ from typing import Dict, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import _lib, fitloop, ops
+from . import _lib, fitloop, fitmonitor, ops
 from ._lib import check, lib
 from . import coopfit, vptfit
 from .coopfit import DYNAMIC, _BlockScaler, _check_grad_scale, _is_dynamic, _scale_args
@@ -260,15 +260,19 @@ class _Towers:
                                           _lib.CALL_STREAM_F32, ops._stream()), "clipmi_encode_image")
         return self.zs[:B]
 
-    def forward(self, block: torch.Tensor, images: torch.Tensor):
-        """(text features [C, E], image features [B, E]) at the block: text forward with deep prompts, image forward."""
+    def text_forward(self, block: torch.Tensor) -> torch.Tensor:
+        """The text half of ``forward``: the text features [C, E] at the block."""
         t, m = self.text, self.model
         deep = block.data_ptr() + 4 * self.nt * self.Dt if self.dt > 1 else None
         with m._launch_lock:
             check(lib.clipmi_text_encoder_train_deep(m._handle, t.base.data_ptr(), _DT[t.base.dtype], block.data_ptr(), self.nt, 0, t.eot.data_ptr(), t.C,
                                                      t.rows, deep, self.dt - 1, t.text.data_ptr(), t.ws.data_ptr(), t.ws.numel(), t.stash.data_ptr(),
                                                      t.stash.numel(), _lib.CALL_DEFAULT, ops._stream()), "clipmi_text_encoder_train_deep")
-        return t.text, self.vision.forward(images, block[self.text_floats:])
+        return t.text
+
+    def forward(self, block: torch.Tensor, images: torch.Tensor):
+        """(text features [C, E], image features [B, E]) at the block: text forward with deep prompts, image forward."""
+        return self.text_forward(block), self.vision.forward(images, block[self.text_floats:])
 
     def backward(self, d_text: torch.Tensor, d_feats: torch.Tensor, stats_text: Optional[torch.Tensor] = None, stats_vision: Optional[torch.Tensor] = None):
         """(d_embed, d_deep, d_vis): the text tower's backward, then the image tower's."""
@@ -341,10 +345,12 @@ def gradients(model, params: Dict[str, torch.Tensor], images: torch.Tensor, labe
     return out
 
 
-class PromptSRCFitState:
+class PromptSRCFitState(fitmonitor.ImageMonitored):
     """The training state of PromptSRC's (or IVLP's) prompts: the fp32 master ``block``, SGD's momentum buffer, GPA's running sum, both
     towers' stashes and the number of steps taken.  ``step`` enqueues one forward, backward and update, ``end_epoch`` one accumulation;
-    neither synchronises.  ``params()`` names the block's views."""
+    neither synchronises.  ``params()`` names the block's views.  ``validate`` scores validation images on the device
+    (``start_monitor``, ``monitor``, ``best_params``, ``val_row_results``; DESIGN.md "Fit monitor", "The image-tower fits")."""
+    _who = "PromptSRCFitState"
 
     def __init__(self, model, tokenized_prompts, params: Dict[str, torch.Tensor], teacher: torch.Tensor, logit_scale: float = 4.6052,
                  w_text: float = 25.0, w_image: float = 10.0, w_logit: float = 1.0, momentum: float = 0.9, dampening: float = 0.0, nesterov: bool = False,
@@ -371,6 +377,27 @@ class PromptSRCFitState:
 
     def params(self, block: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
         return unpack_block(self.block if block is None else block, *self.towers.shape())
+
+    def _master(self) -> torch.Tensor:
+        return self.block
+
+    def validate(self, val_images_or_loader, val_labels, epoch: int, val_batch_size: int = 32, one_call: bool = True) -> None:
+        """Enqueue one validation of the master block as it stands into slot ``epoch`` of the device history; no host read.  The text
+        side's training forward runs ONCE on the block, its features are normalised, and the validation images -- [N_val, 3, R, R] on the
+        GPU with ``val_labels``, in chunks of ``val_batch_size``, or a sized iterable of (images, labels) batches on the GPU with None --
+        run through the image tower's training forward at the block's visual prompts, chunk by chunk (``VPTFitState.validate`` has the
+        rest: row results, finish, selection of the whole block, labels).  The frozen tower and the teacher take no part: validation
+        scores the prompted model's logits.  After ``apply_gpa`` the block is the aggregate, and that is what is scored."""
+        who = "PromptSRCFitState.validate"
+        mon, tw = self._monitor_for(epoch), self.towers
+        text_n = ops.l2_normalize(tw.text_forward(self.block))
+        mon.validate(who, tw.vision, self.block[tw.text_floats:], text_n, self.scale, val_images_or_loader, val_labels, epoch, val_batch_size,
+                     self.block, one_call)
+
+    def best_params(self) -> Dict[str, torch.Tensor]:
+        """The best slot on the device under ``params()``' names: the block of the best epoch so far, or the block ``start_monitor`` saw
+        while no epoch has been taken.  GPA's running sum, the optimiser state and the scaler block are not part of it."""
+        return self.params(self._best_block("best_params"))
 
     def scaler_state(self) -> dict:
         """The dynamic scale's block as ``dict(scale, growth_tracker, skipped_steps, applied_steps, found_inf)`` (``found_inf``: of the
@@ -481,7 +508,8 @@ def fit_prompts(images_or_loader, labels, model, tokenized_prompts, teacher: tor
                 dampening: float = 0.0, weight_decay: float = 5e-4, nesterov: bool = False, w_text: float = 25.0, w_image: float = 10.0,
                 w_logit: float = 1.0, gpa=(30.0, 30.0), grad_scale: float = DEFAULT_GRAD_SCALE, seq_rows: Optional[int] = None,
                 lr_per_epoch: Optional[Sequence[float]] = None, drop_last: bool = False, return_history: bool = False, one_call: bool = False,
-                class_token_position: str = "end", scaler: Optional[dict] = None):
+                class_token_position: str = "end", scaler: Optional[dict] = None, val=None, val_batch_size: int = 32, val_bins: int = 10,
+                final_model: str = "last_step", val_criterion: str = "accuracy", return_monitor: bool = False):
     """Train the prompts starting from ``params`` (not modified; None = ``init_params(model)``): ``epochs`` passes of
     ``torch.optim.SGD(lr, momentum, dampening, weight_decay, nesterov)`` over the whole parameter list on PromptSRC's loss.
     ``images_or_loader`` is a tensor of preprocessed images [N, 3, R, R] with ``labels`` [N], cut into batches of ``batch_size`` in order
@@ -493,8 +521,15 @@ def fit_prompts(images_or_loader, labels, model, tokenized_prompts, teacher: tor
     total losses)`` with ``return_history``.  The model's parameters are NOT written: ``trainers.promptsrc.CustomCLIP.fit_prompts`` does
     that.  ``grad_scale="dynamic"`` with ``scaler`` (module docstring; both methods): a step that overflows fp16 is skipped on the device
     and the scale adapts; the history keeps one loss per step, skipped steps included, GPA aggregates whatever the block holds at the end
-    of an epoch, and the run still synchronises once."""
+    of an epoch, and the run still synchronises once.
+
+    ``val=(val_images_or_loader, val_labels)``, ``val_batch_size``, ``val_bins``, ``final_model``, ``val_criterion`` and
+    ``return_monitor`` as ``vptfit.fit_prompts`` takes them.  Behind every epoch the GPA work comes first and the validation second, the
+    reference's order (promptsrc.py:321-336 inside ``forward_backward``, ahead of Dassl's ``after_epoch``): epochs 0 .. E-2 score the
+    block the epoch trained, the last epoch scores the aggregate GPA has just loaded.  The fitted parameters are bit for bit those of the
+    same call without ``val``; "best_val" returns the best epoch's block (the aggregate when the last epoch is the best)."""
     who = "fit_prompts"
+    fitmonitor.check_image_args(who, val, val_batch_size, val_bins, final_model, val_criterion)
     epochs = int(epochs)
     if epochs < 0:
         raise ValueError(f"{who}: epochs={epochs} (>= 0)")
@@ -506,14 +541,24 @@ def fit_prompts(images_or_loader, labels, model, tokenized_prompts, teacher: tor
                               grad_scale, seq_rows, method, class_token_position, scaler)
     weights = None if method == "ivlp" else _gpa_for(who, gpa, epochs)
 
-    def end_epoch(e: int) -> None:
-        """GPA: the epoch's weighted block joins the running sum; behind the last epoch the sum replaces the parameters."""
-        state.end_epoch(float(weights[e]))
-        if e == epochs - 1:
-            state.apply_gpa()
-
     batches = fitloop.cut_batches(who, images_or_loader, labels, state.C, batch_size, drop_last, model.device)
+    monitored = val is not None and epochs * len(batches) > 0
+
+    def end_epoch(e: int) -> None:
+        """GPA: the epoch's weighted block joins the running sum; behind the last epoch the sum replaces the parameters.  Then the
+        validation, of the block as it stands."""
+        if weights is not None:
+            state.end_epoch(float(weights[e]))
+            if e == epochs - 1:
+                state.apply_gpa()
+        if monitored:
+            state.validate(val[0], val[1], e, val_batch_size)
+
+    if monitored:
+        state.start_monitor(epochs, val_bins, val_criterion, final_model == "best_val")
     _, lr_steps = fitloop.schedule(who, lr, epochs, lr_per_epoch, len(batches), model.device)
     history = fitloop.run_batches(lambda e, k, b, r, want: state.step(b[0], b[1], r, want_loss=want, one_call=one_call), batches, epochs, lr_steps, return_history,
-                                  None if weights is None else end_epoch)
-    return (state.params(), history) if return_history else state.params()
+                                  None if weights is None and not monitored else end_epoch)
+    out = state.best_params() if final_model == "best_val" and monitored else state.params()
+    return fitmonitor.pack(out, history, (state.monitor() if monitored else fitmonitor.empty_monitor(val_bins)) if return_monitor else None,
+                           return_history, return_monitor)

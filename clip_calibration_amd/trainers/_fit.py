@@ -71,3 +71,52 @@ def run_with_transform(who: str, state, clip_model, n_classes: int, E: int, load
         end_epoch = lambda e: state.validate(vf, vl, e)
     losses = fit_with_transform(state, clip_model.image_features_f32, n_classes, loader, transform, epochs, lr, end_epoch=end_epoch, **run)
     return losses, (state.monitor() if return_monitor else None)
+
+
+def image_validation_set(who: str, fit_args: dict) -> None:
+    """The image-tower fits: ``fit_args``' ``val_loader`` (a sized iterable of (test-transformed images, labels) batches on the GPU,
+    iterated once per validated epoch -- the prompts change the image features every epoch, so nothing is cached) turned into
+    ``fit_args["val"] = (val_loader, None)``; ``val_loader`` together with ``val`` is refused."""
+    val_loader = fit_args.pop("val_loader", None)
+    if val_loader is not None and fit_args.get("val") is not None:
+        raise ValueError(f"{who}: val_loader and val are two ways to give one validation set")
+    if val_loader is not None:
+        fit_args["val"] = (val_loader, None)
+
+
+def split_image_monitor_args(who: str, fit_args: dict) -> dict:
+    """The ``transform=`` route of the image-tower fits: the validation arguments popped out of ``fit_args`` and checked as the fit
+    functions check them.  The validation images are the caller's test-transformed ones; the train transform never touches them."""
+    from .. import fitmonitor
+    w = {"val": fit_args.pop("val", None), "val_batch_size": fit_args.pop("val_batch_size", 32), "val_bins": fit_args.pop("val_bins", 10),
+         "final_model": fit_args.pop("final_model", "last_step"), "val_criterion": fit_args.pop("val_criterion", "accuracy"),
+         "return_monitor": bool(fit_args.pop("return_monitor", False))}
+    fitmonitor.check_image_args(who, w["val"], w["val_batch_size"], w["val_bins"], w["final_model"], w["val_criterion"])
+    return w
+
+
+def image_end_epoch(state, watch: dict, epochs: int, steps: int, before=None):
+    """``end_epoch`` for ``augment.fit_with_transform``: ``before(e)`` (PromptSRC's GPA work), then the state's ``validate`` when a
+    validation set was given and the run has steps; None when there is neither."""
+    monitored = watch["val"] is not None and int(epochs) * steps > 0
+    if monitored:
+        state.start_monitor(int(epochs), watch["val_bins"], watch["val_criterion"], watch["final_model"] == "best_val")
+    if not monitored and before is None:
+        return None, False
+
+    def end_epoch(e: int) -> None:
+        if before is not None:
+            before(e)
+        if monitored:
+            state.validate(watch["val"][0], watch["val"][1], e, watch["val_batch_size"])
+    return end_epoch, monitored
+
+
+def pack_monitored(state, fitted, losses, watch: dict, monitored: bool):
+    """``pack`` with the monitor's dict behind the history when ``return_monitor`` was asked for."""
+    from .. import fitmonitor
+    out = pack(fitted, losses)
+    if not watch["return_monitor"]:
+        return out
+    mon = state.monitor() if monitored else fitmonitor.empty_monitor(watch["val_bins"])
+    return out + (mon,) if isinstance(out, tuple) else (out, mon)

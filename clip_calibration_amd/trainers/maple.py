@@ -87,18 +87,28 @@ class CustomCLIP(_CoOpCLIP):
         ``lr`` (0.0035), ``lr_per_epoch``, the optimiser's ``momentum``, ``dampening``, ``weight_decay``, ``nesterov``, ``grad_scale``,
         ``seq_rows``, ``views`` (with a transform) and ``return_history``; the batch size and the order are the loader's.
         ``grad_scale="dynamic"`` with ``scaler=dict(init_scale, growth_factor, backoff_factor, growth_interval)``: the device-side loss
-        scale (``maplefit``'s module docstring)."""
+        scale (``maplefit``'s module docstring).
+
+        Validation, on either route: ``val_loader=`` (a sized iterable of (test-transformed images, labels) batches on the GPU, iterated
+        once per epoch) or ``val=(val_images_or_loader, val_labels)``, with ``val_batch_size``, ``val_bins``, ``final_model``
+        ("last_step" or "best_val", the reference's TEST.FINAL_MODEL), ``val_criterion`` and ``return_monitor`` as
+        ``maplefit.fit_prompt_learner`` takes them.  Validation images go through the test transform, never through ``transform``.
+        ``final_model="best_val"`` installs the best epoch's parameters."""
         import math
         from .. import maplefit
+        _fit.image_validation_set("fit_prompt_learner", fit_args)
         fit_args.setdefault("logit_scale", math.log(self.scale))
         fit_args.setdefault("class_token_position", getattr(self.prompt_learner, "class_token_position", "end"))
         ids, params = self.prompt_learner.tokenized_prompts, self.learner_params()
         if transform is not None:
             from ..augment import fit_with_transform
             run, epochs, lr = _fit.split_fit_args(fit_args, 5, 0.0035)
+            watch = _fit.split_image_monitor_args("fit_prompt_learner", fit_args)
             state = maplefit.MaPLeFitState(self.clip_model, ids, params, **fit_args)
-            losses = fit_with_transform(state, lambda x: x, ids.shape[0], train_loader, transform, epochs, lr, **run)
-            fitted = _fit.pack(state.params(), losses)
+            end, monitored = _fit.image_end_epoch(state, watch, epochs, len(train_loader))
+            losses = fit_with_transform(state, lambda x: x, ids.shape[0], train_loader, transform, epochs, lr, end_epoch=end, **run)
+            best = monitored and watch["final_model"] == "best_val"
+            fitted = _fit.pack_monitored(state, state.best_params() if best else state.params(), losses, watch, monitored)
         else:
             fitted = maplefit.fit_prompt_learner(train_loader, None, self.clip_model, ids, params, **fit_args)
         block = fitted[0] if isinstance(fitted, tuple) else fitted

@@ -73,9 +73,17 @@ class CustomCLIP(_CoOpCLIP):
         ``dampening``, ``weight_decay``, ``nesterov``, ``grad_scale``, ``seq_rows``, ``views`` (with a transform) and
         ``return_history`` and ``one_call``; the batch size and the order are the loader's (``batch_size`` / ``drop_last`` are refused).
         ``grad_scale="dynamic"`` with ``scaler=dict(init_scale, growth_factor, backoff_factor, growth_interval)``, for ``method="ivlp"``
-        as well: the device-side loss scale (``promptsrcfit``'s module docstring)."""
+        as well: the device-side loss scale (``promptsrcfit``'s module docstring).
+
+        Validation, on either route: ``val_loader=`` (a sized iterable of (test-transformed images, labels) batches on the GPU, iterated
+        once per epoch) or ``val=(val_images_or_loader, val_labels)``, with ``val_batch_size``, ``val_bins``, ``final_model``
+        ("last_step" or "best_val", the reference's TEST.FINAL_MODEL), ``val_criterion`` and ``return_monitor`` as
+        ``promptsrcfit.fit_prompts`` takes them: the GPA work of an epoch comes before its validation, so the last epoch scores the
+        aggregate.  Validation images go through the test transform, never through ``transform``.  ``final_model="best_val"`` installs
+        the best epoch's parameters."""
         import math
         from .. import promptsrcfit
+        _fit.image_validation_set("fit_prompts", fit_args)
         fit_args.setdefault("logit_scale", math.log(self.scale))
         fit_args.setdefault("class_token_position", getattr(self.prompt_learner, "class_token_position", "end"))
         ids, params = self.prompt_learner.tokenized_prompts, self.prompt_params()
@@ -88,15 +96,21 @@ class CustomCLIP(_CoOpCLIP):
             run, epochs, lr = _fit.split_fit_args(fit_args, 50, 0.0025)
             epochs = int(epochs)
             gpa = fit_args.pop("gpa", (30.0, 30.0))
+            watch = _fit.split_image_monitor_args("fit_prompts", fit_args)
             state = promptsrcfit.PromptSRCFitState(self.clip_model, ids, params, teacher_text_features, **fit_args)
             weights = None if fit_args.get("method", "promptsrc") == "ivlp" else promptsrcfit._gpa_for("fit_prompts", gpa, epochs)
-            end = None if weights is None else (lambda e: state.end_epoch(float(weights[e])))
+
+            def aggregate(e: int) -> None:
+                state.end_epoch(float(weights[e]))
+                if e == epochs - 1:
+                    state.apply_gpa()
+
+            end, monitored = _fit.image_end_epoch(state, watch, epochs, len(train_loader), None if weights is None else aggregate)
             stepper = state if not one_call else type("OneCall", (), {"step": staticmethod(
                 lambda x, y, r, want_loss=False: state.step(x, y, r, want_loss=want_loss, one_call=True))})()
             losses = fit_with_transform(stepper, lambda x: x, ids.shape[0], train_loader, transform, epochs, lr, end_epoch=end, **run)
-            if weights is not None and epochs * len(train_loader):
-                state.apply_gpa()
-            fitted = _fit.pack(state.params(), losses)
+            best = monitored and watch["final_model"] == "best_val"
+            fitted = _fit.pack_monitored(state, state.best_params() if best else state.params(), losses, watch, monitored)
         else:
             fitted = promptsrcfit.fit_prompts(train_loader, None, self.clip_model, ids, teacher_text_features, params, **fit_args)
         block = fitted[0] if isinstance(fitted, tuple) else fitted

@@ -36,17 +36,27 @@ class CustomCLIP(ZeroshotCLIP):
         ``lr`` (0.0025), ``lr_per_epoch``, the optimiser's ``momentum``, ``dampening``, ``weight_decay``, ``nesterov``, ``grad_scale``,
         ``views`` (with a transform) and ``return_history``; the batch size and the order are the loader's.  The defaults restate the
         reference's VPT config (SGD, lr 0.0025, 5 epochs).  ``grad_scale="dynamic"`` with ``scaler=dict(init_scale, growth_factor,
-        backoff_factor, growth_interval)``: the device-side loss scale (``vptfit``'s module docstring)."""
+        backoff_factor, growth_interval)``: the device-side loss scale (``vptfit``'s module docstring).
+
+        Validation, on either route: ``val_loader=`` (a sized iterable of (test-transformed images, labels) batches on the GPU, iterated
+        once per epoch) or ``val=(val_images_or_loader, val_labels)``, with ``val_batch_size``, ``val_bins``, ``final_model``
+        ("last_step" or "best_val", the reference's TEST.FINAL_MODEL), ``val_criterion`` and ``return_monitor`` as
+        ``vptfit.fit_prompts`` takes them.  Validation images go through the test transform, never through ``transform``.
+        ``final_model="best_val"`` installs the best epoch's prompts into the parameters."""
         import math
         from .. import vptfit
+        _fit.image_validation_set("fit_prompts", fit_args)
         fit_args.setdefault("logit_scale", math.log(self.scale))
         text = self.text_features.float()
         if transform is not None:
             from ..augment import fit_with_transform
             run, epochs, lr = _fit.split_fit_args(fit_args, 5, 0.0025)
+            watch = _fit.split_image_monitor_args("fit_prompts", fit_args)
             state = vptfit.VPTFitState(self.clip_model, text, **fit_args)
-            losses = fit_with_transform(state, lambda x: x, text.shape[0], train_loader, transform, epochs, lr, **run)
-            fitted = _fit.pack(state.prompts, losses)
+            end, monitored = _fit.image_end_epoch(state, watch, epochs, len(train_loader))
+            losses = fit_with_transform(state, lambda x: x, text.shape[0], train_loader, transform, epochs, lr, end_epoch=end, **run)
+            best = monitored and watch["final_model"] == "best_val"
+            fitted = _fit.pack_monitored(state, state.best_prompts() if best else state.prompts, losses, watch, monitored)
         else:
             fitted = vptfit.fit_prompts(train_loader, None, self.clip_model, text, **fit_args)
         block = fitted[0] if isinstance(fitted, tuple) else fitted

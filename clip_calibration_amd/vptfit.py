@@ -38,7 +38,7 @@ from typing import Optional, Sequence
 import numpy as np
 import torch
 
-from . import _lib, fitloop, ops
+from . import _lib, fitloop, fitmonitor, ops
 from ._lib import check, lib
 from .coopfit import DYNAMIC, _BlockScaler, _check_grad_scale, _is_dynamic, _scale_args, operand_stats_dict
 from .fitloop import _need_gpu
@@ -135,6 +135,7 @@ class _Tower:
         self.B = self.ws_B = 0
         self.ws = self.stash = self.feats = self.step_ws = None
         self.step_key = None
+        self.val_ws = None      # clipmi_vision_val_chunk's workspace
         self.d_prompts = torch.empty(depth, n_ctx, self.D, dtype=torch.float32, device=dev)
 
     def images(self, who: str, images) -> torch.Tensor:
@@ -174,6 +175,31 @@ class _Tower:
                                                      self.stash.numel(), None if stats is None else stats.data_ptr(), ops._stream()),
                   "clipmi_vision_encoder_backward")
         return self.d_prompts
+
+    def val_chunk(self, mon, images: torch.Tensor, prompts: torch.Tensor, text_n: torch.Tensor, scale: float, labels_d: torch.Tensor, n_bins: int,
+                  rows: torch.Tensor, row0: int, one_call: bool = True) -> None:
+        """One chunk of validation images into ``rows[row0 : row0 + B]`` (``fitmonitor.ImageMonitor``): the training forward at ``prompts``,
+        the features normalised, the cosine logits against ``text_n`` [C, E] at ``scale`` and ``ops.val_score_rows`` --
+        clipmi_vision_val_chunk, or with ``one_call=False`` the four calls, which give the same bits.  The stash is overwritten, as a
+        training step's forward overwrites it."""
+        m, B, Cn = self.model, images.shape[0], int(text_n.shape[0])
+        if not one_call:
+            feats = self.forward(images, prompts)
+            feats_n, logits = mon.logits_for(B, Cn, self.E, images.device)
+            check(lib.clipmi_l2_normalize(feats.data_ptr(), _lib.F32, feats_n.data_ptr(), B, self.E, ops._stream()), "clipmi_l2_normalize")
+            check(lib.clipmi_logits(feats_n.data_ptr(), text_n.data_ptr(), scale, None, logits.data_ptr(), None, None, B, Cn, self.E, ops._stream()),
+                  "clipmi_logits")
+            ops.val_score_rows(logits, labels_d, n_bins, rows, row0)
+            return
+        self.size(B, tower_ws=False)
+        need = lib.clipmi_vision_val_chunk_bytes(m._handle, B, self.n_ctx, Cn)
+        if self.val_ws is None or self.val_ws.numel() < need:
+            self.val_ws = torch.empty(max(need, 256), dtype=torch.uint8, device=m.device)
+        pr = ops._row_results("val_chunk", rows, B, row0)
+        with m._launch_lock:
+            check(lib.clipmi_vision_val_chunk(m._handle, images.data_ptr(), _DT[images.dtype], B, prompts.data_ptr(), self.n_ctx, self.depth,
+                                              text_n.data_ptr(), Cn, scale, labels_d.data_ptr(), n_bins, pr, self.val_ws.data_ptr(), self.val_ws.numel(),
+                                              self.stash.data_ptr(), self.stash.numel(), ops._stream()), "clipmi_vision_val_chunk")
 
     def one_call_workspace(self, B: int, n_cls: int, scaled: bool = False) -> torch.Tensor:
         if scaled:
@@ -251,10 +277,12 @@ def image_features(model, prompts: torch.Tensor, images: torch.Tensor) -> torch.
     return tower.forward(images, fitloop.master(prompts, images.device)).clone()
 
 
-class VPTFitState:
+class VPTFitState(fitmonitor.ImageMonitored):
     """The training state of VPT's prompts: the fp32 master block ``prompts`` [depth, n_ctx, Dv] (None: the model's own parameters), SGD's
     momentum buffer, the tower's stash and the number of steps taken.  ``step`` enqueues one forward, backward and update and does not
-    synchronise."""
+    synchronise.  ``validate`` scores validation images on the device (``start_monitor``, ``monitor``, ``best_prompts``,
+    ``val_row_results``; DESIGN.md "Fit monitor", "The image-tower fits")."""
+    _who = "VPTFitState"
 
     def __init__(self, model, text_features: torch.Tensor, logit_scale: float = 4.6052, prompts: Optional[torch.Tensor] = None,
                  momentum: float = 0.9, dampening: float = 0.0, nesterov: bool = False, weight_decay: float = 5e-4,
@@ -276,6 +304,33 @@ class VPTFitState:
         self.momentum, self.dampening, self.nesterov, self.weight_decay = momentum, dampening, nesterov, weight_decay
         self.steps = 0
         self._scaler = _BlockScaler(self.scaler, model.device) if self.dynamic else None
+        self._text_n = None     # the fixed text features, normalised by the first validate
+
+    def _master(self) -> torch.Tensor:
+        return self.prompts
+
+    def validate(self, val_images_or_loader, val_labels, epoch: int, val_batch_size: int = 32, one_call: bool = True) -> None:
+        """Enqueue one validation of the current master prompts into slot ``epoch`` of the device history; no host read.
+        ``val_images_or_loader``: preprocessed images [N_val, 3, R, R] on the GPU with ``val_labels`` [N_val], scored in chunks of
+        ``val_batch_size``, or a sized iterable of (images, labels) batches on the GPU (``val_labels`` None).  Every chunk runs the tower's
+        TRAINING forward at the prompts (the features the next step would see; the stash it overwrites is rewritten by that step), and
+        its rows are scored against the text features, normalised once (clipmi_vision_val_chunk; ``one_call=False``: the four separate
+        calls, the same bits); ``ops.val_score_finish`` folds the 16 N_val bytes of row results into the record, byte for byte
+        ``ops.val_score``'s on the whole logits, and ``clipmi_best_select`` keeps the prompts of the best epoch when the monitor selects.
+        Labels: an int64 tensor on the GPU is taken as it is; anything else is range-checked on the host.  Memory: the tower's stash grows
+        to ``val_batch_size`` images when that exceeds the training batch, and stays (41.6 MB per image at ViT-B/16).  Without ``start_monitor`` the
+        history starts with ``epoch + 1`` slots of 10 bins and no selection."""
+        who = "VPTFitState.validate"
+        mon = self._monitor_for(epoch)
+        if self._text_n is None:
+            self._text_n = ops.l2_normalize(self.text)
+        mon.validate(who, self.tower, self.prompts, self._text_n, self.scale, val_images_or_loader, val_labels, epoch, val_batch_size, self.prompts,
+                     one_call)
+
+    def best_prompts(self) -> torch.Tensor:
+        """The best slot on the device: the prompts of the best epoch so far, or the prompts ``start_monitor`` saw while no epoch has
+        been taken."""
+        return self._best_block("best_prompts").view_as(self.prompts)
 
     def scaler_state(self) -> dict:
         """The dynamic scale's block as ``dict(scale, growth_tracker, skipped_steps, applied_steps, found_inf)`` (``found_inf``: of the
@@ -338,7 +393,8 @@ def fit_prompts(images_or_loader, labels, model, text_features: torch.Tensor, pr
                 lr: float = 0.0025, epochs: int = 5, batch_size: int = 32, momentum: float = 0.9, dampening: float = 0.0,
                 weight_decay: float = 5e-4, nesterov: bool = False, grad_scale: float = DEFAULT_GRAD_SCALE,
                 lr_per_epoch: Optional[Sequence[float]] = None, drop_last: bool = False, return_history: bool = False,
-                scaler: Optional[dict] = None):
+                scaler: Optional[dict] = None, val=None, val_batch_size: int = 32, val_bins: int = 10, final_model: str = "last_step",
+                val_criterion: str = "accuracy", return_monitor: bool = False):
     """Train VPT's prompts starting from ``prompts`` (not modified; None = the model's own parameters): ``epochs`` passes of
     ``torch.optim.SGD(lr, momentum, dampening, weight_decay, nesterov)``.  ``images_or_loader`` is a tensor of preprocessed images
     [N, 3, R, R] with ``labels`` [N], cut into batches of ``batch_size`` in order (the last one short unless ``drop_last``), or a sized
@@ -347,13 +403,27 @@ def fit_prompts(images_or_loader, labels, model, text_features: torch.Tensor, pr
     one wait at the end.  Returns the fitted fp32 block [depth, n_ctx, Dv] on the device, or ``(prompts, per-step batch losses)`` with
     ``return_history``.  The model's parameters are NOT written: ``trainers.vpt.CustomCLIP.fit_prompts`` does that.
     ``grad_scale="dynamic"`` with ``scaler`` (module docstring): a step that overflows fp16 is skipped on the device and the scale adapts;
-    the history keeps one loss per step, skipped steps included, and the run still synchronises once."""
+    the history keeps one loss per step, skipped steps included, and the run still synchronises once.
+
+    ``val=(val_images_or_loader, val_labels)`` (preprocessed validation images [N_val, 3, R, R] on the GPU and their labels, or a sized
+    iterable of (images, labels) batches on the GPU with None): behind the last step of every epoch ``VPTFitState.validate`` scores the
+    prompts against them on the device in chunks of ``val_batch_size``, into ``val_bins`` confidence bins -- the fitted prompts are bit for
+    bit those of the same call without ``val``, and the run still synchronises once.  ``final_model``, ``val_criterion`` and
+    ``return_monitor`` as ``coopfit.fit_context`` takes them: "best_val" returns the prompts of the epoch that was strictly better than
+    every earlier one (the starting prompts when no epoch was taken) and is refused without ``val``."""
     who = "fit_prompts"
+    fitmonitor.check_image_args(who, val, val_batch_size, val_bins, final_model, val_criterion)
     epochs = int(epochs)
     if epochs < 0:
         raise ValueError(f"{who}: epochs={epochs} (>= 0)")
     state = VPTFitState(model, text_features, logit_scale, prompts, momentum, dampening, nesterov, weight_decay, grad_scale, scaler)
     batches = fitloop.cut_batches(who, images_or_loader, labels, state.C, batch_size, drop_last, model.device)
     _, lr_steps = fitloop.schedule(who, lr, epochs, lr_per_epoch, len(batches), model.device)
-    history = fitloop.run_batches(lambda e, k, b, r, want: state.step(b[0], b[1], r, want_loss=want), batches, epochs, lr_steps, return_history)
-    return (state.prompts, history) if return_history else state.prompts
+    end_epoch = None
+    if val is not None and epochs * len(batches) > 0:
+        state.start_monitor(epochs, val_bins, val_criterion, final_model == "best_val")
+        end_epoch = lambda e: state.validate(val[0], val[1], e, val_batch_size)
+    history = fitloop.run_batches(lambda e, k, b, r, want: state.step(b[0], b[1], r, want_loss=want), batches, epochs, lr_steps, return_history, end_epoch)
+    out = state.best_prompts() if final_model == "best_val" and end_epoch is not None else state.prompts
+    return fitmonitor.pack(out, history, (state.monitor() if end_epoch is not None else fitmonitor.empty_monitor(val_bins)) if return_monitor else None,
+                           return_history, return_monitor)

@@ -1566,7 +1566,39 @@ int clipmi_probe_mfma_f16(const void* operands, float* sink, unsigned long long*
  * both 16-byte aligned, exactly n_floats floats are written) and returns at once when the word says "not better".  workspace (256-byte
  * aligned): clipmi_best_select_workspace_bytes(n_floats), 0 for n_floats < 1.  CLIPMI_ERR_ARG: a null pointer, an alignment, a criterion
  * other than 0 or 1, epoch < 0; CLIPMI_ERR_SHAPE: n_floats < 1; CLIPMI_ERR_WORKSPACE.
+ *
+ * The row-chunked score, for validation sets whose [N, C] logits never exist in one piece (the image-tower fits).  The row result, 16 bytes,
+ * 16-byte aligned: {float conf, float nll, int32 hit, int32 bin} -- what clipmi_val_score's first launch holds per row before it adds.
+ *
+ * clipmi_val_score_rows: `rows` rows of logits fp32 [rows, C] with the row stride ld against labels int64 [rows], one wave per row, the
+ * per-row code of clipmi_val_score (the same device function); row r's result goes to row_results[r] and nothing else is written.  For a
+ * chunk that starts at row row0 of the set the caller passes row_results + 16 row0 (bytes) and labels + row0.  No workspace.
+ * CLIPMI_ERR_ARG: a null pointer, logits or row_results not 16-byte aligned, labels not 8-byte aligned, n_bins outside 1..64;
+ * CLIPMI_ERR_SHAPE: rows < 1, C < 1, ld < C.
+ *
+ * clipmi_val_score_finish: the N row results into `record` in clipmi_val_score's order of additions -- launch 1: one partial record per 64
+ * rows, thread 0 the head and thread 1 + b bin b, each over the rows in ascending order (int32 counts, float64 sums); launch 2:
+ * clipmi_val_score's own second launch.  The record is therefore byte for byte clipmi_val_score's on the concatenated logits, however the
+ * rows were cut into chunks.  workspace (256-byte aligned): clipmi_val_score_finish_workspace_bytes(N, n_bins) =
+ * clipmi_val_score_workspace_bytes(N, n_bins).  CLIPMI_ERR_ARG: a null pointer, row_results not 16-byte aligned, the record not 8-byte
+ * aligned, the workspace not 256-byte aligned, n_bins outside 1..64; CLIPMI_ERR_SHAPE: N < 1; CLIPMI_ERR_WORKSPACE.
+ *
+ * clipmi_vision_val_chunk: one chunk of B validation images in one call -- clipmi_vision_encoder_train's body at the fp32 master `prompts`
+ * (same stash; the tower's workspace is the head of `workspace`), clipmi_l2_normalize of the features, clipmi_logits against the already
+ * normalised text features text_n fp32 [C, E] at `scale`, clipmi_val_score_rows into row_results (the caller's pointer for the chunk's
+ * first row, as above) -- the same launches as the four calls, hence the same bits.  workspace (256-byte aligned):
+ * clipmi_vision_val_chunk_bytes(m, B, n_ctx, C) = the tower's + 2 x align256(4 B E) + align256(4 B C); 0 for arguments the call refuses.
+ * Every check precedes the first launch: clipmi_vision_encoder_train's, clipmi_val_score_rows', B >= 1, a finite scale.
  * ---------------------------------------------------------------------------------------------------- */
+int clipmi_val_score_rows(const float* logits, int64_t ld, const int64_t* labels, int rows, int C, int n_bins, void* row_results,
+                          clipmi_stream_t stream);
+size_t clipmi_val_score_finish_workspace_bytes(int N, int n_bins);
+int clipmi_val_score_finish(const void* row_results, int N, int n_bins, void* record, void* workspace, size_t workspace_bytes,
+                            clipmi_stream_t stream);
+size_t clipmi_vision_val_chunk_bytes(const clipmi_model* m, int B, int n_ctx, int C);
+int clipmi_vision_val_chunk(clipmi_model* m, const void* image, int image_dtype, int B, const float* prompts, int n_ctx, int depth,
+                            const float* text_n, int C, float scale, const int64_t* labels, int n_bins, void* row_results, void* workspace,
+                            size_t workspace_bytes, void* stash, size_t stash_bytes, clipmi_stream_t stream);
 size_t clipmi_val_score_workspace_bytes(int N, int n_bins);
 int clipmi_val_score(const float* logits, int64_t ld, const int64_t* labels, int N, int C, int n_bins, void* record, void* workspace,
                      size_t workspace_bytes, clipmi_stream_t stream);
