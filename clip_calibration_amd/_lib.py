@@ -320,6 +320,14 @@ _SIGNATURES = {
     "clipmi_val_score_finish": (_i, [_vp, _i, _i, _vp, _vp, _sz, _vp]),
     "clipmi_vision_val_chunk_bytes": (_sz, [_vp, _i, _i, _i]),
     "clipmi_vision_val_chunk": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _vp, _i, _f, _vp, _i, _vp, _vp, _sz, _vp, _sz, _vp]),
+    "clipmi_cocoop_val_rows": (_i, [_vp, _vp, _f, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "clipmi_cocoop_val_chunk_bytes": (_sz, [_vp, _i, _i, _i, _i]),
+    "clipmi_cocoop_val_chunk": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp, _i, _i, _vp, _i, _f, _vp, _i, _vp, _u, _vp, _sz, _vp]),
+    "clipmi_proda_val_mean": (_i, [_vp, _vp, _i, _i, _i, _vp]),
+    "clipmi_proda_val_monitor_bytes": (_sz, [_i, _i, _i]),
+    "clipmi_proda_val_logits_bytes": (_sz, [_vp, _i, _i, _i, _i, _i]),
+    "clipmi_proda_val_logits": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _u, _i, _vp, _i64, _vp, _i, _i, _vp, _i, _vp, _vp,
+                                     _vp, _sz, _vp, _sz, _vp]),
 }
 
 for _name, (_res, _args) in _SIGNATURES.items():

@@ -28,6 +28,14 @@ gradient block holds an inf or a NaN changes neither the parameters nor the mome
 step reads anything back; ``CoCoOpFitState.scaler_state()`` does, once.  DESIGN.md "Dynamic loss scale for the block fits".  The
 reference's ``autocast`` casts differ from this path's fixed fp16 operand points (unverified).  Not covered: ``nn.DataParallel`` over the text encoder
 (one process drives one GPU), class-token positions other than ``end``.
+
+Validation: ``fit_prompt_learner(val=(val_features, val_labels), val_batch_size=, val_bins=, final_model="last_step" | "best_val",
+val_criterion=, return_monitor=)`` scores the parameters behind every epoch on the device and keeps the block of the best epoch in a
+device slot, with no read-back before the run's one wait (``CoCoOpFitState.validate`` / ``start_monitor`` / ``monitor`` / ``best_params``).
+It scores what the INFERENCE forward (``trainers.cocoop.CustomCLIP.forward``) computes: every validation image has its own C prompts, so
+a chunk of ``val_batch_size`` images runs ``val_batch_size x C`` prompts through the inference text tower (clipmi_cocoop_val_chunk) and a
+fused kernel forms an image's C logits in LDS and scores the row -- no [N_val, C] matrix of any kind exists.  DESIGN.md "Fit monitor",
+"CoCoOp and ProDA".
 """
 from __future__ import annotations
 
@@ -39,7 +47,7 @@ from typing import Dict, Optional, Sequence
 import numpy as np
 import torch
 
-from . import _lib, fitloop, ops
+from . import _lib, fitloop, fitmonitor, ops
 from ._lib import check, lib
 from .coopfit import DYNAMIC, MAX_LIVE_ROWS, _DT, _BlockScaler, _Tower, _check_batch, _check_grad_scale, _is_dynamic, _live_rows, _scale_args, operand_stats_dict
 from .coopfit import _check_prompts as _check_coop_prompts
@@ -196,6 +204,10 @@ class CoCoOpFitState:
         self._towers: Dict[int, _CoCoOpTower] = {}
         self.steps = 0
         self._scaler = _BlockScaler(self.scaler, dev) if self.dynamic else None
+        self._mon = None            # the fit monitor's device history, made by start_monitor or the first validate
+        self._val = None            # what a validation keeps between epochs: the inference operands, the set, one workspace per chunk size
+        self.val_stream_f16 = True  # trainers.cocoop.CustomCLIP's text_stream_f16: validation runs the tower as that forward does
+        self.val_batch_size = None  # validate's chunk when its argument is None (None: the largest training batch seen)
 
     def scaler_state(self) -> dict:
         """The dynamic scale's block as ``dict(scale, growth_tracker, skipped_steps, applied_steps, found_inf)`` (``found_inf``: of the
@@ -203,6 +215,119 @@ class CoCoOpFitState:
         if not self.dynamic:
             raise ValueError(f"CoCoOpFitState.scaler_state: the state was made with a static grad_scale={self.grad_scale}")
         return self._scaler.state()
+
+    # ---- per-epoch validation and best-epoch selection on the device (DESIGN.md "Fit monitor", "CoCoOp and ProDA")
+
+    def start_monitor(self, slots: int, val_bins: int = 10, select: bool = False, val_criterion: str = "accuracy") -> None:
+        """The device history ``validate`` writes: ``slots`` epoch records of ``val_bins`` confidence bins and, with ``select``, the best
+        block and the best slot -- a copy of the master block ``[ctx | W1 | b1 | W2 | b2]`` as it is now, replaced whenever a validated
+        epoch is strictly better under ``val_criterion``.  The momentum block and the scaler block are not selected.  Allocations and one
+        small upload; nothing synchronises."""
+        self._mon = fitmonitor.ImageMonitor("CoCoOpFitState.start_monitor", slots, val_bins, val_criterion, self.block if select else None,
+                                            self.block.device)
+
+    def _val_operands(self):
+        """What the inference forward (``trainers.cocoop.CustomCLIP``) works on, made once: the classes' embeddings [C, context_length, D]
+        in the model's type, their EOT rows, the live token rows of the class list and the tower call's flags."""
+        if self._val is None:
+            m = self.model
+            m._ensure_bound()
+            ids_h = torch.from_numpy(np.ascontiguousarray(fitloop._host_int_array("CoCoOpFitState.validate", self.ids, "tokenized_prompts"))).long()
+            with torch.no_grad():
+                base = m.token_embedding(ids_h.to(m.device)).type(m.dtype).contiguous()
+            f16 = self.val_stream_f16 and m.get_option("residual_f16") == 2 and m.get_option("ln_fold") == 1
+            self._val = {"base": base, "eot": ids_h.argmax(dim=-1).to(torch.int32), "rows": m.live_rows(ids_h),
+                         "flags": _lib.CALL_STREAM_F16 if f16 else _lib.CALL_DEFAULT, "set": None, "chunks": {}}
+        return self._val
+
+    def _val_chunk(self, v: dict, B: int):
+        """(the classes' EOT rows repeated for ``B`` images, clipmi_cocoop_val_chunk's workspace), one pair per chunk size."""
+        if B not in v["chunks"]:
+            dev = self.block.device
+            need = lib.clipmi_cocoop_val_chunk_bytes(self.model._handle, self.C, v["rows"], B, self.n_ctx)
+            if need == 0:
+                raise ValueError(f"CoCoOpFitState.validate: {B} x {self.C} prompts are more than the tower takes in one call; pass a smaller val_batch_size")
+            v["chunks"][B] = (v["eot"].repeat(B).to(dev), torch.empty(max(need, 256), dtype=torch.uint8, device=dev))
+        return v["chunks"][B]
+
+    def validate(self, val_features: torch.Tensor, val_labels, epoch: int, val_batch_size: Optional[int] = None) -> None:
+        """Enqueue one validation of the current master block into slot ``epoch`` of the device history; no host read.  It scores what
+        ``trainers.cocoop.CustomCLIP.forward`` would compute with these parameters once they are loaded into the module (rounded through the
+        model's type, as ``CustomCLIP.fit_prompt_learner`` stores them): ``val_features`` (raw image features fp32 or fp16
+        [N_val, E] on the GPU) are L2-normalised once per set; every chunk of ``val_batch_size`` images (None: the state's
+        ``val_batch_size`` attribute, else the largest training batch seen, at least 1) goes through clipmi_cocoop_val_chunk -- the meta-net and the context shift, the prompt assembly, the INFERENCE
+        text tower over ``val_batch_size x C`` prompts and the fused per-pair tail and row score --, ``ops.val_score_finish`` folds the
+        16 N_val bytes of row results into the record, byte for byte ``ops.val_score``'s on the inference logits, and
+        ``clipmi_best_select`` keeps the block of the best epoch when the monitor selects.  Neither the [N_val, C] logits nor an
+        [N_val, C, E] text matrix exists at any time; the footprint is one chunk's operands.  The record does not depend on
+        ``val_batch_size`` as long as the tower's kernel choice, which follows the row count of a call, does not change (include/clipmi.h).
+        ``val_labels`` [N_val]: an int64 tensor on the GPU is taken as it is; anything else is range-checked on the host.  The fitted
+        parameters, the momentum block, the scaler block and the training stash are not touched.  Without ``start_monitor`` the history
+        starts with ``epoch + 1`` slots of 10 bins and no selection."""
+        who = "CoCoOpFitState.validate"
+        if self._mon is None:
+            self.start_monitor(int(epoch) + 1 if isinstance(epoch, int) and epoch >= 0 else 1)
+        mon, m = self._mon, self.model
+        epoch = mon.slot(who, epoch)
+        if val_batch_size is None:
+            val_batch_size = max(self._towers, default=1) if self.val_batch_size is None else self.val_batch_size
+        bs = fitmonitor._batch_size(who, val_batch_size)
+        if not isinstance(val_features, torch.Tensor) or val_features.dim() != 2 or val_features.shape[0] < 1 or val_features.shape[1] != self.E:
+            raise ValueError(f"{who}: val_features {tuple(getattr(val_features, 'shape', ()))} must be [N_val >= 1, E = {self.E}]")
+        _need_gpu(val_features, "val_features")
+        v = self._val_operands()
+        key = (val_features.data_ptr(), val_features._version, tuple(val_features.shape), tuple(val_features.stride()), val_features.dtype,
+               id(val_labels), getattr(val_labels, "_version", None))
+        if v["set"] is None or v["set"][0] != key:
+            labels_d = fitloop.step_labels(who, val_labels, val_features.shape[0], self.C, val_features.device, "validation rows")
+            v["set"] = (key, ops.l2_normalize(val_features), labels_d, val_labels)
+        _, img_n, labels_d, _ = v["set"]
+        N, dev = img_n.shape[0], img_n.device
+        if mon.n_val and N != mon.n_val and mon.seen:
+            raise ValueError(f"{who}: the validation set has {N} rows, the history's earlier epochs {mon.n_val}")
+        rows = mon.room(N, N, dev)
+        # what the module would hold after ``fit_prompt_learner`` copied the masters into it: the block rounded through the model's type
+        # (index-level plumbing on a few ten thousand values, once per validation; the fp32 masters themselves are what is selected)
+        block = self.block if m.dtype == torch.float32 else self.block.to(m.dtype).to(torch.float32)
+        for lo in range(0, N, bs):
+            B = min(bs, N - lo)
+            eot, ws = self._val_chunk(v, B)
+            pr = ops._row_results(who, rows, B, lo)
+            with m._launch_lock:
+                check(lib.clipmi_cocoop_val_chunk(m._handle, v["base"].data_ptr(), _DT[v["base"].dtype], block.data_ptr(), self.n_ctx, self.H,
+                                                  eot.data_ptr(), self.C, v["rows"], img_n[lo:lo + B].data_ptr(), B, self.scale,
+                                                  labels_d[lo:lo + B].data_ptr(), mon.bins, pr, v["flags"], ws.data_ptr(), ws.numel(), ops._stream()),
+                      "clipmi_cocoop_val_chunk")
+        mon.n_val = N
+        need = lib.clipmi_val_score_finish_workspace_bytes(N, mon.bins)
+        if mon.finish_ws is None or mon.finish_ws.numel() < need:
+            mon.finish_ws = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+        ops.val_score_finish(rows[:N], mon.bins, mon.records[epoch], mon.finish_ws)
+        mon.select(epoch, self.block)
+
+    def monitor(self) -> dict:
+        """The history as numbers (``fitmonitor.monitor_dict``, the dict ``CoOpFitState.monitor`` returns).  It reads the history back:
+        one synchronisation."""
+        return fitmonitor.empty_monitor() if self._mon is None or not self._mon.seen else self._mon.summary()
+
+    def monitor_records(self) -> torch.Tensor:
+        """The device history, uint8 [slots, ops.val_record_bytes(val_bins)]; no read-back."""
+        if self._mon is None:
+            raise ValueError("CoCoOpFitState.monitor_records: nothing has been validated")
+        return self._mon.records
+
+    def val_row_results(self) -> torch.Tensor:
+        """The last validation's row results, uint8 [N_val, 16] on the device (``ops.decode_val_row_results``); no read-back."""
+        if self._mon is None or self._mon.rows is None:
+            raise ValueError("CoCoOpFitState.val_row_results: nothing has been validated")
+        return self._mon.row_results()
+
+    def best_params(self) -> Dict[str, torch.Tensor]:
+        """The best slot on the device as the five tensors (views of one block): the parameters of the best epoch so far, or those
+        ``start_monitor`` saw while no epoch has been taken."""
+        if self._mon is None or self._mon.best is None:
+            raise ValueError("CoCoOpFitState.best_params: the monitor does not select (start_monitor(..., select=True))")
+        return collections.OrderedDict(ops.cocoop_block_views(self._mon.best, self.n_ctx, self.D, self.E, self.H))
 
     def params(self) -> Dict[str, torch.Tensor]:
         """The five tensors as views of the master block (fp32, on the device), under the reference's ``state_dict`` names."""
@@ -293,7 +418,8 @@ def fit_prompt_learner(features: torch.Tensor, labels, clip_model, tokenized_pro
                        lr: float = 0.002, epochs: int = 10, batch_size: int = 1, momentum: float = 0.9, dampening: float = 0.0,
                        weight_decay: float = 5e-4, nesterov: bool = False, grad_scale: float = DEFAULT_GRAD_SCALE, seq_rows: Optional[int] = None,
                        lr_per_epoch: Optional[Sequence[float]] = None, order=None, drop_last: bool = False, return_history: bool = False,
-                       scaler: Optional[dict] = None):
+                       scaler: Optional[dict] = None, val=None, val_batch_size: Optional[int] = None, val_bins: int = 10,
+                       final_model: str = "last_step", val_criterion: str = "accuracy", return_monitor: bool = False, val_stream_f16: bool = True):
     """Train CoCoOp's prompt learner on cached ``features`` fp32 [N, E] and ``labels`` [N], starting from ``params`` (a dict of the five
     tensors, not modified; None = ``init_params(clip_model, n_ctx)``).  The loop and its arguments are ``coopfit.fit_context``'s:
     ``epochs`` passes of ``torch.optim.SGD`` over batches of ``batch_size``, ``lr_per_epoch`` (None: ``cosine_warmup_schedule``),
@@ -301,8 +427,20 @@ def fit_prompt_learner(features: torch.Tensor, labels, clip_model, tokenized_pro
     one wait at the end.  Returns the fitted fp32 tensors on the device as a dict (views of one block), or ``(dict, per-step batch
     losses)`` with ``return_history``.  The defaults are unverified restatements of the reference's config (module docstring).
     ``grad_scale="dynamic"`` with ``scaler`` (module docstring): a step that overflows fp16 is skipped on the device and the scale adapts;
-    the history keeps one loss per step, skipped steps included, and the run still synchronises once."""
+    the history keeps one loss per step, skipped steps included, and the run still synchronises once.
+
+    ``val=(val_features, val_labels)`` (raw image features [N_val, E] on the GPU and their labels): behind the last step of every epoch
+    ``CoCoOpFitState.validate`` scores the parameters against them on the device as the inference forward would, in chunks of
+    ``val_batch_size`` images (None: ``batch_size``; a validation costs N_val x C prompts through the text tower), into ``val_bins``
+    confidence bins -- the fitted tensors are bit for bit those of the same call without ``val``, and the run still synchronises once.
+    ``final_model``, ``val_criterion`` and ``return_monitor`` as ``coopfit.fit_context`` takes them: "best_val" returns the five tensors of
+    the epoch that was strictly better than every earlier one (the starting values when no epoch was taken) and is refused without
+    ``val``; ``return_monitor`` adds ``CoCoOpFitState.monitor()``'s dict behind the history.  ``val_stream_f16``: the validation's tower
+    call asks for the fp16 residual stream where the model allows it, as ``trainers.cocoop.CustomCLIP(text_stream_f16=True)`` does."""
     who = "fit_prompt_learner"
+    fitmonitor.check_args(who, val, val_bins, final_model, val_criterion)
+    if val is not None and val_batch_size is not None:
+        fitmonitor._batch_size(who, val_batch_size)
     if params is None:
         params = init_params(clip_model, n_ctx)
     Cn, n_ctx, H, _ = _check_prompts(who, clip_model, tokenized_prompts, params, seq_rows)
@@ -318,12 +456,23 @@ def fit_prompt_learner(features: torch.Tensor, labels, clip_model, tokenized_pro
     per_epoch = steps_per_epoch(N, batch_size, drop_last)
     dev = features.device
     _, lr_steps = fitloop.schedule(who, lr, epochs, lr_per_epoch, per_epoch, dev)
+    if val is not None:
+        vf, vl = fitmonitor.check_val(who, val, E, Cn)
     if epochs * per_epoch == 0:
         out = collections.OrderedDict((k, params[k].detach().to(torch.float32).clone().to(dev if features.is_cuda else "cpu")) for k in NAMES)
-        return (out, np.zeros(0, np.float32)) if return_history else out
+        return fitmonitor.pack(out, np.zeros(0, np.float32), fitmonitor.empty_monitor(val_bins), return_history, return_monitor)
     _need_gpu(features, "features")
     state = CoCoOpFitState(clip_model, tokenized_prompts, params, logit_scale, momentum, dampening, weight_decay, nesterov, grad_scale, seq_rows,
                            scaler)
+    end_epoch = None
+    if val is not None:
+        _need_gpu(vf, "val_features")
+        vl = vl.to(vf.device)
+        state.val_stream_f16 = bool(val_stream_f16)
+        state.start_monitor(epochs, val_bins, final_model == "best_val", val_criterion)
+        end_epoch = lambda e: state.validate(vf, vl, e, batch_size if val_batch_size is None else val_batch_size)
     history = fitloop.run_cached(lambda f, y, r, want: state.step(f, y, r, want_loss=want), features, fitloop.labels_on(labels, lab, dev),
-                                 fitloop.order_on(order, np.int64, dev), batch_size, per_epoch, epochs, lr_steps, return_history)
-    return (state.params(), history) if return_history else state.params()
+                                 fitloop.order_on(order, np.int64, dev), batch_size, per_epoch, epochs, lr_steps, return_history, end_epoch)
+    out = state.best_params() if final_model == "best_val" else state.params()
+    return fitmonitor.pack(out, history, (state.monitor() if val is not None else fitmonitor.empty_monitor(val_bins)) if return_monitor else None,
+                           return_history, return_monitor)

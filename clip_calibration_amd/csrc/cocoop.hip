@@ -7,6 +7,7 @@
 // The text tower between the last two is the ordinary clipmi_text_encoder on B*C prompts -- that is where the time goes
 // (5.96 GFLOP per prompt); these three are HBM-bound glue: algorithmic bytes = 2*L*D per prompt written (+ read by the
 // tower) and 4*E per (image, class) pair read.
+#include "cocoop_tail.h"
 #include "common.h"
 
 namespace clipmi {
@@ -76,17 +77,9 @@ __global__ __launch_bounds__(256) void per_image_logits_kernel(const float* __re
   if (pair >= (int64_t)B * C) return;
   const int b = (int)(pair / C);
   const float* t = txt + pair * E;
-  const float* f = img + (int64_t)b * E;
-  float dot = 0.f, ss = 0.f;
-  for (int e = lane; e < E; e += 64) {
-    const float tv = t[e];
-    dot += tv * f[e];
-    ss += tv * tv;
-  }
-  dot = wave_sum(dot);
-  ss = wave_sum(ss);
-  const float inv = 1.0f / sqrtf(ss);
-  if (lane == 0) logits[pair] = scale * dot * inv;
+  float inv;
+  const float z = pair_logit(img + (int64_t)b * E, t, scale, E, lane, &inv);
+  if (lane == 0) logits[pair] = z;
   if (txt_n_last && b == B - 1) {   // the reference returns the LAST image's text features (cocoop.py:199)
     const int c = (int)(pair % C);
     for (int e = lane; e < E; e += 64) txt_n_last[(int64_t)c * E + e] = t[e] * inv;

@@ -564,4 +564,52 @@ int clipmi_cocoop_train_step_scaled(clipmi_model* m, const clipmi_text_dgrad* wt
                            workspace, workspace_bytes, stash, stash_bytes, (hipStream_t)stream);
 }
 
+// ---- one chunk of Bv validation images (DESIGN.md "Fit monitor", "CoCoOp and ProDA"): the launches of the inference forward (cocoop.py:186-199) --
+// clipmi_cocoop_ctx, clipmi_cocoop_prompts, clipmi_text_encoder over the Bv C prompts -- and the fused per-pair tail and row score
+// (clipmi_cocoop_val_rows).  workspace: the tower's (Bv C prompts) | ctx_shifted fp32 [Bv, n_ctx, D] | prompts fp16 [Bv C, Lc, D] | text fp32
+// [Bv C, E], each part 256-byte aligned
+size_t clipmi_cocoop_val_chunk_bytes(const clipmi_model* m, int C, int seq_rows, int Bv, int n_ctx) {
+  if (!m || C < 1 || Bv < 1 || n_ctx < 1 || (int64_t)Bv * C >= (1ll << 31) / m->g.context_length) return 0;
+  const size_t N = (size_t)Bv * C, D = m->g.text_width;
+  return align256(clipmi_text_workspace_bytes(m, (int)N, seq_rows)) + align256((size_t)Bv * n_ctx * D * 4) + align256(N * m->g.context_length * D * 2) +
+         align256(N * m->g.embed_dim * 4);
+}
+
+int clipmi_cocoop_val_chunk(clipmi_model* m, const void* base, int dtype, const float* params, int n_ctx, int H, const int32_t* eot, int C, int seq_rows,
+                            const float* img_n, int Bv, float scale, const int64_t* labels, int n_bins, void* row_results, unsigned flags, void* workspace,
+                            size_t workspace_bytes, clipmi_stream_t stream) {
+  const char* who = "cocoop_val_chunk";
+  CLIPMI_REQUIRE(m, CLIPMI_ERR_ARG, "%s: null model", who);
+  CLIPMI_REQUIRE(base && params && eot && img_n && labels && row_results && workspace, CLIPMI_ERR_ARG,
+                 "%s: null pointer (base, params, eot, the image features, labels, the row results and the workspace are required)", who);
+  CLIPMI_REQUIRE(dtype == CLIPMI_F16 || dtype == CLIPMI_F32, CLIPMI_ERR_ARG, "%s: bad dtype %d", who, dtype);
+  CLIPMI_REQUIRE(H >= 1 && H <= MAX_H, CLIPMI_ERR_SHAPE, "%s: H=%d (1 .. %d)", who, H, MAX_H);
+  const int Lc = m->g.context_length, D = m->g.text_width, E = m->g.embed_dim;
+  CLIPMI_REQUIRE(n_ctx >= 1 && n_ctx < Lc - 1 && D % 8 == 0, CLIPMI_ERR_SHAPE, "%s: n_ctx=%d (1 .. %d), D=%d (a multiple of 8)", who, n_ctx, Lc - 2, D);
+  CLIPMI_REQUIRE(C >= 1 && Bv >= 1, CLIPMI_ERR_SHAPE, "%s: C=%d Bv=%d (both >= 1)", who, C, Bv);
+  CLIPMI_REQUIRE((int64_t)Bv * C < (1ll << 31) / Lc, CLIPMI_ERR_SHAPE, "%s: too many prompt tokens (Bv * C = %lld prompts)", who, (long long)Bv * C);
+  CLIPMI_REQUIRE(((uintptr_t)params | (uintptr_t)img_n | (uintptr_t)eot) % 4 == 0, CLIPMI_ERR_ARG, "%s: fp32 and int32 arrays must be 4-byte aligned", who);
+  CLIPMI_REQUIRE((uintptr_t)workspace % 256 == 0, CLIPMI_ERR_ARG, "%s: the workspace must be 256-byte aligned", who);
+  const size_t need = clipmi_cocoop_val_chunk_bytes(m, C, seq_rows, Bv, n_ctx);
+  CLIPMI_REQUIRE(workspace_bytes >= need, CLIPMI_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, need);
+  const int N = Bv * C;
+  const size_t tower = align256(clipmi_text_workspace_bytes(m, N, seq_rows));
+  Carver c(static_cast<char*>(workspace) + tower);
+  float* ctx_shifted = c.take<float>((size_t)Bv * n_ctx * D * 4);
+  half_t* prompts = c.take<half_t>((size_t)N * Lc * D * 2);
+  float* text = c.take<float>((size_t)N * E * 4);
+  // the tower's own refusals (unbound weights, the flags) through a call of no prompts, which launches nothing; the tail's through a look at its arguments
+  if (int rc = clipmi_text_encoder(m, nullptr, CLIPMI_F16, nullptr, 0, seq_rows, nullptr, nullptr, workspace, tower, flags, stream)) return rc;
+  CLIPMI_REQUIRE((uintptr_t)row_results % 16 == 0 && (uintptr_t)labels % 8 == 0, CLIPMI_ERR_ARG,
+                 "%s: the row results must be 16-byte aligned, labels 8-byte aligned", who);
+  CLIPMI_REQUIRE(C <= 16384, CLIPMI_ERR_SHAPE, "%s: C=%d (at most 16384: the row kernel keeps an image's logits in LDS)", who, C);
+  CLIPMI_REQUIRE(n_bins >= 1 && n_bins <= 64, CLIPMI_ERR_ARG, "%s: n_bins=%d outside 1..64", who, n_bins);
+  CLIPMI_REQUIRE(std::isfinite(scale), CLIPMI_ERR_ARG, "%s: scale=%g (finite)", who, scale);
+  const Block k = block_of(n_ctx, D, E, H);
+  if (int rc = clipmi_cocoop_ctx(img_n, params + k.w1, params + k.b1, params + k.w2, params + k.b2, params, ctx_shifted, Bv, E, H, D, n_ctx, stream)) return rc;
+  if (int rc = clipmi_cocoop_prompts(base, dtype, ctx_shifted, prompts, Bv, C, Lc, D, n_ctx, stream)) return rc;
+  if (int rc = clipmi_text_encoder(m, prompts, CLIPMI_F16, eot, N, seq_rows, nullptr, text, workspace, tower, flags, stream)) return rc;
+  return clipmi_cocoop_val_rows(img_n, text, scale, labels, Bv, C, E, n_bins, row_results, stream);
+}
+
 }  // extern "C"

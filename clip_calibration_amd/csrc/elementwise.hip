@@ -2,6 +2,7 @@
 // overwrite (MaPLe), positional add, token-embedding gather, casts, row L2 normalisation.
 // All of them move 16 bytes per lane where the layout allows it.
 #include "common.h"
+#include "l2norm.h"
 
 namespace clipmi {
 namespace {
@@ -221,33 +222,7 @@ __global__ __launch_bounds__(256) void l2norm_kernel(const TI* __restrict__ in, 
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
   const TI* x = in + (int64_t)row * E;
-  float ss = 0.f;
-  auto load8 = [&](const TI* p8, float (&v)[8]) {
-    if constexpr (sizeof(TI) == 4) {
-      const f32x4 p = *reinterpret_cast<const f32x4*>(p8), q = *reinterpret_cast<const f32x4*>(p8 + 4);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) { v[e] = p[e]; v[4 + e] = q[e]; }
-    } else {
-      const f16x8 h = *reinterpret_cast<const f16x8*>(p8);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) v[e] = (float)h[e];
-    }
-  };
-  if (vec8) {   // uniform
-    for (int c = lane; c < (E >> 3); c += 64) {
-      float v[8];
-      load8(x + c * 8, v);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) ss = __builtin_fmaf(v[e], v[e], ss);
-    }
-  } else {
-    for (int e = lane; e < E; e += 64) {
-      const float v = (float)x[e];
-      ss = __builtin_fmaf(v, v, ss);
-    }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);
+  const float ss = row_sumsq(x, E, vec8, lane);
   const float inv = 1.0f / sqrtf(ss);
   for (int e = lane; e < E; e += 64) out[(int64_t)row * E + e] = (TO)((float)x[e] * inv);   // TO = fp16: the fp32 value, rounded once
 }

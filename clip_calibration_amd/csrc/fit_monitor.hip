@@ -3,6 +3,7 @@
 //   val_score_rows_kernel     one wave per row, 64 rows per workgroup: max / arg-max (lowest index on a tie), log-sum-exp, nll, confidence and
 //                             its digitize bin; the workgroup's rows are then added in ascending row order into ONE partial record
 //   val_score_chunk_kernel    the same per-row code (score_row) on a chunk of rows, one 16-byte result per row: {conf, nll, hit, bin}
+//   cocoop_val_rows_kernel    CoCoOp: one workgroup per image forms its C per-pair logits in LDS (pair_logit, cocoop_tail.h) and scores them
 //   val_score_partials_kernel the 64-row partial records from the row results, in val_score_rows_kernel's order
 //   val_score_reduce_kernel   ONE workgroup: one thread per field of the record adds the partial records in ascending workgroup order
 //   best_decide_kernel        ONE workgroup: strictly better than the best so far?  updates the best block, writes the decision word
@@ -14,6 +15,7 @@
 #include <cmath>
 #include <cstdint>
 
+#include "cocoop_tail.h"
 #include "common.h"
 
 namespace clipmi {
@@ -24,6 +26,7 @@ constexpr int VS_WAVE = 64;
 constexpr int VS_WAVES = VS_THREADS / VS_WAVE;
 constexpr int VS_ROWS = 64;        // rows per workgroup: the partition of the rows depends on N alone
 constexpr int VS_MAX_BINS = 64;
+constexpr int COCOOP_VAL_MAX_C = 16384;   // cocoop_val_rows_kernel keeps one image's C fp32 logits in LDS: 64 KiB at most
 constexpr int COPY_THREADS = 256;
 constexpr int COPY_MAX_BLOCKS = 1024;
 
@@ -165,6 +168,27 @@ __global__ __launch_bounds__(VS_THREADS) void val_score_chunk_kernel(const float
   if (lane == 0) row_results[row] = res;
 }
 
+// CoCoOp's validation rows: one workgroup per image b.  Its C text features txt[b, c, :] (raw tower outputs) are normalised and dotted with the
+// image's unit feature by pair_logit, one wave per class, into C fp32 logits in LDS -- per_image_logits_kernel's bits --, and wave 0 scores
+// them with score_row; the [Bv, C] logits never go to memory
+__global__ __launch_bounds__(VS_THREADS) void cocoop_val_rows_kernel(const float* __restrict__ img_n, const float* __restrict__ txt, float scale,
+                                                                     const int64_t* __restrict__ labels, int C, int E, int n_bins,
+                                                                     RowResult* __restrict__ row_results) {
+  extern __shared__ float s_z[];   // [C]
+  const int wave = threadIdx.x / VS_WAVE, lane = threadIdx.x % VS_WAVE;
+  const int64_t b = blockIdx.x;
+  const float* f = img_n + b * E;
+  for (int c = wave; c < C; c += VS_WAVES) {
+    float inv;
+    const float z = pair_logit(f, txt + (b * C + c) * E, scale, E, lane, &inv);
+    if (lane == 0) s_z[c] = z;
+  }
+  __syncthreads();
+  if (wave != 0) return;
+  const RowResult res = score_row(s_z, lane == 0 ? labels[b] : 0, C, n_bins, lane);
+  if (lane == 0) row_results[b] = res;
+}
+
 // The partial record of rows [64 k, 64 k + 64) of the N row results, added as val_score_rows_kernel adds its workgroup's rows: thread 0 the
 // head, thread 1 + b bin b, each over the rows in ascending order
 __global__ __launch_bounds__(VS_THREADS) void val_score_partials_kernel(const RowResult* __restrict__ row_results, int N, int n_bins,
@@ -287,6 +311,22 @@ int clipmi_val_score_rows(const float* logits, int64_t ld, const int64_t* labels
   hipLaunchKernelGGL(val_score_chunk_kernel, dim3((unsigned)blocks), dim3(VS_THREADS), 0, (hipStream_t)stream, logits, ld, labels, rows, C, n_bins,
                      (RowResult*)row_results);
   return check_launch("val_score_chunk_kernel");
+}
+
+int clipmi_cocoop_val_rows(const float* img_n, const float* txt, float scale, const int64_t* labels, int Bv, int C, int E, int n_bins, void* row_results,
+                           clipmi_stream_t stream) {
+  CLIPMI_REQUIRE(img_n && txt && labels && row_results, CLIPMI_ERR_ARG,
+                 "cocoop_val_rows: null pointer (the image features, the text features, labels and the row results are required)");
+  CLIPMI_REQUIRE(((uintptr_t)img_n | (uintptr_t)txt) % 4 == 0, CLIPMI_ERR_ARG, "cocoop_val_rows: fp32 arrays must be 4-byte aligned");
+  CLIPMI_REQUIRE((uintptr_t)row_results % 16 == 0, CLIPMI_ERR_ARG, "cocoop_val_rows: the row results must be 16-byte aligned");
+  CLIPMI_REQUIRE((uintptr_t)labels % 8 == 0, CLIPMI_ERR_ARG, "cocoop_val_rows: labels must be 8-byte aligned");
+  CLIPMI_REQUIRE(Bv >= 1 && C >= 1 && C <= COCOOP_VAL_MAX_C && E >= 1, CLIPMI_ERR_SHAPE, "cocoop_val_rows: Bv=%d C=%d E=%d (Bv, E >= 1, C in 1..%d)", Bv, C, E,
+                 COCOOP_VAL_MAX_C);
+  CLIPMI_REQUIRE(n_bins >= 1 && n_bins <= VS_MAX_BINS, CLIPMI_ERR_ARG, "cocoop_val_rows: n_bins=%d outside 1..%d", n_bins, VS_MAX_BINS);
+  CLIPMI_REQUIRE(std::isfinite(scale), CLIPMI_ERR_ARG, "cocoop_val_rows: scale=%g (finite)", scale);
+  hipLaunchKernelGGL(cocoop_val_rows_kernel, dim3((unsigned)Bv), dim3(VS_THREADS), (size_t)C * sizeof(float), (hipStream_t)stream, img_n, txt, scale, labels, C,
+                     E, n_bins, (RowResult*)row_results);
+  return check_launch("cocoop_val_rows_kernel");
 }
 
 size_t clipmi_val_score_finish_workspace_bytes(int N, int n_bins) { return val_score_bytes(N, n_bins); }

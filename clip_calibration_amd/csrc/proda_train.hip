@@ -19,6 +19,8 @@
 #include <cmath>
 
 #include "common.h"
+#include "fit_monitor.h"
+#include "l2norm.h"
 #include "model.h"
 #include "train_rules.h"
 
@@ -27,6 +29,7 @@ namespace {
 
 constexpr int THREADS = 256;
 constexpr int WAVES = THREADS / 64;
+constexpr int VAL_MAX_P = 4096;   // proda_val_mean_kernel keeps a class's P reciprocal norms in LDS
 enum { POS_FRONT = 0, POS_MIDDLE = 1, POS_END = 2 };
 
 // a class's name length as every kernel here reads it: inside [0, L - 3 - n_ctx], so that no row index computed from it leaves the L live
@@ -41,6 +44,20 @@ __device__ __forceinline__ int ctx_row(int ps, int j, int nl, int h) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------- the assembly
+// token row l of a class prompt of the position `ps` whose name is nl tokens long: *j >= 0 -- context vector *j; *j < 0 -- the returned row of
+// the class's base embedding (the row itself outside 1 .. n_ctx + nl, else name token t = base row 1 + n_ctx + t).  The training assembly and
+// the validation's share it.
+__device__ __forceinline__ int class_row_source(int l, int ps, int nl, int n_ctx, int* j) {
+  const int r = l - 1, h = n_ctx / 2;
+  *j = -1;
+  if (r < 0 || r >= n_ctx + nl) return l;
+  int t;
+  if (ps == POS_FRONT) { *j = r < nl ? -1 : r - nl; t = r; }
+  else if (ps == POS_MIDDLE) { *j = r < h ? r : r < h + nl ? -1 : r - nl; t = r - h; }
+  else { *j = r < n_ctx ? r : -1; t = r - n_ctx; }
+  return 1 + n_ctx + t;
+}
+
 __device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 __device__ __forceinline__ f32x4 ld4(const half_t* p) {
   const f16x4 h = *reinterpret_cast<const f16x4*>(p);
@@ -73,24 +90,73 @@ __global__ __launch_bounds__(THREADS) void proda_embed_kernel(const T* __restric
     if (l == 0 && d == 0) eot[n] = n_ctx + 2;
   } else {
     const int c = (int)(n / Pb), q = (int)(n % Pb);
-    const int p = sel[q], nl = clamp_name_len(name_lens[c], L, n_ctx), h = n_ctx / 2;
+    const int p = sel[q], nl = clamp_name_len(name_lens[c], L, n_ctx);
     if (l == 0 && d == 0) eot[n] = cls_eot[c];
     const T* cls = base + (int64_t)c * Lc * D + d;
-    const int r = l - 1;
     if (p < 0 || p >= P) {                          // a selection outside the collection is never an address: the prompt is poisoned
       v = f32x4{NAN, NAN, NAN, NAN};
-    } else if (r < 0 || r >= n_ctx + nl) {
-      v = ld4(cls + (int64_t)l * D);
     } else {
-      const int ps = pos[p];
-      int j, t;                                     // context vector j, or name token t when j < 0
-      if (ps == POS_FRONT) { j = r < nl ? -1 : r - nl; t = r; }
-      else if (ps == POS_MIDDLE) { j = r < h ? r : r < h + nl ? -1 : r - nl; t = r - h; }
-      else { j = r < n_ctx ? r : -1; t = r - n_ctx; }
-      v = j >= 0 ? ld4(ctx + ((int64_t)p * n_ctx + j) * D + d) : ld4(cls + (int64_t)(1 + n_ctx + t) * D);
+      int j;
+      const int src = class_row_source(l, pos[p], nl, n_ctx, &j);
+      v = j >= 0 ? ld4(ctx + ((int64_t)p * n_ctx + j) * D + d) : ld4(cls + (int64_t)src * D);
     }
   }
   *reinterpret_cast<f32x4*>(dst) = v;
+}
+
+// The validation's assembly (proda.py:146-222 with infer = True): the P prompts of the classes c0 .. c0 + cc - 1, class-major, a class's prompts in the
+// order of `order` [P] (the caller's end | middle | front order of ALL contexts), in the MODEL's type T as the inference forward assembles them: a
+// context row is the fp32 master rounded to T (what loading it into the module's parameter does), a base row is copied.  Only the L live rows are
+// written.  One thread per four elements.  No no-class prompts.  eot[n] is the class's own EOT row.
+template <typename T>
+__global__ __launch_bounds__(THREADS) void proda_val_embed_kernel(const T* __restrict__ base, const float* __restrict__ ctx, const int32_t* __restrict__ order,
+                                                                  const int32_t* __restrict__ pos, const int32_t* __restrict__ name_lens,
+                                                                  const int32_t* __restrict__ cls_eot, T* __restrict__ out, int32_t* __restrict__ eot, int c0,
+                                                                  int cc, int P, int L, int Lc, int D, int n_ctx) {
+  const int D4 = D / 4;
+  const int64_t idx = (int64_t)blockIdx.x * THREADS + threadIdx.x;
+  if (idx >= (int64_t)cc * P * L * D4) return;
+  const int d = (int)(idx % D4) * 4, l = (int)((idx / D4) % L);
+  const int64_t n = idx / ((int64_t)D4 * L);
+  const int c = c0 + (int)(n / P), q = (int)(n % P);
+  const int p = order[q], nl = clamp_name_len(name_lens[c], L, n_ctx);
+  if (l == 0 && d == 0) eot[n] = cls_eot[c];
+  const T* cls = base + (int64_t)c * Lc * D + d;
+  f32x4 v;
+  if (p < 0 || p >= P) {
+    v = f32x4{NAN, NAN, NAN, NAN};
+  } else {
+    int j;
+    const int src = class_row_source(l, pos[p], nl, n_ctx, &j);
+    v = j >= 0 ? ld4(ctx + ((int64_t)p * n_ctx + j) * D + d) : ld4(cls + (int64_t)src * D);
+  }
+  T* dst = out + (n * Lc + l) * D + d;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) dst[e] = (T)v[e];
+}
+
+// The validation's classifier (proda.py:324-331): grid (cc), one workgroup per class.  Each of the class's P raw text features is normalised --
+// its reciprocal norm by one wave in l2norm_kernel's order (row_sumsq), the product rounded to fp32 as that kernel stores it -- and the P unit
+// features are added in ascending row order, then divided by P (group_mean_kernel's order): the bits of clipmi_l2_normalize followed by
+// clipmi_group_mean, without the [cc P, E] normalised copy.  The mean is not renormalised.
+__global__ __launch_bounds__(THREADS) void proda_val_mean_kernel(const float* __restrict__ text, float* __restrict__ mean, int P, int E, int vec8) {
+  extern __shared__ float s_inv[];   // [P]
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const float* rows = text + (int64_t)blockIdx.x * P * E;
+  for (int p = wave; p < P; p += WAVES) {
+    const float ss = row_sumsq(rows + (int64_t)p * E, E, vec8, lane);
+    if (lane == 0) s_inv[p] = 1.0f / sqrtf(ss);
+  }
+  __syncthreads();
+  for (int e = threadIdx.x; e < E; e += THREADS) {
+#pragma clang fp contract(off)   // the product and the sum round separately, as the two kernels round them: never one fma
+    float s = 0.f;
+    for (int p = 0; p < P; ++p) {
+      const float unit = rows[(int64_t)p * E + e] * s_inv[p];
+      s = s + unit;
+    }
+    mean[(int64_t)blockIdx.x * E + e] = s / (float)P;
+  }
 }
 
 int check_embed(const char* who, const void* base, const void* nc_base, int dtype, const float* ctx, const int32_t* sel, const int32_t* pos,
@@ -628,6 +694,92 @@ int clipmi_proda_train_step_scaled(clipmi_model* m, const clipmi_text_dgrad* wt,
   return train_step("proda_train_step_scaled", m, wt, base, nc_base, dtype, ctx, buf, n_ctx, sel, pos, name_lens, cls_eot, C, Pb, P, seq_rows, feats, ld, labels, B,
                     scale, 1.f, &sc, alpha, lr, 0, momentum, dampening, weight_decay, nesterov, losses, grad_out, workspace, workspace_bytes, stash, stash_bytes,
                     (hipStream_t)stream);
+}
+
+// ---- one validation (DESIGN.md "Fit monitor", "CoCoOp and ProDA"): set_classifier and forward of the inference mirror (proda.py:316-331, 304-313).
+int clipmi_proda_val_mean(const float* text, float* mean, int G, int P, int E, clipmi_stream_t stream) {
+  CLIPMI_REQUIRE(text && mean, CLIPMI_ERR_ARG, "proda_val_mean: null pointer");
+  CLIPMI_REQUIRE(((uintptr_t)text | (uintptr_t)mean) % 4 == 0, CLIPMI_ERR_ARG, "proda_val_mean: fp32 arrays must be 4-byte aligned");
+  CLIPMI_REQUIRE(G >= 1 && P >= 1 && P <= VAL_MAX_P && E >= 1, CLIPMI_ERR_SHAPE, "proda_val_mean: G=%d P=%d E=%d (G, E >= 1, P in 1..%d)", G, P, E, VAL_MAX_P);
+  const int vec8 = (E % 8 == 0 && (uintptr_t)text % 16 == 0) ? 1 : 0;   // clipmi_l2_normalize's rule
+  hipLaunchKernelGGL(proda_val_mean_kernel, dim3((unsigned)G), dim3(THREADS), (size_t)P * sizeof(float), (hipStream_t)stream, text, mean, P, E, vec8);
+  return check_launch("proda_val_mean_kernel");
+}
+
+size_t clipmi_proda_val_monitor_bytes(int n_val, int C, int n_bins) { return fit_monitor_bytes(n_val, C, n_bins); }
+
+// workspace: the tower's (cc P prompts, cc = min(class_chunk, C)) | prompts in the model's type [cc P, Lc, D] (sized for fp32) | EOT int32 [cc P] | text
+// fp32 [cc P, E] | mean fp32 [C, E] | normalised validation features fp32 [n_val, E] | clipmi_fused_tail's workspace
+size_t clipmi_proda_val_logits_bytes(const clipmi_model* m, int C, int P, int seq_rows, int class_chunk, int n_val) {
+  if (!m || C < 2 || P < 1 || P > VAL_MAX_P || class_chunk < 1 || n_val < 1 || n_val > 262144) return 0;
+  const int cc = class_chunk < C ? class_chunk : C;
+  if ((int64_t)cc * P >= (1ll << 31) / m->g.context_length) return 0;
+  const size_t N = (size_t)cc * P, E = m->g.embed_dim;
+  return align256(clipmi_text_workspace_bytes(m, (int)N, seq_rows)) + align256(N * m->g.context_length * m->g.text_width * 4) + align256(N * 4) +
+         align256(N * E * 4) + align256((size_t)C * E * 4) + align256((size_t)n_val * E * 4) + align256(clipmi_fused_tail_workspace_bytes(n_val, C));
+}
+
+int clipmi_proda_val_logits(clipmi_model* m, const void* base, int dtype, const float* ctx, const int32_t* order, const int32_t* pos, const int32_t* name_lens,
+                            const int32_t* cls_eot, int C, int P, int n_ctx, int seq_rows, int class_chunk, float scale, unsigned flags, int epoch,
+                            const float* val_feats, int64_t val_ld, const int64_t* val_labels, int n_val, int n_bins, void* records, int criterion,
+                            void* best_block, float* best_params, void* monitor_workspace, size_t monitor_workspace_bytes, void* workspace,
+                            size_t workspace_bytes, clipmi_stream_t stream) {
+  const char* who = "proda_val_logits";
+  hipStream_t s = (hipStream_t)stream;
+  CLIPMI_REQUIRE(m, CLIPMI_ERR_ARG, "%s: null model", who);
+  CLIPMI_REQUIRE(base && ctx && order && pos && name_lens && cls_eot && workspace, CLIPMI_ERR_ARG, "%s: null pointer", who);
+  CLIPMI_REQUIRE(dtype == CLIPMI_F16 || dtype == CLIPMI_F32, CLIPMI_ERR_ARG, "%s: bad dtype %d", who, dtype);
+  const int Lc = m->g.context_length, L = live_rows(m, seq_rows), D = m->g.text_width, E = m->g.embed_dim;
+  CLIPMI_REQUIRE(C >= 2 && P >= 1 && P <= VAL_MAX_P && class_chunk >= 1, CLIPMI_ERR_SHAPE, "%s: C=%d (>= 2), P=%d (1 .. %d), class_chunk=%d (>= 1)", who, C, P,
+                 VAL_MAX_P, class_chunk);
+  CLIPMI_REQUIRE(D >= 4 && D % 4 == 0 && n_ctx >= 1 && n_ctx + 3 <= L, CLIPMI_ERR_SHAPE,
+                 "%s: D=%d (a multiple of 4), n_ctx=%d, L=%d rows (SOS, the context, '.' and EOT must fit)", who, D, n_ctx, L);
+  CLIPMI_REQUIRE(E % 16 == 0, CLIPMI_ERR_SHAPE, "%s: E=%d (a multiple of 16, clipmi_fused_tail's)", who, E);
+  const int cc = class_chunk < C ? class_chunk : C;
+  CLIPMI_REQUIRE((int64_t)cc * P < (1ll << 31) / Lc, CLIPMI_ERR_SHAPE, "%s: too many prompt tokens (%lld prompts per tower call)", who, (long long)cc * P);
+  CLIPMI_REQUIRE(((uintptr_t)base | (uintptr_t)ctx) % 16 == 0, CLIPMI_ERR_ARG, "%s: base and ctx must be 16-byte aligned", who);
+  CLIPMI_REQUIRE((uintptr_t)workspace % 256 == 0, CLIPMI_ERR_ARG, "%s: the workspace must be 256-byte aligned", who);
+  CLIPMI_REQUIRE(std::isfinite(scale), CLIPMI_ERR_ARG, "%s: scale=%g (finite)", who, scale);
+  CLIPMI_REQUIRE(epoch >= 0, CLIPMI_ERR_ARG, "%s: epoch=%d (>= 0)", who, epoch);
+  const FitMonitor mon{val_feats, val_ld, val_labels, n_val, n_bins, records, criterion, best_block, best_params, monitor_workspace, monitor_workspace_bytes};
+  if (int rc = check_fit_monitor(who, mon, E, C)) return rc;
+  CLIPMI_REQUIRE(val_ld == E && (uintptr_t)val_feats % 16 == 0, CLIPMI_ERR_ARG, "%s: the validation features must be contiguous (ld == E = %d) and 16-byte aligned",
+                 who, E);
+  CLIPMI_REQUIRE(n_val <= 262144 && (int64_t)n_val * C * 4 < 0xFFFFFFF0ll && (C + 63) / 64 <= 65535, CLIPMI_ERR_SHAPE,
+                 "%s: N_val=%d x C=%d is more than clipmi_fused_tail takes in one call", who, n_val, C);
+  const size_t need = clipmi_proda_val_logits_bytes(m, C, P, seq_rows, class_chunk, n_val);
+  CLIPMI_REQUIRE(need > 0 && workspace_bytes >= need, CLIPMI_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, need);
+  const int N = cc * P;
+  const size_t tower = align256(clipmi_text_workspace_bytes(m, N, seq_rows)), tail_bytes = align256(clipmi_fused_tail_workspace_bytes(n_val, C));
+  // the tower's own refusals (unbound weights, the flags) through a call of no prompts, which launches nothing
+  if (int rc = clipmi_text_encoder(m, nullptr, dtype, nullptr, 0, seq_rows, nullptr, nullptr, workspace, tower, flags, stream)) return rc;
+  Carver c(static_cast<char*>(workspace) + tower);
+  void* prompts = c.take<char>((size_t)N * Lc * D * 4);
+  int32_t* eot = c.take<int32_t>((size_t)N * 4);
+  float* text = c.take<float>((size_t)N * E * 4);
+  float* mean = c.take<float>((size_t)C * E * 4);
+  float* img_n = c.take<float>((size_t)n_val * E * 4);
+  void* tail_ws = c.take<char>(tail_bytes);
+  for (int c0 = 0; c0 < C; c0 += cc) {
+    const int n = C - c0 < cc ? C - c0 : cc;
+    const int64_t total = (int64_t)n * P * L * (D / 4);
+    const dim3 grid((unsigned)((total + THREADS - 1) / THREADS)), threads(THREADS);
+    if (dtype == CLIPMI_F16)
+      hipLaunchKernelGGL(proda_val_embed_kernel<half_t>, grid, threads, 0, s, (const half_t*)base, ctx, order, pos, name_lens, cls_eot, (half_t*)prompts, eot, c0, n,
+                         P, L, Lc, D, n_ctx);
+    else
+      hipLaunchKernelGGL(proda_val_embed_kernel<float>, grid, threads, 0, s, (const float*)base, ctx, order, pos, name_lens, cls_eot, (float*)prompts, eot, c0, n, P,
+                         L, Lc, D, n_ctx);
+    if (int rc = check_launch("proda_val_embed_kernel")) return rc;
+    if (int rc = clipmi_text_encoder(m, prompts, dtype, eot, n * P, seq_rows, nullptr, text, workspace, tower, flags, stream)) return rc;
+    if (int rc = clipmi_proda_val_mean(text, mean + (size_t)c0 * E, n, P, E, stream)) return rc;
+  }
+  // clipmi_fused_tail's ticket counters start from zero (and are left so)
+  if (hipMemsetAsync(tail_ws, 0, 64 * 1024, s) != hipSuccess) return check_launch("hipMemsetAsync");
+  if (int rc = clipmi_fused_tail(val_feats, CLIPMI_F32, 1, mean, scale, nullptr, fit_monitor_logits(mon), img_n, nullptr, nullptr, nullptr, nullptr, 0, tail_ws,
+                                 tail_bytes, n_val, C, E, stream))
+    return rc;
+  return fit_monitor_score(mon, epoch, C, ctx, (int64_t)P * n_ctx * D, stream);
 }
 
 }  // extern "C"

@@ -3,7 +3,11 @@ argument checks of ``val`` / ``val_bins`` / ``final_model`` / ``val_criterion``,
 best slot -- and the dict ``monitor()`` returns.  ``coopfit`` reads the dict's code from here; ``adapterfit`` and ``taskresfit`` use all of
 it, both for their one-call monitored runs (``ops.adapter_fit`` / ``ops.taskres_fit`` with ``monitor=``) and for ``*FitState.validate``.
 ``vptfit``, ``maplefit`` and ``promptsrcfit``, whose validation set is images, use ``ImageMonitor`` -- the same history fed by a
-row-chunked score -- through the ``ImageMonitored`` mix-in of their states.  Nothing here knows the byte layout of a record: that stays with ``ops``' helpers."""
+row-chunked score -- through the ``ImageMonitored`` mix-in of their states.  ``cocoopfit`` and ``prodafit`` validate cached features through
+their inference forwards: CoCoOp, whose classifier differs per image, feeds an ``ImageMonitor``'s row results from a fused per-image kernel;
+ProDA writes its [N_val, C] logits into a workspace of its own and scores them inside one library call, on a plain ``History``.  TempScaling
+has no monitor: it trains on the validation loader itself, so a per-epoch validation would be its own training loss.  Nothing here knows the
+byte layout of a record: that stays with ``ops``' helpers."""
 from __future__ import annotations
 
 from typing import Optional

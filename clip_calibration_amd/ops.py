@@ -1785,3 +1785,45 @@ def cocoop_step(grad: torch.Tensor, params: torch.Tensor, buf: Optional[torch.Te
     check(lib.clipmi_cocoop_step(grad.data_ptr(), params.data_ptr(), None if buf is None else buf.data_ptr(), int(n_ctx), int(D), int(E), int(H),
                                  lr.data_ptr(), int(bool(first_step)), float(momentum), float(dampening), float(weight_decay), int(bool(nesterov)),
                                  _stream()), "clipmi_cocoop_step")
+
+
+# ---- per-epoch validation of the CoCoOp and ProDA fits (csrc/fit_monitor.hip, csrc/proda_train.hip; DESIGN.md "Fit monitor", "CoCoOp and ProDA")
+COCOOP_VAL_MAX_C = 16384      # cocoop_val_rows_kernel keeps one image's C fp32 logits in LDS
+
+
+def cocoop_val_rows(img_n: torch.Tensor, txt: torch.Tensor, scale: float, labels: torch.Tensor, n_bins: int,
+                    row_results: Optional[torch.Tensor] = None, row0: int = 0) -> torch.Tensor:
+    """clipmi_cocoop_val_rows: CoCoOp's per-pair tail fused into the row score.  ``img_n`` fp32 [Bv, E] unit image features, ``txt`` fp32
+    [Bv, C, E] raw text-encoder outputs, ``labels`` int64 [Bv]: per image the C logits ``scale * <img_n[b], normalise(txt[b, c])>`` are
+    formed in LDS (``logits_per_image``'s bits) and scored as ``val_score_rows`` scores a row, into ``row_results[row0 : row0 + Bv]``; the
+    [Bv, C] logits never go to memory.  Returns ``row_results``."""
+    who = "cocoop_val_rows"
+    n_bins = _val_bins(who, n_bins)
+    img_n = _dev(img_n, "img_n", (torch.float32,))
+    txt = _dev(txt, "txt", (torch.float32,))
+    labels = _dev(labels, "labels", (torch.int64,))
+    if img_n.dim() != 2 or img_n.shape[0] < 1:
+        raise ValueError(f"{who}: img_n {tuple(img_n.shape)} must be [Bv >= 1, E]")
+    B, E = img_n.shape
+    if txt.dim() != 3 or txt.shape[0] != B or txt.shape[2] != E or not 1 <= txt.shape[1] <= COCOOP_VAL_MAX_C:
+        raise ValueError(f"{who}: txt must be [Bv={B}, 1 <= C <= {COCOOP_VAL_MAX_C}, E={E}], got {tuple(txt.shape)}")
+    if labels.shape != (B,):
+        raise ValueError(f"{who}: {B} rows need {B} labels, got {tuple(labels.shape)}")
+    if row_results is None:
+        row_results = new_val_row_results(row0 + B, img_n.device)
+    pr = _row_results(who, row_results, B, row0)
+    check(lib.clipmi_cocoop_val_rows(img_n.data_ptr(), txt.data_ptr(), float(scale), labels.data_ptr(), B, txt.shape[1], E, n_bins, pr, _stream()),
+          "clipmi_cocoop_val_rows")
+    return row_results
+
+
+def proda_val_mean(text: torch.Tensor, group: int) -> torch.Tensor:
+    """clipmi_proda_val_mean: raw text features fp32 [G * group, E] -> fp32 [G, E], the mean over a class's ``group`` L2-normalised rows
+    (not renormalised): the bits of ``group_mean(l2_normalize(text), group)`` in one launch, without the normalised copy."""
+    text = _dev(text, "text", (torch.float32,))
+    rows, E = text.shape
+    if group <= 0 or rows % group or rows == 0:
+        raise ValueError(f"proda_val_mean: {rows} rows do not split into groups of {group}")
+    out = torch.empty(rows // group, E, dtype=torch.float32, device=text.device)
+    check(lib.clipmi_proda_val_mean(text.data_ptr(), out.data_ptr(), rows // group, int(group), E, _stream()), "clipmi_proda_val_mean")
+    return out

@@ -36,6 +36,14 @@ class rows or any context's no-class row -- is an inf or a NaN, and updates the 
 advances on a skipped step as on an applied one (the reference draws it in the forward, before ``GradScaler.step`` decides).  No step
 reads anything back; ``ProDAFitState.scaler_state()`` does, once.  With a scale that never changes the dynamic path gives the static
 path's bits.  DESIGN.md "Dynamic loss scale for ProDA".
+
+Validation: ``fit_context(val=(val_features, val_labels), val_class_chunk=, val_bins=, final_model="last_step" | "best_val",
+val_criterion=, return_monitor=)`` scores the contexts behind every epoch on the device and keeps the contexts of the best epoch in a
+device slot, with no read-back before the run's one wait (``ProDAFitState.validate`` / ``start_monitor`` / ``monitor`` / ``best_params``).
+It scores the test-time classifier (proda.py:316-331; ``trainers.proda.CustomCLIP.set_classifier``): the mean over ALL ``n_prompt``
+contexts at their three positions, of which a training step only ever runs ``prompt_bs`` -- one call, clipmi_proda_val_logits, which
+runs the inference text tower ``val_class_chunk`` classes at a time.  It draws no random number: the selection schedule is the one of
+the fit without ``val``.  DESIGN.md "Fit monitor", "CoCoOp and ProDA".
 """
 from __future__ import annotations
 
@@ -46,7 +54,7 @@ from typing import Optional, Sequence
 import numpy as np
 import torch
 
-from . import _lib, fitloop, ops
+from . import _lib, fitloop, fitmonitor, ops
 from ._lib import check, lib
 from .coopfit import DEFAULT_GRAD_SCALE, DYNAMIC, MAX_LIVE_ROWS, _DT, _BlockScaler, _Tower, _check_batch, _check_grad_scale, _is_dynamic, _live_rows, _scale_args
 from .fitloop import _host_int_array, _need_gpu, steps_per_epoch
@@ -256,6 +264,10 @@ class ProDAFitState:
         self._perm = None
         self.steps = 0
         self._scaler = _BlockScaler(self.scaler, dev) if self.dynamic else None
+        self._ids = ids_all[:self.C]
+        self._mon = None            # the fit monitor's device history, made by start_monitor or the first validate
+        self._val = None            # what a validation keeps between epochs: the inference operands, the set and the two workspaces
+        self.val_class_chunk = None # validate's classes per tower call when its argument is None (None: 4096 // n_prompt, at least 1)
 
     def scaler_state(self) -> dict:
         """The dynamic scale's block as ``dict(scale, growth_tracker, skipped_steps, applied_steps, found_inf)`` (``found_inf``: of the
@@ -263,6 +275,113 @@ class ProDAFitState:
         if not self.dynamic:
             raise ValueError(f"ProDAFitState.scaler_state: the state was made with a static grad_scale={self.grad_scale}")
         return self._scaler.state()
+
+    # ---- per-epoch validation and best-epoch selection on the device (DESIGN.md "Fit monitor", "CoCoOp and ProDA")
+
+    def start_monitor(self, slots: int, val_bins: int = 10, select: bool = False, val_criterion: str = "accuracy") -> None:
+        """The device history ``validate`` writes: ``slots`` epoch records of ``val_bins`` confidence bins and, with ``select``, the best
+        block and the best slot -- a copy of the master ``ctx`` [P, n_ctx, D] as it is now, replaced whenever a validated epoch is strictly
+        better under ``val_criterion``.  The momentum buffer and the scaler block are not selected.  Allocations and one small upload;
+        nothing synchronises."""
+        self._mon = fitmonitor.History("ProDAFitState.start_monitor", slots, val_bins, val_criterion, self.ctx.reshape(-1) if select else None,
+                                       self.ctx.device)
+
+    def _val_operands(self):
+        """What the inference mirror (``trainers.proda.CustomCLIP.set_classifier``) works on, made once: the classes' embeddings
+        [C, context_length, D] in the model's type, the order of a class's prompts (ALL contexts, end | middle | front) and the live
+        token rows of the class list."""
+        if self._val is None:
+            m = self.tower.model
+            m._ensure_bound()
+            ids_h = torch.from_numpy(np.ascontiguousarray(self._ids)).long()
+            with torch.no_grad():
+                base = m.token_embedding(ids_h.to(m.device)).type(m.dtype).contiguous()
+            order = torch.from_numpy(reference_order(np.arange(self.P), self.pos_host)).to(m.device)
+            self._val = {"base": base, "order": order, "rows": m.live_rows(ids_h), "set": None, "ws": None, "mon_ws": None}
+        return self._val
+
+    def validate(self, val_features: torch.Tensor, val_labels, epoch: int, val_class_chunk: Optional[int] = None) -> None:
+        """Enqueue one validation of the current master contexts into slot ``epoch`` of the device history; no host read, and no random
+        number is drawn: the selection schedule is not touched.  It scores what ``trainers.proda.CustomCLIP`` would compute with these
+        contexts (proda.py:316-331, 304-313): ALL ``n_prompt`` contexts at their positions, rounded to the model's type as loading them into
+        the module rounds them, through the INFERENCE text tower ``val_class_chunk`` classes at a time (None: as many as keep a call at or
+        below 4096 prompts, ``CustomCLIP``'s ``prompts_per_call``), every feature L2-normalised and a class's ``n_prompt`` features
+        averaged (not renormalised), then ``exp(logit_scale)`` times the normalised ``val_features`` (raw image features fp32
+        [N_val, E] on the GPU) against the means into the monitor's [N_val, C] workspace (4 N_val C bytes), ``clipmi_val_score`` into
+        the record and, when the monitor selects, ``clipmi_best_select`` of ``ctx`` -- one library call, clipmi_proda_val_logits.  The
+        record does not depend on ``val_class_chunk`` as long as the tower's kernel choice, which follows the row count of a call, does
+        not change (include/clipmi.h).  ``val_labels`` [N_val]: an int64 tensor on the GPU is taken as it is; anything else is
+        range-checked on the host.  The contexts, the momentum buffer, the scaler block and the training stash are not touched.  The
+        classes' name lengths are the state's (``name_lens``); the inference mirror derives its own from the EOT rows, which is the
+        state's default.  Without ``start_monitor`` the history starts with ``epoch + 1`` slots of 10 bins and no selection."""
+        who = "ProDAFitState.validate"
+        if self._mon is None:
+            self.start_monitor(int(epoch) + 1 if isinstance(epoch, int) and epoch >= 0 else 1)
+        mon, t, m = self._mon, self.tower, self.tower.model
+        epoch = mon.slot(who, epoch)
+        if val_class_chunk is None:
+            val_class_chunk = self.val_class_chunk
+        cc = max(1, 4096 // self.P) if val_class_chunk is None else val_class_chunk
+        if isinstance(cc, bool) or int(cc) != cc or int(cc) < 1:
+            raise ValueError(f"{who}: val_class_chunk={val_class_chunk} must be an integer >= 1")
+        cc = min(int(cc), self.C)
+        if not isinstance(val_features, torch.Tensor) or val_features.dim() != 2 or val_features.shape[0] < 1 or val_features.shape[1] != t.E:
+            raise ValueError(f"{who}: val_features {tuple(getattr(val_features, 'shape', ()))} must be [N_val >= 1, E = {t.E}]")
+        _need_gpu(val_features, "val_features")
+        v = self._val_operands()
+        key = (val_features.data_ptr(), val_features._version, tuple(val_features.shape), tuple(val_features.stride()), val_features.dtype,
+               id(val_labels), getattr(val_labels, "_version", None))
+        if v["set"] is None or v["set"][0] != key:
+            labels_d = fitloop.step_labels(who, val_labels, val_features.shape[0], self.C, val_features.device, "validation rows")
+            feats = val_features.detach().to(torch.float32).contiguous()
+            if feats.data_ptr() % 16:
+                feats = feats.clone()
+            v["set"] = (key, feats, labels_d, val_labels)
+        _, feats, labels_d, _ = v["set"]
+        N, dev = feats.shape[0], feats.device
+        need = lib.clipmi_proda_val_logits_bytes(m._handle, self.C, self.P, v["rows"], cc, N)
+        mon_need = lib.clipmi_proda_val_monitor_bytes(N, self.C, mon.bins)
+        if need == 0 or mon_need == 0:
+            raise ValueError(f"{who}: N_val={N}, C={self.C}, n_prompt={self.P}, val_class_chunk={cc} are more than one validation call takes")
+        if v["ws"] is None or v["ws"].numel() < need:
+            v["ws"] = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+        if v["mon_ws"] is None or v["mon_ws"].numel() < mon_need:
+            v["mon_ws"] = torch.empty(max(mon_need, 256), dtype=torch.uint8, device=dev)
+        v["n_val"] = N
+        select = mon.block is not None
+        with m._launch_lock:
+            check(lib.clipmi_proda_val_logits(m._handle, v["base"].data_ptr(), _DT[v["base"].dtype], self.ctx.data_ptr(), v["order"].data_ptr(),
+                                              t.pos.data_ptr(), t.name_lens.data_ptr(), t.cls_eot.data_ptr(), self.C, self.P, self.n_ctx, v["rows"], cc,
+                                              self.scale, _lib.CALL_DEFAULT, epoch, feats.data_ptr(), feats.stride(0), labels_d.data_ptr(), N, mon.bins,
+                                              mon.records.data_ptr(), ops.VAL_CRITERIA[mon.criterion], mon.block.data_ptr() if select else None,
+                                              mon.best.data_ptr() if select else None, v["mon_ws"].data_ptr(), v["mon_ws"].numel(),
+                                              v["ws"].data_ptr(), v["ws"].numel(), ops._stream()), "clipmi_proda_val_logits")
+        mon.seen = max(mon.seen, epoch + 1)
+
+    def val_logits(self) -> torch.Tensor:
+        """The fp32 [N_val, C] logits of the last ``validate``, where the monitor's workspace keeps them (the next one overwrites them)."""
+        if self._val is None or self._val.get("mon_ws") is None:
+            raise ValueError("ProDAFitState.val_logits: nothing has been validated")
+        N = self._val["n_val"]
+        return self._val["mon_ws"][:4 * N * self.C].view(torch.float32).view(N, self.C)
+
+    def monitor(self) -> dict:
+        """The history as numbers (``fitmonitor.monitor_dict``, the dict ``CoOpFitState.monitor`` returns).  It reads the history back:
+        one synchronisation."""
+        return fitmonitor.empty_monitor() if self._mon is None or not self._mon.seen else self._mon.summary()
+
+    def monitor_records(self) -> torch.Tensor:
+        """The device history, uint8 [slots, ops.val_record_bytes(val_bins)]; no read-back."""
+        if self._mon is None:
+            raise ValueError("ProDAFitState.monitor_records: nothing has been validated")
+        return self._mon.records
+
+    def best_params(self) -> torch.Tensor:
+        """The best slot on the device, fp32 [P, n_ctx, D]: the contexts of the best epoch so far, or the contexts ``start_monitor`` saw
+        while no epoch has been taken."""
+        if self._mon is None or self._mon.best is None:
+            raise ValueError("ProDAFitState.best_params: the monitor does not select (start_monitor(..., select=True))")
+        return self._mon.best.view_as(self.ctx)
 
     def next_selection(self) -> np.ndarray:
         """The schedule's next slice (``draw_selections``, one step at a time)."""
@@ -358,8 +477,9 @@ def fit_context(features: torch.Tensor, labels, clip_model, tokenized_prompts, c
                 prompt_bs: int = 4, alpha: float = 0.1, logit_scale: float = 4.6052, lr: float = 0.002, epochs: int = 200, batch_size: int = 32,
                 momentum: float = 0.9, dampening: float = 0.0, weight_decay: float = 5e-4, nesterov: bool = False,
                 grad_scale: float = DEFAULT_GRAD_SCALE, seq_rows: Optional[int] = None, lr_per_epoch: Optional[Sequence[float]] = None, order=None,
-                drop_last: bool = False, name_lens=None, selections=None, generator: Optional[torch.Generator] = None, return_history: bool = False,
-                scaler: Optional[dict] = None, return_scaler_state: bool = False):
+                drop_last: bool = False, name_lens=None, selections=None, generator: Optional[torch.Generator] = None, val=None,
+                val_class_chunk: Optional[int] = None, val_bins: int = 10, final_model: str = "last_step", val_criterion: str = "accuracy",
+                return_monitor: bool = False, return_history: bool = False, scaler: Optional[dict] = None, return_scaler_state: bool = False):
     """Train ProDA's contexts on cached ``features`` fp32 [N, E] and ``labels`` [N], starting from ``ctx`` [n_prompt, n_ctx, D] (not
     modified; None = ``init_context(clip_model, n_ctx, n_prompt)``).  The loop and its arguments are ``coopfit.fit_context``'s:
     ``epochs`` passes of ``torch.optim.SGD`` over batches of ``batch_size``, ``lr_per_epoch`` (None: ``cosine_warmup_schedule``),
@@ -367,8 +487,22 @@ def fit_context(features: torch.Tensor, labels, clip_model, tokenized_prompts, c
     one wait at the end.  ``selections``: an int array [steps, prompt_bs] that replaces the schedule drawn from ``generator`` (None: a
     generator seeded with 0).  ``grad_scale="dynamic"`` with ``scaler`` (module docstring): a step that overflows fp16 is skipped on the
     device and the scale adapts; the schedule of rates and selections moves on over a skipped step.  Returns the fitted fp32 contexts on the device, or ``(ctx, per-step total losses)`` with
-    ``return_history``; ``return_scaler_state`` (dynamic only) appends ``ProDAFitState.scaler_state()`` as read after the last step.  The defaults are unverified restatements of the reference's config (module docstring)."""
+    ``return_history``; ``return_scaler_state`` (dynamic only) appends ``ProDAFitState.scaler_state()`` as read after the last step.  The defaults are unverified restatements of the reference's config (module docstring).
+
+    ``val=(val_features, val_labels)`` (raw image features [N_val, E] on the GPU and their labels): behind the last step of every epoch
+    ``ProDAFitState.validate`` scores the contexts against them on the device as the inference mirror would -- the mean over ALL
+    ``n_prompt`` contexts, ``val_class_chunk`` classes per tower call -- into ``val_bins`` confidence bins; it draws no random number, so
+    the fitted contexts and the sequence of selections are bit for bit those of the same call without ``val``, and the run still
+    synchronises once.  ``final_model``, ``val_criterion`` and ``return_monitor`` as ``coopfit.fit_context`` takes them: "best_val" returns
+    the contexts of the epoch that was strictly better than every earlier one (the starting contexts when no epoch was taken) and is
+    refused without ``val``; ``return_monitor`` adds ``ProDAFitState.monitor()``'s dict as the last element of the result.  The six
+    validation arguments stand in front of ``return_history`` (``scaler`` and ``return_scaler_state`` stay the signature's last two): pass
+    them, and the three behind them, by keyword."""
     who = "fit_context"
+    fitmonitor.check_args(who, val, val_bins, final_model, val_criterion)
+    if val is not None and val_class_chunk is not None and (isinstance(val_class_chunk, bool) or int(val_class_chunk) != val_class_chunk
+                                                            or int(val_class_chunk) < 1):
+        raise ValueError(f"{who}: val_class_chunk={val_class_chunk} must be an integer >= 1")
     if ctx is None:
         _check_collection(who, int(n_prompt), int(prompt_bs))
         ctx = init_context(clip_model, n_ctx, n_prompt)
@@ -396,22 +530,33 @@ def fit_context(features: torch.Tensor, labels, clip_model, tokenized_prompts, c
         sels = _check_sel(who, selections, P, positions(P), "selections")
         if sels.ndim != 2 or sels.shape != (steps, int(prompt_bs)):
             raise ValueError(f"{who}: selections {sels.shape} must be [steps, prompt_bs] = [{steps}, {int(prompt_bs)}]")
+    if val is not None:
+        vf, vl = fitmonitor.check_val(who, val, E, Cn)
     if steps == 0:
         out = ctx.detach().to(torch.float32).clone()
-        out = out.to(dev) if features.is_cuda else out
-        out = (out, np.zeros(0, np.float32)) if return_history else out
+        out = (out.to(dev) if features.is_cuda else out,) + ((np.zeros(0, np.float32),) if return_history else ())
         if return_scaler_state:
-            untouched = {"scale": cfg["init_scale"], "growth_tracker": 0, "skipped_steps": 0, "applied_steps": 0, "found_inf": 0}
-            return (out + (untouched,)) if return_history else (out, untouched)
-        return out
+            out += ({"scale": cfg["init_scale"], "growth_tracker": 0, "skipped_steps": 0, "applied_steps": 0, "found_inf": 0},)
+        if return_monitor:
+            out += (fitmonitor.empty_monitor(val_bins),)
+        return out if len(out) > 1 else out[0]
     _need_gpu(features, "features")
     state = ProDAFitState(clip_model, tokenized_prompts, ctx, prompt_bs, alpha, logit_scale, momentum, dampening, nesterov, weight_decay, grad_scale,
                           seq_rows, name_lens, scaler=scaler)
     sels_d = torch.from_numpy(np.ascontiguousarray(sels, dtype=np.int32)).to(dev)
+    end_epoch = None
+    if val is not None:
+        _need_gpu(vf, "val_features")
+        vl = vl.to(vf.device)
+        state.start_monitor(epochs, val_bins, final_model == "best_val", val_criterion)
+        end_epoch = lambda e: state.validate(vf, vl, e, val_class_chunk)
     history = fitloop.run_cached(lambda f, y, r, want: state.step(f, y, r, sel=sels_d[state.steps], want_loss=want), features,
                                  fitloop.labels_on(labels, lab, dev), fitloop.order_on(order, np.int64, dev), batch_size, per_epoch, epochs, lr_steps,
-                                 return_history)
-    out = (state.ctx, history) if return_history else (state.ctx,)
+                                 return_history, end_epoch)
+    fitted = state.best_params() if final_model == "best_val" else state.ctx
+    out = (fitted, history) if return_history else (fitted,)
     if return_scaler_state:
         out = out + (state.scaler_state(),)
+    if return_monitor:
+        out = out + (state.monitor() if val is not None else fitmonitor.empty_monitor(val_bins),)
     return out if len(out) > 1 else out[0]

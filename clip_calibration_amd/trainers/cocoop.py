@@ -118,23 +118,41 @@ class CustomCLIP(nn.Module):
         yields (decoded uint8 images, labels) and is iterated once per epoch, every batch going transform -> image tower ->
         ``CoCoOpFitState.step`` (``augment.fit_with_transform``); ``fit_args`` are then ``epochs``, ``lr``, ``lr_per_epoch``, ``views``,
         ``return_history`` and ``CoCoOpFitState``'s own.  ``grad_scale="dynamic"`` with ``scaler=dict(init_scale, growth_factor,
-        backoff_factor, growth_interval)`` on either route: the device-side loss scale (``cocoopfit``'s module docstring)."""
+        backoff_factor, growth_interval)`` on either route: the device-side loss scale (``cocoopfit``'s module docstring).
+
+        Validation, on either route: ``val_loader=`` (an iterable of (image, label) batches of test-transformed images, run through the
+        frozen image tower once before the first epoch) or ``val=(val_features, val_labels)``, with ``val_batch_size`` (images per
+        validation chunk), ``val_bins``, ``final_model`` ("last_step" or "best_val", the reference's TEST.FINAL_MODEL),
+        ``val_criterion`` and ``return_monitor`` as ``cocoopfit.fit_prompt_learner`` takes them; ``CoCoOpFitState.validate`` runs behind
+        every epoch and scores what this module's ``forward`` would compute.  ``final_model="best_val"`` installs the best epoch's
+        tensors into the module."""
         import math
         from ..cocoopfit import NAMES
+        who = "fit_prompt_learner"
+        _fit.validation_set(who, self.clip_model, fit_args)
         fit_args.setdefault("logit_scale", math.log(self.scale))
         pl = self.prompt_learner
         params = {k: v.detach() for k, v in pl.state_dict().items() if k in NAMES}
         ids = pl.tokenized_prompts
         if transform is not None:
-            from ..augment import fit_with_transform
             from ..cocoopfit import CoCoOpFitState
             run, epochs, lr = _fit.split_fit_args(fit_args, 10, 0.002)
+            E = int(self.clip_model.geometry.embed_dim)
+            watch = _fit.split_monitor_args(who, fit_args, ids.shape[0], E)
+            val_batch_size = fit_args.pop("val_batch_size", None)
+            if watch[0] is not None and val_batch_size is not None:
+                from ..fitmonitor import _batch_size
+                _batch_size(who, val_batch_size)
             state = CoCoOpFitState(self.clip_model, ids, params, **fit_args)
-            losses = fit_with_transform(state, self.clip_model.image_features_f32, ids.shape[0], train_loader, transform, epochs, lr, **run)
-            fitted = _fit.pack(state.params(), losses)
+            state.val_stream_f16, state.val_batch_size = self.text_stream_f16, val_batch_size
+            losses, monitor = _fit.run_with_transform(who, state, self.clip_model, ids.shape[0], E, train_loader, transform, epochs, lr, run, watch)
+            fitted = _fit.pack(state.best_params() if watch[2] else state.params(), losses)
+            if monitor is not None:
+                fitted = fitted + (monitor,) if isinstance(fitted, tuple) else (fitted, monitor)
         else:
             from ..cocoopfit import fit_prompt_learner
-            feats, labels = _fit.cached_features("fit_prompt_learner", self.clip_model, train_loader)
+            feats, labels = _fit.cached_features(who, self.clip_model, train_loader)
+            fit_args.setdefault("val_stream_f16", self.text_stream_f16)
             fitted = fit_prompt_learner(feats, labels, self.clip_model, ids, params, **fit_args)
         values = fitted[0] if isinstance(fitted, tuple) else fitted
         target = dict(pl.named_parameters())

@@ -108,28 +108,42 @@ class CustomCLIP(nn.Module):
         the reference's loop only for a deterministic train transform.  ``transform=TrainPreprocess(...)``: ``train_loader`` yields
         (decoded uint8 images, labels) and is iterated once per epoch, every batch going transform -> image tower ->
         ``ProDAFitState.step`` (``augment.fit_with_transform``); ``fit_args`` are then ``epochs``, ``lr``, ``lr_per_epoch``, ``views``,
-        ``return_history`` and ``ProDAFitState``'s own."""
+        ``return_history`` and ``ProDAFitState``'s own.
+
+        Validation, on either route: ``val_loader=`` (an iterable of (image, label) batches of test-transformed images, run through the
+        frozen image tower once before the first epoch) or ``val=(val_features, val_labels)``, with ``val_class_chunk`` (classes per
+        tower call), ``val_bins``, ``final_model`` ("last_step" or "best_val", the reference's TEST.FINAL_MODEL), ``val_criterion`` and
+        ``return_monitor`` as ``prodafit.fit_context`` takes them; ``ProDAFitState.validate`` runs behind every epoch and scores what
+        ``set_classifier`` + ``forward`` would compute.  ``final_model="best_val"`` installs the best epoch's contexts."""
         import math
+        who = "fit_context"
+        _fit.validation_set(who, self.clip_model, fit_args)
         fit_args.setdefault("logit_scale", math.log(self.scale))
         dynamic = fit_args.get("grad_scale") == "dynamic"
         self._scaler_state = None
         ctx = self.prompt_learner.ctx
         ids = self.prompt_learner.tokenized_prompts
         if transform is not None:
-            from ..augment import fit_with_transform
             from ..prodafit import ProDAFitState
             run, epochs, lr = _fit.split_fit_args(fit_args, 200, 0.002)
+            E = int(self.clip_model.geometry.embed_dim)
+            watch = _fit.split_monitor_args(who, fit_args, ids.shape[0], E)
+            val_class_chunk = fit_args.pop("val_class_chunk", None)
             state = ProDAFitState(self.clip_model, ids, ctx.detach(), **fit_args)
-            losses = fit_with_transform(state, self.clip_model.image_features_f32, ids.shape[0], train_loader, transform, epochs, lr, **run)
-            fitted = _fit.pack(state.ctx, losses)
+            state.val_class_chunk = val_class_chunk
+            losses, monitor = _fit.run_with_transform(who, state, self.clip_model, ids.shape[0], E, train_loader, transform, epochs, lr, run, watch)
+            fitted = _fit.pack(state.best_params() if watch[2] else state.ctx, losses)
+            if monitor is not None:
+                fitted = fitted + (monitor,) if isinstance(fitted, tuple) else (fitted, monitor)
             if dynamic:
                 self._scaler_state = state.scaler_state()
         else:
             from ..prodafit import fit_context
-            feats, labels = _fit.cached_features("fit_context", self.clip_model, train_loader)
+            feats, labels = _fit.cached_features(who, self.clip_model, train_loader)
             fitted = fit_context(feats, labels, self.clip_model, ids, ctx.detach(), return_scaler_state=dynamic, **fit_args)
-            if dynamic:
-                *fitted, self._scaler_state = fitted
+            if dynamic:      # the scaler's state sits behind the history and in front of the monitor's dict
+                fitted = list(fitted)
+                self._scaler_state = fitted.pop(1 + int(bool(fit_args.get("return_history"))))
                 fitted = tuple(fitted) if len(fitted) > 1 else fitted[0]
         with torch.no_grad():
             ctx.copy_(fitted[0] if isinstance(fitted, tuple) else fitted)

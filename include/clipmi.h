@@ -1589,7 +1589,54 @@ int clipmi_probe_mfma_f16(const void* operands, float* sink, unsigned long long*
  * first row, as above) -- the same launches as the four calls, hence the same bits.  workspace (256-byte aligned):
  * clipmi_vision_val_chunk_bytes(m, B, n_ctx, C) = the tower's + 2 x align256(4 B E) + align256(4 B C); 0 for arguments the call refuses.
  * Every check precedes the first launch: clipmi_vision_encoder_train's, clipmi_val_score_rows', B >= 1, a finite scale.
+ *
+ * CoCoOp (every image has its own C prompts, so an [N_val, C] text matrix never exists) and ProDA (the classifier is the mean over ALL P
+ * contexts) validate through the INFERENCE forward: the record is what clipmi_val_score gives on the trainers' forward logits.
+ *
+ * clipmi_cocoop_val_rows: the per-pair tail fused into the row score.  img_n fp32 [Bv, E] (unit image features), txt fp32 [Bv, C, E] (raw
+ * text-encoder outputs, image-major).  One workgroup per image b: z[c] = scale * <img_n[b], txt[b, c] / |txt[b, c]|> by one wave per class
+ * (clipmi_logits_per_image's device function, the same bits) into C fp32 values in LDS, then clipmi_val_score's per-row device function on
+ * them against labels[b]; row_results[b] is written and nothing else -- the [Bv, C] logits never go to memory.  C <= 16384 (LDS).
+ * CLIPMI_ERR_ARG: a null pointer, row_results not 16-byte aligned, labels not 8-byte aligned, n_bins outside 1..64, a non-finite scale;
+ * CLIPMI_ERR_SHAPE: Bv < 1, E < 1, C outside 1..16384.
+ *
+ * clipmi_cocoop_val_chunk: one chunk of Bv validation images in one call, the launches of the inference forward (cocoop.py:186-199):
+ * clipmi_cocoop_ctx (params: the fit's master block [ctx | W1 | b1 | W2 | b2]; img_n fp32 [Bv, E] contiguous, already normalised),
+ * clipmi_cocoop_prompts (base [C, context_length, Dt] fp16 | fp32 -> fp16 prompts), clipmi_text_encoder over the Bv C prompts (eot int32
+ * [Bv C]: the classes' EOT rows repeated per image; seq_rows and flags as that call takes them), clipmi_cocoop_val_rows into row_results
+ * (the caller's pointer for the chunk's first row; labels: the chunk's).  clipmi_val_score_finish then builds the record.  workspace
+ * (256-byte aligned): clipmi_cocoop_val_chunk_bytes(m, C, seq_rows, Bv, n_ctx) = the tower's + 4 Bv n_ctx Dt + 2 Bv C context_length Dt +
+ * 4 Bv C E, each part rounded up to 256; 0 for arguments the call refuses.  Every check precedes the first launch.
+ *
+ * clipmi_proda_val_mean: text fp32 [G P, E] (raw text features, a class's P rows together) -> mean fp32 [G, E]: every row times the
+ * reciprocal of its L2 norm (clipmi_l2_normalize's order and rounding), a class's P unit rows added in ascending row order from 0 and the
+ * sum divided by P (clipmi_group_mean's) -- the bits of those two calls, without the normalised copy.  fp32, no atomics.  P <= 4096.
+ *
+ * clipmi_proda_val_logits: one validation in one call (proda.py:316-331, 304-313).  For classes c0, c0 + class_chunk, ...: the prompts of
+ * ALL P contexts at their positions `pos` in the order `order` int32 [P] (end | middle | front, the inference mirror's), assembled in the
+ * model's type `dtype` with the fp32 master ctx [P, n_ctx, Dt] rounded to it (clipmi_proda_embed's placement, one shared device function;
+ * no selection, no no-class prompts), clipmi_text_encoder, clipmi_proda_val_mean into mean [C, E]; then clipmi_fused_tail of the raw
+ * validation features val_feats fp32 [n_val, E] (contiguous, 16-byte aligned) against mean -- exp(logit_scale) x_n . mean_c, the mean not
+ * renormalised -- into the head of monitor_workspace, fp32 [n_val, C]; then clipmi_val_score into record `epoch` of `records` and, with a best
+ * block, clipmi_best_select of ctx (the arguments from val_labels on are clipmi_taskres_fit_monitored's).  monitor_workspace:
+ * clipmi_proda_val_monitor_bytes(n_val, C, n_bins) = 4 n_val C rounded up to 256 + clipmi_val_score's + the decision word.  workspace:
+ * clipmi_proda_val_logits_bytes(m, C, P, seq_rows, class_chunk, n_val); both sizers return 0 for arguments the call refuses.  The tower's
+ * kernel choice follows the row count of a call (clipmi_encode_image's note): chunkings that keep the choice give the same bits.
  * ---------------------------------------------------------------------------------------------------- */
+int clipmi_cocoop_val_rows(const float* img_n, const float* txt, float scale, const int64_t* labels, int Bv, int C, int E, int n_bins,
+                           void* row_results, clipmi_stream_t stream);
+size_t clipmi_cocoop_val_chunk_bytes(const clipmi_model* m, int C, int seq_rows, int Bv, int n_ctx);
+int clipmi_cocoop_val_chunk(clipmi_model* m, const void* base, int dtype, const float* params, int n_ctx, int H, const int32_t* eot, int C,
+                            int seq_rows, const float* img_n, int Bv, float scale, const int64_t* labels, int n_bins, void* row_results,
+                            unsigned flags, void* workspace, size_t workspace_bytes, clipmi_stream_t stream);
+int clipmi_proda_val_mean(const float* text, float* mean, int G, int P, int E, clipmi_stream_t stream);
+size_t clipmi_proda_val_monitor_bytes(int n_val, int C, int n_bins);
+size_t clipmi_proda_val_logits_bytes(const clipmi_model* m, int C, int P, int seq_rows, int class_chunk, int n_val);
+int clipmi_proda_val_logits(clipmi_model* m, const void* base, int dtype, const float* ctx, const int32_t* order, const int32_t* pos,
+                            const int32_t* name_lens, const int32_t* cls_eot, int C, int P, int n_ctx, int seq_rows, int class_chunk, float scale,
+                            unsigned flags, int epoch, const float* val_feats, int64_t val_ld, const int64_t* val_labels, int n_val, int n_bins,
+                            void* records, int criterion, void* best_block, float* best_params, void* monitor_workspace,
+                            size_t monitor_workspace_bytes, void* workspace, size_t workspace_bytes, clipmi_stream_t stream);
 int clipmi_val_score_rows(const float* logits, int64_t ld, const int64_t* labels, int rows, int C, int n_bins, void* row_results,
                           clipmi_stream_t stream);
 size_t clipmi_val_score_finish_workspace_bytes(int N, int n_bins);
