@@ -98,7 +98,7 @@ def fit_adapter(features: torch.Tensor, labels, text_features: torch.Tensor, w1:
         _need_gpu(vf, "val_features")
         mon = fitmonitor.Monitor(who, epochs, val_bins, val_criterion, block if final_model == "best_val" else None, dev)
         mon.seen = epochs
-        monitor = ops.fit_monitor(vf if vf.dtype == torch.float32 else vf.float(), vl.to(dev), mon.bins, mon.records, val_criterion, mon.block,
+        monitor = ops.fit_monitor(fitmonitor._fp32(vf), vl.to(dev), mon.bins, mon.records, val_criterion, mon.block,
                                   mon.best)
     losses = ops.adapter_fit(features, fitloop.labels_on(labels, lab, dev), text_features, w1, w2, m1, m2, lr_steps, ratio,
                              float(np.float32(math.exp(logit_scale))), batch_size, epochs, momentum, dampening, weight_decay, nesterov,
@@ -107,14 +107,17 @@ def fit_adapter(features: torch.Tensor, labels, text_features: torch.Tensor, w1:
     if final_model == "best_val":
         w1, w2 = mon.best[:w1.numel()].view(w1.shape), mon.best[w1.numel():].view(w2.shape)
     return fitmonitor.pack((w1, w2), losses.cpu().numpy() if return_history else None,
-                           (mon.summary() if mon is not None else fitmonitor.empty_monitor(val_bins)) if return_monitor else None,
+                           fitmonitor.returned_monitor(mon, mon is not None, val_bins, return_monitor),
                            return_history, return_monitor)
 
 
-class AdapterFitState:
+class AdapterFitState(fitmonitor.Monitored):
     """The training state of CLIP-Adapter's bottleneck for callers that produce the image features step by step (a random train
     transform: the image tower runs on every batch): fp32 master weights ``w1`` [H, E], ``w2`` [E, H], their momentum buffers and the
-    number of steps taken.  ``step`` enqueues one forward, backward and SGD update and does not synchronise."""
+    number of steps taken.  ``step`` enqueues one forward, backward and SGD update and does not synchronise.  ``validate`` scores cached
+    validation features on the device (``start_monitor``, ``monitor``, ``best_weights``, ``val_logits``: ``fitmonitor.Monitored`` on a
+    ``fitmonitor.Monitor``)."""
+    _who, _unseen_summary = "AdapterFitState", True
 
     def __init__(self, text_features: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor, ratio: float = 0.2, logit_scale: float = 4.6052,
                  momentum: float = 0.9, dampening: float = 0.0, weight_decay: float = 5e-4, nesterov: bool = False):
@@ -132,16 +135,11 @@ class AdapterFitState:
         self.ratio, self.scale = float(ratio), float(np.float32(math.exp(logit_scale)))
         self.momentum, self.dampening, self.weight_decay, self.nesterov = momentum, dampening, weight_decay, nesterov
         self.steps = 0
-        self._mon = None    # the fit monitor's device history, made by start_monitor or the first validate
 
-    # ---- per-epoch validation and best-epoch selection on the device (DESIGN.md "Fit monitor"), as CoOpFitState has them
+    # ---- per-epoch validation and best-epoch selection on the device (DESIGN.md "Fit monitor")
 
-    def start_monitor(self, slots: int, val_bins: int = 10, select: bool = False, val_criterion: str = "accuracy") -> None:
-        """The device history ``validate`` writes: ``slots`` epoch records of ``val_bins`` confidence bins and, with ``select``, the best
-        block and the best slot (a copy of [w1 | w2] as they are now, replaced whenever an epoch is strictly better under
-        ``val_criterion``).  Allocations and one small upload; nothing synchronises."""
-        self._mon = fitmonitor.Monitor("AdapterFitState.start_monitor", slots, val_bins, val_criterion, self._block if select else None,
-                                       self._block.device)
+    def _master(self) -> torch.Tensor:
+        return self._block      # [w1 | w2]
 
     def validate(self, val_features: torch.Tensor, val_labels, epoch: int) -> None:
         """Enqueue one validation of the current master weights into slot ``epoch`` of the device history; no host read.
@@ -152,38 +150,17 @@ class AdapterFitState:
         with a NaN nll), anything else is range-checked on the host, once per set.  Without ``start_monitor`` the history starts with
         ``epoch + 1`` slots of 10 bins and no selection; it grows when ``epoch`` lies behind its end."""
         who = "AdapterFitState.validate"
-        if self._mon is None:
-            self.start_monitor(int(epoch) + 1 if isinstance(epoch, int) and epoch >= 0 else 1)
-        mon = self._mon
+        mon = self._monitor_for(epoch)
         epoch = mon.slot(who, epoch)
         feats, labels_d = mon.operands(who, val_features, val_labels, self.w1.shape[1], self.text_features.shape[0])
         ops.adapter_val_logits(feats, self.text_features, self.w1, self.w2, self.ratio, self.scale, out=mon.logits)
         mon.score(epoch, labels_d, self._block)
 
-    def val_logits(self) -> torch.Tensor:
-        """The fp32 [N_val, C] logits of the last ``validate``, where the state keeps them (the next ``validate`` overwrites them)."""
-        if self._mon is None or self._mon.logits is None:
-            raise ValueError("AdapterFitState.val_logits: nothing has been validated")
-        return self._mon.logits
-
     def best_weights(self):
         """``(w1, w2)`` of the best slot on the device: the weights of the best epoch so far, or those ``start_monitor`` saw while no
         epoch has been taken.  No read-back."""
-        if self._mon is None or self._mon.best is None:
-            raise ValueError("AdapterFitState.best_weights: the monitor does not select (start_monitor(..., select=True))")
-        k = self.w1.numel()
-        return self._mon.best[:k].view(self.w1.shape), self._mon.best[k:].view(self.w2.shape)
-
-    def monitor_records(self) -> torch.Tensor:
-        """The device history, uint8 [slots, ops.val_record_bytes(val_bins)]; no read-back."""
-        if self._mon is None:
-            raise ValueError("AdapterFitState.monitor_records: nothing has been validated")
-        return self._mon.records
-
-    def monitor(self) -> dict:
-        """The history as numbers (``fitmonitor.monitor_dict``, the dict ``CoOpFitState.monitor`` returns).  It reads the history back:
-        one synchronisation."""
-        return fitmonitor.empty_monitor() if self._mon is None else self._mon.summary()
+        best, k = self._best_block("best_weights"), self.w1.numel()
+        return best[:k].view(self.w1.shape), best[k:].view(self.w2.shape)
 
     def step(self, features: torch.Tensor, labels, lr, want_loss: bool = False) -> Optional[torch.Tensor]:
         """One SGD step on the batch ``features`` fp32 [B, E] (raw image features on the GPU) and ``labels`` [B] at the rate ``lr``: an fp32

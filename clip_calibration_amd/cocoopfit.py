@@ -177,10 +177,12 @@ def gradients(clip_model, tokenized_prompts, params, features: torch.Tensor, lab
     return out
 
 
-class CoCoOpFitState:
+class CoCoOpFitState(fitmonitor.Monitored):
     """The training state of CoCoOp's prompt learner: the fp32 master block ``[ctx | W1 | b1 | W2 | b2]``, SGD's momentum block, the
     tower's stash (one per batch size seen) and the number of steps taken.  ``step`` enqueues one forward, backward and update and does
-    not synchronise."""
+    not synchronise.  ``validate`` scores cached validation features through the inference forward (``start_monitor``, ``monitor``,
+    ``best_params``, ``val_row_results``: ``fitmonitor.Monitored`` on a ``fitmonitor.ImageMonitor``, whose row results it fills)."""
+    _who, _history = "CoCoOpFitState", fitmonitor.ImageMonitor
 
     def __init__(self, clip_model, tokenized_prompts, params, logit_scale: float = 4.6052, momentum: float = 0.9, dampening: float = 0.0,
                  weight_decay: float = 5e-4, nesterov: bool = False, grad_scale: float = DEFAULT_GRAD_SCALE, seq_rows: Optional[int] = None,
@@ -204,8 +206,7 @@ class CoCoOpFitState:
         self._towers: Dict[int, _CoCoOpTower] = {}
         self.steps = 0
         self._scaler = _BlockScaler(self.scaler, dev) if self.dynamic else None
-        self._mon = None            # the fit monitor's device history, made by start_monitor or the first validate
-        self._val = None            # what a validation keeps between epochs: the inference operands, the set, one workspace per chunk size
+        self._val = None            # what a validation keeps between epochs: the inference operands and one workspace per chunk size
         self.val_stream_f16 = True  # trainers.cocoop.CustomCLIP's text_stream_f16: validation runs the tower as that forward does
         self.val_batch_size = None  # validate's chunk when its argument is None (None: the largest training batch seen)
 
@@ -218,13 +219,8 @@ class CoCoOpFitState:
 
     # ---- per-epoch validation and best-epoch selection on the device (DESIGN.md "Fit monitor", "CoCoOp and ProDA")
 
-    def start_monitor(self, slots: int, val_bins: int = 10, select: bool = False, val_criterion: str = "accuracy") -> None:
-        """The device history ``validate`` writes: ``slots`` epoch records of ``val_bins`` confidence bins and, with ``select``, the best
-        block and the best slot -- a copy of the master block ``[ctx | W1 | b1 | W2 | b2]`` as it is now, replaced whenever a validated
-        epoch is strictly better under ``val_criterion``.  The momentum block and the scaler block are not selected.  Allocations and one
-        small upload; nothing synchronises."""
-        self._mon = fitmonitor.ImageMonitor("CoCoOpFitState.start_monitor", slots, val_bins, val_criterion, self.block if select else None,
-                                            self.block.device)
+    def _master(self) -> torch.Tensor:
+        return self.block
 
     def _val_operands(self):
         """What the inference forward (``trainers.cocoop.CustomCLIP``) works on, made once: the classes' embeddings [C, context_length, D]
@@ -237,7 +233,7 @@ class CoCoOpFitState:
                 base = m.token_embedding(ids_h.to(m.device)).type(m.dtype).contiguous()
             f16 = self.val_stream_f16 and m.get_option("residual_f16") == 2 and m.get_option("ln_fold") == 1
             self._val = {"base": base, "eot": ids_h.argmax(dim=-1).to(torch.int32), "rows": m.live_rows(ids_h),
-                         "flags": _lib.CALL_STREAM_F16 if f16 else _lib.CALL_DEFAULT, "set": None, "chunks": {}}
+                         "flags": _lib.CALL_STREAM_F16 if f16 else _lib.CALL_DEFAULT, "chunks": {}}
         return self._val
 
     def _val_chunk(self, v: dict, B: int):
@@ -265,23 +261,13 @@ class CoCoOpFitState:
         parameters, the momentum block, the scaler block and the training stash are not touched.  Without ``start_monitor`` the history
         starts with ``epoch + 1`` slots of 10 bins and no selection."""
         who = "CoCoOpFitState.validate"
-        if self._mon is None:
-            self.start_monitor(int(epoch) + 1 if isinstance(epoch, int) and epoch >= 0 else 1)
-        mon, m = self._mon, self.model
+        mon, m = self._monitor_for(epoch), self.model
         epoch = mon.slot(who, epoch)
         if val_batch_size is None:
             val_batch_size = max(self._towers, default=1) if self.val_batch_size is None else self.val_batch_size
         bs = fitmonitor._batch_size(who, val_batch_size)
-        if not isinstance(val_features, torch.Tensor) or val_features.dim() != 2 or val_features.shape[0] < 1 or val_features.shape[1] != self.E:
-            raise ValueError(f"{who}: val_features {tuple(getattr(val_features, 'shape', ()))} must be [N_val >= 1, E = {self.E}]")
-        _need_gpu(val_features, "val_features")
         v = self._val_operands()
-        key = (val_features.data_ptr(), val_features._version, tuple(val_features.shape), tuple(val_features.stride()), val_features.dtype,
-               id(val_labels), getattr(val_labels, "_version", None))
-        if v["set"] is None or v["set"][0] != key:
-            labels_d = fitloop.step_labels(who, val_labels, val_features.shape[0], self.C, val_features.device, "validation rows")
-            v["set"] = (key, ops.l2_normalize(val_features), labels_d, val_labels)
-        _, img_n, labels_d, _ = v["set"]
+        img_n, labels_d, _ = mon.val_set(who, val_features, val_labels, self.E, self.C, ops.l2_normalize)
         N, dev = img_n.shape[0], img_n.device
         if mon.n_val and N != mon.n_val and mon.seen:
             raise ValueError(f"{who}: the validation set has {N} rows, the history's earlier epochs {mon.n_val}")
@@ -305,29 +291,10 @@ class CoCoOpFitState:
         ops.val_score_finish(rows[:N], mon.bins, mon.records[epoch], mon.finish_ws)
         mon.select(epoch, self.block)
 
-    def monitor(self) -> dict:
-        """The history as numbers (``fitmonitor.monitor_dict``, the dict ``CoOpFitState.monitor`` returns).  It reads the history back:
-        one synchronisation."""
-        return fitmonitor.empty_monitor() if self._mon is None or not self._mon.seen else self._mon.summary()
-
-    def monitor_records(self) -> torch.Tensor:
-        """The device history, uint8 [slots, ops.val_record_bytes(val_bins)]; no read-back."""
-        if self._mon is None:
-            raise ValueError("CoCoOpFitState.monitor_records: nothing has been validated")
-        return self._mon.records
-
-    def val_row_results(self) -> torch.Tensor:
-        """The last validation's row results, uint8 [N_val, 16] on the device (``ops.decode_val_row_results``); no read-back."""
-        if self._mon is None or self._mon.rows is None:
-            raise ValueError("CoCoOpFitState.val_row_results: nothing has been validated")
-        return self._mon.row_results()
-
     def best_params(self) -> Dict[str, torch.Tensor]:
         """The best slot on the device as the five tensors (views of one block): the parameters of the best epoch so far, or those
         ``start_monitor`` saw while no epoch has been taken."""
-        if self._mon is None or self._mon.best is None:
-            raise ValueError("CoCoOpFitState.best_params: the monitor does not select (start_monitor(..., select=True))")
-        return collections.OrderedDict(ops.cocoop_block_views(self._mon.best, self.n_ctx, self.D, self.E, self.H))
+        return collections.OrderedDict(ops.cocoop_block_views(self._best_block("best_params"), self.n_ctx, self.D, self.E, self.H))
 
     def params(self) -> Dict[str, torch.Tensor]:
         """The five tensors as views of the master block (fp32, on the device), under the reference's ``state_dict`` names."""
@@ -469,10 +436,9 @@ def fit_prompt_learner(features: torch.Tensor, labels, clip_model, tokenized_pro
         _need_gpu(vf, "val_features")
         vl = vl.to(vf.device)
         state.val_stream_f16 = bool(val_stream_f16)
-        state.start_monitor(epochs, val_bins, final_model == "best_val", val_criterion)
+        state.start_monitor(epochs, val_bins, select=final_model == "best_val", val_criterion=val_criterion)
         end_epoch = lambda e: state.validate(vf, vl, e, batch_size if val_batch_size is None else val_batch_size)
     history = fitloop.run_cached(lambda f, y, r, want: state.step(f, y, r, want_loss=want), features, fitloop.labels_on(labels, lab, dev),
                                  fitloop.order_on(order, np.int64, dev), batch_size, per_epoch, epochs, lr_steps, return_history, end_epoch)
     out = state.best_params() if final_model == "best_val" else state.params()
-    return fitmonitor.pack(out, history, (state.monitor() if val is not None else fitmonitor.empty_monitor(val_bins)) if return_monitor else None,
-                           return_history, return_monitor)
+    return fitmonitor.pack(out, history, fitmonitor.returned_monitor(state, val is not None, val_bins, return_monitor), return_history, return_monitor)

@@ -445,9 +445,11 @@ def text_features(clip_model, tokenized_prompts, ctx: torch.Tensor, seq_rows: Op
     return tower.forward(fitloop.master(ctx, clip_model.device)).clone()
 
 
-class CoOpFitState:
+class CoOpFitState(fitmonitor.Monitored):
     """The training state of CoOp's context: the fp32 master ``ctx``, SGD's momentum buffer, the tower's stash and the number of steps
-    taken.  ``step`` enqueues one forward, backward and update and does not synchronise."""
+    taken.  ``step`` enqueues one forward, backward and update and does not synchronise.  ``validate`` scores cached validation features
+    on the device (``start_monitor``, ``monitor``, ``best_context``, ``val_logits``: ``fitmonitor.Monitored`` on a ``fitmonitor.Monitor``)."""
+    _who, _unseen_summary = "CoOpFitState", True
 
     def __init__(self, clip_model, tokenized_prompts, ctx: torch.Tensor, logit_scale: float = 4.6052, momentum: float = 0.9,
                  dampening: float = 0.0, nesterov: bool = False, weight_decay: float = 5e-4, grad_scale: float = DEFAULT_GRAD_SCALE,
@@ -475,7 +477,6 @@ class CoOpFitState:
         self.momentum, self.dampening, self.nesterov, self.weight_decay = momentum, dampening, nesterov, weight_decay
         self.steps = 0
         self._scaler = _BlockScaler(self.scaler, dev) if self.dynamic else None
-        self._mon = None    # the fit monitor's device history, made by start_monitor or the first validate
 
     def scaler_state(self) -> dict:
         """The dynamic scale's block as ``dict(scale, growth_tracker, skipped_steps, applied_steps, found_inf)`` (``found_inf``: of the
@@ -486,40 +487,8 @@ class CoOpFitState:
 
     # ---- per-epoch validation and best-epoch selection on the device (csrc/fit_monitor.hip, DESIGN.md "Fit monitor")
 
-    def start_monitor(self, slots: int, val_bins: int = 10, select: bool = False, val_criterion: str = "accuracy") -> None:
-        """The device history ``validate`` writes: ``slots`` epoch records of ``val_bins`` confidence bins and, with ``select``, the best
-        block and the best slot (a copy of the context as it is now, replaced whenever an epoch is strictly better under
-        ``val_criterion``).  Allocations and one small upload; nothing synchronises."""
-        who = "CoOpFitState.start_monitor"
-        if val_criterion not in ops.VAL_CRITERIA:
-            raise ValueError(f"{who}: val_criterion={val_criterion!r} must be one of {sorted(ops.VAL_CRITERIA)}")
-        dev = self.ctx.device
-        self._mon = {"bins": ops._val_bins(who, val_bins), "records": ops.new_val_records(max(int(slots), 1), val_bins, dev), "seen": 0,
-                     "criterion": val_criterion, "block": None, "best": None, "ws": None, "logits": None, "val": None}
-        if select:
-            self._mon["block"] = ops.new_best_block(dev)
-            self._mon["best"] = self.ctx.clone()
-            self._mon["select_ws"] = torch.empty(256, dtype=torch.uint8, device=dev)
-
-    def _val_operands(self, who: str, val_features: torch.Tensor, val_labels):
-        """The validation set as the kernels take it, made once per set: the features L2-normalised in fp32 (``ops.l2_normalize``, what the
-        inference path scores), the labels int64 on the device, the [N_val, C] fp32 logits and the scoring workspace."""
-        mon = self._mon
-        E = self.tower.E
-        if not isinstance(val_features, torch.Tensor) or val_features.dim() != 2 or val_features.shape[0] < 1 or val_features.shape[1] != E:
-            raise ValueError(f"{who}: val_features {tuple(getattr(val_features, 'shape', ()))} must be [N_val >= 1, E = {E}]")
-        _need_gpu(val_features, "val_features")
-        key = (val_features.data_ptr(), val_features._version, tuple(val_features.shape), tuple(val_features.stride()),
-               id(val_labels), getattr(val_labels, "_version", None))
-        if mon["val"] is None or mon["val"][0] != key:
-            N = val_features.shape[0]
-            labels_d = fitloop.step_labels(who, val_labels, N, self.C, val_features.device, "validation rows")
-            img_n = ops.l2_normalize(val_features)
-            need = lib.clipmi_val_score_workspace_bytes(N, mon["bins"])
-            mon["val"] = (key, img_n, labels_d, val_labels)
-            mon["logits"] = torch.empty(N, self.C, dtype=torch.float32, device=val_features.device)
-            mon["ws"] = torch.empty(max(need, 256), dtype=torch.uint8, device=val_features.device)
-        return mon["val"][1], mon["val"][2]
+    def _master(self) -> torch.Tensor:
+        return self.ctx
 
     def validate(self, val_features: torch.Tensor, val_labels, epoch: int) -> None:
         """Enqueue one validation of the current master context into slot ``epoch`` of the device history; no host read.
@@ -534,56 +503,18 @@ class CoOpFitState:
         Without ``start_monitor`` the history starts with ``epoch + 1`` slots of 10 bins and no selection; it grows when ``epoch``
         lies behind its end."""
         who = "CoOpFitState.validate"
-        if isinstance(epoch, bool) or int(epoch) != epoch or int(epoch) < 0:
-            raise ValueError(f"{who}: epoch={epoch} must be an integer >= 0")
-        epoch = int(epoch)
-        if self._mon is None:
-            self.start_monitor(epoch + 1)
-        mon = self._mon
-        img_n, labels_d = self._val_operands(who, val_features, val_labels)
-        if epoch >= mon["records"].shape[0]:
-            grown = ops.new_val_records(epoch + 1, mon["bins"], self.ctx.device)
-            grown[:mon["records"].shape[0]].copy_(mon["records"])
-            mon["records"] = grown
-        t = self.tower
+        mon, t = self._monitor_for(epoch), self.tower
+        epoch = mon.slot(who, epoch)
+        img_n, labels_d = mon.operands(who, val_features, val_labels, t.E, self.C, ops.l2_normalize)
         txt_n = ops.l2_normalize(t.forward(self.ctx))
-        N = img_n.shape[0]
-        check(lib.clipmi_logits(img_n.data_ptr(), txt_n.data_ptr(), self.scale, None, mon["logits"].data_ptr(), None, None, N, t.C, t.E, ops._stream()),
-              "clipmi_logits")
-        record = mon["records"][epoch]
-        ops.val_score(mon["logits"], labels_d, mon["bins"], record, mon["ws"])
-        if mon["block"] is not None:
-            ops.best_select(record, mon["block"], mon["criterion"], epoch, self.ctx, mon["best"], mon["select_ws"])
-        mon["seen"] = max(mon["seen"], epoch + 1)
-
-    def val_logits(self) -> torch.Tensor:
-        """The fp32 [N_val, C] logits of the last ``validate``, where the state keeps them (the next ``validate`` overwrites them)."""
-        if self._mon is None or self._mon["logits"] is None:
-            raise ValueError("CoOpFitState.val_logits: nothing has been validated")
-        return self._mon["logits"]
+        check(lib.clipmi_logits(img_n.data_ptr(), txt_n.data_ptr(), self.scale, None, mon.logits.data_ptr(), None, None, img_n.shape[0], t.C, t.E,
+                                ops._stream()), "clipmi_logits")
+        mon.score(epoch, labels_d, self.ctx)
 
     def best_context(self) -> torch.Tensor:
         """The best slot on the device: the context of the best epoch so far, or the context ``start_monitor`` saw while no epoch has
         been taken.  No read-back."""
-        if self._mon is None or self._mon["best"] is None:
-            raise ValueError("CoOpFitState.best_context: the monitor does not select (start_monitor(..., select=True))")
-        return self._mon["best"]
-
-    def monitor_records(self) -> torch.Tensor:
-        """The device history, uint8 [slots, ops.val_record_bytes(val_bins)]; no read-back."""
-        if self._mon is None:
-            raise ValueError("CoOpFitState.monitor_records: nothing has been validated")
-        return self._mon["records"]
-
-    def monitor(self) -> dict:
-        """The history as numbers: per validated epoch ``accuracy``, ``nll`` (the mean over the rows) and ``ece``
-        (``metrics.ece_from_bins`` of the record's bins), the raw ``bins`` (float64 [epochs, 3, val_bins + 1]: count, sum of confidences,
-        correct), the decoded ``records`` and ``best_epoch`` (None without selection, -1 when no epoch was taken).  It reads the history
-        back: one synchronisation."""
-        mon = self._mon
-        if mon is None:
-            return empty_monitor()
-        return fitmonitor.monitor_dict(mon["records"][:mon["seen"]], mon["bins"], mon["block"])
+        return self._best_block("best_context")
 
     def _one_call(self, features, labels_d, lr_d, losses, first: bool) -> None:
         """``step`` through the library's one-call step: one of four symbols (static or scaled, the class token at the end or placed) on
@@ -696,16 +627,7 @@ def fit_context(features: torch.Tensor, labels, clip_model, tokenized_prompts, c
     behind everything else, read once after the run's one wait: per-epoch ``accuracy``, ``nll`` and ``ece``, the raw ``bins``,
     ``records`` and ``best_epoch`` (``CoOpFitState.monitor``); empty without ``val`` or without steps."""
     who = "fit_context"
-    if final_model not in FINAL_MODELS:
-        raise ValueError(f"{who}: final_model={final_model!r} must be one of {FINAL_MODELS}")
-    if val_criterion not in ops.VAL_CRITERIA:
-        raise ValueError(f"{who}: val_criterion={val_criterion!r} must be one of {sorted(ops.VAL_CRITERIA)}")
-    if final_model == "best_val" and val is None:
-        raise ValueError(f"{who}: final_model='best_val' needs val=(val_features, val_labels)")
-    if val is not None:
-        if not isinstance(val, (tuple, list)) or len(val) != 2:
-            raise ValueError(f"{who}: val must be (val_features, val_labels)")
-        ops._val_bins(who, val_bins)
+    fitmonitor.check_args(who, val, val_bins, final_model, val_criterion)
     ids = _host_int_array(who, tokenized_prompts, "tokenized_prompts")
     if ctx is None:
         ctx = init_context(clip_model, n_ctx, ids.shape[0] if csc else None)
@@ -726,20 +648,11 @@ def fit_context(features: torch.Tensor, labels, clip_model, tokenized_prompts, c
     dev = features.device
     _, lr_steps = fitloop.schedule(who, lr, epochs, lr_per_epoch, per_epoch, dev)
     if val is not None:
-        vf, vl = val
-        if not isinstance(vf, torch.Tensor) or vf.dim() != 2 or vf.shape[0] < 1 or vf.shape[1] != E:
-            raise ValueError(f"{who}: val_features must be a [N_val >= 1, E = {E}] tensor")
-        if not fitloop._on_gpu_as_is(vl):
-            vl = torch.from_numpy(fitloop._labels(who, vl, vf.shape[0], Cn, "validation rows").astype(np.int64))
-
-    def pack(out, history, monitor):
-        res = (out,) + ((history,) if return_history else ()) + ((monitor,) if return_monitor else ())
-        return res if len(res) > 1 else out
-
+        vf, vl = fitmonitor.check_val(who, val, E, Cn)
     if epochs * per_epoch == 0:
         out = ctx.detach().to(torch.float32).clone()
         out = out.to(dev) if features.is_cuda else out
-        return pack(out, np.zeros(0, np.float32), empty_monitor(val_bins))
+        return fitmonitor.pack(out, np.zeros(0, np.float32), empty_monitor(val_bins), return_history, return_monitor)
     _need_gpu(features, "features")
     state = CoOpFitState(clip_model, tokenized_prompts, ctx, logit_scale, momentum, dampening, nesterov, weight_decay, grad_scale, seq_rows,
                          method, teacher, w, T, lam, scaler, class_token_position, name_lens)
@@ -747,9 +660,9 @@ def fit_context(features: torch.Tensor, labels, clip_model, tokenized_prompts, c
     if val is not None:
         _need_gpu(vf, "val_features")
         vl = vl.to(dev)
-        state.start_monitor(epochs, val_bins, final_model == "best_val", val_criterion)
+        state.start_monitor(epochs, val_bins, select=final_model == "best_val", val_criterion=val_criterion)
         end_epoch = lambda e: state.validate(vf, vl, e)
     history = fitloop.run_cached(lambda f, y, r, want: state.step(f, y, r, want_loss=want), features, fitloop.labels_on(labels, lab, dev),
                                  fitloop.order_on(order, np.int64, dev), batch_size, per_epoch, epochs, lr_steps, return_history, end_epoch)
     out = state.best_context() if final_model == "best_val" else state.ctx
-    return pack(out, history, state.monitor() if return_monitor else None)
+    return fitmonitor.pack(out, history, state.monitor() if return_monitor else None, return_history, return_monitor)

@@ -1,13 +1,18 @@
 """What the fits with per-epoch validation share (DESIGN.md "Fit monitor"; reference base_learner.py:41-47, Dassl's ``after_epoch``): the
-argument checks of ``val`` / ``val_bins`` / ``final_model`` / ``val_criterion``, the device history -- epoch records, the best block and the
-best slot -- and the dict ``monitor()`` returns.  ``coopfit`` reads the dict's code from here; ``adapterfit`` and ``taskresfit`` use all of
-it, both for their one-call monitored runs (``ops.adapter_fit`` / ``ops.taskres_fit`` with ``monitor=``) and for ``*FitState.validate``.
-``vptfit``, ``maplefit`` and ``promptsrcfit``, whose validation set is images, use ``ImageMonitor`` -- the same history fed by a
-row-chunked score -- through the ``ImageMonitored`` mix-in of their states.  ``cocoopfit`` and ``prodafit`` validate cached features through
-their inference forwards: CoCoOp, whose classifier differs per image, feeds an ``ImageMonitor``'s row results from a fused per-image kernel;
-ProDA writes its [N_val, C] logits into a workspace of its own and scores them inside one library call, on a plain ``History``.  TempScaling
-has no monitor: it trains on the validation loader itself, so a per-epoch validation would be its own training loss.  Nothing here knows the
-byte layout of a record: that stays with ``ops``' helpers."""
+monitor's whole host state.  This module is the only place that knows it.
+
+* The argument checks of ``val`` / ``val_bins`` / ``final_model`` / ``val_criterion`` with their messages (``check_args``,
+  ``check_image_args``, ``check_val``) and the shape of a fit function's result (``pack``, ``returned_monitor``, ``empty_monitor``).
+* Three history classes.  ``History``: the epoch records, the best block and the best slot on the device, the growth of the records
+  (``slot``), the selection (``select``) and the one cache of a cached-feature validation set (``val_set``: shape and device checks, the
+  key, the labels; the caller says how the features are prepared).  ``Monitor`` adds the [N_val, C] logits and ``clipmi_val_score``'s
+  workspace; ``ImageMonitor`` the 16 N_val bytes of row results of a row-chunked score, and the chunks of a validation set of images.
+* One mix-in, ``Monitored``, that every ``*FitState`` inherits: ``start_monitor``, the auto-start, ``monitor``, ``monitor_records``,
+  ``val_logits`` / ``val_row_results`` and the best slot.  ``ImageMonitored`` is the same with the image states' argument order.
+
+A state names its history class and its master block and writes its own ``validate`` (DESIGN.md "Fit monitor" has the table of the nine).
+TempScaling has no monitor: it trains on the validation loader itself, so a per-epoch validation would be its own training loss.  Nothing
+here knows the byte layout of a record: that stays with ``ops``' helpers."""
 from __future__ import annotations
 
 from typing import Optional
@@ -42,7 +47,7 @@ def monitor_dict(records: torch.Tensor, n_bins: int, block: Optional[torch.Tenso
 
 
 def check_args(who: str, val, val_bins, final_model, val_criterion, first: str = "val_features") -> None:
-    """``coopfit.fit_context``'s checks of the validation arguments, with its messages.  ``first`` names the pair's first element: the
+    """The checks of the validation arguments that every fit function makes first, with one set of messages.  ``first`` names the pair's first element: the
     image-tower fits take ``val_images_or_loader`` there (a tensor of images or a loader of batches; ``ImageMonitor`` checks which)."""
     if final_model not in FINAL_MODELS:
         raise ValueError(f"{who}: final_model={final_model!r} must be one of {FINAL_MODELS}")
@@ -80,6 +85,20 @@ def pack(fitted, history, monitor, return_history: bool, return_monitor: bool):
     return res if len(res) > 1 else res[0]
 
 
+def returned_monitor(source, monitored: bool, val_bins: int, return_monitor: bool) -> Optional[dict]:
+    """The monitor's dict as a fit function returns it: None when it was not asked for, ``empty_monitor(val_bins)`` when the run was not
+    monitored (no ``val``, or no step), else what ``source`` -- a ``History``, or a state with ``monitor()`` -- has recorded."""
+    if not return_monitor:
+        return None
+    if not monitored:
+        return empty_monitor(val_bins)
+    return source.summary() if isinstance(source, History) else source.monitor()
+
+
+def _fp32(features: torch.Tensor) -> torch.Tensor:
+    return features if features.dtype == torch.float32 else features.float()
+
+
 class History:
     """The device history of one fit: ``slots`` epoch records of ``val_bins`` confidence bins and, when ``params`` is given, the best block
     and the best slot -- a copy of ``params`` (one contiguous fp32 block on the GPU: what ``clipmi_best_select`` copies) as it is now,
@@ -96,6 +115,23 @@ class History:
         if params is not None:
             self.block, self.best = ops.new_best_block(dev), params.clone()
         self.select_ws = torch.empty(256, dtype=torch.uint8, device=dev)
+        self.val = None     # val_set's cache: (key, prepared features, labels on the device, the labels as given)
+
+    def val_set(self, who: str, val_features: torch.Tensor, val_labels, E: int, C: int, prepare):
+        """A cached-feature validation set as the kernels take it, made once per set: ``(prepare(val_features), labels int64 on the
+        device, made now)``.  An int64 label tensor on the GPU is taken as it is; anything else is range-checked on the host.  "Once per
+        set" goes by the tensors' addresses, versions, shapes, strides and types: labels given as a list or an array and changed in place
+        between two validations keep their first upload -- pass a new object, or a tensor."""
+        if not isinstance(val_features, torch.Tensor) or val_features.dim() != 2 or val_features.shape[0] < 1 or val_features.shape[1] != E:
+            raise ValueError(f"{who}: val_features {tuple(getattr(val_features, 'shape', ()))} must be [N_val >= 1, E = {E}]")
+        fitloop._need_gpu(val_features, "val_features")
+        key = (val_features.data_ptr(), val_features._version, tuple(val_features.shape), tuple(val_features.stride()), val_features.dtype,
+               id(val_labels), getattr(val_labels, "_version", None))
+        made = self.val is None or self.val[0] != key
+        if made:
+            labels_d = fitloop.step_labels(who, val_labels, val_features.shape[0], C, val_features.device, "validation rows")
+            self.val = (key, prepare(val_features), labels_d, val_labels)
+        return self.val[1], self.val[2], made
 
     def slot(self, who: str, epoch) -> int:
         """``epoch`` as a checked index into the history, which grows when the index lies behind its end."""
@@ -119,31 +155,22 @@ class History:
 
 
 class Monitor(History):
-    """``History`` for the fits on cached features (``adapterfit``, ``taskresfit``): the validation features, their labels, the
-    [N_val, C] logits and ``clipmi_val_score``'s workspace."""
+    """``History`` for the fits that score an [N_val, C] logits matrix (``coopfit``, ``adapterfit``, ``taskresfit``): the validation
+    features, their labels, the logits and ``clipmi_val_score``'s workspace."""
 
     def __init__(self, who: str, slots: int, val_bins: int, val_criterion: str, params: Optional[torch.Tensor], dev):
         super().__init__(who, slots, val_bins, val_criterion, params, dev)
-        self.val = self.logits = self.score_ws = self.run_ws = None
+        self.logits = self.score_ws = None
 
-    def operands(self, who: str, val_features: torch.Tensor, val_labels, E: int, C: int):
-        """The validation set as the kernels take it, made once per set: fp32 features whose rows are read with their stride, the labels
-        int64 on the device (an int64 tensor on the GPU is taken as it is; anything else is range-checked on the host), the [N_val, C] fp32
-        logits and the scoring workspace.  "Once per set" goes by the tensors' versions: labels given as a list or an array and changed in
-        place between two validations keep their first upload -- pass a new object, or a tensor."""
-        if not isinstance(val_features, torch.Tensor) or val_features.dim() != 2 or val_features.shape[0] < 1 or val_features.shape[1] != E:
-            raise ValueError(f"{who}: val_features {tuple(getattr(val_features, 'shape', ()))} must be [N_val >= 1, E = {E}]")
-        fitloop._need_gpu(val_features, "val_features")
-        key = (val_features.data_ptr(), val_features._version, tuple(val_features.shape), tuple(val_features.stride()), val_features.dtype,
-               id(val_labels), getattr(val_labels, "_version", None))
-        if self.val is None or self.val[0] != key:
-            N = val_features.shape[0]
-            labels_d = fitloop.step_labels(who, val_labels, N, C, val_features.device, "validation rows")
-            feats = val_features if val_features.dtype == torch.float32 else val_features.float()
-            self.val = (key, feats, labels_d, val_labels)
-            self.logits = torch.empty(N, C, dtype=torch.float32, device=val_features.device)
-            self.score_ws = torch.empty(max(lib.clipmi_val_score_workspace_bytes(N, self.bins), 256), dtype=torch.uint8, device=val_features.device)
-        return self.val[1], self.val[2]
+    def operands(self, who: str, val_features: torch.Tensor, val_labels, E: int, C: int, prepare=_fp32):
+        """``val_set``'s features and labels -- by default fp32 features whose rows are read with their stride -- and, made with them,
+        the [N_val, C] fp32 logits and the scoring workspace."""
+        feats, labels_d, made = self.val_set(who, val_features, val_labels, E, C, prepare)
+        if made:
+            N, dev = val_features.shape[0], val_features.device
+            self.logits = torch.empty(N, C, dtype=torch.float32, device=dev)
+            self.score_ws = torch.empty(max(lib.clipmi_val_score_workspace_bytes(N, self.bins), 256), dtype=torch.uint8, device=dev)
+        return feats, labels_d
 
     def score(self, epoch: int, labels_d: torch.Tensor, params: Optional[torch.Tensor]) -> None:
         """``self.logits`` into record ``epoch`` and, when the monitor selects, ``params`` into the best slot under the decision; enqueued."""
@@ -163,7 +190,8 @@ class ImageMonitor(History):
     tensor [N_val, 3, R, R] on the GPU cut into chunks of ``val_batch_size``, or a sized iterable of (images, labels) batches on the GPU
     iterated once per validation --, the labels, the 16 N_val-byte row results (``ops.val_score_rows``) and, for the separate calls, the
     [B, C] logits of one chunk.  Its footprint does not depend on N_val x C: no [N_val, C] logits matrix exists at any time.
-    ``ops.val_score_finish`` folds the row results into the record, byte for byte ``ops.val_score``'s on the whole matrix."""
+    ``ops.val_score_finish`` folds the row results into the record, byte for byte ``ops.val_score``'s on the whole matrix.
+    ``cocoopfit``, whose classifier differs per image, keeps its row results here too and fills them from its own fused kernel."""
 
     def __init__(self, who: str, slots: int, val_bins: int, val_criterion: str, params: Optional[torch.Tensor], dev):
         super().__init__(who, slots, val_bins, val_criterion, params, dev)
@@ -241,27 +269,38 @@ class ImageMonitor(History):
         return self.rows[:self.n_val]
 
 
-class ImageMonitored:
-    """What the three image-tower fit states share: ``start_monitor``, ``monitor``, ``val_row_results`` and the best slot.  The state
-    gives ``_who`` (its class name), ``_master()`` (its one fp32 master block) and its own ``validate``."""
+class Monitored:
+    """The monitor surface of a ``*FitState``.  The state gives ``_who`` (its class name), ``_master()`` (its one contiguous fp32 master
+    block on the GPU: what ``clipmi_best_select`` copies), ``_history`` (the history class ``start_monitor`` makes), its own ``validate``,
+    which starts with ``self._monitor_for(epoch)``, and a named view of ``_best_block``.
 
-    _mon: Optional[ImageMonitor] = None
+    ``_unseen_summary``: what ``monitor()`` returns between ``start_monitor`` and the first ``validate``.  True (CoOp, CLIP-Adapter,
+    TaskRes): the history's own summary -- no epochs, ``bins`` of the monitor's width, ``best_epoch`` -1 when it selects.  False (the
+    other six): ``empty_monitor()`` -- 10 bins, ``best_epoch`` None."""
 
-    def start_monitor(self, slots: int, val_bins: int = 10, val_criterion: str = "accuracy", select: bool = False) -> None:
+    _mon: Optional[History] = None
+    _history = Monitor
+    _unseen_summary = False
+
+    def start_monitor(self, slots: int, val_bins: int = 10, select: bool = False, val_criterion: str = "accuracy") -> None:
         """The device history ``validate`` writes: ``slots`` epoch records of ``val_bins`` confidence bins and, with ``select``, the best
         block and the best slot -- a copy of the master block as it is now, replaced whenever a validated epoch is strictly better under
-        ``val_criterion``.  The optimiser state, the scaler block and a GPA sum are not selected.  Allocations and one small upload."""
+        ``val_criterion``.  The optimiser state, the scaler block and a GPA sum are not selected.  Allocations and one small upload;
+        nothing synchronises."""
         master = self._master()
-        self._mon = ImageMonitor(f"{self._who}.start_monitor", slots, val_bins, val_criterion, master if select else None, master.device)
+        self._mon = self._history(f"{self._who}.start_monitor", slots, val_bins, val_criterion, master if select else None, master.device)
 
-    def _monitor_for(self, epoch) -> ImageMonitor:
+    def _monitor_for(self, epoch) -> History:
+        """The history, started with ``epoch + 1`` slots of 10 bins and no selection when ``start_monitor`` was not called."""
         if self._mon is None:
             self.start_monitor(int(epoch) + 1 if isinstance(epoch, int) and epoch >= 0 else 1)
         return self._mon
 
     def monitor(self) -> dict:
-        """The history as numbers (``fitmonitor.monitor_dict``); it reads the history back: one synchronisation."""
-        return empty_monitor() if self._mon is None or not self._mon.seen else self._mon.summary()
+        """The history as numbers (``monitor_dict``); it reads the history back: one synchronisation."""
+        if self._mon is None or not (self._mon.seen or self._unseen_summary):
+            return empty_monitor()
+        return self._mon.summary()
 
     def monitor_records(self) -> torch.Tensor:
         """The device history, uint8 [slots, ops.val_record_bytes(val_bins)]; no read-back."""
@@ -269,13 +308,32 @@ class ImageMonitored:
             raise ValueError(f"{self._who}.monitor_records: nothing has been validated")
         return self._mon.records
 
+    def val_logits(self) -> torch.Tensor:
+        """The fp32 [N_val, C] logits of the last ``validate``, where a ``Monitor`` keeps them (the next ``validate`` overwrites them)."""
+        if getattr(self._mon, "logits", None) is None:
+            raise ValueError(f"{self._who}.val_logits: nothing has been validated")
+        return self._mon.logits
+
     def val_row_results(self) -> torch.Tensor:
-        """The last validation's row results, uint8 [N_val, 16] on the device (``ops.decode_val_row_results``); no read-back."""
-        if self._mon is None or self._mon.rows is None:
+        """The last validation's row results where an ``ImageMonitor`` keeps them, uint8 [N_val, 16] on the device
+        (``ops.decode_val_row_results``); no read-back."""
+        if getattr(self._mon, "rows", None) is None:
             raise ValueError(f"{self._who}.val_row_results: nothing has been validated")
         return self._mon.row_results()
 
     def _best_block(self, what: str) -> torch.Tensor:
+        """The best slot on the device: the master block of the best epoch so far, or the one ``start_monitor`` saw while no epoch has
+        been taken.  No read-back."""
         if self._mon is None or self._mon.best is None:
             raise ValueError(f"{self._who}.{what}: the monitor does not select (start_monitor(..., select=True))")
         return self._mon.best
+
+
+class ImageMonitored(Monitored):
+    """``Monitored`` for the three image-tower fit states, whose public ``start_monitor`` takes the criterion in front of ``select``."""
+
+    _history = ImageMonitor
+
+    def start_monitor(self, slots: int, val_bins: int = 10, val_criterion: str = "accuracy", select: bool = False) -> None:
+        """``Monitored.start_monitor`` in the image states' argument order."""
+        Monitored.start_monitor(self, slots, val_bins, select=select, val_criterion=val_criterion)

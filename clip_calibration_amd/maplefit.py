@@ -419,9 +419,9 @@ def fit_prompt_learner(images_or_loader, labels, model, tokenized_prompts, learn
     _, lr_steps = fitloop.schedule(who, lr, epochs, lr_per_epoch, len(batches), model.device)
     end_epoch = None
     if val is not None and epochs * len(batches) > 0:
-        state.start_monitor(epochs, val_bins, val_criterion, final_model == "best_val")
+        state.start_monitor(epochs, val_bins, val_criterion=val_criterion, select=final_model == "best_val")
         end_epoch = lambda e: state.validate(val[0], val[1], e, val_batch_size)
     history = fitloop.run_batches(lambda e, k, b, r, want: state.step(b[0], b[1], r, want_loss=want), batches, epochs, lr_steps, return_history, end_epoch)
     out = state.best_params() if final_model == "best_val" and end_epoch is not None else state.params()
-    return fitmonitor.pack(out, history, (state.monitor() if end_epoch is not None else fitmonitor.empty_monitor(val_bins)) if return_monitor else None,
+    return fitmonitor.pack(out, history, fitmonitor.returned_monitor(state, end_epoch is not None, val_bins, return_monitor),
                            return_history, return_monitor)

@@ -235,10 +235,19 @@ def context_gradient(clip_model, tokenized_prompts, ctx: torch.Tensor, features:
     return losses[0:1], grad, {"upper": losses[1:2], "m": losses[2:3], "text": text.clone(), "sel": sel_d}
 
 
-class ProDAFitState:
+def _aligned_fp32(features: torch.Tensor) -> torch.Tensor:
+    """What clipmi_proda_val_logits reads: fp32, contiguous, on a 16-byte boundary."""
+    feats = features.detach().to(torch.float32).contiguous()
+    return feats.clone() if feats.data_ptr() % 16 else feats
+
+
+class ProDAFitState(fitmonitor.Monitored):
     """The training state of ProDA's contexts: the fp32 master ``ctx`` [P, n_ctx, D], SGD's momentum buffer, the tower's stash, the
     selection schedule's generator and the number of steps taken.  ``step`` enqueues one forward, backward and update and does not
-    synchronise."""
+    synchronise.  ``validate`` scores cached validation features through the inference mirror (``start_monitor``, ``monitor``,
+    ``best_params``, ``val_logits``: ``fitmonitor.Monitored`` on a plain ``fitmonitor.History``; the logits live in a workspace of the
+    state's own, scored inside the one library call)."""
+    _who, _history = "ProDAFitState", fitmonitor.History
 
     def __init__(self, clip_model, tokenized_prompts, ctx: torch.Tensor, prompt_bs: int = 4, alpha: float = 0.1, logit_scale: float = 4.6052,
                  momentum: float = 0.9, dampening: float = 0.0, nesterov: bool = False, weight_decay: float = 5e-4,
@@ -265,8 +274,7 @@ class ProDAFitState:
         self.steps = 0
         self._scaler = _BlockScaler(self.scaler, dev) if self.dynamic else None
         self._ids = ids_all[:self.C]
-        self._mon = None            # the fit monitor's device history, made by start_monitor or the first validate
-        self._val = None            # what a validation keeps between epochs: the inference operands, the set and the two workspaces
+        self._val = None            # what a validation keeps between epochs: the inference operands and the two workspaces
         self.val_class_chunk = None # validate's classes per tower call when its argument is None (None: 4096 // n_prompt, at least 1)
 
     def scaler_state(self) -> dict:
@@ -278,13 +286,8 @@ class ProDAFitState:
 
     # ---- per-epoch validation and best-epoch selection on the device (DESIGN.md "Fit monitor", "CoCoOp and ProDA")
 
-    def start_monitor(self, slots: int, val_bins: int = 10, select: bool = False, val_criterion: str = "accuracy") -> None:
-        """The device history ``validate`` writes: ``slots`` epoch records of ``val_bins`` confidence bins and, with ``select``, the best
-        block and the best slot -- a copy of the master ``ctx`` [P, n_ctx, D] as it is now, replaced whenever a validated epoch is strictly
-        better under ``val_criterion``.  The momentum buffer and the scaler block are not selected.  Allocations and one small upload;
-        nothing synchronises."""
-        self._mon = fitmonitor.History("ProDAFitState.start_monitor", slots, val_bins, val_criterion, self.ctx.reshape(-1) if select else None,
-                                       self.ctx.device)
+    def _master(self) -> torch.Tensor:
+        return self.ctx.reshape(-1)
 
     def _val_operands(self):
         """What the inference mirror (``trainers.proda.CustomCLIP.set_classifier``) works on, made once: the classes' embeddings
@@ -297,7 +300,7 @@ class ProDAFitState:
             with torch.no_grad():
                 base = m.token_embedding(ids_h.to(m.device)).type(m.dtype).contiguous()
             order = torch.from_numpy(reference_order(np.arange(self.P), self.pos_host)).to(m.device)
-            self._val = {"base": base, "order": order, "rows": m.live_rows(ids_h), "set": None, "ws": None, "mon_ws": None}
+            self._val = {"base": base, "order": order, "rows": m.live_rows(ids_h), "ws": None, "mon_ws": None}
         return self._val
 
     def validate(self, val_features: torch.Tensor, val_labels, epoch: int, val_class_chunk: Optional[int] = None) -> None:
@@ -315,9 +318,7 @@ class ProDAFitState:
         classes' name lengths are the state's (``name_lens``); the inference mirror derives its own from the EOT rows, which is the
         state's default.  Without ``start_monitor`` the history starts with ``epoch + 1`` slots of 10 bins and no selection."""
         who = "ProDAFitState.validate"
-        if self._mon is None:
-            self.start_monitor(int(epoch) + 1 if isinstance(epoch, int) and epoch >= 0 else 1)
-        mon, t, m = self._mon, self.tower, self.tower.model
+        mon, t, m = self._monitor_for(epoch), self.tower, self.tower.model
         epoch = mon.slot(who, epoch)
         if val_class_chunk is None:
             val_class_chunk = self.val_class_chunk
@@ -325,19 +326,8 @@ class ProDAFitState:
         if isinstance(cc, bool) or int(cc) != cc or int(cc) < 1:
             raise ValueError(f"{who}: val_class_chunk={val_class_chunk} must be an integer >= 1")
         cc = min(int(cc), self.C)
-        if not isinstance(val_features, torch.Tensor) or val_features.dim() != 2 or val_features.shape[0] < 1 or val_features.shape[1] != t.E:
-            raise ValueError(f"{who}: val_features {tuple(getattr(val_features, 'shape', ()))} must be [N_val >= 1, E = {t.E}]")
-        _need_gpu(val_features, "val_features")
         v = self._val_operands()
-        key = (val_features.data_ptr(), val_features._version, tuple(val_features.shape), tuple(val_features.stride()), val_features.dtype,
-               id(val_labels), getattr(val_labels, "_version", None))
-        if v["set"] is None or v["set"][0] != key:
-            labels_d = fitloop.step_labels(who, val_labels, val_features.shape[0], self.C, val_features.device, "validation rows")
-            feats = val_features.detach().to(torch.float32).contiguous()
-            if feats.data_ptr() % 16:
-                feats = feats.clone()
-            v["set"] = (key, feats, labels_d, val_labels)
-        _, feats, labels_d, _ = v["set"]
+        feats, labels_d, _ = mon.val_set(who, val_features, val_labels, t.E, self.C, _aligned_fp32)
         N, dev = feats.shape[0], feats.device
         need = lib.clipmi_proda_val_logits_bytes(m._handle, self.C, self.P, v["rows"], cc, N)
         mon_need = lib.clipmi_proda_val_monitor_bytes(N, self.C, mon.bins)
@@ -365,23 +355,10 @@ class ProDAFitState:
         N = self._val["n_val"]
         return self._val["mon_ws"][:4 * N * self.C].view(torch.float32).view(N, self.C)
 
-    def monitor(self) -> dict:
-        """The history as numbers (``fitmonitor.monitor_dict``, the dict ``CoOpFitState.monitor`` returns).  It reads the history back:
-        one synchronisation."""
-        return fitmonitor.empty_monitor() if self._mon is None or not self._mon.seen else self._mon.summary()
-
-    def monitor_records(self) -> torch.Tensor:
-        """The device history, uint8 [slots, ops.val_record_bytes(val_bins)]; no read-back."""
-        if self._mon is None:
-            raise ValueError("ProDAFitState.monitor_records: nothing has been validated")
-        return self._mon.records
-
     def best_params(self) -> torch.Tensor:
         """The best slot on the device, fp32 [P, n_ctx, D]: the contexts of the best epoch so far, or the contexts ``start_monitor`` saw
         while no epoch has been taken."""
-        if self._mon is None or self._mon.best is None:
-            raise ValueError("ProDAFitState.best_params: the monitor does not select (start_monitor(..., select=True))")
-        return self._mon.best.view_as(self.ctx)
+        return self._best_block("best_params").view_as(self.ctx)
 
     def next_selection(self) -> np.ndarray:
         """The schedule's next slice (``draw_selections``, one step at a time)."""
@@ -548,7 +525,7 @@ def fit_context(features: torch.Tensor, labels, clip_model, tokenized_prompts, c
     if val is not None:
         _need_gpu(vf, "val_features")
         vl = vl.to(vf.device)
-        state.start_monitor(epochs, val_bins, final_model == "best_val", val_criterion)
+        state.start_monitor(epochs, val_bins, select=final_model == "best_val", val_criterion=val_criterion)
         end_epoch = lambda e: state.validate(vf, vl, e, val_class_chunk)
     history = fitloop.run_cached(lambda f, y, r, want: state.step(f, y, r, sel=sels_d[state.steps], want_loss=want), features,
                                  fitloop.labels_on(labels, lab, dev), fitloop.order_on(order, np.int64, dev), batch_size, per_epoch, epochs, lr_steps,
@@ -558,5 +535,5 @@ def fit_context(features: torch.Tensor, labels, clip_model, tokenized_prompts, c
     if return_scaler_state:
         out = out + (state.scaler_state(),)
     if return_monitor:
-        out = out + (state.monitor() if val is not None else fitmonitor.empty_monitor(val_bins),)
+        out = out + (fitmonitor.returned_monitor(state, val is not None, val_bins, True),)
     return out if len(out) > 1 else out[0]

@@ -555,10 +555,10 @@ def fit_prompts(images_or_loader, labels, model, tokenized_prompts, teacher: tor
             state.validate(val[0], val[1], e, val_batch_size)
 
     if monitored:
-        state.start_monitor(epochs, val_bins, val_criterion, final_model == "best_val")
+        state.start_monitor(epochs, val_bins, val_criterion=val_criterion, select=final_model == "best_val")
     _, lr_steps = fitloop.schedule(who, lr, epochs, lr_per_epoch, len(batches), model.device)
     history = fitloop.run_batches(lambda e, k, b, r, want: state.step(b[0], b[1], r, want_loss=want, one_call=one_call), batches, epochs, lr_steps, return_history,
                                   None if weights is None and not monitored else end_epoch)
     out = state.best_params() if final_model == "best_val" and monitored else state.params()
-    return fitmonitor.pack(out, history, (state.monitor() if monitored else fitmonitor.empty_monitor(val_bins)) if return_monitor else None,
+    return fitmonitor.pack(out, history, fitmonitor.returned_monitor(state, monitored, val_bins, return_monitor),
                            return_history, return_monitor)

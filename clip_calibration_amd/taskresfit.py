@@ -126,7 +126,7 @@ def fit_residuals(features: torch.Tensor, labels, base_text_features: torch.Tens
         _need_gpu(vf, "val_features")
         mon = fitmonitor.Monitor(who, epochs, val_bins, val_criterion, r if final_model == "best_val" else None, dev)
         mon.seen = epochs
-        monitor = ops.fit_monitor(vf if vf.dtype == torch.float32 else vf.float(), vl.to(dev), mon.bins, mon.records, val_criterion, mon.block,
+        monitor = ops.fit_monitor(fitmonitor._fp32(vf), vl.to(dev), mon.bins, mon.records, val_criterion, mon.block,
                                   mon.best)
     losses = ops.taskres_fit(features, fitloop.labels_on(labels, lab, dev), base_text_features, r, s1, s2, lr_steps, alpha,
                              float(np.float32(math.exp(logit_scale))), batch_size, epochs, optimizer, weight_decay, momentum, dampening, nesterov,
@@ -134,15 +134,18 @@ def fit_residuals(features: torch.Tensor, labels, base_text_features: torch.Tens
                              monitor=monitor)
     torch.cuda.current_stream().synchronize()   # the run's one synchronisation
     return fitmonitor.pack(mon.best if final_model == "best_val" else r, losses.cpu().numpy() if return_history else None,
-                           (mon.summary() if mon is not None else fitmonitor.empty_monitor(val_bins)) if return_monitor else None,
+                           fitmonitor.returned_monitor(mon, mon is not None, val_bins, return_monitor),
                            return_history, return_monitor)
 
 
-class TaskResFitState:
+class TaskResFitState(fitmonitor.Monitored):
     """The training state of TaskRes' residuals for callers that produce the image features step by step (a random train transform: the
     image tower runs on every batch): the fp32 master ``residuals`` [C, E], the optimiser's state (``state1``: Adam's first moment or
     SGD's momentum buffer, ``state2``: Adam's second moment) and the number of steps taken.  ``step`` enqueues one forward, backward and
-    optimiser update and does not synchronise."""
+    optimiser update and does not synchronise.  ``validate`` scores cached validation features on the device (``start_monitor``,
+    ``monitor``, ``best_residuals``, ``val_logits``: ``fitmonitor.Monitored`` on a ``fitmonitor.Monitor``; the optimiser's state is not
+    selected)."""
+    _who, _unseen_summary = "TaskResFitState", True
 
     def __init__(self, base_text_features: torch.Tensor, residuals: Optional[torch.Tensor] = None, alpha: float = 0.5,
                  logit_scale: float = 4.6052, optimizer: str = "adam", betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
@@ -161,16 +164,11 @@ class TaskResFitState:
         self.optimizer, self.betas, self.eps, self.weight_decay = optimizer, (float(betas[0]), float(betas[1])), eps, weight_decay
         self.momentum, self.dampening, self.nesterov = momentum, dampening, nesterov
         self.steps = 0
-        self._mon = None    # the fit monitor's device history, made by start_monitor or the first validate
 
-    # ---- per-epoch validation and best-epoch selection on the device (DESIGN.md "Fit monitor"), as CoOpFitState has them
+    # ---- per-epoch validation and best-epoch selection on the device (DESIGN.md "Fit monitor")
 
-    def start_monitor(self, slots: int, val_bins: int = 10, select: bool = False, val_criterion: str = "accuracy") -> None:
-        """The device history ``validate`` writes: ``slots`` epoch records of ``val_bins`` confidence bins and, with ``select``, the best
-        block and the best slot (a copy of the residuals as they are now, replaced whenever an epoch is strictly better under
-        ``val_criterion``; the optimiser's state is not part of it).  Allocations and one small upload; nothing synchronises."""
-        self._mon = fitmonitor.Monitor("TaskResFitState.start_monitor", slots, val_bins, val_criterion, self.residuals if select else None,
-                                       self.residuals.device)
+    def _master(self) -> torch.Tensor:
+        return self.residuals
 
     def validate(self, val_features: torch.Tensor, val_labels, epoch: int) -> None:
         """Enqueue one validation of the current master residuals into slot ``epoch`` of the device history; no host read.
@@ -181,38 +179,17 @@ class TaskResFitState:
         counts as wrong with a NaN nll), anything else is range-checked on the host, once per set.  Without ``start_monitor`` the history
         starts with ``epoch + 1`` slots of 10 bins and no selection; it grows when ``epoch`` lies behind its end."""
         who = "TaskResFitState.validate"
-        if self._mon is None:
-            self.start_monitor(int(epoch) + 1 if isinstance(epoch, int) and epoch >= 0 else 1)
-        mon = self._mon
+        mon = self._monitor_for(epoch)
         epoch = mon.slot(who, epoch)
         C, E = self.base_text_features.shape
         feats, labels_d = mon.operands(who, val_features, val_labels, E, C)
         ops.taskres_val_logits(feats, self.base_text_features, self.residuals, self.alpha, self.scale, out=mon.logits)
         mon.score(epoch, labels_d, self.residuals)
 
-    def val_logits(self) -> torch.Tensor:
-        """The fp32 [N_val, C] logits of the last ``validate``, where the state keeps them (the next ``validate`` overwrites them)."""
-        if self._mon is None or self._mon.logits is None:
-            raise ValueError("TaskResFitState.val_logits: nothing has been validated")
-        return self._mon.logits
-
     def best_residuals(self) -> torch.Tensor:
         """The best slot on the device: the residuals of the best epoch so far, or those ``start_monitor`` saw while no epoch has been
         taken.  No read-back."""
-        if self._mon is None or self._mon.best is None:
-            raise ValueError("TaskResFitState.best_residuals: the monitor does not select (start_monitor(..., select=True))")
-        return self._mon.best
-
-    def monitor_records(self) -> torch.Tensor:
-        """The device history, uint8 [slots, ops.val_record_bytes(val_bins)]; no read-back."""
-        if self._mon is None:
-            raise ValueError("TaskResFitState.monitor_records: nothing has been validated")
-        return self._mon.records
-
-    def monitor(self) -> dict:
-        """The history as numbers (``fitmonitor.monitor_dict``, the dict ``CoOpFitState.monitor`` returns).  It reads the history back:
-        one synchronisation."""
-        return fitmonitor.empty_monitor() if self._mon is None else self._mon.summary()
+        return self._best_block("best_residuals")
 
     def step(self, features: torch.Tensor, labels, lr, want_loss: bool = False) -> Optional[torch.Tensor]:
         """One optimiser step on the batch ``features`` fp32 [B, E] (raw image features on the GPU) and ``labels`` [B] at the rate

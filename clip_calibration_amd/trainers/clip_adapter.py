@@ -70,7 +70,7 @@ class CustomCLIP(_CoOpCLIP):
             state = AdapterFitState(text, fc1.detach().float(), fc2.detach().float(), **fit_args)
             losses, monitor = _fit.run_with_transform("fit_adapter", state, self.clip_model, text.shape[0], text.shape[1], loader, transform,
                                                       epochs, lr, run, watch)
-            fitted = _fit.pack(state.best_weights() if watch[2] else (state.w1, state.w2), losses)
+            fitted = _fit.pack(state.best_weights() if watch["final_model"] == "best_val" else (state.w1, state.w2), losses)
             fitted = fitted + (monitor,) if monitor is not None else fitted
         else:
             from ..adapterfit import fit_adapter

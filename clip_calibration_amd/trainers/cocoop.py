@@ -140,13 +140,13 @@ class CustomCLIP(nn.Module):
             E = int(self.clip_model.geometry.embed_dim)
             watch = _fit.split_monitor_args(who, fit_args, ids.shape[0], E)
             val_batch_size = fit_args.pop("val_batch_size", None)
-            if watch[0] is not None and val_batch_size is not None:
+            if watch["val"] is not None and val_batch_size is not None:
                 from ..fitmonitor import _batch_size
                 _batch_size(who, val_batch_size)
             state = CoCoOpFitState(self.clip_model, ids, params, **fit_args)
             state.val_stream_f16, state.val_batch_size = self.text_stream_f16, val_batch_size
             losses, monitor = _fit.run_with_transform(who, state, self.clip_model, ids.shape[0], E, train_loader, transform, epochs, lr, run, watch)
-            fitted = _fit.pack(state.best_params() if watch[2] else state.params(), losses)
+            fitted = _fit.pack(state.best_params() if watch["final_model"] == "best_val" else state.params(), losses)
             if monitor is not None:
                 fitted = fitted + (monitor,) if isinstance(fitted, tuple) else (fitted, monitor)
         else:

@@ -96,14 +96,14 @@ class CustomCLIP(_CoOpCLIP):
         ``final_model="best_val"`` installs the best epoch's parameters."""
         import math
         from .. import maplefit
-        _fit.image_validation_set("fit_prompt_learner", fit_args)
+        _fit.validation_set("fit_prompt_learner", None, fit_args)
         fit_args.setdefault("logit_scale", math.log(self.scale))
         fit_args.setdefault("class_token_position", getattr(self.prompt_learner, "class_token_position", "end"))
         ids, params = self.prompt_learner.tokenized_prompts, self.learner_params()
         if transform is not None:
             from ..augment import fit_with_transform
             run, epochs, lr = _fit.split_fit_args(fit_args, 5, 0.0035)
-            watch = _fit.split_image_monitor_args("fit_prompt_learner", fit_args)
+            watch = _fit.split_monitor_args("fit_prompt_learner", fit_args)
             state = maplefit.MaPLeFitState(self.clip_model, ids, params, **fit_args)
             end, monitored = _fit.image_end_epoch(state, watch, epochs, len(train_loader))
             losses = fit_with_transform(state, lambda x: x, ids.shape[0], train_loader, transform, epochs, lr, end_epoch=end, **run)

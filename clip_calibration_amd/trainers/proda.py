@@ -132,7 +132,7 @@ class CustomCLIP(nn.Module):
             state = ProDAFitState(self.clip_model, ids, ctx.detach(), **fit_args)
             state.val_class_chunk = val_class_chunk
             losses, monitor = _fit.run_with_transform(who, state, self.clip_model, ids.shape[0], E, train_loader, transform, epochs, lr, run, watch)
-            fitted = _fit.pack(state.best_params() if watch[2] else state.ctx, losses)
+            fitted = _fit.pack(state.best_params() if watch["final_model"] == "best_val" else state.ctx, losses)
             if monitor is not None:
                 fitted = fitted + (monitor,) if isinstance(fitted, tuple) else (fitted, monitor)
             if dynamic:

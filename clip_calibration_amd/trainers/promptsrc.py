@@ -83,7 +83,7 @@ class CustomCLIP(_CoOpCLIP):
         the best epoch's parameters."""
         import math
         from .. import promptsrcfit
-        _fit.image_validation_set("fit_prompts", fit_args)
+        _fit.validation_set("fit_prompts", None, fit_args)
         fit_args.setdefault("logit_scale", math.log(self.scale))
         fit_args.setdefault("class_token_position", getattr(self.prompt_learner, "class_token_position", "end"))
         ids, params = self.prompt_learner.tokenized_prompts, self.prompt_params()
@@ -96,7 +96,7 @@ class CustomCLIP(_CoOpCLIP):
             run, epochs, lr = _fit.split_fit_args(fit_args, 50, 0.0025)
             epochs = int(epochs)
             gpa = fit_args.pop("gpa", (30.0, 30.0))
-            watch = _fit.split_image_monitor_args("fit_prompts", fit_args)
+            watch = _fit.split_monitor_args("fit_prompts", fit_args)
             state = promptsrcfit.PromptSRCFitState(self.clip_model, ids, params, teacher_text_features, **fit_args)
             weights = None if fit_args.get("method", "promptsrc") == "ivlp" else promptsrcfit._gpa_for("fit_prompts", gpa, epochs)
 

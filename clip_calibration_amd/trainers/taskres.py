@@ -93,7 +93,7 @@ class CustomCLIP(nn.Module):
             state = TaskResFitState(base, res.detach().float(), **fit_args)
             losses, monitor = _fit.run_with_transform("fit_residuals", state, self.clip_model, base.shape[0], base.shape[1], loader, transform,
                                                       epochs, lr, run, watch)
-            fitted = _fit.pack(state.best_residuals() if watch[2] else state.residuals, losses)
+            fitted = _fit.pack(state.best_residuals() if watch["final_model"] == "best_val" else state.residuals, losses)
             if monitor is not None:
                 fitted = fitted + (monitor,) if isinstance(fitted, tuple) else (fitted, monitor)
         else:

@@ -45,13 +45,13 @@ class CustomCLIP(ZeroshotCLIP):
         ``final_model="best_val"`` installs the best epoch's prompts into the parameters."""
         import math
         from .. import vptfit
-        _fit.image_validation_set("fit_prompts", fit_args)
+        _fit.validation_set("fit_prompts", None, fit_args)
         fit_args.setdefault("logit_scale", math.log(self.scale))
         text = self.text_features.float()
         if transform is not None:
             from ..augment import fit_with_transform
             run, epochs, lr = _fit.split_fit_args(fit_args, 5, 0.0025)
-            watch = _fit.split_image_monitor_args("fit_prompts", fit_args)
+            watch = _fit.split_monitor_args("fit_prompts", fit_args)
             state = vptfit.VPTFitState(self.clip_model, text, **fit_args)
             end, monitored = _fit.image_end_epoch(state, watch, epochs, len(train_loader))
             losses = fit_with_transform(state, lambda x: x, text.shape[0], train_loader, transform, epochs, lr, end_epoch=end, **run)

@@ -151,8 +151,9 @@ def test_trainers_refuse_two_validation_sets():
     with pytest.raises(ValueError, match="final_model='best_val' needs val"):
         _fit.split_monitor_args("fit_residuals", {"final_model": "best_val"}, 3, 8)
     args = {"val": (torch.randn(5, 8), [0, 1, 2, 0, 1]), "val_bins": 7, "return_monitor": True, "momentum": 0.5}
-    val, bins, select, criterion, want = _fit.split_monitor_args("fit_adapter", args, 3, 8)
-    assert bins == 7 and not select and criterion == "accuracy" and want and args == {"momentum": 0.5}
+    watch = _fit.split_monitor_args("fit_adapter", args, 3, 8)
+    val = watch.pop("val")
+    assert watch == {"val_bins": 7, "final_model": "last_step", "val_criterion": "accuracy", "return_monitor": True} and args == {"momentum": 0.5}
     assert val[1].dtype == torch.int64 and val[1].tolist() == [0, 1, 2, 0, 1]
 
 

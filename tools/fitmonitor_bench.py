@@ -121,13 +121,13 @@ def main():
             st.step(feats, labels, lr)
             torch.cuda.synchronize()
             mon = st._mon
-            rec, img_n = mon["records"][1], mon["val"][1]
+            rec, img_n = mon.records[1], mon.val[1]
             text = st.tower.text
             calls = {
                 "validate": (lambda: st.validate(vf, vl, 1), a.window, window_ms),
                 "step": (lambda: st.step(feats, labels, lr), a.window, window_ms),
-                "val_score": (lambda: ops.val_score(mon["logits"], vl, BINS, rec, mon["ws"]), a.kernel_window, window_ms),
-                "best_select": (lambda: ops.best_select(rec, mon["block"], "accuracy", 1, st.ctx, mon["best"], mon["select_ws"]), a.kernel_window, window_ms),
+                "val_score": (lambda: ops.val_score(mon.logits, vl, BINS, rec, mon.score_ws), a.kernel_window, window_ms),
+                "best_select": (lambda: ops.best_select(rec, mon.block, "accuracy", 1, st.ctx, mon.best, mon.select_ws), a.kernel_window, window_ms),
                 "torch_scoring_with_readback": (lambda: torch_scoring(img_n, text, st.scale, vl), 1, host_ms),
             }
             res = alternate(calls, a.iters, a.warmup)
