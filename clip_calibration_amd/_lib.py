@@ -328,6 +328,10 @@ _SIGNATURES = {
     "clipmi_proda_val_logits_bytes": (_sz, [_vp, _i, _i, _i, _i, _i]),
     "clipmi_proda_val_logits": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _u, _i, _vp, _i64, _vp, _i, _i, _vp, _i, _vp, _vp,
                                      _vp, _sz, _vp, _sz, _vp]),
+    "clipmi_row_scores_acc_bytes": (_sz, [_i, _i]),
+    "clipmi_row_scores": (_i, [_vp, _i64, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "clipmi_row_scores_finish_workspace_bytes": (_sz, [_i, _i]),
+    "clipmi_row_scores_finish": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _sz, _vp]),
 }
 
 for _name, (_res, _args) in _SIGNATURES.items():

@@ -17,14 +17,16 @@ import numpy as np
 import torch
 
 from . import ops
-from .metrics import (AdaptiveECE, PIECE, ece_from_bins, gap_from_groups, macro_f1, macro_f1_from_counts, mce_from_bins,
+from .metrics import (AdaptiveECE, PIECE, classwise_from_bins, ece_from_bins, gap_from_groups, macro_f1, macro_f1_from_counts, mce_from_bins,
                       quantile_edges_from_order_stats, quantile_ranks)
 
 
 class DeviceCalibrationEvaluator:
     def __init__(self, n_bins: int = 10, device="cuda", keep_samples: bool = False, piece_bins: int = 10,
-                 sample_metrics: str = "host", n_classes: Optional[int] = None):
-        """``sample_metrics``: where macro-F1, ACE and PIECE are computed from the kept samples -- "host" (numpy, after one copy of the
+                 sample_metrics: str = "host", n_classes: Optional[int] = None, proper_scores: bool = False):
+        """``proper_scores``: accept whole rows through ``process_rows`` (csrc/row_scores.hip) and report their mean negative log-likelihood,
+        mean Brier score and class-wise ECE behind the other keys; off by default, and then nothing changes.
+        ``sample_metrics``: where macro-F1, ACE and PIECE are computed from the kept samples -- "host" (numpy, after one copy of the
         vectors) or "device" (kernels; needs ``keep_samples`` and ``n_classes``, the width of the logits the predictions index)."""
         if sample_metrics not in ("host", "device"):
             raise ValueError(f"sample_metrics={sample_metrics!r} (\"host\" or \"device\")")
@@ -36,6 +38,9 @@ class DeviceCalibrationEvaluator:
         self.sample_metrics = sample_metrics
         self.n_classes = None if n_classes is None else int(n_classes)
         self.bins = torch.zeros(3 * (n_bins + 1), dtype=torch.float64, device=device)
+        self.proper_scores = bool(proper_scores)
+        self._row_out: List[torch.Tensor] = []      # fp32 [rows, 2] = (nll, brier) per processed batch
+        self._class_acc: Optional[torch.Tensor] = None   # int64 [3, C, n_bins + 1], ops.new_row_scores_acc
         self._conf: List[torch.Tensor] = []
         self._pred: List[torch.Tensor] = []
         self._gt: List[torch.Tensor] = []
@@ -43,6 +48,30 @@ class DeviceCalibrationEvaluator:
     def reset(self):
         self.bins.zero_()
         self._conf, self._pred, self._gt = [], [], []
+        self._row_out, self._class_acc = [], None
+
+    def process_rows(self, rows: torch.Tensor, gt: torch.Tensor, from_probs: bool = False):
+        """Score whole rows -- fp32 logits [B, C], or probabilities as given with ``from_probs`` (a calibrator's rows need not sum to 1) --
+        against their labels: the rows' (nll, brier) stay on the device, the class-wise bins add up in one integer block."""
+        if not self.proper_scores:
+            raise RuntimeError("evaluator was built with proper_scores=False")
+        gt = gt.to(rows.device, torch.int64)
+        row_out, self._class_acc = ops.row_scores(rows, gt, from_probs=from_probs, n_bins=self.n_bins, acc=self._class_acc)
+        self._row_out.append(row_out)
+
+    def _append_proper_scores(self, res) -> None:
+        """``nll`` and ``brier`` raw, ``cw_ece`` x 100, behind the keys that are there -- only when rows were processed."""
+        rows = [r for r in self._row_out if r.shape[0]]
+        if not rows or self._class_acc is None:
+            return
+        row_out = rows[0] if len(rows) == 1 else torch.cat(rows)
+        if row_out.is_cuda:
+            fin = ops.row_scores_finish(row_out.contiguous(), self._class_acc)
+        else:   # blocks merged on the host (a CPU process group): the same arithmetic in numpy
+            r = row_out.numpy().astype(np.float64)
+            fin = {"nll": float(r[:, 0].mean()), "brier": float(r[:, 1].mean()),
+                   "cw_ece": classwise_from_bins(self._class_acc.numpy(), r.shape[0])}
+        res["nll"], res["brier"], res["cw_ece"] = fin["nll"], fin["brier"], 100.0 * fin["cw_ece"]
 
     def process(self, conf: torch.Tensor, pred: torch.Tensor, gt: torch.Tensor):
         gt = gt.to(conf.device, torch.int64)
@@ -137,6 +166,7 @@ class DeviceCalibrationEvaluator:
                     raise ValueError(f"proximity has {proximity.shape[0]} rows for {conf.shape[0]} samples")
                 res["piece"] = 100.0 * PIECE(conf, proximity, pred, gt, self.piece_bins, self.n_bins)
         res["total"] = int(total)
+        self._append_proper_scores(res)
         return res
 
     def _evaluate_device(self, proximity) -> "OrderedDict[str, float]":
@@ -155,4 +185,5 @@ class DeviceCalibrationEvaluator:
         if "piece" in sample:
             res["piece"] = 100.0 * sample["piece"]
         res["total"] = int(total)
+        self._append_proper_scores(res)
         return res

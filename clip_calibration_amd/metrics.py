@@ -206,3 +206,128 @@ def macro_f1_from_counts(counts) -> float:
     denom = (n_pred + n_gt)[classes]                      # 2 tp + fp + fn
     f1 = np.where(denom > 0, 2 * tp[classes] / np.where(denom > 0, denom, 1), 0.0)
     return float(f1.mean())
+
+
+# ---- proper scores of whole probability rows and the class-wise calibration error (csrc/row_scores.hip): the float64 host path, and the
+# restatement the device kernels are held to.  The reference has none of them. ------------------------------------------------------------
+
+CONF_FIXED_ONE = 2.0 ** 32    # the device's conf_sum is 32.32 fixed point
+
+
+def row_probabilities(rows, from_probs: bool = False) -> np.ndarray:
+    """float64 [N, C]: the rows themselves (``from_probs``; they need not sum to 1) or their softmax."""
+    z = np.asarray(rows, dtype=np.float64)
+    if z.ndim != 2 or z.shape[1] < 1:
+        raise ValueError(f"rows {z.shape} must be [N, C >= 1]")
+    if from_probs:
+        return z
+    with np.errstate(invalid="ignore", over="ignore"):
+        e = np.exp(z - z.max(axis=1, keepdims=True)) if z.shape[0] else z
+        return e / e.sum(axis=1, keepdims=True) if z.shape[0] else z
+
+
+def unscorable_rows(rows, from_probs: bool = False) -> np.ndarray:
+    """bool [N]: rows without a softmax -- a NaN, a +inf or nothing but -inf among the logits; any non-finite probability."""
+    z = np.asarray(rows, dtype=np.float64)
+    if from_probs:
+        return ~np.isfinite(z).all(axis=1)
+    return np.isnan(z).any(axis=1) | np.isinf(z.max(axis=1, initial=-np.inf))
+
+
+def row_scores(rows, gt, from_probs: bool = False):
+    """(nll float64 [N], brier float64 [N]): nll_i = logsumexp(z_i) - z_iy, or -log(max(p_iy, FLT_MIN)) for probabilities;
+    brier_i = sum_c (p_ic - [c == y_i])^2.  NaN for a row without a softmax and for a label outside [0, C) (clipmi_val_score's rule)."""
+    z = np.asarray(rows, dtype=np.float64)
+    p = row_probabilities(z, from_probs)
+    gt = np.asarray(gt).astype(np.int64).reshape(-1)
+    N, C = p.shape
+    if gt.shape[0] != N:
+        raise ValueError(f"{N} rows need {N} labels, got {gt.shape[0]}")
+    ok = (gt >= 0) & (gt < C) & ~unscorable_rows(z, from_probs)
+    y = np.where(ok, gt, 0)
+    idx = np.arange(N)
+    nll, brier = np.full(N, np.nan), np.full(N, np.nan)
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        if from_probs:
+            val = -np.log(np.maximum(p[idx, y], float(np.finfo(np.float32).tiny)))
+        else:
+            m = z.max(axis=1)
+            val = np.log(np.exp(z - m[:, None]).sum(axis=1)) - (z[idx, y] - m)
+        onehot = np.zeros_like(p)
+        onehot[idx, y] = 1.0
+        b = ((p - onehot) ** 2).sum(axis=1)
+    nll[ok], brier[ok] = val[ok], b[ok]
+    return nll, brier
+
+
+def NLL(rows, gt, from_probs: bool = False) -> float:
+    """Mean negative log-likelihood of the labels under the rows (logits, or probabilities with ``from_probs``)."""
+    nll = row_scores(rows, gt, from_probs)[0]
+    return float(nll.mean()) if nll.size else float("nan")
+
+
+def Brier(rows, gt, from_probs: bool = False) -> float:
+    """Mean multi-class Brier score: sum_c (p_c - [c == y])^2 per row (Brier 1950, the unnormalised sum over the classes)."""
+    b = row_scores(rows, gt, from_probs)[1]
+    return float(b.mean()) if b.size else float("nan")
+
+
+def classwise_bin_statistics(probs, gt, n_bins: int = 10, unscorable=None) -> np.ndarray:
+    """float64 [3, C, n_bins + 1] = (count, sum_conf, hits): element (i, c) counts in bin ``digitize_bins(p_ic)`` of class c -- below 0
+    in bin 0, as the device's rule clamps --, adds p_ic clamped to [0, 1] to sum_conf and, when c == y_i, 1 to hits.  The elements of
+    an ``unscorable`` row (bool [N]) count in bin n_bins, hit nothing and add nothing, as on the device."""
+    p = np.asarray(probs, dtype=np.float64)
+    gt = np.asarray(gt).astype(np.int64).reshape(-1)
+    N, C = p.shape
+    bad = np.zeros(N, bool) if unscorable is None else np.asarray(unscorable, bool)
+    which = np.maximum(digitize_bins(p, n_bins), 0)
+    which[bad] = n_bins
+    cls = np.broadcast_to(np.arange(C), (N, C))
+    out = np.zeros((3, C, n_bins + 1))
+    np.add.at(out[0], (cls, which), 1.0)
+    np.add.at(out[1], (cls, which), np.where(bad[:, None], 0.0, np.clip(np.nan_to_num(p), 0.0, 1.0)))
+    hit = (gt >= 0) & (gt < C) & ~bad
+    rows = np.nonzero(hit)[0]
+    np.add.at(out[2], (gt[rows], which[rows, gt[rows]]), 1.0)
+    return out
+
+
+def classwise_fixed_point(probs, gt, n_bins: int = 10, unscorable=None) -> np.ndarray:
+    """int64 [3, C, n_bins + 1]: ``classwise_bin_statistics`` as the device accumulates it -- every element adds
+    round-half-even(clip(p, 0, 1) * 2^32) to sum_conf; integer sums, so exact and independent of the order."""
+    p = np.asarray(probs, dtype=np.float64)
+    N, C = p.shape
+    bad = np.zeros(N, bool) if unscorable is None else np.asarray(unscorable, bool)
+    st = classwise_bin_statistics(p, gt, n_bins, bad)
+    which = np.maximum(digitize_bins(p, n_bins), 0)
+    which[bad] = n_bins
+    fx = np.rint(np.clip(np.nan_to_num(p), 0.0, 1.0) * CONF_FIXED_ONE).astype(np.int64)
+    fx[bad] = 0
+    out = np.zeros((3, C, n_bins + 1), dtype=np.int64)
+    out[0], out[2] = st[0].astype(np.int64), st[2].astype(np.int64)
+    np.add.at(out[1], (np.broadcast_to(np.arange(C), (N, C)), which), fx)
+    return out
+
+
+def classwise_from_bins(acc, n: int) -> float:
+    """Class-wise ECE from [3, C, n_bins + 1] = (count, sum_conf, hits) over ``n`` rows:
+    (1 / C) sum_c sum_b (n_cb / n) |hits_cb / n_cb - conf_cb / n_cb| = sum_cb |hits_cb - conf_cb| / (n C) over the n_bins intervals, with
+    bin n_bins (p == 1.0) counted into the last one, as ``mce_from_bins`` does.  An integer ``acc`` is the device's block, whose sum_conf
+    is 32.32 fixed point."""
+    a = np.asarray(acc)
+    if a.ndim != 3 or a.shape[0] != 3 or a.shape[2] < 2:
+        raise ValueError(f"classwise_from_bins: acc {a.shape} is not [3, C, n_bins + 1]")
+    conf = a[1].astype(np.float64) / CONF_FIXED_ONE if np.issubdtype(a.dtype, np.integer) else a[1].astype(np.float64)
+    hits = a[2].astype(np.float64)
+    conf = np.concatenate([conf[:, :-2], conf[:, -2:].sum(axis=1, keepdims=True)], axis=1)
+    hits = np.concatenate([hits[:, :-2], hits[:, -2:].sum(axis=1, keepdims=True)], axis=1)
+    if n < 1:
+        return float("nan")
+    return float(np.abs(hits - conf).sum(axis=1).sum() / n / a.shape[1])
+
+
+def ClasswiseECE(probs, gt, n_bins: int = 10) -> float:
+    """Class-wise expected calibration error of probability rows (Kull et al. 2019; Nixon et al.'s static calibration error): every
+    class's probabilities are binned on their own and the classes' gaps averaged."""
+    p = np.asarray(probs, dtype=np.float64)
+    return classwise_from_bins(classwise_bin_statistics(p, gt, n_bins, unscorable_rows(p, True)), p.shape[0])

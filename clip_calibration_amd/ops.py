@@ -1827,3 +1827,94 @@ def proda_val_mean(text: torch.Tensor, group: int) -> torch.Tensor:
     out = torch.empty(rows // group, E, dtype=torch.float32, device=text.device)
     check(lib.clipmi_proda_val_mean(text.data_ptr(), out.data_ptr(), rows // group, int(group), E, _stream()), "clipmi_proda_val_mean")
     return out
+
+
+ROW_SCORES_MAX_BINS = 1024     # clipmi_ece_accumulate's limit
+
+
+def _row_score_bins(who: str, n_bins) -> int:
+    if isinstance(n_bins, bool) or int(n_bins) != n_bins or not 1 <= int(n_bins) <= ROW_SCORES_MAX_BINS:
+        raise ValueError(f"{who}: n_bins={n_bins} must be an integer in 1..{ROW_SCORES_MAX_BINS}")
+    return int(n_bins)
+
+
+def new_row_scores_acc(n_classes: int, n_bins: int, device) -> torch.Tensor:
+    """The zeroed class-wise block of ``row_scores``: int64 [3, C, n_bins + 1] = count | conf_sum (32.32 fixed point) | hits on ``device``
+    (``metrics.classwise_from_bins`` reads it)."""
+    n_bins = _row_score_bins("new_row_scores_acc", n_bins)
+    if int(n_classes) < 1:
+        raise ValueError(f"new_row_scores_acc: n_classes={n_classes} (>= 1)")
+    return torch.zeros(3, int(n_classes), n_bins + 1, dtype=torch.int64, device=device)
+
+
+def row_scores(rows: torch.Tensor, labels: torch.Tensor, from_probs: bool = False, n_bins: int = 10, acc: Optional[torch.Tensor] = None,
+               row_out: Optional[torch.Tensor] = None, row0: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """clipmi_row_scores: fp32 ``rows`` [N, C] (the rows may be a column slice) -- logits, or probabilities as given with ``from_probs`` --
+    against ``labels`` int64 [N]: per row the negative log-likelihood and the Brier score into ``row_out[row0 : row0 + N]`` (fp32 [*, 2] on
+    the GPU, made for this call alone when None), and every element into its class's confidence bin of ``acc`` (``new_row_scores_acc``,
+    made when None), which is ADDED to: integer sums, so the block's bytes do not depend on how the rows were cut into calls.  A label
+    outside [0, C) gives a NaN row score and no hit; a row without a softmax (a NaN, a +inf, nothing but -inf; any non-finite
+    probability) gives a NaN row score and counts in the last bin only.  Nothing is read back; the inputs are not written.
+    Returns ``(row_out, acc)``; ``row_scores_finish`` turns them into the scalars."""
+    who = "row_scores"
+    n_bins = _row_score_bins(who, n_bins)
+    if not isinstance(rows, torch.Tensor) or rows.dim() != 2 or rows.shape[1] < 1:
+        raise ValueError(f"{who}: rows {tuple(getattr(rows, 'shape', ()))} must be [N, C >= 1]")
+    if not rows.is_cuda:
+        raise RuntimeError(f"clipmi: `rows` must be a tensor on the GPU (got {rows.device}); the HIP path has no CPU fallback")
+    if rows.dtype != torch.float32:
+        raise TypeError(f"clipmi: `rows` has dtype {rows.dtype}, expected torch.float32")
+    if rows.device.index != torch.cuda.current_device():
+        raise RuntimeError(f"clipmi: `rows` is on {rows.device} but the current device is cuda:{torch.cuda.current_device()}")
+    if rows.shape[0] and (rows.stride(1) != 1 or rows.stride(0) < rows.shape[1]):
+        rows = rows.contiguous()
+    labels = _dev(labels, "labels", (torch.int64,))
+    N, Cn = rows.shape
+    if labels.shape != (N,):
+        raise ValueError(f"{who}: {N} rows need {N} labels, got {tuple(labels.shape)}")
+    if acc is None:
+        acc = new_row_scores_acc(Cn, n_bins, rows.device)
+    _in_place(acc, torch.int64, f"{who}: acc must be a contiguous int64 [3, {Cn}, {n_bins + 1}] tensor on the GPU (new_row_scores_acc)",
+              numel=3 * Cn * (n_bins + 1))
+    if row_out is None:
+        row_out = torch.empty(row0 + N, 2, dtype=torch.float32, device=rows.device)
+    if not (isinstance(row_out, torch.Tensor) and row_out.is_cuda and row_out.dtype == torch.float32 and row_out.is_contiguous()
+            and row_out.dim() == 2 and row_out.shape[1] == 2):
+        raise TypeError(f"{who}: row_out must be a contiguous fp32 [rows, 2] tensor on the GPU")
+    if isinstance(row0, bool) or int(row0) != row0 or row0 < 0 or row0 + N > row_out.shape[0]:
+        raise ValueError(f"{who}: rows {row0} .. {row0 + N} lie outside the {row_out.shape[0]} row scores")
+    if N == 0:
+        return row_out, acc
+    check(lib.clipmi_row_scores(rows.data_ptr(), rows.stride(0), labels.data_ptr(), N, Cn, int(bool(from_probs)), n_bins,
+                                row_out.data_ptr() + 8 * int(row0), acc.data_ptr(), _stream()), "clipmi_row_scores")
+    return row_out, acc
+
+
+def row_scores_finish_device(row_out: torch.Tensor, acc: torch.Tensor, out: Optional[torch.Tensor] = None,
+                             workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """clipmi_row_scores_finish without the read-back: float64 [4] on the GPU = mean nll, mean Brier, class-wise ECE (a fraction), N."""
+    who = "row_scores_finish"
+    if not (isinstance(row_out, torch.Tensor) and row_out.is_cuda and row_out.dtype == torch.float32 and row_out.is_contiguous()
+            and row_out.dim() == 2 and row_out.shape[1] == 2 and row_out.shape[0] >= 1):
+        raise TypeError(f"{who}: row_out must be a contiguous fp32 [N >= 1, 2] tensor on the GPU")
+    if not (isinstance(acc, torch.Tensor) and acc.is_cuda and acc.dtype == torch.int64 and acc.is_contiguous() and acc.dim() == 3
+            and acc.shape[0] == 3 and acc.shape[1] >= 1 and acc.shape[2] >= 2):
+        raise TypeError(f"{who}: acc must be a contiguous int64 [3, C, n_bins + 1] tensor on the GPU (new_row_scores_acc)")
+    N, Cn, n_bins = int(row_out.shape[0]), int(acc.shape[1]), int(acc.shape[2]) - 1
+    if out is None:
+        out = torch.empty(4, dtype=torch.float64, device=row_out.device)
+    _in_place(out, torch.float64, f"{who}: out must be a contiguous float64 [4] tensor on the GPU", numel=4)
+    need = lib.clipmi_row_scores_finish_workspace_bytes(N, Cn)
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=row_out.device)
+    check(lib.clipmi_row_scores_finish(row_out.data_ptr(), N, acc.data_ptr(), Cn, n_bins, out.data_ptr(), workspace.data_ptr(), workspace.numel(),
+                                       _stream()), "clipmi_row_scores_finish")
+    return out
+
+
+def row_scores_finish(row_out: torch.Tensor, acc: torch.Tensor, workspace: Optional[torch.Tensor] = None) -> dict:
+    """clipmi_row_scores_finish: ``dict(nll, brier, cw_ece, n)`` -- the mean negative log-likelihood, the mean Brier score, the class-wise
+    ECE as a fraction and the row count -- from every row of ``row_out`` and the block ``acc``; the order of the additions depends on N
+    and C alone, so the numbers are the same bits however the rows were chunked.  The one read-back of the path: it synchronises."""
+    o = row_scores_finish_device(row_out, acc, workspace=workspace).cpu().numpy()
+    return {"nll": float(o[0]), "brier": float(o[1]), "cw_ece": float(o[2]), "n": int(o[3])}

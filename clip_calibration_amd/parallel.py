@@ -158,6 +158,25 @@ def merge_ece_bins(bins: torch.Tensor, group=None) -> torch.Tensor:
     return bins
 
 
+def merge_row_scores(evaluator, group=None) -> None:
+    """The proper scores of a sharded split: the class-wise integer blocks are summed (exact, whatever the order) and the per-row
+    (nll, brier) vectors concatenated rank-major.  A rank whose shard was empty has no block yet and learns its shape from the others."""
+    if not dist.is_initialized() or dist.get_world_size(group) == 1:
+        return
+    dev = evaluator.bins.device
+    acc = evaluator._class_acc
+    shape = torch.tensor(list(acc.shape[1:]) if acc is not None else [0, 0], dtype=torch.int64, device=dev)
+    dist.all_reduce(shape, op=dist.ReduceOp.MAX, group=group)
+    if int(shape[0]) > 0:
+        if acc is None:
+            acc = torch.zeros(3, int(shape[0]), int(shape[1]), dtype=torch.int64, device=dev)
+        dist.all_reduce(acc, op=dist.ReduceOp.SUM, group=group)
+        evaluator._class_acc = acc
+    rows = [r for r in evaluator._row_out if r.shape[0]]
+    local = torch.cat(rows) if rows else torch.zeros(0, 2, dtype=torch.float32, device=dev)
+    evaluator._row_out = [all_gather_varlen(local, group)]
+
+
 def all_gather_varlen(local: torch.Tensor, group=None) -> torch.Tensor:
     """Concatenate per-rank tensors whose dim-0 lengths differ (rank-major): lengths are exchanged first, shards padded to
     the longest, one all-gather, padding stripped."""
@@ -191,6 +210,8 @@ def gather_samples(evaluator, proximity=None, group=None, has_proximity: Optiona
         evaluator._conf = [all_gather_varlen(cat(evaluator._conf, torch.float32), group)]
         evaluator._pred = [all_gather_varlen(cat(evaluator._pred, torch.int64), group)]
         evaluator._gt = [all_gather_varlen(cat(evaluator._gt, torch.int64), group)]
+    if getattr(evaluator, "proper_scores", False):   # rank-uniform configuration, as keep_samples
+        merge_row_scores(evaluator, group)
     if has_proximity is None:
         has_proximity = proximity is not None
     if not has_proximity:

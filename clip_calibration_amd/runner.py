@@ -152,7 +152,7 @@ def text_feature_dict(base_zs: Dict[str, np.ndarray], current_text_features_zs, 
 @torch.no_grad()
 def test(infer: Callable, loader: Iterable[Tuple[torch.Tensor, torch.Tensor]], val_dict: Optional[Dict[str, np.ndarray]] = None,
          calibrator: Optional[VLCalibration] = None, image_k: int = 10, ece_bins: int = 10, piece_bins: int = 10,
-         device="cuda", group=None, sample_metrics: str = "host") -> "OrderedDict[str, float]":
+         device="cuda", group=None, sample_metrics: str = "host", proper_scores: bool = False) -> "OrderedDict[str, float]":
     """VLBaseLearner.test (base_learner.py:59-152): inference over the split, DAC, softmax top-1, proximity of every test
     image to the base-class val images (exp(-mean K-NN distance), :121-137), then the evaluator's metrics.  Under
     torch.distributed each rank passes its own shard of the loader; samples are gathered before the sample-level metrics.
@@ -162,7 +162,11 @@ def test(infer: Callable, loader: Iterable[Tuple[torch.Tensor, torch.Tensor]], v
     is per sample -- yields (conf', pred').
     ``sample_metrics="device"`` computes macro-F1, ACE and PIECE with kernels from the kept (and, across ranks, gathered) device vectors
     and leaves the proximity on the device; "host" (default) copies the vectors once and uses numpy.  The class count the device
-    metrics need is the width of the logits, so an empty split (no batch, hence no width) is evaluated the host way."""
+    metrics need is the width of the logits, so an empty split (no batch, hence no width) is evaluated the host way.
+    ``proper_scores=True`` appends ``nll``, ``brier`` (both raw) and ``cw_ece`` (x 100) behind the other keys, scored from whole rows on the
+    device (csrc/row_scores.hip): each batch's (DAC-scaled) logits without a base calibrator, the calibrated matrix -- probabilities as the
+    calibrator wrote them -- with one, so the score belongs to what is deployed.  The other keys keep their bits.  An empty split has no
+    rows to score and goes the host way as before: the three keys are not appended."""
     if sample_metrics not in ("host", "device"):
         raise ValueError(f"sample_metrics={sample_metrics!r} (\"host\" or \"device\")")
     ev = None   # built at the first batch, which tells the class count
@@ -175,23 +179,27 @@ def test(infer: Callable, loader: Iterable[Tuple[torch.Tensor, torch.Tensor]], v
         out = _call(infer, image, dac_conf=dac, want_conf_pred=True)
         if ev is None:
             ev = DeviceCalibrationEvaluator(ece_bins, device=device, keep_samples=True, piece_bins=piece_bins, sample_metrics=sample_metrics,
-                                            n_classes=int(out[0].shape[1]))
+                                            n_classes=int(out[0].shape[1]), proper_scores=proper_scores)
         if procal is None:
             ev.process(out[3], out[4], label)
+            if proper_scores:
+                ev.process_rows(out[0].float(), label)
         else:   # out[0] already holds the DAC-scaled logits (the fused logits kernels scale in place): no DAC again below
             kept_logits.append(out[0])
             kept_labels.append(label)
         feats.append(out[1])
     if ev is None:
-        ev = DeviceCalibrationEvaluator(ece_bins, device=device, keep_samples=True, piece_bins=piece_bins)
+        ev = DeviceCalibrationEvaluator(ece_bins, device=device, keep_samples=True, piece_bins=piece_bins, proper_scores=proper_scores)
     proximity = None
     if val_dict is not None and feats:
         refs = torch.as_tensor(np.asarray(val_dict["val_image_features"]), dtype=torch.float32, device=device)
         k = min(image_k, refs.shape[0])
         proximity = torch.exp(-knn_dists_device(torch.cat(feats).float(), refs, k).mean(dim=1))
     if procal is not None and kept_logits:
-        _, conf, pred = procal.predict_device(torch.cat(kept_logits).float(), proximity)
+        probs, conf, pred = procal.predict_device(torch.cat(kept_logits).float(), proximity, want_probs=proper_scores)
         ev.process(conf, pred, torch.cat(kept_labels))
+        if proper_scores:
+            ev.process_rows(probs, torch.cat(kept_labels), from_probs=True)
     if group is not None or (torch.distributed.is_available() and torch.distributed.is_initialized()
                              and torch.distributed.get_world_size() > 1):
         from .parallel import gather_samples

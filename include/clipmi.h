@@ -1653,6 +1653,45 @@ size_t clipmi_best_select_workspace_bytes(int64_t n_floats);
 int clipmi_best_select(const void* record, void* best_block, int criterion, int epoch, const float* params, float* best_params, int64_t n_floats,
                        void* workspace, size_t workspace_bytes, clipmi_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------
+ * Row scores: proper scores of whole probability rows and the class-wise calibration error at test time (csrc/row_scores.hip, DESIGN.md
+ * "Row scores"; the float64 restatement is clip_calibration_amd/metrics.py NLL / Brier / ClasswiseECE).  Nothing is read back to the host.
+ * Additive exports: the ABI version stays.
+ *
+ * clipmi_row_scores: rows fp32 [N, C] with the row stride ld (elements), labels int64 [N].  from_probs = 0: the rows are logits and
+ * p_c = exp(z_c - max) * (1 / sum), sum = sum_c exp(z_c - max), all in fp32, a lane of the row's wave adding its columns c = lane, lane + 64,
+ * ... in ascending order before the xor butterfly (clipmi_val_score's order); from_probs = 1: p_c is the entry as given, the rows need not sum
+ * to 1.  row_out fp32 [N, 2] = per row {nll, brier}: nll = log(sum) - (z[label] - max), or -log(max(p[label], FLT_MIN)); brier =
+ * sum_c (p_c - [c == label])^2.  class_acc int64 [3][C][n_bins + 1] = count | conf_sum | hits is ADDED to: element (i, c) counts in bin
+ * numpy.digitize(p_ic, numpy.linspace(0, 1, n_bins + 1)) - 1 of class c (clipmi_ece_accumulate's rule, one device function: the last bin,
+ * n_bins, holds p == 1.0), adds round-to-nearest-even(clamp(p_ic, 0, 1) * 2^32) to conf_sum (32.32 fixed point) and, when c == label, 1 to
+ * hits.  The caller zeroes the block once (clipmi_row_scores_acc_bytes(C, n_bins) = 24 C (n_bins + 1) bytes, 0 for arguments the call
+ * refuses) and may then add any number of calls, in batches, in stream order: integer additions only (64-bit integer atomics), so the
+ * block's bytes depend neither on the order of the atomics nor on how the rows were cut into calls, and the same inputs give the same bits.
+ * For a chunk that starts at row row0 the caller passes row_out + 2 row0 and labels + row0.
+ * Rows that cannot be scored follow clipmi_val_score's rule: a label outside [0, C) is never used as an address, the row's nll and brier are
+ * NaN and it counts no hit (its probabilities are binned all the same); a row without a softmax -- it holds a NaN or a +inf or nothing but
+ * -inf; with from_probs any non-finite entry -- has a NaN nll and brier, counts no hit, and each of its elements counts in bin n_bins (where
+ * a NaN sorts) and adds nothing to conf_sum.  The inputs are not written.
+ * N == 0 returns CLIPMI_OK without a launch.  Every check precedes the launch.  CLIPMI_ERR_SHAPE: N < 0, C < 1, ld < C, C (n_bins + 1) >=
+ * 2^31; CLIPMI_ERR_ARG: n_bins outside 1..1024 (clipmi_ece_accumulate's limit), from_probs other than 0 or 1, a null pointer, rows not
+ * 4-byte aligned, labels, row_out or class_acc not 8-byte aligned.
+ *
+ * clipmi_row_scores_finish: out float64 [4] (device) = {mean nll, mean brier, class-wise ECE, N} from the N row scores and the block:
+ * class-wise ECE = (1 / C) sum_c sum_b (n_cb / N) |hits_cb / n_cb - conf_cb / n_cb| = sum_c sum_b |hits_cb - conf_cb| / (N C) over the
+ * n_bins intervals, bin n_bins (p == 1.0) counted into the last one.  Launch 1: float64 partial sums, of the rows per 4096 rows (a thread
+ * its 16 rows in ascending order, then a fixed halving tree) and of the classes' gaps per 256 classes; launch 2: one thread adds the
+ * partials in ascending order.  The order depends on N and C alone: the four doubles are the same bits however the rows were chunked.
+ * workspace (256-byte aligned): clipmi_row_scores_finish_workspace_bytes(N, C), 0 for arguments the call refuses.  CLIPMI_ERR_SHAPE: N < 1,
+ * C < 1; CLIPMI_ERR_ARG: n_bins outside 1..1024, a null pointer, an alignment; CLIPMI_ERR_WORKSPACE.
+ * ---------------------------------------------------------------------------------------------------- */
+size_t clipmi_row_scores_acc_bytes(int C, int n_bins);
+int clipmi_row_scores(const float* rows, int64_t ld, const int64_t* labels, int N, int C, int from_probs, int n_bins, float* row_out, void* class_acc,
+                      clipmi_stream_t stream);
+size_t clipmi_row_scores_finish_workspace_bytes(int N, int C);
+int clipmi_row_scores_finish(const float* row_out, int N, const void* class_acc, int C, int n_bins, double* out, void* workspace,
+                             size_t workspace_bytes, clipmi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
