@@ -170,6 +170,12 @@ _SIGNATURES = {
     "clipmi_tempscale_workspace_bytes": (_sz, [_i]),
     "clipmi_tempscale_batch": (_i, [_vp, _i64, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "clipmi_tempscale_fit": (_i, [_vp, _i64, _vp, _vp, _i, _i, _i, _i, _i, _vp, _f, _f, _f, _i, _vp, _vp, _vp, _sz, _vp]),
+    "clipmi_pts_param_count": (_i, [_i, _i, _i]),
+    "clipmi_pts_topk": (_i, [_vp, _i64, _i, _i, _i, _vp, _vp]),
+    "clipmi_pts_apply": (_i, [_vp, _i64, _i, _i, _vp, _i, _i, _i, _vp, _i64, _vp, _vp]),
+    "clipmi_pts_eval": (_i, [_vp, _vp, _i64, _vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "clipmi_pts_fit": (_i, [_vp, _i64, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _f, _f, _f, _i, C.c_double, C.c_double, C.c_double,
+                            _vp, _vp, _vp, _sz, _vp]),
     "clipmi_adapter_train_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "clipmi_adapter_train_step": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _vp, _i, _f, _f, _f, _i, _vp, _vp, _sz, _vp]),
     "clipmi_adapter_fit": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _f, _vp, _i, _f, _f, _f, _i, _vp,

@@ -594,6 +594,137 @@ def tempscale_fit(cosine: torch.Tensor, labels: torch.Tensor, state: torch.Tenso
     return losses
 
 
+# ---- Parameterized temperature scaling (CALIBRATION.SCALING.MODE 'ParameterizedTempScaling', train.py:238-247) ------
+def _pts_rows(logits: torch.Tensor, who: str) -> torch.Tensor:
+    """fp32 [N, C] whose rows are contiguous (a column slice of a wider matrix keeps its row stride: ld > C); N may be 0."""
+    if (isinstance(logits, torch.Tensor) and logits.dim() == 2 and logits.shape[0] > 0 and logits.stride(1) == 1
+            and logits.stride(0) >= logits.shape[1]):
+        _dev(logits[:1], "logits", (torch.float32,))     # read in place with its row stride: the device and dtype checks only
+    else:
+        logits = _dev(logits, "logits", (torch.float32,))
+    if logits.dim() != 2:
+        raise ValueError(f"{who}: logits {tuple(logits.shape)} must be [N, C]")
+    return logits
+
+
+def _pts_net(who: str, n_layers: int, n_nodes: int, top_k: int, C: int) -> int:
+    """The parameter count of the net after the library's own limits (include/clipmi.h, clipmi_pts_param_count)."""
+    n_layers, n_nodes, top_k = int(n_layers), int(n_nodes), int(top_k)
+    P = lib.clipmi_pts_param_count(n_layers, n_nodes, top_k)
+    if P == 0:
+        raise ValueError(f"{who}: n_layers={n_layers} (0 .. 4), n_nodes={n_nodes} (1 .. 32), top_k={top_k} (1 .. 32)")
+    if C < top_k or C < 2:
+        raise ValueError(f"{who}: {C} classes (at least 2, and at least top_k={top_k})")
+    return P
+
+
+def pts_topk(logits: torch.Tensor, top_k: int) -> torch.Tensor:
+    """fp32 [N, top_k]: the ``top_k`` largest values of every row, descending -- ``torch.sort(descending=True)``'s first columns, bit for
+    bit (+0.0 and -0.0 compare equal and come in index order).  -inf is an ordinary value; a row that holds a NaN gives NaNs
+    (include/clipmi.h, clipmi_pts_topk)."""
+    logits = _pts_rows(logits, "pts_topk")
+    N, Cn = logits.shape
+    top_k = int(top_k)
+    _pts_net("pts_topk", 0, 1, top_k, Cn)
+    out = torch.empty(N, top_k, dtype=torch.float32, device=logits.device)
+    check(lib.clipmi_pts_topk(logits.data_ptr(), logits.stride(0) if N else Cn, N, Cn, top_k, out.data_ptr(), _stream()), "clipmi_pts_topk")
+    return out
+
+
+def pts_apply(logits: torch.Tensor, params: torch.Tensor, n_layers: int, n_nodes: int, top_k: int, out: Optional[torch.Tensor] = None,
+              want_temperature: bool = False):
+    """``logits / T`` with every row's own temperature from the PTS net ``params`` (fp32 [P], include/clipmi.h), in one launch.  ``out``
+    (fp32 [N, C] with contiguous rows) may be ``logits`` itself; None allocates.  Returns out, or (out, T fp32 [N]) with
+    ``want_temperature``."""
+    logits = _pts_rows(logits, "pts_apply")
+    N, Cn = logits.shape
+    P = _pts_net("pts_apply", n_layers, n_nodes, top_k, Cn)
+    params = _dev(params, "params", (torch.float32,))
+    if params.shape != (P,):
+        raise ValueError(f"pts_apply: params {tuple(params.shape)} must be fp32 [{P}]")
+    if out is None:
+        out = torch.empty(N, Cn, dtype=torch.float32, device=logits.device)
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.shape == logits.shape and out.device == logits.device
+              and (N == 0 or (out.stride(1) == 1 and out.stride(0) >= Cn))):
+        raise ValueError(f"pts_apply: out must be an fp32 GPU tensor {tuple(logits.shape)} with contiguous rows")
+    temp = torch.empty(N, dtype=torch.float32, device=logits.device) if want_temperature else None
+    check(lib.clipmi_pts_apply(logits.data_ptr(), logits.stride(0) if N else Cn, N, Cn, params.data_ptr(), int(n_layers), int(n_nodes), int(top_k),
+                               out.data_ptr(), out.stride(0) if N else Cn, None if temp is None else temp.data_ptr(), _stream()), "clipmi_pts_apply")
+    return (out, temp) if want_temperature else out
+
+
+def _pts_problem(who: str, logits, labels, n_layers, n_nodes, top_k):
+    logits = _pts_rows(logits, who)
+    labels = _dev(labels, "labels", (torch.int64,))
+    N, Cn = logits.shape
+    if N < 1 or labels.shape != (N,):
+        raise ValueError(f"{who}: logits {tuple(logits.shape)} must be [N >= 1, C] with one label per row, got labels {tuple(labels.shape)}")
+    return logits, labels, _pts_net(who, n_layers, n_nodes, top_k, Cn)
+
+
+def pts_eval(features: torch.Tensor, logits: torch.Tensor, labels: torch.Tensor, params: torch.Tensor, n_layers: int, n_nodes: int, top_k: int,
+             rows: Optional[torch.Tensor] = None, first: int = 0, n_rows: Optional[int] = None) -> torch.Tensor:
+    """One batch of the PTS loss at ``params``, nothing updated: fp32 [1 + P] on the device, (mean loss, the mean gradient of every
+    parameter) over the samples ``rows`` (int32 indices), or ``first .. first + n_rows - 1`` (every row by default).  ``features`` is
+    ``pts_topk(logits, top_k)``."""
+    logits, labels, P = _pts_problem("pts_eval", logits, labels, n_layers, n_nodes, top_k)
+    N, Cn = logits.shape
+    features = _dev(features, "features", (torch.float32,))
+    params = _dev(params, "params", (torch.float32,))
+    if features.shape != (N, int(top_k)) or params.shape != (P,):
+        raise ValueError(f"pts_eval: features {tuple(features.shape)} must be [{N}, {int(top_k)}] and params {tuple(params.shape)} [{P}]")
+    rows, pr = _opt(rows, "rows", (torch.int32,))
+    if rows is not None:
+        if rows.dim() != 1 or rows.numel() < 1:
+            raise ValueError(f"pts_eval: rows {tuple(rows.shape)} must be a non-empty index vector")
+        first, n = 0, rows.numel()
+    else:
+        first = int(first)
+        n = N - first if n_rows is None else int(n_rows)
+        if first < 0 or n < 1 or first + n > N:
+            raise ValueError(f"pts_eval: rows {first} .. {first + n} of {N}")
+    out = torch.empty(1 + P, dtype=torch.float32, device=logits.device)
+    ws = torch.empty(n * (2 + 2 * int(n_layers) * int(n_nodes)), dtype=torch.float32, device=logits.device)
+    check(lib.clipmi_pts_eval(features.data_ptr(), logits.data_ptr(), logits.stride(0), labels.data_ptr(), pr, first, n, N, Cn, params.data_ptr(),
+                              int(n_layers), int(n_nodes), int(top_k), out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "clipmi_pts_eval")
+    return out
+
+
+def pts_fit(logits: torch.Tensor, labels: torch.Tensor, state: torch.Tensor, n_layers: int, n_nodes: int, top_k: int, lr: torch.Tensor,
+            batch_size: int, epochs: int, optimizer: int = _lib.OPTIM_SGD, momentum: float = 0.0, dampening: float = 0.0, weight_decay: float = 0.0,
+            nesterov: bool = False, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8, order: Optional[torch.Tensor] = None,
+            drop_last: bool = False, want_losses: bool = False) -> Optional[torch.Tensor]:
+    """The whole PTS run, enqueued without a host synchronisation (include/clipmi.h, clipmi_pts_fit).  ``state`` fp32 [3 P + 2] on the
+    device is updated in place: (params, two optimiser buffers, steps taken as int32 bits, last batch loss) -- (init, zeros) starts a
+    fresh fit, a returned state continues one.  ``lr`` fp32 [steps], one rate per step; ``order`` int32 [epochs, N] or None (0 .. N-1
+    every epoch).  Returns the per-step batch losses fp32 [steps] when ``want_losses``."""
+    logits, labels, P = _pts_problem("pts_fit", logits, labels, n_layers, n_nodes, top_k)
+    N, Cn = logits.shape
+    batch_size, epochs = int(batch_size), int(epochs)
+    if batch_size < 1 or epochs < 0:
+        raise ValueError(f"pts_fit: batch_size={batch_size} (>= 1), epochs={epochs} (>= 0)")
+    if optimizer not in (_lib.OPTIM_SGD, _lib.OPTIM_ADAM):
+        raise ValueError(f"pts_fit: optimizer={optimizer!r} (OPTIM_SGD or OPTIM_ADAM)")
+    steps = epochs * (N // batch_size if drop_last else -(-N // batch_size))
+    _in_place(state, torch.float32, f"pts_fit: state must be a contiguous fp32 GPU tensor of 3 * {P} + 2 (it is updated in place)", exc=ValueError,
+              numel=3 * P + 2)
+    lr = _dev(lr, "lr", (torch.float32,))
+    if lr.shape != (steps,):
+        raise ValueError(f"pts_fit: lr {tuple(lr.shape)} must hold one rate per step ({steps})")
+    order, po = _opt(order, "order", (torch.int32,))
+    if order is not None and order.shape != (epochs, N):
+        raise ValueError(f"pts_fit: order {tuple(order.shape)} must be [epochs, N] = [{epochs}, {N}]")
+    losses = torch.empty(steps, dtype=torch.float32, device=logits.device) if want_losses else None
+    if steps == 0:   # nothing to launch, and an empty lr has no address to hand over
+        return losses
+    ws = torch.empty(N * int(top_k) + min(batch_size, N) * (2 + 2 * int(n_layers) * int(n_nodes)), dtype=torch.float32, device=logits.device)
+    check(lib.clipmi_pts_fit(logits.data_ptr(), logits.stride(0), labels.data_ptr(), po, N, Cn, int(n_layers), int(n_nodes), int(top_k), batch_size,
+                             epochs, int(bool(drop_last)), lr.data_ptr(), int(optimizer), float(momentum), float(dampening), float(weight_decay),
+                             int(bool(nesterov)), float(betas[0]), float(betas[1]), float(eps), state.data_ptr(),
+                             None if losses is None else losses.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "clipmi_pts_fit")
+    return losses
+
+
 # ---- CLIP-Adapter training (clip_adapter.py:138-187) ---------------------------------------------------------------
 def _adapter_problem(features, labels, text, w1, w2, m1, m2, momentum: float, who: str):
     """The tensors of one adapter training call, checked: raw features fp32 [N, E] (contiguous rows, row stride kept), labels int64 [N],

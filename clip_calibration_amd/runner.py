@@ -137,6 +137,21 @@ def fit_temperature(infer: Callable, loader: Iterable[Tuple[torch.Tensor, torch.
     return fit_logit_scale(torch.cat(logits), torch.cat(labels), **fit_args)
 
 
+@torch.no_grad()
+def fit_pts(infer: Callable, loader: Iterable[Tuple[torch.Tensor, torch.Tensor]], device="cuda", **fit_args):
+    """Parameterized temperature scaling's training run for any ``infer`` whose 3-tuple starts with the base model's SCALED logits
+    (``CustomCLIPParameterizedCalibration.scaled_logits``): one pass of ``loader`` through it, logits and labels kept on the device, then
+    ``ptsfit.fit_pts(logits, labels, **fit_args)``.  Returns what that returns: the fitted parameter block."""
+    from .ptsfit import fit_pts as fit
+    logits, labels = [], []
+    for image, label in device_batches(loader, device):
+        logits.append(_call(infer, image)[0].float())
+        labels.append(label)
+    if not logits:
+        raise ValueError("empty loader")
+    return fit(torch.cat(logits), torch.cat(labels), **fit_args)
+
+
 def text_feature_dict(base_zs: Dict[str, np.ndarray], current_text_features_zs, base_tuned: Dict[str, np.ndarray],
                       current_text_features_tuned) -> Dict[str, np.ndarray]:
     """get_text_features (base_learner.py:241-300): the four matrices DAC.fit consumes.  ``base_zs`` / ``base_tuned`` are

@@ -24,3 +24,4 @@ from .proda import CustomCLIP as ProDACLIP  # noqa: F401
 from .clip_adapter import CustomCLIP as CLIPAdapterCLIP  # noqa: F401
 from .taskres import CustomCLIP as TaskResCLIP  # noqa: F401
 from .tempscaling import CustomCLIPCalibration, ScaleLearner  # noqa: F401
+from .pts import CustomCLIPParameterizedCalibration  # noqa: F401

@@ -420,6 +420,53 @@ int clipmi_tempscale_fit(const float* cosine, int64_t ld, const int64_t* labels,
                          int drop_last, const float* lr, float momentum, float dampening, float weight_decay, int nesterov, float* state,
                          float* losses, void* workspace, size_t workspace_bytes, clipmi_stream_t stream);
 
+/* Parameterized temperature scaling (PTS; Tomani, Cremers, Buettner, ECCV 2022; the reference's CALIBRATION.SCALING.MODE
+ * 'ParameterizedTempScaling' with its P_TS block, for which it ships no trainer): a small MLP on the K largest logits of a row gives
+ * that row's temperature.  For a row z of C logits, fp32 throughout:
+ *   f = the K largest values of z, descending;  h_0 = f;  h_l = relu(W_l h_(l-1) + b_l) for l = 1 .. n_layers, each n_nodes wide;
+ *   t = w_out . h_last + b_out;  T = clamp(|t|, 1e-12, 1e12);  calibrated logits z / T;  p = softmax(z / T);
+ *   loss = (1 / C) sum_c (p_c - [c == y])^2, and a batch's loss is the mean over its rows.
+ * The gradient is torch autograd's on logits / t.abs().clamp(1e-12, 1e12): abs has derivative 0 at 0, clamp passes the gradient on the
+ * closed interval, relu has derivative 0 at 0.  params fp32 [P] = [W_1 | b_1 | ... | W_n | b_n | w_out | b_out], every W row-major
+ * [out, in] (nn.Linear's layout), P = clipmi_pts_param_count(n_layers, n_nodes, K) (0 outside the limits).  Limits: 0 <= n_layers <= 4,
+ * 1 <= n_nodes <= 32, 1 <= K <= 32, C >= K, C >= 2.  logits fp32 [N, C] with row stride ld >= C (elements), labels int64 [N].  One wave
+ * per row; a batch's sums are formed in float64 in a fixed order, without atomics: the same inputs give the same bits.  These exports
+ * are additive: the ABI version does not change with them.
+ *
+ * clipmi_pts_topk: out fp32 [N, K] = the K largest values of every row, descending (the values torch.sort(descending=True) puts first).
+ * -inf is an ordinary value; a row that holds a NaN gives K NaNs.
+ *
+ * clipmi_pts_apply: out[i, c] = logits[i, c] / T_i (IEEE division) in one launch, out with row stride ld_out >= C; out may be logits
+ * itself.  temperature fp32 [N] receives T, or NULL.
+ *
+ * clipmi_pts_eval: one batch at params, nothing updated: batch_out fp32 [1 + P] (device) = {mean loss, the mean gradient of every
+ * parameter} over the samples order[0 .. rows) (int32, device), or first .. first + rows - 1 when order is NULL.  features fp32 [N, K]
+ * is clipmi_pts_topk's output for logits.  workspace (device) of rows * (2 + 2 n_layers n_nodes) floats.
+ *
+ * clipmi_pts_fit: the whole run, epochs * ceil(N / batch) steps (floor with drop_last), enqueued on `stream` without a host
+ * synchronisation: the features once, then two launches per step.  Step k of epoch e takes the samples order[e * N + k * batch ..]
+ * (order int32 [epochs, N], device; NULL = 0 .. N-1 in every epoch); the last batch of an epoch may be short.  state (device) fp32
+ * words [3 P + 2] = {params P | buffer P | buffer P | steps taken int32 | loss of the last batch}: SGD's momentum buffer is the first
+ * buffer, Adam's exp_avg and exp_avg_sq are the two; the caller sets {init, 0 ...} for a fresh fit and may hand a returned state back
+ * to continue.  optimizer 0: torch.optim.SGD's rule as clipmi_tempscale_fit states it (the buffer is initialised on the state's first
+ * step); 1: torch.optim.Adam's (no amsgrad) with the bias corrections of step `steps taken + 1`, formed in float64.  Each step uses
+ * lr[step] (fp32 [steps], device).  losses fp32 [steps] (device) receives every step's batch loss, or NULL.  workspace (device) of
+ * N * K + min(batch, N) * (2 + 2 n_layers n_nodes) floats.  A label outside [0, C) or a sample index outside [0, N) is never
+ * dereferenced; it makes the step's loss and the parameters NaN.  epochs == 0: CLIPMI_OK, nothing is launched.
+ * CLIPMI_ERR_ARG: a null pointer, epochs < 0, an unknown optimizer, its hyper-parameters outside torch's ranges.  CLIPMI_ERR_SHAPE: the
+ * limits above, ld < C, rows < 1, batch < 1, N < 0 (N < 1 for the fit; topk and apply accept N == 0).  CLIPMI_ERR_WORKSPACE: too small. */
+int clipmi_pts_param_count(int n_layers, int n_nodes, int K);
+int clipmi_pts_topk(const float* logits, int64_t ld, int N, int C, int K, float* out, clipmi_stream_t stream);
+int clipmi_pts_apply(const float* logits, int64_t ld, int N, int C, const float* params, int n_layers, int n_nodes, int K, float* out,
+                     int64_t ld_out, float* temperature, clipmi_stream_t stream);
+int clipmi_pts_eval(const float* features, const float* logits, int64_t ld, const int64_t* labels, const int32_t* order, int first, int rows,
+                    int N, int C, const float* params, int n_layers, int n_nodes, int K, float* batch_out, float* workspace,
+                    size_t workspace_floats, clipmi_stream_t stream);
+int clipmi_pts_fit(const float* logits, int64_t ld, const int64_t* labels, const int32_t* order, int N, int C, int n_layers, int n_nodes, int K,
+                   int batch, int epochs, int drop_last, const float* lr, int optimizer, float momentum, float dampening, float weight_decay,
+                   int nesterov, double beta1, double beta2, double eps, float* state, float* losses, float* workspace, size_t workspace_floats,
+                   clipmi_stream_t stream);
+
 /* CLIP-Adapter's bottleneck trained on the device (trainers/classification/clip_adapter.py:138-187: both towers frozen, the text
  * features constant under the shipped config): forward, backward and torch.optim.SGD's step on the two bias-free matrices, all fp32
  * with fp32 master weights.  feats fp32 [n, E] raw (un-normalised) image features with row stride ld >= E (elements), labels int64
