@@ -160,6 +160,9 @@ _SIGNATURES = {
     "clipmi_logits_per_image": (_i, [_vp, _vp, C.c_float, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "clipmi_softmax_rows": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     "clipmi_knn_dists": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "clipmi_nearest_rows": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "clipmi_nearest_rows_workspace": (_sz, [_i, _i, _i, _i]),
+    "clipmi_nearest_rows_splits": (_i, [_i, _i]),
     "clipmi_ece_accumulate": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp]),
     "clipmi_procal_kde": (_i, [C.POINTER(ProcalModel), _vp, _vp, _vp, _i, _vp]),
     "clipmi_procal_rows": (_i, [C.POINTER(ProcalModel), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),

@@ -463,6 +463,26 @@ def order_stats(x: torch.Tensor, ranks) -> Tuple[torch.Tensor, torch.Tensor]:
     return out, nans
 
 
+def nearest_rows(queries: torch.Tensor, refs: torch.Tensor, k: int, splits: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The ``k`` rows of ``refs`` nearest to every row of ``queries`` in L2 distance (include/clipmi.h, clipmi_nearest_rows): what
+    ``torch.cdist(queries, refs).argsort(1)[:, :k]`` selects, without the [Nq, Nr] matrix.  fp32 contiguous device tensors [Nq, E] and
+    [Nr, E]; half inputs are refused, the caller converts.  Returns (dist fp32 [Nq, k], idx int32 [Nq, k]), ascending in (distance, index).
+    ``splits``: slices of the reference rows that share the work of one query block, 0 = the library chooses; the result is the same
+    bits for every value."""
+    queries = _dev(queries, "queries", (torch.float32,))
+    refs = _dev(refs, "refs", (torch.float32,))
+    if queries.dim() != 2 or refs.dim() != 2 or queries.shape[1] != refs.shape[1]:
+        raise ValueError(f"nearest_rows: queries {tuple(queries.shape)} and refs {tuple(refs.shape)} must be [Nq, E] and [Nr, E]")
+    nq, e = queries.shape
+    nr, k, splits = refs.shape[0], int(k), int(splits)
+    dist = torch.empty(nq, k, dtype=torch.float32, device=queries.device)
+    idx = torch.empty(nq, k, dtype=torch.int32, device=queries.device)
+    ws = torch.empty(lib.clipmi_nearest_rows_workspace(nq, nr, k, splits), dtype=torch.uint8, device=queries.device)
+    check(lib.clipmi_nearest_rows(queries.data_ptr(), refs.data_ptr(), dist.data_ptr(), idx.data_ptr(), nq, nr, e, k, splits,
+                                  ws.data_ptr(), ws.numel(), _stream()), "clipmi_nearest_rows")
+    return dist, idx
+
+
 def _edges(edges, name: str, device) -> Tuple[Optional[torch.Tensor], Optional[int], int]:
     """Host float64 edges (numpy / list) -> device float64; a device float64 tensor is taken as it is.  (tensor, pointer, count)."""
     if edges is None:

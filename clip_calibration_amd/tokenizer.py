@@ -138,6 +138,11 @@ class ClipTokenizer:
         text = text.replace(SOT_TEXT, "").replace(EOT_TEXT, "")
         return bytearray(self._unalpha[c] for c in text).decode("utf-8", errors="replace").replace("</w>", " ")
 
+    def symbol(self, i: int) -> str:
+        """The raw vocabulary symbol of id ``i``, e.g. ``photo</w>`` -- the reference's ``tokenizer.decoder[i]``
+        (interpret_prompts/interpret_prompt.py:73); ``<i>`` for an id this table does not know (a sparse merge table)."""
+        return self._sym.get(int(i), f"<{int(i)}>")
+
     # ---- clip.tokenize ----------------------------------------------------------------------------------------
     def tokenize(self, texts: Union[str, Sequence[str]], context_length: int = 77, truncate: bool = False) -> torch.LongTensor:
         """[SOT] + bpe(text) + [EOT], zero padded to context_length (clip/clip.py:188-224); argmax of a row is its EOT."""

@@ -308,6 +308,23 @@ int clipmi_ece_accumulate(const float* conf, const int32_t* pred, const int64_t*
 int clipmi_knn_dists(const float* queries, const float* refs, float* out, int Nq, int Nr, int E, int K,
                      clipmi_stream_t stream);
 
+/* The nearest rows WITH their indices (interpret_prompts/interpret_prompt.py:66-76: torch.cdist + argsort of the whole matrix, for
+ * the nearest vocabulary words of a learned context): for every query row the K rows of refs at the smallest L2 distance, ascending
+ * in the total order (distance, index) -- ties go to the lower index.  queries [Nq, E], refs [Nr, E] fp32; out_dist fp32 [Nq, K] (the
+ * distance, not its square); out_idx int32 [Nq, K].  Distances are fp32 in difference form, sum_e (q_e - r_e)^2 with e ascending: a
+ * pair's distance does not depend on Nq or on `splits`.  A NaN distance counts as +inf: such rows come last, by index.
+ * The grid is (blocks of 16 queries) x (`splits` slices of the 64-row reference tiles); every workgroup writes its slice's K best
+ * pairs per query to the workspace (slices with fewer than K rows, or none, pad with (+inf, INT32_MAX)) and a second launch on the
+ * same stream merges them: the outputs are bit-identical for every `splits` >= 1.  splits = 0: the library chooses
+ * (clipmi_nearest_rows_splits: eight workgroups per CU, what the chip holds at once, where there are tiles for it; never more slices
+ * than tiles).
+ * 1 <= K <= min(32, Nr); E % 64 == 0; pointers 16-byte aligned; Nq == 0: CLIPMI_OK, nothing is launched.  Shapes are checked before
+ * pointers (CLIPMI_ERR_SHAPE, then CLIPMI_ERR_ARG, then CLIPMI_ERR_WORKSPACE), and all of it before anything touches a device. */
+int clipmi_nearest_rows(const float* queries, const float* refs, float* out_dist, int32_t* out_idx, int Nq, int Nr, int E, int K,
+                        int splits, void* workspace, size_t workspace_bytes, clipmi_stream_t stream);
+size_t clipmi_nearest_rows_workspace(int Nq, int Nr, int K, int splits);   /* bytes; 0 on bad arguments */
+int clipmi_nearest_rows_splits(int Nq, int Nr);                            /* the slice count that splits = 0 picks */
+
 /* ProCal, the proximity-informed density-ratio calibrator (trainers/calibration/density_ratio_calibration.py:28-117, used by
  * vl_calibrator.py:112-121 on base_calibration_mode "scaling_based" with procal_flag).  The fit stays on the host (float64); the
  * device evaluates, per test row with confidence c and proximity p,
