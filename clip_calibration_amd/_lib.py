@@ -192,6 +192,8 @@ _SIGNATURES = {
     "clipmi_quickgelu_backward": (_i, [_vp, _vp, _vp, _i64, _vp]),
     "clipmi_attention_backward": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     "clipmi_attention_backward_full": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
+    "clipmi_attention_backward_long_bytes": (_sz, [_i, _i, _i]),
+    "clipmi_attention_backward_long": (_i, [_vp, _vp, _vp, _vp, _sz, _i, _i, _i, _vp]),
     "clipmi_coop_head_workspace_bytes": (_sz, [_i, _i, _i]),
     "clipmi_coop_head": (_i, [_vp, _i64, _vp, _vp, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
     "clipmi_ctx_step": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _i, _f, _f, _f, _i, _vp]),

@@ -1751,7 +1751,259 @@ __global__ __launch_bounds__(THREADS) void attention_backward_full_kernel(const 
 }
 
 DeviceOnce g_abf_once;
+
+// ------------------------------------------------------------------------------------------- attention backward without a mask, L <= 640
+// ViT-L/14's lengths (257 / 577 tokens + prompt rows): the sibling above with nothing of a whole item resident.  Two launches of four-wave
+// workgroups, each over (item, block of ABL_BLOCK = 64 rows); the other side streams through LDS in blocks of 64 rows as [64][72] fp16
+// (rows >= L zero).  Fragments, layouts, the frag_pair operand and the rounding points are the sibling's.
+//   launch 1, query-owned  a wave holds 16 query rows' Q and dO fragments in registers; K and V stream.  Sweep 1: S^T and dP^T per key
+//            block, the running maximum m, sum exp(S / 8 - m) and sum exp(S / 8 - m) dP, both rescaled by exp(m_old - m_new) when the
+//            maximum moves; the row's m, 1 / sum and rowsum(dP o P) go to the workspace ([item][3][L] fp32).  Sweep 2: S^T and dP^T again,
+//            P and dS^T in the accumulator layout, dQ^T += K^T dS^T in registers, / 8 at the store.
+//   launch 2, key-owned    a wave holds 16 keys' K and V fragments; Q, dO and the three statistics stream.  P and dS by launch 1's
+//            expressions, dV += P^T dO and dK += dS^T Q in registers, dK / 8 at the store.
+// A workgroup owns every row it writes and no float atomics: the same inputs give the same bits.
+constexpr int ABL_BLOCK = 64, ABL_BT = ABL_BLOCK / 16;
+
+// rows [r0, r0 + 64) of two row-major operands (64 columns each, at g0 / g1 with leading dimensions ld0 / ld1) into LDS; rows >= L zero
+__device__ __forceinline__ void abl_load_block(half_t* s0, half_t* s1, const half_t* g0, int64_t ld0, const half_t* g1, int64_t ld1, int r0, int L, int t) {
+  const f16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
+  for (int i = t; i < ABL_BLOCK * 8; i += THREADS) {
+    const int r = i >> 3, c = (i & 7) * 8;
+    f16x8 a = zero8, b = zero8;
+    if (r0 + r < L) {
+      a = *reinterpret_cast<const f16x8*>(g0 + (int64_t)(r0 + r) * ld0 + c);
+      b = *reinterpret_cast<const f16x8*>(g1 + (int64_t)(r0 + r) * ld1 + c);
+    }
+    *reinterpret_cast<f16x8*>(s0 + r * ABF_LDH + c) = a;
+    *reinterpret_cast<f16x8*>(s1 + r * ABF_LDH + c) = b;
+  }
+}
+
+// S^T = K Q^T and dP^T = V dO^T of one key block against a wave's 16 queries: [key tile][key 4 lq + i] of query column lr
+__device__ __forceinline__ void abl_scores_t(const half_t* sk, const half_t* sv, const f16x8 (&qb)[2], const f16x8 (&ob)[2], int lr, int lq,
+                                             f32x4 (&s)[ABL_BT], f32x4 (&dp)[ABL_BT]) {
+#pragma unroll
+  for (int kt = 0; kt < ABL_BT; ++kt) {
+    const half_t* kr = sk + (kt * 16 + lr) * ABF_LDH + lq * 8;
+    const half_t* vr = sv + (kt * 16 + lr) * ABF_LDH + lq * 8;
+    s[kt] = mma0(frag_row(kr), qb[0]);
+    s[kt] = mma(frag_row(kr + 32), qb[1], s[kt]);
+    dp[kt] = mma0(frag_row(vr), ob[0]);
+    dp[kt] = mma(frag_row(vr + 32), ob[1], dp[kt]);
+    AB_MFMA_TO_VALU_FENCE(s[kt]);
+    AB_MFMA_TO_VALU_FENCE(dp[kt]);
+  }
+}
+
+__global__ __launch_bounds__(THREADS) void attention_backward_long_dq_kernel(const half_t* __restrict__ qkv, const half_t* __restrict__ d_out,
+                                                                             half_t* __restrict__ dqkv, float* __restrict__ stats, int L, int H, int NB) {
+  __shared__ __attribute__((aligned(16))) half_t sk[ABL_BLOCK * ABF_LDH];
+  __shared__ __attribute__((aligned(16))) half_t sv[ABL_BLOCK * ABF_LDH];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, lr = lane & 15, lq = lane >> 4;
+  const int item = blockIdx.x / NB, q0 = (blockIdx.x % NB) * ABL_BLOCK;
+  const int n = item / H, h = item % H, D = 64 * H;
+  const int64_t row0 = (int64_t)n * L;
+  const half_t* gk = qkv + row0 * 3 * D + D + h * 64;
+  const half_t* gv = gk + D;
+  const int q = q0 + wave * 16 + lr;   // this lane's query (column lr of every product below)
+  const f16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
+  f16x8 qb[2] = {zero8, zero8}, ob[2] = {zero8, zero8};
+  if (q < L) {
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      qb[ks] = *reinterpret_cast<const f16x8*>(qkv + (row0 + q) * 3 * D + h * 64 + ks * 32 + lq * 8);
+      ob[ks] = *reinterpret_cast<const f16x8*>(d_out + (row0 + q) * D + h * 64 + ks * 32 + lq * 8);
+    }
+  }
+  f32x4 s[ABL_BT], dp[ABL_BT];
+
+  // ---- sweep 1: the statistics of 16 query rows
+  float m = -INFINITY, sum = 0.f, rse = 0.f;   // sum and rse: this lane's keys only, on the maximum m that the four lanes of the column share
+  for (int k0 = 0; k0 < L; k0 += ABL_BLOCK) {
+    __syncthreads();
+    abl_load_block(sk, sv, gk, 3 * D, gv, 3 * D, k0, L, t);
+    __syncthreads();
+    abl_scores_t(sk, sv, qb, ob, lr, lq, s, dp);
+    float bm = -INFINITY;
+#pragma unroll
+    for (int kt = 0; kt < ABL_BT; ++kt)
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        if (k0 + kt * 16 + 4 * lq + i < L) bm = fmaxf(bm, s[kt][i] * 0.125f);
+    const float mn = fmaxf(m, col4_max(bm));   // key k0 is live: finite
+    const float sc = __expf(m - mn);           // 0 at the first block
+    sum *= sc;
+    rse *= sc;
+#pragma unroll
+    for (int kt = 0; kt < ABL_BT; ++kt)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const float e = k0 + kt * 16 + 4 * lq + i < L ? __expf(s[kt][i] * 0.125f - mn) : 0.f;
+        sum += e;
+        rse = fmaf(e, dp[kt][i], rse);
+      }
+    m = mn;
+  }
+  const float inv = 1.f / col4_sum(sum);
+  const float rs = col4_sum(rse) * inv;
+  if (lq == 0 && q < L) {
+    float* st = stats + (int64_t)item * 3 * L + q;
+    st[0] = m;
+    st[L] = inv;
+    st[2 * (int64_t)L] = rs;
+  }
+
+  // ---- sweep 2: dQ
+  f32x4 dq[4];
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) dq[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int k0 = 0; k0 < L; k0 += ABL_BLOCK) {
+    __syncthreads();
+    abl_load_block(sk, sv, gk, 3 * D, gv, 3 * D, k0, L, t);
+    __syncthreads();
+    abl_scores_t(sk, sv, qb, ob, lr, lq, s, dp);
+    f16x8 b[ABL_BT / 2];   // B[k][col q = lr] = dS[q][key(k)]
+#pragma unroll
+    for (int u = 0; u < ABL_BT / 2; ++u)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int kt = 2 * u + (j >> 2), i = j & 3;
+        float ds = 0.f;
+        if (k0 + kt * 16 + 4 * lq + i < L && q < L) {
+          const float p = __expf(s[kt][i] * 0.125f - m) * inv;
+          ds = p * (dp[kt][i] - rs);
+        }
+        b[u][j] = (half_t)ds;
+      }
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt)
+#pragma unroll
+      for (int u = 0; u < ABL_BT / 2; ++u) {
+        const f16x8 a = frag_pair(sk, 2 * u, lq, dt * 16 + lr);   // A[row d = lr][k] = K[key(k)][d]
+        dq[dt] = (k0 == 0 && u == 0) ? mma0(a, b[u]) : mma(a, b[u], dq[dt]);
+      }
+  }
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) {
+    AB_MFMA_TO_VALU_FENCE(dq[dt]);
+    if (q < L)   // dQ^T[d = dt * 16 + 4 lq + i][q]
+      *reinterpret_cast<f16x4*>(dqkv + (row0 + q) * 3 * D + h * 64 + dt * 16 + 4 * lq) =
+          f16x4{(half_t)(dq[dt][0] * 0.125f), (half_t)(dq[dt][1] * 0.125f), (half_t)(dq[dt][2] * 0.125f), (half_t)(dq[dt][3] * 0.125f)};
+  }
+}
+
+__global__ __launch_bounds__(THREADS) void attention_backward_long_dkv_kernel(const half_t* __restrict__ qkv, const half_t* __restrict__ d_out,
+                                                                              half_t* __restrict__ dqkv, const float* __restrict__ stats, int L, int H, int NB) {
+  __shared__ __attribute__((aligned(16))) half_t sq[ABL_BLOCK * ABF_LDH];
+  __shared__ __attribute__((aligned(16))) half_t sdo[ABL_BLOCK * ABF_LDH];
+  __shared__ float sst[3 * ABL_BLOCK];   // the block's maximum | 1 / sum | rowsum
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, lr = lane & 15, lq = lane >> 4;
+  const int item = blockIdx.x / NB, key0 = (blockIdx.x % NB) * ABL_BLOCK + wave * 16;
+  const int n = item / H, h = item % H, D = 64 * H;
+  const int64_t row0 = (int64_t)n * L;
+  const half_t* gq = qkv + row0 * 3 * D + h * 64;
+  const half_t* go = d_out + row0 * D + h * 64;
+  const bool key_live = key0 + lr < L;
+  const f16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
+  f16x8 kb[2] = {zero8, zero8}, vb[2] = {zero8, zero8};
+  if (key_live) {
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      kb[ks] = *reinterpret_cast<const f16x8*>(gq + (int64_t)(key0 + lr) * 3 * D + D + ks * 32 + lq * 8);
+      vb[ks] = *reinterpret_cast<const f16x8*>(gq + (int64_t)(key0 + lr) * 3 * D + 2 * D + ks * 32 + lq * 8);
+    }
+  }
+  f32x4 dk[4], dv[4];
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) {
+    dk[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    dv[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+  for (int q0 = 0; q0 < L; q0 += ABL_BLOCK) {
+    __syncthreads();
+    abl_load_block(sq, sdo, gq, 3 * D, go, D, q0, L, t);
+    if (t < 3 * ABL_BLOCK) {
+      const int w = t / ABL_BLOCK, r = t % ABL_BLOCK;
+      sst[t] = q0 + r < L ? stats[((int64_t)item * 3 + w) * L + q0 + r] : 0.f;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < ABL_BT / 2; ++u) {
+      f16x8 pa, dsa;   // A[row key = lr][k] = P[query(k)][key], dS[query(k)][key]
+#pragma unroll
+      for (int hf = 0; hf < 2; ++hf) {
+        const int qt = 2 * u + hf;
+        const half_t* qr = sq + (qt * 16 + lr) * ABF_LDH + lq * 8;
+        const half_t* orow = sdo + (qt * 16 + lr) * ABF_LDH + lq * 8;
+        f32x4 s = mma0(frag_row(qr), kb[0]);
+        s = mma(frag_row(qr + 32), kb[1], s);
+        f32x4 dp = mma0(frag_row(orow), vb[0]);
+        dp = mma(frag_row(orow + 32), vb[1], dp);
+        AB_MFMA_TO_VALU_FENCE(s);
+        AB_MFMA_TO_VALU_FENCE(dp);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int ql = qt * 16 + 4 * lq + i;
+          float p = 0.f, ds = 0.f;
+          if (key_live && q0 + ql < L) {
+            p = __expf(s[i] * 0.125f - sst[ql]) * sst[ABL_BLOCK + ql];
+            ds = p * (dp[i] - sst[2 * ABL_BLOCK + ql]);
+          }
+          pa[hf * 4 + i] = (half_t)p;
+          dsa[hf * 4 + i] = (half_t)ds;
+        }
+      }
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt) {
+        const f16x8 bo = frag_pair(sdo, 2 * u, lq, dt * 16 + lr);   // B[k][col d = lr] = dO[query(k)][d]
+        const f16x8 bq = frag_pair(sq, 2 * u, lq, dt * 16 + lr);
+        dv[dt] = (q0 == 0 && u == 0) ? mma0(pa, bo) : mma(pa, bo, dv[dt]);
+        dk[dt] = (q0 == 0 && u == 0) ? mma0(dsa, bq) : mma(dsa, bq, dk[dt]);
+      }
+    }
+  }
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) {
+    AB_MFMA_TO_VALU_FENCE(dk[dt]);
+    AB_MFMA_TO_VALU_FENCE(dv[dt]);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int key = key0 + 4 * lq + i;
+      if (key < L) {
+        half_t* o = dqkv + (row0 + key) * 3 * D + h * 64 + dt * 16 + lr;
+        o[D] = (half_t)(dk[dt][i] * 0.125f);
+        o[2 * D] = (half_t)dv[dt][i];
+      }
+    }
+  }
+}
 }  // namespace
+
+size_t attention_backward_long_bytes(int N, int L, int H) {
+  if (N < 1 || H < 1 || L < 1 || L > ABL_MAX_L || (int64_t)N * H >= (1ll << 31) || (int64_t)N * L >= (1ll << 31)) return 0;
+  return (size_t)12 * N * H * L;   // three fp32 statistics per (item, query row)
+}
+
+int launch_attention_backward_long(const half_t* qkv, const half_t* d_out, half_t* dqkv, void* ws, size_t ws_bytes, int N, int L, int H, hipStream_t s) {
+  CLIPMI_REQUIRE(N >= 0 && H >= 1 && L >= 1, CLIPMI_ERR_SHAPE, "attention_backward_long: N=%d L=%d H=%d", N, L, H);
+  CLIPMI_REQUIRE(L <= ABL_MAX_L, CLIPMI_ERR_SHAPE, "attention_backward_long: L=%d (at most %d token rows)", L, ABL_MAX_L);
+  const int NB = (L + ABL_BLOCK - 1) / ABL_BLOCK;
+  CLIPMI_REQUIRE((int64_t)N * H < (1ll << 31) && (int64_t)N * L < (1ll << 31) && (int64_t)N * H * NB < (1ll << 31), CLIPMI_ERR_SHAPE,
+                 "attention_backward_long: too many items");
+  if (N == 0) return CLIPMI_OK;
+  CLIPMI_REQUIRE(qkv && d_out && dqkv && ws, CLIPMI_ERR_ARG, "attention_backward_long: null pointer");
+  CLIPMI_REQUIRE((uintptr_t)qkv % 16 == 0 && (uintptr_t)d_out % 16 == 0 && (uintptr_t)dqkv % 16 == 0 && (uintptr_t)ws % 16 == 0, CLIPMI_ERR_ARG,
+                 "attention_backward_long: pointers must be 16-byte aligned");
+  const size_t need = attention_backward_long_bytes(N, L, H);
+  CLIPMI_REQUIRE(ws_bytes >= need, CLIPMI_ERR_ARG, "attention_backward_long: workspace too small: %zu < %zu", ws_bytes, need);
+  float* stats = static_cast<float*>(ws);
+  const dim3 grid((unsigned)((int64_t)N * H * NB));
+  hipLaunchKernelGGL(attention_backward_long_dq_kernel, grid, dim3(THREADS), 0, s, qkv, d_out, dqkv, stats, L, H, NB);
+  if (int rc = check_launch("attention_backward_long_dq_kernel")) return rc;
+  hipLaunchKernelGGL(attention_backward_long_dkv_kernel, grid, dim3(THREADS), 0, s, qkv, d_out, dqkv, stats, L, H, NB);
+  return check_launch("attention_backward_long_dkv_kernel");
+}
 
 int launch_attention_backward_full(const half_t* qkv, const half_t* d_out, half_t* dqkv, int N, int L, int H, hipStream_t s) {
   CLIPMI_REQUIRE(N >= 0 && H >= 1 && L >= 1, CLIPMI_ERR_SHAPE, "attention_backward_full: N=%d L=%d H=%d", N, L, H);
@@ -1788,8 +2040,20 @@ int launch_attention_backward(const half_t* qkv, const half_t* d_out, half_t* dq
 int launch_attention_backward_full(const half_t* qkv, const half_t* d_out, half_t* dqkv, int N, int L, int H, hipStream_t s) {
   return ab::launch_attention_backward_full(qkv, d_out, dqkv, N, L, H, s);
 }
+size_t attention_backward_long_bytes(int N, int L, int H) { return ab::attention_backward_long_bytes(N, L, H); }
+int launch_attention_backward_long(const half_t* qkv, const half_t* d_out, half_t* dqkv, void* ws, size_t ws_bytes, int N, int L, int H, hipStream_t s) {
+  return ab::launch_attention_backward_long(qkv, d_out, dqkv, ws, ws_bytes, N, L, H, s);
+}
 
 }  // namespace clipmi
+
+extern "C" size_t clipmi_attention_backward_long_bytes(int N, int L, int H) { return clipmi::attention_backward_long_bytes(N, L, H); }
+
+extern "C" int clipmi_attention_backward_long(const void* qkv, const void* d_out, void* dqkv, void* workspace, size_t workspace_bytes, int N, int L, int H,
+                                              clipmi_stream_t stream) {
+  return clipmi::launch_attention_backward_long(static_cast<const clipmi::half_t*>(qkv), static_cast<const clipmi::half_t*>(d_out),
+                                                static_cast<clipmi::half_t*>(dqkv), workspace, workspace_bytes, N, L, H, (hipStream_t)stream);
+}
 
 extern "C" int clipmi_attention_backward_full(const void* qkv, const void* d_out, void* dqkv, int N, int L, int H, clipmi_stream_t stream) {
   return clipmi::launch_attention_backward_full(static_cast<const clipmi::half_t*>(qkv), static_cast<const clipmi::half_t*>(d_out),

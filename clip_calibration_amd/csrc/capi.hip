@@ -52,6 +52,7 @@ const OptionDesc kOptions[] = {
     {"attn_small", "CLIPMI_ATTN_SMALL", &Options::attn_small},
     {"tail_unfused", "CLIPMI_TAIL_UNFUSED", &Options::tail_unfused},
     {"vision_pass", "CLIPMI_VISION_PASS", &Options::vision_pass},
+    {"vision_train_long", "CLIPMI_VISION_TRAIN_LONG", &Options::vision_train_long},
 };
 
 // environment spelling -> option value: decimal integers, plus the historical letters of two switches

@@ -154,6 +154,8 @@ struct Options {
   std::atomic<int> attn_ring{1};       // CLIPMI_ATTN_RING, non-causal attention over more than 224 tokens (ViT-L/14): 1 (default) = attention_ring_kernel;
                                        // 0 = the round-1 streaming kernel
   std::atomic<int> tail_unfused{0};    // CLIPMI_TAIL_UNFUSED: 1 = the three-kernel logits tail (A/B aid)
+  std::atomic<int> vision_train_long{0};   // CLIPMI_VISION_TRAIN_LONG: 1 = the image tower's training path takes up to ABL_MAX_L token rows per image (the
+                                           // attention backward beyond ABF_MAX_L rows is attention_backward_long); 0 (default) = at most ABF_MAX_L
   std::atomic<int> vision_pass{50432 * 768};   // CLIPMI_VISION_PASS: stream elements (token rows x width) of one pass of the image tower; larger batches run
                                                // as consecutive passes (each an ordinary call on its images); 0 = never split
 };
@@ -240,6 +242,10 @@ int launch_attention_backward(const half_t* qkv, const half_t* d_out, half_t* dq
 // the same without a mask for L <= 224 token rows, the lengths of the one-key-block forward (the image tower's training path, vision_backward.hip)
 constexpr int ABF_MAX_L = 224;
 int launch_attention_backward_full(const half_t* qkv, const half_t* d_out, half_t* dqkv, int N, int L, int H, hipStream_t s);
+// the same for L <= 640 token rows (ViT-L/14's 257 / 577 tokens + prompt rows) in two launches, with 12 N H L bytes of statistics in a workspace
+constexpr int ABL_MAX_L = 640;
+size_t attention_backward_long_bytes(int N, int L, int H);   // 0 for a shape the launch refuses
+int launch_attention_backward_long(const half_t* qkv, const half_t* d_out, half_t* dqkv, void* ws, size_t ws_bytes, int N, int L, int H, hipStream_t s);
 // attention_cls.hip: the output row of token 0 of every sequence only (the image tower's last block: clip/model.py:419 reads nothing else)
 int launch_attention_cls(const half_t* qkv, half_t* out, int N, int L, int H, hipStream_t s);
 int launch_patchify(const void* image, int image_dtype, half_t* col, int B, int R, int P, int Kpad, hipStream_t s);

@@ -5,7 +5,8 @@
 //
 // The blocks are the text training tower's (text_backward.hip: LayerNorm, GEMM, attention, QuickGELU as separate launches on the fp32
 // residual stream; every Linear's backward is the forward's fp16 GEMM on a transposed copy of the weight) without a mask, and the
-// attention backward is attention.hip's attention_backward_full_kernel.  New here:
+// attention backward is attention.hip's attention_backward_full_kernel (beyond 224 rows per image, option vision_train_long: its two-launch
+// sibling attention_backward_long).  New here:
 //   splice_reduce_kernel   the gradient of one block's prompt rows: the batch's rows added in ascending order, the rows zeroed behind
 // Nothing below ln_pre is differentiated: patch rows, the class embedding and conv1 are frozen.
 // No float atomics and no workgroup waits for another: the same inputs give the same bits.
@@ -55,6 +56,8 @@ struct VisionWs {
   void* img16;     // patch_embed_scratch_bytes(B, R, fp32)
   half_t* p16;     // [layers, n_ctx, D]
   float* dsum;     // [n_ctx, D]
+  void* abl;       // attention_backward_long's statistics, beyond ABF_MAX_L rows per image only (shorter geometries keep their size)
+  size_t abl_bytes;
   size_t bytes;
 };
 VisionWs carve_vision_ws(void* p, const clipmi_model* m, int B, int n_ctx) {
@@ -68,6 +71,8 @@ VisionWs carve_vision_ws(void* p, const clipmi_model* m, int B, int n_ctx) {
   w.img16 = c.take<char>(patch_embed_scratch_bytes(B, m->g.image_resolution, CLIPMI_F32));
   w.p16 = c.take<half_t>((size_t)m->g.vision_layers * n_ctx * D * 2);
   w.dsum = c.take<float>((size_t)n_ctx * D * 4);
+  w.abl_bytes = L > ABF_MAX_L ? attention_backward_long_bytes(B, L, D / 64) : 0;
+  w.abl = w.abl_bytes ? c.take<char>(w.abl_bytes) : nullptr;
   w.bytes = c.off;
   return w;
 }
@@ -92,8 +97,8 @@ int check_vision_shape(const char* who, const clipmi_model* m, int B, int n_ctx)
   CLIPMI_REQUIRE(m, CLIPMI_ERR_ARG, "%s: null model", who);
   CLIPMI_REQUIRE(B >= 0 && n_ctx >= 1, CLIPMI_ERR_SHAPE, "%s: B=%d n_ctx=%d", who, B, n_ctx);
   const int L = m->tokens0() + n_ctx;
-  CLIPMI_REQUIRE(L <= ABF_MAX_L, CLIPMI_ERR_SHAPE, "%s: %d token rows per image (%d tokens + %d prompt rows; at most %d)", who, L, m->tokens0(), n_ctx,
-                 ABF_MAX_L);
+  const int max_l = options().vision_train_long.load(std::memory_order_relaxed) != 0 ? ABL_MAX_L : ABF_MAX_L;   // DESIGN.md "Long attention backward"
+  CLIPMI_REQUIRE(L <= max_l, CLIPMI_ERR_SHAPE, "%s: %d token rows per image (%d tokens + %d prompt rows; at most %d)", who, L, m->tokens0(), n_ctx, max_l);
   CLIPMI_REQUIRE((int64_t)B * L < (1ll << 31) / 4, CLIPMI_ERR_SHAPE, "%s: batch too large for one call", who);
   CLIPMI_REQUIRE(m->g.vision_width % 64 == 0 && m->g.embed_dim % 64 == 0, CLIPMI_ERR_SHAPE, "%s: vision width %d / embed dim %d", who, m->g.vision_width,
                  m->g.embed_dim);
@@ -196,7 +201,11 @@ int run_vision_backward(clipmi_model* m, const clipmi_vision_dgrad* wt, const fl
     if ((rc = launch_ln_backward(st.x(2 * i + 1), D, nullptr, b.ln2_g, w.dy, CLIPMI_F32, g, g16, M, D, 1e-5f, s))) return rc;
     if ((rc = launch_operand_stats(g16, M * D, stats, s))) return rc;
     if ((rc = tower_gemm(g16, D, t.w_out_t, D, nullptr, nullptr, w.att, D, CLIPMI_F16, M, D, D, CLIPMI_EPI_NONE, s))) return rc;                // g W_out
-    if ((rc = launch_attention_backward_full(st.qkv(i), w.att, w.qkv, B, L, H, s))) return rc;
+    if (L <= ABF_MAX_L) {
+      if ((rc = launch_attention_backward_full(st.qkv(i), w.att, w.qkv, B, L, H, s))) return rc;
+    } else if ((rc = launch_attention_backward_long(st.qkv(i), w.att, w.qkv, vw.abl, vw.abl_bytes, B, L, H, s))) {
+      return rc;
+    }
     if ((rc = launch_operand_stats(w.qkv, M * 3 * D, stats, s))) return rc;
     if ((rc = tower_gemm(w.qkv, 3 * D, t.w_qkv_t, 3 * D, nullptr, nullptr, w.dy, D, CLIPMI_F32, M, D, 3 * D, CLIPMI_EPI_NONE, s))) return rc;   // dqkv W_qkv
     if ((rc = launch_ln_backward(st.x(2 * i), D, nullptr, b.ln1_g, w.dy, CLIPMI_F32, g, g16, M, D, 1e-5f, s))) return rc;

@@ -30,8 +30,11 @@ The defaults -- SGD at 0.0035 with momentum 0.9 and weight decay 5e-4, 5 epochs 
 a cosine schedule, n_ctx 2, depth 9 -- restate configs/trainers/MaPLe/vit_b16_c2_ep5_batch4.yaml; the momentum and the weight decay
 are Dassl's public defaults and are UNVERIFIED here; each is an argument.
 
-Not covered (IVLP and PromptSRC train through ``promptsrcfit``): ``nn.DataParallel``, ViT-L lengths (more than 224 token rows
-per image), the ResNet towers, class-token positions other than ``end``.
+ViT-L lengths (more than 224 token rows per image; configs/trainers/MaPLe/vit_l14_c2_ep5_batch4.yaml): refused by default, taken up to
+640 rows with the library option ``vision_train_long`` at 1 (``vptfit.max_rows()``; DESIGN.md "Long attention backward").
+
+Not covered (IVLP and PromptSRC train through ``promptsrcfit``): ``nn.DataParallel``, the ResNet towers, class-token positions other
+than ``end``.
 """
 from __future__ import annotations
 
@@ -95,8 +98,7 @@ def _check_design(who: str, model, learner_params, class_token_position: str = "
     if want != n_ctx:
         raise ValueError(f"{who}: n_ctx={n_ctx} does not match the model's maple_length ({want})")
     tokens = (g.image_resolution // g.vision_patch_size) ** 2 + 1
-    if tokens + n_ctx > vptfit.MAX_ROWS:
-        raise ValueError(f"{who}: {tokens} tokens + {n_ctx} prompt rows = {tokens + n_ctx} rows per image; the backward takes at most {vptfit.MAX_ROWS}")
+    vptfit.check_rows(who, tokens, n_ctx)
     return n_ctx, depth
 
 

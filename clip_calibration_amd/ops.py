@@ -1082,6 +1082,32 @@ def attention_backward(qkv: torch.Tensor, d_out: torch.Tensor, n_seq: int, n_hea
     return out
 
 
+def attention_backward_long(qkv: torch.Tensor, d_out: torch.Tensor, n_seq: int, n_head: int, out: Optional[torch.Tensor] = None,
+                            workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The backward of the ``attention`` WITHOUT a mask for up to 640 token rows per sequence (ViT-L/14's lengths with prompt rows;
+    clipmi_attention_backward_long): operands and result as ``attention_backward``.  ``workspace``: a contiguous uint8 tensor on the GPU of
+    at least ``clipmi_attention_backward_long_bytes(N, L, H)`` = 12 N H L bytes, allocated here when not given."""
+    qkv, d_out = _dev(qkv, "qkv", (torch.float16,)), _dev(d_out, "d_out", (torch.float16,))
+    M, D3 = qkv.shape
+    if n_seq < 0 or n_head < 1 or D3 != 3 * 64 * n_head or (n_seq and M % n_seq) or d_out.shape != (M, 64 * n_head):
+        raise ValueError(f"attention_backward_long: qkv {tuple(qkv.shape)} / d_out {tuple(d_out.shape)} do not fit {n_seq} sequences of {n_head} heads")
+    if out is None:
+        out = torch.empty_like(qkv)
+    else:
+        _in_place(out, torch.float16, "attention_backward_long: out must be a contiguous fp16 tensor on the GPU")
+        if out.numel() < qkv.numel():
+            raise ValueError("attention_backward_long: out is too small")
+    L = M // n_seq if n_seq else 1
+    need = lib.clipmi_attention_backward_long_bytes(n_seq, L, n_head)
+    if workspace is None:
+        workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=qkv.device)
+    else:
+        _in_place(workspace, torch.uint8, "attention_backward_long: workspace must be a contiguous uint8 tensor on the GPU")
+    check(lib.clipmi_attention_backward_long(qkv.data_ptr(), d_out.data_ptr(), out.data_ptr(), workspace.data_ptr(), workspace.numel(), n_seq, L, n_head,
+                                             _stream()), "clipmi_attention_backward_long")
+    return out
+
+
 def _head_inputs(who: str, features, labels, text):
     """(labels, text, B, E, C) of a loss head after the checks coop_head and prompt_head share."""
     if not isinstance(features, torch.Tensor) or features.dim() != 2 or features.stride(1) != 1:

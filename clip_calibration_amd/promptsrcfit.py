@@ -35,8 +35,10 @@ backs off and grows again; ``end_epoch`` aggregates whatever the block holds.  N
 ``PromptSRCFitState.scaler_state()`` does, once.  DESIGN.md "Dynamic loss scale for the block fits"; the reference's ``autocast`` casts
 differ from this path's fixed fp16 operand points (unverified).
 
-Not covered: ``nn.DataParallel``, ViT-L lengths (more than 224 token rows per image), the ResNet towers,
-class-token positions other than ``end``.
+ViT-L lengths (more than 224 token rows per image; configs/trainers/PromptSRC/vit_l14_c4_ep50_batch4.yaml): refused by default, taken
+up to 640 rows with the library option ``vision_train_long`` at 1 (``vptfit.max_rows()``; DESIGN.md "Long attention backward").
+
+Not covered: ``nn.DataParallel``, the ResNet towers, class-token positions other than ``end``.
 """
 from __future__ import annotations
 
@@ -130,8 +132,7 @@ def _check_design(who: str, model, params, class_token_position: str = "end"):
     if nv != int(dd.get("vision_ctx", nv)):
         raise ValueError(f"{who}: visual.VPT has {nv} rows but the model's vision_ctx is {dd.get('vision_ctx')}")
     tokens = (g.image_resolution // g.vision_patch_size) ** 2 + 1
-    if tokens + nv > vptfit.MAX_ROWS:
-        raise ValueError(f"{who}: {tokens} tokens + {nv} prompt rows = {tokens + nv} rows per image; the backward takes at most {vptfit.MAX_ROWS}")
+    vptfit.check_rows(who, tokens, nv)
     return nt, dt, nv, dv
 
 

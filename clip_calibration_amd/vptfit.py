@@ -26,8 +26,15 @@ every step with one synchronisation at the end.  The image tower runs on every s
 The defaults -- SGD at 0.0025 with momentum 0.9 and weight decay 5e-4, 5 epochs, a constant warm-up epoch handing over to a cosine
 schedule -- restate the reference's VPT config and Dassl's public defaults and are UNVERIFIED here; each is an argument.
 
-Not covered (MaPLe trains through ``maplefit`` and PromptSRC / IVLP through ``promptsrcfit``, on this tower): ViT-L lengths (more
-than 224 token rows per image), ``nn.DataParallel``, the ResNet towers.
+ViT-L lengths: by default the backward takes at most 224 token rows per image (tokens + prompt rows).  With the library option
+``vision_train_long`` at 1 (``_lib.set_option``, CLIPMI_VISION_TRAIN_LONG; opt-in until measured on real checkpoints) it takes 640 --
+ViT-L/14's 257 and 577 tokens with their prompt rows -- through ``clipmi_attention_backward_long``; ``max_rows()`` is the limit in
+force, for ``maplefit`` and ``promptsrcfit`` as well, and ``stash_bytes(model, batch, n_ctx)`` the workspace and stash a batch needs
+(DESIGN.md "Long attention backward").  The training forward's patch embedding serves patches of 8, 16 and 32 pixels: a tower with
+patches of 14 is still refused, by the library and by name.
+
+Not covered (MaPLe trains through ``maplefit`` and PromptSRC / IVLP through ``promptsrcfit``, on this tower): ``nn.DataParallel``, the
+ResNet towers.
 """
 from __future__ import annotations
 
@@ -47,7 +54,30 @@ from .fitloop import _need_gpu
 # (profiles/vptfit_parity.txt, "grad_scale").  A model with much larger gradients overflows fp16 at this scale -- the prompts then turn
 # NaN, they do not go wrong silently; pass a smaller power of two.
 DEFAULT_GRAD_SCALE = 4096.0
-MAX_ROWS = 224         # token rows per image that clipmi_vision_encoder_backward takes (the attention backward's limit)
+MAX_ROWS = 224         # token rows per image that clipmi_vision_encoder_backward takes by default (clipmi_attention_backward_full's limit)
+MAX_ROWS_LONG = 640    # with the library option vision_train_long = 1 (clipmi_attention_backward_long's limit)
+
+
+def max_rows() -> int:
+    """Token rows per image (tokens + prompt rows) that the image tower's training path takes now: 224, or 640 with the library option
+    ``vision_train_long`` (``_lib.set_option``, CLIPMI_VISION_TRAIN_LONG) at 1."""
+    return MAX_ROWS_LONG if _lib.get_option("vision_train_long") else MAX_ROWS
+
+
+def check_rows(who: str, tokens: int, n_ctx: int) -> None:
+    """The refusal ``vptfit``, ``maplefit`` and ``promptsrcfit`` share."""
+    limit = max_rows()
+    if tokens + n_ctx > limit:
+        raise ValueError(f"{who}: {tokens} tokens + {n_ctx} prompt rows = {tokens + n_ctx} rows per image; the backward takes at most {limit}")
+
+
+def stash_bytes(model, batch: int, n_ctx: int):
+    """``(workspace_bytes, stash_bytes)`` of the image tower's training path for ``batch`` images with ``n_ctx`` prompt rows
+    (clipmi_vision_train_bytes): the stash grows with rows x layers x width -- 49 fp32 streams, 24 qkv and 24 c_fc outputs at ViT-L/14."""
+    model._ensure_bound()
+    wsb, stb = C.c_size_t(0), C.c_size_t(0)
+    check(lib.clipmi_vision_train_bytes(model._handle, int(batch), int(n_ctx), C.byref(wsb), C.byref(stb)), "clipmi_vision_train_bytes")
+    return wsb.value, stb.value
 
 _DT = {torch.float16: _lib.F16, torch.float32: _lib.F32}
 
@@ -78,8 +108,7 @@ def _check_prompts(who: str, model, prompts: torch.Tensor):
     if not 1 <= depth <= g.vision_layers:
         raise ValueError(f"{who}: depth={depth} for {g.vision_layers} layers")
     tokens = (g.image_resolution // g.vision_patch_size) ** 2 + 1
-    if tokens + n_ctx > MAX_ROWS:
-        raise ValueError(f"{who}: {tokens} tokens + {n_ctx} prompt rows = {tokens + n_ctx} rows per image; the backward takes at most {MAX_ROWS}")
+    check_rows(who, tokens, n_ctx)
     return depth, n_ctx
 
 

@@ -90,6 +90,11 @@ const char* clipmi_last_error(void);
  *                                             call on its images: features equal to the one-pass result up to the library's usual batch
  *                                             dependence (tile and kernel choice follow the row count: <= 2e-4 on normalised features),
  *                                             +8..10 % images/s at 512-1024 images of ViT-B/16; 0 = never split
+ *   vision_train_long (CLIPMI_VISION_TRAIN_LONG)  0 (default) = the image tower's training path (clipmi_vision_train_bytes, clipmi_vision_encoder_train /
+ *                                             _backward, the VPT / MaPLe / PromptSRC one-call steps, clipmi_vision_val_chunk) takes at most 224 token
+ *                                             rows per image; 1 = up to 640 (the lengths of ViT-L/14 and ViT-L/14@336; the patch sizes stay 8, 16, 32): beyond 224 rows the attention backward is
+ *                                             clipmi_attention_backward_long and the workspace holds its statistics; at most 224 rows the same
+ *                                             kernels, sizes and bits either way.  Opt-in until measured
  * and the process-wide DEFAULTS of the three per-model settings (clipmi_model_set_option overrides them per handle):
  *   cls_only_last_block (CLIPMI_CLS_ONLY_LAST_BLOCK)  1 (default since round 6) = the image tower's LAST block computes what the class row
  *                    needs and nothing else -- K | V of every token, Q / attention / out-proj / ln_2 / c_fc / c_proj of the class rows, the only
@@ -832,6 +837,21 @@ int clipmi_attention_backward(const void* qkv, const void* d_out, void* dqkv, in
  *   never stored: a query-owned phase forms the row statistics (maximum, 1 / sum, rowsum(dP o P)) and dQ, a key-owned phase recomputes
  *   S and dP per pair of query tiles and accumulates dK and dV in registers.  No atomics, the same inputs give the same bits. */
 int clipmi_attention_backward_full(const void* qkv, const void* d_out, void* dqkv, int N, int L, int H, clipmi_stream_t stream);
+/* clipmi_attention_backward_long: the same backward without a mask for 1 <= L <= 640 token rows per sequence: ViT-L/14's 257 and 577
+ *   tokens with any prompt rows; short lengths are accepted too.  Operands, layouts and rounding points as clipmi_attention_backward_full
+ *   (fp16 operands; S, softmax, rowsum(dP o P) and dS in fp32; P and dS rounded to fp16 as matrix-core operands; fp32 accumulation; fp16
+ *   outputs).  Nothing of size L x L and no whole item is ever resident.  Two launches of four-wave workgroups over (sequence, head, block
+ *   of 64 rows) with the other side streaming through LDS in blocks of 64 rows: a query-owned launch forms each row's statistics (the
+ *   running maximum, rescaled sums, then 1 / sum and rowsum(dP o P)) into `workspace` and dQ in a second sweep over the keys; a key-owned
+ *   launch recomputes P and dS from the statistics and accumulates dK and dV in registers.  A workgroup owns every row it writes and there
+ *   are no float atomics: the same inputs give the same bits (not the sibling's: the softmax sums are taken in another order).
+ *   workspace: clipmi_attention_backward_long_bytes(N, L, H) = 12 N H L bytes (three fp32 per sequence, head and query row), 16-byte aligned;
+ *   the size query returns 0 for a shape the call refuses and for N == 0.
+ *   CLIPMI_ERR_SHAPE: L > 640, L < 1, H < 1, N < 0, N H, N L or the workgroup count beyond 31 bits.  CLIPMI_ERR_ARG: a null pointer, a
+ *   pointer that is not 16-byte aligned, workspace_bytes below the size query.  N == 0: CLIPMI_OK, pointers may be NULL. */
+size_t clipmi_attention_backward_long_bytes(int N, int L, int H);
+int clipmi_attention_backward_long(const void* qkv, const void* d_out, void* dqkv, void* workspace, size_t workspace_bytes, int N, int L, int H,
+                                   clipmi_stream_t stream);
 
 /* CoOp's loss head (coop.py:205-222 + F.cross_entropy): feats fp32 [B, E] raw image features with row stride ld >= E, labels int64 [B],
  * text fp32 [C, E] raw text features, scale = exp(logit_scale):
