@@ -49,11 +49,20 @@ int launch_splice_reduce(float* g, half_t* g16, float* out, int B, int L, int D,
 
 namespace {
 
-// behind the text tower's workspace: the fp32 gradient stream, the fp16 copy of an fp32 image batch, the prompts as fp16, slot 0's batch sum
+// The front end in front of ln_pre.  Patch rows that are whole 16-byte LDS slots (P in {8, 16, 32}) go through patch_embed.hip's im2col-free
+// loader; every other patch size that divides the resolution (ViT-L/14: kpad 640 against K = 588) takes the inference pass's route
+// (capi.hip, encode_image_pass): patchify into the [B G^2, kpad] fp16 matrix, then the dense GEMM whose epilogue adds the positional rows.
+bool loader_serves(const clipmi_model* m, int B) {
+  const int P = m->g.patch_size;
+  return patch_embed_fits(B, m->g.image_resolution, P, m->g.vision_width) && m->kpad() == 3 * P * P;
+}
+
+// behind the text tower's workspace: the fp32 gradient stream, the front end's slot (the fp16 copy of an fp32 image batch for the loader,
+// the im2col matrix for the patchify route, which reads the image itself), the prompts as fp16, slot 0's batch sum
 struct VisionWs {
   TrainWs t;
   float* g;        // [M, D]
-  void* img16;     // patch_embed_scratch_bytes(B, R, fp32)
+  void* img16;     // patch_embed_scratch_bytes(B, R, fp32), or col_bytes(B): [B G^2, kpad] fp16
   half_t* p16;     // [layers, n_ctx, D]
   float* dsum;     // [n_ctx, D]
   void* abl;       // attention_backward_long's statistics, beyond ABF_MAX_L rows per image only (shorter geometries keep their size)
@@ -68,7 +77,7 @@ VisionWs carve_vision_ws(void* p, const clipmi_model* m, int B, int n_ctx) {
   Carver c(p);
   c.off = w.t.bytes;
   w.g = c.take<float>((size_t)M * D * 4);
-  w.img16 = c.take<char>(patch_embed_scratch_bytes(B, m->g.image_resolution, CLIPMI_F32));
+  w.img16 = c.take<char>(loader_serves(m, B) ? patch_embed_scratch_bytes(B, m->g.image_resolution, CLIPMI_F32) : m->col_bytes(B));
   w.p16 = c.take<half_t>((size_t)m->g.vision_layers * n_ctx * D * 2);
   w.dsum = c.take<float>((size_t)n_ctx * D * 4);
   w.abl_bytes = L > ABF_MAX_L ? attention_backward_long_bytes(B, L, D / 64) : 0;
@@ -102,6 +111,9 @@ int check_vision_shape(const char* who, const clipmi_model* m, int B, int n_ctx)
   CLIPMI_REQUIRE((int64_t)B * L < (1ll << 31) / 4, CLIPMI_ERR_SHAPE, "%s: batch too large for one call", who);
   CLIPMI_REQUIRE(m->g.vision_width % 64 == 0 && m->g.embed_dim % 64 == 0, CLIPMI_ERR_SHAPE, "%s: vision width %d / embed dim %d", who, m->g.vision_width,
                  m->g.embed_dim);
+  // what launch_patchify and the patch GEMM ask of the geometry (kpad is a multiple of the GEMM's K-step by construction)
+  CLIPMI_REQUIRE(m->g.patch_size > 0 && m->g.image_resolution > 0 && m->g.image_resolution % m->g.patch_size == 0, CLIPMI_ERR_SHAPE,
+                 "%s: resolution %d is not a multiple of the patch size %d", who, m->g.image_resolution, m->g.patch_size);
   return CLIPMI_OK;
 }
 
@@ -112,8 +124,6 @@ int check_vision_train_call(const char* who, const clipmi_model* m, int B, int n
   if (int rc = check_vision_shape(who, m, B, n_ctx)) return rc;
   CLIPMI_REQUIRE(m->has_vision, CLIPMI_ERR_STATE, "%s: vision weights not bound (clipmi_set_vision_weights)", who);
   CLIPMI_REQUIRE(depth >= 1 && depth <= m->g.vision_layers, CLIPMI_ERR_SHAPE, "%s: depth=%d for %d layers", who, depth, m->g.vision_layers);
-  CLIPMI_REQUIRE(patch_embed_fits(B, m->g.image_resolution, m->g.patch_size, m->g.vision_width) && m->kpad() == 3 * m->g.patch_size * m->g.patch_size,
-                 CLIPMI_ERR_SHAPE, "%s: patch size %d is not served by the training forward (8, 16 or 32)", who, m->g.patch_size);
   if (B == 0) return CLIPMI_OK;
   CLIPMI_REQUIRE(ws && stash, CLIPMI_ERR_ARG, "%s: null workspace or stash", who);
   CLIPMI_REQUIRE((uintptr_t)ws % 256 == 0 && (uintptr_t)stash % 256 == 0, CLIPMI_ERR_ARG, "%s: workspace and stash must be 256-byte aligned", who);
@@ -147,11 +157,22 @@ int run_vision_train_forward(clipmi_model* m, const void* image, int image_dtype
   if ((rc = launch_cast_f32(prompts, vw.p16, CLIPMI_F16, depth * per, s))) return rc;
   if ((rc = launch_cast_f16(vw.p16, vs.prompts, CLIPMI_F32, depth * per, s))) return rc;
   float* x0 = w.dy;   // [M, D] embeddings before ln_pre
-  if ((rc = launch_patch_embed(image, image_dtype, vw.img16, (const half_t*)m->vw.conv_w, m->kpad(), nullptr, x0, CLIPMI_F32, B, g.image_resolution,
-                               g.patch_size, D, L, s)))
-    return rc;
-  if ((rc = launch_embed_ln(x0, CLIPMI_F32, 1, m->vw.class_embedding, m->vw.positional_embedding, vs.prompts, m->vw.ln_pre_g, m->vw.ln_pre_b, st.x(0), nullptr,
-                            nullptr, B, L, L0, D, 1e-5f, s)))
+  const bool loader = loader_serves(m, B);
+  if (loader) {
+    if ((rc = launch_patch_embed(image, image_dtype, vw.img16, (const half_t*)m->vw.conv_w, m->kpad(), nullptr, x0, CLIPMI_F32, B, g.image_resolution,
+                                 g.patch_size, D, L, s)))
+      return rc;
+  } else {
+    half_t* col = static_cast<half_t*>(vw.img16);   // [B G^2, kpad], the columns behind 3 P^2 zero
+    if ((rc = launch_patchify(image, image_dtype, col, B, g.image_resolution, g.patch_size, m->kpad(), s))) return rc;
+    GemmArgs a{};
+    a.A = col; a.lda = m->kpad(); a.W = (const half_t*)m->vw.conv_w; a.ldw = m->kpad(); a.out = x0; a.ldo = D; a.out_dtype = CLIPMI_F32;
+    a.M = B * (L0 - 1); a.N = D; a.K = m->kpad(); a.epilogue = EPI_PATCH_POS;
+    a.pos = m->vw.positional_embedding; a.patches = L0 - 1; a.tokens = L;   // this epilogue adds pos[1 + p] itself: ln_pre's pass must not
+    if ((rc = launch_gemm(a, s))) return rc;
+  }
+  if ((rc = launch_embed_ln(x0, CLIPMI_F32, loader ? 1 : 0, m->vw.class_embedding, m->vw.positional_embedding, vs.prompts, m->vw.ln_pre_g, m->vw.ln_pre_b,
+                            st.x(0), nullptr, nullptr, B, L, L0, D, 1e-5f, s)))
     return rc;
   if (hipMemsetAsync(st.idx() + B, 0, (size_t)B * 4, s) != hipSuccess) return check_launch("hipMemsetAsync");
   if ((rc = launch_eot_rows(st.idx() + B, st.idx(), B, L, s))) return rc;   // the class rows b L

@@ -31,7 +31,9 @@ a cosine schedule, n_ctx 2, depth 9 -- restate configs/trainers/MaPLe/vit_b16_c2
 are Dassl's public defaults and are UNVERIFIED here; each is an argument.
 
 ViT-L lengths (more than 224 token rows per image; configs/trainers/MaPLe/vit_l14_c2_ep5_batch4.yaml): refused by default, taken up to
-640 rows with the library option ``vision_train_long`` at 1 (``vptfit.max_rows()``; DESIGN.md "Long attention backward").
+640 rows with the library option ``vision_train_long`` at 1 (``vptfit.max_rows()``; DESIGN.md "Long attention backward").  ViT-L/14's
+patches of 14 pixels are served by the image tower's training forward (the patchify + GEMM route of ``vptfit``'s docstring), so with
+the option on that configuration's own towers train here.
 
 Not covered (IVLP and PromptSRC train through ``promptsrcfit``): ``nn.DataParallel``, the ResNet towers, class-token positions other
 than ``end``.

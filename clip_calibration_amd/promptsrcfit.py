@@ -36,7 +36,9 @@ backs off and grows again; ``end_epoch`` aggregates whatever the block holds.  N
 differ from this path's fixed fp16 operand points (unverified).
 
 ViT-L lengths (more than 224 token rows per image; configs/trainers/PromptSRC/vit_l14_c4_ep50_batch4.yaml): refused by default, taken
-up to 640 rows with the library option ``vision_train_long`` at 1 (``vptfit.max_rows()``; DESIGN.md "Long attention backward").
+up to 640 rows with the library option ``vision_train_long`` at 1 (``vptfit.max_rows()``; DESIGN.md "Long attention backward").  ViT-L/14's
+patches of 14 pixels are served by the image tower's training forward (the patchify + GEMM route of ``vptfit``'s docstring) as they are
+by the frozen plain tower's ``clipmi_encode_image``, so with the option on that configuration's own towers train here.
 
 Not covered: ``nn.DataParallel``, the ResNet towers, class-token positions other than ``end``.
 """

@@ -30,8 +30,10 @@ ViT-L lengths: by default the backward takes at most 224 token rows per image (t
 ``vision_train_long`` at 1 (``_lib.set_option``, CLIPMI_VISION_TRAIN_LONG; opt-in until measured on real checkpoints) it takes 640 --
 ViT-L/14's 257 and 577 tokens with their prompt rows -- through ``clipmi_attention_backward_long``; ``max_rows()`` is the limit in
 force, for ``maplefit`` and ``promptsrcfit`` as well, and ``stash_bytes(model, batch, n_ctx)`` the workspace and stash a batch needs
-(DESIGN.md "Long attention backward").  The training forward's patch embedding serves patches of 8, 16 and 32 pixels: a tower with
-patches of 14 is still refused, by the library and by name.
+(DESIGN.md "Long attention backward").  The training forward takes any patch size that divides the resolution: patches of 8, 16 and 32
+pixels through the im2col-free loader, every other size -- ViT-L/14's and ViT-L/14@336px's patches of 14 -- through the inference pass's
+patchify + GEMM route, whose im2col matrix takes the place of the fp16 image copy in the workspace (``stash_bytes`` reports it).  With
+the option on, real ViT-L/14 towers train here, in ``maplefit`` and in ``promptsrcfit``, monitored validation included.
 
 Not covered (MaPLe trains through ``maplefit`` and PromptSRC / IVLP through ``promptsrcfit``, on this tower): ``nn.DataParallel``, the
 ResNet towers.

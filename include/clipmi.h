@@ -966,7 +966,11 @@ int clipmi_vision_train_bytes(const clipmi_model* m, int B, int n_ctx, size_t* w
  * forward reads are the masters rounded through fp16 (the reference's .half()).  L = tokens + n_ctx rows per image.  The blocks run
  * LayerNorm, GEMM, attention (no mask) as separate launches on the fp32 residual stream, c_fc keeps its fp16 pre-activation and
  * QuickGELU is an element-wise launch on that rounded value; then ln_post on the class rows and the projection: out fp32 [B, E].
- * Requires a patch size of 8, 16 or 32, Dv % 64 == 0, E % 64 == 0, L <= 224 (CLIPMI_ERR_SHAPE), 1 <= depth <= vision_layers.
+ * Requires a patch size that divides the resolution, Dv % 64 == 0, E % 64 == 0, L <= 224 (640 with the option vision_train_long;
+ * CLIPMI_ERR_SHAPE), 1 <= depth <= vision_layers.  Patches of 8, 16 and 32 pixels go through clipmi_patch_embed's loader and
+ * clipmi_embed_ln; any other patch size (ViT-L/14) through clipmi_patchify into the workspace, the dense GEMM whose epilogue adds the
+ * positional rows, and clipmi_embed_ln without the positional add, as in clipmi_encode_image (the workspace then holds the im2col
+ * matrix, B * grid^2 * kpad * 2 bytes, where it holds the fp16 copy of an fp32 image batch otherwise: clipmi_vision_train_bytes).
  * CLIPMI_CALL_STREAM_F16: CLIPMI_ERR_STATE.  workspace and stash 256-byte aligned.
  *
  * Byte layout of the stash: clipmi_text_encoder_train's with M = B * L token rows, Dt = Dv and layers = vision_layers --
