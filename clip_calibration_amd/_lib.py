@@ -9,6 +9,8 @@ from __future__ import annotations
 import ctypes as C
 import os
 
+import torch
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # CLIPMI_LIBRARY selects another BUILD of the same library (the tuning build with phase stamps); never a different backend
 LIB_PATH = os.environ.get("CLIPMI_LIBRARY") or os.path.join(_HERE, "csrc", "libclipmi.so")
@@ -18,6 +20,7 @@ ABI_VERSION = 16
 
 OK, ERR_ARG, ERR_SHAPE, ERR_HIP, ERR_WORKSPACE, ERR_STATE = 0, -1, -2, -3, -4, -5
 F16, F32 = 0, 1
+_DT = {torch.float16: F16, torch.float32: F32}                  # the dtype argument of every entry point that takes fp16 or fp32
 COMM_ID_BYTES = 128
 EPI_NONE, EPI_BIAS, EPI_BIAS_QUICKGELU, EPI_BIAS_RESIDUAL, EPI_BIAS_RELU, EPI_BIAS_RESIDUAL16_RELU = 0, 1, 2, 3, 4, 5
 CALL_DEFAULT, CALL_STREAM_F32, CALL_STREAM_F16 = 0, 1, 2   # per-call flags of the tower calls (include/clipmi.h)

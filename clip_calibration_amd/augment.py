@@ -25,8 +25,8 @@ import numpy as np
 import torch
 
 from . import _lib, fitloop
-from ._lib import check, lib
-from .preprocess import CLIP_MEAN, CLIP_STD, Preprocess, _DTYPES, _FILTERS
+from ._lib import _DT, check, lib
+from .preprocess import CLIP_MEAN, CLIP_STD, Preprocess, _FILTERS
 
 Views = Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray, np.ndarray, np.ndarray]
 
@@ -138,7 +138,7 @@ class TrainPreprocess(Preprocess):
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)   # stream-ordered by the caching allocator
         stream = torch.cuda.current_stream(dev)
         check(lib.clipmi_augment(buf.data_ptr(), extent, host.data_ptr(), B, host_v.data_ptr(), V, n, filt, self._table(dev).data_ptr(),
-                                 out.data_ptr(), _DTYPES[self.dtype], ws.data_ptr(), nbytes, stream.cuda_stream), "clipmi_augment")
+                                 out.data_ptr(), _DT[self.dtype], ws.data_ptr(), nbytes, stream.cuda_stream), "clipmi_augment")
         ev = torch.cuda.Event()
         ev.record(stream)
         self._inflight.append(((host, host_v), ev))

@@ -41,7 +41,6 @@ from __future__ import annotations
 
 import collections
 import ctypes as C
-import math
 from typing import Dict, Optional, Sequence
 
 import numpy as np
@@ -138,10 +137,6 @@ class _CoCoOpTower(_Tower):
         return self.step_ws
 
 
-def _scale(logit_scale: float) -> float:
-    return float(np.float32(math.exp(logit_scale)))
-
-
 def gradients(clip_model, tokenized_prompts, params, features: torch.Tensor, labels, logit_scale: float = 4.6052,
               grad_scale: float = DEFAULT_GRAD_SCALE, seq_rows: Optional[int] = None, return_parts: bool = False, return_operand_stats: bool = False):
     """``(loss, grads)`` of CoCoOp's training loss (module docstring) on the GPU: loss fp32 [1], grads a dict of the five fp32 gradients
@@ -154,8 +149,7 @@ def gradients(clip_model, tokenized_prompts, params, features: torch.Tensor, lab
     if _is_dynamic(who, grad_scale):
         raise ValueError(f"{who}: grad_scale={DYNAMIC!r} belongs to a fit (CoCoOpFitState, fit_prompt_learner); one gradient needs a number")
     gs = _check_grad_scale(who, grad_scale)
-    if not math.isfinite(logit_scale):
-        raise ValueError(f"{who}: logit_scale={logit_scale} (finite)")
+    scale = fitloop.exp_logit_scale(who, logit_scale)
     E = int(clip_model.geometry.embed_dim)
     labels_d = _check_batch(who, features, labels, Cn, E)
     _need_gpu(features, "features")
@@ -165,7 +159,7 @@ def gradients(clip_model, tokenized_prompts, params, features: torch.Tensor, lab
     dev = features.device
     views = ops.cocoop_block_views(_master_block(params, n_ctx, tower.D, E, H, dev), n_ctx, tower.D, E, H)
     text = tower.forward(views, features)
-    loss, d_text, rows = ops.cocoop_head(features, labels_d, text, _scale(logit_scale), gs, want_rows=True)
+    loss, d_text, rows = ops.cocoop_head(features, labels_d, text, scale, gs, want_rows=True)
     stats = torch.zeros(4, dtype=torch.int64, device=dev) if return_operand_stats else None
     d_embed = tower.backward(d_text, stats)
     grads = {k: v.clone() for k, v in ops.cocoop_block_views(tower.reduce(d_embed, views[NAMES[3]], gs), n_ctx, tower.D, E, H).items()}
@@ -191,8 +185,7 @@ class CoCoOpFitState(fitmonitor.Monitored):
         self.C, self.n_ctx, self.H, self._last = _check_prompts(who, clip_model, tokenized_prompts, params, seq_rows)
         self.dynamic, self.grad_scale, self.scaler = _scale_args(who, grad_scale, scaler)
         fitloop.check_sgd(who, momentum, dampening, weight_decay, nesterov)
-        if not math.isfinite(logit_scale):
-            raise ValueError(f"{who}: logit_scale={logit_scale} (finite)")
+        self.scale = fitloop.exp_logit_scale(who, logit_scale)
         dev = clip_model.device
         if dev.type != "cuda":
             raise RuntimeError(f"clipmi: {who} needs the model on a ROCm GPU (model.to('cuda')); the HIP path has no CPU fallback")
@@ -201,7 +194,6 @@ class CoCoOpFitState(fitmonitor.Monitored):
         self.block = _master_block(params, self.n_ctx, self.D, self.E, self.H, dev)
         self.buf = torch.zeros_like(self.block) if momentum != 0.0 else None
         self._views = ops.cocoop_block_views(self.block, self.n_ctx, self.D, self.E, self.H)
-        self.scale = _scale(logit_scale)
         self.momentum, self.dampening, self.nesterov, self.weight_decay = momentum, dampening, nesterov, weight_decay
         self._towers: Dict[int, _CoCoOpTower] = {}
         self.steps = 0

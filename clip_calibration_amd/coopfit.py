@@ -68,7 +68,7 @@ import numpy as np
 import torch
 
 from . import _lib, fitloop, fitmonitor, ops
-from ._lib import check, lib
+from ._lib import _DT, check, lib
 from .fitloop import _host_int_array, _need_gpu, steps_per_epoch
 
 # 2^12, measured on the ViT-B/16 text geometry with synthetic weights (profiles/coopfit_parity.txt, "grad_scale"): the smallest of 2^0, 2^4,
@@ -76,8 +76,6 @@ from .fitloop import _host_int_array, _need_gpu, steps_per_epoch
 # 2^4 of headroom below fp16's largest value (2^5.9; 2^1.9 at 2^16).  A model whose gradients are much larger than that model's overflows
 # fp16 at this scale -- the context then turns NaN, it does not go wrong silently; pass a smaller power of two, or grad_scale="dynamic".
 DEFAULT_GRAD_SCALE = 4096.0
-
-_DT = {torch.float16: _lib.F16, torch.float32: _lib.F32}
 
 
 def _check_grad_scale(who: str, grad_scale: float) -> float:
@@ -253,31 +251,27 @@ def _check_method(who: str, method: str, teacher, w: float, T: float, lam: float
         raise ValueError(f"{who}: lam={lam} (finite)")
 
 
+def _pack_dgrad(model, blocks, projection: torch.Tensor, struct, slot: str):
+    """The transposed fp16 copies of a frozen tower's weights (``struct``: clipmi_text_dgrad or clipmi_vision_dgrad, ``projection`` as it
+    lies), packed once per bound model and again when a weight's version moves; the model keeps them under ``slot``."""
+    per_block = [(b.attn.in_proj_weight, b.attn.out_proj.weight, b.mlp.c_fc.weight, b.mlp.c_proj.weight) for b in blocks]
+    key = (id(model._bound),) + tuple((w.data_ptr(), w._version) for w in [projection] + [w for ws in per_block for w in ws])
+    hit = model.__dict__.get(slot)
+    if hit is not None and hit[0] == key:
+        return hit[1]
+    keep = [w.detach().to(torch.float16).t().contiguous() for ws in per_block for w in ws]
+    arr = (_lib.BlockDgrad * len(per_block))(*[_lib.BlockDgrad(*[t.data_ptr() for t in keep[4 * i:4 * i + 4]]) for i in range(len(per_block))])
+    keep.append(projection.detach().to(torch.float16).contiguous())
+    packed = (struct(keep[-1].data_ptr(), arr), arr, keep)
+    model.__dict__[slot] = (key, packed)
+    return packed
+
+
 def _dgrad(model):
     """The transposed fp16 copies of the frozen text weights (clipmi_text_dgrad), packed once per bound model and again when a text
     weight's version moves."""
     model._ensure_bound()
-    blocks = list(model.transformer.resblocks)
-    ws = [model.text_projection] + [w for b in blocks for w in (b.attn.in_proj_weight, b.attn.out_proj.weight, b.mlp.c_fc.weight, b.mlp.c_proj.weight)]
-    key = (id(model._bound),) + tuple((w.data_ptr(), w._version) for w in ws)
-    hit = model.__dict__.get("_coop_dgrad")
-    if hit is not None and hit[0] == key:
-        return hit[1]
-    keep = []
-
-    def t16(w):
-        t = w.detach().to(torch.float16).t().contiguous()
-        keep.append(t)
-        return t.data_ptr()
-
-    arr = (_lib.BlockDgrad * len(blocks))()
-    for i, b in enumerate(blocks):
-        arr[i] = _lib.BlockDgrad(t16(b.attn.in_proj_weight), t16(b.attn.out_proj.weight), t16(b.mlp.c_fc.weight), t16(b.mlp.c_proj.weight))
-    proj = model.text_projection.detach().to(torch.float16).contiguous()
-    keep.append(proj)
-    td = _lib.TextDgrad(proj.data_ptr(), arr)
-    model.__dict__["_coop_dgrad"] = (key, (td, arr, keep))
-    return td, arr, keep
+    return _pack_dgrad(model, model.transformer.resblocks, model.text_projection, _lib.TextDgrad, "_coop_dgrad")
 
 
 class _Tower:
@@ -402,8 +396,7 @@ def context_gradient(clip_model, tokenized_prompts, ctx: torch.Tensor, features:
     if _is_dynamic(who, grad_scale):
         raise ValueError(f"{who}: grad_scale={DYNAMIC!r} belongs to a fit (CoOpFitState, fit_context); one gradient needs a number")
     gs = _check_grad_scale(who, grad_scale)
-    if not math.isfinite(logit_scale):
-        raise ValueError(f"{who}: logit_scale={logit_scale} (finite)")
+    scale = fitloop.exp_logit_scale(who, logit_scale)
     E = int(clip_model.geometry.embed_dim)
     _check_method(who, method, teacher, w, T, lam, Cn, E)
     labels_d = _check_batch(who, features, labels, Cn, E)
@@ -414,7 +407,6 @@ def context_gradient(clip_model, tokenized_prompts, ctx: torch.Tensor, features:
     dev = features.device
     master = fitloop.master(ctx, dev)
     text = tower.forward(master)
-    scale = float(np.float32(math.exp(logit_scale)))
     stats = torch.zeros(4, dtype=torch.int64, device=dev) if return_operand_stats else None
     losses, d_text, d_kl = ops.prompt_head(features, labels_d, text, scale, gs, method, teacher, w, T, _new_losses(method, dev))
     loss = losses[0:1]
@@ -461,8 +453,7 @@ class CoOpFitState(fitmonitor.Monitored):
         _static_prograd(who, method, grad_scale)
         self.dynamic, self.grad_scale, self.scaler = _scale_args(who, grad_scale, scaler)
         fitloop.check_sgd(who, momentum, dampening, weight_decay, nesterov)
-        if not math.isfinite(logit_scale):
-            raise ValueError(f"{who}: logit_scale={logit_scale} (finite)")
+        self.scale = fitloop.exp_logit_scale(who, logit_scale)
         _check_method(who, method, teacher, w, T, lam, self.C, int(clip_model.geometry.embed_dim))
         self.method, self.w, self.T, self.lam = method, float(w), float(T), float(lam)
         self.teacher = None
@@ -473,7 +464,6 @@ class CoOpFitState(fitmonitor.Monitored):
         dev = clip_model.device
         self.ctx = fitloop.master(ctx, dev)
         self.buf = torch.zeros_like(self.ctx) if momentum != 0.0 else None
-        self.scale = float(np.float32(math.exp(logit_scale)))
         self.momentum, self.dampening, self.nesterov, self.weight_decay = momentum, dampening, nesterov, weight_decay
         self.steps = 0
         self._scaler = _BlockScaler(self.scaler, dev) if self.dynamic else None

@@ -123,18 +123,6 @@ int launch_couple(const char* who, const float* block, int n_ctx, int depth, int
 
 inline size_t step_bytes(int n_ctx, int depth, int Dt) { return 2 * align256((size_t)depth * n_ctx * Dt * 4); }
 
-// what the step asks of the optimiser's arguments; the one-call step asks it before anything is enqueued
-int check_step_args(const char* who, const float* block, const float* buf, const float* grad_out, int apply, const float* lr, float grad_scale,
-                    float momentum, float dampening, float weight_decay, int nesterov) {
-  CLIPMI_REQUIRE(block, CLIPMI_ERR_ARG, "%s: null pointer", who);
-  CLIPMI_REQUIRE(apply || grad_out, CLIPMI_ERR_ARG, "%s: null pointer (nothing to write)", who);
-  CLIPMI_REQUIRE(!apply || lr, CLIPMI_ERR_ARG, "%s: null pointer (a step needs lr)", who);
-  CLIPMI_REQUIRE(std::isfinite(grad_scale) && grad_scale > 0.f, CLIPMI_ERR_ARG, "%s: grad_scale=%g (finite, > 0)", who, grad_scale);
-  if (int rc = check_sgd(who, momentum, dampening, weight_decay, nesterov)) return rc;
-  CLIPMI_REQUIRE(!apply || momentum == 0.f || buf, CLIPMI_ERR_ARG, "%s: null pointer (a momentum needs the buffer)", who);
-  return CLIPMI_OK;
-}
-
 int launch_step(const char* who, const float* d_embed, const float* d_deep, const float* d_vis, float* block, float* buf, float* grad_out, int apply, int C,
                 int L, int n_ctx, int depth, int Dt, int Dv, float grad_scale, const float* lr, int first_step, float momentum, float dampening,
                 float weight_decay, int nesterov, void* workspace, size_t workspace_bytes, hipStream_t s) {
@@ -156,6 +144,37 @@ int launch_step(const char* who, const float* d_embed, const float* d_deep, cons
                      (const float*)d_t, (const float*)t_keep, apply ? 1 : 0, 1.f / grad_scale, lr,
                      make_sgd_args(momentum, dampening, weight_decay, nesterov, first_step));
   return check_launch("maple_step_kernel");
+}
+
+// the one-call step's workspace: the text tower's | the image tower's | the buffers between the calls.  vis and d_vis have room for every
+// layer of the image tower, whatever the depth.  Carving and sizing go through this one function.
+struct StepWs {
+  size_t tws, vws, head_bytes, step_bytes, bytes;
+  char* vision;
+  float *text, *d_text, *feats, *d_feats, *d_embed, *d_deep, *vis, *d_vis;
+  void *head, *step;
+};
+int carve_step(const clipmi_model* m, void* p, int C, int seq_rows, int B, int n_ctx, int depth, StepWs* w) {
+  if (int rc = clipmi_text_train_bytes(m, C, seq_rows, &w->tws, nullptr)) return rc;
+  if (int rc = clipmi_vision_train_bytes(m, B, n_ctx, &w->vws, nullptr)) return rc;
+  const int E = m->g.embed_dim, Dt = m->g.text_width, Dv = m->g.vision_width;
+  w->vision = p ? static_cast<char*>(p) + w->tws : nullptr;
+  Carver c(w->vision);
+  c.off = w->vws;
+  w->text = c.take<float>((size_t)C * E * 4);
+  w->d_text = c.take<float>((size_t)C * E * 4);
+  w->feats = c.take<float>((size_t)B * E * 4);
+  w->d_feats = c.take<float>((size_t)B * E * 4);
+  w->d_embed = c.take<float>((size_t)C * live_rows(m, seq_rows) * Dt * 4);
+  w->d_deep = c.take<float>((size_t)depth * n_ctx * Dt * 4);
+  w->vis = c.take<float>((size_t)m->g.vision_layers * n_ctx * Dv * 4);
+  w->d_vis = c.take<float>((size_t)m->g.vision_layers * n_ctx * Dv * 4);
+  w->head_bytes = clipmi_maple_head_workspace_bytes(B, E, C);
+  w->head = c.take<char>(w->head_bytes);
+  w->step_bytes = step_bytes(n_ctx, depth, Dt);
+  w->step = c.take<char>(w->step_bytes);
+  w->bytes = w->tws + c.off;
+  return CLIPMI_OK;
 }
 
 }  // namespace
@@ -187,15 +206,9 @@ int clipmi_maple_step(const float* d_embed, const float* d_deep, const float* d_
 }
 
 size_t clipmi_maple_train_step_bytes(const clipmi_model* m, int n_prompts, int seq_rows, int B, int n_ctx, int depth) {
-  size_t tws = 0, vws = 0;
-  if (!m || n_prompts < 2 || B < 1 || n_ctx < 1 || depth < 1 || clipmi_text_train_bytes(m, n_prompts, seq_rows, &tws, nullptr) != CLIPMI_OK ||
-      clipmi_vision_train_bytes(m, B, n_ctx, &vws, nullptr) != CLIPMI_OK)
-    return 0;
-  const int E = m->g.embed_dim, Dt = m->g.text_width, Dv = m->g.vision_width;
-  const size_t vis = align256((size_t)m->g.vision_layers * n_ctx * Dv * 4);
-  return tws + vws + 2 * align256((size_t)n_prompts * E * 4) + 2 * align256((size_t)B * E * 4) +
-         align256((size_t)n_prompts * live_rows(m, seq_rows) * Dt * 4) + align256((size_t)depth * n_ctx * Dt * 4) + 2 * vis +
-         clipmi_maple_head_workspace_bytes(B, E, n_prompts) + step_bytes(n_ctx, depth, Dt);
+  StepWs w;
+  if (!m || n_prompts < 2 || B < 1 || n_ctx < 1 || depth < 1 || carve_step(m, nullptr, n_prompts, seq_rows, B, n_ctx, depth, &w) != CLIPMI_OK) return 0;
+  return w.bytes;
 }
 
 // the static call's workspace | the block of scale * gradient that clipmi_maple_step leaves with apply = 0 | clipmi_block_step_scaled's
@@ -222,62 +235,50 @@ static int maple_train_step(const char* who, const ScalerCall* sc, size_t need, 
   CLIPMI_REQUIRE(block && lr && labels && image, CLIPMI_ERR_ARG, "%s: null pointer", who);
   const int E = m->g.embed_dim, Dt = m->g.text_width, Dv = m->g.vision_width, L = live_rows(m, seq_rows);
   if (int rc = check_shape(who, n_ctx, depth, Dt, Dv)) return rc;
-  size_t tws = 0, vws = 0;
-  if (int rc = clipmi_text_train_bytes(m, C, seq_rows, &tws, nullptr)) return rc;
-  if (int rc = clipmi_vision_train_bytes(m, B, n_ctx, &vws, nullptr)) return rc;
+  StepWs w;
+  if (int rc = carve_step(m, workspace, C, seq_rows, B, n_ctx, depth, &w)) return rc;
   CLIPMI_REQUIRE(need > 0 && workspace_bytes >= need, CLIPMI_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, need);
-  char* vision_ws = static_cast<char*>(workspace) + tws;
-  if (int rc = check_train_call(who, m, C, workspace, tws, text_stash, text_stash_bytes, seq_rows)) return rc;
+  if (int rc = check_train_call(who, m, C, workspace, w.tws, text_stash, text_stash_bytes, seq_rows)) return rc;
   if (int rc = check_deep(who, m, n_ctx, depth - 1, block, seq_rows)) return rc;
   if (int rc = check_train_inputs(who, m, prompts, dtype, block, n_ctx, eot, seq_rows, nullptr, 0)) return rc;
   if (int rc = check_dgrad(who, m, wt)) return rc;
   CLIPMI_REQUIRE(L <= AB_MAX_L, CLIPMI_ERR_SHAPE, "%s: %d token rows per prompt (at most %d)", who, L, AB_MAX_L);
-  if (int rc = check_vision_train_call(who, m, B, n_ctx, depth, vision_ws, vws, vision_stash, vision_stash_bytes)) return rc;
+  if (int rc = check_vision_train_call(who, m, B, n_ctx, depth, w.vision, w.vws, vision_stash, vision_stash_bytes)) return rc;
   if (int rc = check_vision_dgrad(who, m, wv)) return rc;
   CLIPMI_REQUIRE(image_dtype == CLIPMI_F16 || image_dtype == CLIPMI_F32, CLIPMI_ERR_ARG, "%s: image dtype %d", who, image_dtype);
   CLIPMI_REQUIRE(std::isfinite(scale), CLIPMI_ERR_ARG, "%s: scale=%g (finite)", who, scale);
   if (!sc)
     if (int rc = check_step_args(who, block, buf, grad_out, 1, lr, grad_scale, momentum, dampening, weight_decay, nesterov)) return rc;
-  const size_t head_bytes = clipmi_maple_head_workspace_bytes(B, E, C), st_bytes = step_bytes(n_ctx, depth, Dt);
-  Carver c(vision_ws + vws);
-  float* text = c.take<float>((size_t)C * E * 4);
-  float* d_text = c.take<float>((size_t)C * E * 4);
-  float* feats = c.take<float>((size_t)B * E * 4);
-  float* d_feats = c.take<float>((size_t)B * E * 4);
-  float* d_embed = c.take<float>((size_t)C * L * Dt * 4);
-  float* d_deep = c.take<float>((size_t)depth * n_ctx * Dt * 4);
-  float* vis = c.take<float>((size_t)m->g.vision_layers * n_ctx * Dv * 4);
-  float* d_vis = c.take<float>((size_t)m->g.vision_layers * n_ctx * Dv * 4);
-  void* head_ws = c.take<char>(head_bytes);
-  void* step_ws = c.take<char>(st_bytes);
   const int64_t total = MapleShape{n_ctx, depth, Dt, Dv}.total();
   const size_t scaled_bytes = sc ? block_step_scaled_bytes(total) : 0;
-  float* scaled_grad = c.take<float>(sc ? (size_t)total * 4 : 0);
-  void* scaled_ws = c.take<char>(scaled_bytes);
+  Carver behind(workspace ? static_cast<char*>(workspace) + w.bytes : nullptr);
+  float* scaled_grad = behind.take<float>(sc ? (size_t)total * 4 : 0);
+  void* scaled_ws = behind.take<char>(scaled_bytes);
   if (sc)   // the scaler's and the optimiser's refusals come ahead of the first launch
     if (int rc = check_block_step_scaled(who, scaled_grad, block, buf, grad_out, lr, total, *sc, momentum,
                                          dampening, weight_decay, nesterov, scaled_ws, scaled_bytes))
       return rc;
   const float* deep = block + (int64_t)n_ctx * Dt;
-  if (int rc = launch_couple(who, block, n_ctx, depth, Dt, Dv, vis, s)) return rc;
-  if (int rc = run_train_forward(m, prompts, dtype, block, n_ctx, 0, eot, C, seq_rows, text, workspace, text_stash, s, deep, depth - 1)) return rc;
-  if (int rc = run_vision_train_forward(m, image, image_dtype, B, vis, n_ctx, depth, feats, vision_ws, vision_stash, s)) return rc;
-  if (int rc = launch_maple_head(who, feats, E, labels, text, B, E, C, scale, grad_scale, loss, d_feats, d_text, nullptr, head_ws, head_bytes, s)) return rc;
+  if (int rc = launch_couple(who, block, n_ctx, depth, Dt, Dv, w.vis, s)) return rc;
+  if (int rc = run_train_forward(m, prompts, dtype, block, n_ctx, 0, eot, C, seq_rows, w.text, workspace, text_stash, s, deep, depth - 1)) return rc;
+  if (int rc = run_vision_train_forward(m, image, image_dtype, B, w.vis, n_ctx, depth, w.feats, w.vision, vision_stash, s)) return rc;
+  if (int rc = launch_maple_head(who, w.feats, E, labels, w.text, B, E, C, scale, grad_scale, loss, w.d_feats, w.d_text, nullptr, w.head, w.head_bytes, s))
+    return rc;
   if (sc) {
-    if (int rc = launch_grad_scale_rows(who, d_text, C, E, sc->state, s)) return rc;
-    if (int rc = launch_grad_scale_rows(who, d_feats, B, E, sc->state, s)) return rc;
+    if (int rc = launch_grad_scale_rows(who, w.d_text, C, E, sc->state, s)) return rc;
+    if (int rc = launch_grad_scale_rows(who, w.d_feats, B, E, sc->state, s)) return rc;
   }
-  if (int rc = run_backward(m, wt, d_text, C, seq_rows, d_embed, workspace, text_stash, nullptr, s, n_ctx, depth - 1, d_deep)) return rc;
-  if (int rc = run_vision_backward(m, wv, d_feats, B, n_ctx, depth, d_vis, vision_ws, vision_stash, nullptr, s)) return rc;
+  if (int rc = run_backward(m, wt, w.d_text, C, seq_rows, w.d_embed, workspace, text_stash, nullptr, s, n_ctx, depth - 1, w.d_deep)) return rc;
+  if (int rc = run_vision_backward(m, wv, w.d_feats, B, n_ctx, depth, w.d_vis, w.vision, vision_stash, nullptr, s)) return rc;
   if (sc) {
-    if (int rc = launch_step(who, d_embed, d_deep, d_vis, block, nullptr, scaled_grad, 0, C, L, n_ctx, depth, Dt, Dv, 1.f, nullptr, 0, momentum, dampening,
-                             weight_decay, nesterov, step_ws, st_bytes, s))
+    if (int rc = launch_step(who, w.d_embed, w.d_deep, w.d_vis, block, nullptr, scaled_grad, 0, C, L, n_ctx, depth, Dt, Dv, 1.f, nullptr, 0, momentum, dampening,
+                             weight_decay, nesterov, w.step, w.step_bytes, s))
       return rc;
     return launch_block_step_scaled(scaled_grad, block, buf, grad_out, total, *sc, lr, momentum, dampening,
                                     weight_decay, nesterov, scaled_ws, s);
   }
-  return launch_step(who, d_embed, d_deep, d_vis, block, buf, grad_out, 1, C, L, n_ctx, depth, Dt, Dv, grad_scale, lr, first_step, momentum, dampening,
-                     weight_decay, nesterov, step_ws, st_bytes, s);
+  return launch_step(who, w.d_embed, w.d_deep, w.d_vis, block, buf, grad_out, 1, C, L, n_ctx, depth, Dt, Dv, grad_scale, lr, first_step, momentum, dampening,
+                     weight_decay, nesterov, w.step, w.step_bytes, s);
 }
 
 extern "C" {

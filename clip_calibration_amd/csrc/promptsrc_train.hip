@@ -65,18 +65,6 @@ int check_shape(const char* who, int nt, int dt, int Dt, int nv, int dv, int Dv)
   return CLIPMI_OK;
 }
 
-// what the step asks of the optimiser's arguments; the one-call step asks it before anything is enqueued
-int check_step_args(const char* who, const float* block, const float* buf, const float* grad_out, int apply, const float* lr, float grad_scale,
-                    float momentum, float dampening, float weight_decay, int nesterov) {
-  CLIPMI_REQUIRE(block, CLIPMI_ERR_ARG, "%s: null pointer", who);
-  CLIPMI_REQUIRE(apply || grad_out, CLIPMI_ERR_ARG, "%s: null pointer (nothing to write)", who);
-  CLIPMI_REQUIRE(!apply || lr, CLIPMI_ERR_ARG, "%s: null pointer (a step needs lr)", who);
-  CLIPMI_REQUIRE(std::isfinite(grad_scale) && grad_scale > 0.f, CLIPMI_ERR_ARG, "%s: grad_scale=%g (finite, > 0)", who, grad_scale);
-  if (int rc = check_sgd(who, momentum, dampening, weight_decay, nesterov)) return rc;
-  CLIPMI_REQUIRE(!apply || momentum == 0.f || buf, CLIPMI_ERR_ARG, "%s: null pointer (a momentum needs the buffer)", who);
-  return CLIPMI_OK;
-}
-
 int launch_step(const char* who, const float* d_embed, const float* d_deep, const float* d_vis, float* block, float* buf, float* grad_out, int apply, int C,
                 int L, int nt, int dt, int Dt, int nv, int dv, int Dv, float grad_scale, const float* lr, int first_step, float momentum, float dampening,
                 float weight_decay, int nesterov, hipStream_t s) {

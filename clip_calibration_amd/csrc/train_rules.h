@@ -29,6 +29,18 @@ inline int check_sgd(const char* who, float momentum, float dampening, float wei
                  "%s: nesterov needs a momentum and zero dampening (momentum=%g, dampening=%g)", who, momentum, dampening);
   return CLIPMI_OK;
 }
+// what a block's step (clipmi_maple_step, clipmi_promptsrc_step) asks of the optimiser's arguments; their one-call step asks it before
+// anything is enqueued
+inline int check_step_args(const char* who, const float* block, const float* buf, const float* grad_out, int apply, const float* lr, float grad_scale,
+                           float momentum, float dampening, float weight_decay, int nesterov) {
+  CLIPMI_REQUIRE(block, CLIPMI_ERR_ARG, "%s: null pointer", who);
+  CLIPMI_REQUIRE(apply || grad_out, CLIPMI_ERR_ARG, "%s: null pointer (nothing to write)", who);
+  CLIPMI_REQUIRE(!apply || lr, CLIPMI_ERR_ARG, "%s: null pointer (a step needs lr)", who);
+  CLIPMI_REQUIRE(std::isfinite(grad_scale) && grad_scale > 0.f, CLIPMI_ERR_ARG, "%s: grad_scale=%g (finite, > 0)", who, grad_scale);
+  if (int rc = check_sgd(who, momentum, dampening, weight_decay, nesterov)) return rc;
+  CLIPMI_REQUIRE(!apply || momentum == 0.f || buf, CLIPMI_ERR_ARG, "%s: null pointer (a momentum needs the buffer)", who);
+  return CLIPMI_OK;
+}
 inline SgdArgs make_sgd_args(float momentum, float dampening, float weight_decay, int nesterov, int first_step) {
   return SgdArgs{momentum, (float)(1.0 - (double)dampening), weight_decay, nesterov ? 1 : 0, first_step ? 1 : 0};
 }

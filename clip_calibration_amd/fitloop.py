@@ -90,6 +90,13 @@ def order_on(order: Optional[np.ndarray], dtype, dev) -> Optional[torch.Tensor]:
     return None if order is None else torch.from_numpy(np.ascontiguousarray(order, dtype=dtype)).to(dev)
 
 
+def exp_logit_scale(who: str, logit_scale: float) -> float:
+    """exp(logit_scale) as the fp32 value the heads multiply by; a non-finite logit_scale is refused."""
+    if not math.isfinite(logit_scale):
+        raise ValueError(f"{who}: logit_scale={logit_scale} (finite)")
+    return float(np.float32(math.exp(logit_scale)))
+
+
 def master(t: torch.Tensor, dev) -> torch.Tensor:
     """A fresh contiguous fp32 copy on the device: the master values the kernels update in place."""
     return t.detach().to(device=dev, dtype=torch.float32, copy=True).contiguous()

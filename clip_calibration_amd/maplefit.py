@@ -48,9 +48,9 @@ import numpy as np
 import torch
 
 from . import _lib, fitloop, fitmonitor, ops
-from ._lib import check, lib
+from ._lib import _DT, check, lib
 from . import coopfit, vptfit
-from .coopfit import DYNAMIC, _BlockScaler, _check_grad_scale, _is_dynamic, _scale_args
+from .coopfit import DYNAMIC, _check_grad_scale, _is_dynamic
 
 # 2^10, one power of two for both towers' backwards, measured at ViT-B/16 with synthetic weights, n_ctx 2, depth 9, batch 4, 100 classes
 # (profiles/maplefit_parity.txt, "grad_scale"): the text tower's dgrad-GEMM operands reach 1413 there (2^5.5 of headroom below fp16's
@@ -59,8 +59,6 @@ from .coopfit import DYNAMIC, _BlockScaler, _check_grad_scale, _is_dynamic, _sca
 # with much larger gradients overflows fp16 at this scale -- the parameters then turn NaN, they do not go wrong silently; pass a smaller
 # power of two.
 DEFAULT_GRAD_SCALE = 1024.0
-
-_DT = {torch.float16: _lib.F16, torch.float32: _lib.F32}
 
 
 def param_names(depth: int):
@@ -159,58 +157,83 @@ def maple_step(d_embed: torch.Tensor, d_deep: Optional[torch.Tensor], d_vis: tor
     return grad
 
 
-class _Towers:
-    """Both frozen towers in training mode for one prompt set: coopfit's text tower and vptfit's image tower, driven with deep prompts."""
+class _TwoTowers:
+    """Both frozen towers in training mode for one prompt set: coopfit's text tower driven with deep prompts and vptfit's image tower.
+    ``nt`` / ``dt`` and ``nv`` / ``dv`` are the prompt rows and the prompt depth of the text side and of the image side; the text side's
+    prompts are the front of the master block, [ctx [nt, Dt] | deep [dt - 1, nt, Dt]].  A method supplies ``image_prompts`` (where the
+    image tower's prompts come from) and ``_step_bytes`` (its one-call sizing symbols)."""
 
-    def __init__(self, who: str, model, tokenized_prompts, learner_params, seq_rows: Optional[int], class_token_position: str = "end"):
-        self.n_ctx, self.depth = _check_design(who, model, learner_params, class_token_position)
-        Cn, n_ctx, per_class, last = coopfit._check_prompts(who, model, tokenized_prompts, learner_params["ctx"])
+    def __init__(self, who: str, model, tokenized_prompts, Cn: int, last_eot: int, nt: int, dt: int, nv: int, dv: int, seq_rows: Optional[int]):
+        self.nt, self.dt, self.nv, self.dv = nt, dt, nv, dv
         self.model, self.C = model, Cn
-        self.text = coopfit._Tower(who, model, tokenized_prompts, Cn, n_ctx, False, last, seq_rows)
-        self.vision = vptfit._Tower(who, model, self.depth, n_ctx)
+        self.text = coopfit._Tower(who, model, tokenized_prompts, Cn, nt, False, last_eot, seq_rows)
+        self.vision = vptfit._Tower(who, model, dv, nv)
         g = model.geometry
         self.Dt, self.Dv, self.E = int(g.transformer_width), int(g.vision_width), int(g.embed_dim)
-        dev = model.device
-        self.vis = torch.empty(self.depth, n_ctx, self.Dv, dtype=torch.float32, device=dev)
-        self.d_deep = torch.empty(max(self.depth - 1, 1), n_ctx, self.Dt, dtype=torch.float32, device=dev)
-        self.step_ws = torch.empty(max(lib.clipmi_maple_step_workspace_bytes(n_ctx, self.depth, self.Dt), 256), dtype=torch.uint8, device=dev)
+        self.d_deep = torch.empty(max(dt - 1, 1), nt, self.Dt, dtype=torch.float32, device=model.device)
         self.one_ws = None
 
-    def deep_ptr(self, block: torch.Tensor):
-        return block.data_ptr() + 4 * self.n_ctx * self.Dt if self.depth > 1 else None
-
     def text_forward(self, block: torch.Tensor) -> torch.Tensor:
-        """The text half of ``forward``: couple (the image tower's prompts into ``self.vis``), then the text features [C, E]."""
+        """The text features [C, E] at the block."""
         t, m = self.text, self.model
-        couple(block, self.n_ctx, self.depth, self.Dt, self.Dv, self.vis)
+        deep = block.data_ptr() + 4 * self.nt * self.Dt if self.dt > 1 else None
         with m._launch_lock:
-            check(lib.clipmi_text_encoder_train_deep(m._handle, t.base.data_ptr(), _DT[t.base.dtype], block.data_ptr(), self.n_ctx, 0, t.eot.data_ptr(), t.C,
-                                                     t.rows, self.deep_ptr(block), self.depth - 1, t.text.data_ptr(), t.ws.data_ptr(), t.ws.numel(),
-                                                     t.stash.data_ptr(), t.stash.numel(), _lib.CALL_DEFAULT, ops._stream()),
-                  "clipmi_text_encoder_train_deep")
+            check(lib.clipmi_text_encoder_train_deep(m._handle, t.base.data_ptr(), _DT[t.base.dtype], block.data_ptr(), self.nt, 0, t.eot.data_ptr(), t.C,
+                                                     t.rows, deep, self.dt - 1, t.text.data_ptr(), t.ws.data_ptr(), t.ws.numel(), t.stash.data_ptr(),
+                                                     t.stash.numel(), _lib.CALL_DEFAULT, ops._stream()), "clipmi_text_encoder_train_deep")
         return t.text
 
     def forward(self, block: torch.Tensor, images: torch.Tensor):
-        """(text features [C, E], image features [B, E]) at the block: couple, text forward, image forward."""
-        return self.text_forward(block), self.vision.forward(images, self.vis)
+        """(text features [C, E], image features [B, E]) at the block: the image tower's prompts, the text forward, the image forward."""
+        vis = self.image_prompts(block)
+        return self.text_forward(block), self.vision.forward(images, vis)
 
     def backward(self, d_text: torch.Tensor, d_feats: torch.Tensor, stats_text: Optional[torch.Tensor] = None, stats_vision: Optional[torch.Tensor] = None):
         """(d_embed, d_deep, d_vis): the text tower's backward, then the image tower's."""
         t, m = self.text, self.model
         with m._launch_lock:
-            check(lib.clipmi_text_encoder_backward_deep(m._handle, C.byref(t.dgrad[0]), d_text.data_ptr(), t.C, t.rows, self.n_ctx, self.depth - 1,
-                                                        t.d_embed.data_ptr(), self.d_deep.data_ptr() if self.depth > 1 else None, t.ws.data_ptr(),
+            check(lib.clipmi_text_encoder_backward_deep(m._handle, C.byref(t.dgrad[0]), d_text.data_ptr(), t.C, t.rows, self.nt, self.dt - 1,
+                                                        t.d_embed.data_ptr(), self.d_deep.data_ptr() if self.dt > 1 else None, t.ws.data_ptr(),
                                                         t.ws.numel(), t.stash.data_ptr(), t.stash.numel(),
                                                         None if stats_text is None else stats_text.data_ptr(), ops._stream()),
                   "clipmi_text_encoder_backward_deep")
-        return t.d_embed, (self.d_deep if self.depth > 1 else None), self.vision.backward(d_feats, stats_vision)
+        return t.d_embed, (self.d_deep if self.dt > 1 else None), self.vision.backward(d_feats, stats_vision)
 
     def one_call_workspace(self, B: int, scaled: bool = False) -> torch.Tensor:
-        sizer = lib.clipmi_maple_train_step_scaled_bytes if scaled else lib.clipmi_maple_train_step_bytes
-        need = sizer(self.model._handle, self.C, self.text.rows, B, self.n_ctx, self.depth)
+        """The one-call step's workspace: grown when a call needs more, never shrunk."""
+        need = self._step_bytes(B, scaled)
         if self.one_ws is None or self.one_ws.numel() < need:
             self.one_ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.model.device)
         return self.one_ws
+
+    def one_call_front(self, images: torch.Tensor, B: int, labels_d: torch.Tensor):
+        """The arguments every two-tower one-call symbol begins with, up to the labels."""
+        t, v = self.text, self.vision
+        return (self.model._handle, C.byref(t.dgrad[0]), C.byref(v.dgrad[0]), t.base.data_ptr(), _DT[t.base.dtype], t.eot.data_ptr(), t.C, t.rows,
+                images.data_ptr(), _DT[images.dtype], B, labels_d.data_ptr())
+
+    def stashes(self):
+        t, v = self.text, self.vision
+        return t.stash.data_ptr(), t.stash.numel(), v.stash.data_ptr(), v.stash.numel()
+
+
+class _Towers(_TwoTowers):
+    """MaPLe's towers: one rows / depth pair for both sides (``n_ctx``, ``depth``), the image tower's prompts coupled into ``vis``."""
+
+    def __init__(self, who: str, model, tokenized_prompts, learner_params, seq_rows: Optional[int], class_token_position: str = "end"):
+        self.n_ctx, self.depth = n_ctx, depth = _check_design(who, model, learner_params, class_token_position)
+        Cn, _, _, last = coopfit._check_prompts(who, model, tokenized_prompts, learner_params["ctx"])
+        super().__init__(who, model, tokenized_prompts, Cn, last, n_ctx, depth, n_ctx, depth, seq_rows)
+        dev = model.device
+        self.vis = torch.empty(depth, n_ctx, self.Dv, dtype=torch.float32, device=dev)
+        self.step_ws = torch.empty(max(lib.clipmi_maple_step_workspace_bytes(n_ctx, depth, self.Dt), 256), dtype=torch.uint8, device=dev)
+
+    def image_prompts(self, block: torch.Tensor) -> torch.Tensor:
+        return couple(block, self.n_ctx, self.depth, self.Dt, self.Dv, self.vis)
+
+    def _step_bytes(self, B: int, scaled: bool) -> int:
+        sizer = lib.clipmi_maple_train_step_scaled_bytes if scaled else lib.clipmi_maple_train_step_bytes
+        return sizer(self.model._handle, self.C, self.text.rows, B, self.n_ctx, self.depth)
 
 
 def gradients(model, learner_params: Dict[str, torch.Tensor], images: torch.Tensor, labels, tokenized_prompts, logit_scale: float = 4.6052,
@@ -226,15 +249,13 @@ def gradients(model, learner_params: Dict[str, torch.Tensor], images: torch.Tens
     if _is_dynamic(who, grad_scale):
         raise ValueError(f"{who}: grad_scale={DYNAMIC!r} belongs to a fit (MaPLeFitState, fit_prompt_learner); one gradient needs a number")
     gs = _check_grad_scale(who, grad_scale)
-    if not math.isfinite(logit_scale):
-        raise ValueError(f"{who}: logit_scale={logit_scale} (finite)")
+    scale = fitloop.exp_logit_scale(who, logit_scale)
     tw = _Towers(who, model, tokenized_prompts, learner_params, seq_rows, class_token_position)
     images = tw.vision.images(who, images)
     dev = images.device
     labels_d = fitloop.step_labels(who, labels, images.shape[0], tw.C, dev, "images")
     block = pack_block(learner_params, tw.depth, dev)
     text, feats = tw.forward(block, images)
-    scale = float(np.float32(math.exp(logit_scale)))
     st = torch.zeros(4, dtype=torch.int64, device=dev) if return_operand_stats else None
     sv = torch.zeros(4, dtype=torch.int64, device=dev) if return_operand_stats else None
     loss, d_feats, d_text = maple_head(feats, labels_d, text, scale, gs)
@@ -256,7 +277,7 @@ def features(model, learner_params: Dict[str, torch.Tensor], images: torch.Tenso
     return text.clone(), feats.clone()
 
 
-class MaPLeFitState(fitmonitor.ImageMonitored):
+class MaPLeFitState(vptfit._BlockFitState):
     """The training state of MaPLe's prompt learner: the fp32 master ``block``, SGD's momentum buffer, both towers' stashes and the number
     of steps taken.  ``step`` enqueues one forward, backward and update and does not synchronise.  ``params()`` names the block's views.
     ``validate`` scores validation images on the device (``start_monitor``, ``monitor``, ``best_params``, ``val_row_results``; DESIGN.md
@@ -267,26 +288,15 @@ class MaPLeFitState(fitmonitor.ImageMonitored):
                  dampening: float = 0.0, nesterov: bool = False, weight_decay: float = 5e-4, grad_scale: float = DEFAULT_GRAD_SCALE,
                  seq_rows: Optional[int] = None, class_token_position: str = "end", scaler: Optional[dict] = None):
         who = "MaPLeFitState"
-        self.dynamic, self.grad_scale, self.scaler = _scale_args(who, grad_scale, scaler)
-        fitloop.check_sgd(who, momentum, dampening, weight_decay, nesterov)
-        if not math.isfinite(logit_scale):
-            raise ValueError(f"{who}: logit_scale={logit_scale} (finite)")
+        self._init_optimiser(who, logit_scale, momentum, dampening, nesterov, weight_decay, grad_scale, scaler)
         self.towers = _Towers(who, model, tokenized_prompts, learner_params, seq_rows, class_token_position)
         self.C = self.towers.C
-        self.block = pack_block(learner_params, self.towers.depth, model.device)
-        self.buf = torch.zeros_like(self.block) if momentum != 0.0 else None
-        self.scale = float(np.float32(math.exp(logit_scale)))
-        self.momentum, self.dampening, self.nesterov, self.weight_decay = momentum, dampening, nesterov, weight_decay
-        self.steps = 0
-        self._scaler = _BlockScaler(self.scaler, model.device) if self.dynamic else None
+        self._init_block(pack_block(learner_params, self.towers.depth, model.device))
         self._scaled_grad = torch.empty_like(self.block) if self.dynamic else None    # scale * gradient, as clipmi_maple_step leaves it
 
     def params(self, block: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
         t = self.towers
         return unpack_block(self.block if block is None else block, t.n_ctx, t.depth, t.Dt, t.Dv)
-
-    def _master(self) -> torch.Tensor:
-        return self.block
 
     def validate(self, val_images_or_loader, val_labels, epoch: int, val_batch_size: int = 32, one_call: bool = True) -> None:
         """Enqueue one validation of the current master block into slot ``epoch`` of the device history; no host read.  The text side's
@@ -296,80 +306,38 @@ class MaPLeFitState(fitmonitor.ImageMonitored):
         (``VPTFitState.validate`` has the rest: row results, finish, selection of the whole block, labels)."""
         who = "MaPLeFitState.validate"
         mon, tw = self._monitor_for(epoch), self.towers
+        vis = tw.image_prompts(self.block)
         text_n = ops.l2_normalize(tw.text_forward(self.block))
-        mon.validate(who, tw.vision, tw.vis, text_n, self.scale, val_images_or_loader, val_labels, epoch, val_batch_size, self.block, one_call)
+        mon.validate(who, tw.vision, vis, text_n, self.scale, val_images_or_loader, val_labels, epoch, val_batch_size, self.block, one_call)
 
     def best_params(self) -> Dict[str, torch.Tensor]:
         """The best slot on the device under ``params()``' names: the block of the best epoch so far, or the block ``start_monitor`` saw
         while no epoch has been taken."""
         return self.params(self._best_block("best_params"))
 
-    def scaler_state(self) -> dict:
-        """The dynamic scale's block as ``dict(scale, growth_tracker, skipped_steps, applied_steps, found_inf)`` (``found_inf``: of the
-        last step).  It waits for the steps enqueued so far: one synchronisation, the only read-back of the dynamic path."""
-        if not self.dynamic:
-            raise ValueError(f"MaPLeFitState.scaler_state: the state was made with a static grad_scale={self.grad_scale}")
-        return self._scaler.state()
+    def _vision(self):
+        return self.towers.vision
 
-    def step(self, images: torch.Tensor, labels, lr, want_loss: bool = False, one_call: bool = False) -> Optional[torch.Tensor]:
-        """One optimiser step on the batch ``images`` [B, 3, R, R] (preprocessed, fp16 or fp32, on the GPU) and ``labels`` [B] at the rate
-        ``lr``: an fp32 tensor of one element on the device is read where it lies; a Python number is uploaded on every call.  A label
-        tensor on the GPU is taken as it is -- a label outside [0, C) then makes the parameters NaN, it is never used as an address; host
-        labels are range-checked.  ``one_call``: the same launches through clipmi_maple_train_step, whose workspace holds both towers'.
-        Returns the batch loss, fp32 [1] on the device, when ``want_loss``.  Under ``grad_scale="dynamic"`` the head runs at
-        ``grad_scale = 1``, ``d_text`` and ``d_feats`` are multiplied by the device block's scale, clipmi_maple_step forms the gradient
-        without applying it and clipmi_block_step_scaled decides on the device whether the step is applied (one call:
-        clipmi_maple_train_step_scaled); a skipped step still counts in ``steps`` and still returns its loss; whether it was applied is in
-        ``scaler_state()``."""
-        who = "MaPLeFitState.step"
+    def _one_call(self, images, B, labels_d):
         tw = self.towers
-        t, v, m = tw.text, tw.vision, tw.model
-        images = v.images(who, images)
-        dev, B = images.device, images.shape[0]
-        labels_d = fitloop.step_labels(who, labels, B, self.C, dev, "images")
-        lr_d = ops._dev(fitloop.lr_operand(lr, dev), "lr", (torch.float32,))
-        first = self.steps == 0
-        sgd = (float(self.momentum), float(self.dampening), float(self.weight_decay), int(bool(self.nesterov)))
-        loss = torch.empty(1, dtype=torch.float32, device=dev)
-        if self.dynamic and one_call:
-            v.size(B, tower_ws=False)
-            ws, sc = tw.one_call_workspace(B, scaled=True), self._scaler
-            with m._launch_lock:
-                check(lib.clipmi_maple_train_step_scaled(m._handle, C.byref(t.dgrad[0]), C.byref(v.dgrad[0]), t.base.data_ptr(), _DT[t.base.dtype],
-                                                         t.eot.data_ptr(), t.C, t.rows, images.data_ptr(), _DT[images.dtype], B, labels_d.data_ptr(),
-                                                         self.block.data_ptr(), None if self.buf is None else self.buf.data_ptr(), tw.n_ctx, tw.depth,
-                                                         self.scale, sc.block.data_ptr(), *sc.args(), lr_d.data_ptr(), *sgd, loss.data_ptr(), None,
-                                                         ws.data_ptr(), ws.numel(), t.stash.data_ptr(), t.stash.numel(), v.stash.data_ptr(),
-                                                         v.stash.numel(), ops._stream()),
-                      "clipmi_maple_train_step_scaled")
-        elif self.dynamic:
-            text, feats = tw.forward(self.block, images)
-            _, d_feats, d_text = maple_head(feats, labels_d, text, self.scale, 1.0, loss)
-            ops.grad_scale_rows(d_text, self._scaler.block)
-            ops.grad_scale_rows(d_feats, self._scaler.block)
-            d_embed, d_deep, d_vis = tw.backward(d_text, d_feats)
-            check(lib.clipmi_maple_step(d_embed.data_ptr(), None if d_deep is None else d_deep.data_ptr(), d_vis.data_ptr(), self.block.data_ptr(), None,
-                                        self._scaled_grad.data_ptr(), 0, t.C, t.L, tw.n_ctx, tw.depth, tw.Dt, tw.Dv, 1.0, None, 0, *sgd,
-                                        tw.step_ws.data_ptr(), tw.step_ws.numel(), ops._stream()), "clipmi_maple_step")
-            self._scaler.step(self._scaled_grad, self.block, self.buf, lr_d, *sgd)
-        elif one_call:
-            v.size(B, tower_ws=False)
-            ws = tw.one_call_workspace(B)
-            with m._launch_lock:
-                check(lib.clipmi_maple_train_step(m._handle, C.byref(t.dgrad[0]), C.byref(v.dgrad[0]), t.base.data_ptr(), _DT[t.base.dtype], t.eot.data_ptr(),
-                                                  t.C, t.rows, images.data_ptr(), _DT[images.dtype], B, labels_d.data_ptr(), self.block.data_ptr(),
-                                                  None if self.buf is None else self.buf.data_ptr(), tw.n_ctx, tw.depth, self.scale, self.grad_scale,
-                                                  lr_d.data_ptr(), int(first), *sgd, loss.data_ptr(), None, ws.data_ptr(), ws.numel(),
-                                                  t.stash.data_ptr(), t.stash.numel(), v.stash.data_ptr(), v.stash.numel(), ops._stream()),
-                      "clipmi_maple_train_step")
-        else:
-            text, feats = tw.forward(self.block, images)
-            _, d_feats, d_text = maple_head(feats, labels_d, text, self.scale, self.grad_scale, loss)
-            d_embed, d_deep, d_vis = tw.backward(d_text, d_feats)
-            maple_step(d_embed, d_deep, d_vis, self.block, t.C, t.L, tw.n_ctx, tw.depth, tw.Dt, tw.Dv, self.grad_scale, self.buf, lr_d, first, *sgd,
-                       want_grad=False, ws=tw.step_ws)
-        self.steps += 1
-        return loss if want_loss else None
+        front = tw.one_call_front(images, B, labels_d) + (self.block.data_ptr(), None if self.buf is None else self.buf.data_ptr(), tw.n_ctx, tw.depth)
+        return "clipmi_maple_train_step", tw.one_call_workspace(B, self.dynamic), front, (), tw.stashes()
+
+    def _head(self, images, labels_d, grad_scale, loss):
+        text, feats = self.towers.forward(self.block, images)
+        _, d_feats, d_text = maple_head(feats, labels_d, text, self.scale, grad_scale, loss)
+        return d_text, d_feats
+
+    def _apply(self, outs, lr_d, first, sgd):
+        """Under the dynamic scale clipmi_maple_step leaves scale * gradient in ``_scaled_grad`` and applies nothing."""
+        tw = self.towers
+        d_embed, d_deep, d_vis = tw.backward(*outs)
+        grad, buf, gs, lr, first = (self._scaled_grad, None, 1.0, None, 0) if self.dynamic else (None, self.buf, self.grad_scale, lr_d, first)
+        check(lib.clipmi_maple_step(d_embed.data_ptr(), None if d_deep is None else d_deep.data_ptr(), d_vis.data_ptr(), self.block.data_ptr(),
+                                    None if buf is None else buf.data_ptr(), None if grad is None else grad.data_ptr(), int(not self.dynamic), tw.C,
+                                    tw.text.L, tw.n_ctx, tw.depth, tw.Dt, tw.Dv, gs, None if lr is None else lr.data_ptr(), int(first), *sgd,
+                                    tw.step_ws.data_ptr(), tw.step_ws.numel(), ops._stream()), "clipmi_maple_step")
+        return grad
 
 
 def init_learner_params(model, n_ctx: int = 2, depth: int = 9, seed: int = 0) -> Dict[str, torch.Tensor]:

@@ -19,11 +19,9 @@ import torch
 import torch.nn as nn
 
 from . import _lib, ops
-from ._lib import F16, F32, check, lib
+from ._lib import _DT, F16, F32, check, lib
 from .resnet import ModifiedResNet
 from .synthetic import ClipGeometry, geometry_from_state_dict, resnet_config_from_state_dict
-
-_DT = {torch.float16: F16, torch.float32: F32}
 
 
 # --------------------------------------------------------------------------------------------------------------------

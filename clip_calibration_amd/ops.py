@@ -14,9 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import F16, F32, check, lib
-
-_DT = {torch.float16: F16, torch.float32: F32}
+from ._lib import _DT, F16, F32, check, lib
 
 
 def _stream() -> int:
@@ -1047,11 +1045,8 @@ def layernorm_backward(x: torch.Tensor, gamma: torch.Tensor, dy: torch.Tensor, g
         raise ValueError("layernorm_backward: fewer rows in x or g than in dy")
     if row_idx is not None and row_idx.shape != (rows,):
         raise ValueError("layernorm_backward: one row index per row of dy")
-    check(lib.clipmi_layernorm_backward(x.data_ptr(), x.stride(0), pi, gamma.data_ptr(), dy.data_ptr(), _DTC[dy.dtype], g.data_ptr(),
+    check(lib.clipmi_layernorm_backward(x.data_ptr(), x.stride(0), pi, gamma.data_ptr(), dy.data_ptr(), _DT[dy.dtype], g.data_ptr(),
                                         None if g16 is None else g16.data_ptr(), rows, D, float(eps), _stream()), "clipmi_layernorm_backward")
-
-
-_DTC = {torch.float16: F16, torch.float32: F32}
 
 
 def quickgelu_backward(h: torch.Tensor, d_a: torch.Tensor) -> torch.Tensor:

@@ -18,12 +18,11 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import check, lib
+from ._lib import _DT, check, lib
 
 CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)     # clip/clip.py:80
 CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
 _FILTERS = {"bicubic": _lib.FILTER_BICUBIC, "bilinear": _lib.FILTER_BILINEAR}
-_DTYPES = {torch.float16: _lib.F16, torch.float32: _lib.F32}
 
 
 def resize_geometry(height: int, width: int, n_px: int) -> Tuple[int, int, int, int]:
@@ -135,7 +134,7 @@ class Preprocess:
                  dtype: torch.dtype = torch.float16, normalize: bool = True):
         if interpolation not in _FILTERS:
             raise ValueError(f"Preprocess: interpolation {interpolation!r} is not supported (bicubic, bilinear)")
-        if dtype not in _DTYPES:
+        if dtype not in _DT:
             raise TypeError(f"Preprocess: dtype must be torch.float16 or torch.float32, got {dtype}")
         if not 1 <= int(n_px) <= 4096:
             raise ValueError(f"Preprocess: n_px = {n_px} outside 1 .. 4096")
@@ -231,7 +230,7 @@ class Preprocess:
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)   # stream-ordered by the caching allocator: no reuse across streams in flight
         stream = torch.cuda.current_stream(dev)
         check(lib.clipmi_preprocess(buf.data_ptr(), extent, host.data_ptr(), B, n, filt, self._table(dev).data_ptr(), out.data_ptr(),
-                                    _DTYPES[self.dtype], ws.data_ptr(), nbytes, stream.cuda_stream), "clipmi_preprocess")
+                                    _DT[self.dtype], ws.data_ptr(), nbytes, stream.cuda_stream), "clipmi_preprocess")
         ev = torch.cuda.Event()
         ev.record(stream)
         self._inflight.append((host, ev))

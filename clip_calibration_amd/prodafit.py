@@ -194,10 +194,6 @@ class _ProDATower(_Tower):
         return self.step_ws
 
 
-def _scale(logit_scale: float) -> float:
-    return float(np.float32(math.exp(logit_scale)))
-
-
 def context_gradient(clip_model, tokenized_prompts, ctx: torch.Tensor, features: torch.Tensor, labels, sel=None, name_lens=None, alpha: float = 0.1,
                      logit_scale: float = 4.6052, grad_scale: float = DEFAULT_GRAD_SCALE, seq_rows: Optional[int] = None, return_parts: bool = False):
     """``(loss, grad)`` of ProDA's training loss (module docstring) with respect to ``ctx`` [P, n_ctx, D] on the GPU: loss fp32 [1], grad
@@ -218,8 +214,7 @@ def context_gradient(clip_model, tokenized_prompts, ctx: torch.Tensor, features:
     if _is_dynamic(who, grad_scale):
         raise ValueError(f"{who}: grad_scale={DYNAMIC!r} belongs to a fit (ProDAFitState, fit_context); one gradient needs a number")
     gs = _check_grad_scale(who, grad_scale)
-    if not math.isfinite(logit_scale):
-        raise ValueError(f"{who}: logit_scale={logit_scale} (finite)")
+    scale = fitloop.exp_logit_scale(who, logit_scale)
     E = int(clip_model.geometry.embed_dim)
     labels_d = _check_batch(who, features, labels, Cn, E)
     _need_gpu(features, "features")
@@ -227,7 +222,7 @@ def context_gradient(clip_model, tokenized_prompts, ctx: torch.Tensor, features:
     dev = features.device
     sel_d = torch.from_numpy(sel_h).to(dev)
     text = tower.forward(fitloop.master(ctx, dev), sel_d)
-    losses, d_text = ops.proda_head(features, labels_d, text, Cn, len(sel_h), _scale(logit_scale), gs, alpha)
+    losses, d_text = ops.proda_head(features, labels_d, text, Cn, len(sel_h), scale, gs, alpha)
     d_embed = tower.backward(d_text)
     grad = ops.proda_ctx_step(d_embed, sel_d, tower.pos, tower.name_lens, n_ctx, gs)
     if not return_parts:
@@ -260,13 +255,11 @@ class ProDAFitState(fitmonitor.Monitored):
         self.alpha = _check_alpha(who, alpha)
         self.dynamic, self.grad_scale, self.scaler = _scale_args(who, grad_scale, scaler)
         fitloop.check_sgd(who, momentum, dampening, weight_decay, nesterov)
-        if not math.isfinite(logit_scale):
-            raise ValueError(f"{who}: logit_scale={logit_scale} (finite)")
+        self.scale = fitloop.exp_logit_scale(who, logit_scale)
         self.tower = _ProDATower(who, clip_model, ids_all, self.C, self.P, self.Pb, self.n_ctx, nl, last, seq_rows)
         dev = clip_model.device
         self.ctx = fitloop.master(ctx, dev)
         self.buf = torch.zeros_like(self.ctx) if momentum != 0.0 else None
-        self.scale = _scale(logit_scale)
         self.momentum, self.dampening, self.nesterov, self.weight_decay = momentum, dampening, nesterov, weight_decay
         self.generator = generator if generator is not None else torch.Generator().manual_seed(0)
         self.pos_host = positions(self.P)

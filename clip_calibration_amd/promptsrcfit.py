@@ -44,7 +44,6 @@ Not covered: ``nn.DataParallel``, the ResNet towers, class-token positions other
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 from typing import Dict, Optional, Sequence, Tuple
 
@@ -52,9 +51,9 @@ import numpy as np
 import torch
 
 from . import _lib, fitloop, fitmonitor, ops
-from ._lib import check, lib
-from . import coopfit, vptfit
-from .coopfit import DYNAMIC, _BlockScaler, _check_grad_scale, _is_dynamic, _scale_args
+from ._lib import _DT, check, lib
+from . import coopfit, maplefit, vptfit
+from .coopfit import DYNAMIC, _check_grad_scale, _is_dynamic
 from .fitloop import _need_gpu
 
 # 2^10, one power of two for both towers' backwards, measured at ViT-B/16 with synthetic weights, nt = nv = 4, depths 9 / 9, batch 4, 100
@@ -66,8 +65,6 @@ from .fitloop import _need_gpu
 DEFAULT_GRAD_SCALE = 1024.0
 METHODS = ("promptsrc", "ivlp")
 LOSS_NAMES = ("total", "ce", "text_l1", "image_l1", "logit_kl")
-
-_DT = {torch.float16: _lib.F16, torch.float32: _lib.F32}
 
 
 def param_names(dt: int, dv: int):
@@ -231,25 +228,22 @@ def gpa_accumulate(block: torch.Tensor, gpa: torch.Tensor, weight: float, first:
     return gpa
 
 
-class _Towers:
-    """Both frozen towers in training mode for one prompt set -- coopfit's text tower driven with deep prompts and vptfit's image tower --
-    and the frozen plain image forward on the same handle."""
+class _Towers(maplefit._TwoTowers):
+    """PromptSRC's and IVLP's towers: the image tower's prompts are the block's own tail, and the frozen plain image forward runs on the
+    same handle."""
 
     def __init__(self, who: str, model, tokenized_prompts, params, seq_rows: Optional[int], class_token_position: str = "end"):
-        self.nt, self.dt, self.nv, self.dv = _check_design(who, model, params, class_token_position)
-        Cn, last = _check_ids(who, model, tokenized_prompts, self.nt)
-        self.model, self.C = model, Cn
-        self.text = coopfit._Tower(who, model, tokenized_prompts, Cn, self.nt, False, last, seq_rows)
-        self.vision = vptfit._Tower(who, model, self.dv, self.nv)
-        g = model.geometry
-        self.Dt, self.Dv, self.E = int(g.transformer_width), int(g.vision_width), int(g.embed_dim)
-        dev = model.device
-        self.text_floats = self.dt * self.nt * self.Dt
-        self.d_deep = torch.empty(max(self.dt - 1, 1), self.nt, self.Dt, dtype=torch.float32, device=dev)
-        self.one_ws = self.zs = self.head_ws = None
+        nt, dt, nv, dv = _check_design(who, model, params, class_token_position)
+        Cn, last = _check_ids(who, model, tokenized_prompts, nt)
+        super().__init__(who, model, tokenized_prompts, Cn, last, nt, dt, nv, dv, seq_rows)
+        self.text_floats = dt * nt * self.Dt
+        self.zs = self.head_ws = None
 
     def shape(self):
         return self.nt, self.dt, self.Dt, self.nv, self.dv, self.Dv
+
+    def image_prompts(self, block: torch.Tensor) -> torch.Tensor:
+        return block[self.text_floats:]
 
     def frozen(self, images: torch.Tensor) -> torch.Tensor:
         """The frozen plain tower's features fp32 [B, E]: no prompt hook whatever the model carries, fp32 residual stream."""
@@ -263,45 +257,16 @@ class _Towers:
                                           _lib.CALL_STREAM_F32, ops._stream()), "clipmi_encode_image")
         return self.zs[:B]
 
-    def text_forward(self, block: torch.Tensor) -> torch.Tensor:
-        """The text half of ``forward``: the text features [C, E] at the block."""
-        t, m = self.text, self.model
-        deep = block.data_ptr() + 4 * self.nt * self.Dt if self.dt > 1 else None
-        with m._launch_lock:
-            check(lib.clipmi_text_encoder_train_deep(m._handle, t.base.data_ptr(), _DT[t.base.dtype], block.data_ptr(), self.nt, 0, t.eot.data_ptr(), t.C,
-                                                     t.rows, deep, self.dt - 1, t.text.data_ptr(), t.ws.data_ptr(), t.ws.numel(), t.stash.data_ptr(),
-                                                     t.stash.numel(), _lib.CALL_DEFAULT, ops._stream()), "clipmi_text_encoder_train_deep")
-        return t.text
-
-    def forward(self, block: torch.Tensor, images: torch.Tensor):
-        """(text features [C, E], image features [B, E]) at the block: text forward with deep prompts, image forward."""
-        return self.text_forward(block), self.vision.forward(images, block[self.text_floats:])
-
-    def backward(self, d_text: torch.Tensor, d_feats: torch.Tensor, stats_text: Optional[torch.Tensor] = None, stats_vision: Optional[torch.Tensor] = None):
-        """(d_embed, d_deep, d_vis): the text tower's backward, then the image tower's."""
-        t, m = self.text, self.model
-        with m._launch_lock:
-            check(lib.clipmi_text_encoder_backward_deep(m._handle, C.byref(t.dgrad[0]), d_text.data_ptr(), t.C, t.rows, self.nt, self.dt - 1,
-                                                        t.d_embed.data_ptr(), self.d_deep.data_ptr() if self.dt > 1 else None, t.ws.data_ptr(),
-                                                        t.ws.numel(), t.stash.data_ptr(), t.stash.numel(),
-                                                        None if stats_text is None else stats_text.data_ptr(), ops._stream()),
-                  "clipmi_text_encoder_backward_deep")
-        return t.d_embed, (self.d_deep if self.dt > 1 else None), self.vision.backward(d_feats, stats_vision)
-
     def head_workspace(self, B: int) -> torch.Tensor:
         need = lib.clipmi_promptsrc_head_workspace_bytes(B, self.E, self.C)
         if self.head_ws is None or self.head_ws.numel() < need:
             self.head_ws = torch.empty(max(need, 8), dtype=torch.uint8, device=self.model.device)
         return self.head_ws
 
-    def one_call_workspace(self, B: int, scaled: bool = False) -> torch.Tensor:
+    def _step_bytes(self, B: int, scaled: bool) -> int:
         if scaled:
-            need = lib.clipmi_promptsrc_train_step_scaled_bytes(self.model._handle, self.C, self.text.rows, B, self.nt, self.dt, self.nv, self.dv)
-        else:
-            need = lib.clipmi_promptsrc_train_step_bytes(self.model._handle, self.C, self.text.rows, B, self.nt, self.dt, self.nv)
-        if self.one_ws is None or self.one_ws.numel() < need:
-            self.one_ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.model.device)
-        return self.one_ws
+            return lib.clipmi_promptsrc_train_step_scaled_bytes(self.model._handle, self.C, self.text.rows, B, self.nt, self.dt, self.nv, self.dv)
+        return lib.clipmi_promptsrc_train_step_bytes(self.model._handle, self.C, self.text.rows, B, self.nt, self.dt, self.nv)
 
 
 def _method_weights(who: str, method: str, w_text: float, w_image: float, w_logit: float):
@@ -324,8 +289,7 @@ def gradients(model, params: Dict[str, torch.Tensor], images: torch.Tensor, labe
         raise ValueError(f"{who}: grad_scale={DYNAMIC!r} belongs to a fit (PromptSRCFitState, fit_prompts); one gradient needs a number")
     gs = _check_grad_scale(who, grad_scale)
     wt, wi, wl = _method_weights(who, method, w_text, w_image, w_logit)
-    if not math.isfinite(logit_scale):
-        raise ValueError(f"{who}: logit_scale={logit_scale} (finite)")
+    scale = fitloop.exp_logit_scale(who, logit_scale)
     tw = _Towers(who, model, tokenized_prompts, params, seq_rows, class_token_position)
     teacher = _check_teacher(who, model, teacher, tw.C)
     images = tw.vision.images(who, images)
@@ -334,7 +298,6 @@ def gradients(model, params: Dict[str, torch.Tensor], images: torch.Tensor, labe
     block = pack_block(params, dev)
     zs = tw.frozen(images)
     text, feats = tw.forward(block, images)
-    scale = float(np.float32(math.exp(logit_scale)))
     st = torch.zeros(4, dtype=torch.int64, device=dev) if return_operand_stats else None
     sv = torch.zeros(4, dtype=torch.int64, device=dev) if return_operand_stats else None
     losses, d_feats, d_text = promptsrc_head(feats, zs, text, teacher, labels_d, scale, gs, wt, wi, wl)
@@ -348,41 +311,30 @@ def gradients(model, params: Dict[str, torch.Tensor], images: torch.Tensor, labe
     return out
 
 
-class PromptSRCFitState(fitmonitor.ImageMonitored):
+class PromptSRCFitState(vptfit._BlockFitState):
     """The training state of PromptSRC's (or IVLP's) prompts: the fp32 master ``block``, SGD's momentum buffer, GPA's running sum, both
     towers' stashes and the number of steps taken.  ``step`` enqueues one forward, backward and update, ``end_epoch`` one accumulation;
     neither synchronises.  ``params()`` names the block's views.  ``validate`` scores validation images on the device
     (``start_monitor``, ``monitor``, ``best_params``, ``val_row_results``; DESIGN.md "Fit monitor", "The image-tower fits")."""
-    _who = "PromptSRCFitState"
+    _who, _n_losses = "PromptSRCFitState", 5
 
     def __init__(self, model, tokenized_prompts, params: Dict[str, torch.Tensor], teacher: torch.Tensor, logit_scale: float = 4.6052,
                  w_text: float = 25.0, w_image: float = 10.0, w_logit: float = 1.0, momentum: float = 0.9, dampening: float = 0.0, nesterov: bool = False,
                  weight_decay: float = 5e-4, grad_scale: float = DEFAULT_GRAD_SCALE, seq_rows: Optional[int] = None, method: str = "promptsrc",
                  class_token_position: str = "end", scaler: Optional[dict] = None):
         who = "PromptSRCFitState"
-        self.dynamic, self.grad_scale, self.scaler = _scale_args(who, grad_scale, scaler)
-        fitloop.check_sgd(who, momentum, dampening, weight_decay, nesterov)
+        self._init_optimiser(who, logit_scale, momentum, dampening, nesterov, weight_decay, grad_scale, scaler)
         self.weights = _method_weights(who, method, w_text, w_image, w_logit)
-        if not math.isfinite(logit_scale):
-            raise ValueError(f"{who}: logit_scale={logit_scale} (finite)")
         self.towers = _Towers(who, model, tokenized_prompts, params, seq_rows, class_token_position)
         self.C = self.towers.C
         self.teacher = _check_teacher(who, model, teacher, self.C)
-        self.block = pack_block(params, model.device)
-        self.buf = torch.zeros_like(self.block) if momentum != 0.0 else None
+        self._init_block(pack_block(params, model.device))
         self.gpa = None
         self.epochs_seen = 0
-        self.scale = float(np.float32(math.exp(logit_scale)))
-        self.momentum, self.dampening, self.nesterov, self.weight_decay = momentum, dampening, nesterov, weight_decay
-        self.steps = 0
-        self._scaler = _BlockScaler(self.scaler, model.device) if self.dynamic else None
         self._scaled_grad = torch.empty_like(self.block) if self.dynamic else None    # scale * gradient, as clipmi_promptsrc_step leaves it
 
     def params(self, block: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
         return unpack_block(self.block if block is None else block, *self.towers.shape())
-
-    def _master(self) -> torch.Tensor:
-        return self.block
 
     def validate(self, val_images_or_loader, val_labels, epoch: int, val_batch_size: int = 32, one_call: bool = True) -> None:
         """Enqueue one validation of the master block as it stands into slot ``epoch`` of the device history; no host read.  The text
@@ -394,7 +346,7 @@ class PromptSRCFitState(fitmonitor.ImageMonitored):
         who = "PromptSRCFitState.validate"
         mon, tw = self._monitor_for(epoch), self.towers
         text_n = ops.l2_normalize(tw.text_forward(self.block))
-        mon.validate(who, tw.vision, self.block[tw.text_floats:], text_n, self.scale, val_images_or_loader, val_labels, epoch, val_batch_size,
+        mon.validate(who, tw.vision, tw.image_prompts(self.block), text_n, self.scale, val_images_or_loader, val_labels, epoch, val_batch_size,
                      self.block, one_call)
 
     def best_params(self) -> Dict[str, torch.Tensor]:
@@ -402,76 +354,34 @@ class PromptSRCFitState(fitmonitor.ImageMonitored):
         while no epoch has been taken.  GPA's running sum, the optimiser state and the scaler block are not part of it."""
         return self.params(self._best_block("best_params"))
 
-    def scaler_state(self) -> dict:
-        """The dynamic scale's block as ``dict(scale, growth_tracker, skipped_steps, applied_steps, found_inf)`` (``found_inf``: of the
-        last step).  It waits for the steps enqueued so far: one synchronisation, the only read-back of the dynamic path."""
-        if not self.dynamic:
-            raise ValueError(f"PromptSRCFitState.scaler_state: the state was made with a static grad_scale={self.grad_scale}")
-        return self._scaler.state()
+    def _vision(self):
+        return self.towers.vision
 
-    def step(self, images: torch.Tensor, labels, lr, want_loss: bool = False, one_call: bool = False) -> Optional[torch.Tensor]:
-        """One optimiser step on the batch ``images`` [B, 3, R, R] (preprocessed, fp16 or fp32, on the GPU) and ``labels`` [B] at the rate
-        ``lr``: an fp32 tensor of one element on the device is read where it lies; a Python number is uploaded on every call.  A label
-        tensor on the GPU is taken as it is -- a label outside [0, C) then makes the parameters NaN, it is never used as an address; host
-        labels are range-checked.  ``one_call``: the same launches through clipmi_promptsrc_train_step, whose workspace holds both
-        towers'.  Returns the batch's total loss, fp32 [1] on the device (a view of the five terms kept in ``last_losses``), when
-        ``want_loss``.  Under ``grad_scale="dynamic"`` the head runs at ``grad_scale = 1``, ``d_text`` and ``d_feats`` are multiplied by
-        the device block's scale, clipmi_promptsrc_step forms the gradient without applying it and clipmi_block_step_scaled decides on the
-        device whether the step is applied (one call: clipmi_promptsrc_train_step_scaled); a skipped step still counts in ``steps`` and
-        still returns its losses; whether it was applied is in ``scaler_state()``."""
-        who = "PromptSRCFitState.step"
+    def _one_call(self, images, B, labels_d):
         tw = self.towers
-        t, v, m = tw.text, tw.vision, tw.model
-        images = v.images(who, images)
-        dev, B = images.device, images.shape[0]
-        labels_d = fitloop.step_labels(who, labels, B, self.C, dev, "images")
-        lr_d = ops._dev(fitloop.lr_operand(lr, dev), "lr", (torch.float32,))
-        first = self.steps == 0
-        sgd = (float(self.momentum), float(self.dampening), float(self.weight_decay), int(bool(self.nesterov)))
-        losses = torch.empty(5, dtype=torch.float32, device=dev)
-        if self.dynamic and one_call:
-            v.size(B, tower_ws=False)
-            ws, sc = tw.one_call_workspace(B, scaled=True), self._scaler
-            with m._launch_lock:
-                check(lib.clipmi_promptsrc_train_step_scaled(m._handle, C.byref(t.dgrad[0]), C.byref(v.dgrad[0]), t.base.data_ptr(), _DT[t.base.dtype],
-                                                             t.eot.data_ptr(), t.C, t.rows, images.data_ptr(), _DT[images.dtype], B, labels_d.data_ptr(),
-                                                             self.teacher.data_ptr(), self.block.data_ptr(),
-                                                             None if self.buf is None else self.buf.data_ptr(), tw.nt, tw.dt, tw.nv, tw.dv, self.scale,
-                                                             sc.block.data_ptr(), *sc.args(), *self.weights, lr_d.data_ptr(), *sgd, losses.data_ptr(), None,
-                                                             ws.data_ptr(), ws.numel(), t.stash.data_ptr(), t.stash.numel(), v.stash.data_ptr(),
-                                                             v.stash.numel(), ops._stream()), "clipmi_promptsrc_train_step_scaled")
-        elif self.dynamic:
-            zs = tw.frozen(images)
-            text, feats = tw.forward(self.block, images)
-            _, d_feats, d_text = promptsrc_head(feats, zs, text, self.teacher, labels_d, self.scale, 1.0, *self.weights, losses=losses,
-                                                ws=tw.head_workspace(B))
-            ops.grad_scale_rows(d_text, self._scaler.block)
-            ops.grad_scale_rows(d_feats, self._scaler.block)
-            d_embed, d_deep, d_vis = tw.backward(d_text, d_feats)
-            check(lib.clipmi_promptsrc_step(d_embed.data_ptr(), None if d_deep is None else d_deep.data_ptr(), d_vis.data_ptr(), self.block.data_ptr(),
-                                            None, self._scaled_grad.data_ptr(), 0, t.C, t.L, *tw.shape(), 1.0, None, 0, *sgd, ops._stream()),
-                  "clipmi_promptsrc_step")
-            self._scaler.step(self._scaled_grad, self.block, self.buf, lr_d, *sgd)
-        elif one_call:
-            v.size(B, tower_ws=False)
-            ws = tw.one_call_workspace(B)
-            with m._launch_lock:
-                check(lib.clipmi_promptsrc_train_step(m._handle, C.byref(t.dgrad[0]), C.byref(v.dgrad[0]), t.base.data_ptr(), _DT[t.base.dtype],
-                                                      t.eot.data_ptr(), t.C, t.rows, images.data_ptr(), _DT[images.dtype], B, labels_d.data_ptr(),
-                                                      self.teacher.data_ptr(), self.block.data_ptr(), None if self.buf is None else self.buf.data_ptr(),
-                                                      tw.nt, tw.dt, tw.nv, tw.dv, self.scale, self.grad_scale, *self.weights, lr_d.data_ptr(), int(first),
-                                                      *sgd, losses.data_ptr(), None, ws.data_ptr(), ws.numel(), t.stash.data_ptr(), t.stash.numel(),
-                                                      v.stash.data_ptr(), v.stash.numel(), ops._stream()), "clipmi_promptsrc_train_step")
-        else:
-            zs = tw.frozen(images)
-            text, feats = tw.forward(self.block, images)
-            _, d_feats, d_text = promptsrc_head(feats, zs, text, self.teacher, labels_d, self.scale, self.grad_scale, *self.weights, losses=losses,
-                                                ws=tw.head_workspace(B))
-            d_embed, d_deep, d_vis = tw.backward(d_text, d_feats)
-            promptsrc_step(d_embed, d_deep, d_vis, self.block, t.C, t.L, *tw.shape(), self.grad_scale, self.buf, lr_d, first, *sgd, want_grad=False)
-        self.steps += 1
-        self.last_losses = losses
-        return losses[:1] if want_loss else None
+        front = tw.one_call_front(images, B, labels_d) + (self.teacher.data_ptr(), self.block.data_ptr(),
+                                                          None if self.buf is None else self.buf.data_ptr(), tw.nt, tw.dt, tw.nv, tw.dv)
+        return "clipmi_promptsrc_train_step", tw.one_call_workspace(B, self.dynamic), front, self.weights, tw.stashes()
+
+    def _head(self, images, labels_d, grad_scale, losses):
+        """The frozen plain tower first; ``losses`` (kept in ``last_losses``): total, CE, text L1, image L1, logit KL."""
+        tw = self.towers
+        zs = tw.frozen(images)
+        text, feats = tw.forward(self.block, images)
+        _, d_feats, d_text = promptsrc_head(feats, zs, text, self.teacher, labels_d, self.scale, grad_scale, *self.weights, losses=losses,
+                                            ws=tw.head_workspace(images.shape[0]))
+        return d_text, d_feats
+
+    def _apply(self, outs, lr_d, first, sgd):
+        """Under the dynamic scale clipmi_promptsrc_step leaves scale * gradient in ``_scaled_grad`` and applies nothing."""
+        tw = self.towers
+        d_embed, d_deep, d_vis = tw.backward(*outs)
+        grad, buf, gs, lr, first = (self._scaled_grad, None, 1.0, None, 0) if self.dynamic else (None, self.buf, self.grad_scale, lr_d, first)
+        check(lib.clipmi_promptsrc_step(d_embed.data_ptr(), None if d_deep is None else d_deep.data_ptr(), d_vis.data_ptr(), self.block.data_ptr(),
+                                        None if buf is None else buf.data_ptr(), None if grad is None else grad.data_ptr(), int(not self.dynamic), tw.C,
+                                        tw.text.L, *tw.shape(), gs, None if lr is None else lr.data_ptr(), int(first), *sgd, ops._stream()),
+              "clipmi_promptsrc_step")
+        return grad
 
     def end_epoch(self, weight: float) -> None:
         """GPA: add ``weight`` times the block as it stands to the running sum (one launch; the first call initialises the sum)."""

@@ -41,15 +41,13 @@ ResNet towers.
 from __future__ import annotations
 
 import ctypes as C
-import math
 from typing import Optional, Sequence
 
-import numpy as np
 import torch
 
 from . import _lib, fitloop, fitmonitor, ops
-from ._lib import check, lib
-from .coopfit import DYNAMIC, _BlockScaler, _check_grad_scale, _is_dynamic, _scale_args, operand_stats_dict
+from ._lib import _DT, check, lib
+from .coopfit import DYNAMIC, _BlockScaler, _pack_dgrad, _check_grad_scale, _is_dynamic, _scale_args, operand_stats_dict
 from .fitloop import _need_gpu
 
 # 2^12: CoOp's value (profiles/coopfit_parity.txt) holds for the image tower's backward at the ViT-B/16 geometry as well
@@ -80,8 +78,6 @@ def stash_bytes(model, batch: int, n_ctx: int):
     wsb, stb = C.c_size_t(0), C.c_size_t(0)
     check(lib.clipmi_vision_train_bytes(model._handle, int(batch), int(n_ctx), C.byref(wsb), C.byref(stb)), "clipmi_vision_train_bytes")
     return wsb.value, stb.value
-
-_DT = {torch.float16: _lib.F16, torch.float32: _lib.F32}
 
 
 def model_prompts(model) -> torch.Tensor:
@@ -118,27 +114,7 @@ def _dgrad(model):
     """The transposed fp16 copies of the frozen image tower's weights (clipmi_vision_dgrad), packed once per bound model and again when a
     vision weight's version moves."""
     model._ensure_bound()
-    blocks = list(model.visual.transformer.resblocks)
-    ws = [model.visual.proj] + [w for b in blocks for w in (b.attn.in_proj_weight, b.attn.out_proj.weight, b.mlp.c_fc.weight, b.mlp.c_proj.weight)]
-    key = (id(model._bound),) + tuple((w.data_ptr(), w._version) for w in ws)
-    hit = model.__dict__.get("_vpt_dgrad")
-    if hit is not None and hit[0] == key:
-        return hit[1]
-    keep = []
-
-    def t16(w):
-        t = w.detach().to(torch.float16).t().contiguous()
-        keep.append(t)
-        return t.data_ptr()
-
-    arr = (_lib.BlockDgrad * len(blocks))()
-    for i, b in enumerate(blocks):
-        arr[i] = _lib.BlockDgrad(t16(b.attn.in_proj_weight), t16(b.attn.out_proj.weight), t16(b.mlp.c_fc.weight), t16(b.mlp.c_proj.weight))
-    proj = model.visual.proj.detach().to(torch.float16).contiguous()
-    keep.append(proj)
-    vd = _lib.VisionDgrad(proj.data_ptr(), arr)
-    model.__dict__["_vpt_dgrad"] = (key, (vd, arr, keep))
-    return vd, arr, keep
+    return _pack_dgrad(model, model.visual.transformer.resblocks, model.visual.proj, _lib.VisionDgrad, "_vpt_dgrad")
 
 
 def _check_text(who: str, model, text_features) -> torch.Tensor:
@@ -280,8 +256,7 @@ def prompt_gradient(model, prompts: torch.Tensor, images: torch.Tensor, labels, 
     if _is_dynamic(who, grad_scale):
         raise ValueError(f"{who}: grad_scale={DYNAMIC!r} belongs to a fit (VPTFitState, fit_prompts); one gradient needs a number")
     gs = _check_grad_scale(who, grad_scale)
-    if not math.isfinite(logit_scale):
-        raise ValueError(f"{who}: logit_scale={logit_scale} (finite)")
+    scale = fitloop.exp_logit_scale(who, logit_scale)
     text = _check_text(who, model, text_features)
     tower = _Tower(who, model, depth, n_ctx)
     images = tower.images(who, images)
@@ -289,7 +264,6 @@ def prompt_gradient(model, prompts: torch.Tensor, images: torch.Tensor, labels, 
     labels_d = fitloop.step_labels(who, labels, images.shape[0], text.shape[0], dev, "images")
     master = fitloop.master(prompts, dev)
     feats = tower.forward(images, master, flags)
-    scale = float(np.float32(math.exp(logit_scale)))
     stats = torch.zeros(4, dtype=torch.int64, device=dev) if return_operand_stats else None
     loss, d_feats = vpt_head(feats, labels_d, text, scale, gs)
     grad = vpt_step(tower.backward(d_feats, stats), gs)
@@ -308,12 +282,86 @@ def image_features(model, prompts: torch.Tensor, images: torch.Tensor) -> torch.
     return tower.forward(images, fitloop.master(prompts, images.device)).clone()
 
 
-class VPTFitState(fitmonitor.ImageMonitored):
+class _BlockFitState(fitmonitor.ImageMonitored):
+    """What the states of the fits through the image tower share (VPTFitState, maplefit.MaPLeFitState, promptsrcfit.PromptSRCFitState): one
+    fp32 master block under ``_master_name``, SGD's arguments and momentum buffer, the static or dynamic loss scale and the one ``step``.
+    A state supplies ``_vision`` (the image tower), ``_one_call`` (its one-call symbol and that symbol's own arguments), ``_head`` (forward
+    and head at a grad_scale) and ``_apply`` (backward and the block's step)."""
+    _master_name = "block"
+    _n_losses = 1
+
+    def _init_optimiser(self, who: str, logit_scale: float, momentum: float, dampening: float, nesterov: bool, weight_decay: float, grad_scale, scaler) -> None:
+        """The refusals that need no model, in the order every state has made them."""
+        self.dynamic, self.grad_scale, self.scaler = _scale_args(who, grad_scale, scaler)
+        fitloop.check_sgd(who, momentum, dampening, weight_decay, nesterov)
+        self.scale = fitloop.exp_logit_scale(who, logit_scale)
+        self.momentum, self.dampening, self.nesterov, self.weight_decay = momentum, dampening, nesterov, weight_decay
+
+    def _init_block(self, master: torch.Tensor) -> None:
+        """``master`` becomes the block the steps update; the buffer, the step count and the scaler's device block with it."""
+        setattr(self, self._master_name, master)
+        self.buf = torch.zeros_like(master) if self.momentum != 0.0 else None
+        self.steps = 0
+        self._scaler = _BlockScaler(self.scaler, master.device) if self.dynamic else None
+
+    def _master(self) -> torch.Tensor:
+        return getattr(self, self._master_name)
+
+    def scaler_state(self) -> dict:
+        """The dynamic scale's block as ``dict(scale, growth_tracker, skipped_steps, applied_steps, found_inf)`` (``found_inf``: of the
+        last step).  It waits for the steps enqueued so far: one synchronisation, the only read-back of the dynamic path."""
+        if not self.dynamic:
+            raise ValueError(f"{self._who}.scaler_state: the state was made with a static grad_scale={self.grad_scale}")
+        return self._scaler.state()
+
+    def step(self, images: torch.Tensor, labels, lr, want_loss: bool = False, one_call: bool = False) -> Optional[torch.Tensor]:
+        """One optimiser step on the batch ``images`` [B, 3, R, R] (preprocessed, fp16 or fp32, on the GPU) and ``labels`` [B] at the rate
+        ``lr``: an fp32 tensor of one element on the device is read where it lies; a Python number is uploaded on every call.  A label
+        tensor on the GPU is taken as it is -- a label outside [0, C) then makes the parameters NaN, it is never used as an address; host
+        labels are range-checked.  ``one_call``: the same launches through the fit's one-call symbol, whose workspace holds the towers'
+        (the separate calls' workspace is then not allocated; the stashes are the same).  Returns the batch loss, fp32 [1] on the device
+        (the first of the head's losses, all kept in ``last_losses``), when ``want_loss``.  Under ``grad_scale="dynamic"`` the head runs at
+        ``grad_scale = 1``, the head's output gradients are multiplied by the device block's scale, the gradient block is formed without
+        being applied and clipmi_block_step_scaled decides on the device whether the step is applied (one call: the ``_scaled`` symbol);
+        a skipped step still counts in ``steps`` and still returns its loss; whether it was applied is in ``scaler_state()``."""
+        who = f"{self._who}.step"
+        v = self._vision()
+        images = v.images(who, images)
+        dev, B = images.device, images.shape[0]
+        labels_d = fitloop.step_labels(who, labels, B, self.C, dev, "images")
+        lr_d = ops._dev(fitloop.lr_operand(lr, dev), "lr", (torch.float32,))
+        first = self.steps == 0
+        sgd = (float(self.momentum), float(self.dampening), float(self.weight_decay), int(bool(self.nesterov)))
+        loss = torch.empty(self._n_losses, dtype=torch.float32, device=dev)
+        if one_call:
+            v.size(B, tower_ws=False)
+            stem, ws, front, weights, stashes = self._one_call(images, B, labels_d)
+            if self.dynamic:
+                name, how, rate = stem + "_scaled", (self._scaler.block.data_ptr(), *self._scaler.args()), (lr_d.data_ptr(),)
+            else:
+                name, how, rate = stem, (self.grad_scale,), (lr_d.data_ptr(), int(first))
+            with v.model._launch_lock:
+                check(getattr(lib, name)(*front, self.scale, *how, *weights, *rate, *sgd, loss.data_ptr(), None, ws.data_ptr(), ws.numel(), *stashes,
+                                         ops._stream()), name)
+        else:
+            outs = self._head(images, labels_d, 1.0 if self.dynamic else self.grad_scale, loss)
+            if self.dynamic:
+                for d_out in outs:
+                    ops.grad_scale_rows(d_out, self._scaler.block)
+                self._scaler.step(self._apply(outs, lr_d, first, sgd), self._master(), self.buf, lr_d, *sgd)
+            else:
+                self._apply(outs, lr_d, first, sgd)
+        self.steps += 1
+        self.last_losses = loss
+        return loss[:1] if want_loss else None
+
+
+class VPTFitState(_BlockFitState):
     """The training state of VPT's prompts: the fp32 master block ``prompts`` [depth, n_ctx, Dv] (None: the model's own parameters), SGD's
     momentum buffer, the tower's stash and the number of steps taken.  ``step`` enqueues one forward, backward and update and does not
     synchronise.  ``validate`` scores validation images on the device (``start_monitor``, ``monitor``, ``best_prompts``,
     ``val_row_results``; DESIGN.md "Fit monitor", "The image-tower fits")."""
-    _who = "VPTFitState"
+    _who, _master_name = "VPTFitState", "prompts"
 
     def __init__(self, model, text_features: torch.Tensor, logit_scale: float = 4.6052, prompts: Optional[torch.Tensor] = None,
                  momentum: float = 0.9, dampening: float = 0.0, nesterov: bool = False, weight_decay: float = 5e-4,
@@ -322,23 +370,12 @@ class VPTFitState(fitmonitor.ImageMonitored):
         if prompts is None:
             prompts = model_prompts(model)
         self.depth, self.n_ctx = _check_prompts(who, model, prompts)
-        self.dynamic, self.grad_scale, self.scaler = _scale_args(who, grad_scale, scaler)
-        fitloop.check_sgd(who, momentum, dampening, weight_decay, nesterov)
-        if not math.isfinite(logit_scale):
-            raise ValueError(f"{who}: logit_scale={logit_scale} (finite)")
+        self._init_optimiser(who, logit_scale, momentum, dampening, nesterov, weight_decay, grad_scale, scaler)
         self.text = _check_text(who, model, text_features)
         self.C = int(self.text.shape[0])
         self.tower = _Tower(who, model, self.depth, self.n_ctx)
-        self.prompts = fitloop.master(prompts, model.device)
-        self.buf = torch.zeros_like(self.prompts) if momentum != 0.0 else None
-        self.scale = float(np.float32(math.exp(logit_scale)))
-        self.momentum, self.dampening, self.nesterov, self.weight_decay = momentum, dampening, nesterov, weight_decay
-        self.steps = 0
-        self._scaler = _BlockScaler(self.scaler, model.device) if self.dynamic else None
+        self._init_block(fitloop.master(prompts, model.device))
         self._text_n = None     # the fixed text features, normalised by the first validate
-
-    def _master(self) -> torch.Tensor:
-        return self.prompts
 
     def validate(self, val_images_or_loader, val_labels, epoch: int, val_batch_size: int = 32, one_call: bool = True) -> None:
         """Enqueue one validation of the current master prompts into slot ``epoch`` of the device history; no host read.
@@ -363,61 +400,23 @@ class VPTFitState(fitmonitor.ImageMonitored):
         been taken."""
         return self._best_block("best_prompts").view_as(self.prompts)
 
-    def scaler_state(self) -> dict:
-        """The dynamic scale's block as ``dict(scale, growth_tracker, skipped_steps, applied_steps, found_inf)`` (``found_inf``: of the
-        last step).  It waits for the steps enqueued so far: one synchronisation, the only read-back of the dynamic path."""
-        if not self.dynamic:
-            raise ValueError(f"VPTFitState.scaler_state: the state was made with a static grad_scale={self.grad_scale}")
-        return self._scaler.state()
+    def _vision(self):
+        return self.tower
 
-    def step(self, images: torch.Tensor, labels, lr, want_loss: bool = False, one_call: bool = False) -> Optional[torch.Tensor]:
-        """One optimiser step on the batch ``images`` [B, 3, R, R] (preprocessed, fp16 or fp32, on the GPU) and ``labels`` [B] at the rate
-        ``lr``: an fp32 tensor of one element on the device is read where it lies; a Python number is uploaded on every call.  A label
-        tensor on the GPU is taken as it is -- a label outside [0, C) then makes the prompts NaN, it is never used as an address; host
-        labels are range-checked.  ``one_call``: the same launches through clipmi_vpt_train_step, whose workspace holds the tower's (the
-        separate calls' workspace is then not allocated; the stash is the same).  Returns the batch loss, fp32 [1] on the device, when
-        ``want_loss``.  Under ``grad_scale="dynamic"`` the head runs at ``grad_scale = 1``, ``d_feats`` is multiplied by the device block's
-        scale and clipmi_block_step_scaled decides on the device whether the step is applied (one call: clipmi_vpt_train_step_scaled); a
-        skipped step still counts in ``steps`` and still returns its loss; whether it was applied is in ``scaler_state()``."""
-        who = "VPTFitState.step"
-        t, m = self.tower, self.tower.model
-        images = t.images(who, images)
-        dev, B = images.device, images.shape[0]
-        labels_d = fitloop.step_labels(who, labels, B, self.C, dev, "images")
-        lr_d = ops._dev(fitloop.lr_operand(lr, dev), "lr", (torch.float32,))
-        first = self.steps == 0
-        sgd = (float(self.momentum), float(self.dampening), float(self.weight_decay), int(bool(self.nesterov)))
-        loss = torch.empty(1, dtype=torch.float32, device=dev)
-        if self.dynamic and one_call:
-            t.size(B, tower_ws=False)
-            ws, sc = t.one_call_workspace(B, self.C, scaled=True), self._scaler
-            with m._launch_lock:
-                check(lib.clipmi_vpt_train_step_scaled(m._handle, C.byref(t.dgrad[0]), images.data_ptr(), _DT[images.dtype], B, self.prompts.data_ptr(),
-                                                       None if self.buf is None else self.buf.data_ptr(), self.n_ctx, self.depth, self.text.data_ptr(),
-                                                       self.C, labels_d.data_ptr(), self.scale, sc.block.data_ptr(), *sc.args(), lr_d.data_ptr(), *sgd,
-                                                       loss.data_ptr(), None, ws.data_ptr(), ws.numel(), t.stash.data_ptr(), t.stash.numel(),
-                                                       ops._stream()),
-                      "clipmi_vpt_train_step_scaled")
-        elif self.dynamic:
-            feats = t.forward(images, self.prompts)
-            _, d_feats = vpt_head(feats, labels_d, self.text, self.scale, 1.0, loss)
-            ops.grad_scale_rows(d_feats, self._scaler.block)
-            self._scaler.step(t.backward(d_feats), self.prompts, self.buf, lr_d, *sgd)
-        elif one_call:
-            t.size(B, tower_ws=False)
-            ws = t.one_call_workspace(B, self.C)
-            with m._launch_lock:
-                check(lib.clipmi_vpt_train_step(m._handle, C.byref(t.dgrad[0]), images.data_ptr(), _DT[images.dtype], B, self.prompts.data_ptr(),
-                                                None if self.buf is None else self.buf.data_ptr(), self.n_ctx, self.depth, self.text.data_ptr(), self.C,
-                                                labels_d.data_ptr(), self.scale, self.grad_scale, lr_d.data_ptr(), int(first), *sgd, loss.data_ptr(),
-                                                None, ws.data_ptr(), ws.numel(), t.stash.data_ptr(), t.stash.numel(), ops._stream()),
-                      "clipmi_vpt_train_step")
-        else:
-            feats = t.forward(images, self.prompts)
-            _, d_feats = vpt_head(feats, labels_d, self.text, self.scale, self.grad_scale, loss)
-            vpt_step(t.backward(d_feats), self.grad_scale, self.prompts, self.buf, lr_d, first, *sgd, want_grad=False)
-        self.steps += 1
-        return loss if want_loss else None
+    def _one_call(self, images, B, labels_d):
+        t = self.tower
+        ws = t.one_call_workspace(B, self.C, scaled=self.dynamic)
+        front = (t.model._handle, C.byref(t.dgrad[0]), images.data_ptr(), _DT[images.dtype], B, self.prompts.data_ptr(),
+                 None if self.buf is None else self.buf.data_ptr(), self.n_ctx, self.depth, self.text.data_ptr(), self.C, labels_d.data_ptr())
+        return "clipmi_vpt_train_step", ws, front, (), (t.stash.data_ptr(), t.stash.numel())
+
+    def _head(self, images, labels_d, grad_scale, loss):
+        return vpt_head(self.tower.forward(images, self.prompts), labels_d, self.text, self.scale, grad_scale, loss)[1:]
+
+    def _apply(self, outs, lr_d, first, sgd):
+        """The tower's backward leaves the prompts' gradient as it is: under the dynamic scale that is the block the scaled step takes."""
+        grad = self.tower.backward(outs[0])
+        return grad if self.dynamic else vpt_step(grad, self.grad_scale, self.prompts, self.buf, lr_d, first, *sgd, want_grad=False)
 
 
 def fit_prompts(images_or_loader, labels, model, text_features: torch.Tensor, prompts: Optional[torch.Tensor] = None, logit_scale: float = 4.6052,
