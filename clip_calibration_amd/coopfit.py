@@ -55,8 +55,19 @@ scores the context behind every epoch on the device (``CoOpFitState.validate``, 
 strictly best epoch in a device slot, the reference's TEST.FINAL_MODEL (base_learner.py:41-47), with no read-back before the run's one
 wait.  DESIGN.md "Fit monitor".
 
-Not covered: ``nn.DataParallel`` (one process drives one GPU), ProGrad under a dynamic loss scale, and models whose text tower carries
-deep prompts.
+``shard=Shard(world, rank, gather)`` on ``CoOpFitState``, ``fit_context`` and ``context_gradient``: the class-sharded fit, this project's
+form of the reference's ``nn.DataParallel`` around the text encoder (coop.py:266-272).  One process per GPU; rank r owns the contiguous
+classes of the balanced split and runs the tower's forward and backward over its own prompts only; the raw text features are gathered and
+compacted (csrc/shard_train.hip), the loss head runs replicated on every rank, and the context's gradient is the ranks' partial class sums
+gathered and added in rank order, so every rank ends a step with the same bits.  A class-specific context keeps its own rows per rank
+(``gathered_context()``).  With ``world == 1`` the bits are the unsharded path's.  ``gather``: ``parallel.shard_gather(exchange)`` over
+RCCL, or one ``LocalGather`` shared by all the ranks' states in one process on one GPU (a step of one state then steps them all, and the
+others' ``step`` is refused).
+Refused under ``shard``, each by name: C < world, a class-token position other than "end", ``grad_scale="dynamic"``, ``val=`` /
+``final_model="best_val"``, ``one_call=True``.  DESIGN.md "Class-sharded CoOp fit".
+
+Not covered: ``nn.DataParallel`` itself in one process (``shard=`` stands in for it, with the refusals above), ProGrad under a dynamic loss
+scale, and models whose text tower carries deep prompts.
 """
 from __future__ import annotations
 
@@ -251,6 +262,103 @@ def _check_method(who: str, method: str, teacher, w: float, T: float, lam: float
         raise ValueError(f"{who}: lam={lam} (finite)")
 
 
+# ---- class sharding (DESIGN.md "Class-sharded CoOp fit"): one shard state per rank, two all-gathers per step
+
+class LocalGather:
+    """The gather of ``world`` shard states that live in ONE process on one GPU: the states' phases run one after the other on one
+    stream, each rank posts its send and receive blocks through its own port, and the post that completes the set fills every rank's
+    receive block with device copies, rank-major -- what ``clipmi_allgather`` leaves.  The whole feature runs on a single GPU this way,
+    through the kernels and the phase code of the multi-process run; it is the oracle that run is compared with bit for bit."""
+
+    def __init__(self, world: int):
+        if isinstance(world, bool) or int(world) != world or world < 1:
+            raise ValueError(f"LocalGather: world={world} must be an integer >= 1")
+        self.world = int(world)
+        self.states = [None] * self.world      # the shard states, filed by their rank as they are made
+        self.driver = None                     # the state whose ``step`` steps them all: the first that steps
+        self._posts = {}
+
+    def port(self, rank: int):
+        """Rank ``rank``'s ``gather(src, dst, bytes_per_rank, stream)``."""
+        def gather(src: torch.Tensor, dst: torch.Tensor, nbytes: int, stream: int) -> None:
+            self._posts[rank] = (src, dst)
+            if len(self._posts) < self.world:
+                return
+            posts, self._posts = self._posts, {}
+            srcs = [posts[r][0].view(-1).view(torch.uint8)[:nbytes] for r in range(self.world)]
+            if stream != ops._stream():     # torch enqueues the copies on its current stream: it must be the one the phases launched on
+                raise RuntimeError("LocalGather: the gather was asked for on a stream that is not torch's current stream")
+            for r in range(self.world):
+                out = posts[r][1].view(-1).view(torch.uint8)
+                for s in range(self.world):
+                    out[s * nbytes:(s + 1) * nbytes].copy_(srcs[s])
+        return gather
+
+
+class Shard:
+    """Which part of a class-sharded fit a state is: ``world`` ranks, this one's ``rank``, and ``gather(src, dst, bytes_per_rank,
+    stream)``, which leaves rank r's ``src`` in ``dst[r * bytes_per_rank : (r + 1) * bytes_per_rank]`` on every rank, in stream order
+    (``src``, ``dst``: contiguous device tensors).  ``gather``: ``parallel.shard_gather(exchange)`` for one process per GPU over RCCL,
+    or a ``LocalGather`` shared by the ``world`` states of one process."""
+
+    def __init__(self, world: int, rank: int, gather):
+        for name, v in (("world", world), ("rank", rank)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise ValueError(f"Shard: {name}={v!r} must be an integer")
+        if world < 1 or not 0 <= rank < world:
+            raise ValueError(f"Shard: rank={rank} outside world={world}")
+        self.world, self.rank = int(world), int(rank)
+        self.local = gather if isinstance(gather, LocalGather) else None
+        if self.local is not None and self.local.world != self.world:
+            raise ValueError(f"Shard: world={world} but the LocalGather was made for {self.local.world}")
+        if self.local is None and not callable(gather):
+            raise ValueError("Shard: gather must be a LocalGather or a callable gather(src, dst, bytes_per_rank, stream)")
+        self.gather = self.local.port(self.rank) if self.local is not None else gather
+
+    def peer(self, rank: int) -> "Shard":
+        """Rank ``rank`` of the same local world."""
+        return Shard(self.world, rank, self.local)
+
+
+def shard_classes(n_cls: int, world: int, rank: int) -> Tuple[int, int]:
+    """Classes [lo, hi) of ``n_cls`` that ``rank`` of ``world`` owns: contiguous, the first ``n_cls mod world`` ranks one class more."""
+    from .parallel import shard_bounds
+    if n_cls < world:
+        raise ValueError(f"shard: C={n_cls} classes cannot be split over world={world} ranks (C < G: a rank would own no class)")
+    return shard_bounds(n_cls, rank, world)
+
+
+def _check_shard(who: str, shard, n_cls: int, class_token_position, grad_scale, val=None, final_model: str = "last_step") -> None:
+    """What the first version of the sharded fit refuses, each by name, before any device call."""
+    if not isinstance(shard, Shard):
+        raise ValueError(f"{who}: shard must be a coopfit.Shard(world, rank, gather), got {type(shard).__name__}")
+    shard_classes(n_cls, shard.world, shard.rank)
+    if class_token_position != "end":
+        raise ValueError(f"{who}: shard covers class_token_position='end' only, not {class_token_position!r}")
+    if isinstance(grad_scale, str):
+        raise ValueError(f"{who}: shard needs a static grad_scale; the dynamic loss scale (grad_scale={grad_scale!r}) is not sharded")
+    if val is not None or final_model == "best_val":
+        raise ValueError(f"{who}: shard has no validation: val= and final_model='best_val' are not sharded")
+
+
+def shard_states(make, shard: Optional[Shard]):
+    """This rank's state from ``make(shard)``: under a ``LocalGather`` all the world's states are made here, one per rank, and the one
+    of ``shard.rank`` is returned (its ``step`` then steps them all); otherwise the one state."""
+    if shard is None or shard.local is None:
+        return make(shard)
+    return [make(shard.peer(r)) for r in range(shard.world)][shard.rank]
+
+
+def _run_phases(gens) -> None:
+    """Advance the shard states' phase generators in lock step, rank after rank, until they end (they end together: every rank runs the
+    same phases).  One generator under an RCCL gather; all ``world`` under a local one, where a phase's last post completes the gather."""
+    live = True
+    while live:
+        for g in gens:
+            if next(g, StopIteration) is StopIteration:
+                live = False
+
+
 def _pack_dgrad(model, blocks, projection: torch.Tensor, struct, slot: str):
     """The transposed fp16 copies of a frozen tower's weights (``struct``: clipmi_text_dgrad or clipmi_vision_dgrad, ``projection`` as it
     lies), packed once per bound model and again when a weight's version moves; the model keeps them under ``slot``."""
@@ -377,7 +485,7 @@ def _new_losses(method: str, dev) -> torch.Tensor:
 def context_gradient(clip_model, tokenized_prompts, ctx: torch.Tensor, features: torch.Tensor, labels, logit_scale: float = 4.6052,
                      grad_scale: float = DEFAULT_GRAD_SCALE, seq_rows: Optional[int] = None, return_operand_stats: bool = False,
                      method: str = "coop", teacher: Optional[torch.Tensor] = None, w: float = 8.0, T: float = 1.0, lam: float = 1.0,
-                     return_parts: bool = False, class_token_position: str = "end", name_lens=None):
+                     return_parts: bool = False, class_token_position: str = "end", name_lens=None, shard: Optional[Shard] = None):
     """``(loss, grad)`` of ``F.cross_entropy(exp(logit_scale) * normalise(features) @ normalise(text_encoder(prompts(ctx))).T, labels)``
     with respect to ``ctx`` ([n_ctx, D] generic or [C, n_ctx, D] class-specific), on the GPU: loss fp32 [1], grad fp32 of ctx's shape.
     ``features`` fp32 [B, E] raw image features (the rows may be a column slice), ``tokenized_prompts`` [C, context_length] the ids of
@@ -389,9 +497,19 @@ def context_gradient(clip_model, tokenized_prompts, ctx: torch.Tensor, features:
     gradient the one ProGrad applies (module docstring; ``teacher``, ``w``, ``T``, ``lam``).  ``return_parts`` adds a dict (before the
     operand statistics): KgCoOp ``ce``, ``score`` (fp32 [1] each); ProGrad ``xe``, ``kl``, ``grad_xe``, ``grad_kl``, ``projected``
     (int32 [1]) and ``dots`` (float64 [3]: a.a, b.b, a.b of a = grad_xe, b = grad_kl); CoOp an empty one.
-    ``class_token_position``, ``name_lens``: the prompts' layout (module docstring)."""
+    ``class_token_position``, ``name_lens``: the prompts' layout (module docstring).
+
+    ``shard``: the gradient the class-sharded step would apply (module docstring), reduced over the ranks in rank order -- the same
+    bits on every rank, of the whole context's shape also for a class-specific one.  ProGrad's parts are then ``xe``, ``kl``,
+    ``projected`` and ``dots``; the operand statistics are per rank and are not returned."""
     who = "context_gradient"
     Cn, n_ctx, per_class, last = _check_prompts(who, clip_model, tokenized_prompts, ctx)
+    if shard is not None:
+        _check_shard(who, shard, Cn, class_token_position, grad_scale)
+        if return_operand_stats:
+            raise ValueError(f"{who}: shard returns no operand statistics (return_operand_stats=True)")
+        return _sharded_gradient(clip_model, tokenized_prompts, ctx, features, labels, logit_scale, grad_scale, seq_rows, method, teacher, w, T, lam,
+                                 return_parts, shard)
     placement = _placement(who, tokenized_prompts, n_ctx, class_token_position, name_lens)
     if _is_dynamic(who, grad_scale):
         raise ValueError(f"{who}: grad_scale={DYNAMIC!r} belongs to a fit (CoOpFitState, fit_context); one gradient needs a number")
@@ -427,6 +545,28 @@ def context_gradient(clip_model, tokenized_prompts, ctx: torch.Tensor, features:
     return out + (operand_stats_dict(stats),)
 
 
+def _sharded_gradient(clip_model, tokenized_prompts, ctx, features, labels, logit_scale, grad_scale, seq_rows, method, teacher, w, T, lam, return_parts,
+                      shard: Shard):
+    """``context_gradient`` under ``shard``: the sharded step's phases with a report in the step's place."""
+    make = lambda sh: CoOpFitState(clip_model, tokenized_prompts, ctx, logit_scale, 0.0, 0.0, False, 0.0, grad_scale, seq_rows, method, teacher, w, T, lam,
+                                   shard=sh)
+    state = shard_states(make, shard)
+    labels_d = _check_batch("context_gradient", features, labels, state.C, state.tower.E)
+    _need_gpu(features, "features")
+    dev = features.device
+    states = state._shard_states("context_gradient")
+    reports, losses = [{} for _ in states], [_new_losses(method, dev) for _ in states]
+    _run_phases([s._shard_phases(features, labels_d, None, l, True, r) for s, l, r in zip(states, losses, reports)])
+    k = states.index(state)
+    report, loss3 = reports[k], losses[k]
+    parts = {}
+    if method == "kgcoop":
+        parts = {"ce": loss3[1:2], "score": loss3[2:3]}
+    elif method == "prograd":
+        parts = {"xe": loss3[0:1], "kl": loss3[1:2], "projected": report["projected"], "dots": report["dots"]}
+    return (loss3[0:1], report["grad"]) + ((parts,) if return_parts else ())
+
+
 def text_features(clip_model, tokenized_prompts, ctx: torch.Tensor, seq_rows: Optional[int] = None, class_token_position: str = "end",
                   name_lens=None) -> torch.Tensor:
     """The raw text features fp32 [C, E] of the training forward at ``ctx``: what the loss head is given."""
@@ -446,9 +586,12 @@ class CoOpFitState(fitmonitor.Monitored):
     def __init__(self, clip_model, tokenized_prompts, ctx: torch.Tensor, logit_scale: float = 4.6052, momentum: float = 0.9,
                  dampening: float = 0.0, nesterov: bool = False, weight_decay: float = 5e-4, grad_scale: float = DEFAULT_GRAD_SCALE,
                  seq_rows: Optional[int] = None, method: str = "coop", teacher: Optional[torch.Tensor] = None, w: float = 8.0, T: float = 1.0,
-                 lam: float = 1.0, scaler: Optional[dict] = None, class_token_position: str = "end", name_lens=None):
+                 lam: float = 1.0, scaler: Optional[dict] = None, class_token_position: str = "end", name_lens=None, shard: Optional[Shard] = None):
         who = "CoOpFitState"
         self.C, self.n_ctx, self.per_class, last = _check_prompts(who, clip_model, tokenized_prompts, ctx)
+        self.shard = shard
+        if shard is not None:
+            _check_shard(who, shard, self.C, class_token_position, grad_scale)
         placement = _placement(who, tokenized_prompts, self.n_ctx, class_token_position, name_lens)
         _static_prograd(who, method, grad_scale)
         self.dynamic, self.grad_scale, self.scaler = _scale_args(who, grad_scale, scaler)
@@ -460,9 +603,16 @@ class CoOpFitState(fitmonitor.Monitored):
         if method != "coop":
             _need_gpu(teacher, "teacher")
             self.teacher = teacher.detach().contiguous()
-        self.tower = _Tower(who, clip_model, tokenized_prompts, self.C, self.n_ctx, self.per_class, last, seq_rows, placement)
         dev = clip_model.device
-        self.ctx = fitloop.master(ctx, dev)
+        if shard is None:
+            self.tower = _Tower(who, clip_model, tokenized_prompts, self.C, self.n_ctx, self.per_class, last, seq_rows, placement)
+            self.ctx = fitloop.master(ctx, dev)
+        else:   # the tower over the rank's own prompts (the live-row cut is the full prompt set's), a class-specific context's own rows
+            self.lo, self.hi = shard_classes(self.C, shard.world, shard.rank)
+            ids = _host_int_array(who, tokenized_prompts, "tokenized_prompts")[self.lo:self.hi]
+            self.tower = _Tower(who, clip_model, ids, self.hi - self.lo, self.n_ctx, self.per_class, last, seq_rows)
+            self.ctx = fitloop.master(ctx[self.lo:self.hi] if self.per_class else ctx, dev)
+            self._shard_buffers(dev)
         self.buf = torch.zeros_like(self.ctx) if momentum != 0.0 else None
         self.momentum, self.dampening, self.nesterov, self.weight_decay = momentum, dampening, nesterov, weight_decay
         self.steps = 0
@@ -474,6 +624,109 @@ class CoOpFitState(fitmonitor.Monitored):
         if not self.dynamic:
             raise ValueError(f"CoOpFitState.scaler_state: the state was made with a static grad_scale={self.grad_scale}")
         return self._scaler.state()
+
+    # ---- the class-sharded step (csrc/shard_train.hip, DESIGN.md "Class-sharded CoOp fit")
+
+    def _shard_buffers(self, dev) -> None:
+        """The send and receive blocks of the step's two gathers, made once.  The tower writes its text features straight into the
+        first rows of the padded send block."""
+        sh, t = self.shard, self.tower
+        G, P = sh.world, -(-self.C // sh.world)
+        f32 = dict(dtype=torch.float32, device=dev)
+        self._send_text = torch.empty(P, t.E, **f32)
+        t.text = self._send_text[:t.C]
+        self._all_text = torch.empty(G, P, t.E, **f32)
+        self._text = torch.empty(self.C, t.E, **f32)
+        prograd = self.method == "prograd"
+        if not self.per_class:      # the partial gradient(s): ProGrad's two travel in one gather
+            k = 2 if prograd else 1
+            self._send_part = torch.empty(k, t.n_ctx, t.D, **f32)
+            self._all_part = torch.empty(G, k, t.n_ctx, t.D, **f32)
+        if prograd:                 # class-specific: every rank's dots travel; generic: the reduced vectors' dots are every rank's own
+            n = G if self.per_class else 1
+            self._send_dots = torch.empty(3, dtype=torch.float64, device=dev) if self.per_class else None
+            self._all_dots = torch.empty(n, 3, dtype=torch.float64, device=dev)
+            self._prograd_ws = ops.shard_prograd_workspace(self.ctx.numel(), dev)
+        self._rows = None           # gathered_context's blocks, made on first use
+        if sh.local is not None:
+            sh.local.states[sh.rank], sh.local.driver = self, None      # a new set of states chooses its driver anew
+
+    def _gather_rows(self, own: torch.Tensor):
+        """A phase: the ranks' own rows of a class-specific [C_r, n_ctx, D] block gathered into the full [C, n_ctx, D]; the result is
+        left in ``self._rows[2]``."""
+        t, sh = self.tower, self.shard
+        if self._rows is None:
+            P, n = self._send_text.shape[0], t.n_ctx * t.D
+            f32 = dict(dtype=torch.float32, device=own.device)
+            self._rows = (torch.empty(P, n, **f32), torch.empty(sh.world, P, n, **f32), torch.empty(self.C, t.n_ctx, t.D, **f32))
+        send, recv, full = self._rows
+        send[:t.C].copy_(own.view(t.C, -1))
+        sh.gather(send, recv, send.numel() * 4, ops._stream())
+        yield
+        ops.shard_compact(recv, self.C, full)
+
+    def _shard_phases(self, features, labels_d, lr_d, losses, first: bool, report: Optional[dict] = None):
+        """One sharded step as phases, a ``yield`` behind every gather.  ``report``: a dict that receives the reduced gradient (and
+        ProGrad's decision) INSTEAD of a step: neither the context nor the momentum buffer is touched."""
+        t, sh, st = self.tower, self.shard, ops._stream()
+        step = report is None
+        ctx, buf, lr_d = (self.ctx, self.buf, lr_d) if step else (None, None, None)
+        sgd = (self.momentum, self.dampening, self.weight_decay, self.nesterov)
+        prograd = self.method == "prograd"
+        t.forward(self.ctx)                                                                  # the rank's own prompts
+        sh.gather(self._send_text, self._all_text, self._send_text.numel() * 4, st)
+        yield
+        text = ops.shard_compact(self._all_text, self.C, self._text)
+        _, d_text, d_kl = ops.prompt_head(features, labels_d, text, self.scale, self.grad_scale, self.method, self.teacher, self.w, self.T, losses)
+        d_embed = t.backward(d_text[self.lo:self.hi])                                        # the rank's own rows of the replicated d_text
+        d_embed_kl = t.backward(d_kl[self.lo:self.hi], second=True) if prograd else None
+        out = None
+        if not self.per_class:
+            ops.ctx_partial(d_embed, t.C, t.n_ctx, self._send_part[0])
+            if prograd:
+                ops.ctx_partial(d_embed_kl, t.C, t.n_ctx, self._send_part[1])
+            sh.gather(self._send_part, self._all_part, self._send_part.numel() * 4, st)
+            yield
+            if not prograd:
+                out = ops.ctx_step_gathered(self._all_part.view(sh.world, -1), t.n_ctx, t.D, self.grad_scale, ctx, buf, lr_d, first, *sgd, want_grad=not step)
+            else:
+                ops.shard_prograd_dots(self._all_part[:, 0], self._all_part[:, 1], 1, t.n_ctx, False, self.grad_scale, self._prograd_ws, self._all_dots[0])
+        elif not prograd:           # every rank steps its own classes' rows with the unsharded rule: nothing is reduced
+            out = ops.ctx_step(d_embed, t.C, t.n_ctx, True, self.grad_scale, ctx, buf, lr_d, first, *sgd, want_grad=not step)
+        else:
+            ops.shard_prograd_dots(d_embed, d_embed_kl, t.C, t.n_ctx, True, self.grad_scale, self._prograd_ws, self._send_dots)
+            sh.gather(self._send_dots, self._all_dots, 24, st)
+            yield
+        if prograd:
+            out = ops.shard_prograd_apply(self._all_dots, self.lam, self._prograd_ws, self.ctx.shape, ctx, buf, lr_d, first, *sgd, want_report=not step)
+        if step:
+            return
+        grad = out[0] if prograd else out
+        if prograd:
+            report["projected"], report["dots"] = out[1], out[2]
+        if self.per_class:
+            yield from self._gather_rows(grad)
+            grad = self._rows[2].clone()
+        report["grad"] = grad
+
+    def _shard_states(self, who: str):
+        """The states whose phases this process runs: this one alone, or all of a local gather's world."""
+        local = self.shard.local
+        if local is None:
+            return [self]
+        if any(s is None for s in local.states):
+            raise ValueError(f"{who}: the LocalGather holds {sum(s is not None for s in local.states)} of its {local.world} shard states; "
+                             "make one state per rank before the first step")
+        return local.states
+
+    def gathered_context(self) -> torch.Tensor:
+        """The whole context on the device: ``ctx`` itself for a generic context (every rank holds the same bits) and without ``shard``;
+        for a class-specific context under ``shard`` the ranks' rows gathered into a fresh [C, n_ctx, D] -- one all-gather that every
+        rank enters (under a local gather this call runs it for all of them)."""
+        if self.shard is None or not self.per_class:
+            return self.ctx
+        _run_phases([s._gather_rows(s.ctx) for s in self._shard_states("CoOpFitState.gathered_context")])
+        return self._rows[2].clone()
 
     # ---- per-epoch validation and best-epoch selection on the device (csrc/fit_monitor.hip, DESIGN.md "Fit monitor")
 
@@ -493,6 +746,8 @@ class CoOpFitState(fitmonitor.Monitored):
         Without ``start_monitor`` the history starts with ``epoch + 1`` slots of 10 bins and no selection; it grows when ``epoch``
         lies behind its end."""
         who = "CoOpFitState.validate"
+        if self.shard is not None:
+            raise ValueError(f"{who}: shard has no validation (the first version of the sharded fit scores nothing between epochs)")
         mon, t = self._monitor_for(epoch), self.tower
         epoch = mon.slot(who, epoch)
         img_n, labels_d = mon.operands(who, val_features, val_labels, t.E, self.C, ops.l2_normalize)
@@ -557,7 +812,22 @@ class CoOpFitState(fitmonitor.Monitored):
         t, first = self.tower, self.steps == 0
         sgd = (self.momentum, self.dampening, self.weight_decay, self.nesterov)
         losses = _new_losses(self.method, dev)
-        if one_call:
+        if self.shard is not None:
+            # every rank is given the same batch; under a local gather this call steps all the world's states, one phase at a time
+            if one_call:
+                raise ValueError("CoOpFitState.step: shard has no one-call step (one_call=True); the sharded step is the separate calls")
+            states = self._shard_states("CoOpFitState.step")
+            local = self.shard.local
+            if local is not None:       # one state drives: a caller who stepped every rank's state, as under RCCL, would take G steps
+                if local.driver is None:
+                    local.driver = self
+                if local.driver is not self:
+                    raise ValueError(f"CoOpFitState.step: under a LocalGather the step of rank {local.driver.shard.rank}'s state steps every rank; "
+                                     f"rank {self.shard.rank}'s state must not be stepped as well")
+            _run_phases([s._shard_phases(features, labels_d, lr_d, losses if s is self else _new_losses(s.method, dev), first) for s in states])
+            for s in states:
+                s.steps += s is not self
+        elif one_call:
             self._one_call(features, labels_d, lr_d, losses, first)
         elif self.dynamic:
             self._step_scaled(features, labels_d, lr_d, losses)
@@ -592,7 +862,8 @@ def fit_context(features: torch.Tensor, labels, clip_model, tokenized_prompts, c
                 grad_scale: float = DEFAULT_GRAD_SCALE, seq_rows: Optional[int] = None, lr_per_epoch: Optional[Sequence[float]] = None,
                 order=None, drop_last: bool = False, return_history: bool = False, method: str = "coop", teacher: Optional[torch.Tensor] = None,
                 w: float = 8.0, T: float = 1.0, lam: float = 1.0, scaler: Optional[dict] = None, class_token_position: str = "end", name_lens=None,
-                val=None, val_bins: int = 10, final_model: str = "last_step", val_criterion: str = "accuracy", return_monitor: bool = False):
+                val=None, val_bins: int = 10, final_model: str = "last_step", val_criterion: str = "accuracy", return_monitor: bool = False,
+                shard: Optional[Shard] = None):
     """Train CoOp's context on cached ``features`` fp32 [N, E] (raw image features on the GPU; the rows may be a column slice) and
     ``labels`` [N], starting from ``ctx`` (not modified; None = ``init_context(clip_model, n_ctx, C if csc else None)``): ``epochs``
     passes of ``torch.optim.SGD(lr, momentum, dampening, weight_decay, nesterov)`` over batches of ``batch_size``.
@@ -615,13 +886,19 @@ def fit_context(features: torch.Tensor, labels, clip_model, tokenized_prompts, c
     better than every earlier one under ``val_criterion`` -- "accuracy" (Dassl's rule) or "nll", where an epoch with a non-finite nll is
     never taken; the starting context when no epoch was taken.  "best_val" without ``val`` is refused.  ``return_monitor`` adds a dict
     behind everything else, read once after the run's one wait: per-epoch ``accuracy``, ``nll`` and ``ece``, the raw ``bins``,
-    ``records`` and ``best_epoch`` (``CoOpFitState.monitor``); empty without ``val`` or without steps."""
+    ``records`` and ``best_epoch`` (``CoOpFitState.monitor``); empty without ``val`` or without steps.
+
+    ``shard=Shard(world, rank, gather)``: the class-sharded fit (module docstring).  Every rank makes this call with the same arguments
+    -- the whole prompt set, the whole context, all features -- and returns the same whole context; with a ``LocalGather`` the one call
+    runs all ``world`` shard states in this process."""
     who = "fit_context"
     fitmonitor.check_args(who, val, val_bins, final_model, val_criterion)
     ids = _host_int_array(who, tokenized_prompts, "tokenized_prompts")
     if ctx is None:
         ctx = init_context(clip_model, n_ctx, ids.shape[0] if csc else None)
     Cn, n_ctx, per_class, _ = _check_prompts(who, clip_model, tokenized_prompts, ctx)
+    if shard is not None:
+        _check_shard(who, shard, Cn, class_token_position, grad_scale, val, final_model)
     E = int(clip_model.geometry.embed_dim)
     if not isinstance(features, torch.Tensor) or features.dim() != 2 or features.shape[0] < 1 or features.shape[1] != E:
         raise ValueError(f"{who}: features must be a [N >= 1, E = {E}] tensor")
@@ -644,8 +921,9 @@ def fit_context(features: torch.Tensor, labels, clip_model, tokenized_prompts, c
         out = out.to(dev) if features.is_cuda else out
         return fitmonitor.pack(out, np.zeros(0, np.float32), empty_monitor(val_bins), return_history, return_monitor)
     _need_gpu(features, "features")
-    state = CoOpFitState(clip_model, tokenized_prompts, ctx, logit_scale, momentum, dampening, nesterov, weight_decay, grad_scale, seq_rows,
-                         method, teacher, w, T, lam, scaler, class_token_position, name_lens)
+    make = lambda sh: CoOpFitState(clip_model, tokenized_prompts, ctx, logit_scale, momentum, dampening, nesterov, weight_decay, grad_scale, seq_rows,
+                                   method, teacher, w, T, lam, scaler, class_token_position, name_lens, sh)
+    state = shard_states(make, shard)     # under a LocalGather all the world's states live here; a step of one steps them all
     end_epoch = None
     if val is not None:
         _need_gpu(vf, "val_features")
@@ -654,5 +932,5 @@ def fit_context(features: torch.Tensor, labels, clip_model, tokenized_prompts, c
         end_epoch = lambda e: state.validate(vf, vl, e)
     history = fitloop.run_cached(lambda f, y, r, want: state.step(f, y, r, want_loss=want), features, fitloop.labels_on(labels, lab, dev),
                                  fitloop.order_on(order, np.int64, dev), batch_size, per_epoch, epochs, lr_steps, return_history, end_epoch)
-    out = state.best_context() if final_model == "best_val" else state.ctx
+    out = state.best_context() if final_model == "best_val" else state.gathered_context()
     return fitmonitor.pack(out, history, state.monitor() if return_monitor else None, return_history, return_monitor)

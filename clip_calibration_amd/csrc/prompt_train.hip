@@ -321,9 +321,8 @@ int enqueue_ctx_step(const float* d_embed, float* ctx, float* buf, float* grad_o
 // (reference prograd.py:371-409).  a and b are the context gradients of the cross-entropy and of the distillation loss, each formed as
 // ctx_step_kernel forms its gradient.  Two launches: the first keeps a and b and writes every workgroup's partial sums of a.a, b.b and a.b
 // in float64 (a grid of at most DOT_BLOCKS workgroups, a function of the context's size alone); the second adds the partials in a fixed
-// order in every workgroup, decides, and steps.  The reference compares dot(a / |a|, b / |b|) with 0: that is a.b < 0 unless a norm is
-// zero or something is not finite, where the reference's comparison is false and the plain a is applied.
-constexpr int DOT_BLOCKS = 256;
+// order in every workgroup, decides, and steps by train_rules.h's ProGrad rule (shard_train.hip's class-sharded step shares it).
+constexpr int DOT_BLOCKS = PROGRAD_DOT_BLOCKS;
 
 // workspace: partial sums [3, DOT_BLOCKS] float64 | a [total] | b [total] fp32
 struct ProgradWs {
@@ -369,19 +368,14 @@ __global__ __launch_bounds__(256) void prograd_step_kernel(ProgradWs w, int n_pa
   for (int i = 0; i < 3; ++i) d[i] = t < n_part ? w.part[i * DOT_BLOCKS + t] : 0.0;
   block_sum_f64(d, sl);
   const double aa = d[0], bb = d[1], ab = d[2];
-  const bool finite = isfinite(aa) && isfinite(bb) && isfinite(ab);
-  const bool project = finite && ab < 0.0 && aa > 0.0 && bb > 0.0;
+  const bool project = prograd_projects(aa, bb, ab);
   if (blockIdx.x == 0 && t == 0) {
     if (projected) *projected = project ? 1 : 0;
     if (dots) { dots[0] = aa; dots[1] = bb; dots[2] = ab; }
   }
   const int64_t idx = (int64_t)blockIdx.x * 256 + t;
   if (idx >= total) return;
-  float g = w.a[idx];
-  if (project) {
-    const float k = (float)((double)lambda * (ab / bb));
-    g = g - k * w.b[idx];
-  }
+  const float g = prograd_element(w.a[idx], w.b[idx], project, lambda, ab, bb);
   if (grad_out) grad_out[idx] = g;
   if (ctx) sgd_element_fma(ctx, buf, idx, g, *lr, sgd);
 }

@@ -1,0 +1,225 @@
+// The class-sharded CoOp-family fit (DESIGN.md "Class-sharded CoOp fit"): what a rank adds around the unsharded step's kernels when the
+// classes are split over G ranks and two all-gathers per step move the text features and the context's partial gradients.
+//   shard_compact_kernel        the gathered, padded [G, ceil(C / G), E] block -> the full [C, E] matrix, one launch
+//   ctx_partial_kernel          a rank's partial context gradient: its own classes' rows in ascending order (ctx_grad_element)
+//   ctx_step_gathered_kernel    the G partials added in rank order, 1 / grad_scale, torch.optim.SGD's rule (sgd_element_fma)
+//   shard_prograd_*_kernel      ProGrad on the reduced vectors (generic context) or on a rank's own rows (class-specific context): the
+//                               float64 dots of one rank, then the G ranks' dots added in rank order, the decision and the step
+// With G = 1 every chain is the unsharded kernel's chain (prompt_train.hip): the same additions in the same order, the same partition of
+// the float64 dots, the same rules of train_rules.h -- the same bits.  No float atomics, no workgroup waits for another.
+#include <cmath>
+
+#include "common.h"
+#include "train_rules.h"
+
+namespace clipmi {
+namespace {
+
+constexpr int THREADS = 256;
+
+// the balanced split: the first C mod G ranks own one class more.  *lo: the first class of the rank that owns class c
+__device__ __forceinline__ int shard_owner(int c, int C, int G, int* lo) {
+  const int base = C / G, rem = C % G, cut = rem * (base + 1);
+  const int r = c < cut ? c / (base + 1) : rem + (c - cut) / base;   // base >= 1: C >= G
+  *lo = r * base + (r < rem ? r : rem);
+  return r;
+}
+
+// one thread per element of out [C, E]: row c is row c - lo of its owner's block of P = ceil(C / G) rows; the padding rows are never read
+__global__ __launch_bounds__(THREADS) void shard_compact_kernel(const float* __restrict__ gathered, float* __restrict__ out, int C, int G, int P, int64_t E) {
+  const int64_t idx = (int64_t)blockIdx.x * THREADS + threadIdx.x;
+  if (idx >= (int64_t)C * E) return;
+  const int c = (int)(idx / E);
+  int lo;
+  const int r = shard_owner(c, C, G, &lo);
+  out[idx] = gathered[((int64_t)r * P + (c - lo)) * E + idx % E];
+}
+
+// one thread per element of the partial [n_ctx, D]: the rank's C own classes added in ascending order, unscaled (times 1.0 is exact)
+__global__ __launch_bounds__(THREADS) void ctx_partial_kernel(const float* __restrict__ d_embed, float* __restrict__ partial, int C, int L, int D, int n_ctx) {
+  const int64_t idx = (int64_t)blockIdx.x * THREADS + threadIdx.x;
+  if (idx >= (int64_t)n_ctx * D) return;
+  partial[idx] = ctx_grad_element(d_embed, idx, C, L, D, n_ctx, 0, 1.f);
+}
+
+// element idx of the G partials (rank r's at partials + r * stride) added in rank order
+__device__ __forceinline__ float rank_sum(const float* __restrict__ partials, int64_t idx, int G, int64_t stride) {
+  float s = partials[idx];
+  for (int r = 1; r < G; ++r) s += partials[(int64_t)r * stride + idx];
+  return s;
+}
+
+__global__ __launch_bounds__(THREADS) void ctx_step_gathered_kernel(const float* __restrict__ partials, int G, int64_t stride, float* __restrict__ ctx,
+                                                                    float* __restrict__ buf, float* __restrict__ grad_out, int64_t total, float inv_scale,
+                                                                    const float* __restrict__ lr, SgdArgs sgd) {
+  const int64_t idx = (int64_t)blockIdx.x * THREADS + threadIdx.x;
+  if (idx >= total) return;
+  const float g = rank_sum(partials, idx, G, stride) * inv_scale;
+  if (grad_out) grad_out[idx] = g;
+  if (ctx) sgd_element_fma(ctx, buf, idx, g, *lr, sgd);
+}
+
+// ------------------------------------------------------------------------------------------------------------------------- ProGrad
+// workspace: per-workgroup partial sums [3, PROGRAD_DOT_BLOCKS] float64 | a [total] | b [total] fp32 -- clipmi_prograd_step's layout
+struct DotsWs {
+  double* part;
+  float *a, *b;
+};
+inline size_t dots_bytes(int64_t total) { return align256(3 * PROGRAD_DOT_BLOCKS * sizeof(double)) + 2 * align256((size_t)total * 4); }
+inline DotsWs dots_carve(void* ws, int64_t total) {
+  char* p = static_cast<char*>(ws);
+  DotsWs w;
+  w.part = reinterpret_cast<double*>(p);
+  w.a = reinterpret_cast<float*>(p + align256(3 * PROGRAD_DOT_BLOCKS * sizeof(double)));
+  w.b = reinterpret_cast<float*>(p + align256(3 * PROGRAD_DOT_BLOCKS * sizeof(double)) + align256((size_t)total * 4));
+  return w;
+}
+
+// a and b of `total` elements, kept in the workspace, and every workgroup's float64 partial sums of a.a, b.b, a.b: prograd_dots_kernel's
+// grid and order.  per_class: the rank's own rows of its two d_embed (C its own classes); else the rank-ordered sums of the G gathered partials
+__global__ __launch_bounds__(256) void shard_prograd_dots_kernel(const float* __restrict__ src_a, const float* __restrict__ src_b, int G, int64_t stride, int C,
+                                                                 int L, int D, int n_ctx, int per_class, float inv_scale, int64_t total, DotsWs w) {
+  __shared__ double sl[3][256];
+  double d[3] = {0.0, 0.0, 0.0};
+  for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * 256) {
+    const float a = per_class ? ctx_grad_element(src_a, idx, C, L, D, n_ctx, 1, inv_scale) : rank_sum(src_a, idx, G, stride) * inv_scale;
+    const float b = per_class ? ctx_grad_element(src_b, idx, C, L, D, n_ctx, 1, inv_scale) : rank_sum(src_b, idx, G, stride) * inv_scale;
+    w.a[idx] = a;
+    w.b[idx] = b;
+    d[0] += (double)a * (double)a;
+    d[1] += (double)b * (double)b;
+    d[2] += (double)a * (double)b;
+  }
+  block_sum_f64(d, sl);
+  if (threadIdx.x == 0)
+    for (int i = 0; i < 3; ++i) w.part[i * PROGRAD_DOT_BLOCKS + blockIdx.x] = d[i];
+}
+
+// one workgroup: the n_part partial sums by the tree prograd_step_kernel adds them with -> this rank's dots [3]
+__global__ __launch_bounds__(256) void shard_prograd_finish_kernel(DotsWs w, int n_part, double* __restrict__ dots_rank) {
+  __shared__ double sl[3][256];
+  const int t = threadIdx.x;
+  double d[3];
+  for (int i = 0; i < 3; ++i) d[i] = t < n_part ? w.part[i * PROGRAD_DOT_BLOCKS + t] : 0.0;
+  block_sum_f64(d, sl);
+  if (t == 0)
+    for (int i = 0; i < 3; ++i) dots_rank[i] = d[i];
+}
+
+// one thread per element: the G ranks' dots [G, 3] added in rank order (every thread of every rank forms the same three sums), the
+// decision and the element by train_rules.h's ProGrad rule, the SGD rule
+__global__ __launch_bounds__(256) void shard_prograd_apply_kernel(DotsWs w, const double* __restrict__ dots_ranks, int G, float lambda, float* __restrict__ ctx,
+                                                                  float* __restrict__ buf, float* __restrict__ grad_out, int* __restrict__ projected,
+                                                                  double* __restrict__ dots, int64_t total, const float* __restrict__ lr, SgdArgs sgd) {
+#pragma clang fp contract(off)
+  double aa = dots_ranks[0], bb = dots_ranks[1], ab = dots_ranks[2];
+  for (int r = 1; r < G; ++r) {
+    aa += dots_ranks[3 * r];
+    bb += dots_ranks[3 * r + 1];
+    ab += dots_ranks[3 * r + 2];
+  }
+  const bool project = prograd_projects(aa, bb, ab);
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    if (projected) *projected = project ? 1 : 0;
+    if (dots) { dots[0] = aa; dots[1] = bb; dots[2] = ab; }
+  }
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= total) return;
+  const float g = prograd_element(w.a[idx], w.b[idx], project, lambda, ab, bb);
+  if (grad_out) grad_out[idx] = g;
+  if (ctx) sgd_element_fma(ctx, buf, idx, g, *lr, sgd);
+}
+
+// what the stepping entry points ask of the context and the optimiser, before anything is launched
+int check_step(const char* who, const float* ctx, const float* buf, const float* lr, int64_t total, float grad_scale, float momentum, float dampening,
+               float weight_decay, int nesterov) {
+  CLIPMI_REQUIRE(!ctx || lr, CLIPMI_ERR_ARG, "%s: null pointer (a step needs lr)", who);
+  CLIPMI_REQUIRE(total >= 1 && total < (1ll << 31) * THREADS, CLIPMI_ERR_SHAPE, "%s: %lld context elements", who, (long long)total);
+  CLIPMI_REQUIRE(std::isfinite(grad_scale) && grad_scale > 0.f, CLIPMI_ERR_ARG, "%s: grad_scale=%g (finite, > 0)", who, grad_scale);
+  if (int rc = check_sgd(who, momentum, dampening, weight_decay, nesterov)) return rc;
+  CLIPMI_REQUIRE(!ctx || momentum == 0.f || buf, CLIPMI_ERR_ARG, "%s: null pointer (a momentum needs the buffer)", who);
+  return CLIPMI_OK;
+}
+
+inline unsigned blocks_of(int64_t total) { return (unsigned)((total + THREADS - 1) / THREADS); }
+
+}  // namespace
+}  // namespace clipmi
+
+using namespace clipmi;
+
+extern "C" {
+
+int clipmi_shard_compact(const float* gathered, float* out, int C, int G, int64_t E, clipmi_stream_t stream) {
+  CLIPMI_REQUIRE(gathered && out, CLIPMI_ERR_ARG, "shard_compact: null pointer");
+  CLIPMI_REQUIRE(G >= 1 && C >= G && E >= 1, CLIPMI_ERR_SHAPE, "shard_compact: C=%d G=%d E=%lld (C >= G >= 1)", C, G, (long long)E);
+  CLIPMI_REQUIRE((int64_t)C * E < (1ll << 31) * THREADS, CLIPMI_ERR_SHAPE, "shard_compact: C * E too large");
+  hipLaunchKernelGGL(shard_compact_kernel, dim3(blocks_of((int64_t)C * E)), dim3(THREADS), 0, (hipStream_t)stream, gathered, out, C, G, (C + G - 1) / G, E);
+  return check_launch("shard_compact_kernel");
+}
+
+int clipmi_ctx_partial(const float* d_embed, float* partial, int C, int L, int D, int n_ctx, clipmi_stream_t stream) {
+  CLIPMI_REQUIRE(d_embed && partial, CLIPMI_ERR_ARG, "ctx_partial: null pointer");
+  CLIPMI_REQUIRE(C >= 1 && D >= 1 && n_ctx >= 1 && 1 + n_ctx <= L, CLIPMI_ERR_SHAPE, "ctx_partial: C=%d L=%d D=%d n_ctx=%d", C, L, D, n_ctx);
+  hipLaunchKernelGGL(ctx_partial_kernel, dim3(blocks_of((int64_t)n_ctx * D)), dim3(THREADS), 0, (hipStream_t)stream, d_embed, partial, C, L, D, n_ctx);
+  return check_launch("ctx_partial_kernel");
+}
+
+int clipmi_ctx_step_gathered(const float* partials, int G, int64_t rank_stride, float* ctx, float* buf, float* grad_out, int D, int n_ctx, float grad_scale,
+                             const float* lr, int first_step, float momentum, float dampening, float weight_decay, int nesterov, clipmi_stream_t stream) {
+  CLIPMI_REQUIRE(partials && (ctx || grad_out), CLIPMI_ERR_ARG, "ctx_step_gathered: null pointer (partials and one of ctx, grad_out are required)");
+  CLIPMI_REQUIRE(G >= 1 && D >= 1 && n_ctx >= 1, CLIPMI_ERR_SHAPE, "ctx_step_gathered: G=%d D=%d n_ctx=%d", G, D, n_ctx);
+  const int64_t total = (int64_t)n_ctx * D;
+  CLIPMI_REQUIRE(rank_stride >= total, CLIPMI_ERR_SHAPE, "ctx_step_gathered: rank_stride=%lld below the partial's %lld elements", (long long)rank_stride,
+                 (long long)total);
+  if (int rc = check_step("ctx_step_gathered", ctx, buf, lr, total, grad_scale, momentum, dampening, weight_decay, nesterov)) return rc;
+  hipLaunchKernelGGL(ctx_step_gathered_kernel, dim3(blocks_of(total)), dim3(THREADS), 0, (hipStream_t)stream, partials, G, rank_stride, ctx, buf, grad_out, total,
+                     1.f / grad_scale, lr, make_sgd_args(momentum, dampening, weight_decay, nesterov, first_step));
+  return check_launch("ctx_step_gathered_kernel");
+}
+
+size_t clipmi_shard_prograd_workspace_bytes(int64_t total) { return total >= 1 && total < (1ll << 31) * 256 ? dots_bytes(total) : 0; }
+
+int clipmi_shard_prograd_dots(const float* src_a, const float* src_b, int G, int64_t rank_stride, int C, int L, int D, int n_ctx, int per_class,
+                              float grad_scale, double* dots_rank, void* workspace, size_t workspace_bytes, clipmi_stream_t stream) {
+  const char* who = "shard_prograd_dots";
+  CLIPMI_REQUIRE(src_a && src_b && dots_rank && workspace, CLIPMI_ERR_ARG, "%s: null pointer", who);
+  CLIPMI_REQUIRE(C >= 1 && D >= 1 && n_ctx >= 1, CLIPMI_ERR_SHAPE, "%s: C=%d D=%d n_ctx=%d", who, C, D, n_ctx);
+  const int64_t total = (int64_t)n_ctx * D * (per_class ? C : 1);
+  if (per_class)
+    CLIPMI_REQUIRE(1 + n_ctx <= L, CLIPMI_ERR_SHAPE, "%s: L=%d n_ctx=%d", who, L, n_ctx);
+  else
+    CLIPMI_REQUIRE(G >= 1 && rank_stride >= total, CLIPMI_ERR_SHAPE, "%s: G=%d rank_stride=%lld (partials of %lld elements)", who, G, (long long)rank_stride,
+                   (long long)total);
+  CLIPMI_REQUIRE(std::isfinite(grad_scale) && grad_scale > 0.f, CLIPMI_ERR_ARG, "%s: grad_scale=%g (finite, > 0)", who, grad_scale);
+  CLIPMI_REQUIRE((uintptr_t)workspace % 256 == 0, CLIPMI_ERR_ARG, "%s: the workspace must be 256-byte aligned", who);
+  const size_t need = clipmi_shard_prograd_workspace_bytes(total);
+  CLIPMI_REQUIRE(need > 0 && workspace_bytes >= need, CLIPMI_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, need);
+  const DotsWs w = dots_carve(workspace, total);
+  const int64_t blocks = (total + 255) / 256;
+  const int n_part = (int)(blocks < PROGRAD_DOT_BLOCKS ? blocks : PROGRAD_DOT_BLOCKS);
+  hipLaunchKernelGGL(shard_prograd_dots_kernel, dim3((unsigned)n_part), dim3(256), 0, (hipStream_t)stream, src_a, src_b, G, rank_stride, C, L, D, n_ctx,
+                     per_class ? 1 : 0, 1.f / grad_scale, total, w);
+  if (int rc = check_launch("shard_prograd_dots_kernel")) return rc;
+  hipLaunchKernelGGL(shard_prograd_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, w, n_part, dots_rank);
+  return check_launch("shard_prograd_finish_kernel");
+}
+
+int clipmi_shard_prograd_apply(const double* dots_ranks, int G, float lambda, float* ctx, float* buf, float* grad_out, int* projected, double* dots,
+                               int64_t total, const float* lr, int first_step, float momentum, float dampening, float weight_decay, int nesterov,
+                               void* workspace, size_t workspace_bytes, clipmi_stream_t stream) {
+  const char* who = "shard_prograd_apply";
+  CLIPMI_REQUIRE(dots_ranks && workspace, CLIPMI_ERR_ARG, "%s: null pointer", who);
+  CLIPMI_REQUIRE(ctx || grad_out || projected || dots, CLIPMI_ERR_ARG, "%s: null pointer (nothing to write)", who);
+  CLIPMI_REQUIRE(G >= 1, CLIPMI_ERR_SHAPE, "%s: G=%d", who, G);
+  CLIPMI_REQUIRE(std::isfinite(lambda), CLIPMI_ERR_ARG, "%s: lambda=%g (finite)", who, lambda);
+  if (int rc = check_step(who, ctx, buf, lr, total, 1.f, momentum, dampening, weight_decay, nesterov)) return rc;
+  CLIPMI_REQUIRE((uintptr_t)workspace % 256 == 0, CLIPMI_ERR_ARG, "%s: the workspace must be 256-byte aligned", who);
+  const size_t need = clipmi_shard_prograd_workspace_bytes(total);
+  CLIPMI_REQUIRE(need > 0 && workspace_bytes >= need, CLIPMI_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, need);
+  hipLaunchKernelGGL(shard_prograd_apply_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, dots_carve(workspace, total), dots_ranks,
+                     G, lambda, ctx, buf, grad_out, projected, dots, total, lr, make_sgd_args(momentum, dampening, weight_decay, nesterov, first_step));
+  return check_launch("shard_prograd_apply_kernel");
+}
+
+}  // extern "C"

@@ -45,6 +45,9 @@ inline SgdArgs make_sgd_args(float momentum, float dampening, float weight_decay
   return SgdArgs{momentum, (float)(1.0 - (double)dampening), weight_decay, nesterov ? 1 : 0, first_step ? 1 : 0};
 }
 
+// ProGrad's float64 dots: the first launch's grid is at most this many workgroups, a function of the context's size alone
+constexpr int PROGRAD_DOT_BLOCKS = 256;
+
 #ifdef __HIPCC__
 // torch.optim.SGD's rule on one element (torch rounds the products of add(other, alpha) before it adds)
 __device__ __forceinline__ void sgd_element(float* __restrict__ w, float* __restrict__ buf, int64_t idx, float grad, float lr, const SgdArgs& a) {
@@ -89,6 +92,20 @@ __device__ __forceinline__ float ctx_grad_element(const float* __restrict__ d_em
     for (int64_t c = 0; c < C; ++c) g += d_embed[((c * L) + 1 + j) * D + d];
   }
   return g * inv_scale;
+}
+
+// ProGrad's rule (reference prograd.py:371-409) on the float64 dots a.a, b.b, a.b of its two context gradients (prompt_train.hip's
+// prograd_step_kernel, shard_train.hip): the reference compares dot(a / |a|, b / |b|) with 0, which is a.b < 0 unless a norm is zero or
+// something is not finite, where its comparison is false and the plain a is applied.  The element: a - lambda (a.b / b.b) b, the scalar
+// in float64, the product rounded before the subtraction
+__device__ __forceinline__ bool prograd_projects(double aa, double bb, double ab) {
+  return isfinite(aa) && isfinite(bb) && isfinite(ab) && ab < 0.0 && aa > 0.0 && bb > 0.0;
+}
+__device__ __forceinline__ float prograd_element(float a, float b, bool project, float lambda, double ab, double bb) {
+#pragma clang fp contract(off)
+  if (!project) return a;
+  const float k = (float)((double)lambda * (ab / bb));
+  return a - k * b;
 }
 
 // torch.optim.Adam's rule on one element: g += wd w;  m += (g - m)(1 - b1)  (lerp_ with a weight below one half);

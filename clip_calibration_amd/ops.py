@@ -1642,6 +1642,135 @@ def prograd_step(d_embed_xe: torch.Tensor, d_embed_kl: torch.Tensor, n_prompts: 
     return (grad, proj, dots) if want_report else None
 
 
+# ---- the class-sharded CoOp-family fit (csrc/shard_train.hip, DESIGN.md "Class-sharded CoOp fit")
+
+def shard_compact(gathered: torch.Tensor, n_rows: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The gathered, padded fp32 [G, ceil(n_rows / G), E] block -> fp32 [n_rows, E]: row c is the row of the rank that owns class c
+    under the balanced split.  The padding rows are never read.  One launch."""
+    gathered = _dev(gathered, "gathered", (torch.float32,))
+    if gathered.dim() != 3 or not 1 <= gathered.shape[0] <= n_rows or gathered.shape[1] != -(-n_rows // gathered.shape[0]):
+        raise ValueError(f"shard_compact: gathered {tuple(gathered.shape)} must be [G, ceil({n_rows} / G), E] with G <= {n_rows}")
+    G, _, E = gathered.shape
+    if out is None:
+        out = torch.empty(n_rows, E, dtype=torch.float32, device=gathered.device)
+    else:
+        _in_place(out, torch.float32, "shard_compact: out must be a contiguous fp32 tensor on the GPU", numel=n_rows * E)
+    check(lib.clipmi_shard_compact(gathered.data_ptr(), out.data_ptr(), int(n_rows), G, E, _stream()), "clipmi_shard_compact")
+    return out
+
+
+def ctx_partial(d_embed: torch.Tensor, n_prompts: int, n_ctx: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """A rank's partial context gradient fp32 [n_ctx, D] from its own ``d_embed`` fp32 [n_prompts * L, D]: the classes' context rows
+    added in ascending order, unscaled.  ``out``: where it is written (the rank's send block)."""
+    d_embed = _dev(d_embed, "d_embed", (torch.float32,))
+    M, D = d_embed.shape
+    if n_prompts < 1 or M % n_prompts:
+        raise ValueError(f"ctx_partial: {M} rows do not split into {n_prompts} prompts")
+    if out is None:
+        out = torch.empty(n_ctx, D, dtype=torch.float32, device=d_embed.device)
+    else:
+        _in_place(out, torch.float32, "ctx_partial: out must be a contiguous fp32 tensor on the GPU", numel=n_ctx * D)
+    check(lib.clipmi_ctx_partial(d_embed.data_ptr(), out.data_ptr(), int(n_prompts), M // n_prompts, D, int(n_ctx), _stream()), "clipmi_ctx_partial")
+    return out
+
+
+def _step_targets(who: str, shape, ctx, buf, lr):
+    """The pointers of ``ctx`` (of ``shape``), ``buf`` and ``lr``, or None each without a context, after the checks the sharded steps share."""
+    if ctx is None:
+        return None, None, None
+    _in_place(ctx, torch.float32, f"{who}: ctx must be a contiguous fp32 tensor on the GPU")
+    if tuple(ctx.shape) != tuple(shape):
+        raise ValueError(f"{who}: ctx {tuple(ctx.shape)} must be {tuple(shape)}")
+    if buf is not None:
+        _in_place(buf, torch.float32, f"{who}: buf must be a contiguous fp32 tensor on the GPU", numel=ctx.numel())
+    lr = _dev(lr, "lr", (torch.float32,))
+    if lr.numel() != 1:
+        raise ValueError(f"{who}: lr must hold one rate")
+    return ctx.data_ptr(), None if buf is None else buf.data_ptr(), lr.data_ptr()
+
+
+def ctx_step_gathered(partials: torch.Tensor, n_ctx: int, D: int, grad_scale: float, ctx: Optional[torch.Tensor] = None,
+                      buf: Optional[torch.Tensor] = None, lr: Optional[torch.Tensor] = None, first_step: bool = False, momentum: float = 0.0,
+                      dampening: float = 0.0, weight_decay: float = 0.0, nesterov: bool = False, want_grad: bool = True) -> Optional[torch.Tensor]:
+    """``ctx_step`` from the gathered partials fp32 [G, >= n_ctx * D] (rank r's ``ctx_partial`` first in row r): the partials added in
+    rank order, divided by ``grad_scale``, and with ``ctx`` [n_ctx, D] torch.optim.SGD's step on it in place.  A row wider than
+    ``n_ctx * D`` is a padded rank stride: the elements behind a rank's partial are not read."""
+    who = "ctx_step_gathered"
+    _in_place(partials, torch.float32, f"{who}: partials must be a contiguous fp32 tensor on the GPU")
+    n_ctx, D = int(n_ctx), int(D)
+    if n_ctx < 1 or D < 1 or partials.dim() != 2 or partials.shape[0] < 1 or partials.shape[1] < n_ctx * D:
+        raise ValueError(f"{who}: partials {tuple(partials.shape)} must be [G >= 1, >= n_ctx * D = {n_ctx} * {D}]")
+    G, stride = partials.shape
+    if ctx is None and not want_grad:
+        raise ValueError(f"{who}: nothing to do (no ctx and no gradient wanted)")
+    pc, pb, pl = _step_targets(who, (n_ctx, D), ctx, buf, lr)
+    grad = torch.empty(n_ctx, D, dtype=torch.float32, device=partials.device) if want_grad else None
+    check(lib.clipmi_ctx_step_gathered(partials.data_ptr(), G, stride, pc, pb, None if grad is None else grad.data_ptr(), int(D), int(n_ctx),
+                                       float(grad_scale), pl, int(bool(first_step)), float(momentum), float(dampening), float(weight_decay),
+                                       int(bool(nesterov)), _stream()), "clipmi_ctx_step_gathered")
+    return grad
+
+
+def shard_prograd_workspace(total: int, device) -> torch.Tensor:
+    """The workspace ``shard_prograd_dots`` and ``shard_prograd_apply`` share for a context of ``total`` elements."""
+    return torch.empty(max(lib.clipmi_shard_prograd_workspace_bytes(int(total)), 256), dtype=torch.uint8, device=device)
+
+
+def shard_prograd_dots(src_a: torch.Tensor, src_b: torch.Tensor, n_prompts: int, n_ctx: int, per_class: bool, grad_scale: float,
+                       workspace: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ProGrad's a and b into ``workspace`` and this rank's float64 dots [3] (a.a, b.b, a.b).  ``per_class``: from the rank's own two
+    ``d_embed`` fp32 [n_prompts * L, D]; else from the gathered partials of the two losses, fp32 [G, >= n_ctx * D] views of equal strides
+    (``n_prompts`` is not read)."""
+    who = "shard_prograd_dots"
+    if out is None:
+        out = torch.empty(3, dtype=torch.float64, device=src_a.device)
+    else:
+        _in_place(out, torch.float64, f"{who}: out must be a contiguous float64 tensor on the GPU", numel=3)
+    if per_class:
+        src_a, src_b = _dev(src_a, "d_embed_xe", (torch.float32,)), _dev(src_b, "d_embed_kl", (torch.float32,))
+        M, D = src_a.shape
+        if src_b.shape != src_a.shape or n_prompts < 1 or M % n_prompts:
+            raise ValueError(f"{who}: two d_embed of [{n_prompts} * L, D] expected, got {tuple(src_a.shape)} and {tuple(src_b.shape)}")
+        G, stride, L, Cn = 1, 0, M // n_prompts, int(n_prompts)
+    else:
+        for t in (src_a, src_b):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 3 and t.stride(2) == 1
+                    and t.stride(1) == t.shape[2] and t.shape[1] == n_ctx):
+                raise TypeError(f"{who}: the partials must be fp32 [G, n_ctx, D] views on the GPU with contiguous rows")
+        if src_a.shape != src_b.shape or src_a.stride(0) != src_b.stride(0):
+            raise ValueError(f"{who}: the two partials differ in shape or stride")
+        G, stride, D, L, Cn = src_a.shape[0], src_a.stride(0), src_a.shape[2], 1 + n_ctx, 1
+    check(lib.clipmi_shard_prograd_dots(src_a.data_ptr(), src_b.data_ptr(), G, stride, Cn, L, D, int(n_ctx), int(bool(per_class)), float(grad_scale),
+                                        out.data_ptr(), workspace.data_ptr(), workspace.numel(), _stream()), "clipmi_shard_prograd_dots")
+    return out
+
+
+def shard_prograd_apply(dots_ranks: torch.Tensor, lam: float, workspace: torch.Tensor, shape, ctx: Optional[torch.Tensor] = None,
+                        buf: Optional[torch.Tensor] = None, lr: Optional[torch.Tensor] = None, first_step: bool = False, momentum: float = 0.0,
+                        dampening: float = 0.0, weight_decay: float = 0.0, nesterov: bool = False, want_report: bool = True):
+    """The ranks' dots float64 [G, 3] added in rank order, ProGrad's decision and the step on ``ctx`` (of ``shape``, the elements that
+    ``shard_prograd_dots`` left a and b of in ``workspace``).  Returns ``(grad, projected, dots)`` as ``prograd_step`` when ``want_report``."""
+    who = "shard_prograd_apply"
+    _in_place(dots_ranks, torch.float64, f"{who}: dots_ranks must be a contiguous float64 tensor on the GPU")
+    if dots_ranks.dim() != 2 or dots_ranks.shape[1] != 3:
+        raise ValueError(f"{who}: dots_ranks {tuple(dots_ranks.shape)} must be [G, 3]")
+    shape, dev = tuple(int(x) for x in shape), dots_ranks.device
+    total = int(np.prod(shape))
+    if ctx is None and not want_report:
+        raise ValueError(f"{who}: nothing to do (no ctx and no report)")
+    pc, pb, pl = _step_targets(who, shape, ctx, buf, lr)
+    grad = proj = dots = None
+    if want_report:
+        grad = torch.empty(shape, dtype=torch.float32, device=dev)
+        proj = torch.empty(1, dtype=torch.int32, device=dev)
+        dots = torch.empty(3, dtype=torch.float64, device=dev)
+    check(lib.clipmi_shard_prograd_apply(dots_ranks.data_ptr(), dots_ranks.shape[0], float(lam), pc, pb, None if grad is None else grad.data_ptr(),
+                                         None if proj is None else proj.data_ptr(), None if dots is None else dots.data_ptr(), total, pl,
+                                         int(bool(first_step)), float(momentum), float(dampening), float(weight_decay), int(bool(nesterov)),
+                                         workspace.data_ptr(), workspace.numel(), _stream()), "clipmi_shard_prograd_apply")
+    return (grad, proj, dots) if want_report else None
+
+
 PROMPT_POSITIONS = {"front": 0, "middle": 1, "end": 2}   # `position` of clipmi_prompt_place and clipmi_proda_embed's pos (plain integers there)
 
 

@@ -9,6 +9,8 @@ coop.py:268-272, tempscaling.py:117-120)."""
 from __future__ import annotations
 
 import ctypes as C
+import os
+import signal
 from typing import Optional, Tuple
 
 import torch
@@ -120,6 +122,51 @@ class EmbeddingExchange:
             from . import _lib
             _lib.lib.clipmi_comm_destroy(self._comm)
             self._comm = None
+
+
+def shard_gather(exchange: EmbeddingExchange):
+    """The ``gather(src, dst, bytes_per_rank, stream)`` of a class-sharded CoOp fit (``coopfit.Shard``) over an exchange's RCCL
+    communicator: ``clipmi_allgather`` on the caller's stream.  One process per GPU; the torch backend is refused, since the fit's
+    second gather carries raw bytes of two types on a stream the library owns."""
+    if exchange._comm is None:
+        raise ValueError("shard_gather: the exchange has no RCCL communicator (backend 'torch'); the sharded fit needs backend='rccl'")
+    from . import _lib
+
+    def gather(src: torch.Tensor, dst: torch.Tensor, nbytes: int, stream: int) -> None:
+        _lib.check(_lib.lib.clipmi_allgather(exchange._comm, src.data_ptr(), dst.data_ptr(), int(nbytes), stream), "clipmi_allgather")
+    return gather
+
+
+_VISIBLE = ("HIP_VISIBLE_DEVICES", "CUDA_VISIBLE_DEVICES")
+
+
+def rank_env(k: int, port: Optional[int] = None, env=None) -> dict:
+    """The environment of a child process that is to see ONE GPU, the k-th of those this process sees: a visible-device list the parent
+    already carries is indexed, never overwritten (``HIP_VISIBLE_DEVICES=4,5`` and k = 1 give 5); without one the child gets
+    ``HIP_VISIBLE_DEVICES=k``.  ``port``: the loopback rendezvous of the ranks' gloo group (``MASTER_ADDR``, ``MASTER_PORT``)."""
+    out = dict(os.environ if env is None else env)
+    lists = {v: [d.strip() for d in out[v].split(",") if d.strip()] for v in _VISIBLE if out.get(v, "").strip()}
+    for v, devices in lists.items():
+        if not 0 <= k < len(devices):
+            raise ValueError(f"rank_env: device {k} outside {v}={out[v]}")
+        out[v] = devices[k]
+    if not lists:
+        out["HIP_VISIBLE_DEVICES"] = str(k)
+    if port is not None:
+        out.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    return out
+
+
+def end_session(p) -> None:
+    """End a child that was started with ``start_new_session=True`` together with everything it started -- a ``timeout`` wrapper AND
+    the rank process under it: the whole process group is killed and the child reaped.  Killing the wrapper alone would orphan the rank,
+    possibly inside a collective whose peer is gone, with its time limit removed."""
+    if p.poll() is None:
+        try:
+            os.killpg(p.pid, signal.SIGKILL)
+        except ProcessLookupError:
+            pass
+    p.wait()
 
 
 def all_gather_embeddings(local: torch.Tensor, group=None) -> torch.Tensor:

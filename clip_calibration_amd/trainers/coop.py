@@ -193,9 +193,21 @@ class CustomCLIP(nn.Module):
         Validation (the cached route): ``val_loader=`` (an iterable of (image, label) batches, run through the image tower once before the
         first epoch, as the train features are) or ``val=(val_features, val_labels)``, with ``val_bins``, ``final_model`` ("last_step" or
         "best_val", the reference's TEST.FINAL_MODEL), ``val_criterion`` and ``return_monitor`` as ``coopfit.fit_context`` takes them.
-        ``final_model="best_val"`` installs the best epoch's context into the prompt learner."""
+        ``final_model="best_val"`` installs the best epoch's context into the prompt learner.
+
+        ``shard=coopfit.Shard(world, rank, gather)`` on either route: the class-sharded fit, one process per GPU, every rank making
+        this call on the same data (``coopfit``'s module docstring; KgCoOp's and ProGrad's ``fit_context`` pass it on).  What ``shard``
+        refuses -- validation by ``val_loader=`` included -- is refused here, before either tower runs.  With a ``LocalGather`` the one
+        call makes and steps all the ranks' states, on either route."""
         import math
         val_loader = fit_args.pop("val_loader", None)
+        shard = fit_args.get("shard")
+        if shard is not None:
+            from ..coopfit import DEFAULT_GRAD_SCALE, _check_shard
+            _check_shard("fit_context", shard, self.prompt_learner.tokenized_prompts.shape[0],
+                         fit_args.get("class_token_position", getattr(self.prompt_learner, "class_token_position", "end")),
+                         fit_args.get("grad_scale", DEFAULT_GRAD_SCALE), val_loader if val_loader is not None else fit_args.get("val"),
+                         fit_args.get("final_model", "last_step"))
         if val_loader is not None and fit_args.get("val") is not None:
             raise ValueError("fit_context: val_loader and val are two ways to give one validation set")
         monitored = val_loader is not None or any(k in fit_args for k in ("val", "val_bins", "final_model", "val_criterion", "return_monitor"))
@@ -210,11 +222,11 @@ class CustomCLIP(nn.Module):
         fit_args.setdefault("name_lens", getattr(self.prompt_learner, "name_lens", None))
         if transform is not None:
             from ..augment import fit_with_transform
-            from ..coopfit import CoOpFitState
+            from ..coopfit import CoOpFitState, shard_states
             run, epochs, lr = _fit.split_fit_args(fit_args, 200, 0.002)
-            state = CoOpFitState(self.clip_model, ids, ctx.detach(), **fit_args)
+            state = shard_states(lambda sh: CoOpFitState(self.clip_model, ids, ctx.detach(), **dict(fit_args, shard=sh)), shard)
             losses = fit_with_transform(state, self.clip_model.image_features_f32, ids.shape[0], train_loader, transform, epochs, lr, **run)
-            fitted = _fit.pack(state.ctx, losses)
+            fitted = _fit.pack(state.gathered_context(), losses)   # state.ctx, but for a class-specific context under shard=
         else:
             from ..coopfit import fit_context
             feats, labels = _fit.cached_features("fit_context", self.clip_model, train_loader)

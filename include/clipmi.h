@@ -1198,6 +1198,43 @@ int clipmi_prograd_step(const float* d_embed_xe, const float* d_embed_kl, float*
                         int first_step, float momentum, float dampening, float weight_decay, int nesterov, void* workspace,
                         size_t workspace_bytes, clipmi_stream_t stream);
 
+/* The class-sharded fit of CoOp, KgCoOp and ProGrad (DESIGN.md "Class-sharded CoOp fit"): G ranks, rank r owning the contiguous classes
+ * the balanced split gives it (the first C mod G ranks one class more, C >= G), two all-gathers per step.  Everything below is fp32 with
+ * fixed summation orders and no atomics; with G = 1 each chain is the unsharded entry point's, bit for bit.
+ *
+ * Compaction: gathered fp32 [G, P, E], P = ceil(C / G), block r holding rank r's rows first and padding behind them that is never read;
+ * out fp32 [C, E], row c the row of the rank that owns class c.  One launch. */
+int clipmi_shard_compact(const float* gathered, float* out, int C, int G, int64_t E, clipmi_stream_t stream);
+
+/* A rank's partial context gradient (generic context): partial fp32 [n_ctx, D], partial[j, :] = sum_c d_embed[c * L + 1 + j, :] over the
+ * C classes of d_embed fp32 [C * L, D] -- the rank's own -- in ascending order, unscaled.  1 + n_ctx <= L.  One launch. */
+int clipmi_ctx_partial(const float* d_embed, float* partial, int C, int L, int D, int n_ctx, clipmi_stream_t stream);
+
+/* The gathered partials' sum and the step: partials fp32, rank r's [n_ctx, D] at partials + r * rank_stride (elements, >= n_ctx * D);
+ * grad = (partial_0 + partial_1 + .. + partial_{G-1}) / grad_scale, added in rank order, then clipmi_ctx_step's SGD rule on ctx
+ * [n_ctx, D] with the same optional outputs and NULL conventions.  Every rank that is given the same partials writes the same bits,
+ * whatever order the bytes arrived in.  One launch. */
+int clipmi_ctx_step_gathered(const float* partials, int G, int64_t rank_stride, float* ctx, float* buf, float* grad_out, int D, int n_ctx,
+                             float grad_scale, const float* lr, int first_step, float momentum, float dampening, float weight_decay,
+                             int nesterov, clipmi_stream_t stream);
+
+/* ProGrad under the sharding, in two calls with at most one all-gather between them.  The first forms a and b (kept in the workspace) and
+ * this rank's float64 dots {a.a, b.b, a.b} into dots_rank [3], over the partition clipmi_prograd_step uses.  per_class == 0 (generic
+ * context): src_a, src_b are the gathered partials of the two losses as clipmi_ctx_step_gathered takes them, a and b their rank-ordered
+ * sums over 1 / grad_scale, n_ctx * D elements, the same on every rank (nothing more to gather: the second call takes G = 1).
+ * per_class != 0: src_a, src_b are the rank's own two d_embed fp32 [C * L, D], a and b its own C * n_ctx * D elements; G and rank_stride
+ * are not read, and dots_rank is what the ranks gather.  The second call adds dots_ranks float64 [G, 3] in rank order, decides as
+ * clipmi_prograd_step decides and steps the `total` elements of ctx that the first call's a and b cover, with clipmi_prograd_step's
+ * optional outputs.  workspace (256-byte aligned, the same for both calls): clipmi_shard_prograd_workspace_bytes(total) bytes (0 for a
+ * total outside the range).  Two launches and one launch. */
+size_t clipmi_shard_prograd_workspace_bytes(int64_t total);
+int clipmi_shard_prograd_dots(const float* src_a, const float* src_b, int G, int64_t rank_stride, int C, int L, int D, int n_ctx,
+                              int per_class, float grad_scale, double* dots_rank, void* workspace, size_t workspace_bytes,
+                              clipmi_stream_t stream);
+int clipmi_shard_prograd_apply(const double* dots_ranks, int G, float lambda, float* ctx, float* buf, float* grad_out, int* projected,
+                               double* dots, int64_t total, const float* lr, int first_step, float momentum, float dampening,
+                               float weight_decay, int nesterov, void* workspace, size_t workspace_bytes, clipmi_stream_t stream);
+
 /* One training step of CoOp, KgCoOp or ProGrad as ONE call: clipmi_text_encoder_train, clipmi_prompt_head, clipmi_text_encoder_backward
  * (twice for ProGrad, one after the other: they share the tower's workspace and read the same stash) and clipmi_ctx_step or
  * clipmi_prograd_step, enqueued in this order on `stream` -- the same launches, the same bits as the calls one by one.  losses fp32 [3]
