@@ -263,6 +263,10 @@ _SIGNATURES = {
                                                     _vp, _f, _f, _i, _i, _vp, _f, _vp, _f, _f, _f, _i, _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
     "clipmi_block_step_scaled_workspace_bytes": (_sz, [_i64]),
     "clipmi_block_step_scaled": (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _f, _f, _i, _vp, _f, _f, _f, _i, _vp, _sz, _vp]),
+    "clipmi_block_step_adam": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _f, _vp, _i64, _vp, _i64, C.c_double, C.c_double, C.c_double, _f, _i, _vp]),
+    "clipmi_block_step_adam_scaled_workspace_bytes": (_sz, [_i64]),
+    "clipmi_block_step_adam_scaled": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _f, _f, _i, _vp, _vp, _i64, C.c_double, C.c_double, C.c_double, _f, _i,
+                                           _vp, _sz, _vp]),
     "clipmi_cocoop_train_step_scaled_bytes": (_sz, [_vp, _i, _i, _i, _i, _i]),
     "clipmi_cocoop_train_step_scaled": (_i, [_vp, C.POINTER(TextDgrad), _vp, _i, _vp, _vp, _i, _i, _vp, _i, _i, _vp, _i64, _vp, _i, _f, _vp, _f, _f, _i,
                                              _vp, _f, _f, _f, _i, _vp, _vp, _vp, _sz, _vp, _sz, _vp]),

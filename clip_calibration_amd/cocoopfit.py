@@ -48,7 +48,7 @@ import torch
 
 from . import _lib, fitloop, fitmonitor, ops
 from ._lib import check, lib
-from .coopfit import DYNAMIC, MAX_LIVE_ROWS, _DT, _BlockScaler, _Tower, _check_batch, _check_grad_scale, _is_dynamic, _live_rows, _scale_args, operand_stats_dict
+from .coopfit import DYNAMIC, MAX_LIVE_ROWS, _DT, _AdamBlock, _BlockScaler, _Tower, _check_batch, _check_grad_scale, _is_dynamic, _live_rows, _scale_args, operand_stats_dict
 from .coopfit import _check_prompts as _check_coop_prompts
 from .fitloop import _need_gpu, steps_per_epoch
 
@@ -178,13 +178,15 @@ class CoCoOpFitState(fitmonitor.Monitored):
     ``best_params``, ``val_row_results``: ``fitmonitor.Monitored`` on a ``fitmonitor.ImageMonitor``, whose row results it fills)."""
     _who, _history = "CoCoOpFitState", fitmonitor.ImageMonitor
 
-    def __init__(self, clip_model, tokenized_prompts, params, logit_scale: float = 4.6052, momentum: float = 0.9, dampening: float = 0.0,
-                 weight_decay: float = 5e-4, nesterov: bool = False, grad_scale: float = DEFAULT_GRAD_SCALE, seq_rows: Optional[int] = None,
-                 scaler: Optional[dict] = None):
+    def __init__(self, clip_model, tokenized_prompts, params, logit_scale: float = 4.6052, momentum: float = 0.9,
+                 dampening: float = 0.0, weight_decay: float = 5e-4, nesterov: bool = False, grad_scale: float = DEFAULT_GRAD_SCALE,
+                 seq_rows: Optional[int] = None, scaler: Optional[dict] = None, optimizer: str = "sgd", betas=(0.9, 0.999), eps: float = 1e-8):
+        """``optimizer``: "sgd" (``momentum``, ``dampening``, ``nesterov``), "adam" or "adamw" (``betas``, ``eps``;
+        ``weight_decay`` keeps the fit's default of 5e-4 under all three -- torch's AdamW default of 1e-2 is NOT taken over)."""
         who = "CoCoOpFitState"
         self.C, self.n_ctx, self.H, self._last = _check_prompts(who, clip_model, tokenized_prompts, params, seq_rows)
         self.dynamic, self.grad_scale, self.scaler = _scale_args(who, grad_scale, scaler)
-        fitloop.check_sgd(who, momentum, dampening, weight_decay, nesterov)
+        self.optimizer, momentum, dampening, nesterov, betas = fitloop.check_optimizer(who, optimizer, momentum, dampening, nesterov, weight_decay, betas, eps)
         self.scale = fitloop.exp_logit_scale(who, logit_scale)
         dev = clip_model.device
         if dev.type != "cuda":
@@ -198,6 +200,7 @@ class CoCoOpFitState(fitmonitor.Monitored):
         self._towers: Dict[int, _CoCoOpTower] = {}
         self.steps = 0
         self._scaler = _BlockScaler(self.scaler, dev) if self.dynamic else None
+        self._adam = _AdamBlock(self.optimizer, betas, eps, weight_decay, self.block) if self.optimizer != "sgd" else None
         self._val = None            # what a validation keeps between epochs: the inference operands and one workspace per chunk size
         self.val_stream_f16 = True  # trainers.cocoop.CustomCLIP's text_stream_f16: validation runs the tower as that forward does
         self.val_batch_size = None  # validate's chunk when its argument is None (None: the largest training batch seen)
@@ -304,8 +307,12 @@ class CoCoOpFitState(fitmonitor.Monitored):
         Returns the batch loss, fp32 [1] on the device, when ``want_loss``.  Under ``grad_scale="dynamic"`` the head and the reduce run at
         ``grad_scale = 1``, ``d_text`` is multiplied by the device block's scale in between and clipmi_block_step_scaled decides on the
         device whether the step is applied (one call: clipmi_cocoop_train_step_scaled); a skipped step still counts in ``steps`` and still
-        returns its loss; whether it was applied is in ``scaler_state()``."""
+        returns its loss; whether it was applied is in ``scaler_state()``.  Under ``optimizer="adam" | "adamw"`` the reduce leaves the
+        block's gradient as ``gradients`` returns it and clipmi_block_step_adam applies it (clipmi_block_step_adam_scaled under the dynamic
+        scale); ``one_call`` is then refused: the one-call steps stay SGD."""
         who = "CoCoOpFitState.step"
+        if one_call and self._adam is not None:
+            raise ValueError(f"{who}: one_call=True with optimizer={self.optimizer!r}: the one-call steps stay SGD")
         labels_d = _check_batch(who, features, labels, self.C, self.E)
         _need_gpu(features, "features")
         if features.dtype != torch.float32 or features.stride(1) != 1:
@@ -315,7 +322,14 @@ class CoCoOpFitState(fitmonitor.Monitored):
         t, m, first = self.tower(int(features.shape[0])), self.model, self.steps == 0
         sgd = (self.momentum, self.dampening, self.weight_decay, self.nesterov)
         loss = torch.empty(1, dtype=torch.float32, device=dev)
-        if self.dynamic and one_call:
+        if self._adam is not None:
+            gs = 1.0 if self.dynamic else self.grad_scale
+            text = t.forward(self._views, features)
+            _, d_text = ops.cocoop_head(features, labels_d, text, self.scale, gs, loss)
+            if self.dynamic:
+                ops.grad_scale_rows(d_text, self._scaler.block)
+            self._adam.step(t.reduce(t.backward(d_text), self._views[NAMES[3]], gs), self.block, lr_d, 1.0, self._scaler)
+        elif self.dynamic and one_call:
             ws, sc = t.one_call_workspace(scaled=True), self._scaler
             with m._launch_lock:
                 check(lib.clipmi_cocoop_train_step_scaled(m._handle, C.byref(t.dgrad[0]), t.base.data_ptr(), _DT[t.base.dtype], self.block.data_ptr(),
@@ -374,11 +388,11 @@ def init_params(clip_model, n_ctx: int = 4, ctx_init_ids: Optional[torch.Tensor]
 
 
 def fit_prompt_learner(features: torch.Tensor, labels, clip_model, tokenized_prompts, params=None, n_ctx: int = 4, logit_scale: float = 4.6052,
-                       lr: float = 0.002, epochs: int = 10, batch_size: int = 1, momentum: float = 0.9, dampening: float = 0.0,
-                       weight_decay: float = 5e-4, nesterov: bool = False, grad_scale: float = DEFAULT_GRAD_SCALE, seq_rows: Optional[int] = None,
+                       lr: float = 0.002, epochs: int = 10, batch_size: int = 1, momentum: float = 0.9,
+                       dampening: float = 0.0, weight_decay: float = 5e-4, nesterov: bool = False, grad_scale: float = DEFAULT_GRAD_SCALE, seq_rows: Optional[int] = None,
                        lr_per_epoch: Optional[Sequence[float]] = None, order=None, drop_last: bool = False, return_history: bool = False,
                        scaler: Optional[dict] = None, val=None, val_batch_size: Optional[int] = None, val_bins: int = 10,
-                       final_model: str = "last_step", val_criterion: str = "accuracy", return_monitor: bool = False, val_stream_f16: bool = True):
+                       final_model: str = "last_step", val_criterion: str = "accuracy", return_monitor: bool = False, val_stream_f16: bool = True, optimizer: str = "sgd", betas=(0.9, 0.999), eps: float = 1e-8):
     """Train CoCoOp's prompt learner on cached ``features`` fp32 [N, E] and ``labels`` [N], starting from ``params`` (a dict of the five
     tensors, not modified; None = ``init_params(clip_model, n_ctx)``).  The loop and its arguments are ``coopfit.fit_context``'s:
     ``epochs`` passes of ``torch.optim.SGD`` over batches of ``batch_size``, ``lr_per_epoch`` (None: ``cosine_warmup_schedule``),
@@ -395,7 +409,11 @@ def fit_prompt_learner(features: torch.Tensor, labels, clip_model, tokenized_pro
     ``final_model``, ``val_criterion`` and ``return_monitor`` as ``coopfit.fit_context`` takes them: "best_val" returns the five tensors of
     the epoch that was strictly better than every earlier one (the starting values when no epoch was taken) and is refused without
     ``val``; ``return_monitor`` adds ``CoCoOpFitState.monitor()``'s dict behind the history.  ``val_stream_f16``: the validation's tower
-    call asks for the fp16 residual stream where the model allows it, as ``trainers.cocoop.CustomCLIP(text_stream_f16=True)`` does."""
+    call asks for the fp16 residual stream where the model allows it, as ``trainers.cocoop.CustomCLIP(text_stream_f16=True)`` does.
+
+    ``optimizer``, ``betas``, ``eps``: "sgd" (the default; ``momentum``, ``dampening``, ``nesterov``), "adam" or
+    "adamw", as ``coopfit.fit_context`` takes them; ``weight_decay`` keeps this fit's default of 5e-4 under all three (torch's AdamW
+    default of 1e-2 is NOT taken over).  DESIGN.md "Adam steps for the prompt fits"."""
     who = "fit_prompt_learner"
     fitmonitor.check_args(who, val, val_bins, final_model, val_criterion)
     if val is not None and val_batch_size is not None:
@@ -408,7 +426,7 @@ def fit_prompt_learner(features: torch.Tensor, labels, clip_model, tokenized_pro
         raise ValueError(f"{who}: features must be a [N >= 1, E = {E}] tensor")
     N = features.shape[0]
     epochs, batch_size = fitloop.check_run(who, epochs, batch_size)
-    fitloop.check_sgd(who, momentum, dampening, weight_decay, nesterov)
+    fitloop.check_optimizer(who, optimizer, momentum, dampening, nesterov, weight_decay, betas, eps)
     _scale_args(who, grad_scale, scaler)
     lab = fitloop._labels(who, labels, N, Cn)
     order = fitloop.check_order(who, order, epochs, N)
@@ -422,7 +440,7 @@ def fit_prompt_learner(features: torch.Tensor, labels, clip_model, tokenized_pro
         return fitmonitor.pack(out, np.zeros(0, np.float32), fitmonitor.empty_monitor(val_bins), return_history, return_monitor)
     _need_gpu(features, "features")
     state = CoCoOpFitState(clip_model, tokenized_prompts, params, logit_scale, momentum, dampening, weight_decay, nesterov, grad_scale, seq_rows,
-                           scaler)
+                           scaler, optimizer, betas, eps)
     end_epoch = None
     if val is not None:
         _need_gpu(vf, "val_features")

@@ -66,6 +66,12 @@ others' ``step`` is refused).
 Refused under ``shard``, each by name: C < world, a class-token position other than "end", ``grad_scale="dynamic"``, ``val=`` /
 ``final_model="best_val"``, ``one_call=True``.  DESIGN.md "Class-sharded CoOp fit".
 
+``optimizer``: "sgd" (the default: everything above, the same launches and bits), "adam" or "adamw" with ``betas`` and ``eps``, the
+reference's OPTIM.NAME, for all three methods.  The context's gradient is formed by the step entry without being applied and
+clipmi_block_step_adam (csrc/optim_step.hip) applies ``torch.optim.Adam``'s or ``torch.optim.AdamW``'s rule to the master context;
+``_AdamBlock`` keeps the moments and the bias-correction table beside it, for this fit and the five others.  DESIGN.md "Adam steps for
+the prompt fits".
+
 Not covered: ``nn.DataParallel`` itself in one process (``shard=`` stands in for it, with the refusals above), ProGrad under a dynamic loss
 scale, and models whose text tower carries deep prompts.
 """
@@ -171,6 +177,43 @@ class _BlockScaler:
 
     def state(self) -> dict:
         return ops.scaler_state_dict(self.block)
+
+
+class _AdamBlock:
+    """torch.optim.Adam's or AdamW's state beside a fit's fp32 master block (DESIGN.md "Adam steps for the prompt fits"): the two
+    moments, the bias-correction table on the device and the number of steps enqueued.  ``step`` applies a gradient block that the fit's
+    own launches formed without applying it; under a ``_BlockScaler`` the device decides whether the step counts, and ``steps_taken``
+    is then an upper bound of the applied steps, which is all the table's length has to cover."""
+    TABLE_STEPS = 1024     # the table's first length; it doubles when the steps reach it
+
+    def __init__(self, optimizer: str, betas, eps: float, weight_decay: float, master: torch.Tensor):
+        self.decoupled = optimizer == "adamw"
+        self.betas, self.eps, self.weight_decay = betas, float(eps), float(weight_decay)
+        self.exp_avg, self.exp_avg_sq = torch.zeros_like(master), torch.zeros_like(master)
+        self.steps_taken = 0
+        self.table = None
+        self.ws = None
+
+    def _table(self, dev) -> torch.Tensor:
+        """The table with a row for step ``steps_taken + 1``; a longer one is uploaded (in stream order) when it has none."""
+        need = self.steps_taken + 1
+        if self.table is None or self.table.shape[0] < need:
+            self.table = torch.from_numpy(fitloop.adam_bias_table(self.betas, max(self.TABLE_STEPS, 2 * need))).to(dev)
+        return self.table
+
+    def step(self, grad: torch.Tensor, params: torch.Tensor, lr_d: torch.Tensor, grad_scale: float = 1.0, scaler: Optional[_BlockScaler] = None) -> None:
+        """``ops.block_step_adam`` on ``grad`` = ``grad_scale`` * gradient, or, with ``scaler``, ``ops.block_step_adam_scaled`` on
+        ``grad`` = the scaler's scale * gradient."""
+        table = self._table(params.device)
+        rule = dict(betas=self.betas, eps=self.eps, weight_decay=self.weight_decay, decoupled=self.decoupled, want_grad=False)
+        if scaler is None:
+            ops.block_step_adam(grad, params, self.exp_avg, self.exp_avg_sq, lr_d, self.steps_taken + 1, table, grad_scale, **rule)
+        else:
+            if self.ws is None:
+                need = lib.clipmi_block_step_adam_scaled_workspace_bytes(params.numel())
+                self.ws = torch.empty(max(need, 256), dtype=torch.uint8, device=params.device)
+            ops.block_step_adam_scaled(grad, scaler.block, params, self.exp_avg, self.exp_avg_sq, lr_d, table, *scaler.args(), workspace=self.ws, **rule)
+        self.steps_taken += 1
 
 
 def _check_prompts(who: str, clip_model, tokenized_prompts, ctx) -> Tuple[int, int, bool, int]:
@@ -584,9 +627,12 @@ class CoOpFitState(fitmonitor.Monitored):
     _who, _unseen_summary = "CoOpFitState", True
 
     def __init__(self, clip_model, tokenized_prompts, ctx: torch.Tensor, logit_scale: float = 4.6052, momentum: float = 0.9,
-                 dampening: float = 0.0, nesterov: bool = False, weight_decay: float = 5e-4, grad_scale: float = DEFAULT_GRAD_SCALE,
-                 seq_rows: Optional[int] = None, method: str = "coop", teacher: Optional[torch.Tensor] = None, w: float = 8.0, T: float = 1.0,
-                 lam: float = 1.0, scaler: Optional[dict] = None, class_token_position: str = "end", name_lens=None, shard: Optional[Shard] = None):
+                 dampening: float = 0.0, nesterov: bool = False, weight_decay: float = 5e-4,
+                 grad_scale: float = DEFAULT_GRAD_SCALE, seq_rows: Optional[int] = None, method: str = "coop", teacher: Optional[torch.Tensor] = None,
+                 w: float = 8.0, T: float = 1.0, lam: float = 1.0, scaler: Optional[dict] = None, class_token_position: str = "end", name_lens=None,
+                 shard: Optional[Shard] = None, optimizer: str = "sgd", betas=(0.9, 0.999), eps: float = 1e-8):
+        """``optimizer``: "sgd" (``momentum``, ``dampening``, ``nesterov``), "adam" or "adamw" (``betas``, ``eps``;
+        ``weight_decay`` keeps the fit's default of 5e-4 under all three -- torch's AdamW default of 1e-2 is NOT taken over)."""
         who = "CoOpFitState"
         self.C, self.n_ctx, self.per_class, last = _check_prompts(who, clip_model, tokenized_prompts, ctx)
         self.shard = shard
@@ -595,7 +641,8 @@ class CoOpFitState(fitmonitor.Monitored):
         placement = _placement(who, tokenized_prompts, self.n_ctx, class_token_position, name_lens)
         _static_prograd(who, method, grad_scale)
         self.dynamic, self.grad_scale, self.scaler = _scale_args(who, grad_scale, scaler)
-        fitloop.check_sgd(who, momentum, dampening, weight_decay, nesterov)
+        self.optimizer, momentum, dampening, nesterov, betas = fitloop.check_optimizer(who, optimizer, momentum, dampening, nesterov, weight_decay, betas,
+                                                                                       eps, shard=shard)
         self.scale = fitloop.exp_logit_scale(who, logit_scale)
         _check_method(who, method, teacher, w, T, lam, self.C, int(clip_model.geometry.embed_dim))
         self.method, self.w, self.T, self.lam = method, float(w), float(T), float(lam)
@@ -617,6 +664,7 @@ class CoOpFitState(fitmonitor.Monitored):
         self.momentum, self.dampening, self.nesterov, self.weight_decay = momentum, dampening, nesterov, weight_decay
         self.steps = 0
         self._scaler = _BlockScaler(self.scaler, dev) if self.dynamic else None
+        self._adam = _AdamBlock(self.optimizer, betas, eps, weight_decay, self.ctx) if self.optimizer != "sgd" else None
 
     def scaler_state(self) -> dict:
         """The dynamic scale's block as ``dict(scale, growth_tracker, skipped_steps, applied_steps, found_inf)`` (``found_inf``: of the
@@ -795,6 +843,26 @@ class CoOpFitState(fitmonitor.Monitored):
         ops.ctx_step_scaled(d_embed, t.C, t.n_ctx, t.per_class, sc.block, self.ctx, self.buf, lr_d, *sc.args(), float(self.momentum), float(self.dampening),
                             float(self.weight_decay), bool(self.nesterov), want_grad=False, workspace=sc.ws)
 
+    def _step_adam(self, features, labels_d, lr_d, losses) -> None:
+        """``step`` under Adam or AdamW: the SGD step's forward, head and backward(s), the context's gradient formed by the same step
+        entry WITHOUT applying it (``context_gradient``'s way; ProGrad's is the projected one), and the rule in ``_AdamBlock.step``.
+        Under the dynamic scale the backward carries scale * gradient as in ``_step_scaled``, the class sums are formed at
+        ``grad_scale = 1`` (clipmi_ctx_step_scaled's own first launch cannot be reached without its step) and handed on as they are:
+        clipmi_block_step_adam_scaled divides by the scale, as that launch does."""
+        t, sc = self.tower, self._scaler
+        text = t.forward(self.ctx)
+        gs = 1.0 if self.dynamic else self.grad_scale
+        _, d_text, d_kl = ops.prompt_head(features, labels_d, text, self.scale, gs, self.method, self.teacher, self.w, 1.0 if self.dynamic else self.T, losses)
+        if self.dynamic:
+            ops.grad_scale_rows(d_text, sc.block)
+        d_embed = t.context_rows(t.backward(d_text))
+        if self.method != "prograd":
+            grad = ops.ctx_step(d_embed, t.C, t.n_ctx, t.per_class, gs)
+        else:
+            d_embed_kl = t.context_rows(t.backward(d_kl, second=True), second=True)
+            grad = ops.prograd_step(d_embed, d_embed_kl, t.C, t.n_ctx, t.per_class, gs, self.lam)[0]
+        self._adam.step(grad, self.ctx, lr_d, 1.0, sc)
+
     def step(self, features: torch.Tensor, labels, lr, want_loss: bool = False, one_call: bool = False) -> Optional[torch.Tensor]:
         """One optimiser step on the batch ``features`` fp32 [B, E] (raw image features on the GPU) and ``labels`` [B] at the rate ``lr``:
         an fp32 tensor of one element on the device is read where it lies (``rates[k:k + 1]``); a Python number is uploaded on every call.
@@ -827,6 +895,10 @@ class CoOpFitState(fitmonitor.Monitored):
             _run_phases([s._shard_phases(features, labels_d, lr_d, losses if s is self else _new_losses(s.method, dev), first) for s in states])
             for s in states:
                 s.steps += s is not self
+        elif self._adam is not None:
+            if one_call:
+                raise ValueError(f"CoOpFitState.step: one_call=True with optimizer={self.optimizer!r}: the one-call steps stay SGD")
+            self._step_adam(features, labels_d, lr_d, losses)
         elif one_call:
             self._one_call(features, labels_d, lr_d, losses, first)
         elif self.dynamic:
@@ -863,7 +935,7 @@ def fit_context(features: torch.Tensor, labels, clip_model, tokenized_prompts, c
                 order=None, drop_last: bool = False, return_history: bool = False, method: str = "coop", teacher: Optional[torch.Tensor] = None,
                 w: float = 8.0, T: float = 1.0, lam: float = 1.0, scaler: Optional[dict] = None, class_token_position: str = "end", name_lens=None,
                 val=None, val_bins: int = 10, final_model: str = "last_step", val_criterion: str = "accuracy", return_monitor: bool = False,
-                shard: Optional[Shard] = None):
+                shard: Optional[Shard] = None, optimizer: str = "sgd", betas=(0.9, 0.999), eps: float = 1e-8):
     """Train CoOp's context on cached ``features`` fp32 [N, E] (raw image features on the GPU; the rows may be a column slice) and
     ``labels`` [N], starting from ``ctx`` (not modified; None = ``init_context(clip_model, n_ctx, C if csc else None)``): ``epochs``
     passes of ``torch.optim.SGD(lr, momentum, dampening, weight_decay, nesterov)`` over batches of ``batch_size``.
@@ -888,6 +960,14 @@ def fit_context(features: torch.Tensor, labels, clip_model, tokenized_prompts, c
     behind everything else, read once after the run's one wait: per-epoch ``accuracy``, ``nll`` and ``ece``, the raw ``bins``,
     ``records`` and ``best_epoch`` (``CoOpFitState.monitor``); empty without ``val`` or without steps.
 
+    ``optimizer``: "sgd" (the default: ``momentum``, ``dampening``, ``nesterov`` -- the launches and bits of the
+    fit without this argument), "adam" or "adamw": ``torch.optim.Adam`` / ``torch.optim.AdamW`` (no amsgrad) with ``betas`` and ``eps`` on
+    the same forward, head and backward; the context's gradient is formed without being applied and clipmi_block_step_adam applies it
+    (clipmi_block_step_adam_scaled under ``grad_scale="dynamic"``, where a skipped step leaves the context and both moments as they are
+    and is not one of Adam's steps; ProGrad keeps its static scale).  ``weight_decay`` keeps this fit's default of 5e-4 under all three:
+    torch's AdamW default of 1e-2 is NOT taken over.  Refused by name before any device call: an unknown optimiser, a ``momentum``,
+    ``dampening`` or ``nesterov`` other than the signature's default together with an Adam optimiser, and ``shard`` with one.  DESIGN.md "Adam steps for the prompt fits".
+
     ``shard=Shard(world, rank, gather)``: the class-sharded fit (module docstring).  Every rank makes this call with the same arguments
     -- the whole prompt set, the whole context, all features -- and returns the same whole context; with a ``LocalGather`` the one call
     runs all ``world`` shard states in this process."""
@@ -904,7 +984,7 @@ def fit_context(features: torch.Tensor, labels, clip_model, tokenized_prompts, c
         raise ValueError(f"{who}: features must be a [N >= 1, E = {E}] tensor")
     N = features.shape[0]
     epochs, batch_size = fitloop.check_run(who, epochs, batch_size)
-    fitloop.check_sgd(who, momentum, dampening, weight_decay, nesterov)
+    fitloop.check_optimizer(who, optimizer, momentum, dampening, nesterov, weight_decay, betas, eps, shard=shard)
     _static_prograd(who, method, grad_scale)
     _scale_args(who, grad_scale, scaler)
     _check_method(who, method, teacher, w, T, lam, Cn, E)
@@ -922,7 +1002,7 @@ def fit_context(features: torch.Tensor, labels, clip_model, tokenized_prompts, c
         return fitmonitor.pack(out, np.zeros(0, np.float32), empty_monitor(val_bins), return_history, return_monitor)
     _need_gpu(features, "features")
     make = lambda sh: CoOpFitState(clip_model, tokenized_prompts, ctx, logit_scale, momentum, dampening, nesterov, weight_decay, grad_scale, seq_rows,
-                                   method, teacher, w, T, lam, scaler, class_token_position, name_lens, sh)
+                                   method, teacher, w, T, lam, scaler, class_token_position, name_lens, sh, optimizer, betas, eps)
     state = shard_states(make, shard)     # under a LocalGather all the world's states live here; a step of one steps them all
     end_epoch = None
     if val is not None:

@@ -122,13 +122,23 @@ int check_scaler(const char* who, const ScalerCall& sc) {
   return CLIPMI_OK;
 }
 
+// the first two launches of a block's scaled step, for the callers that apply a rule of their own behind them (optim_step.hip): the
+// unscale-and-flag launch over a block of scale * gradient, and the decision launch; every argument has been checked
+int launch_block_unscale(const float* grad, float* grad_out, int64_t total, const ScalerCall& sc, const ScaledWs& w, hipStream_t s) {
+  hipLaunchKernelGGL(block_unscale_kernel, dim3((unsigned)scaled_grad_blocks(total)), dim3(THREADS), 0, s, grad, grad_out, total,
+                     (const clipmi_scaler_state*)sc.state, w);
+  return check_launch("block_unscale_kernel");
+}
+int launch_scaler_update(const ScaledWs& w, int64_t total, const ScalerCall& sc, hipStream_t s) {
+  hipLaunchKernelGGL(scaler_update_kernel, dim3(1), dim3(THREADS), 0, s, w, scaled_grad_blocks(total), sc.state, sc.growth, sc.backoff, sc.interval);
+  return check_launch("scaler_update_kernel");
+}
+
 // the decision launch and the step launch behind a first launch that has filled w.grad and w.flags; every argument has been checked
 int launch_scaled_decide_apply(const ScaledWs& w, int64_t total, float* params, float* buf, const ScalerCall& sc, const float* lr, float momentum,
                                float dampening, float weight_decay, int nesterov, hipStream_t s) {
-  const int64_t blocks = scaled_grad_blocks(total);
-  hipLaunchKernelGGL(scaler_update_kernel, dim3(1), dim3(THREADS), 0, s, w, blocks, sc.state, sc.growth, sc.backoff, sc.interval);
-  if (int rc = check_launch("scaler_update_kernel")) return rc;
-  hipLaunchKernelGGL(scaled_apply_kernel, dim3((unsigned)blocks), dim3(THREADS), 0, s, w, params, buf, total, lr,
+  if (int rc = launch_scaler_update(w, total, sc, s)) return rc;
+  hipLaunchKernelGGL(scaled_apply_kernel, dim3((unsigned)scaled_grad_blocks(total)), dim3(THREADS), 0, s, w, params, buf, total, lr,
                      make_sgd_args(momentum, dampening, weight_decay, nesterov, 0));
   return check_launch("scaled_apply_kernel");
 }
@@ -180,9 +190,7 @@ int check_block_step_scaled(const char* who, const float* grad, const float* par
 int launch_block_step_scaled(const float* grad, float* params, float* buf, float* grad_out, int64_t total, const ScalerCall& sc, const float* lr, float momentum,
                              float dampening, float weight_decay, int nesterov, void* workspace, hipStream_t s) {
   const ScaledWs w = scaled_carve(workspace, total);
-  hipLaunchKernelGGL(block_unscale_kernel, dim3((unsigned)scaled_grad_blocks(total)), dim3(THREADS), 0, s, grad, grad_out, total,
-                     (const clipmi_scaler_state*)sc.state, w);
-  if (int rc = check_launch("block_unscale_kernel")) return rc;
+  if (int rc = launch_block_unscale(grad, grad_out, total, sc, w, s)) return rc;
   return launch_scaled_decide_apply(w, total, params, buf, sc, lr, momentum, dampening, weight_decay, nesterov, s);
 }
 

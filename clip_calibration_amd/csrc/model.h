@@ -169,6 +169,10 @@ int check_scaler(const char* who, const ScalerCall& sc);
 // the decision launch and the step launch of a scaled step whose own first launch has filled w.grad and w.flags (proda_train.hip)
 int launch_scaled_decide_apply(const ScaledWs& w, int64_t total, float* params, float* buf, const ScalerCall& sc, const float* lr, float momentum,
                                float dampening, float weight_decay, int nesterov, hipStream_t s);
+// the first two launches of a block's scaled step on their own: unscale and flag (w.grad, w.flags), then the decision and the state's
+// update (optim_step.hip applies Adam's rule behind them)
+int launch_block_unscale(const float* grad, float* grad_out, int64_t total, const ScalerCall& sc, const ScaledWs& w, hipStream_t s);
+int launch_scaler_update(const ScaledWs& w, int64_t total, const ScalerCall& sc, hipStream_t s);
 size_t block_step_scaled_bytes(int64_t total);   // 0 for a total the step refuses
 int check_block_step_scaled(const char* who, const float* grad, const float* params, const float* buf, const float* grad_out, const float* lr, int64_t total,
                             const ScalerCall& sc, float momentum, float dampening, float weight_decay, int nesterov, const void* workspace,

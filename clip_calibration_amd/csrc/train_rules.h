@@ -125,6 +125,23 @@ __device__ __forceinline__ void adam_element(float* __restrict__ w, float* __res
   w[idx] = p - step_size * m1 / denom;
 }
 
+// torch.optim.AdamW's rule on one element (Adam with decoupled_weight_decay): w *= 1 - lr wd, the factor formed in double and rounded
+// once as torch's Python scalar is, then Adam's rule above on the decayed value with no weight decay in the gradient
+__device__ __forceinline__ void adamw_element(float* __restrict__ w, float* __restrict__ m, float* __restrict__ v, int64_t idx, float grad, float lr,
+                                              const AdamArgs& a) {
+#pragma clang fp contract(off)
+  float p = w[idx];
+  if (a.weight_decay != 0.f) p = p * (float)(1.0 - (double)lr * (double)a.weight_decay);
+  const float m0 = m[idx];
+  const float m1 = m0 + (grad - m0) * a.one_minus_beta1;
+  const float v1 = a.beta2 * v[idx] + (a.one_minus_beta2 * grad) * grad;
+  m[idx] = m1;
+  v[idx] = v1;
+  const float step_size = (float)((double)lr / a.bias_correction1);
+  const float denom = sqrtf(v1) / (float)a.bias_correction2_sqrt + a.eps;
+  w[idx] = p - step_size * m1 / denom;
+}
+
 // One value per wave (the same in every lane) to the sum / maximum over the workgroup's WAVES waves, in ascending wave order through sw
 // (WAVES floats of LDS): one barrier.  Every thread of the workgroup calls it and holds the result.  There is no barrier in front: a
 // caller that reduces twice gives each reduction WAVES floats of its own, or puts a barrier between the two.

@@ -66,6 +66,57 @@ def check_sgd(who: str, momentum: float, dampening: float, weight_decay: float, 
         raise ValueError(f"{who}: Nesterov momentum requires a momentum and zero dampening")
 
 
+OPTIMIZERS = ("sgd", "adam", "adamw")     # the reference's OPTIM.NAME values the prompt fits take
+SGD_DEFAULTS = (0.9, 0.0, False)          # momentum, dampening, nesterov of every prompt fit when the caller names none
+
+
+def check_adam(who: str, betas, eps: float, weight_decay: float) -> Tuple[float, float]:
+    """torch.optim.Adam's argument checks (no amsgrad); returns the betas as a pair of floats."""
+    try:
+        b1, b2 = (float(b) for b in betas)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: betas={betas!r} must be a pair of numbers") from None
+    if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):
+        raise ValueError(f"{who}: betas={betas!r} (both in [0, 1))")
+    if not (math.isfinite(eps) and eps > 0.0):
+        raise ValueError(f"{who}: eps={eps} (finite, > 0)")
+    if not weight_decay >= 0.0 or not math.isfinite(weight_decay):
+        raise ValueError(f"{who}: weight_decay={weight_decay} (finite, >= 0)")
+    return b1, b2
+
+
+def adam_bias_table(betas, steps: int) -> np.ndarray:
+    """float64 [steps, 2]: row t - 1 holds ``1 - beta1 ** t`` and ``math.sqrt(1 - beta2 ** t)`` for Adam's step number t = 1 .. steps,
+    formed in Python doubles exactly as torch's single-tensor Adam forms them.  The step kernels index it (no pow on the device)."""
+    b1, b2 = (float(b) for b in betas)
+    if int(steps) < 1:
+        raise ValueError(f"adam_bias_table: steps={steps} (>= 1)")
+    return np.array([[1 - b1 ** t, math.sqrt(1 - b2 ** t)] for t in range(1, int(steps) + 1)], dtype=np.float64)
+
+
+def check_optimizer(who: str, optimizer, momentum, dampening, nesterov, weight_decay: float, betas=(0.9, 0.999), eps: float = 1e-8,
+                    one_call: bool = False, shard=None, sgd_defaults=SGD_DEFAULTS):
+    """The optimiser arguments of a prompt fit after their checks, before any device call: ``(optimizer, momentum, dampening, nesterov,
+    betas)``.  ``"sgd"``: torch.optim.SGD's checks, the arguments as they are, ``betas`` None.  ``"adam"`` / ``"adamw"``: ``momentum``,
+    ``dampening`` and ``nesterov`` belong to SGD -- a value other than the fit's own default (``sgd_defaults``; a signature cannot tell a
+    default from the same value passed on purpose) is refused --; torch.optim.Adam's checks; the one-call steps and the class-sharded fit
+    stay SGD and are refused.  The three come back as 0, 0, False there, which is what the fits' gradient-only calls take."""
+    if not isinstance(optimizer, str) or optimizer not in OPTIMIZERS:
+        raise ValueError(f"{who}: optimizer={optimizer!r} must be one of {OPTIMIZERS}")
+    if optimizer == "sgd":
+        check_sgd(who, momentum, dampening, weight_decay, nesterov)
+        return optimizer, momentum, dampening, nesterov, None
+    for name, v, d in zip(("momentum", "dampening", "nesterov"), (momentum, dampening, nesterov), sgd_defaults):
+        if v is not None and v != d:
+            raise ValueError(f"{who}: {name}={v!r} is an argument of optimizer='sgd'; optimizer={optimizer!r} takes betas and eps")
+    betas = check_adam(who, betas, eps, weight_decay)
+    if one_call:
+        raise ValueError(f"{who}: one_call=True with optimizer={optimizer!r}: the one-call steps stay SGD")
+    if shard is not None:
+        raise ValueError(f"{who}: shard with optimizer={optimizer!r}: the class-sharded fit stays SGD")
+    return optimizer, 0.0, 0.0, False, betas
+
+
 def check_run(who: str, epochs, batch_size) -> Tuple[int, int]:
     epochs, batch_size = int(epochs), int(batch_size)
     if epochs < 0 or batch_size < 1:

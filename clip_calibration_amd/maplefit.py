@@ -284,15 +284,16 @@ class MaPLeFitState(vptfit._BlockFitState):
     "Fit monitor", "The image-tower fits")."""
     _who = "MaPLeFitState"
 
-    def __init__(self, model, tokenized_prompts, learner_params: Dict[str, torch.Tensor], logit_scale: float = 4.6052, momentum: float = 0.9,
-                 dampening: float = 0.0, nesterov: bool = False, weight_decay: float = 5e-4, grad_scale: float = DEFAULT_GRAD_SCALE,
-                 seq_rows: Optional[int] = None, class_token_position: str = "end", scaler: Optional[dict] = None):
+    def __init__(self, model, tokenized_prompts, learner_params: Dict[str, torch.Tensor], logit_scale: float = 4.6052,
+                 momentum: float = 0.9, dampening: float = 0.0, nesterov: bool = False, weight_decay: float = 5e-4,
+                 grad_scale: float = DEFAULT_GRAD_SCALE, seq_rows: Optional[int] = None, class_token_position: str = "end", scaler: Optional[dict] = None,
+                 optimizer: str = "sgd", betas=(0.9, 0.999), eps: float = 1e-8):
         who = "MaPLeFitState"
-        self._init_optimiser(who, logit_scale, momentum, dampening, nesterov, weight_decay, grad_scale, scaler)
+        self._init_optimiser(who, logit_scale, momentum, dampening, nesterov, weight_decay, grad_scale, scaler, optimizer, betas, eps)
         self.towers = _Towers(who, model, tokenized_prompts, learner_params, seq_rows, class_token_position)
         self.C = self.towers.C
         self._init_block(pack_block(learner_params, self.towers.depth, model.device))
-        self._scaled_grad = torch.empty_like(self.block) if self.dynamic else None    # scale * gradient, as clipmi_maple_step leaves it
+        self._scaled_grad = torch.empty_like(self.block) if self._defer else None    # scale * gradient, as clipmi_maple_step leaves it
 
     def params(self, block: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
         t = self.towers
@@ -329,12 +330,12 @@ class MaPLeFitState(vptfit._BlockFitState):
         return d_text, d_feats
 
     def _apply(self, outs, lr_d, first, sgd):
-        """Under the dynamic scale clipmi_maple_step leaves scale * gradient in ``_scaled_grad`` and applies nothing."""
+        """Under the dynamic scale and under Adam clipmi_maple_step leaves scale * gradient in ``_scaled_grad`` and applies nothing."""
         tw = self.towers
         d_embed, d_deep, d_vis = tw.backward(*outs)
-        grad, buf, gs, lr, first = (self._scaled_grad, None, 1.0, None, 0) if self.dynamic else (None, self.buf, self.grad_scale, lr_d, first)
+        grad, buf, gs, lr, first = (self._scaled_grad, None, 1.0, None, 0) if self._defer else (None, self.buf, self.grad_scale, lr_d, first)
         check(lib.clipmi_maple_step(d_embed.data_ptr(), None if d_deep is None else d_deep.data_ptr(), d_vis.data_ptr(), self.block.data_ptr(),
-                                    None if buf is None else buf.data_ptr(), None if grad is None else grad.data_ptr(), int(not self.dynamic), tw.C,
+                                    None if buf is None else buf.data_ptr(), None if grad is None else grad.data_ptr(), int(not self._defer), tw.C,
                                     tw.text.L, tw.n_ctx, tw.depth, tw.Dt, tw.Dv, gs, None if lr is None else lr.data_ptr(), int(first), *sgd,
                                     tw.step_ws.data_ptr(), tw.step_ws.numel(), ops._stream()), "clipmi_maple_step")
         return grad
@@ -358,11 +359,11 @@ def init_learner_params(model, n_ctx: int = 2, depth: int = 9, seed: int = 0) ->
 
 
 def fit_prompt_learner(images_or_loader, labels, model, tokenized_prompts, learner_params: Optional[Dict[str, torch.Tensor]] = None, n_ctx: int = 2,
-                       depth: int = 9, logit_scale: float = 4.6052, lr: float = 0.0035, epochs: int = 5, batch_size: int = 4, momentum: float = 0.9,
-                       dampening: float = 0.0, weight_decay: float = 5e-4, nesterov: bool = False, grad_scale: float = DEFAULT_GRAD_SCALE,
+                       depth: int = 9, logit_scale: float = 4.6052, lr: float = 0.0035, epochs: int = 5, batch_size: int = 4,
+                       momentum: float = 0.9, dampening: float = 0.0, weight_decay: float = 5e-4, nesterov: bool = False, grad_scale: float = DEFAULT_GRAD_SCALE,
                        seq_rows: Optional[int] = None, lr_per_epoch: Optional[Sequence[float]] = None, drop_last: bool = False,
-                       return_history: bool = False, class_token_position: str = "end", scaler: Optional[dict] = None, val=None,
-                       val_batch_size: int = 32, val_bins: int = 10, final_model: str = "last_step", val_criterion: str = "accuracy",
+                       return_history: bool = False, class_token_position: str = "end", scaler: Optional[dict] = None, optimizer: str = "sgd", betas=(0.9, 0.999), eps: float = 1e-8,
+                       val=None, val_batch_size: int = 32, val_bins: int = 10, final_model: str = "last_step", val_criterion: str = "accuracy",
                        return_monitor: bool = False):
     """Train MaPLe's prompt learner starting from ``learner_params`` (not modified; None = ``init_learner_params(model, n_ctx, depth)``):
     ``epochs`` passes of ``torch.optim.SGD(lr, momentum, dampening, weight_decay, nesterov)`` over the whole parameter list.
@@ -377,16 +378,22 @@ def fit_prompt_learner(images_or_loader, labels, model, tokenized_prompts, learn
 
     ``val=(val_images_or_loader, val_labels)``, ``val_batch_size``, ``val_bins``, ``final_model``, ``val_criterion`` and
     ``return_monitor`` as ``vptfit.fit_prompts`` takes them: behind every epoch ``MaPLeFitState.validate`` scores the block on the device;
-    the fitted parameters are bit for bit those of the same call without ``val``; "best_val" returns the best epoch's parameters."""
+    the fitted parameters are bit for bit those of the same call without ``val``; "best_val" returns the best epoch's parameters.
+
+    ``optimizer``, ``betas``, ``eps``: "sgd" (the default; ``momentum``, ``dampening``, ``nesterov``), "adam" or
+    "adamw", as ``coopfit.fit_context`` takes them; ``weight_decay`` keeps this fit's default of 5e-4 under all three (torch's AdamW
+    default of 1e-2 is NOT taken over).  DESIGN.md "Adam steps for the prompt fits"."""
     who = "fit_prompt_learner"
     fitmonitor.check_image_args(who, val, val_batch_size, val_bins, final_model, val_criterion)
     epochs = int(epochs)
     if epochs < 0:
         raise ValueError(f"{who}: epochs={epochs} (>= 0)")
+    if optimizer != "sgd":      # by this function's name; SGD's arguments are the state's to check, as before
+        fitloop.check_optimizer(who, optimizer, momentum, dampening, nesterov, weight_decay, betas, eps)
     if learner_params is None:
         learner_params = init_learner_params(model, n_ctx, depth)
     state = MaPLeFitState(model, tokenized_prompts, learner_params, logit_scale, momentum, dampening, nesterov, weight_decay, grad_scale, seq_rows,
-                          class_token_position, scaler)
+                          class_token_position, scaler, optimizer, betas, eps)
     batches = fitloop.cut_batches(who, images_or_loader, labels, state.C, batch_size, drop_last, model.device)
     _, lr_steps = fitloop.schedule(who, lr, epochs, lr_per_epoch, len(batches), model.device)
     end_epoch = None

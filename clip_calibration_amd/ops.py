@@ -1256,6 +1256,68 @@ def block_step_scaled(grad: torch.Tensor, state: torch.Tensor, params: torch.Ten
     return out
 
 
+def _adam_operands(who: str, grad, params, exp_avg, exp_avg_sq, lr, bias_table, betas, eps, weight_decay):
+    """(total, the table's rows) after the checks ``block_step_adam`` and ``block_step_adam_scaled`` share."""
+    _in_place(grad, torch.float32, f"{who}: grad must be a contiguous fp32 tensor on the GPU")
+    _in_place(params, torch.float32, f"{who}: params must be a contiguous fp32 tensor on the GPU")
+    total = params.numel()
+    if total < 1 or grad.numel() != total:
+        raise ValueError(f"{who}: grad {tuple(grad.shape)} and params {tuple(params.shape)} must hold the same number of elements (>= 1)")
+    _in_place(exp_avg, torch.float32, f"{who}: exp_avg must be a contiguous fp32 tensor on the GPU", numel=total)
+    _in_place(exp_avg_sq, torch.float32, f"{who}: exp_avg_sq must be a contiguous fp32 tensor on the GPU", numel=total)
+    if lr.numel() != 1:
+        raise ValueError(f"{who}: lr {tuple(lr.shape)} must hold one element")
+    _in_place(bias_table, torch.float64, f"{who}: bias_table must be a contiguous float64 [steps, 2] tensor on the GPU (fitloop.adam_bias_table)")
+    if bias_table.dim() != 2 or bias_table.shape[1] != 2 or bias_table.shape[0] < 1:
+        raise ValueError(f"{who}: bias_table {tuple(bias_table.shape)} must be [steps >= 1, 2]")
+    if len(betas) != 2:
+        raise ValueError(f"{who}: betas={betas!r} must be a pair")
+    return total, bias_table.shape[0]
+
+
+def block_step_adam(grad: torch.Tensor, params: torch.Tensor, exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor, lr: torch.Tensor, t: int,
+                    bias_table: torch.Tensor, grad_scale: float = 1.0, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
+                    decoupled: bool = False, want_grad: bool = True) -> Optional[torch.Tensor]:
+    """clipmi_block_step_adam: torch.optim.Adam's step (``decoupled``: torch.optim.AdamW's) number ``t`` >= 1 on the fp32 master block
+    ``params`` with the moments ``exp_avg`` and ``exp_avg_sq`` (zeros before the first step), in place, at the rate ``lr`` fp32 [1].
+    ``grad``, of as many elements, is ``grad_scale`` times the gradient.  ``bias_table``: ``fitloop.adam_bias_table(betas, steps)`` on the
+    device, ``steps >= t``.  One launch.  Returns the unscaled gradient (``params``' shape) when ``want_grad``."""
+    who = "block_step_adam"
+    lr = _dev(lr, "lr", (torch.float32,))
+    total, rows = _adam_operands(who, grad, params, exp_avg, exp_avg_sq, lr, bias_table, betas, eps, weight_decay)
+    out = torch.empty_like(params) if want_grad else None
+    check(lib.clipmi_block_step_adam(grad.data_ptr(), params.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(),
+                                     None if out is None else out.data_ptr(), total, float(grad_scale), lr.data_ptr(), int(t), bias_table.data_ptr(),
+                                     rows, float(betas[0]), float(betas[1]), float(eps), float(weight_decay), int(bool(decoupled)), _stream()),
+          "clipmi_block_step_adam")
+    return out
+
+
+def block_step_adam_scaled(grad: torch.Tensor, state: torch.Tensor, params: torch.Tensor, exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor,
+                           lr: torch.Tensor, bias_table: torch.Tensor, growth_factor: float = 2.0, backoff_factor: float = 0.5,
+                           growth_interval: int = 2000, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0, decoupled: bool = False,
+                           want_grad: bool = True, workspace: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
+    """clipmi_block_step_adam_scaled: ``block_step_adam`` under the dynamic loss scale of ``state`` (``new_scaler_state``), as
+    ``block_step_scaled`` is SGD's: ``grad`` is the block's gradient times the state's scale; a gradient with an inf or a NaN leaves
+    ``params`` and both moments as they are, backs the scale off and does not count as one of Adam's steps; a clean one is applied at
+    ``t`` = the state's applied steps.  ``bias_table`` must have a row for every step enqueued so far and this one.  Nothing is read
+    back.  ``workspace``: a uint8 tensor to reuse between steps.  Returns the unscaled gradient when ``want_grad``."""
+    who = "block_step_adam_scaled"
+    lr = _dev(lr, "lr", (torch.float32,))
+    total, rows = _adam_operands(who, grad, params, exp_avg, exp_avg_sq, lr, bias_table, betas, eps, weight_decay)
+    ps = _scaler_state(who, state)
+    out = torch.empty_like(params) if want_grad else None
+    need = lib.clipmi_block_step_adam_scaled_workspace_bytes(total)
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=params.device)
+    check(lib.clipmi_block_step_adam_scaled(grad.data_ptr(), params.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(),
+                                            None if out is None else out.data_ptr(), total, ps, float(growth_factor), float(backoff_factor),
+                                            int(growth_interval), lr.data_ptr(), bias_table.data_ptr(), rows, float(betas[0]), float(betas[1]),
+                                            float(eps), float(weight_decay), int(bool(decoupled)), workspace.data_ptr(), workspace.numel(), _stream()),
+          "clipmi_block_step_adam_scaled")
+    return out
+
+
 # ---- fit monitor (csrc/fit_monitor.hip).  The helpers below are the only place that knows the byte layout of the epoch record and of the
 # best block (include/clipmi.h "Fit monitor").
 

@@ -56,7 +56,7 @@ import torch
 
 from . import _lib, fitloop, fitmonitor, ops
 from ._lib import check, lib
-from .coopfit import DEFAULT_GRAD_SCALE, DYNAMIC, MAX_LIVE_ROWS, _DT, _BlockScaler, _Tower, _check_batch, _check_grad_scale, _is_dynamic, _live_rows, _scale_args
+from .coopfit import DEFAULT_GRAD_SCALE, DYNAMIC, MAX_LIVE_ROWS, _DT, _AdamBlock, _BlockScaler, _Tower, _check_batch, _check_grad_scale, _is_dynamic, _live_rows, _scale_args
 from .fitloop import _host_int_array, _need_gpu, steps_per_epoch
 
 
@@ -246,15 +246,18 @@ class ProDAFitState(fitmonitor.Monitored):
 
     def __init__(self, clip_model, tokenized_prompts, ctx: torch.Tensor, prompt_bs: int = 4, alpha: float = 0.1, logit_scale: float = 4.6052,
                  momentum: float = 0.9, dampening: float = 0.0, nesterov: bool = False, weight_decay: float = 5e-4,
-                 grad_scale: float = DEFAULT_GRAD_SCALE, seq_rows: Optional[int] = None, name_lens=None, generator: Optional[torch.Generator] = None,
-                 scaler: Optional[dict] = None):
+                 grad_scale: float = DEFAULT_GRAD_SCALE, seq_rows: Optional[int] = None, name_lens=None,
+                 optimizer: str = "sgd", betas=(0.9, 0.999), eps: float = 1e-8,
+                 generator: Optional[torch.Generator] = None, scaler: Optional[dict] = None):
+        """``optimizer``: "sgd" (``momentum``, ``dampening``, ``nesterov``), "adam" or "adamw" (``betas``, ``eps``;
+        ``weight_decay`` keeps the fit's default of 5e-4 under all three -- torch's AdamW default of 1e-2 is NOT taken over)."""
         who = "ProDAFitState"
         ids_all, self.C, self.P, self.n_ctx, nl, last = _check_prompts(who, clip_model, tokenized_prompts, ctx, name_lens, seq_rows)
         self.Pb = int(prompt_bs)
         _check_collection(who, self.P, self.Pb)
         self.alpha = _check_alpha(who, alpha)
         self.dynamic, self.grad_scale, self.scaler = _scale_args(who, grad_scale, scaler)
-        fitloop.check_sgd(who, momentum, dampening, weight_decay, nesterov)
+        self.optimizer, momentum, dampening, nesterov, betas = fitloop.check_optimizer(who, optimizer, momentum, dampening, nesterov, weight_decay, betas, eps)
         self.scale = fitloop.exp_logit_scale(who, logit_scale)
         self.tower = _ProDATower(who, clip_model, ids_all, self.C, self.P, self.Pb, self.n_ctx, nl, last, seq_rows)
         dev = clip_model.device
@@ -266,6 +269,7 @@ class ProDAFitState(fitmonitor.Monitored):
         self._perm = None
         self.steps = 0
         self._scaler = _BlockScaler(self.scaler, dev) if self.dynamic else None
+        self._adam = _AdamBlock(self.optimizer, betas, eps, weight_decay, self.ctx) if self.optimizer != "sgd" else None
         self._ids = ids_all[:self.C]
         self._val = None            # what a validation keeps between epochs: the inference operands and the two workspaces
         self.val_class_chunk = None # validate's classes per tower call when its argument is None (None: 4096 // n_prompt, at least 1)
@@ -370,8 +374,13 @@ class ProDAFitState(fitmonitor.Monitored):
         address); anything else is checked and ordered on the host.  ``one_call``: the same launches through
         clipmi_proda_train_step (clipmi_proda_train_step_scaled under the dynamic scale).  Returns the batch loss, fp32 [1] on the device,
         when ``want_loss``.  Under the dynamic scale a skipped step still counts in ``steps`` -- the selection schedule moves on -- and
-        still returns its loss; whether it was applied is in ``scaler_state()``."""
+        still returns its loss; whether it was applied is in ``scaler_state()``.  Under ``optimizer="adam" | "adamw"`` the gather-reduce
+        leaves the contexts' gradient as ``context_gradient`` returns it -- every context has one, its no-class prompt's row -- and
+        clipmi_block_step_adam applies it to the whole collection (clipmi_block_step_adam_scaled under the dynamic scale, on the gradient
+        formed at ``grad_scale = 1``); ``one_call`` is then refused: the one-call steps stay SGD."""
         who = "ProDAFitState.step"
+        if one_call and self._adam is not None:
+            raise ValueError(f"{who}: one_call=True with optimizer={self.optimizer!r}: the one-call steps stay SGD")
         labels_d = _check_batch(who, features, labels, self.C, self.tower.E)
         _need_gpu(features, "features")
         if features.dtype != torch.float32 or features.stride(1) != 1:
@@ -390,7 +399,15 @@ class ProDAFitState(fitmonitor.Monitored):
         t, m, first = self.tower, self.tower.model, self.steps == 0
         sgd = (self.momentum, self.dampening, self.weight_decay, self.nesterov)
         losses = torch.empty(3, dtype=torch.float32, device=dev)
-        if self.dynamic:
+        if self._adam is not None:
+            gs = 1.0 if self.dynamic else self.grad_scale
+            text = t.forward(self.ctx, sel_d)
+            _, d_text = ops.proda_head(features, labels_d, text, t.n_cls, t.Pb, self.scale, gs, self.alpha, losses)
+            if self.dynamic:
+                ops.grad_scale_rows(d_text, self._scaler.block)
+            grad = ops.proda_ctx_step(t.backward(d_text), sel_d, t.pos, t.name_lens, t.n_ctx, gs)
+            self._adam.step(grad, self.ctx, lr_d, 1.0, self._scaler)
+        elif self.dynamic:
             self._step_scaled(features, labels_d, sel_d, lr_d, losses, one_call)
         elif one_call:
             ws = t.one_call_workspace(features.shape[0])
@@ -447,7 +464,8 @@ def fit_context(features: torch.Tensor, labels, clip_model, tokenized_prompts, c
                 prompt_bs: int = 4, alpha: float = 0.1, logit_scale: float = 4.6052, lr: float = 0.002, epochs: int = 200, batch_size: int = 32,
                 momentum: float = 0.9, dampening: float = 0.0, weight_decay: float = 5e-4, nesterov: bool = False,
                 grad_scale: float = DEFAULT_GRAD_SCALE, seq_rows: Optional[int] = None, lr_per_epoch: Optional[Sequence[float]] = None, order=None,
-                drop_last: bool = False, name_lens=None, selections=None, generator: Optional[torch.Generator] = None, val=None,
+                drop_last: bool = False, name_lens=None, selections=None, generator: Optional[torch.Generator] = None,
+                optimizer: str = "sgd", betas=(0.9, 0.999), eps: float = 1e-8, val=None,
                 val_class_chunk: Optional[int] = None, val_bins: int = 10, final_model: str = "last_step", val_criterion: str = "accuracy",
                 return_monitor: bool = False, return_history: bool = False, scaler: Optional[dict] = None, return_scaler_state: bool = False):
     """Train ProDA's contexts on cached ``features`` fp32 [N, E] and ``labels`` [N], starting from ``ctx`` [n_prompt, n_ctx, D] (not
@@ -467,7 +485,11 @@ def fit_context(features: torch.Tensor, labels, clip_model, tokenized_prompts, c
     the contexts of the epoch that was strictly better than every earlier one (the starting contexts when no epoch was taken) and is
     refused without ``val``; ``return_monitor`` adds ``ProDAFitState.monitor()``'s dict as the last element of the result.  The six
     validation arguments stand in front of ``return_history`` (``scaler`` and ``return_scaler_state`` stay the signature's last two): pass
-    them, and the three behind them, by keyword."""
+    them, and the three behind them, by keyword.
+
+    ``optimizer``, ``betas``, ``eps``: "sgd" (the default; ``momentum``, ``dampening``, ``nesterov``), "adam" or
+    "adamw", as ``coopfit.fit_context`` takes them; ``weight_decay`` keeps this fit's default of 5e-4 under all three (torch's AdamW
+    default of 1e-2 is NOT taken over).  DESIGN.md "Adam steps for the prompt fits"."""
     who = "fit_context"
     fitmonitor.check_args(who, val, val_bins, final_model, val_criterion)
     if val is not None and val_class_chunk is not None and (isinstance(val_class_chunk, bool) or int(val_class_chunk) != val_class_chunk
@@ -483,7 +505,7 @@ def fit_context(features: torch.Tensor, labels, clip_model, tokenized_prompts, c
         raise ValueError(f"{who}: features must be a [N >= 1, E = {E}] tensor")
     N = features.shape[0]
     epochs, batch_size = fitloop.check_run(who, epochs, batch_size)
-    fitloop.check_sgd(who, momentum, dampening, weight_decay, nesterov)
+    fitloop.check_optimizer(who, optimizer, momentum, dampening, nesterov, weight_decay, betas, eps)
     dynamic, _, cfg = _scale_args(who, grad_scale, scaler)
     if return_scaler_state and not dynamic:
         raise ValueError(f"{who}: return_scaler_state is an argument of grad_scale={DYNAMIC!r}")
@@ -512,7 +534,7 @@ def fit_context(features: torch.Tensor, labels, clip_model, tokenized_prompts, c
         return out if len(out) > 1 else out[0]
     _need_gpu(features, "features")
     state = ProDAFitState(clip_model, tokenized_prompts, ctx, prompt_bs, alpha, logit_scale, momentum, dampening, nesterov, weight_decay, grad_scale,
-                          seq_rows, name_lens, scaler=scaler)
+                          seq_rows, name_lens, scaler=scaler, optimizer=optimizer, betas=betas, eps=eps)
     sels_d = torch.from_numpy(np.ascontiguousarray(sels, dtype=np.int32)).to(dev)
     end_epoch = None
     if val is not None:

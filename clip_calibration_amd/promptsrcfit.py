@@ -319,11 +319,12 @@ class PromptSRCFitState(vptfit._BlockFitState):
     _who, _n_losses = "PromptSRCFitState", 5
 
     def __init__(self, model, tokenized_prompts, params: Dict[str, torch.Tensor], teacher: torch.Tensor, logit_scale: float = 4.6052,
-                 w_text: float = 25.0, w_image: float = 10.0, w_logit: float = 1.0, momentum: float = 0.9, dampening: float = 0.0, nesterov: bool = False,
-                 weight_decay: float = 5e-4, grad_scale: float = DEFAULT_GRAD_SCALE, seq_rows: Optional[int] = None, method: str = "promptsrc",
-                 class_token_position: str = "end", scaler: Optional[dict] = None):
+                 w_text: float = 25.0, w_image: float = 10.0, w_logit: float = 1.0, momentum: float = 0.9, dampening: float = 0.0,
+                 nesterov: bool = False, weight_decay: float = 5e-4, grad_scale: float = DEFAULT_GRAD_SCALE, seq_rows: Optional[int] = None,
+                 method: str = "promptsrc", class_token_position: str = "end", scaler: Optional[dict] = None, optimizer: str = "sgd", betas=(0.9, 0.999),
+                 eps: float = 1e-8):
         who = "PromptSRCFitState"
-        self._init_optimiser(who, logit_scale, momentum, dampening, nesterov, weight_decay, grad_scale, scaler)
+        self._init_optimiser(who, logit_scale, momentum, dampening, nesterov, weight_decay, grad_scale, scaler, optimizer, betas, eps)
         self.weights = _method_weights(who, method, w_text, w_image, w_logit)
         self.towers = _Towers(who, model, tokenized_prompts, params, seq_rows, class_token_position)
         self.C = self.towers.C
@@ -331,7 +332,7 @@ class PromptSRCFitState(vptfit._BlockFitState):
         self._init_block(pack_block(params, model.device))
         self.gpa = None
         self.epochs_seen = 0
-        self._scaled_grad = torch.empty_like(self.block) if self.dynamic else None    # scale * gradient, as clipmi_promptsrc_step leaves it
+        self._scaled_grad = torch.empty_like(self.block) if self._defer else None    # scale * gradient, as clipmi_promptsrc_step leaves it
 
     def params(self, block: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
         return unpack_block(self.block if block is None else block, *self.towers.shape())
@@ -373,12 +374,12 @@ class PromptSRCFitState(vptfit._BlockFitState):
         return d_text, d_feats
 
     def _apply(self, outs, lr_d, first, sgd):
-        """Under the dynamic scale clipmi_promptsrc_step leaves scale * gradient in ``_scaled_grad`` and applies nothing."""
+        """Under the dynamic scale and under Adam clipmi_promptsrc_step leaves scale * gradient in ``_scaled_grad`` and applies nothing."""
         tw = self.towers
         d_embed, d_deep, d_vis = tw.backward(*outs)
-        grad, buf, gs, lr, first = (self._scaled_grad, None, 1.0, None, 0) if self.dynamic else (None, self.buf, self.grad_scale, lr_d, first)
+        grad, buf, gs, lr, first = (self._scaled_grad, None, 1.0, None, 0) if self._defer else (None, self.buf, self.grad_scale, lr_d, first)
         check(lib.clipmi_promptsrc_step(d_embed.data_ptr(), None if d_deep is None else d_deep.data_ptr(), d_vis.data_ptr(), self.block.data_ptr(),
-                                        None if buf is None else buf.data_ptr(), None if grad is None else grad.data_ptr(), int(not self.dynamic), tw.C,
+                                        None if buf is None else buf.data_ptr(), None if grad is None else grad.data_ptr(), int(not self._defer), tw.C,
                                         tw.text.L, *tw.shape(), gs, None if lr is None else lr.data_ptr(), int(first), *sgd, ops._stream()),
               "clipmi_promptsrc_step")
         return grad
@@ -417,12 +418,13 @@ def init_params(model, seed: int = 0) -> Dict[str, torch.Tensor]:
 
 
 def fit_prompts(images_or_loader, labels, model, tokenized_prompts, teacher: torch.Tensor, params: Optional[Dict[str, torch.Tensor]] = None,
-                method: str = "promptsrc", logit_scale: float = 4.6052, lr: float = 0.0025, epochs: int = 50, batch_size: int = 4, momentum: float = 0.9,
-                dampening: float = 0.0, weight_decay: float = 5e-4, nesterov: bool = False, w_text: float = 25.0, w_image: float = 10.0,
+                method: str = "promptsrc", logit_scale: float = 4.6052, lr: float = 0.0025, epochs: int = 50, batch_size: int = 4,
+                momentum: float = 0.9, dampening: float = 0.0, weight_decay: float = 5e-4, nesterov: bool = False, w_text: float = 25.0, w_image: float = 10.0,
                 w_logit: float = 1.0, gpa=(30.0, 30.0), grad_scale: float = DEFAULT_GRAD_SCALE, seq_rows: Optional[int] = None,
                 lr_per_epoch: Optional[Sequence[float]] = None, drop_last: bool = False, return_history: bool = False, one_call: bool = False,
-                class_token_position: str = "end", scaler: Optional[dict] = None, val=None, val_batch_size: int = 32, val_bins: int = 10,
-                final_model: str = "last_step", val_criterion: str = "accuracy", return_monitor: bool = False):
+                class_token_position: str = "end", scaler: Optional[dict] = None, optimizer: str = "sgd", betas=(0.9, 0.999), eps: float = 1e-8,
+                val=None, val_batch_size: int = 32, val_bins: int = 10, final_model: str = "last_step", val_criterion: str = "accuracy",
+                return_monitor: bool = False):
     """Train the prompts starting from ``params`` (not modified; None = ``init_params(model)``): ``epochs`` passes of
     ``torch.optim.SGD(lr, momentum, dampening, weight_decay, nesterov)`` over the whole parameter list on PromptSRC's loss.
     ``images_or_loader`` is a tensor of preprocessed images [N, 3, R, R] with ``labels`` [N], cut into batches of ``batch_size`` in order
@@ -440,7 +442,11 @@ def fit_prompts(images_or_loader, labels, model, tokenized_prompts, teacher: tor
     ``return_monitor`` as ``vptfit.fit_prompts`` takes them.  Behind every epoch the GPA work comes first and the validation second, the
     reference's order (promptsrc.py:321-336 inside ``forward_backward``, ahead of Dassl's ``after_epoch``): epochs 0 .. E-2 score the
     block the epoch trained, the last epoch scores the aggregate GPA has just loaded.  The fitted parameters are bit for bit those of the
-    same call without ``val``; "best_val" returns the best epoch's block (the aggregate when the last epoch is the best)."""
+    same call without ``val``; "best_val" returns the best epoch's block (the aggregate when the last epoch is the best).
+
+    ``optimizer``, ``betas``, ``eps``: "sgd" (the default; ``momentum``, ``dampening``, ``nesterov``), "adam" or
+    "adamw", as ``coopfit.fit_context`` takes them; ``weight_decay`` keeps this fit's default of 5e-4 under all three (torch's AdamW
+    default of 1e-2 is NOT taken over).  ``one_call=True`` with an Adam optimiser is refused.  DESIGN.md "Adam steps for the prompt fits"."""
     who = "fit_prompts"
     fitmonitor.check_image_args(who, val, val_batch_size, val_bins, final_model, val_criterion)
     epochs = int(epochs)
@@ -448,10 +454,12 @@ def fit_prompts(images_or_loader, labels, model, tokenized_prompts, teacher: tor
         raise ValueError(f"{who}: epochs={epochs} (>= 0)")
     if method not in METHODS:
         raise ValueError(f"{who}: method={method!r} must be one of {METHODS}")
+    if optimizer != "sgd":      # by this function's name; SGD's arguments are the state's to check, as before
+        fitloop.check_optimizer(who, optimizer, momentum, dampening, nesterov, weight_decay, betas, eps, one_call=one_call)
     if params is None:
         params = init_params(model)
     state = PromptSRCFitState(model, tokenized_prompts, params, teacher, logit_scale, w_text, w_image, w_logit, momentum, dampening, nesterov, weight_decay,
-                              grad_scale, seq_rows, method, class_token_position, scaler)
+                              grad_scale, seq_rows, method, class_token_position, scaler, optimizer, betas, eps)
     weights = None if method == "ivlp" else _gpa_for(who, gpa, epochs)
 
     batches = fitloop.cut_batches(who, images_or_loader, labels, state.C, batch_size, drop_last, model.device)

@@ -47,7 +47,7 @@ import torch
 
 from . import _lib, fitloop, fitmonitor, ops
 from ._lib import _DT, check, lib
-from .coopfit import DYNAMIC, _BlockScaler, _pack_dgrad, _check_grad_scale, _is_dynamic, _scale_args, operand_stats_dict
+from .coopfit import DYNAMIC, _AdamBlock, _BlockScaler, _pack_dgrad, _check_grad_scale, _is_dynamic, _scale_args, operand_stats_dict
 from .fitloop import _need_gpu
 
 # 2^12: CoOp's value (profiles/coopfit_parity.txt) holds for the image tower's backward at the ViT-B/16 geometry as well
@@ -290,12 +290,19 @@ class _BlockFitState(fitmonitor.ImageMonitored):
     _master_name = "block"
     _n_losses = 1
 
-    def _init_optimiser(self, who: str, logit_scale: float, momentum: float, dampening: float, nesterov: bool, weight_decay: float, grad_scale, scaler) -> None:
-        """The refusals that need no model, in the order every state has made them."""
+    def _init_optimiser(self, who: str, logit_scale: float, momentum, dampening, nesterov, weight_decay: float, grad_scale, scaler,
+                        optimizer: str = "sgd", betas=(0.9, 0.999), eps: float = 1e-8) -> None:
+        """The refusals that need no model, in the order every state has made them.  ``optimizer``: "sgd" (``momentum``, ``dampening``,
+        ``nesterov``), "adam" or "adamw" (``betas``, ``eps``; ``weight_decay`` keeps the fit's own default -- torch's
+        AdamW default of 1e-2 is NOT taken over)."""
         self.dynamic, self.grad_scale, self.scaler = _scale_args(who, grad_scale, scaler)
-        fitloop.check_sgd(who, momentum, dampening, weight_decay, nesterov)
+        self.optimizer, momentum, dampening, nesterov, self._betas = fitloop.check_optimizer(who, optimizer, momentum, dampening, nesterov, weight_decay,
+                                                                                             betas, eps)
+        self._eps = eps
         self.scale = fitloop.exp_logit_scale(who, logit_scale)
         self.momentum, self.dampening, self.nesterov, self.weight_decay = momentum, dampening, nesterov, weight_decay
+        # the block's step entry forms the gradient at grad_scale = 1 and applies nothing: under the dynamic scale and under Adam
+        self._defer = self.dynamic or self.optimizer != "sgd"
 
     def _init_block(self, master: torch.Tensor) -> None:
         """``master`` becomes the block the steps update; the buffer, the step count and the scaler's device block with it."""
@@ -303,6 +310,7 @@ class _BlockFitState(fitmonitor.ImageMonitored):
         self.buf = torch.zeros_like(master) if self.momentum != 0.0 else None
         self.steps = 0
         self._scaler = _BlockScaler(self.scaler, master.device) if self.dynamic else None
+        self._adam = _AdamBlock(self.optimizer, self._betas, self._eps, self.weight_decay, master) if self.optimizer != "sgd" else None
 
     def _master(self) -> torch.Tensor:
         return getattr(self, self._master_name)
@@ -323,8 +331,13 @@ class _BlockFitState(fitmonitor.ImageMonitored):
         (the first of the head's losses, all kept in ``last_losses``), when ``want_loss``.  Under ``grad_scale="dynamic"`` the head runs at
         ``grad_scale = 1``, the head's output gradients are multiplied by the device block's scale, the gradient block is formed without
         being applied and clipmi_block_step_scaled decides on the device whether the step is applied (one call: the ``_scaled`` symbol);
-        a skipped step still counts in ``steps`` and still returns its loss; whether it was applied is in ``scaler_state()``."""
+        a skipped step still counts in ``steps`` and still returns its loss; whether it was applied is in ``scaler_state()``.  Under
+        ``optimizer="adam" | "adamw"`` the gradient block is formed the same way -- at ``grad_scale = 1``, not applied -- and
+        clipmi_block_step_adam divides it by ``grad_scale`` and applies the rule (clipmi_block_step_adam_scaled under the dynamic scale);
+        ``one_call`` is then refused: the one-call steps stay SGD."""
         who = f"{self._who}.step"
+        if one_call and self._adam is not None:
+            raise ValueError(f"{who}: one_call=True with optimizer={self.optimizer!r}: the one-call steps stay SGD")
         v = self._vision()
         images = v.images(who, images)
         dev, B = images.device, images.shape[0]
@@ -348,6 +361,9 @@ class _BlockFitState(fitmonitor.ImageMonitored):
             if self.dynamic:
                 for d_out in outs:
                     ops.grad_scale_rows(d_out, self._scaler.block)
+            if self._adam is not None:      # the block of grad_scale * gradient (the scaler's scale * gradient under the dynamic scale)
+                self._adam.step(self._apply(outs, lr_d, first, sgd), self._master(), lr_d, 1.0 if self.dynamic else self.grad_scale, self._scaler)
+            elif self.dynamic:
                 self._scaler.step(self._apply(outs, lr_d, first, sgd), self._master(), self.buf, lr_d, *sgd)
             else:
                 self._apply(outs, lr_d, first, sgd)
@@ -365,12 +381,12 @@ class VPTFitState(_BlockFitState):
 
     def __init__(self, model, text_features: torch.Tensor, logit_scale: float = 4.6052, prompts: Optional[torch.Tensor] = None,
                  momentum: float = 0.9, dampening: float = 0.0, nesterov: bool = False, weight_decay: float = 5e-4,
-                 grad_scale: float = DEFAULT_GRAD_SCALE, scaler: Optional[dict] = None):
+                 grad_scale: float = DEFAULT_GRAD_SCALE, scaler: Optional[dict] = None, optimizer: str = "sgd", betas=(0.9, 0.999), eps: float = 1e-8):
         who = "VPTFitState"
         if prompts is None:
             prompts = model_prompts(model)
         self.depth, self.n_ctx = _check_prompts(who, model, prompts)
-        self._init_optimiser(who, logit_scale, momentum, dampening, nesterov, weight_decay, grad_scale, scaler)
+        self._init_optimiser(who, logit_scale, momentum, dampening, nesterov, weight_decay, grad_scale, scaler, optimizer, betas, eps)
         self.text = _check_text(who, model, text_features)
         self.C = int(self.text.shape[0])
         self.tower = _Tower(who, model, self.depth, self.n_ctx)
@@ -414,17 +430,18 @@ class VPTFitState(_BlockFitState):
         return vpt_head(self.tower.forward(images, self.prompts), labels_d, self.text, self.scale, grad_scale, loss)[1:]
 
     def _apply(self, outs, lr_d, first, sgd):
-        """The tower's backward leaves the prompts' gradient as it is: under the dynamic scale that is the block the scaled step takes."""
+        """The tower's backward leaves the prompts' gradient as it is: under the dynamic scale and under Adam that is the block the
+        step behind it takes."""
         grad = self.tower.backward(outs[0])
-        return grad if self.dynamic else vpt_step(grad, self.grad_scale, self.prompts, self.buf, lr_d, first, *sgd, want_grad=False)
+        return grad if self._defer else vpt_step(grad, self.grad_scale, self.prompts, self.buf, lr_d, first, *sgd, want_grad=False)
 
 
 def fit_prompts(images_or_loader, labels, model, text_features: torch.Tensor, prompts: Optional[torch.Tensor] = None, logit_scale: float = 4.6052,
                 lr: float = 0.0025, epochs: int = 5, batch_size: int = 32, momentum: float = 0.9, dampening: float = 0.0,
                 weight_decay: float = 5e-4, nesterov: bool = False, grad_scale: float = DEFAULT_GRAD_SCALE,
                 lr_per_epoch: Optional[Sequence[float]] = None, drop_last: bool = False, return_history: bool = False,
-                scaler: Optional[dict] = None, val=None, val_batch_size: int = 32, val_bins: int = 10, final_model: str = "last_step",
-                val_criterion: str = "accuracy", return_monitor: bool = False):
+                scaler: Optional[dict] = None, optimizer: str = "sgd", betas=(0.9, 0.999), eps: float = 1e-8, val=None, val_batch_size: int = 32,
+                val_bins: int = 10, final_model: str = "last_step", val_criterion: str = "accuracy", return_monitor: bool = False):
     """Train VPT's prompts starting from ``prompts`` (not modified; None = the model's own parameters): ``epochs`` passes of
     ``torch.optim.SGD(lr, momentum, dampening, weight_decay, nesterov)``.  ``images_or_loader`` is a tensor of preprocessed images
     [N, 3, R, R] with ``labels`` [N], cut into batches of ``batch_size`` in order (the last one short unless ``drop_last``), or a sized
@@ -440,13 +457,19 @@ def fit_prompts(images_or_loader, labels, model, text_features: torch.Tensor, pr
     prompts against them on the device in chunks of ``val_batch_size``, into ``val_bins`` confidence bins -- the fitted prompts are bit for
     bit those of the same call without ``val``, and the run still synchronises once.  ``final_model``, ``val_criterion`` and
     ``return_monitor`` as ``coopfit.fit_context`` takes them: "best_val" returns the prompts of the epoch that was strictly better than
-    every earlier one (the starting prompts when no epoch was taken) and is refused without ``val``."""
+    every earlier one (the starting prompts when no epoch was taken) and is refused without ``val``.
+
+    ``optimizer``, ``betas``, ``eps``: "sgd" (the default; ``momentum``, ``dampening``, ``nesterov``), "adam" or
+    "adamw", as ``coopfit.fit_context`` takes them; ``weight_decay`` keeps this fit's default of 5e-4 under all three (torch's AdamW
+    default of 1e-2 is NOT taken over).  DESIGN.md "Adam steps for the prompt fits"."""
     who = "fit_prompts"
     fitmonitor.check_image_args(who, val, val_batch_size, val_bins, final_model, val_criterion)
     epochs = int(epochs)
     if epochs < 0:
         raise ValueError(f"{who}: epochs={epochs} (>= 0)")
-    state = VPTFitState(model, text_features, logit_scale, prompts, momentum, dampening, nesterov, weight_decay, grad_scale, scaler)
+    if optimizer != "sgd":      # by this function's name; SGD's arguments are the state's to check, as before
+        fitloop.check_optimizer(who, optimizer, momentum, dampening, nesterov, weight_decay, betas, eps)
+    state = VPTFitState(model, text_features, logit_scale, prompts, momentum, dampening, nesterov, weight_decay, grad_scale, scaler, optimizer, betas, eps)
     batches = fitloop.cut_batches(who, images_or_loader, labels, state.C, batch_size, drop_last, model.device)
     _, lr_steps = fitloop.schedule(who, lr, epochs, lr_per_epoch, len(batches), model.device)
     end_epoch = None

@@ -1377,6 +1377,35 @@ int clipmi_block_step_scaled(const float* grad, float* params, float* buf, float
                              float growth_factor, float backoff_factor, int growth_interval, const float* lr, float momentum, float dampening,
                              float weight_decay, int nesterov, void* workspace, size_t workspace_bytes, clipmi_stream_t stream);
 
+/* torch.optim.Adam's and torch.optim.AdamW's step (no amsgrad) on ONE fp32 master block, for the prompt fits: their own launches form the
+ * block's gradient without applying it (apply = 0 / grad_out) and one of these two calls applies it (csrc/optim_step.hip, DESIGN.md "Adam
+ * steps for the prompt fits").  Additive exports: the ABI version stays.
+ *   grad [total]        grad_scale * gradient (clipmi_block_step_adam) or state->scale * gradient (the _scaled call); g = grad * (1 / scale)
+ *   params, exp_avg, exp_avg_sq [total]   the master block and Adam's two moments (zero before the first step), updated in place
+ *   grad_out [total]    optional (NULL): receives g; may be grad itself
+ *   lr                  the step's rate, fp32 [1] on the device
+ *   bias_table          float64 [table_len, 2] on the device, 8-byte aligned: row t - 1 holds 1 - beta1^t and sqrt(1 - beta2^t) as the host
+ *                       forms them in double for Adam's step number t = 1 .. table_len; the kernels index it and call no pow
+ *   decoupled           0: Adam (g += weight_decay w, then the rule); != 0: AdamW (w *= 1 - lr weight_decay, then the rule without weight decay)
+ * clipmi_block_step_adam is ONE launch, one thread per element, at the caller's step number t (1 on the first step).
+ * clipmi_block_step_adam_scaled is three launches: clipmi_block_step_scaled's first two (unscale and flag; decide and update the state
+ * block) and the rule on a clean step alone, at t = state->applied_steps as the second launch has just left it (this step counted).  A
+ * skipped step writes none of params, exp_avg, exp_avg_sq and does not advance t; the caller keeps table_len >= the steps it has enqueued
+ * (an upper bound of the applied ones; a t behind the table writes nothing).  With the flags clear the scaled call's bits are the static
+ * call's at grad_scale = scale and t = applied_steps.  No atomics, integer flags, the same inputs give the same bits.  workspace (256-byte
+ * aligned): clipmi_block_step_adam_scaled_workspace_bytes(total) bytes, 0 for a total the call refuses.  Every check precedes the first
+ * launch.  CLIPMI_ERR_ARG: a null pointer (grad, params, exp_avg, exp_avg_sq, lr, bias_table; state and the workspace), a pointer that is
+ * not aligned, table_len < 1, t < 1, t > table_len, a beta outside [0, 1), eps not finite or <= 0, weight_decay negative or not finite,
+ * grad_scale not finite or <= 0, the scaler's own refusals; CLIPMI_ERR_SHAPE: total < 1 or total >= 2^39; CLIPMI_ERR_WORKSPACE. */
+int clipmi_block_step_adam(const float* grad, float* params, float* exp_avg, float* exp_avg_sq, float* grad_out, int64_t total, float grad_scale,
+                           const float* lr, int64_t t, const double* bias_table, int64_t table_len, double beta1, double beta2, double eps,
+                           float weight_decay, int decoupled, clipmi_stream_t stream);
+size_t clipmi_block_step_adam_scaled_workspace_bytes(int64_t total);
+int clipmi_block_step_adam_scaled(const float* grad, float* params, float* exp_avg, float* exp_avg_sq, float* grad_out, int64_t total,
+                                  clipmi_scaler_state* state, float growth_factor, float backoff_factor, int growth_interval, const float* lr,
+                                  const double* bias_table, int64_t table_len, double beta1, double beta2, double eps, float weight_decay,
+                                  int decoupled, void* workspace, size_t workspace_bytes, clipmi_stream_t stream);
+
 /* The four one-call steps under the scaler.  Each is its static call with `state` and the scaler's three arguments in grad_scale's place
  * and without first_step (the state block knows the first applied step), and enqueues, in order: the static call's launches up to the
  * head, the head at grad_scale = 1, clipmi_grad_scale_rows on every fp32 gradient the head hands to a backward (d_text for CoCoOp; d_feats
