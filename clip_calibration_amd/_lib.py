@@ -248,6 +248,8 @@ _SIGNATURES = {
     "clipmi_shard_prograd_workspace_bytes": (_sz, [_i64]),
     "clipmi_shard_prograd_dots": (_i, [_vp, _vp, _i, _i64, _i, _i, _i, _i, _i, _f, _vp, _vp, _sz, _vp]),
     "clipmi_shard_prograd_apply": (_i, [_vp, _i, _f, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i, _f, _f, _f, _i, _vp, _sz, _vp]),
+    "clipmi_block_rank_mean": (_i, [_vp, _i, _sz, _sz, _vp, _vp]),
+    "clipmi_block_step_gathered": (_i, [_vp, _i, _sz, _sz, _f, _vp, _vp, _vp, _vp, _i, _f, _f, _f, _i, _vp]),
     "clipmi_ctx_step_scaled_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "clipmi_ctx_step_scaled": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _f, _f, _i, _vp, _f, _f, _f, _i, _vp, _sz, _vp]),
     "clipmi_prompt_train_step_scaled_bytes": (_sz, [_vp, _i, _i, _i, _i, _i, _i]),

@@ -392,6 +392,36 @@ def shard_states(make, shard: Optional[Shard]):
     return [make(shard.peer(r)) for r in range(shard.world)][shard.rank]
 
 
+def _file_state(shard: Shard, state) -> None:
+    """A new shard state files itself with its local gather (nothing to do under an RCCL gather)."""
+    if shard.local is not None:
+        shard.local.states[shard.rank], shard.local.driver = state, None      # a new set of states chooses its driver anew
+
+
+def _world_states(shard: Shard, state, who: str):
+    """The states whose phases this process runs: ``state`` alone, or all of a local gather's world."""
+    local = shard.local
+    if local is None:
+        return [state]
+    if any(s is None for s in local.states):
+        raise ValueError(f"{who}: the LocalGather holds {sum(s is not None for s in local.states)} of its {local.world} shard states; "
+                         "make one state per rank before the first step")
+    return local.states
+
+
+def _drive(shard: Shard, state, who: str) -> None:
+    """Under a local gather one state drives: a caller who stepped every rank's state, as under RCCL, would take G steps.  The first state
+    that steps is the driver; a step of another state is refused."""
+    local = shard.local
+    if local is None:
+        return
+    if local.driver is None:
+        local.driver = state
+    if local.driver is not state:
+        raise ValueError(f"{who}: under a LocalGather the step of rank {local.driver.shard.rank}'s state steps every rank; "
+                         f"rank {shard.rank}'s state must not be stepped as well")
+
+
 def _run_phases(gens) -> None:
     """Advance the shard states' phase generators in lock step, rank after rank, until they end (they end together: every rank runs the
     same phases).  One generator under an RCCL gather; all ``world`` under a local one, where a phase's last post completes the gather."""
@@ -696,8 +726,7 @@ class CoOpFitState(fitmonitor.Monitored):
             self._all_dots = torch.empty(n, 3, dtype=torch.float64, device=dev)
             self._prograd_ws = ops.shard_prograd_workspace(self.ctx.numel(), dev)
         self._rows = None           # gathered_context's blocks, made on first use
-        if sh.local is not None:
-            sh.local.states[sh.rank], sh.local.driver = self, None      # a new set of states chooses its driver anew
+        _file_state(sh, self)
 
     def _gather_rows(self, own: torch.Tensor):
         """A phase: the ranks' own rows of a class-specific [C_r, n_ctx, D] block gathered into the full [C, n_ctx, D]; the result is
@@ -759,13 +788,7 @@ class CoOpFitState(fitmonitor.Monitored):
 
     def _shard_states(self, who: str):
         """The states whose phases this process runs: this one alone, or all of a local gather's world."""
-        local = self.shard.local
-        if local is None:
-            return [self]
-        if any(s is None for s in local.states):
-            raise ValueError(f"{who}: the LocalGather holds {sum(s is not None for s in local.states)} of its {local.world} shard states; "
-                             "make one state per rank before the first step")
-        return local.states
+        return _world_states(self.shard, self, who)
 
     def gathered_context(self) -> torch.Tensor:
         """The whole context on the device: ``ctx`` itself for a generic context (every rank holds the same bits) and without ``shard``;
@@ -885,13 +908,7 @@ class CoOpFitState(fitmonitor.Monitored):
             if one_call:
                 raise ValueError("CoOpFitState.step: shard has no one-call step (one_call=True); the sharded step is the separate calls")
             states = self._shard_states("CoOpFitState.step")
-            local = self.shard.local
-            if local is not None:       # one state drives: a caller who stepped every rank's state, as under RCCL, would take G steps
-                if local.driver is None:
-                    local.driver = self
-                if local.driver is not self:
-                    raise ValueError(f"CoOpFitState.step: under a LocalGather the step of rank {local.driver.shard.rank}'s state steps every rank; "
-                                     f"rank {self.shard.rank}'s state must not be stepped as well")
+            _drive(self.shard, self, "CoOpFitState.step")
             _run_phases([s._shard_phases(features, labels_d, lr_d, losses if s is self else _new_losses(s.method, dev), first) for s in states])
             for s in states:
                 s.steps += s is not self

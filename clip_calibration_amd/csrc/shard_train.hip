@@ -5,6 +5,8 @@
 //   ctx_step_gathered_kernel    the G partials added in rank order, 1 / grad_scale, torch.optim.SGD's rule (sgd_element_fma)
 //   shard_prograd_*_kernel      ProGrad on the reduced vectors (generic context) or on a rank's own rows (class-specific context): the
 //                               float64 dots of one rank, then the G ranks' dots added in rank order, the decision and the step
+//   block_rank_mean_kernel      the batch-sharded block fits' reduction: G gathered blocks -> their rank-ordered mean (VPT, MaPLe, PromptSRC)
+//   block_step_gathered_kernel  the same mean, 1 / grad_scale and the SGD rule in one launch: the static SGD route of those fits
 // With G = 1 every chain is the unsharded kernel's chain (prompt_train.hip): the same additions in the same order, the same partition of
 // the float64 dots, the same rules of train_rules.h -- the same bits.  No float atomics, no workgroup waits for another.
 #include <cmath>
@@ -143,6 +145,72 @@ int check_step(const char* who, const float* ctx, const float* buf, const float*
 
 inline unsigned blocks_of(int64_t total) { return (unsigned)((total + THREADS - 1) / THREADS); }
 
+// ------------------------------------------------------- the batch-sharded block fits (DESIGN.md "Batch-sharded image-tower fits")
+// The G ranks' send blocks [scale * gradient | losses], gathered rank-major, become the block every rank agrees on: the rank-ordered sum
+// times inv = (float)(1.0 / G).  A streaming kernel: G reads and one write per element, no reuse.  The middle of the block goes through
+// 16-byte loads and stores, a capped grid striding over it; the floats in front of the first 16-byte boundary and behind the last whole
+// vector go one by one, and so does the whole block when the rows' bases or the output do not share the first row's alignment.
+constexpr int MEAN_MAX_BLOCKS = 2048;
+
+__device__ __forceinline__ float4 rank_sum4(const float* __restrict__ partials, int64_t idx, int G, int64_t stride) {
+  float4 s = *reinterpret_cast<const float4*>(partials + idx);
+#pragma unroll 4
+  for (int r = 1; r < G; ++r) {
+    const float4 p = *reinterpret_cast<const float4*>(partials + (int64_t)r * stride + idx);
+    s.x += p.x;
+    s.y += p.y;
+    s.z += p.z;
+    s.w += p.w;
+  }
+  return s;
+}
+
+// elements [head, head + 4 nvec) as vectors; [0, head) and [head + 4 nvec, total) as scalars (head == total, nvec == 0: all of them)
+__global__ __launch_bounds__(THREADS) void block_rank_mean_kernel(const float* __restrict__ gathered, int G, int64_t stride, int64_t total, int64_t head,
+                                                                  int64_t nvec, float inv, float* __restrict__ out) {
+  const int64_t tid = (int64_t)blockIdx.x * THREADS + threadIdx.x, step = (int64_t)gridDim.x * THREADS;
+  for (int64_t v = tid; v < nvec; v += step) {
+    const int64_t idx = head + 4 * v;
+    float4 s = rank_sum4(gathered, idx, G, stride);
+    s.x *= inv;
+    s.y *= inv;
+    s.z *= inv;
+    s.w *= inv;
+    *reinterpret_cast<float4*>(out + idx) = s;
+  }
+  const int64_t tail = head + 4 * nvec, n_scalar = head + (total - tail);
+  for (int64_t k = tid; k < n_scalar; k += step) {
+    const int64_t idx = k < head ? k : tail + (k - head);
+    out[idx] = rank_sum(gathered, idx, G, stride) * inv;
+  }
+}
+
+// the static SGD route's step from the gathered blocks: the mean as above, 1 / grad_scale, torch.optim.SGD's rule -- with G = 1 the
+// arithmetic of a block's own step entry (maple_step_kernel, promptsrc_step_kernel, vpt_step_kernel) behind its scale * gradient
+__global__ __launch_bounds__(THREADS) void block_step_gathered_kernel(const float* __restrict__ gathered, int G, int64_t stride, float* __restrict__ params,
+                                                                      float* __restrict__ buf, float* __restrict__ grad_out, int64_t total, float inv,
+                                                                      float inv_scale, const float* __restrict__ lr, SgdArgs sgd) {
+  const int64_t idx = (int64_t)blockIdx.x * THREADS + threadIdx.x;
+  if (idx >= total) return;
+  const float g = (rank_sum(gathered, idx, G, stride) * inv) * inv_scale;
+  if (grad_out) grad_out[idx] = g;
+  if (params) sgd_element_fma(params, buf, idx, g, *lr, sgd);
+}
+
+// what both entry points ask of the gathered blocks and of what they write (`out`: total floats), before anything is launched
+int check_gathered(const char* who, const float* gathered, int world, size_t stride, size_t total, const float* out) {
+  CLIPMI_REQUIRE(gathered, CLIPMI_ERR_ARG, "%s: null pointer", who);
+  CLIPMI_REQUIRE((uintptr_t)gathered % 4 == 0 && (uintptr_t)out % 4 == 0, CLIPMI_ERR_ARG, "%s: a pointer is not 4-byte aligned", who);
+  CLIPMI_REQUIRE(world >= 1, CLIPMI_ERR_SHAPE, "%s: world=%d (>= 1)", who, world);
+  CLIPMI_REQUIRE(total >= 1 && total < ((size_t)1 << 39), CLIPMI_ERR_SHAPE, "%s: total=%zu (in [1, 2^39))", who, total);
+  CLIPMI_REQUIRE(stride >= total && stride < ((size_t)1 << 40), CLIPMI_ERR_SHAPE, "%s: stride=%zu below total=%zu (or 2^40 and more)", who, stride, total);
+  if (out) {
+    const uintptr_t g0 = (uintptr_t)gathered, g1 = g0 + 4 * ((size_t)(world - 1) * stride + total), o0 = (uintptr_t)out, o1 = o0 + 4 * total;
+    CLIPMI_REQUIRE(o1 <= g0 || g1 <= o0, CLIPMI_ERR_ARG, "%s: the output overlaps the gathered blocks", who);
+  }
+  return CLIPMI_OK;
+}
+
 }  // namespace
 }  // namespace clipmi
 
@@ -220,6 +288,36 @@ int clipmi_shard_prograd_apply(const double* dots_ranks, int G, float lambda, fl
   hipLaunchKernelGGL(shard_prograd_apply_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, dots_carve(workspace, total), dots_ranks,
                      G, lambda, ctx, buf, grad_out, projected, dots, total, lr, make_sgd_args(momentum, dampening, weight_decay, nesterov, first_step));
   return check_launch("shard_prograd_apply_kernel");
+}
+
+int clipmi_block_rank_mean(const float* gathered, int world, size_t stride, size_t total, float* out, clipmi_stream_t stream) {
+  const char* who = "block_rank_mean";
+  CLIPMI_REQUIRE(out, CLIPMI_ERR_ARG, "%s: null pointer", who);
+  if (int rc = check_gathered(who, gathered, world, stride, total, out)) return rc;
+  // the vector path needs every row's base and the output on the first row's 16-byte phase; the head reaches the first boundary
+  int64_t head = (int64_t)((16 - (uintptr_t)gathered % 16) % 16 / 4), nvec = 0;
+  if (stride % 4 == 0 && (uintptr_t)out % 16 == (uintptr_t)gathered % 16 && (int64_t)total >= head + 4)
+    nvec = ((int64_t)total - head) / 4;
+  else
+    head = (int64_t)total;
+  const int64_t n_scalar = (int64_t)total - 4 * nvec, work = nvec > n_scalar ? nvec : n_scalar, blocks = (work + THREADS - 1) / THREADS;
+  hipLaunchKernelGGL(block_rank_mean_kernel, dim3((unsigned)(blocks < MEAN_MAX_BLOCKS ? blocks : MEAN_MAX_BLOCKS)), dim3(THREADS), 0, (hipStream_t)stream,
+                     gathered, world, (int64_t)stride, (int64_t)total, head, nvec, (float)(1.0 / world), out);
+  return check_launch("block_rank_mean_kernel");
+}
+
+int clipmi_block_step_gathered(const float* gathered, int world, size_t stride, size_t total, float grad_scale, float* params, float* buf, float* grad_out,
+                               const float* lr, int first_step, float momentum, float dampening, float weight_decay, int nesterov, clipmi_stream_t stream) {
+  const char* who = "block_step_gathered";
+  CLIPMI_REQUIRE(params || grad_out, CLIPMI_ERR_ARG, "%s: null pointer (one of params, grad_out is required)", who);
+  if (int rc = check_gathered(who, gathered, world, stride, total, params)) return rc;
+  if (int rc = check_gathered(who, gathered, world, stride, total, buf)) return rc;
+  if (int rc = check_gathered(who, gathered, world, stride, total, grad_out)) return rc;
+  if (int rc = check_step(who, params, buf, lr, (int64_t)total, grad_scale, momentum, dampening, weight_decay, nesterov)) return rc;
+  hipLaunchKernelGGL(block_step_gathered_kernel, dim3(blocks_of((int64_t)total)), dim3(THREADS), 0, (hipStream_t)stream, gathered, world, (int64_t)stride, params,
+                     buf, grad_out, (int64_t)total, (float)(1.0 / world), 1.f / grad_scale, lr,
+                     make_sgd_args(momentum, dampening, weight_decay, nesterov, first_step));
+  return check_launch("block_step_gathered_kernel");
 }
 
 }  // extern "C"

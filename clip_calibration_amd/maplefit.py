@@ -35,7 +35,11 @@ ViT-L lengths (more than 224 token rows per image; configs/trainers/MaPLe/vit_l1
 patches of 14 pixels are served by the image tower's training forward (the patchify + GEMM route of ``vptfit``'s docstring), so with
 the option on that configuration's own towers train here.
 
-Not covered (IVLP and PromptSRC train through ``promptsrcfit``): ``nn.DataParallel``, the ResNet towers, class-token positions other
+``shard=coopfit.Shard(world, rank, gather)`` on ``MaPLeFitState``, ``fit_prompt_learner`` and ``gradients``: the batch-sharded fit of
+``vptfit``'s docstring (the reference's ``nn.DataParallel``, maple.py:273-277); only the image batch is sharded, the text tower runs over
+all C prompts on every rank.  DESIGN.md "Batch-sharded image-tower fits".
+
+Not covered (IVLP and PromptSRC train through ``promptsrcfit``): ``nn.DataParallel`` itself in one process, the ResNet towers, class-token positions other
 than ``end``.
 """
 from __future__ import annotations
@@ -50,7 +54,7 @@ import torch
 from . import _lib, fitloop, fitmonitor, ops
 from ._lib import _DT, check, lib
 from . import coopfit, vptfit
-from .coopfit import DYNAMIC, _check_grad_scale, _is_dynamic
+from .coopfit import DYNAMIC, Shard, _check_grad_scale, _is_dynamic
 
 # 2^10, one power of two for both towers' backwards, measured at ViT-B/16 with synthetic weights, n_ctx 2, depth 9, batch 4, 100 classes
 # (profiles/maplefit_parity.txt, "grad_scale"): the text tower's dgrad-GEMM operands reach 1413 there (2^5.5 of headroom below fp16's
@@ -238,17 +242,25 @@ class _Towers(_TwoTowers):
 
 def gradients(model, learner_params: Dict[str, torch.Tensor], images: torch.Tensor, labels, tokenized_prompts, logit_scale: float = 4.6052,
               grad_scale: float = DEFAULT_GRAD_SCALE, seq_rows: Optional[int] = None, return_operand_stats: bool = False,
-              class_token_position: str = "end"):
+              class_token_position: str = "end", shard: Optional[Shard] = None):
     """``(loss, grads)`` of ``F.cross_entropy(exp(logit_scale) * normalise(image features) @ normalise(text features).T, labels)`` with
     respect to every prompt-learner parameter, on the GPU: loss fp32 [1], grads a dict of fp32 tensors under ``learner_params``' names.
     ``images`` [B, 3, R, R] preprocessed, ``tokenized_prompts`` [C, context_length] the ids of ``"X .. X name."``; ``seq_rows`` as
     ``coopfit.context_gradient`` takes it.  ``return_operand_stats`` adds ``{"text": {...}, "vision": {...}}``: per tower, over every
     fp16 dgrad-GEMM operand element, ``elements``, ``zeros``, ``subnormals``, ``max`` -- the measurement behind the default
-    ``grad_scale``.  A diagnostic entry point: every call allocates both towers' workspaces and stashes."""
+    ``grad_scale``.  A diagnostic entry point: every call allocates both towers' workspaces and stashes.
+    ``shard``: the loss and the gradients the batch-sharded step would apply, reduced over the ranks in rank order -- the same bits on
+    every rank; every rank passes the whole batch, and the operand statistics (per rank) are refused."""
     who = "maplefit.gradients"
     if _is_dynamic(who, grad_scale):
         raise ValueError(f"{who}: grad_scale={DYNAMIC!r} belongs to a fit (MaPLeFitState, fit_prompt_learner); one gradient needs a number")
     gs = _check_grad_scale(who, grad_scale)
+    if shard is not None:
+        vptfit.check_shard(who, shard, return_operand_stats=return_operand_stats)
+        state = coopfit.shard_states(lambda sh: MaPLeFitState(model, tokenized_prompts, learner_params, logit_scale, 0.0, 0.0, False, 0.0, gs, seq_rows,
+                                                              class_token_position, shard=sh), shard)
+        losses, grad = state._shard_gradient(who, images, labels)
+        return losses[:1], {k: v.clone() for k, v in state.params(grad).items()}
     scale = fitloop.exp_logit_scale(who, logit_scale)
     tw = _Towers(who, model, tokenized_prompts, learner_params, seq_rows, class_token_position)
     images = tw.vision.images(who, images)
@@ -287,13 +299,13 @@ class MaPLeFitState(vptfit._BlockFitState):
     def __init__(self, model, tokenized_prompts, learner_params: Dict[str, torch.Tensor], logit_scale: float = 4.6052,
                  momentum: float = 0.9, dampening: float = 0.0, nesterov: bool = False, weight_decay: float = 5e-4,
                  grad_scale: float = DEFAULT_GRAD_SCALE, seq_rows: Optional[int] = None, class_token_position: str = "end", scaler: Optional[dict] = None,
-                 optimizer: str = "sgd", betas=(0.9, 0.999), eps: float = 1e-8):
+                 optimizer: str = "sgd", betas=(0.9, 0.999), eps: float = 1e-8, shard: Optional[Shard] = None):
         who = "MaPLeFitState"
-        self._init_optimiser(who, logit_scale, momentum, dampening, nesterov, weight_decay, grad_scale, scaler, optimizer, betas, eps)
+        self._init_optimiser(who, logit_scale, momentum, dampening, nesterov, weight_decay, grad_scale, scaler, optimizer, betas, eps, shard)
         self.towers = _Towers(who, model, tokenized_prompts, learner_params, seq_rows, class_token_position)
         self.C = self.towers.C
         self._init_block(pack_block(learner_params, self.towers.depth, model.device))
-        self._scaled_grad = torch.empty_like(self.block) if self._defer else None    # scale * gradient, as clipmi_maple_step leaves it
+        self._scaled_grad = self._grad_block()    # scale * gradient, as clipmi_maple_step leaves it (under shard: the send block's front)
 
     def params(self, block: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
         t = self.towers
@@ -306,6 +318,7 @@ class MaPLeFitState(vptfit._BlockFitState):
         on the GPU with None -- run through the image tower's training forward at the coupled prompts, chunk by chunk
         (``VPTFitState.validate`` has the rest: row results, finish, selection of the whole block, labels)."""
         who = "MaPLeFitState.validate"
+        self._no_shard_validate(who)
         mon, tw = self._monitor_for(epoch), self.towers
         vis = tw.image_prompts(self.block)
         text_n = ops.l2_normalize(tw.text_forward(self.block))
@@ -363,7 +376,7 @@ def fit_prompt_learner(images_or_loader, labels, model, tokenized_prompts, learn
                        momentum: float = 0.9, dampening: float = 0.0, weight_decay: float = 5e-4, nesterov: bool = False, grad_scale: float = DEFAULT_GRAD_SCALE,
                        seq_rows: Optional[int] = None, lr_per_epoch: Optional[Sequence[float]] = None, drop_last: bool = False,
                        return_history: bool = False, class_token_position: str = "end", scaler: Optional[dict] = None, optimizer: str = "sgd", betas=(0.9, 0.999), eps: float = 1e-8,
-                       val=None, val_batch_size: int = 32, val_bins: int = 10, final_model: str = "last_step", val_criterion: str = "accuracy",
+                       shard: Optional[Shard] = None, val=None, val_batch_size: int = 32, val_bins: int = 10, final_model: str = "last_step", val_criterion: str = "accuracy",
                        return_monitor: bool = False):
     """Train MaPLe's prompt learner starting from ``learner_params`` (not modified; None = ``init_learner_params(model, n_ctx, depth)``):
     ``epochs`` passes of ``torch.optim.SGD(lr, momentum, dampening, weight_decay, nesterov)`` over the whole parameter list.
@@ -382,8 +395,14 @@ def fit_prompt_learner(images_or_loader, labels, model, tokenized_prompts, learn
 
     ``optimizer``, ``betas``, ``eps``: "sgd" (the default; ``momentum``, ``dampening``, ``nesterov``), "adam" or
     "adamw", as ``coopfit.fit_context`` takes them; ``weight_decay`` keeps this fit's default of 5e-4 under all three (torch's AdamW
-    default of 1e-2 is NOT taken over).  DESIGN.md "Adam steps for the prompt fits"."""
+    default of 1e-2 is NOT taken over).  DESIGN.md "Adam steps for the prompt fits".
+
+    ``shard=coopfit.Shard(world, rank, gather)``: the batch-sharded fit as ``vptfit.fit_prompts`` takes it (DESIGN.md "Batch-sharded
+    image-tower fits"; the reference's ``nn.DataParallel``, maple.py:273-277).  Only the image batch is sharded: the text tower runs
+    over all C prompts on every rank."""
     who = "fit_prompt_learner"
+    if shard is not None:
+        vptfit.check_shard(who, shard, val=val, final_model=final_model)
     fitmonitor.check_image_args(who, val, val_batch_size, val_bins, final_model, val_criterion)
     epochs = int(epochs)
     if epochs < 0:
@@ -392,8 +411,9 @@ def fit_prompt_learner(images_or_loader, labels, model, tokenized_prompts, learn
         fitloop.check_optimizer(who, optimizer, momentum, dampening, nesterov, weight_decay, betas, eps)
     if learner_params is None:
         learner_params = init_learner_params(model, n_ctx, depth)
-    state = MaPLeFitState(model, tokenized_prompts, learner_params, logit_scale, momentum, dampening, nesterov, weight_decay, grad_scale, seq_rows,
-                          class_token_position, scaler, optimizer, betas, eps)
+    vptfit.check_shard_batches(who, shard, images_or_loader, batch_size, drop_last)
+    state = coopfit.shard_states(lambda sh: MaPLeFitState(model, tokenized_prompts, learner_params, logit_scale, momentum, dampening, nesterov, weight_decay,
+                                                          grad_scale, seq_rows, class_token_position, scaler, optimizer, betas, eps, sh), shard)
     batches = fitloop.cut_batches(who, images_or_loader, labels, state.C, batch_size, drop_last, model.device)
     _, lr_steps = fitloop.schedule(who, lr, epochs, lr_per_epoch, len(batches), model.device)
     end_epoch = None

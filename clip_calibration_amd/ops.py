@@ -1833,6 +1833,59 @@ def shard_prograd_apply(dots_ranks: torch.Tensor, lam: float, workspace: torch.T
     return (grad, proj, dots) if want_report else None
 
 
+# ---- the batch-sharded fits through the image tower (csrc/shard_train.hip, DESIGN.md "Batch-sharded image-tower fits")
+
+def _gathered_rows(who: str, gathered, total) -> Tuple[int, int, int]:
+    """``(G, stride, total)`` of gathered blocks fp32 [G, >= total] on the GPU: rows of unit element stride, ``stride(0)`` floats apart (a
+    column range of a wider receive block is taken where it lies)."""
+    if not (isinstance(gathered, torch.Tensor) and gathered.is_cuda and gathered.dtype == torch.float32 and gathered.dim() == 2
+            and gathered.shape[0] >= 1 and gathered.shape[1] >= 1 and (gathered.stride(1) == 1 or gathered.shape[1] == 1)):
+        raise TypeError(f"{who}: gathered must be an fp32 [G >= 1, >= total] tensor on the GPU whose rows have unit element stride")
+    if gathered.device.index != torch.cuda.current_device():
+        raise RuntimeError(f"clipmi: `gathered` is on {gathered.device} but the current device is cuda:{torch.cuda.current_device()}")
+    if isinstance(total, bool) or int(total) != total or not 1 <= int(total) <= gathered.shape[1]:
+        raise ValueError(f"{who}: total={total} must be an integer in [1, {gathered.shape[1]}] (gathered {tuple(gathered.shape)})")
+    G, stride = gathered.shape[0], gathered.stride(0) if gathered.shape[0] > 1 else gathered.shape[1]
+    if stride < int(total):
+        raise ValueError(f"{who}: the rows of gathered lie {stride} floats apart, fewer than total={total}")
+    return G, stride, int(total)
+
+
+def block_rank_mean(gathered: torch.Tensor, total: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """clipmi_block_rank_mean: the rank-ordered mean fp32 [total] of the first ``total`` floats of every row of ``gathered`` fp32
+    [G, >= total] (rank r's block in row r; the floats of a row behind ``total`` are never read):
+    ``(((p_0 + p_1) + p_2) + ..) * float32(1 / G)``, the same bits on every run; an inf or a NaN stays one; with G = 1 the row itself.
+    ``out``: a contiguous fp32 tensor of ``total`` elements that does not overlap ``gathered``.  One launch."""
+    who = "block_rank_mean"
+    G, stride, total = _gathered_rows(who, gathered, total)
+    if out is None:
+        out = torch.empty(total, dtype=torch.float32, device=gathered.device)
+    else:
+        _in_place(out, torch.float32, f"{who}: out must be a contiguous fp32 tensor of {total} elements on the GPU", numel=total)
+    check(lib.clipmi_block_rank_mean(gathered.data_ptr(), G, stride, total, out.data_ptr(), _stream()), "clipmi_block_rank_mean")
+    return out
+
+
+def block_step_gathered(gathered: torch.Tensor, total: int, grad_scale: float, params: Optional[torch.Tensor] = None, buf: Optional[torch.Tensor] = None,
+                        lr: Optional[torch.Tensor] = None, first_step: bool = False, momentum: float = 0.0, dampening: float = 0.0,
+                        weight_decay: float = 0.0, nesterov: bool = False, want_grad: bool = True) -> Optional[torch.Tensor]:
+    """clipmi_block_step_gathered: ``block_rank_mean`` of ``gathered`` (rank r's ``grad_scale`` * gradient in row r), divided by
+    ``grad_scale``, and with ``params`` (fp32, ``total`` elements) torch.optim.SGD's step on it in place -- one launch.  Returns the
+    gradient fp32 [total] when ``want_grad``."""
+    who = "block_step_gathered"
+    G, stride, total = _gathered_rows(who, gathered, total)
+    if params is None and not want_grad:
+        raise ValueError(f"{who}: nothing to do (no params and no gradient wanted)")
+    if params is not None and params.numel() != total:
+        raise ValueError(f"{who}: params {tuple(params.shape)} must hold total={total} elements")
+    pp, pb, pl = _step_targets(who, () if params is None else params.shape, params, buf, lr)
+    grad = torch.empty(total, dtype=torch.float32, device=gathered.device) if want_grad else None
+    check(lib.clipmi_block_step_gathered(gathered.data_ptr(), G, stride, total, float(grad_scale), pp, pb, None if grad is None else grad.data_ptr(), pl,
+                                         int(bool(first_step)), float(momentum), float(dampening), float(weight_decay), int(bool(nesterov)), _stream()),
+          "clipmi_block_step_gathered")
+    return grad
+
+
 PROMPT_POSITIONS = {"front": 0, "middle": 1, "end": 2}   # `position` of clipmi_prompt_place and clipmi_proda_embed's pos (plain integers there)
 
 

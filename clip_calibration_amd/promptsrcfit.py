@@ -40,7 +40,11 @@ up to 640 rows with the library option ``vision_train_long`` at 1 (``vptfit.max_
 patches of 14 pixels are served by the image tower's training forward (the patchify + GEMM route of ``vptfit``'s docstring) as they are
 by the frozen plain tower's ``clipmi_encode_image``, so with the option on that configuration's own towers train here.
 
-Not covered: ``nn.DataParallel``, the ResNet towers, class-token positions other than ``end``.
+``shard=coopfit.Shard(world, rank, gather)`` on ``PromptSRCFitState``, ``fit_prompts`` and ``gradients`` (both methods): the
+batch-sharded fit of ``vptfit``'s docstring (the reference's ``nn.DataParallel``, promptsrc.py:278); only the image batch is sharded,
+the text tower runs over all C prompts on every rank and every rank keeps GPA's sum.  DESIGN.md "Batch-sharded image-tower fits".
+
+Not covered: ``nn.DataParallel`` itself in one process, the ResNet towers, class-token positions other than ``end``.
 """
 from __future__ import annotations
 
@@ -53,7 +57,7 @@ import torch
 from . import _lib, fitloop, fitmonitor, ops
 from ._lib import _DT, check, lib
 from . import coopfit, maplefit, vptfit
-from .coopfit import DYNAMIC, _check_grad_scale, _is_dynamic
+from .coopfit import DYNAMIC, Shard, _check_grad_scale, _is_dynamic
 from .fitloop import _need_gpu
 
 # 2^10, one power of two for both towers' backwards, measured at ViT-B/16 with synthetic weights, nt = nv = 4, depths 9 / 9, batch 4, 100
@@ -277,18 +281,29 @@ def _method_weights(who: str, method: str, w_text: float, w_image: float, w_logi
 
 def gradients(model, params: Dict[str, torch.Tensor], images: torch.Tensor, labels, tokenized_prompts, teacher: torch.Tensor, logit_scale: float = 4.6052,
               w_text: float = 25.0, w_image: float = 10.0, w_logit: float = 1.0, grad_scale: float = DEFAULT_GRAD_SCALE, seq_rows: Optional[int] = None,
-              return_operand_stats: bool = False, return_features: bool = False, method: str = "promptsrc", class_token_position: str = "end"):
+              return_operand_stats: bool = False, return_features: bool = False, method: str = "promptsrc", class_token_position: str = "end",
+              shard: Optional[Shard] = None):
     """``(losses, grads)`` of PromptSRC's loss on one batch with respect to every prompt parameter, on the GPU: losses fp32 [5] (total, CE,
     text L1, image L1, logit KL; the last three unweighted), grads a dict of fp32 tensors under ``params``' names.  ``images`` [B, 3, R, R]
     preprocessed, ``tokenized_prompts`` [C, context_length] the ids of ``"X .. X name."``, ``teacher`` [C, E] the frozen text features;
     ``seq_rows`` as ``coopfit.context_gradient`` takes it.  ``return_operand_stats`` adds ``{"text": {...}, "vision": {...}}`` as
     ``maplefit.gradients`` does; ``return_features`` adds ``{"text", "feats", "zs"}``, the raw features the head was given.  A diagnostic
-    entry point: every call allocates both towers' workspaces and stashes."""
+    entry point: every call allocates both towers' workspaces and stashes.
+    ``shard``: the five losses and the gradients the batch-sharded step would apply, reduced over the ranks in rank order -- the same bits
+    on every rank; every rank passes the whole batch; the operand statistics and the features (per rank) are refused."""
     who = "promptsrcfit.gradients"
     if _is_dynamic(who, grad_scale):
         raise ValueError(f"{who}: grad_scale={DYNAMIC!r} belongs to a fit (PromptSRCFitState, fit_prompts); one gradient needs a number")
     gs = _check_grad_scale(who, grad_scale)
     wt, wi, wl = _method_weights(who, method, w_text, w_image, w_logit)
+    if shard is not None:
+        vptfit.check_shard(who, shard, return_operand_stats=return_operand_stats)
+        if return_features:
+            raise ValueError(f"{who}: shard returns no features (return_features=True): they are per rank")
+        state = coopfit.shard_states(lambda sh: PromptSRCFitState(model, tokenized_prompts, params, teacher, logit_scale, w_text, w_image, w_logit, 0.0, 0.0,
+                                                                  False, 0.0, gs, seq_rows, method, class_token_position, shard=sh), shard)
+        losses, grad = state._shard_gradient(who, images, labels)
+        return losses, {k: v.clone() for k, v in state.params(grad).items()}
     scale = fitloop.exp_logit_scale(who, logit_scale)
     tw = _Towers(who, model, tokenized_prompts, params, seq_rows, class_token_position)
     teacher = _check_teacher(who, model, teacher, tw.C)
@@ -322,9 +337,9 @@ class PromptSRCFitState(vptfit._BlockFitState):
                  w_text: float = 25.0, w_image: float = 10.0, w_logit: float = 1.0, momentum: float = 0.9, dampening: float = 0.0,
                  nesterov: bool = False, weight_decay: float = 5e-4, grad_scale: float = DEFAULT_GRAD_SCALE, seq_rows: Optional[int] = None,
                  method: str = "promptsrc", class_token_position: str = "end", scaler: Optional[dict] = None, optimizer: str = "sgd", betas=(0.9, 0.999),
-                 eps: float = 1e-8):
+                 eps: float = 1e-8, shard: Optional[Shard] = None):
         who = "PromptSRCFitState"
-        self._init_optimiser(who, logit_scale, momentum, dampening, nesterov, weight_decay, grad_scale, scaler, optimizer, betas, eps)
+        self._init_optimiser(who, logit_scale, momentum, dampening, nesterov, weight_decay, grad_scale, scaler, optimizer, betas, eps, shard)
         self.weights = _method_weights(who, method, w_text, w_image, w_logit)
         self.towers = _Towers(who, model, tokenized_prompts, params, seq_rows, class_token_position)
         self.C = self.towers.C
@@ -332,7 +347,7 @@ class PromptSRCFitState(vptfit._BlockFitState):
         self._init_block(pack_block(params, model.device))
         self.gpa = None
         self.epochs_seen = 0
-        self._scaled_grad = torch.empty_like(self.block) if self._defer else None    # scale * gradient, as clipmi_promptsrc_step leaves it
+        self._scaled_grad = self._grad_block()    # scale * gradient, as clipmi_promptsrc_step leaves it (under shard: the send block's front)
 
     def params(self, block: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
         return unpack_block(self.block if block is None else block, *self.towers.shape())
@@ -345,6 +360,7 @@ class PromptSRCFitState(vptfit._BlockFitState):
         rest: row results, finish, selection of the whole block, labels).  The frozen tower and the teacher take no part: validation
         scores the prompted model's logits.  After ``apply_gpa`` the block is the aggregate, and that is what is scored."""
         who = "PromptSRCFitState.validate"
+        self._no_shard_validate(who)
         mon, tw = self._monitor_for(epoch), self.towers
         text_n = ops.l2_normalize(tw.text_forward(self.block))
         mon.validate(who, tw.vision, tw.image_prompts(self.block), text_n, self.scale, val_images_or_loader, val_labels, epoch, val_batch_size,
@@ -385,16 +401,20 @@ class PromptSRCFitState(vptfit._BlockFitState):
         return grad
 
     def end_epoch(self, weight: float) -> None:
-        """GPA: add ``weight`` times the block as it stands to the running sum (one launch; the first call initialises the sum)."""
-        if self.gpa is None:
-            self.gpa = torch.empty_like(self.block)
-        gpa_accumulate(self.block, self.gpa, weight, self.epochs_seen == 0)
-        self.epochs_seen += 1
+        """GPA: add ``weight`` times the block as it stands to the running sum (one launch; the first call initialises the sum).  Under
+        ``shard`` every rank keeps its own sum of the same bits; with a ``LocalGather`` this call serves all the world's states, as
+        ``step`` does."""
+        for s in self._world("PromptSRCFitState.end_epoch"):
+            if s.gpa is None:
+                s.gpa = torch.empty_like(s.block)
+            gpa_accumulate(s.block, s.gpa, weight, s.epochs_seen == 0)
+            s.epochs_seen += 1
 
     def apply_gpa(self) -> None:
         """The running sum replaces the parameters (after the last epoch)."""
-        if self.gpa is not None:
-            self.block.copy_(self.gpa)
+        for s in self._world("PromptSRCFitState.apply_gpa"):
+            if s.gpa is not None:
+                s.block.copy_(s.gpa)
 
 
 def _gpa_for(who: str, gpa, epochs: int) -> Optional[np.ndarray]:
@@ -423,7 +443,7 @@ def fit_prompts(images_or_loader, labels, model, tokenized_prompts, teacher: tor
                 w_logit: float = 1.0, gpa=(30.0, 30.0), grad_scale: float = DEFAULT_GRAD_SCALE, seq_rows: Optional[int] = None,
                 lr_per_epoch: Optional[Sequence[float]] = None, drop_last: bool = False, return_history: bool = False, one_call: bool = False,
                 class_token_position: str = "end", scaler: Optional[dict] = None, optimizer: str = "sgd", betas=(0.9, 0.999), eps: float = 1e-8,
-                val=None, val_batch_size: int = 32, val_bins: int = 10, final_model: str = "last_step", val_criterion: str = "accuracy",
+                shard: Optional[Shard] = None, val=None, val_batch_size: int = 32, val_bins: int = 10, final_model: str = "last_step", val_criterion: str = "accuracy",
                 return_monitor: bool = False):
     """Train the prompts starting from ``params`` (not modified; None = ``init_params(model)``): ``epochs`` passes of
     ``torch.optim.SGD(lr, momentum, dampening, weight_decay, nesterov)`` over the whole parameter list on PromptSRC's loss.
@@ -446,8 +466,14 @@ def fit_prompts(images_or_loader, labels, model, tokenized_prompts, teacher: tor
 
     ``optimizer``, ``betas``, ``eps``: "sgd" (the default; ``momentum``, ``dampening``, ``nesterov``), "adam" or
     "adamw", as ``coopfit.fit_context`` takes them; ``weight_decay`` keeps this fit's default of 5e-4 under all three (torch's AdamW
-    default of 1e-2 is NOT taken over).  ``one_call=True`` with an Adam optimiser is refused.  DESIGN.md "Adam steps for the prompt fits"."""
+    default of 1e-2 is NOT taken over).  ``one_call=True`` with an Adam optimiser is refused.  DESIGN.md "Adam steps for the prompt fits".
+
+    ``shard=coopfit.Shard(world, rank, gather)``: the batch-sharded fit as ``vptfit.fit_prompts`` takes it (DESIGN.md "Batch-sharded
+    image-tower fits"; the reference's ``nn.DataParallel``, promptsrc.py:278), both methods.  Only the image batch is sharded: the text
+    tower runs over all C prompts on every rank, and every rank keeps GPA's sum.  ``one_call=True`` is refused as well."""
     who = "fit_prompts"
+    if shard is not None:
+        vptfit.check_shard(who, shard, one_call=one_call, val=val, final_model=final_model)
     fitmonitor.check_image_args(who, val, val_batch_size, val_bins, final_model, val_criterion)
     epochs = int(epochs)
     if epochs < 0:
@@ -458,8 +484,10 @@ def fit_prompts(images_or_loader, labels, model, tokenized_prompts, teacher: tor
         fitloop.check_optimizer(who, optimizer, momentum, dampening, nesterov, weight_decay, betas, eps, one_call=one_call)
     if params is None:
         params = init_params(model)
-    state = PromptSRCFitState(model, tokenized_prompts, params, teacher, logit_scale, w_text, w_image, w_logit, momentum, dampening, nesterov, weight_decay,
-                              grad_scale, seq_rows, method, class_token_position, scaler, optimizer, betas, eps)
+    vptfit.check_shard_batches(who, shard, images_or_loader, batch_size, drop_last)
+    state = coopfit.shard_states(lambda sh: PromptSRCFitState(model, tokenized_prompts, params, teacher, logit_scale, w_text, w_image, w_logit, momentum,
+                                                              dampening, nesterov, weight_decay, grad_scale, seq_rows, method, class_token_position, scaler,
+                                                              optimizer, betas, eps, sh), shard)
     weights = None if method == "ivlp" else _gpa_for(who, gpa, epochs)
 
     batches = fitloop.cut_batches(who, images_or_loader, labels, state.C, batch_size, drop_last, model.device)

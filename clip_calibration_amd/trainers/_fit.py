@@ -32,6 +32,17 @@ def cached_features(who: str, clip_model, loader):
     return torch.cat(feats), torch.cat(labels)
 
 
+def batch_shard(who: str, fit_args: dict):
+    """``fit_args``' ``shard`` (or None) after the refusals of the batch-sharded image-tower fits (``vptfit.check_shard``), validation by
+    ``val_loader=`` included: called in front of ``validation_set``, before either tower runs."""
+    shard = fit_args.get("shard")
+    if shard is not None:
+        from ..vptfit import check_shard
+        val = fit_args.get("val_loader") if fit_args.get("val_loader") is not None else fit_args.get("val")
+        check_shard(who, shard, bool(fit_args.get("one_call", False)), val, fit_args.get("final_model", "last_step"))
+    return shard
+
+
 def validation_set(who: str, clip_model, fit_args: dict) -> None:
     """``fit_args``' ``val_loader`` turned into ``fit_args["val"]``; ``val_loader`` together with ``val`` is refused.  With a
     ``clip_model`` the loader is an iterable of (preprocessed image, label) batches, run through the frozen image tower once, and ``val`` is

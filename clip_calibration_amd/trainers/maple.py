@@ -96,6 +96,7 @@ class CustomCLIP(_CoOpCLIP):
         ``final_model="best_val"`` installs the best epoch's parameters."""
         import math
         from .. import maplefit
+        shard = _fit.batch_shard("fit_prompt_learner", fit_args)
         _fit.validation_set("fit_prompt_learner", None, fit_args)
         fit_args.setdefault("logit_scale", math.log(self.scale))
         fit_args.setdefault("class_token_position", getattr(self.prompt_learner, "class_token_position", "end"))
@@ -104,7 +105,8 @@ class CustomCLIP(_CoOpCLIP):
             from ..augment import fit_with_transform
             run, epochs, lr = _fit.split_fit_args(fit_args, 5, 0.0035)
             watch = _fit.split_monitor_args("fit_prompt_learner", fit_args)
-            state = maplefit.MaPLeFitState(self.clip_model, ids, params, **fit_args)
+            from ..coopfit import shard_states
+            state = shard_states(lambda sh: maplefit.MaPLeFitState(self.clip_model, ids, params, **dict(fit_args, shard=sh)), shard)
             end, monitored = _fit.image_end_epoch(state, watch, epochs, len(train_loader))
             losses = fit_with_transform(state, lambda x: x, ids.shape[0], train_loader, transform, epochs, lr, end_epoch=end, **run)
             best = monitored and watch["final_model"] == "best_val"

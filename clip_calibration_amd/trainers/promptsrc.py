@@ -83,6 +83,7 @@ class CustomCLIP(_CoOpCLIP):
         the best epoch's parameters."""
         import math
         from .. import promptsrcfit
+        shard = _fit.batch_shard("fit_prompts", fit_args)
         _fit.validation_set("fit_prompts", None, fit_args)
         fit_args.setdefault("logit_scale", math.log(self.scale))
         fit_args.setdefault("class_token_position", getattr(self.prompt_learner, "class_token_position", "end"))
@@ -97,7 +98,9 @@ class CustomCLIP(_CoOpCLIP):
             epochs = int(epochs)
             gpa = fit_args.pop("gpa", (30.0, 30.0))
             watch = _fit.split_monitor_args("fit_prompts", fit_args)
-            state = promptsrcfit.PromptSRCFitState(self.clip_model, ids, params, teacher_text_features, **fit_args)
+            from ..coopfit import shard_states
+            state = shard_states(lambda sh: promptsrcfit.PromptSRCFitState(self.clip_model, ids, params, teacher_text_features, **dict(fit_args, shard=sh)),
+                                 shard)
             weights = None if fit_args.get("method", "promptsrc") == "ivlp" else promptsrcfit._gpa_for("fit_prompts", gpa, epochs)
 
             def aggregate(e: int) -> None:

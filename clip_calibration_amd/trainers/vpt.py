@@ -45,14 +45,16 @@ class CustomCLIP(ZeroshotCLIP):
         ``final_model="best_val"`` installs the best epoch's prompts into the parameters."""
         import math
         from .. import vptfit
+        shard = _fit.batch_shard("fit_prompts", fit_args)
         _fit.validation_set("fit_prompts", None, fit_args)
         fit_args.setdefault("logit_scale", math.log(self.scale))
         text = self.text_features.float()
         if transform is not None:
             from ..augment import fit_with_transform
+            from ..coopfit import shard_states
             run, epochs, lr = _fit.split_fit_args(fit_args, 5, 0.0025)
             watch = _fit.split_monitor_args("fit_prompts", fit_args)
-            state = vptfit.VPTFitState(self.clip_model, text, **fit_args)
+            state = shard_states(lambda sh: vptfit.VPTFitState(self.clip_model, text, **dict(fit_args, shard=sh)), shard)
             end, monitored = _fit.image_end_epoch(state, watch, epochs, len(train_loader))
             losses = fit_with_transform(state, lambda x: x, text.shape[0], train_loader, transform, epochs, lr, end_epoch=end, **run)
             best = monitored and watch["final_model"] == "best_val"

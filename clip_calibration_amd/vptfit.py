@@ -35,8 +35,16 @@ pixels through the im2col-free loader, every other size -- ViT-L/14's and ViT-L/
 patchify + GEMM route, whose im2col matrix takes the place of the fp16 image copy in the workspace (``stash_bytes`` reports it).  With
 the option on, real ViT-L/14 towers train here, in ``maplefit`` and in ``promptsrcfit``, monitored validation included.
 
-Not covered (MaPLe trains through ``maplefit`` and PromptSRC / IVLP through ``promptsrcfit``, on this tower): ``nn.DataParallel``, the
-ResNet towers.
+``shard=coopfit.Shard(world, rank, gather)`` on ``VPTFitState``, ``fit_prompts`` and ``prompt_gradient``: the batch-sharded fit, this
+project's form of the reference's ``nn.DataParallel`` (vpt.py:171), shared with ``maplefit`` and ``promptsrcfit`` through
+``_BlockFitState``.  One process per GPU; every rank is given the whole batch and runs the tower over its own B / G rows; one all-gather
+moves the ranks' blocks ``[scale * gradient | losses]``, clipmi_block_rank_mean (csrc/shard_train.hip) forms their rank-ordered mean and
+the unsharded route's step applies it, so every rank ends a step with the same bits; with ``world == 1`` they are the unsharded bits.
+All three optimisers and both loss scales.  Refused, each by name: a batch that is no multiple of ``world``, ``one_call=True``,
+``val=`` / ``final_model="best_val"`` / ``validate``, ``return_operand_stats``.  DESIGN.md "Batch-sharded image-tower fits".
+
+Not covered (MaPLe trains through ``maplefit`` and PromptSRC / IVLP through ``promptsrcfit``, on this tower): ``nn.DataParallel`` itself
+in one process (``shard=`` stands in for it), the ResNet towers.
 """
 from __future__ import annotations
 
@@ -45,9 +53,9 @@ from typing import Optional, Sequence
 
 import torch
 
-from . import _lib, fitloop, fitmonitor, ops
+from . import _lib, coopfit, fitloop, fitmonitor, ops
 from ._lib import _DT, check, lib
-from .coopfit import DYNAMIC, _AdamBlock, _BlockScaler, _pack_dgrad, _check_grad_scale, _is_dynamic, _scale_args, operand_stats_dict
+from .coopfit import DYNAMIC, Shard, _AdamBlock, _BlockScaler, _pack_dgrad, _check_grad_scale, _is_dynamic, _scale_args, operand_stats_dict
 from .fitloop import _need_gpu
 
 # 2^12: CoOp's value (profiles/coopfit_parity.txt) holds for the image tower's backward at the ViT-B/16 geometry as well
@@ -245,17 +253,29 @@ def vpt_step(d_prompts: torch.Tensor, grad_scale: float, prompts: Optional[torch
 
 
 def prompt_gradient(model, prompts: torch.Tensor, images: torch.Tensor, labels, text_features: torch.Tensor, logit_scale: float = 4.6052,
-                    grad_scale: float = DEFAULT_GRAD_SCALE, return_operand_stats: bool = False, flags: int = _lib.CALL_DEFAULT):
+                    grad_scale: float = DEFAULT_GRAD_SCALE, return_operand_stats: bool = False, flags: int = _lib.CALL_DEFAULT,
+                    shard: Optional[Shard] = None):
     """``(loss, grad)`` of ``F.cross_entropy(exp(logit_scale) * normalise(encode_image(images; prompts)) @ normalise(text_features).T,
     labels)`` with respect to ``prompts`` [depth, n_ctx, Dv] (slot 0: ``visual.VPT``), on the GPU: loss fp32 [1], grad fp32 of the block's
     shape.  ``return_operand_stats`` adds a dict over every fp16 dgrad-GEMM operand element: ``elements``, ``zeros``, ``subnormals``,
     ``max`` -- the measurement behind the default ``grad_scale``.  A diagnostic entry point: every call allocates a workspace and a stash
-    of its own (41.6 MB per image at ViT-B/16 with 8 prompt rows); a training loop keeps a ``VPTFitState``."""
+    of its own (41.6 MB per image at ViT-B/16 with 8 prompt rows); a training loop keeps a ``VPTFitState``.
+
+    ``shard``: the loss and the gradient the batch-sharded step would apply (module docstring), reduced over the ranks in rank order --
+    the same bits on every rank.  Every rank passes the whole batch; the operand statistics are per rank and are not returned, and the
+    forward takes the default ``flags``."""
     who = "prompt_gradient"
     depth, n_ctx = _check_prompts(who, model, prompts)
     if _is_dynamic(who, grad_scale):
         raise ValueError(f"{who}: grad_scale={DYNAMIC!r} belongs to a fit (VPTFitState, fit_prompts); one gradient needs a number")
     gs = _check_grad_scale(who, grad_scale)
+    if shard is not None:
+        check_shard(who, shard, return_operand_stats=return_operand_stats)
+        if flags != _lib.CALL_DEFAULT:
+            raise ValueError(f"{who}: shard takes the default call flags (flags={flags})")
+        state = coopfit.shard_states(lambda sh: VPTFitState(model, text_features, logit_scale, prompts, 0.0, 0.0, False, 0.0, gs, shard=sh), shard)
+        losses, grad = state._shard_gradient(who, images, labels)
+        return losses[:1], grad
     scale = fitloop.exp_logit_scale(who, logit_scale)
     text = _check_text(who, model, text_features)
     tower = _Tower(who, model, depth, n_ctx)
@@ -282,6 +302,37 @@ def image_features(model, prompts: torch.Tensor, images: torch.Tensor) -> torch.
     return tower.forward(images, fitloop.master(prompts, images.device)).clone()
 
 
+def check_shard(who: str, shard, one_call: bool = False, val=None, final_model: str = "last_step", return_operand_stats: bool = False) -> None:
+    """What the batch-sharded fits refuse (``vptfit``, ``maplefit``, ``promptsrcfit``; DESIGN.md "Batch-sharded image-tower fits"), each by
+    name, before any device call."""
+    if not isinstance(shard, Shard):
+        raise ValueError(f"{who}: shard must be a coopfit.Shard(world, rank, gather), got {type(shard).__name__}")
+    if one_call:
+        raise ValueError(f"{who}: shard has no one-call step (one_call=True); the sharded step is the separate calls around one all-gather")
+    if val is not None or final_model == "best_val":
+        raise ValueError(f"{who}: shard has no validation: val=, val_loader= and final_model='best_val' are not sharded")
+    if return_operand_stats:
+        raise ValueError(f"{who}: shard returns no operand statistics (return_operand_stats=True): they are per rank")
+
+
+def check_shard_batch(who: str, shard: Shard, B: int) -> int:
+    """The images per rank of a batch of ``B`` under ``shard``; a batch that does not split evenly is refused."""
+    if B % shard.world:
+        raise ValueError(f"{who}: a batch of B={B} images does not split over G={shard.world} ranks (B must be a multiple of G; ragged "
+                         "batches are not sharded)")
+    return B // shard.world
+
+
+def check_shard_batches(who: str, shard: Optional[Shard], images_or_loader, batch_size, drop_last: bool) -> None:
+    """``check_shard_batch`` of the batches ``fitloop.cut_batches`` will cut from a tensor of images -- the full ones and the short last
+    one --, before any device call (a loader's batches meet the check in ``step``)."""
+    if shard is None or not isinstance(images_or_loader, torch.Tensor) or int(batch_size) < 1:
+        return
+    N, bs = images_or_loader.shape[0], int(batch_size)
+    for B in ([bs] if N >= bs else []) + ([N % bs] if N % bs and not drop_last else []):
+        check_shard_batch(who, shard, B)
+
+
 class _BlockFitState(fitmonitor.ImageMonitored):
     """What the states of the fits through the image tower share (VPTFitState, maplefit.MaPLeFitState, promptsrcfit.PromptSRCFitState): one
     fp32 master block under ``_master_name``, SGD's arguments and momentum buffer, the static or dynamic loss scale and the one ``step``.
@@ -291,26 +342,47 @@ class _BlockFitState(fitmonitor.ImageMonitored):
     _n_losses = 1
 
     def _init_optimiser(self, who: str, logit_scale: float, momentum, dampening, nesterov, weight_decay: float, grad_scale, scaler,
-                        optimizer: str = "sgd", betas=(0.9, 0.999), eps: float = 1e-8) -> None:
+                        optimizer: str = "sgd", betas=(0.9, 0.999), eps: float = 1e-8, shard: Optional[Shard] = None) -> None:
         """The refusals that need no model, in the order every state has made them.  ``optimizer``: "sgd" (``momentum``, ``dampening``,
         ``nesterov``), "adam" or "adamw" (``betas``, ``eps``; ``weight_decay`` keeps the fit's own default -- torch's
-        AdamW default of 1e-2 is NOT taken over)."""
+        AdamW default of 1e-2 is NOT taken over).  ``shard``: the batch-sharded fit (``check_shard``)."""
+        self.shard = shard
+        if shard is not None:
+            check_shard(who, shard)
         self.dynamic, self.grad_scale, self.scaler = _scale_args(who, grad_scale, scaler)
         self.optimizer, momentum, dampening, nesterov, self._betas = fitloop.check_optimizer(who, optimizer, momentum, dampening, nesterov, weight_decay,
                                                                                              betas, eps)
         self._eps = eps
         self.scale = fitloop.exp_logit_scale(who, logit_scale)
         self.momentum, self.dampening, self.nesterov, self.weight_decay = momentum, dampening, nesterov, weight_decay
-        # the block's step entry forms the gradient at grad_scale = 1 and applies nothing: under the dynamic scale and under Adam
-        self._defer = self.dynamic or self.optimizer != "sgd"
+        # the block's step entry forms the gradient at grad_scale = 1 and applies nothing: under the dynamic scale, under Adam, and
+        # under ``shard``, where the block it leaves is what the rank sends
+        self._defer = self.dynamic or self.optimizer != "sgd" or shard is not None
 
     def _init_block(self, master: torch.Tensor) -> None:
-        """``master`` becomes the block the steps update; the buffer, the step count and the scaler's device block with it."""
+        """``master`` becomes the block the steps update; the buffer, the step count and the scaler's device block with it.  Under
+        ``shard`` also the step's send block [scale * gradient | losses], the receive block [G, the same] and the reduced block, made
+        once; the state files itself with a local gather."""
         setattr(self, self._master_name, master)
         self.buf = torch.zeros_like(master) if self.momentum != 0.0 else None
         self.steps = 0
         self._scaler = _BlockScaler(self.scaler, master.device) if self.dynamic else None
         self._adam = _AdamBlock(self.optimizer, self._betas, self._eps, self.weight_decay, master) if self.optimizer != "sgd" else None
+        if self.shard is not None:
+            n = master.numel() + self._n_losses
+            stride = (n + 3) // 4 * 4       # whole 16-byte vectors per rank: every row of the receive block starts on the first row's phase
+            self._send = torch.zeros(stride, dtype=torch.float32, device=master.device)
+            self._recv = torch.empty(self.shard.world, stride, dtype=torch.float32, device=master.device)
+            self._reduced = torch.empty(n, dtype=torch.float32, device=master.device)
+            coopfit._file_state(self.shard, self)
+
+    def _grad_block(self) -> Optional[torch.Tensor]:
+        """Where a deferred step entry leaves scale * gradient: the front of the send block under ``shard``, a block of the state's own
+        under the dynamic scale and under Adam, nothing on the static SGD route (the entry applies the step itself)."""
+        master = self._master()
+        if self.shard is not None:
+            return self._send[:master.numel()].view_as(master)
+        return torch.empty_like(master) if self._defer else None
 
     def _master(self) -> torch.Tensor:
         return getattr(self, self._master_name)
@@ -334,15 +406,29 @@ class _BlockFitState(fitmonitor.ImageMonitored):
         a skipped step still counts in ``steps`` and still returns its loss; whether it was applied is in ``scaler_state()``.  Under
         ``optimizer="adam" | "adamw"`` the gradient block is formed the same way -- at ``grad_scale = 1``, not applied -- and
         clipmi_block_step_adam divides it by ``grad_scale`` and applies the rule (clipmi_block_step_adam_scaled under the dynamic scale);
-        ``one_call`` is then refused: the one-call steps stay SGD."""
+        ``one_call`` is then refused: the one-call steps stay SGD.  Under ``shard`` every rank is given the WHOLE batch (B a multiple of
+        the world size) and steps on its own B / G rows, views of it; ``last_losses`` and the returned loss are the reduced ones, the
+        same bits on every rank; ``one_call`` is refused; under a ``LocalGather`` the step of one state steps them all."""
         who = f"{self._who}.step"
+        if self.shard is not None:
+            check_shard(who, self.shard, one_call)
         if one_call and self._adam is not None:
             raise ValueError(f"{who}: one_call=True with optimizer={self.optimizer!r}: the one-call steps stay SGD")
         v = self._vision()
         images = v.images(who, images)
         dev, B = images.device, images.shape[0]
+        if self.shard is not None:
+            check_shard_batch(who, self.shard, B)
         labels_d = fitloop.step_labels(who, labels, B, self.C, dev, "images")
         lr_d = ops._dev(fitloop.lr_operand(lr, dev), "lr", (torch.float32,))
+        if self.shard is not None:
+            # every rank is given the same batch; under a local gather this call steps all the world's states, one phase at a time
+            states = coopfit._world_states(self.shard, self, who)
+            coopfit._drive(self.shard, self, who)
+            coopfit._run_phases([s._shard_phases(images, labels_d, lr_d) for s in states])
+            for s in states:
+                s.steps += 1
+            return self.last_losses[:1] if want_loss else None
         first = self.steps == 0
         sgd = (float(self.momentum), float(self.dampening), float(self.weight_decay), int(bool(self.nesterov)))
         loss = torch.empty(self._n_losses, dtype=torch.float32, device=dev)
@@ -371,6 +457,60 @@ class _BlockFitState(fitmonitor.ImageMonitored):
         self.last_losses = loss
         return loss[:1] if want_loss else None
 
+    # ---- the batch-sharded step (csrc/shard_train.hip, DESIGN.md "Batch-sharded image-tower fits")
+
+    def _world(self, who: str):
+        """The states a call on this one serves: itself, or under a ``LocalGather`` all the world's."""
+        return [self] if self.shard is None else coopfit._world_states(self.shard, self, who)
+
+    def _no_shard_validate(self, who: str) -> None:
+        if self.shard is not None:
+            raise ValueError(f"{who}: shard has no validation (validate: the sharded fit scores nothing between epochs)")
+
+    def _shard_phases(self, images: torch.Tensor, labels_d: torch.Tensor, lr_d: Optional[torch.Tensor], report: Optional[dict] = None):
+        """One sharded step as phases, a ``yield`` behind the gather (``coopfit._run_phases``).  The rank's own rows of the whole batch
+        go through the unsharded step's launches up to the block's step entry, which leaves scale * gradient in the send block beside
+        the head's losses; one all-gather; the rank-ordered mean; the unsharded route's step on the block every rank agrees on.
+        ``report``: a dict that receives the reduced ``grad`` and ``losses`` INSTEAD of a step (static scale): nothing is updated."""
+        sh, master = self.shard, self._master()
+        total, n = master.numel(), images.shape[0] // sh.world
+        rows = slice(sh.rank * n, (sh.rank + 1) * n)
+        first = self.steps == 0
+        sgd = (float(self.momentum), float(self.dampening), float(self.weight_decay), int(bool(self.nesterov)))
+        outs = self._head(images[rows], labels_d[rows], 1.0 if self.dynamic else self.grad_scale, self._send[total:total + self._n_losses])
+        if self.dynamic:
+            for d_out in outs:
+                ops.grad_scale_rows(d_out, self._scaler.block)
+        self._apply(outs, None, first, sgd)
+        sh.gather(self._send, self._recv, self._send.numel() * 4, ops._stream())
+        yield
+        if report is not None:
+            report["grad"] = ops.block_step_gathered(self._recv, total, self.grad_scale).view_as(master)
+            report["losses"] = ops.block_rank_mean(self._recv[:, total:], self._n_losses)
+        elif not self.dynamic and self._adam is None:      # the mean, 1 / grad_scale and SGD's rule in one launch; the losses' mean beside it
+            ops.block_step_gathered(self._recv, total, self.grad_scale, master, self.buf, lr_d, first, *sgd, want_grad=False)
+            self.last_losses = ops.block_rank_mean(self._recv[:, total:], self._n_losses)
+        else:
+            ops.block_rank_mean(self._recv, total + self._n_losses, self._reduced)
+            grad = self._reduced[:total]
+            if self._adam is not None:
+                self._adam.step(grad, master, lr_d, 1.0 if self.dynamic else self.grad_scale, self._scaler)
+            else:
+                self._scaler.step(grad, master, self.buf, lr_d, *sgd)
+            self.last_losses = self._reduced[total:].clone()     # the reduced block is the next step's as well: the history keeps its own
+
+    def _shard_gradient(self, who: str, images: torch.Tensor, labels):
+        """``(losses fp32 [n_losses], grad of the master's shape)`` of the whole batch, reduced over the ranks: the diagnostic entry
+        points under ``shard``.  Under a local gather this call runs every rank's phases."""
+        images = self._vision().images(who, images)
+        check_shard_batch(who, self.shard, images.shape[0])
+        labels_d = fitloop.step_labels(who, labels, images.shape[0], self.C, images.device, "images")
+        states = coopfit._world_states(self.shard, self, who)
+        reports = [{} for _ in states]
+        coopfit._run_phases([s._shard_phases(images, labels_d, None, r) for s, r in zip(states, reports)])
+        report = reports[states.index(self)]
+        return report["losses"], report["grad"]
+
 
 class VPTFitState(_BlockFitState):
     """The training state of VPT's prompts: the fp32 master block ``prompts`` [depth, n_ctx, Dv] (None: the model's own parameters), SGD's
@@ -381,16 +521,19 @@ class VPTFitState(_BlockFitState):
 
     def __init__(self, model, text_features: torch.Tensor, logit_scale: float = 4.6052, prompts: Optional[torch.Tensor] = None,
                  momentum: float = 0.9, dampening: float = 0.0, nesterov: bool = False, weight_decay: float = 5e-4,
-                 grad_scale: float = DEFAULT_GRAD_SCALE, scaler: Optional[dict] = None, optimizer: str = "sgd", betas=(0.9, 0.999), eps: float = 1e-8):
+                 grad_scale: float = DEFAULT_GRAD_SCALE, scaler: Optional[dict] = None, optimizer: str = "sgd", betas=(0.9, 0.999), eps: float = 1e-8,
+                 shard: Optional[Shard] = None):
         who = "VPTFitState"
         if prompts is None:
             prompts = model_prompts(model)
         self.depth, self.n_ctx = _check_prompts(who, model, prompts)
-        self._init_optimiser(who, logit_scale, momentum, dampening, nesterov, weight_decay, grad_scale, scaler, optimizer, betas, eps)
+        self._init_optimiser(who, logit_scale, momentum, dampening, nesterov, weight_decay, grad_scale, scaler, optimizer, betas, eps, shard)
         self.text = _check_text(who, model, text_features)
         self.C = int(self.text.shape[0])
         self.tower = _Tower(who, model, self.depth, self.n_ctx)
         self._init_block(fitloop.master(prompts, model.device))
+        if shard is not None:   # the tower's backward writes the prompts' gradient straight into the send block
+            self.tower.d_prompts = self._grad_block()
         self._text_n = None     # the fixed text features, normalised by the first validate
 
     def validate(self, val_images_or_loader, val_labels, epoch: int, val_batch_size: int = 32, one_call: bool = True) -> None:
@@ -405,6 +548,7 @@ class VPTFitState(_BlockFitState):
         to ``val_batch_size`` images when that exceeds the training batch, and stays (41.6 MB per image at ViT-B/16).  Without ``start_monitor`` the
         history starts with ``epoch + 1`` slots of 10 bins and no selection."""
         who = "VPTFitState.validate"
+        self._no_shard_validate(who)
         mon = self._monitor_for(epoch)
         if self._text_n is None:
             self._text_n = ops.l2_normalize(self.text)
@@ -440,7 +584,8 @@ def fit_prompts(images_or_loader, labels, model, text_features: torch.Tensor, pr
                 lr: float = 0.0025, epochs: int = 5, batch_size: int = 32, momentum: float = 0.9, dampening: float = 0.0,
                 weight_decay: float = 5e-4, nesterov: bool = False, grad_scale: float = DEFAULT_GRAD_SCALE,
                 lr_per_epoch: Optional[Sequence[float]] = None, drop_last: bool = False, return_history: bool = False,
-                scaler: Optional[dict] = None, optimizer: str = "sgd", betas=(0.9, 0.999), eps: float = 1e-8, val=None, val_batch_size: int = 32,
+                scaler: Optional[dict] = None, optimizer: str = "sgd", betas=(0.9, 0.999), eps: float = 1e-8, shard: Optional[Shard] = None,
+                val=None, val_batch_size: int = 32,
                 val_bins: int = 10, final_model: str = "last_step", val_criterion: str = "accuracy", return_monitor: bool = False):
     """Train VPT's prompts starting from ``prompts`` (not modified; None = the model's own parameters): ``epochs`` passes of
     ``torch.optim.SGD(lr, momentum, dampening, weight_decay, nesterov)``.  ``images_or_loader`` is a tensor of preprocessed images
@@ -461,15 +606,25 @@ def fit_prompts(images_or_loader, labels, model, text_features: torch.Tensor, pr
 
     ``optimizer``, ``betas``, ``eps``: "sgd" (the default; ``momentum``, ``dampening``, ``nesterov``), "adam" or
     "adamw", as ``coopfit.fit_context`` takes them; ``weight_decay`` keeps this fit's default of 5e-4 under all three (torch's AdamW
-    default of 1e-2 is NOT taken over).  DESIGN.md "Adam steps for the prompt fits"."""
+    default of 1e-2 is NOT taken over).  DESIGN.md "Adam steps for the prompt fits".
+
+    ``shard=coopfit.Shard(world, rank, gather)``: the batch-sharded fit (DESIGN.md "Batch-sharded image-tower fits"), this project's form
+    of the reference's ``nn.DataParallel`` (vpt.py:171).  Every rank makes this call with the same arguments -- all images, whole batches
+    whose sizes are multiples of ``world`` -- runs the tower over its own rows of every batch and returns the same prompts; with a
+    ``LocalGather`` the one call runs all ``world`` states in this process.  All three optimisers and both loss scales; ``val`` and
+    ``final_model="best_val"`` are refused."""
     who = "fit_prompts"
+    if shard is not None:
+        check_shard(who, shard, val=val, final_model=final_model)
     fitmonitor.check_image_args(who, val, val_batch_size, val_bins, final_model, val_criterion)
     epochs = int(epochs)
     if epochs < 0:
         raise ValueError(f"{who}: epochs={epochs} (>= 0)")
     if optimizer != "sgd":      # by this function's name; SGD's arguments are the state's to check, as before
         fitloop.check_optimizer(who, optimizer, momentum, dampening, nesterov, weight_decay, betas, eps)
-    state = VPTFitState(model, text_features, logit_scale, prompts, momentum, dampening, nesterov, weight_decay, grad_scale, scaler, optimizer, betas, eps)
+    check_shard_batches(who, shard, images_or_loader, batch_size, drop_last)
+    state = coopfit.shard_states(lambda sh: VPTFitState(model, text_features, logit_scale, prompts, momentum, dampening, nesterov, weight_decay, grad_scale,
+                                                        scaler, optimizer, betas, eps, sh), shard)
     batches = fitloop.cut_batches(who, images_or_loader, labels, state.C, batch_size, drop_last, model.device)
     _, lr_steps = fitloop.schedule(who, lr, epochs, lr_per_epoch, len(batches), model.device)
     end_epoch = None

@@ -1235,6 +1235,25 @@ int clipmi_shard_prograd_apply(const double* dots_ranks, int G, float lambda, fl
                                double* dots, int64_t total, const float* lr, int first_step, float momentum, float dampening,
                                float weight_decay, int nesterov, void* workspace, size_t workspace_bytes, clipmi_stream_t stream);
 
+/* The batch-sharded fits through the image tower (VPT, MaPLe, PromptSRC / IVLP; DESIGN.md "Batch-sharded image-tower fits"): every rank
+ * runs the step over its own B / G images and sends one block [scale * gradient | losses]; one all-gather leaves rank r's block at
+ * gathered + r * stride (floats; stride >= total, and the floats of a row behind `total` are never read).
+ *
+ * The rank-ordered mean: out[i] = (((p_0[i] + p_1[i]) + p_2[i]) + ..) * inv with inv = (float)(1.0 / world), all in fp32, no atomics:
+ * the same bits on every rank and on every run; an inf or a NaN of any rank stays one; with world == 1 the output is the input bit for
+ * bit.  16-byte loads and stores where the row bases, the stride and the output allow, single floats elsewhere.  Refused before any
+ * launch: a null or misaligned (4 bytes) pointer, world < 1, total outside [1, 2^39), stride < total, out overlapping the gathered
+ * blocks.  One launch. */
+int clipmi_block_rank_mean(const float* gathered, int world, size_t stride, size_t total, float* out, clipmi_stream_t stream);
+
+/* The same mean, divided by grad_scale, and torch.optim.SGD's rule on params fp32 [total] in place (clipmi_ctx_step's optional outputs
+ * and NULL conventions: params NULL forms grad_out alone, buf may be NULL without a momentum): the static SGD route's step.  With
+ * world == 1 the bits are those of the fit's own step entry applied to the same scale * gradient.  params, buf and grad_out must not
+ * overlap the gathered blocks.  One launch. */
+int clipmi_block_step_gathered(const float* gathered, int world, size_t stride, size_t total, float grad_scale, float* params, float* buf,
+                               float* grad_out, const float* lr, int first_step, float momentum, float dampening, float weight_decay,
+                               int nesterov, clipmi_stream_t stream);
+
 /* One training step of CoOp, KgCoOp or ProGrad as ONE call: clipmi_text_encoder_train, clipmi_prompt_head, clipmi_text_encoder_backward
  * (twice for ProGrad, one after the other: they share the tower's workspace and read the same stash) and clipmi_ctx_step or
  * clipmi_prograd_step, enqueued in this order on `stream` -- the same launches, the same bits as the calls one by one.  losses fp32 [3]
