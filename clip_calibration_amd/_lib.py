@@ -294,6 +294,11 @@ _SIGNATURES = {
     "clipmi_proda_train_step_scaled_bytes": (_sz, [_vp, _i, _i, _i, _i, _i, _i]),
     "clipmi_proda_train_step_scaled": (_i, [_vp, C.POINTER(TextDgrad), _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i64, _vp, _i,
                                             _f, _vp, _f, _f, _i, _f, _vp, _f, _f, _f, _i, _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
+    "clipmi_proda_embed_shard": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "clipmi_proda_shard_compact": (_i, [_vp, _vp, _i, _i, _i, _i, _i64, _vp]),
+    "clipmi_proda_ctx_partial": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "clipmi_proda_ctx_step_gathered": (_i, [_vp, _i, _i64, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _i, _f, _f, _f, _i, _vp]),
+    "clipmi_proda_ctx_reduce_gathered_scaled": (_i, [_vp, _i, _i64, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _f, _f, _i, _vp, _f, _f, _f, _i, _vp, _sz, _vp]),
     "clipmi_cocoop_block_floats": (_sz, [_i, _i, _i, _i]),
     "clipmi_cocoop_meta": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "clipmi_cocoop_embed": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),

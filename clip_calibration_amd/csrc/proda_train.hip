@@ -14,6 +14,8 @@
 //   proda_ctx_step_kernel      the context's gradient (classes ascending, the no-class row last) and the SGD rule
 //   proda_scaled_grad_kernel   the same gradient under the dynamic loss scale: divided by the device scale, into the scaled step's workspace with
 //                              one found-non-finite flag per workgroup; grad_scaler.hip's decision and step launches follow it
+//   proda_shard_compact_kernel, proda_ctx_partial_kernel, proda_ctx_step_gathered_kernel, proda_gathered_scaled_grad_kernel
+//                              the class-sharded step (one process per GPU, two all-gathers): described where they stand
 // Notation: N = C Pb + P text rows; row c Pb + q is class c with the q-th selected context, row C Pb + p the no-class prompt of context p.
 // No float atomics and no workgroup waits for another: the same inputs give the same bits.
 #include <cmath>
@@ -71,21 +73,23 @@ __device__ __forceinline__ f32x4 ld4(const half_t* p) {
 //   middle  r < h: ctx[r];  r < h + nl: the name token r - h;  else ctx[r - nl]
 // and the base row l everywhere else (SOS; '.', EOT and the padding from 1 + n_ctx + nl on).  Name token t is base row 1 + n_ctx + t.
 // The EOT row of a class prompt is the class's own, cls_eot[c], whatever the position and the name length.
+// The no-class prompts written are those of the contexts p0 .. p0 + Pn - 1 (all P of them but for a rank of the class-sharded fit, which
+// owns a range); the class arrays then start at the rank's first class.
 template <typename T>
 __global__ __launch_bounds__(THREADS) void proda_embed_kernel(const T* __restrict__ base, const T* __restrict__ nc_base, const float* __restrict__ ctx,
                                                               const int32_t* __restrict__ sel, const int32_t* __restrict__ pos,
                                                               const int32_t* __restrict__ name_lens, const int32_t* __restrict__ cls_eot, float* __restrict__ out,
-                                                              int32_t* __restrict__ eot, int C, int Pb, int P, int L, int Lc, int D, int n_ctx) {
+                                                              int32_t* __restrict__ eot, int C, int Pb, int P, int p0, int Pn, int L, int Lc, int D, int n_ctx) {
   const int D4 = D / 4;
   const int64_t idx = (int64_t)blockIdx.x * THREADS + threadIdx.x;
-  const int64_t N = (int64_t)C * Pb + P;
+  const int64_t N = (int64_t)C * Pb + Pn;
   if (idx >= N * L * D4) return;
   const int d = (int)(idx % D4) * 4, l = (int)((idx / D4) % L);
   const int64_t n = idx / ((int64_t)D4 * L);
   float* dst = out + (n * Lc + l) * D + d;
   f32x4 v;
   if (n >= (int64_t)C * Pb) {                       // [SOS | ctx_p | '.' EOT pad]
-    const int p = (int)(n - (int64_t)C * Pb);
+    const int p = p0 + (int)(n - (int64_t)C * Pb);
     v = (l >= 1 && l <= n_ctx) ? ld4(ctx + ((int64_t)p * n_ctx + (l - 1)) * D + d) : ld4(nc_base + (int64_t)l * D + d);
     if (l == 0 && d == 0) eot[n] = n_ctx + 2;
   } else {
@@ -160,10 +164,11 @@ __global__ __launch_bounds__(THREADS) void proda_val_mean_kernel(const float* __
 }
 
 int check_embed(const char* who, const void* base, const void* nc_base, int dtype, const float* ctx, const int32_t* sel, const int32_t* pos,
-                const int32_t* name_lens, const int32_t* cls_eot, const float* out, const int32_t* eot, int C, int Pb, int P, int L, int Lc, int D, int n_ctx) {
+                const int32_t* name_lens, const int32_t* cls_eot, const float* out, const int32_t* eot, int C, int Pb, int P, int L, int Lc, int D, int n_ctx,
+                int min_C = 2) {
   CLIPMI_REQUIRE(base && nc_base && ctx && sel && pos && name_lens && cls_eot && out && eot, CLIPMI_ERR_ARG, "%s: null pointer", who);
   CLIPMI_REQUIRE(dtype == CLIPMI_F16 || dtype == CLIPMI_F32, CLIPMI_ERR_ARG, "%s: bad dtype %d", who, dtype);
-  CLIPMI_REQUIRE(C >= 2 && P >= 2 && Pb >= 1 && Pb <= P, CLIPMI_ERR_SHAPE, "%s: C=%d (>= 2), P=%d (>= 2), Pb=%d (1 .. P)", who, C, P, Pb);
+  CLIPMI_REQUIRE(C >= min_C && P >= 2 && Pb >= 1 && Pb <= P, CLIPMI_ERR_SHAPE, "%s: C=%d (>= %d), P=%d (>= 2), Pb=%d (1 .. P)", who, C, min_C, P, Pb);
   CLIPMI_REQUIRE(D >= 4 && D % 4 == 0 && n_ctx >= 1 && L <= Lc && n_ctx + 3 <= L, CLIPMI_ERR_SHAPE,
                  "%s: D=%d (a multiple of 4), n_ctx=%d, L=%d of Lc=%d rows (SOS, the context, '.' and EOT must fit)", who, D, n_ctx, L, Lc);
   CLIPMI_REQUIRE(((int64_t)C * Pb + P) * Lc < (1ll << 31), CLIPMI_ERR_SHAPE, "%s: too many prompt tokens", who);
@@ -174,15 +179,17 @@ int check_embed(const char* who, const void* base, const void* nc_base, int dtyp
 
 // the launch alone: the caller has passed check_embed
 int enqueue_embed(const void* base, const void* nc_base, int dtype, const float* ctx, const int32_t* sel, const int32_t* pos, const int32_t* name_lens,
-                  const int32_t* cls_eot, float* out, int32_t* eot, int C, int Pb, int P, int L, int Lc, int D, int n_ctx, hipStream_t s) {
-  const int64_t total = ((int64_t)C * Pb + P) * L * (D / 4);
+                  const int32_t* cls_eot, float* out, int32_t* eot, int C, int Pb, int P, int L, int Lc, int D, int n_ctx, hipStream_t s, int p0 = 0,
+                  int Pn = -1) {
+  if (Pn < 0) Pn = P;   // every context's no-class prompt: the unsharded step
+  const int64_t total = ((int64_t)C * Pb + Pn) * L * (D / 4);
   const dim3 grid((unsigned)((total + THREADS - 1) / THREADS)), threads(THREADS);
   if (dtype == CLIPMI_F16)
     hipLaunchKernelGGL(proda_embed_kernel<half_t>, grid, threads, 0, s, (const half_t*)base, (const half_t*)nc_base, ctx, sel, pos, name_lens, cls_eot, out,
-                       eot, C, Pb, P, L, Lc, D, n_ctx);
+                       eot, C, Pb, P, p0, Pn, L, Lc, D, n_ctx);
   else
     hipLaunchKernelGGL(proda_embed_kernel<float>, grid, threads, 0, s, (const float*)base, (const float*)nc_base, ctx, sel, pos, name_lens, cls_eot, out, eot,
-                       C, Pb, P, L, Lc, D, n_ctx);
+                       C, Pb, P, p0, Pn, L, Lc, D, n_ctx);
   return check_launch("proda_embed_kernel");
 }
 
@@ -538,12 +545,259 @@ int enqueue_ctx_step_scaled(const float* d_embed, float* ctx, float* buf, float*
   return launch_scaled_decide_apply(w, total, ctx, buf, sc, lr, momentum, dampening, weight_decay, nesterov, s);
 }
 
+// ---------------------------------------------------------------------------------- the class-sharded step (DESIGN.md "Class-sharded ProDA fit")
+// Rank r of G owns the classes the balanced split gives it (shard_owner, train_rules.h), with all Pb prompts of each, and the no-class
+// prompts of the contexts the same split of P gives it.  Its tower runs over C_r Pb + P_r prompts, the class prompts first.
+//   proda_shard_compact_kernel        the gathered text features [G, RB, E], RB = ceil(C / G) Pb + ceil(P / G) -> [C Pb + P, E] in the unsharded order
+//   proda_ctx_partial_kernel          a rank's send block: [Pb, n_ctx, D] class sums of its own classes | its own no-class rows [P_r, n_ctx, D]
+//   proda_ctx_step_gathered_kernel    the G class sums added in rank order, the owner's no-class row last, 1 / grad_scale, the SGD rule
+//   proda_gathered_scaled_grad_kernel the same sum under the dynamic loss scale, in proda_scaled_grad_kernel's shape
+// With G = 1 every chain is proda_grad_element's: 0 + the classes ascending + the no-class row.  V = 4: 16-byte accesses; V = 1: scalar.
+template <int V>
+__device__ __forceinline__ void ldv(const float* __restrict__ p, float (&x)[V]) {
+  if constexpr (V == 4) {
+    const f32x4 v = *reinterpret_cast<const f32x4*>(p);
+    x[0] = v[0]; x[1] = v[1]; x[2] = v[2]; x[3] = v[3];
+  } else {
+    x[0] = *p;
+  }
+}
+template <int V>
+__device__ __forceinline__ void stv(float* __restrict__ p, const float (&x)[V]) {
+  if constexpr (V == 4)
+    *reinterpret_cast<f32x4*>(p) = f32x4{x[0], x[1], x[2], x[3]};
+  else
+    *p = x[0];
+}
+
+// one thread per element of out [C Pb + P, E].  Block r of the gathered rows is rank r's tower output as it lies -- its C_r Pb class rows, then
+// its P_r no-class rows -- with padding behind them up to RB rows that is never read
+__global__ __launch_bounds__(THREADS) void proda_shard_compact_kernel(const float* __restrict__ gathered, float* __restrict__ out, int C, int Pb, int P, int G,
+                                                                      int RB, int64_t E) {
+  const int64_t idx = (int64_t)blockIdx.x * THREADS + threadIdx.x;
+  const int64_t n_cls = (int64_t)C * Pb;
+  if (idx >= (n_cls + P) * E) return;
+  const int64_t n = idx / E;
+  int lo, r;
+  int64_t row;
+  if (n < n_cls) {
+    const int c = (int)(n / Pb);
+    r = shard_owner(c, C, G, &lo);
+    row = (int64_t)(c - lo) * Pb + n % Pb;
+  } else {
+    const int p = (int)(n - n_cls);
+    r = shard_owner(p, P, G, &lo);
+    row = (int64_t)(C / G + (r < C % G ? 1 : 0)) * Pb + (p - lo);
+  }
+  out[idx] = gathered[((int64_t)r * RB + row) * E + idx % E];
+}
+
+// one thread per V elements of the send block [(Pb + Pn), n_ctx, D] from the rank's own d_embed [(C Pb + Pn) L, D] (C its own classes, Pn its
+// own no-class prompts; name_lens its own classes').  Slot q < Pb: the rows of the C prompts c Pb + q that hold context vector j of context
+// sel[q], c ascending from 0.f, unscaled (a selection outside [0, P) is never an index: its sums are zero and no context reads them).
+// Slot Pb + i: row 1 + j of the rank's i-th no-class prompt, copied.
+template <int V>
+__global__ __launch_bounds__(THREADS) void proda_ctx_partial_kernel(const float* __restrict__ d_embed, float* __restrict__ partial,
+                                                                    const int32_t* __restrict__ sel, const int32_t* __restrict__ pos,
+                                                                    const int32_t* __restrict__ name_lens, int C, int Pb, int P, int Pn, int L, int D, int n_ctx) {
+  const int DV = D / V;
+  const int64_t idx = (int64_t)blockIdx.x * THREADS + threadIdx.x;
+  if (idx >= (int64_t)(Pb + Pn) * n_ctx * DV) return;
+  const int d = (int)(idx % DV) * V, j = (int)((idx / DV) % n_ctx), s = (int)(idx / ((int64_t)DV * n_ctx));
+  float g[V];
+  if (s < Pb) {
+#pragma unroll
+    for (int v = 0; v < V; ++v) g[v] = 0.f;
+    const int p = sel[s];
+    if (p >= 0 && p < P) {
+      const int ps = pos[p], h = n_ctx / 2;
+      for (int64_t c = 0; c < C; ++c) {
+        const int row = ctx_row(ps, j, clamp_name_len(name_lens[c], L, n_ctx), h);
+        float x[V];
+        ldv<V>(d_embed + ((c * Pb + s) * L + row) * D + d, x);
+#pragma unroll
+        for (int v = 0; v < V; ++v) g[v] += x[v];
+      }
+    }
+  } else {
+    ldv<V>(d_embed + (((int64_t)C * Pb + (s - Pb)) * L + 1 + j) * D + d, g);
+  }
+  stv<V>(partial + ((int64_t)s * n_ctx + j) * D + d, g);
+}
+
+// V elements e .. e + V - 1 (e = j D + d) of context p's gradient from the G gathered send blocks (rank r's at gathered + r stride): if p is
+// selected at slot q the G class sums of slot q added in RANK order from 0.f; then, always and last, the no-class row of the rank that owns p
+template <int V>
+__device__ __forceinline__ void proda_gathered_elements(const float* __restrict__ gathered, int G, int64_t stride, int p, int64_t e,
+                                                        const int32_t* __restrict__ sel, int Pb, int P, int64_t nD, float inv_scale, float (&g)[V]) {
+  int slot = -1;
+  for (int q = 0; q < Pb; ++q)
+    if (sel[q] == p && slot < 0) slot = q;
+#pragma unroll
+  for (int v = 0; v < V; ++v) g[v] = 0.f;
+  float x[V];
+  if (slot >= 0) {
+    for (int r = 0; r < G; ++r) {
+      ldv<V>(gathered + (int64_t)r * stride + slot * nD + e, x);
+#pragma unroll
+      for (int v = 0; v < V; ++v) g[v] += x[v];
+    }
+  }
+  int lo;
+  const int r = shard_owner(p, P, G, &lo);
+  ldv<V>(gathered + (int64_t)r * stride + (Pb + (p - lo)) * nD + e, x);
+#pragma unroll
+  for (int v = 0; v < V; ++v) g[v] = (g[v] + x[v]) * inv_scale;
+}
+
+// one thread per V elements of ctx [P, n_ctx D]; the SGD rule on registers, ctx and buf read and written once
+template <int V>
+__global__ __launch_bounds__(THREADS) void proda_ctx_step_gathered_kernel(const float* __restrict__ gathered, int G, int64_t stride, float* __restrict__ ctx,
+                                                                          float* __restrict__ buf, float* __restrict__ grad_out,
+                                                                          const int32_t* __restrict__ sel, int Pb, int P, int64_t nD, float inv_scale,
+                                                                          const float* __restrict__ lr, SgdArgs sgd) {
+  const int64_t nV = nD / V, idx = (int64_t)blockIdx.x * THREADS + threadIdx.x;
+  if (idx >= P * nV) return;
+  const int p = (int)(idx / nV);
+  const int64_t e = (idx % nV) * V, o = p * nD + e;
+  float g[V];
+  proda_gathered_elements<V>(gathered, G, stride, p, e, sel, Pb, P, nD, inv_scale, g);
+  if (grad_out) stv<V>(grad_out + o, g);
+  if (!ctx) return;
+  const bool with_buf = sgd.momentum != 0.f;
+  float w[V], b[V];
+  ldv<V>(ctx + o, w);
+  if (with_buf) ldv<V>(buf + o, b);
+  const float rate = *lr;
+#pragma unroll
+  for (int v = 0; v < V; ++v) sgd_element_fma(w, b, v, g[v], rate, sgd);
+  stv<V>(ctx + o, w);
+  if (with_buf) stv<V>(buf + o, b);
+}
+
+// The same sum under the dynamic loss scale, one thread per element as proda_scaled_grad_kernel: times 1 / state->scale into the step's
+// workspace and into grad_out, the workgroup's flag set when any element it produced is an inf or a NaN
+__global__ __launch_bounds__(THREADS) void proda_gathered_scaled_grad_kernel(const float* __restrict__ gathered, int G, int64_t stride, float* __restrict__ grad_out,
+                                                                             const int32_t* __restrict__ sel, int Pb, int P, int64_t nD,
+                                                                             const clipmi_scaler_state* __restrict__ st, ScaledWs w) {
+  const int64_t idx = (int64_t)blockIdx.x * THREADS + threadIdx.x;
+  int bad = 0;
+  if (idx < P * nD) {
+    float g[1];
+    proda_gathered_elements<1>(gathered, G, stride, (int)(idx / nD), idx % nD, sel, Pb, P, nD, 1.f / st->scale, g);
+    w.grad[idx] = g[0];
+    if (grad_out) grad_out[idx] = g[0];
+    bad = !isfinite(g[0]);
+  }
+  bad = __syncthreads_or(bad);
+  if (threadIdx.x == 0) w.flags[blockIdx.x] = bad ? 1 : 0;
+}
+
+inline bool aligned16(const void* p) { return (uintptr_t)p % 16 == 0; }
+
+// what both gathered steps ask of the send blocks: rank r's block of (Pb + ceil(P / G)) n_ctx D floats at gathered + r rank_stride
+int check_gathered_step(const char* who, const float* gathered, int G, int64_t rank_stride, const int32_t* sel, int Pb, int P, int D, int n_ctx) {
+  CLIPMI_REQUIRE(gathered && sel, CLIPMI_ERR_ARG, "%s: null pointer (the gathered blocks and sel are required)", who);
+  CLIPMI_REQUIRE(G >= 1 && P >= 2 && P >= G && Pb >= 1 && Pb <= P && D >= 1 && n_ctx >= 1, CLIPMI_ERR_SHAPE, "%s: G=%d P=%d (>= 2, >= G) Pb=%d (1 .. P) D=%d n_ctx=%d",
+                 who, G, P, Pb, D, n_ctx);
+  CLIPMI_REQUIRE((int64_t)P * n_ctx * D < (1ll << 31), CLIPMI_ERR_SHAPE, "%s: context set too large", who);
+  const int64_t block = (int64_t)(Pb + (P + G - 1) / G) * n_ctx * D;
+  CLIPMI_REQUIRE(rank_stride >= block && rank_stride < (1ll << 40), CLIPMI_ERR_SHAPE, "%s: rank_stride=%lld below a rank's block of %lld elements", who,
+                 (long long)rank_stride, (long long)block);
+  return CLIPMI_OK;
+}
+
 }  // namespace
 }  // namespace clipmi
 
 using namespace clipmi;
 
 extern "C" {
+
+int clipmi_proda_embed_shard(const void* base, const void* nc_base, int dtype, const float* ctx, const int32_t* sel, const int32_t* pos,
+                             const int32_t* name_lens, const int32_t* cls_eot, float* prompts, int32_t* eot, int C, int Pb, int P, int p0, int Pn, int L,
+                             int Lc, int D, int n_ctx, clipmi_stream_t stream) {
+  const char* who = "proda_embed_shard";
+  if (int rc = check_embed(who, base, nc_base, dtype, ctx, sel, pos, name_lens, cls_eot, prompts, eot, C, Pb, P, L, Lc, D, n_ctx, 1)) return rc;
+  CLIPMI_REQUIRE(p0 >= 0 && Pn >= 1 && p0 <= P - Pn, CLIPMI_ERR_SHAPE, "%s: the no-class prompts [%d, %d + %d) leave the P=%d contexts", who, p0, p0, Pn, P);
+  return enqueue_embed(base, nc_base, dtype, ctx, sel, pos, name_lens, cls_eot, prompts, eot, C, Pb, P, L, Lc, D, n_ctx, (hipStream_t)stream, p0, Pn);
+}
+
+int clipmi_proda_shard_compact(const float* gathered, float* out, int C, int Pb, int P, int G, int64_t E, clipmi_stream_t stream) {
+  const char* who = "proda_shard_compact";
+  CLIPMI_REQUIRE(gathered && out, CLIPMI_ERR_ARG, "%s: null pointer", who);
+  CLIPMI_REQUIRE(G >= 1 && C >= G && P >= G && Pb >= 1 && E >= 1, CLIPMI_ERR_SHAPE, "%s: C=%d P=%d G=%d Pb=%d E=%lld (C >= G, P >= G, G >= 1)", who, C, P, G, Pb,
+                 (long long)E);
+  const int64_t RB = (int64_t)((C + G - 1) / G) * Pb + (P + G - 1) / G, rows = (int64_t)C * Pb + P;
+  CLIPMI_REQUIRE(RB < (1ll << 31) && E < (1ll << 31) && rows * E < (1ll << 31) * THREADS && G * RB * E < (1ll << 40), CLIPMI_ERR_SHAPE, "%s: too many rows", who);
+  hipLaunchKernelGGL(proda_shard_compact_kernel, dim3((unsigned)((rows * E + THREADS - 1) / THREADS)), dim3(THREADS), 0, (hipStream_t)stream, gathered, out, C,
+                     Pb, P, G, (int)RB, E);
+  return check_launch("proda_shard_compact_kernel");
+}
+
+int clipmi_proda_ctx_partial(const float* d_embed, float* partial, const int32_t* sel, const int32_t* pos, const int32_t* name_lens, int C, int Pb, int P,
+                             int Pn, int L, int D, int n_ctx, clipmi_stream_t stream) {
+  const char* who = "proda_ctx_partial";
+  CLIPMI_REQUIRE(d_embed && partial && sel && pos && name_lens, CLIPMI_ERR_ARG, "%s: null pointer", who);
+  CLIPMI_REQUIRE(C >= 1 && P >= 2 && Pb >= 1 && Pb <= P && Pn >= 1 && Pn <= P && D >= 1 && n_ctx >= 1 && n_ctx + 3 <= L, CLIPMI_ERR_SHAPE,
+                 "%s: C=%d Pb=%d P=%d Pn=%d L=%d D=%d n_ctx=%d", who, C, Pb, P, Pn, L, D, n_ctx);
+  CLIPMI_REQUIRE(((int64_t)C * Pb + Pn) * L < (1ll << 31) && (int64_t)(Pb + Pn) * n_ctx * D < (1ll << 31), CLIPMI_ERR_SHAPE, "%s: prompt set or block too large", who);
+  const bool vec = D % 4 == 0 && aligned16(d_embed) && aligned16(partial);
+  const int64_t total = (int64_t)(Pb + Pn) * n_ctx * (vec ? D / 4 : D);
+  const dim3 grid((unsigned)((total + THREADS - 1) / THREADS)), threads(THREADS);
+  if (vec)
+    hipLaunchKernelGGL(proda_ctx_partial_kernel<4>, grid, threads, 0, (hipStream_t)stream, d_embed, partial, sel, pos, name_lens, C, Pb, P, Pn, L, D, n_ctx);
+  else
+    hipLaunchKernelGGL(proda_ctx_partial_kernel<1>, grid, threads, 0, (hipStream_t)stream, d_embed, partial, sel, pos, name_lens, C, Pb, P, Pn, L, D, n_ctx);
+  return check_launch("proda_ctx_partial_kernel");
+}
+
+int clipmi_proda_ctx_step_gathered(const float* gathered, int G, int64_t rank_stride, float* ctx, float* buf, float* grad_out, const int32_t* sel, int Pb, int P,
+                                   int D, int n_ctx, float grad_scale, const float* lr, int first_step, float momentum, float dampening, float weight_decay,
+                                   int nesterov, clipmi_stream_t stream) {
+  const char* who = "proda_ctx_step_gathered";
+  CLIPMI_REQUIRE(ctx || grad_out, CLIPMI_ERR_ARG, "%s: null pointer (one of ctx, grad_out is required)", who);
+  CLIPMI_REQUIRE(!ctx || lr, CLIPMI_ERR_ARG, "%s: null pointer (a step needs lr)", who);
+  if (int rc = check_gathered_step(who, gathered, G, rank_stride, sel, Pb, P, D, n_ctx)) return rc;
+  CLIPMI_REQUIRE(std::isfinite(grad_scale) && grad_scale > 0.f, CLIPMI_ERR_ARG, "%s: grad_scale=%g (finite, > 0)", who, grad_scale);
+  if (int rc = check_sgd(who, momentum, dampening, weight_decay, nesterov)) return rc;
+  CLIPMI_REQUIRE(!ctx || momentum == 0.f || buf, CLIPMI_ERR_ARG, "%s: null pointer (a momentum needs the buffer)", who);
+  const int64_t nD = (int64_t)n_ctx * D;
+  // 16-byte accesses need every block of n_ctx D floats of the three streams on one 16-byte phase
+  const bool vec = nD % 4 == 0 && rank_stride % 4 == 0 && aligned16(gathered) && aligned16(ctx) && aligned16(buf) && aligned16(grad_out);
+  const int64_t total = P * (vec ? nD / 4 : nD);
+  const dim3 grid((unsigned)((total + THREADS - 1) / THREADS)), threads(THREADS);
+  const SgdArgs sgd = make_sgd_args(momentum, dampening, weight_decay, nesterov, first_step);
+  if (vec)
+    hipLaunchKernelGGL(proda_ctx_step_gathered_kernel<4>, grid, threads, 0, (hipStream_t)stream, gathered, G, rank_stride, ctx, buf, grad_out, sel, Pb, P, nD,
+                       1.f / grad_scale, lr, sgd);
+  else
+    hipLaunchKernelGGL(proda_ctx_step_gathered_kernel<1>, grid, threads, 0, (hipStream_t)stream, gathered, G, rank_stride, ctx, buf, grad_out, sel, Pb, P, nD,
+                       1.f / grad_scale, lr, sgd);
+  return check_launch("proda_ctx_step_gathered_kernel");
+}
+
+int clipmi_proda_ctx_reduce_gathered_scaled(const float* gathered, int G, int64_t rank_stride, float* ctx, float* buf, float* grad_out, const int32_t* sel,
+                                            int Pb, int P, int D, int n_ctx, clipmi_scaler_state* state, float growth_factor, float backoff_factor,
+                                            int growth_interval, const float* lr, float momentum, float dampening, float weight_decay, int nesterov,
+                                            void* workspace, size_t workspace_bytes, clipmi_stream_t stream) {
+  const char* who = "proda_ctx_reduce_gathered_scaled";
+  const ScalerCall sc{state, growth_factor, backoff_factor, growth_interval};
+  CLIPMI_REQUIRE(ctx && lr && workspace, CLIPMI_ERR_ARG, "%s: null pointer (ctx, lr and the workspace are required)", who);
+  if (int rc = check_scaler(who, sc)) return rc;
+  if (int rc = check_gathered_step(who, gathered, G, rank_stride, sel, Pb, P, D, n_ctx)) return rc;
+  if (int rc = check_sgd(who, momentum, dampening, weight_decay, nesterov)) return rc;
+  CLIPMI_REQUIRE(momentum == 0.f || buf, CLIPMI_ERR_ARG, "%s: null pointer (a momentum needs the buffer)", who);
+  CLIPMI_REQUIRE((uintptr_t)workspace % 256 == 0, CLIPMI_ERR_ARG, "%s: the workspace must be 256-byte aligned", who);
+  const int64_t nD = (int64_t)n_ctx * D, total = P * nD;
+  const size_t need = scaled_step_bytes(total);
+  CLIPMI_REQUIRE(workspace_bytes >= need, CLIPMI_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, need);
+  const ScaledWs w = scaled_carve(workspace, total);
+  hipLaunchKernelGGL(proda_gathered_scaled_grad_kernel, dim3((unsigned)scaled_grad_blocks(total)), dim3(THREADS), 0, (hipStream_t)stream, gathered, G, rank_stride,
+                     grad_out, sel, Pb, P, nD, (const clipmi_scaler_state*)state, w);
+  if (int rc = check_launch("proda_gathered_scaled_grad_kernel")) return rc;
+  return launch_scaled_decide_apply(w, total, ctx, buf, sc, lr, momentum, dampening, weight_decay, nesterov, (hipStream_t)stream);
+}
 
 int clipmi_proda_embed(const void* base, const void* nc_base, int dtype, const float* ctx, const int32_t* sel, const int32_t* pos, const int32_t* name_lens,
                        const int32_t* cls_eot, float* prompts, int32_t* eot, int C, int Pb, int P, int L, int Lc, int D, int n_ctx, clipmi_stream_t stream) {

@@ -19,15 +19,7 @@ namespace {
 
 constexpr int THREADS = 256;
 
-// the balanced split: the first C mod G ranks own one class more.  *lo: the first class of the rank that owns class c
-__device__ __forceinline__ int shard_owner(int c, int C, int G, int* lo) {
-  const int base = C / G, rem = C % G, cut = rem * (base + 1);
-  const int r = c < cut ? c / (base + 1) : rem + (c - cut) / base;   // base >= 1: C >= G
-  *lo = r * base + (r < rem ? r : rem);
-  return r;
-}
-
-// one thread per element of out [C, E]: row c is row c - lo of its owner's block of P = ceil(C / G) rows; the padding rows are never read
+// one thread per element of out [C, E] (shard_owner: train_rules.h): row c is row c - lo of its owner's block of P = ceil(C / G) rows; the padding rows are never read
 __global__ __launch_bounds__(THREADS) void shard_compact_kernel(const float* __restrict__ gathered, float* __restrict__ out, int C, int G, int P, int64_t E) {
   const int64_t idx = (int64_t)blockIdx.x * THREADS + threadIdx.x;
   if (idx >= (int64_t)C * E) return;

@@ -94,6 +94,15 @@ __device__ __forceinline__ float ctx_grad_element(const float* __restrict__ d_em
   return g * inv_scale;
 }
 
+// The balanced split of the class-sharded fits (shard_train.hip, proda_train.hip): the first C mod G of the G ranks own one item more.
+// Returns the rank that owns item c of C; *lo: that rank's first item
+__device__ __forceinline__ int shard_owner(int c, int C, int G, int* lo) {
+  const int base = C / G, rem = C % G, cut = rem * (base + 1);
+  const int r = c < cut ? c / (base + 1) : rem + (c - cut) / base;   // base >= 1: C >= G
+  *lo = r * base + (r < rem ? r : rem);
+  return r;
+}
+
 // ProGrad's rule (reference prograd.py:371-409) on the float64 dots a.a, b.b, a.b of its two context gradients (prompt_train.hip's
 // prograd_step_kernel, shard_train.hip): the reference compares dot(a / |a|, b / |b|) with 0, which is a.b < 0 unless a norm is zero or
 // something is not finite, where its comparison is false and the plain a is applied.  The element: a - lambda (a.b / b.b) b, the scalar

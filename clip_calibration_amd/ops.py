@@ -2062,6 +2062,150 @@ def proda_ctx_step_scaled(d_embed: torch.Tensor, sel: torch.Tensor, pos: torch.T
     return grad
 
 
+# ---- the class-sharded ProDA fit (csrc/proda_train.hip, DESIGN.md "Class-sharded ProDA fit")
+
+def proda_embed_shard(base: torch.Tensor, nc_base: torch.Tensor, ctx: torch.Tensor, sel: torch.Tensor, pos: torch.Tensor, name_lens: torch.Tensor,
+                      cls_eot: torch.Tensor, nc_lo: int, nc_hi: int, rows: int = 0, prompts: Optional[torch.Tensor] = None,
+                      eot: Optional[torch.Tensor] = None):
+    """``proda_embed`` for one rank of the class-sharded fit: ``base`` [C_r, Lc, D], ``name_lens`` and ``cls_eot`` [C_r] are the rank's own
+    classes' (one class is enough), ``ctx`` [P, n_ctx, D], ``sel`` and ``pos`` the whole collection's, and the no-class prompts written are
+    those of the contexts ``nc_lo .. nc_hi - 1``: ``(prompts fp32 [C_r * Pb + P_r, Lc, D], eot int32 [C_r * Pb + P_r])``."""
+    base = _dev(base, "base", (torch.float16, torch.float32))
+    nc_base = _dev(nc_base, "nc_base", (base.dtype,))
+    ctx = _dev(ctx, "ctx", (torch.float32,))
+    if base.dim() != 3 or ctx.dim() != 3 or nc_base.shape != (1,) + tuple(base.shape[1:]) or ctx.shape[2] != base.shape[2]:
+        raise ValueError(f"proda_embed_shard: base {tuple(base.shape)}, nc_base {tuple(nc_base.shape)} and ctx {tuple(ctx.shape)} do not agree")
+    Cn, Lc, D = base.shape
+    P, n_ctx = int(ctx.shape[0]), int(ctx.shape[1])
+    nc_lo, nc_hi = int(nc_lo), int(nc_hi)
+    if not 0 <= nc_lo < nc_hi <= P:
+        raise ValueError(f"proda_embed_shard: the no-class prompts [{nc_lo}, {nc_hi}) must be a non-empty range of the {P} contexts")
+    sel = _dev(sel, "sel", (torch.int32,))
+    Pb = int(sel.numel())
+    sel, pos, name_lens = _proda_index(sel, "sel", Pb), _proda_index(pos, "pos", P), _proda_index(name_lens, "name_lens", Cn)
+    cls_eot = _proda_index(cls_eot, "cls_eot", Cn)
+    N = Cn * Pb + nc_hi - nc_lo
+    L = int(rows) if 0 < int(rows) < Lc else Lc
+    if prompts is None:
+        prompts = torch.empty(N, Lc, D, dtype=torch.float32, device=base.device)
+    else:
+        _in_place(prompts, torch.float32, "proda_embed_shard: prompts must be a contiguous fp32 tensor on the GPU", numel=N * Lc * D)
+    if eot is None:
+        eot = torch.empty(N, dtype=torch.int32, device=base.device)
+    else:
+        _in_place(eot, torch.int32, "proda_embed_shard: eot must be a contiguous int32 tensor on the GPU", numel=N)
+    check(lib.clipmi_proda_embed_shard(base.data_ptr(), nc_base.data_ptr(), _DT[base.dtype], ctx.data_ptr(), sel.data_ptr(), pos.data_ptr(),
+                                       name_lens.data_ptr(), cls_eot.data_ptr(), prompts.data_ptr(), eot.data_ptr(), Cn, Pb, P, nc_lo, nc_hi - nc_lo, L, Lc, D,
+                                       n_ctx, _stream()), "clipmi_proda_embed_shard")
+    return prompts, eot
+
+
+def proda_shard_rows(n_cls: int, n_sel: int, n_prompt: int, world: int) -> int:
+    """Rows of one rank's block of the gathered text features: ``ceil(C / G) * Pb + ceil(P / G)``."""
+    return -(-int(n_cls) // int(world)) * int(n_sel) + -(-int(n_prompt) // int(world))
+
+
+def proda_shard_compact(gathered: torch.Tensor, n_cls: int, n_sel: int, n_prompt: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The gathered, padded fp32 [G, ``proda_shard_rows``, E] text features -> fp32 [n_cls * n_sel + n_prompt, E] in the unsharded order:
+    block r holds rank r's ``C_r * Pb`` class rows, then its ``P_r`` no-class rows, then padding that is never read.  One launch."""
+    gathered = _dev(gathered, "gathered", (torch.float32,))
+    Cn, Pb, P = int(n_cls), int(n_sel), int(n_prompt)
+    if gathered.dim() != 3 or not 1 <= gathered.shape[0] <= min(Cn, P) or Pb < 1 or gathered.shape[1] != proda_shard_rows(Cn, Pb, P, gathered.shape[0]):
+        raise ValueError(f"proda_shard_compact: gathered {tuple(gathered.shape)} must be [G, ceil({Cn} / G) * {Pb} + ceil({P} / G), E] with G <= min({Cn}, {P})")
+    G, _, E = gathered.shape
+    N = Cn * Pb + P
+    if out is None:
+        out = torch.empty(N, E, dtype=torch.float32, device=gathered.device)
+    else:
+        _in_place(out, torch.float32, "proda_shard_compact: out must be a contiguous fp32 tensor on the GPU", numel=N * E)
+    check(lib.clipmi_proda_shard_compact(gathered.data_ptr(), out.data_ptr(), Cn, Pb, P, G, E, _stream()), "clipmi_proda_shard_compact")
+    return out
+
+
+def proda_ctx_partial(d_embed: torch.Tensor, sel: torch.Tensor, pos: torch.Tensor, name_lens: torch.Tensor, n_own: int, n_ctx: int,
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """A rank's send block fp32 [Pb + n_own, n_ctx, D] from its own ``d_embed`` fp32 [(C_r * Pb + n_own) * L, D]: per selected slot the
+    class rows of the rank's ``C_r`` classes (``name_lens`` [C_r], its own) added in ascending order, unscaled, then the rows of its
+    ``n_own`` no-class prompts as they are.  ``sel`` [Pb], ``pos`` [P]: int32 on the device, the whole collection's.  ``out``: where it is
+    written -- the first rows of the rank's padded send block."""
+    who = "proda_ctx_partial"
+    d_embed = _dev(d_embed, "d_embed", (torch.float32,))
+    sel, pos, name_lens = (_dev(t, n, (torch.int32,)) for t, n in ((sel, "sel"), (pos, "pos"), (name_lens, "name_lens")))
+    Pb, P, Cn, Pn, n_ctx = int(sel.numel()), int(pos.numel()), int(name_lens.numel()), int(n_own), int(n_ctx)
+    N = Cn * Pb + Pn
+    if d_embed.dim() != 2 or Pn < 1 or Pn > P or Cn < 1 or d_embed.shape[0] % N:
+        raise ValueError(f"{who}: d_embed {tuple(d_embed.shape)} does not split into {Cn} * {Pb} class prompts and {Pn} (1 .. {P}) no-class prompts")
+    L, D = d_embed.shape[0] // N, d_embed.shape[1]
+    if out is None:
+        out = torch.empty(Pb + Pn, n_ctx, D, dtype=torch.float32, device=d_embed.device)
+    else:
+        _in_place(out, torch.float32, f"{who}: out must be a contiguous fp32 tensor on the GPU", numel=(Pb + Pn) * n_ctx * D)
+    check(lib.clipmi_proda_ctx_partial(d_embed.data_ptr(), out.data_ptr(), sel.data_ptr(), pos.data_ptr(), name_lens.data_ptr(), Cn, Pb, P, Pn, L, D, n_ctx,
+                                       _stream()), "clipmi_proda_ctx_partial")
+    return out
+
+
+def _proda_gathered(who: str, gathered: torch.Tensor, sel: torch.Tensor, n_prompt: int, n_ctx: int, D: int):
+    """(G, rank stride, Pb) of the gathered send blocks fp32 [G, >= (Pb + ceil(P / G)) * n_ctx * D] after their checks."""
+    _in_place(gathered, torch.float32, f"{who}: gathered must be a contiguous fp32 tensor on the GPU")
+    Pb = int(sel.numel())
+    if gathered.dim() != 2 or not 1 <= gathered.shape[0] <= n_prompt or n_ctx < 1 or D < 1:
+        raise ValueError(f"{who}: gathered {tuple(gathered.shape)} must be [G, elements per rank] with 1 <= G <= P = {n_prompt}")
+    G, stride = gathered.shape
+    need = (Pb + -(-n_prompt // G)) * n_ctx * D
+    if stride < need:
+        raise ValueError(f"{who}: gathered {tuple(gathered.shape)} holds fewer than (Pb + ceil(P / G)) * n_ctx * D = {need} elements per rank")
+    return G, stride, Pb
+
+
+def proda_ctx_step_gathered(gathered: torch.Tensor, sel: torch.Tensor, n_prompt: int, n_ctx: int, D: int, grad_scale: float,
+                            ctx: Optional[torch.Tensor] = None, buf: Optional[torch.Tensor] = None, lr: Optional[torch.Tensor] = None,
+                            first_step: bool = False, momentum: float = 0.0, dampening: float = 0.0, weight_decay: float = 0.0, nesterov: bool = False,
+                            want_grad: bool = True) -> Optional[torch.Tensor]:
+    """``proda_ctx_step`` from the gathered send blocks fp32 [G, >= (Pb + ceil(P / G)) * n_ctx * D] (rank r's ``proda_ctx_partial`` first
+    in row r, padding behind it that is never read): for a context selected at slot q the G class sums of slot q added in rank order,
+    then -- for every context -- its no-class row from the rank that owns it, divided by ``grad_scale``; with ``ctx`` [P, n_ctx, D]
+    torch.optim.SGD's step on it in place."""
+    who = "proda_ctx_step_gathered"
+    sel = _dev(sel, "sel", (torch.int32,))
+    P, n_ctx, D = int(n_prompt), int(n_ctx), int(D)
+    G, stride, Pb = _proda_gathered(who, gathered, sel, P, n_ctx, D)
+    if ctx is None and not want_grad:
+        raise ValueError(f"{who}: nothing to do (no ctx and no gradient wanted)")
+    pc, pb, pl = _step_targets(who, (P, n_ctx, D), ctx, buf, lr)
+    grad = torch.empty(P, n_ctx, D, dtype=torch.float32, device=gathered.device) if want_grad else None
+    check(lib.clipmi_proda_ctx_step_gathered(gathered.data_ptr(), G, stride, pc, pb, None if grad is None else grad.data_ptr(), sel.data_ptr(), Pb, P, D, n_ctx,
+                                             float(grad_scale), pl, int(bool(first_step)), float(momentum), float(dampening), float(weight_decay),
+                                             int(bool(nesterov)), _stream()), "clipmi_proda_ctx_step_gathered")
+    return grad
+
+
+def proda_ctx_reduce_gathered_scaled(gathered: torch.Tensor, sel: torch.Tensor, n_prompt: int, n_ctx: int, D: int, state: torch.Tensor, ctx: torch.Tensor,
+                                     buf: Optional[torch.Tensor], lr: torch.Tensor, growth_factor: float = 2.0, backoff_factor: float = 0.5,
+                                     growth_interval: int = 2000, momentum: float = 0.0, dampening: float = 0.0, weight_decay: float = 0.0,
+                                     nesterov: bool = False, want_grad: bool = True, workspace: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
+    """``proda_ctx_step_gathered`` under the dynamic loss scale of ``state``, as ``proda_ctx_step_scaled`` is ``proda_ctx_step``'s: the
+    rank-ordered sum divided by the block's scale, the step skipped and the scale backed off when any element is an inf or a NaN.  Every
+    rank reduces the same gathered bytes and so decides alike.  Returns the unscaled gradient [P, n_ctx, D] when ``want_grad``."""
+    who = "proda_ctx_reduce_gathered_scaled"
+    sel = _dev(sel, "sel", (torch.int32,))
+    P, n_ctx, D = int(n_prompt), int(n_ctx), int(D)
+    G, stride, Pb = _proda_gathered(who, gathered, sel, P, n_ctx, D)
+    if ctx is None:
+        raise ValueError(f"{who}: ctx is required (the step decides whether to write it)")
+    pc, pb, pl = _step_targets(who, (P, n_ctx, D), ctx, buf, lr)
+    ps = _scaler_state(who, state)
+    grad = torch.empty(P, n_ctx, D, dtype=torch.float32, device=gathered.device) if want_grad else None
+    need = lib.clipmi_proda_ctx_step_scaled_workspace_bytes(P, D, n_ctx)
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=gathered.device)
+    check(lib.clipmi_proda_ctx_reduce_gathered_scaled(gathered.data_ptr(), G, stride, pc, pb, None if grad is None else grad.data_ptr(), sel.data_ptr(), Pb, P,
+                                                      D, n_ctx, ps, float(growth_factor), float(backoff_factor), int(growth_interval), pl, float(momentum),
+                                                      float(dampening), float(weight_decay), int(bool(nesterov)), workspace.data_ptr(), workspace.numel(),
+                                                      _stream()), "clipmi_proda_ctx_reduce_gathered_scaled")
+    return grad
+
+
 def cocoop_block_layout(n_ctx: int, D: int, E: int, H: int):
     """The offsets, in floats, of ``ctx | W1 | b1 | W2 | b2`` in CoCoOp's parameter block, and its size: a dict name -> (offset, shape),
     the names those of the reference's ``state_dict``, and the total (clipmi_cocoop_block_floats)."""

@@ -25,8 +25,22 @@ prompts, more than 80 live token rows (the backward's limit).
 
 UNVERIFIED, as for CoOp: Dassl is not part of this environment, so the defaults -- SGD at 0.002 with momentum 0.9 and weight decay 5e-4,
 batches of 32, 32 prompts in slices of 4, 16 context vectors from N(0, 0.02^2), alpha = 0.1 -- restate the reference's configs and
-Dassl's public defaults without a run of the reference behind them; each is an argument.  Not covered: ``nn.DataParallel`` over the text
-encoder (one process drives one GPU).
+Dassl's public defaults without a run of the reference behind them; each is an argument.
+
+``shard=coopfit.Shard(world, rank, gather)`` on ``ProDAFitState``, ``fit_context`` and ``context_gradient`` is the class-sharded fit, in
+the place of the reference's ``nn.DataParallel`` over the text encoder (proda.py:374-378): one process per GPU, rank r of G running the
+tower over the contiguous classes ``parallel.shard_bounds(C, r, G)`` with all ``prompt_bs`` prompts of each and over the no-class
+prompts of the contexts ``shard_bounds(P, r, G)`` -- dealt out, not replicated: the tower's kernel choice follows a call's row count,
+and replicated rows could differ in their bits from rank to rank.  Two all-gathers per step move the raw text features and the ranks'
+partial gradients (clipmi_proda_ctx_partial); the head runs replicated, and clipmi_proda_ctx_step_gathered adds the partials in rank
+order, so every rank holds the same contexts bit for bit with no all-reduce and no float atomic.  Every rank is given the same batch
+and the whole collection.  ``grad_scale="dynamic"`` works under the shard (clipmi_proda_ctx_reduce_gathered_scaled): every rank reduces
+the same gathered bytes, takes the same skip-or-apply decision and holds the same scaler block.  The selection schedule is drawn on the
+host: under a ``LocalGather`` only the driving state -- the first that steps -- draws, and stepping another is refused; under RCCL
+EVERY RANK MUST BE BUILT WITH THE SAME GENERATOR SEED (the default is one), or be given the same ``selections`` / ``sel``.  With one
+rank the sharded step gives the unsharded step's bits.  Refused under ``shard``, by name and before any device call: ``C < G``,
+``P < G``, ``optimizer="adam" | "adamw"``, ``one_call=True``, ``val=`` / ``final_model="best_val"`` / ``validate``, and
+``context_gradient``'s operand statistics.  DESIGN.md "Class-sharded ProDA fit".
 
 ``grad_scale="dynamic"`` with ``scaler=dict(init_scale, growth_factor, backoff_factor, growth_interval)`` is the reference's ``prec ==
 "amp"`` branch (proda.py:370, 388-394, ``torch.cuda.amp.GradScaler``) with the scale in a device block, as ``coopfit``'s: the head runs at
@@ -56,8 +70,10 @@ import torch
 
 from . import _lib, fitloop, fitmonitor, ops
 from ._lib import check, lib
-from .coopfit import DEFAULT_GRAD_SCALE, DYNAMIC, MAX_LIVE_ROWS, _DT, _AdamBlock, _BlockScaler, _Tower, _check_batch, _check_grad_scale, _is_dynamic, _live_rows, _scale_args
+from .coopfit import (DEFAULT_GRAD_SCALE, DYNAMIC, MAX_LIVE_ROWS, _DT, Shard, _AdamBlock, _BlockScaler, _Tower, _check_batch, _check_grad_scale, _drive,
+                      _file_state, _is_dynamic, _live_rows, _run_phases, _scale_args, _world_states, operand_stats_dict, shard_states)
 from .fitloop import _host_int_array, _need_gpu, steps_per_epoch
+from .parallel import shard_bounds
 
 
 def positions(n_prompt: int) -> np.ndarray:
@@ -161,12 +177,14 @@ def _check_prompts(who: str, clip_model, tokenized_prompts, ctx, name_lens, seq_
 
 
 class _ProDATower(_Tower):
-    """``coopfit._Tower`` over ProDA's N = C Pb + P assembled prompts: ``base`` holds the C class embeddings and, last, the no-class one."""
+    """``coopfit._Tower`` over ProDA's N = C Pb + P assembled prompts: ``base`` holds the C class embeddings and, last, the no-class one.
+    ``nc=(lo, hi)``: a rank of the class-sharded fit -- ``ids_all``, ``n_cls`` and ``name_lens`` are its own classes' and of the P
+    no-class prompts it runs those of the contexts lo .. hi - 1: N = C_r Pb + (hi - lo)."""
 
-    def __init__(self, who, clip_model, ids_all, n_cls, P, Pb, n_ctx, name_lens, last_eot, seq_rows):
-        super().__init__(who, clip_model, ids_all, n_cls * Pb + P, n_ctx, False, last_eot, seq_rows)
+    def __init__(self, who, clip_model, ids_all, n_cls, P, Pb, n_ctx, name_lens, last_eot, seq_rows, nc=None):
+        super().__init__(who, clip_model, ids_all, n_cls * Pb + (P if nc is None else nc[1] - nc[0]), n_ctx, False, last_eot, seq_rows)
         dev = clip_model.device
-        self.n_cls, self.P, self.Pb = n_cls, P, Pb
+        self.n_cls, self.P, self.Pb, self.nc = n_cls, P, Pb, nc
         self.N = self.C                       # _Tower sizes workspace, stash, text and d_embed by the number of prompts
         self.cls_base, self.nc_base = self.base[:n_cls], self.base[n_cls:]
         self.cls_eot = self.eot[:n_cls].contiguous()      # of the ids: every prompt of a class keeps its class's EOT row
@@ -177,7 +195,10 @@ class _ProDATower(_Tower):
 
     def forward(self, ctx: torch.Tensor, sel: torch.Tensor) -> torch.Tensor:
         m = self.model
-        ops.proda_embed(self.cls_base, self.nc_base, ctx, sel, self.pos, self.name_lens, self.cls_eot, self.rows, self.prompts, self.eot)
+        if self.nc is None:
+            ops.proda_embed(self.cls_base, self.nc_base, ctx, sel, self.pos, self.name_lens, self.cls_eot, self.rows, self.prompts, self.eot)
+        else:
+            ops.proda_embed_shard(self.cls_base, self.nc_base, ctx, sel, self.pos, self.name_lens, self.cls_eot, *self.nc, self.rows, self.prompts, self.eot)
         with m._launch_lock:
             check(lib.clipmi_text_encoder_train(m._handle, self.prompts.data_ptr(), _lib.F32, None, 0, 0, self.eot.data_ptr(), self.N, self.rows, None,
                                                 self.text.data_ptr(), self.ws.data_ptr(), self.ws.numel(), self.stash.data_ptr(), self.stash.numel(),
@@ -194,17 +215,41 @@ class _ProDATower(_Tower):
         return self.step_ws
 
 
+def check_shard(who: str, shard, n_cls: int, n_prompt: int, one_call: bool = False, val=None, final_model: str = "last_step") -> None:
+    """What the class-sharded ProDA fit refuses, each by name, before any device call (the optimiser is ``fitloop.check_optimizer``'s
+    to refuse)."""
+    if not isinstance(shard, Shard):
+        raise ValueError(f"{who}: shard must be a coopfit.Shard(world, rank, gather), got {type(shard).__name__}")
+    if n_cls < shard.world:
+        raise ValueError(f"{who}: shard: C={n_cls} classes cannot be split over world={shard.world} ranks (C < G: a rank would own no class)")
+    if n_prompt < shard.world:
+        raise ValueError(f"{who}: shard: P={n_prompt} no-class prompts cannot be dealt out to world={shard.world} ranks (P < G: a rank would own none)")
+    if one_call:
+        raise ValueError(f"{who}: shard has no one-call step (one_call=True); the sharded step is the separate calls")
+    if val is not None or final_model == "best_val":
+        raise ValueError(f"{who}: shard has no validation: val=, val_loader= and final_model='best_val' are not sharded")
+
+
 def context_gradient(clip_model, tokenized_prompts, ctx: torch.Tensor, features: torch.Tensor, labels, sel=None, name_lens=None, alpha: float = 0.1,
-                     logit_scale: float = 4.6052, grad_scale: float = DEFAULT_GRAD_SCALE, seq_rows: Optional[int] = None, return_parts: bool = False):
+                     logit_scale: float = 4.6052, grad_scale: float = DEFAULT_GRAD_SCALE, seq_rows: Optional[int] = None, return_parts: bool = False,
+                     return_operand_stats: bool = False, shard: Optional[Shard] = None):
     """``(loss, grad)`` of ProDA's training loss (module docstring) with respect to ``ctx`` [P, n_ctx, D] on the GPU: loss fp32 [1], grad
     fp32 [P, n_ctx, D].  ``tokenized_prompts`` [C, context_length]: the ids of ``"X .. X name."``; ``features`` fp32 [B, E] raw image
     features (the rows may be a column slice).  ``sel``: the contexts this step uses (None: all of them; any order -- it is put into the
     reference's end | middle | front order); ``name_lens``: the classes' name lengths in tokens (None: EOT - n_ctx - 2, as the inference
     mirror derives them; a shorter one moves fewer tokens in front of or between the context vectors, as in the reference, and the
     EOT row stays the prompt's own).  ``return_parts`` adds a dict: ``upper``, ``m`` (fp32 [1] each), ``text`` (the raw text features fp32
-    [C Pb + P, E], class prompts first) and ``sel`` (int32, as used)."""
+    [C Pb + P, E], class prompts first) and ``sel`` (int32, as used).  ``return_operand_stats`` adds, last, ``coopfit.context_gradient``'s
+    dict over every fp16 dgrad-GEMM operand element of the backward.
+
+    ``shard``: the gradient the class-sharded step would apply (module docstring), reduced over the ranks in rank order -- the same bits
+    on every rank; ``text`` is then the gathered, compacted matrix.  The operand statistics are per rank and are refused."""
     who = "context_gradient"
     ids_all, Cn, P, n_ctx, nl, last = _check_prompts(who, clip_model, tokenized_prompts, ctx, name_lens, seq_rows)
+    if shard is not None:
+        check_shard(who, shard, Cn, P)
+        if return_operand_stats:
+            raise ValueError(f"{who}: shard returns no operand statistics (return_operand_stats=True)")
     pos = positions(P)
     sel_h = _check_sel(who, np.arange(P) if sel is None else sel, P, pos)
     if sel_h.ndim != 1:
@@ -218,16 +263,29 @@ def context_gradient(clip_model, tokenized_prompts, ctx: torch.Tensor, features:
     E = int(clip_model.geometry.embed_dim)
     labels_d = _check_batch(who, features, labels, Cn, E)
     _need_gpu(features, "features")
-    tower = _ProDATower(who, clip_model, ids_all, Cn, P, len(sel_h), n_ctx, nl, last, seq_rows)
     dev = features.device
-    sel_d = torch.from_numpy(sel_h).to(dev)
-    text = tower.forward(fitloop.master(ctx, dev), sel_d)
-    losses, d_text = ops.proda_head(features, labels_d, text, Cn, len(sel_h), scale, gs, alpha)
-    d_embed = tower.backward(d_text)
-    grad = ops.proda_ctx_step(d_embed, sel_d, tower.pos, tower.name_lens, n_ctx, gs)
-    if not return_parts:
-        return losses[0:1], grad
-    return losses[0:1], grad, {"upper": losses[1:2], "m": losses[2:3], "text": text.clone(), "sel": sel_d}
+    if shard is not None:     # the sharded step's phases with a report in the step's place
+        make = lambda sh: ProDAFitState(clip_model, tokenized_prompts, ctx, len(sel_h), alpha, logit_scale, 0.0, 0.0, False, 0.0, gs, seq_rows, name_lens,
+                                        shard=sh)
+        state = shard_states(make, shard)
+        states = _world_states(shard, state, who)
+        sel_d = torch.from_numpy(sel_h).to(dev)
+        reports, losses = [{} for _ in states], [torch.empty(3, dtype=torch.float32, device=dev) for _ in states]
+        _run_phases([s._shard_phases(features, labels_d, sel_d, None, l, True, r) for s, l, r in zip(states, losses, reports)])
+        k = states.index(state)
+        losses, grad, text = losses[k], reports[k]["grad"], reports[k]["text"]
+    else:
+        tower = _ProDATower(who, clip_model, ids_all, Cn, P, len(sel_h), n_ctx, nl, last, seq_rows)
+        sel_d = torch.from_numpy(sel_h).to(dev)
+        text = tower.forward(fitloop.master(ctx, dev), sel_d)
+        stats = torch.zeros(4, dtype=torch.int64, device=dev) if return_operand_stats else None
+        losses, d_text = ops.proda_head(features, labels_d, text, Cn, len(sel_h), scale, gs, alpha)
+        d_embed = tower.backward(d_text, stats)
+        grad = ops.proda_ctx_step(d_embed, sel_d, tower.pos, tower.name_lens, n_ctx, gs)
+    out = (losses[0:1], grad)
+    if return_parts:
+        out += ({"upper": losses[1:2], "m": losses[2:3], "text": text.clone(), "sel": sel_d},)
+    return out + ((operand_stats_dict(stats),) if return_operand_stats else ())
 
 
 def _aligned_fp32(features: torch.Tensor) -> torch.Tensor:
@@ -248,19 +306,33 @@ class ProDAFitState(fitmonitor.Monitored):
                  momentum: float = 0.9, dampening: float = 0.0, nesterov: bool = False, weight_decay: float = 5e-4,
                  grad_scale: float = DEFAULT_GRAD_SCALE, seq_rows: Optional[int] = None, name_lens=None,
                  optimizer: str = "sgd", betas=(0.9, 0.999), eps: float = 1e-8,
-                 generator: Optional[torch.Generator] = None, scaler: Optional[dict] = None):
+                 shard: Optional[Shard] = None, generator: Optional[torch.Generator] = None, scaler: Optional[dict] = None):
         """``optimizer``: "sgd" (``momentum``, ``dampening``, ``nesterov``), "adam" or "adamw" (``betas``, ``eps``;
-        ``weight_decay`` keeps the fit's default of 5e-4 under all three -- torch's AdamW default of 1e-2 is NOT taken over)."""
+        ``weight_decay`` keeps the fit's default of 5e-4 under all three -- torch's AdamW default of 1e-2 is NOT taken over).
+        ``shard``: this state is one rank of the class-sharded fit (module docstring).  It holds the whole ``ctx`` and runs the tower
+        over its own classes and no-class prompts; ``generator`` must be seeded alike on every rank of an RCCL run (the default is)."""
         who = "ProDAFitState"
         ids_all, self.C, self.P, self.n_ctx, nl, last = _check_prompts(who, clip_model, tokenized_prompts, ctx, name_lens, seq_rows)
         self.Pb = int(prompt_bs)
         _check_collection(who, self.P, self.Pb)
+        self.shard = shard
+        if shard is not None:
+            check_shard(who, shard, self.C, self.P)
         self.alpha = _check_alpha(who, alpha)
         self.dynamic, self.grad_scale, self.scaler = _scale_args(who, grad_scale, scaler)
-        self.optimizer, momentum, dampening, nesterov, betas = fitloop.check_optimizer(who, optimizer, momentum, dampening, nesterov, weight_decay, betas, eps)
+        self.optimizer, momentum, dampening, nesterov, betas = fitloop.check_optimizer(who, optimizer, momentum, dampening, nesterov, weight_decay, betas, eps,
+                                                                                       shard=shard)
         self.scale = fitloop.exp_logit_scale(who, logit_scale)
-        self.tower = _ProDATower(who, clip_model, ids_all, self.C, self.P, self.Pb, self.n_ctx, nl, last, seq_rows)
         dev = clip_model.device
+        if shard is None:
+            self.tower = _ProDATower(who, clip_model, ids_all, self.C, self.P, self.Pb, self.n_ctx, nl, last, seq_rows)
+        else:   # the tower over the rank's own classes and no-class prompts; the live-row cut is the full prompt set's
+            self.lo, self.hi = shard_bounds(self.C, shard.rank, shard.world)
+            self.nc_lo, self.nc_hi = shard_bounds(self.P, shard.rank, shard.world)
+            own = np.concatenate([ids_all[self.lo:self.hi], ids_all[self.C:]])
+            self.tower = _ProDATower(who, clip_model, own, self.hi - self.lo, self.P, self.Pb, self.n_ctx, nl[self.lo:self.hi], last, seq_rows,
+                                     nc=(self.nc_lo, self.nc_hi))
+            self._shard_buffers(dev)
         self.ctx = fitloop.master(ctx, dev)
         self.buf = torch.zeros_like(self.ctx) if momentum != 0.0 else None
         self.momentum, self.dampening, self.nesterov, self.weight_decay = momentum, dampening, nesterov, weight_decay
@@ -280,6 +352,58 @@ class ProDAFitState(fitmonitor.Monitored):
         if not self.dynamic:
             raise ValueError(f"ProDAFitState.scaler_state: the state was made with a static grad_scale={self.grad_scale}")
         return self._scaler.state()
+
+    # ---- the class-sharded step (csrc/proda_train.hip, DESIGN.md "Class-sharded ProDA fit")
+
+    def _shard_buffers(self, dev) -> None:
+        """The send and receive blocks of the step's two gathers, made once.  The tower writes its text features straight into the first
+        rows of the padded send block; the padding of either block is moved and never read."""
+        sh, t = self.shard, self.tower
+        G, rows = sh.world, ops.proda_shard_rows(self.C, self.Pb, self.P, sh.world)
+        f32 = dict(dtype=torch.float32, device=dev)
+        self._send_text = torch.empty(rows, t.E, **f32)
+        t.text = self._send_text[:t.N]
+        self._all_text = torch.empty(G, rows, t.E, **f32)
+        self._text = torch.empty(self.C * self.Pb + self.P, t.E, **f32)
+        self._own_d_text = torch.empty(t.N, t.E, **f32)
+        slots = self.Pb + -(-self.P // G)          # the class sums of the Pb selected contexts | the rank's no-class rows, padded
+        self._send_part = torch.empty(slots, t.n_ctx, t.D, **f32)
+        self._all_part = torch.empty(G, slots * t.n_ctx * t.D, **f32)
+        _file_state(sh, self)
+
+    def _shard_phases(self, features, labels_d, sel_d, lr_d, losses, first: bool, report: Optional[dict] = None):
+        """One sharded step as phases, a ``yield`` behind every gather.  ``report``: a dict that receives the reduced gradient and the
+        compacted text features INSTEAD of a step: neither the contexts nor the momentum buffer nor the scaler block is touched."""
+        t, sh, st = self.tower, self.shard, ops._stream()
+        gs = 1.0 if self.dynamic else self.grad_scale
+        t.forward(self.ctx, sel_d)                                                           # the rank's own prompts
+        sh.gather(self._send_text, self._all_text, self._send_text.numel() * 4, st)
+        yield
+        text = ops.proda_shard_compact(self._all_text, self.C, self.Pb, self.P, self._text)
+        _, d_text = ops.proda_head(features, labels_d, text, self.C, self.Pb, self.scale, gs, self.alpha, losses)
+        own, n_cls, all_cls = self._own_d_text, (self.hi - self.lo) * self.Pb, self.C * self.Pb
+        own[:n_cls].copy_(d_text[self.lo * self.Pb:self.hi * self.Pb])                       # the rank's own rows of the replicated d_text
+        own[n_cls:].copy_(d_text[all_cls + self.nc_lo:all_cls + self.nc_hi])
+        if self.dynamic:
+            ops.grad_scale_rows(own, self._scaler.block)
+        d_embed = t.backward(own)
+        n_own = self.nc_hi - self.nc_lo
+        ops.proda_ctx_partial(d_embed, sel_d, t.pos, t.name_lens, n_own, t.n_ctx, self._send_part[:self.Pb + n_own])
+        sh.gather(self._send_part, self._all_part, self._send_part.numel() * 4, st)
+        yield
+        if report is not None:
+            report["grad"], report["text"] = ops.proda_ctx_step_gathered(self._all_part, sel_d, self.P, t.n_ctx, t.D, gs), text
+            return
+        sgd = (float(self.momentum), float(self.dampening), float(self.weight_decay), bool(self.nesterov))
+        if self.dynamic:
+            sc = self._scaler
+            if sc.ws is None:
+                need = lib.clipmi_proda_ctx_step_scaled_workspace_bytes(self.P, t.D, t.n_ctx)
+                sc.ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.ctx.device)
+            ops.proda_ctx_reduce_gathered_scaled(self._all_part, sel_d, self.P, t.n_ctx, t.D, sc.block, self.ctx, self.buf, lr_d, *sc.args(), *sgd,
+                                                 want_grad=False, workspace=sc.ws)
+        else:
+            ops.proda_ctx_step_gathered(self._all_part, sel_d, self.P, t.n_ctx, t.D, gs, self.ctx, self.buf, lr_d, first, *sgd, want_grad=False)
 
     # ---- per-epoch validation and best-epoch selection on the device (DESIGN.md "Fit monitor", "CoCoOp and ProDA")
 
@@ -315,6 +439,8 @@ class ProDAFitState(fitmonitor.Monitored):
         classes' name lengths are the state's (``name_lens``); the inference mirror derives its own from the EOT rows, which is the
         state's default.  Without ``start_monitor`` the history starts with ``epoch + 1`` slots of 10 bins and no selection."""
         who = "ProDAFitState.validate"
+        if self.shard is not None:
+            raise ValueError(f"{who}: shard has no validation (the sharded fit scores nothing between epochs)")
         mon, t, m = self._monitor_for(epoch), self.tower, self.tower.model
         epoch = mon.slot(who, epoch)
         if val_class_chunk is None:
@@ -377,10 +503,20 @@ class ProDAFitState(fitmonitor.Monitored):
         still returns its loss; whether it was applied is in ``scaler_state()``.  Under ``optimizer="adam" | "adamw"`` the gather-reduce
         leaves the contexts' gradient as ``context_gradient`` returns it -- every context has one, its no-class prompt's row -- and
         clipmi_block_step_adam applies it to the whole collection (clipmi_block_step_adam_scaled under the dynamic scale, on the gradient
-        formed at ``grad_scale = 1``); ``one_call`` is then refused: the one-call steps stay SGD."""
+        formed at ``grad_scale = 1``); ``one_call`` is then refused: the one-call steps stay SGD.  Under ``shard`` every rank makes this
+        call with the same batch and, where ``sel`` is None, draws the same selection from its like-seeded generator; under a
+        ``LocalGather`` the first state that steps drives all the world's states and draws alone (``one_call`` is refused)."""
         who = "ProDAFitState.step"
         if one_call and self._adam is not None:
             raise ValueError(f"{who}: one_call=True with optimizer={self.optimizer!r}: the one-call steps stay SGD")
+        states = None
+        if self.shard is not None:
+            # every rank is given the same batch; under a local gather this call steps all the world's states, one phase at a time, and
+            # this state alone draws the selection
+            if one_call:
+                raise ValueError(f"{who}: shard has no one-call step (one_call=True); the sharded step is the separate calls")
+            states = _world_states(self.shard, self, who)
+            _drive(self.shard, self, who)
         labels_d = _check_batch(who, features, labels, self.C, self.tower.E)
         _need_gpu(features, "features")
         if features.dtype != torch.float32 or features.stride(1) != 1:
@@ -399,7 +535,11 @@ class ProDAFitState(fitmonitor.Monitored):
         t, m, first = self.tower, self.tower.model, self.steps == 0
         sgd = (self.momentum, self.dampening, self.weight_decay, self.nesterov)
         losses = torch.empty(3, dtype=torch.float32, device=dev)
-        if self._adam is not None:
+        if states is not None:
+            _run_phases([s._shard_phases(features, labels_d, sel_d, lr_d, losses if s is self else torch.empty_like(losses), first) for s in states])
+            for s in states:
+                s.steps += s is not self
+        elif self._adam is not None:
             gs = 1.0 if self.dynamic else self.grad_scale
             text = t.forward(self.ctx, sel_d)
             _, d_text = ops.proda_head(features, labels_d, text, t.n_cls, t.Pb, self.scale, gs, self.alpha, losses)
@@ -467,7 +607,8 @@ def fit_context(features: torch.Tensor, labels, clip_model, tokenized_prompts, c
                 drop_last: bool = False, name_lens=None, selections=None, generator: Optional[torch.Generator] = None,
                 optimizer: str = "sgd", betas=(0.9, 0.999), eps: float = 1e-8, val=None,
                 val_class_chunk: Optional[int] = None, val_bins: int = 10, final_model: str = "last_step", val_criterion: str = "accuracy",
-                return_monitor: bool = False, return_history: bool = False, scaler: Optional[dict] = None, return_scaler_state: bool = False):
+                return_monitor: bool = False, shard: Optional[Shard] = None, return_history: bool = False, scaler: Optional[dict] = None,
+                return_scaler_state: bool = False):
     """Train ProDA's contexts on cached ``features`` fp32 [N, E] and ``labels`` [N], starting from ``ctx`` [n_prompt, n_ctx, D] (not
     modified; None = ``init_context(clip_model, n_ctx, n_prompt)``).  The loop and its arguments are ``coopfit.fit_context``'s:
     ``epochs`` passes of ``torch.optim.SGD`` over batches of ``batch_size``, ``lr_per_epoch`` (None: ``cosine_warmup_schedule``),
@@ -489,7 +630,13 @@ def fit_context(features: torch.Tensor, labels, clip_model, tokenized_prompts, c
 
     ``optimizer``, ``betas``, ``eps``: "sgd" (the default; ``momentum``, ``dampening``, ``nesterov``), "adam" or
     "adamw", as ``coopfit.fit_context`` takes them; ``weight_decay`` keeps this fit's default of 5e-4 under all three (torch's AdamW
-    default of 1e-2 is NOT taken over).  DESIGN.md "Adam steps for the prompt fits"."""
+    default of 1e-2 is NOT taken over).  DESIGN.md "Adam steps for the prompt fits".
+
+    ``shard=Shard(world, rank, gather)``: the class-sharded fit (module docstring).  Every rank makes this call with the same arguments
+    -- the whole prompt set, the whole collection, all features -- and returns the same contexts.  The schedule of selections is drawn
+    here, on the host, once: under RCCL every rank must pass a like-seeded ``generator`` (None is one) or the same ``selections``.  With
+    a ``LocalGather`` the one call runs all ``world`` shard states in this process.  Both loss scales work; Adam, validation and
+    ``final_model="best_val"`` are refused."""
     who = "fit_context"
     fitmonitor.check_args(who, val, val_bins, final_model, val_criterion)
     if val is not None and val_class_chunk is not None and (isinstance(val_class_chunk, bool) or int(val_class_chunk) != val_class_chunk
@@ -500,12 +647,14 @@ def fit_context(features: torch.Tensor, labels, clip_model, tokenized_prompts, c
         ctx = init_context(clip_model, n_ctx, n_prompt)
     _, Cn, P, n_ctx, _, _ = _check_prompts(who, clip_model, tokenized_prompts, ctx, name_lens, seq_rows)
     _check_collection(who, P, int(prompt_bs))
+    if shard is not None:
+        check_shard(who, shard, Cn, P, False, val, final_model)
     E = int(clip_model.geometry.embed_dim)
     if not isinstance(features, torch.Tensor) or features.dim() != 2 or features.shape[0] < 1 or features.shape[1] != E:
         raise ValueError(f"{who}: features must be a [N >= 1, E = {E}] tensor")
     N = features.shape[0]
     epochs, batch_size = fitloop.check_run(who, epochs, batch_size)
-    fitloop.check_optimizer(who, optimizer, momentum, dampening, nesterov, weight_decay, betas, eps)
+    fitloop.check_optimizer(who, optimizer, momentum, dampening, nesterov, weight_decay, betas, eps, shard=shard)
     dynamic, _, cfg = _scale_args(who, grad_scale, scaler)
     if return_scaler_state and not dynamic:
         raise ValueError(f"{who}: return_scaler_state is an argument of grad_scale={DYNAMIC!r}")
@@ -533,8 +682,9 @@ def fit_context(features: torch.Tensor, labels, clip_model, tokenized_prompts, c
             out += (fitmonitor.empty_monitor(val_bins),)
         return out if len(out) > 1 else out[0]
     _need_gpu(features, "features")
-    state = ProDAFitState(clip_model, tokenized_prompts, ctx, prompt_bs, alpha, logit_scale, momentum, dampening, nesterov, weight_decay, grad_scale,
-                          seq_rows, name_lens, scaler=scaler, optimizer=optimizer, betas=betas, eps=eps)
+    make = lambda sh: ProDAFitState(clip_model, tokenized_prompts, ctx, prompt_bs, alpha, logit_scale, momentum, dampening, nesterov, weight_decay,
+                                    grad_scale, seq_rows, name_lens, scaler=scaler, optimizer=optimizer, betas=betas, eps=eps, shard=sh)
+    state = shard_states(make, shard)     # under a LocalGather all the world's states live here; a step of one steps them all
     sels_d = torch.from_numpy(np.ascontiguousarray(sels, dtype=np.int32)).to(dev)
     end_epoch = None
     if val is not None:

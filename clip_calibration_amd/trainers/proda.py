@@ -114,9 +114,20 @@ class CustomCLIP(nn.Module):
         frozen image tower once before the first epoch) or ``val=(val_features, val_labels)``, with ``val_class_chunk`` (classes per
         tower call), ``val_bins``, ``final_model`` ("last_step" or "best_val", the reference's TEST.FINAL_MODEL), ``val_criterion`` and
         ``return_monitor`` as ``prodafit.fit_context`` takes them; ``ProDAFitState.validate`` runs behind every epoch and scores what
-        ``set_classifier`` + ``forward`` would compute.  ``final_model="best_val"`` installs the best epoch's contexts."""
+        ``set_classifier`` + ``forward`` would compute.  ``final_model="best_val"`` installs the best epoch's contexts.
+
+        ``shard=coopfit.Shard(world, rank, gather)`` on either route: the class-sharded fit in the place of the reference's
+        ``nn.DataParallel`` over the text encoder, one process per GPU, every rank making this call on the same data with a like-seeded
+        ``generator`` (``prodafit``'s module docstring).  What ``shard`` refuses -- validation by ``val_loader=`` included -- is refused
+        here, before either tower runs.  With a ``LocalGather`` the one call makes and steps all the ranks' states, on either route."""
         import math
         who = "fit_context"
+        shard = fit_args.get("shard")
+        if shard is not None:
+            from ..prodafit import check_shard
+            val = fit_args.get("val_loader") if fit_args.get("val_loader") is not None else fit_args.get("val")
+            check_shard(who, shard, self.prompt_learner.tokenized_prompts.shape[0], self.prompt_learner.ctx.shape[0], bool(fit_args.get("one_call", False)),
+                        val, fit_args.get("final_model", "last_step"))
         _fit.validation_set(who, self.clip_model, fit_args)
         fit_args.setdefault("logit_scale", math.log(self.scale))
         dynamic = fit_args.get("grad_scale") == "dynamic"
@@ -129,7 +140,8 @@ class CustomCLIP(nn.Module):
             E = int(self.clip_model.geometry.embed_dim)
             watch = _fit.split_monitor_args(who, fit_args, ids.shape[0], E)
             val_class_chunk = fit_args.pop("val_class_chunk", None)
-            state = ProDAFitState(self.clip_model, ids, ctx.detach(), **fit_args)
+            from ..coopfit import shard_states
+            state = shard_states(lambda sh: ProDAFitState(self.clip_model, ids, ctx.detach(), **dict(fit_args, shard=sh)), shard)
             state.val_class_chunk = val_class_chunk
             losses, monitor = _fit.run_with_transform(who, state, self.clip_model, ids.shape[0], E, train_loader, transform, epochs, lr, run, watch)
             fitted = _fit.pack(state.best_params() if watch["final_model"] == "best_val" else state.ctx, losses)

@@ -1556,6 +1556,51 @@ int clipmi_proda_train_step_scaled(clipmi_model* m, const clipmi_text_dgrad* wt,
                                    float weight_decay, int nesterov, float* losses, float* grad_out, void* workspace, size_t workspace_bytes,
                                    void* stash, size_t stash_bytes, clipmi_stream_t stream);
 
+/* The class-sharded ProDA fit (DESIGN.md "Class-sharded ProDA fit"): G ranks, rank r owning the contiguous classes [c_lo, c_hi) of the
+ * balanced split of C (the first C mod G ranks one more, C >= G) with all Pb prompts of each, and the no-class prompts of the contexts
+ * [p_lo, p_hi) the same split of P gives it (P >= G): C_r Pb + P_r prompts, the class prompts first.  Two all-gathers per step.  fp32, fixed
+ * summation orders, no atomics; with G = 1 every chain is clipmi_proda_ctx_step's (clipmi_proda_ctx_step_scaled's), bit for bit.  These
+ * exports are additive: the ABI version does not change with them.
+ *
+ * clipmi_proda_embed_shard: clipmi_proda_embed for one rank.  base, name_lens and cls_eot start at the rank's first class and C is the
+ *   number of its classes (>= 1); ctx [P, n_ctx, D], sel and pos are the whole collection's; the no-class prompts written are those of the
+ *   contexts p0 .. p0 + Pn - 1.  prompts [C Pb + Pn, Lc, D], eot [C Pb + Pn].  With C the whole class set, p0 = 0 and Pn = P it is
+ *   clipmi_proda_embed.
+ * clipmi_proda_shard_compact: gathered fp32 [G, RB, E], RB = ceil(C / G) Pb + ceil(P / G), block r holding rank r's tower output as it lies
+ *   -- C_r Pb class rows, then P_r no-class rows -- and padding behind them that is never read; out fp32 [C Pb + P, E] in the unsharded
+ *   order clipmi_proda_head takes.  One launch.
+ * clipmi_proda_ctx_partial: a rank's send block, fp32 [(Pb + Pn), n_ctx, D], from its own d_embed fp32 [(C Pb + Pn) L, D] (C, Pn, name_lens:
+ *   the rank's own).  Slot q < Pb: for context vector j of context sel[q] the sum over the rank's classes c = 0 .. C-1 (ascending, from
+ *   0) of the row of prompt c Pb + q that holds it (clipmi_proda_embed's row rule), unscaled; a selection outside [0, P) gives zeros and
+ *   is never an index.  Slot Pb + i: row 1 + j of the rank's i-th no-class prompt, copied.  Ranks pad the block to (Pb + ceil(P / G))
+ *   n_ctx D floats -- 4 (Pb + ceil(P / G)) n_ctx D bytes per rank and gather.  One launch; 16-byte accesses when D is a multiple of 4 and
+ *   both pointers are 16-byte aligned, scalar ones otherwise.
+ * clipmi_proda_ctx_step_gathered: the gathered send blocks, rank r's at gathered + r * rank_stride (elements, >= (Pb + ceil(P / G))
+ *   n_ctx D).  The gradient of ctx[p, j, d]: if p == sel[q], the G class sums of slot q added in RANK order from 0; then -- always, and
+ *   last -- the no-class row of the rank that owns p; times 1 / grad_scale.  Then clipmi_proda_ctx_step's SGD rule with the same optional
+ *   outputs and NULL conventions.  The padding of a block is never read.  Every rank given the same blocks writes the same bits.  One
+ *   launch, one thread per four elements when n_ctx D and rank_stride are multiples of 4 and every pointer is 16-byte aligned (a block of
+ *   n_ctx D floats that is no multiple of 4 floats puts the streams on different 16-byte phases), per element otherwise.
+ * clipmi_proda_ctx_reduce_gathered_scaled: the same sum under the scaler's rule, as clipmi_proda_ctx_step_scaled is
+ *   clipmi_proda_ctx_step's: one thread per element, workgroups of 256, times 1 / state->scale into the workspace and grad_out with one
+ *   integer flag per workgroup; clipmi_ctx_step_scaled's second and third launches follow unchanged.  Every rank reduces the same
+ *   gathered bytes, so every rank takes the same decision and holds the same state block.  workspace (256-byte aligned):
+ *   clipmi_proda_ctx_step_scaled_workspace_bytes(P, D, n_ctx) bytes.  Every check precedes the first launch. */
+int clipmi_proda_embed_shard(const void* base, const void* nc_base, int dtype, const float* ctx, const int32_t* sel, const int32_t* pos,
+                             const int32_t* name_lens, const int32_t* cls_eot, float* prompts, int32_t* eot, int C, int Pb, int P, int p0, int Pn,
+                             int L, int Lc, int D, int n_ctx, clipmi_stream_t stream);
+int clipmi_proda_shard_compact(const float* gathered, float* out, int C, int Pb, int P, int G, int64_t E, clipmi_stream_t stream);
+int clipmi_proda_ctx_partial(const float* d_embed, float* partial, const int32_t* sel, const int32_t* pos, const int32_t* name_lens, int C,
+                             int Pb, int P, int Pn, int L, int D, int n_ctx, clipmi_stream_t stream);
+int clipmi_proda_ctx_step_gathered(const float* gathered, int G, int64_t rank_stride, float* ctx, float* buf, float* grad_out,
+                                   const int32_t* sel, int Pb, int P, int D, int n_ctx, float grad_scale, const float* lr, int first_step,
+                                   float momentum, float dampening, float weight_decay, int nesterov, clipmi_stream_t stream);
+int clipmi_proda_ctx_reduce_gathered_scaled(const float* gathered, int G, int64_t rank_stride, float* ctx, float* buf, float* grad_out,
+                                            const int32_t* sel, int Pb, int P, int D, int n_ctx, clipmi_scaler_state* state,
+                                            float growth_factor, float backoff_factor, int growth_interval, const float* lr, float momentum,
+                                            float dampening, float weight_decay, int nesterov, void* workspace, size_t workspace_bytes,
+                                            clipmi_stream_t stream);
+
 /* CoCoOp's context and meta-net trained on the same frozen-tower backward (reference trainers/classification/cocoop.py:153-202, 259-278;
  * csrc/cocoop_train.hip, DESIGN.md "CoCoOp fit").  The five learned tensors live in ONE fp32 block of clipmi_cocoop_block_floats(n_ctx, D,
  * E, H) floats laid out as ctx [n_ctx, D] | W1 [H, E] | b1 [H] | W2 [D, H] | b2 [D] (D the text width, E the embedding width, H the
