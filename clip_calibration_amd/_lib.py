@@ -307,6 +307,11 @@ _SIGNATURES = {
     "clipmi_cocoop_reduce_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "clipmi_cocoop_reduce": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _sz, _vp]),
     "clipmi_cocoop_step": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _f, _f, _f, _i, _vp]),
+    "clipmi_cocoop_embed_classes": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "clipmi_cocoop_shard_compact": (_i, [_vp, _vp, _i, _i, _i, _i, _i64, _vp]),
+    "clipmi_cocoop_shard_rows": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "clipmi_cocoop_dcs_partial": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "clipmi_cocoop_reduce_gathered": (_i, [_vp, _i, _i64, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _sz, _vp]),
     "clipmi_cocoop_train_step_bytes": (_sz, [_vp, _i, _i, _i, _i, _i]),
     "clipmi_cocoop_train_step": (_i, [_vp, C.POINTER(TextDgrad), _vp, _i, _vp, _vp, _i, _i, _vp, _i, _i, _vp, _i64, _vp, _i, _f, _f, _vp, _i, _f, _f, _f, _i,
                                       _vp, _vp, _vp, _sz, _vp, _sz, _vp]),

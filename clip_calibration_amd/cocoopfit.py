@@ -26,8 +26,20 @@ the reference behind them; each is an argument.
 "amp"`` branch (cocoop.py:249, ``torch.cuda.amp.GradScaler``) as ``coopfit`` has it: the scale lives in a block on the device, a step whose
 gradient block holds an inf or a NaN changes neither the parameters nor the momentum block, and the scale backs off and grows again.  No
 step reads anything back; ``CoCoOpFitState.scaler_state()`` does, once.  DESIGN.md "Dynamic loss scale for the block fits".  The
-reference's ``autocast`` casts differ from this path's fixed fp16 operand points (unverified).  Not covered: ``nn.DataParallel`` over the text encoder
-(one process drives one GPU), class-token positions other than ``end``.
+reference's ``autocast`` casts differ from this path's fixed fp16 operand points (unverified).  Not covered: class-token positions other
+than ``end`` (the reference has none).
+
+``shard=coopfit.Shard(world, rank, gather)`` on ``CoCoOpFitState``, ``fit_prompt_learner`` and ``gradients`` is the class-sharded fit, in
+the place of the reference's ``nn.DataParallel`` over the text encoder (cocoop.py:252-257): one process per GPU, rank r of G running the
+tower over the ``B x C_r`` prompts of its contiguous classes ``coopfit.shard_classes(C, G, r)`` -- the stash and the workspace are sized by
+``B x C_r`` (``stash_bytes``).  The meta-net, the head, the meta-net's backward and the optimiser step run replicated on every rank; two
+all-gathers per step move the raw text features (``B x ceil(C / G)`` rows per rank) and the ranks' partial sums ``[B, n_ctx, D]``
+(clipmi_cocoop_dcs_partial), which clipmi_cocoop_reduce_gathered adds in rank order: every rank then holds the same gradient block bit
+for bit, with no all-reduce and no float atomic, and steps its replicated master block with the unsharded state's own step.  So SGD,
+``optimizer="adam" | "adamw"`` and ``grad_scale="dynamic"`` all work under the shard, and every rank takes the same skip-or-apply
+decision.  Every rank is given the same batch.  With one rank the sharded step gives the unsharded step's bits.  Refused under ``shard``,
+by name and before any device call: ``C < G``, ``one_call=True``, ``val=`` / ``val_loader=`` / ``final_model="best_val"`` /
+``validate``, and ``gradients``' operand statistics.  DESIGN.md "Class-sharded CoCoOp fit".
 
 Validation: ``fit_prompt_learner(val=(val_features, val_labels), val_batch_size=, val_bins=, final_model="last_step" | "best_val",
 val_criterion=, return_monitor=)`` scores the parameters behind every epoch on the device and keeps the block of the best epoch in a
@@ -48,9 +60,10 @@ import torch
 
 from . import _lib, fitloop, fitmonitor, ops
 from ._lib import check, lib
-from .coopfit import DYNAMIC, MAX_LIVE_ROWS, _DT, _AdamBlock, _BlockScaler, _Tower, _check_batch, _check_grad_scale, _is_dynamic, _live_rows, _scale_args, operand_stats_dict
+from .coopfit import (DYNAMIC, MAX_LIVE_ROWS, _DT, Shard, _AdamBlock, _BlockScaler, _Tower, _check_batch, _check_grad_scale, _drive, _file_state, _is_dynamic,
+                      _live_rows, _run_phases, _scale_args, _world_states, operand_stats_dict, shard_classes, shard_states)
 from .coopfit import _check_prompts as _check_coop_prompts
-from .fitloop import _need_gpu, steps_per_epoch
+from .fitloop import _host_int_array, _need_gpu, steps_per_epoch
 
 # 2^10, measured on the ViT-B/16 text geometry with synthetic weights at the reference's batch of 1 (profiles/cocoopfit_parity.txt,
 # "grad_scale"): with one image dz is not divided down by a batch, and CoOp's 2^12 leaves the largest fp16 dgrad-GEMM operand only 2^1.9
@@ -101,12 +114,14 @@ def _master_block(params, n_ctx: int, D: int, E: int, H: int, dev) -> torch.Tens
 
 
 class _CoCoOpTower(_Tower):
-    """``coopfit._Tower`` over CoCoOp's N = B C assembled prompts of one batch size, with the meta-net's kept outputs."""
+    """``coopfit._Tower`` over CoCoOp's N = B C assembled prompts of one batch size, with the meta-net's kept outputs.  ``sharded``: a
+    rank of the class-sharded fit -- ``tokenized_prompts`` and ``n_cls`` are its own classes' (one is enough), ``last_eot`` the whole
+    prompt set's."""
 
-    def __init__(self, who, clip_model, tokenized_prompts, n_cls, B, n_ctx, H, last_eot, seq_rows):
+    def __init__(self, who, clip_model, tokenized_prompts, n_cls, B, n_ctx, H, last_eot, seq_rows, sharded=False):
         super().__init__(who, clip_model, tokenized_prompts, n_cls * B, n_ctx, False, last_eot, seq_rows)
         dev = clip_model.device
-        self.n_cls, self.B, self.H = n_cls, B, H
+        self.n_cls, self.B, self.H, self.sharded = n_cls, B, H, sharded
         self.N = self.C                       # _Tower sizes workspace, stash, text and d_embed by the number of prompts
         self.cls_eot = self.eot               # of the ids: every image's prompt of a class keeps the class's EOT row
         self.prompts = torch.empty(self.N, self.Lc, self.D, dtype=torch.float32, device=dev)
@@ -117,7 +132,10 @@ class _CoCoOpTower(_Tower):
     def forward(self, views: Dict[str, torch.Tensor], features: torch.Tensor) -> torch.Tensor:
         m = self.model
         ops.cocoop_meta(features, *(views[k] for k in NAMES[1:]), out=self.meta)
-        ops.cocoop_embed(self.base, views["ctx"], self.meta[2], self.cls_eot, self.rows, self.prompts, self.eot)
+        if self.sharded:
+            ops.cocoop_embed_classes(self.base, views["ctx"], self.meta[2], self.cls_eot, 0, self.n_cls, self.rows, self.prompts, self.eot)
+        else:
+            ops.cocoop_embed(self.base, views["ctx"], self.meta[2], self.cls_eot, self.rows, self.prompts, self.eot)
         with m._launch_lock:
             check(lib.clipmi_text_encoder_train(m._handle, self.prompts.data_ptr(), _lib.F32, None, 0, 0, self.eot.data_ptr(), self.N, self.rows, None,
                                                 self.text.data_ptr(), self.ws.data_ptr(), self.ws.numel(), self.stash.data_ptr(), self.stash.numel(),
@@ -137,15 +155,53 @@ class _CoCoOpTower(_Tower):
         return self.step_ws
 
 
+def check_shard(who: str, shard, n_cls: int, one_call: bool = False, val=None, final_model: str = "last_step") -> None:
+    """What the class-sharded CoCoOp fit refuses, each by name, before any device call.  Both loss scales and the three optimisers pass:
+    every rank steps the same replicated block with the same gradient."""
+    if not isinstance(shard, Shard):
+        raise ValueError(f"{who}: shard must be a coopfit.Shard(world, rank, gather), got {type(shard).__name__}")
+    if n_cls < shard.world:
+        raise ValueError(f"{who}: shard: C={n_cls} classes cannot be split over world={shard.world} ranks (C < G: a rank would own no class)")
+    if one_call:
+        raise ValueError(f"{who}: shard has no one-call step (one_call=True); the sharded step is the separate calls")
+    if val is not None or final_model == "best_val":
+        raise ValueError(f"{who}: shard has no validation: val=, val_loader= and final_model='best_val' are not sharded")
+
+
+def stash_bytes(clip_model, tokenized_prompts, batch: int, seq_rows: Optional[int] = None, world: int = 1, rank: int = 0):
+    """``(workspace bytes, stash bytes)`` of the training tower of one step on ``batch`` images, as clipmi_text_train_bytes reports them
+    for the ``batch x C_r`` prompts of ``rank`` of ``world`` under the live-row cut of the WHOLE prompt set (``world=1``: the unsharded
+    ``batch x C``).  The model must be bound to its GPU; nothing is launched."""
+    who = "stash_bytes"
+    ids = _host_int_array(who, tokenized_prompts, "tokenized_prompts")
+    if isinstance(batch, bool) or int(batch) != batch or batch < 1:
+        raise ValueError(f"{who}: batch={batch} must be an integer >= 1")
+    lo, hi = shard_classes(int(ids.shape[0]), int(world), int(rank))
+    rows = _live_rows(clip_model, int(ids.argmax(axis=-1).max()), seq_rows)
+    clip_model._ensure_bound()
+    wsb, stb = C.c_size_t(0), C.c_size_t(0)
+    check(lib.clipmi_text_train_bytes(clip_model._handle, int(batch) * (hi - lo), rows, C.byref(wsb), C.byref(stb)), "clipmi_text_train_bytes")
+    return wsb.value, stb.value
+
+
 def gradients(clip_model, tokenized_prompts, params, features: torch.Tensor, labels, logit_scale: float = 4.6052,
-              grad_scale: float = DEFAULT_GRAD_SCALE, seq_rows: Optional[int] = None, return_parts: bool = False, return_operand_stats: bool = False):
+              grad_scale: float = DEFAULT_GRAD_SCALE, seq_rows: Optional[int] = None, return_parts: bool = False, return_operand_stats: bool = False,
+              shard: Optional[Shard] = None):
     """``(loss, grads)`` of CoCoOp's training loss (module docstring) on the GPU: loss fp32 [1], grads a dict of the five fp32 gradients
     under the names of ``params`` (the reference's ``state_dict`` names).  ``tokenized_prompts`` [C, context_length]: the ids of
     ``"X .. X name."``; ``features`` fp32 [B, E] raw image features (the rows may be a column slice).  ``return_parts`` adds a dict:
     ``text`` (raw text features fp32 [B C, E]), ``x_n``, ``hid``, ``pi`` and the row losses ``rows``; ``return_operand_stats`` the
-    dict ``coopfit.context_gradient`` returns."""
+    dict ``coopfit.context_gradient`` returns.
+
+    ``shard``: the gradient block the class-sharded step would apply (module docstring), reduced over the ranks in rank order -- the same
+    bits on every rank; ``text`` is then the gathered, compacted matrix.  Under a ``LocalGather`` the call runs all ranks.  The operand
+    statistics are per rank and are refused."""
     who = "gradients"
     Cn, n_ctx, H, last = _check_prompts(who, clip_model, tokenized_prompts, params, seq_rows)
+    if shard is not None:
+        check_shard(who, shard, Cn)
+        if return_operand_stats:
+            raise ValueError(f"{who}: shard returns no operand statistics (return_operand_stats=True)")
     if _is_dynamic(who, grad_scale):
         raise ValueError(f"{who}: grad_scale={DYNAMIC!r} belongs to a fit (CoCoOpFitState, fit_prompt_learner); one gradient needs a number")
     gs = _check_grad_scale(who, grad_scale)
@@ -155,6 +211,16 @@ def gradients(clip_model, tokenized_prompts, params, features: torch.Tensor, lab
     _need_gpu(features, "features")
     if features.dtype != torch.float32 or features.stride(1) != 1:
         raise TypeError(f"{who}: features must be fp32 with unit column stride")
+    if shard is not None:     # the sharded step's phases with a report in the step's place
+        make = lambda sh: CoCoOpFitState(clip_model, tokenized_prompts, params, logit_scale, 0.0, 0.0, 0.0, False, gs, seq_rows, shard=sh)
+        state = shard_states(make, shard)
+        states = _world_states(shard, state, who)
+        reports = [{} for _ in states]
+        _run_phases([s._shard_phases(features, labels_d, None, torch.empty(1, dtype=torch.float32, device=features.device), True, r)
+                     for s, r in zip(states, reports)])
+        report = reports[states.index(state)]
+        grads = {k: v.clone() for k, v in ops.cocoop_block_views(report["grad"], n_ctx, state.D, E, H).items()}
+        return (report["loss"], grads) + (({k: report[k] for k in ("text", "x_n", "hid", "pi", "rows")},) if return_parts else ())
     tower = _CoCoOpTower(who, clip_model, tokenized_prompts, Cn, features.shape[0], n_ctx, H, last, seq_rows)
     dev = features.device
     views = ops.cocoop_block_views(_master_block(params, n_ctx, tower.D, E, H, dev), n_ctx, tower.D, E, H)
@@ -180,11 +246,17 @@ class CoCoOpFitState(fitmonitor.Monitored):
 
     def __init__(self, clip_model, tokenized_prompts, params, logit_scale: float = 4.6052, momentum: float = 0.9,
                  dampening: float = 0.0, weight_decay: float = 5e-4, nesterov: bool = False, grad_scale: float = DEFAULT_GRAD_SCALE,
-                 seq_rows: Optional[int] = None, scaler: Optional[dict] = None, optimizer: str = "sgd", betas=(0.9, 0.999), eps: float = 1e-8):
+                 seq_rows: Optional[int] = None, scaler: Optional[dict] = None, optimizer: str = "sgd", betas=(0.9, 0.999), eps: float = 1e-8,
+                 shard: Optional[Shard] = None):
         """``optimizer``: "sgd" (``momentum``, ``dampening``, ``nesterov``), "adam" or "adamw" (``betas``, ``eps``;
-        ``weight_decay`` keeps the fit's default of 5e-4 under all three -- torch's AdamW default of 1e-2 is NOT taken over)."""
+        ``weight_decay`` keeps the fit's default of 5e-4 under all three -- torch's AdamW default of 1e-2 is NOT taken over).
+        ``shard``: this state is one rank of the class-sharded fit (module docstring).  It holds the whole master block and runs the
+        tower over its own classes; both loss scales and all three optimisers work under it."""
         who = "CoCoOpFitState"
         self.C, self.n_ctx, self.H, self._last = _check_prompts(who, clip_model, tokenized_prompts, params, seq_rows)
+        self.shard = shard
+        if shard is not None:
+            check_shard(who, shard, self.C)
         self.dynamic, self.grad_scale, self.scaler = _scale_args(who, grad_scale, scaler)
         self.optimizer, momentum, dampening, nesterov, betas = fitloop.check_optimizer(who, optimizer, momentum, dampening, nesterov, weight_decay, betas, eps)
         self.scale = fitloop.exp_logit_scale(who, logit_scale)
@@ -204,6 +276,10 @@ class CoCoOpFitState(fitmonitor.Monitored):
         self._val = None            # what a validation keeps between epochs: the inference operands and one workspace per chunk size
         self.val_stream_f16 = True  # trainers.cocoop.CustomCLIP's text_stream_f16: validation runs the tower as that forward does
         self.val_batch_size = None  # validate's chunk when its argument is None (None: the largest training batch seen)
+        if shard is not None:       # the tower over the rank's own classes; the live-row cut is the full prompt set's
+            self.lo, self.hi = shard_classes(self.C, shard.world, shard.rank)
+            self._own_ids = _host_int_array(who, tokenized_prompts, "tokenized_prompts")[self.lo:self.hi]
+            _file_state(shard, self)
 
     def scaler_state(self) -> dict:
         """The dynamic scale's block as ``dict(scale, growth_tracker, skipped_steps, applied_steps, found_inf)`` (``found_inf``: of the
@@ -256,6 +332,8 @@ class CoCoOpFitState(fitmonitor.Monitored):
         parameters, the momentum block, the scaler block and the training stash are not touched.  Without ``start_monitor`` the history
         starts with ``epoch + 1`` slots of 10 bins and no selection."""
         who = "CoCoOpFitState.validate"
+        if self.shard is not None:
+            raise ValueError(f"{who}: shard has no validation (the sharded fit scores nothing between epochs)")
         mon, m = self._monitor_for(epoch), self.model
         epoch = mon.slot(who, epoch)
         if val_batch_size is None:
@@ -296,9 +374,59 @@ class CoCoOpFitState(fitmonitor.Monitored):
         return collections.OrderedDict(self._views)
 
     def tower(self, B: int) -> _CoCoOpTower:
-        if B not in self._towers:
+        if B not in self._towers and self.shard is None:
             self._towers[B] = _CoCoOpTower("CoCoOpFitState.step", self.model, self.ids, self.C, B, self.n_ctx, self.H, self._last, self.seq_rows)
+        elif B not in self._towers:
+            self._towers[B] = self._shard_tower(B)
         return self._towers[B]
+
+    # ---- the class-sharded step (csrc/cocoop_train.hip, DESIGN.md "Class-sharded CoCoOp fit")
+
+    def _shard_tower(self, B: int) -> _CoCoOpTower:
+        """The rank's tower for batches of ``B`` with the send and receive blocks of the step's two gathers, made once per batch size.
+        The tower writes its text features straight into the first rows of the padded send block; the padding is moved and never read."""
+        G, Cr = self.shard.world, self.hi - self.lo
+        t = _CoCoOpTower("CoCoOpFitState.step", self.model, self._own_ids, Cr, B, self.n_ctx, self.H, self._last, self.seq_rows, sharded=True)
+        f32 = dict(dtype=torch.float32, device=self.block.device)
+        rows = B * ops.cocoop_shard_pad(self.C, G)
+        t.send_text = torch.empty(rows, t.E, **f32)
+        t.text = t.send_text[:t.N]
+        t.all_text = torch.empty(G, rows * t.E, **f32)
+        t.full_text = torch.empty(B * self.C, t.E, **f32)
+        t.own_d_text = torch.empty(t.N, t.E, **f32)
+        t.send_part = torch.empty(B, t.n_ctx, t.D, **f32)
+        t.all_part = torch.empty(G, B * t.n_ctx * t.D, **f32)
+        return t
+
+    def _shard_phases(self, features, labels_d, lr_d, loss, first: bool, report: Optional[dict] = None):
+        """One sharded step as phases, a ``yield`` behind every gather.  ``report``: a dict that receives the reduced gradient block,
+        the loss and the parts ``gradients`` returns INSTEAD of a step: no block of the state is touched."""
+        B, sh, st = int(features.shape[0]), self.shard, ops._stream()
+        t = self.tower(B)
+        gs = 1.0 if self.dynamic else self.grad_scale
+        t.forward(self._views, features)                                   # the meta-net over all B rows, then the rank's own B C_r prompts
+        sh.gather(t.send_text, t.all_text, t.send_text.numel() * 4, st)
+        yield
+        text = ops.cocoop_shard_compact(t.all_text, B, self.C, t.E, t.full_text)
+        head = ops.cocoop_head(features, labels_d, text, self.scale, gs, loss, want_rows=report is not None)
+        own = ops.cocoop_shard_rows(head[1], B, self.lo, self.hi, t.own_d_text)   # the rank's own rows of the replicated d_text
+        if self.dynamic:
+            ops.grad_scale_rows(own, self._scaler.block)
+        ops.cocoop_dcs_partial(t.backward(own), B, t.n_cls, t.n_ctx, t.send_part)
+        sh.gather(t.send_part, t.all_part, t.send_part.numel() * 4, st)
+        yield
+        grad = ops.cocoop_reduce_gathered(t.all_part, t.meta[0], t.meta[1], self._views[NAMES[3]], t.n_ctx, gs, t.grad)
+        if report is not None:
+            report.update(grad=grad.clone(), loss=loss, text=text.clone(), x_n=t.meta[0].clone(), hid=t.meta[1].clone(), pi=t.meta[2].clone(),
+                          rows=head[2])
+            return
+        sgd = (self.momentum, self.dampening, self.weight_decay, self.nesterov)
+        if self._adam is not None:
+            self._adam.step(grad, self.block, lr_d, 1.0, self._scaler)
+        elif self.dynamic:
+            self._scaler.step(grad, self.block, self.buf, lr_d, *sgd)
+        else:
+            ops.cocoop_step(grad, self.block, self.buf, lr_d, self.n_ctx, self.D, self.E, self.H, first, *sgd)
 
     def step(self, features: torch.Tensor, labels, lr, want_loss: bool = False, one_call: bool = False) -> Optional[torch.Tensor]:
         """One optimiser step on the batch ``features`` fp32 [B, E] and ``labels`` [B] at the rate ``lr``, as ``CoOpFitState.step`` takes
@@ -309,19 +437,32 @@ class CoCoOpFitState(fitmonitor.Monitored):
         device whether the step is applied (one call: clipmi_cocoop_train_step_scaled); a skipped step still counts in ``steps`` and still
         returns its loss; whether it was applied is in ``scaler_state()``.  Under ``optimizer="adam" | "adamw"`` the reduce leaves the
         block's gradient as ``gradients`` returns it and clipmi_block_step_adam applies it (clipmi_block_step_adam_scaled under the dynamic
-        scale); ``one_call`` is then refused: the one-call steps stay SGD."""
+        scale); ``one_call`` is then refused: the one-call steps stay SGD.  Under ``shard`` every rank makes this call with the same
+        batch; under a ``LocalGather`` the first state that steps drives all the world's states (``one_call`` is refused)."""
         who = "CoCoOpFitState.step"
+        if one_call and self.shard is not None:
+            raise ValueError(f"{who}: shard has no one-call step (one_call=True); the sharded step is the separate calls")
         if one_call and self._adam is not None:
             raise ValueError(f"{who}: one_call=True with optimizer={self.optimizer!r}: the one-call steps stay SGD")
+        states = None
+        if self.shard is not None:
+            states = _world_states(self.shard, self, who)
+            _drive(self.shard, self, who)
         labels_d = _check_batch(who, features, labels, self.C, self.E)
         _need_gpu(features, "features")
         if features.dtype != torch.float32 or features.stride(1) != 1:
             raise TypeError(f"{who}: features must be fp32 with unit column stride")
         dev = features.device
         lr_d = ops._dev(fitloop.lr_operand(lr, dev), "lr", (torch.float32,))
-        t, m, first = self.tower(int(features.shape[0])), self.model, self.steps == 0
-        sgd = (self.momentum, self.dampening, self.weight_decay, self.nesterov)
+        first = self.steps == 0
         loss = torch.empty(1, dtype=torch.float32, device=dev)
+        if states is not None:
+            _run_phases([s._shard_phases(features, labels_d, lr_d, loss if s is self else torch.empty_like(loss), first) for s in states])
+            for s in states:
+                s.steps += 1
+            return loss if want_loss else None
+        t, m = self.tower(int(features.shape[0])), self.model
+        sgd = (self.momentum, self.dampening, self.weight_decay, self.nesterov)
         if self._adam is not None:
             gs = 1.0 if self.dynamic else self.grad_scale
             text = t.forward(self._views, features)
@@ -392,7 +533,8 @@ def fit_prompt_learner(features: torch.Tensor, labels, clip_model, tokenized_pro
                        dampening: float = 0.0, weight_decay: float = 5e-4, nesterov: bool = False, grad_scale: float = DEFAULT_GRAD_SCALE, seq_rows: Optional[int] = None,
                        lr_per_epoch: Optional[Sequence[float]] = None, order=None, drop_last: bool = False, return_history: bool = False,
                        scaler: Optional[dict] = None, val=None, val_batch_size: Optional[int] = None, val_bins: int = 10,
-                       final_model: str = "last_step", val_criterion: str = "accuracy", return_monitor: bool = False, val_stream_f16: bool = True, optimizer: str = "sgd", betas=(0.9, 0.999), eps: float = 1e-8):
+                       final_model: str = "last_step", val_criterion: str = "accuracy", return_monitor: bool = False, val_stream_f16: bool = True, optimizer: str = "sgd", betas=(0.9, 0.999), eps: float = 1e-8,
+                       shard: Optional[Shard] = None):
     """Train CoCoOp's prompt learner on cached ``features`` fp32 [N, E] and ``labels`` [N], starting from ``params`` (a dict of the five
     tensors, not modified; None = ``init_params(clip_model, n_ctx)``).  The loop and its arguments are ``coopfit.fit_context``'s:
     ``epochs`` passes of ``torch.optim.SGD`` over batches of ``batch_size``, ``lr_per_epoch`` (None: ``cosine_warmup_schedule``),
@@ -413,7 +555,11 @@ def fit_prompt_learner(features: torch.Tensor, labels, clip_model, tokenized_pro
 
     ``optimizer``, ``betas``, ``eps``: "sgd" (the default; ``momentum``, ``dampening``, ``nesterov``), "adam" or
     "adamw", as ``coopfit.fit_context`` takes them; ``weight_decay`` keeps this fit's default of 5e-4 under all three (torch's AdamW
-    default of 1e-2 is NOT taken over).  DESIGN.md "Adam steps for the prompt fits"."""
+    default of 1e-2 is NOT taken over).  DESIGN.md "Adam steps for the prompt fits".
+
+    ``shard=Shard(world, rank, gather)``: the class-sharded fit (module docstring).  Every rank makes this call with the same arguments
+    -- the whole prompt set, all features -- and returns the same tensors.  With a ``LocalGather`` the one call runs all ``world`` shard
+    states in this process.  Both loss scales and all three optimisers work; validation and ``final_model="best_val"`` are refused."""
     who = "fit_prompt_learner"
     fitmonitor.check_args(who, val, val_bins, final_model, val_criterion)
     if val is not None and val_batch_size is not None:
@@ -421,6 +567,8 @@ def fit_prompt_learner(features: torch.Tensor, labels, clip_model, tokenized_pro
     if params is None:
         params = init_params(clip_model, n_ctx)
     Cn, n_ctx, H, _ = _check_prompts(who, clip_model, tokenized_prompts, params, seq_rows)
+    if shard is not None:
+        check_shard(who, shard, Cn, False, val, final_model)
     E, D = int(clip_model.geometry.embed_dim), int(clip_model.ln_final.weight.shape[0])
     if not isinstance(features, torch.Tensor) or features.dim() != 2 or features.shape[0] < 1 or features.shape[1] != E:
         raise ValueError(f"{who}: features must be a [N >= 1, E = {E}] tensor")
@@ -439,8 +587,9 @@ def fit_prompt_learner(features: torch.Tensor, labels, clip_model, tokenized_pro
         out = collections.OrderedDict((k, params[k].detach().to(torch.float32).clone().to(dev if features.is_cuda else "cpu")) for k in NAMES)
         return fitmonitor.pack(out, np.zeros(0, np.float32), fitmonitor.empty_monitor(val_bins), return_history, return_monitor)
     _need_gpu(features, "features")
-    state = CoCoOpFitState(clip_model, tokenized_prompts, params, logit_scale, momentum, dampening, weight_decay, nesterov, grad_scale, seq_rows,
-                           scaler, optimizer, betas, eps)
+    make = lambda sh: CoCoOpFitState(clip_model, tokenized_prompts, params, logit_scale, momentum, dampening, weight_decay, nesterov, grad_scale, seq_rows,
+                                     scaler, optimizer, betas, eps, shard=sh)
+    state = shard_states(make, shard)     # under a LocalGather all the world's states live here; a step of one steps them all
     end_epoch = None
     if val is not None:
         _need_gpu(vf, "val_features")

@@ -13,6 +13,8 @@
 //   cocoop_dhid_kernel         dhid[b, h] = [hid > 0] sum_d W2[d, h] dpi[b, d]
 //   cocoop_dw1_kernel          db1, dW1
 //   cocoop_step_kernel         sgd_element_fma over the parameter block [ctx | W1 | b1 | W2 | b2]
+//   cocoop_shard_compact_kernel, cocoop_shard_rows_kernel, cocoop_dcs_partial_kernel, cocoop_dcs_gathered_kernel
+//                              the class-sharded step's copies and sums (below, "the class-sharded step")
 // Notation: N = B C prompts, prompt b C + c is image b with class c; H the meta-net's hidden width.  No float atomics and no workgroup waits
 // for another: the same inputs give the same bits.
 #include <cmath>
@@ -121,10 +123,10 @@ __global__ __launch_bounds__(THREADS) void cocoop_embed_kernel(const T* __restri
 }
 
 int check_embed(const char* who, const void* base, int dtype, const float* ctx, const float* pi, const int32_t* cls_eot, const float* out, const int32_t* eot,
-                int B, int C, int L, int Lc, int D, int n_ctx) {
+                int B, int C, int L, int Lc, int D, int n_ctx, int min_c = 2) {
   CLIPMI_REQUIRE(base && ctx && pi && cls_eot && out && eot, CLIPMI_ERR_ARG, "%s: null pointer", who);
   CLIPMI_REQUIRE(dtype == CLIPMI_F16 || dtype == CLIPMI_F32, CLIPMI_ERR_ARG, "%s: bad dtype %d", who, dtype);
-  CLIPMI_REQUIRE(B >= 1 && C >= 2, CLIPMI_ERR_SHAPE, "%s: B=%d (>= 1), C=%d (>= 2)", who, B, C);
+  CLIPMI_REQUIRE(B >= 1 && C >= min_c, CLIPMI_ERR_SHAPE, "%s: B=%d (>= 1), C=%d (>= %d)", who, B, C, min_c);
   CLIPMI_REQUIRE(D >= 4 && D % 4 == 0, CLIPMI_ERR_SHAPE, "%s: D=%d (a multiple of 4)", who, D);
   CLIPMI_REQUIRE(L >= 1 && L <= Lc && n_ctx >= 1 && 1 + n_ctx <= L, CLIPMI_ERR_SHAPE, "%s: n_ctx=%d, L=%d of Lc=%d rows (SOS and the context must fit the live rows)",
                  who, n_ctx, L, Lc);
@@ -402,6 +404,142 @@ int enqueue_step(const float* grad, float* params, float* buf, int n_ctx, int D,
   return check_launch("cocoop_step_kernel");
 }
 
+// ------------------------------------------------------------------------------ the class-sharded step (DESIGN.md "Class-sharded CoCoOp fit")
+// Rank r of G owns the classes [lo, hi) the balanced split gives it (shard_owner, train_rules.h) and runs the tower over its B C_r prompts,
+// image-major: prompt b C_r + (c - lo) is image b with class c.  Its rows are no contiguous range of the unsharded [B, C, .], hence the copies.
+//   cocoop_shard_compact_kernel   the gathered text features [G, >= B ceil(C / G), E] -> [B, C, E]
+//   cocoop_shard_rows_kernel      rows {b C + c : lo <= c < hi} of d_text [B, C, E] -> [B C_r, E]
+//   cocoop_dcs_partial_kernel     cocoop_dcs_kernel's sum over the rank's own classes, c ascending from 0.f, unscaled
+//   cocoop_dcs_gathered_kernel    the G partials added in rank order from 0.f, times 1 / grad_scale once, into the reduce workspace's dcs
+// With G = 1 the chain is cocoop_dcs_kernel's: (0 + the classes ascending) = p, 0.f + p = p (p is never -0: it started from +0), p * inv_scale.
+// V = 4: 16-byte accesses; V = 1: scalar.
+template <int V>
+__device__ __forceinline__ void ldv(const float* __restrict__ p, float (&x)[V]) {
+  if constexpr (V == 4) {
+    const f32x4 v = *reinterpret_cast<const f32x4*>(p);
+    x[0] = v[0]; x[1] = v[1]; x[2] = v[2]; x[3] = v[3];
+  } else {
+    x[0] = *p;
+  }
+}
+template <int V>
+__device__ __forceinline__ void stv(float* __restrict__ p, const float (&x)[V]) {
+  if constexpr (V == 4)
+    *reinterpret_cast<f32x4*>(p) = f32x4{x[0], x[1], x[2], x[3]};
+  else
+    *p = x[0];
+}
+inline bool aligned16(const void* p) { return (uintptr_t)p % 16 == 0; }
+
+// one thread per V elements of out [B, C, E]: block r of gathered (at r stride) holds rank r's [B, C_r, E] as its tower left it; the rows
+// behind them and the elements behind B ceil(C / G) E of a block are never read
+template <int V>
+__global__ __launch_bounds__(THREADS) void cocoop_shard_compact_kernel(const float* __restrict__ gathered, float* __restrict__ out, int B, int C, int G,
+                                                                       int E, int64_t stride) {
+  const int EV = E / V;
+  const int64_t idx = (int64_t)blockIdx.x * THREADS + threadIdx.x;
+  if (idx >= (int64_t)B * C * EV) return;
+  const int e = (int)(idx % EV) * V, c = (int)((idx / EV) % C);
+  const int64_t b = idx / ((int64_t)EV * C);
+  int lo;
+  const int r = shard_owner(c, C, G, &lo);
+  const int Cr = C / G + (r < C % G ? 1 : 0);
+  float x[V];
+  ldv<V>(gathered + (int64_t)r * stride + (b * Cr + (c - lo)) * E + e, x);
+  stv<V>(out + (b * C + c) * E + e, x);
+}
+
+// one thread per V elements of out [B, C_r, E], C_r = hi - lo: out[b, c] = d_text[b, lo + c]
+template <int V>
+__global__ __launch_bounds__(THREADS) void cocoop_shard_rows_kernel(const float* __restrict__ d_text, float* __restrict__ out, int B, int C, int lo, int Cr,
+                                                                    int E) {
+  const int EV = E / V;
+  const int64_t idx = (int64_t)blockIdx.x * THREADS + threadIdx.x;
+  if (idx >= (int64_t)B * Cr * EV) return;
+  const int e = (int)(idx % EV) * V, c = (int)((idx / EV) % Cr);
+  const int64_t b = idx / ((int64_t)EV * Cr);
+  float x[V];
+  ldv<V>(d_text + (b * C + lo + c) * E + e, x);
+  stv<V>(out + (b * Cr + c) * E + e, x);
+}
+
+// one thread per V elements of partial [B, n_ctx, D]: the C (the rank's own) prompts of image b, c ascending from 0.f; no scale
+template <int V>
+__global__ __launch_bounds__(THREADS) void cocoop_dcs_partial_kernel(const float* __restrict__ d_embed, float* __restrict__ partial, int B, int C, int L, int D,
+                                                                     int n_ctx) {
+  const int DV = D / V;
+  const int64_t idx = (int64_t)blockIdx.x * THREADS + threadIdx.x;
+  if (idx >= (int64_t)B * n_ctx * DV) return;
+  const int d = (int)(idx % DV) * V, j = (int)((idx / DV) % n_ctx);
+  const int64_t b = idx / ((int64_t)DV * n_ctx);
+  float g[V];
+#pragma unroll
+  for (int v = 0; v < V; ++v) g[v] = 0.f;
+  for (int64_t c = 0; c < C; ++c) {
+    float x[V];
+    ldv<V>(d_embed + ((b * C + c) * L + 1 + j) * D + d, x);
+#pragma unroll
+    for (int v = 0; v < V; ++v) g[v] += x[v];
+  }
+  stv<V>(partial + (b * n_ctx + j) * D + d, g);
+}
+
+// one thread per V elements of dcs [B n_ctx D]: the G partials (rank r's at partials + r stride) in rank order from 0.f, then 1 / grad_scale
+template <int V>
+__global__ __launch_bounds__(THREADS) void cocoop_dcs_gathered_kernel(const float* __restrict__ partials, int G, int64_t stride, float* __restrict__ dcs,
+                                                                      int64_t total, float inv_scale) {
+  const int64_t idx = ((int64_t)blockIdx.x * THREADS + threadIdx.x) * V;
+  if (idx >= total) return;
+  float g[V], x[V];
+#pragma unroll
+  for (int v = 0; v < V; ++v) g[v] = 0.f;
+  for (int r = 0; r < G; ++r) {
+    ldv<V>(partials + (int64_t)r * stride + idx, x);
+#pragma unroll
+    for (int v = 0; v < V; ++v) g[v] += x[v];
+  }
+#pragma unroll
+  for (int v = 0; v < V; ++v) g[v] *= inv_scale;
+  stv<V>(dcs + idx, g);
+}
+
+int check_reduce_gathered(const char* who, const float* partials, int G, int64_t rank_stride, const float* x_n, const float* hid, const float* w2,
+                          const float* grad, int B, int D, int E, int H, int n_ctx, float grad_scale, const void* workspace, size_t workspace_bytes) {
+  CLIPMI_REQUIRE(partials && x_n && hid && w2 && grad && workspace, CLIPMI_ERR_ARG, "%s: null pointer", who);
+  CLIPMI_REQUIRE(G >= 1 && B >= 1 && D >= 1 && E >= 1 && n_ctx >= 1, CLIPMI_ERR_SHAPE, "%s: G=%d B=%d D=%d E=%d n_ctx=%d", who, G, B, D, E, n_ctx);
+  CLIPMI_REQUIRE(H >= 1 && H <= MAX_H, CLIPMI_ERR_SHAPE, "%s: H=%d (1 .. %d)", who, H, MAX_H);
+  CLIPMI_REQUIRE(std::isfinite(grad_scale) && grad_scale > 0.f, CLIPMI_ERR_ARG, "%s: grad_scale=%g (finite, > 0)", who, grad_scale);
+  CLIPMI_REQUIRE(block_of(n_ctx, D, E, H).total < (1ll << 31) && (int64_t)B * n_ctx * D < (1ll << 31), CLIPMI_ERR_SHAPE, "%s: parameter block too large", who);
+  const int64_t block = (int64_t)B * n_ctx * D;
+  CLIPMI_REQUIRE(rank_stride >= block && rank_stride < (1ll << 40), CLIPMI_ERR_SHAPE, "%s: rank_stride=%lld below a rank's block of %lld elements", who,
+                 (long long)rank_stride, (long long)block);
+  CLIPMI_REQUIRE((uintptr_t)workspace % 4 == 0, CLIPMI_ERR_ARG, "%s: the workspace must be 4-byte aligned", who);
+  const size_t need = clipmi_cocoop_reduce_workspace_bytes(B, n_ctx, D, H);
+  CLIPMI_REQUIRE(workspace_bytes >= need, CLIPMI_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, need);
+  return CLIPMI_OK;
+}
+
+// the rank-ordered sum, then cocoop_reduce's last three launches as they are: the caller has passed check_reduce_gathered
+int enqueue_reduce_gathered(const float* partials, int G, int64_t rank_stride, const float* x_n, const float* hid, const float* w2, float* grad, int B, int D,
+                            int E, int H, int n_ctx, float grad_scale, void* workspace, hipStream_t s) {
+  const ReduceWs ws = reduce_carve(workspace, B, n_ctx, D, H);
+  const Block k = block_of(n_ctx, D, E, H);
+  const dim3 threads(THREADS);
+  auto per = [](int64_t items) { return dim3((unsigned)((items + THREADS - 1) / THREADS)); };
+  const int64_t total = (int64_t)B * n_ctx * D;
+  if (total % 4 == 0 && rank_stride % 4 == 0 && aligned16(partials) && aligned16(ws.dcs))
+    hipLaunchKernelGGL(cocoop_dcs_gathered_kernel<4>, per(total / 4), threads, 0, s, partials, G, rank_stride, ws.dcs, total, 1.f / grad_scale);
+  else
+    hipLaunchKernelGGL(cocoop_dcs_gathered_kernel<1>, per(total), threads, 0, s, partials, G, rank_stride, ws.dcs, total, 1.f / grad_scale);
+  if (int rc = check_launch("cocoop_dcs_gathered_kernel")) return rc;
+  hipLaunchKernelGGL(cocoop_dw2_kernel, per((int64_t)D * H), threads, 0, s, ws, hid, grad, k, B, D, H, n_ctx);
+  if (int rc = check_launch("cocoop_dw2_kernel")) return rc;
+  hipLaunchKernelGGL(cocoop_dhid_kernel, dim3((unsigned)B), threads, 0, s, ws, hid, w2, D, H);
+  if (int rc = check_launch("cocoop_dhid_kernel")) return rc;
+  hipLaunchKernelGGL(cocoop_dw1_kernel, per((int64_t)H * E), threads, 0, s, ws, x_n, grad, k, B, E, H);
+  return check_launch("cocoop_dw1_kernel");
+}
+
 }  // namespace
 }  // namespace clipmi
 
@@ -452,6 +590,78 @@ int clipmi_cocoop_step(const float* grad, float* params, float* buf, int n_ctx, 
                        float dampening, float weight_decay, int nesterov, clipmi_stream_t stream) {
   if (int rc = check_step("cocoop_step", grad, params, buf, lr, n_ctx, D, E, H, momentum, dampening, weight_decay, nesterov)) return rc;
   return enqueue_step(grad, params, buf, n_ctx, D, E, H, lr, first_step, momentum, dampening, weight_decay, nesterov, (hipStream_t)stream);
+}
+
+// ---- the class-sharded step's entry points (include/clipmi.h; DESIGN.md "Class-sharded CoCoOp fit")
+
+int clipmi_cocoop_embed_classes(const void* base, int dtype, const float* ctx, const float* pi, const int32_t* cls_eot, float* prompts, int32_t* eot, int B,
+                                int C, int lo, int hi, int L, int Lc, int D, int n_ctx, clipmi_stream_t stream) {
+  const char* who = "cocoop_embed_classes";
+  CLIPMI_REQUIRE(base && cls_eot, CLIPMI_ERR_ARG, "%s: null pointer", who);
+  CLIPMI_REQUIRE(dtype == CLIPMI_F16 || dtype == CLIPMI_F32, CLIPMI_ERR_ARG, "%s: bad dtype %d", who, dtype);
+  CLIPMI_REQUIRE(C >= 1 && lo >= 0 && lo < hi && hi <= C, CLIPMI_ERR_SHAPE, "%s: classes [%d, %d) of C=%d (a non-empty range)", who, lo, hi, C);
+  CLIPMI_REQUIRE(Lc >= 1 && D >= 1 && (int64_t)C * Lc < (1ll << 31) / D, CLIPMI_ERR_SHAPE, "%s: C=%d Lc=%d D=%d", who, C, Lc, D);
+  const void* own = static_cast<const char*>(base) + (size_t)lo * Lc * D * (dtype == CLIPMI_F16 ? 2 : 4);
+  if (int rc = check_embed(who, own, dtype, ctx, pi, cls_eot + lo, prompts, eot, B, hi - lo, L, Lc, D, n_ctx, 1)) return rc;
+  return enqueue_embed(own, dtype, ctx, pi, cls_eot + lo, prompts, eot, B, hi - lo, L, Lc, D, n_ctx, (hipStream_t)stream);
+}
+
+int clipmi_cocoop_shard_compact(const float* gathered, float* out, int B, int C, int G, int E, int64_t rank_stride, clipmi_stream_t stream) {
+  const char* who = "cocoop_shard_compact";
+  CLIPMI_REQUIRE(gathered && out, CLIPMI_ERR_ARG, "%s: null pointer", who);
+  CLIPMI_REQUIRE(G >= 1 && C >= G && B >= 1 && E >= 1, CLIPMI_ERR_SHAPE, "%s: B=%d C=%d G=%d E=%d (C >= G >= 1)", who, B, C, G, E);
+  const int64_t block = (int64_t)B * ((C + G - 1) / G) * E;
+  CLIPMI_REQUIRE((int64_t)B * C < (1ll << 31) / E, CLIPMI_ERR_SHAPE, "%s: B * C * E too large", who);
+  CLIPMI_REQUIRE(rank_stride >= block && rank_stride < (1ll << 40), CLIPMI_ERR_SHAPE, "%s: rank_stride=%lld below a rank's block of %lld elements", who,
+                 (long long)rank_stride, (long long)block);
+  const bool vec = E % 4 == 0 && rank_stride % 4 == 0 && aligned16(gathered) && aligned16(out);
+  const int64_t total = (int64_t)B * C * (vec ? E / 4 : E);
+  const dim3 grid((unsigned)((total + THREADS - 1) / THREADS)), threads(THREADS);
+  if (vec)
+    hipLaunchKernelGGL(cocoop_shard_compact_kernel<4>, grid, threads, 0, (hipStream_t)stream, gathered, out, B, C, G, E, rank_stride);
+  else
+    hipLaunchKernelGGL(cocoop_shard_compact_kernel<1>, grid, threads, 0, (hipStream_t)stream, gathered, out, B, C, G, E, rank_stride);
+  return check_launch("cocoop_shard_compact_kernel");
+}
+
+int clipmi_cocoop_shard_rows(const float* d_text, float* out, int B, int C, int lo, int hi, int E, clipmi_stream_t stream) {
+  const char* who = "cocoop_shard_rows";
+  CLIPMI_REQUIRE(d_text && out, CLIPMI_ERR_ARG, "%s: null pointer", who);
+  CLIPMI_REQUIRE(B >= 1 && C >= 1 && E >= 1 && lo >= 0 && lo < hi && hi <= C, CLIPMI_ERR_SHAPE, "%s: B=%d E=%d, classes [%d, %d) of C=%d (a non-empty range)", who,
+                 B, E, lo, hi, C);
+  CLIPMI_REQUIRE((int64_t)B * C < (1ll << 31) / E, CLIPMI_ERR_SHAPE, "%s: B * C * E too large", who);
+  const bool vec = E % 4 == 0 && aligned16(d_text) && aligned16(out);
+  const int64_t total = (int64_t)B * (hi - lo) * (vec ? E / 4 : E);
+  const dim3 grid((unsigned)((total + THREADS - 1) / THREADS)), threads(THREADS);
+  if (vec)
+    hipLaunchKernelGGL(cocoop_shard_rows_kernel<4>, grid, threads, 0, (hipStream_t)stream, d_text, out, B, C, lo, hi - lo, E);
+  else
+    hipLaunchKernelGGL(cocoop_shard_rows_kernel<1>, grid, threads, 0, (hipStream_t)stream, d_text, out, B, C, lo, hi - lo, E);
+  return check_launch("cocoop_shard_rows_kernel");
+}
+
+int clipmi_cocoop_dcs_partial(const float* d_embed, float* partial, int B, int C, int L, int D, int n_ctx, clipmi_stream_t stream) {
+  const char* who = "cocoop_dcs_partial";
+  CLIPMI_REQUIRE(d_embed && partial, CLIPMI_ERR_ARG, "%s: null pointer", who);
+  CLIPMI_REQUIRE(B >= 1 && C >= 1 && D >= 1, CLIPMI_ERR_SHAPE, "%s: B=%d C=%d D=%d (all >= 1)", who, B, C, D);
+  CLIPMI_REQUIRE(n_ctx >= 1 && 1 + n_ctx <= L, CLIPMI_ERR_SHAPE, "%s: n_ctx=%d, L=%d (SOS and the context must fit the live rows)", who, n_ctx, L);
+  CLIPMI_REQUIRE((int64_t)B * C * L < (1ll << 31) && (int64_t)B * n_ctx * D < (1ll << 31), CLIPMI_ERR_SHAPE, "%s: prompt set or block too large", who);
+  const bool vec = D % 4 == 0 && aligned16(d_embed) && aligned16(partial);
+  const int64_t total = (int64_t)B * n_ctx * (vec ? D / 4 : D);
+  const dim3 grid((unsigned)((total + THREADS - 1) / THREADS)), threads(THREADS);
+  if (vec)
+    hipLaunchKernelGGL(cocoop_dcs_partial_kernel<4>, grid, threads, 0, (hipStream_t)stream, d_embed, partial, B, C, L, D, n_ctx);
+  else
+    hipLaunchKernelGGL(cocoop_dcs_partial_kernel<1>, grid, threads, 0, (hipStream_t)stream, d_embed, partial, B, C, L, D, n_ctx);
+  return check_launch("cocoop_dcs_partial_kernel");
+}
+
+int clipmi_cocoop_reduce_gathered(const float* partials, int G, int64_t rank_stride, const float* x_n, const float* hid, const float* w2, float* grad, int B,
+                                  int D, int E, int H, int n_ctx, float grad_scale, void* workspace, size_t workspace_bytes, clipmi_stream_t stream) {
+  if (int rc = check_reduce_gathered("cocoop_reduce_gathered", partials, G, rank_stride, x_n, hid, w2, grad, B, D, E, H, n_ctx, grad_scale, workspace,
+                                     workspace_bytes))
+    return rc;
+  return enqueue_reduce_gathered(partials, G, rank_stride, x_n, hid, w2, grad, B, D, E, H, n_ctx, grad_scale, workspace, (hipStream_t)stream);
 }
 
 // workspace: the tower's workspace (N prompts) | x_n [B, E] | hid [B, H] | pi [B, D] | prompts fp32 [N, Lc, D] | EOT int32 [N] | text features

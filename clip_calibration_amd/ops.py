@@ -2347,6 +2347,123 @@ def cocoop_step(grad: torch.Tensor, params: torch.Tensor, buf: Optional[torch.Te
                                  _stream()), "clipmi_cocoop_step")
 
 
+# ---- the class-sharded CoCoOp fit (csrc/cocoop_train.hip, DESIGN.md "Class-sharded CoCoOp fit")
+
+def cocoop_embed_classes(base: torch.Tensor, ctx: torch.Tensor, pi: torch.Tensor, cls_eot: torch.Tensor, lo: int, hi: int, rows: int = 0,
+                         prompts: Optional[torch.Tensor] = None, eot: Optional[torch.Tensor] = None):
+    """``cocoop_embed`` for the classes ``[lo, hi)`` of ``base`` [C, Lc, D] and ``cls_eot`` [C] (one class is enough): ``(prompts fp32
+    [B * (hi - lo), Lc, D], eot int32 [B * (hi - lo)])``, image-major -- the slice ``[:, lo:hi]`` of ``cocoop_embed``'s [B, C, Lc, D]."""
+    base = _dev(base, "base", (torch.float16, torch.float32))
+    ctx, pi = _dev(ctx, "ctx", (torch.float32,)), _dev(pi, "pi", (torch.float32,))
+    cls_eot = _dev(cls_eot, "cls_eot", (torch.int32,))
+    if base.dim() != 3 or ctx.dim() != 2 or pi.dim() != 2 or ctx.shape[1] != base.shape[2] or pi.shape[1] != base.shape[2] or cls_eot.shape != (base.shape[0],):
+        raise ValueError(f"cocoop_embed_classes: base {tuple(base.shape)}, ctx {tuple(ctx.shape)}, pi {tuple(pi.shape)} and cls_eot {tuple(cls_eot.shape)} "
+                         "do not agree")
+    Cn, Lc, D = base.shape
+    lo, hi = int(lo), int(hi)
+    if not 0 <= lo < hi <= Cn:
+        raise ValueError(f"cocoop_embed_classes: the classes [{lo}, {hi}) must be a non-empty range of the {Cn} classes")
+    B, n_ctx = int(pi.shape[0]), int(ctx.shape[0])
+    N = B * (hi - lo)
+    L = int(rows) if 0 < int(rows) < Lc else Lc
+    if prompts is None:
+        prompts = torch.empty(N, Lc, D, dtype=torch.float32, device=base.device)
+    else:
+        _in_place(prompts, torch.float32, "cocoop_embed_classes: prompts must be a contiguous fp32 tensor on the GPU", numel=N * Lc * D)
+    if eot is None:
+        eot = torch.empty(N, dtype=torch.int32, device=base.device)
+    else:
+        _in_place(eot, torch.int32, "cocoop_embed_classes: eot must be a contiguous int32 tensor on the GPU", numel=N)
+    check(lib.clipmi_cocoop_embed_classes(base.data_ptr(), _DT[base.dtype], ctx.data_ptr(), pi.data_ptr(), cls_eot.data_ptr(), prompts.data_ptr(),
+                                          eot.data_ptr(), B, Cn, lo, hi, L, Lc, D, n_ctx, _stream()), "clipmi_cocoop_embed_classes")
+    return prompts, eot
+
+
+def cocoop_shard_pad(n_cls: int, world: int) -> int:
+    """Classes per rank of the gathered text features' blocks: ``ceil(C / G)``."""
+    return -(-int(n_cls) // int(world))
+
+
+def cocoop_shard_compact(gathered: torch.Tensor, B: int, n_cls: int, E: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The gathered fp32 [G, elements per rank >= B * ceil(C / G) * E] text features -> fp32 [B * C, E] in the unsharded, image-major order:
+    rank r's block starts with its own [B, C_r, E]; what lies behind it is never read.  One launch."""
+    who = "cocoop_shard_compact"
+    _in_place(gathered, torch.float32, f"{who}: gathered must be a contiguous fp32 tensor on the GPU")
+    B, Cn, E = int(B), int(n_cls), int(E)
+    if gathered.dim() != 2 or not 1 <= gathered.shape[0] <= Cn or B < 1 or E < 1:
+        raise ValueError(f"{who}: gathered {tuple(gathered.shape)} must be [G, elements per rank] with 1 <= G <= C = {Cn}")
+    G, stride = gathered.shape
+    need = B * cocoop_shard_pad(Cn, G) * E
+    if stride < need:
+        raise ValueError(f"{who}: gathered {tuple(gathered.shape)} holds fewer than B * ceil(C / G) * E = {need} elements per rank")
+    if out is None:
+        out = torch.empty(B * Cn, E, dtype=torch.float32, device=gathered.device)
+    else:
+        _in_place(out, torch.float32, f"{who}: out must be a contiguous fp32 tensor on the GPU", numel=B * Cn * E)
+    check(lib.clipmi_cocoop_shard_compact(gathered.data_ptr(), out.data_ptr(), B, Cn, G, E, stride, _stream()), "clipmi_cocoop_shard_compact")
+    return out
+
+
+def cocoop_shard_rows(d_text: torch.Tensor, B: int, lo: int, hi: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The rows ``{b * C + c : lo <= c < hi}`` of ``d_text`` fp32 [B * C, E] as a contiguous fp32 [B * (hi - lo), E].  One launch."""
+    who = "cocoop_shard_rows"
+    d_text = _dev(d_text, "d_text", (torch.float32,))
+    B, lo, hi = int(B), int(lo), int(hi)
+    if d_text.dim() != 2 or B < 1 or d_text.shape[0] % B:
+        raise ValueError(f"{who}: d_text {tuple(d_text.shape)} does not split into {B} images")
+    Cn, E = d_text.shape[0] // B, int(d_text.shape[1])
+    if not 0 <= lo < hi <= Cn:
+        raise ValueError(f"{who}: the classes [{lo}, {hi}) must be a non-empty range of the {Cn} classes")
+    if out is None:
+        out = torch.empty(B * (hi - lo), E, dtype=torch.float32, device=d_text.device)
+    else:
+        _in_place(out, torch.float32, f"{who}: out must be a contiguous fp32 tensor on the GPU", numel=B * (hi - lo) * E)
+    check(lib.clipmi_cocoop_shard_rows(d_text.data_ptr(), out.data_ptr(), B, Cn, lo, hi, E, _stream()), "clipmi_cocoop_shard_rows")
+    return out
+
+
+def cocoop_dcs_partial(d_embed: torch.Tensor, B: int, n_cls: int, n_ctx: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """A rank's send block fp32 [B, n_ctx, D] from its own ``d_embed`` fp32 [B * C_r * L, D] (``n_cls`` = C_r >= 1, its own classes):
+    the context rows of an image's C_r prompts added in ascending class order from 0, unscaled.  One launch."""
+    who = "cocoop_dcs_partial"
+    d_embed = _dev(d_embed, "d_embed", (torch.float32,))
+    B, Cn, n_ctx = int(B), int(n_cls), int(n_ctx)
+    if d_embed.dim() != 2 or B < 1 or Cn < 1 or d_embed.shape[0] % (B * Cn):
+        raise ValueError(f"{who}: d_embed {tuple(d_embed.shape)} does not split into {B} x {Cn} prompts")
+    L, D = d_embed.shape[0] // (B * Cn), int(d_embed.shape[1])
+    if out is None:
+        out = torch.empty(B, n_ctx, D, dtype=torch.float32, device=d_embed.device)
+    else:
+        _in_place(out, torch.float32, f"{who}: out must be a contiguous fp32 tensor on the GPU", numel=B * n_ctx * D)
+    check(lib.clipmi_cocoop_dcs_partial(d_embed.data_ptr(), out.data_ptr(), B, Cn, L, D, n_ctx, _stream()), "clipmi_cocoop_dcs_partial")
+    return out
+
+
+def cocoop_reduce_gathered(partials: torch.Tensor, x_n: torch.Tensor, hid: torch.Tensor, w2: torch.Tensor, n_ctx: int, grad_scale: float,
+                           grad: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``cocoop_reduce`` from the gathered partials fp32 [G, elements per rank >= B * n_ctx * D] (rank r's ``cocoop_dcs_partial`` first in
+    row r): the G partials added in rank order from 0, one multiplication by ``1 / grad_scale``, then the meta-net's backward as
+    ``cocoop_reduce`` runs it.  Every rank given the same blocks writes the same gradient block."""
+    who = "cocoop_reduce_gathered"
+    _in_place(partials, torch.float32, f"{who}: partials must be a contiguous fp32 tensor on the GPU")
+    x_n, hid, w2 = (_dev(t, n, (torch.float32,)) for t, n in ((x_n, "x_n"), (hid, "hid"), (w2, "w2")))
+    if partials.dim() != 2 or x_n.dim() != 2 or hid.dim() != 2 or w2.dim() != 2 or hid.shape[0] != x_n.shape[0] or w2.shape[1] != hid.shape[1]:
+        raise ValueError(f"{who}: partials {tuple(partials.shape)}, x_n {tuple(x_n.shape)}, hid {tuple(hid.shape)}, w2 {tuple(w2.shape)} do not agree")
+    (B, E), H, D, n_ctx = x_n.shape, int(hid.shape[1]), int(w2.shape[0]), int(n_ctx)
+    G, stride = partials.shape
+    if G < 1 or n_ctx < 1 or stride < B * n_ctx * D:
+        raise ValueError(f"{who}: partials {tuple(partials.shape)} holds fewer than B * n_ctx * D = {B * n_ctx * D} elements per rank")
+    total = lib.clipmi_cocoop_block_floats(n_ctx, D, E, H)
+    if grad is None:
+        grad = torch.empty(max(total, 1), dtype=torch.float32, device=partials.device)
+    else:
+        _in_place(grad, torch.float32, f"{who}: grad must be a contiguous fp32 tensor on the GPU", numel=total)
+    ws = torch.empty(max(lib.clipmi_cocoop_reduce_workspace_bytes(B, n_ctx, D, H), 8), dtype=torch.uint8, device=partials.device)
+    check(lib.clipmi_cocoop_reduce_gathered(partials.data_ptr(), G, stride, x_n.data_ptr(), hid.data_ptr(), w2.data_ptr(), grad.data_ptr(), B, D, E, H, n_ctx,
+                                            float(grad_scale), ws.data_ptr(), ws.numel(), _stream()), "clipmi_cocoop_reduce_gathered")
+    return grad
+
+
 # ---- per-epoch validation of the CoCoOp and ProDA fits (csrc/fit_monitor.hip, csrc/proda_train.hip; DESIGN.md "Fit monitor", "CoCoOp and ProDA")
 COCOOP_VAL_MAX_C = 16384      # cocoop_val_rows_kernel keeps one image's C fp32 logits in LDS
 

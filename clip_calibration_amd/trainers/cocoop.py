@@ -125,10 +125,22 @@ class CustomCLIP(nn.Module):
         validation chunk), ``val_bins``, ``final_model`` ("last_step" or "best_val", the reference's TEST.FINAL_MODEL),
         ``val_criterion`` and ``return_monitor`` as ``cocoopfit.fit_prompt_learner`` takes them; ``CoCoOpFitState.validate`` runs behind
         every epoch and scores what this module's ``forward`` would compute.  ``final_model="best_val"`` installs the best epoch's
-        tensors into the module."""
+        tensors into the module.
+
+        ``shard=coopfit.Shard(world, rank, gather)`` on either route: the class-sharded fit in the place of the reference's
+        ``nn.DataParallel`` over the text encoder, one process per GPU, every rank making this call on the same data (``cocoopfit``'s
+        module docstring).  Both loss scales and all three optimisers work under it.  What ``shard`` refuses -- validation by
+        ``val_loader=`` included -- is refused here, before either tower runs.  With a ``LocalGather`` the one call makes and steps all
+        the ranks' states, on either route."""
         import math
         from ..cocoopfit import NAMES
         who = "fit_prompt_learner"
+        shard = fit_args.get("shard")
+        if shard is not None:
+            from ..cocoopfit import check_shard
+            val = fit_args.get("val_loader") if fit_args.get("val_loader") is not None else fit_args.get("val")
+            check_shard(who, shard, self.prompt_learner.tokenized_prompts.shape[0], bool(fit_args.get("one_call", False)), val,
+                        fit_args.get("final_model", "last_step"))
         _fit.validation_set(who, self.clip_model, fit_args)
         fit_args.setdefault("logit_scale", math.log(self.scale))
         pl = self.prompt_learner
@@ -143,7 +155,8 @@ class CustomCLIP(nn.Module):
             if watch["val"] is not None and val_batch_size is not None:
                 from ..fitmonitor import _batch_size
                 _batch_size(who, val_batch_size)
-            state = CoCoOpFitState(self.clip_model, ids, params, **fit_args)
+            from ..coopfit import shard_states
+            state = shard_states(lambda sh: CoCoOpFitState(self.clip_model, ids, params, **dict(fit_args, shard=sh)), shard)
             state.val_stream_f16, state.val_batch_size = self.text_stream_f16, val_batch_size
             losses, monitor = _fit.run_with_transform(who, state, self.clip_model, ids.shape[0], E, train_loader, transform, epochs, lr, run, watch)
             fitted = _fit.pack(state.best_params() if watch["final_model"] == "best_val" else state.params(), losses)

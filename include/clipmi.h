@@ -1656,6 +1656,35 @@ int clipmi_cocoop_train_step(clipmi_model* m, const clipmi_text_dgrad* wt, const
                              float weight_decay, int nesterov, float* loss, float* grad_out, void* workspace, size_t workspace_bytes,
                              void* stash, size_t stash_bytes, clipmi_stream_t stream);
 
+/* The class-sharded CoCoOp fit (DESIGN.md "Class-sharded CoCoOp fit"): G ranks, rank r owning the contiguous classes [lo, hi) of the
+ * balanced split of C (the first C mod G ranks one more, C >= G), C_r = hi - lo of them.  Its tower runs over the B C_r prompts of its
+ * classes, image-major: prompt b C_r + (c - lo) is image b with class c.  Two all-gathers per step; the meta-net, the head, the
+ * meta-net's backward and the optimiser step run replicated.  fp32, fixed summation orders, no atomics; with G = 1 every chain is the
+ * unsharded call's, bit for bit.  These exports are additive: the ABI version does not change with them.
+ *
+ * clipmi_cocoop_embed_classes: clipmi_cocoop_embed for the classes [lo, hi) of C (one class is enough): base [C, Lc, D] and cls_eot [C]
+ *   are the whole class set's, prompts [B C_r, Lc, D] and eot [B C_r] the rank's.  The same kernel: the output is the slice [:, lo:hi] of
+ *   clipmi_cocoop_embed's [B, C, Lc, D].  base + lo Lc D elements must be 16-byte aligned.
+ * clipmi_cocoop_shard_compact: gathered fp32, rank r's block at gathered + r rank_stride (elements, >= B ceil(C / G) E) holding its tower's
+ *   [B, C_r, E] as it lies and padding behind it that is never read; out fp32 [B, C, E], the unsharded order clipmi_cocoop_head takes.
+ * clipmi_cocoop_shard_rows: out fp32 [B, C_r, E] = d_text[:, lo:hi] of d_text fp32 [B, C, E]: what the rank's backward is given.
+ * clipmi_cocoop_dcs_partial: a rank's send block fp32 [B, n_ctx, D] from its own d_embed fp32 [B C L, D] (C: its own classes, >= 1):
+ *   partial[b, j] = sum_c d_embed[(b C + c) L + 1 + j], c ascending from 0, unscaled.
+ * clipmi_cocoop_reduce_gathered: clipmi_cocoop_reduce from the gathered partials, rank r's at partials + r rank_stride (elements, >= B n_ctx
+ *   D): dcs[b, j] = (1 / grad_scale) (sum_r partial_r[b, j]), r ascending from 0 and the one multiplication last; then
+ *   clipmi_cocoop_reduce's three further launches unchanged.  Every rank given the same blocks writes the same bits.  workspace:
+ *   clipmi_cocoop_reduce_workspace_bytes(B, n_ctx, D, H) bytes.  Every check precedes the first launch.
+ * The three copies and the two sums run one thread per four elements when the row length (E, D; B n_ctx D for the reduce) and rank_stride
+ *   are multiples of 4 and the pointers are 16-byte aligned, one thread per element otherwise.  One launch each (four for the reduce). */
+int clipmi_cocoop_embed_classes(const void* base, int dtype, const float* ctx, const float* pi, const int32_t* cls_eot, float* prompts,
+                                int32_t* eot, int B, int C, int lo, int hi, int L, int Lc, int D, int n_ctx, clipmi_stream_t stream);
+int clipmi_cocoop_shard_compact(const float* gathered, float* out, int B, int C, int G, int E, int64_t rank_stride, clipmi_stream_t stream);
+int clipmi_cocoop_shard_rows(const float* d_text, float* out, int B, int C, int lo, int hi, int E, clipmi_stream_t stream);
+int clipmi_cocoop_dcs_partial(const float* d_embed, float* partial, int B, int C, int L, int D, int n_ctx, clipmi_stream_t stream);
+int clipmi_cocoop_reduce_gathered(const float* partials, int G, int64_t rank_stride, const float* x_n, const float* hid, const float* w2,
+                                  float* grad, int B, int D, int E, int H, int n_ctx, float grad_scale, void* workspace,
+                                  size_t workspace_bytes, clipmi_stream_t stream);
+
 /* Timing aid for bench.py (the per-kernel roofline of its JSON line): the five launches of the vision tower's residual
  * block 0 -- 0 in-proj, 1 attention, 2 out-proj + residual, 3 c_fc + QuickGELU, 4 c_proj + residual (clip/model.py:181-188)
  * -- issued exactly as clipmi_encode_image issues them (LayerNorm fold, fp16 stream, tile selection) on the operands the
