@@ -60,10 +60,12 @@ import torch
 
 from . import _lib, fitloop, fitmonitor, ops
 from ._lib import check, lib
-from .coopfit import (DYNAMIC, MAX_LIVE_ROWS, _DT, Shard, _AdamBlock, _BlockScaler, _Tower, _check_batch, _check_grad_scale, _drive, _file_state, _is_dynamic,
-                      _live_rows, _run_phases, _scale_args, _world_states, operand_stats_dict, shard_classes, shard_states)
+from . import shard as sharding
+from .coopfit import (DYNAMIC, MAX_LIVE_ROWS, _DT, _AdamBlock, _BlockScaler, _Tower, _check_batch, _check_grad_scale, _is_dynamic, _live_rows, _scale_args,
+                      operand_stats_dict)
 from .coopfit import _check_prompts as _check_coop_prompts
 from .fitloop import _host_int_array, _need_gpu, steps_per_epoch
+from .shard import Shard, shard_classes, shard_states
 
 # 2^10, measured on the ViT-B/16 text geometry with synthetic weights at the reference's batch of 1 (profiles/cocoopfit_parity.txt,
 # "grad_scale"): with one image dz is not divided down by a batch, and CoOp's 2^12 leaves the largest fp16 dgrad-GEMM operand only 2^1.9
@@ -155,19 +157,6 @@ class _CoCoOpTower(_Tower):
         return self.step_ws
 
 
-def check_shard(who: str, shard, n_cls: int, one_call: bool = False, val=None, final_model: str = "last_step") -> None:
-    """What the class-sharded CoCoOp fit refuses, each by name, before any device call.  Both loss scales and the three optimisers pass:
-    every rank steps the same replicated block with the same gradient."""
-    if not isinstance(shard, Shard):
-        raise ValueError(f"{who}: shard must be a coopfit.Shard(world, rank, gather), got {type(shard).__name__}")
-    if n_cls < shard.world:
-        raise ValueError(f"{who}: shard: C={n_cls} classes cannot be split over world={shard.world} ranks (C < G: a rank would own no class)")
-    if one_call:
-        raise ValueError(f"{who}: shard has no one-call step (one_call=True); the sharded step is the separate calls")
-    if val is not None or final_model == "best_val":
-        raise ValueError(f"{who}: shard has no validation: val=, val_loader= and final_model='best_val' are not sharded")
-
-
 def stash_bytes(clip_model, tokenized_prompts, batch: int, seq_rows: Optional[int] = None, world: int = 1, rank: int = 0):
     """``(workspace bytes, stash bytes)`` of the training tower of one step on ``batch`` images, as clipmi_text_train_bytes reports them
     for the ``batch x C_r`` prompts of ``rank`` of ``world`` under the live-row cut of the WHOLE prompt set (``world=1``: the unsharded
@@ -199,9 +188,7 @@ def gradients(clip_model, tokenized_prompts, params, features: torch.Tensor, lab
     who = "gradients"
     Cn, n_ctx, H, last = _check_prompts(who, clip_model, tokenized_prompts, params, seq_rows)
     if shard is not None:
-        check_shard(who, shard, Cn)
-        if return_operand_stats:
-            raise ValueError(f"{who}: shard returns no operand statistics (return_operand_stats=True)")
+        sharding.check(who, shard, n_cls=Cn, return_operand_stats=return_operand_stats)
     if _is_dynamic(who, grad_scale):
         raise ValueError(f"{who}: grad_scale={DYNAMIC!r} belongs to a fit (CoCoOpFitState, fit_prompt_learner); one gradient needs a number")
     gs = _check_grad_scale(who, grad_scale)
@@ -214,11 +201,8 @@ def gradients(clip_model, tokenized_prompts, params, features: torch.Tensor, lab
     if shard is not None:     # the sharded step's phases with a report in the step's place
         make = lambda sh: CoCoOpFitState(clip_model, tokenized_prompts, params, logit_scale, 0.0, 0.0, 0.0, False, gs, seq_rows, shard=sh)
         state = shard_states(make, shard)
-        states = _world_states(shard, state, who)
-        reports = [{} for _ in states]
-        _run_phases([s._shard_phases(features, labels_d, None, torch.empty(1, dtype=torch.float32, device=features.device), True, r)
-                     for s, r in zip(states, reports)])
-        report = reports[states.index(state)]
+        phases = lambda s, r: s._shard_phases(features, labels_d, None, torch.empty(1, dtype=torch.float32, device=features.device), True, r)
+        report = sharding.report_all(shard, state, who, phases)
         grads = {k: v.clone() for k, v in ops.cocoop_block_views(report["grad"], n_ctx, state.D, E, H).items()}
         return (report["loss"], grads) + (({k: report[k] for k in ("text", "x_n", "hid", "pi", "rows")},) if return_parts else ())
     tower = _CoCoOpTower(who, clip_model, tokenized_prompts, Cn, features.shape[0], n_ctx, H, last, seq_rows)
@@ -256,7 +240,7 @@ class CoCoOpFitState(fitmonitor.Monitored):
         self.C, self.n_ctx, self.H, self._last = _check_prompts(who, clip_model, tokenized_prompts, params, seq_rows)
         self.shard = shard
         if shard is not None:
-            check_shard(who, shard, self.C)
+            sharding.check(who, shard, n_cls=self.C)
         self.dynamic, self.grad_scale, self.scaler = _scale_args(who, grad_scale, scaler)
         self.optimizer, momentum, dampening, nesterov, betas = fitloop.check_optimizer(who, optimizer, momentum, dampening, nesterov, weight_decay, betas, eps)
         self.scale = fitloop.exp_logit_scale(who, logit_scale)
@@ -279,7 +263,7 @@ class CoCoOpFitState(fitmonitor.Monitored):
         if shard is not None:       # the tower over the rank's own classes; the live-row cut is the full prompt set's
             self.lo, self.hi = shard_classes(self.C, shard.world, shard.rank)
             self._own_ids = _host_int_array(who, tokenized_prompts, "tokenized_prompts")[self.lo:self.hi]
-            _file_state(shard, self)
+            sharding.file_state(shard, self)
 
     def scaler_state(self) -> dict:
         """The dynamic scale's block as ``dict(scale, growth_tracker, skipped_steps, applied_steps, found_inf)`` (``found_inf``: of the
@@ -440,14 +424,11 @@ class CoCoOpFitState(fitmonitor.Monitored):
         scale); ``one_call`` is then refused: the one-call steps stay SGD.  Under ``shard`` every rank makes this call with the same
         batch; under a ``LocalGather`` the first state that steps drives all the world's states (``one_call`` is refused)."""
         who = "CoCoOpFitState.step"
-        if one_call and self.shard is not None:
-            raise ValueError(f"{who}: shard has no one-call step (one_call=True); the sharded step is the separate calls")
+        if self.shard is not None:
+            sharding.check(who, self.shard, one_call=one_call)
         if one_call and self._adam is not None:
             raise ValueError(f"{who}: one_call=True with optimizer={self.optimizer!r}: the one-call steps stay SGD")
-        states = None
-        if self.shard is not None:
-            states = _world_states(self.shard, self, who)
-            _drive(self.shard, self, who)
+        states = sharding.drive(self.shard, self, who) if self.shard is not None else None
         labels_d = _check_batch(who, features, labels, self.C, self.E)
         _need_gpu(features, "features")
         if features.dtype != torch.float32 or features.stride(1) != 1:
@@ -457,9 +438,8 @@ class CoCoOpFitState(fitmonitor.Monitored):
         first = self.steps == 0
         loss = torch.empty(1, dtype=torch.float32, device=dev)
         if states is not None:
-            _run_phases([s._shard_phases(features, labels_d, lr_d, loss if s is self else torch.empty_like(loss), first) for s in states])
-            for s in states:
-                s.steps += 1
+            sharding.step_all(states, self, lambda s: s._shard_phases(features, labels_d, lr_d, loss if s is self else torch.empty_like(loss), first))
+            self.steps += 1
             return loss if want_loss else None
         t, m = self.tower(int(features.shape[0])), self.model
         sgd = (self.momentum, self.dampening, self.weight_decay, self.nesterov)
@@ -568,7 +548,7 @@ def fit_prompt_learner(features: torch.Tensor, labels, clip_model, tokenized_pro
         params = init_params(clip_model, n_ctx)
     Cn, n_ctx, H, _ = _check_prompts(who, clip_model, tokenized_prompts, params, seq_rows)
     if shard is not None:
-        check_shard(who, shard, Cn, False, val, final_model)
+        sharding.check(who, shard, n_cls=Cn, val=val, final_model=final_model)
     E, D = int(clip_model.geometry.embed_dim), int(clip_model.ln_final.weight.shape[0])
     if not isinstance(features, torch.Tensor) or features.dim() != 2 or features.shape[0] < 1 or features.shape[1] != E:
         raise ValueError(f"{who}: features must be a [N >= 1, E = {E}] tensor")

@@ -56,15 +56,13 @@ strictly best epoch in a device slot, the reference's TEST.FINAL_MODEL (base_lea
 wait.  DESIGN.md "Fit monitor".
 
 ``shard=Shard(world, rank, gather)`` on ``CoOpFitState``, ``fit_context`` and ``context_gradient``: the class-sharded fit, this project's
-form of the reference's ``nn.DataParallel`` around the text encoder (coop.py:266-272).  One process per GPU; rank r owns the contiguous
-classes of the balanced split and runs the tower's forward and backward over its own prompts only; the raw text features are gathered and
-compacted (csrc/shard_train.hip), the loss head runs replicated on every rank, and the context's gradient is the ranks' partial class sums
-gathered and added in rank order, so every rank ends a step with the same bits.  A class-specific context keeps its own rows per rank
-(``gathered_context()``).  With ``world == 1`` the bits are the unsharded path's.  ``gather``: ``parallel.shard_gather(exchange)`` over
-RCCL, or one ``LocalGather`` shared by all the ranks' states in one process on one GPU (a step of one state then steps them all, and the
-others' ``step`` is refused).
-Refused under ``shard``, each by name: C < world, a class-token position other than "end", ``grad_scale="dynamic"``, ``val=`` /
-``final_model="best_val"``, ``one_call=True``.  DESIGN.md "Class-sharded CoOp fit".
+form of the reference's ``nn.DataParallel`` around the text encoder (coop.py:266-272); ``shard.py`` has ``Shard``, ``LocalGather`` and the
+protocol every sharded fit follows.  Rank r owns the contiguous classes of the balanced split and runs the tower's forward and backward
+over its own prompts only; the raw text features are gathered and compacted (csrc/shard_train.hip), the loss head runs replicated on every
+rank, and the context's gradient is the ranks' partial class sums gathered and added in rank order, so every rank ends a step with the
+same bits.  A class-specific context keeps its own rows per rank (``gathered_context()``).  With ``world == 1`` the bits are the unsharded
+path's.  Refused under ``shard``, each by name (``shard.check``): C < world, a class-token position other than "end",
+``grad_scale="dynamic"``, ``val=`` / ``final_model="best_val"``, ``one_call=True``.  DESIGN.md "Class-sharded CoOp fit".
 
 ``optimizer``: "sgd" (the default: everything above, the same launches and bits), "adam" or "adamw" with ``betas`` and ``eps``, the
 reference's OPTIM.NAME, for all three methods.  The context's gradient is formed by the step entry without being applied and
@@ -85,8 +83,10 @@ import numpy as np
 import torch
 
 from . import _lib, fitloop, fitmonitor, ops
+from . import shard as sharding      # under its own name: ``shard`` is every entry point's argument
 from ._lib import _DT, check, lib
 from .fitloop import _host_int_array, _need_gpu, steps_per_epoch
+from .shard import LocalGather, Shard, shard_classes, shard_states
 
 # 2^12, measured on the ViT-B/16 text geometry with synthetic weights (profiles/coopfit_parity.txt, "grad_scale"): the smallest of 2^0, 2^4,
 # 2^8, 2^12, 2^16 that leaves under 1 % of the fp16 dgrad-GEMM operand elements subnormal (0.76 %; 6.8 % at 2^8, 52 % at 2^0) with at least
@@ -305,133 +305,6 @@ def _check_method(who: str, method: str, teacher, w: float, T: float, lam: float
         raise ValueError(f"{who}: lam={lam} (finite)")
 
 
-# ---- class sharding (DESIGN.md "Class-sharded CoOp fit"): one shard state per rank, two all-gathers per step
-
-class LocalGather:
-    """The gather of ``world`` shard states that live in ONE process on one GPU: the states' phases run one after the other on one
-    stream, each rank posts its send and receive blocks through its own port, and the post that completes the set fills every rank's
-    receive block with device copies, rank-major -- what ``clipmi_allgather`` leaves.  The whole feature runs on a single GPU this way,
-    through the kernels and the phase code of the multi-process run; it is the oracle that run is compared with bit for bit."""
-
-    def __init__(self, world: int):
-        if isinstance(world, bool) or int(world) != world or world < 1:
-            raise ValueError(f"LocalGather: world={world} must be an integer >= 1")
-        self.world = int(world)
-        self.states = [None] * self.world      # the shard states, filed by their rank as they are made
-        self.driver = None                     # the state whose ``step`` steps them all: the first that steps
-        self._posts = {}
-
-    def port(self, rank: int):
-        """Rank ``rank``'s ``gather(src, dst, bytes_per_rank, stream)``."""
-        def gather(src: torch.Tensor, dst: torch.Tensor, nbytes: int, stream: int) -> None:
-            self._posts[rank] = (src, dst)
-            if len(self._posts) < self.world:
-                return
-            posts, self._posts = self._posts, {}
-            srcs = [posts[r][0].view(-1).view(torch.uint8)[:nbytes] for r in range(self.world)]
-            if stream != ops._stream():     # torch enqueues the copies on its current stream: it must be the one the phases launched on
-                raise RuntimeError("LocalGather: the gather was asked for on a stream that is not torch's current stream")
-            for r in range(self.world):
-                out = posts[r][1].view(-1).view(torch.uint8)
-                for s in range(self.world):
-                    out[s * nbytes:(s + 1) * nbytes].copy_(srcs[s])
-        return gather
-
-
-class Shard:
-    """Which part of a class-sharded fit a state is: ``world`` ranks, this one's ``rank``, and ``gather(src, dst, bytes_per_rank,
-    stream)``, which leaves rank r's ``src`` in ``dst[r * bytes_per_rank : (r + 1) * bytes_per_rank]`` on every rank, in stream order
-    (``src``, ``dst``: contiguous device tensors).  ``gather``: ``parallel.shard_gather(exchange)`` for one process per GPU over RCCL,
-    or a ``LocalGather`` shared by the ``world`` states of one process."""
-
-    def __init__(self, world: int, rank: int, gather):
-        for name, v in (("world", world), ("rank", rank)):
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-                raise ValueError(f"Shard: {name}={v!r} must be an integer")
-        if world < 1 or not 0 <= rank < world:
-            raise ValueError(f"Shard: rank={rank} outside world={world}")
-        self.world, self.rank = int(world), int(rank)
-        self.local = gather if isinstance(gather, LocalGather) else None
-        if self.local is not None and self.local.world != self.world:
-            raise ValueError(f"Shard: world={world} but the LocalGather was made for {self.local.world}")
-        if self.local is None and not callable(gather):
-            raise ValueError("Shard: gather must be a LocalGather or a callable gather(src, dst, bytes_per_rank, stream)")
-        self.gather = self.local.port(self.rank) if self.local is not None else gather
-
-    def peer(self, rank: int) -> "Shard":
-        """Rank ``rank`` of the same local world."""
-        return Shard(self.world, rank, self.local)
-
-
-def shard_classes(n_cls: int, world: int, rank: int) -> Tuple[int, int]:
-    """Classes [lo, hi) of ``n_cls`` that ``rank`` of ``world`` owns: contiguous, the first ``n_cls mod world`` ranks one class more."""
-    from .parallel import shard_bounds
-    if n_cls < world:
-        raise ValueError(f"shard: C={n_cls} classes cannot be split over world={world} ranks (C < G: a rank would own no class)")
-    return shard_bounds(n_cls, rank, world)
-
-
-def _check_shard(who: str, shard, n_cls: int, class_token_position, grad_scale, val=None, final_model: str = "last_step") -> None:
-    """What the first version of the sharded fit refuses, each by name, before any device call."""
-    if not isinstance(shard, Shard):
-        raise ValueError(f"{who}: shard must be a coopfit.Shard(world, rank, gather), got {type(shard).__name__}")
-    shard_classes(n_cls, shard.world, shard.rank)
-    if class_token_position != "end":
-        raise ValueError(f"{who}: shard covers class_token_position='end' only, not {class_token_position!r}")
-    if isinstance(grad_scale, str):
-        raise ValueError(f"{who}: shard needs a static grad_scale; the dynamic loss scale (grad_scale={grad_scale!r}) is not sharded")
-    if val is not None or final_model == "best_val":
-        raise ValueError(f"{who}: shard has no validation: val= and final_model='best_val' are not sharded")
-
-
-def shard_states(make, shard: Optional[Shard]):
-    """This rank's state from ``make(shard)``: under a ``LocalGather`` all the world's states are made here, one per rank, and the one
-    of ``shard.rank`` is returned (its ``step`` then steps them all); otherwise the one state."""
-    if shard is None or shard.local is None:
-        return make(shard)
-    return [make(shard.peer(r)) for r in range(shard.world)][shard.rank]
-
-
-def _file_state(shard: Shard, state) -> None:
-    """A new shard state files itself with its local gather (nothing to do under an RCCL gather)."""
-    if shard.local is not None:
-        shard.local.states[shard.rank], shard.local.driver = state, None      # a new set of states chooses its driver anew
-
-
-def _world_states(shard: Shard, state, who: str):
-    """The states whose phases this process runs: ``state`` alone, or all of a local gather's world."""
-    local = shard.local
-    if local is None:
-        return [state]
-    if any(s is None for s in local.states):
-        raise ValueError(f"{who}: the LocalGather holds {sum(s is not None for s in local.states)} of its {local.world} shard states; "
-                         "make one state per rank before the first step")
-    return local.states
-
-
-def _drive(shard: Shard, state, who: str) -> None:
-    """Under a local gather one state drives: a caller who stepped every rank's state, as under RCCL, would take G steps.  The first state
-    that steps is the driver; a step of another state is refused."""
-    local = shard.local
-    if local is None:
-        return
-    if local.driver is None:
-        local.driver = state
-    if local.driver is not state:
-        raise ValueError(f"{who}: under a LocalGather the step of rank {local.driver.shard.rank}'s state steps every rank; "
-                         f"rank {shard.rank}'s state must not be stepped as well")
-
-
-def _run_phases(gens) -> None:
-    """Advance the shard states' phase generators in lock step, rank after rank, until they end (they end together: every rank runs the
-    same phases).  One generator under an RCCL gather; all ``world`` under a local one, where a phase's last post completes the gather."""
-    live = True
-    while live:
-        for g in gens:
-            if next(g, StopIteration) is StopIteration:
-                live = False
-
-
 def _pack_dgrad(model, blocks, projection: torch.Tensor, struct, slot: str):
     """The transposed fp16 copies of a frozen tower's weights (``struct``: clipmi_text_dgrad or clipmi_vision_dgrad, ``projection`` as it
     lies), packed once per bound model and again when a weight's version moves; the model keeps them under ``slot``."""
@@ -578,9 +451,8 @@ def context_gradient(clip_model, tokenized_prompts, ctx: torch.Tensor, features:
     who = "context_gradient"
     Cn, n_ctx, per_class, last = _check_prompts(who, clip_model, tokenized_prompts, ctx)
     if shard is not None:
-        _check_shard(who, shard, Cn, class_token_position, grad_scale)
-        if return_operand_stats:
-            raise ValueError(f"{who}: shard returns no operand statistics (return_operand_stats=True)")
+        sharding.check(who, shard, "coop", n_cls=Cn, class_token_position=class_token_position, grad_scale=grad_scale,
+                       return_operand_stats=return_operand_stats)
         return _sharded_gradient(clip_model, tokenized_prompts, ctx, features, labels, logit_scale, grad_scale, seq_rows, method, teacher, w, T, lam,
                                  return_parts, shard)
     placement = _placement(who, tokenized_prompts, n_ctx, class_token_position, name_lens)
@@ -626,13 +498,12 @@ def _sharded_gradient(clip_model, tokenized_prompts, ctx, features, labels, logi
     state = shard_states(make, shard)
     labels_d = _check_batch("context_gradient", features, labels, state.C, state.tower.E)
     _need_gpu(features, "features")
-    dev = features.device
-    states = state._shard_states("context_gradient")
-    reports, losses = [{} for _ in states], [_new_losses(method, dev) for _ in states]
-    _run_phases([s._shard_phases(features, labels_d, None, l, True, r) for s, l, r in zip(states, losses, reports)])
-    k = states.index(state)
-    report, loss3 = reports[k], losses[k]
-    parts = {}
+
+    def phases(s, report):
+        report["losses"] = _new_losses(method, features.device)
+        return s._shard_phases(features, labels_d, None, report["losses"], True, report)
+    report = sharding.report_all(shard, state, "context_gradient", phases)
+    loss3, parts = report["losses"], {}
     if method == "kgcoop":
         parts = {"ce": loss3[1:2], "score": loss3[2:3]}
     elif method == "prograd":
@@ -667,7 +538,7 @@ class CoOpFitState(fitmonitor.Monitored):
         self.C, self.n_ctx, self.per_class, last = _check_prompts(who, clip_model, tokenized_prompts, ctx)
         self.shard = shard
         if shard is not None:
-            _check_shard(who, shard, self.C, class_token_position, grad_scale)
+            sharding.check(who, shard, "coop", n_cls=self.C, class_token_position=class_token_position, grad_scale=grad_scale)
         placement = _placement(who, tokenized_prompts, self.n_ctx, class_token_position, name_lens)
         _static_prograd(who, method, grad_scale)
         self.dynamic, self.grad_scale, self.scaler = _scale_args(who, grad_scale, scaler)
@@ -726,7 +597,7 @@ class CoOpFitState(fitmonitor.Monitored):
             self._all_dots = torch.empty(n, 3, dtype=torch.float64, device=dev)
             self._prograd_ws = ops.shard_prograd_workspace(self.ctx.numel(), dev)
         self._rows = None           # gathered_context's blocks, made on first use
-        _file_state(sh, self)
+        sharding.file_state(sh, self)
 
     def _gather_rows(self, own: torch.Tensor):
         """A phase: the ranks' own rows of a class-specific [C_r, n_ctx, D] block gathered into the full [C, n_ctx, D]; the result is
@@ -786,17 +657,13 @@ class CoOpFitState(fitmonitor.Monitored):
             grad = self._rows[2].clone()
         report["grad"] = grad
 
-    def _shard_states(self, who: str):
-        """The states whose phases this process runs: this one alone, or all of a local gather's world."""
-        return _world_states(self.shard, self, who)
-
     def gathered_context(self) -> torch.Tensor:
         """The whole context on the device: ``ctx`` itself for a generic context (every rank holds the same bits) and without ``shard``;
         for a class-specific context under ``shard`` the ranks' rows gathered into a fresh [C, n_ctx, D] -- one all-gather that every
         rank enters (under a local gather this call runs it for all of them)."""
         if self.shard is None or not self.per_class:
             return self.ctx
-        _run_phases([s._gather_rows(s.ctx) for s in self._shard_states("CoOpFitState.gathered_context")])
+        sharding.run_all(self.shard, self, "CoOpFitState.gathered_context", lambda s: s._gather_rows(s.ctx))
         return self._rows[2].clone()
 
     # ---- per-epoch validation and best-epoch selection on the device (csrc/fit_monitor.hip, DESIGN.md "Fit monitor")
@@ -905,13 +772,9 @@ class CoOpFitState(fitmonitor.Monitored):
         losses = _new_losses(self.method, dev)
         if self.shard is not None:
             # every rank is given the same batch; under a local gather this call steps all the world's states, one phase at a time
-            if one_call:
-                raise ValueError("CoOpFitState.step: shard has no one-call step (one_call=True); the sharded step is the separate calls")
-            states = self._shard_states("CoOpFitState.step")
-            _drive(self.shard, self, "CoOpFitState.step")
-            _run_phases([s._shard_phases(features, labels_d, lr_d, losses if s is self else _new_losses(s.method, dev), first) for s in states])
-            for s in states:
-                s.steps += s is not self
+            sharding.check("CoOpFitState.step", self.shard, "coop", one_call=one_call)
+            sharding.step_all(sharding.drive(self.shard, self, "CoOpFitState.step"), self,
+                              lambda s: s._shard_phases(features, labels_d, lr_d, losses if s is self else _new_losses(s.method, dev), first))
         elif self._adam is not None:
             if one_call:
                 raise ValueError(f"CoOpFitState.step: one_call=True with optimizer={self.optimizer!r}: the one-call steps stay SGD")
@@ -995,7 +858,7 @@ def fit_context(features: torch.Tensor, labels, clip_model, tokenized_prompts, c
         ctx = init_context(clip_model, n_ctx, ids.shape[0] if csc else None)
     Cn, n_ctx, per_class, _ = _check_prompts(who, clip_model, tokenized_prompts, ctx)
     if shard is not None:
-        _check_shard(who, shard, Cn, class_token_position, grad_scale, val, final_model)
+        sharding.check(who, shard, "coop", n_cls=Cn, class_token_position=class_token_position, grad_scale=grad_scale, val=val, final_model=final_model)
     E = int(clip_model.geometry.embed_dim)
     if not isinstance(features, torch.Tensor) or features.dim() != 2 or features.shape[0] < 1 or features.shape[1] != E:
         raise ValueError(f"{who}: features must be a [N >= 1, E = {E}] tensor")

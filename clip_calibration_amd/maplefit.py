@@ -54,6 +54,7 @@ import torch
 from . import _lib, fitloop, fitmonitor, ops
 from ._lib import _DT, check, lib
 from . import coopfit, vptfit
+from . import shard as sharding
 from .coopfit import DYNAMIC, Shard, _check_grad_scale, _is_dynamic
 
 # 2^10, one power of two for both towers' backwards, measured at ViT-B/16 with synthetic weights, n_ctx 2, depth 9, batch 4, 100 classes
@@ -256,7 +257,7 @@ def gradients(model, learner_params: Dict[str, torch.Tensor], images: torch.Tens
         raise ValueError(f"{who}: grad_scale={DYNAMIC!r} belongs to a fit (MaPLeFitState, fit_prompt_learner); one gradient needs a number")
     gs = _check_grad_scale(who, grad_scale)
     if shard is not None:
-        vptfit.check_shard(who, shard, return_operand_stats=return_operand_stats)
+        sharding.check(who, shard, "block", return_operand_stats=return_operand_stats)
         state = coopfit.shard_states(lambda sh: MaPLeFitState(model, tokenized_prompts, learner_params, logit_scale, 0.0, 0.0, False, 0.0, gs, seq_rows,
                                                               class_token_position, shard=sh), shard)
         losses, grad = state._shard_gradient(who, images, labels)
@@ -402,7 +403,7 @@ def fit_prompt_learner(images_or_loader, labels, model, tokenized_prompts, learn
     over all C prompts on every rank."""
     who = "fit_prompt_learner"
     if shard is not None:
-        vptfit.check_shard(who, shard, val=val, final_model=final_model)
+        sharding.check(who, shard, "block", val=val, final_model=final_model)
     fitmonitor.check_image_args(who, val, val_batch_size, val_bins, final_model, val_criterion)
     epochs = int(epochs)
     if epochs < 0:
@@ -411,7 +412,7 @@ def fit_prompt_learner(images_or_loader, labels, model, tokenized_prompts, learn
         fitloop.check_optimizer(who, optimizer, momentum, dampening, nesterov, weight_decay, betas, eps)
     if learner_params is None:
         learner_params = init_learner_params(model, n_ctx, depth)
-    vptfit.check_shard_batches(who, shard, images_or_loader, batch_size, drop_last)
+    sharding.check_batches(who, shard, images_or_loader, batch_size, drop_last)
     state = coopfit.shard_states(lambda sh: MaPLeFitState(model, tokenized_prompts, learner_params, logit_scale, momentum, dampening, nesterov, weight_decay,
                                                           grad_scale, seq_rows, class_token_position, scaler, optimizer, betas, eps, sh), shard)
     batches = fitloop.cut_batches(who, images_or_loader, labels, state.C, batch_size, drop_last, model.device)

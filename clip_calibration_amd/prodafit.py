@@ -69,11 +69,13 @@ import numpy as np
 import torch
 
 from . import _lib, fitloop, fitmonitor, ops
+from . import shard as sharding
 from ._lib import check, lib
-from .coopfit import (DEFAULT_GRAD_SCALE, DYNAMIC, MAX_LIVE_ROWS, _DT, Shard, _AdamBlock, _BlockScaler, _Tower, _check_batch, _check_grad_scale, _drive,
-                      _file_state, _is_dynamic, _live_rows, _run_phases, _scale_args, _world_states, operand_stats_dict, shard_states)
+from .coopfit import (DEFAULT_GRAD_SCALE, DYNAMIC, MAX_LIVE_ROWS, _DT, _AdamBlock, _BlockScaler, _Tower, _check_batch, _check_grad_scale, _is_dynamic,
+                      _live_rows, _scale_args, operand_stats_dict)
 from .fitloop import _host_int_array, _need_gpu, steps_per_epoch
 from .parallel import shard_bounds
+from .shard import Shard, shard_states
 
 
 def positions(n_prompt: int) -> np.ndarray:
@@ -215,21 +217,6 @@ class _ProDATower(_Tower):
         return self.step_ws
 
 
-def check_shard(who: str, shard, n_cls: int, n_prompt: int, one_call: bool = False, val=None, final_model: str = "last_step") -> None:
-    """What the class-sharded ProDA fit refuses, each by name, before any device call (the optimiser is ``fitloop.check_optimizer``'s
-    to refuse)."""
-    if not isinstance(shard, Shard):
-        raise ValueError(f"{who}: shard must be a coopfit.Shard(world, rank, gather), got {type(shard).__name__}")
-    if n_cls < shard.world:
-        raise ValueError(f"{who}: shard: C={n_cls} classes cannot be split over world={shard.world} ranks (C < G: a rank would own no class)")
-    if n_prompt < shard.world:
-        raise ValueError(f"{who}: shard: P={n_prompt} no-class prompts cannot be dealt out to world={shard.world} ranks (P < G: a rank would own none)")
-    if one_call:
-        raise ValueError(f"{who}: shard has no one-call step (one_call=True); the sharded step is the separate calls")
-    if val is not None or final_model == "best_val":
-        raise ValueError(f"{who}: shard has no validation: val=, val_loader= and final_model='best_val' are not sharded")
-
-
 def context_gradient(clip_model, tokenized_prompts, ctx: torch.Tensor, features: torch.Tensor, labels, sel=None, name_lens=None, alpha: float = 0.1,
                      logit_scale: float = 4.6052, grad_scale: float = DEFAULT_GRAD_SCALE, seq_rows: Optional[int] = None, return_parts: bool = False,
                      return_operand_stats: bool = False, shard: Optional[Shard] = None):
@@ -247,9 +234,7 @@ def context_gradient(clip_model, tokenized_prompts, ctx: torch.Tensor, features:
     who = "context_gradient"
     ids_all, Cn, P, n_ctx, nl, last = _check_prompts(who, clip_model, tokenized_prompts, ctx, name_lens, seq_rows)
     if shard is not None:
-        check_shard(who, shard, Cn, P)
-        if return_operand_stats:
-            raise ValueError(f"{who}: shard returns no operand statistics (return_operand_stats=True)")
+        sharding.check(who, shard, n_cls=Cn, n_prompt=P, return_operand_stats=return_operand_stats)
     pos = positions(P)
     sel_h = _check_sel(who, np.arange(P) if sel is None else sel, P, pos)
     if sel_h.ndim != 1:
@@ -268,12 +253,13 @@ def context_gradient(clip_model, tokenized_prompts, ctx: torch.Tensor, features:
         make = lambda sh: ProDAFitState(clip_model, tokenized_prompts, ctx, len(sel_h), alpha, logit_scale, 0.0, 0.0, False, 0.0, gs, seq_rows, name_lens,
                                         shard=sh)
         state = shard_states(make, shard)
-        states = _world_states(shard, state, who)
         sel_d = torch.from_numpy(sel_h).to(dev)
-        reports, losses = [{} for _ in states], [torch.empty(3, dtype=torch.float32, device=dev) for _ in states]
-        _run_phases([s._shard_phases(features, labels_d, sel_d, None, l, True, r) for s, l, r in zip(states, losses, reports)])
-        k = states.index(state)
-        losses, grad, text = losses[k], reports[k]["grad"], reports[k]["text"]
+
+        def phases(s, report):
+            report["losses"] = torch.empty(3, dtype=torch.float32, device=dev)
+            return s._shard_phases(features, labels_d, sel_d, None, report["losses"], True, report)
+        report = sharding.report_all(shard, state, who, phases)
+        losses, grad, text = report["losses"], report["grad"], report["text"]
     else:
         tower = _ProDATower(who, clip_model, ids_all, Cn, P, len(sel_h), n_ctx, nl, last, seq_rows)
         sel_d = torch.from_numpy(sel_h).to(dev)
@@ -317,7 +303,7 @@ class ProDAFitState(fitmonitor.Monitored):
         _check_collection(who, self.P, self.Pb)
         self.shard = shard
         if shard is not None:
-            check_shard(who, shard, self.C, self.P)
+            sharding.check(who, shard, n_cls=self.C, n_prompt=self.P)
         self.alpha = _check_alpha(who, alpha)
         self.dynamic, self.grad_scale, self.scaler = _scale_args(who, grad_scale, scaler)
         self.optimizer, momentum, dampening, nesterov, betas = fitloop.check_optimizer(who, optimizer, momentum, dampening, nesterov, weight_decay, betas, eps,
@@ -369,7 +355,7 @@ class ProDAFitState(fitmonitor.Monitored):
         slots = self.Pb + -(-self.P // G)          # the class sums of the Pb selected contexts | the rank's no-class rows, padded
         self._send_part = torch.empty(slots, t.n_ctx, t.D, **f32)
         self._all_part = torch.empty(G, slots * t.n_ctx * t.D, **f32)
-        _file_state(sh, self)
+        sharding.file_state(sh, self)
 
     def _shard_phases(self, features, labels_d, sel_d, lr_d, losses, first: bool, report: Optional[dict] = None):
         """One sharded step as phases, a ``yield`` behind every gather.  ``report``: a dict that receives the reduced gradient and the
@@ -513,10 +499,8 @@ class ProDAFitState(fitmonitor.Monitored):
         if self.shard is not None:
             # every rank is given the same batch; under a local gather this call steps all the world's states, one phase at a time, and
             # this state alone draws the selection
-            if one_call:
-                raise ValueError(f"{who}: shard has no one-call step (one_call=True); the sharded step is the separate calls")
-            states = _world_states(self.shard, self, who)
-            _drive(self.shard, self, who)
+            sharding.check(who, self.shard, one_call=one_call)
+            states = sharding.drive(self.shard, self, who)
         labels_d = _check_batch(who, features, labels, self.C, self.tower.E)
         _need_gpu(features, "features")
         if features.dtype != torch.float32 or features.stride(1) != 1:
@@ -536,9 +520,7 @@ class ProDAFitState(fitmonitor.Monitored):
         sgd = (self.momentum, self.dampening, self.weight_decay, self.nesterov)
         losses = torch.empty(3, dtype=torch.float32, device=dev)
         if states is not None:
-            _run_phases([s._shard_phases(features, labels_d, sel_d, lr_d, losses if s is self else torch.empty_like(losses), first) for s in states])
-            for s in states:
-                s.steps += s is not self
+            sharding.step_all(states, self, lambda s: s._shard_phases(features, labels_d, sel_d, lr_d, losses if s is self else torch.empty_like(losses), first))
         elif self._adam is not None:
             gs = 1.0 if self.dynamic else self.grad_scale
             text = t.forward(self.ctx, sel_d)
@@ -648,7 +630,7 @@ def fit_context(features: torch.Tensor, labels, clip_model, tokenized_prompts, c
     _, Cn, P, n_ctx, _, _ = _check_prompts(who, clip_model, tokenized_prompts, ctx, name_lens, seq_rows)
     _check_collection(who, P, int(prompt_bs))
     if shard is not None:
-        check_shard(who, shard, Cn, P, False, val, final_model)
+        sharding.check(who, shard, n_cls=Cn, n_prompt=P, val=val, final_model=final_model)
     E = int(clip_model.geometry.embed_dim)
     if not isinstance(features, torch.Tensor) or features.dim() != 2 or features.shape[0] < 1 or features.shape[1] != E:
         raise ValueError(f"{who}: features must be a [N >= 1, E = {E}] tensor")

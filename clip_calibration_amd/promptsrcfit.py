@@ -57,6 +57,7 @@ import torch
 from . import _lib, fitloop, fitmonitor, ops
 from ._lib import _DT, check, lib
 from . import coopfit, maplefit, vptfit
+from . import shard as sharding
 from .coopfit import DYNAMIC, Shard, _check_grad_scale, _is_dynamic
 from .fitloop import _need_gpu
 
@@ -297,7 +298,7 @@ def gradients(model, params: Dict[str, torch.Tensor], images: torch.Tensor, labe
     gs = _check_grad_scale(who, grad_scale)
     wt, wi, wl = _method_weights(who, method, w_text, w_image, w_logit)
     if shard is not None:
-        vptfit.check_shard(who, shard, return_operand_stats=return_operand_stats)
+        sharding.check(who, shard, "block", return_operand_stats=return_operand_stats)
         if return_features:
             raise ValueError(f"{who}: shard returns no features (return_features=True): they are per rank")
         state = coopfit.shard_states(lambda sh: PromptSRCFitState(model, tokenized_prompts, params, teacher, logit_scale, w_text, w_image, w_logit, 0.0, 0.0,
@@ -404,7 +405,7 @@ class PromptSRCFitState(vptfit._BlockFitState):
         """GPA: add ``weight`` times the block as it stands to the running sum (one launch; the first call initialises the sum).  Under
         ``shard`` every rank keeps its own sum of the same bits; with a ``LocalGather`` this call serves all the world's states, as
         ``step`` does."""
-        for s in self._world("PromptSRCFitState.end_epoch"):
+        for s in sharding.world_states(self.shard, self, "PromptSRCFitState.end_epoch"):
             if s.gpa is None:
                 s.gpa = torch.empty_like(s.block)
             gpa_accumulate(s.block, s.gpa, weight, s.epochs_seen == 0)
@@ -412,7 +413,7 @@ class PromptSRCFitState(vptfit._BlockFitState):
 
     def apply_gpa(self) -> None:
         """The running sum replaces the parameters (after the last epoch)."""
-        for s in self._world("PromptSRCFitState.apply_gpa"):
+        for s in sharding.world_states(self.shard, self, "PromptSRCFitState.apply_gpa"):
             if s.gpa is not None:
                 s.block.copy_(s.gpa)
 
@@ -473,7 +474,7 @@ def fit_prompts(images_or_loader, labels, model, tokenized_prompts, teacher: tor
     tower runs over all C prompts on every rank, and every rank keeps GPA's sum.  ``one_call=True`` is refused as well."""
     who = "fit_prompts"
     if shard is not None:
-        vptfit.check_shard(who, shard, one_call=one_call, val=val, final_model=final_model)
+        sharding.check(who, shard, "block", one_call=one_call, val=val, final_model=final_model)
     fitmonitor.check_image_args(who, val, val_batch_size, val_bins, final_model, val_criterion)
     epochs = int(epochs)
     if epochs < 0:
@@ -484,7 +485,7 @@ def fit_prompts(images_or_loader, labels, model, tokenized_prompts, teacher: tor
         fitloop.check_optimizer(who, optimizer, momentum, dampening, nesterov, weight_decay, betas, eps, one_call=one_call)
     if params is None:
         params = init_params(model)
-    vptfit.check_shard_batches(who, shard, images_or_loader, batch_size, drop_last)
+    sharding.check_batches(who, shard, images_or_loader, batch_size, drop_last)
     state = coopfit.shard_states(lambda sh: PromptSRCFitState(model, tokenized_prompts, params, teacher, logit_scale, w_text, w_image, w_logit, momentum,
                                                               dampening, nesterov, weight_decay, grad_scale, seq_rows, method, class_token_position, scaler,
                                                               optimizer, betas, eps, sh), shard)

@@ -32,14 +32,16 @@ def cached_features(who: str, clip_model, loader):
     return torch.cat(feats), torch.cat(labels)
 
 
-def batch_shard(who: str, fit_args: dict):
-    """``fit_args``' ``shard`` (or None) after the refusals of the batch-sharded image-tower fits (``vptfit.check_shard``), validation by
-    ``val_loader=`` included: called in front of ``validation_set``, before either tower runs."""
+def checked_shard(who: str, fit_args: dict, family=None, **facts):
+    """``fit_args``' ``shard`` (or None) after ``shard.check``'s refusals in ``family``'s words, validation by ``val_loader=`` included:
+    called in front of ``validation_set``, before either tower runs.  ``facts``: what the trainer knows (``n_cls``, ``n_prompt``, ..)."""
     shard = fit_args.get("shard")
     if shard is not None:
-        from ..vptfit import check_shard
+        from ..shard import check
+        if family != "coop":    # coopfit's entry points take no ``one_call``
+            facts["one_call"] = bool(fit_args.get("one_call", False))
         val = fit_args.get("val_loader") if fit_args.get("val_loader") is not None else fit_args.get("val")
-        check_shard(who, shard, bool(fit_args.get("one_call", False)), val, fit_args.get("final_model", "last_step"))
+        check(who, shard, family, val=val, final_model=fit_args.get("final_model", "last_step"), **facts)
     return shard
 
 

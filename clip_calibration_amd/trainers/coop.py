@@ -200,14 +200,9 @@ class CustomCLIP(nn.Module):
         refuses -- validation by ``val_loader=`` included -- is refused here, before either tower runs.  With a ``LocalGather`` the one
         call makes and steps all the ranks' states, on either route."""
         import math
+        shard = _fit.checked_shard("fit_context", fit_args, "coop", n_cls=self.prompt_learner.tokenized_prompts.shape[0], grad_scale=fit_args.get("grad_scale"),
+                                   class_token_position=fit_args.get("class_token_position", getattr(self.prompt_learner, "class_token_position", "end")))
         val_loader = fit_args.pop("val_loader", None)
-        shard = fit_args.get("shard")
-        if shard is not None:
-            from ..coopfit import DEFAULT_GRAD_SCALE, _check_shard
-            _check_shard("fit_context", shard, self.prompt_learner.tokenized_prompts.shape[0],
-                         fit_args.get("class_token_position", getattr(self.prompt_learner, "class_token_position", "end")),
-                         fit_args.get("grad_scale", DEFAULT_GRAD_SCALE), val_loader if val_loader is not None else fit_args.get("val"),
-                         fit_args.get("final_model", "last_step"))
         if val_loader is not None and fit_args.get("val") is not None:
             raise ValueError("fit_context: val_loader and val are two ways to give one validation set")
         monitored = val_loader is not None or any(k in fit_args for k in ("val", "val_bins", "final_model", "val_criterion", "return_monitor"))

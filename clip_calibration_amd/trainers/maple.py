@@ -96,7 +96,7 @@ class CustomCLIP(_CoOpCLIP):
         ``final_model="best_val"`` installs the best epoch's parameters."""
         import math
         from .. import maplefit
-        shard = _fit.batch_shard("fit_prompt_learner", fit_args)
+        shard = _fit.checked_shard("fit_prompt_learner", fit_args, "block")
         _fit.validation_set("fit_prompt_learner", None, fit_args)
         fit_args.setdefault("logit_scale", math.log(self.scale))
         fit_args.setdefault("class_token_position", getattr(self.prompt_learner, "class_token_position", "end"))

@@ -122,12 +122,7 @@ class CustomCLIP(nn.Module):
         here, before either tower runs.  With a ``LocalGather`` the one call makes and steps all the ranks' states, on either route."""
         import math
         who = "fit_context"
-        shard = fit_args.get("shard")
-        if shard is not None:
-            from ..prodafit import check_shard
-            val = fit_args.get("val_loader") if fit_args.get("val_loader") is not None else fit_args.get("val")
-            check_shard(who, shard, self.prompt_learner.tokenized_prompts.shape[0], self.prompt_learner.ctx.shape[0], bool(fit_args.get("one_call", False)),
-                        val, fit_args.get("final_model", "last_step"))
+        shard = _fit.checked_shard(who, fit_args, n_cls=self.prompt_learner.tokenized_prompts.shape[0], n_prompt=self.prompt_learner.ctx.shape[0])
         _fit.validation_set(who, self.clip_model, fit_args)
         fit_args.setdefault("logit_scale", math.log(self.scale))
         dynamic = fit_args.get("grad_scale") == "dynamic"

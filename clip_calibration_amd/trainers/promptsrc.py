@@ -83,7 +83,7 @@ class CustomCLIP(_CoOpCLIP):
         the best epoch's parameters."""
         import math
         from .. import promptsrcfit
-        shard = _fit.batch_shard("fit_prompts", fit_args)
+        shard = _fit.checked_shard("fit_prompts", fit_args, "block")
         _fit.validation_set("fit_prompts", None, fit_args)
         fit_args.setdefault("logit_scale", math.log(self.scale))
         fit_args.setdefault("class_token_position", getattr(self.prompt_learner, "class_token_position", "end"))

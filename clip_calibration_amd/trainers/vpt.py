@@ -45,7 +45,7 @@ class CustomCLIP(ZeroshotCLIP):
         ``final_model="best_val"`` installs the best epoch's prompts into the parameters."""
         import math
         from .. import vptfit
-        shard = _fit.batch_shard("fit_prompts", fit_args)
+        shard = _fit.checked_shard("fit_prompts", fit_args, "block")
         _fit.validation_set("fit_prompts", None, fit_args)
         fit_args.setdefault("logit_scale", math.log(self.scale))
         text = self.text_features.float()

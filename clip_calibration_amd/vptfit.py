@@ -53,10 +53,12 @@ from typing import Optional, Sequence
 
 import torch
 
-from . import _lib, coopfit, fitloop, fitmonitor, ops
+from . import _lib, fitloop, fitmonitor, ops
+from . import shard as sharding
 from ._lib import _DT, check, lib
-from .coopfit import DYNAMIC, Shard, _AdamBlock, _BlockScaler, _pack_dgrad, _check_grad_scale, _is_dynamic, _scale_args, operand_stats_dict
+from .coopfit import DYNAMIC, _AdamBlock, _BlockScaler, _pack_dgrad, _check_grad_scale, _is_dynamic, _scale_args, operand_stats_dict
 from .fitloop import _need_gpu
+from .shard import Shard, shard_states
 
 # 2^12: CoOp's value (profiles/coopfit_parity.txt) holds for the image tower's backward at the ViT-B/16 geometry as well
 # (profiles/vptfit_parity.txt, "grad_scale").  A model with much larger gradients overflows fp16 at this scale -- the prompts then turn
@@ -270,10 +272,10 @@ def prompt_gradient(model, prompts: torch.Tensor, images: torch.Tensor, labels, 
         raise ValueError(f"{who}: grad_scale={DYNAMIC!r} belongs to a fit (VPTFitState, fit_prompts); one gradient needs a number")
     gs = _check_grad_scale(who, grad_scale)
     if shard is not None:
-        check_shard(who, shard, return_operand_stats=return_operand_stats)
+        sharding.check(who, shard, "block", return_operand_stats=return_operand_stats)
         if flags != _lib.CALL_DEFAULT:
             raise ValueError(f"{who}: shard takes the default call flags (flags={flags})")
-        state = coopfit.shard_states(lambda sh: VPTFitState(model, text_features, logit_scale, prompts, 0.0, 0.0, False, 0.0, gs, shard=sh), shard)
+        state = shard_states(lambda sh: VPTFitState(model, text_features, logit_scale, prompts, 0.0, 0.0, False, 0.0, gs, shard=sh), shard)
         losses, grad = state._shard_gradient(who, images, labels)
         return losses[:1], grad
     scale = fitloop.exp_logit_scale(who, logit_scale)
@@ -302,37 +304,6 @@ def image_features(model, prompts: torch.Tensor, images: torch.Tensor) -> torch.
     return tower.forward(images, fitloop.master(prompts, images.device)).clone()
 
 
-def check_shard(who: str, shard, one_call: bool = False, val=None, final_model: str = "last_step", return_operand_stats: bool = False) -> None:
-    """What the batch-sharded fits refuse (``vptfit``, ``maplefit``, ``promptsrcfit``; DESIGN.md "Batch-sharded image-tower fits"), each by
-    name, before any device call."""
-    if not isinstance(shard, Shard):
-        raise ValueError(f"{who}: shard must be a coopfit.Shard(world, rank, gather), got {type(shard).__name__}")
-    if one_call:
-        raise ValueError(f"{who}: shard has no one-call step (one_call=True); the sharded step is the separate calls around one all-gather")
-    if val is not None or final_model == "best_val":
-        raise ValueError(f"{who}: shard has no validation: val=, val_loader= and final_model='best_val' are not sharded")
-    if return_operand_stats:
-        raise ValueError(f"{who}: shard returns no operand statistics (return_operand_stats=True): they are per rank")
-
-
-def check_shard_batch(who: str, shard: Shard, B: int) -> int:
-    """The images per rank of a batch of ``B`` under ``shard``; a batch that does not split evenly is refused."""
-    if B % shard.world:
-        raise ValueError(f"{who}: a batch of B={B} images does not split over G={shard.world} ranks (B must be a multiple of G; ragged "
-                         "batches are not sharded)")
-    return B // shard.world
-
-
-def check_shard_batches(who: str, shard: Optional[Shard], images_or_loader, batch_size, drop_last: bool) -> None:
-    """``check_shard_batch`` of the batches ``fitloop.cut_batches`` will cut from a tensor of images -- the full ones and the short last
-    one --, before any device call (a loader's batches meet the check in ``step``)."""
-    if shard is None or not isinstance(images_or_loader, torch.Tensor) or int(batch_size) < 1:
-        return
-    N, bs = images_or_loader.shape[0], int(batch_size)
-    for B in ([bs] if N >= bs else []) + ([N % bs] if N % bs and not drop_last else []):
-        check_shard_batch(who, shard, B)
-
-
 class _BlockFitState(fitmonitor.ImageMonitored):
     """What the states of the fits through the image tower share (VPTFitState, maplefit.MaPLeFitState, promptsrcfit.PromptSRCFitState): one
     fp32 master block under ``_master_name``, SGD's arguments and momentum buffer, the static or dynamic loss scale and the one ``step``.
@@ -345,10 +316,10 @@ class _BlockFitState(fitmonitor.ImageMonitored):
                         optimizer: str = "sgd", betas=(0.9, 0.999), eps: float = 1e-8, shard: Optional[Shard] = None) -> None:
         """The refusals that need no model, in the order every state has made them.  ``optimizer``: "sgd" (``momentum``, ``dampening``,
         ``nesterov``), "adam" or "adamw" (``betas``, ``eps``; ``weight_decay`` keeps the fit's own default -- torch's
-        AdamW default of 1e-2 is NOT taken over).  ``shard``: the batch-sharded fit (``check_shard``)."""
+        AdamW default of 1e-2 is NOT taken over).  ``shard``: the batch-sharded fit (``shard.check``)."""
         self.shard = shard
         if shard is not None:
-            check_shard(who, shard)
+            sharding.check(who, shard, "block")
         self.dynamic, self.grad_scale, self.scaler = _scale_args(who, grad_scale, scaler)
         self.optimizer, momentum, dampening, nesterov, self._betas = fitloop.check_optimizer(who, optimizer, momentum, dampening, nesterov, weight_decay,
                                                                                              betas, eps)
@@ -374,7 +345,7 @@ class _BlockFitState(fitmonitor.ImageMonitored):
             self._send = torch.zeros(stride, dtype=torch.float32, device=master.device)
             self._recv = torch.empty(self.shard.world, stride, dtype=torch.float32, device=master.device)
             self._reduced = torch.empty(n, dtype=torch.float32, device=master.device)
-            coopfit._file_state(self.shard, self)
+            sharding.file_state(self.shard, self)
 
     def _grad_block(self) -> Optional[torch.Tensor]:
         """Where a deferred step entry leaves scale * gradient: the front of the send block under ``shard``, a block of the state's own
@@ -411,23 +382,20 @@ class _BlockFitState(fitmonitor.ImageMonitored):
         same bits on every rank; ``one_call`` is refused; under a ``LocalGather`` the step of one state steps them all."""
         who = f"{self._who}.step"
         if self.shard is not None:
-            check_shard(who, self.shard, one_call)
+            sharding.check(who, self.shard, "block", one_call=one_call)
         if one_call and self._adam is not None:
             raise ValueError(f"{who}: one_call=True with optimizer={self.optimizer!r}: the one-call steps stay SGD")
         v = self._vision()
         images = v.images(who, images)
         dev, B = images.device, images.shape[0]
         if self.shard is not None:
-            check_shard_batch(who, self.shard, B)
+            sharding.check_batch(who, self.shard, B)
         labels_d = fitloop.step_labels(who, labels, B, self.C, dev, "images")
         lr_d = ops._dev(fitloop.lr_operand(lr, dev), "lr", (torch.float32,))
         if self.shard is not None:
             # every rank is given the same batch; under a local gather this call steps all the world's states, one phase at a time
-            states = coopfit._world_states(self.shard, self, who)
-            coopfit._drive(self.shard, self, who)
-            coopfit._run_phases([s._shard_phases(images, labels_d, lr_d) for s in states])
-            for s in states:
-                s.steps += 1
+            sharding.step_all(sharding.drive(self.shard, self, who), self, lambda s: s._shard_phases(images, labels_d, lr_d))
+            self.steps += 1
             return self.last_losses[:1] if want_loss else None
         first = self.steps == 0
         sgd = (float(self.momentum), float(self.dampening), float(self.weight_decay), int(bool(self.nesterov)))
@@ -459,16 +427,12 @@ class _BlockFitState(fitmonitor.ImageMonitored):
 
     # ---- the batch-sharded step (csrc/shard_train.hip, DESIGN.md "Batch-sharded image-tower fits")
 
-    def _world(self, who: str):
-        """The states a call on this one serves: itself, or under a ``LocalGather`` all the world's."""
-        return [self] if self.shard is None else coopfit._world_states(self.shard, self, who)
-
     def _no_shard_validate(self, who: str) -> None:
         if self.shard is not None:
             raise ValueError(f"{who}: shard has no validation (validate: the sharded fit scores nothing between epochs)")
 
     def _shard_phases(self, images: torch.Tensor, labels_d: torch.Tensor, lr_d: Optional[torch.Tensor], report: Optional[dict] = None):
-        """One sharded step as phases, a ``yield`` behind the gather (``coopfit._run_phases``).  The rank's own rows of the whole batch
+        """One sharded step as phases, a ``yield`` behind the gather (``shard.run_phases``).  The rank's own rows of the whole batch
         go through the unsharded step's launches up to the block's step entry, which leaves scale * gradient in the send block beside
         the head's losses; one all-gather; the rank-ordered mean; the unsharded route's step on the block every rank agrees on.
         ``report``: a dict that receives the reduced ``grad`` and ``losses`` INSTEAD of a step (static scale): nothing is updated."""
@@ -503,12 +467,9 @@ class _BlockFitState(fitmonitor.ImageMonitored):
         """``(losses fp32 [n_losses], grad of the master's shape)`` of the whole batch, reduced over the ranks: the diagnostic entry
         points under ``shard``.  Under a local gather this call runs every rank's phases."""
         images = self._vision().images(who, images)
-        check_shard_batch(who, self.shard, images.shape[0])
+        sharding.check_batch(who, self.shard, images.shape[0])
         labels_d = fitloop.step_labels(who, labels, images.shape[0], self.C, images.device, "images")
-        states = coopfit._world_states(self.shard, self, who)
-        reports = [{} for _ in states]
-        coopfit._run_phases([s._shard_phases(images, labels_d, None, r) for s, r in zip(states, reports)])
-        report = reports[states.index(self)]
+        report = sharding.report_all(self.shard, self, who, lambda s, r: s._shard_phases(images, labels_d, None, r))
         return report["losses"], report["grad"]
 
 
@@ -615,16 +576,16 @@ def fit_prompts(images_or_loader, labels, model, text_features: torch.Tensor, pr
     ``final_model="best_val"`` are refused."""
     who = "fit_prompts"
     if shard is not None:
-        check_shard(who, shard, val=val, final_model=final_model)
+        sharding.check(who, shard, "block", val=val, final_model=final_model)
     fitmonitor.check_image_args(who, val, val_batch_size, val_bins, final_model, val_criterion)
     epochs = int(epochs)
     if epochs < 0:
         raise ValueError(f"{who}: epochs={epochs} (>= 0)")
     if optimizer != "sgd":      # by this function's name; SGD's arguments are the state's to check, as before
         fitloop.check_optimizer(who, optimizer, momentum, dampening, nesterov, weight_decay, betas, eps)
-    check_shard_batches(who, shard, images_or_loader, batch_size, drop_last)
-    state = coopfit.shard_states(lambda sh: VPTFitState(model, text_features, logit_scale, prompts, momentum, dampening, nesterov, weight_decay, grad_scale,
-                                                        scaler, optimizer, betas, eps, sh), shard)
+    sharding.check_batches(who, shard, images_or_loader, batch_size, drop_last)
+    state = shard_states(lambda sh: VPTFitState(model, text_features, logit_scale, prompts, momentum, dampening, nesterov, weight_decay, grad_scale,
+                                                scaler, optimizer, betas, eps, sh), shard)
     batches = fitloop.cut_batches(who, images_or_loader, labels, state.C, batch_size, drop_last, model.device)
     _, lr_steps = fitloop.schedule(who, lr, epochs, lr_per_epoch, len(batches), model.device)
     end_epoch = None

@@ -14,7 +14,7 @@ import maplefit_ref
 import promptsrcfit_ref
 import vptfit_ref
 
-from clip_calibration_amd import _lib, coopfit, maplefit, promptsrcfit, vptfit  # noqa: E402
+from clip_calibration_amd import _lib, coopfit, maplefit, promptsrcfit, shard, vptfit  # noqa: E402
 from clip_calibration_amd.model import build_model  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -158,18 +158,18 @@ def test_trainers_refuse_before_either_tower_runs():
     from clip_calibration_amd.trainers import _fit
     for who in ("fit_prompts", "fit_prompt_learner"):
         with pytest.raises(ValueError, match=f"{who}: shard has no validation"):
-            _fit.batch_shard(who, {"shard": two(), "val_loader": object()})
+            _fit.checked_shard(who, {"shard": two(), "val_loader": object()}, "block")
         with pytest.raises(ValueError, match=f"{who}: shard has no one-call step"):
-            _fit.batch_shard(who, {"shard": two(), "one_call": True})
-        assert _fit.batch_shard(who, {"lr": 1e-3}) is None and isinstance(_fit.batch_shard(who, {"shard": two()}), coopfit.Shard)
+            _fit.checked_shard(who, {"shard": two(), "one_call": True}, "block")
+        assert _fit.checked_shard(who, {"lr": 1e-3}, "block") is None and isinstance(_fit.checked_shard(who, {"shard": two()}, "block"), coopfit.Shard)
 
 
 def test_check_shard_batch():
     sh = coopfit.Shard(4, 1, coopfit.LocalGather(4))
-    assert vptfit.check_shard_batch("f", sh, 8) == 2 and vptfit.check_shard_batch("f", sh, 4) == 1
+    assert shard.check_batch("f", sh, 8) == 2 and shard.check_batch("f", sh, 4) == 1
     for B in (1, 3, 6):
         with pytest.raises(ValueError, match=f"f: a batch of B={B} images does not split over G=4 ranks"):
-            vptfit.check_shard_batch("f", sh, B)
+            shard.check_batch("f", sh, B)
 
 
 def test_header_and_binding_carry_the_entry_points():

@@ -9,7 +9,7 @@ import cocoopfit_ref as cref
 import cocoopshard_ref as sref
 import coopfit_ref
 
-from clip_calibration_amd import _lib, cocoopfit, coopfit  # noqa: E402
+from clip_calibration_amd import _lib, cocoopfit, coopfit, shard  # noqa: E402
 from clip_calibration_amd.model import build_model  # noqa: E402
 
 B, N_CTX, L, D, E, H = 2, 4, 9, 6, 5, 3
@@ -113,11 +113,11 @@ def test_refusals_name_their_cause_before_any_device_call(cpu_model):
         clip.fit_prompt_learner(object(), shard=two(), one_call=True)
     with pytest.raises(ValueError, match="fit_prompt_learner: shard must be a coopfit.Shard"):
         clip.fit_prompt_learner(object(), shard="two")
-    # check_shard itself: the one-call step, which only CoCoOpFitState.step takes (tests/test_gpu_cocoopshard.py steps a state)
+    # shard.check itself: the one-call step, which only CoCoOpFitState.step takes (tests/test_gpu_cocoopshard.py steps a state)
     with pytest.raises(ValueError, match=r"f: shard has no one-call step \(one_call=True\)"):
-        cocoopfit.check_shard("f", two(), 5, one_call=True)
+        shard.check("f", two(), n_cls=5, one_call=True)
     with pytest.raises(ValueError, match="f: shard has no validation"):
-        cocoopfit.check_shard("f", two(), 5, final_model="best_val")
+        shard.check("f", two(), n_cls=5, final_model="best_val")
 
 
 def test_header_and_binding_carry_the_entry_points():

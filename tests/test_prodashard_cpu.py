@@ -9,7 +9,7 @@ import coopfit_ref
 import prodafit_ref as dref
 import prodashard_ref as sref
 
-from clip_calibration_amd import _lib, coopfit, prodafit  # noqa: E402
+from clip_calibration_amd import _lib, coopfit, prodafit, shard  # noqa: E402
 from clip_calibration_amd.model import build_model  # noqa: E402
 from clip_calibration_amd.parallel import shard_bounds  # noqa: E402
 
@@ -115,11 +115,11 @@ def test_refusals_name_their_cause_before_any_device_call(cpu_model):
         clip.fit_context(object(), shard=two(), val_loader=object())
     with pytest.raises(ValueError, match="fit_context: shard: C=5 classes cannot be split over world=8"):
         clip.fit_context(object(), shard=coopfit.Shard(8, 0, coopfit.LocalGather(8)))
-    # check_shard itself: the one-call step, which only ProDAFitState.step takes (tests/test_gpu_prodashard.py steps a state)
+    # shard.check itself: the one-call step, which only ProDAFitState.step takes (tests/test_gpu_prodashard.py steps a state)
     with pytest.raises(ValueError, match=r"f: shard has no one-call step \(one_call=True\)"):
-        prodafit.check_shard("f", two(), 5, 8, one_call=True)
+        shard.check("f", two(), n_cls=5, n_prompt=8, one_call=True)
     with pytest.raises(ValueError, match="f: shard has no validation"):
-        prodafit.check_shard("f", two(), 5, 8, final_model="best_val")
+        shard.check("f", two(), n_cls=5, n_prompt=8, final_model="best_val")
 
 
 def test_header_and_binding_carry_the_entry_points():
