@@ -58,11 +58,10 @@ from typing import Dict, Optional, Sequence
 import numpy as np
 import torch
 
-from . import _lib, fitloop, fitmonitor, ops
+from . import _lib, fitloop, fitmonitor, fitoptim, ops
 from ._lib import check, lib
 from . import shard as sharding
-from .coopfit import (DYNAMIC, MAX_LIVE_ROWS, _DT, _AdamBlock, _BlockScaler, _Tower, _check_batch, _check_grad_scale, _is_dynamic, _live_rows, _scale_args,
-                      operand_stats_dict)
+from .coopfit import MAX_LIVE_ROWS, _DT, _Tower, _check_batch, _live_rows, operand_stats_dict
 from .coopfit import _check_prompts as _check_coop_prompts
 from .fitloop import _host_int_array, _need_gpu, steps_per_epoch
 from .shard import Shard, shard_classes, shard_states
@@ -189,9 +188,7 @@ def gradients(clip_model, tokenized_prompts, params, features: torch.Tensor, lab
     Cn, n_ctx, H, last = _check_prompts(who, clip_model, tokenized_prompts, params, seq_rows)
     if shard is not None:
         sharding.check(who, shard, n_cls=Cn, return_operand_stats=return_operand_stats)
-    if _is_dynamic(who, grad_scale):
-        raise ValueError(f"{who}: grad_scale={DYNAMIC!r} belongs to a fit (CoCoOpFitState, fit_prompt_learner); one gradient needs a number")
-    gs = _check_grad_scale(who, grad_scale)
+    gs = fitoptim.static_grad_scale(who, grad_scale, "CoCoOpFitState", "fit_prompt_learner")
     scale = fitloop.exp_logit_scale(who, logit_scale)
     E = int(clip_model.geometry.embed_dim)
     labels_d = _check_batch(who, features, labels, Cn, E)
@@ -221,11 +218,12 @@ def gradients(clip_model, tokenized_prompts, params, features: torch.Tensor, lab
     return out
 
 
-class CoCoOpFitState(fitmonitor.Monitored):
+class CoCoOpFitState(fitmonitor.Monitored, fitoptim.Optimised):
     """The training state of CoCoOp's prompt learner: the fp32 master block ``[ctx | W1 | b1 | W2 | b2]``, SGD's momentum block, the
     tower's stash (one per batch size seen) and the number of steps taken.  ``step`` enqueues one forward, backward and update and does
     not synchronise.  ``validate`` scores cached validation features through the inference forward (``start_monitor``, ``monitor``,
-    ``best_params``, ``val_row_results``: ``fitmonitor.Monitored`` on a ``fitmonitor.ImageMonitor``, whose row results it fills)."""
+    ``best_params``, ``val_row_results``: ``fitmonitor.Monitored`` on a ``fitmonitor.ImageMonitor``, whose row results it fills).  The
+    loss scale, the optimiser's arguments and moments and ``scaler_state`` are ``fitoptim.Optimised``'s."""
     _who, _history = "CoCoOpFitState", fitmonitor.ImageMonitor
 
     def __init__(self, clip_model, tokenized_prompts, params, logit_scale: float = 4.6052, momentum: float = 0.9,
@@ -241,22 +239,16 @@ class CoCoOpFitState(fitmonitor.Monitored):
         self.shard = shard
         if shard is not None:
             sharding.check(who, shard, n_cls=self.C)
-        self.dynamic, self.grad_scale, self.scaler = _scale_args(who, grad_scale, scaler)
-        self.optimizer, momentum, dampening, nesterov, betas = fitloop.check_optimizer(who, optimizer, momentum, dampening, nesterov, weight_decay, betas, eps)
-        self.scale = fitloop.exp_logit_scale(who, logit_scale)
+        self._init_optimiser(who, logit_scale, momentum, dampening, nesterov, weight_decay, grad_scale, scaler, optimizer, betas, eps)
         dev = clip_model.device
         if dev.type != "cuda":
             raise RuntimeError(f"clipmi: {who} needs the model on a ROCm GPU (model.to('cuda')); the HIP path has no CPU fallback")
         self.model, self.ids, self.seq_rows = clip_model, tokenized_prompts, seq_rows
         self.D, self.E = int(clip_model.ln_final.weight.shape[0]), int(clip_model.geometry.embed_dim)
         self.block = _master_block(params, self.n_ctx, self.D, self.E, self.H, dev)
-        self.buf = torch.zeros_like(self.block) if momentum != 0.0 else None
+        self._init_moments(self.block)
         self._views = ops.cocoop_block_views(self.block, self.n_ctx, self.D, self.E, self.H)
-        self.momentum, self.dampening, self.nesterov, self.weight_decay = momentum, dampening, nesterov, weight_decay
         self._towers: Dict[int, _CoCoOpTower] = {}
-        self.steps = 0
-        self._scaler = _BlockScaler(self.scaler, dev) if self.dynamic else None
-        self._adam = _AdamBlock(self.optimizer, betas, eps, weight_decay, self.block) if self.optimizer != "sgd" else None
         self._val = None            # what a validation keeps between epochs: the inference operands and one workspace per chunk size
         self.val_stream_f16 = True  # trainers.cocoop.CustomCLIP's text_stream_f16: validation runs the tower as that forward does
         self.val_batch_size = None  # validate's chunk when its argument is None (None: the largest training batch seen)
@@ -264,13 +256,6 @@ class CoCoOpFitState(fitmonitor.Monitored):
             self.lo, self.hi = shard_classes(self.C, shard.world, shard.rank)
             self._own_ids = _host_int_array(who, tokenized_prompts, "tokenized_prompts")[self.lo:self.hi]
             sharding.file_state(shard, self)
-
-    def scaler_state(self) -> dict:
-        """The dynamic scale's block as ``dict(scale, growth_tracker, skipped_steps, applied_steps, found_inf)`` (``found_inf``: of the
-        last step).  It waits for the steps enqueued so far: one synchronisation, the only read-back of the dynamic path."""
-        if not self.dynamic:
-            raise ValueError(f"CoCoOpFitState.scaler_state: the state was made with a static grad_scale={self.grad_scale}")
-        return self._scaler.state()
 
     # ---- per-epoch validation and best-epoch selection on the device (DESIGN.md "Fit monitor", "CoCoOp and ProDA")
 
@@ -386,16 +371,14 @@ class CoCoOpFitState(fitmonitor.Monitored):
         """One sharded step as phases, a ``yield`` behind every gather.  ``report``: a dict that receives the reduced gradient block,
         the loss and the parts ``gradients`` returns INSTEAD of a step: no block of the state is touched."""
         B, sh, st = int(features.shape[0]), self.shard, ops._stream()
-        t = self.tower(B)
-        gs = 1.0 if self.dynamic else self.grad_scale
+        t, gs = self.tower(B), self._head_scale
         t.forward(self._views, features)                                   # the meta-net over all B rows, then the rank's own B C_r prompts
         sh.gather(t.send_text, t.all_text, t.send_text.numel() * 4, st)
         yield
         text = ops.cocoop_shard_compact(t.all_text, B, self.C, t.E, t.full_text)
         head = ops.cocoop_head(features, labels_d, text, self.scale, gs, loss, want_rows=report is not None)
         own = ops.cocoop_shard_rows(head[1], B, self.lo, self.hi, t.own_d_text)   # the rank's own rows of the replicated d_text
-        if self.dynamic:
-            ops.grad_scale_rows(own, self._scaler.block)
+        self._scale_rows(own)
         ops.cocoop_dcs_partial(t.backward(own), B, t.n_cls, t.n_ctx, t.send_part)
         sh.gather(t.send_part, t.all_part, t.send_part.numel() * 4, st)
         yield
@@ -404,13 +387,10 @@ class CoCoOpFitState(fitmonitor.Monitored):
             report.update(grad=grad.clone(), loss=loss, text=text.clone(), x_n=t.meta[0].clone(), hid=t.meta[1].clone(), pi=t.meta[2].clone(),
                           rows=head[2])
             return
-        sgd = (self.momentum, self.dampening, self.weight_decay, self.nesterov)
-        if self._adam is not None:
-            self._adam.step(grad, self.block, lr_d, 1.0, self._scaler)
-        elif self.dynamic:
-            self._scaler.step(grad, self.block, self.buf, lr_d, *sgd)
-        else:
-            ops.cocoop_step(grad, self.block, self.buf, lr_d, self.n_ctx, self.D, self.E, self.H, first, *sgd)
+        self._apply_block(grad, lr_d, lambda: self._static_step(grad, lr_d, first))
+
+    def _static_step(self, grad: torch.Tensor, lr_d: torch.Tensor, first: bool) -> None:
+        ops.cocoop_step(grad, self.block, self.buf, lr_d, self.n_ctx, self.D, self.E, self.H, first, *self._sgd)
 
     def step(self, features: torch.Tensor, labels, lr, want_loss: bool = False, one_call: bool = False) -> Optional[torch.Tensor]:
         """One optimiser step on the batch ``features`` fp32 [B, E] and ``labels`` [B] at the rate ``lr``, as ``CoOpFitState.step`` takes
@@ -426,8 +406,7 @@ class CoCoOpFitState(fitmonitor.Monitored):
         who = "CoCoOpFitState.step"
         if self.shard is not None:
             sharding.check(who, self.shard, one_call=one_call)
-        if one_call and self._adam is not None:
-            raise ValueError(f"{who}: one_call=True with optimizer={self.optimizer!r}: the one-call steps stay SGD")
+        self._no_one_call_adam(who, one_call)
         states = sharding.drive(self.shard, self, who) if self.shard is not None else None
         labels_d = _check_batch(who, features, labels, self.C, self.E)
         _need_gpu(features, "features")
@@ -441,46 +420,24 @@ class CoCoOpFitState(fitmonitor.Monitored):
             sharding.step_all(states, self, lambda s: s._shard_phases(features, labels_d, lr_d, loss if s is self else torch.empty_like(loss), first))
             self.steps += 1
             return loss if want_loss else None
-        t, m = self.tower(int(features.shape[0])), self.model
-        sgd = (self.momentum, self.dampening, self.weight_decay, self.nesterov)
-        if self._adam is not None:
-            gs = 1.0 if self.dynamic else self.grad_scale
+        t, m, sc = self.tower(int(features.shape[0])), self.model, self._scaler
+        if one_call:        # one of two symbols (static or scaled) on one run of arguments
+            ws = t.one_call_workspace(scaled=self.dynamic)
+            name = "clipmi_cocoop_train_step" + ("_scaled" if self.dynamic else "")
+            front = (m._handle, C.byref(t.dgrad[0]), t.base.data_ptr(), _DT[t.base.dtype], self.block.data_ptr(),
+                     None if self.buf is None else self.buf.data_ptr(), t.n_ctx, t.H, t.cls_eot.data_ptr(), t.n_cls, t.rows, features.data_ptr(),
+                     features.stride(0), labels_d.data_ptr(), features.shape[0], self.scale)
+            how = (sc.block.data_ptr(), *sc.args(), lr_d.data_ptr()) if self.dynamic else (self.grad_scale, lr_d.data_ptr(), int(first))
+            with m._launch_lock:
+                check(getattr(lib, name)(*front, *how, *self._sgd, loss.data_ptr(), None, ws.data_ptr(), ws.numel(), t.stash.data_ptr(), t.stash.numel(),
+                                         ops._stream()), name)
+        else:
+            gs = self._head_scale
             text = t.forward(self._views, features)
             _, d_text = ops.cocoop_head(features, labels_d, text, self.scale, gs, loss)
-            if self.dynamic:
-                ops.grad_scale_rows(d_text, self._scaler.block)
-            self._adam.step(t.reduce(t.backward(d_text), self._views[NAMES[3]], gs), self.block, lr_d, 1.0, self._scaler)
-        elif self.dynamic and one_call:
-            ws, sc = t.one_call_workspace(scaled=True), self._scaler
-            with m._launch_lock:
-                check(lib.clipmi_cocoop_train_step_scaled(m._handle, C.byref(t.dgrad[0]), t.base.data_ptr(), _DT[t.base.dtype], self.block.data_ptr(),
-                                                          None if self.buf is None else self.buf.data_ptr(), t.n_ctx, t.H, t.cls_eot.data_ptr(), t.n_cls,
-                                                          t.rows, features.data_ptr(), features.stride(0), labels_d.data_ptr(), features.shape[0],
-                                                          self.scale, sc.block.data_ptr(), *sc.args(), lr_d.data_ptr(), *map(float, sgd[:3]),
-                                                          int(bool(sgd[3])), loss.data_ptr(), None, ws.data_ptr(), ws.numel(), t.stash.data_ptr(),
-                                                          t.stash.numel(), ops._stream()),
-                      "clipmi_cocoop_train_step_scaled")
-        elif self.dynamic:
-            text = t.forward(self._views, features)
-            _, d_text = ops.cocoop_head(features, labels_d, text, self.scale, 1.0, loss)
-            ops.grad_scale_rows(d_text, self._scaler.block)
-            grad = t.reduce(t.backward(d_text), self._views[NAMES[3]], 1.0)
-            self._scaler.step(grad, self.block, self.buf, lr_d, *sgd)
-        elif one_call:
-            ws = t.one_call_workspace()
-            with m._launch_lock:
-                check(lib.clipmi_cocoop_train_step(m._handle, C.byref(t.dgrad[0]), t.base.data_ptr(), _DT[t.base.dtype], self.block.data_ptr(),
-                                                   None if self.buf is None else self.buf.data_ptr(), t.n_ctx, t.H, t.cls_eot.data_ptr(), t.n_cls, t.rows,
-                                                   features.data_ptr(), features.stride(0), labels_d.data_ptr(), features.shape[0], self.scale,
-                                                   self.grad_scale, lr_d.data_ptr(), int(first), *map(float, sgd[:3]), int(bool(sgd[3])), loss.data_ptr(),
-                                                   None, ws.data_ptr(), ws.numel(), t.stash.data_ptr(), t.stash.numel(), ops._stream()),
-                      "clipmi_cocoop_train_step")
-        else:
-            text = t.forward(self._views, features)
-            _, d_text = ops.cocoop_head(features, labels_d, text, self.scale, self.grad_scale, loss)
-            d_embed = t.backward(d_text)
-            grad = t.reduce(d_embed, self._views[NAMES[3]], self.grad_scale)
-            ops.cocoop_step(grad, self.block, self.buf, lr_d, self.n_ctx, self.D, self.E, self.H, first, *sgd)
+            self._scale_rows(d_text)
+            grad = t.reduce(t.backward(d_text), self._views[NAMES[3]], gs)
+            self._apply_block(grad, lr_d, lambda: self._static_step(grad, lr_d, first))
         self.steps += 1
         return loss if want_loss else None
 
@@ -554,8 +511,7 @@ def fit_prompt_learner(features: torch.Tensor, labels, clip_model, tokenized_pro
         raise ValueError(f"{who}: features must be a [N >= 1, E = {E}] tensor")
     N = features.shape[0]
     epochs, batch_size = fitloop.check_run(who, epochs, batch_size)
-    fitloop.check_optimizer(who, optimizer, momentum, dampening, nesterov, weight_decay, betas, eps)
-    _scale_args(who, grad_scale, scaler)
+    fitoptim.check_fit(who, optimizer, momentum, dampening, nesterov, weight_decay, betas, eps, grad_scale, scaler)
     lab = fitloop._labels(who, labels, N, Cn)
     order = fitloop.check_order(who, order, epochs, N)
     per_epoch = steps_per_epoch(N, batch_size, drop_last)

@@ -67,8 +67,11 @@ path's.  Refused under ``shard``, each by name (``shard.check``): C < world, a c
 ``optimizer``: "sgd" (the default: everything above, the same launches and bits), "adam" or "adamw" with ``betas`` and ``eps``, the
 reference's OPTIM.NAME, for all three methods.  The context's gradient is formed by the step entry without being applied and
 clipmi_block_step_adam (csrc/optim_step.hip) applies ``torch.optim.Adam``'s or ``torch.optim.AdamW``'s rule to the master context;
-``_AdamBlock`` keeps the moments and the bias-correction table beside it, for this fit and the five others.  DESIGN.md "Adam steps for
-the prompt fits".
+``fitoptim._AdamBlock`` keeps the moments and the bias-correction table beside it.  DESIGN.md "Adam steps for the prompt fits".
+
+The loss scale's argument rules, the scaler's device block, Adam's moments and the mix-in every fit state takes them through
+(``fitoptim.Optimised``) live in ``fitoptim.py``, for this fit and the five others; this module re-exports ``DYNAMIC`` from there and
+keeps ``DEFAULT_GRAD_SCALE``.  DESIGN.md "Fit optimiser: shared plumbing".
 
 Not covered: ``nn.DataParallel`` itself in one process (``shard=`` stands in for it, with the refusals above), ProGrad under a dynamic loss
 scale, and models whose text tower carries deep prompts.
@@ -82,7 +85,7 @@ from typing import Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import _lib, fitloop, fitmonitor, ops
+from . import _lib, fitloop, fitmonitor, fitoptim, ops
 from . import shard as sharding      # under its own name: ``shard`` is every entry point's argument
 from ._lib import _DT, check, lib
 from .fitloop import _host_int_array, _need_gpu, steps_per_epoch
@@ -95,125 +98,13 @@ from .shard import LocalGather, Shard, shard_classes, shard_states
 DEFAULT_GRAD_SCALE = 4096.0
 
 
-def _check_grad_scale(who: str, grad_scale: float) -> float:
-    g = float(grad_scale)
-    if not (math.isfinite(g) and g > 0.0 and math.frexp(g)[0] == 0.5):
-        raise ValueError(f"{who}: grad_scale={grad_scale} must be a power of two (the scaling has to be exact)")
-    return g
-
-
-DYNAMIC = "dynamic"
-
-
-def _is_dynamic(who: str, grad_scale) -> bool:
-    """True for ``grad_scale="dynamic"``; any other string is refused, a number is the static path's."""
-    if isinstance(grad_scale, str):
-        if grad_scale != DYNAMIC:
-            raise ValueError(f"{who}: grad_scale={grad_scale!r} must be a power of two or {DYNAMIC!r}")
-        return True
-    return False
-
-
-def _check_scaler(who: str, scaler) -> dict:
-    """torch.cuda.amp.GradScaler's arguments with its defaults filled in; the scale and both factors must be powers of two."""
-    if scaler is not None and not isinstance(scaler, dict):
-        raise ValueError(f"{who}: scaler must be a dict of {sorted(ops.SCALER_DEFAULTS)} or None")
-    cfg = dict(ops.SCALER_DEFAULTS)
-    for k, v in (scaler or {}).items():
-        if k not in cfg:
-            raise ValueError(f"{who}: scaler has no option {k!r} (one of {sorted(cfg)})")
-        cfg[k] = v
-    for k in ("init_scale", "growth_factor", "backoff_factor"):
-        g = float(cfg[k])
-        if not (math.isfinite(g) and 2.0 ** -126 <= g <= 2.0 ** 127 and math.frexp(g)[0] == 0.5):
-            raise ValueError(f"{who}: scaler[{k!r}]={cfg[k]} must be a finite, positive power of two of fp32's range (the scaling has to be exact)")
-        cfg[k] = g
-    if cfg["growth_factor"] < 1.0 or cfg["backoff_factor"] > 1.0:
-        raise ValueError(f"{who}: scaler growth_factor={cfg['growth_factor']} (>= 1), backoff_factor={cfg['backoff_factor']} (<= 1)")
-    gi = cfg["growth_interval"]
-    if isinstance(gi, bool) or int(gi) != gi or not 1 <= int(gi) < 2 ** 31:
-        raise ValueError(f"{who}: scaler growth_interval={gi} must be an integer >= 1")
-    cfg["growth_interval"] = int(gi)
-    return cfg
-
-
-def _scale_args(who: str, grad_scale, scaler):
-    """``(dynamic, grad_scale, scaler)`` after the checks every fit makes of the pair: a number with no ``scaler`` (the static path; the
-    dict is then None), or ``"dynamic"`` with the scaler's dict filled in (the number is then None)."""
-    if _is_dynamic(who, grad_scale):
-        return True, None, _check_scaler(who, scaler)
-    if scaler is not None:
-        raise ValueError(f"{who}: scaler is an argument of grad_scale={DYNAMIC!r}")
-    return False, _check_grad_scale(who, grad_scale), None
+DYNAMIC = fitoptim.DYNAMIC     # re-exported: the value of ``grad_scale`` that asks for the dynamic loss scale (``fitoptim``)
 
 
 def _static_prograd(who: str, method: str, grad_scale) -> None:
     """ProGrad has no dynamic loss scale: its two gradients share one step."""
-    if method == "prograd" and _is_dynamic(who, grad_scale):
+    if method == "prograd" and fitoptim._is_dynamic(who, grad_scale):
         raise ValueError(f"{who}: grad_scale={DYNAMIC!r} covers method 'coop' and 'kgcoop'; ProGrad keeps a static scale")
-
-
-class _BlockScaler:
-    """The dynamic loss scale of a fit: the device block (clipmi_scaler_state; only the kernels touch it once it is made), the scaler's
-    arguments and the scaled step's workspace.  ``step`` is for the fits whose parameters are one fp32 master block (CoCoOp, VPT, MaPLe,
-    PromptSRC); CoOp's and ProDA's scaled steps are their own."""
-
-    def __init__(self, cfg: dict, dev):
-        self.cfg = cfg
-        self.block = ops.new_scaler_state(cfg["init_scale"], dev)
-        self.ws = None
-
-    def args(self):
-        """The three arguments every ``_scaled`` call takes behind the state block."""
-        return self.cfg["growth_factor"], self.cfg["backoff_factor"], self.cfg["growth_interval"]
-
-    def step(self, grad: torch.Tensor, params: torch.Tensor, buf: Optional[torch.Tensor], lr_d: torch.Tensor, momentum: float, dampening: float,
-             weight_decay: float, nesterov: bool) -> None:
-        """``ops.block_step_scaled`` on ``grad`` = scale * gradient: unscale, decide on the device, apply when clean."""
-        if self.ws is None:
-            self.ws = torch.empty(max(lib.clipmi_block_step_scaled_workspace_bytes(params.numel()), 256), dtype=torch.uint8, device=params.device)
-        ops.block_step_scaled(grad, self.block, params, buf, lr_d, *self.args(), momentum, dampening, weight_decay, nesterov, want_grad=False,
-                              workspace=self.ws)
-
-    def state(self) -> dict:
-        return ops.scaler_state_dict(self.block)
-
-
-class _AdamBlock:
-    """torch.optim.Adam's or AdamW's state beside a fit's fp32 master block (DESIGN.md "Adam steps for the prompt fits"): the two
-    moments, the bias-correction table on the device and the number of steps enqueued.  ``step`` applies a gradient block that the fit's
-    own launches formed without applying it; under a ``_BlockScaler`` the device decides whether the step counts, and ``steps_taken``
-    is then an upper bound of the applied steps, which is all the table's length has to cover."""
-    TABLE_STEPS = 1024     # the table's first length; it doubles when the steps reach it
-
-    def __init__(self, optimizer: str, betas, eps: float, weight_decay: float, master: torch.Tensor):
-        self.decoupled = optimizer == "adamw"
-        self.betas, self.eps, self.weight_decay = betas, float(eps), float(weight_decay)
-        self.exp_avg, self.exp_avg_sq = torch.zeros_like(master), torch.zeros_like(master)
-        self.steps_taken = 0
-        self.table = None
-        self.ws = None
-
-    def _table(self, dev) -> torch.Tensor:
-        """The table with a row for step ``steps_taken + 1``; a longer one is uploaded (in stream order) when it has none."""
-        need = self.steps_taken + 1
-        if self.table is None or self.table.shape[0] < need:
-            self.table = torch.from_numpy(fitloop.adam_bias_table(self.betas, max(self.TABLE_STEPS, 2 * need))).to(dev)
-        return self.table
-
-    def step(self, grad: torch.Tensor, params: torch.Tensor, lr_d: torch.Tensor, grad_scale: float = 1.0, scaler: Optional[_BlockScaler] = None) -> None:
-        """``ops.block_step_adam`` on ``grad`` = ``grad_scale`` * gradient, or, with ``scaler``, ``ops.block_step_adam_scaled`` on
-        ``grad`` = the scaler's scale * gradient."""
-        table = self._table(params.device)
-        rule = dict(betas=self.betas, eps=self.eps, weight_decay=self.weight_decay, decoupled=self.decoupled, want_grad=False)
-        if scaler is None:
-            ops.block_step_adam(grad, params, self.exp_avg, self.exp_avg_sq, lr_d, self.steps_taken + 1, table, grad_scale, **rule)
-        else:
-            if self.ws is None:
-                need = lib.clipmi_block_step_adam_scaled_workspace_bytes(params.numel())
-                self.ws = torch.empty(max(need, 256), dtype=torch.uint8, device=params.device)
-            ops.block_step_adam_scaled(grad, scaler.block, params, self.exp_avg, self.exp_avg_sq, lr_d, table, *scaler.args(), workspace=self.ws, **rule)
-        self.steps_taken += 1
 
 
 def _check_prompts(who: str, clip_model, tokenized_prompts, ctx) -> Tuple[int, int, bool, int]:
@@ -456,9 +347,7 @@ def context_gradient(clip_model, tokenized_prompts, ctx: torch.Tensor, features:
         return _sharded_gradient(clip_model, tokenized_prompts, ctx, features, labels, logit_scale, grad_scale, seq_rows, method, teacher, w, T, lam,
                                  return_parts, shard)
     placement = _placement(who, tokenized_prompts, n_ctx, class_token_position, name_lens)
-    if _is_dynamic(who, grad_scale):
-        raise ValueError(f"{who}: grad_scale={DYNAMIC!r} belongs to a fit (CoOpFitState, fit_context); one gradient needs a number")
-    gs = _check_grad_scale(who, grad_scale)
+    gs = fitoptim.static_grad_scale(who, grad_scale, "CoOpFitState", "fit_context")
     scale = fitloop.exp_logit_scale(who, logit_scale)
     E = int(clip_model.geometry.embed_dim)
     _check_method(who, method, teacher, w, T, lam, Cn, E)
@@ -521,10 +410,11 @@ def text_features(clip_model, tokenized_prompts, ctx: torch.Tensor, seq_rows: Op
     return tower.forward(fitloop.master(ctx, clip_model.device)).clone()
 
 
-class CoOpFitState(fitmonitor.Monitored):
+class CoOpFitState(fitmonitor.Monitored, fitoptim.Optimised):
     """The training state of CoOp's context: the fp32 master ``ctx``, SGD's momentum buffer, the tower's stash and the number of steps
     taken.  ``step`` enqueues one forward, backward and update and does not synchronise.  ``validate`` scores cached validation features
-    on the device (``start_monitor``, ``monitor``, ``best_context``, ``val_logits``: ``fitmonitor.Monitored`` on a ``fitmonitor.Monitor``)."""
+    on the device (``start_monitor``, ``monitor``, ``best_context``, ``val_logits``: ``fitmonitor.Monitored`` on a ``fitmonitor.Monitor``).
+    The loss scale, the optimiser's arguments and moments and ``scaler_state`` are ``fitoptim.Optimised``'s."""
     _who, _unseen_summary = "CoOpFitState", True
 
     def __init__(self, clip_model, tokenized_prompts, ctx: torch.Tensor, logit_scale: float = 4.6052, momentum: float = 0.9,
@@ -541,10 +431,7 @@ class CoOpFitState(fitmonitor.Monitored):
             sharding.check(who, shard, "coop", n_cls=self.C, class_token_position=class_token_position, grad_scale=grad_scale)
         placement = _placement(who, tokenized_prompts, self.n_ctx, class_token_position, name_lens)
         _static_prograd(who, method, grad_scale)
-        self.dynamic, self.grad_scale, self.scaler = _scale_args(who, grad_scale, scaler)
-        self.optimizer, momentum, dampening, nesterov, betas = fitloop.check_optimizer(who, optimizer, momentum, dampening, nesterov, weight_decay, betas,
-                                                                                       eps, shard=shard)
-        self.scale = fitloop.exp_logit_scale(who, logit_scale)
+        self._init_optimiser(who, logit_scale, momentum, dampening, nesterov, weight_decay, grad_scale, scaler, optimizer, betas, eps, sgd_shard=shard)
         _check_method(who, method, teacher, w, T, lam, self.C, int(clip_model.geometry.embed_dim))
         self.method, self.w, self.T, self.lam = method, float(w), float(T), float(lam)
         self.teacher = None
@@ -561,18 +448,7 @@ class CoOpFitState(fitmonitor.Monitored):
             self.tower = _Tower(who, clip_model, ids, self.hi - self.lo, self.n_ctx, self.per_class, last, seq_rows)
             self.ctx = fitloop.master(ctx[self.lo:self.hi] if self.per_class else ctx, dev)
             self._shard_buffers(dev)
-        self.buf = torch.zeros_like(self.ctx) if momentum != 0.0 else None
-        self.momentum, self.dampening, self.nesterov, self.weight_decay = momentum, dampening, nesterov, weight_decay
-        self.steps = 0
-        self._scaler = _BlockScaler(self.scaler, dev) if self.dynamic else None
-        self._adam = _AdamBlock(self.optimizer, betas, eps, weight_decay, self.ctx) if self.optimizer != "sgd" else None
-
-    def scaler_state(self) -> dict:
-        """The dynamic scale's block as ``dict(scale, growth_tracker, skipped_steps, applied_steps, found_inf)`` (``found_inf``: of the
-        last step).  It waits for the steps enqueued so far: one synchronisation."""
-        if not self.dynamic:
-            raise ValueError(f"CoOpFitState.scaler_state: the state was made with a static grad_scale={self.grad_scale}")
-        return self._scaler.state()
+        self._init_moments(self.ctx)
 
     # ---- the class-sharded step (csrc/shard_train.hip, DESIGN.md "Class-sharded CoOp fit")
 
@@ -619,7 +495,7 @@ class CoOpFitState(fitmonitor.Monitored):
         t, sh, st = self.tower, self.shard, ops._stream()
         step = report is None
         ctx, buf, lr_d = (self.ctx, self.buf, lr_d) if step else (None, None, None)
-        sgd = (self.momentum, self.dampening, self.weight_decay, self.nesterov)
+        sgd = self._sgd
         prograd = self.method == "prograd"
         t.forward(self.ctx)                                                                  # the rank's own prompts
         sh.gather(self._send_text, self._all_text, self._send_text.numel() * 4, st)
@@ -709,7 +585,7 @@ class CoOpFitState(fitmonitor.Monitored):
         head = (m._handle, C.byref(t.dgrad[0]), t.base.data_ptr(), _DT[t.base.dtype], self.ctx.data_ptr(), buf, t.n_ctx, int(t.per_class),
                 *(() if t.position is None else (t.position, t.name_lens.data_ptr())), t.eot.data_ptr(), t.C, t.rows, features.data_ptr(),
                 features.stride(0), labels_d.data_ptr(), features.shape[0], self.scale)
-        sgd = (float(self.momentum), float(self.dampening), float(self.weight_decay), int(bool(self.nesterov)))
+        sgd = self._sgd
         tail = (ws.data_ptr(), ws.numel(), t.stash.data_ptr(), t.stash.numel(), ops._stream())
         mode = ops.PROMPT_MODES[self.method]
         if self.dynamic:
@@ -719,39 +595,40 @@ class CoOpFitState(fitmonitor.Monitored):
         with m._launch_lock:
             check(getattr(lib, name)(*head, *mid, *tail), name)
 
-    def _step_scaled(self, features, labels_d, lr_d, losses) -> None:
-        """``step`` under the dynamic scale: the head at grad_scale = 1, its d_text times the block's scale, the backward, and
-        clipmi_ctx_step_scaled, which decides on the device whether the step is applied."""
+    def _apply_scaled(self, d_embed: torch.Tensor, lr_d: torch.Tensor) -> None:
+        """SGD under the dynamic scale is CoOp's own kernel, not the block's: clipmi_ctx_step_scaled is handed the tower's input gradient,
+        forms the class sums itself and decides on the device whether the step is applied."""
         t, sc = self.tower, self._scaler
-        text = t.forward(self.ctx)
-        _, d_text, _ = ops.prompt_head(features, labels_d, text, self.scale, 1.0, self.method, self.teacher, self.w, 1.0, losses)
-        ops.grad_scale_rows(d_text, sc.block)
-        d_embed = t.context_rows(t.backward(d_text))
         if sc.ws is None:
             need = lib.clipmi_ctx_step_scaled_workspace_bytes(t.C, t.D, t.n_ctx, int(t.per_class))
             sc.ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.ctx.device)
-        ops.ctx_step_scaled(d_embed, t.C, t.n_ctx, t.per_class, sc.block, self.ctx, self.buf, lr_d, *sc.args(), float(self.momentum), float(self.dampening),
-                            float(self.weight_decay), bool(self.nesterov), want_grad=False, workspace=sc.ws)
+        ops.ctx_step_scaled(d_embed, t.C, t.n_ctx, t.per_class, sc.block, self.ctx, self.buf, lr_d, *sc.args(), *self._sgd, want_grad=False, workspace=sc.ws)
 
-    def _step_adam(self, features, labels_d, lr_d, losses) -> None:
-        """``step`` under Adam or AdamW: the SGD step's forward, head and backward(s), the context's gradient formed by the same step
-        entry WITHOUT applying it (``context_gradient``'s way; ProGrad's is the projected one), and the rule in ``_AdamBlock.step``.
-        Under the dynamic scale the backward carries scale * gradient as in ``_step_scaled``, the class sums are formed at
-        ``grad_scale = 1`` (clipmi_ctx_step_scaled's own first launch cannot be reached without its step) and handed on as they are:
-        clipmi_block_step_adam_scaled divides by the scale, as that launch does."""
-        t, sc = self.tower, self._scaler
+    def _separate_calls(self, features, labels_d, lr_d, losses, first: bool) -> None:
+        """``step`` launch by launch: the forward, the head at the head's scale, under the dynamic scale its d_text times the block's
+        scale, the backward(s), and the step.  Static SGD: the step entry (ProGrad's with its projection) forms the gradient and applies
+        it.  Dynamic SGD: ``_apply_scaled``.  Adam or AdamW: the same entry forms the gradient WITHOUT applying it (``context_gradient``'s
+        way; ProGrad's is the projected one; under the dynamic scale at ``grad_scale = 1``, since clipmi_ctx_step_scaled's own first
+        launch cannot be reached without its step) and ``_AdamBlock.step`` applies the rule -- clipmi_block_step_adam_scaled divides by
+        the scale, as that launch does.  ``T`` is 1 under the dynamic scale, where ProGrad is refused anyway."""
+        t, gs, prograd = self.tower, self._head_scale, self.method == "prograd"
         text = t.forward(self.ctx)
-        gs = 1.0 if self.dynamic else self.grad_scale
         _, d_text, d_kl = ops.prompt_head(features, labels_d, text, self.scale, gs, self.method, self.teacher, self.w, 1.0 if self.dynamic else self.T, losses)
-        if self.dynamic:
-            ops.grad_scale_rows(d_text, sc.block)
+        self._scale_rows(d_text)
         d_embed = t.context_rows(t.backward(d_text))
-        if self.method != "prograd":
-            grad = ops.ctx_step(d_embed, t.C, t.n_ctx, t.per_class, gs)
-        else:
-            d_embed_kl = t.context_rows(t.backward(d_kl, second=True), second=True)
+        d_embed_kl = t.context_rows(t.backward(d_kl, second=True), second=True) if prograd else None
+        grad = d_embed
+        if self._adam is not None and prograd:
             grad = ops.prograd_step(d_embed, d_embed_kl, t.C, t.n_ctx, t.per_class, gs, self.lam)[0]
-        self._adam.step(grad, self.ctx, lr_d, 1.0, sc)
+        elif self._adam is not None:
+            grad = ops.ctx_step(d_embed, t.C, t.n_ctx, t.per_class, gs)
+
+        def static_step():
+            if prograd:
+                ops.prograd_step(d_embed, d_embed_kl, t.C, t.n_ctx, t.per_class, gs, self.lam, self.ctx, self.buf, lr_d, first, *self._sgd, want_report=False)
+            else:
+                ops.ctx_step(d_embed, t.C, t.n_ctx, t.per_class, gs, self.ctx, self.buf, lr_d, first, *self._sgd, want_grad=False)
+        self._apply_block(grad, lr_d, static_step)
 
     def step(self, features: torch.Tensor, labels, lr, want_loss: bool = False, one_call: bool = False) -> Optional[torch.Tensor]:
         """One optimiser step on the batch ``features`` fp32 [B, E] (raw image features on the GPU) and ``labels`` [B] at the rate ``lr``:
@@ -767,32 +644,16 @@ class CoOpFitState(fitmonitor.Monitored):
             raise TypeError("CoOpFitState.step: features must be fp32 with unit column stride")
         dev = features.device
         lr_d = ops._dev(fitloop.lr_operand(lr, dev), "lr", (torch.float32,))
-        t, first = self.tower, self.steps == 0
-        sgd = (self.momentum, self.dampening, self.weight_decay, self.nesterov)
+        first = self.steps == 0
         losses = _new_losses(self.method, dev)
         if self.shard is not None:
             # every rank is given the same batch; under a local gather this call steps all the world's states, one phase at a time
             sharding.check("CoOpFitState.step", self.shard, "coop", one_call=one_call)
             sharding.step_all(sharding.drive(self.shard, self, "CoOpFitState.step"), self,
                               lambda s: s._shard_phases(features, labels_d, lr_d, losses if s is self else _new_losses(s.method, dev), first))
-        elif self._adam is not None:
-            if one_call:
-                raise ValueError(f"CoOpFitState.step: one_call=True with optimizer={self.optimizer!r}: the one-call steps stay SGD")
-            self._step_adam(features, labels_d, lr_d, losses)
-        elif one_call:
-            self._one_call(features, labels_d, lr_d, losses, first)
-        elif self.dynamic:
-            self._step_scaled(features, labels_d, lr_d, losses)
         else:
-            text = t.forward(self.ctx)
-            _, d_text, d_kl = ops.prompt_head(features, labels_d, text, self.scale, self.grad_scale, self.method, self.teacher, self.w, self.T, losses)
-            d_embed = t.context_rows(t.backward(d_text))
-            if self.method != "prograd":
-                ops.ctx_step(d_embed, t.C, t.n_ctx, t.per_class, self.grad_scale, self.ctx, self.buf, lr_d, first, *sgd, want_grad=False)
-            else:
-                d_embed_kl = t.context_rows(t.backward(d_kl, second=True), second=True)
-                ops.prograd_step(d_embed, d_embed_kl, t.C, t.n_ctx, t.per_class, self.grad_scale, self.lam, self.ctx, self.buf, lr_d, first, *sgd,
-                                 want_report=False)
+            self._no_one_call_adam("CoOpFitState.step", one_call)
+            (self._one_call if one_call else self._separate_calls)(features, labels_d, lr_d, losses, first)
         self.steps += 1
         return losses[0:1] if want_loss else None
 
@@ -864,9 +725,8 @@ def fit_context(features: torch.Tensor, labels, clip_model, tokenized_prompts, c
         raise ValueError(f"{who}: features must be a [N >= 1, E = {E}] tensor")
     N = features.shape[0]
     epochs, batch_size = fitloop.check_run(who, epochs, batch_size)
-    fitloop.check_optimizer(who, optimizer, momentum, dampening, nesterov, weight_decay, betas, eps, shard=shard)
-    _static_prograd(who, method, grad_scale)
-    _scale_args(who, grad_scale, scaler)
+    fitoptim.check_fit(who, optimizer, momentum, dampening, nesterov, weight_decay, betas, eps, grad_scale, scaler, shard=shard,
+                       between=lambda: _static_prograd(who, method, grad_scale))
     _check_method(who, method, teacher, w, T, lam, Cn, E)
     _placement(who, tokenized_prompts, n_ctx, class_token_position, name_lens)
     lab = fitloop._labels(who, labels, N, Cn)

@@ -94,6 +94,11 @@ def adam_bias_table(betas, steps: int) -> np.ndarray:
     return np.array([[1 - b1 ** t, math.sqrt(1 - b2 ** t)] for t in range(1, int(steps) + 1)], dtype=np.float64)
 
 
+def refuse_one_call(who: str, optimizer: str) -> None:
+    """The one-call steps stay SGD: ``check_optimizer(one_call=True)`` and every state's ``step(one_call=True)`` under Adam end here."""
+    raise ValueError(f"{who}: one_call=True with optimizer={optimizer!r}: the one-call steps stay SGD")
+
+
 def check_optimizer(who: str, optimizer, momentum, dampening, nesterov, weight_decay: float, betas=(0.9, 0.999), eps: float = 1e-8,
                     one_call: bool = False, shard=None, sgd_defaults=SGD_DEFAULTS):
     """The optimiser arguments of a prompt fit after their checks, before any device call: ``(optimizer, momentum, dampening, nesterov,
@@ -111,7 +116,7 @@ def check_optimizer(who: str, optimizer, momentum, dampening, nesterov, weight_d
             raise ValueError(f"{who}: {name}={v!r} is an argument of optimizer='sgd'; optimizer={optimizer!r} takes betas and eps")
     betas = check_adam(who, betas, eps, weight_decay)
     if one_call:
-        raise ValueError(f"{who}: one_call=True with optimizer={optimizer!r}: the one-call steps stay SGD")
+        refuse_one_call(who, optimizer)
     if shard is not None:
         raise ValueError(f"{who}: shard with optimizer={optimizer!r}: the class-sharded fit stays SGD")
     return optimizer, 0.0, 0.0, False, betas

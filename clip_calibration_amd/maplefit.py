@@ -51,11 +51,11 @@ from typing import Dict, Optional, Sequence
 import numpy as np
 import torch
 
-from . import _lib, fitloop, fitmonitor, ops
+from . import _lib, fitloop, fitmonitor, fitoptim, ops
 from ._lib import _DT, check, lib
 from . import coopfit, vptfit
 from . import shard as sharding
-from .coopfit import DYNAMIC, Shard, _check_grad_scale, _is_dynamic
+from .coopfit import Shard
 
 # 2^10, one power of two for both towers' backwards, measured at ViT-B/16 with synthetic weights, n_ctx 2, depth 9, batch 4, 100 classes
 # (profiles/maplefit_parity.txt, "grad_scale"): the text tower's dgrad-GEMM operands reach 1413 there (2^5.5 of headroom below fp16's
@@ -253,9 +253,7 @@ def gradients(model, learner_params: Dict[str, torch.Tensor], images: torch.Tens
     ``shard``: the loss and the gradients the batch-sharded step would apply, reduced over the ranks in rank order -- the same bits on
     every rank; every rank passes the whole batch, and the operand statistics (per rank) are refused."""
     who = "maplefit.gradients"
-    if _is_dynamic(who, grad_scale):
-        raise ValueError(f"{who}: grad_scale={DYNAMIC!r} belongs to a fit (MaPLeFitState, fit_prompt_learner); one gradient needs a number")
-    gs = _check_grad_scale(who, grad_scale)
+    gs = fitoptim.static_grad_scale(who, grad_scale, "MaPLeFitState", "fit_prompt_learner")
     if shard is not None:
         sharding.check(who, shard, "block", return_operand_stats=return_operand_stats)
         state = coopfit.shard_states(lambda sh: MaPLeFitState(model, tokenized_prompts, learner_params, logit_scale, 0.0, 0.0, False, 0.0, gs, seq_rows,

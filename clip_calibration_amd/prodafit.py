@@ -68,11 +68,10 @@ from typing import Optional, Sequence
 import numpy as np
 import torch
 
-from . import _lib, fitloop, fitmonitor, ops
+from . import _lib, fitloop, fitmonitor, fitoptim, ops
 from . import shard as sharding
 from ._lib import check, lib
-from .coopfit import (DEFAULT_GRAD_SCALE, DYNAMIC, MAX_LIVE_ROWS, _DT, _AdamBlock, _BlockScaler, _Tower, _check_batch, _check_grad_scale, _is_dynamic,
-                      _live_rows, _scale_args, operand_stats_dict)
+from .coopfit import DEFAULT_GRAD_SCALE, MAX_LIVE_ROWS, _DT, _Tower, _check_batch, _live_rows, operand_stats_dict
 from .fitloop import _host_int_array, _need_gpu, steps_per_epoch
 from .parallel import shard_bounds
 from .shard import Shard, shard_states
@@ -241,9 +240,7 @@ def context_gradient(clip_model, tokenized_prompts, ctx: torch.Tensor, features:
         raise ValueError(f"{who}: sel {sel_h.shape} must be one selection [prompt_bs]")
     _check_collection(who, P, len(sel_h))
     alpha = _check_alpha(who, alpha)
-    if _is_dynamic(who, grad_scale):
-        raise ValueError(f"{who}: grad_scale={DYNAMIC!r} belongs to a fit (ProDAFitState, fit_context); one gradient needs a number")
-    gs = _check_grad_scale(who, grad_scale)
+    gs = fitoptim.static_grad_scale(who, grad_scale, "ProDAFitState", "fit_context")
     scale = fitloop.exp_logit_scale(who, logit_scale)
     E = int(clip_model.geometry.embed_dim)
     labels_d = _check_batch(who, features, labels, Cn, E)
@@ -280,12 +277,13 @@ def _aligned_fp32(features: torch.Tensor) -> torch.Tensor:
     return feats.clone() if feats.data_ptr() % 16 else feats
 
 
-class ProDAFitState(fitmonitor.Monitored):
+class ProDAFitState(fitmonitor.Monitored, fitoptim.Optimised):
     """The training state of ProDA's contexts: the fp32 master ``ctx`` [P, n_ctx, D], SGD's momentum buffer, the tower's stash, the
     selection schedule's generator and the number of steps taken.  ``step`` enqueues one forward, backward and update and does not
     synchronise.  ``validate`` scores cached validation features through the inference mirror (``start_monitor``, ``monitor``,
     ``best_params``, ``val_logits``: ``fitmonitor.Monitored`` on a plain ``fitmonitor.History``; the logits live in a workspace of the
-    state's own, scored inside the one library call)."""
+    state's own, scored inside the one library call).  The loss scale, the optimiser's arguments and moments and ``scaler_state`` are
+    ``fitoptim.Optimised``'s."""
     _who, _history = "ProDAFitState", fitmonitor.History
 
     def __init__(self, clip_model, tokenized_prompts, ctx: torch.Tensor, prompt_bs: int = 4, alpha: float = 0.1, logit_scale: float = 4.6052,
@@ -305,10 +303,7 @@ class ProDAFitState(fitmonitor.Monitored):
         if shard is not None:
             sharding.check(who, shard, n_cls=self.C, n_prompt=self.P)
         self.alpha = _check_alpha(who, alpha)
-        self.dynamic, self.grad_scale, self.scaler = _scale_args(who, grad_scale, scaler)
-        self.optimizer, momentum, dampening, nesterov, betas = fitloop.check_optimizer(who, optimizer, momentum, dampening, nesterov, weight_decay, betas, eps,
-                                                                                       shard=shard)
-        self.scale = fitloop.exp_logit_scale(who, logit_scale)
+        self._init_optimiser(who, logit_scale, momentum, dampening, nesterov, weight_decay, grad_scale, scaler, optimizer, betas, eps, sgd_shard=shard)
         dev = clip_model.device
         if shard is None:
             self.tower = _ProDATower(who, clip_model, ids_all, self.C, self.P, self.Pb, self.n_ctx, nl, last, seq_rows)
@@ -320,24 +315,13 @@ class ProDAFitState(fitmonitor.Monitored):
                                      nc=(self.nc_lo, self.nc_hi))
             self._shard_buffers(dev)
         self.ctx = fitloop.master(ctx, dev)
-        self.buf = torch.zeros_like(self.ctx) if momentum != 0.0 else None
-        self.momentum, self.dampening, self.nesterov, self.weight_decay = momentum, dampening, nesterov, weight_decay
+        self._init_moments(self.ctx)
         self.generator = generator if generator is not None else torch.Generator().manual_seed(0)
         self.pos_host = positions(self.P)
         self._perm = None
-        self.steps = 0
-        self._scaler = _BlockScaler(self.scaler, dev) if self.dynamic else None
-        self._adam = _AdamBlock(self.optimizer, betas, eps, weight_decay, self.ctx) if self.optimizer != "sgd" else None
         self._ids = ids_all[:self.C]
         self._val = None            # what a validation keeps between epochs: the inference operands and the two workspaces
         self.val_class_chunk = None # validate's classes per tower call when its argument is None (None: 4096 // n_prompt, at least 1)
-
-    def scaler_state(self) -> dict:
-        """The dynamic scale's block as ``dict(scale, growth_tracker, skipped_steps, applied_steps, found_inf)`` (``found_inf``: of the
-        last step).  It waits for the steps enqueued so far: one synchronisation, the only read-back of the dynamic path."""
-        if not self.dynamic:
-            raise ValueError(f"ProDAFitState.scaler_state: the state was made with a static grad_scale={self.grad_scale}")
-        return self._scaler.state()
 
     # ---- the class-sharded step (csrc/proda_train.hip, DESIGN.md "Class-sharded ProDA fit")
 
@@ -360,8 +344,7 @@ class ProDAFitState(fitmonitor.Monitored):
     def _shard_phases(self, features, labels_d, sel_d, lr_d, losses, first: bool, report: Optional[dict] = None):
         """One sharded step as phases, a ``yield`` behind every gather.  ``report``: a dict that receives the reduced gradient and the
         compacted text features INSTEAD of a step: neither the contexts nor the momentum buffer nor the scaler block is touched."""
-        t, sh, st = self.tower, self.shard, ops._stream()
-        gs = 1.0 if self.dynamic else self.grad_scale
+        t, sh, st, gs = self.tower, self.shard, ops._stream(), self._head_scale
         t.forward(self.ctx, sel_d)                                                           # the rank's own prompts
         sh.gather(self._send_text, self._all_text, self._send_text.numel() * 4, st)
         yield
@@ -370,8 +353,7 @@ class ProDAFitState(fitmonitor.Monitored):
         own, n_cls, all_cls = self._own_d_text, (self.hi - self.lo) * self.Pb, self.C * self.Pb
         own[:n_cls].copy_(d_text[self.lo * self.Pb:self.hi * self.Pb])                       # the rank's own rows of the replicated d_text
         own[n_cls:].copy_(d_text[all_cls + self.nc_lo:all_cls + self.nc_hi])
-        if self.dynamic:
-            ops.grad_scale_rows(own, self._scaler.block)
+        self._scale_rows(own)
         d_embed = t.backward(own)
         n_own = self.nc_hi - self.nc_lo
         ops.proda_ctx_partial(d_embed, sel_d, t.pos, t.name_lens, n_own, t.n_ctx, self._send_part[:self.Pb + n_own])
@@ -380,16 +362,19 @@ class ProDAFitState(fitmonitor.Monitored):
         if report is not None:
             report["grad"], report["text"] = ops.proda_ctx_step_gathered(self._all_part, sel_d, self.P, t.n_ctx, t.D, gs), text
             return
-        sgd = (float(self.momentum), float(self.dampening), float(self.weight_decay), bool(self.nesterov))
         if self.dynamic:
-            sc = self._scaler
-            if sc.ws is None:
-                need = lib.clipmi_proda_ctx_step_scaled_workspace_bytes(self.P, t.D, t.n_ctx)
-                sc.ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.ctx.device)
-            ops.proda_ctx_reduce_gathered_scaled(self._all_part, sel_d, self.P, t.n_ctx, t.D, sc.block, self.ctx, self.buf, lr_d, *sc.args(), *sgd,
-                                                 want_grad=False, workspace=sc.ws)
+            ops.proda_ctx_reduce_gathered_scaled(self._all_part, sel_d, self.P, t.n_ctx, t.D, self._scaler.block, self.ctx, self.buf, lr_d,
+                                                 *self._scaler.args(), *self._sgd, want_grad=False, workspace=self._scaled_ws())
         else:
-            ops.proda_ctx_step_gathered(self._all_part, sel_d, self.P, t.n_ctx, t.D, gs, self.ctx, self.buf, lr_d, first, *sgd, want_grad=False)
+            ops.proda_ctx_step_gathered(self._all_part, sel_d, self.P, t.n_ctx, t.D, gs, self.ctx, self.buf, lr_d, first, *self._sgd, want_grad=False)
+
+    def _scaled_ws(self) -> torch.Tensor:
+        """The workspace of ProDA's scaled steps (one size for the unsharded and the gathered one), made on the first step."""
+        sc, t = self._scaler, self.tower
+        if sc.ws is None:
+            need = lib.clipmi_proda_ctx_step_scaled_workspace_bytes(self.P, t.D, t.n_ctx)
+            sc.ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.ctx.device)
+        return sc.ws
 
     # ---- per-epoch validation and best-epoch selection on the device (DESIGN.md "Fit monitor", "CoCoOp and ProDA")
 
@@ -493,8 +478,7 @@ class ProDAFitState(fitmonitor.Monitored):
         call with the same batch and, where ``sel`` is None, draws the same selection from its like-seeded generator; under a
         ``LocalGather`` the first state that steps drives all the world's states and draws alone (``one_call`` is refused)."""
         who = "ProDAFitState.step"
-        if one_call and self._adam is not None:
-            raise ValueError(f"{who}: one_call=True with optimizer={self.optimizer!r}: the one-call steps stay SGD")
+        self._no_one_call_adam(who, one_call)
         states = None
         if self.shard is not None:
             # every rank is given the same batch; under a local gather this call steps all the world's states, one phase at a time, and
@@ -516,64 +500,48 @@ class ProDAFitState(fitmonitor.Monitored):
                 raise ValueError(f"{who}: sel {sel_h.shape} must be [prompt_bs] = [{self.Pb}]")
             sel_d = torch.from_numpy(sel_h).to(dev)
         lr_d = ops._dev(fitloop.lr_operand(lr, dev), "lr", (torch.float32,))
-        t, m, first = self.tower, self.tower.model, self.steps == 0
-        sgd = (self.momentum, self.dampening, self.weight_decay, self.nesterov)
+        t, first = self.tower, self.steps == 0
         losses = torch.empty(3, dtype=torch.float32, device=dev)
         if states is not None:
             sharding.step_all(states, self, lambda s: s._shard_phases(features, labels_d, sel_d, lr_d, losses if s is self else torch.empty_like(losses), first))
-        elif self._adam is not None:
-            gs = 1.0 if self.dynamic else self.grad_scale
+        elif one_call:
+            self._one_call(features, labels_d, sel_d, lr_d, losses, first)
+        else:
+            gs = self._head_scale
             text = t.forward(self.ctx, sel_d)
             _, d_text = ops.proda_head(features, labels_d, text, t.n_cls, t.Pb, self.scale, gs, self.alpha, losses)
-            if self.dynamic:
-                ops.grad_scale_rows(d_text, self._scaler.block)
-            grad = ops.proda_ctx_step(t.backward(d_text), sel_d, t.pos, t.name_lens, t.n_ctx, gs)
-            self._adam.step(grad, self.ctx, lr_d, 1.0, self._scaler)
-        elif self.dynamic:
-            self._step_scaled(features, labels_d, sel_d, lr_d, losses, one_call)
-        elif one_call:
-            ws = t.one_call_workspace(features.shape[0])
-            with m._launch_lock:
-                check(lib.clipmi_proda_train_step(m._handle, C.byref(t.dgrad[0]), t.cls_base.data_ptr(), t.nc_base.data_ptr(), _DT[t.base.dtype],
-                                                  self.ctx.data_ptr(), None if self.buf is None else self.buf.data_ptr(), t.n_ctx, sel_d.data_ptr(),
-                                                  t.pos.data_ptr(), t.name_lens.data_ptr(), t.cls_eot.data_ptr(), t.n_cls, t.Pb, t.P, t.rows, features.data_ptr(),
-                                                  features.stride(0), labels_d.data_ptr(), features.shape[0], self.scale, self.grad_scale, self.alpha,
-                                                  lr_d.data_ptr(), int(first), *map(float, sgd[:3]), int(bool(sgd[3])), losses.data_ptr(), None,
-                                                  ws.data_ptr(), ws.numel(), t.stash.data_ptr(), t.stash.numel(), ops._stream()),
-                      "clipmi_proda_train_step")
-        else:
-            text = t.forward(self.ctx, sel_d)
-            _, d_text = ops.proda_head(features, labels_d, text, t.n_cls, t.Pb, self.scale, self.grad_scale, self.alpha, losses)
+            self._scale_rows(d_text)
             d_embed = t.backward(d_text)
-            ops.proda_ctx_step(d_embed, sel_d, t.pos, t.name_lens, t.n_ctx, self.grad_scale, self.ctx, self.buf, lr_d, first, *sgd, want_grad=False)
+            step_args = (d_embed, sel_d, t.pos, t.name_lens, t.n_ctx)
+            # Adam: the step entry forms the contexts' gradient at the head's scale and applies nothing
+            grad = ops.proda_ctx_step(*step_args, gs) if self._adam is not None else (d_embed, sel_d)
+            self._apply_block(grad, lr_d, lambda: ops.proda_ctx_step(*step_args, gs, self.ctx, self.buf, lr_d, first, *self._sgd, want_grad=False))
         self.steps += 1
         return losses[0:1] if want_loss else None
 
-    def _step_scaled(self, features, labels_d, sel_d, lr_d, losses, one_call: bool) -> None:
-        """``step`` under the dynamic scale: the head at grad_scale = 1, its d_text times the block's scale, the backward, and
-        clipmi_proda_ctx_step_scaled, which decides on the device whether the step is applied."""
+    def _apply_scaled(self, grad, lr_d: torch.Tensor) -> None:
+        """SGD under the dynamic scale is ProDA's own kernel, not the block's: clipmi_proda_ctx_step_scaled is handed the tower's input
+        gradient and the selection (``grad`` is the pair), gathers and reduces the selected contexts' rows itself and decides on the
+        device whether the step is applied."""
+        t, sc = self.tower, self._scaler
+        ops.proda_ctx_step_scaled(*grad, t.pos, t.name_lens, t.n_ctx, sc.block, self.ctx, self.buf, lr_d, *sc.args(), *self._sgd, want_grad=False,
+                                  workspace=self._scaled_ws())
+
+    def _one_call(self, features, labels_d, sel_d, lr_d, losses, first: bool) -> None:
+        """``step`` through the library's one-call step: one of two symbols (static or scaled) on one run of arguments."""
         t, m, sc = self.tower, self.tower.model, self._scaler
-        sgd = (float(self.momentum), float(self.dampening), float(self.weight_decay), int(bool(self.nesterov)))
-        if one_call:
-            ws = t.one_call_workspace(features.shape[0], scaled=True)
-            with m._launch_lock:
-                check(lib.clipmi_proda_train_step_scaled(m._handle, C.byref(t.dgrad[0]), t.cls_base.data_ptr(), t.nc_base.data_ptr(), _DT[t.base.dtype],
-                                                         self.ctx.data_ptr(), None if self.buf is None else self.buf.data_ptr(), t.n_ctx,
-                                                         sel_d.data_ptr(), t.pos.data_ptr(), t.name_lens.data_ptr(), t.cls_eot.data_ptr(), t.n_cls, t.Pb,
-                                                         t.P, t.rows, features.data_ptr(), features.stride(0), labels_d.data_ptr(), features.shape[0],
-                                                         self.scale, sc.block.data_ptr(), *sc.args(), self.alpha, lr_d.data_ptr(), *sgd, losses.data_ptr(), None,
-                                                         ws.data_ptr(), ws.numel(), t.stash.data_ptr(), t.stash.numel(), ops._stream()),
-                      "clipmi_proda_train_step_scaled")
-            return
-        text = t.forward(self.ctx, sel_d)
-        _, d_text = ops.proda_head(features, labels_d, text, t.n_cls, t.Pb, self.scale, 1.0, self.alpha, losses)
-        ops.grad_scale_rows(d_text, sc.block)
-        d_embed = t.backward(d_text)
-        if sc.ws is None:
-            need = lib.clipmi_proda_ctx_step_scaled_workspace_bytes(t.P, t.D, t.n_ctx)
-            sc.ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.ctx.device)
-        ops.proda_ctx_step_scaled(d_embed, sel_d, t.pos, t.name_lens, t.n_ctx, sc.block, self.ctx, self.buf, lr_d, *sc.args(), *sgd[:3], bool(sgd[3]),
-                                  want_grad=False, workspace=sc.ws)
+        ws = t.one_call_workspace(features.shape[0], scaled=self.dynamic)
+        name = "clipmi_proda_train_step" + ("_scaled" if self.dynamic else "")
+        front = (m._handle, C.byref(t.dgrad[0]), t.cls_base.data_ptr(), t.nc_base.data_ptr(), _DT[t.base.dtype], self.ctx.data_ptr(),
+                 None if self.buf is None else self.buf.data_ptr(), t.n_ctx, sel_d.data_ptr(), t.pos.data_ptr(), t.name_lens.data_ptr(), t.cls_eot.data_ptr(),
+                 t.n_cls, t.Pb, t.P, t.rows, features.data_ptr(), features.stride(0), labels_d.data_ptr(), features.shape[0], self.scale)
+        if self.dynamic:
+            how = (sc.block.data_ptr(), *sc.args(), self.alpha, lr_d.data_ptr())
+        else:
+            how = (self.grad_scale, self.alpha, lr_d.data_ptr(), int(first))
+        with m._launch_lock:
+            check(getattr(lib, name)(*front, *how, *self._sgd, losses.data_ptr(), None, ws.data_ptr(), ws.numel(), t.stash.data_ptr(), t.stash.numel(),
+                                     ops._stream()), name)
 
 
 def init_context(clip_model, n_ctx: int = 16, n_prompt: int = 32, seed: int = 0) -> torch.Tensor:
@@ -636,10 +604,9 @@ def fit_context(features: torch.Tensor, labels, clip_model, tokenized_prompts, c
         raise ValueError(f"{who}: features must be a [N >= 1, E = {E}] tensor")
     N = features.shape[0]
     epochs, batch_size = fitloop.check_run(who, epochs, batch_size)
-    fitloop.check_optimizer(who, optimizer, momentum, dampening, nesterov, weight_decay, betas, eps, shard=shard)
-    dynamic, _, cfg = _scale_args(who, grad_scale, scaler)
+    dynamic, _, cfg = fitoptim.check_fit(who, optimizer, momentum, dampening, nesterov, weight_decay, betas, eps, grad_scale, scaler, shard=shard)
     if return_scaler_state and not dynamic:
-        raise ValueError(f"{who}: return_scaler_state is an argument of grad_scale={DYNAMIC!r}")
+        raise ValueError(f"{who}: return_scaler_state is an argument of grad_scale={fitoptim.DYNAMIC!r}")
     _check_alpha(who, alpha)
     lab = fitloop._labels(who, labels, N, Cn)
     order = fitloop.check_order(who, order, epochs, N)

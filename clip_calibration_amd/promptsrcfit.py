@@ -54,11 +54,11 @@ from typing import Dict, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import _lib, fitloop, fitmonitor, ops
+from . import _lib, fitloop, fitmonitor, fitoptim, ops
 from ._lib import _DT, check, lib
 from . import coopfit, maplefit, vptfit
 from . import shard as sharding
-from .coopfit import DYNAMIC, Shard, _check_grad_scale, _is_dynamic
+from .coopfit import Shard
 from .fitloop import _need_gpu
 
 # 2^10, one power of two for both towers' backwards, measured at ViT-B/16 with synthetic weights, nt = nv = 4, depths 9 / 9, batch 4, 100
@@ -293,9 +293,7 @@ def gradients(model, params: Dict[str, torch.Tensor], images: torch.Tensor, labe
     ``shard``: the five losses and the gradients the batch-sharded step would apply, reduced over the ranks in rank order -- the same bits
     on every rank; every rank passes the whole batch; the operand statistics and the features (per rank) are refused."""
     who = "promptsrcfit.gradients"
-    if _is_dynamic(who, grad_scale):
-        raise ValueError(f"{who}: grad_scale={DYNAMIC!r} belongs to a fit (PromptSRCFitState, fit_prompts); one gradient needs a number")
-    gs = _check_grad_scale(who, grad_scale)
+    gs = fitoptim.static_grad_scale(who, grad_scale, "PromptSRCFitState", "fit_prompts")
     wt, wi, wl = _method_weights(who, method, w_text, w_image, w_logit)
     if shard is not None:
         sharding.check(who, shard, "block", return_operand_stats=return_operand_stats)

@@ -14,8 +14,8 @@ the masters rounded through fp16, the reference's ``.half()``.  DESIGN.md "VPT f
 ``grad_scale``: as in ``coopfit`` -- the whole backward carries ``grad_scale`` times the gradient (a power of two), the head multiplies
 and the step divides.  profiles/vptfit_parity.txt has the measurement behind the default.  ``grad_scale="dynamic"`` with
 ``scaler=dict(init_scale, growth_factor, backoff_factor, growth_interval)`` is the reference's ``prec == "amp"`` branch (vpt.py:164,
-``torch.cuda.amp.GradScaler``) as ``coopfit`` has it: the scale lives in a block on the device, a step whose gradient holds an inf or a
-NaN changes neither the prompts nor the momentum buffer, and the scale backs off and grows again.  No step reads anything back;
+``torch.cuda.amp.GradScaler``) as ``coopfit`` describes it and ``fitoptim`` holds it for every fit: the scale lives in a block on the
+device, a step whose gradient holds an inf or a NaN changes neither the prompts nor the momentum buffer, and the scale backs off and grows again.  No step reads anything back;
 ``VPTFitState.scaler_state()`` does, once.  DESIGN.md "Dynamic loss scale for the block fits"; the reference's ``autocast`` casts differ
 from this path's fixed fp16 operand points (unverified).
 
@@ -53,10 +53,10 @@ from typing import Optional, Sequence
 
 import torch
 
-from . import _lib, fitloop, fitmonitor, ops
+from . import _lib, fitloop, fitmonitor, fitoptim, ops
 from . import shard as sharding
 from ._lib import _DT, check, lib
-from .coopfit import DYNAMIC, _AdamBlock, _BlockScaler, _pack_dgrad, _check_grad_scale, _is_dynamic, _scale_args, operand_stats_dict
+from .coopfit import _pack_dgrad, operand_stats_dict
 from .fitloop import _need_gpu
 from .shard import Shard, shard_states
 
@@ -268,9 +268,7 @@ def prompt_gradient(model, prompts: torch.Tensor, images: torch.Tensor, labels, 
     forward takes the default ``flags``."""
     who = "prompt_gradient"
     depth, n_ctx = _check_prompts(who, model, prompts)
-    if _is_dynamic(who, grad_scale):
-        raise ValueError(f"{who}: grad_scale={DYNAMIC!r} belongs to a fit (VPTFitState, fit_prompts); one gradient needs a number")
-    gs = _check_grad_scale(who, grad_scale)
+    gs = fitoptim.static_grad_scale(who, grad_scale, "VPTFitState", "fit_prompts")
     if shard is not None:
         sharding.check(who, shard, "block", return_operand_stats=return_operand_stats)
         if flags != _lib.CALL_DEFAULT:
@@ -304,41 +302,31 @@ def image_features(model, prompts: torch.Tensor, images: torch.Tensor) -> torch.
     return tower.forward(images, fitloop.master(prompts, images.device)).clone()
 
 
-class _BlockFitState(fitmonitor.ImageMonitored):
+class _BlockFitState(fitmonitor.ImageMonitored, fitoptim.Optimised):
     """What the states of the fits through the image tower share (VPTFitState, maplefit.MaPLeFitState, promptsrcfit.PromptSRCFitState): one
-    fp32 master block under ``_master_name``, SGD's arguments and momentum buffer, the static or dynamic loss scale and the one ``step``.
-    A state supplies ``_vision`` (the image tower), ``_one_call`` (its one-call symbol and that symbol's own arguments), ``_head`` (forward
+    fp32 master block under ``_master_name``, the one ``step`` and the batch-sharded step; the optimiser's arguments and moments, the static
+    or dynamic loss scale and ``scaler_state`` are ``fitoptim.Optimised``'s.  A state supplies ``_vision`` (the image tower), ``_one_call`` (its one-call symbol and that symbol's own arguments), ``_head`` (forward
     and head at a grad_scale) and ``_apply`` (backward and the block's step)."""
     _master_name = "block"
     _n_losses = 1
 
     def _init_optimiser(self, who: str, logit_scale: float, momentum, dampening, nesterov, weight_decay: float, grad_scale, scaler,
                         optimizer: str = "sgd", betas=(0.9, 0.999), eps: float = 1e-8, shard: Optional[Shard] = None) -> None:
-        """The refusals that need no model, in the order every state has made them.  ``optimizer``: "sgd" (``momentum``, ``dampening``,
-        ``nesterov``), "adam" or "adamw" (``betas``, ``eps``; ``weight_decay`` keeps the fit's own default -- torch's
-        AdamW default of 1e-2 is NOT taken over).  ``shard``: the batch-sharded fit (``shard.check``)."""
+        """``shard``: the batch-sharded fit (``shard.check``), which takes all three optimisers; then ``fitoptim.Optimised``'s refusals."""
         self.shard = shard
         if shard is not None:
             sharding.check(who, shard, "block")
-        self.dynamic, self.grad_scale, self.scaler = _scale_args(who, grad_scale, scaler)
-        self.optimizer, momentum, dampening, nesterov, self._betas = fitloop.check_optimizer(who, optimizer, momentum, dampening, nesterov, weight_decay,
-                                                                                             betas, eps)
-        self._eps = eps
-        self.scale = fitloop.exp_logit_scale(who, logit_scale)
-        self.momentum, self.dampening, self.nesterov, self.weight_decay = momentum, dampening, nesterov, weight_decay
+        super()._init_optimiser(who, logit_scale, momentum, dampening, nesterov, weight_decay, grad_scale, scaler, optimizer, betas, eps)
         # the block's step entry forms the gradient at grad_scale = 1 and applies nothing: under the dynamic scale, under Adam, and
         # under ``shard``, where the block it leaves is what the rank sends
         self._defer = self.dynamic or self.optimizer != "sgd" or shard is not None
 
     def _init_block(self, master: torch.Tensor) -> None:
-        """``master`` becomes the block the steps update; the buffer, the step count and the scaler's device block with it.  Under
-        ``shard`` also the step's send block [scale * gradient | losses], the receive block [G, the same] and the reduced block, made
-        once; the state files itself with a local gather."""
+        """``master`` becomes the block the steps update (``_init_moments`` beside it).  Under ``shard`` also the step's send block
+        [scale * gradient | losses], the receive block [G, the same] and the reduced block, made once; the state files itself with a
+        local gather."""
         setattr(self, self._master_name, master)
-        self.buf = torch.zeros_like(master) if self.momentum != 0.0 else None
-        self.steps = 0
-        self._scaler = _BlockScaler(self.scaler, master.device) if self.dynamic else None
-        self._adam = _AdamBlock(self.optimizer, self._betas, self._eps, self.weight_decay, master) if self.optimizer != "sgd" else None
+        self._init_moments(master)
         if self.shard is not None:
             n = master.numel() + self._n_losses
             stride = (n + 3) // 4 * 4       # whole 16-byte vectors per rank: every row of the receive block starts on the first row's phase
@@ -358,13 +346,6 @@ class _BlockFitState(fitmonitor.ImageMonitored):
     def _master(self) -> torch.Tensor:
         return getattr(self, self._master_name)
 
-    def scaler_state(self) -> dict:
-        """The dynamic scale's block as ``dict(scale, growth_tracker, skipped_steps, applied_steps, found_inf)`` (``found_inf``: of the
-        last step).  It waits for the steps enqueued so far: one synchronisation, the only read-back of the dynamic path."""
-        if not self.dynamic:
-            raise ValueError(f"{self._who}.scaler_state: the state was made with a static grad_scale={self.grad_scale}")
-        return self._scaler.state()
-
     def step(self, images: torch.Tensor, labels, lr, want_loss: bool = False, one_call: bool = False) -> Optional[torch.Tensor]:
         """One optimiser step on the batch ``images`` [B, 3, R, R] (preprocessed, fp16 or fp32, on the GPU) and ``labels`` [B] at the rate
         ``lr``: an fp32 tensor of one element on the device is read where it lies; a Python number is uploaded on every call.  A label
@@ -383,8 +364,7 @@ class _BlockFitState(fitmonitor.ImageMonitored):
         who = f"{self._who}.step"
         if self.shard is not None:
             sharding.check(who, self.shard, "block", one_call=one_call)
-        if one_call and self._adam is not None:
-            raise ValueError(f"{who}: one_call=True with optimizer={self.optimizer!r}: the one-call steps stay SGD")
+        self._no_one_call_adam(who, one_call)
         v = self._vision()
         images = v.images(who, images)
         dev, B = images.device, images.shape[0]
@@ -397,8 +377,7 @@ class _BlockFitState(fitmonitor.ImageMonitored):
             sharding.step_all(sharding.drive(self.shard, self, who), self, lambda s: s._shard_phases(images, labels_d, lr_d))
             self.steps += 1
             return self.last_losses[:1] if want_loss else None
-        first = self.steps == 0
-        sgd = (float(self.momentum), float(self.dampening), float(self.weight_decay), int(bool(self.nesterov)))
+        first, sgd = self.steps == 0, self._sgd
         loss = torch.empty(self._n_losses, dtype=torch.float32, device=dev)
         if one_call:
             v.size(B, tower_ws=False)
@@ -411,16 +390,11 @@ class _BlockFitState(fitmonitor.ImageMonitored):
                 check(getattr(lib, name)(*front, self.scale, *how, *weights, *rate, *sgd, loss.data_ptr(), None, ws.data_ptr(), ws.numel(), *stashes,
                                          ops._stream()), name)
         else:
-            outs = self._head(images, labels_d, 1.0 if self.dynamic else self.grad_scale, loss)
-            if self.dynamic:
-                for d_out in outs:
-                    ops.grad_scale_rows(d_out, self._scaler.block)
-            if self._adam is not None:      # the block of grad_scale * gradient (the scaler's scale * gradient under the dynamic scale)
-                self._adam.step(self._apply(outs, lr_d, first, sgd), self._master(), lr_d, 1.0 if self.dynamic else self.grad_scale, self._scaler)
-            elif self.dynamic:
-                self._scaler.step(self._apply(outs, lr_d, first, sgd), self._master(), self.buf, lr_d, *sgd)
-            else:
-                self._apply(outs, lr_d, first, sgd)
+            outs = self._head(images, labels_d, self._head_scale, loss)
+            self._scale_rows(*outs)
+            grad = self._apply(outs, lr_d, first, sgd)      # static SGD: the block's step entry has applied the step itself
+            if self._defer:     # the block of grad_scale * gradient (the scaler's scale * gradient under the dynamic scale): Adam is told which
+                self._apply_block(grad, lr_d, None, self._head_scale)
         self.steps += 1
         self.last_losses = loss
         return loss[:1] if want_loss else None
@@ -439,12 +413,9 @@ class _BlockFitState(fitmonitor.ImageMonitored):
         sh, master = self.shard, self._master()
         total, n = master.numel(), images.shape[0] // sh.world
         rows = slice(sh.rank * n, (sh.rank + 1) * n)
-        first = self.steps == 0
-        sgd = (float(self.momentum), float(self.dampening), float(self.weight_decay), int(bool(self.nesterov)))
-        outs = self._head(images[rows], labels_d[rows], 1.0 if self.dynamic else self.grad_scale, self._send[total:total + self._n_losses])
-        if self.dynamic:
-            for d_out in outs:
-                ops.grad_scale_rows(d_out, self._scaler.block)
+        first, sgd = self.steps == 0, self._sgd
+        outs = self._head(images[rows], labels_d[rows], self._head_scale, self._send[total:total + self._n_losses])
+        self._scale_rows(*outs)
         self._apply(outs, None, first, sgd)
         sh.gather(self._send, self._recv, self._send.numel() * 4, ops._stream())
         yield
@@ -456,11 +427,7 @@ class _BlockFitState(fitmonitor.ImageMonitored):
             self.last_losses = ops.block_rank_mean(self._recv[:, total:], self._n_losses)
         else:
             ops.block_rank_mean(self._recv, total + self._n_losses, self._reduced)
-            grad = self._reduced[:total]
-            if self._adam is not None:
-                self._adam.step(grad, master, lr_d, 1.0 if self.dynamic else self.grad_scale, self._scaler)
-            else:
-                self._scaler.step(grad, master, self.buf, lr_d, *sgd)
+            self._apply_block(self._reduced[:total], lr_d, None, self._head_scale)      # static SGD took the branch above
             self.last_losses = self._reduced[total:].clone()     # the reduced block is the next step's as well: the history keeps its own
 
     def _shard_gradient(self, who: str, images: torch.Tensor, labels):

@@ -13,7 +13,7 @@ import torch
 import coopfit_ref
 import scalerfit_ref as ref
 
-from clip_calibration_amd import _lib, coopfit, ops  # noqa: E402
+from clip_calibration_amd import _lib, coopfit, fitoptim, ops  # noqa: E402
 from clip_calibration_amd.model import build_model  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -133,8 +133,8 @@ def test_python_argument_checks(cpu_model):
     with pytest.raises(ValueError, match="power of two"):
         coopfit.context_gradient(cpu_model, ids, ctx, f, y, grad_scale="auto")
     assert ops.SCALER_DEFAULTS == {"init_scale": 2.0 ** 16, "growth_factor": 2.0, "backoff_factor": 0.5, "growth_interval": 2000}
-    assert coopfit._check_scaler("t", None) == ops.SCALER_DEFAULTS
-    assert coopfit._check_scaler("t", {"growth_factor": 1.0, "backoff_factor": 1.0})["growth_factor"] == 1.0
+    assert fitoptim._check_scaler("t", None) == ops.SCALER_DEFAULTS
+    assert fitoptim._check_scaler("t", {"growth_factor": 1.0, "backoff_factor": 1.0})["growth_factor"] == 1.0
 
 
 def test_state_block_layout():

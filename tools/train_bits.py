@@ -10,7 +10,14 @@ and compare the files:
     python tools/train_bits.py --compare before.txt after.txt     # exit status 1 if a digest differs
 
 Every case is small (a few rows, C on both sides of a workgroup's stride, odd E); a row with a label outside [0, C) is part of the
-head cases.  Measurement only; bench.py does not run it."""
+head cases.
+
+``--group fits`` adds the fit states (CoOp, KgCoOp and ProGrad with a generic and CoOp with a class-specific context, ProDA, CoCoOp, VPT,
+MaPLe, PromptSRC) on the tests' tiny cases: three steps on every route a state accepts -- static SGD, one call, the dynamic loss scale
+(started above fp16's overflow point, so that the first step is skipped), dynamic in one call, Adam, AdamW, Adam under the dynamic scale,
+and the sharded step over a local gather with one rank and with two.  A digest covers the losses, the master block, the momentum buffer
+or Adam's moments and the scaler's block: two checkouts of the package Python on one library issue the same launches exactly when every
+digest is equal.  Measurement only; bench.py does not run it."""
 import argparse
 import ctypes as C
 import hashlib
@@ -23,6 +30,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(1, os.path.join(ROOT, "tests"))     # the fit states' cases are the tests' (coopfit_ref.make_case and its siblings)
 
 
 def digest(*tensors):
@@ -53,7 +61,7 @@ def prompt_ids(geom, n_cls, n_ctx):
 
 def cases():
     """Yields (name, digest)."""
-    from clip_calibration_amd import coopfit, ops, synthetic as syn
+    from clip_calibration_amd import coopfit, fitoptim, ops, synthetic as syn
     from clip_calibration_amd._lib import check, lib
     from clip_calibration_amd.model import build_model
 
@@ -147,7 +155,7 @@ def cases():
                                   T=2.0, lam=0.8, class_token_position=pos or "end", name_lens=[0, 1, 2] if pos else None, **kw)
         t, h, mode = st.tower, model._handle, ops.PROMPT_MODES[method]
         block = ops.new_scaler_state(scaler["init_scale"], "cuda") if scaler else None
-        cfg = coopfit._check_scaler(name, scaler)
+        cfg = fitoptim._check_scaler(name, scaler)
         sizer = getattr(lib, "clipmi_prompt_train_step" + ("_scaled" if scaler else "") + ("_placed" if pos else "") + "_bytes")
         ws = torch.empty(sizer(h, t.C, t.rows, 4, mode, t.n_ctx, pc), dtype=torch.uint8).cuda()
         losses, grad = torch.zeros(2, 3).cuda(), torch.zeros(2, *st.ctx.shape).cuda()
@@ -178,6 +186,90 @@ def cases():
     yield "tempscale_fit", digest(state, losses)
 
 
+# the dynamic routes start above fp16's overflow point and fall to 2^8 or 2^11 with the first, skipped step (tests/test_gpu_cocoopshard_ranks.py ROUTES
+# has CoCoOp's values, measured on its case; 2^40 overflows whatever the case)
+OVER = {"init_scale": 2.0 ** 40, "backoff_factor": 2.0 ** -32}
+COCOOP_OVER = {"init_scale": 2.0 ** 16, "backoff_factor": 2.0 ** -5}
+
+
+def fit_routes(dynamic=True, one_call=True, shard_adam=False, shard_dynamic=False, over=OVER):
+    """(route name, constructor arguments, one_call, world) of every route a state accepts."""
+    dyn = dict(grad_scale="dynamic", scaler=over)
+    routes = [("static", {}, False, 0), ("adam", dict(optimizer="adam"), False, 0), ("adamw", dict(optimizer="adamw"), False, 0)]
+    if one_call:
+        routes.append(("one_call", {}, True, 0))
+    if dynamic:
+        routes += [("dynamic", dyn, False, 0), ("adam+dynamic", dict(dyn, optimizer="adam"), False, 0)]
+        if one_call:
+            routes.append(("dynamic+one_call", dyn, True, 0))
+    for world in (1, 2):
+        routes.append((f"shard{world}", {}, False, world))
+        if shard_dynamic:
+            routes.append((f"shard{world} dynamic", dyn, False, world))
+        if shard_adam:
+            routes.append((f"shard{world} adam", dict(optimizer="adam"), False, world))
+    return routes
+
+
+def fit_cases():
+    """Yields (name, digest): three steps of every fit state on every route."""
+    import cocoopfit_ref
+    import coopfit_ref
+    import maplefit_ref
+    import prodafit_ref
+    import promptsrcfit_ref
+    import vptfit_ref
+    from clip_calibration_amd import cocoopfit, coopfit, maplefit, prodafit, promptsrcfit, vptfit
+    from clip_calibration_amd.model import build_model
+
+    Cn, B, gs = 5, 4, 256.0     # the tests' grad_scale: the synthetic weights give gradients far larger than ViT-B/16's
+    fits = []                   # (name, make(**kw), batch, step arguments, routes)
+    text_model = {g: build_model(dict(coopfit_ref.state_dict(g)), {"trainer": "CoOp"}).cuda() for g in ("tiny", "tiny3")}
+    for name in ("coop", "coop_csc", "kgcoop", "prograd"):
+        c, m = coopfit_ref.make_case("tiny", Cn, 4, B, csc=name == "coop_csc"), text_model["tiny"]
+        extra = {}
+        if name in ("kgcoop", "prograd"):
+            extra = dict(method=name, teacher=(torch.randn(Cn, m.geometry.embed_dim, generator=torch.Generator().manual_seed(3)) * 2.0).cuda())
+        make = lambda c=c, m=m, extra=extra, **kw: coopfit.CoOpFitState(m, c["ids"], c["ctx"], coopfit_ref.LOGIT_SCALE, **dict(dict(grad_scale=gs), **kw), **extra)
+        fits.append((name, make, (c["feats"].cuda(), c["labels"].cuda()), {}, fit_routes(dynamic=name != "prograd")))
+    c, m = prodafit_ref.make_case("tiny", Cn, 4, 8, 4, B), text_model["tiny"]
+    make = lambda c=c, m=m, **kw: prodafit.ProDAFitState(m, c["ids"], c["ctx"], prompt_bs=4, logit_scale=prodafit_ref.LOGIT_SCALE, **dict(dict(grad_scale=gs), **kw))
+    fits.append(("proda", make, (c["feats"].cuda(), c["labels"].cuda()), {"sel": np.array([0, 3, 5, 6])}, fit_routes(shard_dynamic=True)))
+    c, m = cocoopfit_ref.make_case("tiny3", 3, 4, 3), text_model["tiny3"]
+    make = lambda c=c, m=m, **kw: cocoopfit.CoCoOpFitState(m, c["ids"], c["params"], logit_scale=cocoopfit_ref.LOGIT_SCALE, **dict(dict(grad_scale=gs), **kw))
+    fits.append(("cocoop", make, (c["feats"].cuda(), c["labels"].cuda()), {}, fit_routes(shard_adam=True, shard_dynamic=True, over=COCOOP_OVER)))
+    c = vptfit_ref.make_case("tiny", 2, 2, B, Cn)
+    m = build_model(dict(c["sd"]), {"trainer": "VPT", "vision_depth": 2, "vision_ctx": 2, "language_depth": 0, "language_ctx": 0}).cuda()
+    make = lambda c=c, m=m, text=c["text"].cuda(), **kw: vptfit.VPTFitState(m, text, vptfit_ref.LOGIT_SCALE, c["prompts"], **dict(dict(grad_scale=gs), **kw))
+    fits.append(("vpt", make, (c["images"].cuda(), c["labels"].cuda()), {}, fit_routes(shard_adam=True, shard_dynamic=True)))
+    c = maplefit_ref.make_case("tiny3", 2, 1, Cn, B)
+    m = build_model(dict(c["sd"]), maplefit_ref.design(1)).cuda()
+    make = lambda c=c, m=m, **kw: maplefit.MaPLeFitState(m, c["ids"], c["pl"], maplefit_ref.LOGIT_SCALE, seq_rows=maplefit_ref.live_rows(c["ids"], False),
+                                                         **dict(dict(grad_scale=gs), **kw))
+    fits.append(("maple", make, (c["images"].cuda(), c["labels"].cuda()), {}, fit_routes(shard_adam=True, shard_dynamic=True)))
+    c = promptsrcfit_ref.make_case("tiny", 2, 2, 3, 2, Cn, B)
+    m = build_model(dict(c["sd"]), promptsrcfit_ref.design(3, 2, 2, 2)).cuda()
+    make = lambda c=c, m=m, teacher=c["teacher"].cuda(), **kw: promptsrcfit.PromptSRCFitState(
+        m, c["ids"], c["p"], teacher, promptsrcfit_ref.LOGIT_SCALE, seq_rows=promptsrcfit_ref.live_rows(c["ids"], True), **dict(dict(grad_scale=gs), **kw))
+    fits.append(("promptsrc", make, (c["images"].cuda(), c["labels"].cuda()), {}, fit_routes(shard_adam=True, shard_dynamic=True)))
+
+    lr = torch.tensor([2e-3, 1e-3, 5e-4], dtype=torch.float32).cuda()
+    for name, make, batch, step_kw, routes in fits:
+        for route, kw, one_call, world in routes:
+            if world:
+                local = coopfit.LocalGather(world)
+                st = [make(shard=coopfit.Shard(world, r, local), **kw) for r in range(world)][0]      # a step of one steps them all
+            else:
+                st = make(**kw)
+            call = dict(step_kw, want_loss=True, **({"one_call": True} if one_call else {}))
+            losses = torch.cat([st.step(*batch, lr[k:k + 1], **call) for k in range(3)])
+            torch.cuda.synchronize()
+            if st.dynamic:
+                assert st.scaler_state()["skipped_steps"] >= 1 and st.scaler_state()["applied_steps"] >= 1, (name, route, st.scaler_state())
+            moments = (st.buf,) if st._adam is None else (st._adam.exp_avg, st._adam.exp_avg_sq)
+            yield f"fit {name} {route}", digest(losses, st._master(), *moments, *((st._scaler.block,) if st.dynamic else ()))
+
+
 def read(path):
     return dict(line.rstrip("\n").rsplit("  ", 1) for line in open(path) if line.strip())
 
@@ -185,6 +277,7 @@ def read(path):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
+    ap.add_argument("--group", choices=("kernels", "fits", "all"), default="kernels", help="the kernel families (the default), the fit states, or both")
     ap.add_argument("--compare", nargs=2, metavar=("BEFORE", "AFTER"))
     a = ap.parse_args()
     if a.compare:
@@ -195,7 +288,8 @@ def main():
             print(f"{'equal ' if n in equal else 'DIFFER'}  {n}  {before.get(n, '-')}  {after.get(n, '-')}")
         print(f"{len(equal)} of {len(names)} digests equal")
         sys.exit(0 if len(equal) == len(names) else 1)
-    lines = [f"{name}  {value}" for name, value in cases()]
+    groups = [g for g, on in ((cases, a.group != "fits"), (fit_cases, a.group != "kernels")) if on]
+    lines = [f"{name}  {value}" for group in groups for name, value in group()]
     text = "\n".join(lines) + "\n"
     sys.stdout.write(text)
     if a.out:
